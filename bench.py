@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's config, on N MI355X of one node.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -17,8 +17,13 @@ The JSON line also carries
                 taken inside rtw_ctx_render) against the 157.3 TFLOP/s f32 vector peak.  The path is
                 VALU-bound by construction (12 B of HBM per pixel per frame); `hbm` gives the achieved
                 framebuffer GB/s for completeness.
-  cpu_baseline  the CPU oracle (a port: the reference's Rust cannot be built offline) timed on this
+  cpu_baseline  (--full only) the CPU oracle (a port: the reference's Rust cannot be built offline) timed on this
                 host's cores on a bounded sample of the SAME frame (every 17th 8-row block, fewer spp).
+
+A plain run sets up, warms up, times the --steps frames and prints the line; --full adds the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed: DIR/frame.npy (the [H][W][3] f32 frame on rank 0,
+the array a caller of the render path receives) and DIR/counters.npy (f64 [camera_rays, segments] of that frame,
+all ranks).  The scene, camera and seeds are fixed, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -77,7 +82,10 @@ def main():
     ap.add_argument("--accel", choices=["bvh", "brute"], default="bvh")
     ap.add_argument("--config", choices=["c3", "c2", "c4", "c5"], default="c3",
                     help="c3 = BASELINE.json's metric config (default); the others exist to profile their kernels and are NOT the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the last step's frame and counters as DIR/<name>.npy")
     ap.add_argument("--global-nodes", action="store_true", help="A/B: BVH nodes in global memory (f32) instead of LDS (f16)")
     ap.add_argument("--spp", type=int, default=0, help="override samples per pixel (INVALID as a benchmark; for smoke runs)")
     ap.add_argument("--chunk-sums", action="store_true", help="RTW_FLAG_CHUNK_SUMS: bank one partial sum per 4 samples (A/B; not the default association)")
@@ -86,6 +94,8 @@ def main():
     ap.add_argument("--devices", default="", help="single-process rtw_mgpu over these HIP ordinals, e.g. 0,0,0 = three contexts on one GPU "
                                                   "(a rehearsal of the N-GPU path on a 1-GPU box: INVALID as a benchmark)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # dmabuf IPC only on this pool: must be in the environment BEFORE anything initialises HIP / HSA (torch.cuda, librtw_hip)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -178,6 +188,7 @@ def main():
     frame = None
     for _ in range(args.steps):
         frame, st = step()
+        last = (st.camera_rays, st.segments)
         seg += st.segments; rays += st.camera_rays; nodes += st.node_tests; tests += st.sphere_tests
         kernel_ms += st.kernel_ms
         for k in range(5):
@@ -187,6 +198,8 @@ def main():
     elapsed = par.max_over_ranks(elapsed, world, dev)
     seg, rays, nodes, tests = par.reduce_counters([seg, rays, nodes, tests], world, dev)
     kernel_ms_max = par.max_over_ranks(kernel_ms, world, dev)
+    if args.dump_outputs:
+        last = par.reduce_counters(list(last), world, dev)        # collective: every rank takes part
 
     if single_process_multi:
         world = args.gpus                                           # per-GPU figures below divide by the GPUs that shared the frame
@@ -256,9 +269,14 @@ def main():
                                          "bank, 12 B per camera ray written by the render kernel and read back by the in-order resolve; "
                                          "the path is not HBM-bound"}},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(R, scene, cam, p)
         assert frame is not None and bool(torch.isfinite(frame).all())
+        if args.dump_outputs:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "frame.npy"), frame.cpu().numpy().astype(np.float32))
+            np.save(os.path.join(args.dump_outputs, "counters.npy"), np.array(last, dtype=np.float64))
         print(json.dumps(out), flush=True)
     r.close()
     if world > 1 and not single_process_multi:

@@ -19,6 +19,9 @@ committed so that the GPU box and later rounds never need the reference tree.
                       statistically (block means), not bit for bit.  Plus, verbatim, Rust/test.png (256x256), the
                       image the reference's writer test saves (write_img.rs:33-58): an exact golden for the 8-bit
                       quantiser.
+  ref_statistical.npz the reference's own C++ objects (oracle/_ref, serial, srand(seed)) rendering the three 96x54 views
+                      of the statistical tier (test_oracle_golden.statistical_view), reduced to 6x6-block means
+                      (<view>_blocks, 9x16x3 f64) + the segment count (<view>_segments).
 """
 import ctypes as C
 import hashlib
@@ -103,9 +106,25 @@ def ref_images():
     np.savez_compressed(os.path.join(HERE, "ref_images.npz"), **out)
 
 
+def ref_statistical():
+    from tests import oracle_binding as O
+    from tests.test_oracle_golden import statistical_view
+    assert O.have_ref(), "build oracle/_ref first (make -C oracle)"
+    out = {}
+    for name in ("c1", "metal_cpp", "metal_glass_cpp"):
+        scene, cam, p, seed = statistical_view(name)
+        b, seg, _ = O.ref_render(cam, scene, p, rand_seed=seed)
+        out[name + "_blocks"] = O.block_means(b)
+        out[name + "_segments"] = np.array(seg, np.uint64)
+        print("statistical", name, "seed", seed, seg, "segments")
+    np.savez_compressed(os.path.join(HERE, "ref_statistical.npz"), **out)
+
+
 def main():
     if sys.argv[1:] == ["images"]:
         return ref_images()
+    if sys.argv[1:] == ["statistical"]:
+        return ref_statistical()
     ref_images()
     from tests import oracle_binding as O
     import rtw_amd as R
@@ -181,6 +200,9 @@ def main():
     json.dump({"source": "oracle/_ref: Camera (C++/headers/viewport.h:24-46); unit direction, so focal_length == 1",
                "cameras": cams}, open(os.path.join(HERE, "ref_camera.json"), "w"), indent=0)
     print("cameras:", len(cams))
+
+    # 5. statistical tier
+    ref_statistical()
 
 
 if __name__ == "__main__":

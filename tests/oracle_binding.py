@@ -13,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_SO = os.environ.get("RTW_ORACLE_LIB", os.path.join(ORACLE_DIR, "librtw_oracle.so"))   # override: the sanitizer build
 REF_SO = os.path.join(ORACLE_DIR, "_ref", "librtw_ref.so")
+REF_STATS = os.path.join(ROOT, "tests", "golden", "ref_statistical.npz")
 
 
 class Bounce(C.Structure):
@@ -118,3 +119,20 @@ def ref_render(cam, scene, params, rand_seed=1):
                               out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(seg), C.byref(sec))
     assert rc == 0
     return out, seg.value, sec.value
+
+
+def block_means(x):
+    """6x6 block means of a 54 x 96 frame: [9][16][3] f64 (the statistical tier's unit of comparison)."""
+    return np.asarray(x, np.float64)[:54, :96].reshape(9, 6, 16, 6, 3).mean(axis=(1, 3))
+
+
+def ref_render_blocks(name, cam, scene, params, rand_seed):
+    """(block_means, segments) of the reference's own C++ objects rendering a view of the statistical tier, as stored in
+    tests/golden/ref_statistical.npz (tests/golden/make_fixtures.py); where oracle/_ref is built, the view is rendered
+    again and must reproduce the stored values exactly (serial, srand(rand_seed))."""
+    z = np.load(REF_STATS)
+    blocks, seg = z[name + "_blocks"], int(z[name + "_segments"])
+    if have_ref():
+        b, s, _ = ref_render(cam, scene, params, rand_seed)
+        assert s == seg and np.array_equal(block_means(b), blocks), name
+    return blocks, seg

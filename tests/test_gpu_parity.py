@@ -448,6 +448,32 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(gpu):
     assert abs(d["roofline"]["units_per_launch"]["segments"] * 2 / (1920 * 1080 * 8) - d["config"]["segments_per_camera_ray"]) < 1e-3
 
 
+def test_bench_dump_outputs_and_full(gpu, tmp_path):
+    """bench.py --dump-outputs DIR writes the last timed frame and its counters, and they are what the library renders for the
+    bench view; a plain run leaves the CPU baseline out, --full adds it."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--warmup", "0", "--spp", "8"]
+
+    def run(*extra):
+        out = subprocess.run(base + list(extra), capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+
+    d = run("--steps", "2", "--dump-outputs", str(tmp_path / "out"))
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and "cpu_baseline" not in d
+    frame, counters = np.load(tmp_path / "out" / "frame.npy"), np.load(tmp_path / "out" / "counters.npy")
+    assert frame.dtype == np.float32 and frame.shape == (1080, 1920, 3) and counters.dtype == np.float64
+    scene = R.Scene.generate(R.SCENE_C2, 42)
+    cam, p = R.default_view(R.SCENE_C5)
+    cam.shutter, p.accel, p.samples = 0.0, R.ACCEL_BVH, 8
+    gpu.set_scene(scene, cam.time0, cam.time0 + cam.shutter)
+    img, st = gpu.render(cam, p)
+    assert np.array_equal(frame, img) and counters.tolist() == [st.camera_rays, st.segments]
+    d = run("--steps", "1", "--full")
+    assert d["steps"] == 1 and d["cpu_baseline"]["value"] > 0
+
+
 # ---- quads, instances, constant-density medium (SURVEY.md 8 f4) -------------------------------------------
 def _blocks16(img):
     q = np.round(np.clip(np.nan_to_num(img.astype(np.float64)) * 255.0, 0, 255))

@@ -131,15 +131,9 @@ def test_cerr_trace_pixels_on_the_gpu(gpu):
 
 def test_cpp_dialect_bit_exact_and_statistical(gpu):
     """RTW_FLAG_CPP_DIELECTRIC | RTW_FLAG_CPP_DIFFUSE on the HIP path == the oracle bit for bit (both closest-hit
-    strategies), and -- where oracle/_ref exists -- statistically == the reference's own C++ objects."""
-    glass = R.Sphere.with_albedo((-1.0, 0.0, -1.0), 0.5, (1, 1, 1), R.GLASS_M)
-    scene = R.Scene.generate(R.SCENE_METAL_TEST)
-    spheres = [scene._spheres[i] for i in range(scene.n_spheres)] + [glass.pod]
-    scene = R.Scene(spheres)
-    cam, h = O.viewport_new(96, np.float32(96) / np.float32(54))
-    cam.lens_radius = 0.01
-    p = flag_params(depth=10, flags=R.FLAG_CPP)
-    p.width, p.height, p.samples, p.integrator, p.sampler, p.gamma = 96, 54, 192, R.INTEGRATOR_GRADIENT, R.SAMPLER_ROW, 1.0
+    strategies), and statistically == the reference's own C++ objects (their render stored in tests/golden)."""
+    from tests.test_oracle_golden import statistical_view
+    scene, cam, p, seed = statistical_view("metal_glass_cpp")
     ref, st_ref = O.render(cam, scene, p, threads=16)
     gpu.set_scene(scene)
     imgs = {}
@@ -152,14 +146,10 @@ def test_cpp_dialect_bit_exact_and_statistical(gpu):
     p.flags = 0
     plain, _ = gpu.render(cam, p)
     assert not np.array_equal(plain, ref)
-    if O.have_ref():
-        p.flags = R.FLAG_CPP
-        b, seg, _ = O.ref_render(cam, scene, p, rand_seed=5)
-
-        def blocks(x):
-            return x[:54, :96].reshape(9, 6, 16, 6, 3).mean(axis=(1, 3))
-        da = blocks(imgs[R.ACCEL_BVH].astype(np.float64)) - blocks(b)
-        assert abs(da.mean()) < 2e-3 and np.abs(da).max() < 0.05, (da.mean(), np.abs(da).max())
+    p.flags = R.FLAG_CPP
+    b, seg = O.ref_render_blocks("metal_glass_cpp", cam, scene, p, seed)
+    da = O.block_means(imgs[R.ACCEL_BVH]) - b
+    assert abs(da.mean()) < 2e-3 and np.abs(da).max() < 0.05, (da.mean(), np.abs(da).max())
 
 
 def test_rust2_integrator_honours_cpp_dielectric(gpu):

@@ -63,11 +63,11 @@ def test_single_context_timeline_fields(gpu):
     assert st.enqueue_ms > 0.0 and st.start_ms >= 0.0 and st.total_ms >= st.enqueue_ms
 
 
-def test_example_prints_the_per_device_timeline(gpu):
+def test_example_prints_the_per_device_timeline(gpu, tmp_path):
     """examples/render_scene --devices 0,0,0: the C ABI from compiled code, frame in a std::vector (pageable)."""
     exe = os.path.join(ROOT, "examples", "render_scene")
     assert os.path.exists(exe), "make -C raytracing-in-a-weekend_amd/csrc example"
-    out = subprocess.run([exe, "--devices", "0,0,0", "--spp", "8"], capture_output=True, text=True, timeout=300)
+    out = subprocess.run([exe, "--devices", "0,0,0", "--spp", "8", "--out", str(tmp_path / "out.png")], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr
     lines = [l for l in out.stdout.splitlines() if l.startswith("device ")]
     assert len(lines) == 3 and all("enqueue" in l and "start" in l for l in lines), out.stdout

@@ -87,15 +87,24 @@ def test_s_test_images(name, mat, flags):
     assert mism == 0, f"{mism} of {h * w} pixels differ from the reference's {name} image"
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (only exists where /root/reference does)")
 def test_ref_s_test_md5():
-    """The restated pixel loop of oracle/ref_driver.cpp reproduces the md5 the real viewport.cpp produced."""
+    """The stored s_test images (the goldens of test_s_test_images), written out as the reference's P3 text (ppm_writer.cpp:
+    "R G B" + two spaces per pixel, a newline per row), have the md5 the real viewport.cpp produced; where oracle/_ref is built,
+    the restated pixel loop of oracle/ref_driver.cpp reproduces that md5 as well."""
     z = np.load(os.path.join(GOLD, "s_test.npz"))
+    want = {"control": "c3cad547adfa8b69cb9c02308e1ccc3c", "glass": "b5ce407b2062997eb6df78452e7249dc"}
+    for name, md5 in want.items():
+        h, w = [int(x) for x in z[name + "_shape"]]
+        yellow = np.unpackbits(z[name + "_bits"])[: h * w].reshape(h, w).astype(bool)
+        text = f"P3\n{w} {h}\n255\n" + "".join("".join("255 255 0  " if y else "0 0 255  " for y in row) + "\n" for row in yellow)
+        assert hashlib.md5(text.encode()).hexdigest() == md5 == bytes(z[name + "_md5"]).decode(), name
+    if not O.have_ref():
+        return
     L = O.ref()
     pa, pb, la, lb = C.POINTER(C.c_char)(), C.POINTER(C.c_char)(), C.c_size_t(), C.c_size_t()
     L.rtw_ref_s_test(C.byref(pa), C.byref(la), C.byref(pb), C.byref(lb))
-    assert hashlib.md5(C.string_at(pa, la.value)).hexdigest() == "c3cad547adfa8b69cb9c02308e1ccc3c" == bytes(z["control_md5"]).decode()
-    assert hashlib.md5(C.string_at(pb, lb.value)).hexdigest() == "b5ce407b2062997eb6df78452e7249dc" == bytes(z["glass_md5"]).decode()
+    assert hashlib.md5(C.string_at(pa, la.value)).hexdigest() == want["control"]
+    assert hashlib.md5(C.string_at(pb, lb.value)).hexdigest() == want["glass"]
     L.rtw_ref_free(pa)
     L.rtw_ref_free(pb)
 
@@ -315,18 +324,33 @@ def test_bg_color_emission_and_nan_poison():
 
 
 # ---- 8. statistical tier vs the reference's own objects (lambert + mirror: identical distributions) ---
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (only exists where /root/reference does)")
+def statistical_view(name):
+    """The 96 x 54 views of the statistical tier -> (scene, cam, params, rand seed).  The reference's own C++ objects rendered
+    each one (oracle/_ref, srand(seed)); their block means and segment counts are stored in golden/ref_statistical.npz
+    (make_fixtures.py), read through O.ref_render_blocks."""
+    cam, _ = O.viewport_new(96, np.float32(96) / np.float32(54))
+    if name == "c1":
+        scene, flags, samples, seed = R.Scene.generate(R.SCENE_C1), 0, 128, 7
+    elif name == "metal_cpp":
+        scene, flags, samples, seed = R.Scene.generate(R.SCENE_METAL_TEST), R.FLAG_CPP, 192, 11
+    else:
+        assert name == "metal_glass_cpp", name
+        base = R.Scene.generate(R.SCENE_METAL_TEST)
+        glass = R.Sphere.with_albedo((-1.0, 0.0, -1.0), 0.5, (1, 1, 1), R.GLASS_M)
+        scene = R.Scene([base._spheres[i] for i in range(base.n_spheres)] + [glass.pod])
+        cam.lens_radius = 0.01
+        flags, samples, seed = R.FLAG_CPP, 192, 5
+    p = flag_params(depth=10, flags=flags)
+    p.width, p.height, p.samples, p.integrator, p.sampler, p.gamma = 96, 54, samples, R.INTEGRATOR_GRADIENT, R.SAMPLER_ROW, 1.0
+    return scene, cam, p, seed
+
+
 def test_oracle_vs_reference_objects_statistical():
-    scene = R.Scene.generate(R.SCENE_C1)
-    cam, h = O.viewport_new(96, np.float32(96) / np.float32(54))
-    p = flag_params(depth=10)
-    p.width, p.height, p.samples, p.integrator, p.sampler, p.gamma = 96, 54, 128, R.INTEGRATOR_GRADIENT, R.SAMPLER_ROW, 1.0
+    scene, cam, p, seed = statistical_view("c1")
     a, sa = O.render(cam, scene, p)
-    b, seg, _ = O.ref_render(cam, scene, p, rand_seed=7)
+    b, seg = O.ref_render_blocks("c1", cam, scene, p, seed)
     # 6x6 block means; per-block noise estimated from the within-block spread of both images
-    def blocks(x):
-        return x[:54, :96].reshape(9, 6, 16, 6, 3).mean(axis=(1, 3))
-    da = blocks(a.astype(np.float64)) - blocks(b)
+    da = O.block_means(a) - b
     assert abs(da.mean()) < 2e-3, da.mean()
     assert np.abs(da).max() < 0.06, np.abs(da).max()
     # mean path length agrees (the C++ loop counts one query per ray_colorD call that reaches the loop)
@@ -383,21 +407,14 @@ def test_rust2_ray_color_semantics():
 
 
 # ---- 10. the C++ twin's dialect: RTW_FLAG_CPP_DIELECTRIC | RTW_FLAG_CPP_DIFFUSE ------------------
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (only exists where /root/reference does)")
 def test_oracle_cpp_dialect_vs_reference_objects_statistical():
     """metal_test's four spheres (C++/src/tests.cpp:195-212: lambert, mirror, FUZZY3 = 0.7) rendered by the reference's own
     C++ objects and by the oracle with the C++ dialect flags: the fuzzy sphere is where the dialects differ (C++ normalises the
     diffuse and the mirror direction before the lerp, C++/src/materials.cpp:4-13; Rust does not, materials.rs:141-149)."""
-    scene = R.Scene.generate(R.SCENE_METAL_TEST)
-    cam, h = O.viewport_new(96, np.float32(96) / np.float32(54))
-    p = flag_params(depth=10, flags=R.FLAG_CPP)
-    p.width, p.height, p.samples, p.integrator, p.sampler, p.gamma = 96, 54, 192, R.INTEGRATOR_GRADIENT, R.SAMPLER_ROW, 1.0
+    scene, cam, p, seed = statistical_view("metal_cpp")
     a, sa = O.render(cam, scene, p)
-    b, seg, _ = O.ref_render(cam, scene, p, rand_seed=11)
-
-    def blocks(x):
-        return x[:54, :96].reshape(9, 6, 16, 6, 3).mean(axis=(1, 3))
-    da = blocks(a.astype(np.float64)) - blocks(b)
+    b, seg = O.ref_render_blocks("metal_cpp", cam, scene, p, seed)
+    da = O.block_means(a) - b
     assert abs(da.mean()) < 2e-3, da.mean()
     assert np.abs(da).max() < 0.05, np.abs(da).max()
     assert abs(sa.segments / sa.camera_rays - seg / sa.camera_rays) < 0.02
