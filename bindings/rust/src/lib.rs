@@ -41,6 +41,13 @@ pub struct RtwStats { pub camera_rays: u64, pub segments: u64, pub sphere_tests:
     pub phase_steps: [u64; 6], pub phase_lanes: [u64; 6], pub quad_tests: u64,
     pub enqueue_ms: f32, pub start_ms: f32 }      // ABI v4: the call's timeline (rtw.h)
 
+/// `PerlinNoise` (texture.rs:61-68) without the never-read ranfloat; RtwPerlin::new(seed) == rtw_perlin_new (identity permutations).
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct RtwPerlin { pub ranvec: [[f32; 3]; 256], pub perm_x: [u8; 256], pub perm_y: [u8; 256], pub perm_z: [u8; 256] }
+/// Per texture: `ImageTexture.noise` (index into the tables, -1 = None) and `noise_scale` (texture.rs:21-27).
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct RtwTextureNoise { pub perlin: i32, pub scale: f32 }
+
 #[repr(C)] pub struct RtwCtx { _private: [u8; 0] }
 #[repr(C)] pub struct RtwMgpu { _private: [u8; 0] }
 
@@ -62,6 +69,13 @@ extern "C" {
     fn rtw_mgpu_create(devices: *const i32, n: u32, out: *mut *mut RtwMgpu) -> i32;
     fn rtw_mgpu_destroy(m: *mut RtwMgpu);
     fn rtw_mgpu_set_scene(m: *mut RtwMgpu, scene: *const RtwScene, t_begin: f32, t_end: f32) -> i32;
+    fn rtw_perlin_new(seed: u64, out: *mut RtwPerlin) -> i32;
+    fn rtw_perlin_eval(t: *const RtwPerlin, points: *const f32, n: u32, turb_depth: u32, out: *mut f32) -> i32;
+    fn rtw_ctx_perlin_eval(ctx: *mut RtwCtx, t: *const RtwPerlin, points: *const f32, n: u32, turb_depth: u32, out: *mut f32) -> i32;
+    fn rtw_ctx_set_texture_noise(ctx: *mut RtwCtx, tables: *const RtwPerlin, n_tables: u32,
+                                 per_texture: *const RtwTextureNoise, n_textures: u32) -> i32;
+    fn rtw_mgpu_set_texture_noise(m: *mut RtwMgpu, tables: *const RtwPerlin, n_tables: u32,
+                                  per_texture: *const RtwTextureNoise, n_textures: u32) -> i32;
     fn rtw_mgpu_render(m: *mut RtwMgpu, cam: *const RtwCamera, p: *const RtwParams, out_rgb: *mut c_void,
                        per_device: *mut RtwStats, total: *mut RtwStats) -> i32;
 }
@@ -105,6 +119,18 @@ impl Renderer {
             n_quads: quads.len() as u32, n_instances: instances.len() as u32,
             n_inst_spheres: inst_spheres.len() as u32, n_inst_quads: inst_quads.len() as u32 };
         check(unsafe { rtw_ctx_set_scene(self.ctx, &sc, t_begin, t_end) })
+    }
+    /// ImageTexture{noise, noise_scale} of the scene just set (per_texture[i] for its texture i; an empty slice clears it).
+    /// set_scene clears it; RTW_INTEGRATOR_RUST2 is refused while a used texture has noise.
+    pub fn set_texture_noise(&mut self, tables: &[RtwPerlin], per_texture: &[RtwTextureNoise]) -> Result<(), RtwError> {
+        let (t, pt) = if per_texture.is_empty() { (std::ptr::null(), std::ptr::null()) } else { (tables.as_ptr(), per_texture.as_ptr()) };
+        check(unsafe { rtw_ctx_set_texture_noise(self.ctx, t, tables.len() as u32, pt, per_texture.len() as u32) })
+    }
+    /// PerlinNoise::noise (turb_depth 0) / turb(p, turb_depth) at `points` on this context's GPU.
+    pub fn perlin_eval(&mut self, t: &RtwPerlin, points: &[[f32; 3]], turb_depth: u32) -> Result<Vec<f32>, RtwError> {
+        let mut out = vec![0f32; points.len()];
+        check(unsafe { rtw_ctx_perlin_eval(self.ctx, t, points.as_ptr() as *const f32, points.len() as u32, turb_depth, out.as_mut_ptr()) })?;
+        Ok(out)
     }
     /// Tuning knobs (`RTW_OPT_*` of rtw.h: 1 chunk length, 2 sample bank GiB, 3 LDS geometry, 4 workgroups per CU, 5 list-walk
     /// threshold); none of them changes the image.
@@ -173,3 +199,23 @@ impl Drop for MultiRenderer { fn drop(&mut self) { unsafe { rtw_mgpu_destroy(sel
 //         Ok(r.render(&cam, &p)?.0.into_iter().map(|row| row.into_iter().map(Rgb).collect()).collect())
 //     }
 // }
+
+impl RtwPerlin {
+    /// PerlinNoise::new (texture.rs:110-149) with the tables drawn from PCG32(seed) (host only).
+    pub fn new(seed: u64) -> Result<RtwPerlin, RtwError> {
+        let mut t = RtwPerlin { ranvec: [[0.0; 3]; 256], perm_x: [0; 256], perm_y: [0; 256], perm_z: [0; 256] };
+        check(unsafe { rtw_perlin_new(seed, &mut t) })?;
+        Ok(t)
+    }
+    /// PerlinNoise::noise (turb_depth 0) / turb(p, turb_depth) on the host.
+    pub fn eval(&self, points: &[[f32; 3]], turb_depth: u32) -> Result<Vec<f32>, RtwError> {
+        let mut out = vec![0f32; points.len()];
+        check(unsafe { rtw_perlin_eval(self, points.as_ptr() as *const f32, points.len() as u32, turb_depth, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+}
+
+/// rtw_mgpu_set_texture_noise: the same on every device of an `rtw_mgpu` (handle from rtw_mgpu_create).
+pub unsafe fn mgpu_set_texture_noise(m: *mut RtwMgpu, tables: &[RtwPerlin], per_texture: &[RtwTextureNoise]) -> i32 {
+    rtw_mgpu_set_texture_noise(m, tables.as_ptr(), tables.len() as u32, per_texture.as_ptr(), per_texture.len() as u32)
+}

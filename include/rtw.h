@@ -107,8 +107,8 @@ typedef struct RtwSphere {
 } RtwSphere;
 
 /* `ImageTexture{img,row,col}` (Rust/src/texture.rs:21-27): row == width, col == height,
- * texel (x,y) lives at texels[3*(texel_offset + y*row + x)] (texture.rs:265). Perlin noise is
- * out of scope. */
+ * texel (x,y) lives at texels[3*(texel_offset + y*row + x)] (texture.rs:265).  The texture's optional Perlin noise
+ * (`ImageTexture.noise` / `noise_scale`) is set per context with rtw_ctx_set_texture_noise (RtwTextureNoise, below). */
 typedef struct RtwTexture {
     uint32_t row;
     uint32_t col;
@@ -266,7 +266,8 @@ int  rtw_ctx_render(rtw_ctx *ctx, const RtwCamera *cam, const RtwParams *params,
  * rtw_ctx_set_scene(ctx, scene, start_frame / fps, (start_frame + n_frames - 1) / fps + shutter). */
 int  rtw_ctx_render_multi(rtw_ctx *ctx, const RtwCamera *cam, const RtwParams *params, float fps,
                           uint32_t start_frame, uint32_t n_frames, float *out_rgb, RtwStats *stats);
-/* One-shot convenience: create ctx on the current device, set scene, render, destroy. */
+/* One-shot convenience: create ctx on the current device, set scene, render, destroy.  Renders without texture noise
+ * (use a context and rtw_ctx_set_texture_noise for that). */
 int  rtw_render(const RtwCamera *cam, const RtwScene *scene, const RtwParams *params,
                 float *out_rgb, RtwStats *stats);
 
@@ -318,9 +319,40 @@ int  rtw_mgpu_set_scene(rtw_mgpu *m, const RtwScene *scene, float t_begin, float
 int  rtw_mgpu_set_option(rtw_mgpu *m, uint32_t key, double value);
 int  rtw_mgpu_render(rtw_mgpu *m, const RtwCamera *cam, const RtwParams *params, float *out_rgb,
                      RtwStats *per_device, RtwStats *total);
-/* One-shot: create, set scene for [cam->time0, cam->time0 + cam->shutter], render, destroy. */
+/* One-shot: create, set scene for [cam->time0, cam->time0 + cam->shutter], render, destroy.  Renders without texture noise. */
 int  rtw_render_multi_gpu(const int *devices, uint32_t n_devices, const RtwCamera *cam, const RtwScene *scene,
                           const RtwParams *params, float *out_rgb, RtwStats *per_device);
+
+/* ---- Perlin noise of image textures (Rust/src/texture.rs:61-194, 259-267) ----------------------------------------------------
+ * `ImageTexture{noise: Option<PerlinNoise>, noise_scale}`: every texel the texture returns is multiplied by noise(p / noise_scale), p the
+ * hit point (spheres: r.at(t) in world space, also for a moving sphere; quads: the hit point; members of an instance: the point in the
+ * instance's LOCAL frame; constant-density media: the local point of the boundary hit).  The 1x1 textures of Sphere::new / Quad::new
+ * (tex < 0) never carry noise.  A scale of 0 is not rejected: p / 0 is inf or NaN and flows through as in the reference. */
+typedef struct RtwPerlin {            /* PerlinNoise (texture.rs:61-68); ranfloat is never read by noise(), so it is not carried */
+    float   ranvec[256][3];
+    uint8_t perm_x[256], perm_y[256], perm_z[256];
+} RtwPerlin;
+typedef struct RtwTextureNoise {      /* per RtwTexture: ImageTexture.noise / noise_scale */
+    int32_t perlin;                   /* index into the table array, -1 = no noise */
+    float   scale;
+} RtwTextureNoise;
+/* PerlinNoise::new (texture.rs:110-149) from `seed`: ranvec[i] = Vec3::random(-1, 1).unit() with the scene generators' PCG32 (the
+ * reference draws from the OS: its tables cannot be reproduced).  The permutations are the identity, as the reference's
+ * create_permute leaves them (its shuffle loop runs over the empty range 255..0).  Host only. */
+int rtw_perlin_new(uint64_t seed, RtwPerlin *out);
+/* PerlinNoise::noise (turb_depth == 0) or PerlinNoise::turb(p, turb_depth) at n points [n][3] on the host: out[n]. */
+int rtw_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t turb_depth, float *out);
+/* The same on ctx's GPU (the function the render kernels call), host buffers in and out; blocking. */
+int rtw_ctx_perlin_eval(rtw_ctx *ctx, const RtwPerlin *t, const float *points, uint32_t n, uint32_t turb_depth, float *out);
+/* Noise of the textures of the scene of the last rtw_ctx_set_scene (which clears it): per_texture[i] for RtwScene.textures[i],
+ * n_textures == the scene's texture count, every perlin index < n_tables (or -1).  per_texture == NULL with n_textures == 0 clears it.
+ * RTW_E_NO_SCENE before any scene.  While a texture that a sphere, quad or instance member uses has noise, renders run the noise build
+ * of the generic kernel, and RTW_INTEGRATOR_RUST2 (whose textures have no noise) fails with RTW_E_UNSUPPORTED.  The tables are copied. */
+int rtw_ctx_set_texture_noise(rtw_ctx *ctx, const RtwPerlin *tables, uint32_t n_tables,
+                              const RtwTextureNoise *per_texture, uint32_t n_textures);
+/* The same on every device of m (rtw_mgpu_set_scene clears it). */
+int rtw_mgpu_set_texture_noise(rtw_mgpu *m, const RtwPerlin *tables, uint32_t n_tables,
+                               const RtwTextureNoise *per_texture, uint32_t n_textures);
 
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 

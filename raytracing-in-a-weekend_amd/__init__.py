@@ -14,6 +14,8 @@ Reference surface mirrored (names and argument meaning):
   Quad.new                                  Rust/src/objects/quad.rs:84-110
   Instance.new / new_quads / new_sphere / new_box, translate, rotate   Rust/src/objects/instance.rs:83-248
   METALLIC_M, SCATTER_M, FUZZY3_M, GLASS_M, GLASSR_M   Rust/src/objects/materials.rs:157-212
+  PerlinNoise.new / noise / turb / value    Rust/src/texture.rs:61-194
+  ImageTexture::from_color_noise / new_with_noise      Rust/src/texture.rs:228-245 (texture_from_color_noise, texture_with_noise)
 
 The directory name carries a hyphen (it is fixed by the build contract); import it with
 ``importlib.import_module("raytracing-in-a-weekend_amd")`` or through the ``rtw_amd`` alias module
@@ -114,6 +116,16 @@ class RtwStats(C.Structure):
         return {k: (list(getattr(self, k)) if k.startswith("phase_") else getattr(self, k)) for k, _ in self._fields_}
 
 
+class RtwPerlin(C.Structure):
+    """`PerlinNoise` (Rust/src/texture.rs:61-68) without the never-read ranfloat."""
+    _fields_ = [("ranvec", (C.c_float * 3) * 256), ("perm_x", C.c_uint8 * 256), ("perm_y", C.c_uint8 * 256), ("perm_z", C.c_uint8 * 256)]
+
+
+class RtwTextureNoise(C.Structure):
+    """Per texture: `ImageTexture.noise` (index into the tables, -1 = None) and `noise_scale`."""
+    _fields_ = [("perlin", C.c_int32), ("scale", C.c_float)]
+
+
 _lib = None
 
 
@@ -179,6 +191,11 @@ def lib() -> C.CDLL:
     L.rtw_box_quads.argtypes = [fp, fp, fp, fp, C.POINTER(RtwQuad)]
     L.rtw_scene_generate_geom.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(RtwSphere), C.POINTER(RtwQuad), C.POINTER(RtwInstance),
                                           C.POINTER(RtwSphere), C.POINTER(RtwQuad), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), fp]
+    L.rtw_perlin_new.argtypes = [C.c_uint64, C.POINTER(RtwPerlin)]
+    L.rtw_perlin_eval.argtypes = [C.POINTER(RtwPerlin), fp, C.c_uint32, C.c_uint32, fp]
+    L.rtw_ctx_perlin_eval.argtypes = [C.c_void_p, C.POINTER(RtwPerlin), fp, C.c_uint32, C.c_uint32, fp]
+    L.rtw_ctx_set_texture_noise.argtypes = [C.c_void_p, C.POINTER(RtwPerlin), C.c_uint32, C.POINTER(RtwTextureNoise), C.c_uint32]
+    L.rtw_mgpu_set_texture_noise.argtypes = [C.c_void_p, C.POINTER(RtwPerlin), C.c_uint32, C.POINTER(RtwTextureNoise), C.c_uint32]
     _lib = L
     return L
 
@@ -299,13 +316,70 @@ class Instance:
         self.density, self.medium = float(density), MEDIUM_CONST_DENSITY
 
 
+class PerlinNoise:
+    """`PerlinNoise` (Rust/src/texture.rs:61-194).  `PerlinNoise(seed)` == PerlinNoise::new with the tables drawn from the library's
+    PCG32(seed) (the reference draws from the OS: its tables cannot be reproduced); the permutations are the identity, as the reference's
+    create_permute leaves them.  noise / turb / value take one point [3] or an array [..., 3] and run on the host (rtw_perlin_eval)."""
+
+    def __init__(self, seed: int = 0):
+        self.seed = int(seed)
+        self.pod = RtwPerlin()
+        _check(lib().rtw_perlin_new(C.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF), C.byref(self.pod)), "rtw_perlin_new")
+
+    @property
+    def ranvec(self) -> np.ndarray:
+        return np.ctypeslib.as_array(self.pod.ranvec).reshape(256, 3)
+
+    @property
+    def perm(self):
+        return tuple(np.ctypeslib.as_array(getattr(self.pod, k)) for k in ("perm_x", "perm_y", "perm_z"))
+
+    def _eval(self, p, depth: int) -> np.ndarray:
+        pts = np.ascontiguousarray(p, dtype=np.float32)
+        flat = pts.reshape(-1, 3)
+        out = np.empty(len(flat), np.float32)
+        if len(flat):
+            _check(lib().rtw_perlin_eval(C.byref(self.pod), flat.ctypes.data_as(C.POINTER(C.c_float)), len(flat), int(depth),
+                                         out.ctypes.data_as(C.POINTER(C.c_float))), "rtw_perlin_eval")
+        out = out.reshape(pts.shape[:-1])
+        return out[()] if out.ndim == 0 else out
+
+    def noise(self, p):
+        """PerlinNoise::noise (texture.rs:154-179)."""
+        return self._eval(p, 0)
+
+    def turb(self, p, depth: int):
+        """PerlinNoise::turb (texture.rs:181-193); depth 0 is |0| = 0 there, as here."""
+        if int(depth) == 0:
+            n = np.zeros(np.asarray(p).shape[:-1], np.float32)
+            return n[()] if n.ndim == 0 else n
+        return self._eval(p, int(depth))
+
+    def value(self, p):
+        """PerlinNoise::value (texture.rs:150-152): (1 + noise(p)) * 0.5 in f32."""
+        return (np.float32(1.0) + np.asarray(self.noise(p), np.float32)) * np.float32(0.5)
+
+
+def texture_with_noise(img, scale: float, perlin: Optional[PerlinNoise] = None, seed: int = 0):
+    """ImageTexture::new_with_noise(img, width, height, scale) (texture.rs:228-236): (texture array [height][width][3], noise entry) --
+    pass the array in Scene(textures=...) and the entry as Scene(noise={its index: entry})."""
+    return np.ascontiguousarray(img, dtype=np.float32), (perlin if perlin is not None else PerlinNoise(seed), float(scale))
+
+
+def texture_from_color_noise(color, scale: float, perlin: Optional[PerlinNoise] = None, seed: int = 0):
+    """ImageTexture::from_color_noise(color, scale) (texture.rs:237-245): a 1x1 image of `color` with noise."""
+    return texture_with_noise(np.asarray(color, np.float32).reshape(1, 1, 3), scale, perlin, seed)
+
+
 class Scene:
     """`Scene` (Rust/src/viewport.rs:79-151): spheres (+ image textures), quads, instances, background colour."""
 
     def __init__(self, spheres: Sequence, textures: Sequence[np.ndarray] = (), background=(0.0, 0.0, 0.0),
-                 quads: Sequence = (), instances: Sequence = (), emission_images=None):
+                 quads: Sequence = (), instances: Sequence = (), emission_images=None, noise=None):
         """`emission_images` {texture index: index of the texture that is its Rust2 `emmit_img`} (Rust2/src/objects/texture.rs:34-41;
-        RTW_INTEGRATOR_RUST2 only)."""
+        RTW_INTEGRATOR_RUST2 only).  `noise` {texture index: (PerlinNoise, noise_scale)}: ImageTexture.noise / noise_scale
+        (texture.rs:21-27); Renderer / MultiRenderer.set_scene pass it on.  to_json drops it, as the reference's JSON form does."""
+        self.noise = dict(noise or {})
         pods = [s.pod if isinstance(s, Sphere) else s for s in spheres]
         self._spheres = (RtwSphere * max(1, len(pods)))(*pods)
         self.n_spheres = len(pods)
@@ -390,8 +464,24 @@ class Scene:
         sc._install_geom(list(qd)[:n[1]], list(ins)[:n[2]], list(isp)[:n[3]], list(iqd)[:n[4]])
         return sc
 
+    def noise_pods(self):
+        """The arguments of rtw_ctx_set_texture_noise for `self.noise`: (tables, n_tables, per_texture, n_textures), or None without noise."""
+        if not self.noise:
+            return None
+        tables, index = [], {}
+        per = (RtwTextureNoise * max(1, self.n_textures))(*[RtwTextureNoise(-1, 1.0) for _ in range(max(1, self.n_textures))])
+        for t, (perlin, scale) in self.noise.items():
+            if not 0 <= int(t) < self.n_textures:
+                raise RtwError(-1, f"noise for texture {t}: the scene has {self.n_textures} textures")
+            if id(perlin) not in index:
+                index[id(perlin)] = len(tables)
+                tables.append(perlin.pod)
+            per[int(t)] = RtwTextureNoise(index[id(perlin)], float(scale))
+        tb = (RtwPerlin * len(tables))(*tables)
+        return tb, len(tables), per, self.n_textures
+
     def to_json(self) -> str:
-        """`Into<JsonValue> for Scene` (Rust/src/viewport.rs:174-180)."""
+        """`Into<JsonValue> for Scene` (Rust/src/viewport.rs:174-180).  Texture noise is not serialised (texture.rs:268-276)."""
         n = lib().rtw_scene_to_json(C.byref(self.pod), None, 0)
         buf = C.create_string_buffer(n + 1)
         lib().rtw_scene_to_json(C.byref(self.pod), buf, n + 1)
@@ -544,6 +634,21 @@ class Renderer:
     def set_scene(self, scene: Scene, t_begin: float = 0.0, t_end: float = 0.0):
         self._scene = scene     # keep host arrays alive
         _check(lib().rtw_ctx_set_scene(self._h, C.byref(scene.pod), float(t_begin), float(t_end)), "rtw_ctx_set_scene")
+        nz = scene.noise_pods()
+        if nz is not None:
+            _check(lib().rtw_ctx_set_texture_noise(self._h, *nz), "rtw_ctx_set_texture_noise")
+
+    def set_texture_noise(self, tables=None, n_tables: int = 0, per_texture=None, n_textures: int = 0):
+        """rtw_ctx_set_texture_noise as is (no arguments: clear the noise of the current scene)."""
+        _check(lib().rtw_ctx_set_texture_noise(self._h, tables, n_tables, per_texture, n_textures), "rtw_ctx_set_texture_noise")
+
+    def perlin_eval(self, perlin: PerlinNoise, p, depth: int = 0) -> np.ndarray:
+        """PerlinNoise::noise (depth 0) / turb(p, depth) on this context's GPU (rtw_ctx_perlin_eval)."""
+        pts = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3)
+        out = np.empty(len(pts), np.float32)
+        _check(lib().rtw_ctx_perlin_eval(self._h, C.byref(perlin.pod), pts.ctypes.data_as(C.POINTER(C.c_float)), len(pts), int(depth),
+                                         out.ctypes.data_as(C.POINTER(C.c_float))), "rtw_ctx_perlin_eval")
+        return out
 
     def set_option(self, key: int, value: float):
         """Tuning knobs (OPT_*); none of them changes the image."""
@@ -596,6 +701,9 @@ class MultiRenderer:
     def set_scene(self, scene: Scene, t_begin: float = 0.0, t_end: float = 0.0):
         self._scene = scene
         _check(lib().rtw_mgpu_set_scene(self._h, C.byref(scene.pod), float(t_begin), float(t_end)), "rtw_mgpu_set_scene")
+        nz = scene.noise_pods()
+        if nz is not None:
+            _check(lib().rtw_mgpu_set_texture_noise(self._h, *nz), "rtw_mgpu_set_texture_noise")
 
     def set_option(self, key: int, value: float):
         _check(lib().rtw_mgpu_set_option(self._h, int(key), float(value)), "rtw_mgpu_set_option")

@@ -13,6 +13,7 @@
 //   Rust/src/objects/materials.rs:89-154   refract, reflectance, Material::on_hit (+ diffuse :213-228)
 //   Rust/src/viewport/ray_color.rs:12-92   ray_color_gradient / ray_color_bg_color
 //   Rust/src/texture.rs:259-267            ImageTexture::color_at
+//   Rust/src/texture.rs:86-107,154-193     PerlinNoise::perlin_interp, noise, turb (the noise build, SPEC 7)
 //   Rust/src/objects/quad.rs:37-81         Quad::collision_normal
 //   Rust/src/objects/instance.rs:250-310   Instance::collision_normal (+ const_density :24-26)
 //   Rust/src/vec3.rs:161-181               Vec3::rotated
@@ -460,6 +461,78 @@ __device__ __forceinline__ v3 sphere_albedo(const DevScene &sc, const DevMat &m,
     return (ld3(px) * 1.0f) * ld3(m.cm);
 }
 
+// ---- Perlin noise of image textures (texture.rs:61-194): the noise build (SPEC 7) only ------------------------------------------------
+// One definition for the host entry point (rtw_perlin_eval), the evaluation kernel and the render kernels.  Every operation is the
+// reference's, one f32 rounding each, in its order (the library is built with -ffp-contract=off).
+// Rust `f as isize` for a floor()ed f32: saturating, NaN -> 0 (64-bit: the cell index of |p| >= 2^31 does not wrap early)
+__host__ __device__ __forceinline__ int64_t perlin_cell(float f) {
+    if (f != f) return 0;
+    if (f >= 0x1p63f) return INT64_MAX;
+    if (f <= -0x1p63f) return INT64_MIN;
+    return (int64_t)f;
+}
+// PerlinNoise::noise (texture.rs:154-179) + perlin_interp (:86-107)
+__host__ __device__ __forceinline__ float perlin_noise(const RtwPerlin &t, float x, float y, float z) {
+    const float fx = floorf(x), fy = floorf(y), fz = floorf(z);
+    const float u = x - fx, v = y - fy, w = z - fz;
+    // (i + di) & 255 with release-mode wrapping addition: isize::MAX + 1 wraps to isize::MIN
+    const uint64_t i = (uint64_t)perlin_cell(fx), j = (uint64_t)perlin_cell(fy), k = (uint64_t)perlin_cell(fz);
+    const float uu = u * u * (3.0f - 2.0f * u);
+    const float vv = v * v * (3.0f - 2.0f * v);
+    const float ww = w * w * (3.0f - 2.0f * w);
+    float accum = 0.0f;
+    for (int di = 0; di < 2; di++) {
+        for (int dj = 0; dj < 2; dj++) {
+            for (int dk = 0; dk < 2; dk++) {
+                const uint32_t h = (uint32_t)t.perm_x[(i + (uint64_t)di) & 255u] ^ (uint32_t)t.perm_y[(j + (uint64_t)dj) & 255u] ^
+                                   (uint32_t)t.perm_z[(k + (uint64_t)dk) & 255u];
+                const float *c = t.ranvec[h];
+                const float fi = (float)di, fj = (float)dj, fk = (float)dk;
+                const float d = c[0] * (u - fi) + c[1] * (v - fj) + c[2] * (w - fk);            // Vec3::dot (vec3.rs:194-196)
+                accum += (fi * uu + (1.0f - fi) * (1.0f - uu)) * (fj * vv + (1.0f - fj) * (1.0f - vv)) * (fk * ww + (1.0f - fk) * (1.0f - ww)) * d;
+            }
+        }
+    }
+    return accum;
+}
+// PerlinNoise::turb (texture.rs:181-193)
+__host__ __device__ __forceinline__ float perlin_turb(const RtwPerlin &t, float x, float y, float z, uint32_t depth) {
+    float accum = 0.0f, weight = 1.0f;
+    for (uint32_t d = 0; d < depth; d++) {
+        accum += weight * perlin_noise(t, x, y, z);
+        weight *= 0.5f;
+        x *= 2.0f; y *= 2.0f; z *= 2.0f;
+    }
+    return __builtin_fabsf(accum);
+}
+// depth 0: noise(p), else turb(p, depth) -- the two entry points of rtw_perlin_eval / rtw_ctx_perlin_eval
+__host__ __device__ __forceinline__ float perlin_eval(const RtwPerlin &t, float x, float y, float z, uint32_t depth) {
+    return depth == 0u ? perlin_noise(t, x, y, z) : perlin_turb(t, x, y, z, depth);
+}
+
+// The noise of a scene's textures (rtw_ctx_set_texture_noise): tex[i] for RtwScene.textures[i], tables[tex[i].perlin].  Plain global
+// loads: a few KB, cache-resident.
+struct DevNoise {
+    const RtwPerlin *tables;
+    const RtwTextureNoise *tex;
+};
+// ImageTexture::color_at's noise_mult (texture.rs:260-266): noise(p / noise_scale), or 1.0 when texture `tex` has no noise
+__device__ __forceinline__ float noise_mult(const DevNoise &nz, int32_t tex, v3 p) {
+    const RtwTextureNoise tn = nz.tex[tex];
+    if (tn.perlin < 0) return 1.0f;
+    return perlin_noise(nz.tables[tn.perlin], p.x / tn.scale, p.y / tn.scale, p.z / tn.scale);    // Vec3 / f32 (vec3.rs:120-129)
+}
+// sphere_albedo with the texture's noise at `point` (r.at(t), sphere.rs:145): the noise multiplier takes the place of the `* 1.0f`
+__device__ __forceinline__ v3 sphere_albedo_noise(const DevScene &sc, const DevNoise &nz, const DevMat &m, v3 normal, v3 point) {
+    if (m.tex < 0) return ld3(m.cm);
+    float u, v;
+    sphere_uv(normal, u, v);
+    uint32_t tx = tex_index(floorf(u * (float)(m.tex_row - 1)), m.tex_row - 1);
+    uint32_t ty = tex_index(floorf(v * (float)(m.tex_col - 1)), m.tex_col - 1);
+    const float *px = sc.texels + 3 * (size_t)(m.tex_offset + ty * m.tex_row + tx);
+    return (ld3(px) * noise_mult(nz, m.tex, point)) * ld3(m.cm);
+}
+
 // Rust2's ImageTexture::color_at (Rust2/src/objects/texture.rs:94-105), reached from Rust2's Sphere::color (Rust2/src/objects/sphere.rs:92-107):
 // multiplied = img[x * width + y] with x = (u * width) as usize, y = (v * height) as usize -- scaled by the size, not size - 1, and indexed
 // TRANSPOSED (part of the contract: SURVEY.md 8 a10) --; emmited = emmit_img[emmit_x * emmit_width + emmit_y] with floor() before the casts.
@@ -676,6 +749,7 @@ __device__ __forceinline__ float ln_f32(float xf) {
 }
 
 #ifdef RTW_GEOM_EAGER_RECORDS
+#error "RTW_GEOM_EAGER_RECORDS has no noise build (SPEC 7, rtw_kernels.hip): the experiment predates texture noise"
 // Quad::collision_normal (quad.rs:37-81) against quad `qi` of `quads`; on Some(hit) that is strictly closer
 // than the current one (`min_hit == None || min_hit > i`) it replaces h.
 __device__ __forceinline__ void quad_test(const DevScene &sc, const DevQuad *quads, uint32_t qi, v3 o, v3 d,
@@ -832,8 +906,10 @@ __device__ __forceinline__ bool quad_pick(const DevQuad *quads, uint32_t qi, v3 
     return true;
 }
 
-// The `Hit` of quad `qi` at parameter t (quad.rs:64-81); qi is per lane here (vector loads).
-__device__ __forceinline__ void quad_record(const DevScene &sc, const DevQuad *quads, uint32_t qi, v3 o, v3 d, float t, GeomHit &h) {
+// The `Hit` of quad `qi` at parameter t (quad.rs:64-81); qi is per lane here (vector loads).  NOISE (SPEC 7): the texel is multiplied by
+// its texture's noise at the hit point (o, d: the frame the quad is hit in) instead of by 1.0.
+template <bool NOISE = false>
+__device__ __forceinline__ void quad_record(const DevScene &sc, const DevNoise &nz, const DevQuad *quads, uint32_t qi, v3 o, v3 d, float t, GeomHit &h) {
     const DevQuad &q = quads[qi];
     const v3 point = o + d * t;
     v3 cm = ld3(q.albedo);
@@ -847,7 +923,8 @@ __device__ __forceinline__ void quad_record(const DevScene &sc, const DevQuad *q
         const RtwTexture tx = sc.tex[tex];
         const uint32_t ix = alfa != 1.0f ? tex_index(floorf(alfa * (float)tx.row), tx.row - 1) : tx.row - 1;
         const uint32_t iy = beta != 1.0f ? tex_index(floorf(beta * (float)tx.col), tx.col - 1) : tx.col - 1;
-        cm = ld3(sc.texels + 3 * (size_t)(tx.texel_offset + iy * tx.row + ix)) * 1.0f;
+        if constexpr (NOISE) cm = ld3(sc.texels + 3 * (size_t)(tx.texel_offset + iy * tx.row + ix)) * noise_mult(nz, tex, point);
+        else cm = ld3(sc.texels + 3 * (size_t)(tx.texel_offset + iy * tx.row + ix)) * 1.0f;
     }
     h.t = t; h.point = point; h.normal = ld3(q.normal); h.cm = cm;
     h.m = mat_params(q.metallicness, q.opacity, q.ir);
@@ -889,24 +966,29 @@ __device__ __forceinline__ bool instance_pick(const DevGeom &g, const DevInstanc
     return found;
 }
 
-// The `Hit` of an instance's member `code` at parameter t, in the instance's frame.
-__device__ __forceinline__ void member_record(const DevScene &sc, const DevGeom &g, int code, v3 o, v3 d, float tm, float t, GeomHit &h) {
+// The `Hit` of an instance's member `code` at parameter t, in the instance's frame.  NOISE: the texture noise is taken at the LOCAL
+// hit point, the member being hit with the rotated, translated ray (instance.rs:257-261).
+template <bool NOISE = false>
+__device__ __forceinline__ void member_record(const DevScene &sc, const DevNoise &nz, const DevGeom &g, int code, v3 o, v3 d, float tm, float t, GeomHit &h) {
     if (code >= 0) {
         const f4 gg = g.igeom[code], vv = g.ivel[code];
         const v3 c = mk(gg.x, gg.y, gg.z) + mk(vv.x, vv.y, vv.z) * tm;
         const DevMat mat = g.imat[code];
         h.t = t; h.point = o + d * t; h.normal = unit(h.point - c);
-        h.cm = sphere_albedo(sc, mat, h.normal);
+        if constexpr (NOISE) h.cm = sphere_albedo_noise(sc, nz, mat, h.normal, h.point);
+        else h.cm = sphere_albedo(sc, mat, h.normal);
         h.m = mat_params(mat);
         h.emitted = ld3(mat.emitted);
     } else {
-        quad_record(sc, g.iquads, (uint32_t)~code, o, d, t, h);
+        quad_record<NOISE>(sc, nz, g.iquads, (uint32_t)~code, o, d, t, h);
     }
 }
 
 // The part of Scene::collision_normal (viewport.rs:136-150) after the top-level spheres: quads, then instances.
-// `sphere_found` / `sphere_t` are the sphere result; returns true when a quad or an instance wins, h = its Hit.
-__device__ __forceinline__ bool geom_closest(const DevScene &sc, const DevGeom &g, v3 o, v3 d, float tm, float mint, float maxt,
+// `sphere_found` / `sphere_t` are the sphere result; returns true when a quad or an instance wins, h = its Hit.  NOISE: the noise build
+// (textures with noise; `nz` is read only then).
+template <bool NOISE = false>
+__device__ __forceinline__ bool geom_closest(const DevScene &sc, const DevNoise &nz, const DevGeom &g, v3 o, v3 d, float tm, float mint, float maxt,
                                              bool sphere_found, float sphere_t, Rng &rng, GeomHit &h, uint32_t &n_sph, uint32_t &n_quad) {
     bool found = sphere_found;
     float ht = sphere_t;
@@ -944,12 +1026,12 @@ __device__ __forceinline__ bool geom_closest(const DevScene &sc, const DevGeom &
     }
     if (ifound && (!found || ht > it)) win = 2;
     if (win == 1) {
-        quad_record(sc, g.quads, qk, o, d, ht, h);
+        quad_record<NOISE>(sc, nz, g.quads, qk, o, d, ht, h);
     } else if (win == 2) {
         const DevInstance &in = g.inst[ii];
         const v3 tr = ld3(in.tr);
         const v3 lo = rotated(o - tr, in.back, in.back_k), ld = rotated(d, in.back, in.back_k);
-        member_record(sc, g, icode, lo, ld, tm, it, h);
+        member_record<NOISE>(sc, nz, g, icode, lo, ld, tm, it, h);      // (the medium moves the point only after col_mod is fixed: instance.rs:281-305)
         if (imed) { h.point = imp; h.normal = imn; }
         h.point = rotated(h.point, in.fwd, in.fwd_k) + tr;
         h.normal = rotated(h.normal, in.fwd, in.fwd_k);

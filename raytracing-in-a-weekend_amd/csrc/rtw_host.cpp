@@ -102,6 +102,26 @@ void rtw_vec3_rotated(const float v[3], const float rot[3], float out[3]) {
     out[2] = x * -bs + y * as * bc + z * ac * bc;
 }
 
+// PerlinNoise::new (Rust/src/texture.rs:110-149): ranvec[i] = Vec3::random(-1, 1).unit() -- each component xi * (max - min) + min
+// (vec3.rs:221-227), then divided by the root of its dot product (vec3.rs:191-206), no rejection loop -- drawn from PCG32(seed) instead of
+// the OS-seeded thread_rng.  ranfloat is drawn by the reference but never read by noise(): not carried.  create_permute's shuffle runs
+// over the empty range PERLIN_POINT_COUNT - 1..0 (texture.rs:142), so every permutation is the identity.
+static_assert(sizeof(RtwPerlin) == 3840 && sizeof(RtwTextureNoise) == 8, "POD layout");
+int rtw_perlin_new(uint64_t seed, RtwPerlin *out) {
+    if (!out) return RTW_E_INVALID;
+    Pcg32 g(seed);
+    const float lo = -1.0f, hi = 1.0f;
+    for (int i = 0; i < 256; i++) {
+        V p;
+        p.x = g.f() * (hi - lo) + lo;
+        p.y = g.f() * (hi - lo) + lo;
+        p.z = g.f() * (hi - lo) + lo;
+        st(out->ranvec[i], unit(p));
+    }
+    for (int i = 0; i < 256; i++) out->perm_x[i] = out->perm_y[i] = out->perm_z[i] = (uint8_t)i;
+    return RTW_OK;
+}
+
 uint32_t rtw_part_rows(uint32_t height, uint32_t row_block, uint32_t part_index, uint32_t part_count) {
     if (part_count <= 1) return height;
     if (row_block == 0 || part_index >= part_count) return 0;

@@ -74,10 +74,14 @@ struct KArgs {
     uint32_t *queue;              // work-item counter, zeroed before launch
     unsigned long long endtimes_ref;   // -DRTW_ENDTIMES builds: reference wave lifetime for the histogram (0 = none)
     unsigned long long *stats;    // [0] camera rays [1] segments [2] sphere tests [3] node tests [4] nan pixels [5..7] phase steps [8..10] phase lanes [14] quad tests [16..19] steps, lanes of phases 3 (switch), 4 (new path)
+    // (appended: the offsets of everything above, which the other builds read, stay where they were)
+    DevNoise noise;               // texture noise (rtw_ctx_set_texture_noise); noise.tex != null selects the noise build (SPEC 7), which alone reads it
 };
 
 // accel: RTW_ACCEL_BRUTE, RTW_ACCEL_BVH; the BVH launch picks the LDS-resident variant when a.bvh.nodes16 != null
 void launch_render(const KArgs &a, bool moving, uint32_t accel, uint32_t grid, hipStream_t stream);
+// rtw_ctx_perlin_eval: out[i] = perlin_eval(*t, points[i], depth) for i < n (device pointers), on `stream`
+void launch_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t depth, float *out, hipStream_t stream);
 // Resident workgroups per CU for the kernel variant (occupancy API), >= 1.
 uint32_t kernel_blocks_per_cu(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);
 // Is there a build of the BVH kernel for this configuration that reads the spheres' {centre, r^2} from LDS?  (KArgs.lds_geom_off may only be set then)

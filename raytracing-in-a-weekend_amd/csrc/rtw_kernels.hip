@@ -49,13 +49,16 @@ namespace rtw {
 // SPEC == 4 is the reference's own demo configuration, presentation_image (main.rs:89-419): ray_color_bg_color with the render_row sampler; SPEC == 5 is
 // Rust2's: its `ray_color` through its fixed-centre `render_row` (Rust2/src/viewport.rs:87-114); SPEC == 6 is ray_color_gradient through the stratified
 // `Viewport::render` (viewport.rs:430-478: the reference's serial driver, quad_test's).  All three keep the generic build's step and fold the switches.
-// SPEC == 0 reads everything from the (wave-uniform) kernel arguments.
+// SPEC == 0 reads everything from the (wave-uniform) kernel arguments.  SPEC == 7 is SPEC == 0 plus the noise of image textures (texture.rs:
+// 259-267, rtw_ctx_set_texture_noise): the generic step with noise(p / scale) in place of the texel's `* 1.0`; only scenes with noise select it.
 constexpr bool gradient_spec(int spec) { return spec >= 1 && spec <= 3; }
+constexpr bool generic_spec(int spec) { return spec == 0 || spec == 7; }
+constexpr bool noise_spec(int spec) { return spec == 7; }
 template <int SPEC> __device__ __forceinline__ uint32_t integ(const KArgs &A) {
-    return SPEC == 5 ? (uint32_t)RTW_INTEGRATOR_RUST2 : SPEC == 4 ? (uint32_t)RTW_INTEGRATOR_BG_COLOR : SPEC ? (uint32_t)RTW_INTEGRATOR_GRADIENT : A.integrator;
+    return SPEC == 5 ? (uint32_t)RTW_INTEGRATOR_RUST2 : SPEC == 4 ? (uint32_t)RTW_INTEGRATOR_BG_COLOR : !generic_spec(SPEC) ? (uint32_t)RTW_INTEGRATOR_GRADIENT : A.integrator;
 }
 template <int SPEC> __device__ __forceinline__ uint32_t samp(const KArgs &A) {
-    return SPEC == 6 ? (uint32_t)RTW_SAMPLER_STRATIFIED : SPEC == 5 ? (uint32_t)RTW_SAMPLER_CENTRES : SPEC ? (uint32_t)RTW_SAMPLER_ROW : A.sampler;
+    return SPEC == 6 ? (uint32_t)RTW_SAMPLER_STRATIFIED : SPEC == 5 ? (uint32_t)RTW_SAMPLER_CENTRES : !generic_spec(SPEC) ? (uint32_t)RTW_SAMPLER_ROW : A.sampler;
 }
 
 struct Pixel {            // the work unit a lane owns: a run of consecutive samples of one pixel.  Four registers (they live through every step of
@@ -251,7 +254,7 @@ __device__ __forceinline__ void start_path(const KArgs &A, const Pixel &px, Path
             random_in_unit_disk(pt.rng, rx, ry, false, cn);
             o = cam_o + mk(rx, ry, 0.0f) * cam.lens_radius;
         } else {
-            random_in_unit_disk(pt.rng, rx, ry, !SPEC && (A.flags & RTW_FLAG_CPP_DIFFUSE), cn);   // always drawn (viewport.rs:288)
+            random_in_unit_disk(pt.rng, rx, ry, generic_spec(SPEC) && (A.flags & RTW_FLAG_CPP_DIFFUSE), cn);   // always drawn (viewport.rs:288)
             o = cam_o + (ld3(cam.u) * rx + ld3(cam.v) * ry) * cam.lens_radius;
             if (samp<SPEC>(A) == RTW_SAMPLER_ROW) {              // viewport.rs:290-297
                 jx = rng_offset(pt.rng, (float)px_i(px));
@@ -303,7 +306,7 @@ __device__ __forceinline__ bool shade_surface(const KArgs &A, Path &pt, v3 ud, v
         return false;
     }
     float cos_theta;
-    const v3 nd = on_hit(mat, point, normal, pt.d, ud, pt.rng, cos_theta, SPEC ? 0u : A.flags, cn);
+    const v3 nd = on_hit(mat, point, normal, pt.d, ud, pt.rng, cos_theta, generic_spec(SPEC) ? A.flags : 0u, cn);
     if (integ<SPEC>(A) == RTW_INTEGRATOR_BG_COLOR) {           // ray_color.rs:64-88, front-to-back
         // lambertian_scatter_pdf (materials.rs:5-13); pdf == 0 makes the reference's `color * pdf / pdf` a 0/0
         const float pdf = cos_theta > 0.0f ? cos_theta * 0.318309886183790671538f : 0.0f;
@@ -333,7 +336,8 @@ __device__ __forceinline__ bool shade_hit(const KArgs &A, Path &pt, v3 ud, int b
     const v3 normal = unit(point - c);                       // sphere.rs:127
     const DevMat mat = sc.mat[best];
     v3 cm, emitted = ld3(mat.emitted);
-    if ((SPEC == 0 || SPEC == 5) && integ<SPEC>(A) == RTW_INTEGRATOR_RUST2 && mat.tex >= 0) rust2_sphere_color(sc, mat, normal, cm, emitted);     // Rust2's own lookup rule
+    if ((generic_spec(SPEC) || SPEC == 5) && integ<SPEC>(A) == RTW_INTEGRATOR_RUST2 && mat.tex >= 0) rust2_sphere_color(sc, mat, normal, cm, emitted);     // Rust2's own lookup rule
+    else if constexpr (noise_spec(SPEC)) cm = sphere_albedo_noise(sc, A.noise, mat, normal, point);         // noise at r.at(t) (sphere.rs:145)
     else cm = (SPEC == 1 || SPEC == 3) ? ld3(mat.cm) : sphere_albedo(sc, mat, normal);
     return shade_surface<SPEC>(A, pt, ud, point, normal, cm, mat_params(mat), emitted, cn);
 }
@@ -393,7 +397,7 @@ __device__ __forceinline__ void start_path_second(const Pixel &px, Path &pt, flo
 template <bool MOVING, int SPEC>
 __device__ __forceinline__ bool shade_geom(const KArgs &A, Path &pt, int best, float best_t, uint32_t &n_sph, uint32_t &n_quad) {
     GeomHit h;
-    if (geom_closest(A.sc, A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, pt.rng, h, n_sph, n_quad)) {
+    if (geom_closest<noise_spec(SPEC)>(A.sc, A.noise, A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, pt.rng, h, n_sph, n_quad)) {
         mat_derive(h.m);
         return shade_surface<SPEC>(A, pt, unit(pt.d), h.point, h.normal, h.cm, h.m, h.emitted);
     }
@@ -407,7 +411,7 @@ __device__ __forceinline__ bool finish_path(const KArgs &A, Pixel &px, Path &pt,
     RTW_CEN(cn, CEN_BANK);
     if (pt.poison) { const float qn = __builtin_nanf(""); pt.L = mk(qn, qn, qn); }
     float3 *dst = reinterpret_cast<float3 *>(A.samples + 3 * (size_t)px.slot);
-    if (SPEC == 3 || (SPEC == 0 && (A.flags & RTW_FLAG_CHUNK_SUMS))) {        // one slot per unit, the unit's samples added into it in sample order
+    if (SPEC == 3 || (generic_spec(SPEC) && (A.flags & RTW_FLAG_CHUNK_SUMS))) {        // one slot per unit, the unit's samples added into it in sample order
         if (px_s(px) & (RTW_SUM_CHUNK - 1u)) {      // (chunk_len == RTW_SUM_CHUNK in this mode, units start on multiples of it)
             const float3 acc = *dst;
             pt.L = mk(acc.x, acc.y, acc.z) + pt.L;
@@ -545,7 +549,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? RTW_GEOM_BRUTE_WAVES : 1) void re
         if (have && newpath) { newpath = false; start_path<SPEC>(A, px, pt); n_rays++; }
         if (have) {
             bool finished;
-            if (!SPEC && A.depth == 0 && A.integrator != RTW_INTEGRATOR_NORMAL) {   // `if depth < 1 { return black }` (ray_color.rs:14-16)
+            if (generic_spec(SPEC) && A.depth == 0 && A.integrator != RTW_INTEGRATOR_NORMAL) {   // `if depth < 1 { return black }` (ray_color.rs:14-16)
                 pt.L = A.integrator == RTW_INTEGRATOR_RUST2 ? ld3(A.bg) : mk(0, 0, 0); finished = true;
             } else {
                 int best; float best_t;
@@ -917,7 +921,7 @@ constexpr bool two_halves_step(int spec, bool geom, bool moving) {
 #endif
 }
 template <bool MOVING, int NODES, int SPEC, bool GEOM>
-__global__ __launch_bounds__(RTW_BLOCK, GEOM ? (SPEC != 0 ? RTW_BVH_WAVES_GEOM_SPEC : RTW_BVH_WAVES_GEOM) : (two_halves_step(SPEC, GEOM, MOVING) ? (SPEC == 2 ? RTW_BVH_WAVES_SPEC2 : RTW_BVH_WAVES_SPEC) : (gradient_spec(SPEC) ? RTW_BVH_WAVES_SPEC2 : (SPEC != 0 ? RTW_BVH_WAVES_FOLDED : RTW_BVH_WAVES)))) void render_bvh(const KArgs A) {
+__global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WAVES_GEOM_SPEC : RTW_BVH_WAVES_GEOM) : (two_halves_step(SPEC, GEOM, MOVING) ? (SPEC == 2 ? RTW_BVH_WAVES_SPEC2 : RTW_BVH_WAVES_SPEC) : (gradient_spec(SPEC) ? RTW_BVH_WAVES_SPEC2 : (!generic_spec(SPEC) ? RTW_BVH_WAVES_FOLDED : RTW_BVH_WAVES)))) void render_bvh(const KArgs A) {
     constexpr bool LDSN = NODES != 0, geom_in_lds = NODES == 2;
     // LDS is all dynamic, sized by the host for THIS tree (rtw_shim.hip, render_enqueue_impl): -- LDS-node variants -- the f16 nodes at
     // offset 0, then the per-lane traversal stack [level][thread] (a level is one conflict-free row; depth + 3 levels: the sentinel,
@@ -1117,7 +1121,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (SPEC != 0 ? RTW_BVH_WAVES_GEOM_S
                     // c. next camera ray (a lane whose path continues keeps its scattered ray)
                     if (fl & F_NEWPATH) { fl &= ~F_NEWPATH; start_path<SPEC>(A, px, pt, cn); started = true; }
                     // d. start the next closest-hit query
-                    if (!SPEC && A.depth == 0 && A.integrator != RTW_INTEGRATOR_NORMAL) {   // `if depth < 1 { return black }` (ray_color.rs:14-16)
+                    if (generic_spec(SPEC) && A.depth == 0 && A.integrator != RTW_INTEGRATOR_NORMAL) {   // `if depth < 1 { return black }` (ray_color.rs:14-16)
                         pt.L = A.integrator == RTW_INTEGRATOR_RUST2 ? ld3(A.bg) : mk(0, 0, 0);
                         fl |= F_DONE;                                      // banked on the next SHADE trip
                     } else {
@@ -1271,7 +1275,8 @@ static kernel_fn pick_kernel_spec(bool moving, uint32_t accel, int nodes) {
     return moving ? render_brute<true, SPEC, false> : render_brute<false, SPEC, false>;
 }
 // quads / instances in the scene: the step of the generic build (SPEC == 0: everything from the kernel arguments; SPEC == 2: the common configuration folded
-// in at compile time, sphere textures kept) with the extra closest-hit stage (sphere geometry always global: kernel_has_lds_geom)
+// in at compile time, sphere textures kept; SPEC == 7: SPEC == 0 with texture noise) with the extra closest-hit stage (sphere geometry always global:
+// kernel_has_lds_geom)
 template <int SPEC>
 static kernel_fn pick_kernel_geom(bool moving, uint32_t accel, int nodes) {
     if (accel == RTW_ACCEL_BVH) {
@@ -1282,6 +1287,8 @@ static kernel_fn pick_kernel_geom(bool moving, uint32_t accel, int nodes) {
 }
 static kernel_fn pick_kernel(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
     const int nodes = lds_nodes ? (a.lds_geom_off ? 2 : 1) : 0;
+    // a texture that a sphere, quad or member uses has noise (rtw_shim.hip sets noise.tex only then): the noise build, for every integrator, sampler and flag
+    if (a.noise.tex) return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<7>(moving, accel, nodes) : pick_kernel_spec<7>(moving, accel, nodes);
     if (a.geom.n_quads || a.geom.n_inst) {
 #ifndef RTW_GEOM_GENERIC_ONLY
         if (is_common_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<2>(moving, accel, nodes);
@@ -1299,6 +1306,17 @@ static kernel_fn pick_kernel(const KArgs &a, bool moving, uint32_t accel, bool l
     if (!is_common_config(a)) return pick_kernel_spec<0>(moving, accel, nodes);
     if (a.flags & RTW_FLAG_CHUNK_SUMS) return a.has_textures ? pick_kernel_spec<0>(moving, accel, nodes) : pick_kernel_spec<3>(moving, accel, nodes);
     return a.has_textures ? pick_kernel_spec<2>(moving, accel, nodes) : pick_kernel_spec<1>(moving, accel, nodes);
+}
+
+// PerlinNoise::noise / turb at n points (rtw_ctx_perlin_eval): the function the noise build's texel lookups call
+__global__ __launch_bounds__(RTW_BLOCK) void perlin_eval_kernel(const RtwPerlin *t, const float *points, uint32_t n, uint32_t depth, float *out) {
+    const uint32_t i = blockIdx.x * RTW_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    out[i] = perlin_eval(*t, points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2], depth);
+}
+
+void launch_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t depth, float *out, hipStream_t stream) {
+    hipLaunchKernelGGL(perlin_eval_kernel, dim3((n + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, t, points, n, depth, out);
 }
 
 bool kernel_has_lds_geom(const KArgs &a) { return !(a.geom.n_quads || a.geom.n_inst); }

@@ -47,6 +47,12 @@ struct rtw_ctx {
     void *d_quads = nullptr, *d_inst = nullptr, *d_igeom = nullptr, *d_ivel = nullptr, *d_imat = nullptr, *d_iquads = nullptr;
     DevBvh bvh{};
     void *d_nodes = nullptr, *d_nodes16 = nullptr, *d_big_geom = nullptr, *d_big_vel = nullptr, *d_big_index = nullptr;
+    // texture noise of the scene (rtw_ctx_set_texture_noise; cleared by rtw_ctx_set_scene)
+    uint32_t n_textures = 0;
+    std::vector<uint8_t> tex_used;       // [n_textures]: a sphere, quad or instance member reads texture i
+    bool noise_active = false;           // a used texture has noise: renders take the noise build (SPEC 7)
+    DevNoise noise{};                    // device tables / per-texture entries (null when no noise is set)
+    void *d_perlin = nullptr, *d_tex_noise = nullptr;
     // scratch
     uint32_t *d_queue = nullptr;
     unsigned long long *d_stats = nullptr;
@@ -223,10 +229,20 @@ int rtw_ctx_create(int device, rtw_ctx **out) {
     return RTW_OK;
 }
 
+static void free_noise(rtw_ctx *c) {
+    void **bufs[] = { &c->d_perlin, &c->d_tex_noise };
+    for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    c->noise = DevNoise{};
+    c->noise_active = false;
+}
+
 static void free_scene(rtw_ctx *c) {
     void **bufs[] = { &c->d_quads, &c->d_inst, &c->d_igeom, &c->d_ivel, &c->d_imat, &c->d_iquads,
                       &c->d_geom, &c->d_vel, &c->d_mat, &c->d_tex, &c->d_texels, &c->d_nodes, &c->d_nodes16, &c->d_big_geom, &c->d_big_vel, &c->d_big_index };
     for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    free_noise(c);
+    c->n_textures = 0;
+    c->tex_used.clear();
     c->has_scene = false;
 }
 
@@ -381,7 +397,73 @@ int rtw_ctx_set_scene(rtw_ctx *c, const RtwScene *s, float t_begin, float t_end)
     std::memcpy(c->bg, s->background, sizeof c->bg);
     c->has_textures = false;
     for (uint32_t i = 0; i < s->n_spheres; i++) if (s->spheres[i].tex >= 0) c->has_textures = true;
+    // which textures the primitives read: noise on any of them selects the noise build (rtw_ctx_set_texture_noise)
+    c->n_textures = s->n_textures;
+    c->tex_used.assign(s->n_textures, 0);
+    for (uint32_t i = 0; i < s->n_spheres; i++) if (s->spheres[i].tex >= 0) c->tex_used[s->spheres[i].tex] = 1;
+    for (uint32_t i = 0; i < s->n_inst_spheres; i++) if (s->inst_spheres[i].tex >= 0) c->tex_used[s->inst_spheres[i].tex] = 1;
+    for (uint32_t i = 0; i < s->n_quads; i++) if (s->quads[i].tex >= 0) c->tex_used[s->quads[i].tex] = 1;
+    for (uint32_t i = 0; i < s->n_inst_quads; i++) if (s->inst_quads[i].tex >= 0) c->tex_used[s->inst_quads[i].tex] = 1;
     c->has_scene = true;
+    return RTW_OK;
+}
+
+int rtw_ctx_set_texture_noise(rtw_ctx *c, const RtwPerlin *tables, uint32_t n_tables, const RtwTextureNoise *per_texture, uint32_t n_textures) {
+    if (!c) return RTW_E_INVALID;
+    if (!c->has_scene) return RTW_E_NO_SCENE;
+    if (c->pend.active) return RTW_E_INVALID;
+    if (!per_texture) {                                            // NULL / 0: no noise
+        if (n_textures != 0) return RTW_E_INVALID;
+        HIP_TRY(hipSetDevice(c->device));
+        free_noise(c);
+        return RTW_OK;
+    }
+    if (n_textures != c->n_textures || (n_tables && !tables)) return RTW_E_INVALID;
+    bool active = false;
+    for (uint32_t i = 0; i < n_textures; i++) {
+        const int32_t k = per_texture[i].perlin;
+        if (k < -1 || (k >= 0 && (uint32_t)k >= n_tables)) return RTW_E_INVALID;
+        if (k >= 0 && c->tex_used[i]) active = true;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    free_noise(c);
+    if (!active) return RTW_OK;                                    // no texture a primitive reads has noise: the image is the noise-free one
+    std::vector<RtwPerlin> tb(tables, tables + n_tables);
+    std::vector<RtwTextureNoise> tn(per_texture, per_texture + n_textures);
+    int rc;
+    if ((rc = upload(&c->d_perlin, tb)) || (rc = upload(&c->d_tex_noise, tn))) { free_noise(c); return rc; }
+    c->noise.tables = (const RtwPerlin *)c->d_perlin;
+    c->noise.tex = (const RtwTextureNoise *)c->d_tex_noise;
+    c->noise_active = true;
+    return RTW_OK;
+}
+
+int rtw_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t turb_depth, float *out) {
+    if (!t || !points || !out || n == 0) return RTW_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) out[i] = perlin_eval(*t, points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2], turb_depth);
+    return RTW_OK;
+}
+
+int rtw_ctx_perlin_eval(rtw_ctx *c, const RtwPerlin *t, const float *points, uint32_t n, uint32_t turb_depth, float *out) {
+    if (!c || !t || !points || !out || n == 0) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t pts_bytes = 3 * sizeof(float) * (size_t)n, out_bytes = sizeof(float) * (size_t)n;
+    void *d_t = nullptr, *d_p = nullptr, *d_o = nullptr;
+    hipError_t e = hipMalloc(&d_t, sizeof(RtwPerlin));
+    if (e == hipSuccess) e = hipMalloc(&d_p, pts_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_o, out_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(RtwPerlin), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_p, points, pts_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch_perlin_eval((const RtwPerlin *)d_t, (const float *)d_p, n, turb_depth, (float *)d_o, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, out_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    const bool alloc_failed = e == hipErrorOutOfMemory;
+    for (void *b : { d_t, d_p, d_o }) if (b) (void)hipFree(b);
+    if (e != hipSuccess) { g_last_hip = (int)e; return alloc_failed ? RTW_E_NOMEM : RTW_E_HIP; }
     return RTW_OK;
 }
 
@@ -450,6 +532,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     if (p->integrator > RTW_INTEGRATOR_RUST2 || p->sampler > RTW_SAMPLER_NO_RAND || p->accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
     if (p->part_count > 1 && (p->row_block == 0 || p->part_index >= p->part_count)) return RTW_E_INVALID;
     if (p->width > 65535u || p->height > 65535u) return RTW_E_INVALID;      // a lane keeps (column, row) in one register (rtw_kernels.hip Pixel)
+    if (c->noise_active && p->integrator == RTW_INTEGRATOR_RUST2) return RTW_E_UNSUPPORTED;   // Rust2's textures have no noise
     if (!c->pend.marked) c->pend.t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(c->device));
 
@@ -507,6 +590,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     a.mint = p->mint; a.maxt = p->maxt;
     std::memcpy(a.bg, c->bg, sizeof a.bg);
     a.queue = c->d_queue; a.stats = c->d_stats;
+    if (c->noise_active) a.noise = c->noise;                       // (selects the noise build: pick_kernel)
 #ifdef RTW_ENDTIMES
     if (const char *e = getenv("RTW_ENDTIMES_REF")) a.endtimes_ref = std::strtoull(e, nullptr, 10);       // diagnostic build only
 #endif
@@ -875,6 +959,12 @@ void rtw_mgpu_destroy(rtw_mgpu *m) {
 int rtw_mgpu_set_scene(rtw_mgpu *m, const RtwScene *scene, float t_begin, float t_end) {
     if (!m) return RTW_E_INVALID;
     for (rtw_ctx *c : m->ctx) { int rc = rtw_ctx_set_scene(c, scene, t_begin, t_end); if (rc != RTW_OK) return rc; }
+    return RTW_OK;
+}
+
+int rtw_mgpu_set_texture_noise(rtw_mgpu *m, const RtwPerlin *tables, uint32_t n_tables, const RtwTextureNoise *per_texture, uint32_t n_textures) {
+    if (!m) return RTW_E_INVALID;
+    for (rtw_ctx *c : m->ctx) { int rc = rtw_ctx_set_texture_noise(c, tables, n_tables, per_texture, n_textures); if (rc != RTW_OK) return rc; }
     return RTW_OK;
 }
 
