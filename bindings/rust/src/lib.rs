@@ -48,6 +48,21 @@ pub struct RtwPerlin { pub ranvec: [[f32; 3]; 256], pub perm_x: [u8; 256], pub p
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct RtwTextureNoise { pub perlin: i32, pub scale: f32 }
 
+/// Arguments of the bilateral post-process (Rust2/src/postprocessing.rs:12-131): Proximity{size, type}, the input's format
+/// (0 = [h][w][3] u8, 1 = the renderer's f32 frame, quantised first as Vec3::to_rgb_u8), the range term (0 = computed as the reference).
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RtwBilateral { pub size: u32, pub proximity: u32, pub in_format: u32, pub avg_gradient: f32 }
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct RtwFilterStats { pub avg_gradient: f32, pub spatial: f32, pub gradient_ms: f32, pub table_ms: f32, pub filter_ms: f32,
+    pub total_ms: f32, pub taps: u64 }
+/// Rust2 `ProximityType` (postprocessing.rs:12-15).
+#[repr(u32)] #[derive(Clone, Copy)]
+pub enum ProximityKind { Square = 0, Edges = 1 }
+/// Rust2 `Proximity::new(size, type)` (postprocessing.rs:23-29); size <= 64.
+#[derive(Clone, Copy)]
+pub struct Proximity { pub size: u32, pub kind: ProximityKind }
+impl Proximity { pub fn new(size: u32, kind: ProximityKind) -> Self { Self { size, kind } } }
+
 #[repr(C)] pub struct RtwCtx { _private: [u8; 0] }
 #[repr(C)] pub struct RtwMgpu { _private: [u8; 0] }
 
@@ -76,6 +91,9 @@ extern "C" {
                                  per_texture: *const RtwTextureNoise, n_textures: u32) -> i32;
     fn rtw_mgpu_set_texture_noise(m: *mut RtwMgpu, tables: *const RtwPerlin, n_tables: u32,
                                   per_texture: *const RtwTextureNoise, n_textures: u32) -> i32;
+    fn rtw_bilateral_filter(img: *const c_void, w: u32, h: u32, p: *const RtwBilateral, out: *mut u8, st: *mut RtwFilterStats) -> i32;
+    fn rtw_ctx_bilateral_filter(ctx: *mut RtwCtx, img: *const c_void, w: u32, h: u32, p: *const RtwBilateral, out: *mut u8,
+                                st: *mut RtwFilterStats) -> i32;
     fn rtw_mgpu_render(m: *mut RtwMgpu, cam: *const RtwCamera, p: *const RtwParams, out_rgb: *mut c_void,
                        per_device: *mut RtwStats, total: *mut RtwStats) -> i32;
 }
@@ -131,6 +149,14 @@ impl Renderer {
         let mut out = vec![0f32; points.len()];
         check(unsafe { rtw_ctx_perlin_eval(self.ctx, t, points.as_ptr() as *const f32, points.len() as u32, turb_depth, out.as_mut_ptr()) })?;
         Ok(out)
+    }
+    /// Rust2 `bilateral_filter` on this context's GPU: `rgb` is [h][w][3] u8 (`ImageBuffer<Rgb<u8>>::as_raw()`) or, with
+    /// in_format 1, the f32 frame of `render` flattened; bit-identical to the reference.
+    pub fn bilateral_filter(&mut self, rgb: *const c_void, w: u32, h: u32, p: &RtwBilateral) -> Result<(Vec<u8>, RtwFilterStats), RtwError> {
+        let mut out = vec![0u8; w as usize * h as usize * 3];
+        let mut st = RtwFilterStats::default();
+        check(unsafe { rtw_ctx_bilateral_filter(self.ctx, rgb, w, h, p, out.as_mut_ptr(), &mut st) })?;
+        Ok((out, st))
     }
     /// Tuning knobs (`RTW_OPT_*` of rtw.h: 1 chunk length, 2 sample bank GiB, 3 LDS geometry, 4 workgroups per CU, 5 list-walk
     /// threshold); none of them changes the image.
@@ -219,3 +245,25 @@ impl RtwPerlin {
 pub unsafe fn mgpu_set_texture_noise(m: *mut RtwMgpu, tables: &[RtwPerlin], per_texture: &[RtwTextureNoise]) -> i32 {
     rtw_mgpu_set_texture_noise(m, tables.as_ptr(), tables.len() as u32, per_texture.as_ptr(), per_texture.len() as u32)
 }
+
+/// rtw_bilateral_filter: the library's host form of Rust2's `bilateral_filter` on a [h][w][3] u8 image.
+pub fn bilateral_filter_host(rgb: &[u8], w: u32, h: u32, proximity: Proximity) -> Result<Vec<u8>, RtwError> {
+    let p = RtwBilateral { size: proximity.size, proximity: proximity.kind as u32, in_format: 0, avg_gradient: 0.0 };
+    let mut out = vec![0u8; rgb.len()];
+    check(unsafe { rtw_bilateral_filter(rgb.as_ptr() as *const c_void, w, h, &p, out.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok(out)
+}
+
+/// Rust2 `bilateral_filter(img, proximity)` on GPU 0 for a [h][w][3] u8 image (`Img::as_raw()`), bit-identical to the reference.
+pub fn bilateral_filter_gpu(rgb: &[u8], w: u32, h: u32, proximity: Proximity) -> Result<Vec<u8>, RtwError> {
+    let p = RtwBilateral { size: proximity.size, proximity: proximity.kind as u32, in_format: 0, avg_gradient: 0.0 };
+    Ok(Renderer::new(0)?.bilateral_filter(rgb.as_ptr() as *const c_void, w, h, &p)?.0)
+}
+
+// In the reference crate (Rust2/src/postprocessing.rs, next to `bilateral_filter`), with its `Img` type:
+//
+// pub(crate) fn bilateral_filter_gpu(img: &Img, proximity: Proximity) -> Result<Img, RtwError> {
+//     let (w, h) = img.dimensions();
+//     let raw = rtw::bilateral_filter_gpu(img.as_raw(), w, h, proximity)?;
+//     Ok(ImageBuffer::from_raw(w, h, raw).unwrap())
+// }

@@ -354,6 +354,43 @@ int rtw_ctx_set_texture_noise(rtw_ctx *ctx, const RtwPerlin *tables, uint32_t n_
 int rtw_mgpu_set_texture_noise(rtw_mgpu *m, const RtwPerlin *tables, uint32_t n_tables,
                                const RtwTextureNoise *per_texture, uint32_t n_textures);
 
+/* ---- bilateral filter of a frame (Rust2/src/postprocessing.rs:12-131) -----------------------------------------------------------
+ * `bilateral_filter(img, Proximity::new(size, Square | Edges))`, the post-process Rust2 runs on the 8-bit image of render_rows_async
+ * (postprocessing.rs:444-447), reproduced bit for bit: spatial = ceil(0.02 sqrt(w*w + h*h)); the range term is the mean of the
+ * intensity gradient over the interior pixels, summed serially in the reference's order (rows outer, columns inner); the window of a
+ * pixel is x - min(x, size) .. x + min(w-x-1, size) by y - min(y, size) .. y + min(h-y-1, size), both half-open (the neighbours at +size
+ * are never taken), column outer, row inner; Edges keeps the taps with |dx| + |dy| < size.  Every weight is libm expf of an argument
+ * that depends only on (dx*dx + dy*dy, |channel difference|): the library tabulates them on the host and the device looks them up.
+ * The output byte is `(col_sum * 255 / w_sum) as u8` (truncated, saturated, NaN -> 0): a uniform image (mean gradient 0) and size 0
+ * come out all zeros, as in the reference.
+ * img / out are [h][w][3], row-major; w >= 3, h >= 3 (the reference's (w-2)*(h-2) underflows below), w*w + h*h must fit in u32, and
+ * size <= RTW_BILATERAL_MAX_SIZE (the window holds (2 size)^2 taps; larger sizes return RTW_E_INVALID). */
+#define RTW_BILATERAL_MAX_SIZE 64u
+enum { RTW_PROXIMITY_SQUARE = 0, RTW_PROXIMITY_EDGES = 1 };          /* ProximityType (postprocessing.rs:12-15) */
+enum { RTW_PIXELS_U8 = 0,                                            /* [h][w][3] uint8_t                                           */
+       RTW_PIXELS_F32_RUST2 = 1 };                                   /* [h][w][3] float, quantised first as rtw_quantize_u8_rust2 */
+typedef struct RtwBilateral {
+    uint32_t size;                  /* Proximity.size, 0 .. RTW_BILATERAL_MAX_SIZE                                   */
+    uint32_t proximity;             /* RTW_PROXIMITY_SQUARE | RTW_PROXIMITY_EDGES                                    */
+    uint32_t in_format;             /* RTW_PIXELS_U8 | RTW_PIXELS_F32_RUST2                                          */
+    float    avg_gradient;          /* 0 = computed as the reference does; > 0 (finite) = used as given, the gradient pass is skipped */
+} RtwBilateral;
+typedef struct RtwFilterStats {
+    float    avg_gradient;          /* the range term used (computed or given)                                      */
+    float    spatial;               /* ceil(0.02 sqrt(w*w + h*h))                                                    */
+    float    gradient_ms;           /* device: the gradient terms and their serial sum (0 when skipped); host: the serial sum */
+    float    table_ms;              /* host time to build the weight table (and, on the device path, to enqueue its upload) */
+    float    filter_ms;             /* device: the filter kernel (hipEvent); host: the per-pixel loop                 */
+    float    total_ms;              /* host wall time of the call                                                    */
+    uint64_t taps;                  /* window entries evaluated over the whole image (each is 3 weights)             */
+} RtwFilterStats;
+/* The host form (the library's CPU path, the same table and serial sum; threads over rows). */
+int rtw_bilateral_filter(const void *in, uint32_t w, uint32_t h, const RtwBilateral *params, uint8_t *out, RtwFilterStats *stats);
+/* On ctx's GPU, on its stream, blocking.  `in` and `out` may be host memory or device memory of ctx's GPU.  Needs no scene and leaves
+ * the scene, and every render, untouched.  stats may be NULL. */
+int rtw_ctx_bilateral_filter(rtw_ctx *ctx, const void *in, uint32_t w, uint32_t h, const RtwBilateral *params, uint8_t *out,
+                             RtwFilterStats *stats);
+
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 
 /* Viewport::new (viewport.rs:308-401).  Options the reference takes as Option<> are pointers

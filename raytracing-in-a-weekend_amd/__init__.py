@@ -16,6 +16,7 @@ Reference surface mirrored (names and argument meaning):
   METALLIC_M, SCATTER_M, FUZZY3_M, GLASS_M, GLASSR_M   Rust/src/objects/materials.rs:157-212
   PerlinNoise.new / noise / turb / value    Rust/src/texture.rs:61-194
   ImageTexture::from_color_noise / new_with_noise      Rust/src/texture.rs:228-245 (texture_from_color_noise, texture_with_noise)
+  bilateral_filter(img, Proximity::new(size, type))  Rust2/src/postprocessing.rs:12-131 (bilateral_filter; Renderer.bilateral_filter)
 
 The directory name carries a hyphen (it is fixed by the build contract); import it with
 ``importlib.import_module("raytracing-in-a-weekend_amd")`` or through the ``rtw_amd`` alias module
@@ -43,6 +44,9 @@ OPT_CHUNK_LEN, OPT_SAMPLE_BANK_GB, OPT_LDS_GEOM, OPT_BLOCKS_PER_CU, OPT_LIST_WAL
 OPT_TAIL_UNITS = 9
 SCENE_C1, SCENE_C2, SCENE_C4, SCENE_C5, SCENE_METAL_TEST, SCENE_QUAD_TEST, SCENE_PRESENTATION, SCENE_FIRST_FRAME = 1, 2, 4, 5, 6, 7, 8, 9
 MEDIUM_SURFACE, MEDIUM_CONST_DENSITY = 0, 1
+PROXIMITY_SQUARE, PROXIMITY_EDGES = 0, 1             # Rust2 ProximityType (postprocessing.rs:12-15)
+PIXELS_U8, PIXELS_F32_RUST2 = 0, 1                   # RtwBilateral.in_format
+BILATERAL_MAX_SIZE = 64
 
 # materials.rs:157-212 presets as (metallicness, opacity, ir)
 METALLIC_M = (1.0, 0.0, 1.0)
@@ -126,6 +130,19 @@ class RtwTextureNoise(C.Structure):
     _fields_ = [("perlin", C.c_int32), ("scale", C.c_float)]
 
 
+class RtwBilateral(C.Structure):
+    """Arguments of the bilateral post-process: Proximity{size, type}, the input's format, the range term (0 = computed)."""
+    _fields_ = [("size", C.c_uint32), ("proximity", C.c_uint32), ("in_format", C.c_uint32), ("avg_gradient", C.c_float)]
+
+
+class RtwFilterStats(C.Structure):
+    _fields_ = [("avg_gradient", C.c_float), ("spatial", C.c_float), ("gradient_ms", C.c_float), ("table_ms", C.c_float),
+                ("filter_ms", C.c_float), ("total_ms", C.c_float), ("taps", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -196,6 +213,9 @@ def lib() -> C.CDLL:
     L.rtw_ctx_perlin_eval.argtypes = [C.c_void_p, C.POINTER(RtwPerlin), fp, C.c_uint32, C.c_uint32, fp]
     L.rtw_ctx_set_texture_noise.argtypes = [C.c_void_p, C.POINTER(RtwPerlin), C.c_uint32, C.POINTER(RtwTextureNoise), C.c_uint32]
     L.rtw_mgpu_set_texture_noise.argtypes = [C.c_void_p, C.POINTER(RtwPerlin), C.c_uint32, C.POINTER(RtwTextureNoise), C.c_uint32]
+    L.rtw_bilateral_filter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwBilateral), C.c_void_p, C.POINTER(RtwFilterStats)]
+    L.rtw_ctx_bilateral_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwBilateral), C.c_void_p,
+                                           C.POINTER(RtwFilterStats)]
     _lib = L
     return L
 
@@ -654,6 +674,36 @@ class Renderer:
         """Tuning knobs (OPT_*); none of them changes the image."""
         _check(lib().rtw_ctx_set_option(self._h, int(key), float(value)), "rtw_ctx_set_option")
 
+    def bilateral_filter(self, img, size: int, proximity: int = PROXIMITY_SQUARE, avg_gradient: float = 0.0, out=None, shape=None,
+                         in_format: Optional[int] = None):
+        """Rust2's `bilateral_filter(img, Proximity::new(size, proximity))` on this context's GPU (rtw_ctx_bilateral_filter).
+        `img`: a numpy [h][w][3] uint8 array, or float32 (quantised first with Rust2's rule, as quantize_u8_rust2); or an int device
+        pointer (e.g. torch_tensor.data_ptr()) with shape=(h, w) and in_format PIXELS_U8 / PIXELS_F32_RUST2.  `out` as in render():
+        None -> new numpy uint8 array, numpy array -> host buffer, int -> device pointer of [h][w][3] uint8.  Returns (out, RtwFilterStats)."""
+        if isinstance(img, np.ndarray):
+            fmt = _pixel_format(img) if in_format is None else int(in_format)
+            a = np.ascontiguousarray(img, np.uint8 if fmt == PIXELS_U8 else np.float32)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"bilateral_filter: image of shape {a.shape}, expected [h][w][3]")
+            h, w = a.shape[:2]
+            src = C.c_void_p(a.ctypes.data)
+        else:
+            if shape is None or in_format is None:
+                raise ValueError("bilateral_filter: a device pointer needs shape=(h, w) and in_format")
+            h, w = (int(v) for v in shape)
+            fmt, src = int(in_format), C.c_void_p(int(img))
+        if out is None:
+            out = np.empty((h, w, 3), np.uint8)
+        if isinstance(out, np.ndarray):
+            assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size == h * w * 3
+            dst = C.c_void_p(out.ctypes.data)
+        else:
+            dst = C.c_void_p(int(out))
+        st = RtwFilterStats()
+        prm = RtwBilateral(int(size), int(proximity), fmt, float(avg_gradient))
+        _check(lib().rtw_ctx_bilateral_filter(self._h, src, w, h, C.byref(prm), dst, C.byref(st)), "rtw_ctx_bilateral_filter")
+        return out, st
+
     def render(self, cam: RtwCamera, params: RtwParams, out=None):
         """Render into `out`: None -> new numpy array; numpy array -> host buffer; int -> raw device pointer
         (e.g. torch_tensor.data_ptr()) of [rows][width][3] f32.  Returns (out, RtwStats)."""
@@ -751,6 +801,30 @@ def quantize_u8_rust2(img: np.ndarray) -> np.ndarray:
     out = np.empty(a.shape, np.uint8)
     lib().rtw_quantize_u8_rust2(a.ctypes.data_as(C.POINTER(C.c_float)), a.size, out.ctypes.data_as(C.POINTER(C.c_uint8)))
     return out
+
+
+def _pixel_format(img: np.ndarray) -> int:
+    if img.dtype == np.uint8:
+        return PIXELS_U8
+    if img.dtype == np.float32:
+        return PIXELS_F32_RUST2
+    raise ValueError(f"bilateral_filter: dtype {img.dtype}, expected uint8 or float32")
+
+
+def bilateral_filter(img: np.ndarray, size: int, proximity: int = PROXIMITY_SQUARE, avg_gradient: float = 0.0):
+    """Rust2's `bilateral_filter(img, Proximity::new(size, proximity))` (Rust2/src/postprocessing.rs:70-131) on the host
+    (rtw_bilateral_filter), bit for bit.  img: [h][w][3] uint8, or float32 quantised first as quantize_u8_rust2.  avg_gradient 0 computes
+    the range term as the reference does; a positive value is used as given.  Returns (uint8 [h][w][3], RtwFilterStats)."""
+    fmt = _pixel_format(np.asarray(img))
+    a = np.ascontiguousarray(img, np.uint8 if fmt == PIXELS_U8 else np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"bilateral_filter: image of shape {a.shape}, expected [h][w][3]")
+    out = np.empty(a.shape, np.uint8)
+    st = RtwFilterStats()
+    prm = RtwBilateral(int(size), int(proximity), fmt, float(avg_gradient))
+    _check(lib().rtw_bilateral_filter(C.c_void_p(a.ctypes.data), a.shape[1], a.shape[0], C.byref(prm), C.c_void_p(out.ctypes.data),
+                                      C.byref(st)), "rtw_bilateral_filter")
+    return out, st
 
 
 def write_img_f32(img: np.ndarray, filename: str):

@@ -3,6 +3,7 @@
 // without a HIP device every render entry point fails with RTW_E_NO_DEVICE / RTW_E_HIP.
 #include "rtw_kernels.h"
 #include "rtw_host.h"
+#include "rtw_filter.h"
 
 #include <link.h>
 
@@ -53,6 +54,7 @@ struct rtw_ctx {
     bool noise_active = false;           // a used texture has noise: renders take the noise build (SPEC 7)
     DevNoise noise{};                    // device tables / per-texture entries (null when no noise is set)
     void *d_perlin = nullptr, *d_tex_noise = nullptr;
+    FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
     // scratch
     uint32_t *d_queue = nullptr;
     unsigned long long *d_stats = nullptr;
@@ -258,6 +260,7 @@ void rtw_ctx_destroy(rtw_ctx *c) {
     if (c->ev_mark) (void)hipEventDestroy(c->ev_mark);
     if (c->d_samples) (void)hipFree(c->d_samples);
     if (c->d_order) (void)hipFree(c->d_order);
+    filter_scratch_free(c->filter);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -465,6 +468,13 @@ int rtw_ctx_perlin_eval(rtw_ctx *c, const RtwPerlin *t, const float *points, uin
     for (void *b : { d_t, d_p, d_o }) if (b) (void)hipFree(b);
     if (e != hipSuccess) { g_last_hip = (int)e; return alloc_failed ? RTW_E_NOMEM : RTW_E_HIP; }
     return RTW_OK;
+}
+
+// The bilateral post-process (rtw_filter.hip) on this context's GPU and stream; the scene is not involved.
+int rtw_ctx_bilateral_filter(rtw_ctx *c, const void *in, uint32_t w, uint32_t h, const RtwBilateral *p, uint8_t *out, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return bilateral_filter_device(c->device, c->stream, &c->filter, in, w, h, p, out, stats, &g_last_hip);
 }
 
 } // extern "C"
