@@ -19,6 +19,12 @@ pub struct RtwTexture { pub row: u32, pub col: u32, pub texel_offset: u32, pub e
 pub struct RtwQuad { pub origin: [f32; 3], pub u: [f32; 3], pub v: [f32; 3], pub velocity: [f32; 3], pub tex_color: [f32; 3],
     pub metallicness: f32, pub opacity: f32, pub ir: f32, pub emitted: [f32; 3], pub tex: i32 }
 
+/// Rust2 `Triangle` (Rust2/src/objects/triangle.rs:12-50) + its Material; normal / d / w (Triangle::new) are written by
+/// `Triangle::new` and recomputed by the library wherever it reads triangles.
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RtwTriangle { pub origin: [f32; 3], pub u: [f32; 3], pub v: [f32; 3], pub normal: [f32; 3], pub d: f32, pub w: [f32; 3],
+    pub tex_color: [f32; 3], pub metallicness: f32, pub opacity: f32, pub ir: f32, pub emitted: [f32; 3], pub tex: i32 }
+
 /// `Instance` (objects/instance.rs:27-38): member ranges into the scene's instance pools; medium 1 = const_density.
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct RtwInstance { pub first_sphere: u32, pub n_spheres: u32, pub first_quad: u32, pub n_quads: u32,
@@ -94,6 +100,14 @@ extern "C" {
     fn rtw_bilateral_filter(img: *const c_void, w: u32, h: u32, p: *const RtwBilateral, out: *mut u8, st: *mut RtwFilterStats) -> i32;
     fn rtw_ctx_bilateral_filter(ctx: *mut RtwCtx, img: *const c_void, w: u32, h: u32, p: *const RtwBilateral, out: *mut u8,
                                 st: *mut RtwFilterStats) -> i32;
+    fn rtw_triangle_new(origin: *const f32, u: *const f32, v: *const f32, mat3: *const f32, emitted: *const f32,
+                        color: *const f32, tex: i32, out: *mut RtwTriangle) -> i32;
+    fn rtw_ctx_set_triangles(ctx: *mut RtwCtx, tris: *const RtwTriangle, n: u32) -> i32;
+    fn rtw_mgpu_set_triangles(m: *mut RtwMgpu, tris: *const RtwTriangle, n: u32) -> i32;
+    fn rtw_triangle_hits(tris: *const RtwTriangle, n: u32, rays: *const f32, n_rays: u32, mint: f32, maxt: f32,
+                         t_out: *mut f32, idx_out: *mut i32) -> i32;
+    fn rtw_ctx_triangle_hits(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, mint: f32, maxt: f32, accel: u32,
+                             t_out: *mut f32, idx_out: *mut i32, stats: *mut RtwStats) -> i32;
     fn rtw_mgpu_render(m: *mut RtwMgpu, cam: *const RtwCamera, p: *const RtwParams, out_rgb: *mut c_void,
                        per_device: *mut RtwStats, total: *mut RtwStats) -> i32;
 }
@@ -143,6 +157,19 @@ impl Renderer {
     pub fn set_texture_noise(&mut self, tables: &[RtwPerlin], per_texture: &[RtwTextureNoise]) -> Result<(), RtwError> {
         let (t, pt) = if per_texture.is_empty() { (std::ptr::null(), std::ptr::null()) } else { (tables.as_ptr(), per_texture.as_ptr()) };
         check(unsafe { rtw_ctx_set_texture_noise(self.ctx, t, tables.len() as u32, pt, per_texture.len() as u32) })
+    }
+    /// Rust2 triangles of the scene just set (an empty slice clears them); set_scene clears them.  Builds their tree: RTW_ACCEL_BVH
+    /// renders use it, RTW_ACCEL_BRUTE renders walk the list -- the same image.  Refused (RTW_E_UNSUPPORTED) while texture noise is set.
+    pub fn set_triangles(&mut self, tris: &[RtwTriangle]) -> Result<(), RtwError> {
+        let p = if tris.is_empty() { std::ptr::null() } else { tris.as_ptr() };
+        check(unsafe { rtw_ctx_set_triangles(self.ctx, p, tris.len() as u32) })
+    }
+    /// The closest of this context's triangles per ray ([origin, direction]) on its GPU: (t, index or -1) per ray.
+    pub fn triangle_hits(&mut self, rays: &[[f32; 6]], mint: f32, maxt: f32, accel: u32) -> Result<(Vec<f32>, Vec<i32>), RtwError> {
+        let (mut t, mut i) = (vec![0f32; rays.len()], vec![0i32; rays.len()]);
+        check(unsafe { rtw_ctx_triangle_hits(self.ctx, rays.as_ptr() as *const f32, rays.len() as u32, mint, maxt, accel,
+                                             t.as_mut_ptr(), i.as_mut_ptr(), std::ptr::null_mut()) })?;
+        Ok((t, i))
     }
     /// PerlinNoise::noise (turb_depth 0) / turb(p, turb_depth) at `points` on this context's GPU.
     pub fn perlin_eval(&mut self, t: &RtwPerlin, points: &[[f32; 3]], turb_depth: u32) -> Result<Vec<f32>, RtwError> {
@@ -255,6 +282,23 @@ pub fn bilateral_filter_host(rgb: &[u8], w: u32, h: u32, proximity: Proximity) -
 }
 
 /// Rust2 `bilateral_filter(img, proximity)` on GPU 0 for a [h][w][3] u8 image (`Img::as_raw()`), bit-identical to the reference.
+impl RtwTriangle {
+    /// Rust2 `Triangle::new(origin, u, v, mat, ConstColorTexture(color))` (tex = -1) or with `textures[tex]`.
+    pub fn new(origin: [f32; 3], u: [f32; 3], v: [f32; 3], mat3: [f32; 3], emitted: [f32; 3], color: [f32; 3], tex: i32) -> Result<Self, RtwError> {
+        let mut t = RtwTriangle::default();
+        check(unsafe { rtw_triangle_new(origin.as_ptr(), u.as_ptr(), v.as_ptr(), mat3.as_ptr(), emitted.as_ptr(), color.as_ptr(), tex, &mut t) })?;
+        Ok(t)
+    }
+}
+
+/// The closest triangle per ray on the host (the list walk): (t, index or -1) per ray.
+pub fn triangle_hits(tris: &[RtwTriangle], rays: &[[f32; 6]], mint: f32, maxt: f32) -> Result<(Vec<f32>, Vec<i32>), RtwError> {
+    let (mut t, mut i) = (vec![0f32; rays.len()], vec![0i32; rays.len()]);
+    check(unsafe { rtw_triangle_hits(tris.as_ptr(), tris.len() as u32, rays.as_ptr() as *const f32, rays.len() as u32, mint, maxt,
+                                     t.as_mut_ptr(), i.as_mut_ptr()) })?;
+    Ok((t, i))
+}
+
 pub fn bilateral_filter_gpu(rgb: &[u8], w: u32, h: u32, proximity: Proximity) -> Result<Vec<u8>, RtwError> {
     let p = RtwBilateral { size: proximity.size, proximity: proximity.kind as u32, in_format: 0, avg_gradient: 0.0 };
     Ok(Renderer::new(0)?.bilateral_filter(rgb.as_ptr() as *const c_void, w, h, &p)?.0)

@@ -216,7 +216,7 @@ typedef struct RtwStats {
     uint64_t camera_rays;    /* (pixel, sample) primary rays traced                   */
     uint64_t segments;       /* closest-hit queries == BASELINE "rays x bounces"      */
     uint64_t sphere_tests;   /* exact ray/sphere quadratic evaluations                */
-    uint64_t node_tests;     /* BVH node slab tests (0 for RTW_ACCEL_BRUTE)           */
+    uint64_t node_tests;     /* BVH node slab tests (0 for RTW_ACCEL_BRUTE); with triangles also the triangle-tree node visits */
     uint32_t nan_pixels;     /* output pixels with a NaN channel                      */
     uint32_t rows;           /* rows written by this call                             */
     float    kernel_ms;      /* device time of the render kernels (hipEvent)          */
@@ -225,7 +225,7 @@ typedef struct RtwStats {
      * experimental phases) and the lanes that were live in them; lanes / (64 * steps) is the SIMD efficiency of a phase. */
     uint64_t phase_steps[6];
     uint64_t phase_lanes[6];
-    uint64_t quad_tests;     /* ray/quad plane tests (top-level quads and instance members) */
+    uint64_t quad_tests;     /* ray/quad plane tests (top-level quads and instance members) and ray/triangle plane tests */
     /* v4: the call's timeline.  enqueue_ms: host time from the begin of the call (rtw_mgpu_render: of the whole call, the same instant for
      * every device) until this context's kernels had been issued; start_ms: device time from a marker recorded on this context's stream at
      * the begin of the call (before any device was given work) to the start of its first kernel.  A fork that is asynchronous shows
@@ -390,6 +390,60 @@ int rtw_bilateral_filter(const void *in, uint32_t w, uint32_t h, const RtwBilate
  * the scene, and every render, untouched.  stats may be NULL. */
 int rtw_ctx_bilateral_filter(rtw_ctx *ctx, const void *in, uint32_t w, uint32_t h, const RtwBilateral *params, uint8_t *out,
                              RtwFilterStats *stats);
+
+/* ---- Rust2 triangles (Rust2/src/objects/triangle.rs) ----------------------------------------------------------------------------
+ * `Triangle{origin, u, v, mat, texture}` with the derived fields of Triangle::new (:28-50): n = u x v, normal = unit(n),
+ * d = normal . origin, w = n / (n . n); the hit test of get_hit (:95-124) restated operation by operation in f32: reject when
+ * |normal . dir| <= 1e-8 or t < mint || t > maxt (t = (d - normal . o) / (normal . dir)); point = o + dir t, planar = point - origin,
+ * alfa = w . (planar x v), beta = w . (u x planar), reject when alfa < 0 || beta < 0 || alfa + beta > 1.  The normal is never flipped.
+ * NaN falls through as in the reference: a degenerate triangle (u x v == 0) has a NaN normal and reports a NaN-t hit for every ray.
+ * Extension of this library (Rust/ has no triangles): Scene::collision_normal stays spheres, quads, instances; the triangles come LAST, as
+ * one more group: the closest triangle in list order (a later one replaces the current one only when strictly closer, the quad rule), and
+ * that one replaces the result so far only when strictly closer.  Material inline as in RtwQuad; no velocity (Rust2's triangle has none).
+ * tex < 0: the constant colour tex_color; tex >= 0 under RTW_INTEGRATOR_RUST2: Rust2's ImageTexture::color_at(alfa, beta)
+ * (Rust2/src/objects/texture.rs:94-105, emission image from RtwTexture.emit_tex, else `emitted`); under every other integrator the
+ * quad's texel rule at (alfa, beta).  The derived fields are written by rtw_triangle_new and recomputed by the library from origin /
+ * u / v wherever it reads triangles (rtw_ctx_set_triangles, rtw_triangle_hits). */
+typedef struct RtwTriangle {
+    float origin[3];
+    float u[3];
+    float v[3];
+    float normal[3];      /* derived: unit(u x v)        */
+    float d;              /* derived: normal . origin    */
+    float w[3];           /* derived: n / (n . n)        */
+    float tex_color[3];
+    float metallicness;
+    float opacity;
+    float ir;
+    float emitted[3];
+    int32_t tex;          /* index into RtwScene.textures, or -1 */
+} RtwTriangle;
+/* Triangle::new with ConstColorTexture(color) (tex = -1) or textures[tex]: mat3 == NULL -> the quad default, emitted == NULL -> 0. */
+int rtw_triangle_new(const float origin[3], const float u[3], const float v[3], const float *mat3, const float *emitted,
+                     const float color[3], int32_t tex, RtwTriangle *out);
+/* The triangles of the scene of the last rtw_ctx_set_scene (which clears them): uploads them and builds their BVH (a binned-SAH tree, leaves
+ * of <= 4 triangles, global memory).  tris == NULL with n == 0 clears them.  RTW_E_NO_SCENE before any scene; RTW_E_INVALID for a tex
+ * beyond the scene's textures; RTW_E_UNSUPPORTED while texture noise is set (and rtw_ctx_set_texture_noise with triangles set fails alike).
+ * RTW_ACCEL_BRUTE renders walk the triangle list, RTW_ACCEL_BVH renders use the tree -- the same image bit for bit (DESIGN.md "Rust2
+ * triangles"): the tree only prunes, with boxes inflated by the rounding bound, ties to the lower index.  Where that bound cannot hold the
+ * list is walked instead: a triangle with a non-finite derived field, a coordinate beyond 2^40, |w| beyond 2^40 or an ill-conditioned shape
+ * (max(|u|,|v|)^2 / |u x v| > 256); non-finite mint / maxt or beyond 2^40; per ray, an origin or direction that is not finite or with
+ * |o| + |d| max(|mint|, |maxt|) beyond 2^40.  RtwStats.quad_tests counts the triangle tests too, RtwStats.node_tests the triangle-tree node
+ * visits.  The one-shot rtw_render / rtw_render_multi_gpu carry no triangles. */
+int rtw_ctx_set_triangles(rtw_ctx *ctx, const RtwTriangle *tris, uint32_t n);
+int rtw_mgpu_set_triangles(rtw_mgpu *m, const RtwTriangle *tris, uint32_t n);
+/* Host self-check of the tree rtw_ctx_set_triangles builds (no GPU): every triangle reachable exactly once, each leaf box contains its
+ * triangles' inflated boxes, each node box its children's, skip links well formed.  RTW_OK or RTW_E_INVALID.  Optional outputs: node count,
+ * depth, and list_walk = 1 when the triangles fall back to the list walk (a condition above). */
+int rtw_triangle_bvh_validate(const RtwTriangle *tris, uint32_t n, uint32_t *n_nodes, uint32_t *depth, uint32_t *list_walk);
+/* Closest-hit queries against the triangles alone, for tests and tools.  rays: [n_rays][6] = origin, direction.  t_out[i] = the t of the
+ * closest triangle (the group rule above), idx_out[i] = its index in the list, or -1 (t_out = +inf) when none.  The host form walks the list;
+ * the device form runs the device functions the render kernels call on the context's triangles, the list walk (RTW_ACCEL_BRUTE) or the
+ * tree (RTW_ACCEL_BVH); host buffers in and out, blocking.  RTW_E_NO_SCENE when the context has no triangles. */
+int rtw_triangle_hits(const RtwTriangle *tris, uint32_t n, const float *rays, uint32_t n_rays, float mint, float maxt,
+                      float *t_out, int32_t *idx_out);
+int rtw_ctx_triangle_hits(rtw_ctx *ctx, const float *rays, uint32_t n_rays, float mint, float maxt, uint32_t accel,
+                          float *t_out, int32_t *idx_out, RtwStats *stats);
 
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 

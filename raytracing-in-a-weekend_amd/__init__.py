@@ -17,6 +17,7 @@ Reference surface mirrored (names and argument meaning):
   PerlinNoise.new / noise / turb / value    Rust/src/texture.rs:61-194
   ImageTexture::from_color_noise / new_with_noise      Rust/src/texture.rs:228-245 (texture_from_color_noise, texture_with_noise)
   bilateral_filter(img, Proximity::new(size, type))  Rust2/src/postprocessing.rs:12-131 (bilateral_filter; Renderer.bilateral_filter)
+  Triangle.new (+ from_mesh), Scene(triangles=)       Rust2/src/objects/triangle.rs:28-124 (triangle_hits; Renderer.triangle_hits)
 
 The directory name carries a hyphen (it is fixed by the build contract); import it with
 ``importlib.import_module("raytracing-in-a-weekend_amd")`` or through the ``rtw_amd`` alias module
@@ -84,6 +85,12 @@ class RtwTexture(C.Structure):
 class RtwQuad(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3), ("velocity", C.c_float * 3),
                 ("tex_color", C.c_float * 3), ("metallicness", C.c_float), ("opacity", C.c_float), ("ir", C.c_float),
+                ("emitted", C.c_float * 3), ("tex", C.c_int32)]
+
+
+class RtwTriangle(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3), ("normal", C.c_float * 3), ("d", C.c_float),
+                ("w", C.c_float * 3), ("tex_color", C.c_float * 3), ("metallicness", C.c_float), ("opacity", C.c_float), ("ir", C.c_float),
                 ("emitted", C.c_float * 3), ("tex", C.c_int32)]
 
 
@@ -216,6 +223,13 @@ def lib() -> C.CDLL:
     L.rtw_bilateral_filter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwBilateral), C.c_void_p, C.POINTER(RtwFilterStats)]
     L.rtw_ctx_bilateral_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwBilateral), C.c_void_p,
                                            C.POINTER(RtwFilterStats)]
+    L.rtw_triangle_new.argtypes = [fp, fp, fp, fp, fp, fp, C.c_int32, C.POINTER(RtwTriangle)]
+    L.rtw_ctx_set_triangles.argtypes = [C.c_void_p, C.POINTER(RtwTriangle), C.c_uint32]
+    L.rtw_mgpu_set_triangles.argtypes = [C.c_void_p, C.POINTER(RtwTriangle), C.c_uint32]
+    L.rtw_triangle_bvh_validate.argtypes = [C.POINTER(RtwTriangle), C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
+    L.rtw_triangle_hits.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, fp, C.c_uint32, C.c_float, C.c_float, fp, C.POINTER(C.c_int32)]
+    L.rtw_ctx_triangle_hits.argtypes = [C.c_void_p, fp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, fp, C.POINTER(C.c_int32),
+                                        C.POINTER(RtwStats)]
     _lib = L
     return L
 
@@ -294,6 +308,128 @@ class Quad:
                                   _fptr(_f3(color)), C.byref(q)), "rtw_quad_new")
         q.tex = int(tex_index)
         return Quad(q)
+
+
+class Triangle:
+    """Rust2's `Triangle` (Rust2/src/objects/triangle.rs:12-50) with its material and ConstColorTexture / ImageTexture inline."""
+
+    def __init__(self, pod: RtwTriangle):
+        self.pod = pod
+
+    @staticmethod
+    def new(origin, u, v, mat=None, color=(1.0, 1.0, 1.0), emitted=None, tex_index: int = -1) -> "Triangle":
+        t = RtwTriangle()
+        _check(lib().rtw_triangle_new(_fptr(_f3(origin)), _fptr(_f3(u)), _fptr(_f3(v)), _fptr(_f3(mat)), _fptr(_f3(emitted)),
+                                      _fptr(_f3(color)), int(tex_index), C.byref(t)), "rtw_triangle_new")
+        return Triangle(t)
+
+    @staticmethod
+    def from_mesh(vertices, faces, mat=None, color=(1.0, 1.0, 1.0), emitted=None, tex_index: int = -1) -> "TriangleArray":
+        """An indexed mesh as triangles: face (a, b, c) -> origin = v[a], u = v[b] - v[a], v = v[c] - v[a] (f32).  One material for all."""
+        vtx = np.asarray(vertices, np.float32).reshape(-1, 3)
+        f = np.asarray(faces, np.int64).reshape(-1, 3)
+        if len(f) and (f.min() < 0 or f.max() >= len(vtx)):
+            raise ValueError("from_mesh: a face index is outside the vertex array")
+        o = vtx[f[:, 0]]
+        return TriangleArray(o, vtx[f[:, 1]] - o, vtx[f[:, 2]] - o, mat, color, emitted, tex_index)
+
+
+class TriangleArray:
+    """Many triangles as one ctypes array of RtwTriangle, one material for all.  The derived fields (normal, d, w) are left 0: the library
+    recomputes them wherever it reads triangles (rtw.h); Triangle.new fills them."""
+
+    def __init__(self, origin, u, v, mat=None, color=(1.0, 1.0, 1.0), emitted=None, tex_index: int = -1):
+        o, uu, vv = (np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (origin, u, v))
+        n = len(o)
+        self.n = n
+        self.arr = (RtwTriangle * max(1, n))()
+        rec = np.frombuffer(self.arr, dtype=np.float32, count=max(1, n) * (C.sizeof(RtwTriangle) // 4)).reshape(max(1, n), -1)
+        m = np.asarray(mat if mat is not None else SCATTER_M, np.float32)
+        rec[:n, 0:3], rec[:n, 3:6], rec[:n, 6:9] = o, uu, vv
+        rec[:n, 16:19] = np.asarray(color, np.float32)
+        rec[:n, 19:22] = m
+        rec[:n, 22:25] = np.asarray(emitted if emitted is not None else (0.0, 0.0, 0.0), np.float32)
+        rec[:n, 25].view(np.int32)[:] = int(tex_index)
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        return Triangle(self.arr[i])
+
+
+def _triangle_array(triangles):
+    """(ctypes array of RtwTriangle, count) of a TriangleArray or a sequence of Triangle / RtwTriangle."""
+    if isinstance(triangles, TriangleArray):
+        return triangles.arr, triangles.n
+    pods = [t.pod if isinstance(t, Triangle) else t for t in triangles]
+    return (RtwTriangle * max(1, len(pods)))(*pods), len(pods)
+
+
+def _rays(rays):
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    if len(r) == 0:
+        raise ValueError("triangle_hits: no rays")
+    return r
+
+
+def triangle_hits(triangles, rays, mint: float, maxt: float):
+    """The closest triangle per ray on the host (rtw_triangle_hits, the list walk): rays [n][6] = origin, direction.
+    Returns (t [n] float32, +inf on a miss; index [n] int32, -1 on a miss)."""
+    arr, n = _triangle_array(triangles)
+    r = _rays(rays)
+    t = np.empty(len(r), np.float32)
+    idx = np.empty(len(r), np.int32)
+    _check(lib().rtw_triangle_hits(arr, n, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt),
+                                   t.ctypes.data_as(C.POINTER(C.c_float)), idx.ctypes.data_as(C.POINTER(C.c_int32))), "rtw_triangle_hits")
+    return t, idx
+
+
+def triangle_bvh_validate(triangles):
+    """rtw_triangle_bvh_validate: (status, n_nodes, depth, list_walk)."""
+    arr, n = _triangle_array(triangles)
+    nn, dp, lw = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    rc = lib().rtw_triangle_bvh_validate(arr, n, C.byref(nn), C.byref(dp), C.byref(lw))
+    return rc, nn.value, dp.value, lw.value
+
+
+def mesh_icosphere(level: int = 2, centre=(0.0, 0.0, 0.0), radius: float = 1.0):
+    """A subdivided icosahedron (20 * 4^level faces): (vertices [n][3] float32, faces [m][3] int64), outward winding."""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t),
+         (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    verts = [np.array(p, np.float64) / np.linalg.norm(p) for p in v]
+    for _ in range(int(level)):
+        cache, nf = {}, []
+
+        def mid(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in cache:
+                m = verts[a] + verts[b]
+                verts.append(m / np.linalg.norm(m))
+                cache[key] = len(verts) - 1
+            return cache[key]
+        for a, b, c in f:
+            ab, bc, ca = mid(a, b), mid(b, c), mid(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = nf
+    vtx = (np.array(verts) * float(radius) + np.asarray(centre, np.float64)).astype(np.float32)
+    return vtx, np.array(f, np.int64)
+
+
+def mesh_terrain(n_side: int, size: float = 20.0, height: float = 1.0, seed: int = 0, centre=(0.0, 0.0, 0.0)):
+    """A height field over an n_side x n_side grid of [-size/2, size/2]^2 in x/z (2 * n_side^2 faces, upward winding): a few smooth
+    waves plus seeded noise.  Returns (vertices, faces) as mesh_icosphere."""
+    rng = np.random.default_rng(seed)
+    xs = np.linspace(-size / 2, size / 2, n_side + 1)
+    X, Z = np.meshgrid(xs, xs, indexing="xy")
+    Y = height * (0.5 * np.sin(X * 0.7) * np.cos(Z * 0.5) + 0.3 * np.sin(X * 0.23 + Z * 0.31)) + 0.05 * height * rng.standard_normal(X.shape)
+    vtx = (np.stack([X, Y, Z], -1).reshape(-1, 3) + np.asarray(centre, np.float64)).astype(np.float32)
+    i = np.arange(n_side)
+    a = (i[:, None] * (n_side + 1) + i[None, :]).reshape(-1)
+    faces = np.concatenate([np.stack([a, a + n_side + 1, a + 1], 1), np.stack([a + 1, a + n_side + 1, a + n_side + 2], 1)])
+    return vtx, faces.astype(np.int64)
 
 
 class Instance:
@@ -395,11 +531,17 @@ class Scene:
     """`Scene` (Rust/src/viewport.rs:79-151): spheres (+ image textures), quads, instances, background colour."""
 
     def __init__(self, spheres: Sequence, textures: Sequence[np.ndarray] = (), background=(0.0, 0.0, 0.0),
-                 quads: Sequence = (), instances: Sequence = (), emission_images=None, noise=None):
+                 quads: Sequence = (), instances: Sequence = (), emission_images=None, noise=None, triangles=None):
         """`emission_images` {texture index: index of the texture that is its Rust2 `emmit_img`} (Rust2/src/objects/texture.rs:34-41;
         RTW_INTEGRATOR_RUST2 only).  `noise` {texture index: (PerlinNoise, noise_scale)}: ImageTexture.noise / noise_scale
         (texture.rs:21-27); Renderer / MultiRenderer.set_scene pass it on.  to_json drops it, as the reference's JSON form does."""
         self.noise = dict(noise or {})
+        # Rust2 triangles (a TriangleArray or a sequence of Triangle): not part of RtwScene -- Renderer / MultiRenderer.set_scene install them
+        # with rtw_ctx_set_triangles when there are some; to_json drops them (the reference's JSON has none)
+        self.triangles = None
+        self.n_triangles = 0
+        if triangles is not None and len(triangles):
+            self.triangles, self.n_triangles = _triangle_array(triangles)
         pods = [s.pod if isinstance(s, Sphere) else s for s in spheres]
         self._spheres = (RtwSphere * max(1, len(pods)))(*pods)
         self.n_spheres = len(pods)
@@ -657,6 +799,27 @@ class Renderer:
         nz = scene.noise_pods()
         if nz is not None:
             _check(lib().rtw_ctx_set_texture_noise(self._h, *nz), "rtw_ctx_set_texture_noise")
+        if scene.n_triangles:
+            _check(lib().rtw_ctx_set_triangles(self._h, scene.triangles, scene.n_triangles), "rtw_ctx_set_triangles")
+
+    def set_triangles(self, triangles=None):
+        """rtw_ctx_set_triangles for the current scene (None: clear them)."""
+        if triangles is None or len(triangles) == 0:
+            _check(lib().rtw_ctx_set_triangles(self._h, None, 0), "rtw_ctx_set_triangles")
+            return
+        self._tris = _triangle_array(triangles)
+        _check(lib().rtw_ctx_set_triangles(self._h, *self._tris), "rtw_ctx_set_triangles")
+
+    def triangle_hits(self, rays, mint: float, maxt: float, accel: int = ACCEL_BVH):
+        """The closest of this context's triangles per ray on its GPU (rtw_ctx_triangle_hits): (t, index, RtwStats) as triangle_hits."""
+        r = _rays(rays)
+        t = np.empty(len(r), np.float32)
+        idx = np.empty(len(r), np.int32)
+        st = RtwStats()
+        _check(lib().rtw_ctx_triangle_hits(self._h, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt), int(accel),
+                                           t.ctypes.data_as(C.POINTER(C.c_float)), idx.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st)),
+               "rtw_ctx_triangle_hits")
+        return t, idx, st
 
     def set_texture_noise(self, tables=None, n_tables: int = 0, per_texture=None, n_textures: int = 0):
         """rtw_ctx_set_texture_noise as is (no arguments: clear the noise of the current scene)."""
@@ -754,6 +917,16 @@ class MultiRenderer:
         nz = scene.noise_pods()
         if nz is not None:
             _check(lib().rtw_mgpu_set_texture_noise(self._h, *nz), "rtw_mgpu_set_texture_noise")
+        if scene.n_triangles:
+            _check(lib().rtw_mgpu_set_triangles(self._h, scene.triangles, scene.n_triangles), "rtw_mgpu_set_triangles")
+
+    def set_triangles(self, triangles=None):
+        """rtw_mgpu_set_triangles on every device (None: clear them)."""
+        if triangles is None or len(triangles) == 0:
+            _check(lib().rtw_mgpu_set_triangles(self._h, None, 0), "rtw_mgpu_set_triangles")
+            return
+        self._tris = _triangle_array(triangles)
+        _check(lib().rtw_mgpu_set_triangles(self._h, *self._tris), "rtw_mgpu_set_triangles")
 
     def set_option(self, key: int, value: float):
         _check(lib().rtw_mgpu_set_option(self._h, int(key), float(value)), "rtw_mgpu_set_option")

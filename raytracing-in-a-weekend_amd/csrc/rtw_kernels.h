@@ -1,6 +1,7 @@
 // rtw_kernels.h -- kernel argument block shared by rtw_kernels.hip (device) and rtw_shim.hip (host).
 #pragma once
 #include "rtw_device.h"
+#include "rtw_tri.h"
 #include "rtw_host.h"
 
 #define RTW_QUEUE_BYTES 4096u   // the work queue's counters (KArgs.queue): up to 8 sub-queues ...
@@ -76,12 +77,18 @@ struct KArgs {
     unsigned long long *stats;    // [0] camera rays [1] segments [2] sphere tests [3] node tests [4] nan pixels [5..7] phase steps [8..10] phase lanes [14] quad tests [16..19] steps, lanes of phases 3 (switch), 4 (new path)
     // (appended: the offsets of everything above, which the other builds read, stay where they were)
     DevNoise noise;               // texture noise (rtw_ctx_set_texture_noise); noise.tex != null selects the noise build (SPEC 7), which alone reads it
+    DevTris tris;                 // Rust2 triangles (rtw_ctx_set_triangles); tris.n != 0 selects the triangle build (SPEC 8), which alone reads it;
+                                  // tris.nodes == null: walk the triangle list
 };
 
 // accel: RTW_ACCEL_BRUTE, RTW_ACCEL_BVH; the BVH launch picks the LDS-resident variant when a.bvh.nodes16 != null
 void launch_render(const KArgs &a, bool moving, uint32_t accel, uint32_t grid, hipStream_t stream);
 // rtw_ctx_perlin_eval: out[i] = perlin_eval(*t, points[i], depth) for i < n (device pointers), on `stream`
 void launch_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t depth, float *out, hipStream_t stream);
+// rtw_ctx_triangle_hits: the closest triangle of T for each of n rays ([n][6] = o, d; device pointers), on `stream`; counters[0] triangle
+// tests, [1] node visits (device u64, accumulated)
+void launch_tri_hits(const DevTris &T, const float *rays, uint32_t n, float mint, float maxt, float *t_out, int32_t *idx_out,
+                     unsigned long long *counters, hipStream_t stream);
 // Resident workgroups per CU for the kernel variant (occupancy API), >= 1.
 uint32_t kernel_blocks_per_cu(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);
 // Is there a build of the BVH kernel for this configuration that reads the spheres' {centre, r^2} from LDS?  (KArgs.lds_geom_off may only be set then)

@@ -51,9 +51,12 @@ namespace rtw {
 // `Viewport::render` (viewport.rs:430-478: the reference's serial driver, quad_test's).  All three keep the generic build's step and fold the switches.
 // SPEC == 0 reads everything from the (wave-uniform) kernel arguments.  SPEC == 7 is SPEC == 0 plus the noise of image textures (texture.rs:
 // 259-267, rtw_ctx_set_texture_noise): the generic step with noise(p / scale) in place of the texel's `* 1.0`; only scenes with noise select it.
+// SPEC == 8 is SPEC == 0 plus Rust2's triangles (rtw_ctx_set_triangles): the closest-hit stage after the instances walks their list or tree;
+// only scenes with triangles select it.
 constexpr bool gradient_spec(int spec) { return spec >= 1 && spec <= 3; }
-constexpr bool generic_spec(int spec) { return spec == 0 || spec == 7; }
+constexpr bool generic_spec(int spec) { return spec == 0 || spec == 7 || spec == 8; }
 constexpr bool noise_spec(int spec) { return spec == 7; }
+constexpr bool tri_spec(int spec) { return spec == 8; }
 template <int SPEC> __device__ __forceinline__ uint32_t integ(const KArgs &A) {
     return SPEC == 5 ? (uint32_t)RTW_INTEGRATOR_RUST2 : SPEC == 4 ? (uint32_t)RTW_INTEGRATOR_BG_COLOR : !generic_spec(SPEC) ? (uint32_t)RTW_INTEGRATOR_GRADIENT : A.integrator;
 }
@@ -394,10 +397,19 @@ __device__ __forceinline__ void start_path_second(const Pixel &px, Path &pt, flo
 
 // Scenes with quads / instances (generic build only): finish Scene::collision_normal (viewport.rs:136-150) for
 // the query whose sphere part returned (best, best_t), then shade whichever object won.
+// SPEC 8: the triangles come last (their tests count as quad tests, their node visits go to the workgroup's counter, tri_node_counter).
 template <bool MOVING, int SPEC>
 __device__ __forceinline__ bool shade_geom(const KArgs &A, Path &pt, int best, float best_t, uint32_t &n_sph, uint32_t &n_quad) {
     GeomHit h;
-    if (geom_closest<noise_spec(SPEC)>(A.sc, A.noise, A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, pt.rng, h, n_sph, n_quad)) {
+    bool won = geom_closest<noise_spec(SPEC)>(A.sc, A.noise, A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, pt.rng, h, n_sph, n_quad);
+    if constexpr (tri_spec(SPEC)) {          // the triangles last (rtw.h): the closest one replaces the result so far when strictly closer
+        float tt;
+        uint32_t n_nodes = 0;
+        const int k = tri_closest(A.tris, pt.o, pt.d, A.mint, A.maxt, won || best >= 0, won ? h.t : best_t, tt, n_quad, n_nodes);
+        if (n_nodes) atomicAdd(tri_node_counter(A.tris), n_nodes);
+        if (k >= 0) { tri_record(A.sc, A.tris, (uint32_t)k, pt.o, pt.d, tt, integ<SPEC>(A) == RTW_INTEGRATOR_RUST2, h); won = true; }
+    }
+    if (won) {
         mat_derive(h.m);
         return shade_surface<SPEC>(A, pt, unit(pt.d), h.point, h.normal, h.cm, h.m, h.emitted);
     }
@@ -475,6 +487,16 @@ __device__ __forceinline__ void flush_tests(const KArgs &A, uint32_t n) {
     if ((threadIdx.x & 63u) == 0) atomicAdd(&A.stats[2], q);
 }
 
+// Triangle builds: the workgroup's node-visit counter (tri_node_counter) is zeroed before the loop and added to stats[3] after it
+__device__ __forceinline__ void tri_nodes_begin(const KArgs &A) {
+    if (threadIdx.x == 0) *tri_node_counter(A.tris) = 0u;
+    __syncthreads();
+}
+__device__ __forceinline__ void tri_nodes_end(const KArgs &A) {
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(&A.stats[3], (unsigned long long)*tri_node_counter(A.tris));
+}
+
 __device__ __forceinline__ void flush_quads(const KArgs &A, uint32_t n_quad) {
     unsigned long long q = n_quad;
     for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off);
@@ -541,6 +563,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? RTW_GEOM_BRUTE_WAVES : 1) void re
     Path pt; pt.o = pt.d = pt.L = mk(0, 0, 0); pt.thr = mk(1, 1, 1); pt.tm = 0; pt.k = 0; pt.poison = false; pt.rng.state = 0; pt.rng.inc = 1;
     uint32_t n_seg = 0, n_rays = 0, n_isph = 0, n_quad = 0;
     uint32_t trips = 0; bool aborted = false;
+    if constexpr (tri_spec(SPEC)) tri_nodes_begin(A);
 
     for (;;) {
         if (fetch_pixel(A, !have && !dead, px, dead, rs)) { have = true; newpath = true; }
@@ -563,6 +586,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? RTW_GEOM_BRUTE_WAVES : 1) void re
             }
         }
     }
+    if constexpr (tri_spec(SPEC)) tri_nodes_end(A);
     flush_counters(A, n_seg, n_rays, (unsigned long long)n_seg * A.sc.n + n_isph, 0);
     if (GEOM) flush_quads(A, n_quad);
     if (aborted && (threadIdx.x & 63u) == 0) atomicAdd(&A.stats[23], 1ull);
@@ -942,6 +966,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
         if (geom_in_lds) for (uint32_t i = threadIdx.x; i < sc.n; i += RTW_BLOCK) lgeom[i] = sc.geom[i];
         __syncthreads();
     }
+    if constexpr (tri_spec(SPEC)) tri_nodes_begin(A);
 
     // Lane flags live in ONE VGPR: as separate bools the compiler keeps them as lane masks in SGPR pairs and re-merges
     // every one of them under exec on every trip of the loop (3 SALU each), although only SHADE steps change them.
@@ -1196,6 +1221,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
         c_time[which] += __builtin_amdgcn_s_memtime() - t_begin;
 #endif
     }
+    if constexpr (tri_spec(SPEC)) tri_nodes_end(A);
     if (GEOM) { flush_quads(A, n_quad); flush_tests(A, n_isph); }
 #ifdef RTW_CENSUS
     for (int k = 0; k < CEN_N; k++) {          // diagnostic build: stats[32 + 2k] = wave-level executions of sub-block k, [33 + 2k] = lanes live in them
@@ -1289,6 +1315,8 @@ static kernel_fn pick_kernel(const KArgs &a, bool moving, uint32_t accel, bool l
     const int nodes = lds_nodes ? (a.lds_geom_off ? 2 : 1) : 0;
     // a texture that a sphere, quad or member uses has noise (rtw_shim.hip sets noise.tex only then): the noise build, for every integrator, sampler and flag
     if (a.noise.tex) return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<7>(moving, accel, nodes) : pick_kernel_spec<7>(moving, accel, nodes);
+    // triangles (rtw_shim.hip sets tris.n only then; never together with noise): the triangle build, for every integrator, sampler and flag
+    if (a.tris.n) return pick_kernel_geom<8>(moving, accel, nodes);
     if (a.geom.n_quads || a.geom.n_inst) {
 #ifndef RTW_GEOM_GENERIC_ONLY
         if (is_common_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<2>(moving, accel, nodes);
@@ -1319,7 +1347,29 @@ void launch_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uin
     hipLaunchKernelGGL(perlin_eval_kernel, dim3((n + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, t, points, n, depth, out);
 }
 
-bool kernel_has_lds_geom(const KArgs &a) { return !(a.geom.n_quads || a.geom.n_inst); }
+// The closest triangle per ray through tri_closest, the function the triangle build's closest-hit stage calls (rtw_ctx_triangle_hits)
+__global__ __launch_bounds__(RTW_BLOCK) void tri_hits_kernel(const DevTris T, const float *rays, uint32_t n, float mint, float maxt, float *t_out,
+                                                             int32_t *idx_out, unsigned long long *counters) {
+    const uint32_t i = blockIdx.x * RTW_BLOCK + threadIdx.x;
+    uint32_t n_tests = 0, n_nodes = 0;
+    if (i < n) {
+        const float *r = rays + 6 * (size_t)i;
+        float t;
+        const int k = tri_closest(T, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), mint, maxt, false, 0.0f, t, n_tests, n_nodes);
+        t_out[i] = k >= 0 ? t : __builtin_inff();
+        idx_out[i] = k;
+    }
+    unsigned long long a = n_tests, b = n_nodes;
+    for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
+    if ((threadIdx.x & 63u) == 0) { atomicAdd(&counters[0], a); atomicAdd(&counters[1], b); }
+}
+
+void launch_tri_hits(const DevTris &T, const float *rays, uint32_t n, float mint, float maxt, float *t_out, int32_t *idx_out,
+                     unsigned long long *counters, hipStream_t stream) {
+    hipLaunchKernelGGL(tri_hits_kernel, dim3((n + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, T, rays, n, mint, maxt, t_out, idx_out, counters);
+}
+
+bool kernel_has_lds_geom(const KArgs &a) { return !(a.geom.n_quads || a.geom.n_inst || a.tris.n); }
 
 void launch_render(const KArgs &a, bool moving, uint32_t accel, uint32_t grid, hipStream_t stream) {
     hipLaunchKernelGGL(pick_kernel(a, moving, accel, a.bvh.nodes16 != nullptr), dim3(grid), dim3(RTW_BLOCK), a.lds_bytes, stream, a);

@@ -55,6 +55,11 @@ struct rtw_ctx {
     DevNoise noise{};                    // device tables / per-texture entries (null when no noise is set)
     void *d_perlin = nullptr, *d_tex_noise = nullptr;
     FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
+    // Rust2 triangles of the scene (rtw_ctx_set_triangles; cleared by rtw_ctx_set_scene)
+    DevTris tris{};                      // tris.nodes stays null here: a render sets it when the tree may be used
+    const TriNode *tri_nodes = nullptr;
+    bool tri_tree = false;               // no triangle breaks the cull's derivation (DESIGN.md "Rust2 triangles")
+    void *d_tri_list = nullptr, *d_tri_leaf = nullptr, *d_tri_nodes = nullptr;
     // scratch
     uint32_t *d_queue = nullptr;
     unsigned long long *d_stats = nullptr;
@@ -238,11 +243,20 @@ static void free_noise(rtw_ctx *c) {
     c->noise_active = false;
 }
 
+static void free_tris(rtw_ctx *c) {
+    void **bufs[] = { &c->d_tri_list, &c->d_tri_leaf, &c->d_tri_nodes };
+    for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    c->tris = DevTris{};
+    c->tri_nodes = nullptr;
+    c->tri_tree = false;
+}
+
 static void free_scene(rtw_ctx *c) {
     void **bufs[] = { &c->d_quads, &c->d_inst, &c->d_igeom, &c->d_ivel, &c->d_imat, &c->d_iquads,
                       &c->d_geom, &c->d_vel, &c->d_mat, &c->d_tex, &c->d_texels, &c->d_nodes, &c->d_nodes16, &c->d_big_geom, &c->d_big_vel, &c->d_big_index };
     for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
     free_noise(c);
+    free_tris(c);
     c->n_textures = 0;
     c->tex_used.clear();
     c->has_scene = false;
@@ -422,6 +436,7 @@ int rtw_ctx_set_texture_noise(rtw_ctx *c, const RtwPerlin *tables, uint32_t n_ta
         return RTW_OK;
     }
     if (n_textures != c->n_textures || (n_tables && !tables)) return RTW_E_INVALID;
+    if (c->tris.n) return RTW_E_UNSUPPORTED;                       // texture noise on triangles: not implemented
     bool active = false;
     for (uint32_t i = 0; i < n_textures; i++) {
         const int32_t k = per_texture[i].perlin;
@@ -438,6 +453,72 @@ int rtw_ctx_set_texture_noise(rtw_ctx *c, const RtwPerlin *tables, uint32_t n_ta
     c->noise.tables = (const RtwPerlin *)c->d_perlin;
     c->noise.tex = (const RtwTextureNoise *)c->d_tex_noise;
     c->noise_active = true;
+    return RTW_OK;
+}
+
+int rtw_ctx_set_triangles(rtw_ctx *c, const RtwTriangle *tris, uint32_t n) {
+    if (!c) return RTW_E_INVALID;
+    if (!c->has_scene) return RTW_E_NO_SCENE;
+    if (c->pend.active || (n && !tris) || (!n && tris)) return RTW_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) if (tris[i].tex < -1 || tris[i].tex >= (int32_t)c->n_textures) return RTW_E_INVALID;
+    if (n && c->noise_active) return RTW_E_UNSUPPORTED;
+    HIP_TRY(hipSetDevice(c->device));
+    free_tris(c);
+    if (!n) return RTW_OK;
+    std::vector<DevTri> list;
+    TriBuild b;
+    try { list.resize(n); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+    tri_prepare(tris, n, list.data());
+    if (!tri_build(list.data(), n, b)) return RTW_E_NOMEM;
+    std::vector<DevTri> leaf(b.leaf, b.leaf + n);
+    std::vector<TriNode> nodes(b.nodes, b.nodes + b.n_nodes);
+    int rc;
+    if ((rc = upload(&c->d_tri_list, list)) || (rc = upload(&c->d_tri_leaf, leaf)) || (rc = upload(&c->d_tri_nodes, nodes))) { free_tris(c); return rc; }
+    c->tris.list = (const DevTri *)c->d_tri_list; c->tris.leaf = (const DevTri *)c->d_tri_leaf;
+    c->tris.n = n; c->tris.n_nodes = b.n_nodes;
+    c->tri_nodes = (const TriNode *)c->d_tri_nodes;
+    c->tri_tree = !b.list_walk;
+    return RTW_OK;
+}
+
+// The triangle view a render or query of this context uses: the tree only for RTW_ACCEL_BVH and a range the cull's derivation covers
+static DevTris tri_view(const rtw_ctx *c, uint32_t accel, float mint, float maxt) {
+    DevTris t = c->tris;
+    const float tb = std::fmax(std::fabs(mint), std::fabs(maxt));
+    t.t_bound = tb;
+    const bool range_ok = std::isfinite(mint) && std::isfinite(maxt) && tb <= RTW_TRI_COORD_MAX;
+    t.nodes = (accel == RTW_ACCEL_BVH && c->tri_tree && range_ok) ? c->tri_nodes : nullptr;
+    return t;
+}
+
+int rtw_ctx_triangle_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float mint, float maxt, uint32_t accel,
+                          float *t_out, int32_t *idx_out, RtwStats *stats) {
+    if (!c || !rays || !t_out || !idx_out || n_rays == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    if (!c->tris.n) return RTW_E_NO_SCENE;
+    HIP_TRY(hipSetDevice(c->device));
+    const DevTris T = tri_view(c, accel, mint, maxt);
+    const size_t ray_bytes = 6 * sizeof(float) * (size_t)n_rays, t_bytes = sizeof(float) * (size_t)n_rays, i_bytes = sizeof(int32_t) * (size_t)n_rays;
+    void *d_r = nullptr, *d_t = nullptr, *d_i = nullptr, *d_c = nullptr;
+    unsigned long long cnt[2] = { 0, 0 };
+    hipError_t e = hipMalloc(&d_r, ray_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_t, t_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_i, i_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_c, sizeof cnt);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_r, rays, ray_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_c, 0, sizeof cnt, c->stream);
+    if (e == hipSuccess) {
+        launch_tri_hits(T, (const float *)d_r, n_rays, mint, maxt, (float *)d_t, (int32_t *)d_i, (unsigned long long *)d_c, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(t_out, d_t, t_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(idx_out, d_i, i_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt, d_c, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    const bool alloc_failed = e == hipErrorOutOfMemory;
+    for (void *b : { d_r, d_t, d_i, d_c }) if (b) (void)hipFree(b);
+    if (e != hipSuccess) { g_last_hip = (int)e; return alloc_failed ? RTW_E_NOMEM : RTW_E_HIP; }
+    if (stats) { std::memset(stats, 0, sizeof *stats); stats->quad_tests = cnt[0]; stats->node_tests = cnt[1]; }
     return RTW_OK;
 }
 
@@ -543,6 +624,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     if (p->part_count > 1 && (p->row_block == 0 || p->part_index >= p->part_count)) return RTW_E_INVALID;
     if (p->width > 65535u || p->height > 65535u) return RTW_E_INVALID;      // a lane keeps (column, row) in one register (rtw_kernels.hip Pixel)
     if (c->noise_active && p->integrator == RTW_INTEGRATOR_RUST2) return RTW_E_UNSUPPORTED;   // Rust2's textures have no noise
+    if (c->noise_active && c->tris.n) return RTW_E_UNSUPPORTED;                              // (rtw_ctx_set_triangles / _set_texture_noise refuse it too)
     if (!c->pend.marked) c->pend.t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(c->device));
 
@@ -601,6 +683,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     std::memcpy(a.bg, c->bg, sizeof a.bg);
     a.queue = c->d_queue; a.stats = c->d_stats;
     if (c->noise_active) a.noise = c->noise;                       // (selects the noise build: pick_kernel)
+    if (c->tris.n) a.tris = tri_view(c, p->accel, p->mint, p->maxt);   // (selects the triangle build; the tree for RTW_ACCEL_BVH requests)
 #ifdef RTW_ENDTIMES
     if (const char *e = getenv("RTW_ENDTIMES_REF")) a.endtimes_ref = std::strtoull(e, nullptr, 10);       // diagnostic build only
 #endif
@@ -701,6 +784,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
         }
         a.lds_bytes = off;
     }
+    if (a.tris.n) { a.tris.lds_off = (a.lds_bytes + 15u) & ~15u; a.lds_bytes = a.tris.lds_off + 16u; }   // the triangle build's node-visit counter
 
     // persistent grid: as many workgroups as the kernel's registers let be resident, capped by the work
     uint32_t per_cu = c->opt_blocks_per_cu;
@@ -975,6 +1059,12 @@ int rtw_mgpu_set_scene(rtw_mgpu *m, const RtwScene *scene, float t_begin, float 
 int rtw_mgpu_set_texture_noise(rtw_mgpu *m, const RtwPerlin *tables, uint32_t n_tables, const RtwTextureNoise *per_texture, uint32_t n_textures) {
     if (!m) return RTW_E_INVALID;
     for (rtw_ctx *c : m->ctx) { int rc = rtw_ctx_set_texture_noise(c, tables, n_tables, per_texture, n_textures); if (rc != RTW_OK) return rc; }
+    return RTW_OK;
+}
+
+int rtw_mgpu_set_triangles(rtw_mgpu *m, const RtwTriangle *tris, uint32_t n) {
+    if (!m) return RTW_E_INVALID;
+    for (rtw_ctx *c : m->ctx) { int rc = rtw_ctx_set_triangles(c, tris, n); if (rc != RTW_OK) return rc; }
     return RTW_OK;
 }
 

@@ -1,0 +1,277 @@
+// rtw_tri.cpp -- host side of Rust2's triangles: Triangle::new, the tree builder (binned SAH, leaves of <= 4, bounded depth), its
+// self-check and the host list walk (DESIGN.md "Rust2 triangles").
+#include "rtw_tri.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+namespace rtw {
+
+static const float TRI_DEFAULT_M[3] = { 0.0f, 0.0f, 1.0f };     // the quad default (rtw_quad_new: EMPTY_M == SCATTER_M)
+
+void tri_prepare(const RtwTriangle *t, uint32_t n, DevTri *list) {
+    for (uint32_t i = 0; i < n; i++) {
+        const RtwTriangle &s = t[i];
+        DevTri &d = list[i];
+        std::memset(&d, 0, sizeof d);
+        for (int k = 0; k < 3; k++) {
+            d.origin[k] = s.origin[k]; d.u[k] = s.u[k]; d.v[k] = s.v[k];
+            d.albedo[k] = s.tex_color[k] * 1.0f;                  // (the quad's texel * 1.0; Rust2's ConstColorTexture: the same bits)
+            d.emitted[k] = s.emitted[k];
+        }
+        tri_derive(d.origin, d.u, d.v, d.normal, d.d, d.w);
+        d.index = i;
+        d.metallicness = s.metallicness; d.opacity = s.opacity; d.ir = s.ir; d.tex = s.tex;
+    }
+}
+
+TriBuild::~TriBuild() { delete[] nodes; delete[] leaf; }
+
+namespace {
+
+// The static part of the cull's error radius (DESIGN.md "Rust2 triangles"), and the conditions under which the derivation holds.
+struct TriBox { double lo[3], hi[3], c[3]; };
+
+bool tri_box(const DevTri &t, TriBox &b) {
+    bool ok = true;
+    const float *f[] = { t.origin, t.u, t.v, t.normal, t.w };
+    for (const float *p : f) for (int k = 0; k < 3; k++) if (!std::isfinite(p[k])) ok = false;
+    if (!std::isfinite(t.d)) ok = false;
+    if (!ok) {
+        for (int k = 0; k < 3; k++) { b.lo[k] = b.hi[k] = b.c[k] = 0.0; }
+        return false;
+    }
+    double amax = 0.0;
+    for (int k = 0; k < 3; k++) {
+        const double a = t.origin[k], p = a + (double)t.u[k], q = a + (double)t.v[k];
+        b.lo[k] = std::min(a, std::min(p, q)); b.hi[k] = std::max(a, std::max(p, q));
+        amax = std::max(amax, std::max(std::fabs(b.lo[k]), std::fabs(b.hi[k])));
+        if (!(std::fabs((double)t.w[k]) <= 0x1p40)) ok = false;
+    }
+    const double lu = std::sqrt((double)t.u[0] * t.u[0] + (double)t.u[1] * t.u[1] + (double)t.u[2] * t.u[2]);
+    const double lv = std::sqrt((double)t.v[0] * t.v[0] + (double)t.v[1] * t.v[1] + (double)t.v[2] * t.v[2]);
+    const double nx = (double)t.u[1] * t.v[2] - (double)t.u[2] * t.v[1], ny = (double)t.u[2] * t.v[0] - (double)t.u[0] * t.v[2],
+                 nz = (double)t.u[0] * t.v[1] - (double)t.u[1] * t.v[0];
+    const double nl = std::sqrt(nx * nx + ny * ny + nz * nz), e = std::max(lu, lv);
+    const double kappa = nl > 0.0 ? e * e / nl : HUGE_VAL;
+    if (!(amax <= 0x1p40) || !(kappa <= 256.0)) ok = false;
+    const double r = 0x1p-24 * (256.0 * amax + 4096.0 * kappa * (1.0 + kappa) * e) + 0x1p-100;
+    for (int k = 0; k < 3; k++) {
+        b.lo[k] -= r; b.hi[k] += r;
+        b.c[k] = 0.5 * (b.lo[k] + b.hi[k]);
+    }
+    return ok;
+}
+
+struct Builder {
+    const DevTri *list;
+    const std::vector<TriBox> &box;
+    std::vector<uint32_t> idx;
+    std::vector<TriNode> nodes;
+    std::vector<DevTri> leaf;
+    uint32_t depth = 0;
+
+    static float down(double x) { float f = (float)x; if ((double)f > x) f = std::nextafter(f, -INFINITY); return f; }
+    static float up(double x) { float f = (float)x; if ((double)f < x) f = std::nextafter(f, INFINITY); return f; }
+    static double area(const double *lo, const double *hi) {
+        const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+        return dx * dy + dy * dz + dz * dx;
+    }
+
+    void build(uint32_t begin, uint32_t end, uint32_t level) {
+        depth = std::max(depth, level);
+        const uint32_t me = (uint32_t)nodes.size();
+        nodes.push_back(TriNode{});
+        double lo[3] = { HUGE_VAL, HUGE_VAL, HUGE_VAL }, hi[3] = { -HUGE_VAL, -HUGE_VAL, -HUGE_VAL };
+        double clo[3] = { HUGE_VAL, HUGE_VAL, HUGE_VAL }, chi[3] = { -HUGE_VAL, -HUGE_VAL, -HUGE_VAL };
+        for (uint32_t i = begin; i < end; i++) {
+            const TriBox &b = box[idx[i]];
+            for (int k = 0; k < 3; k++) {
+                lo[k] = std::min(lo[k], b.lo[k]); hi[k] = std::max(hi[k], b.hi[k]);
+                clo[k] = std::min(clo[k], b.c[k]); chi[k] = std::max(chi[k], b.c[k]);
+            }
+        }
+        for (int k = 0; k < 3; k++) { nodes[me].lo[k] = down(lo[k]); nodes[me].hi[k] = up(hi[k]); }
+        const uint32_t n = end - begin;
+        if (n <= 4) {
+            nodes[me].leaf = ((uint32_t)leaf.size() << 3) | n;
+            for (uint32_t i = begin; i < end; i++) leaf.push_back(list[idx[i]]);
+            nodes[me].skip = (uint32_t)nodes.size();
+            return;
+        }
+        // binned SAH over the box centres (16 bins per axis); past depth 48, or when no split separates anything, the median of the widest axis
+        enum { B = 16 };
+        int axis = -1; uint32_t split_bin = 0; double best = HUGE_VAL;
+        if (level < 48) {
+            for (int k = 0; k < 3; k++) {
+                const double ext = chi[k] - clo[k];
+                if (!(ext > 0.0)) continue;
+                uint32_t cnt[B] = {}; double blo[B][3], bhi[B][3];
+                for (int j = 0; j < B; j++) for (int a = 0; a < 3; a++) { blo[j][a] = HUGE_VAL; bhi[j][a] = -HUGE_VAL; }
+                for (uint32_t i = begin; i < end; i++) {
+                    const TriBox &b = box[idx[i]];
+                    int j = (int)((b.c[k] - clo[k]) / ext * B); j = j < 0 ? 0 : j >= B ? B - 1 : j;
+                    cnt[j]++;
+                    for (int a = 0; a < 3; a++) { blo[j][a] = std::min(blo[j][a], b.lo[a]); bhi[j][a] = std::max(bhi[j][a], b.hi[a]); }
+                }
+                double rlo[3] = { HUGE_VAL, HUGE_VAL, HUGE_VAL }, rhi[3] = { -HUGE_VAL, -HUGE_VAL, -HUGE_VAL };
+                double rcost[B]; uint32_t rn = 0;
+                for (int j = B - 1; j > 0; j--) {
+                    for (int a = 0; a < 3; a++) { rlo[a] = std::min(rlo[a], blo[j][a]); rhi[a] = std::max(rhi[a], bhi[j][a]); }
+                    rn += cnt[j];
+                    rcost[j] = rn ? area(rlo, rhi) * rn : 0.0;
+                }
+                double llo[3] = { HUGE_VAL, HUGE_VAL, HUGE_VAL }, lhi[3] = { -HUGE_VAL, -HUGE_VAL, -HUGE_VAL };
+                uint32_t ln = 0;
+                for (int j = 0; j < B - 1; j++) {
+                    for (int a = 0; a < 3; a++) { llo[a] = std::min(llo[a], blo[j][a]); lhi[a] = std::max(lhi[a], bhi[j][a]); }
+                    ln += cnt[j];
+                    if (ln == 0 || ln == n) continue;
+                    const double c = area(llo, lhi) * ln + rcost[j + 1];
+                    if (c < best) { best = c; axis = k; split_bin = (uint32_t)j; }
+                }
+            }
+        }
+        uint32_t mid;
+        if (axis >= 0) {
+            const double ext = chi[axis] - clo[axis];
+            auto left = [&](uint32_t t) {
+                int j = (int)((box[t].c[axis] - clo[axis]) / ext * B); j = j < 0 ? 0 : j >= B ? B - 1 : j;
+                return (uint32_t)j <= split_bin;
+            };
+            mid = (uint32_t)(std::partition(idx.begin() + begin, idx.begin() + end, left) - idx.begin());
+        } else {
+            int k = 0;
+            for (int a = 1; a < 3; a++) if (chi[a] - clo[a] > chi[k] - clo[k]) k = a;
+            mid = begin + n / 2;
+            std::nth_element(idx.begin() + begin, idx.begin() + mid, idx.begin() + end, [&](uint32_t x, uint32_t y) {
+                return box[x].c[k] < box[y].c[k] || (box[x].c[k] == box[y].c[k] && x < y);
+            });
+        }
+        build(begin, mid, level + 1);
+        build(mid, end, level + 1);
+        nodes[me].leaf = 0;
+        nodes[me].skip = (uint32_t)nodes.size();
+    }
+};
+
+} // namespace
+
+bool tri_build(const DevTri *list, uint32_t n, TriBuild &out) {
+    try {
+        std::vector<TriBox> box(n);
+        bool ok = true;
+        for (uint32_t i = 0; i < n; i++) if (!tri_box(list[i], box[i])) ok = false;
+        Builder b{ list, box, {}, {}, {} };
+        b.idx.resize(n);
+        for (uint32_t i = 0; i < n; i++) b.idx[i] = i;
+        b.nodes.reserve(n > 0 ? 2 * ((size_t)n / 2 + 1) : 0);
+        b.leaf.reserve(n);
+        if (n) b.build(0, n, 0);
+        out.n_nodes = (uint32_t)b.nodes.size();
+        out.nodes = new TriNode[b.nodes.size() + 1];
+        out.leaf = new DevTri[b.leaf.size() + 1];
+        std::copy(b.nodes.begin(), b.nodes.end(), out.nodes);
+        std::copy(b.leaf.begin(), b.leaf.end(), out.leaf);
+        out.depth = b.depth;
+        out.list_walk = !ok;
+        return true;
+    } catch (const std::bad_alloc &) {
+        return false;
+    }
+}
+
+} // namespace rtw
+
+using namespace rtw;
+
+extern "C" {
+
+int rtw_triangle_new(const float origin[3], const float u[3], const float v[3], const float *mat3, const float *emitted,
+                     const float color[3], int32_t tex, RtwTriangle *out) {
+    if (!origin || !u || !v || !color || !out || tex < -1) return RTW_E_INVALID;
+    std::memset(out, 0, sizeof *out);
+    const float *m = mat3 ? mat3 : TRI_DEFAULT_M;
+    for (int k = 0; k < 3; k++) {
+        out->origin[k] = origin[k]; out->u[k] = u[k]; out->v[k] = v[k];
+        out->tex_color[k] = color[k];
+        out->emitted[k] = emitted ? emitted[k] : 0.0f;
+    }
+    tri_derive(out->origin, out->u, out->v, out->normal, out->d, out->w);
+    out->metallicness = m[0]; out->opacity = m[1]; out->ir = m[2];
+    out->tex = tex;
+    return RTW_OK;
+}
+
+int rtw_triangle_hits(const RtwTriangle *tris, uint32_t n, const float *rays, uint32_t n_rays, float mint, float maxt,
+                      float *t_out, int32_t *idx_out) {
+    if ((n && !tris) || !rays || !t_out || !idx_out || n_rays == 0) return RTW_E_INVALID;
+    std::vector<DevTri> list;
+    try { list.resize(n); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+    tri_prepare(tris, n, list.data());
+    for (uint32_t i = 0; i < n_rays; i++) {
+        const float *r = rays + 6 * (size_t)i;
+        float t;
+        const int k = tri_closest_host(list.data(), n, r[0], r[1], r[2], r[3], r[4], r[5], mint, maxt, t);
+        t_out[i] = k >= 0 ? t : INFINITY;
+        idx_out[i] = k;
+    }
+    return RTW_OK;
+}
+
+int rtw_triangle_bvh_validate(const RtwTriangle *tris, uint32_t n, uint32_t *n_nodes, uint32_t *depth, uint32_t *list_walk) {
+    if ((n && !tris) || n == 0) return RTW_E_INVALID;
+    std::vector<DevTri> list(n);
+    tri_prepare(tris, n, list.data());
+    TriBuild b;
+    if (!tri_build(list.data(), n, b)) return RTW_E_NOMEM;
+    std::vector<TriBox> box(n);
+    for (uint32_t i = 0; i < n; i++) tri_box(list[i], box[i]);
+    std::vector<uint8_t> seen(n, 0);
+    uint32_t leaf_slots = 0;
+    bool ok = b.n_nodes > 0;
+    // every node: a leaf with its triangles inside its box, or an inner node whose children (i + 1 and the left child's skip) lie inside
+    // it and end where it says (skip)
+    auto inside = [](const TriNode &o, const float *lo, const float *hi) {
+        for (int k = 0; k < 3; k++) if (!(o.lo[k] <= lo[k] && hi[k] <= o.hi[k])) return false;
+        return true;
+    };
+    std::vector<uint32_t> todo{ 0 };
+    uint32_t visited = 0;
+    while (ok && !todo.empty()) {
+        const uint32_t i = todo.back(); todo.pop_back();
+        if (i >= b.n_nodes || ++visited > b.n_nodes) { ok = false; break; }
+        const TriNode &nd = b.nodes[i];
+        if (nd.skip <= i || nd.skip > b.n_nodes) { ok = false; break; }
+        if (nd.leaf) {
+            const uint32_t first = nd.leaf >> 3, cnt = nd.leaf & 7u;
+            if (cnt == 0 || cnt > 4 || nd.skip != i + 1 || first + cnt > n) { ok = false; break; }
+            for (uint32_t j = first; j < first + cnt; j++) {
+                const uint32_t t = b.leaf[j].index;
+                if (t >= n || seen[t]) { ok = false; break; }
+                seen[t] = 1; leaf_slots++;
+                if (std::memcmp(&b.leaf[j], &list[t], sizeof(DevTri)) != 0) { ok = false; break; }
+                if (!b.list_walk) {
+                    for (int k = 0; k < 3; k++)
+                        if (!((double)nd.lo[k] <= box[t].lo[k] && box[t].hi[k] <= (double)nd.hi[k])) ok = false;
+                }
+            }
+        } else {
+            const uint32_t l = i + 1;
+            if (l >= b.n_nodes) { ok = false; break; }
+            const uint32_t r = b.nodes[l].skip;
+            if (r >= b.n_nodes || b.nodes[r].skip != nd.skip) { ok = false; break; }
+            if (!b.list_walk && (!inside(nd, b.nodes[l].lo, b.nodes[l].hi) || !inside(nd, b.nodes[r].lo, b.nodes[r].hi))) { ok = false; break; }
+            todo.push_back(r); todo.push_back(l);
+        }
+    }
+    if (ok && (b.nodes[0].skip != b.n_nodes || leaf_slots != n || visited != b.n_nodes)) ok = false;
+    if (n_nodes) *n_nodes = b.n_nodes;
+    if (depth) *depth = b.depth;
+    if (list_walk) *list_walk = b.list_walk ? 1u : 0u;
+    return ok ? RTW_OK : RTW_E_INVALID;
+}
+
+} // extern "C"
