@@ -400,9 +400,10 @@ int rtw_ctx_bilateral_filter(rtw_ctx *ctx, const void *in, uint32_t w, uint32_t 
  * Extension of this library (Rust/ has no triangles): Scene::collision_normal stays spheres, quads, instances; the triangles come LAST, as
  * one more group: the closest triangle in list order (a later one replaces the current one only when strictly closer, the quad rule), and
  * that one replaces the result so far only when strictly closer.  Material inline as in RtwQuad; no velocity (Rust2's triangle has none).
- * tex < 0: the constant colour tex_color; tex >= 0 under RTW_INTEGRATOR_RUST2: Rust2's ImageTexture::color_at(alfa, beta)
- * (Rust2/src/objects/texture.rs:94-105, emission image from RtwTexture.emit_tex, else `emitted`); under every other integrator the
- * quad's texel rule at (alfa, beta).  The derived fields are written by rtw_triangle_new and recomputed by the library from origin /
+ * tex < 0: the constant colour tex_color and `emitted` (ConstColorTexture, Rust2/src/objects/texture.rs:13-31); tex >= 0 under
+ * RTW_INTEGRATOR_RUST2: Rust2's ImageTexture::color_at(alfa, beta) (Rust2/src/objects/texture.rs:94-105, emission image from
+ * RtwTexture.emit_tex, else `emitted`); under every other integrator the quad's texel rule at (alfa, beta) (Rust/src/objects/quad.rs:64-79,
+ * the texel times 1.0) and `emitted`.  alfa, beta are those of the hit point r.at(t) (Triangle::color, :130-136).  The derived fields are written by rtw_triangle_new and recomputed by the library from origin /
  * u / v wherever it reads triangles (rtw_ctx_set_triangles, rtw_triangle_hits). */
 typedef struct RtwTriangle {
     float origin[3];

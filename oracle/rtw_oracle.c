@@ -24,6 +24,9 @@
  *   Rust/src/objects/instance.rs:250-310  Instance::collision_normal (+ const_density :24-26) -> instance_hit()
  *   Rust/src/vec3.rs:161-181              Vec3::rotated                       -> rot_make(), v3_rotated()
  *   Rust/src/viewport.rs:136-150          Scene::collision_normal             -> closest_hit()
+ *   Rust/src/texture.rs:61-194,259-267    PerlinNoise, ImageTexture noise_mult -> perlin_noise(), perlin_turb(), noise_mult()
+ *   Rust2/src/objects/triangle.rs:28-136  Triangle::new, get_hit, color       -> tri_make(), tri_hit_t(), tri_record()
+ *   (the last two only through rtw_oracle_render_ex, which takes the triangles and the noise a device context carries)
  *
  * Parity status.  The reference draws every random number from rand 0.8.5's ThreadRng (OS-seeded
  * ChaCha12, crate NOT vendored under /root/reference, Rust/Cargo.lock) and no reference test pins a
@@ -174,31 +177,27 @@ static inline uint32_t f32_as_usize(float f) {
     return (uint32_t)f;
 }
 
-/* sphere.rs:129-146 + texture.rs:259-267: nearest texel by spherical UV, times col_mod.
- * Indices are clamped to the image (the reference would panic on an out-of-range index). */
-static v3 sphere_albedo(const RtwScene *sc, const RtwSphere *s, v3 normal) {
-    v3 tex;
-    if (s->tex < 0 || (uint32_t)s->tex >= sc->n_textures) {
-        tex = v3_ld(s->tex_color); /* 1x1: floor(u*0)=0, floor(v*0)=0 */
-    } else {
-        const RtwTexture *t = &sc->textures[s->tex];
-        const float PI = 3.14159265358979323846f, FRAC_1_PI = 0.318309886183790671538f;
-        float u = (atan2f(-normal.z, normal.x) + PI) * FRAC_1_PI * 0.5f;
-        float v = 1.0f - (FRAC_1_PI * acosf(-normal.y));
-        uint32_t tx = f32_as_usize(floorf(u * (float)(t->row - 1)));
-        uint32_t ty = f32_as_usize(floorf(v * (float)(t->col - 1)));
-        if (tx > t->row - 1) tx = t->row - 1;
-        if (ty > t->col - 1) ty = t->col - 1;
-        tex = v3_ld(&sc->texels[3 * (size_t)(t->texel_offset + ty * t->row + tx)]);
-    }
-    tex = v3_scale(tex, 1.0f);                    /* texture.rs:265  img[..] * noise_mult, noise None */
-    return v3_mul(tex, v3_ld(s->col_mod));        /* sphere.rs:145 */
-}
+/* ------------------------------------------------------------------------------------------------
+ * What rtw_oracle_render_ex adds to a scene (RtwOracleExtras), resolved once per render.
+ * ---------------------------------------------------------------------------------------------- */
+/* Rust2's `Triangle` (Rust2/src/objects/triangle.rs:12-24): origin, u, v and the internals normal, d, w of Triangle::new */
+typedef struct { v3 origin, u, v, normal, w; float d; } tri_t;
+
+typedef struct {
+    const RtwScene *sc;
+    const RtwOracleExtras *x;    /* NULL: no triangles, no noise (rtw_oracle_render) */
+    const tri_t *tris;           /* x->triangles with their derived fields, recomputed here (tri_make) */
+    uint32_t n_tris;
+    int noise;                   /* x carries per-texture noise */
+    int device_uv;               /* RTW_ORACLE_FLAG_DEVICE_UV */
+    int rust2;                   /* RTW_INTEGRATOR_RUST2: the triangles take Rust2's texel rule (rtw.h "Rust2 triangles") */
+} world_t;
 
 /* TEST ONLY: the device's lean atan2 / acos for the spherical UV (csrc/rtw_device.h atan2_plain / acos_plain), restated operation for operation --
  * `/` and sqrtf are correctly rounded here, as div_plain / sqrt_plain are on the device for the arguments they are used with -- so that their
- * accuracy and their effect on the texel choice can be measured on the CPU (tests/test_round3_cpu.py).  The oracle's own renders use libm
- * (sphere_albedo below), like the reference (Rust's f32::atan2 / f32::acos). */
+ * accuracy and their effect on the texel choice can be measured on the CPU (tests/test_round3_cpu.py), and so that renders under
+ * RTW_ORACLE_FLAG_DEVICE_UV pick the device's texels.  The oracle's own renders use libm (sphere_uv below), like the reference (Rust's
+ * f32::atan2 / f32::acos). */
 static float atan2_plain(float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
     const float k = fmaxf(ax, ay) < 0x1p-60f ? 0x1p80f : 1.0f;
@@ -227,6 +226,17 @@ static float acos_plain(float x) {
     const float two = r + r;
     return small ? 1.57079632679489661923f - r : (x < 0.0f ? 3.14159265358979323846f - two : two);
 }
+/* (u, v) of an outward normal (sphere.rs:132-133): libm, or under RTW_ORACLE_FLAG_DEVICE_UV the device's sequences above */
+static inline void sphere_uv(const world_t *w, v3 normal, float *u, float *v) {
+    const float PI = 3.14159265358979323846f, FRAC_1_PI = 0.318309886183790671538f;
+    if (w->device_uv) {
+        *u = (atan2_plain(-normal.z, normal.x) + PI) * FRAC_1_PI * 0.5f;
+        *v = 1.0f - (FRAC_1_PI * acos_plain(-normal.y));
+    } else {
+        *u = (atan2f(-normal.z, normal.x) + PI) * FRAC_1_PI * 0.5f;
+        *v = 1.0f - (FRAC_1_PI * acosf(-normal.y));
+    }
+}
 /* (u, v) of sphere.rs:132-133 for n normals; plain != 0: through the device's sequences, else through libm.  out: [n][4] = atan2, acos, u, v */
 void rtw_oracle_sphere_uv(const float *normals, size_t n, int plain, float *out) {
     const float PI = 3.14159265358979323846f, FRAC_1_PI = 0.318309886183790671538f;
@@ -237,6 +247,83 @@ void rtw_oracle_sphere_uv(const float *normals, size_t n, int plain, float *out)
         out[4 * i + 2] = (at + PI) * FRAC_1_PI * 0.5f;
         out[4 * i + 3] = 1.0f - (FRAC_1_PI * ac);
     }
+}
+
+/* ---- PerlinNoise (Rust/src/texture.rs:61-194) ----------------------------------------------------------------------------------- */
+/* Rust `f as isize` (saturating, NaN -> 0), for the floor()ed coordinates of noise() (:159-161) */
+static inline int64_t f32_as_isize(float f) {
+    if (f != f) return 0;
+    if (f >= 0x1p63f) return INT64_MAX;
+    if (f < -0x1p63f) return INT64_MIN;
+    return (int64_t)f;
+}
+/* PerlinNoise::noise (:154-179) with perlin_interp (:86-107) */
+static float perlin_noise(const RtwPerlin *t, v3 p) {
+    const float u = p.x - floorf(p.x), v = p.y - floorf(p.y), w = p.z - floorf(p.z);                    /* :155-157 */
+    const uint64_t i = (uint64_t)f32_as_isize(floorf(p.x)), j = (uint64_t)f32_as_isize(floorf(p.y)),  /* :159-161 */
+                   k = (uint64_t)f32_as_isize(floorf(p.z));
+    const float uu = u * u * (3.0f - 2.0f * u);                                                        /* :87-89 */
+    const float vv = v * v * (3.0f - 2.0f * v);
+    const float ww = w * w * (3.0f - 2.0f * w);
+    float accum = 0.0f;
+    for (uint64_t di = 0; di < 2; di++)
+        for (uint64_t dj = 0; dj < 2; dj++)
+            for (uint64_t dk = 0; dk < 2; dk++) {
+                /* c[di][dj][dk] (:168-177): (i + di) & 255 with isize's wrapping addition (release build) */
+                const v3 c = v3_ld(t->ranvec[t->perm_x[(i + di) & 255u] ^ t->perm_y[(j + dj) & 255u] ^ t->perm_z[(k + dk) & 255u]]);
+                const float fi = (float)di, fj = (float)dj, fk = (float)dk;                            /* :95-97 */
+                const v3 weight_v = v3_make(u - fi, v - fj, w - fk);                                   /* :98 */
+                accum += (fi * uu + (1.0f - fi) * (1.0f - uu)) * (fj * vv + (1.0f - fj) * (1.0f - vv))
+                       * (fk * ww + (1.0f - fk) * (1.0f - ww)) * v3_dot(c, weight_v);                  /* :99-102 */
+            }
+    return accum;
+}
+/* PerlinNoise::turb (:181-193) */
+static float perlin_turb(const RtwPerlin *t, v3 p, uint32_t depth) {
+    float accum = 0.0f, weight = 1.0f;
+    for (uint32_t d = 0; d < depth; d++) {
+        accum += weight * perlin_noise(t, p);
+        weight *= 0.5f;
+        p = v3_scale(p, 2.0f);                                                                         /* temp_p *= 2.0 */
+    }
+    return fabsf(accum);
+}
+int rtw_oracle_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t turb_depth, float *out) {
+    if (!t || (n && (!points || !out))) return RTW_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        const v3 p = v3_ld(points + 3 * (size_t)i);
+        out[i] = turb_depth == 0 ? perlin_noise(t, p) : perlin_turb(t, p, turb_depth);
+    }
+    return RTW_OK;
+}
+/* ImageTexture::color_at's noise_mult (texture.rs:260-264): noise(p / noise_scale) when texture `tex` has noise, else 1.0 */
+static inline float noise_mult(const world_t *w, int32_t tex, v3 p) {
+    if (!w->noise) return 1.0f;
+    const RtwTextureNoise *tn = &w->x->tex_noise[tex];
+    if (tn->perlin < 0) return 1.0f;
+    return perlin_noise(&w->x->perlin[tn->perlin], v3_div(p, tn->scale));                              /* Vec3 / f32 (vec3.rs:120-129) */
+}
+
+/* sphere.rs:129-146 + texture.rs:259-267: nearest texel by spherical UV, times the noise at `point` (r.at(t), sphere.rs:145; 1.0 without
+ * noise), times col_mod.  Indices are clamped to the image (the reference would panic on an out-of-range index). */
+static v3 sphere_albedo(const world_t *w, const RtwSphere *s, v3 normal, v3 point) {
+    const RtwScene *sc = w->sc;
+    v3 tex;
+    if (s->tex < 0 || (uint32_t)s->tex >= sc->n_textures) {
+        tex = v3_ld(s->tex_color); /* 1x1: floor(u*0)=0, floor(v*0)=0; no noise (Sphere::new's from_color) */
+        tex = v3_scale(tex, 1.0f);
+    } else {
+        const RtwTexture *t = &sc->textures[s->tex];
+        float u, v;
+        sphere_uv(w, normal, &u, &v);
+        uint32_t tx = f32_as_usize(floorf(u * (float)(t->row - 1)));
+        uint32_t ty = f32_as_usize(floorf(v * (float)(t->col - 1)));
+        if (tx > t->row - 1) tx = t->row - 1;
+        if (ty > t->col - 1) ty = t->col - 1;
+        tex = v3_ld(&sc->texels[3 * (size_t)(t->texel_offset + ty * t->row + tx)]);
+        tex = v3_scale(tex, noise_mult(w, s->tex, point));   /* texture.rs:265  img[..] * noise_mult */
+    }
+    return v3_mul(tex, v3_ld(s->col_mod));        /* sphere.rs:145 */
 }
 
 /* Rust2's ImageTexture::color_at (Rust2/src/objects/texture.rs:94-105) as written: the sample of an image of `width` x `height` texels at
@@ -256,11 +343,11 @@ uint32_t rtw_oracle_rust2_texel_index(float u, float v, uint32_t width, uint32_t
 /* Rust2 Sphere::color (Rust2/src/objects/sphere.rs:92-107) for a sphere with an image texture: ColorResult{emmited, multiplied}.  `multiplied`
  * is the texel (times the POD's col_mod, which a Rust2 scene leaves at 1: x * 1.0 == x); `emmited` the texel of the texture's emission
  * image (RtwTexture.emit_tex), or the sphere's constant emission when it has none. */
-static void rust2_sphere_color(const RtwScene *sc, const RtwSphere *s, v3 normal, v3 *mult, v3 *emit) {
+static void rust2_sphere_color(const world_t *w, const RtwSphere *s, v3 normal, v3 *mult, v3 *emit) {
+    const RtwScene *sc = w->sc;
     const RtwTexture *t = &sc->textures[s->tex];
-    const float PI = 3.14159265358979323846f, FRAC_1_PI = 0.318309886183790671538f;
-    const float u = (atan2f(-normal.z, normal.x) + PI) * FRAC_1_PI * 0.5f;
-    const float v = 1.0f - (FRAC_1_PI * acosf(-normal.y));
+    float u, v;
+    sphere_uv(w, normal, &u, &v);
     *mult = v3_mul(v3_ld(&sc->texels[3 * ((size_t)t->texel_offset + rust2_texel_index(u, v, t->row, t->col, 0))]), v3_ld(s->col_mod));
     if (t->emit_tex != 0 && t->emit_tex <= sc->n_textures) {
         const RtwTexture *e = &sc->textures[t->emit_tex - 1];
@@ -293,7 +380,7 @@ static inline mat_t sphere_mat(const RtwSphere *s) {
  * aabb/aabb.rs:140-152) -- strict, so the first of equal t wins; a NaN t can only enter first.
  * (The reference's AABB tree only prunes this loop; its bounds ignore velocity, which this restatement
  * does not reproduce: DESIGN.md 1.) */
-static int closest_sphere(const RtwScene *sc, const RtwSphere *list, uint32_t n, ray_t r, float mint, float maxt,
+static int closest_sphere(const world_t *w, const RtwSphere *list, uint32_t n, ray_t r, float mint, float maxt,
                           hit_t *h, counters_t *cn) {
     int best = -1; float best_t = 0.0f; v3 best_c = { 0, 0, 0 };
     for (uint32_t i = 0; i < n; i++) {
@@ -307,7 +394,7 @@ static int closest_sphere(const RtwScene *sc, const RtwSphere *list, uint32_t n,
     h->sphere = best;
     h->point = ray_at(r, best_t);
     h->normal = v3_unit(v3_sub(ray_at(r, best_t), best_c));   /* :127 */
-    h->col_mod = sphere_albedo(sc, &list[best], h->normal);
+    h->col_mod = sphere_albedo(w, &list[best], h->normal, h->point);
     h->mat = sphere_mat(&list[best]);
     return 1;
 }
@@ -326,7 +413,8 @@ static inline quad_derived_t quad_prepare(const RtwQuad *q) {
 }
 
 /* Quad::collision_normal (quad.rs:37-81) */
-static int quad_hit(const RtwScene *sc, const RtwQuad *q, ray_t r, float mint, float maxt, hit_t *h) {
+static int quad_hit(const world_t *w, const RtwQuad *q, ray_t r, float mint, float maxt, hit_t *h) {
+    const RtwScene *sc = w->sc;
     quad_derived_t g = quad_prepare(q);
     float denominator = v3_dot(g.normal, r.dir);
     if (fabsf(denominator) <= 1e-8f) return 0;
@@ -337,9 +425,9 @@ static int quad_hit(const RtwScene *sc, const RtwQuad *q, ray_t r, float mint, f
     float alfa = v3_dot(g.w, v3_cross(planar, v3_ld(q->v)));
     float beta = v3_dot(g.w, v3_cross(v3_ld(q->u), planar));
     if (alfa < 0.0f || alfa > 1.0f || beta < 0.0f || beta > 1.0f) return 0;
-    v3 tex;
+    v3 tex; float mult = 1.0f;
     if (q->tex < 0 || (uint32_t)q->tex >= sc->n_textures) {
-        tex = v3_ld(q->tex_color);                 /* 1x1: both indices are 0 */
+        tex = v3_ld(q->tex_color);                 /* 1x1: both indices are 0; no noise (Quad::new's from_color) */
     } else {
         const RtwTexture *tx = &sc->textures[q->tex];
         uint32_t ix = alfa != 1.0f ? f32_as_usize(floorf(alfa * (float)tx->row)) : tx->row - 1;   /* :66-70 */
@@ -347,22 +435,23 @@ static int quad_hit(const RtwScene *sc, const RtwQuad *q, ray_t r, float mint, f
         if (ix > tx->row - 1) ix = tx->row - 1;
         if (iy > tx->col - 1) iy = tx->col - 1;
         tex = v3_ld(&sc->texels[3 * (size_t)(tx->texel_offset + iy * tx->row + ix)]);
+        mult = noise_mult(w, q->tex, point);       /* at the hit point of the frame the quad is hit in */
     }
     h->t = t; h->normal = g.normal; h->point = point;
-    h->col_mod = v3_scale(tex, 1.0f);              /* texture.rs:265, noise None */
+    h->col_mod = v3_scale(tex, mult);              /* texture.rs:265  img[..] * noise_mult */
     h->mat.metallicness = q->metallicness; h->mat.opacity = q->opacity; h->mat.ir = q->ir;
     h->mat.emitted[0] = q->emitted[0]; h->mat.emitted[1] = q->emitted[1]; h->mat.emitted[2] = q->emitted[2];
     return 1;
 }
 
 /* Closest quad of a list in list order (QuadAABB::collision_normal, aabb/qaabb.rs:196-258, prunes this loop). */
-static int closest_quad(const RtwScene *sc, const RtwQuad *list, uint32_t n, ray_t r, float mint, float maxt,
+static int closest_quad(const world_t *w, const RtwQuad *list, uint32_t n, ray_t r, float mint, float maxt,
                         hit_t *h, counters_t *cn) {
     int best = -1;
     for (uint32_t i = 0; i < n; i++) {
         hit_t q;
         cn->quad_tests++;
-        if (!quad_hit(sc, &list[i], r, mint, maxt, &q)) continue;
+        if (!quad_hit(w, &list[i], r, mint, maxt, &q)) continue;
         if (best < 0 || h->t > q.t) { *h = q; h->sphere = (int)i; best = (int)i; }
     }
     return best >= 0;
@@ -414,19 +503,21 @@ static inline float ln_f32(float xf) {
 float rtw_oracle_ln(float x) { return ln_f32(x); }
 void rtw_oracle_ln_bulk(const float *x, float *out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = ln_f32(x[i]); }
 
-/* closest member of an instance, spheres then quads (instance.rs:263-273: `for i in vec![s_hit, q_hit]`) */
-static int instance_members(const RtwScene *sc, const RtwInstance *in, ray_t r, float mint, float maxt,
+/* closest member of an instance, spheres then quads (instance.rs:263-273: `for i in vec![s_hit, q_hit]`); in local coordinates, so a
+ * member's texture noise is taken at the local point */
+static int instance_members(const world_t *w, const RtwInstance *in, ray_t r, float mint, float maxt,
                             hit_t *h, counters_t *cn) {
+    const RtwScene *sc = w->sc;
     hit_t s_hit, q_hit; int found = 0;
-    if (closest_sphere(sc, sc->inst_spheres + in->first_sphere, in->n_spheres, r, mint, maxt, &s_hit, cn)) { *h = s_hit; found = 1; }
-    if (closest_quad(sc, sc->inst_quads + in->first_quad, in->n_quads, r, mint, maxt, &q_hit, cn)) {
+    if (closest_sphere(w, sc->inst_spheres + in->first_sphere, in->n_spheres, r, mint, maxt, &s_hit, cn)) { *h = s_hit; found = 1; }
+    if (closest_quad(w, sc->inst_quads + in->first_quad, in->n_quads, r, mint, maxt, &q_hit, cn)) {
         if (!found || h->t > q_hit.t) { *h = q_hit; found = 1; }
     }
     return found;
 }
 
 /* Instance::collision_normal (instance.rs:250-310) */
-static int instance_hit(const RtwScene *sc, const RtwInstance *in, ray_t r0, float mint, float maxt,
+static int instance_hit(const world_t *w, const RtwInstance *in, ray_t r0, float mint, float maxt,
                         hit_t *h, counters_t *cn, rng_t *rng) {
     v3 tr = v3_ld(in->translation), rot = v3_ld(in->rotation);
     rot_t back = rot_make(v3_neg(rot)), fwd = rot_make(rot);
@@ -434,13 +525,13 @@ static int instance_hit(const RtwScene *sc, const RtwInstance *in, ray_t r0, flo
     r.origin = v3_rotated(v3_sub(r0.origin, tr), back);
     r.dir = v3_rotated(r0.dir, back);
     r.time = r0.time;
-    if (!instance_members(sc, in, r, mint, maxt, h, cn)) return 0;
+    if (!instance_members(w, in, r, mint, maxt, h, cn)) return 0;
     if (in->medium == RTW_MEDIUM_CONST_DENSITY) {   /* const_density (:24-26): thread_rng().gen::<f32>().ln() / -d */
         float distance = ln_f32(rng_f32(rng)) / -in->density;
         if (distance >= 0.0f) {
             hit_t second;
             r.origin = v3_add(h->point, v3_scale(r.dir, distance));
-            if (!instance_members(sc, in, r, mint, maxt, &second, cn)) return 0;   /* left the volume first (:292) */
+            if (!instance_members(w, in, r, mint, maxt, &second, cn)) return 0;   /* left the volume first (:292) */
             h->point = r.origin;
             h->normal = random_unit_vec(rng);
         }
@@ -450,24 +541,130 @@ static int instance_hit(const RtwScene *sc, const RtwInstance *in, ray_t r0, flo
     return 1;
 }
 
+/* ---- Rust2 triangles (Rust2/src/objects/triangle.rs) ------------------------------------------------------------------------------ */
+/* Triangle::new (:28-49): n = u.cross(v), normal = n.unit() (Rust2/src/vec3.rs:219-221: n / n.length()), d = normal.dot(origin),
+ * w = n / n.dot(n) -- from origin / u / v alone, never from the pod's own derived fields */
+static tri_t tri_make(const RtwTriangle *t) {
+    tri_t g;
+    g.origin = v3_ld(t->origin); g.u = v3_ld(t->u); g.v = v3_ld(t->v);
+    v3 n = v3_cross(g.u, g.v);                      /* :35 (Rust2/src/vec3.rs:212-218) */
+    g.normal = v3_unit(n);                          /* :36 */
+    g.d = v3_dot(g.normal, g.origin);               /* :45 (Rust2/src/vec3.rs:209-211) */
+    g.w = v3_div(n, v3_dot(n, n));                  /* :46 */
+    return g;
+}
+void rtw_oracle_triangle_derived(const RtwTriangle *tris, uint32_t n, float *out) {
+    for (uint32_t i = 0; i < n; i++) {
+        tri_t g = tri_make(&tris[i]);
+        float *o = out + 7 * (size_t)i;
+        o[0] = g.normal.x; o[1] = g.normal.y; o[2] = g.normal.z; o[3] = g.d; o[4] = g.w.x; o[5] = g.w.y; o[6] = g.w.z;
+    }
+}
+/* get_hit (:91-124): Some(t) or None.  NaN falls through as written: a NaN t passes `t < mint || t > maxt`, NaN alfa / beta pass the
+ * interior test. */
+static inline int tri_hit_t(const tri_t *g, ray_t r, float mint, float maxt, float *t_out) {
+    float denominator = v3_dot(g->normal, r.dir);                       /* :93 */
+    if (fabsf(denominator) <= 1e-8f) return 0;                          /* :94 */
+    float t = (g->d - v3_dot(g->normal, r.origin)) / denominator;       /* :98 */
+    if (t < mint || t > maxt) return 0;                                 /* :99 */
+    v3 planar = v3_sub(ray_at(r, t), g->origin);                        /* :106-107 (Rust2/src/vec3.rs:337-339) */
+    float alfa = v3_dot(g->w, v3_cross(planar, g->v));                  /* :109 */
+    float beta = v3_dot(g->w, v3_cross(g->u, planar));                  /* :110 */
+    if (alfa < 0.0f || beta < 0.0f || alfa + beta > 1.0f) return 0;     /* :111 */
+    *t_out = t;
+    return 1;
+}
+/* The triangle group (rtw.h "Rust2 triangles"): the closest triangle in list order, a later one only when strictly closer (the quad rule,
+ * closest_quad).  Returns its index or -1. */
+static int closest_triangle(const tri_t *list, uint32_t n, ray_t r, float mint, float maxt, float *bt) {
+    int best = -1; *bt = 0.0f;
+    for (uint32_t k = 0; k < n; k++) {
+        float t;
+        if (!tri_hit_t(&list[k], r, mint, maxt, &t)) continue;
+        if (best < 0 || *bt > t) { best = (int)k; *bt = t; }
+    }
+    return best;
+}
+int rtw_oracle_triangle_hits(const RtwTriangle *tris, uint32_t n, const float *rays, uint32_t n_rays, float mint, float maxt,
+                             float *t_out, int32_t *idx_out) {
+    if ((n && !tris) || !rays || !t_out || !idx_out || n_rays == 0) return RTW_E_INVALID;
+    tri_t *list = (tri_t *)malloc(sizeof(tri_t) * (n ? n : 1));
+    if (!list) return RTW_E_NOMEM;
+    for (uint32_t k = 0; k < n; k++) list[k] = tri_make(&tris[k]);
+    for (uint32_t i = 0; i < n_rays; i++) {
+        ray_t r; r.origin = v3_ld(rays + 6 * (size_t)i); r.dir = v3_ld(rays + 6 * (size_t)i + 3); r.time = 0.0f;
+        float t;
+        const int k = closest_triangle(list, n, r, mint, maxt, &t);
+        t_out[i] = k >= 0 ? t : INFINITY;
+        idx_out[i] = k;
+    }
+    free(list);
+    return RTW_OK;
+}
+/* The Hit of triangle k at t (get_hit :118-123: t, the unflipped normal, p = r.at(t)) and its colour, Triangle::color (:130-136):
+ * alfa, beta of the point, then the texture at (alfa, beta).  tex < 0: ConstColorTexture (Rust2/src/objects/texture.rs:24-31), the
+ * constant colour and emission.  An image texture under RTW_INTEGRATOR_RUST2: Rust2's ImageTexture::color_at(alfa, beta) (:94-105), the
+ * emission image when the texture has one (RtwTexture.emit_tex), else the constant emission; under every other integrator: the quad's
+ * texel rule at (alfa, beta) (Rust/src/objects/quad.rs:64-79) times 1.0, the constant emission (rtw.h "Rust2 triangles"). */
+static void tri_record(const world_t *w, uint32_t k, ray_t r, float t, hit_t *h) {
+    const RtwScene *sc = w->sc;
+    const RtwTriangle *s = &w->x->triangles[k];
+    const tri_t *g = &w->tris[k];
+    v3 point = ray_at(r, t);
+    v3 cm = v3_ld(s->tex_color), em = v3_ld(s->emitted);
+    if (s->tex >= 0) {
+        v3 planar = v3_sub(point, g->origin);                           /* :131 */
+        float alfa = v3_dot(g->w, v3_cross(planar, g->v));              /* :132 */
+        float beta = v3_dot(g->w, v3_cross(g->u, planar));              /* :133 */
+        const RtwTexture *tx = &sc->textures[s->tex];
+        if (w->rust2) {
+            cm = v3_ld(&sc->texels[3 * ((size_t)tx->texel_offset + rust2_texel_index(alfa, beta, tx->row, tx->col, 0))]);
+            if (tx->emit_tex != 0 && tx->emit_tex <= sc->n_textures) {
+                const RtwTexture *e = &sc->textures[tx->emit_tex - 1];
+                em = v3_ld(&sc->texels[3 * ((size_t)e->texel_offset + rust2_texel_index(alfa, beta, e->row, e->col, 1))]);
+            }
+        } else {
+            uint32_t ix = alfa != 1.0f ? f32_as_usize(floorf(alfa * (float)tx->row)) : tx->row - 1;   /* quad.rs:66-70 */
+            uint32_t iy = beta != 1.0f ? f32_as_usize(floorf(beta * (float)tx->col)) : tx->col - 1;   /* quad.rs:71-75 */
+            if (ix > tx->row - 1) ix = tx->row - 1;
+            if (iy > tx->col - 1) iy = tx->col - 1;
+            cm = v3_scale(v3_ld(&sc->texels[3 * (size_t)(tx->texel_offset + iy * tx->row + ix)]), 1.0f);
+        }
+    }
+    h->t = t; h->point = point; h->normal = g->normal; h->col_mod = cm;
+    h->mat.metallicness = s->metallicness; h->mat.opacity = s->opacity; h->mat.ir = s->ir;
+    h->mat.emitted[0] = em.x; h->mat.emitted[1] = em.y; h->mat.emitted[2] = em.z;
+}
+
 /* Scene::collision_normal (viewport.rs:136-150): spheres, quads, instances; a later hit replaces an earlier
  * one only when strictly closer.  The three AABB trees (aabb.rs, qaabb.rs, iaabb.rs) only prune the list
  * walks below; instances are visited in list order (the reference's IAABB order comes from an unseeded
- * random split axis, aabb/iaabb.rs:87, and matters only for which medium draws first). */
-static int closest_hit(const RtwScene *sc, ray_t r, float mint, float maxt, hit_t *h, counters_t *cn, rng_t *rng) {
+ * random split axis, aabb/iaabb.rs:87, and matters only for which medium draws first).  The extension's
+ * triangles come last, as one more group (rtw.h "Rust2 triangles"). */
+static int closest_hit(const world_t *w, ray_t r, float mint, float maxt, hit_t *h, counters_t *cn, rng_t *rng) {
+    const RtwScene *sc = w->sc;
     int found = 0; hit_t c;
     cn->segments++;
-    if (closest_sphere(sc, sc->spheres, sc->n_spheres, r, mint, maxt, &c, cn)) { *h = c; found = 1; }
-    if (sc->n_quads && closest_quad(sc, sc->quads, sc->n_quads, r, mint, maxt, &c, cn)) {
+    if (closest_sphere(w, sc->spheres, sc->n_spheres, r, mint, maxt, &c, cn)) { *h = c; found = 1; }
+    if (sc->n_quads && closest_quad(w, sc->quads, sc->n_quads, r, mint, maxt, &c, cn)) {
         if (!found || h->t > c.t) { *h = c; h->sphere = (int)sc->n_spheres + c.sphere; found = 1; }
     }
     if (sc->n_instances) {
         int ibest = 0; hit_t ih; int ifound = 0;
         for (uint32_t i = 0; i < sc->n_instances; i++) {
-            if (!instance_hit(sc, &sc->instances[i], r, mint, maxt, &c, cn, rng)) continue;
+            if (!instance_hit(w, &sc->instances[i], r, mint, maxt, &c, cn, rng)) continue;
             if (!ifound || ih.t > c.t) { ih = c; ibest = (int)i; ifound = 1; }
         }
         if (ifound && (!found || h->t > ih.t)) { *h = ih; h->sphere = (int)(sc->n_spheres + sc->n_quads) + ibest; found = 1; }
+    }
+    if (w->n_tris) {
+        float tt;
+        const int k = closest_triangle(w->tris, w->n_tris, r, mint, maxt, &tt);
+        cn->quad_tests += w->n_tris;                   /* a triangle test counts as a quad test (RtwStats.quad_tests) */
+        if (k >= 0 && (!found || h->t > tt)) {
+            tri_record(w, (uint32_t)k, r, tt, h);
+            h->sphere = (int)(sc->n_spheres + sc->n_quads + sc->n_instances) + k; found = 1;
+        }
     }
     return found;
 }
@@ -554,7 +751,7 @@ static inline v3 sky_gradient(v3 dir) {
 }
 
 typedef struct {
-    const RtwScene *sc; const RtwParams *p; counters_t *cn; rng_t *rng;
+    const RtwScene *sc; const world_t *w; const RtwParams *p; counters_t *cn; rng_t *rng;
     RtwOracleBounce *trace; int trace_cap, trace_n;
 } ctx_t;
 
@@ -579,7 +776,7 @@ static void trace_record(ctx_t *c, int hit, const hit_t *h, const scatter_t *s, 
 static v3 ray_color_gradient_rec(ctx_t *c, ray_t r, uint32_t depth) {
     if (depth < 1) return v3_make(0, 0, 0);
     hit_t h;
-    if (closest_hit(c->sc, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
+    if (closest_hit(c->w, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
         scatter_t s = on_hit(&h.mat, &h, r, c->rng, c->p->flags);
         fix_degenerate(&s, &h);
         trace_record(c, 1, &h, &s, r);
@@ -596,7 +793,7 @@ static v3 ray_color_gradient_iter(ctx_t *c, ray_t r, uint32_t depth) {
     v3 thr = v3_make(1.0f, 1.0f, 1.0f);
     for (uint32_t k = 0; k < depth; k++) {
         hit_t h;
-        if (!closest_hit(c->sc, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
+        if (!closest_hit(c->w, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
             trace_record(c, 0, NULL, NULL, r);
             return v3_mul(sky_gradient(r.dir), thr);
         }
@@ -618,7 +815,7 @@ static inline float lambertian_scatter_pdf(float cos_theta) {
 static v3 ray_color_bg_rec(ctx_t *c, ray_t r, uint32_t depth) {
     if (depth < 1) return v3_make(0, 0, 0);
     hit_t h;
-    if (closest_hit(c->sc, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
+    if (closest_hit(c->w, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
         const mat_t *sp = &h.mat;
         scatter_t s = on_hit(sp, &h, r, c->rng, c->p->flags);
         fix_degenerate(&s, &h);
@@ -643,7 +840,7 @@ static v3 ray_color_bg_iter(ctx_t *c, ray_t r, uint32_t depth) {
     int poison = 0;
     for (uint32_t k = 0; k < depth; k++) {
         hit_t h;
-        if (!closest_hit(c->sc, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
+        if (!closest_hit(c->w, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
             trace_record(c, 0, NULL, NULL, r);
             L = v3_add(L, v3_mul(v3_ld(c->sc->background), thr));
             goto done;
@@ -665,7 +862,7 @@ done:
 /* C++/src/tests.cpp:76-97 ray_colorSc: (normal + 1) * 0.5 of the closest hit, else sky */
 static v3 ray_color_normal(ctx_t *c, ray_t r) {
     hit_t h;
-    if (closest_hit(c->sc, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
+    if (closest_hit(c->w, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
         trace_record(c, 1, &h, NULL, r);
         return v3_scale(v3_make(h.normal.x + 1.0f, h.normal.y + 1.0f, h.normal.z + 1.0f), 0.5f);
     }
@@ -678,7 +875,7 @@ static v3 ray_color_flag(ctx_t *c, ray_t r, uint32_t depth) {
     v3 thr = v3_make(1.0f, 1.0f, 1.0f);
     for (uint32_t k = 0; k < depth; k++) {
         hit_t h;
-        if (!closest_hit(c->sc, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
+        if (!closest_hit(c->w, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
             trace_record(c, 0, NULL, NULL, r);
             return v3_mul(v3_make(0.0f, 0.0f, 1.0f), thr);
         }
@@ -724,10 +921,11 @@ static ray_t rust2_on_hit(const mat_t *s, const hit_t *h, ray_t r, rng_t *rng, u
 
 /* A top-level sphere with an image texture takes its ColorResult from Rust2's own lookup rule (instance members keep the Rust/ rule: instances
  * are the Rust/ tree's, Rust2 has none). */
-static void rust2_color_override(const RtwScene *sc, const hit_t *h, v3 *multiplied, v3 *emmited) {
+static void rust2_color_override(const world_t *w, const hit_t *h, v3 *multiplied, v3 *emmited) {
+    const RtwScene *sc = w->sc;
     if (h->sphere >= 0 && (uint32_t)h->sphere < sc->n_spheres) {
         const RtwSphere *s = &sc->spheres[h->sphere];
-        if (s->tex >= 0 && (uint32_t)s->tex < sc->n_textures) rust2_sphere_color(sc, s, h->normal, multiplied, emmited);
+        if (s->tex >= 0 && (uint32_t)s->tex < sc->n_textures) rust2_sphere_color(w, s, h->normal, multiplied, emmited);
     }
 }
 
@@ -735,12 +933,12 @@ static void rust2_color_override(const RtwScene *sc, const hit_t *h, v3 *multipl
 static v3 ray_color_rust2_rec(ctx_t *c, ray_t r, uint32_t depth) {
     if (depth == 0) return v3_ld(c->sc->background);
     hit_t h;
-    if (closest_hit(c->sc, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
+    if (closest_hit(c->w, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
         const mat_t *sp = &h.mat;
         ray_t next = rust2_on_hit(sp, &h, r, c->rng, c->p->flags);   /* o.color(&h) draws nothing; o.reflect(&h) does */
         trace_record(c, 1, &h, NULL, r);
         v3 emmited = v3_ld(sp->emitted), multiplied = h.col_mod;
-        rust2_color_override(c->sc, &h, &multiplied, &emmited);
+        rust2_color_override(c->w, &h, &multiplied, &emmited);
         v3 next_color = ray_color_rust2_rec(c, next, depth - 1);
         return v3_add(emmited, v3_mul(next_color, multiplied));      /* emmited + next.field_wise_mult(multiplied) */
     }
@@ -753,7 +951,7 @@ static v3 ray_color_rust2_iter(ctx_t *c, ray_t r, uint32_t depth) {
     v3 thr = v3_make(1.0f, 1.0f, 1.0f), L = v3_make(0, 0, 0);
     for (uint32_t k = 0; k < depth; k++) {
         hit_t h;
-        if (!closest_hit(c->sc, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
+        if (!closest_hit(c->w, r, c->p->mint, c->p->maxt, &h, c->cn, c->rng)) {
             trace_record(c, 0, NULL, NULL, r);
             return v3_add(L, v3_mul(v3_ld(c->sc->background), thr));
         }
@@ -761,7 +959,7 @@ static v3 ray_color_rust2_iter(ctx_t *c, ray_t r, uint32_t depth) {
         ray_t next = rust2_on_hit(sp, &h, r, c->rng, c->p->flags);
         trace_record(c, 1, &h, NULL, r);
         v3 emmited = v3_ld(sp->emitted), multiplied = h.col_mod;
-        rust2_color_override(c->sc, &h, &multiplied, &emmited);
+        rust2_color_override(c->w, &h, &multiplied, &emmited);
         L = v3_add(L, v3_mul(emmited, thr));
         thr = v3_mul(thr, multiplied);
         r = next;
@@ -794,7 +992,7 @@ static uint32_t sampler_count(uint32_t sampler, uint32_t samples, uint32_t *root
     return n;
 }
 
-static void render_pixel(const RtwCamera *cam, const RtwScene *sc, const RtwParams *p,
+static void render_pixel(const RtwCamera *cam, const world_t *w, const RtwParams *p,
                          uint32_t i, uint32_t j, float out[3], counters_t *cn, uint64_t *camera_rays) {
     v3 origin = v3_ld(cam->origin), cu = v3_ld(cam->u), cv = v3_ld(cam->v);
     v3 p00 = v3_ld(cam->pixel00), du = v3_ld(cam->delta_u), dv = v3_ld(cam->delta_v);
@@ -802,7 +1000,7 @@ static void render_pixel(const RtwCamera *cam, const RtwScene *sc, const RtwPara
     uint32_t s_root, n = sampler_count(p->sampler, p->samples, &s_root);
     uint32_t pixel = j * p->width + i;
     v3 color = v3_make(0, 0, 0), part = v3_make(0, 0, 0);
-    ctx_t c; memset(&c, 0, sizeof c); c.sc = sc; c.p = p; c.cn = cn;
+    ctx_t c; memset(&c, 0, sizeof c); c.sc = w->sc; c.w = w; c.p = p; c.cn = cn;
 
     if (p->sampler == RTW_SAMPLER_NO_RAND) {                        /* viewport.rs:498-508 */
         rng_t rng = rng_seed(p->seed, pixel, 0); rng.permuted = (p->flags & RTW_ORACLE_FLAG_PERMUTED_STREAM) != 0; c.rng = &rng;
@@ -862,7 +1060,7 @@ static void render_pixel(const RtwCamera *cam, const RtwScene *sc, const RtwPara
  * into_par_iter over rows Rust2/src/viewport.rs:119-122).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
-    const RtwCamera *cam; const RtwScene *sc; const RtwParams *p;
+    const RtwCamera *cam; const world_t *w; const RtwParams *p;
     float *out; const uint32_t *rows; uint32_t n_rows;
     atomic_uint next;
     pthread_mutex_t mu;
@@ -878,7 +1076,7 @@ static void *worker(void *arg) {
         uint32_t j = jb->rows[k];
         float *row = jb->out + (size_t)k * jb->p->width * 3;
         for (uint32_t i = 0; i < jb->p->width; i++) {
-            render_pixel(jb->cam, jb->sc, jb->p, i, j, row + 3 * (size_t)i, &cn, &rays);
+            render_pixel(jb->cam, jb->w, jb->p, i, j, row + 3 * (size_t)i, &cn, &rays);
             if (isnan(row[3 * i]) || isnan(row[3 * i + 1]) || isnan(row[3 * i + 2])) nans++;
         }
     }
@@ -904,9 +1102,15 @@ static int params_ok(const RtwCamera *cam, const RtwScene *sc, const RtwParams *
     return 1;
 }
 
-int rtw_oracle_render(const RtwCamera *cam, const RtwScene *sc, const RtwParams *p,
-                      float *out_rgb, RtwStats *stats, int threads) {
-    if (!params_ok(cam, sc, p) || !out_rgb) return RTW_E_INVALID;
+static inline world_t world_make(const RtwScene *sc, const RtwParams *p) {
+    world_t w; memset(&w, 0, sizeof w);
+    w.sc = sc;
+    w.device_uv = (p->flags & RTW_ORACLE_FLAG_DEVICE_UV) != 0;
+    w.rust2 = p->integrator == RTW_INTEGRATOR_RUST2;
+    return w;
+}
+
+static int render_world(const RtwCamera *cam, const world_t *w, const RtwParams *p, float *out_rgb, RtwStats *stats, int threads) {
     struct timespec t0, t1; clock_gettime(CLOCK_MONOTONIC, &t0);
     uint32_t *rows = (uint32_t *)malloc(sizeof(uint32_t) * p->height);
     if (!rows) return RTW_E_NOMEM;
@@ -915,7 +1119,7 @@ int rtw_oracle_render(const RtwCamera *cam, const RtwScene *sc, const RtwParams 
         if (p->part_count <= 1 || (r / p->row_block) % p->part_count == p->part_index) rows[n_rows++] = r;
 
     job_t jb; memset(&jb, 0, sizeof jb);
-    jb.cam = cam; jb.sc = sc; jb.p = p; jb.out = out_rgb; jb.rows = rows; jb.n_rows = n_rows;
+    jb.cam = cam; jb.w = w; jb.p = p; jb.out = out_rgb; jb.rows = rows; jb.n_rows = n_rows;
     atomic_init(&jb.next, 0); pthread_mutex_init(&jb.mu, NULL);
     if (threads <= 1) worker(&jb);
     else {
@@ -940,13 +1144,52 @@ int rtw_oracle_render(const RtwCamera *cam, const RtwScene *sc, const RtwParams 
     return RTW_OK;
 }
 
+int rtw_oracle_render(const RtwCamera *cam, const RtwScene *sc, const RtwParams *p,
+                      float *out_rgb, RtwStats *stats, int threads) {
+    if (!params_ok(cam, sc, p) || !out_rgb) return RTW_E_INVALID;
+    const world_t w = world_make(sc, p);
+    return render_world(cam, &w, p, out_rgb, stats, threads);
+}
+
+/* The checks rtw_ctx_set_triangles / rtw_ctx_set_texture_noise make (rtw.h): a triangle texture and every noise table inside the scene's. */
+static int extras_ok(const RtwScene *sc, const RtwOracleExtras *x) {
+    if (x->n_triangles && !x->triangles) return 0;
+    for (uint32_t k = 0; k < x->n_triangles; k++)
+        if (x->triangles[k].tex >= 0 && (uint32_t)x->triangles[k].tex >= sc->n_textures) return 0;
+    if (x->n_tex_noise) {
+        if (!x->tex_noise || x->n_tex_noise != sc->n_textures || (x->n_perlin && !x->perlin)) return 0;
+        for (uint32_t k = 0; k < x->n_tex_noise; k++)
+            if (x->tex_noise[k].perlin >= 0 && (uint32_t)x->tex_noise[k].perlin >= x->n_perlin) return 0;
+    }
+    return 1;
+}
+
+int rtw_oracle_render_ex(const RtwCamera *cam, const RtwScene *sc, const RtwOracleExtras *x, const RtwParams *p,
+                         float *out_rgb, RtwStats *stats, int threads) {
+    if (!params_ok(cam, sc, p) || !out_rgb || (x && !extras_ok(sc, x))) return RTW_E_INVALID;
+    world_t w = world_make(sc, p);
+    tri_t *tris = NULL;
+    if (x && x->n_triangles) {
+        tris = (tri_t *)malloc(sizeof(tri_t) * x->n_triangles);
+        if (!tris) return RTW_E_NOMEM;
+        for (uint32_t k = 0; k < x->n_triangles; k++) tris[k] = tri_make(&x->triangles[k]);
+        w.tris = tris; w.n_tris = x->n_triangles;
+    }
+    if (x && x->n_tex_noise) w.noise = 1;
+    if (w.n_tris || w.noise) w.x = x;
+    const int rc = render_world(cam, &w, p, out_rgb, stats, threads);
+    free(tris);
+    return rc;
+}
+
 int rtw_oracle_trace_ray(const float origin[3], const float dir[3], float time,
                          const RtwScene *sc, const RtwParams *p, uint32_t pixel, uint32_t sample,
                          RtwOracleBounce *out, int cap, float rgb[3]) {
     if (!origin || !dir || !sc || !p) return RTW_E_INVALID;
     counters_t cn = { 0, 0, 0 };
     rng_t rng = rng_seed(p->seed, pixel, sample); rng.permuted = (p->flags & RTW_ORACLE_FLAG_PERMUTED_STREAM) != 0;
-    ctx_t c; memset(&c, 0, sizeof c); c.sc = sc; c.p = p; c.cn = &cn; c.rng = &rng;
+    const world_t w = world_make(sc, p);
+    ctx_t c; memset(&c, 0, sizeof c); c.sc = sc; c.w = &w; c.p = p; c.cn = &cn; c.rng = &rng;
     c.trace = out; c.trace_cap = cap;
     ray_t r; r.origin = v3_ld(origin); r.dir = v3_ld(dir); r.time = time;
     v3 col = ray_color(&c, r);

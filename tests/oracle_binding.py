@@ -16,6 +16,16 @@ REF_SO = os.path.join(ORACLE_DIR, "_ref", "librtw_ref.so")
 REF_STATS = os.path.join(ROOT, "tests", "golden", "ref_statistical.npz")
 
 
+FLAG_DEVICE_UV = 0x20000000          # RTW_ORACLE_FLAG_DEVICE_UV (rtw_oracle.h): oracle params only, never a device call
+
+
+class Extras(C.Structure):
+    """RtwOracleExtras (rtw_oracle.h): the triangles and the texture noise a device context carries besides the RtwScene."""
+    _fields_ = [("triangles", C.POINTER(R.RtwTriangle)), ("n_triangles", C.c_uint32),
+                ("perlin", C.POINTER(R.RtwPerlin)), ("n_perlin", C.c_uint32),
+                ("tex_noise", C.POINTER(R.RtwTextureNoise)), ("n_tex_noise", C.c_uint32)]
+
+
 class Bounce(C.Structure):
     _fields_ = [("hit", C.c_int32), ("sphere", C.c_int32), ("front_face", C.c_int32), ("cannot_refract", C.c_int32),
                 ("t", C.c_float), ("ratio", C.c_float), ("normal", C.c_float * 3), ("point", C.c_float * 3),
@@ -53,6 +63,13 @@ def lib():
         L.rtw_oracle_sphere_uv.restype = None
         L.rtw_oracle_rotated.argtypes = [fp, fp, fp]
         L.rtw_oracle_rotated.restype = None
+        L.rtw_oracle_render_ex.argtypes = [C.POINTER(R.RtwCamera), C.POINTER(R.RtwScene), C.POINTER(Extras), C.POINTER(R.RtwParams), fp,
+                                           C.POINTER(R.RtwStats), C.c_int]
+        L.rtw_oracle_triangle_hits.argtypes = [C.POINTER(R.RtwTriangle), C.c_uint32, fp, C.c_uint32, C.c_float, C.c_float, fp,
+                                               C.POINTER(C.c_int32)]
+        L.rtw_oracle_triangle_derived.argtypes = [C.POINTER(R.RtwTriangle), C.c_uint32, fp]
+        L.rtw_oracle_triangle_derived.restype = None
+        L.rtw_oracle_perlin_eval.argtypes = [C.POINTER(R.RtwPerlin), fp, C.c_uint32, C.c_uint32, fp]
         _lib = L
     return _lib
 
@@ -83,15 +100,73 @@ def ref():
     return _ref
 
 
-def render(cam, scene, params, threads=8):
-    """rtw_oracle_render -> ([rows][W][3] f32, RtwStats)."""
+def extras(scene):
+    """The RtwOracleExtras of a Scene: its triangles (scene.triangles) and its noise (scene.noise_pods()), or None when it has neither.
+    The ctypes arrays are kept alive on the returned structure."""
+    nz = scene.noise_pods()
+    if not scene.n_triangles and nz is None:
+        return None
+    x = Extras()
+    if scene.n_triangles:
+        x.triangles, x.n_triangles = C.cast(scene.triangles, C.POINTER(R.RtwTriangle)), scene.n_triangles
+    if nz is not None:
+        tables, n_tables, per, n_tex = nz
+        x.perlin, x.n_perlin = C.cast(tables, C.POINTER(R.RtwPerlin)), n_tables
+        x.tex_noise, x.n_tex_noise = C.cast(per, C.POINTER(R.RtwTextureNoise)), n_tex
+        x._keep = nz
+    return x
+
+
+def render(cam, scene, params, threads=8, device_uv=False, x=None):
+    """rtw_oracle_render -> ([rows][W][3] f32, RtwStats).  A Scene with triangles or texture noise goes through rtw_oracle_render_ex with
+    them (or with `x`, an Extras, when given); device_uv renders with RTW_ORACLE_FLAG_DEVICE_UV set on a copy of `params`."""
     rows = R.lib().rtw_part_rows(params.height, params.row_block, params.part_index, params.part_count)
     out = np.empty((rows, params.width, 3), np.float32)
     st = R.RtwStats()
-    rc = lib().rtw_oracle_render(C.byref(cam), C.byref(scene.pod), C.byref(params), out.ctypes.data_as(C.POINTER(C.c_float)),
-                                 C.byref(st), threads)
+    if device_uv:
+        params = R.RtwParams.from_buffer_copy(params)
+        params.flags |= FLAG_DEVICE_UV
+    if x is None:
+        x = extras(scene)
+    if x is None:
+        rc = lib().rtw_oracle_render(C.byref(cam), C.byref(scene.pod), C.byref(params), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                     C.byref(st), threads)
+    else:
+        rc = lib().rtw_oracle_render_ex(C.byref(cam), C.byref(scene.pod), C.byref(x), C.byref(params),
+                                        out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st), threads)
     assert rc == 0, rc
     return out, st
+
+
+def triangle_hits(triangles, rays, mint, maxt):
+    """rtw_oracle_triangle_hits: (t [n] f32, +inf on a miss; index [n] i32, -1 on a miss), the contract of rtw_triangle_hits."""
+    arr, n = R._triangle_array(triangles)
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    t = np.empty(len(r), np.float32)
+    idx = np.empty(len(r), np.int32)
+    rc = lib().rtw_oracle_triangle_hits(arr, n, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt),
+                                        t.ctypes.data_as(C.POINTER(C.c_float)), idx.ctypes.data_as(C.POINTER(C.c_int32)))
+    assert rc == 0, rc
+    return t, idx
+
+
+def triangle_derived(triangles):
+    """The oracle's Triangle::new of each triangle: [n][7] f32 = normal, d, w."""
+    arr, n = R._triangle_array(triangles)
+    out = np.empty((n, 7), np.float32)
+    lib().rtw_oracle_triangle_derived(arr, n, out.ctypes.data_as(C.POINTER(C.c_float)))
+    return out
+
+
+def perlin_eval(perlin, points, depth=0):
+    """rtw_oracle_perlin_eval: PerlinNoise::noise (depth 0) or turb(p, depth) of a PerlinNoise at points [..., 3] -> f32 [...]."""
+    pts = np.ascontiguousarray(points, np.float32)
+    flat = pts.reshape(-1, 3)
+    out = np.empty(len(flat), np.float32)
+    rc = lib().rtw_oracle_perlin_eval(C.byref(perlin.pod), flat.ctypes.data_as(C.POINTER(C.c_float)), len(flat), int(depth),
+                                      out.ctypes.data_as(C.POINTER(C.c_float)))
+    assert rc == 0, rc
+    return out.reshape(pts.shape[:-1])
 
 
 def trace_ray(origin, direction, time, scene, params, pixel=0, sample=0, cap=64):

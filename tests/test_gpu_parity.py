@@ -92,6 +92,11 @@ def test_c5_motion_blur_and_texture(gpu):
         assert bad <= 0.002 * 160 * 90, bad
         assert np.abs(img - ref).max() < 0.05
     assert np.array_equal(out[R.ACCEL_BRUTE][0], out[R.ACCEL_BVH][0])
+    # with the device's atan2 / acos sequences in the oracle (RTW_ORACLE_FLAG_DEVICE_UV) the texel choice is the same: bit for bit
+    dev, st_dev = O.render(cam, scene, p, 16, device_uv=True)
+    assert st_dev.segments == st_ref.segments
+    for accel, (img, st) in out.items():
+        assert np.array_equal(img.view(np.uint32), dev.view(np.uint32)), (accel, int((img != dev).any(axis=2).sum()))
 
 
 @pytest.mark.parametrize("sampler", [R.SAMPLER_ROW, R.SAMPLER_STRATIFIED, R.SAMPLER_CENTRES, R.SAMPLER_NO_RAND])
@@ -652,3 +657,24 @@ def test_reference_texture_reflection_scene(gpu):
         same = (ulp_diff(img, ref) <= 2).all(axis=2)
         assert same.mean() > 0.999, (accel, same.mean())
     assert np.array_equal(out[R.ACCEL_BRUTE][0], out[R.ACCEL_BVH][0])
+
+
+def test_reference_texture_reflection_scene_exact_under_the_device_uv(gpu):
+    """The reflection_test scene above at 100 x 75, 16 spp and gamma 1 (no powf), against the oracle with the device's atan2 / acos
+    sequences (RTW_ORACLE_FLAG_DEVICE_UV): every pixel bit for bit."""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_images.npz"))
+    tex = z["squares_png_rgb"].astype(np.float32) / np.float32(255.0)
+    spheres = [R.Sphere.new((0.520, 0.0, -1.0), 0.45, (0.95, 0.95, 0.95), R.METALLIC_M),
+               R.Sphere.new_with_texture((-1001.0, 0.0, 0.0), 1000.0, None, R.METALLIC_M, 0)]
+    scene = R.Scene(spheres, textures=[tex])
+    vp = R.Viewport.new_from_res(100, 75, 16, 10, 1.0, vfov=90.0, origin=(0.0, 0.0, 0.0))
+    vp.maxt = 1000.0
+    cam = vp.camera()
+    p = vp.params(R.INTEGRATOR_GRADIENT, R.SAMPLER_STRATIFIED)
+    _, st_ref, out = render_both(gpu, scene, cam, p)
+    dev, st_dev = O.render(cam, scene, p, 16, device_uv=True)
+    assert st_dev.segments == st_ref.segments
+    assert len(np.unique(np.round(dev.reshape(-1, 3), 2), axis=0)) > 20
+    for accel, (img, st) in out.items():
+        assert st.segments == st_dev.segments
+        assert np.array_equal(img.view(np.uint32), dev.view(np.uint32)), (accel, int((img != dev).any(axis=2).sum()))

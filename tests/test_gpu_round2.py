@@ -461,6 +461,7 @@ def test_every_build_of_the_traversal_kernel(gpu, moving, textured):
             p = vp.params(integrator, R.SAMPLER_ROW)
             p.gamma, p.flags = 1.0, flags
             ref, st_ref = O.render(cam, scene, p, threads=16)
+            dev, _ = O.render(cam, scene, p, threads=16, device_uv=True) if textured else (ref, st_ref)   # the device's texel choice
             for lds_geom in (0, 1):                                            # NODES 1 / 2
                 for extra in (0, R.FLAG_GLOBAL_NODES):                         # NODES 0
                     gpu.set_option(R.OPT_LDS_GEOM, lds_geom)
@@ -468,9 +469,11 @@ def test_every_build_of_the_traversal_kernel(gpu, moving, textured):
                     img, st = gpu.render(cam, p)
                     assert st.node_tests > 0 and st.segments == st_ref.segments, (integrator, flags, lds_geom, extra)
                     assert close(img, ref), (integrator, flags, lds_geom, extra)
+                    assert np.array_equal(img.view(np.uint32), dev.view(np.uint32)), (integrator, flags, lds_geom, extra)
                     seen.add((integrator, flags, lds_geom, extra))
             p.accel, p.flags = R.ACCEL_BRUTE, flags
             img, st = gpu.render(cam, p)
             assert st.segments == st_ref.segments and close(img, ref)
+            assert np.array_equal(img.view(np.uint32), dev.view(np.uint32)), (integrator, flags)
     gpu.set_option(R.OPT_LDS_GEOM, -1)
     assert len(seen) == 16

@@ -101,6 +101,9 @@ def test_rust2_image_texture_on_the_gpu(gpu, shape):
         same = (ulp_diff(im, ref) <= 2).all(axis=2)
         assert same.mean() > 0.995, (accel, same.mean())
     assert np.array_equal(out[R.ACCEL_BRUTE][0], out[R.ACCEL_BVH][0]) and np.array_equal(out[R.ACCEL_BVH][0], out["tree forced"][0])
+    dev, st_dev = O.render(cam, scene, p, 16, device_uv=True)              # the device's atan2 / acos sequences: bit for bit
+    for accel, (im, st) in out.items():
+        assert st.segments == st_dev.segments and np.array_equal(im.view(np.uint32), dev.view(np.uint32)), accel
     # the same scene without the emission image and under the Rust/ lookup (gradient integrator shares nothing else: compare the DIRECT view
     # of the sphere at depth 1 with a white background, where a pixel is emmited + texel)
     p.depth, p.samples = 1, 1                                           # (one sample through the pixel centre: Rust2's fixed-centre sampler)
@@ -114,6 +117,8 @@ def test_rust2_image_texture_on_the_gpu(gpu, shape):
         assert any(np.abs(px - t - e).max() < 1e-6 for t in flat for e in emit.reshape(-1, 3)), px
     O_ref, _ = O.render(cam, scene, p, threads=4)
     assert (ulp_diff(direct, O_ref) <= 2).all(axis=2).mean() > 0.995
+    O_dev, _ = O.render(cam, scene, p, threads=4, device_uv=True)
+    assert np.array_equal(direct.view(np.uint32), O_dev.view(np.uint32))
 
 
 def test_second_hip_runtime_is_refused_loudly(gpu):

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 import rtw_amd as R
-from tests.test_triangles_cpu import adversarial_rays, pods, random_mesh, same, tri_hits_np, tri_new
+from tests.test_triangles_cpu import adversarial_rays, pods, random_mesh, reference_triangle_test, same, tri_hits_np, tri_new
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -152,32 +152,8 @@ def test_render_wild_rays_and_ranges(gpu):
 
 # ---- the reference's own scene ---------------------------------------------------------------------------------------------------
 def test_reference_triangle_test_scene(gpu):
-    W, H, S = 400, 300, 25
-    tri = R.Triangle.new((1, -1, 3), (-1, 2, 0), (-2, 1, 0), R.SCATTER_M, (0.5, 0.5, 0.5), (0.0, 0.0, 0.0))
-    scene = R.Scene([], background=(0.6, 0.6, 0.6), triangles=[tri])
-    cam = R.camera2_new(f32(W) / f32(H), (0, 0, 0), (0, 1, 0), (0, 0, 1), 50.0, 0.0)
-    p = params(R.INTEGRATOR_RUST2, R.SAMPLER_CENTRES, 0, W, H, S, 2)
-    p.mint, p.maxt = 0.0001, 10000.0
+    scene, cam, p, want, hit = reference_triangle_test()             # (the numpy known answer, shared with the oracle's test)
     gpu.set_scene(scene)
-    # numpy: the camera rays of the fixed-centre sampler (Rust2/src/viewport.rs:92-104), coverage by the triangle, 0.6 * 0.5 or 0.6 per
-    # sample, added in sample order and divided by 25
-    s_root = 5
-    i = np.arange(W, dtype=f32)[None, :, None]
-    j = np.arange(H, dtype=f32)[:, None, None]
-    s = np.arange(S)
-    kx, ly = (s // s_root).astype(f32), (s % s_root).astype(f32)
-    jx = (i + (kx + f32(0.5)) / f32(s_root)) / f32(W)
-    jy = (j + (ly + f32(0.5)) / f32(s_root)) / f32(H)
-    p00, du, dv = (np.array(x, f32) for x in (cam.pixel00, cam.delta_u, cam.delta_v))
-    d = (p00 + du * jx[..., None]) + dv * jy[..., None]
-    o = np.broadcast_to(np.array(cam.origin, f32), d.shape)
-    rays = np.concatenate([o, d], -1).reshape(-1, 6)
-    _, hit = tri_hits_np([tri.pod.origin], [tri.pod.u], [tri.pod.v], rays, 0.0001, 10000.0)
-    val = np.where(hit.reshape(H, W, S) >= 0, f32(0.6) * f32(0.5), f32(0.6)).astype(f32)
-    acc = np.zeros((H, W), f32)
-    for q in range(S):
-        acc = acc + val[:, :, q]
-    want = acc / f32(S)
     for accel in (R.ACCEL_BRUTE, R.ACCEL_BVH):
         p.accel = accel
         img, st = gpu.render(cam, p)

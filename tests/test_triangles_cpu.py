@@ -76,6 +76,39 @@ def random_mesh(rng, n, scale=4.0, size=0.6):
     return O, U, V
 
 
+# ---- the reference's triangle_test scene (Rust2/src/objects/triangle.rs:162-200) as a numpy known answer ----------------------------
+def reference_triangle_test():
+    """One grey Lambert triangle (ConstColorTexture(WHITE * 0.5, BLACK)) on a 0.6 background, Rust2's camera and fixed-centre sampler,
+    400 x 300 x 25, depth 2.  The numpy answer: the camera rays of the fixed-centre sampler (Rust2/src/viewport.rs:92-104), coverage by
+    the triangle, 0.6 * 0.5 or 0.6 per sample, added in sample order and divided by 25.
+    Returns (scene, camera, params, want [H][W] f32, hit [H * W * S] triangle index per camera ray)."""
+    W, H, S = 400, 300, 25
+    tri = R.Triangle.new((1, -1, 3), (-1, 2, 0), (-2, 1, 0), R.SCATTER_M, (0.5, 0.5, 0.5), (0.0, 0.0, 0.0))
+    scene = R.Scene([], background=(0.6, 0.6, 0.6), triangles=[tri])
+    cam = R.camera2_new(f32(W) / f32(H), (0, 0, 0), (0, 1, 0), (0, 0, 1), 50.0, 0.0)
+    p = R.RtwParams()
+    p.width, p.height, p.samples, p.depth, p.gamma = W, H, S, 2, 1.0
+    p.mint, p.maxt = 0.0001, 10000.0
+    p.integrator, p.sampler, p.flags, p.seed = R.INTEGRATOR_RUST2, R.SAMPLER_CENTRES, 0, 77
+    s_root = 5
+    i = np.arange(W, dtype=f32)[None, :, None]
+    j = np.arange(H, dtype=f32)[:, None, None]
+    s = np.arange(S)
+    kx, ly = (s // s_root).astype(f32), (s % s_root).astype(f32)
+    jx = (i + (kx + f32(0.5)) / f32(s_root)) / f32(W)
+    jy = (j + (ly + f32(0.5)) / f32(s_root)) / f32(H)
+    p00, du, dv = (np.array(x, f32) for x in (cam.pixel00, cam.delta_u, cam.delta_v))
+    d = (p00 + du * jx[..., None]) + dv * jy[..., None]
+    o = np.broadcast_to(np.array(cam.origin, f32), d.shape)
+    rays = np.concatenate([o, d], -1).reshape(-1, 6)
+    _, hit = tri_hits_np([tri.pod.origin], [tri.pod.u], [tri.pod.v], rays, 0.0001, 10000.0)
+    val = np.where(hit.reshape(H, W, S) >= 0, f32(0.6) * f32(0.5), f32(0.6)).astype(f32)
+    acc = np.zeros((H, W), f32)
+    for q in range(S):
+        acc = acc + val[:, :, q]
+    return scene, cam, p, acc / f32(S), hit
+
+
 # ---- Triangle::new ---------------------------------------------------------------------------------------------------------------
 def test_triangle_new_matches_restatement_bitwise():
     rng = np.random.default_rng(1)
