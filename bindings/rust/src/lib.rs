@@ -73,7 +73,11 @@ impl Proximity { pub fn new(size: u32, kind: ProximityKind) -> Self { Self { siz
 #[repr(C)] pub struct RtwMgpu { _private: [u8; 0] }
 
 #[repr(u32)] #[derive(Clone, Copy)]
-pub enum Integrator { Gradient = 0, BgColor = 1, Normal = 2, Flag = 3, Rust2 = 4 }   // ray_color.rs:12-92; Rust2/src/viewport/ray_color.rs:12-37
+pub enum Integrator { Gradient = 0, BgColor = 1, Normal = 2, Flag = 3, Rust2 = 4, LightCast = 5, LightBiased = 6 }   // ray_color.rs:12-92; Rust2/src/viewport/ray_color.rs:12-37, :55-164
+/// A light of Rust2's light-biased integrators: a top-level sphere (kind 0) or quad (kind 1) of the scene (rtw.h RtwLight).
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct RtwLight { pub kind: u32, pub index: u32 }
+pub const RTW_MAX_LIGHTS: usize = 16;
 #[repr(u32)] #[derive(Clone, Copy)]
 pub enum Sampler { Row = 0, Stratified = 1, Centres = 2, NoRand = 3 }      // viewport.rs:270-305, 430-516
 
@@ -103,6 +107,8 @@ extern "C" {
     fn rtw_triangle_new(origin: *const f32, u: *const f32, v: *const f32, mat3: *const f32, emitted: *const f32,
                         color: *const f32, tex: i32, out: *mut RtwTriangle) -> i32;
     fn rtw_ctx_set_triangles(ctx: *mut RtwCtx, tris: *const RtwTriangle, n: u32) -> i32;
+    fn rtw_ctx_set_lights(ctx: *mut RtwCtx, lights: *const RtwLight, n: u32, biased_weight: f32) -> i32;
+    fn rtw_mgpu_set_lights(m: *mut RtwMgpu, lights: *const RtwLight, n: u32, biased_weight: f32) -> i32;
     fn rtw_mgpu_set_triangles(m: *mut RtwMgpu, tris: *const RtwTriangle, n: u32) -> i32;
     fn rtw_triangle_hits(tris: *const RtwTriangle, n: u32, rays: *const f32, n_rays: u32, mint: f32, maxt: f32,
                          t_out: *mut f32, idx_out: *mut i32) -> i32;
@@ -163,6 +169,12 @@ impl Renderer {
     pub fn set_triangles(&mut self, tris: &[RtwTriangle]) -> Result<(), RtwError> {
         let p = if tris.is_empty() { std::ptr::null() } else { tris.as_ptr() };
         check(unsafe { rtw_ctx_set_triangles(self.ctx, p, tris.len() as u32) })
+    }
+    /// The `lights` / `biased_weight` captures of Rust2's light_biased_ray_cast / light_biased_ray_color closures (an empty slice clears
+    /// them; set_scene clears them): Integrator::LightCast / LightBiased then send one shadow ray per light from every surface hit.
+    pub fn set_lights(&mut self, lights: &[RtwLight], biased_weight: f32) -> Result<(), RtwError> {
+        let p = if lights.is_empty() { std::ptr::null() } else { lights.as_ptr() };
+        check(unsafe { rtw_ctx_set_lights(self.ctx, p, lights.len() as u32, biased_weight) })
     }
     /// The closest of this context's triangles per ray ([origin, direction]) on its GPU: (t, index or -1) per ray.
     pub fn triangle_hits(&mut self, rays: &[[f32; 6]], mint: f32, maxt: f32, accel: u32) -> Result<(Vec<f32>, Vec<i32>), RtwError> {

@@ -50,11 +50,15 @@ enum {
     RTW_INTEGRATOR_BG_COLOR = 1, /* ray_color_bg_color, Rust/src/viewport/ray_color.rs:43-92 (emission + background)        */
     RTW_INTEGRATOR_NORMAL   = 2, /* normal shading of the closest hit, C++/src/tests.cpp:76-97 (ray_colorSc)                */
     RTW_INTEGRATOR_FLAG     = 3, /* RNG-free yellow/blue test integrator, Rust/src/viewport/glass_tests.rs:8-54             */
-    RTW_INTEGRATOR_RUST2    = 4  /* Rust2 `ray_color` (Rust2/src/viewport/ray_color.rs:12-37): emmited + next * multiplied,
+    RTW_INTEGRATOR_RUST2    = 4, /* Rust2 `ray_color` (Rust2/src/viewport/ray_color.rs:12-37): emmited + next * multiplied,
                                     depth 0 and misses return the background, with Rust2's Material trait objects
                                     (Rust2/src/objects/material.rs): opacity > 0 -> MirrorGlass{ir}, metallicness == 1 ->
                                     Mirror (reflects the UN-normalised direction), else Lambertian (unit(n + rand));
                                     ColorResult{emmited, multiplied} = {emitted, tex * col_mod}                             */
+    RTW_INTEGRATOR_LIGHT_CAST = 5,   /* Rust2 `light_biased_ray_cast` (Rust2/src/viewport/ray_color.rs:55-108): ONE surface hit and a shadow ray
+                                    towards every light of rtw_ctx_set_lights; RtwParams.depth is ignored; a miss returns the background */
+    RTW_INTEGRATOR_LIGHT_BIASED = 6  /* Rust2 `light_biased_ray_color` (ray_color.rs:111-164): RTW_INTEGRATOR_RUST2's path, draw for draw,
+                                    plus one shadow ray per light at every surface hit (see "light-biased integrators" below)       */
 };
 
 /* ---- samplers: which driver loop generates the camera rays ---------------------------------- */
@@ -445,6 +449,54 @@ int rtw_triangle_hits(const RtwTriangle *tris, uint32_t n, const float *rays, ui
                       float *t_out, int32_t *idx_out);
 int rtw_ctx_triangle_hits(rtw_ctx *ctx, const float *rays, uint32_t n_rays, float mint, float maxt, uint32_t accel,
                           float *t_out, int32_t *idx_out, RtwStats *stats);
+
+/* ---- light-biased integrators (Rust2/src/viewport/ray_color.rs:55-164, objects/material.rs material_pdf) ---------------------------
+ * RTW_INTEGRATOR_LIGHT_CAST / RTW_INTEGRATOR_LIGHT_BIASED send, from every surface hit h, one shadow ray per light: towards the MID-POINT of
+ * the light's bounding box (no random draw), `Ray::new(h.p, unit(mid - h.p))` with ray.time 0 whatever the path's time.  The light counts when
+ * the closest hit of that ray over the whole scene IS the light (the same top-level object: the reference compares hit records, `hr.0 == hl`,
+ * which differs from this only for coincident duplicate objects).  Then, with e the light's emitted colour at that hit (the constant, or for a
+ * textured sphere Rust2's emission image, RtwTexture.emit_tex), pdf = material_pdf of the SURFACE's material for the shadow ray and
+ * distance2 = t * t * |dir|^2:
+ *   LIGHT_BIASED: skipped when pdf <= 1 / (255 * max(e.x, e.y, e.z)); else count += w, S += e * pdf / distance2 * w   (count starts at 1)
+ *   LIGHT_CAST:   count += 1, S += e * pdf / distance2                                                               (count starts at 0)
+ * and the hit returns (next + S) (.) multiplied / count + emmited (LIGHT_CAST: S (.) multiplied / count + emmited, emmited alone when count == 0),
+ * evaluated front to back (DESIGN.md "Light-biased integrators" gives the association).  Materials as RTW_INTEGRATOR_RUST2 selects them:
+ * opacity > 0 MirrorGlass, metallicness == 1 Mirror, else Lambertian.  Nothing is guarded that the reference does not guard: a hit point that is
+ * the mid-point gives a NaN direction: the reference's sphere test ACCEPTS such a ray (every comparison with its NaN root is false) and reports
+ * the first top-level sphere of the list, so when that sphere is the light a 0 or NaN pdf flows into S, and otherwise nothing is added; a light
+ * that emits nothing gives 1 / 0 = inf as the skip threshold (LIGHT_BIASED always skips it).
+ * The shadow rays draw nothing: the random stream of a LIGHT_BIASED path is RTW_INTEGRATOR_RUST2's, and with no lights set (or w == 0 and
+ * finite terms) the image is RTW_INTEGRATOR_RUST2's bit for bit.  RtwStats.segments counts the shadow queries, camera_rays does not change.
+ * A light names a TOP-LEVEL sphere or quad of the scene; lights inside instances and triangle lights are not expressible.
+ * Renders with these integrators return RTW_E_UNSUPPORTED while triangles or texture noise are set, or when the scene holds a constant-density
+ * instance (its hit draws ln(xi); Rust2 has no media).  Without a light list both integrators are legal (the loop is empty). */
+#define RTW_MAX_LIGHTS 16u
+enum { RTW_LIGHT_SPHERE = 0, RTW_LIGHT_QUAD = 1 };
+typedef struct RtwLight {
+    uint32_t kind;        /* RTW_LIGHT_SPHERE: RtwScene.spheres[index]; RTW_LIGHT_QUAD: RtwScene.quads[index] */
+    uint32_t index;
+} RtwLight;
+/* The lights of the scene of the last rtw_ctx_set_scene (which clears them), and biased_weight (the reference's test uses 100).
+ * lights == NULL with n == 0 clears them.  RTW_E_NO_SCENE before any scene; RTW_E_INVALID for n > RTW_MAX_LIGHTS, a NULL / n mismatch, an
+ * unknown kind or an index beyond the scene, and while a render of the context is pending.  A sphere light's mid-point is formed from
+ * RtwSphere.center alone -- its place at ray.time 0, the time of the shadow rays; the velocity is not read. */
+int rtw_ctx_set_lights(rtw_ctx *ctx, const RtwLight *lights, uint32_t n, float biased_weight);
+int rtw_mgpu_set_lights(rtw_mgpu *m, const RtwLight *lights, uint32_t n, float biased_weight);
+/* Host only (no context, no GPU): the argument checks of rtw_ctx_set_lights for a light list against `scene`: RTW_OK or RTW_E_INVALID. */
+int rtw_lights_validate(const RtwScene *scene, const RtwLight *lights, uint32_t n);
+/* Host only, for tests and tools: the pure pieces, the same definitions the kernels compile (csrc/rtw_light.h).
+ * rtw_light_mid: the mid-point (min + max) * 0.5 per axis of the light's box -- sphere: origin -/+ radius (Rust2/src/objects/sphere.rs:22-34);
+ * quad: its four corners, an axis thinner than 0.005 widened to that about its centre first (objects/quad.rs:53-110).  RTW_E_INVALID as
+ * rtw_ctx_set_lights. */
+int rtw_light_mid(const RtwScene *scene, const RtwLight *light, float mid[3]);
+/* material_pdf(h, r) (objects/material.rs:45-62, 93-99, 199-232) of the material mat3 = {metallicness, opacity, ir} for the hit
+ * h = {p, n, incoming ray direction dir_in and time time_in} and the ray r = {ray_o, ray_d, ray_time}. */
+float rtw_material_pdf(const float mat3[3], const float p[3], const float n[3], const float dir_in[3], float time_in,
+                       const float ray_o[3], const float ray_d[3], float ray_time);
+/* One accepted light of the loop above: updates S[3] and *count as `integrator` (LIGHT_CAST / LIGHT_BIASED) does for a light with emitted
+ * colour e, hit at parameter t by the shadow ray of direction dir.  Returns 1 when the light was added, 0 when LIGHT_BIASED skipped it,
+ * RTW_E_INVALID for another integrator or a NULL pointer. */
+int rtw_light_term(uint32_t integrator, float pdf, const float e[3], float t, const float dir[3], float biased_weight, float S[3], float *count);
 
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 

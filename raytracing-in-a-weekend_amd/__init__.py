@@ -37,6 +37,9 @@ LIB_PATH = os.environ.get("RTW_HIP_LIB", os.path.join(_HERE, "librtw_hip.so"))  
 # ---- enums (include/rtw.h) ---------------------------------------------------------------------
 RTW_OK = 0
 INTEGRATOR_GRADIENT, INTEGRATOR_BG_COLOR, INTEGRATOR_NORMAL, INTEGRATOR_FLAG, INTEGRATOR_RUST2 = 0, 1, 2, 3, 4
+INTEGRATOR_LIGHT_CAST, INTEGRATOR_LIGHT_BIASED = 5, 6   # Rust2 light_biased_ray_cast / light_biased_ray_color (set_lights)
+LIGHT_SPHERE, LIGHT_QUAD = 0, 1                         # RtwLight.kind
+MAX_LIGHTS = 16
 SAMPLER_ROW, SAMPLER_STRATIFIED, SAMPLER_CENTRES, SAMPLER_NO_RAND = 0, 1, 2, 3
 ACCEL_BRUTE, ACCEL_BVH = 0, 1
 FLAG_RECURSIVE_ORDER, FLAG_CPP_DIELECTRIC, FLAG_GLOBAL_NODES, FLAG_CPP_DIFFUSE, FLAG_CHUNK_SUMS = 1, 2, 4, 8, 16
@@ -92,6 +95,10 @@ class RtwTriangle(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3), ("normal", C.c_float * 3), ("d", C.c_float),
                 ("w", C.c_float * 3), ("tex_color", C.c_float * 3), ("metallicness", C.c_float), ("opacity", C.c_float), ("ir", C.c_float),
                 ("emitted", C.c_float * 3), ("tex", C.c_int32)]
+
+
+class RtwLight(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32)]
 
 
 class RtwInstance(C.Structure):
@@ -230,6 +237,13 @@ def lib() -> C.CDLL:
     L.rtw_triangle_hits.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, fp, C.c_uint32, C.c_float, C.c_float, fp, C.POINTER(C.c_int32)]
     L.rtw_ctx_triangle_hits.argtypes = [C.c_void_p, fp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, fp, C.POINTER(C.c_int32),
                                         C.POINTER(RtwStats)]
+    L.rtw_ctx_set_lights.argtypes = [C.c_void_p, C.POINTER(RtwLight), C.c_uint32, C.c_float]
+    L.rtw_mgpu_set_lights.argtypes = [C.c_void_p, C.POINTER(RtwLight), C.c_uint32, C.c_float]
+    L.rtw_lights_validate.argtypes = [C.POINTER(RtwScene), C.POINTER(RtwLight), C.c_uint32]
+    L.rtw_light_mid.argtypes = [C.POINTER(RtwScene), C.POINTER(RtwLight), fp]
+    L.rtw_material_pdf.argtypes = [fp, fp, fp, fp, C.c_float, fp, fp, C.c_float]
+    L.rtw_material_pdf.restype = C.c_float
+    L.rtw_light_term.argtypes = [C.c_uint32, C.c_float, fp, C.c_float, fp, C.c_float, fp, fp]
     _lib = L
     return L
 
@@ -355,6 +369,39 @@ class TriangleArray:
 
     def __getitem__(self, i):
         return Triangle(self.arr[i])
+
+
+def _light_array(lights):
+    """(RtwLight array or None, n) of a sequence of (kind, index) pairs / RtwLight."""
+    if lights is None or len(lights) == 0:
+        return None, 0
+    arr = (RtwLight * len(lights))()
+    for i, l in enumerate(lights):
+        arr[i] = l if isinstance(l, RtwLight) else RtwLight(int(l[0]), int(l[1]))
+    return arr, len(lights)
+
+
+def light_mid(scene: "Scene", light) -> np.ndarray:
+    """rtw_light_mid: the mid-point of the light's bounding box, the point its shadow rays aim at ((kind, index) of a top-level sphere / quad)."""
+    arr, _ = _light_array([light])
+    out = (C.c_float * 3)()
+    _check(lib().rtw_light_mid(C.byref(scene.pod), arr, out), "rtw_light_mid")
+    return np.array(list(out), np.float32)
+
+
+def material_pdf(mat, p, n, dir_in, time_in, ray_o, ray_d, ray_time) -> np.float32:
+    """rtw_material_pdf: Rust2's material_pdf(h, r) of mat = (metallicness, opacity, ir)."""
+    return np.float32(lib().rtw_material_pdf(_f3(mat), _f3(p), _f3(n), _f3(dir_in), float(time_in), _f3(ray_o), _f3(ray_d), float(ray_time)))
+
+
+def light_term(integrator: int, pdf, e, t, direction, weight, S, count):
+    """rtw_light_term: (added, S, count) after one accepted light of the light loop."""
+    s = _f3(S)
+    c = C.c_float(float(count))
+    rc = lib().rtw_light_term(int(integrator), float(pdf), _f3(e), float(t), _f3(direction), float(weight), s, C.byref(c))
+    if rc < 0:
+        _check(rc, "rtw_light_term")
+    return bool(rc), np.array(list(s), np.float32), np.float32(c.value)
 
 
 def _triangle_array(triangles):
@@ -810,6 +857,12 @@ class Renderer:
         self._tris = _triangle_array(triangles)
         _check(lib().rtw_ctx_set_triangles(self._h, *self._tris), "rtw_ctx_set_triangles")
 
+    def set_lights(self, lights=None, biased_weight: float = 100.0):
+        """rtw_ctx_set_lights for the current scene: (kind, index) pairs naming top-level spheres / quads (None: clear).  The lights of
+        INTEGRATOR_LIGHT_CAST / INTEGRATOR_LIGHT_BIASED; a new scene clears them."""
+        arr, n = _light_array(lights)
+        _check(lib().rtw_ctx_set_lights(self._h, arr, n, float(biased_weight)), "rtw_ctx_set_lights")
+
     def triangle_hits(self, rays, mint: float, maxt: float, accel: int = ACCEL_BVH):
         """The closest of this context's triangles per ray on its GPU (rtw_ctx_triangle_hits): (t, index, RtwStats) as triangle_hits."""
         r = _rays(rays)
@@ -927,6 +980,11 @@ class MultiRenderer:
             return
         self._tris = _triangle_array(triangles)
         _check(lib().rtw_mgpu_set_triangles(self._h, *self._tris), "rtw_mgpu_set_triangles")
+
+    def set_lights(self, lights=None, biased_weight: float = 100.0):
+        """rtw_mgpu_set_lights on every device (None: clear them)."""
+        arr, n = _light_array(lights)
+        _check(lib().rtw_mgpu_set_lights(self._h, arr, n, float(biased_weight)), "rtw_mgpu_set_lights")
 
     def set_option(self, key: int, value: float):
         _check(lib().rtw_mgpu_set_option(self._h, int(key), float(value)), "rtw_mgpu_set_option")

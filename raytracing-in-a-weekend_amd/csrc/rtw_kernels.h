@@ -2,6 +2,7 @@
 #pragma once
 #include "rtw_device.h"
 #include "rtw_tri.h"
+#include "rtw_light.h"
 #include "rtw_host.h"
 
 #define RTW_QUEUE_BYTES 4096u   // the work queue's counters (KArgs.queue): up to 8 sub-queues ...
@@ -79,6 +80,8 @@ struct KArgs {
     DevNoise noise;               // texture noise (rtw_ctx_set_texture_noise); noise.tex != null selects the noise build (SPEC 7), which alone reads it
     DevTris tris;                 // Rust2 triangles (rtw_ctx_set_triangles); tris.n != 0 selects the triangle build (SPEC 8), which alone reads it;
                                   // tris.nodes == null: walk the triangle list
+    DevLights lights;             // the light list (rtw_ctx_set_lights); read by the light build (SPEC 9) alone, which RTW_INTEGRATOR_LIGHT_CAST /
+                                  // _LIGHT_BIASED select
 };
 
 // accel: RTW_ACCEL_BRUTE, RTW_ACCEL_BVH; the BVH launch picks the LDS-resident variant when a.bvh.nodes16 != null

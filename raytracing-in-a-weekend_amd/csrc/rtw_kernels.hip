@@ -52,9 +52,11 @@ namespace rtw {
 // SPEC == 0 reads everything from the (wave-uniform) kernel arguments.  SPEC == 7 is SPEC == 0 plus the noise of image textures (texture.rs:
 // 259-267, rtw_ctx_set_texture_noise): the generic step with noise(p / scale) in place of the texel's `* 1.0`; only scenes with noise select it.
 // SPEC == 8 is SPEC == 0 plus Rust2's triangles (rtw_ctx_set_triangles): the closest-hit stage after the instances walks their list or tree;
-// only scenes with triangles select it.
+// only scenes with triangles select it.  SPEC == 9 is the generic build's driver (every sampler, RtwParams.flags) with Rust2's light-biased integrators
+// (rtw_light.h, rtw_ctx_set_lights) as its step: only RTW_INTEGRATOR_LIGHT_CAST / _LIGHT_BIASED select it, and it runs no other integrator.
 constexpr bool gradient_spec(int spec) { return spec >= 1 && spec <= 3; }
-constexpr bool generic_spec(int spec) { return spec == 0 || spec == 7 || spec == 8; }
+constexpr bool generic_spec(int spec) { return spec == 0 || spec == 7 || spec == 8 || spec == 9; }
+constexpr bool light_spec(int spec) { return spec == 9; }
 constexpr bool noise_spec(int spec) { return spec == 7; }
 constexpr bool tri_spec(int spec) { return spec == 8; }
 template <int SPEC> __device__ __forceinline__ uint32_t integ(const KArgs &A) {
@@ -416,6 +418,163 @@ __device__ __forceinline__ bool shade_geom(const KArgs &A, Path &pt, int best, f
     return shade<MOVING, SPEC>(A, pt, best, best_t);
 }
 
+template <bool MOVING>
+__device__ __forceinline__ void closest_brute(const DevScene &sc, v3 o, v3 d, float tm, float mint, float maxt, int &best, float &best_t);   // (below)
+
+// ---- the light build (SPEC 9): Rust2's light_biased_ray_cast / light_biased_ray_color (rtw_light.h) --------------------------------------
+// A surface hit owes one shadow query per light before its path goes on.  The pieces below are shared by both render kernels: render_brute
+// runs the queries in a loop (a straight second list walk per light), render_bvh hands them to its scheduler one at a time.
+
+// The `Hit` of the path's closest-hit query and ColorResult of its object, as RTW_INTEGRATOR_RUST2 forms them (shade_geom / shade_hit).
+// False on a miss.
+template <bool MOVING, bool GEOM>
+__device__ __forceinline__ bool light_path_hit(const KArgs &A, Path &pt, int best, float best_t, v3 &point, v3 &normal, v3 &cm, MatP &m, v3 &emitted,
+                                               uint32_t &n_sph, uint32_t &n_quad) {
+    if constexpr (GEOM) {
+        GeomHit h;
+        if (geom_closest<false>(A.sc, A.noise, A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, pt.rng, h, n_sph, n_quad)) {
+            mat_derive(h.m);
+            point = h.point; normal = h.normal; cm = h.cm; m = h.m; emitted = h.emitted;
+            return true;
+        }
+    }
+    if (best < 0) return false;
+    const DevScene &sc = A.sc;
+    f4 g = sc.geom[best];
+    v3 c = mk(g.x, g.y, g.z);
+    if (MOVING) { f4 vv = sc.vel[best]; c = c + mk(vv.x, vv.y, vv.z) * pt.tm; }
+    point = pt.o + pt.d * best_t;
+    normal = unit(point - c);
+    const DevMat mat = sc.mat[best];
+    emitted = ld3(mat.emitted);
+    if (mat.tex >= 0) rust2_sphere_color(sc, mat, normal, cm, emitted);
+    else cm = ld3(mat.cm);
+    m = mat_params(mat);
+    return true;
+}
+
+// At the surface hit: keep what material_pdf and the combination need, draw the scattered ray (light_biased_ray_color calls o.reflect(&h) first,
+// ray_color.rs:124; light_biased_ray_cast draws nothing), move the path's origin to the hit point.
+__device__ __forceinline__ void light_surface(const KArgs &A, Path &pt, v3 point, v3 normal, v3 cm, const MatP m, v3 emitted, LightPath &lp) {
+    const bool biased = A.integrator == RTW_INTEGRATOR_LIGHT_BIASED;
+    lp.n = normal; lp.din = pt.d; lp.tm = pt.tm;
+    lp.metallicness = m.metallicness; lp.opacity = m.opacity; lp.ir = m.ir;
+    lp.cm = cm; lp.e = emitted;
+    lp.S = mk(0, 0, 0); lp.count = biased ? 1.0f : 0.0f;
+    v3 scat = mk(0, 0, 0);
+    if (biased) scat = on_hit_rust2(m, normal, pt.d, pt.rng, A.flags);
+    lp.scat = scat;
+    pt.o = point;
+}
+
+// The shadow ray towards light i: Ray::new(h.p, unit(mid - h.p)), time 0 (ray_color.rs:136-137)
+__device__ __forceinline__ void light_ray(uint32_t i, Path &pt) {
+    const f4 row = light_row((uint32_t)offsetof(KArgs, lights), i);
+    const v3 mid = mk(row.x, row.y, row.z);
+    const v3 to = mid - pt.o;
+    pt.d = to / len(to);
+    pt.tm = 0.0f;
+}
+
+// The shadow query of light i is complete: (best, best_t) its sphere part.  Finishes Scene::collision_normal for it (GEOM) and, when the
+// closest object IS the light, adds the light's term.
+template <bool MOVING, bool GEOM>
+__device__ __forceinline__ void light_result(const KArgs &A, uint32_t i, const Path &pt, int best, float best_t, LightPath &lp, uint32_t &n_sph, uint32_t &n_quad) {
+    uint32_t code = best >= 0 ? (uint32_t)best : LIGHT_HIT_NONE;
+    float t = best_t;
+    if constexpr (GEOM) {
+        float tg;
+        const uint32_t cg = shadow_geom_pick(A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, tg, n_sph, n_quad);
+        if (cg != LIGHT_HIT_NONE) { code = cg; t = tg; }
+    }
+    const f4 row = light_row((uint32_t)offsetof(KArgs, lights), i);
+    const float code_bits = row.w;
+    if (code != __float_as_uint(code_bits) || code >= LIGHT_HIT_NONE) return;
+    v3 e;
+    if (code & LIGHT_HIT_QUAD) {
+        e = ld3(A.geom.quads[code & ~LIGHT_HIT_QUAD].emitted);
+    } else {
+        const DevMat mat = A.sc.mat[code];
+        e = ld3(mat.emitted);
+        if (mat.tex >= 0) {                                   // Rust2's emission image at the shadow ray's hit
+            f4 g = A.sc.geom[code];
+            v3 c = mk(g.x, g.y, g.z);
+            if (MOVING) { f4 vv = A.sc.vel[code]; c = c + mk(vv.x, vv.y, vv.z) * pt.tm; }
+            v3 cm_unused;
+            rust2_sphere_color(A.sc, mat, unit((pt.o + pt.d * t) - c), cm_unused, e);
+        }
+    }
+    const float pdf = light_material_pdf(lp.metallicness, lp.opacity, lp.ir, tol(pt.o), tol(lp.n), tol(lp.din), lp.tm, tol(pt.o), tol(pt.d), pt.tm);
+    lv3 S = tol(lp.S);
+    light_add(A.integrator == RTW_INTEGRATOR_LIGHT_BIASED, pdf, tol(e), t, tol(pt.d), A.lights.weight, S, lp.count);
+    lp.S = mk(S.x, S.y, S.z);
+}
+
+// Every light has been asked: the hit's return value, front to back (DESIGN.md "Light-biased integrators"):
+//   LIGHT_BIASED  L += thr (.) ((S (.) m) / count + e),  thr = thr (.) (m / count), the scattered ray goes on (depth as RTW_INTEGRATOR_RUST2)
+//   LIGHT_CAST    L = (S (.) m) / count + e  (e alone when count == 0); the path ends
+// Returns true when the path is finished.
+__device__ __forceinline__ bool light_finish(const KArgs &A, Path &pt, const LightPath &lp) {
+    if (A.integrator != RTW_INTEGRATOR_LIGHT_BIASED) {
+        v3 c = mk(0, 0, 0);
+        if (lp.count != 0.0f) c = (lp.S * lp.cm) / lp.count;
+        pt.L = c + lp.e;
+        return true;
+    }
+    pt.L = pt.L + pt.thr * ((lp.S * lp.cm) / lp.count + lp.e);
+    pt.thr = pt.thr * (lp.cm / lp.count);
+    pt.d = lp.scat; pt.tm = lp.tm;
+    pt.k++;
+    if (pt.k >= A.depth) { pt.L = pt.L + ld3(A.bg) * pt.thr; return true; }
+    return false;
+}
+
+// render_brute: the whole step for a lane whose path query returned (best, best_t) -- the shadow queries are list walks of their own.
+template <bool MOVING, bool GEOM>
+__device__ __forceinline__ bool light_step_brute(const KArgs &A, Path &pt, int best, float best_t, uint32_t &n_seg, uint32_t &n_sph, uint32_t &n_quad) {
+    v3 point, normal, cm, emitted; MatP m;
+    if (!light_path_hit<MOVING, GEOM>(A, pt, best, best_t, point, normal, cm, m, emitted, n_sph, n_quad)) {
+        pt.L = pt.L + ld3(A.bg) * pt.thr;
+        return true;
+    }
+    LightPath lp;
+    light_surface(A, pt, point, normal, cm, m, emitted, lp);
+    const uint32_t n = A.lights.n;
+    for (uint32_t i = 0; i < n; ++i) {
+        light_ray(i, pt);
+        int sb; float st;
+        closest_brute<MOVING>(A.sc, pt.o, pt.d, pt.tm, A.mint, A.maxt, sb, st);
+        n_seg++;
+        light_result<MOVING, GEOM>(A, i, pt, sb, st, lp, n_sph, n_quad);
+    }
+    return light_finish(A, pt, lp);
+}
+
+// render_bvh: one SHADE step of a lane whose query is complete.  `fl` carries LF_SHADOW (the query was a shadow query) and the pending
+// light (rtw_light.h); the caller starts the next query -- shadow or path -- from pt.o / pt.d / pt.tm like any other.
+template <bool MOVING, bool GEOM>
+__device__ __forceinline__ bool light_step_bvh(const KArgs &A, Path &pt, LightPath &lp, uint32_t &fl, int best, float best_t, uint32_t &n_sph, uint32_t &n_quad) {
+    const uint32_t n = A.lights.n;
+    if (!(fl & LF_SHADOW)) {                               // path result
+        v3 point, normal, cm, emitted; MatP m;
+        if (!light_path_hit<MOVING, GEOM>(A, pt, best, best_t, point, normal, cm, m, emitted, n_sph, n_quad)) {
+            pt.L = pt.L + ld3(A.bg) * pt.thr;
+            return true;
+        }
+        light_surface(A, pt, point, normal, cm, m, emitted, lp);
+        if (n == 0u) return light_finish(A, pt, lp);
+        fl |= LF_SHADOW;                                      // (light 0: the pending-light bits are clear)
+        light_ray(0u, pt);
+        return false;
+    }
+    uint32_t i = (fl & LF_LIGHT_MASK) >> LF_LIGHT_SHIFT;                           // shadow result: one compare, the pdf, a few dozen VALU
+    light_result<MOVING, GEOM>(A, i, pt, best, best_t, lp, n_sph, n_quad);
+    i++;
+    if (i < n) { fl += 1u << LF_LIGHT_SHIFT; light_ray(i, pt); return false; }
+    fl &= ~(LF_SHADOW | LF_LIGHT_MASK);
+    return light_finish(A, pt, lp);
+}
+
 // A path ended: bank its radiance in the sample buffer (the resolve kernel adds the samples of a pixel
 // in sample order, viewport.rs:299).  Returns true when the unit is done.
 template <int SPEC>
@@ -572,13 +731,16 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? RTW_GEOM_BRUTE_WAVES : 1) void re
         if (have && newpath) { newpath = false; start_path<SPEC>(A, px, pt); n_rays++; }
         if (have) {
             bool finished;
-            if (generic_spec(SPEC) && A.depth == 0 && A.integrator != RTW_INTEGRATOR_NORMAL) {   // `if depth < 1 { return black }` (ray_color.rs:14-16)
-                pt.L = A.integrator == RTW_INTEGRATOR_RUST2 ? ld3(A.bg) : mk(0, 0, 0); finished = true;
+            // (the light build: light_biased_ray_color returns the background at depth 0, light_biased_ray_cast ignores the depth)
+            if (light_spec(SPEC) ? (A.depth == 0 && A.integrator == RTW_INTEGRATOR_LIGHT_BIASED)
+                                 : (generic_spec(SPEC) && A.depth == 0 && A.integrator != RTW_INTEGRATOR_NORMAL)) {   // `if depth < 1 { return black }` (ray_color.rs:14-16)
+                pt.L = (light_spec(SPEC) || A.integrator == RTW_INTEGRATOR_RUST2) ? ld3(A.bg) : mk(0, 0, 0); finished = true;
             } else {
                 int best; float best_t;
                 closest_brute<MOVING>(A.sc, pt.o, pt.d, pt.tm, A.mint, A.maxt, best, best_t);
                 n_seg++;
-                finished = GEOM ? shade_geom<MOVING, SPEC>(A, pt, best, best_t, n_isph, n_quad) : shade<MOVING, SPEC>(A, pt, best, best_t);
+                if constexpr (light_spec(SPEC)) finished = light_step_brute<MOVING, GEOM>(A, pt, best, best_t, n_seg, n_isph, n_quad);
+                else finished = GEOM ? shade_geom<MOVING, SPEC>(A, pt, best, best_t, n_isph, n_quad) : shade<MOVING, SPEC>(A, pt, best, best_t);
             }
             if (finished) {
                 if (finish_path<SPEC>(A, px, pt)) have = false;
@@ -974,6 +1136,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
                       F_INFLIGHT = 2u,   // a closest-hit query is in flight / complete and waiting to be shaded
                       F_NEWPATH = 4u,    // the next SHADE step starts the next sample of the unit
                       F_DONE = 8u,       // a finished path waits for the next SHADE step to bank it
+                                         // (the light build adds LF_SHADOW and the pending light: rtw_light.h)
                       F_K_SHIFT = 8u };  // specialised builds: the path's bounce count (Path.k) in bits 8..31
     uint32_t fl = 0u;
     Pixel px; px.ij = px.rng_base = px.s = px.slot = 0;
@@ -982,6 +1145,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
     rs.t_dry = 0ull;
 #endif
     Path pt; pt.o = pt.d = pt.L = mk(0, 0, 0); pt.thr = mk(1, 1, 1); pt.tm = 0; pt.k = 0; pt.poison = false; pt.rng.state = 0; pt.rng.inc = 1;
+    typename std::conditional<light_spec(SPEC), LightPath, char>::type lp{};      // the light build: what a surface hit keeps while its shadow queries run
     Trav tr; tr.node = (int)Code<stack_t>::END; tr.sp = 0; tr.best = -1; tr.best_t = 0; tr.a = tr.ra = 1; tr.ix = tr.iy = tr.iz = 0;
     tr.kpx = tr.kpy = tr.kpz = tr.kmx = tr.kmy = tr.kmz = 0; tr.selx = tr.sely = tr.selz = 0; tr.tau_t = tr.lo_lim = tr.hi_lim = 0;
     // Work counters live in SGPRs: they are sums of ballot popcounts the scheduler computes anyway (node visits ==
@@ -1111,7 +1275,10 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
                 RTW_CEN(cn, CEN_SHADING);
                 if (fl & F_INFLIGHT) {
                     fl &= ~F_INFLIGHT;
-                    const bool done = GEOM ? shade_geom<MOVING, SPEC>(A, pt, tr.best, tr.best_t, n_isph, n_quad) : shade<MOVING, SPEC>(A, pt, tr.best, tr.best_t, cn);
+                    bool done;
+                    // (the light build: a path result or a shadow result; the lane's next query, shadow or path, starts below like any other)
+                    if constexpr (light_spec(SPEC)) done = light_step_bvh<MOVING, GEOM>(A, pt, lp, fl, tr.best, tr.best_t, n_isph, n_quad);
+                    else done = GEOM ? shade_geom<MOVING, SPEC>(A, pt, tr.best, tr.best_t, n_isph, n_quad) : shade<MOVING, SPEC>(A, pt, tr.best, tr.best_t, cn);
                     if (done) fl |= F_DONE;
                 }
             }
@@ -1146,12 +1313,14 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
                     // c. next camera ray (a lane whose path continues keeps its scattered ray)
                     if (fl & F_NEWPATH) { fl &= ~F_NEWPATH; start_path<SPEC>(A, px, pt, cn); started = true; }
                     // d. start the next closest-hit query
-                    if (generic_spec(SPEC) && A.depth == 0 && A.integrator != RTW_INTEGRATOR_NORMAL) {   // `if depth < 1 { return black }` (ray_color.rs:14-16)
-                        pt.L = A.integrator == RTW_INTEGRATOR_RUST2 ? ld3(A.bg) : mk(0, 0, 0);
+                    if (light_spec(SPEC) ? (A.depth == 0 && A.integrator == RTW_INTEGRATOR_LIGHT_BIASED)
+                                         : (generic_spec(SPEC) && A.depth == 0 && A.integrator != RTW_INTEGRATOR_NORMAL)) {   // `if depth < 1 { return black }` (ray_color.rs:14-16)
+                        pt.L = (light_spec(SPEC) || A.integrator == RTW_INTEGRATOR_RUST2) ? ld3(A.bg) : mk(0, 0, 0);
                         fl |= F_DONE;                                      // banked on the next SHADE trip
                     } else {
                         trav_begin<MOVING, stack_t>(A, pt, tr, lds_addr(lds_raw) + A.lds_stack_off + threadIdx.x * (uint32_t)sizeof(stack_t), a_plain, a_odd, cn);
-                        if constexpr (GEOM) wild_ray_query<MOVING, stack_t>(A, pt, tr, n_isph);
+                        // (the light build asks for it without quads too: a hit point that IS a light's mid-point makes the shadow direction NaN)
+                        if constexpr (GEOM || light_spec(SPEC)) wild_ray_query<MOVING, stack_t>(A, pt, tr, n_isph);
                         fl |= F_INFLIGHT;
                     }
                 }
@@ -1222,7 +1391,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
 #endif
     }
     if constexpr (tri_spec(SPEC)) tri_nodes_end(A);
-    if (GEOM) { flush_quads(A, n_quad); flush_tests(A, n_isph); }
+    if (GEOM || light_spec(SPEC)) { flush_quads(A, n_quad); flush_tests(A, n_isph); }
 #ifdef RTW_CENSUS
     for (int k = 0; k < CEN_N; k++) {          // diagnostic build: stats[32 + 2k] = wave-level executions of sub-block k, [33 + 2k] = lanes live in them
         unsigned long long w = cn->w[k], n = cn->n[k];
@@ -1313,6 +1482,9 @@ static kernel_fn pick_kernel_geom(bool moving, uint32_t accel, int nodes) {
 }
 static kernel_fn pick_kernel(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
     const int nodes = lds_nodes ? (a.lds_geom_off ? 2 : 1) : 0;
+    // Rust2's light-biased integrators: the light build, for every sampler and flag (rtw_shim.hip refuses them with noise or triangles)
+    if (a.integrator == RTW_INTEGRATOR_LIGHT_CAST || a.integrator == RTW_INTEGRATOR_LIGHT_BIASED)
+        return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<9>(moving, accel, nodes) : pick_kernel_spec<9>(moving, accel, nodes);
     // a texture that a sphere, quad or member uses has noise (rtw_shim.hip sets noise.tex only then): the noise build, for every integrator, sampler and flag
     if (a.noise.tex) return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<7>(moving, accel, nodes) : pick_kernel_spec<7>(moving, accel, nodes);
     // triangles (rtw_shim.hip sets tris.n only then; never together with noise): the triangle build, for every integrator, sampler and flag

@@ -60,6 +60,11 @@ struct rtw_ctx {
     const TriNode *tri_nodes = nullptr;
     bool tri_tree = false;               // no triangle breaks the cull's derivation (DESIGN.md "Rust2 triangles")
     void *d_tri_list = nullptr, *d_tri_leaf = nullptr, *d_tri_nodes = nullptr;
+    // lights of the scene (rtw_ctx_set_lights; cleared by rtw_ctx_set_scene): the rows the light build reads from its arguments
+    DevLights lights{};
+    std::vector<RtwSphere> h_spheres;    // host copies of the top-level spheres and quads: a light's mid-point is formed from them
+    std::vector<RtwQuad> h_quads;
+    bool has_medium = false;             // an instance of the scene is a constant-density medium (the light integrators refuse it)
     // scratch
     uint32_t *d_queue = nullptr;
     unsigned long long *d_stats = nullptr;
@@ -257,6 +262,8 @@ static void free_scene(rtw_ctx *c) {
     for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
     free_noise(c);
     free_tris(c);
+    c->lights = DevLights{};
+    c->h_spheres.clear(); c->h_quads.clear(); c->has_medium = false;
     c->n_textures = 0;
     c->tex_used.clear();
     c->has_scene = false;
@@ -421,7 +428,83 @@ int rtw_ctx_set_scene(rtw_ctx *c, const RtwScene *s, float t_begin, float t_end)
     for (uint32_t i = 0; i < s->n_inst_spheres; i++) if (s->inst_spheres[i].tex >= 0) c->tex_used[s->inst_spheres[i].tex] = 1;
     for (uint32_t i = 0; i < s->n_quads; i++) if (s->quads[i].tex >= 0) c->tex_used[s->quads[i].tex] = 1;
     for (uint32_t i = 0; i < s->n_inst_quads; i++) if (s->inst_quads[i].tex >= 0) c->tex_used[s->inst_quads[i].tex] = 1;
+    c->h_spheres.assign(s->spheres, s->spheres + s->n_spheres);
+    c->h_quads.assign(s->quads, s->quads + s->n_quads);
+    for (uint32_t i = 0; i < s->n_instances; i++) if (s->instances[i].medium == RTW_MEDIUM_CONST_DENSITY) c->has_medium = true;
     c->has_scene = true;
+    return RTW_OK;
+}
+
+// ---- lights (rtw.h "light-biased integrators") ----------------------------------------------------------------------------------------
+// The argument checks shared by rtw_ctx_set_lights and rtw_light_mid, and the light's row {mid-point, object code}.
+static int light_row_of(const RtwSphere *spheres, uint32_t n_spheres, const RtwQuad *quads, uint32_t n_quads, const RtwLight &l, float row[4]) {
+    uint32_t code;
+    if (l.kind == RTW_LIGHT_SPHERE) {
+        if (l.index >= n_spheres || !spheres) return RTW_E_INVALID;
+        light_mid_sphere(spheres[l.index].center, spheres[l.index].radius, row);
+        code = l.index;
+    } else if (l.kind == RTW_LIGHT_QUAD) {
+        if (l.index >= n_quads || !quads || l.index >= LIGHT_HIT_QUAD) return RTW_E_INVALID;
+        light_mid_quad(quads[l.index].origin, quads[l.index].u, quads[l.index].v, row);
+        code = LIGHT_HIT_QUAD | l.index;
+    } else return RTW_E_INVALID;
+    std::memcpy(&row[3], &code, sizeof code);
+    return RTW_OK;
+}
+
+int rtw_light_mid(const RtwScene *scene, const RtwLight *light, float mid[3]) {
+    if (!scene || !light || !mid) return RTW_E_INVALID;
+    float row[4];
+    const int rc = light_row_of(scene->spheres, scene->n_spheres, scene->quads, scene->n_quads, *light, row);
+    if (rc != RTW_OK) return rc;
+    mid[0] = row[0]; mid[1] = row[1]; mid[2] = row[2];
+    return RTW_OK;
+}
+
+float rtw_material_pdf(const float mat3[3], const float p[3], const float n[3], const float dir_in[3], float time_in,
+                       const float ray_o[3], const float ray_d[3], float ray_time) {
+    if (!mat3 || !p || !n || !dir_in || !ray_o || !ray_d) return NAN;
+    return light_material_pdf(mat3[0], mat3[1], mat3[2], lmk(p[0], p[1], p[2]), lmk(n[0], n[1], n[2]), lmk(dir_in[0], dir_in[1], dir_in[2]), time_in,
+                              lmk(ray_o[0], ray_o[1], ray_o[2]), lmk(ray_d[0], ray_d[1], ray_d[2]), ray_time);
+}
+
+int rtw_light_term(uint32_t integrator, float pdf, const float e[3], float t, const float dir[3], float biased_weight, float S[3], float *count) {
+    if (!e || !dir || !S || !count) return RTW_E_INVALID;
+    if (integrator != RTW_INTEGRATOR_LIGHT_CAST && integrator != RTW_INTEGRATOR_LIGHT_BIASED) return RTW_E_INVALID;
+    lv3 s = lmk(S[0], S[1], S[2]);
+    const bool added = light_add(integrator == RTW_INTEGRATOR_LIGHT_BIASED, pdf, lmk(e[0], e[1], e[2]), t, lmk(dir[0], dir[1], dir[2]), biased_weight, s, *count);
+    S[0] = s.x; S[1] = s.y; S[2] = s.z;
+    return added ? 1 : 0;
+}
+
+// The checks of a light list against a scene's top-level spheres and quads, and its rows: shared by rtw_lights_validate (host only) and
+// rtw_ctx_set_lights.  rows may be null.
+static int lights_check(const RtwSphere *spheres, uint32_t n_spheres, const RtwQuad *quads, uint32_t n_quads, const RtwLight *lights, uint32_t n,
+                        float (*rows)[4]) {
+    if ((n && !lights) || (!n && lights) || n > RTW_MAX_LIGHTS) return RTW_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        float row[4];
+        const int rc = light_row_of(spheres, n_spheres, quads, n_quads, lights[i], row);
+        if (rc != RTW_OK) return rc;
+        if (rows) std::memcpy(rows[i], row, sizeof row);
+    }
+    return RTW_OK;
+}
+
+int rtw_lights_validate(const RtwScene *scene, const RtwLight *lights, uint32_t n) {
+    if (!scene) return RTW_E_INVALID;
+    return lights_check(scene->spheres, scene->n_spheres, scene->quads, scene->n_quads, lights, n, nullptr);
+}
+
+int rtw_ctx_set_lights(rtw_ctx *c, const RtwLight *lights, uint32_t n, float biased_weight) {
+    if (!c) return RTW_E_INVALID;
+    if (!c->has_scene) return RTW_E_NO_SCENE;
+    if (c->pend.active) return RTW_E_INVALID;
+    DevLights d{};
+    const int rc = lights_check(c->h_spheres.data(), (uint32_t)c->h_spheres.size(), c->h_quads.data(), (uint32_t)c->h_quads.size(), lights, n, d.row);
+    if (rc != RTW_OK) return rc;
+    d.n = n; d.weight = biased_weight;
+    c->lights = d;
     return RTW_OK;
 }
 
@@ -620,11 +703,14 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     if (c->pend.active) return RTW_E_INVALID;
     if (!c->has_scene) return RTW_E_NO_SCENE;
     if (p->width == 0 || p->height == 0 || p->samples == 0) return RTW_E_INVALID;
-    if (p->integrator > RTW_INTEGRATOR_RUST2 || p->sampler > RTW_SAMPLER_NO_RAND || p->accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    if (p->integrator > RTW_INTEGRATOR_LIGHT_BIASED || p->sampler > RTW_SAMPLER_NO_RAND || p->accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
     if (p->part_count > 1 && (p->row_block == 0 || p->part_index >= p->part_count)) return RTW_E_INVALID;
     if (p->width > 65535u || p->height > 65535u) return RTW_E_INVALID;      // a lane keeps (column, row) in one register (rtw_kernels.hip Pixel)
     if (c->noise_active && p->integrator == RTW_INTEGRATOR_RUST2) return RTW_E_UNSUPPORTED;   // Rust2's textures have no noise
     if (c->noise_active && c->tris.n) return RTW_E_UNSUPPORTED;                              // (rtw_ctx_set_triangles / _set_texture_noise refuse it too)
+    const bool light_integrator = p->integrator == RTW_INTEGRATOR_LIGHT_CAST || p->integrator == RTW_INTEGRATOR_LIGHT_BIASED;
+    // Rust2's light-biased integrators: no noise (Rust2's textures have none), no triangle lights or occluders yet, no media (Rust2 has none)
+    if (light_integrator && (c->noise_active || c->tris.n || c->has_medium)) return RTW_E_UNSUPPORTED;
     if (!c->pend.marked) c->pend.t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(c->device));
 
@@ -658,6 +744,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
             const float ta = cam->time0, tb = cam->time0 + cam->shutter;
             if (!(std::fmin(ta, tb) >= c->t_begin && std::fmax(ta, tb) <= c->t_end)) accel = RTW_ACCEL_BRUTE;
             if (ta != ta || tb != tb) accel = RTW_ACCEL_BRUTE;         // (fmin / fmax drop a NaN: a NaN shutter makes every moving centre NaN, which only the list walk answers like the reference)
+            if (light_integrator && !(c->t_begin <= 0.0f && c->t_end >= 0.0f)) accel = RTW_ACCEL_BRUTE;   // the shadow rays run at ray.time 0
         }
         if (!c->bvh_ok) accel = RTW_ACCEL_BRUTE;
         // a handful of spheres: the list walk IS the fastest closest-hit (the traversal scheduler only costs)
@@ -684,6 +771,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     a.queue = c->d_queue; a.stats = c->d_stats;
     if (c->noise_active) a.noise = c->noise;                       // (selects the noise build: pick_kernel)
     if (c->tris.n) a.tris = tri_view(c, p->accel, p->mint, p->maxt);   // (selects the triangle build; the tree for RTW_ACCEL_BVH requests)
+    if (light_integrator) a.lights = c->lights;                    // (the integrator selects the light build, which alone reads them)
 #ifdef RTW_ENDTIMES
     if (const char *e = getenv("RTW_ENDTIMES_REF")) a.endtimes_ref = std::strtoull(e, nullptr, 10);       // diagnostic build only
 #endif
@@ -1059,6 +1147,12 @@ int rtw_mgpu_set_scene(rtw_mgpu *m, const RtwScene *scene, float t_begin, float 
 int rtw_mgpu_set_texture_noise(rtw_mgpu *m, const RtwPerlin *tables, uint32_t n_tables, const RtwTextureNoise *per_texture, uint32_t n_textures) {
     if (!m) return RTW_E_INVALID;
     for (rtw_ctx *c : m->ctx) { int rc = rtw_ctx_set_texture_noise(c, tables, n_tables, per_texture, n_textures); if (rc != RTW_OK) return rc; }
+    return RTW_OK;
+}
+
+int rtw_mgpu_set_lights(rtw_mgpu *m, const RtwLight *lights, uint32_t n, float biased_weight) {
+    if (!m) return RTW_E_INVALID;
+    for (rtw_ctx *c : m->ctx) { int rc = rtw_ctx_set_lights(c, lights, n, biased_weight); if (rc != RTW_OK) return rc; }
     return RTW_OK;
 }
 
