@@ -78,6 +78,9 @@ pub enum Integrator { Gradient = 0, BgColor = 1, Normal = 2, Flag = 3, Rust2 = 4
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct RtwLight { pub kind: u32, pub index: u32 }
 pub const RTW_MAX_LIGHTS: usize = 16;
+/// RtwParams.flags bit (rtw.h): under the Rust2 integrators an object with opacity < 0 is `MixedMaterial::new(ir)`
+/// (Rust2/src/objects/material.rs:235-297), i.e. material triple (0, -1, exp).
+pub const RTW_FLAG_MIXED_MATERIAL: u32 = 32;
 #[repr(u32)] #[derive(Clone, Copy)]
 pub enum Sampler { Row = 0, Stratified = 1, Centres = 2, NoRand = 3 }      // viewport.rs:270-305, 430-516
 

@@ -54,6 +54,7 @@ enum {
                                     depth 0 and misses return the background, with Rust2's Material trait objects
                                     (Rust2/src/objects/material.rs): opacity > 0 -> MirrorGlass{ir}, metallicness == 1 ->
                                     Mirror (reflects the UN-normalised direction), else Lambertian (unit(n + rand));
+                                    with RTW_FLAG_MIXED_MATERIAL opacity < 0 -> MixedMaterial{exp = ir};
                                     ColorResult{emmited, multiplied} = {emitted, tex * col_mod}                             */
     RTW_INTEGRATOR_LIGHT_CAST = 5,   /* Rust2 `light_biased_ray_cast` (Rust2/src/viewport/ray_color.rs:55-108): ONE surface hit and a shadow ray
                                     towards every light of rtw_ctx_set_lights; RtwParams.depth is ignored; a miss returns the background */
@@ -215,6 +216,9 @@ typedef struct RtwParams {
                                         only (<= 2e-6 relative, far inside BASELINE.json's 1e-3).  The bank shrinks 4x (12.4 GB -> 3.1 GB at
                                         1920x1080x500).  The oracle implements the same association under the same flag. */
 #define RTW_SUM_CHUNK            4u
+#define RTW_FLAG_MIXED_MATERIAL 32u  /* Rust2's MixedMaterial (see "MixedMaterial" below): under RTW_INTEGRATOR_RUST2 / _LIGHT_CAST / _LIGHT_BIASED an
+                                        object with opacity < 0 is MixedMaterial::new(ir), a Phong lobe of exponent ir about the normal.  With any
+                                        other integrator: RTW_E_UNSUPPORTED.  Without the flag opacity < 0 selects what it always did. */
 
 typedef struct RtwStats {
     uint64_t camera_rays;    /* (pixel, sample) primary rays traced                   */
@@ -497,6 +501,36 @@ float rtw_material_pdf(const float mat3[3], const float p[3], const float n[3], 
  * colour e, hit at parameter t by the shadow ray of direction dir.  Returns 1 when the light was added, 0 when LIGHT_BIASED skipped it,
  * RTW_E_INVALID for another integrator or a NULL pointer. */
 int rtw_light_term(uint32_t integrator, float pdf, const float e[3], float t, const float dir[3], float biased_weight, float S[3], float *count);
+
+/* ---- MixedMaterial (Rust2/src/objects/material.rs:235-297, onb.rs:30-44) ----------------------------------------------------------
+ * With RTW_FLAG_MIXED_MATERIAL, under RTW_INTEGRATOR_RUST2, RTW_INTEGRATOR_LIGHT_CAST and RTW_INTEGRATOR_LIGHT_BIASED, a sphere, quad or instance
+ * member whose opacity < 0 is `MixedMaterial::new(exp)` with exp = ir (gen_exp = 1 / (exp + 1)); opacity > 0 stays MirrorGlass and opacity == 0
+ * keeps its meaning (Mirror or Lambertian by metallicness).  Without the flag nothing changes: opacity < 0 is Mirror or Lambertian.
+ *   on_hit: two draws from the pixel's stream, xi_phi then xi_cos;  phi = (xi_phi * 2) * PI, cos_theta = pow(1 - xi_cos, gen_exp),
+ *     sin_theta = sqrt(1 - cos_theta^2), local = (cos(phi) sin_theta, sin(phi) sin_theta, cos_theta);  the basis is ONB::new_from_w(h.n):
+ *     w = unit(n), a = (0,1,0) when |w.x| > 0.9 else (1,0,0), v = unit(w x a), u = unit(w x v);  direction = ((u x) + (v y)) + (w z).
+ *     The normal is the hit's as reported, NOT flipped for a back-face hit (the lobe then points into the surface), and the scattered ray is
+ *     built with Ray::new: its ray.time is 0, not the incoming ray's.
+ *   material_pdf: 0 when the ray does not start at the hit point (1e-7 per component);  cos = unit(rd) . unit(n), negated unless din . n < 0;
+ *     0 when cos < 0 (a NaN passes);  else pow(cos, exp) * (exp + 1) * (1 / 2 / PI).  No clamp at 1.
+ * pow, sin and cos are the library's own total f32 functions (csrc/rtw_mixed.h: the same bits on host and device, 1.05 / 1.44 / 1.43 ulp at
+ * most against f64 over the arguments a render can produce), where the reference calls the platform libm.
+ * A render with the flag returns RTW_E_INVALID when a MixedMaterial object's exp is negative or not finite, and RTW_E_UNSUPPORTED when the scene
+ * holds such an object together with triangles, texture noise or a constant-density instance.  MixedMaterial on triangles is not expressible.
+ * With the flag set and no object with opacity < 0 in the scene the render is exactly the render without the flag. */
+/* Host only (no context, no GPU): what a render of `scene` with `params` answers to the flag -- RTW_OK, RTW_E_UNSUPPORTED or RTW_E_INVALID as
+ * above; n_triangles / texture_noise: as if that many triangles / any texture noise were set on the context. */
+int rtw_mixed_validate(const RtwScene *scene, const RtwParams *params, uint32_t n_triangles, uint32_t texture_noise);
+/* Host only, for tests and tools: the pure pieces, the same definitions the kernels compile (csrc/rtw_mixed.h).
+ * rtw_mixed_dir: on_hit's direction for the two uniform draws.  rtw_mixed_pdf: material_pdf for the hit {p, n, incoming direction dir_in} and
+ * the ray {ray_o, ray_d}. */
+int rtw_mixed_dir(float exp, float xi_phi, float xi_cos, const float n[3], float out_dir[3]);
+int rtw_mixed_pdf(float exp, const float p[3], const float n[3], const float dir_in[3], const float ray_o[3], const float ray_d[3], float *out);
+/* The three elementary functions over arrays: out[i] = pow(x[i], y[i]) for x >= 0 (0, 1, inf, NaN included) and finite y >= 0 (libm's special
+ * cases: pow(x, 0) = 1 even for a NaN x, pow(0, y > 0) = 0; x < 0 gives NaN); sin / cos of phi in [0, 2 pi] (NaN for NaN). */
+int rtw_pow_plain(const float *x, const float *y, size_t n, float *out);
+int rtw_sin_plain(const float *phi, size_t n, float *out);
+int rtw_cos_plain(const float *phi, size_t n, float *out);
 
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 

@@ -44,6 +44,7 @@ SAMPLER_ROW, SAMPLER_STRATIFIED, SAMPLER_CENTRES, SAMPLER_NO_RAND = 0, 1, 2, 3
 ACCEL_BRUTE, ACCEL_BVH = 0, 1
 FLAG_RECURSIVE_ORDER, FLAG_CPP_DIELECTRIC, FLAG_GLOBAL_NODES, FLAG_CPP_DIFFUSE, FLAG_CHUNK_SUMS = 1, 2, 4, 8, 16
 FLAG_CPP = FLAG_CPP_DIELECTRIC | FLAG_CPP_DIFFUSE      # what Viewport::RenderGPU of the C++ tree asks for
+FLAG_MIXED_MATERIAL = 32   # Rust2's integrators: an object with opacity < 0 is MixedMaterial::new(ir) (see mixed())
 OPT_CHUNK_LEN, OPT_SAMPLE_BANK_GB, OPT_LDS_GEOM, OPT_BLOCKS_PER_CU, OPT_LIST_WALK_MAX, OPT_TILE_ORDER, OPT_GRAB_BLOCKS, OPT_SUB_QUEUES = 1, 2, 3, 4, 5, 6, 7, 8
 OPT_TAIL_UNITS = 9
 SCENE_C1, SCENE_C2, SCENE_C4, SCENE_C5, SCENE_METAL_TEST, SCENE_QUAD_TEST, SCENE_PRESENTATION, SCENE_FIRST_FRAME = 1, 2, 4, 5, 6, 7, 8, 9
@@ -244,6 +245,12 @@ def lib() -> C.CDLL:
     L.rtw_material_pdf.argtypes = [fp, fp, fp, fp, C.c_float, fp, fp, C.c_float]
     L.rtw_material_pdf.restype = C.c_float
     L.rtw_light_term.argtypes = [C.c_uint32, C.c_float, fp, C.c_float, fp, C.c_float, fp, fp]
+    L.rtw_mixed_validate.argtypes = [C.POINTER(RtwScene), C.POINTER(RtwParams), C.c_uint32, C.c_uint32]
+    L.rtw_mixed_dir.argtypes = [C.c_float, C.c_float, C.c_float, fp, fp]
+    L.rtw_mixed_pdf.argtypes = [C.c_float, fp, fp, fp, fp, fp, fp]
+    L.rtw_pow_plain.argtypes = [fp, fp, C.c_size_t, fp]
+    L.rtw_sin_plain.argtypes = [fp, C.c_size_t, fp]
+    L.rtw_cos_plain.argtypes = [fp, C.c_size_t, fp]
     _lib = L
     return L
 
@@ -402,6 +409,54 @@ def light_term(integrator: int, pdf, e, t, direction, weight, S, count):
     if rc < 0:
         _check(rc, "rtw_light_term")
     return bool(rc), np.array(list(s), np.float32), np.float32(c.value)
+
+
+def mixed(exp: float):
+    """The material triple of Rust2's MixedMaterial::new(exp) under FLAG_MIXED_MATERIAL: (metallicness, opacity, ir) = (0, -1, exp)."""
+    return (0.0, -1.0, float(exp))
+
+
+def mixed_validate(scene: "Scene", params: "RtwParams", n_triangles: int = 0, texture_noise: bool = False) -> int:
+    """rtw_mixed_validate: the status a render of `scene` with `params` answers to FLAG_MIXED_MATERIAL (host only)."""
+    return int(lib().rtw_mixed_validate(C.byref(scene.pod), C.byref(params), int(n_triangles), 1 if texture_noise else 0))
+
+
+def mixed_dir(exp, xi_phi, xi_cos, n) -> np.ndarray:
+    """rtw_mixed_dir: MixedMaterial::on_hit's direction about the normal n for the two uniform draws (phi's first)."""
+    out = (C.c_float * 3)()
+    _check(lib().rtw_mixed_dir(float(exp), float(xi_phi), float(xi_cos), _f3(n), out), "rtw_mixed_dir")
+    return np.array(list(out), np.float32)
+
+
+def mixed_pdf(exp, p, n, dir_in, ray_o, ray_d) -> np.float32:
+    """rtw_mixed_pdf: MixedMaterial::material_pdf(h, r) for the hit {p, n, incoming direction} and the ray {ray_o, ray_d}."""
+    out = C.c_float()
+    _check(lib().rtw_mixed_pdf(float(exp), _f3(p), _f3(n), _f3(dir_in), _f3(ray_o), _f3(ray_d), C.byref(out)), "rtw_mixed_pdf")
+    return np.float32(out.value)
+
+
+def _plain1(fn, what, *arrays):
+    arrs = np.broadcast_arrays(*[np.asarray(a, np.float32) for a in arrays])
+    arrs = [np.ascontiguousarray(a, np.float32) for a in arrs]
+    out = np.empty(arrs[0].shape, np.float32)
+    fp = C.POINTER(C.c_float)
+    _check(fn(*[a.ctypes.data_as(fp) for a in arrs], out.size, out.ctypes.data_as(fp)), what)
+    return out
+
+
+def pow_plain(x, y) -> np.ndarray:
+    """rtw_pow_plain over arrays (broadcast): the library's f32 pow for x >= 0, finite y >= 0."""
+    return _plain1(lib().rtw_pow_plain, "rtw_pow_plain", x, y)
+
+
+def sin_plain(phi) -> np.ndarray:
+    """rtw_sin_plain over an array: the library's f32 sin for phi in [0, 2 pi]."""
+    return _plain1(lib().rtw_sin_plain, "rtw_sin_plain", phi)
+
+
+def cos_plain(phi) -> np.ndarray:
+    """rtw_cos_plain over an array: the library's f32 cos for phi in [0, 2 pi]."""
+    return _plain1(lib().rtw_cos_plain, "rtw_cos_plain", phi)
 
 
 def _triangle_array(triangles):
@@ -746,6 +801,7 @@ class Viewport:
         self.shutter_speed, self.fps, self.frame = 0.0, 30.0, 0
         self.seed = 1
         self.mint, self.maxt = 0.001, 100000.0
+        self.flags = 0                       # RtwParams.flags of every render (FLAG_*), passed through unchanged
 
     @staticmethod
     def new(width, aspect_ratio, samples, depth, gamma, vfov=None, origin=None, direction=None, vup=None, msg=None, lens_radius=None):
@@ -765,7 +821,7 @@ class Viewport:
         p = RtwParams()
         p.width, p.height, p.samples, p.depth = self.width, self.height, self.samples, self.depth
         p.gamma, p.mint, p.maxt = self.gamma, self.mint, self.maxt
-        p.integrator, p.sampler, p.accel, p.flags, p.seed = integrator, sampler, accel, 0, self.seed
+        p.integrator, p.sampler, p.accel, p.flags, p.seed = integrator, sampler, accel, int(self.flags), self.seed
         p.row_block, p.part_index, p.part_count = 8, 0, 1
         return p
 

@@ -3,6 +3,7 @@
 #include "rtw_device.h"
 #include "rtw_tri.h"
 #include "rtw_light.h"
+#include "rtw_mixed.h"
 #include "rtw_host.h"
 
 #define RTW_QUEUE_BYTES 4096u   // the work queue's counters (KArgs.queue): up to 8 sub-queues ...

@@ -54,9 +54,13 @@ namespace rtw {
 // SPEC == 8 is SPEC == 0 plus Rust2's triangles (rtw_ctx_set_triangles): the closest-hit stage after the instances walks their list or tree;
 // only scenes with triangles select it.  SPEC == 9 is the generic build's driver (every sampler, RtwParams.flags) with Rust2's light-biased integrators
 // (rtw_light.h, rtw_ctx_set_lights) as its step: only RTW_INTEGRATOR_LIGHT_CAST / _LIGHT_BIASED select it, and it runs no other integrator.
+// SPEC == 10 is SPEC == 9 with Rust2's MixedMaterial (rtw_mixed.h) in the material step: an object with opacity < 0 scatters into a Phong lobe.
+// Only RTW_FLAG_MIXED_MATERIAL on a scene that holds such an object selects it; it also runs RTW_INTEGRATOR_RUST2, as LIGHT_BIASED with an
+// empty light list (that path is RUST2's bit for bit).
 constexpr bool gradient_spec(int spec) { return spec >= 1 && spec <= 3; }
-constexpr bool generic_spec(int spec) { return spec == 0 || spec == 7 || spec == 8 || spec == 9; }
-constexpr bool light_spec(int spec) { return spec == 9; }
+constexpr bool generic_spec(int spec) { return spec == 0 || spec == 7 || spec == 8 || spec == 9 || spec == 10; }
+constexpr bool light_spec(int spec) { return spec == 9 || spec == 10; }
+constexpr bool mixed_spec(int spec) { return spec == 10; }
 constexpr bool noise_spec(int spec) { return spec == 7; }
 constexpr bool tri_spec(int spec) { return spec == 8; }
 template <int SPEC> __device__ __forceinline__ uint32_t integ(const KArgs &A) {
@@ -455,14 +459,29 @@ __device__ __forceinline__ bool light_path_hit(const KArgs &A, Path &pt, int bes
 
 // At the surface hit: keep what material_pdf and the combination need, draw the scattered ray (light_biased_ray_color calls o.reflect(&h) first,
 // ray_color.rs:124; light_biased_ray_cast draws nothing), move the path's origin to the hit point.
+// MIXED (SPEC 10): every integrator but LIGHT_CAST walks on (RTW_INTEGRATOR_RUST2 is LIGHT_BIASED without lights), and a surface with
+// opacity < 0 is MixedMaterial::new(ir): two draws, phi then cos theta, and the lobe about the hit's normal as reported (rtw_mixed.h).
+template <bool MIXED>
+__device__ __forceinline__ bool light_walks_on(const KArgs &A) {
+    return MIXED ? A.integrator != RTW_INTEGRATOR_LIGHT_CAST : A.integrator == RTW_INTEGRATOR_LIGHT_BIASED;
+}
+template <bool MIXED>
 __device__ __forceinline__ void light_surface(const KArgs &A, Path &pt, v3 point, v3 normal, v3 cm, const MatP m, v3 emitted, LightPath &lp) {
-    const bool biased = A.integrator == RTW_INTEGRATOR_LIGHT_BIASED;
+    const bool biased = light_walks_on<MIXED>(A);
     lp.n = normal; lp.din = pt.d; lp.tm = pt.tm;
     lp.metallicness = m.metallicness; lp.opacity = m.opacity; lp.ir = m.ir;
     lp.cm = cm; lp.e = emitted;
     lp.S = mk(0, 0, 0); lp.count = biased ? 1.0f : 0.0f;
     v3 scat = mk(0, 0, 0);
-    if (biased) scat = on_hit_rust2(m, normal, pt.d, pt.rng, A.flags);
+    if (biased) {
+        if (MIXED && m.opacity < 0.0f) {
+            const float xi_phi = rng_f32(pt.rng), xi_cos = rng_f32(pt.rng);
+            const lv3 dir = mixed_dir(m.ir, xi_phi, xi_cos, tol(normal));
+            scat = mk(dir.x, dir.y, dir.z);
+        } else {
+            scat = on_hit_rust2(m, normal, pt.d, pt.rng, A.flags);
+        }
+    }
     lp.scat = scat;
     pt.o = point;
 }
@@ -478,7 +497,7 @@ __device__ __forceinline__ void light_ray(uint32_t i, Path &pt) {
 
 // The shadow query of light i is complete: (best, best_t) its sphere part.  Finishes Scene::collision_normal for it (GEOM) and, when the
 // closest object IS the light, adds the light's term.
-template <bool MOVING, bool GEOM>
+template <bool MOVING, bool GEOM, bool MIXED>
 __device__ __forceinline__ void light_result(const KArgs &A, uint32_t i, const Path &pt, int best, float best_t, LightPath &lp, uint32_t &n_sph, uint32_t &n_quad) {
     uint32_t code = best >= 0 ? (uint32_t)best : LIGHT_HIT_NONE;
     float t = best_t;
@@ -504,9 +523,11 @@ __device__ __forceinline__ void light_result(const KArgs &A, uint32_t i, const P
             rust2_sphere_color(A.sc, mat, unit((pt.o + pt.d * t) - c), cm_unused, e);
         }
     }
-    const float pdf = light_material_pdf(lp.metallicness, lp.opacity, lp.ir, tol(pt.o), tol(lp.n), tol(lp.din), lp.tm, tol(pt.o), tol(pt.d), pt.tm);
+    float pdf;
+    if (MIXED && lp.opacity < 0.0f) pdf = mixed_pdf(lp.ir, tol(pt.o), tol(lp.n), tol(lp.din), tol(pt.o), tol(pt.d));
+    else pdf = light_material_pdf(lp.metallicness, lp.opacity, lp.ir, tol(pt.o), tol(lp.n), tol(lp.din), lp.tm, tol(pt.o), tol(pt.d), pt.tm);
     lv3 S = tol(lp.S);
-    light_add(A.integrator == RTW_INTEGRATOR_LIGHT_BIASED, pdf, tol(e), t, tol(pt.d), A.lights.weight, S, lp.count);
+    light_add(light_walks_on<MIXED>(A), pdf, tol(e), t, tol(pt.d), A.lights.weight, S, lp.count);
     lp.S = mk(S.x, S.y, S.z);
 }
 
@@ -514,8 +535,9 @@ __device__ __forceinline__ void light_result(const KArgs &A, uint32_t i, const P
 //   LIGHT_BIASED  L += thr (.) ((S (.) m) / count + e),  thr = thr (.) (m / count), the scattered ray goes on (depth as RTW_INTEGRATOR_RUST2)
 //   LIGHT_CAST    L = (S (.) m) / count + e  (e alone when count == 0); the path ends
 // Returns true when the path is finished.
+template <bool MIXED>
 __device__ __forceinline__ bool light_finish(const KArgs &A, Path &pt, const LightPath &lp) {
-    if (A.integrator != RTW_INTEGRATOR_LIGHT_BIASED) {
+    if (!light_walks_on<MIXED>(A)) {
         v3 c = mk(0, 0, 0);
         if (lp.count != 0.0f) c = (lp.S * lp.cm) / lp.count;
         pt.L = c + lp.e;
@@ -524,13 +546,14 @@ __device__ __forceinline__ bool light_finish(const KArgs &A, Path &pt, const Lig
     pt.L = pt.L + pt.thr * ((lp.S * lp.cm) / lp.count + lp.e);
     pt.thr = pt.thr * (lp.cm / lp.count);
     pt.d = lp.scat; pt.tm = lp.tm;
+    if (MIXED && lp.opacity < 0.0f) pt.tm = 0.0f;             // MixedMaterial::on_hit builds its ray with Ray::new: time 0, not h.r.time
     pt.k++;
     if (pt.k >= A.depth) { pt.L = pt.L + ld3(A.bg) * pt.thr; return true; }
     return false;
 }
 
 // render_brute: the whole step for a lane whose path query returned (best, best_t) -- the shadow queries are list walks of their own.
-template <bool MOVING, bool GEOM>
+template <bool MOVING, bool GEOM, bool MIXED>
 __device__ __forceinline__ bool light_step_brute(const KArgs &A, Path &pt, int best, float best_t, uint32_t &n_seg, uint32_t &n_sph, uint32_t &n_quad) {
     v3 point, normal, cm, emitted; MatP m;
     if (!light_path_hit<MOVING, GEOM>(A, pt, best, best_t, point, normal, cm, m, emitted, n_sph, n_quad)) {
@@ -538,21 +561,21 @@ __device__ __forceinline__ bool light_step_brute(const KArgs &A, Path &pt, int b
         return true;
     }
     LightPath lp;
-    light_surface(A, pt, point, normal, cm, m, emitted, lp);
+    light_surface<MIXED>(A, pt, point, normal, cm, m, emitted, lp);
     const uint32_t n = A.lights.n;
     for (uint32_t i = 0; i < n; ++i) {
         light_ray(i, pt);
         int sb; float st;
         closest_brute<MOVING>(A.sc, pt.o, pt.d, pt.tm, A.mint, A.maxt, sb, st);
         n_seg++;
-        light_result<MOVING, GEOM>(A, i, pt, sb, st, lp, n_sph, n_quad);
+        light_result<MOVING, GEOM, MIXED>(A, i, pt, sb, st, lp, n_sph, n_quad);
     }
-    return light_finish(A, pt, lp);
+    return light_finish<MIXED>(A, pt, lp);
 }
 
 // render_bvh: one SHADE step of a lane whose query is complete.  `fl` carries LF_SHADOW (the query was a shadow query) and the pending
 // light (rtw_light.h); the caller starts the next query -- shadow or path -- from pt.o / pt.d / pt.tm like any other.
-template <bool MOVING, bool GEOM>
+template <bool MOVING, bool GEOM, bool MIXED>
 __device__ __forceinline__ bool light_step_bvh(const KArgs &A, Path &pt, LightPath &lp, uint32_t &fl, int best, float best_t, uint32_t &n_sph, uint32_t &n_quad) {
     const uint32_t n = A.lights.n;
     if (!(fl & LF_SHADOW)) {                               // path result
@@ -561,18 +584,18 @@ __device__ __forceinline__ bool light_step_bvh(const KArgs &A, Path &pt, LightPa
             pt.L = pt.L + ld3(A.bg) * pt.thr;
             return true;
         }
-        light_surface(A, pt, point, normal, cm, m, emitted, lp);
-        if (n == 0u) return light_finish(A, pt, lp);
+        light_surface<MIXED>(A, pt, point, normal, cm, m, emitted, lp);
+        if (n == 0u) return light_finish<MIXED>(A, pt, lp);
         fl |= LF_SHADOW;                                      // (light 0: the pending-light bits are clear)
         light_ray(0u, pt);
         return false;
     }
     uint32_t i = (fl & LF_LIGHT_MASK) >> LF_LIGHT_SHIFT;                           // shadow result: one compare, the pdf, a few dozen VALU
-    light_result<MOVING, GEOM>(A, i, pt, best, best_t, lp, n_sph, n_quad);
+    light_result<MOVING, GEOM, MIXED>(A, i, pt, best, best_t, lp, n_sph, n_quad);
     i++;
     if (i < n) { fl += 1u << LF_LIGHT_SHIFT; light_ray(i, pt); return false; }
     fl &= ~(LF_SHADOW | LF_LIGHT_MASK);
-    return light_finish(A, pt, lp);
+    return light_finish<MIXED>(A, pt, lp);
 }
 
 // A path ended: bank its radiance in the sample buffer (the resolve kernel adds the samples of a pixel
@@ -732,14 +755,14 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? RTW_GEOM_BRUTE_WAVES : 1) void re
         if (have) {
             bool finished;
             // (the light build: light_biased_ray_color returns the background at depth 0, light_biased_ray_cast ignores the depth)
-            if (light_spec(SPEC) ? (A.depth == 0 && A.integrator == RTW_INTEGRATOR_LIGHT_BIASED)
+            if (light_spec(SPEC) ? (A.depth == 0 && (mixed_spec(SPEC) ? A.integrator != RTW_INTEGRATOR_LIGHT_CAST : A.integrator == RTW_INTEGRATOR_LIGHT_BIASED))
                                  : (generic_spec(SPEC) && A.depth == 0 && A.integrator != RTW_INTEGRATOR_NORMAL)) {   // `if depth < 1 { return black }` (ray_color.rs:14-16)
                 pt.L = (light_spec(SPEC) || A.integrator == RTW_INTEGRATOR_RUST2) ? ld3(A.bg) : mk(0, 0, 0); finished = true;
             } else {
                 int best; float best_t;
                 closest_brute<MOVING>(A.sc, pt.o, pt.d, pt.tm, A.mint, A.maxt, best, best_t);
                 n_seg++;
-                if constexpr (light_spec(SPEC)) finished = light_step_brute<MOVING, GEOM>(A, pt, best, best_t, n_seg, n_isph, n_quad);
+                if constexpr (light_spec(SPEC)) finished = light_step_brute<MOVING, GEOM, mixed_spec(SPEC)>(A, pt, best, best_t, n_seg, n_isph, n_quad);
                 else finished = GEOM ? shade_geom<MOVING, SPEC>(A, pt, best, best_t, n_isph, n_quad) : shade<MOVING, SPEC>(A, pt, best, best_t);
             }
             if (finished) {
@@ -1277,7 +1300,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
                     fl &= ~F_INFLIGHT;
                     bool done;
                     // (the light build: a path result or a shadow result; the lane's next query, shadow or path, starts below like any other)
-                    if constexpr (light_spec(SPEC)) done = light_step_bvh<MOVING, GEOM>(A, pt, lp, fl, tr.best, tr.best_t, n_isph, n_quad);
+                    if constexpr (light_spec(SPEC)) done = light_step_bvh<MOVING, GEOM, mixed_spec(SPEC)>(A, pt, lp, fl, tr.best, tr.best_t, n_isph, n_quad);
                     else done = GEOM ? shade_geom<MOVING, SPEC>(A, pt, tr.best, tr.best_t, n_isph, n_quad) : shade<MOVING, SPEC>(A, pt, tr.best, tr.best_t, cn);
                     if (done) fl |= F_DONE;
                 }
@@ -1313,7 +1336,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
                     // c. next camera ray (a lane whose path continues keeps its scattered ray)
                     if (fl & F_NEWPATH) { fl &= ~F_NEWPATH; start_path<SPEC>(A, px, pt, cn); started = true; }
                     // d. start the next closest-hit query
-                    if (light_spec(SPEC) ? (A.depth == 0 && A.integrator == RTW_INTEGRATOR_LIGHT_BIASED)
+                    if (light_spec(SPEC) ? (A.depth == 0 && (mixed_spec(SPEC) ? A.integrator != RTW_INTEGRATOR_LIGHT_CAST : A.integrator == RTW_INTEGRATOR_LIGHT_BIASED))
                                          : (generic_spec(SPEC) && A.depth == 0 && A.integrator != RTW_INTEGRATOR_NORMAL)) {   // `if depth < 1 { return black }` (ray_color.rs:14-16)
                         pt.L = (light_spec(SPEC) || A.integrator == RTW_INTEGRATOR_RUST2) ? ld3(A.bg) : mk(0, 0, 0);
                         fl |= F_DONE;                                      // banked on the next SHADE trip
@@ -1482,6 +1505,10 @@ static kernel_fn pick_kernel_geom(bool moving, uint32_t accel, int nodes) {
 }
 static kernel_fn pick_kernel(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
     const int nodes = lds_nodes ? (a.lds_geom_off ? 2 : 1) : 0;
+    // RTW_FLAG_MIXED_MATERIAL on a scene with a MixedMaterial object (rtw_shim.hip clears the bit otherwise, and refuses the flag under any
+    // integrator but RUST2 / LIGHT_CAST / LIGHT_BIASED): the mixed build, for every sampler and flag
+    if (a.flags & RTW_FLAG_MIXED_MATERIAL)
+        return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<10>(moving, accel, nodes) : pick_kernel_spec<10>(moving, accel, nodes);
     // Rust2's light-biased integrators: the light build, for every sampler and flag (rtw_shim.hip refuses them with noise or triangles)
     if (a.integrator == RTW_INTEGRATOR_LIGHT_CAST || a.integrator == RTW_INTEGRATOR_LIGHT_BIASED)
         return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<9>(moving, accel, nodes) : pick_kernel_spec<9>(moving, accel, nodes);

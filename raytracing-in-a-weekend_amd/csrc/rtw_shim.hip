@@ -65,6 +65,9 @@ struct rtw_ctx {
     std::vector<RtwSphere> h_spheres;    // host copies of the top-level spheres and quads: a light's mid-point is formed from them
     std::vector<RtwQuad> h_quads;
     bool has_medium = false;             // an instance of the scene is a constant-density medium (the light integrators refuse it)
+    // MixedMaterial (RTW_FLAG_MIXED_MATERIAL): does the scene hold an object with opacity < 0, and is the exponent (ir) of every such object
+    // finite and >= 0?  Computed once by rtw_ctx_set_scene.
+    bool has_mixed = false, mixed_bad = false;
     // scratch
     uint32_t *d_queue = nullptr;
     unsigned long long *d_stats = nullptr;
@@ -264,6 +267,7 @@ static void free_scene(rtw_ctx *c) {
     free_tris(c);
     c->lights = DevLights{};
     c->h_spheres.clear(); c->h_quads.clear(); c->has_medium = false;
+    c->has_mixed = c->mixed_bad = false;
     c->n_textures = 0;
     c->tex_used.clear();
     c->has_scene = false;
@@ -291,6 +295,71 @@ void rtw_ctx_destroy(rtw_ctx *c) {
 int rtw_ctx_set_stream(rtw_ctx *c, void *hip_stream) {
     if (!c) return RTW_E_INVALID;
     c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    return RTW_OK;
+}
+
+// ---- MixedMaterial (rtw.h "MixedMaterial") ------------------------------------------------------------------------------------------
+// Which objects of a scene RTW_FLAG_MIXED_MATERIAL turns into MixedMaterial::new(ir) -- opacity < 0, wherever {metallicness, opacity, ir} is
+// carried -- and whether an exponent among them is outside pow_plain's domain (not finite, or negative).
+static void scene_mixed(const RtwScene *s, bool &has_mixed, bool &mixed_bad) {
+    has_mixed = mixed_bad = false;
+    auto see = [&](float opacity, float ir) {
+        if (!(opacity < 0.0f)) return;
+        has_mixed = true;
+        if (!(ir >= 0.0f && ir <= 3.402823466e38f)) mixed_bad = true;
+    };
+    for (uint32_t i = 0; i < s->n_spheres; i++) see(s->spheres[i].opacity, s->spheres[i].ir);
+    for (uint32_t i = 0; i < s->n_quads; i++) see(s->quads[i].opacity, s->quads[i].ir);
+    for (uint32_t i = 0; i < s->n_inst_spheres; i++) see(s->inst_spheres[i].opacity, s->inst_spheres[i].ir);
+    for (uint32_t i = 0; i < s->n_inst_quads; i++) see(s->inst_quads[i].opacity, s->inst_quads[i].ir);
+}
+// What a render answers to RTW_FLAG_MIXED_MATERIAL: shared by rtw_ctx_render and rtw_mixed_validate (host only).
+static int mixed_check(uint32_t flags, uint32_t integrator, bool has_mixed, bool mixed_bad, bool noise, bool tris, bool medium) {
+    if (!(flags & RTW_FLAG_MIXED_MATERIAL)) return RTW_OK;
+    if (integrator != RTW_INTEGRATOR_RUST2 && integrator != RTW_INTEGRATOR_LIGHT_CAST && integrator != RTW_INTEGRATOR_LIGHT_BIASED) return RTW_E_UNSUPPORTED;
+    if (!has_mixed) return RTW_OK;
+    if (mixed_bad) return RTW_E_INVALID;
+    if (noise || tris || medium) return RTW_E_UNSUPPORTED;
+    return RTW_OK;
+}
+
+int rtw_mixed_validate(const RtwScene *scene, const RtwParams *params, uint32_t n_triangles, uint32_t texture_noise) {
+    if (!scene || !params) return RTW_E_INVALID;
+    if ((scene->n_spheres && !scene->spheres) || (scene->n_quads && !scene->quads) || (scene->n_inst_spheres && !scene->inst_spheres) ||
+        (scene->n_inst_quads && !scene->inst_quads) || (scene->n_instances && !scene->instances)) return RTW_E_INVALID;
+    bool has_mixed, mixed_bad, medium = false;
+    scene_mixed(scene, has_mixed, mixed_bad);
+    for (uint32_t i = 0; i < scene->n_instances; i++) if (scene->instances[i].medium == RTW_MEDIUM_CONST_DENSITY) medium = true;
+    return mixed_check(params->flags, params->integrator, has_mixed, mixed_bad, texture_noise != 0u, n_triangles != 0u, medium);
+}
+
+int rtw_mixed_dir(float exp, float xi_phi, float xi_cos, const float n[3], float out_dir[3]) {
+    if (!n || !out_dir) return RTW_E_INVALID;
+    const lv3 d = mixed_dir(exp, xi_phi, xi_cos, lmk(n[0], n[1], n[2]));
+    out_dir[0] = d.x; out_dir[1] = d.y; out_dir[2] = d.z;
+    return RTW_OK;
+}
+
+int rtw_mixed_pdf(float exp, const float p[3], const float n[3], const float dir_in[3], const float ray_o[3], const float ray_d[3], float *out) {
+    if (!p || !n || !dir_in || !ray_o || !ray_d || !out) return RTW_E_INVALID;
+    *out = mixed_pdf(exp, lmk(p[0], p[1], p[2]), lmk(n[0], n[1], n[2]), lmk(dir_in[0], dir_in[1], dir_in[2]), lmk(ray_o[0], ray_o[1], ray_o[2]),
+                     lmk(ray_d[0], ray_d[1], ray_d[2]));
+    return RTW_OK;
+}
+
+int rtw_pow_plain(const float *x, const float *y, size_t n, float *out) {
+    if (n && (!x || !y || !out)) return RTW_E_INVALID;
+    for (size_t i = 0; i < n; i++) out[i] = pow_plain(x[i], y[i]);
+    return RTW_OK;
+}
+int rtw_sin_plain(const float *phi, size_t n, float *out) {
+    if (n && (!phi || !out)) return RTW_E_INVALID;
+    for (size_t i = 0; i < n; i++) out[i] = sin_plain(phi[i]);
+    return RTW_OK;
+}
+int rtw_cos_plain(const float *phi, size_t n, float *out) {
+    if (n && (!phi || !out)) return RTW_E_INVALID;
+    for (size_t i = 0; i < n; i++) out[i] = cos_plain(phi[i]);
     return RTW_OK;
 }
 
@@ -431,6 +500,7 @@ int rtw_ctx_set_scene(rtw_ctx *c, const RtwScene *s, float t_begin, float t_end)
     c->h_spheres.assign(s->spheres, s->spheres + s->n_spheres);
     c->h_quads.assign(s->quads, s->quads + s->n_quads);
     for (uint32_t i = 0; i < s->n_instances; i++) if (s->instances[i].medium == RTW_MEDIUM_CONST_DENSITY) c->has_medium = true;
+    scene_mixed(s, c->has_mixed, c->mixed_bad);
     c->has_scene = true;
     return RTW_OK;
 }
@@ -711,6 +781,9 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     const bool light_integrator = p->integrator == RTW_INTEGRATOR_LIGHT_CAST || p->integrator == RTW_INTEGRATOR_LIGHT_BIASED;
     // Rust2's light-biased integrators: no noise (Rust2's textures have none), no triangle lights or occluders yet, no media (Rust2 has none)
     if (light_integrator && (c->noise_active || c->tris.n || c->has_medium)) return RTW_E_UNSUPPORTED;
+    // RTW_FLAG_MIXED_MATERIAL: Rust2's integrators only; a scene with a MixedMaterial object runs the mixed build, which is the light build's driver
+    if (const int mrc = mixed_check(p->flags, p->integrator, c->has_mixed, c->mixed_bad, c->noise_active, c->tris.n != 0u, c->has_medium)) return mrc;
+    const bool mixed_active = (p->flags & RTW_FLAG_MIXED_MATERIAL) && c->has_mixed;
     if (!c->pend.marked) c->pend.t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(c->device));
 
@@ -744,7 +817,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
             const float ta = cam->time0, tb = cam->time0 + cam->shutter;
             if (!(std::fmin(ta, tb) >= c->t_begin && std::fmax(ta, tb) <= c->t_end)) accel = RTW_ACCEL_BRUTE;
             if (ta != ta || tb != tb) accel = RTW_ACCEL_BRUTE;         // (fmin / fmax drop a NaN: a NaN shutter makes every moving centre NaN, which only the list walk answers like the reference)
-            if (light_integrator && !(c->t_begin <= 0.0f && c->t_end >= 0.0f)) accel = RTW_ACCEL_BRUTE;   // the shadow rays run at ray.time 0
+            if ((light_integrator || mixed_active) && !(c->t_begin <= 0.0f && c->t_end >= 0.0f)) accel = RTW_ACCEL_BRUTE;   // the shadow rays run at ray.time 0, and so do the rays a MixedMaterial scatters
         }
         if (!c->bvh_ok) accel = RTW_ACCEL_BRUTE;
         // a handful of spheres: the list walk IS the fastest closest-hit (the traversal scheduler only costs)
@@ -756,6 +829,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     a.cam = *cam; a.sc = c->sc; a.bvh = c->bvh; a.geom = c->geom;
     if (p->flags & RTW_FLAG_GLOBAL_NODES) a.bvh.nodes16 = nullptr;
     a.flags = p->flags;
+    if (!mixed_active) a.flags &= ~RTW_FLAG_MIXED_MATERIAL;       // (the bit selects the mixed build: pick_kernel; without a MixedMaterial object every build is as it was)
     a.width = p->width; a.height = p->height;
     const uint32_t n_rows = rtw_part_rows(p->height, p->row_block, p->part_index, p->part_count);
     a.row_block = p->row_block ? p->row_block : 1; a.part_index = p->part_index; a.part_count = p->part_count;
