@@ -242,9 +242,9 @@ def camera_ray(cam, i, j):
 
 
 class Rng:
-    def __init__(self, seed, pixel):
+    def __init__(self, seed, pixel, sample=0):
         self.state = (C.c_uint32 * 2)()
-        O.lib().rtw_oracle_rng_seed(seed, pixel, 0, self.state)
+        O.lib().rtw_oracle_rng_seed(seed, pixel, sample, self.state)
 
     def next(self):
         return F(O.lib().rtw_oracle_rng_next(self.state))
@@ -384,35 +384,91 @@ def trace(ls, o, d, params, pixel, check=True, time=0.0, rng=None):
     return {"ftb": L, "rec": c, "queries": queries, "hits": hits, "bound": bound, "blocked": blocked}
 
 
+SUM_CHUNK = 4            # RTW_SUM_CHUNK (rtw.h)
+SAMPLERS = (R.SAMPLER_NO_RAND, R.SAMPLER_ROW, R.SAMPLER_STRATIFIED, R.SAMPLER_CENTRES)
+
+
+def sampler_count(sampler, samples):
+    """(rays per pixel, s_root) of a sampler (oracle/rtw_oracle.c sampler_count): STRATIFIED rounds sqrt(samples) up, CENTRES down."""
+    if sampler == R.SAMPLER_STRATIFIED:
+        root = int(np.ceil(np.sqrt(F(samples))))
+        return root * root, root
+    if sampler == R.SAMPLER_CENTRES:
+        root = int(np.floor(np.sqrt(F(samples))))
+        return root * root, root
+    return (1 if sampler == R.SAMPLER_NO_RAND else samples), 0
+
+
+def pixel_samples(cam, params, i, j):
+    """The camera rays of pixel (i, j), in sample order, as oracle/rtw_oracle.c render_pixel draws them: (origin, direction, ray.time, the
+    sample's stream (seed, pixel, s) after the camera draws -- None under RTW_SAMPLER_NO_RAND, whose path starts on the fresh stream).  Every
+    sampler but NO_RAND draws a lens-disk point first (random_in_unit_disk: (2 xi - 1, 2 xi - 1), accept len2 <= 1); lens_radius must be 0, so
+    the point moves nothing.  ROW (render_row, viewport.rs:286-297): two pixel offsets and the ray's time; STRATIFIED (viewport.rs:452-470):
+    cell x = s / root, y = s % root, an offset in each, time 0; CENTRES (Rust2 viewport.rs:92-104): the cell centres over Rust2's camera
+    (pixel00 = left_top, delta_u / delta_v the FULL viewport, divided by width / height at use), time 0."""
+    if params.sampler == R.SAMPLER_NO_RAND:
+        o, d = camera_ray(cam, i, j)
+        yield o, d, 0.0, None
+        return
+    assert cam.lens_radius == 0.0
+    n, root = sampler_count(params.sampler, params.samples)
+    pixel = j * params.width + i
+    o, p00, du, dv = v(list(cam.origin)), v(list(cam.pixel00)), v(list(cam.delta_u)), v(list(cam.delta_v))
+    for s in range(n):
+        rng = Rng(params.seed, pixel, s)
+        while True:
+            x, y = F(F(rng.next() * F(2.0)) - F(1.0)), F(F(rng.next() * F(2.0)) - F(1.0))
+            if F(F(x * x) + F(y * y)) <= F(1.0):
+                break
+        tm = F(0.0)
+        if params.sampler == R.SAMPLER_ROW:
+            jx, jy = F(F(i) + rng.next()), F(F(j) + rng.next())
+            tm = F(F(cam.time0) + F(F(cam.shutter) * rng.next()))
+        elif params.sampler == R.SAMPLER_STRATIFIED:
+            jx = F(F(i) + F(F(F(s // root) + rng.next()) / F(root)))
+            jy = F(F(j) + F(F(F(s % root) + rng.next()) / F(root)))
+        else:
+            jx = F(F(F(i) + F(F(F(s // root) + F(0.5)) / F(root))) / F(params.width))
+            jy = F(F(F(j) + F(F(F(s % root) + F(0.5)) / F(root))) / F(params.height))
+        d = ((p00 + (du * jx).astype(F)).astype(F) + (dv * jy).astype(F)).astype(F)
+        yield o.copy(), d, tm, rng
+
+
+def resolve(params, cols):
+    """The driver's pixel: the samples added from +0 left to right and divided by their number (viewport.rs:299-301) -- or, with
+    RTW_FLAG_CHUNK_SUMS, the samples of each chunk of RTW_SUM_CHUNK added left to right into a partial sum (starting from the chunk's first
+    sample, not from 0) and the partial sums added from +0 in chunk order (rtw.h)."""
+    acc = np.zeros(3, F)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if params.flags & R.FLAG_CHUNK_SUMS:
+            for k in range(0, len(cols), SUM_CHUNK):
+                part = np.asarray(cols[k], F).copy()
+                for c in cols[k + 1:k + SUM_CHUNK]:
+                    part = (part + c).astype(F)
+                acc = (acc + part).astype(F)
+        else:
+            for c in cols:
+                acc = (acc + c).astype(F)
+        return (acc / F(len(cols))).astype(F)
+
+
 def render(ls, cam, params, check=False):
-    """The restatement's frame, one sample per pixel, gamma 1, under RTW_SAMPLER_NO_RAND or RTW_SAMPLER_ROW (render_row, viewport.rs:286-297:
-    a lens-disk point, two pixel offsets and the ray's time drawn from the pixel's stream before the path; lens_radius must be 0):
-    ([h][w][3] f32, segments = path queries + n_lights * path hits, shadow queries blocked by another object per light)."""
-    assert params.sampler in (R.SAMPLER_NO_RAND, R.SAMPLER_ROW) and params.gamma == 1.0 and params.samples == 1
+    """The restatement's frame at gamma 1 under any sampler (pixel_samples: the oracle's camera draws, stream (seed, pixel, s) per sample;
+    resolve: the driver's sum): ([h][w][3] f32, segments = path queries + n_lights * path hits, shadow queries blocked by another object per
+    light).  check (RTW_SAMPLER_NO_RAND only): the hop-by-hop check of trace."""
+    assert params.sampler in SAMPLERS and params.gamma == 1.0
     img = np.empty((params.height, params.width, 3), F)
     seg, blocked = 0, np.zeros(len(ls.lights), np.int64)
     for j in range(params.height):
         for i in range(params.width):
             pixel = j * params.width + i
-            if params.sampler == R.SAMPLER_NO_RAND:
-                o, d = camera_ray(cam, i, j)
-                r = trace(ls, o, d, params, pixel, check=check)
-            else:
-                assert cam.lens_radius == 0.0
-                rng = Rng(params.seed, pixel)
-                while True:                                                   # random_in_unit_disk: (2 xi - 1, 2 xi - 1), accept len2 <= 1
-                    x, y = F(F(rng.next() * F(2.0)) - F(1.0)), F(F(rng.next() * F(2.0)) - F(1.0))
-                    if F(F(x * x) + F(y * y)) <= F(1.0):
-                        break
-                jx, jy = F(F(i) + rng.next()), F(F(j) + rng.next())
-                tm = F(F(cam.time0) + F(F(cam.shutter) * rng.next()))
-                o, p00, du, dv = v(list(cam.origin)), v(list(cam.pixel00)), v(list(cam.delta_u)), v(list(cam.delta_v))
-                d = ((p00 + (du * jx).astype(F)).astype(F) + (dv * jy).astype(F)).astype(F)
-                r = trace(ls, o, d, params, pixel, check=False, time=tm, rng=rng)
-            # the driver: sum of one sample starting at +0, divided by 1
-            img[j, i] = ((np.zeros(3, F) + r["ftb"]).astype(F) / F(1.0)).astype(F)
-            seg += r["queries"] + len(ls.lights) * r["hits"]
-            blocked += np.asarray(r["blocked"], np.int64)
+            cols = []
+            for o, d, tm, rng in pixel_samples(cam, params, i, j):
+                r = trace(ls, o, d, params, pixel, check=check and rng is None, time=tm, rng=rng)
+                cols.append(r["ftb"])
+                seg += r["queries"] + len(ls.lights) * r["hits"]
+                blocked += np.asarray(r["blocked"], np.int64)
+            img[j, i] = resolve(params, cols)
     return img, seg, blocked
 
 

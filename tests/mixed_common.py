@@ -254,7 +254,9 @@ def oracle_params(params, **kw):
 def trace(ms, o, d, params, pixel, check=True, time=0.0, rng=None):
     """lights_common.trace with the mixed branch and RTW_INTEGRATOR_RUST2 (LIGHT_BIASED's path without lights).  Returns {"ftb", "rec",
     "queries", "hits", "shadow" (shadow queries), "bound", "mixed_hits", "times" (ray.time of every path query)}.  check: hop by hop against
-    the oracle's full RUST2 trace for as long as the path has met no mixed surface (`rng` None only)."""
+    the oracle's full RUST2 trace for as long as the path has met no mixed surface (`rng` None only).  Also "inst_hits" (path hits on an
+    instance), "shadow_inst" (shadow queries whose closest hit is an instance), "reached" / "blocked" (per light: shadow queries whose closest
+    hit is the light's own object / another object)."""
     assert rng is None or not check
     mixed_on = bool(params.flags & R.FLAG_MIXED_MATERIAL)
     time = float(F(time))
@@ -267,6 +269,8 @@ def trace(ms, o, d, params, pixel, check=True, time=0.0, rng=None):
         full, _ = O.trace_ray(o, d, time, ms.scene, oracle_params(params), pixel, 0, cap=max(4, depth + 2))
     rng = LC.Rng(params.seed, pixel) if rng is None else rng
     levels, queries, hits, shadow, mixed_hits, times = [], 0, 0, 0, 0, []
+    n_top = len(ms.spheres) + len(ms.quads)                  # object codes from here on are instances
+    inst_hits, shadow_inst, reached, blocked = 0, 0, [0] * len(ms.lights), [0] * len(ms.lights)
     end_bg = True
     o, d = v(o), v(d)
     for k in range(depth):
@@ -284,6 +288,7 @@ def trace(ms, o, d, params, pixel, check=True, time=0.0, rng=None):
             break
         hits += 1
         obj, t, p, n = h
+        inst_hits += int(obj >= n_top)
         mat = ms.mat(obj)
         if not mixed_on and is_mixed(mat):
             mat = (mat[0], 0.0, mat[2])                      # without the flag opacity < 0 is Mirror / Lambertian by metallicness
@@ -298,8 +303,11 @@ def trace(ms, o, d, params, pixel, check=True, time=0.0, rng=None):
                 rd = (to / np.sqrt(dot(to, to))).astype(F)
             sh = LC.closest(ms, p, rd, p1, pixel)
             shadow += 1
+            shadow_inst += int(sh is not None and sh[0] >= n_top)
             if sh is None or sh[0] != ms.light_obj[li]:
+                blocked[li] += int(sh is not None)
                 continue
+            reached[li] += 1
             _, el = ms.color(sh[0], sh[3])
             pdf = material_pdf(mat, p, n, d, time, p, rd, 0.0)
             s, dc = LC.light_term(not cast, pdf, el, sh[1], rd, ms.weight)
@@ -318,7 +326,8 @@ def trace(ms, o, d, params, pixel, check=True, time=0.0, rng=None):
         assert len(full) == queries, (len(full), queries)
     bg = ms.background
     n_l = len(lights)
-    out = {"queries": queries, "hits": hits, "shadow": shadow, "mixed_hits": mixed_hits, "times": times, "bound": 0.0}
+    out = {"queries": queries, "hits": hits, "shadow": shadow, "mixed_hits": mixed_hits, "times": times, "bound": 0.0,
+           "inst_hits": inst_hits, "shadow_inst": shadow_inst, "reached": reached, "blocked": blocked}
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         if cast:
             if not levels:
@@ -353,38 +362,35 @@ def trace(ms, o, d, params, pixel, check=True, time=0.0, rng=None):
 
 
 def render(ms, cam, params, check=False):
-    """The restatement's frame (one sample per pixel, gamma 1, RTW_SAMPLER_NO_RAND or RTW_SAMPLER_ROW as lights_common.render):
-    ([h][w][3] f32, segments = path + shadow queries, {"mixed_hits", "nonzero_time_queries", "max_rel" (front to back against the
-    recursion, relative to its bound)})."""
-    assert params.sampler in (R.SAMPLER_NO_RAND, R.SAMPLER_ROW) and params.gamma == 1.0 and params.samples == 1
+    """The restatement's frame (gamma 1, any sampler: lights_common.pixel_samples and lights_common.resolve, as lights_common.render):
+    ([h][w][3] f32, segments = path + shadow queries, {"mixed_hits", "nonzero_time_queries", "time_reset", "max_rel" (front to back against
+    the recursion, relative to its bound), "path_queries", "path_hits", "inst_hits", "shadow_inst", "reached" / "blocked" per light})."""
+    assert params.sampler in LC.SAMPLERS and params.gamma == 1.0
     img = np.empty((params.height, params.width, 3), F)
-    seg, info = 0, {"mixed_hits": 0, "nonzero_time_queries": 0, "time_reset": 0, "max_rel": 0.0}
+    n_l = len(ms.lights)
+    seg, info = 0, {"mixed_hits": 0, "nonzero_time_queries": 0, "time_reset": 0, "max_rel": 0.0, "path_queries": 0, "path_hits": 0,
+                    "inst_hits": 0, "shadow_inst": 0, "reached": np.zeros(n_l, np.int64), "blocked": np.zeros(n_l, np.int64)}
     for j in range(params.height):
         for i in range(params.width):
             pixel = j * params.width + i
-            if params.sampler == R.SAMPLER_NO_RAND:
-                o, d = LC.camera_ray(cam, i, j)
-                r = trace(ms, o, d, params, pixel, check=check)
-            else:
-                assert cam.lens_radius == 0.0
-                rng = LC.Rng(params.seed, pixel)
-                while True:
-                    x, y = F(F(rng.next() * F(2.0)) - F(1.0)), F(F(rng.next() * F(2.0)) - F(1.0))
-                    if F(F(x * x) + F(y * y)) <= F(1.0):
-                        break
-                jx, jy = F(F(i) + rng.next()), F(F(j) + rng.next())
-                tm = F(F(cam.time0) + F(F(cam.shutter) * rng.next()))
-                o, p00, du, dv = v(list(cam.origin)), v(list(cam.pixel00)), v(list(cam.delta_u)), v(list(cam.delta_v))
-                d = ((p00 + (du * jx).astype(F)).astype(F) + (dv * jy).astype(F)).astype(F)
-                r = trace(ms, o, d, params, pixel, check=False, time=tm, rng=rng)
-            img[j, i] = ((np.zeros(3, F) + r["ftb"]).astype(F) / F(1.0)).astype(F)
-            seg += r["queries"] + r["shadow"]
-            info["mixed_hits"] += r["mixed_hits"]
-            info["nonzero_time_queries"] += sum(1 for t in r["times"] if t != 0.0)
-            info["time_reset"] += int(r["times"][0] != 0.0 and any(t == 0.0 for t in r["times"][1:]))
-            with np.errstate(divide="ignore", invalid="ignore"):
-                ok = np.isfinite(r["rec"]) & (r["rec"] != 0) & np.isfinite(r["ftb"])
-                if r["bound"] > 0 and ok.any():
-                    rel = np.abs(r["ftb"][ok].astype(np.float64) - r["rec"][ok]) / np.abs(r["rec"][ok].astype(np.float64))
-                    info["max_rel"] = max(info["max_rel"], float(rel.max() / r["bound"]))
+            cols = []
+            for o, d, tm, rng in LC.pixel_samples(cam, params, i, j):
+                r = trace(ms, o, d, params, pixel, check=check and rng is None, time=tm, rng=rng)
+                cols.append(r["ftb"])
+                seg += r["queries"] + r["shadow"]
+                info["mixed_hits"] += r["mixed_hits"]
+                info["nonzero_time_queries"] += sum(1 for t in r["times"] if t != 0.0)
+                info["time_reset"] += int(bool(r["times"]) and r["times"][0] != 0.0 and any(t == 0.0 for t in r["times"][1:]))
+                info["path_queries"] += r["queries"]
+                info["path_hits"] += r["hits"]
+                info["inst_hits"] += r["inst_hits"]
+                info["shadow_inst"] += r["shadow_inst"]
+                info["reached"] += np.asarray(r["reached"], np.int64)
+                info["blocked"] += np.asarray(r["blocked"], np.int64)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    ok = np.isfinite(r["rec"]) & (r["rec"] != 0) & np.isfinite(r["ftb"])
+                    if r["bound"] > 0 and ok.any():
+                        rel = np.abs(r["ftb"][ok].astype(np.float64) - r["rec"][ok]) / np.abs(r["rec"][ok].astype(np.float64))
+                        info["max_rel"] = max(info["max_rel"], float(rel.max() / r["bound"]))
+            img[j, i] = LC.resolve(params, cols)
     return img, seg, info
