@@ -117,6 +117,12 @@ extern "C" {
                          t_out: *mut f32, idx_out: *mut i32) -> i32;
     fn rtw_ctx_triangle_hits(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, mint: f32, maxt: f32, accel: u32,
                              t_out: *mut f32, idx_out: *mut i32, stats: *mut RtwStats) -> i32;
+    fn rtw_camera2_new(aspect: f32, origin: *const f32, vup: *const f32, dir: *const f32, vfov: f32, lens_radius: f32, cam: *mut RtwCamera) -> i32;
+    fn rtw_depth_rays(cam: *const RtwCamera, width: u32, height: u32, rays_out: *mut f32) -> i32;
+    fn rtw_ctx_scene_hits(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, time: f32, mint: f32, maxt: f32, accel: u32,
+                          t_out: *mut f32, idx_out: *mut i32, normal_out: *mut f32, stats: *mut RtwStats) -> i32;
+    fn rtw_ctx_depth_map(ctx: *mut RtwCtx, cam: *const RtwCamera, width: u32, height: u32, time: f32, mint: f32, maxt: f32, accel: u32,
+                         depth_out: *mut f32, idx_out: *mut i32, normal_out: *mut f32, stats: *mut RtwStats) -> i32;
     fn rtw_mgpu_render(m: *mut RtwMgpu, cam: *const RtwCamera, p: *const RtwParams, out_rgb: *mut c_void,
                        per_device: *mut RtwStats, total: *mut RtwStats) -> i32;
 }
@@ -185,6 +191,23 @@ impl Renderer {
         check(unsafe { rtw_ctx_triangle_hits(self.ctx, rays.as_ptr() as *const f32, rays.len() as u32, mint, maxt, accel,
                                              t.as_mut_ptr(), i.as_mut_ptr(), std::ptr::null_mut()) })?;
         Ok((t, i))
+    }
+    /// The closest hit of each ray ([origin, direction], the direction not normalised) against the whole scene -- spheres, quads,
+    /// instances, triangles; constant-density instances are skipped --: (t or +inf, top-level index or -1, outward normal or 0) per ray.
+    pub fn scene_hits(&mut self, rays: &[[f32; 6]], time: f32, mint: f32, maxt: f32, accel: u32)
+                      -> Result<(Vec<f32>, Vec<i32>, Vec<[f32; 3]>), RtwError> {
+        let (mut t, mut i, mut n) = (vec![0f32; rays.len()], vec![0i32; rays.len()], vec![[0f32; 3]; rays.len()]);
+        check(unsafe { rtw_ctx_scene_hits(self.ctx, rays.as_ptr() as *const f32, rays.len() as u32, time, mint, maxt, accel,
+                                          t.as_mut_ptr(), i.as_mut_ptr(), n.as_mut_ptr() as *mut f32, std::ptr::null_mut()) })?;
+        Ok((t, i, n))
+    }
+    /// Rust2's `Viewport::depth_map` in one launch, for a camera of `rtw_camera2_new`: row-major [height][width] hit.t, maxt * 1.6 on a
+    /// miss (row j is row j of the image: the reference's leading empty row is not reproduced).
+    pub fn depth_map(&mut self, cam: &RtwCamera, width: u32, height: u32, time: f32, mint: f32, maxt: f32, accel: u32) -> Result<Vec<f32>, RtwError> {
+        let mut d = vec![0f32; width as usize * height as usize];
+        check(unsafe { rtw_ctx_depth_map(self.ctx, cam, width, height, time, mint, maxt, accel, d.as_mut_ptr(), std::ptr::null_mut(),
+                                         std::ptr::null_mut(), std::ptr::null_mut()) })?;
+        Ok(d)
     }
     /// PerlinNoise::noise (turb_depth 0) / turb(p, turb_depth) at `points` on this context's GPU.
     pub fn perlin_eval(&mut self, t: &RtwPerlin, points: &[[f32; 3]], turb_depth: u32) -> Result<Vec<f32>, RtwError> {
@@ -312,6 +335,20 @@ pub fn triangle_hits(tris: &[RtwTriangle], rays: &[[f32; 6]], mint: f32, maxt: f
     check(unsafe { rtw_triangle_hits(tris.as_ptr(), tris.len() as u32, rays.as_ptr() as *const f32, rays.len() as u32, mint, maxt,
                                      t.as_mut_ptr(), i.as_mut_ptr()) })?;
     Ok((t, i))
+}
+
+/// Rust2's `Camera::new(aspect, origin, vup, dir, vfov, lens_radius)` (Rust2/src/viewport/camera.rs:19-53).
+pub fn camera2_new(aspect: f32, origin: [f32; 3], vup: [f32; 3], dir: [f32; 3], vfov: f32, lens_radius: f32) -> Result<RtwCamera, RtwError> {
+    let mut cam = RtwCamera::default();
+    check(unsafe { rtw_camera2_new(aspect, origin.as_ptr(), vup.as_ptr(), dir.as_ptr(), vfov, lens_radius, &mut cam) })?;
+    Ok(cam)
+}
+
+/// The rays of Rust2's `Viewport::depth_map` for a camera of `rtw_camera2_new` (host only): [origin, unit direction] per pixel, row-major.
+pub fn depth_rays(cam: &RtwCamera, width: u32, height: u32) -> Result<Vec<[f32; 6]>, RtwError> {
+    let mut r = vec![[0f32; 6]; width as usize * height as usize];
+    check(unsafe { rtw_depth_rays(cam, width, height, r.as_mut_ptr() as *mut f32) })?;
+    Ok(r)
 }
 
 pub fn bilateral_filter_gpu(rgb: &[u8], w: u32, h: u32, proximity: Proximity) -> Result<Vec<u8>, RtwError> {

@@ -454,6 +454,39 @@ int rtw_triangle_hits(const RtwTriangle *tris, uint32_t n, const float *rays, ui
 int rtw_ctx_triangle_hits(rtw_ctx *ctx, const float *rays, uint32_t n_rays, float mint, float maxt, uint32_t accel,
                           float *t_out, int32_t *idx_out, RtwStats *stats);
 
+/* ---- scene ray queries and Rust2's depth_map (Rust2/src/viewport.rs:62-85) -------------------------------------------------------
+ * One closest-hit query per ray against the WHOLE scene of a context -- the spheres, quads and instances of rtw_ctx_set_scene and the
+ * triangles of rtw_ctx_set_triangles -- with no path around it: t, the top-level object and the normal of the first surface, for depth,
+ * object-id and normal buffers (a guide for the bilateral filter, picking, debugging a scene).
+ * The top-level object index counts spheres first, then quads, then instances, then triangles: a triangle k is reported as
+ * n_spheres + n_quads + n_instances + k.  The tie rule is Scene::collision_normal's, the render's: within a group the first of equal t in
+ * list order wins, a later group replaces an earlier one only when strictly closer.  RTW_ACCEL_BVH (the sphere tree and the triangle
+ * tree, under the conditions a render puts on them, RTW_OPT_LIST_WALK_MAX included) returns the same t, index and normal as
+ * RTW_ACCEL_BRUTE bit for bit, ties included.  The direction is used as given, NOT normalised: t is in units of |d|.  `time` is the
+ * ray.time: a moving sphere is at centre + velocity * time.  The normal is the outward geometric normal of the render's hit record (sphere:
+ * unit(point - centre); quad and triangle: the stored normal, never flipped; instance member: the member's, rotated into the world).
+ * CONSTANT-DENSITY INSTANCES ARE SKIPPED: their hit is a random scattering distance and a query has no sample stream, so the answer is
+ * the first SOLID surface; such an instance keeps its index slot (the other indices do not shift) and is never reported.
+ * No host implementation (the library has no CPU path for sphere, quad or instance hits) and no rtw_mgpu_* form. */
+/* Host only, pure: the rays of Viewport::depth_map for Rust2's camera (rtw_camera2_new: pixel00 = left_top, delta_u / delta_v = the
+ * full-viewport delta_x / delta_y).  Pixel (i, j), row-major at rays_out[(j * width + i) * 6]: origin = cam.origin, direction =
+ * unit(left_top + delta_x * (i as f32 / width as f32) + delta_y * (j as f32 / height as f32)) in f32 without FMA (viewport.rs:77-80, :63).
+ * RTW_E_INVALID for a NULL pointer or a zero size. */
+int rtw_depth_rays(const RtwCamera *cam, uint32_t width, uint32_t height, float *rays_out /* [height*width][6] */);
+/* The closest hit of each of n_rays rays ([n][6] = origin, direction) within [mint, maxt]: t_out[i] = its t, idx_out[i] = its top-level
+ * index; a miss writes +inf and -1.  normal_out ([n][3], may be NULL): the normal, 0 0 0 on a miss.  stats (may be NULL): segments
+ * (= n_rays), sphere_tests, node_tests, quad_tests, kernel_ms.  rays, t_out, idx_out and normal_out may each be host memory or device
+ * memory of ctx's GPU, as rtw_ctx_render's out_rgb (host memory is staged).  Blocking.  RTW_E_INVALID for a NULL ctx / rays / t_out /
+ * idx_out, n_rays == 0 or an unknown accel; RTW_E_NO_SCENE before rtw_ctx_set_scene. */
+int rtw_ctx_scene_hits(rtw_ctx *ctx, const float *rays, uint32_t n_rays, float time, float mint, float maxt, uint32_t accel,
+                       float *t_out, int32_t *idx_out, float *normal_out, RtwStats *stats);
+/* Viewport::depth_map in one launch: the kernel builds the ray of every pixel itself, by the rule of rtw_depth_rays, and writes
+ * depth_out[j][i] = hit.t, or maxt * 1.6f on a miss (viewport.rs:68).  Row j of the output is row j of the image (the reference's
+ * leading empty row, an artefact of `vec![vec![]]`, is not reproduced).  idx_out ([height][width], -1 on a miss) and normal_out
+ * ([height][width][3]) may be NULL; memory kinds, stats and statuses as rtw_ctx_scene_hits (width * height must fit 32 bits). */
+int rtw_ctx_depth_map(rtw_ctx *ctx, const RtwCamera *cam, uint32_t width, uint32_t height, float time, float mint, float maxt,
+                      uint32_t accel, float *depth_out, int32_t *idx_out, float *normal_out, RtwStats *stats);
+
 /* ---- light-biased integrators (Rust2/src/viewport/ray_color.rs:55-164, objects/material.rs material_pdf) ---------------------------
  * RTW_INTEGRATOR_LIGHT_CAST / RTW_INTEGRATOR_LIGHT_BIASED send, from every surface hit h, one shadow ray per light: towards the MID-POINT of
  * the light's bounding box (no random draw), `Ray::new(h.p, unit(mid - h.p))` with ray.time 0 whatever the path's time.  The light counts when

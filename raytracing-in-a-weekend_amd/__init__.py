@@ -238,6 +238,11 @@ def lib() -> C.CDLL:
     L.rtw_triangle_hits.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, fp, C.c_uint32, C.c_float, C.c_float, fp, C.POINTER(C.c_int32)]
     L.rtw_ctx_triangle_hits.argtypes = [C.c_void_p, fp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, fp, C.POINTER(C.c_int32),
                                         C.POINTER(RtwStats)]
+    L.rtw_depth_rays.argtypes = [C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, fp]
+    L.rtw_ctx_scene_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.POINTER(RtwStats)]
+    L.rtw_ctx_depth_map.argtypes = [C.c_void_p, C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtwStats)]
     L.rtw_ctx_set_lights.argtypes = [C.c_void_p, C.POINTER(RtwLight), C.c_uint32, C.c_float]
     L.rtw_mgpu_set_lights.argtypes = [C.c_void_p, C.POINTER(RtwLight), C.c_uint32, C.c_float]
     L.rtw_lights_validate.argtypes = [C.POINTER(RtwScene), C.POINTER(RtwLight), C.c_uint32]
@@ -484,6 +489,15 @@ def triangle_hits(triangles, rays, mint: float, maxt: float):
     _check(lib().rtw_triangle_hits(arr, n, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt),
                                    t.ctypes.data_as(C.POINTER(C.c_float)), idx.ctypes.data_as(C.POINTER(C.c_int32))), "rtw_triangle_hits")
     return t, idx
+
+
+def depth_rays(cam: RtwCamera, width: int, height: int) -> np.ndarray:
+    """The rays of Rust2's Viewport::depth_map for a camera of camera2_new (rtw_depth_rays): [height * width, 6] float32 = origin, unit
+    direction, pixel (i, j) at row j * width + i."""
+    width, height = int(width), int(height)
+    out = np.empty((max(0, width * height), 6), np.float32)
+    _check(lib().rtw_depth_rays(C.byref(cam), width, height, out.ctypes.data_as(C.POINTER(C.c_float))), "rtw_depth_rays")
+    return out
 
 
 def triangle_bvh_validate(triangles):
@@ -929,6 +943,32 @@ class Renderer:
                                            t.ctypes.data_as(C.POINTER(C.c_float)), idx.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st)),
                "rtw_ctx_triangle_hits")
         return t, idx, st
+
+    def scene_hits(self, rays, mint: float, maxt: float, time: float = 0.0, accel: int = ACCEL_BVH, normals: bool = False):
+        """The closest hit of each ray ([n][6] = origin, direction; the direction is not normalised) against this context's whole scene
+        (rtw_ctx_scene_hits): (t [n] float32, +inf on a miss; top-level index [n] int32 -- spheres, quads, instances, triangles --, -1 on a
+        miss[; normals [n][3] float32, 0 on a miss]; RtwStats).  Constant-density instances are skipped."""
+        r = _rays(rays)
+        t = np.empty(len(r), np.float32)
+        idx = np.empty(len(r), np.int32)
+        nrm = np.empty((len(r), 3), np.float32) if normals else None
+        st = RtwStats()
+        _check(lib().rtw_ctx_scene_hits(self._h, r.ctypes.data, len(r), float(time), float(mint), float(maxt), int(accel), t.ctypes.data,
+                                        idx.ctypes.data, nrm.ctypes.data if normals else None, C.byref(st)), "rtw_ctx_scene_hits")
+        return (t, idx, nrm, st) if normals else (t, idx, st)
+
+    def depth_map(self, cam: RtwCamera, width: int, height: int, mint: float, maxt: float, time: float = 0.0, accel: int = ACCEL_BVH,
+                  ids: bool = False, normals: bool = False):
+        """Rust2's Viewport::depth_map in one launch (rtw_ctx_depth_map), for a camera of camera2_new: (depth [height][width] float32 -- the
+        hit's t, maxt * 1.6 on a miss --[, ids [height][width] int32, -1 on a miss][, normals [height][width][3] float32]; RtwStats)."""
+        width, height = int(width), int(height)
+        depth = np.empty((height, width), np.float32)
+        idx = np.empty((height, width), np.int32) if ids else None
+        nrm = np.empty((height, width, 3), np.float32) if normals else None
+        st = RtwStats()
+        _check(lib().rtw_ctx_depth_map(self._h, C.byref(cam), width, height, float(time), float(mint), float(maxt), int(accel), depth.ctypes.data,
+                                       idx.ctypes.data if ids else None, nrm.ctypes.data if normals else None, C.byref(st)), "rtw_ctx_depth_map")
+        return (depth,) + ((idx,) if ids else ()) + ((nrm,) if normals else ()) + (st,)
 
     def set_texture_noise(self, tables=None, n_tables: int = 0, per_texture=None, n_textures: int = 0):
         """rtw_ctx_set_texture_noise as is (no arguments: clear the noise of the current scene)."""

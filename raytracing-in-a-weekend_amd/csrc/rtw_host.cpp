@@ -168,6 +168,21 @@ int rtw_camera2_new(float aspect, const float origin[3], const float vup[3], con
     return RTW_OK;
 }
 
+// The rays of Rust2's Viewport::depth_map (Rust2/src/viewport.rs:72-85), normalised as ray_depth does (:63): the host twin of the ray
+// the depth-map kernel builds per pixel (rtw_query.hip) -- same operations, same order, no FMA (this TU is built with -ffp-contract=off).
+int rtw_depth_rays(const RtwCamera *cam, uint32_t width, uint32_t height, float *rays_out) {
+    if (!cam || !rays_out || width == 0 || height == 0) return RTW_E_INVALID;
+    const V left_top = ld(cam->pixel00), delta_x = ld(cam->delta_u), delta_y = ld(cam->delta_v);
+    for (uint32_t j = 0; j < height; j++) {
+        for (uint32_t i = 0; i < width; i++) {
+            const V dir = (left_top + delta_x * ((float)i / (float)width)) + delta_y * ((float)j / (float)height);
+            float *r = rays_out + 6 * ((size_t)j * width + i);
+            st(r, ld(cam->origin)); st(r + 3, unit(dir));
+        }
+    }
+    return RTW_OK;
+}
+
 // Viewport::new (viewport.rs:308-401)
 int rtw_viewport_new(uint32_t width, float aspect_ratio, const float *vfov, const float *origin,
                      const float *direction, const float *vup, const float *lens_radius,

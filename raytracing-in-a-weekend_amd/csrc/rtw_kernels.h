@@ -93,6 +93,30 @@ void launch_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uin
 // tests, [1] node visits (device u64, accumulated)
 void launch_tri_hits(const DevTris &T, const float *rays, uint32_t n, float mint, float maxt, float *t_out, int32_t *idx_out,
                      unsigned long long *counters, hipStream_t stream);
+// rtw_ctx_scene_hits / rtw_ctx_depth_map (rtw_query.hip): one closest-hit query per ray over spheres, quads, instances and triangles.
+struct QueryArgs {
+    DevScene sc;
+    DevBvh   bvh;
+    DevGeom  geom;
+    DevTris  tris;                // tris.n == 0: none; tris.nodes == null: walk the triangle list
+    RtwCamera cam;                // from_camera: Rust2's camera (rtw_camera2_new), pixel i = (i % width, i / width)
+    uint32_t width, height;
+    const float *rays;            // else: [n][6] = o, d (device)
+    uint32_t n;
+    uint32_t levels;              // tree: levels of the per-lane LDS stack (DevBvh.depth + 2: the sentinel, one per tree level)
+    float time, mint, maxt;
+    float miss_t;                 // t_out of a miss: +inf (scene_hits) or maxt * 1.6 (depth_map, Rust2/src/viewport.rs:68)
+    float span;                   // tree: the farthest a sphere centre reaches (rtw_ctx.scene_span), for the per-ray check
+    float *t_out;                 // [n]
+    int32_t *idx_out;             // [n] or null
+    float *normal_out;            // [n][3] or null
+    unsigned long long *counters; // RTW_QUERY_SLOTS lines of RTW_QUERY_STRIDE counters, a workgroup adds to line blockIdx % RTW_QUERY_SLOTS (the host sums
+                                  // the lines): [0] sphere tests [1] node visits (both trees) [2] quad + triangle tests [3] waves whose stack was too short
+};
+#define RTW_QUERY_SLOTS 64u       // one atomic per wave and counter, spread over 64 cache lines: tens of thousands of waves adding to ONE line serialise
+#define RTW_QUERY_STRIDE 16u      // counters (u64) per line: 128 bytes
+// from_camera: rays built from q.cam, else read from q.rays; tree: the sphere group through DevBvh.nodes (dynamic LDS = levels * RTW_BLOCK * 4)
+void launch_scene_hits(const QueryArgs &q, bool from_camera, bool tree, hipStream_t stream);
 // Resident workgroups per CU for the kernel variant (occupancy API), >= 1.
 uint32_t kernel_blocks_per_cu(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);
 // Is there a build of the BVH kernel for this configuration that reads the spheres' {centre, r^2} from LDS?  (KArgs.lds_geom_off may only be set then)

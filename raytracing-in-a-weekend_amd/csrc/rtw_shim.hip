@@ -72,6 +72,7 @@ struct rtw_ctx {
     uint32_t *d_queue = nullptr;
     unsigned long long *d_stats = nullptr;
     unsigned long long *h_stats = nullptr;   // pinned: the counter read-back is a true async copy
+    unsigned long long *d_qstats = nullptr, *h_qstats = nullptr;   // counters of the scene queries: RTW_QUERY_SLOTS lines of RTW_QUERY_STRIDE (rtw_kernels.h)
     float *d_out = nullptr;
     size_t d_out_cap = 0;
     float *h_out = nullptr;              // pinned staging for a multi-GPU frame in PAGEABLE host memory: a device-to-host copy into pageable memory returns only
@@ -238,6 +239,8 @@ int rtw_ctx_create(int device, rtw_ctx **out) {
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_queue, RTW_QUEUE_BYTES);
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_stats, RTW_N_STATS * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_stats, RTW_N_STATS * sizeof(unsigned long long), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_qstats, RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_qstats, RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long), hipHostMallocDefault);
     if (e != hipSuccess) { g_last_hip = (int)e; rtw_ctx_destroy(c); return RTW_E_HIP; }
     c->stream = c->own_stream;
     *out = c;
@@ -280,6 +283,8 @@ void rtw_ctx_destroy(rtw_ctx *c) {
     if (c->d_queue) (void)hipFree(c->d_queue);
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->h_stats) (void)hipHostFree(c->h_stats);
+    if (c->d_qstats) (void)hipFree(c->d_qstats);
+    if (c->h_qstats) (void)hipHostFree(c->h_qstats);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->ev_mark) (void)hipEventDestroy(c->ev_mark);
@@ -673,6 +678,98 @@ int rtw_ctx_triangle_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float 
     if (e != hipSuccess) { g_last_hip = (int)e; return alloc_failed ? RTW_E_NOMEM : RTW_E_HIP; }
     if (stats) { std::memset(stats, 0, sizeof *stats); stats->quad_tests = cnt[0]; stats->node_tests = cnt[1]; }
     return RTW_OK;
+}
+
+// ---- scene ray queries (rtw.h "scene ray queries"; kernel: rtw_query.hip) ------------------------------------------------------------
+// Is `p` memory this context's kernels can address (device or managed memory of its GPU)?  Anything else is staged.
+static bool query_on_device(const rtw_ctx *c, const void *p) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) && attr.device == c->device;
+}
+
+// Both calls: cam != null builds the rays of a width x height map in the kernel, else `rays` [n][6] are read.
+static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, const float *rays, uint32_t n, float time, float mint,
+                       float maxt, uint32_t accel, float miss_t, float *t_out, int32_t *idx_out, float *normal_out, RtwStats *stats) {
+    if (c->pend.active) return RTW_E_INVALID;
+    if (!c->has_scene) return RTW_E_NO_SCENE;
+    HIP_TRY(hipSetDevice(c->device));
+    // The tree under the conditions a render puts on it (render_enqueue_impl); the per-ray ones are checked by the kernel, ray by ray
+    bool tree = accel == RTW_ACCEL_BVH && c->bvh_ok && c->sc.n > c->opt_list_walk_max;
+    if (mint != mint || maxt != maxt || time != time) tree = false;
+    if (!(c->scene_span <= 1e18)) tree = false;
+    if (c->sc.moving && !(time >= c->t_begin && time <= c->t_end)) tree = false;
+
+    QueryArgs q;
+    std::memset(&q, 0, sizeof q);
+    q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom;
+    if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
+    if (cam) { q.cam = *cam; q.width = width; q.height = height; }
+    q.n = n; q.levels = c->bvh.depth + 2u;
+    q.time = time; q.mint = mint; q.maxt = maxt; q.miss_t = miss_t; q.span = (float)c->scene_span;
+    q.counters = c->d_qstats;
+
+    const size_t ray_bytes = 6 * sizeof(float) * (size_t)n, t_bytes = sizeof(float) * (size_t)n, i_bytes = sizeof(int32_t) * (size_t)n;
+    void *d_r = nullptr, *d_t = nullptr, *d_i = nullptr, *d_n = nullptr;       // staging, for whatever is not this GPU's memory
+    hipError_t e = hipSuccess;
+    if (rays) {
+        if (query_on_device(c, rays)) q.rays = rays;
+        else {
+            e = hipMalloc(&d_r, ray_bytes);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_r, rays, ray_bytes, hipMemcpyDefault, c->stream);
+            q.rays = (const float *)d_r;
+        }
+    }
+    if (query_on_device(c, t_out)) q.t_out = t_out;
+    else { if (e == hipSuccess) e = hipMalloc(&d_t, t_bytes); q.t_out = (float *)d_t; }
+    if (idx_out) {
+        if (query_on_device(c, idx_out)) q.idx_out = idx_out;
+        else { if (e == hipSuccess) e = hipMalloc(&d_i, i_bytes); q.idx_out = (int32_t *)d_i; }
+    }
+    if (normal_out) {
+        if (query_on_device(c, normal_out)) q.normal_out = normal_out;
+        else { if (e == hipSuccess) e = hipMalloc(&d_n, 3 * t_bytes); q.normal_out = (float *)d_n; }
+    }
+    const size_t q_bytes = RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_qstats, 0, q_bytes, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    if (e == hipSuccess) {
+        launch_scene_hits(q, cam != nullptr, tree, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess && d_t) e = hipMemcpyAsync(t_out, d_t, t_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess && d_i) e = hipMemcpyAsync(idx_out, d_i, i_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess && d_n) e = hipMemcpyAsync(normal_out, d_n, 3 * t_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->h_qstats, c->d_qstats, q_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    const bool alloc_failed = e == hipErrorOutOfMemory;
+    for (void *b : { d_r, d_t, d_i, d_n }) if (b) (void)hipFree(b);
+    if (e != hipSuccess) { g_last_hip = (int)e; (void)hipGetLastError(); return alloc_failed ? RTW_E_NOMEM : RTW_E_HIP; }
+    unsigned long long sum[4] = { 0, 0, 0, 0 };
+    for (uint32_t s = 0; s < RTW_QUERY_SLOTS; s++) for (int k = 0; k < 4; k++) sum[k] += c->h_qstats[s * RTW_QUERY_STRIDE + k];
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        stats->segments = n;
+        stats->sphere_tests = sum[0]; stats->node_tests = sum[1]; stats->quad_tests = sum[2];
+        stats->kernel_ms = ms;
+    }
+    return sum[3] ? RTW_E_INTERNAL : RTW_OK;
+}
+
+int rtw_ctx_scene_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float time, float mint, float maxt, uint32_t accel,
+                       float *t_out, int32_t *idx_out, float *normal_out, RtwStats *stats) {
+    if (!c || !rays || !t_out || !idx_out || n_rays == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    return scene_query(c, nullptr, 0, 0, rays, n_rays, time, mint, maxt, accel, std::numeric_limits<float>::infinity(), t_out, idx_out, normal_out, stats);
+}
+
+int rtw_ctx_depth_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, float time, float mint, float maxt, uint32_t accel,
+                      float *depth_out, int32_t *idx_out, float *normal_out, RtwStats *stats) {
+    if (!c || !cam || !depth_out || width == 0 || height == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    if ((uint64_t)width * height > 0xFFFFFFFFull) return RTW_E_INVALID;
+    return scene_query(c, cam, width, height, nullptr, width * height, time, mint, maxt, accel, host_mul(maxt, 1.6f), depth_out, idx_out, normal_out, stats);
 }
 
 int rtw_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t turb_depth, float *out) {
