@@ -14,6 +14,7 @@
 // The gradient sum is an f32 sum of ~2 M terms whose association fixes `avg`: it is added in the reference's order, by one wave.
 // Everything here is compiled with -ffp-contract=off and correctly rounded f32 division and sqrt (Makefile), like the reference.
 #include "rtw_filter.h"
+#include "rtw_devmem.h"
 #include "rtw_host.h"
 
 #include <algorithm>
@@ -287,36 +288,24 @@ double ms_since(std::chrono::steady_clock::time_point t) {
 
 // ---- device path ---------------------------------------------------------------------------------------------------------------------
 struct FilterScratch {
-    void *img = nullptr;   size_t img_cap = 0;     // the u8 frame on the device (copied or quantised)
-    void *f32 = nullptr;   size_t f32_cap = 0;     // a host f32 frame, staged for the quantise kernel
-    void *terms = nullptr; size_t terms_cap = 0;   // the gradient terms
-    void *table = nullptr; size_t table_cap = 0;   // weight table [rows][256] f32, then the d2 -> row map
-    void *out = nullptr;   size_t out_cap = 0;     // the u8 result when the caller's buffer is host memory
-    float *sum = nullptr;                          // the gradient sum (device) ...
-    float *h_sum = nullptr;                        // ... and its pinned read-back slot
-    void *h_table = nullptr; size_t h_table_cap = 0;   // pinned: the table's upload is a true async copy
+    DevMem img;                                    // the u8 frame on the device (copied or quantised)
+    DevMem f32;                                    // a host f32 frame, staged for the quantise kernel
+    DevMem terms;                                  // the gradient terms
+    DevMem table;                                  // weight table [rows][256] f32, then the d2 -> row map
+    DevMem out;                                    // the u8 result when the caller's buffer is host memory
+    DevMem sum;                                    // the gradient sum (device) ...
+    PinnedMem h_sum;                               // ... and its pinned read-back slot
+    PinnedMem h_table;                             // pinned: the table's upload is a true async copy
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
 };
 
 void filter_scratch_free(FilterScratch *f) {
     if (!f) return;
-    for (void *b : { f->img, f->f32, f->terms, f->table, f->out, (void *)f->sum }) if (b) (void)hipFree(b);
-    if (f->h_sum) (void)hipHostFree(f->h_sum);
-    if (f->h_table) (void)hipHostFree(f->h_table);
     for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
-    delete f;
+    delete f;                                      // (the buffers free themselves)
 }
 
 namespace {
-hipError_t grow(void **buf, size_t *cap, size_t bytes) {
-    if (*cap >= bytes) return hipSuccess;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *cap = 0;
-    hipError_t e = hipMalloc(buf, bytes);
-    if (e == hipSuccess) *cap = bytes;
-    return e;
-}
-
 bool on_device(const void *p, int device) {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -345,8 +334,8 @@ int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scra
         if (!f) return RTW_E_NOMEM;
         *scratch = f;
         for (hipEvent_t &e : f->ev) FILTER_TRY(hipEventCreate(&e));
-        FILTER_TRY(hipMalloc((void **)&f->sum, sizeof(float)));
-        FILTER_TRY(hipHostMalloc((void **)&f->h_sum, sizeof(float), hipHostMallocDefault));
+        FILTER_TRY(f->sum.reserve(sizeof(float)));
+        FILTER_TRY(f->h_sum.reserve(sizeof(float)));
     }
     FilterScratch *f = *scratch;
     const size_t n_bytes = (size_t)w * h * 3;
@@ -356,36 +345,36 @@ int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scra
     if (p->in_format == RTW_PIXELS_U8) {
         if (on_device(in, device)) img = (const uint8_t *)in;
         else {
-            FILTER_TRY(grow(&f->img, &f->img_cap, n_bytes));
-            FILTER_TRY(hipMemcpyAsync(f->img, in, n_bytes, hipMemcpyDefault, stream));
-            img = (const uint8_t *)f->img;
+            FILTER_TRY(f->img.reserve(n_bytes));
+            FILTER_TRY(hipMemcpyAsync(f->img.ptr, in, n_bytes, hipMemcpyDefault, stream));
+            img = f->img.as<uint8_t>();
         }
     } else {
         const float *src = (const float *)in;
         if (!on_device(in, device)) {
-            FILTER_TRY(grow(&f->f32, &f->f32_cap, n_bytes * sizeof(float)));
-            FILTER_TRY(hipMemcpyAsync(f->f32, in, n_bytes * sizeof(float), hipMemcpyDefault, stream));
-            src = (const float *)f->f32;
+            FILTER_TRY(f->f32.reserve(n_bytes * sizeof(float)));
+            FILTER_TRY(hipMemcpyAsync(f->f32.ptr, in, n_bytes * sizeof(float), hipMemcpyDefault, stream));
+            src = f->f32.as<float>();
         }
-        FILTER_TRY(grow(&f->img, &f->img_cap, n_bytes));
-        hipLaunchKernelGGL(bilateral_quantize_kernel, dim3((unsigned)((n_bytes + 255) / 256)), dim3(256), 0, stream, src, n_bytes, (uint8_t *)f->img);
+        FILTER_TRY(f->img.reserve(n_bytes));
+        hipLaunchKernelGGL(bilateral_quantize_kernel, dim3((unsigned)((n_bytes + 255) / 256)), dim3(256), 0, stream, src, n_bytes, f->img.as<uint8_t>());
         FILTER_TRY(hipGetLastError());
-        img = (const uint8_t *)f->img;
+        img = f->img.as<uint8_t>();
     }
 
     // the range term: the gradient terms in parallel, their sum in the reference's order by one wave, read back
     float avg = p->avg_gradient, gradient_ms = 0.0f;
     if (!(avg > 0.0f)) {
         const uint32_t n = (w - 2) * (h - 2);
-        FILTER_TRY(grow(&f->terms, &f->terms_cap, (size_t)n * sizeof(float)));
+        FILTER_TRY(f->terms.reserve((size_t)n * sizeof(float)));
         FILTER_TRY(hipEventRecord(f->ev[0], stream));
-        hipLaunchKernelGGL(bilateral_gradient_terms_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, img, w, n, (float *)f->terms);
-        hipLaunchKernelGGL(bilateral_gradient_sum_kernel, dim3(1), dim3(64), 0, stream, (const float *)f->terms, n, f->sum);
+        hipLaunchKernelGGL(bilateral_gradient_terms_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, img, w, n, f->terms.as<float>());
+        hipLaunchKernelGGL(bilateral_gradient_sum_kernel, dim3(1), dim3(64), 0, stream, f->terms.as<const float>(), n, f->sum.as<float>());
         FILTER_TRY(hipGetLastError());
         FILTER_TRY(hipEventRecord(f->ev[1], stream));
-        FILTER_TRY(hipMemcpyAsync(f->h_sum, f->sum, sizeof(float), hipMemcpyDeviceToHost, stream));
+        FILTER_TRY(hipMemcpyAsync(f->h_sum.ptr, f->sum.ptr, sizeof(float), hipMemcpyDeviceToHost, stream));
         FILTER_TRY(hipStreamSynchronize(stream));
-        avg = avg_from_sum(*f->h_sum, w, h);
+        avg = avg_from_sum(*f->h_sum.as<float>(), w, h);
         gradient_ms = event_ms(f->ev[0], f->ev[1]);
     }
 
@@ -396,23 +385,18 @@ int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scra
     make_plan(w, h, p->size, edges, pl);
     const size_t n_rows = std::max<size_t>(1, pl.row_d2.size());
     const size_t table_bytes = n_rows * 256 * sizeof(float), map_bytes = pl.rowmap.size() * sizeof(uint16_t);
-    if (f->h_table_cap < table_bytes + map_bytes) {
-        if (f->h_table) (void)hipHostFree(f->h_table);
-        f->h_table = nullptr; f->h_table_cap = 0;
-        FILTER_TRY(hipHostMalloc(&f->h_table, table_bytes + map_bytes, hipHostMallocDefault));
-        f->h_table_cap = table_bytes + map_bytes;
-    }
-    std::memset(f->h_table, 0, table_bytes);
-    build_table(pl, range_term(avg), (float *)f->h_table);
-    std::memcpy((char *)f->h_table + table_bytes, pl.rowmap.data(), map_bytes);
-    FILTER_TRY(grow(&f->table, &f->table_cap, table_bytes + map_bytes));
-    FILTER_TRY(hipMemcpyAsync(f->table, f->h_table, table_bytes + map_bytes, hipMemcpyHostToDevice, stream));
+    FILTER_TRY(f->h_table.reserve(table_bytes + map_bytes));
+    std::memset(f->h_table.ptr, 0, table_bytes);
+    build_table(pl, range_term(avg), f->h_table.as<float>());
+    std::memcpy(f->h_table.as<char>() + table_bytes, pl.rowmap.data(), map_bytes);
+    FILTER_TRY(f->table.reserve(table_bytes + map_bytes));
+    FILTER_TRY(hipMemcpyAsync(f->table.ptr, f->h_table.ptr, table_bytes + map_bytes, hipMemcpyHostToDevice, stream));
     const float table_ms = (float)ms_since(t1);
 
     // the filter
     uint8_t *dst = out;
     const bool direct = on_device(out, device);
-    if (!direct) { FILTER_TRY(grow(&f->out, &f->out_cap, n_bytes)); dst = (uint8_t *)f->out; }
+    if (!direct) { FILTER_TRY(f->out.reserve(n_bytes)); dst = f->out.as<uint8_t>(); }
     const int s = (int)p->size;
     const size_t tile_bytes = (size_t)(FBX + 2 * s) * (FBY + 2 * s) * sizeof(uint32_t);
     const bool table_lds = table_bytes + tile_bytes <= TABLE_LDS_MAX;
@@ -420,8 +404,8 @@ int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scra
     const void *kern = table_lds ? (const void *)bilateral_filter_kernel<true> : (const void *)bilateral_filter_kernel<false>;
     if (lds > 64u * 1024u) FILTER_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const dim3 grid((w + FBX - 1) / FBX, (h + FBY - 1) / FBY);
-    const float *d_table = (const float *)f->table;
-    const uint16_t *d_map = (const uint16_t *)((const char *)f->table + table_bytes);
+    const float *d_table = f->table.as<float>();
+    const uint16_t *d_map = (const uint16_t *)(f->table.as<char>() + table_bytes);
     FILTER_TRY(hipEventRecord(f->ev[2], stream));
     if (table_lds)
         hipLaunchKernelGGL(bilateral_filter_kernel<true>, grid, dim3(FBX * FBY), lds, stream, img, w, h, s, (int)edges, d_table,

@@ -4,6 +4,7 @@
 #include "rtw_kernels.h"
 #include "rtw_host.h"
 #include "rtw_filter.h"
+#include "rtw_devmem.h"
 
 #include <link.h>
 
@@ -28,6 +29,26 @@ static thread_local int g_last_hip = 0;
         if (e_ != hipSuccess) { g_last_hip = (int)e_; return RTW_E_HIP; } \
     } while (0)
 
+// Every allocation of a context is a DevMem / PinnedMem (rtw_devmem.h) in one of these groups; a group is dropped as a unit by assigning an empty
+// one.  The kernels never see them: they get the typed views (DevScene, DevGeom, DevBvh, DevTris, DevNoise) that rtw_ctx_set_* fill from the buffers.
+struct SceneMem {
+    DevMem geom, vel, mat, tex, texels;
+    DevMem quads, inst, igeom, ivel, imat, iquads;
+    DevMem nodes, nodes16, big_geom, big_vel, big_index;
+};
+struct NoiseMem { DevMem perlin, tex_noise; };
+struct TriMem { DevMem list, leaf, nodes; };
+struct ScratchMem {
+    DevMem queue, stats;
+    PinnedMem h_stats;                   // pinned: the counter read-back is a true async copy
+    DevMem qstats; PinnedMem h_qstats;   // counters of the scene queries: RTW_QUERY_SLOTS lines of RTW_QUERY_STRIDE (rtw_kernels.h)
+    DevMem out;                          // compact rows of a render whose destination the kernels cannot write
+    PinnedMem h_out;                     // pinned staging for a multi-GPU frame in PAGEABLE host memory: a device-to-host copy into pageable memory returns only
+                                         // when it is done, which would hold the fork of rtw_mgpu_render at this device until it has rendered its share
+    DevMem order;                        // RTW_OPT_TILE_ORDER: queue position -> tile, valid for order_key
+    DevMem samples;                      // per-sample radiance bank (see render_enqueue)
+};
+
 struct rtw_ctx {
     int device = 0;
     int n_cu = 0;
@@ -43,23 +64,20 @@ struct rtw_ctx {
     float t_begin = 0.0f, t_end = 0.0f;  // ray.time range the BVH bounds were expanded for (rtw_ctx_set_scene)
     DevScene sc{};
     float bg[3] = { 0, 0, 0 };
-    void *d_geom = nullptr, *d_vel = nullptr, *d_mat = nullptr, *d_tex = nullptr, *d_texels = nullptr;
     DevGeom geom{};
-    void *d_quads = nullptr, *d_inst = nullptr, *d_igeom = nullptr, *d_ivel = nullptr, *d_imat = nullptr, *d_iquads = nullptr;
     DevBvh bvh{};
-    void *d_nodes = nullptr, *d_nodes16 = nullptr, *d_big_geom = nullptr, *d_big_vel = nullptr, *d_big_index = nullptr;
+    SceneMem scene_mem;
     // texture noise of the scene (rtw_ctx_set_texture_noise; cleared by rtw_ctx_set_scene)
     uint32_t n_textures = 0;
     std::vector<uint8_t> tex_used;       // [n_textures]: a sphere, quad or instance member reads texture i
     bool noise_active = false;           // a used texture has noise: renders take the noise build (SPEC 7)
     DevNoise noise{};                    // device tables / per-texture entries (null when no noise is set)
-    void *d_perlin = nullptr, *d_tex_noise = nullptr;
+    NoiseMem noise_mem;
     FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
     // Rust2 triangles of the scene (rtw_ctx_set_triangles; cleared by rtw_ctx_set_scene)
-    DevTris tris{};                      // tris.nodes stays null here: a render sets it when the tree may be used
-    const TriNode *tri_nodes = nullptr;
+    DevTris tris{};                      // tris.nodes stays null here: a render sets it (tri_view) when the tree may be used
     bool tri_tree = false;               // no triangle breaks the cull's derivation (DESIGN.md "Rust2 triangles")
-    void *d_tri_list = nullptr, *d_tri_leaf = nullptr, *d_tri_nodes = nullptr;
+    TriMem tri_mem;
     // lights of the scene (rtw_ctx_set_lights; cleared by rtw_ctx_set_scene): the rows the light build reads from its arguments
     DevLights lights{};
     std::vector<RtwSphere> h_spheres;    // host copies of the top-level spheres and quads: a light's mid-point is formed from them
@@ -68,22 +86,10 @@ struct rtw_ctx {
     // MixedMaterial (RTW_FLAG_MIXED_MATERIAL): does the scene hold an object with opacity < 0, and is the exponent (ir) of every such object
     // finite and >= 0?  Computed once by rtw_ctx_set_scene.
     bool has_mixed = false, mixed_bad = false;
-    // scratch
-    uint32_t *d_queue = nullptr;
-    unsigned long long *d_stats = nullptr;
-    unsigned long long *h_stats = nullptr;   // pinned: the counter read-back is a true async copy
-    unsigned long long *d_qstats = nullptr, *h_qstats = nullptr;   // counters of the scene queries: RTW_QUERY_SLOTS lines of RTW_QUERY_STRIDE (rtw_kernels.h)
-    float *d_out = nullptr;
-    size_t d_out_cap = 0;
-    float *h_out = nullptr;              // pinned staging for a multi-GPU frame in PAGEABLE host memory: a device-to-host copy into pageable memory returns only
-    size_t h_out_cap = 0;                // when it is done, which would hold the fork of rtw_mgpu_render at this device until it has rendered its share
-    uint32_t *d_order = nullptr;         // RTW_OPT_TILE_ORDER: queue position -> tile, valid for order_key
-    size_t d_order_cap = 0;
+    ScratchMem scr;
     TileOrderKey order_key{};
     SceneCull cull{};                    // what the tile-order heuristic knows about the scene (host copy, set by rtw_ctx_set_scene)
     uint32_t scene_serial = 0;           // bumped by every rtw_ctx_set_scene
-    float *d_samples = nullptr;          // per-sample radiance bank (see render_enqueue)
-    size_t d_samples_cap = 0;
     // options (rtw_ctx_set_option)
     uint32_t opt_chunk_len = 0;          // 0 = auto (render_enqueue); round 1 tuned a fixed 4 on the bench frame (1: 13.5, 2: 17.0, 4: 17.9, 8: 17.3, 16: 16.8 Gsegments/s)
     uint64_t opt_bank_bytes = 48ull << 30;
@@ -169,11 +175,9 @@ static void prepare_quads(const RtwQuad *q, uint32_t n, std::vector<DevQuad> &ou
 }
 
 template <class T>
-static int upload(void **dst, const std::vector<T> &src) {
-    size_t bytes = src.size() * sizeof(T);
-    if (bytes == 0) bytes = sizeof(T);
-    HIP_TRY(hipMalloc(dst, bytes));
-    if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+static int upload(DevMem &dst, const std::vector<T> &src) {
+    HIP_TRY(dst.reserve(src.empty() ? sizeof(T) : src.size() * sizeof(T)));       // (an empty list is still an address: "absent" is the caller's decision)
+    if (!src.empty()) HIP_TRY(hipMemcpy(dst.ptr, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return RTW_OK;
 }
 
@@ -236,11 +240,11 @@ int rtw_ctx_create(int device, rtw_ctx **out) {
     if (e == hipSuccess) e = hipEventCreate(&c->ev0);
     if (e == hipSuccess) e = hipEventCreate(&c->ev1);
     if (e == hipSuccess) e = hipEventCreate(&c->ev_mark);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_queue, RTW_QUEUE_BYTES);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_stats, RTW_N_STATS * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_stats, RTW_N_STATS * sizeof(unsigned long long), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_qstats, RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_qstats, RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long), hipHostMallocDefault);
+    if (e == hipSuccess) e = c->scr.queue.reserve(RTW_QUEUE_BYTES);
+    if (e == hipSuccess) e = c->scr.stats.reserve(RTW_N_STATS * sizeof(unsigned long long));
+    if (e == hipSuccess) e = c->scr.h_stats.reserve(RTW_N_STATS * sizeof(unsigned long long));
+    if (e == hipSuccess) e = c->scr.qstats.reserve(RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long));
+    if (e == hipSuccess) e = c->scr.h_qstats.reserve(RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long));
     if (e != hipSuccess) { g_last_hip = (int)e; rtw_ctx_destroy(c); return RTW_E_HIP; }
     c->stream = c->own_stream;
     *out = c;
@@ -248,24 +252,19 @@ int rtw_ctx_create(int device, rtw_ctx **out) {
 }
 
 static void free_noise(rtw_ctx *c) {
-    void **bufs[] = { &c->d_perlin, &c->d_tex_noise };
-    for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    c->noise_mem = NoiseMem{};
     c->noise = DevNoise{};
     c->noise_active = false;
 }
 
 static void free_tris(rtw_ctx *c) {
-    void **bufs[] = { &c->d_tri_list, &c->d_tri_leaf, &c->d_tri_nodes };
-    for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    c->tri_mem = TriMem{};
     c->tris = DevTris{};
-    c->tri_nodes = nullptr;
     c->tri_tree = false;
 }
 
 static void free_scene(rtw_ctx *c) {
-    void **bufs[] = { &c->d_quads, &c->d_inst, &c->d_igeom, &c->d_ivel, &c->d_imat, &c->d_iquads,
-                      &c->d_geom, &c->d_vel, &c->d_mat, &c->d_tex, &c->d_texels, &c->d_nodes, &c->d_nodes16, &c->d_big_geom, &c->d_big_vel, &c->d_big_index };
-    for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    c->scene_mem = SceneMem{};
     free_noise(c);
     free_tris(c);
     c->lights = DevLights{};
@@ -279,18 +278,10 @@ static void free_scene(rtw_ctx *c) {
 void rtw_ctx_destroy(rtw_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    free_scene(c);
-    if (c->d_queue) (void)hipFree(c->d_queue);
-    if (c->d_stats) (void)hipFree(c->d_stats);
-    if (c->h_stats) (void)hipHostFree(c->h_stats);
-    if (c->d_qstats) (void)hipFree(c->d_qstats);
-    if (c->h_qstats) (void)hipHostFree(c->h_qstats);
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    if (c->ev_mark) (void)hipEventDestroy(c->ev_mark);
-    if (c->d_samples) (void)hipFree(c->d_samples);
-    if (c->d_order) (void)hipFree(c->d_order);
+    free_scene(c);                       // memory first, on its device, then the events and the stream: nothing is left for `delete` to free
+    c->scr = ScratchMem{};
     filter_scratch_free(c->filter);
+    if (c->ev_mark) (void)hipEventDestroy(c->ev_mark);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -402,9 +393,10 @@ int rtw_ctx_set_scene(rtw_ctx *c, const RtwScene *s, float t_begin, float t_end)
     std::vector<RtwTexture> tex(s->textures, s->textures + s->n_textures);
     std::vector<float> texels(s->texels, s->texels + 3 * (size_t)s->n_texels);
 
+    SceneMem m;                          // the context gets it when all of it is there: a failure below leaves the context without a scene
     int rc;
-    if ((rc = upload(&c->d_geom, geom)) || (rc = upload(&c->d_vel, vel)) || (rc = upload(&c->d_mat, mat)) ||
-        (rc = upload(&c->d_tex, tex)) || (rc = upload(&c->d_texels, texels))) { free_scene(c); return rc; }
+    if ((rc = upload(m.geom, geom)) || (rc = upload(m.vel, vel)) || (rc = upload(m.mat, mat)) ||
+        (rc = upload(m.tex, tex)) || (rc = upload(m.texels, texels))) return rc;
 
     // quads and instances (Scene::new, viewport.rs:122-135).  Their AABB trees (qaabb.rs, iaabb.rs) only prune list
     // walks over a handful of objects: the device walks the lists.
@@ -429,11 +421,11 @@ int rtw_ctx_set_scene(rtw_ctx *c, const RtwScene *s, float t_begin, float t_end)
             }
             rotation_coefficients(d.back, d.back_k); rotation_coefficients(d.fwd, d.fwd_k);
         }
-        if ((rc = upload(&c->d_quads, quads)) || (rc = upload(&c->d_iquads, iquads)) || (rc = upload(&c->d_inst, inst)) ||
-            (rc = upload(&c->d_igeom, igeom)) || (rc = upload(&c->d_ivel, ivel)) || (rc = upload(&c->d_imat, imat))) { free_scene(c); return rc; }
-        c->geom.quads = (const DevQuad *)c->d_quads; c->geom.iquads = (const DevQuad *)c->d_iquads;
-        c->geom.inst = (const DevInstance *)c->d_inst;
-        c->geom.igeom = (const f4 *)c->d_igeom; c->geom.ivel = (const f4 *)c->d_ivel; c->geom.imat = (const DevMat *)c->d_imat;
+        if ((rc = upload(m.quads, quads)) || (rc = upload(m.iquads, iquads)) || (rc = upload(m.inst, inst)) ||
+            (rc = upload(m.igeom, igeom)) || (rc = upload(m.ivel, ivel)) || (rc = upload(m.imat, imat))) return rc;
+        c->geom.quads = m.quads.as<DevQuad>(); c->geom.iquads = m.iquads.as<DevQuad>();
+        c->geom.inst = m.inst.as<DevInstance>();
+        c->geom.igeom = m.igeom.as<f4>(); c->geom.ivel = m.ivel.as<f4>(); c->geom.imat = m.imat.as<DevMat>();
         c->geom.n_quads = s->n_quads; c->geom.n_inst = s->n_instances;
     }
 
@@ -442,14 +434,13 @@ int rtw_ctx_set_scene(rtw_ctx *c, const RtwScene *s, float t_begin, float t_end)
     build_bvh(s->spheres, s->n_spheres, std::fmin(t_begin, t_end), std::fmax(t_begin, t_end), bb);
     std::vector<f4> big_geom, big_vel;
     for (uint32_t i : bb.big) { big_geom.push_back(geom[i]); big_vel.push_back(vel[i]); }
-    if ((rc = upload(&c->d_nodes16, bb.nodes16))) { free_scene(c); return rc; }
-    c->bvh.nodes16 = bb.nodes16.empty() ? nullptr : (const BvhNode16 *)c->d_nodes16;
+    if ((rc = upload(m.nodes16, bb.nodes16)) || (rc = upload(m.nodes, bb.nodes)) || (rc = upload(m.big_geom, big_geom)) ||
+        (rc = upload(m.big_vel, big_vel)) || (rc = upload(m.big_index, bb.big))) return rc;
+    c->bvh.nodes16 = bb.nodes16.empty() ? nullptr : m.nodes16.as<BvhNode16>();     // (null = "this tree has no f16 nodes": the kernels' builds differ)
     c->bvh.n_nodes = (uint32_t)bb.nodes.size();
-    if ((rc = upload(&c->d_nodes, bb.nodes)) || (rc = upload(&c->d_big_geom, big_geom)) ||
-        (rc = upload(&c->d_big_vel, big_vel)) || (rc = upload(&c->d_big_index, bb.big))) { free_scene(c); return rc; }
-    c->bvh.nodes = (const BvhNode *)c->d_nodes;
-    c->bvh.big_geom = (const f4 *)c->d_big_geom; c->bvh.big_vel = (const f4 *)c->d_big_vel;
-    c->bvh.big_index = (const uint32_t *)c->d_big_index; c->bvh.n_big = (uint32_t)bb.big.size();
+    c->bvh.nodes = m.nodes.as<BvhNode>();
+    c->bvh.big_geom = m.big_geom.as<f4>(); c->bvh.big_vel = m.big_vel.as<f4>();
+    c->bvh.big_index = m.big_index.as<uint32_t>(); c->bvh.n_big = (uint32_t)bb.big.size();
     c->bvh.root = bb.root; c->bvh.depth = bb.depth;
     c->bvh_ok = bb.depth <= RTW_BVH_STACK;        // build_bvh guarantees it; a deeper tree would overflow the per-lane LDS stack
     {   // The tree prunes on the premise that the reference's quadratic is computed in ORDINARY f32 (DESIGN.md "Conservative traversal").  A centre at 1e19 or
@@ -489,8 +480,9 @@ int rtw_ctx_set_scene(rtw_ctx *c, const RtwScene *s, float t_begin, float t_end)
     c->bvh.inv_2rmin = bb.r_min > 0.0f ? 1.0f / (2.0f * bb.r_min) : INFINITY;
     c->bvh.abs_max = bb.abs_max;
 
-    c->sc.geom = (const f4 *)c->d_geom; c->sc.vel = (const f4 *)c->d_vel; c->sc.mat = (const DevMat *)c->d_mat;
-    c->sc.tex = (const RtwTexture *)c->d_tex; c->sc.texels = (const float *)c->d_texels;
+    c->sc.geom = m.geom.as<f4>(); c->sc.vel = m.vel.as<f4>(); c->sc.mat = m.mat.as<DevMat>();
+    c->sc.tex = m.tex.as<RtwTexture>(); c->sc.texels = m.texels.as<float>();
+    c->scene_mem = std::move(m);
     c->sc.n = s->n_spheres; c->sc.moving = moving ? 1u : 0u;
     std::memcpy(c->bg, s->background, sizeof c->bg);
     c->has_textures = false;
@@ -606,10 +598,12 @@ int rtw_ctx_set_texture_noise(rtw_ctx *c, const RtwPerlin *tables, uint32_t n_ta
     if (!active) return RTW_OK;                                    // no texture a primitive reads has noise: the image is the noise-free one
     std::vector<RtwPerlin> tb(tables, tables + n_tables);
     std::vector<RtwTextureNoise> tn(per_texture, per_texture + n_textures);
+    NoiseMem m;
     int rc;
-    if ((rc = upload(&c->d_perlin, tb)) || (rc = upload(&c->d_tex_noise, tn))) { free_noise(c); return rc; }
-    c->noise.tables = (const RtwPerlin *)c->d_perlin;
-    c->noise.tex = (const RtwTextureNoise *)c->d_tex_noise;
+    if ((rc = upload(m.perlin, tb)) || (rc = upload(m.tex_noise, tn))) return rc;
+    c->noise.tables = m.perlin.as<RtwPerlin>();
+    c->noise.tex = m.tex_noise.as<RtwTextureNoise>();
+    c->noise_mem = std::move(m);
     c->noise_active = true;
     return RTW_OK;
 }
@@ -630,13 +624,24 @@ int rtw_ctx_set_triangles(rtw_ctx *c, const RtwTriangle *tris, uint32_t n) {
     if (!tri_build(list.data(), n, b)) return RTW_E_NOMEM;
     std::vector<DevTri> leaf(b.leaf, b.leaf + n);
     std::vector<TriNode> nodes(b.nodes, b.nodes + b.n_nodes);
+    TriMem m;
     int rc;
-    if ((rc = upload(&c->d_tri_list, list)) || (rc = upload(&c->d_tri_leaf, leaf)) || (rc = upload(&c->d_tri_nodes, nodes))) { free_tris(c); return rc; }
-    c->tris.list = (const DevTri *)c->d_tri_list; c->tris.leaf = (const DevTri *)c->d_tri_leaf;
+    if ((rc = upload(m.list, list)) || (rc = upload(m.leaf, leaf)) || (rc = upload(m.nodes, nodes))) return rc;
+    c->tris.list = m.list.as<DevTri>(); c->tris.leaf = m.leaf.as<DevTri>();
     c->tris.n = n; c->tris.n_nodes = b.n_nodes;
-    c->tri_nodes = (const TriNode *)c->d_tri_nodes;
     c->tri_tree = !b.list_walk;
+    c->tri_mem = std::move(m);
     return RTW_OK;
+}
+
+// The end of a call that works through temporaries of its own (DevMem locals): `e` is what its chain of HIP calls came to.  After a failure the
+// stream is waited for first -- part of the chain may have been enqueued, and nothing may still use the temporaries when the caller's scope frees them.
+static int call_status(rtw_ctx *c, hipError_t e) {
+    if (e == hipSuccess) return RTW_OK;
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipGetLastError();
+    g_last_hip = (int)e;
+    return e == hipErrorOutOfMemory ? RTW_E_NOMEM : RTW_E_HIP;
 }
 
 // The triangle view a render or query of this context uses: the tree only for RTW_ACCEL_BVH and a range the cull's derivation covers
@@ -645,7 +650,7 @@ static DevTris tri_view(const rtw_ctx *c, uint32_t accel, float mint, float maxt
     const float tb = std::fmax(std::fabs(mint), std::fabs(maxt));
     t.t_bound = tb;
     const bool range_ok = std::isfinite(mint) && std::isfinite(maxt) && tb <= RTW_TRI_COORD_MAX;
-    t.nodes = (accel == RTW_ACCEL_BVH && c->tri_tree && range_ok) ? c->tri_nodes : nullptr;
+    t.nodes = (accel == RTW_ACCEL_BVH && c->tri_tree && range_ok) ? c->tri_mem.nodes.as<TriNode>() : nullptr;
     return t;
 }
 
@@ -657,25 +662,23 @@ int rtw_ctx_triangle_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float 
     HIP_TRY(hipSetDevice(c->device));
     const DevTris T = tri_view(c, accel, mint, maxt);
     const size_t ray_bytes = 6 * sizeof(float) * (size_t)n_rays, t_bytes = sizeof(float) * (size_t)n_rays, i_bytes = sizeof(int32_t) * (size_t)n_rays;
-    void *d_r = nullptr, *d_t = nullptr, *d_i = nullptr, *d_c = nullptr;
+    DevMem d_r, d_t, d_i, d_c;
     unsigned long long cnt[2] = { 0, 0 };
-    hipError_t e = hipMalloc(&d_r, ray_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_t, t_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_i, i_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_c, sizeof cnt);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_r, rays, ray_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_c, 0, sizeof cnt, c->stream);
+    hipError_t e = d_r.reserve(ray_bytes);
+    if (e == hipSuccess) e = d_t.reserve(t_bytes);
+    if (e == hipSuccess) e = d_i.reserve(i_bytes);
+    if (e == hipSuccess) e = d_c.reserve(sizeof cnt);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_r.ptr, rays, ray_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_c.ptr, 0, sizeof cnt, c->stream);
     if (e == hipSuccess) {
-        launch_tri_hits(T, (const float *)d_r, n_rays, mint, maxt, (float *)d_t, (int32_t *)d_i, (unsigned long long *)d_c, c->stream);
+        launch_tri_hits(T, d_r.as<const float>(), n_rays, mint, maxt, d_t.as<float>(), d_i.as<int32_t>(), d_c.as<unsigned long long>(), c->stream);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(t_out, d_t, t_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(idx_out, d_i, i_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt, d_c, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t_out, d_t.ptr, t_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(idx_out, d_i.ptr, i_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt, d_c.ptr, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    const bool alloc_failed = e == hipErrorOutOfMemory;
-    for (void *b : { d_r, d_t, d_i, d_c }) if (b) (void)hipFree(b);
-    if (e != hipSuccess) { g_last_hip = (int)e; return alloc_failed ? RTW_E_NOMEM : RTW_E_HIP; }
+    if (const int rc = call_status(c, e)) return rc;
     if (stats) { std::memset(stats, 0, sizeof *stats); stats->quad_tests = cnt[0]; stats->node_tests = cnt[1]; }
     return RTW_OK;
 }
@@ -707,49 +710,48 @@ static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_
     if (cam) { q.cam = *cam; q.width = width; q.height = height; }
     q.n = n; q.levels = c->bvh.depth + 2u;
     q.time = time; q.mint = mint; q.maxt = maxt; q.miss_t = miss_t; q.span = (float)c->scene_span;
-    q.counters = c->d_qstats;
+    q.counters = c->scr.qstats.as<unsigned long long>();
 
     const size_t ray_bytes = 6 * sizeof(float) * (size_t)n, t_bytes = sizeof(float) * (size_t)n, i_bytes = sizeof(int32_t) * (size_t)n;
-    void *d_r = nullptr, *d_t = nullptr, *d_i = nullptr, *d_n = nullptr;       // staging, for whatever is not this GPU's memory
+    DevMem d_r, d_t, d_i, d_n;           // staging, for whatever is not this GPU's memory
     hipError_t e = hipSuccess;
     if (rays) {
         if (query_on_device(c, rays)) q.rays = rays;
         else {
-            e = hipMalloc(&d_r, ray_bytes);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_r, rays, ray_bytes, hipMemcpyDefault, c->stream);
-            q.rays = (const float *)d_r;
+            e = d_r.reserve(ray_bytes);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_r.ptr, rays, ray_bytes, hipMemcpyDefault, c->stream);
+            q.rays = d_r.as<const float>();
         }
     }
     if (query_on_device(c, t_out)) q.t_out = t_out;
-    else { if (e == hipSuccess) e = hipMalloc(&d_t, t_bytes); q.t_out = (float *)d_t; }
+    else { if (e == hipSuccess) e = d_t.reserve(t_bytes); q.t_out = d_t.as<float>(); }
     if (idx_out) {
         if (query_on_device(c, idx_out)) q.idx_out = idx_out;
-        else { if (e == hipSuccess) e = hipMalloc(&d_i, i_bytes); q.idx_out = (int32_t *)d_i; }
+        else { if (e == hipSuccess) e = d_i.reserve(i_bytes); q.idx_out = d_i.as<int32_t>(); }
     }
     if (normal_out) {
         if (query_on_device(c, normal_out)) q.normal_out = normal_out;
-        else { if (e == hipSuccess) e = hipMalloc(&d_n, 3 * t_bytes); q.normal_out = (float *)d_n; }
+        else { if (e == hipSuccess) e = d_n.reserve(3 * t_bytes); q.normal_out = d_n.as<float>(); }
     }
     const size_t q_bytes = RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_qstats, 0, q_bytes, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->scr.qstats.ptr, 0, q_bytes, c->stream);
     if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
     if (e == hipSuccess) {
         launch_scene_hits(q, cam != nullptr, tree, c->stream);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess && d_t) e = hipMemcpyAsync(t_out, d_t, t_bytes, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess && d_i) e = hipMemcpyAsync(idx_out, d_i, i_bytes, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess && d_n) e = hipMemcpyAsync(normal_out, d_n, 3 * t_bytes, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->h_qstats, c->d_qstats, q_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && d_t.ptr) e = hipMemcpyAsync(t_out, d_t.ptr, t_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess && d_i.ptr) e = hipMemcpyAsync(idx_out, d_i.ptr, i_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess && d_n.ptr) e = hipMemcpyAsync(normal_out, d_n.ptr, 3 * t_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->scr.h_qstats.ptr, c->scr.qstats.ptr, q_bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     float ms = 0.0f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    const bool alloc_failed = e == hipErrorOutOfMemory;
-    for (void *b : { d_r, d_t, d_i, d_n }) if (b) (void)hipFree(b);
-    if (e != hipSuccess) { g_last_hip = (int)e; (void)hipGetLastError(); return alloc_failed ? RTW_E_NOMEM : RTW_E_HIP; }
+    if (const int rc = call_status(c, e)) return rc;
+    const unsigned long long *h_qstats = c->scr.h_qstats.as<unsigned long long>();
     unsigned long long sum[4] = { 0, 0, 0, 0 };
-    for (uint32_t s = 0; s < RTW_QUERY_SLOTS; s++) for (int k = 0; k < 4; k++) sum[k] += c->h_qstats[s * RTW_QUERY_STRIDE + k];
+    for (uint32_t s = 0; s < RTW_QUERY_SLOTS; s++) for (int k = 0; k < 4; k++) sum[k] += h_qstats[s * RTW_QUERY_STRIDE + k];
     if (stats) {
         std::memset(stats, 0, sizeof *stats);
         stats->segments = n;
@@ -783,22 +785,19 @@ int rtw_ctx_perlin_eval(rtw_ctx *c, const RtwPerlin *t, const float *points, uin
     if (c->pend.active) return RTW_E_INVALID;
     HIP_TRY(hipSetDevice(c->device));
     const size_t pts_bytes = 3 * sizeof(float) * (size_t)n, out_bytes = sizeof(float) * (size_t)n;
-    void *d_t = nullptr, *d_p = nullptr, *d_o = nullptr;
-    hipError_t e = hipMalloc(&d_t, sizeof(RtwPerlin));
-    if (e == hipSuccess) e = hipMalloc(&d_p, pts_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_o, out_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, sizeof(RtwPerlin), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_p, points, pts_bytes, hipMemcpyHostToDevice, c->stream);
+    DevMem d_t, d_p, d_o;
+    hipError_t e = d_t.reserve(sizeof(RtwPerlin));
+    if (e == hipSuccess) e = d_p.reserve(pts_bytes);
+    if (e == hipSuccess) e = d_o.reserve(out_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_t.ptr, t, sizeof(RtwPerlin), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_p.ptr, points, pts_bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        launch_perlin_eval((const RtwPerlin *)d_t, (const float *)d_p, n, turb_depth, (float *)d_o, c->stream);
+        launch_perlin_eval(d_t.as<const RtwPerlin>(), d_p.as<const float>(), n, turb_depth, d_o.as<float>(), c->stream);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, out_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_o.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    const bool alloc_failed = e == hipErrorOutOfMemory;
-    for (void *b : { d_t, d_p, d_o }) if (b) (void)hipFree(b);
-    if (e != hipSuccess) { g_last_hip = (int)e; return alloc_failed ? RTW_E_NOMEM : RTW_E_HIP; }
-    return RTW_OK;
+    return call_status(c, e);
 }
 
 // The bilateral post-process (rtw_filter.hip) on this context's GPU and stream; the scene is not involved.
@@ -939,7 +938,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     a.inv_gamma = host_div(1.0f, p->gamma);                       // viewport.rs:232
     a.mint = p->mint; a.maxt = p->maxt;
     std::memcpy(a.bg, c->bg, sizeof a.bg);
-    a.queue = c->d_queue; a.stats = c->d_stats;
+    a.queue = c->scr.queue.as<uint32_t>(); a.stats = c->scr.stats.as<unsigned long long>();
     if (c->noise_active) a.noise = c->noise;                       // (selects the noise build: pick_kernel)
     if (c->tris.n) a.tris = tri_view(c, p->accel, p->mint, p->maxt);   // (selects the triangle build; the tree for RTW_ACCEL_BVH requests)
     if (light_integrator) a.lights = c->lights;                    // (the integrator selects the light build, which alone reads them)
@@ -980,13 +979,8 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     if (band_tile_rows == 0) return RTW_E_NOMEM;                  // one row of tiles does not fit the budget
     if (band_tile_rows > tile_rows) band_tile_rows = tile_rows;
     const size_t sample_bytes = (size_t)(band_tile_rows * slots_per_tile_row) * 12;
-    if (c->d_samples_cap < sample_bytes) {
-        if (c->d_samples) (void)hipFree(c->d_samples);
-        c->d_samples = nullptr; c->d_samples_cap = 0;
-        if (hipMalloc((void **)&c->d_samples, sample_bytes ? sample_bytes : 12) != hipSuccess) { (void)hipGetLastError(); return RTW_E_NOMEM; }
-        c->d_samples_cap = sample_bytes;
-    }
-    a.samples = c->d_samples;
+    if (c->scr.samples.reserve(sample_bytes) != hipSuccess) { (void)hipGetLastError(); return RTW_E_NOMEM; }
+    a.samples = c->scr.samples.as<float>();
 
     // destination: the kernels write compact rows either straight into the caller's device buffer or into the context's
     const size_t out_bytes = (size_t)n_rows * p->width * 3 * sizeof(float);
@@ -1004,21 +998,11 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     const bool direct = c->attr_on_device && c->attr_device == c->device && !(out.scatter && p->part_count > 1);
     // A multi-GPU frame in pageable host memory (the reference's Img, a Vec, a numpy array): staged through this context's pinned buffer
     const bool staged = out.scatter && !c->attr_on_device && !pinned_host;
-    if (staged && c->h_out_cap < out_bytes) {
-        if (c->h_out) (void)hipHostFree(c->h_out);
-        c->h_out = nullptr; c->h_out_cap = 0;
-        if (hipHostMalloc((void **)&c->h_out, out_bytes ? out_bytes : 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return RTW_E_NOMEM; }
-        c->h_out_cap = out_bytes;
-    }
+    if (staged && c->scr.h_out.reserve(out_bytes) != hipSuccess) { (void)hipGetLastError(); return RTW_E_NOMEM; }
     if (direct) a.out = out.base;
     else {
-        if (c->d_out_cap < out_bytes) {
-            if (c->d_out) (void)hipFree(c->d_out);
-            c->d_out = nullptr; c->d_out_cap = 0;
-            HIP_TRY(hipMalloc((void **)&c->d_out, out_bytes ? out_bytes : 4));
-            c->d_out_cap = out_bytes;
-        }
-        a.out = c->d_out;
+        HIP_TRY(c->scr.out.reserve(out_bytes));
+        a.out = c->scr.out.as<float>();
     }
 
     // dynamic LDS layout of the BVH kernel for this tree
@@ -1058,11 +1042,11 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     if (!(phases & PH_LAUNCH)) return RTW_OK;          // PREPARE only: everything that can wait for the device is behind us
 
     if (!c->pend.marked) HIP_TRY(hipEventRecord(c->ev_mark, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_stats, 0, RTW_N_STATS * sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(a.stats, 0, RTW_N_STATS * sizeof(unsigned long long), c->stream));
 #ifdef RTW_ENDTIMES
-    HIP_TRY(hipMemsetAsync(c->d_stats + 24, 0xFF, sizeof(unsigned long long), c->stream));     // atomicMin targets (diagnostic build only)
-    HIP_TRY(hipMemsetAsync(c->d_stats + 26, 0xFF, sizeof(unsigned long long), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_stats + 28, 0xFF, sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(a.stats + 24, 0xFF, sizeof(unsigned long long), c->stream));     // atomicMin targets (diagnostic build only)
+    HIP_TRY(hipMemsetAsync(a.stats + 26, 0xFF, sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(a.stats + 28, 0xFF, sizeof(unsigned long long), c->stream));
 #endif
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     for (uint32_t tr0 = 0; tr0 < tile_rows || tr0 == 0; tr0 += (uint32_t)band_tile_rows) {
@@ -1084,20 +1068,15 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
             // tiles worth of work in flight when the queue runs dry: four units for every lane of the full grid
             const uint64_t per_tile = 64ull * a.n_chunks;
             key.tail_tiles = (uint32_t)std::min<uint64_t>(a.n_tiles, ((uint64_t)c->n_cu * per_cu * RTW_BLOCK * 4ull + per_tile - 1) / per_tile);
-            if (!c->d_order || std::memcmp(&key, &c->order_key, sizeof key) != 0) {
+            if (!c->scr.order.ptr || std::memcmp(&key, &c->order_key, sizeof key) != 0) {
                 std::vector<uint32_t> order;
                 build_tile_order(c->opt_tile_order, a.tiles_x, tiles_y, a.k_base, a.row_block, a.part_index, a.part_count, *cam, c->cull, key.tail_tiles, order);
-                if (c->d_order_cap < order.size()) {
-                    if (c->d_order) (void)hipFree(c->d_order);
-                    c->d_order = nullptr; c->d_order_cap = 0;
-                    HIP_TRY(hipMalloc((void **)&c->d_order, order.size() * sizeof(uint32_t)));
-                    c->d_order_cap = order.size();
-                }
-                HIP_TRY(hipMemcpyAsync(c->d_order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(c->scr.order.reserve(order.size() * sizeof(uint32_t)));
+                HIP_TRY(hipMemcpyAsync(c->scr.order.ptr, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
                 HIP_TRY(hipStreamSynchronize(c->stream));          // (`order` is a local: the copy must be done before it goes away; once per frame shape)
                 c->order_key = key;
             }
-            a.tile_order = c->d_order;
+            a.tile_order = c->scr.order.as<uint32_t>();
         }
         // Small launches are latency-bound, not throughput-bound: a lane should own >= ~16 work units before another resident
         // workgroup per CU pays (profiles/r02_small_frame.log: C1 0.494 -> 0.276 ms with 1 workgroup per CU instead of 6, `First
@@ -1149,13 +1128,13 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
             if (blocks > a.n_chunks) blocks = a.n_chunks;
             a.grab_max = (blocks ? blocks : 1u) * 64u;
         }
-        HIP_TRY(hipMemsetAsync(c->d_queue, 0, RTW_QUEUE_BYTES, c->stream));
+        HIP_TRY(hipMemsetAsync(a.queue, 0, RTW_QUEUE_BYTES, c->stream));
         if (a.n_tiles) launch_render(a, c->sc.moving != 0, accel, grid, c->stream);
         HIP_TRY(hipGetLastError());
         if (tile_rows == 0) break;
     }
     HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_stats, c->d_stats, RTW_N_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->scr.h_stats.ptr, a.stats, RTW_N_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     c->pend.active = true; c->pend.n_rows = n_rows;
     c->pend.dst = out.base; c->pend.scatter = out.scatter; c->pend.direct = direct; c->pend.staged = staged;
     c->pend.width = p->width; c->pend.height = p->height; c->pend.row_block = a.row_block; c->pend.part_index = p->part_index; c->pend.part_count = p->part_count;
@@ -1172,11 +1151,11 @@ static int render_copy(rtw_ctx *c) {
     if (q.direct) return RTW_OK;                        // the kernels wrote into the caller's device buffer
     HIP_TRY(hipSetDevice(c->device));
     if (q.staged) {                                     // pinned staging now (a true asynchronous copy), the caller's pageable frame in render_wait
-        HIP_TRY(hipMemcpyAsync(c->h_out, c->d_out, q.out_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->scr.h_out.ptr, c->scr.out.ptr, q.out_bytes, hipMemcpyDeviceToHost, c->stream));
     } else if (q.scatter) {
-        const int rc = scatter_rows(c, c->d_out, q.dst, q.width, q.height, q.row_block, q.part_index, q.part_count);
+        const int rc = scatter_rows(c, c->scr.out.as<float>(), q.dst, q.width, q.height, q.row_block, q.part_index, q.part_count);
         if (rc != RTW_OK) return rc;
-    } else HIP_TRY(hipMemcpyAsync(q.dst, c->d_out, q.out_bytes, hipMemcpyDefault, c->stream));
+    } else HIP_TRY(hipMemcpyAsync(q.dst, c->scr.out.ptr, q.out_bytes, hipMemcpyDefault, c->stream));
     return RTW_OK;
 }
 
@@ -1187,11 +1166,11 @@ static int render_wait(rtw_ctx *c, RtwStats *stats) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->pend.staged)
-        scatter_rows_host(c->h_out, c->pend.dst, c->pend.width, c->pend.height, c->pend.n_rows, c->pend.row_block, c->pend.part_index, c->pend.part_count);
+        scatter_rows_host(c->scr.h_out.as<float>(), c->pend.dst, c->pend.width, c->pend.height, c->pend.n_rows, c->pend.row_block, c->pend.part_index, c->pend.part_count);
     float ms = 0.0f, start_ms = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     HIP_TRY(hipEventElapsedTime(&start_ms, c->ev_mark, c->ev0));
-    const unsigned long long *h_stats = c->h_stats;
+    const unsigned long long *h_stats = c->scr.h_stats.as<unsigned long long>();
     const bool kernel_gave_up = h_stats[23] != 0ull;           // safety valve of the persistent loop (rtw_kernels.hip RTW_MAX_TRIPS)
     if (stats) {
         std::memset(stats, 0, sizeof *stats);
