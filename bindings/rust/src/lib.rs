@@ -113,6 +113,12 @@ extern "C" {
     fn rtw_ctx_set_lights(ctx: *mut RtwCtx, lights: *const RtwLight, n: u32, biased_weight: f32) -> i32;
     fn rtw_mgpu_set_lights(m: *mut RtwMgpu, lights: *const RtwLight, n: u32, biased_weight: f32) -> i32;
     fn rtw_mgpu_set_triangles(m: *mut RtwMgpu, tris: *const RtwTriangle, n: u32) -> i32;
+    fn rtw_ctx_set_instance_rotations(ctx: *mut RtwCtx, quat: *const [f32; 4], n: u32) -> i32;
+    fn rtw_mgpu_set_instance_rotations(m: *mut RtwMgpu, quat: *const [f32; 4], n: u32) -> i32;
+    fn rtw_quat_rotate(q: *const f32, v: *const f32, out: *mut f32) -> i32;
+    fn rtw_quat_mul(a: *const f32, b: *const f32, out: *mut f32) -> i32;
+    fn rtw_quat_from_axis(angle: f32, axis: *const f32, out: *mut f32) -> i32;
+    fn rtw_quat_from_euler(euler: *const f32, out: *mut f32) -> i32;
     fn rtw_triangle_hits(tris: *const RtwTriangle, n: u32, rays: *const f32, n_rays: u32, mint: f32, maxt: f32,
                          t_out: *mut f32, idx_out: *mut i32) -> i32;
     fn rtw_ctx_triangle_hits(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, mint: f32, maxt: f32, accel: u32,
@@ -184,6 +190,13 @@ impl Renderer {
     pub fn set_lights(&mut self, lights: &[RtwLight], biased_weight: f32) -> Result<(), RtwError> {
         let p = if lights.is_empty() { std::ptr::null() } else { lights.as_ptr() };
         check(unsafe { rtw_ctx_set_lights(self.ctx, p, lights.len() as u32, biased_weight) })
+    }
+    /// Rust2's `Instance.rotation`, one quaternion [w, x, y, z] per instance of the scene (`Instance::getr()`; an empty slice clears them;
+    /// set_scene clears them): Integrator::Rust2 / LightCast / LightBiased and the scene queries then hit the instances as Rust2's
+    /// `Instance::get_hit` does.
+    pub fn set_instance_rotations(&mut self, quats: &[[f32; 4]]) -> Result<(), RtwError> {
+        let p = if quats.is_empty() { std::ptr::null() } else { quats.as_ptr() };
+        check(unsafe { rtw_ctx_set_instance_rotations(self.ctx, p, quats.len() as u32) })
     }
     /// The closest of this context's triangles per ray ([origin, direction]) on its GPU: (t, index or -1) per ray.
     pub fn triangle_hits(&mut self, rays: &[[f32; 6]], mint: f32, maxt: f32, accel: u32) -> Result<(Vec<f32>, Vec<i32>), RtwError> {
@@ -261,6 +274,11 @@ impl MultiRenderer {
     }
     pub fn set_scene(&mut self, sc: &RtwScene, t_begin: f32, t_end: f32) -> Result<(), RtwError> {
         check(unsafe { rtw_mgpu_set_scene(self.m, sc, t_begin, t_end) })
+    }
+    /// rtw_mgpu_set_instance_rotations: `Renderer::set_instance_rotations` on every device.
+    pub fn set_instance_rotations(&mut self, quats: &[[f32; 4]]) -> Result<(), RtwError> {
+        let p = if quats.is_empty() { std::ptr::null() } else { quats.as_ptr() };
+        check(unsafe { rtw_mgpu_set_instance_rotations(self.m, p, quats.len() as u32) })
     }
     pub fn render(&mut self, cam: &RtwCamera, p: &RtwParams) -> Result<(Vec<Vec<[f32; 3]>>, Vec<RtwStats>), RtwError> {
         let mut flat = vec![[0f32; 3]; (p.width as usize) * (p.height as usize)];
@@ -342,6 +360,31 @@ pub fn camera2_new(aspect: f32, origin: [f32; 3], vup: [f32; 3], dir: [f32; 3], 
     let mut cam = RtwCamera::default();
     check(unsafe { rtw_camera2_new(aspect, origin.as_ptr(), vup.as_ptr(), dir.as_ptr(), vfov, lens_radius, &mut cam) })?;
     Ok(cam)
+}
+
+/// Rust2's `Quaternion::rotate` ([w, x, y, z]; q need not be normalised), the definition the kernels compile (host only).
+pub fn quat_rotate(q: [f32; 4], v: [f32; 3]) -> [f32; 3] {
+    let mut out = [0f32; 3];
+    unsafe { rtw_quat_rotate(q.as_ptr(), v.as_ptr(), out.as_mut_ptr()) };
+    out
+}
+/// `a.hamilton(&b)`: `Instance::rotate(rot)` is `rotation = quat_mul(rotation, rot)`.
+pub fn quat_mul(a: [f32; 4], b: [f32; 4]) -> [f32; 4] {
+    let mut out = [0f32; 4];
+    unsafe { rtw_quat_mul(a.as_ptr(), b.as_ptr(), out.as_mut_ptr()) };
+    out
+}
+/// `Quaternion::new_from_axis(angle, axis)`.
+pub fn quat_from_axis(angle: f32, axis: [f32; 3]) -> [f32; 4] {
+    let mut out = [0f32; 4];
+    unsafe { rtw_quat_from_axis(angle, axis.as_ptr(), out.as_mut_ptr()) };
+    out
+}
+/// `Quaternion::from(&EulerAngles { x, y, z })`.
+pub fn quat_from_euler(euler: [f32; 3]) -> [f32; 4] {
+    let mut out = [0f32; 4];
+    unsafe { rtw_quat_from_euler(euler.as_ptr(), out.as_mut_ptr()) };
+    out
 }
 
 /// The rays of Rust2's `Viewport::depth_map` for a camera of `rtw_camera2_new` (host only): [origin, unit direction] per pixel, row-major.

@@ -565,6 +565,39 @@ int rtw_pow_plain(const float *x, const float *y, size_t n, float *out);
 int rtw_sin_plain(const float *phi, size_t n, float *out);
 int rtw_cos_plain(const float *phi, size_t n, float *out);
 
+/* ---- quaternion-rotated instances (Rust2/src/objects/instance.rs:21-47, 215-255, quaternions.rs, rotation.rs) -------------------------
+ * A Rust2 `Instance` carries a position and a QUATERNION rotation, where RtwInstance.rotation is Rust/'s Euler Vec3::rotated (another formula,
+ * other bits).  With rotations set, an instance is hit as Rust2's Instance::get_hit writes it: r.origin -= position; r = r.rotated(q) (origin
+ * and direction through Quaternion::rotate); the members are tested in that frame with the render's mint / maxt; the winner comes back as
+ * p = q.rotate(p) + position, n = q.rotate(n) -- the SAME q both ways, not its conjugate (the reference's image depends on it); t is untouched.
+ * The hit's ray (Rust2's Hit.r) is NOT turned back either: on_hit and material_pdf of a member read the direction in the instance's frame (the side
+ * test of material_pdf is d_local . n, a Mirror reflects d_local about the turned normal), as the reference does.
+ * Quaternion::rotate(v) = qn.hamilton((0, v)).hamilton(qn.conjugate()).get_vec(), qn = q * (1.0 / q.len()), len = sqrt(w*w + x*x + y*y + z*z);
+ * hamilton as written (four products per component, added left to right), in f32 without FMA; the library forms qn once per instance on the
+ * host with the same operations.  Members keep the library's order (the instance's spheres, then its quads).
+ * rtw_ctx_set_instance_rotations: quat[i] = {w, x, y, z} for RtwScene.instances[i] of the last rtw_ctx_set_scene (which clears them); n must
+ * equal the scene's instance count; quat == NULL with n == 0 clears them.  Every instance is then a quaternion instance -- (1, 0, 0, 0)
+ * included, with no special case -- and ignores RtwInstance.rotation, which must be 0 there.  RTW_E_NO_SCENE before any scene; RTW_E_INVALID for
+ * a count mismatch, a component that is not finite, a quaternion whose len is 0 or not finite, a non-zero Euler rotation or medium != 0 on an
+ * instance (constant density is Rust/'s; the reference defines no mix of the two), and while a render of the context is pending.
+ * Renders: RTW_INTEGRATOR_RUST2, _LIGHT_CAST and _LIGHT_BIASED, with or without RTW_FLAG_MIXED_MATERIAL, run the quaternion build of the render
+ * kernels (shadow rays cross the rotated instances like any other ray).  NOT BUILT, RTW_E_INVALID at the render: any other integrator, active
+ * texture noise, triangles in the context.  rtw_ctx_scene_hits / rtw_ctx_depth_map honour the rotations (the normal is q.rotate(n_local)).
+ * The one-shot rtw_render / rtw_render_multi_gpu carry no rotations. */
+int rtw_ctx_set_instance_rotations(rtw_ctx *ctx, const float (*quat)[4] /* w,x,y,z */, uint32_t n);
+int rtw_mgpu_set_instance_rotations(rtw_mgpu *m, const float (*quat)[4], uint32_t n);
+/* Host only (no context, no GPU): the argument checks of rtw_ctx_set_instance_rotations against `scene`: RTW_OK or RTW_E_INVALID. */
+int rtw_instance_rotations_validate(const RtwScene *scene, const float (*quat)[4], uint32_t n);
+/* Host only, pure, the same definitions the kernels compile (csrc/rtw_quat.h); quaternions are {w, x, y, z}.
+ * rtw_quat_rotate: Quaternion::rotate (q need not be normalised).  rtw_quat_mul: a.hamilton(b) -- what Instance::rotate applies,
+ * rotation = rotation.hamilton(rot).  rtw_quat_from_axis: Quaternion::new_from_axis(angle, axis): (cos(angle * 0.5), sin(angle * 0.5) *
+ * unit(axis)) with the platform's sinf / cosf, as rtw_vec3_rotated uses them.  rtw_quat_from_euler: From<&EulerAngles> for euler = {x, y, z}.
+ * RTW_E_INVALID for a NULL pointer. */
+int rtw_quat_rotate(const float q[4], const float v[3], float out[3]);
+int rtw_quat_mul(const float a[4], const float b[4], float out[4]);
+int rtw_quat_from_axis(float angle, const float axis[3], float out[4]);
+int rtw_quat_from_euler(const float euler[3], float out[4]);
+
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 
 /* Viewport::new (viewport.rs:308-401).  Options the reference takes as Option<> are pointers

@@ -253,6 +253,13 @@ def lib() -> C.CDLL:
     L.rtw_mixed_validate.argtypes = [C.POINTER(RtwScene), C.POINTER(RtwParams), C.c_uint32, C.c_uint32]
     L.rtw_mixed_dir.argtypes = [C.c_float, C.c_float, C.c_float, fp, fp]
     L.rtw_mixed_pdf.argtypes = [C.c_float, fp, fp, fp, fp, fp, fp]
+    L.rtw_ctx_set_instance_rotations.argtypes = [C.c_void_p, fp, C.c_uint32]
+    L.rtw_mgpu_set_instance_rotations.argtypes = [C.c_void_p, fp, C.c_uint32]
+    L.rtw_instance_rotations_validate.argtypes = [C.POINTER(RtwScene), fp, C.c_uint32]
+    L.rtw_quat_rotate.argtypes = [fp, fp, fp]
+    L.rtw_quat_mul.argtypes = [fp, fp, fp]
+    L.rtw_quat_from_axis.argtypes = [C.c_float, fp, fp]
+    L.rtw_quat_from_euler.argtypes = [fp, fp]
     L.rtw_pow_plain.argtypes = [fp, fp, C.c_size_t, fp]
     L.rtw_sin_plain.argtypes = [fp, C.c_size_t, fp]
     L.rtw_cos_plain.argtypes = [fp, C.c_size_t, fp]
@@ -438,6 +445,53 @@ def mixed_pdf(exp, p, n, dir_in, ray_o, ray_d) -> np.float32:
     out = C.c_float()
     _check(lib().rtw_mixed_pdf(float(exp), _f3(p), _f3(n), _f3(dir_in), _f3(ray_o), _f3(ray_d), C.byref(out)), "rtw_mixed_pdf")
     return np.float32(out.value)
+
+
+def _quat_array(quats):
+    """(float pointer or None, n, keep-alive array) of a sequence of (w, x, y, z) quaternions."""
+    if quats is None or len(quats) == 0:
+        return None, 0, None
+    arr = np.ascontiguousarray(quats, np.float32)
+    assert arr.ndim == 2 and arr.shape[1] == 4, "quaternions are [n][4] = w, x, y, z"
+    return arr.ctypes.data_as(C.POINTER(C.c_float)), len(arr), arr
+
+
+def _f4(q):
+    return (C.c_float * 4)(*[float(x) for x in q])
+
+
+def quat_rotate(q, v) -> np.ndarray:
+    """rtw_quat_rotate: Rust2's Quaternion::rotate of v by q = (w, x, y, z) (q need not be normalised)."""
+    out = (C.c_float * 3)()
+    _check(lib().rtw_quat_rotate(_f4(q), _f3(v), out), "rtw_quat_rotate")
+    return np.array(list(out), np.float32)
+
+
+def quat_mul(a, b) -> np.ndarray:
+    """rtw_quat_mul: a.hamilton(b) -- Instance::rotate(rot) is rotation = quat_mul(rotation, rot)."""
+    out = (C.c_float * 4)()
+    _check(lib().rtw_quat_mul(_f4(a), _f4(b), out), "rtw_quat_mul")
+    return np.array(list(out), np.float32)
+
+
+def quat_from_axis(angle: float, axis) -> np.ndarray:
+    """rtw_quat_from_axis: Quaternion::new_from_axis(angle, axis) as (w, x, y, z)."""
+    out = (C.c_float * 4)()
+    _check(lib().rtw_quat_from_axis(float(angle), _f3(axis), out), "rtw_quat_from_axis")
+    return np.array(list(out), np.float32)
+
+
+def quat_from_euler(euler) -> np.ndarray:
+    """rtw_quat_from_euler: Rust2's From<&EulerAngles> for Quaternion, euler = (x, y, z)."""
+    out = (C.c_float * 4)()
+    _check(lib().rtw_quat_from_euler(_f3(euler), out), "rtw_quat_from_euler")
+    return np.array(list(out), np.float32)
+
+
+def instance_rotations_validate(scene: "Scene", quats) -> int:
+    """rtw_instance_rotations_validate: the status rtw_ctx_set_instance_rotations answers for `quats` on `scene` (host only)."""
+    ptr, n, _keep = _quat_array(quats)
+    return int(lib().rtw_instance_rotations_validate(C.byref(scene.pod), ptr, n))
 
 
 def _plain1(fn, what, *arrays):
@@ -933,6 +987,12 @@ class Renderer:
         arr, n = _light_array(lights)
         _check(lib().rtw_ctx_set_lights(self._h, arr, n, float(biased_weight)), "rtw_ctx_set_lights")
 
+    def set_instance_rotations(self, quats=None):
+        """rtw_ctx_set_instance_rotations for the current scene: one (w, x, y, z) per instance (None: clear).  Rust2's quaternion rotation of an
+        Instance; renders under INTEGRATOR_RUST2 / _LIGHT_CAST / _LIGHT_BIASED and the scene queries honour it; a new scene clears it."""
+        ptr, n, _keep = _quat_array(quats)
+        _check(lib().rtw_ctx_set_instance_rotations(self._h, ptr, n), "rtw_ctx_set_instance_rotations")
+
     def triangle_hits(self, rays, mint: float, maxt: float, accel: int = ACCEL_BVH):
         """The closest of this context's triangles per ray on its GPU (rtw_ctx_triangle_hits): (t, index, RtwStats) as triangle_hits."""
         r = _rays(rays)
@@ -1081,6 +1141,11 @@ class MultiRenderer:
         """rtw_mgpu_set_lights on every device (None: clear them)."""
         arr, n = _light_array(lights)
         _check(lib().rtw_mgpu_set_lights(self._h, arr, n, float(biased_weight)), "rtw_mgpu_set_lights")
+
+    def set_instance_rotations(self, quats=None):
+        """rtw_mgpu_set_instance_rotations on every device (None: clear them)."""
+        ptr, n, _keep = _quat_array(quats)
+        _check(lib().rtw_mgpu_set_instance_rotations(self._h, ptr, n), "rtw_mgpu_set_instance_rotations")
 
     def set_option(self, key: int, value: float):
         _check(lib().rtw_mgpu_set_option(self._h, int(key), float(value)), "rtw_mgpu_set_option")

@@ -17,10 +17,12 @@
 //   Rust/src/objects/quad.rs:37-81         Quad::collision_normal
 //   Rust/src/objects/instance.rs:250-310   Instance::collision_normal (+ const_density :24-26)
 //   Rust/src/vec3.rs:161-181               Vec3::rotated
+//   Rust2/src/objects/instance.rs:215-255  Instance::get_hit with a quaternion rotation (rtw_quat.h; the quaternion build, SPEC 11)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rtw.h"
+#include "rtw_quat.h"
 
 namespace rtw {
 
@@ -728,6 +730,25 @@ __device__ __forceinline__ v3 rotated(v3 a, const float *q, const float *k) {
     return o;
 }
 
+// Rust2's Instance::get_hit (Rust2/src/objects/instance.rs:215-255) where the context holds instance rotations (rtw_ctx_set_instance_rotations):
+// the ray goes into the instance's frame as r.origin -= position; r = r.rotated(q), and the winner comes back as p = q.rotate(p) + position,
+// n = q.rotate(n) -- the SAME q both ways, as the reference has it.  `quats` holds one normalised row {w, x, y, z} per instance.
+// Row i for a wave-uniform i (the instance walk): a scalar load through the constant address space
+__device__ __forceinline__ quat inst_quat(const f4 *quats, uint32_t i) {
+    const f4 r = ((cf4_ptr)(uintptr_t)quats)[i];
+    return qmk(r.x, r.y, r.z, r.w);
+}
+// ... and for a per-lane i (the record of the instance a lane's ray hit)
+__device__ __forceinline__ quat inst_quat_lane(const f4 *quats, uint32_t i) {
+    const f4 r = quats[i];
+    return qmk(r.x, r.y, r.z, r.w);
+}
+__device__ __forceinline__ v3 quat_rot(quat qn, v3 a) {
+    v3 o;
+    quat_rotate_n(qn, a.x, a.y, a.z, o.x, o.y, o.z);
+    return o;
+}
+
 // ln(x), x a positive normal f32: f64 atanh series, rounded once.  The same operations as oracle/rtw_oracle.c
 // ln_f32 (f64 add/mul/div are IEEE on both sides, no contraction), correctly rounded for every xi = k 2^-24.
 __device__ __forceinline__ float ln_f32(float xf) {
@@ -986,10 +1007,13 @@ __device__ __forceinline__ void member_record(const DevScene &sc, const DevNoise
 
 // The part of Scene::collision_normal (viewport.rs:136-150) after the top-level spheres: quads, then instances.
 // `sphere_found` / `sphere_t` are the sphere result; returns true when a quad or an instance wins, h = its Hit.  NOISE: the noise build
-// (textures with noise; `nz` is read only then).
-template <bool NOISE = false>
+// (textures with noise; `nz` is read only then).  QUAT: the quaternion build (`quats`: one normalised row per instance; the Euler fields of
+// DevInstance are not read, and there are no media: rtw_ctx_set_instance_rotations refuses them).  *hit_dir (QUAT): when an instance wins, the
+// direction of the ray the member was hit with, in the instance's frame -- Rust2's Hit.r, which Instance::get_hit does not turn back.
+template <bool NOISE = false, bool QUAT = false>
 __device__ __forceinline__ bool geom_closest(const DevScene &sc, const DevNoise &nz, const DevGeom &g, v3 o, v3 d, float tm, float mint, float maxt,
-                                             bool sphere_found, float sphere_t, Rng &rng, GeomHit &h, uint32_t &n_sph, uint32_t &n_quad) {
+                                             bool sphere_found, float sphere_t, Rng &rng, GeomHit &h, uint32_t &n_sph, uint32_t &n_quad,
+                                             const f4 *quats = nullptr, v3 *hit_dir = nullptr) {
     bool found = sphere_found;
     float ht = sphere_t;
     int win = 0;                                               // 1: top-level quad qk, 2: instance ii
@@ -1009,11 +1033,13 @@ __device__ __forceinline__ bool geom_closest(const DevScene &sc, const DevNoise 
     for (uint32_t i = 0; i < g.n_inst; ++i) {                 // Instance::collision_normal (instance.rs:250-310)
         const DevInstance in = g.inst[i];
         const v3 tr = ld3(in.tr);
-        const v3 lo = rotated(o - tr, in.back, in.back_k), ld = rotated(d, in.back, in.back_k);
+        v3 lo, ld;
+        if constexpr (QUAT) { const quat qn = inst_quat(quats, i); lo = quat_rot(qn, o - tr); ld = quat_rot(qn, d); }
+        else { lo = rotated(o - tr, in.back, in.back_k); ld = rotated(d, in.back, in.back_k); }
         float ct; int code;
         if (!instance_pick(g, in, lo, ld, tm, mint, maxt, ct, code, n_sph, n_quad)) continue;
         bool med = false; v3 mp = mk(0, 0, 0), mn = mk(0, 0, 0);
-        if (in.medium == RTW_MEDIUM_CONST_DENSITY) {           // const_density (:24-26)
+        if (!QUAT && in.medium == RTW_MEDIUM_CONST_DENSITY) {  // const_density (:24-26)
             const float distance = ln_f32(rng_f32(rng)) / -in.density;
             if (distance >= 0.0f) {
                 const v3 o2 = (lo + ld * ct) + ld * distance;
@@ -1030,11 +1056,20 @@ __device__ __forceinline__ bool geom_closest(const DevScene &sc, const DevNoise 
     } else if (win == 2) {
         const DevInstance &in = g.inst[ii];
         const v3 tr = ld3(in.tr);
-        const v3 lo = rotated(o - tr, in.back, in.back_k), ld = rotated(d, in.back, in.back_k);
-        member_record<NOISE>(sc, nz, g, icode, lo, ld, tm, it, h);      // (the medium moves the point only after col_mod is fixed: instance.rs:281-305)
-        if (imed) { h.point = imp; h.normal = imn; }
-        h.point = rotated(h.point, in.fwd, in.fwd_k) + tr;
-        h.normal = rotated(h.normal, in.fwd, in.fwd_k);
+        if constexpr (QUAT) {
+            const quat qn = inst_quat_lane(quats, ii);
+            const v3 ld = quat_rot(qn, d);
+            member_record<NOISE>(sc, nz, g, icode, quat_rot(qn, o - tr), ld, tm, it, h);
+            if (hit_dir) *hit_dir = ld;
+            h.point = quat_rot(qn, h.point) + tr;
+            h.normal = quat_rot(qn, h.normal);
+        } else {
+            const v3 lo = rotated(o - tr, in.back, in.back_k), ld = rotated(d, in.back, in.back_k);
+            member_record<NOISE>(sc, nz, g, icode, lo, ld, tm, it, h);  // (the medium moves the point only after col_mod is fixed: instance.rs:281-305)
+            if (imed) { h.point = imp; h.normal = imn; }
+            h.point = rotated(h.point, in.fwd, in.fwd_k) + tr;
+            h.normal = rotated(h.normal, in.fwd, in.fwd_k);
+        }
     }
     return win != 0;
 }

@@ -83,6 +83,8 @@ struct KArgs {
                                   // tris.nodes == null: walk the triangle list
     DevLights lights;             // the light list (rtw_ctx_set_lights); read by the light build (SPEC 9) alone, which RTW_INTEGRATOR_LIGHT_CAST /
                                   // _LIGHT_BIASED select
+    const f4 *inst_quats;         // Rust2's instance rotations (rtw_ctx_set_instance_rotations): one normalised {w, x, y, z} per instance; non-null selects
+                                  // the quaternion build (SPEC 11), which alone reads it (and the lights, for every integrator it serves)
 };
 
 // accel: RTW_ACCEL_BRUTE, RTW_ACCEL_BVH; the BVH launch picks the LDS-resident variant when a.bvh.nodes16 != null
@@ -99,6 +101,7 @@ struct QueryArgs {
     DevBvh   bvh;
     DevGeom  geom;
     DevTris  tris;                // tris.n == 0: none; tris.nodes == null: walk the triangle list
+    const f4 *inst_quats;         // Rust2's instance rotations, one normalised {w, x, y, z} per instance, or null: the Euler rotation of DevInstance
     RtwCamera cam;                // from_camera: Rust2's camera (rtw_camera2_new), pixel i = (i % width, i / width)
     uint32_t width, height;
     const float *rays;            // else: [n][6] = o, d (device)

@@ -56,11 +56,15 @@ namespace rtw {
 // (rtw_light.h, rtw_ctx_set_lights) as its step: only RTW_INTEGRATOR_LIGHT_CAST / _LIGHT_BIASED select it, and it runs no other integrator.
 // SPEC == 10 is SPEC == 9 with Rust2's MixedMaterial (rtw_mixed.h) in the material step: an object with opacity < 0 scatters into a Phong lobe.
 // Only RTW_FLAG_MIXED_MATERIAL on a scene that holds such an object selects it; it also runs RTW_INTEGRATOR_RUST2, as LIGHT_BIASED with an
-// empty light list (that path is RUST2's bit for bit).
+// empty light list (that path is RUST2's bit for bit).  SPEC == 11 is SPEC == 10's step with Rust2's quaternion transform
+// (rtw_quat.h) in every instance walk -- the path's closest hit and the shadow queries; only a context that holds instance rotations
+// (rtw_ctx_set_instance_rotations) selects it, for RUST2 / LIGHT_CAST / LIGHT_BIASED.  It serves renders with and without
+// RTW_FLAG_MIXED_MATERIAL, so it asks the flag at run time where SPEC == 10 knows it is set.  GEOM variants only: rotations imply instances.
 constexpr bool gradient_spec(int spec) { return spec >= 1 && spec <= 3; }
-constexpr bool generic_spec(int spec) { return spec == 0 || spec == 7 || spec == 8 || spec == 9 || spec == 10; }
-constexpr bool light_spec(int spec) { return spec == 9 || spec == 10; }
-constexpr bool mixed_spec(int spec) { return spec == 10; }
+constexpr bool generic_spec(int spec) { return spec == 0 || spec == 7 || spec == 8 || spec == 9 || spec == 10 || spec == 11; }
+constexpr bool light_spec(int spec) { return spec == 9 || spec == 10 || spec == 11; }
+constexpr int mixed_spec(int spec) { return spec == 10 ? 1 : spec == 11 ? 2 : 0; }     // 1: the flag is known to be set; 2: KArgs.flags says
+constexpr bool quat_spec(int spec) { return spec == 11; }
 constexpr bool noise_spec(int spec) { return spec == 7; }
 constexpr bool tri_spec(int spec) { return spec == 8; }
 template <int SPEC> __device__ __forceinline__ uint32_t integ(const KArgs &A) {
@@ -430,13 +434,18 @@ __device__ __forceinline__ void closest_brute(const DevScene &sc, v3 o, v3 d, fl
 // runs the queries in a loop (a straight second list walk per light), render_bvh hands them to its scheduler one at a time.
 
 // The `Hit` of the path's closest-hit query and ColorResult of its object, as RTW_INTEGRATOR_RUST2 forms them (shade_geom / shade_hit).
-// False on a miss.
-template <bool MOVING, bool GEOM>
+// False on a miss.  din: Hit.r.direction, what the material reads as the incoming direction -- the path's, except for a member of a
+// quaternion instance (QUAT), where Rust2's Hit keeps the ray in the instance's frame (Instance::get_hit turns p and n back, not r).
+template <bool MOVING, bool GEOM, bool QUAT>
 __device__ __forceinline__ bool light_path_hit(const KArgs &A, Path &pt, int best, float best_t, v3 &point, v3 &normal, v3 &cm, MatP &m, v3 &emitted,
-                                               uint32_t &n_sph, uint32_t &n_quad) {
+                                               v3 &din, uint32_t &n_sph, uint32_t &n_quad) {
+    din = pt.d;
     if constexpr (GEOM) {
         GeomHit h;
-        if (geom_closest<false>(A.sc, A.noise, A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, pt.rng, h, n_sph, n_quad)) {
+        bool won;
+        if constexpr (QUAT) won = geom_closest<false, true>(A.sc, A.noise, A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, pt.rng, h, n_sph, n_quad, A.inst_quats, &din);
+        else won = geom_closest<false>(A.sc, A.noise, A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, pt.rng, h, n_sph, n_quad);
+        if (won) {
             mat_derive(h.m);
             point = h.point; normal = h.normal; cm = h.cm; m = h.m; emitted = h.emitted;
             return true;
@@ -461,25 +470,31 @@ __device__ __forceinline__ bool light_path_hit(const KArgs &A, Path &pt, int bes
 // ray_color.rs:124; light_biased_ray_cast draws nothing), move the path's origin to the hit point.
 // MIXED (SPEC 10): every integrator but LIGHT_CAST walks on (RTW_INTEGRATOR_RUST2 is LIGHT_BIASED without lights), and a surface with
 // opacity < 0 is MixedMaterial::new(ir): two draws, phi then cos theta, and the lobe about the hit's normal as reported (rtw_mixed.h).
-template <bool MIXED>
+template <int MIXED>
 __device__ __forceinline__ bool light_walks_on(const KArgs &A) {
     return MIXED ? A.integrator != RTW_INTEGRATOR_LIGHT_CAST : A.integrator == RTW_INTEGRATOR_LIGHT_BIASED;
 }
-template <bool MIXED>
-__device__ __forceinline__ void light_surface(const KArgs &A, Path &pt, v3 point, v3 normal, v3 cm, const MatP m, v3 emitted, LightPath &lp) {
+// Is a surface with this opacity a MixedMaterial?  (MIXED == 2, SPEC 11: only when the render carries the flag)
+template <int MIXED>
+__device__ __forceinline__ bool mixed_surface(const KArgs &A, float opacity) {
+    if (MIXED == 2) return (A.flags & RTW_FLAG_MIXED_MATERIAL) != 0u && opacity < 0.0f;
+    return MIXED && opacity < 0.0f;
+}
+template <int MIXED>
+__device__ __forceinline__ void light_surface(const KArgs &A, Path &pt, v3 point, v3 normal, v3 cm, const MatP m, v3 emitted, v3 din, LightPath &lp) {
     const bool biased = light_walks_on<MIXED>(A);
-    lp.n = normal; lp.din = pt.d; lp.tm = pt.tm;
+    lp.n = normal; lp.din = din; lp.tm = pt.tm;
     lp.metallicness = m.metallicness; lp.opacity = m.opacity; lp.ir = m.ir;
     lp.cm = cm; lp.e = emitted;
     lp.S = mk(0, 0, 0); lp.count = biased ? 1.0f : 0.0f;
     v3 scat = mk(0, 0, 0);
     if (biased) {
-        if (MIXED && m.opacity < 0.0f) {
+        if (mixed_surface<MIXED>(A, m.opacity)) {
             const float xi_phi = rng_f32(pt.rng), xi_cos = rng_f32(pt.rng);
             const lv3 dir = mixed_dir(m.ir, xi_phi, xi_cos, tol(normal));
             scat = mk(dir.x, dir.y, dir.z);
         } else {
-            scat = on_hit_rust2(m, normal, pt.d, pt.rng, A.flags);
+            scat = on_hit_rust2(m, normal, din, pt.rng, A.flags);
         }
     }
     lp.scat = scat;
@@ -497,13 +512,15 @@ __device__ __forceinline__ void light_ray(uint32_t i, Path &pt) {
 
 // The shadow query of light i is complete: (best, best_t) its sphere part.  Finishes Scene::collision_normal for it (GEOM) and, when the
 // closest object IS the light, adds the light's term.
-template <bool MOVING, bool GEOM, bool MIXED>
+template <bool MOVING, bool GEOM, int MIXED, bool QUAT>
 __device__ __forceinline__ void light_result(const KArgs &A, uint32_t i, const Path &pt, int best, float best_t, LightPath &lp, uint32_t &n_sph, uint32_t &n_quad) {
     uint32_t code = best >= 0 ? (uint32_t)best : LIGHT_HIT_NONE;
     float t = best_t;
     if constexpr (GEOM) {
         float tg;
-        const uint32_t cg = shadow_geom_pick(A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, tg, n_sph, n_quad);
+        uint32_t cg;
+        if constexpr (QUAT) cg = shadow_geom_pick<true>(A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, tg, n_sph, n_quad, A.inst_quats);
+        else cg = shadow_geom_pick(A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, tg, n_sph, n_quad);
         if (cg != LIGHT_HIT_NONE) { code = cg; t = tg; }
     }
     const f4 row = light_row((uint32_t)offsetof(KArgs, lights), i);
@@ -524,7 +541,7 @@ __device__ __forceinline__ void light_result(const KArgs &A, uint32_t i, const P
         }
     }
     float pdf;
-    if (MIXED && lp.opacity < 0.0f) pdf = mixed_pdf(lp.ir, tol(pt.o), tol(lp.n), tol(lp.din), tol(pt.o), tol(pt.d));
+    if (mixed_surface<MIXED>(A, lp.opacity)) pdf = mixed_pdf(lp.ir, tol(pt.o), tol(lp.n), tol(lp.din), tol(pt.o), tol(pt.d));
     else pdf = light_material_pdf(lp.metallicness, lp.opacity, lp.ir, tol(pt.o), tol(lp.n), tol(lp.din), lp.tm, tol(pt.o), tol(pt.d), pt.tm);
     lv3 S = tol(lp.S);
     light_add(light_walks_on<MIXED>(A), pdf, tol(e), t, tol(pt.d), A.lights.weight, S, lp.count);
@@ -535,7 +552,7 @@ __device__ __forceinline__ void light_result(const KArgs &A, uint32_t i, const P
 //   LIGHT_BIASED  L += thr (.) ((S (.) m) / count + e),  thr = thr (.) (m / count), the scattered ray goes on (depth as RTW_INTEGRATOR_RUST2)
 //   LIGHT_CAST    L = (S (.) m) / count + e  (e alone when count == 0); the path ends
 // Returns true when the path is finished.
-template <bool MIXED>
+template <int MIXED>
 __device__ __forceinline__ bool light_finish(const KArgs &A, Path &pt, const LightPath &lp) {
     if (!light_walks_on<MIXED>(A)) {
         v3 c = mk(0, 0, 0);
@@ -546,52 +563,52 @@ __device__ __forceinline__ bool light_finish(const KArgs &A, Path &pt, const Lig
     pt.L = pt.L + pt.thr * ((lp.S * lp.cm) / lp.count + lp.e);
     pt.thr = pt.thr * (lp.cm / lp.count);
     pt.d = lp.scat; pt.tm = lp.tm;
-    if (MIXED && lp.opacity < 0.0f) pt.tm = 0.0f;             // MixedMaterial::on_hit builds its ray with Ray::new: time 0, not h.r.time
+    if (mixed_surface<MIXED>(A, lp.opacity)) pt.tm = 0.0f;             // MixedMaterial::on_hit builds its ray with Ray::new: time 0, not h.r.time
     pt.k++;
     if (pt.k >= A.depth) { pt.L = pt.L + ld3(A.bg) * pt.thr; return true; }
     return false;
 }
 
 // render_brute: the whole step for a lane whose path query returned (best, best_t) -- the shadow queries are list walks of their own.
-template <bool MOVING, bool GEOM, bool MIXED>
+template <bool MOVING, bool GEOM, int MIXED, bool QUAT>
 __device__ __forceinline__ bool light_step_brute(const KArgs &A, Path &pt, int best, float best_t, uint32_t &n_seg, uint32_t &n_sph, uint32_t &n_quad) {
-    v3 point, normal, cm, emitted; MatP m;
-    if (!light_path_hit<MOVING, GEOM>(A, pt, best, best_t, point, normal, cm, m, emitted, n_sph, n_quad)) {
+    v3 point, normal, cm, emitted, din; MatP m;
+    if (!light_path_hit<MOVING, GEOM, QUAT>(A, pt, best, best_t, point, normal, cm, m, emitted, din, n_sph, n_quad)) {
         pt.L = pt.L + ld3(A.bg) * pt.thr;
         return true;
     }
     LightPath lp;
-    light_surface<MIXED>(A, pt, point, normal, cm, m, emitted, lp);
+    light_surface<MIXED>(A, pt, point, normal, cm, m, emitted, din, lp);
     const uint32_t n = A.lights.n;
     for (uint32_t i = 0; i < n; ++i) {
         light_ray(i, pt);
         int sb; float st;
         closest_brute<MOVING>(A.sc, pt.o, pt.d, pt.tm, A.mint, A.maxt, sb, st);
         n_seg++;
-        light_result<MOVING, GEOM, MIXED>(A, i, pt, sb, st, lp, n_sph, n_quad);
+        light_result<MOVING, GEOM, MIXED, QUAT>(A, i, pt, sb, st, lp, n_sph, n_quad);
     }
     return light_finish<MIXED>(A, pt, lp);
 }
 
 // render_bvh: one SHADE step of a lane whose query is complete.  `fl` carries LF_SHADOW (the query was a shadow query) and the pending
 // light (rtw_light.h); the caller starts the next query -- shadow or path -- from pt.o / pt.d / pt.tm like any other.
-template <bool MOVING, bool GEOM, bool MIXED>
+template <bool MOVING, bool GEOM, int MIXED, bool QUAT>
 __device__ __forceinline__ bool light_step_bvh(const KArgs &A, Path &pt, LightPath &lp, uint32_t &fl, int best, float best_t, uint32_t &n_sph, uint32_t &n_quad) {
     const uint32_t n = A.lights.n;
     if (!(fl & LF_SHADOW)) {                               // path result
-        v3 point, normal, cm, emitted; MatP m;
-        if (!light_path_hit<MOVING, GEOM>(A, pt, best, best_t, point, normal, cm, m, emitted, n_sph, n_quad)) {
+        v3 point, normal, cm, emitted, din; MatP m;
+        if (!light_path_hit<MOVING, GEOM, QUAT>(A, pt, best, best_t, point, normal, cm, m, emitted, din, n_sph, n_quad)) {
             pt.L = pt.L + ld3(A.bg) * pt.thr;
             return true;
         }
-        light_surface<MIXED>(A, pt, point, normal, cm, m, emitted, lp);
+        light_surface<MIXED>(A, pt, point, normal, cm, m, emitted, din, lp);
         if (n == 0u) return light_finish<MIXED>(A, pt, lp);
         fl |= LF_SHADOW;                                      // (light 0: the pending-light bits are clear)
         light_ray(0u, pt);
         return false;
     }
     uint32_t i = (fl & LF_LIGHT_MASK) >> LF_LIGHT_SHIFT;                           // shadow result: one compare, the pdf, a few dozen VALU
-    light_result<MOVING, GEOM, MIXED>(A, i, pt, best, best_t, lp, n_sph, n_quad);
+    light_result<MOVING, GEOM, MIXED, QUAT>(A, i, pt, best, best_t, lp, n_sph, n_quad);
     i++;
     if (i < n) { fl += 1u << LF_LIGHT_SHIFT; light_ray(i, pt); return false; }
     fl &= ~(LF_SHADOW | LF_LIGHT_MASK);
@@ -762,7 +779,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? RTW_GEOM_BRUTE_WAVES : 1) void re
                 int best; float best_t;
                 closest_brute<MOVING>(A.sc, pt.o, pt.d, pt.tm, A.mint, A.maxt, best, best_t);
                 n_seg++;
-                if constexpr (light_spec(SPEC)) finished = light_step_brute<MOVING, GEOM, mixed_spec(SPEC)>(A, pt, best, best_t, n_seg, n_isph, n_quad);
+                if constexpr (light_spec(SPEC)) finished = light_step_brute<MOVING, GEOM, mixed_spec(SPEC), quat_spec(SPEC)>(A, pt, best, best_t, n_seg, n_isph, n_quad);
                 else finished = GEOM ? shade_geom<MOVING, SPEC>(A, pt, best, best_t, n_isph, n_quad) : shade<MOVING, SPEC>(A, pt, best, best_t);
             }
             if (finished) {
@@ -1300,7 +1317,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
                     fl &= ~F_INFLIGHT;
                     bool done;
                     // (the light build: a path result or a shadow result; the lane's next query, shadow or path, starts below like any other)
-                    if constexpr (light_spec(SPEC)) done = light_step_bvh<MOVING, GEOM, mixed_spec(SPEC)>(A, pt, lp, fl, tr.best, tr.best_t, n_isph, n_quad);
+                    if constexpr (light_spec(SPEC)) done = light_step_bvh<MOVING, GEOM, mixed_spec(SPEC), quat_spec(SPEC)>(A, pt, lp, fl, tr.best, tr.best_t, n_isph, n_quad);
                     else done = GEOM ? shade_geom<MOVING, SPEC>(A, pt, tr.best, tr.best_t, n_isph, n_quad) : shade<MOVING, SPEC>(A, pt, tr.best, tr.best_t, cn);
                     if (done) fl |= F_DONE;
                 }
@@ -1505,6 +1522,9 @@ static kernel_fn pick_kernel_geom(bool moving, uint32_t accel, int nodes) {
 }
 static kernel_fn pick_kernel(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
     const int nodes = lds_nodes ? (a.lds_geom_off ? 2 : 1) : 0;
+    // instance rotations (rtw_shim.hip sets inst_quats only then, for a scene with instances under RUST2 / LIGHT_CAST / LIGHT_BIASED): the
+    // quaternion build, for every sampler and flag, with or without RTW_FLAG_MIXED_MATERIAL
+    if (a.inst_quats) return pick_kernel_geom<11>(moving, accel, nodes);
     // RTW_FLAG_MIXED_MATERIAL on a scene with a MixedMaterial object (rtw_shim.hip clears the bit otherwise, and refuses the flag under any
     // integrator but RUST2 / LIGHT_CAST / LIGHT_BIASED): the mixed build, for every sampler and flag
     if (a.flags & RTW_FLAG_MIXED_MATERIAL)

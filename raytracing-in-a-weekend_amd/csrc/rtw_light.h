@@ -2,7 +2,7 @@
 // (Rust2/src/objects/material.rs:45-62, 93-99, 199-232).  The pure pieces are __host__ __device__, one definition for the light build of the
 // render kernels (SPEC 9) and for the host entry points rtw_light_mid / rtw_material_pdf / rtw_light_term (rtw_shim.hip) that the CPU tests
 // call.  f32, one rounding per written operation, no FMA (-ffp-contract=off), the reference's operation order (DESIGN.md "Light-biased
-// integrators").  Only SPEC 9 compiles the device part.
+// integrators").  Only the light builds (SPEC 9, 10, 11) compile the device part.
 #pragma once
 #include "rtw_device.h"
 
@@ -157,9 +157,10 @@ __device__ __forceinline__ f4 light_row(uint32_t off, uint32_t i) {
 
 // The closest-hit walk over quads and instances for a shadow ray: which object wins, no record.  Returns the object code when a quad or an
 // instance beats the sphere result (t_out = its t), LIGHT_HIT_NONE otherwise.  As geom_closest without media (the light integrators refuse
-// scenes with a constant-density instance).
+// scenes with a constant-density instance).  QUAT: the quaternion build (SPEC 11), the ray enters an instance as in geom_closest<.., true>.
+template <bool QUAT = false>
 __device__ __forceinline__ uint32_t shadow_geom_pick(const DevGeom &g, v3 o, v3 d, float tm, float mint, float maxt, bool sphere_found, float sphere_t,
-                                                     float &t_out, uint32_t &n_sph, uint32_t &n_quad) {
+                                                     float &t_out, uint32_t &n_sph, uint32_t &n_quad, const f4 *quats = nullptr) {
     bool found = sphere_found;
     float ht = sphere_t;
     uint32_t code = LIGHT_HIT_NONE;
@@ -176,7 +177,9 @@ __device__ __forceinline__ uint32_t shadow_geom_pick(const DevGeom &g, v3 o, v3 
     for (uint32_t i = 0; i < g.n_inst; ++i) {
         const DevInstance in = g.inst[i];
         const v3 tr = ld3(in.tr);
-        const v3 lo = rotated(o - tr, in.back, in.back_k), ld = rotated(d, in.back, in.back_k);
+        v3 lo, ld;
+        if constexpr (QUAT) { const quat qn = inst_quat(quats, i); lo = quat_rot(qn, o - tr); ld = quat_rot(qn, d); }
+        else { lo = rotated(o - tr, in.back, in.back_k); ld = rotated(d, in.back, in.back_k); }
         float ct; int c;
         if (!instance_pick(g, in, lo, ld, tm, mint, maxt, ct, c, n_sph, n_quad)) continue;
         if (!ifound || it > ct) { it = ct; ifound = true; }

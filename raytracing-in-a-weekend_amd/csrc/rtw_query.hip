@@ -251,7 +251,9 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
             const DevInstance in = g.inst[k];
             if (in.medium == RTW_MEDIUM_CONST_DENSITY) continue;
             const v3 tr = ld3(in.tr);
-            const v3 lo = rotated(o - tr, in.back, in.back_k), ld = rotated(d, in.back, in.back_k);
+            v3 lo, ld;
+            if (A.inst_quats) { const quat qn = inst_quat(A.inst_quats, k); lo = quat_rot(qn, o - tr); ld = quat_rot(qn, d); }   // (a wave-uniform branch)
+            else { lo = rotated(o - tr, in.back, in.back_k); ld = rotated(d, in.back, in.back_k); }
             float ct; int code;
             if (!instance_pick(g, in, lo, ld, tm, mint, maxt, ct, code, n_sph, n_quad)) continue;
             if (!ifound || it > ct) { it = ct; ii = k; icode = code; ifound = true; }
@@ -280,14 +282,17 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
                 } else if (win == 2) {                             // the member's normal in the instance's frame, rotated forward (instance.rs:304)
                     const DevInstance &in = g.inst[ii];
                     const v3 tr = ld3(in.tr);
-                    const v3 lo = rotated(o - tr, in.back, in.back_k), ld = rotated(d, in.back, in.back_k);
+                    const bool rq = A.inst_quats != nullptr;
+                    quat qn = qmk(1.0f, 0.0f, 0.0f, 0.0f);
+                    if (rq) qn = inst_quat_lane(A.inst_quats, ii);
+                    const v3 lo = rq ? quat_rot(qn, o - tr) : rotated(o - tr, in.back, in.back_k), ld = rq ? quat_rot(qn, d) : rotated(d, in.back, in.back_k);
                     v3 ln;
                     if (icode >= 0) {
                         const f4 gg = g.igeom[icode], vv = g.ivel[icode];
                         const v3 c = mk(gg.x, gg.y, gg.z) + mk(vv.x, vv.y, vv.z) * tm;
                         ln = unit((lo + ld * ht) - c);
                     } else ln = ld3(g.iquads[(uint32_t)~icode].normal);
-                    nrm = rotated(ln, in.fwd, in.fwd_k);
+                    nrm = rq ? quat_rot(qn, ln) : rotated(ln, in.fwd, in.fwd_k);      // Rust2: q.rotate(n), the same q as on the way in
                 } else {
                     nrm = ld3(A.tris.list[tk].normal);
                 }

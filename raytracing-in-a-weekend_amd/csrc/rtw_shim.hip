@@ -38,6 +38,7 @@ struct SceneMem {
 };
 struct NoiseMem { DevMem perlin, tex_noise; };
 struct TriMem { DevMem list, leaf, nodes; };
+struct QuatMem { DevMem rows; };
 struct ScratchMem {
     DevMem queue, stats;
     PinnedMem h_stats;                   // pinned: the counter read-back is a true async copy
@@ -83,6 +84,10 @@ struct rtw_ctx {
     std::vector<RtwSphere> h_spheres;    // host copies of the top-level spheres and quads: a light's mid-point is formed from them
     std::vector<RtwQuad> h_quads;
     bool has_medium = false;             // an instance of the scene is a constant-density medium (the light integrators refuse it)
+    // Rust2's instance rotations (rtw_ctx_set_instance_rotations; cleared by rtw_ctx_set_scene): one normalised quaternion per instance
+    std::vector<RtwInstance> h_instances;   // host copy of the instances: the checks of the setter read them
+    const f4 *inst_quats = nullptr;      // non-null: renders take the quaternion build (SPEC 11), the queries rotate by them
+    QuatMem quat_mem;
     // MixedMaterial (RTW_FLAG_MIXED_MATERIAL): does the scene hold an object with opacity < 0, and is the exponent (ir) of every such object
     // finite and >= 0?  Computed once by rtw_ctx_set_scene.
     bool has_mixed = false, mixed_bad = false;
@@ -263,10 +268,17 @@ static void free_tris(rtw_ctx *c) {
     c->tri_tree = false;
 }
 
+static void free_quats(rtw_ctx *c) {
+    c->quat_mem = QuatMem{};
+    c->inst_quats = nullptr;
+}
+
 static void free_scene(rtw_ctx *c) {
     c->scene_mem = SceneMem{};
     free_noise(c);
     free_tris(c);
+    free_quats(c);
+    c->h_instances.clear();
     c->lights = DevLights{};
     c->h_spheres.clear(); c->h_quads.clear(); c->has_medium = false;
     c->has_mixed = c->mixed_bad = false;
@@ -496,6 +508,7 @@ int rtw_ctx_set_scene(rtw_ctx *c, const RtwScene *s, float t_begin, float t_end)
     for (uint32_t i = 0; i < s->n_inst_quads; i++) if (s->inst_quads[i].tex >= 0) c->tex_used[s->inst_quads[i].tex] = 1;
     c->h_spheres.assign(s->spheres, s->spheres + s->n_spheres);
     c->h_quads.assign(s->quads, s->quads + s->n_quads);
+    c->h_instances.assign(s->instances, s->instances + s->n_instances);
     for (uint32_t i = 0; i < s->n_instances; i++) if (s->instances[i].medium == RTW_MEDIUM_CONST_DENSITY) c->has_medium = true;
     scene_mixed(s, c->has_mixed, c->mixed_bad);
     c->has_scene = true;
@@ -572,6 +585,86 @@ int rtw_ctx_set_lights(rtw_ctx *c, const RtwLight *lights, uint32_t n, float bia
     if (rc != RTW_OK) return rc;
     d.n = n; d.weight = biased_weight;
     c->lights = d;
+    return RTW_OK;
+}
+
+// ---- Rust2's instance rotations (rtw.h "quaternion-rotated instances") ------------------------------------------------------------------
+// The checks of a rotation list against a scene's instances, and the rows the kernels read (the normalised quaternions, formed with the
+// operations of Quaternion::rotate): shared by rtw_instance_rotations_validate (host only) and rtw_ctx_set_instance_rotations.  rows may be null.
+static int quats_check(const RtwInstance *inst, uint32_t n_inst, const float (*qs)[4], uint32_t n, f4 *rows) {
+    if (!qs || n != n_inst || (n && !inst)) return RTW_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        const quat q = qmk(qs[i][0], qs[i][1], qs[i][2], qs[i][3]);
+        if (!std::isfinite(q.w) || !std::isfinite(q.x) || !std::isfinite(q.y) || !std::isfinite(q.z)) return RTW_E_INVALID;
+        const float l = quat_len(q);
+        if (!(l > 0.0f) || !std::isfinite(l)) return RTW_E_INVALID;
+        if (inst[i].rotation[0] != 0.0f || inst[i].rotation[1] != 0.0f || inst[i].rotation[2] != 0.0f) return RTW_E_INVALID;   // one rotation per instance
+        if (inst[i].medium != RTW_MEDIUM_SURFACE) return RTW_E_INVALID;       // constant density is Rust/'s: the reference defines no mix of the two
+        const quat qn = quat_normalised(q);
+        if (rows) { f4 r; r.x = qn.w; r.y = qn.x; r.z = qn.y; r.w = qn.z; rows[i] = r; }
+    }
+    return RTW_OK;
+}
+
+int rtw_instance_rotations_validate(const RtwScene *scene, const float (*qs)[4], uint32_t n) {
+    if (!scene) return RTW_E_INVALID;
+    if (!qs && n == 0) return RTW_OK;
+    return quats_check(scene->instances, scene->n_instances, qs, n, nullptr);
+}
+
+int rtw_ctx_set_instance_rotations(rtw_ctx *c, const float (*qs)[4], uint32_t n) {
+    if (!c) return RTW_E_INVALID;
+    if (!c->has_scene) return RTW_E_NO_SCENE;
+    if (c->pend.active) return RTW_E_INVALID;
+    std::vector<f4> rows;
+    if (qs || n) {
+        if (!qs || n != c->h_instances.size()) return RTW_E_INVALID;            // (before anything is sized by the caller's n)
+        try { rows.resize(n); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+        const int rc = quats_check(c->h_instances.data(), (uint32_t)c->h_instances.size(), qs, n, rows.data());
+        if (rc != RTW_OK) return rc;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    free_quats(c);
+    if (!n) return RTW_OK;                                         // NULL / 0, or a scene without instances: nothing to rotate
+    QuatMem m;
+    if (const int rc = upload(m.rows, rows)) return rc;
+    c->inst_quats = m.rows.as<f4>();
+    c->quat_mem = std::move(m);
+    return RTW_OK;
+}
+
+// What a render answers while instance rotations are set: the quaternion build serves Rust2's three integrators, and nothing is built for
+// texture noise or triangles next to it.
+static int quats_render_check(bool rotations, uint32_t integrator, bool noise, bool tris) {
+    if (!rotations) return RTW_OK;
+    if (integrator != RTW_INTEGRATOR_RUST2 && integrator != RTW_INTEGRATOR_LIGHT_CAST && integrator != RTW_INTEGRATOR_LIGHT_BIASED) return RTW_E_INVALID;
+    if (noise || tris) return RTW_E_INVALID;
+    return RTW_OK;
+}
+
+int rtw_quat_rotate(const float q[4], const float v[3], float out[3]) {
+    if (!q || !v || !out) return RTW_E_INVALID;
+    float x, y, z;
+    quat_rotate(qmk(q[0], q[1], q[2], q[3]), v[0], v[1], v[2], x, y, z);
+    out[0] = x; out[1] = y; out[2] = z;
+    return RTW_OK;
+}
+int rtw_quat_mul(const float a[4], const float b[4], float out[4]) {
+    if (!a || !b || !out) return RTW_E_INVALID;
+    const quat r = quat_hamilton(qmk(a[0], a[1], a[2], a[3]), qmk(b[0], b[1], b[2], b[3]));
+    out[0] = r.w; out[1] = r.x; out[2] = r.y; out[3] = r.z;
+    return RTW_OK;
+}
+int rtw_quat_from_axis(float angle, const float axis[3], float out[4]) {
+    if (!axis || !out) return RTW_E_INVALID;
+    const quat r = quat_from_axis(angle, axis[0], axis[1], axis[2]);
+    out[0] = r.w; out[1] = r.x; out[2] = r.y; out[3] = r.z;
+    return RTW_OK;
+}
+int rtw_quat_from_euler(const float euler[3], float out[4]) {
+    if (!euler || !out) return RTW_E_INVALID;
+    const quat r = quat_from_euler(euler[0], euler[1], euler[2]);
+    out[0] = r.w; out[1] = r.x; out[2] = r.y; out[3] = r.z;
     return RTW_OK;
 }
 
@@ -705,7 +798,7 @@ static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_
 
     QueryArgs q;
     std::memset(&q, 0, sizeof q);
-    q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom;
+    q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom; q.inst_quats = c->inst_quats;
     if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
     if (cam) { q.cam = *cam; q.width = width; q.height = height; }
     q.n = n; q.levels = c->bvh.depth + 2u;
@@ -872,6 +965,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     if (p->integrator > RTW_INTEGRATOR_LIGHT_BIASED || p->sampler > RTW_SAMPLER_NO_RAND || p->accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
     if (p->part_count > 1 && (p->row_block == 0 || p->part_index >= p->part_count)) return RTW_E_INVALID;
     if (p->width > 65535u || p->height > 65535u) return RTW_E_INVALID;      // a lane keeps (column, row) in one register (rtw_kernels.hip Pixel)
+    if (const int qrc = quats_render_check(c->inst_quats != nullptr, p->integrator, c->noise_active, c->tris.n != 0u)) return qrc;
     if (c->noise_active && p->integrator == RTW_INTEGRATOR_RUST2) return RTW_E_UNSUPPORTED;   // Rust2's textures have no noise
     if (c->noise_active && c->tris.n) return RTW_E_UNSUPPORTED;                              // (rtw_ctx_set_triangles / _set_texture_noise refuse it too)
     const bool light_integrator = p->integrator == RTW_INTEGRATOR_LIGHT_CAST || p->integrator == RTW_INTEGRATOR_LIGHT_BIASED;
@@ -942,6 +1036,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     if (c->noise_active) a.noise = c->noise;                       // (selects the noise build: pick_kernel)
     if (c->tris.n) a.tris = tri_view(c, p->accel, p->mint, p->maxt);   // (selects the triangle build; the tree for RTW_ACCEL_BVH requests)
     if (light_integrator) a.lights = c->lights;                    // (the integrator selects the light build, which alone reads them)
+    a.inst_quats = c->inst_quats;                                  // (selects the quaternion build, whatever the integrator of the three it serves)
 #ifdef RTW_ENDTIMES
     if (const char *e = getenv("RTW_ENDTIMES_REF")) a.endtimes_ref = std::strtoull(e, nullptr, 10);       // diagnostic build only
 #endif
@@ -1303,6 +1398,18 @@ int rtw_mgpu_set_texture_noise(rtw_mgpu *m, const RtwPerlin *tables, uint32_t n_
 int rtw_mgpu_set_lights(rtw_mgpu *m, const RtwLight *lights, uint32_t n, float biased_weight) {
     if (!m) return RTW_E_INVALID;
     for (rtw_ctx *c : m->ctx) { int rc = rtw_ctx_set_lights(c, lights, n, biased_weight); if (rc != RTW_OK) return rc; }
+    return RTW_OK;
+}
+
+int rtw_mgpu_set_instance_rotations(rtw_mgpu *m, const float (*qs)[4], uint32_t n) {
+    if (!m) return RTW_E_INVALID;
+    // every context holds the same scene: the list is checked against each before any context is touched, so a refusal leaves all as they were
+    for (rtw_ctx *c : m->ctx) {
+        if (!c->has_scene) return RTW_E_NO_SCENE;
+        if (c->pend.active) return RTW_E_INVALID;
+        if (qs || n) { const int rc = quats_check(c->h_instances.data(), (uint32_t)c->h_instances.size(), qs, n, nullptr); if (rc != RTW_OK) return rc; }
+    }
+    for (rtw_ctx *c : m->ctx) { int rc = rtw_ctx_set_instance_rotations(c, qs, n); if (rc != RTW_OK) return rc; }
     return RTW_OK;
 }
 
