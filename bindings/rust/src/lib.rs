@@ -61,6 +61,10 @@ pub struct RtwBilateral { pub size: u32, pub proximity: u32, pub in_format: u32,
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
 pub struct RtwFilterStats { pub avg_gradient: f32, pub spatial: f32, pub gradient_ms: f32, pub table_ms: f32, pub filter_ms: f32,
     pub total_ms: f32, pub taps: u64 }
+/// Arguments of the guided filter (include/rtw.h): the bilateral ones, the two sigmas (0 = term off) and same_object (1 = a tap on
+/// another object id weighs 0).
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RtwGuidedFilter { pub base: RtwBilateral, pub sigma_depth: f32, pub sigma_normal: f32, pub same_object: u32 }
 /// Rust2 `ProximityType` (postprocessing.rs:12-15).
 #[repr(u32)] #[derive(Clone, Copy)]
 pub enum ProximityKind { Square = 0, Edges = 1 }
@@ -107,6 +111,10 @@ extern "C" {
     fn rtw_bilateral_filter(img: *const c_void, w: u32, h: u32, p: *const RtwBilateral, out: *mut u8, st: *mut RtwFilterStats) -> i32;
     fn rtw_ctx_bilateral_filter(ctx: *mut RtwCtx, img: *const c_void, w: u32, h: u32, p: *const RtwBilateral, out: *mut u8,
                                 st: *mut RtwFilterStats) -> i32;
+    fn rtw_guided_filter(img: *const c_void, w: u32, h: u32, depth: *const f32, normal: *const f32, idx: *const i32,
+                             p: *const RtwGuidedFilter, out: *mut u8, st: *mut RtwFilterStats) -> i32;
+    fn rtw_ctx_guided_filter(ctx: *mut RtwCtx, img: *const c_void, w: u32, h: u32, depth: *const f32, normal: *const f32,
+                                 idx: *const i32, p: *const RtwGuidedFilter, out: *mut u8, st: *mut RtwFilterStats) -> i32;
     fn rtw_triangle_new(origin: *const f32, u: *const f32, v: *const f32, mat3: *const f32, emitted: *const f32,
                         color: *const f32, tex: i32, out: *mut RtwTriangle) -> i32;
     fn rtw_ctx_set_triangles(ctx: *mut RtwCtx, tris: *const RtwTriangle, n: u32) -> i32;
@@ -236,6 +244,15 @@ impl Renderer {
         check(unsafe { rtw_ctx_bilateral_filter(self.ctx, rgb, w, h, p, out.as_mut_ptr(), &mut st) })?;
         Ok((out, st))
     }
+    /// The guided filter on this context's GPU (rtw_ctx_guided_filter): `bilateral_filter` with every tap weighted by the guides -- depth
+    /// [h][w] f32, normal [h][w][3] f32, idx [h][w] i32, each host or device memory, null where its term is off.
+    pub fn guided_filter(&mut self, rgb: *const c_void, w: u32, h: u32, depth: *const f32, normal: *const f32, idx: *const i32,
+                         p: &RtwGuidedFilter) -> Result<(Vec<u8>, RtwFilterStats), RtwError> {
+        let mut out = vec![0u8; w as usize * h as usize * 3];
+        let mut st = RtwFilterStats::default();
+        check(unsafe { rtw_ctx_guided_filter(self.ctx, rgb, w, h, depth, normal, idx, p, out.as_mut_ptr(), &mut st) })?;
+        Ok((out, st))
+    }
     /// Tuning knobs (`RTW_OPT_*` of rtw.h: 1 chunk length, 2 sample bank GiB, 3 LDS geometry, 4 workgroups per CU, 5 list-walk
     /// threshold); none of them changes the image.
     pub fn set_option(&mut self, key: u32, value: f64) -> Result<(), RtwError> { check(unsafe { rtw_ctx_set_option(self.ctx, key, value) }) }
@@ -334,6 +351,16 @@ pub fn bilateral_filter_host(rgb: &[u8], w: u32, h: u32, proximity: Proximity) -
     let p = RtwBilateral { size: proximity.size, proximity: proximity.kind as u32, in_format: 0, avg_gradient: 0.0 };
     let mut out = vec![0u8; rgb.len()];
     check(unsafe { rtw_bilateral_filter(rgb.as_ptr() as *const c_void, w, h, &p, out.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok(out)
+}
+
+/// rtw_guided_filter: the host form of the guided filter (a guide whose term is off may be empty).
+pub fn guided_filter_host(rgb: &[u8], w: u32, h: u32, depth: &[f32], normal: &[f32], idx: &[i32], p: &RtwGuidedFilter) -> Result<Vec<u8>, RtwError> {
+    let mut out = vec![0u8; rgb.len()];
+    let ptr = |n: usize, q: *const c_void| if n == 0 { std::ptr::null() } else { q };
+    check(unsafe { rtw_guided_filter(rgb.as_ptr() as *const c_void, w, h, ptr(depth.len(), depth.as_ptr() as *const c_void) as *const f32,
+                                     ptr(normal.len(), normal.as_ptr() as *const c_void) as *const f32,
+                                     ptr(idx.len(), idx.as_ptr() as *const c_void) as *const i32, p, out.as_mut_ptr(), std::ptr::null_mut()) })?;
     Ok(out)
 }
 

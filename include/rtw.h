@@ -299,8 +299,10 @@ enum {
     RTW_OPT_TAIL_UNITS       = 9, /* guided unit length: the last tiles of the work queue are cut into units of ONE sample (k blocks of them per
                                      resident wave, k = this value) and the tiles before them into units of a third of the launch's length;
                                      0 (default) = one unit length for the whole launch.  Measured: no gain.  v4                 */
-    RTW_OPT_SUB_QUEUES       = 8  /* 0 (default): the work queue is eight sub-queues with a counter each (a wave starts on the one of its
+    RTW_OPT_SUB_QUEUES       = 8, /* 0 (default): the work queue is eight sub-queues with a counter each (a wave starts on the one of its
                                      XCD and helps out on the others when it is empty), a single one for tiny launches; 1: always single */
+    RTW_OPT_GUIDED_LAYOUT    = 10 /* rtw_ctx_guided_filter: 0 (default) places the weight table and the guide tile by size;
+                                     1 table and guides in LDS, 2 guides only, 3 table only, 4 neither -- followed where it fits in LDS  */
 };
 int  rtw_ctx_set_option(rtw_ctx *ctx, uint32_t key, double value);
 
@@ -398,6 +400,38 @@ int rtw_bilateral_filter(const void *in, uint32_t w, uint32_t h, const RtwBilate
  * the scene, and every render, untouched.  stats may be NULL. */
 int rtw_ctx_bilateral_filter(rtw_ctx *ctx, const void *in, uint32_t w, uint32_t h, const RtwBilateral *params, uint8_t *out,
                              RtwFilterStats *stats);
+
+/* ---- guided (joint / cross bilateral) filter: the bilateral filter steered by depth, normal and object-id buffers ----------------------
+ * rtw_bilateral_filter with every tap's three channel weights multiplied by one guide weight g, formed from the buffers that
+ * rtw_ctx_depth_map / rtw_ctx_scene_hits write.  For centre pixel p and tap q, in f32, one rounding per written operation:
+ *     a = 0
+ *     if sigma_depth  > 0:  dz = depth[q] - depth[p];   a = a + inv_depth  * (dz * dz)
+ *     if sigma_normal > 0:  d  = normal[q] - normal[p]; a = a + inv_normal * ((d.x*d.x + d.y*d.y) + d.z*d.z)
+ *     g = (a >= 0) ? exp_plain(-a) : 0                  (a NaN a -- inf - inf, a NaN depth -- drops the tap)
+ *     if same_object and idx[q] != idx[p]:  g = 0
+ *     w_c = table[d2][|k_c|] * g;   col_sum[c] += (q[c] * w_c) / 255;   w_sum[c] += w_c
+ * with inv_depth = 0.5f / (sigma_depth * sigma_depth), inv_normal likewise, and exp_plain the library's own exponential (rtw_exp_plain:
+ * the same bits on the host and on the GPU).  Everything else -- formats, spatial, the range term or a given avg_gradient, the window
+ * with its half-open quirk, the tap order, Edges, the libm weight table, the output byte -- is rtw_bilateral_filter's.  With no term on, g
+ * is not applied and the output is rtw_bilateral_filter's bit for bit; so it is with guides that are constant over the image (g = 1).
+ * Guides: depth [h][w] f32, normal [h][w][3] f32, idx [h][w] i32, row-major.  A miss of rtw_ctx_depth_map (depth maxt * 1.6, normal 0 0 0,
+ * idx -1) is simply another depth, normal and object.  A guide whose term is off may be NULL and is never read.
+ * RTW_E_INVALID: everything rtw_bilateral_filter refuses; a sigma that is negative or not finite, or so small that its inv_* is not finite;
+ * sigma_depth > 0 with depth == NULL; sigma_normal > 0 with normal == NULL; same_object with idx == NULL; same_object > 1.
+ * There is no rtw_mgpu_* form and no JSON form. */
+typedef struct RtwGuidedFilter {
+    RtwBilateral base;              /* size, proximity, in_format, avg_gradient: as rtw_bilateral_filter             */
+    float    sigma_depth;           /* 0 = no depth term; else in the units of `depth`                               */
+    float    sigma_normal;          /* 0 = no normal term; else in units of |n - n'|                                 */
+    uint32_t same_object;           /* 1 = a tap on another idx weighs 0                                             */
+} RtwGuidedFilter;
+/* The host form (threads over rows).  RtwFilterStats as rtw_bilateral_filter: taps counts window entries. */
+int rtw_guided_filter(const void *in, uint32_t w, uint32_t h, const float *depth, const float *normal, const int32_t *idx,
+                      const RtwGuidedFilter *params, uint8_t *out, RtwFilterStats *stats);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host form.  `in`, `out` and each guide may independently be host memory or
+ * device memory of ctx's GPU (host memory is staged).  Needs no scene and leaves the scene, and every render, untouched. */
+int rtw_ctx_guided_filter(rtw_ctx *ctx, const void *in, uint32_t w, uint32_t h, const float *depth, const float *normal,
+                          const int32_t *idx, const RtwGuidedFilter *params, uint8_t *out, RtwFilterStats *stats);
 
 /* ---- Rust2 triangles (Rust2/src/objects/triangle.rs) ----------------------------------------------------------------------------
  * `Triangle{origin, u, v, mat, texture}` with the derived fields of Triangle::new (:28-50): n = u x v, normal = unit(n),
@@ -562,6 +596,9 @@ int rtw_mixed_pdf(float exp, const float p[3], const float n[3], const float dir
 /* The three elementary functions over arrays: out[i] = pow(x[i], y[i]) for x >= 0 (0, 1, inf, NaN included) and finite y >= 0 (libm's special
  * cases: pow(x, 0) = 1 even for a NaN x, pow(0, y > 0) = 0; x < 0 gives NaN); sin / cos of phi in [0, 2 pi] (NaN for NaN). */
 int rtw_pow_plain(const float *x, const float *y, size_t n, float *out);
+/* out[i] = exp(x[i]) for x <= 0 (csrc/rtw_exp.h, the guided filter's exponential): exp(+-0) = 1 exactly, exp(-inf) = 0, NaN for NaN, and a
+ * result below 2^-126 is +0 (no subnormal is ever returned); x > 0 is outside the domain and gives NaN. */
+int rtw_exp_plain(const float *x, size_t n, float *out);
 int rtw_sin_plain(const float *phi, size_t n, float *out);
 int rtw_cos_plain(const float *phi, size_t n, float *out);
 

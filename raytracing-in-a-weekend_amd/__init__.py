@@ -17,6 +17,7 @@ Reference surface mirrored (names and argument meaning):
   PerlinNoise.new / noise / turb / value    Rust/src/texture.rs:61-194
   ImageTexture::from_color_noise / new_with_noise      Rust/src/texture.rs:228-245 (texture_from_color_noise, texture_with_noise)
   bilateral_filter(img, Proximity::new(size, type))  Rust2/src/postprocessing.rs:12-131 (bilateral_filter; Renderer.bilateral_filter)
+  (extension) guided_filter(img, size, depth=, normal=, ids=, ..)   the bilateral filter steered by depth_map's buffers (Renderer.guided_filter)
   Triangle.new (+ from_mesh), Scene(triangles=)       Rust2/src/objects/triangle.rs:28-124 (triangle_hits; Renderer.triangle_hits)
 
 The directory name carries a hyphen (it is fixed by the build contract); import it with
@@ -47,6 +48,7 @@ FLAG_CPP = FLAG_CPP_DIELECTRIC | FLAG_CPP_DIFFUSE      # what Viewport::RenderGP
 FLAG_MIXED_MATERIAL = 32   # Rust2's integrators: an object with opacity < 0 is MixedMaterial::new(ir) (see mixed())
 OPT_CHUNK_LEN, OPT_SAMPLE_BANK_GB, OPT_LDS_GEOM, OPT_BLOCKS_PER_CU, OPT_LIST_WALK_MAX, OPT_TILE_ORDER, OPT_GRAB_BLOCKS, OPT_SUB_QUEUES = 1, 2, 3, 4, 5, 6, 7, 8
 OPT_TAIL_UNITS = 9
+OPT_GUIDED_LAYOUT = 10                               # Renderer.guided_filter: 0 by size, 1 table + guides in LDS, 2 guides, 3 table, 4 neither
 SCENE_C1, SCENE_C2, SCENE_C4, SCENE_C5, SCENE_METAL_TEST, SCENE_QUAD_TEST, SCENE_PRESENTATION, SCENE_FIRST_FRAME = 1, 2, 4, 5, 6, 7, 8, 9
 MEDIUM_SURFACE, MEDIUM_CONST_DENSITY = 0, 1
 PROXIMITY_SQUARE, PROXIMITY_EDGES = 0, 1             # Rust2 ProximityType (postprocessing.rs:12-15)
@@ -150,6 +152,11 @@ class RtwBilateral(C.Structure):
     _fields_ = [("size", C.c_uint32), ("proximity", C.c_uint32), ("in_format", C.c_uint32), ("avg_gradient", C.c_float)]
 
 
+class RtwGuidedFilter(C.Structure):
+    """Arguments of the guided filter: the bilateral ones, the two sigmas (0 = term off) and same_object (include/rtw.h)."""
+    _fields_ = [("base", RtwBilateral), ("sigma_depth", C.c_float), ("sigma_normal", C.c_float), ("same_object", C.c_uint32)]
+
+
 class RtwFilterStats(C.Structure):
     _fields_ = [("avg_gradient", C.c_float), ("spatial", C.c_float), ("gradient_ms", C.c_float), ("table_ms", C.c_float),
                 ("filter_ms", C.c_float), ("total_ms", C.c_float), ("taps", C.c_uint64)]
@@ -231,6 +238,10 @@ def lib() -> C.CDLL:
     L.rtw_bilateral_filter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwBilateral), C.c_void_p, C.POINTER(RtwFilterStats)]
     L.rtw_ctx_bilateral_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwBilateral), C.c_void_p,
                                            C.POINTER(RtwFilterStats)]
+    L.rtw_guided_filter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtwGuidedFilter), C.c_void_p,
+                                    C.POINTER(RtwFilterStats)]
+    L.rtw_ctx_guided_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(RtwGuidedFilter), C.c_void_p, C.POINTER(RtwFilterStats)]
     L.rtw_triangle_new.argtypes = [fp, fp, fp, fp, fp, fp, C.c_int32, C.POINTER(RtwTriangle)]
     L.rtw_ctx_set_triangles.argtypes = [C.c_void_p, C.POINTER(RtwTriangle), C.c_uint32]
     L.rtw_mgpu_set_triangles.argtypes = [C.c_void_p, C.POINTER(RtwTriangle), C.c_uint32]
@@ -262,6 +273,7 @@ def lib() -> C.CDLL:
     L.rtw_quat_from_euler.argtypes = [fp, fp]
     L.rtw_pow_plain.argtypes = [fp, fp, C.c_size_t, fp]
     L.rtw_sin_plain.argtypes = [fp, C.c_size_t, fp]
+    L.rtw_exp_plain.argtypes = [fp, C.c_size_t, fp]
     L.rtw_cos_plain.argtypes = [fp, C.c_size_t, fp]
     _lib = L
     return L
@@ -506,6 +518,11 @@ def _plain1(fn, what, *arrays):
 def pow_plain(x, y) -> np.ndarray:
     """rtw_pow_plain over arrays (broadcast): the library's f32 pow for x >= 0, finite y >= 0."""
     return _plain1(lib().rtw_pow_plain, "rtw_pow_plain", x, y)
+
+
+def exp_plain(x) -> np.ndarray:
+    """rtw_exp_plain over an array: the guided filter's f32 exp for x <= 0 (a result below 2^-126 is +0)."""
+    return _plain1(lib().rtw_exp_plain, "rtw_exp_plain", x)
 
 
 def sin_plain(phi) -> np.ndarray:
@@ -1052,28 +1069,28 @@ class Renderer:
         `img`: a numpy [h][w][3] uint8 array, or float32 (quantised first with Rust2's rule, as quantize_u8_rust2); or an int device
         pointer (e.g. torch_tensor.data_ptr()) with shape=(h, w) and in_format PIXELS_U8 / PIXELS_F32_RUST2.  `out` as in render():
         None -> new numpy uint8 array, numpy array -> host buffer, int -> device pointer of [h][w][3] uint8.  Returns (out, RtwFilterStats)."""
-        if isinstance(img, np.ndarray):
-            fmt = _pixel_format(img) if in_format is None else int(in_format)
-            a = np.ascontiguousarray(img, np.uint8 if fmt == PIXELS_U8 else np.float32)
-            if a.ndim != 3 or a.shape[2] != 3:
-                raise ValueError(f"bilateral_filter: image of shape {a.shape}, expected [h][w][3]")
-            h, w = a.shape[:2]
-            src = C.c_void_p(a.ctypes.data)
-        else:
-            if shape is None or in_format is None:
-                raise ValueError("bilateral_filter: a device pointer needs shape=(h, w) and in_format")
-            h, w = (int(v) for v in shape)
-            fmt, src = int(in_format), C.c_void_p(int(img))
-        if out is None:
-            out = np.empty((h, w, 3), np.uint8)
-        if isinstance(out, np.ndarray):
-            assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size == h * w * 3
-            dst = C.c_void_p(out.ctypes.data)
-        else:
-            dst = C.c_void_p(int(out))
+        src, w, h, fmt, _keep = _filter_source("bilateral_filter", img, shape, in_format)
+        out, dst = _filter_out(out, h, w)
         st = RtwFilterStats()
         prm = RtwBilateral(int(size), int(proximity), fmt, float(avg_gradient))
         _check(lib().rtw_ctx_bilateral_filter(self._h, src, w, h, C.byref(prm), dst, C.byref(st)), "rtw_ctx_bilateral_filter")
+        return out, st
+
+    def guided_filter(self, img, size: int, depth=None, normal=None, ids=None, sigma_depth: float = 0.0, sigma_normal: float = 0.0,
+                      same_object: bool = False, proximity: int = PROXIMITY_SQUARE, avg_gradient: float = 0.0, out=None, shape=None,
+                      in_format: Optional[int] = None):
+        """The bilateral filter guided by depth / normal / object-id buffers on this context's GPU (rtw_ctx_guided_filter, include/rtw.h):
+        each tap's weights are multiplied by exp_plain(-(dz^2 / (2 sigma_depth^2) + |dn|^2 / (2 sigma_normal^2))), and by 0 on another
+        object with same_object.  `img`, `out`, `shape`, `in_format` as bilateral_filter.  `depth` [h][w] float32, `normal` [h][w][3]
+        float32, `ids` [h][w] int32 (what depth_map writes): numpy arrays, or int device pointers; None where the term is off.
+        Returns (out, RtwFilterStats)."""
+        src, w, h, fmt, _keep = _filter_source("guided_filter", img, shape, in_format)
+        guides, _keep_g = _guide_pointers(h, w, depth, normal, ids)
+        out, dst = _filter_out(out, h, w)
+        st = RtwFilterStats()
+        prm = RtwGuidedFilter(RtwBilateral(int(size), int(proximity), fmt, float(avg_gradient)), float(sigma_depth), float(sigma_normal),
+                              int(same_object))
+        _check(lib().rtw_ctx_guided_filter(self._h, src, w, h, *guides, C.byref(prm), dst, C.byref(st)), "rtw_ctx_guided_filter")
         return out, st
 
     def render(self, cam: RtwCamera, params: RtwParams, out=None):
@@ -1203,19 +1220,70 @@ def _pixel_format(img: np.ndarray) -> int:
     raise ValueError(f"bilateral_filter: dtype {img.dtype}, expected uint8 or float32")
 
 
+def _filter_source(what, img, shape, in_format):
+    """(pointer, w, h, format, the array kept alive) of a filter's image argument: a numpy array, or a device pointer with shape + format."""
+    if isinstance(img, np.ndarray):
+        fmt = _pixel_format(img) if in_format is None else int(in_format)
+        a = np.ascontiguousarray(img, np.uint8 if fmt == PIXELS_U8 else np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"{what}: image of shape {a.shape}, expected [h][w][3]")
+        return C.c_void_p(a.ctypes.data), a.shape[1], a.shape[0], fmt, a
+    if shape is None or in_format is None:
+        raise ValueError(f"{what}: a device pointer needs shape=(h, w) and in_format")
+    h, w = (int(v) for v in shape)
+    return C.c_void_p(int(img)), w, h, int(in_format), None
+
+
+def _filter_out(out, h, w):
+    """(out, pointer) of a filter's `out` argument: None -> a new numpy uint8 array, a numpy array -> host buffer, int -> device pointer."""
+    if out is None:
+        out = np.empty((h, w, 3), np.uint8)
+    if isinstance(out, np.ndarray):
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size == h * w * 3
+        return out, C.c_void_p(out.ctypes.data)
+    return out, C.c_void_p(int(out))
+
+
 def bilateral_filter(img: np.ndarray, size: int, proximity: int = PROXIMITY_SQUARE, avg_gradient: float = 0.0):
     """Rust2's `bilateral_filter(img, Proximity::new(size, proximity))` (Rust2/src/postprocessing.rs:70-131) on the host
     (rtw_bilateral_filter), bit for bit.  img: [h][w][3] uint8, or float32 quantised first as quantize_u8_rust2.  avg_gradient 0 computes
     the range term as the reference does; a positive value is used as given.  Returns (uint8 [h][w][3], RtwFilterStats)."""
-    fmt = _pixel_format(np.asarray(img))
-    a = np.ascontiguousarray(img, np.uint8 if fmt == PIXELS_U8 else np.float32)
-    if a.ndim != 3 or a.shape[2] != 3:
-        raise ValueError(f"bilateral_filter: image of shape {a.shape}, expected [h][w][3]")
-    out = np.empty(a.shape, np.uint8)
+    src, w, h, fmt, _keep = _filter_source("bilateral_filter", np.asarray(img), None, None)
+    out, dst = _filter_out(None, h, w)
     st = RtwFilterStats()
     prm = RtwBilateral(int(size), int(proximity), fmt, float(avg_gradient))
-    _check(lib().rtw_bilateral_filter(C.c_void_p(a.ctypes.data), a.shape[1], a.shape[0], C.byref(prm), C.c_void_p(out.ctypes.data),
-                                      C.byref(st)), "rtw_bilateral_filter")
+    _check(lib().rtw_bilateral_filter(src, w, h, C.byref(prm), dst, C.byref(st)), "rtw_bilateral_filter")
+    return out, st
+
+
+def _guide_pointers(h, w, depth, normal, ids):
+    """The three guide arguments as pointers: numpy arrays are shape-checked against the image, ints are device pointers, None is NULL."""
+    keep, ptrs = [], []
+    for name, g, dtype, shp in (("depth", depth, np.float32, (h, w)), ("normal", normal, np.float32, (h, w, 3)), ("ids", ids, np.int32, (h, w))):
+        if g is None:
+            ptrs.append(None)
+        elif isinstance(g, np.ndarray):
+            if g.shape != shp:
+                raise ValueError(f"guided_filter: {name} of shape {g.shape}, expected {shp}")
+            a = np.ascontiguousarray(g, dtype)
+            keep.append(a)
+            ptrs.append(C.c_void_p(a.ctypes.data))
+        else:
+            ptrs.append(C.c_void_p(int(g)))
+    return ptrs, keep
+
+
+def guided_filter(img: np.ndarray, size: int, depth=None, normal=None, ids=None, sigma_depth: float = 0.0, sigma_normal: float = 0.0,
+                  same_object: bool = False, proximity: int = PROXIMITY_SQUARE, avg_gradient: float = 0.0):
+    """The guided filter on the host (rtw_guided_filter), the bytes of Renderer.guided_filter: bilateral_filter with each tap's weights
+    multiplied by the guide weight of depth [h][w] / normal [h][w][3] / ids [h][w] (include/rtw.h).  Returns (uint8 [h][w][3], RtwFilterStats)."""
+    src, w, h, fmt, _keep = _filter_source("guided_filter", np.asarray(img), None, None)
+    guides, _keep_g = _guide_pointers(h, w, depth, normal, ids)
+    out, dst = _filter_out(None, h, w)
+    st = RtwFilterStats()
+    prm = RtwGuidedFilter(RtwBilateral(int(size), int(proximity), fmt, float(avg_gradient)), float(sigma_depth), float(sigma_normal),
+                          int(same_object))
+    _check(lib().rtw_guided_filter(src, w, h, *guides, C.byref(prm), dst, C.byref(st)), "rtw_guided_filter")
     return out, st
 
 

@@ -1,4 +1,4 @@
-// rtw_filter.h -- the bilateral post-process (rtw_filter.hip) as rtw_shim.hip's context entry point sees it.
+// rtw_filter.h -- the bilateral and the guided post-process (rtw_filter.hip) as rtw_shim.hip's context entry point sees it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rtw.h"
@@ -12,5 +12,10 @@ void filter_scratch_free(FilterScratch *f);
 // rtw_ctx_bilateral_filter on `device` / `stream`; *scratch is created on first use.  A failed HIP call stores its code in *last_hip.
 int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scratch, const void *in, uint32_t w, uint32_t h,
                             const RtwBilateral *p, uint8_t *out, RtwFilterStats *stats, int *last_hip);
+
+// rtw_ctx_guided_filter likewise, on the same scratch.  layout: RTW_OPT_GUIDED_LAYOUT (0 = chosen by size).
+int guided_filter_device(int device, hipStream_t stream, FilterScratch **scratch, uint32_t layout, const void *in, uint32_t w, uint32_t h,
+                         const float *depth, const float *normal, const int32_t *idx, const RtwGuidedFilter *p, uint8_t *out,
+                         RtwFilterStats *stats, int *last_hip);
 
 } // namespace rtw

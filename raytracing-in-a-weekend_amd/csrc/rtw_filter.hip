@@ -15,6 +15,7 @@
 // Everything here is compiled with -ffp-contract=off and correctly rounded f32 division and sqrt (Makefile), like the reference.
 #include "rtw_filter.h"
 #include "rtw_devmem.h"
+#include "rtw_exp.h"
 #include "rtw_host.h"
 
 #include <algorithm>
@@ -31,6 +32,12 @@ namespace {
 constexpr uint32_t FBX = 32, FBY = 16;          // filter workgroup: 32 x 16 output pixels (a wave covers two rows of 32: conflict-free tile reads)
 constexpr uint32_t SUM_CHUNK = 2048;            // terms the summing wave moves through LDS per step: 8 float4 per lane
 constexpr uint32_t TABLE_LDS_MAX = 80u * 1024u; // table + tile in LDS while two workgroups still fit in a CU's 160 KiB; else the table stays global
+// The guided filter (profiles/guided_lds_ab.log): the guide planes sit in LDS behind the pixel tile while both fit in
+// GUIDED_GUIDE_LDS_MAX, else the taps' guides are read from global memory; the table joins them only while everything still fits in
+// GUIDED_TABLE_LDS_MAX (two workgroups per CU) -- at 1080p / size 10 the table in global memory beside guides in LDS was the fastest.
+constexpr uint32_t GUIDED_GUIDE_LDS_MAX = 80u * 1024u;
+constexpr uint32_t GUIDED_TABLE_LDS_MAX = 80u * 1024u;
+constexpr uint32_t GUIDED_LDS_CAP = 160u * 1024u;         // what a workgroup can have at all: the limit of an RTW_OPT_GUIDED_LAYOUT request
 
 // ---- the arithmetic shared by the host path and the kernels ------------------------------------------------------------------------
 // intensity (postprocessing.rs:64-68): 0.2989 * r / 255 + 0.5870 * g / 255 + 0.1140 * b / 255, left to right
@@ -181,6 +188,128 @@ __global__ void __launch_bounds__(FBX * FBY) bilateral_filter_kernel(const uint8
     o[2] = rust_as_u8((cs2 * 255.0f) / ws2);
 }
 
+// ---- the guided (joint bilateral) filter: DESIGN.md 8b -----------------------------------------------------------------------------
+// The guide weight of tap q for centre p, one definition for the host path and the kernel.  TERMS: GUIDE_DEPTH | GUIDE_NORMAL | GUIDE_IDX.
+//   a = 0;  depth: a += inv_depth * dz^2;  normal: a += inv_normal * ((dx^2 + dy^2) + dz^2);  g = a >= 0 ? exp_plain(-a) : 0 (a NaN a drops
+//   the tap);  same_object: g = 0 where the ids differ.
+constexpr int GUIDE_DEPTH = 1, GUIDE_NORMAL = 2, GUIDE_IDX = 4;
+
+struct GuidePixel { float z, nx, ny, nz; int32_t id; };
+
+template <int TERMS>
+__host__ __device__ inline float guide_weight(float inv_depth, float inv_normal, const GuidePixel &p, const GuidePixel &q) {
+    float a = 0.0f;
+    if (TERMS & GUIDE_DEPTH) {
+        const float dz = q.z - p.z;
+        a = a + inv_depth * (dz * dz);
+    }
+    if (TERMS & GUIDE_NORMAL) {
+        const float dx = q.nx - p.nx, dy = q.ny - p.ny, dz = q.nz - p.nz;
+        a = a + inv_normal * ((dx * dx + dy * dy) + dz * dz);
+    }
+    float g = a >= 0.0f ? exp_plain(-a) : 0.0f;
+    if ((TERMS & GUIDE_IDX) && q.id != p.id) g = 0.0f;
+    return g;
+}
+
+// pixel i of the guide planes ([h][w] f32, [h][w][3] f32, [h][w] i32); a plane whose term is off is not read
+template <int TERMS>
+__host__ __device__ inline GuidePixel guide_load(const float *depth, const float *normal, const int32_t *idx, size_t i) {
+    GuidePixel g = { 0.0f, 0.0f, 0.0f, 0.0f, 0 };
+    if (TERMS & GUIDE_DEPTH) g.z = depth[i];
+    if (TERMS & GUIDE_NORMAL) { g.nx = normal[3 * i]; g.ny = normal[3 * i + 1]; g.nz = normal[3 * i + 2]; }
+    if (TERMS & GUIDE_IDX) g.id = idx[i];
+    return g;
+}
+
+constexpr uint32_t guide_planes(int terms) { return (terms & GUIDE_DEPTH ? 1u : 0u) + (terms & GUIDE_NORMAL ? 3u : 0u) + (terms & GUIDE_IDX ? 1u : 0u); }
+
+// bilateral_filter_kernel with every tap's three weights multiplied by the guide weight: the same workgroup, tile, loop and tap order.
+// LDS (dwords): [table, with TABLE_LDS][packed-pixel tile][with GUIDE_LDS one plane of tile size per guide component: z | nx | ny | nz | id].
+// The planes are separate arrays, so a wave's read of one component is two rows of 32 consecutive dwords like the pixel tile's.  Without
+// GUIDE_LDS the taps' guides come from global memory (a wave reads two runs of 32 consecutive pixels per plane).  TERMS == 0 is the plain
+// filter: no guide is touched and no weight is multiplied.
+template <bool TABLE_LDS, bool GUIDE_LDS, int TERMS>
+__global__ void __launch_bounds__(FBX * FBY) guided_filter_kernel(const uint8_t *__restrict__ img, uint32_t w, uint32_t h, int s, int edges,
+                                                                  const float *__restrict__ table, uint32_t table_floats,
+                                                                  const uint16_t *__restrict__ rowmap, const float *__restrict__ depth,
+                                                                  const float *__restrict__ normal, const int32_t *__restrict__ idx,
+                                                                  float inv_depth, float inv_normal, uint8_t *__restrict__ out) {
+    extern __shared__ uint32_t smem[];
+    float *ltab = (float *)smem;
+    uint32_t *tile = smem + (TABLE_LDS ? table_floats : 0);
+    const int tx = (int)(threadIdx.x % FBX), ty = (int)(threadIdx.x / FBX);
+    const int x0 = (int)(blockIdx.x * FBX), y0 = (int)(blockIdx.y * FBY);
+    const int tw = (int)FBX + 2 * s, th = (int)FBY + 2 * s;
+    const int tn = tw * th;
+    // the guide planes behind the tile, in the order z, nx, ny, nz, id; an absent one takes no room
+    float *gz = (float *)(tile + tn);
+    float *gn = gz + ((TERMS & GUIDE_DEPTH) ? tn : 0);
+    int32_t *gi = (int32_t *)(gn + ((TERMS & GUIDE_NORMAL) ? 3 * tn : 0));
+    for (int i = (int)threadIdx.x; i < tn; i += (int)(FBX * FBY)) {
+        const int ix = x0 - s + i % tw, iy = y0 - s + i / tw;
+        const bool in = ix >= 0 && iy >= 0 && ix < (int)w && iy < (int)h;
+        uint32_t v = 0;
+        if (in) {
+            const uint8_t *p = img + 3 * ((size_t)iy * w + ix);
+            v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+        }
+        tile[i] = v;
+        if (GUIDE_LDS && TERMS) {
+            GuidePixel g = { 0.0f, 0.0f, 0.0f, 0.0f, 0 };
+            if (in) g = guide_load<TERMS>(depth, normal, idx, (size_t)iy * w + ix);
+            if (TERMS & GUIDE_DEPTH) gz[i] = g.z;
+            if (TERMS & GUIDE_NORMAL) { gn[i] = g.nx; gn[tn + i] = g.ny; gn[2 * tn + i] = g.nz; }
+            if (TERMS & GUIDE_IDX) gi[i] = g.id;
+        }
+    }
+    if (TABLE_LDS)
+        for (uint32_t i = threadIdx.x; i < table_floats / 4; i += FBX * FBY) ((float4 *)ltab)[i] = ((const float4 *)table)[i];
+    __syncthreads();
+    const int x = x0 + tx, y = y0 + ty;
+    if (x >= (int)w || y >= (int)h) return;
+    const int centre = (ty + s) * tw + tx + s;
+    const uint32_t pc = tile[centre];
+    const int p0 = (int)(pc & 255u), p1 = (int)((pc >> 8) & 255u), p2 = (int)(pc >> 16);
+    const size_t pix = (size_t)y * w + x;
+    const GuidePixel gp = guide_load<TERMS>(depth, normal, idx, pix);
+    const int lx = -min(x, s), hx = min((int)w - x - 1, s), ly = -min(y, s), hy = min((int)h - y - 1, s);
+    float cs0 = 0.0f, cs1 = 0.0f, cs2 = 0.0f, ws0 = 0.0f, ws1 = 0.0f, ws2 = 0.0f;
+    for (int dx = -s; dx < s; dx++) {
+        const int adx = dx < 0 ? -dx : dx;
+        const int dy_lo = edges ? -(s - 1 - adx) : -s, dy_hi = edges ? s - 1 - adx : s - 1;     // inclusive
+        const bool col_in = dx >= lx && dx < hx;
+        for (int dy = dy_lo; dy <= dy_hi; dy++) {
+            const float *t = (TABLE_LDS ? ltab : table) + 256u * rowmap[dx * dx + dy * dy];
+            if (col_in && dy >= ly && dy < hy) {
+                const int off = centre + dy * tw + dx;
+                const uint32_t q = tile[off];
+                const int q0 = (int)(q & 255u), q1 = (int)((q >> 8) & 255u), q2 = (int)(q >> 16);
+                float w0 = t[q0 > p0 ? q0 - p0 : p0 - q0], w1 = t[q1 > p1 ? q1 - p1 : p1 - q1], w2 = t[q2 > p2 ? q2 - p2 : p2 - q2];
+                if (TERMS) {
+                    GuidePixel gq = { 0.0f, 0.0f, 0.0f, 0.0f, 0 };
+                    if (GUIDE_LDS) {
+                        if (TERMS & GUIDE_DEPTH) gq.z = gz[off];
+                        if (TERMS & GUIDE_NORMAL) { gq.nx = gn[off]; gq.ny = gn[tn + off]; gq.nz = gn[2 * tn + off]; }
+                        if (TERMS & GUIDE_IDX) gq.id = gi[off];
+                    } else {
+                        gq = guide_load<TERMS>(depth, normal, idx, (size_t)((int64_t)pix + (int64_t)dy * (int64_t)w + dx));
+                    }
+                    const float g = guide_weight<TERMS>(inv_depth, inv_normal, gp, gq);
+                    w0 = w0 * g; w1 = w1 * g; w2 = w2 * g;
+                }
+                cs0 += ((float)q0 * w0) / 255.0f; ws0 += w0;
+                cs1 += ((float)q1 * w1) / 255.0f; ws1 += w1;
+                cs2 += ((float)q2 * w2) / 255.0f; ws2 += w2;
+            }
+        }
+    }
+    uint8_t *o = out + 3 * pix;
+    o[0] = rust_as_u8((cs0 * 255.0f) / ws0);
+    o[1] = rust_as_u8((cs1 * 255.0f) / ws1);
+    o[2] = rust_as_u8((cs2 * 255.0f) / ws2);
+}
+
 // ---- host side: checks, the window's d2 rows, the weight table ---------------------------------------------------------------------
 int check_args(const void *in, uint32_t w, uint32_t h, const RtwBilateral *p, const uint8_t *out) {
     if (!in || !p || !out) return RTW_E_INVALID;
@@ -280,6 +409,82 @@ void host_filter_rows(const uint8_t *img, uint32_t w, uint32_t h, uint32_t size,
         }
 }
 
+// ---- the guided filter on the host ---------------------------------------------------------------------------------------------------
+struct GuideArgs {
+    const float *depth = nullptr, *normal = nullptr;
+    const int32_t *idx = nullptr;
+    float inv_depth = 0.0f, inv_normal = 0.0f;
+    int terms = 0;                                 // GUIDE_DEPTH | GUIDE_NORMAL | GUIDE_IDX: the terms that are on
+};
+
+// everything rtw_bilateral_filter refuses, and the guide terms (rtw.h); fills `g` (a guide whose term is off is dropped here: never read)
+int check_guided_args(const void *in, uint32_t w, uint32_t h, const float *depth, const float *normal, const int32_t *idx,
+                      const RtwGuidedFilter *p, const uint8_t *out, GuideArgs &g) {
+    if (!p) return RTW_E_INVALID;
+    const int rc = check_args(in, w, h, &p->base, out);
+    if (rc != RTW_OK) return rc;
+    if (!(p->sigma_depth >= 0.0f) || !std::isfinite(p->sigma_depth)) return RTW_E_INVALID;
+    if (!(p->sigma_normal >= 0.0f) || !std::isfinite(p->sigma_normal)) return RTW_E_INVALID;
+    if (p->same_object > 1) return RTW_E_INVALID;
+    g = GuideArgs();
+    if (p->sigma_depth > 0.0f) {
+        g.inv_depth = 0.5f / (p->sigma_depth * p->sigma_depth);
+        if (!depth || !std::isfinite(g.inv_depth)) return RTW_E_INVALID;        // (a tiny sigma: inf * 0 for equal guides)
+        g.depth = depth;
+        g.terms |= GUIDE_DEPTH;
+    }
+    if (p->sigma_normal > 0.0f) {
+        g.inv_normal = 0.5f / (p->sigma_normal * p->sigma_normal);
+        if (!normal || !std::isfinite(g.inv_normal)) return RTW_E_INVALID;
+        g.normal = normal;
+        g.terms |= GUIDE_NORMAL;
+    }
+    if (p->same_object) {
+        if (!idx) return RTW_E_INVALID;
+        g.idx = idx;
+        g.terms |= GUIDE_IDX;
+    }
+    return RTW_OK;
+}
+
+// host_filter_rows with the guide weight on every tap (TERMS == 0: the same arithmetic as host_filter_rows, nothing multiplied)
+template <int TERMS>
+void host_guided_rows(const uint8_t *img, uint32_t w, uint32_t h, uint32_t size, bool edges, const Plan &pl, const float *table,
+                      const GuideArgs &ga, uint8_t *out, uint32_t y_begin, uint32_t y_end) {
+    for (uint32_t y = y_begin; y < y_end; y++)
+        for (uint32_t x = 0; x < w; x++) {
+            const uint8_t *p = img + 3 * ((size_t)y * w + x);
+            const GuidePixel gp = guide_load<TERMS>(ga.depth, ga.normal, ga.idx, (size_t)y * w + x);
+            const uint32_t left = x - std::min(x, size), right = x + std::min(w - x - 1, size);
+            const uint32_t up = y - std::min(y, size), down = y + std::min(h - y - 1, size);
+            float col[3] = { 0, 0, 0 }, ws[3] = { 0, 0, 0 };
+            for (uint32_t xi = left; xi < right; xi++)
+                for (uint32_t yi = up; yi < down; yi++) {
+                    const int dx = (int)xi - (int)x, dy = (int)yi - (int)y;
+                    if (edges && !((uint32_t)(std::abs(dx) + std::abs(dy)) < size)) continue;
+                    const float *t = table + 256u * pl.rowmap[dx * dx + dy * dy];
+                    const uint8_t *q = img + 3 * ((size_t)yi * w + xi);
+                    float g = 1.0f;
+                    if (TERMS) g = guide_weight<TERMS>(ga.inv_depth, ga.inv_normal, gp, guide_load<TERMS>(ga.depth, ga.normal, ga.idx, (size_t)yi * w + xi));
+                    for (int c = 0; c < 3; c++) {
+                        float wt = t[std::abs((int)q[c] - (int)p[c])];
+                        if (TERMS) wt = wt * g;
+                        col[c] += ((float)q[c] * wt) / 255.0f;
+                        ws[c] += wt;
+                    }
+                }
+            for (int c = 0; c < 3; c++) out[3 * ((size_t)y * w + x) + c] = rust_as_u8((col[c] * 255.0f) / ws[c]);
+        }
+}
+
+using HostGuidedRows = void (*)(const uint8_t *, uint32_t, uint32_t, uint32_t, bool, const Plan &, const float *, const GuideArgs &, uint8_t *,
+                                uint32_t, uint32_t);
+HostGuidedRows host_guided_rows_for(int terms) {
+    static const HostGuidedRows f[8] = { host_guided_rows<0>, host_guided_rows<1>, host_guided_rows<2>, host_guided_rows<3>,
+                                         host_guided_rows<4>, host_guided_rows<5>, host_guided_rows<6>, host_guided_rows<7> };
+    return f[terms & 7];
+}
+
 double ms_since(std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
@@ -293,6 +498,7 @@ struct FilterScratch {
     DevMem terms;                                  // the gradient terms
     DevMem table;                                  // weight table [rows][256] f32, then the d2 -> row map
     DevMem out;                                    // the u8 result when the caller's buffer is host memory
+    DevMem depth, normal, idx;                     // the guided filter's guides when the caller's are host memory
     DevMem sum;                                    // the gradient sum (device) ...
     PinnedMem h_sum;                               // ... and its pinned read-back slot
     PinnedMem h_table;                             // pinned: the table's upload is a true async copy
@@ -318,16 +524,25 @@ float event_ms(hipEvent_t a, hipEvent_t b) {
 }
 } // namespace
 
-int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scratch, const void *in, uint32_t w, uint32_t h,
-                            const RtwBilateral *p, uint8_t *out, RtwFilterStats *stats, int *last_hip) {
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = check_args(in, w, h, p, out);
-    if (rc != RTW_OK) return rc;
 #define FILTER_TRY(expr)                                                                                                          \
     do {                                                                                                                          \
         hipError_t e_ = (expr);                                                                                                   \
         if (e_ != hipSuccess) { *last_hip = (int)e_; return e_ == hipErrorOutOfMemory ? RTW_E_NOMEM : RTW_E_HIP; } \
     } while (0)
+
+namespace {
+// What both filters do before their kernel: the scratch, the u8 frame on the device, the range term, the weight table and its upload.
+struct Prepared {
+    FilterScratch *f = nullptr;
+    const uint8_t *img = nullptr;
+    float avg = 0.0f, gradient_ms = 0.0f, table_ms = 0.0f;
+    bool edges = false;
+    Plan pl;
+    size_t n_bytes = 0, n_rows = 0, table_bytes = 0;
+};
+
+int prepare_filter(int device, hipStream_t stream, FilterScratch **scratch, const void *in, uint32_t w, uint32_t h, const RtwBilateral *p,
+                   Prepared &pr, int *last_hip) {
     FILTER_TRY(hipSetDevice(device));
     if (!*scratch) {
         FilterScratch *f = new (std::nothrow) FilterScratch();
@@ -337,8 +552,8 @@ int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scra
         FILTER_TRY(f->sum.reserve(sizeof(float)));
         FILTER_TRY(f->h_sum.reserve(sizeof(float)));
     }
-    FilterScratch *f = *scratch;
-    const size_t n_bytes = (size_t)w * h * 3;
+    FilterScratch *f = pr.f = *scratch;
+    const size_t n_bytes = pr.n_bytes = (size_t)w * h * 3;
 
     // the u8 frame on the device
     const uint8_t *img;
@@ -361,6 +576,7 @@ int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scra
         FILTER_TRY(hipGetLastError());
         img = f->img.as<uint8_t>();
     }
+    pr.img = img;
 
     // the range term: the gradient terms in parallel, their sum in the reference's order by one wave, read back
     float avg = p->avg_gradient, gradient_ms = 0.0f;
@@ -377,21 +593,50 @@ int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scra
         avg = avg_from_sum(*f->h_sum.as<float>(), w, h);
         gradient_ms = event_ms(f->ev[0], f->ev[1]);
     }
+    pr.avg = avg;
+    pr.gradient_ms = gradient_ms;
 
     // the weight table (host libm expf) and the d2 -> row map, uploaded together
     const auto t1 = std::chrono::steady_clock::now();
-    const bool edges = p->proximity == RTW_PROXIMITY_EDGES;
-    Plan pl;
-    make_plan(w, h, p->size, edges, pl);
-    const size_t n_rows = std::max<size_t>(1, pl.row_d2.size());
-    const size_t table_bytes = n_rows * 256 * sizeof(float), map_bytes = pl.rowmap.size() * sizeof(uint16_t);
+    pr.edges = p->proximity == RTW_PROXIMITY_EDGES;
+    Plan &pl = pr.pl;
+    make_plan(w, h, p->size, pr.edges, pl);
+    const size_t n_rows = pr.n_rows = std::max<size_t>(1, pl.row_d2.size());
+    const size_t table_bytes = pr.table_bytes = n_rows * 256 * sizeof(float), map_bytes = pl.rowmap.size() * sizeof(uint16_t);
     FILTER_TRY(f->h_table.reserve(table_bytes + map_bytes));
     std::memset(f->h_table.ptr, 0, table_bytes);
     build_table(pl, range_term(avg), f->h_table.as<float>());
     std::memcpy(f->h_table.as<char>() + table_bytes, pl.rowmap.data(), map_bytes);
     FILTER_TRY(f->table.reserve(table_bytes + map_bytes));
     FILTER_TRY(hipMemcpyAsync(f->table.ptr, f->h_table.ptr, table_bytes + map_bytes, hipMemcpyHostToDevice, stream));
-    const float table_ms = (float)ms_since(t1);
+    pr.table_ms = (float)ms_since(t1);
+    return RTW_OK;
+}
+
+void fill_stats(RtwFilterStats *stats, const Prepared &pr, std::chrono::steady_clock::time_point t0) {
+    if (!stats) return;
+    stats->avg_gradient = pr.avg;
+    stats->spatial = pr.pl.spatial;
+    stats->gradient_ms = pr.gradient_ms;
+    stats->table_ms = pr.table_ms;
+    stats->filter_ms = event_ms(pr.f->ev[2], pr.f->ev[3]);
+    stats->total_ms = (float)ms_since(t0);
+    stats->taps = pr.pl.taps;
+}
+} // namespace
+
+int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scratch, const void *in, uint32_t w, uint32_t h,
+                            const RtwBilateral *p, uint8_t *out, RtwFilterStats *stats, int *last_hip) {
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = check_args(in, w, h, p, out);
+    if (rc != RTW_OK) return rc;
+    Prepared pr;
+    rc = prepare_filter(device, stream, scratch, in, w, h, p, pr, last_hip);
+    if (rc != RTW_OK) return rc;
+    FilterScratch *f = pr.f;
+    const uint8_t *img = pr.img;
+    const bool edges = pr.edges;
+    const size_t n_bytes = pr.n_bytes, n_rows = pr.n_rows, table_bytes = pr.table_bytes;
 
     // the filter
     uint8_t *dst = out;
@@ -417,18 +662,99 @@ int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scra
     FILTER_TRY(hipEventRecord(f->ev[3], stream));
     if (!direct) FILTER_TRY(hipMemcpyAsync(out, dst, n_bytes, hipMemcpyDefault, stream));
     FILTER_TRY(hipStreamSynchronize(stream));
-#undef FILTER_TRY
-    if (stats) {
-        stats->avg_gradient = avg;
-        stats->spatial = pl.spatial;
-        stats->gradient_ms = gradient_ms;
-        stats->table_ms = table_ms;
-        stats->filter_ms = event_ms(f->ev[2], f->ev[3]);
-        stats->total_ms = (float)ms_since(t0);
-        stats->taps = pl.taps;
-    }
+    fill_stats(stats, pr, t0);
     return RTW_OK;
 }
+
+// ---- the guided filter on the device -------------------------------------------------------------------------------------------------
+namespace {
+using GuidedKernel = void (*)(const uint8_t *, uint32_t, uint32_t, int, int, const float *, uint32_t, const uint16_t *, const float *,
+                              const float *, const int32_t *, float, float, uint8_t *);
+template <int TERMS>
+GuidedKernel guided_kernel_of(bool table_lds, bool guide_lds) {
+    if (table_lds) return guide_lds ? guided_filter_kernel<true, true, TERMS> : guided_filter_kernel<true, false, TERMS>;
+    return guide_lds ? guided_filter_kernel<false, true, TERMS> : guided_filter_kernel<false, false, TERMS>;
+}
+GuidedKernel guided_kernel_for(int terms, bool table_lds, bool guide_lds) {
+    switch (terms & 7) {
+    case 0: return guided_kernel_of<0>(table_lds, false);          // no guide: nothing to place
+    case 1: return guided_kernel_of<1>(table_lds, guide_lds);
+    case 2: return guided_kernel_of<2>(table_lds, guide_lds);
+    case 3: return guided_kernel_of<3>(table_lds, guide_lds);
+    case 4: return guided_kernel_of<4>(table_lds, guide_lds);
+    case 5: return guided_kernel_of<5>(table_lds, guide_lds);
+    case 6: return guided_kernel_of<6>(table_lds, guide_lds);
+    default: return guided_kernel_of<7>(table_lds, guide_lds);
+    }
+}
+
+// Where the weight table and the guide tile go (profiles/guided_lds_ab.log).  layout 0 decides by size; 1 .. 4 ask for
+// table + guides in LDS / guides only / table only / neither, and are followed where the request fits in GUIDED_LDS_CAP.
+void guided_layout(uint32_t layout, size_t table_bytes, size_t tile_bytes, size_t guide_bytes, bool &table_lds, bool &guide_lds) {
+    guide_lds = guide_bytes > 0 && tile_bytes + guide_bytes <= GUIDED_GUIDE_LDS_MAX;
+    table_lds = table_bytes + tile_bytes + (guide_lds ? guide_bytes : 0) <= GUIDED_TABLE_LDS_MAX;
+    if (layout >= 1 && layout <= 4) {
+        const bool t = layout == 1 || layout == 3, g = guide_bytes > 0 && (layout == 1 || layout == 2);
+        if (tile_bytes + (t ? table_bytes : 0) + (g ? guide_bytes : 0) <= GUIDED_LDS_CAP) { table_lds = t; guide_lds = g; }
+    }
+}
+} // namespace
+
+int guided_filter_device(int device, hipStream_t stream, FilterScratch **scratch, uint32_t layout, const void *in, uint32_t w, uint32_t h,
+                         const float *depth, const float *normal, const int32_t *idx, const RtwGuidedFilter *p, uint8_t *out,
+                         RtwFilterStats *stats, int *last_hip) {
+    const auto t0 = std::chrono::steady_clock::now();
+    GuideArgs ga;
+    int rc = check_guided_args(in, w, h, depth, normal, idx, p, out, ga);
+    if (rc != RTW_OK) return rc;
+    Prepared pr;
+    rc = prepare_filter(device, stream, scratch, in, w, h, &p->base, pr, last_hip);
+    if (rc != RTW_OK) return rc;
+    FilterScratch *f = pr.f;
+
+    // the guides on the device: a host plane is staged; a plane whose term is off is not touched
+    const size_t n_px = (size_t)w * h;
+    if (ga.depth && !on_device(ga.depth, device)) {
+        FILTER_TRY(f->depth.reserve(n_px * sizeof(float)));
+        FILTER_TRY(hipMemcpyAsync(f->depth.ptr, ga.depth, n_px * sizeof(float), hipMemcpyDefault, stream));
+        ga.depth = f->depth.as<const float>();
+    }
+    if (ga.normal && !on_device(ga.normal, device)) {
+        FILTER_TRY(f->normal.reserve(n_px * 3 * sizeof(float)));
+        FILTER_TRY(hipMemcpyAsync(f->normal.ptr, ga.normal, n_px * 3 * sizeof(float), hipMemcpyDefault, stream));
+        ga.normal = f->normal.as<const float>();
+    }
+    if (ga.idx && !on_device(ga.idx, device)) {
+        FILTER_TRY(f->idx.reserve(n_px * sizeof(int32_t)));
+        FILTER_TRY(hipMemcpyAsync(f->idx.ptr, ga.idx, n_px * sizeof(int32_t), hipMemcpyDefault, stream));
+        ga.idx = f->idx.as<const int32_t>();
+    }
+
+    uint8_t *dst = out;
+    const bool direct = on_device(out, device);
+    if (!direct) { FILTER_TRY(f->out.reserve(pr.n_bytes)); dst = f->out.as<uint8_t>(); }
+    const int s = (int)p->base.size;
+    const size_t tile_bytes = (size_t)(FBX + 2 * s) * (FBY + 2 * s) * sizeof(uint32_t);
+    const size_t guide_bytes = tile_bytes * guide_planes(ga.terms);
+    bool table_lds, guide_lds;
+    guided_layout(layout, pr.table_bytes, tile_bytes, guide_bytes, table_lds, guide_lds);
+    const size_t lds = tile_bytes + (table_lds ? pr.table_bytes : 0) + (guide_lds ? guide_bytes : 0);
+    const GuidedKernel kern = guided_kernel_for(ga.terms, table_lds, guide_lds);
+    if (lds > 64u * 1024u) FILTER_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const dim3 grid((w + FBX - 1) / FBX, (h + FBY - 1) / FBY);
+    const float *d_table = f->table.as<float>();
+    const uint16_t *d_map = (const uint16_t *)(f->table.as<char>() + pr.table_bytes);
+    FILTER_TRY(hipEventRecord(f->ev[2], stream));
+    hipLaunchKernelGGL(kern, grid, dim3(FBX * FBY), lds, stream, pr.img, w, h, s, (int)pr.edges, d_table, (uint32_t)(pr.n_rows * 256), d_map,
+                       ga.depth, ga.normal, ga.idx, ga.inv_depth, ga.inv_normal, dst);
+    FILTER_TRY(hipGetLastError());
+    FILTER_TRY(hipEventRecord(f->ev[3], stream));
+    if (!direct) FILTER_TRY(hipMemcpyAsync(out, dst, pr.n_bytes, hipMemcpyDefault, stream));
+    FILTER_TRY(hipStreamSynchronize(stream));
+    fill_stats(stats, pr, t0);
+    return RTW_OK;
+}
+#undef FILTER_TRY
 
 } // namespace rtw
 
@@ -436,11 +762,13 @@ int bilateral_filter_device(int device, hipStream_t stream, FilterScratch **scra
 static_assert(sizeof(RtwBilateral) == 16 && sizeof(RtwFilterStats) == 32, "POD layout");
 static_assert(offsetof(RtwFilterStats, taps) == 24, "RtwFilterStats has no padding");
 
-extern "C" int rtw_bilateral_filter(const void *in, uint32_t w, uint32_t h, const RtwBilateral *p, uint8_t *out, RtwFilterStats *stats) {
-    using namespace rtw;
+static_assert(sizeof(RtwGuidedFilter) == 28 && offsetof(RtwGuidedFilter, sigma_depth) == 16, "POD layout");
+
+namespace rtw {
+namespace {
+// both host filters after their argument checks; ga == nullptr: the plain one
+int host_filter(const void *in, uint32_t w, uint32_t h, const RtwBilateral *p, const GuideArgs *ga, uint8_t *out, RtwFilterStats *stats) {
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = check_args(in, w, h, p, out);
-    if (rc != RTW_OK) return rc;
     const size_t n_bytes = (size_t)w * h * 3;
     std::vector<uint8_t> quantised;
     const uint8_t *img = (const uint8_t *)in;
@@ -469,9 +797,12 @@ extern "C" int rtw_bilateral_filter(const void *in, uint32_t w, uint32_t h, cons
     std::vector<std::thread> pool;
     for (uint32_t t = 1; t < n_threads; t++) {
         const uint32_t a = std::min(h, t * per), b = std::min(h, a + per);
-        if (a < b) pool.emplace_back(host_filter_rows, img, w, h, p->size, edges, std::cref(pl), table.data(), out, a, b);
+        if (a >= b) continue;
+        if (ga) pool.emplace_back(host_guided_rows_for(ga->terms), img, w, h, p->size, edges, std::cref(pl), table.data(), std::cref(*ga), out, a, b);
+        else pool.emplace_back(host_filter_rows, img, w, h, p->size, edges, std::cref(pl), table.data(), out, a, b);
     }
-    host_filter_rows(img, w, h, p->size, edges, pl, table.data(), out, 0, std::min(h, per));
+    if (ga) host_guided_rows_for(ga->terms)(img, w, h, p->size, edges, pl, table.data(), *ga, out, 0, std::min(h, per));
+    else host_filter_rows(img, w, h, p->size, edges, pl, table.data(), out, 0, std::min(h, per));
     for (std::thread &t : pool) t.join();
     if (stats) {
         stats->avg_gradient = avg;
@@ -483,4 +814,18 @@ extern "C" int rtw_bilateral_filter(const void *in, uint32_t w, uint32_t h, cons
         stats->taps = pl.taps;
     }
     return RTW_OK;
+}
+} // namespace
+} // namespace rtw
+
+extern "C" int rtw_bilateral_filter(const void *in, uint32_t w, uint32_t h, const RtwBilateral *p, uint8_t *out, RtwFilterStats *stats) {
+    const int rc = rtw::check_args(in, w, h, p, out);
+    return rc != RTW_OK ? rc : rtw::host_filter(in, w, h, p, nullptr, out, stats);
+}
+
+extern "C" int rtw_guided_filter(const void *in, uint32_t w, uint32_t h, const float *depth, const float *normal, const int32_t *idx,
+                                 const RtwGuidedFilter *p, uint8_t *out, RtwFilterStats *stats) {
+    rtw::GuideArgs ga;
+    const int rc = rtw::check_guided_args(in, w, h, depth, normal, idx, p, out, ga);
+    return rc != RTW_OK ? rc : rtw::host_filter(in, w, h, &p->base, &ga, out, stats);
 }

@@ -5,6 +5,7 @@
 #include "rtw_host.h"
 #include "rtw_filter.h"
 #include "rtw_devmem.h"
+#include "rtw_exp.h"
 
 #include <link.h>
 
@@ -107,6 +108,7 @@ struct rtw_ctx {
     uint32_t opt_sub_queues = 0;         // RTW_OPT_SUB_QUEUES: 0 = eight sub-queues (one per XCD) for all but tiny launches, 1 = a single queue
     double opt_tail_units = 0.0;         // RTW_OPT_TAIL_UNITS: blocks of short units per resident wave at the end of the queue (render_enqueue); 0 = off.
                                          // OFF by default: measured, it does not shorten a launch (profiles/r03_tail_units.log, r03_endtimes.log)
+    uint32_t opt_guided_layout = 0;      // RTW_OPT_GUIDED_LAYOUT: where rtw_ctx_guided_filter keeps its table and guide tile (0 = by size)
     uint32_t opt_grab_blocks = 2;        // RTW_OPT_GRAB_BLOCKS (profiles/r02_grab_sweep.log: 1 / 2 / 4 / 8 / a tile's 42 blocks = 83.9 / 82.9 / 83.7 / 86.8 / 107.9 ms on the bench frame)
 
     // cache of a per-call driver query (tens of microseconds: visible on small frames)
@@ -358,6 +360,11 @@ int rtw_mixed_pdf(float exp, const float p[3], const float n[3], const float dir
 int rtw_pow_plain(const float *x, const float *y, size_t n, float *out) {
     if (n && (!x || !y || !out)) return RTW_E_INVALID;
     for (size_t i = 0; i < n; i++) out[i] = pow_plain(x[i], y[i]);
+    return RTW_OK;
+}
+int rtw_exp_plain(const float *x, size_t n, float *out) {
+    if (n && (!x || !out)) return RTW_E_INVALID;
+    for (size_t i = 0; i < n; i++) out[i] = exp_plain(x[i]);
     return RTW_OK;
 }
 int rtw_sin_plain(const float *phi, size_t n, float *out) {
@@ -900,6 +907,14 @@ int rtw_ctx_bilateral_filter(rtw_ctx *c, const void *in, uint32_t w, uint32_t h,
     return bilateral_filter_device(c->device, c->stream, &c->filter, in, w, h, p, out, stats, &g_last_hip);
 }
 
+// The guided filter (rtw_filter.hip) likewise.
+int rtw_ctx_guided_filter(rtw_ctx *c, const void *in, uint32_t w, uint32_t h, const float *depth, const float *normal, const int32_t *idx,
+                          const RtwGuidedFilter *p, uint8_t *out, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return guided_filter_device(c->device, c->stream, &c->filter, c->opt_guided_layout, in, w, h, depth, normal, idx, p, out, stats, &g_last_hip);
+}
+
 } // extern "C"
 
 // Copy the compact rows of partition (row_block, part_index, part_count) from `src` (device) to their image rows of the
@@ -1338,6 +1353,7 @@ int rtw_ctx_set_option(rtw_ctx *c, uint32_t key, double v) {
     case RTW_OPT_TILE_ORDER:     if (!(v >= 0.0 && v <= 5.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_tile_order = (uint32_t)v; return RTW_OK;
     case RTW_OPT_SUB_QUEUES:     if (!(v == 0.0 || v == 1.0)) return RTW_E_INVALID; c->opt_sub_queues = (uint32_t)v; return RTW_OK;
     case RTW_OPT_TAIL_UNITS:     if (!(v >= 0.0 && v <= 1024.0)) return RTW_E_INVALID; c->opt_tail_units = v; return RTW_OK;
+    case RTW_OPT_GUIDED_LAYOUT:  if (!(v >= 0.0 && v <= 4.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_guided_layout = (uint32_t)v; return RTW_OK;
     case RTW_OPT_GRAB_BLOCKS:    if (!(v >= 0.0 && v <= 65536.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_grab_blocks = (uint32_t)v; return RTW_OK;
     default: return RTW_E_INVALID;
     }
