@@ -390,6 +390,8 @@ def test_a_constant_density_instance_is_skipped(gpu, geom, accel):
 # ---- 5. range edges ----------------------------------------------------------------------------------------------------------------
 
 def test_range_edges_follow_the_oracle(gpu, oracle):
+    """The range edges through the LIST walk: with one sphere both accel values walk the list (node_tests == 0).  The same edges through the
+    tree, its tie rule at x == maxt included, are test_gpu_query_edges.py's (test_range_edges_through_the_forced_tree)."""
     scene = R.Scene([R.Sphere.new((0.0, 0.0, -5.0), 1.0, (0.5, 0.5, 0.5), R.SCATTER_M)],
                     quads=[R.Quad.new((2.0, -1.0, -7.0), (2.0, 0.0, 0.0), (0.0, 2.0, 0.0))])
     rays = np.array([[0, 0, 0, 0, 0, -1.25],            # the sphere: roots 3.2 and 4.8
@@ -414,8 +416,9 @@ def test_range_edges_follow_the_oracle(gpu, oracle):
         want = oracle_hits(oracle, scene, rays, 0.0, mint, maxt)
         seen.add(tuple(int(i) for i in want[1]))
         for accel in (R.ACCEL_BRUTE, R.ACCEL_BVH):
-            t, idx, nrm, _ = gpu.scene_hits(rays, mint, maxt, accel=accel, normals=True)
+            t, idx, nrm, st = gpu.scene_hits(rays, mint, maxt, accel=accel, normals=True)
             assert_same((t, idx, nrm), want, f"range [{mint!r}, {maxt!r}], accel {accel}")
+            assert st.node_tests == 0
     assert {(0, 1, -1), (-1, 1, -1), (0, -1, -1), (-1, -1, -1)} <= seen          # the edges do flip hits into misses
     far = oracle_hits(oracle, scene, rays, 0.0, cases[5][0], MAXT)
     assert far[1][0] == 0 and far[0][0] == t_far
