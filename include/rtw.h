@@ -700,6 +700,18 @@ int rtw_write_ppm_f32(const char *path, const float *rgb, uint32_t width, uint32
  * contains the f32 boxes, depth within the device stack.  RTW_OK or RTW_E_INVALID; optional outputs describe the tree. */
 int rtw_bvh_validate(const RtwScene *scene, float t_begin, float t_end,
                      uint32_t *n_nodes, uint32_t *depth, uint32_t *n_big, uint32_t *has_f16);
+/* Testing and measuring entry points, not part of the render path: the CPU tests and the builder's yardstick read the tree through them.
+ * The same tree, handed out (no GPU): `nodes` receives n_nodes 64-byte records {lo0[3], hi0[3], lo1[3], hi1[3], c0, c1, pad[2]} with
+ * nodes[0] the root (child >= 0: node, < 0: ~sphere), `nodes16` (optional) the 32-byte f16 records when the tree has them, `big` the
+ * spheres kept outside the tree; depth_cap is the depth the builder allowed itself.  Every output pointer may be NULL. */
+int rtw_bvh_dump(const RtwScene *scene, float t_begin, float t_end, void *nodes, uint32_t node_cap, uint32_t *n_nodes, int32_t *root,
+                 uint32_t *depth, uint32_t *depth_cap, uint32_t *big, uint32_t big_cap, uint32_t *n_big, uint16_t *nodes16);
+/* Host twin of the render kernel's closest-hit query over that tree (a measuring and testing tool, no GPU): rays = n x {origin[3],
+ * direction[3]}; hit[i] = sphere index or -1, t[i] its parameter, visits[i] (optional) the inner-node visits, counted as
+ * RtwStats.node_tests counts them.  use_tree == 0 walks the sphere list with the same sphere test.  The tree is built once per CALL:
+ * pass the rays of a scene in one batch. */
+int rtw_bvh_query_host(const RtwScene *scene, float t_begin, float t_end, const float *rays, uint32_t n, float time, float mint, float maxt,
+                       uint32_t use_tree, int32_t *hit, float *t, uint32_t *visits);
 
 /* Scene generators for the BASELINE configs.  Each fills caller arrays; call with
  * spheres == NULL to query the counts.  Returns RTW_OK or RTW_E_INVALID if capacity is too small. */

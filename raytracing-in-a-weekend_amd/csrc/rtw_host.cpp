@@ -533,53 +533,105 @@ inline float box_area(const Box &b) {
 struct Prim { Box box; float cen[3]; uint32_t sphere; };
 inline uint32_t ceil_log2(uint32_t n) { uint32_t l = 0; while ((1ull << l) < n) l++; return l; }
 
+// The builder works on a pointer tree (leaves first: node i < n_leaves holds prims[i]) and flattens it at the end.
+struct TNode { Box box; int32_t parent, c[2]; uint32_t height; };     // leaf: c[0] < 0, height 0
+
 struct Builder {
     std::vector<Prim> prims;
-    std::vector<BvhNode> nodes;
-    uint32_t max_depth = 0;
+    std::vector<TNode> t;
+    uint32_t cap = RTW_BVH_STACK;      // deepest level a leaf may sit on
+    bool sweep = true;
 
-    // returns child reference (>= 0 node, < 0 ~sphere) and its box
-    int32_t build(uint32_t first, uint32_t count, uint32_t depth, Box &out_box) {
-        max_depth = std::max(max_depth, depth);
-        Box bb; box_empty(bb);
-        for (uint32_t i = first; i < first + count; i++) box_grow(bb, prims[i].box);
-        out_box = bb;
-        if (count == 1) return ~(int32_t)prims[first].sphere;
-
-        // binned SAH over centroids
+    // Top-down SAH.  Returns the pointer-tree node of prims [first, first + count).
+    // Depth bound by construction: a median split of `count` spheres needs ceil(log2(count)) more levels, so the invariant is
+    // depth + ceil(log2(count)) <= cap.  It holds at the root (cap >= ceil(log2(n))) and a median split keeps it; a SAH split may
+    // leave count - 1 spheres on one side: the sweep prices only the splits whose two sides keep the invariant (the median is always
+    // one of them), the binned search is only tried when even a count - 1 child keeps it.  (Geometrically spaced spheres used to reach depth 27 under the old "SAH until depth 20" rule and
+    // overflowed the device stack.)
+    int32_t build(uint32_t first, uint32_t count, uint32_t depth) {
+        if (count == 1) return (int32_t)first;
         Box cb; box_empty(cb);
         for (uint32_t i = first; i < first + count; i++)
             for (int k = 0; k < 3; k++) { cb.lo[k] = std::min(cb.lo[k], prims[i].cen[k]); cb.hi[k] = std::max(cb.hi[k], prims[i].cen[k]); }
         uint32_t mid = first + count / 2;
+        int best_axis = -1;
+        if (sweep) best_axis = split_sweep(first, count, depth, mid);
+        else if (depth + 1 + ceil_log2(count - 1) <= cap) best_axis = split_binned(first, count, cb, mid);
+        if (best_axis < 0 || mid == first || mid == first + count) {
+            // median split on the widest centroid axis (also the depth-limit fallback)
+            int ax = 0;
+            for (int k = 1; k < 3; k++) if (cb.hi[k] - cb.lo[k] > cb.hi[ax] - cb.lo[ax]) ax = k;
+            mid = first + count / 2;
+            std::nth_element(prims.begin() + first, prims.begin() + mid, prims.begin() + first + count,
+                             [&](const Prim &a, const Prim &b) { return a.cen[ax] != b.cen[ax] ? a.cen[ax] < b.cen[ax] : a.sphere < b.sphere; });
+        }
+        const int32_t me = (int32_t)t.size();
+        t.push_back(TNode{});
+        const int32_t c0 = build(first, mid - first, depth + 1);
+        const int32_t c1 = build(mid, first + count - mid, depth + 1);
+        t[me].c[0] = c0; t[me].c[1] = c1; t[me].parent = -1;
+        t[c0].parent = t[c1].parent = me;
+        refit(me);
+        return me;
+    }
+    void refit(int32_t i) {
+        TNode &n = t[i];
+        n.box = t[n.c[0]].box; box_grow(n.box, t[n.c[1]].box);
+        n.height = 1u + std::max(t[n.c[0]].height, t[n.c[1]].height);
+    }
+
+    // (a) SAH over the primitive boxes by a full sweep along all three axes: every one of the count - 1 splits of the
+    // centroid order is priced with area(left) * n_left + area(right) * n_right.  (Single-sphere leaves: the leaf term of the
+    // two-term cost, area(sphere box) x the cost of a leaf test, is the same for every tree over the same spheres.)
+    int split_sweep(uint32_t first, uint32_t count, uint32_t depth, uint32_t &mid) {
+        int best_axis = -1; double best_cost = std::numeric_limits<double>::infinity(); uint32_t best_k = 0;
+        std::vector<double> right(count);
+        for (int ax = 0; ax < 3; ax++) {
+            std::sort(prims.begin() + first, prims.begin() + first + count,
+                      [&](const Prim &a, const Prim &b) { return a.cen[ax] != b.cen[ax] ? a.cen[ax] < b.cen[ax] : a.sphere < b.sphere; });
+            Box acc; box_empty(acc);
+            for (uint32_t k = count - 1; k > 0; k--) { box_grow(acc, prims[first + k].box); right[k] = box_area_d(acc); }
+            box_empty(acc);
+            for (uint32_t k = 1; k < count; k++) {            // left = [0, k), right = [k, count)
+                box_grow(acc, prims[first + k - 1].box);
+                // both sides must keep the depth invariant
+                if (depth + 1 + ceil_log2(std::max(k, count - k)) > cap) continue;
+                const double cost = box_area_d(acc) * (double)k + right[k] * (double)(count - k);
+                if (cost < best_cost) { best_cost = cost; best_axis = ax; best_k = k; }
+            }
+        }
+        if (best_axis < 0) return -1;
+        if (best_axis != 2)
+            std::sort(prims.begin() + first, prims.begin() + first + count,
+                      [&](const Prim &a, const Prim &b) { return a.cen[best_axis] != b.cen[best_axis] ? a.cen[best_axis] < b.cen[best_axis] : a.sphere < b.sphere; });
+        mid = first + best_k;
+        return best_axis;
+    }
+
+    // The earlier split search, 16-bin centroid SAH: the builder of scenes above RTW_BVH_OPTIMISE_MAX, and what `scripts/sim/wave_sim visits` prices the new tree against.
+    int split_binned(uint32_t first, uint32_t count, const Box &cb, uint32_t &mid) {
         int best_axis = -1; float best_cost = FLT_MAX; float best_split = 0.0f;
         const int NB = 16;
-        // Depth bound by construction (rtw_host.h: depth <= RTW_BVH_STACK): a median split of `count` spheres needs
-        // ceil(log2(count)) more levels, so the invariant is  depth + ceil(log2(count)) <= RTW_BVH_STACK.  It holds at the root
-        // (count <= 2^24) and a median split keeps it; a SAH split may leave count - 1 spheres on one side, so SAH is only tried
-        // when even that child keeps the invariant.  (Geometrically spaced spheres used to reach depth 27 under the old
-        // "SAH until depth 20" rule and overflowed the device stack.)
-        if (depth + 1 + ceil_log2(count - 1) <= RTW_BVH_STACK) {
-            for (int ax = 0; ax < 3; ax++) {
-                float ext = cb.hi[ax] - cb.lo[ax];
-                if (!(ext > 0.0f)) continue;
-                Box bins[NB]; uint32_t cnt[NB];
-                for (int b = 0; b < NB; b++) { box_empty(bins[b]); cnt[b] = 0; }
-                for (uint32_t i = first; i < first + count; i++) {
-                    // (clamped BEFORE the conversion: non-finite centres make this NaN or +-inf, and float -> int of those is undefined)
-                    const float fb = (prims[i].cen[ax] - cb.lo[ax]) / ext * NB;
-                    const int b = fb >= 0.0f ? (fb < (float)NB ? (int)fb : NB - 1) : 0;
-                    box_grow(bins[b], prims[i].box); cnt[b]++;
-                }
-                float right_area[NB]; uint32_t right_cnt[NB];
-                Box acc; box_empty(acc); uint32_t c = 0;
-                for (int b = NB - 1; b > 0; b--) { box_grow(acc, bins[b]); c += cnt[b]; right_area[b] = c ? box_area(acc) : 0.0f; right_cnt[b] = c; }
-                box_empty(acc); c = 0;
-                for (int b = 0; b < NB - 1; b++) {
-                    box_grow(acc, bins[b]); c += cnt[b];
-                    if (c == 0 || right_cnt[b + 1] == 0) continue;
-                    float cost = box_area(acc) * (float)c + right_area[b + 1] * (float)right_cnt[b + 1];
-                    if (cost < best_cost) { best_cost = cost; best_axis = ax; best_split = cb.lo[ax] + ext * (float)(b + 1) / NB; }
-                }
+        for (int ax = 0; ax < 3; ax++) {
+            float ext = cb.hi[ax] - cb.lo[ax];
+            if (!(ext > 0.0f)) continue;
+            Box bins[NB]; uint32_t cnt[NB];
+            for (int b = 0; b < NB; b++) { box_empty(bins[b]); cnt[b] = 0; }
+            for (uint32_t i = first; i < first + count; i++) {
+                // (clamped BEFORE the conversion: non-finite centres make this NaN or +-inf, and float -> int of those is undefined)
+                const float fb = (prims[i].cen[ax] - cb.lo[ax]) / ext * NB;
+                const int b = fb >= 0.0f ? (fb < (float)NB ? (int)fb : NB - 1) : 0;
+                box_grow(bins[b], prims[i].box); cnt[b]++;
+            }
+            float right_area[NB]; uint32_t right_cnt[NB];
+            Box acc; box_empty(acc); uint32_t c = 0;
+            for (int b = NB - 1; b > 0; b--) { box_grow(acc, bins[b]); c += cnt[b]; right_area[b] = c ? box_area(acc) : 0.0f; right_cnt[b] = c; }
+            box_empty(acc); c = 0;
+            for (int b = 0; b < NB - 1; b++) {
+                box_grow(acc, bins[b]); c += cnt[b];
+                if (c == 0 || right_cnt[b + 1] == 0) continue;
+                float cost = box_area(acc) * (float)c + right_area[b + 1] * (float)right_cnt[b + 1];
+                if (cost < best_cost) { best_cost = cost; best_axis = ax; best_split = cb.lo[ax] + ext * (float)(b + 1) / NB; }
             }
         }
         if (best_axis >= 0) {
@@ -587,20 +639,92 @@ struct Builder {
                                      [&](const Prim &p) { return p.cen[best_axis] < best_split; });
             mid = (uint32_t)(it - prims.begin());
         }
-        if (best_axis < 0 || mid == first || mid == first + count) {
-            // median split on the widest centroid axis (also the depth-limit fallback)
-            int ax = 0;
-            for (int k = 1; k < 3; k++) if (cb.hi[k] - cb.lo[k] > cb.hi[ax] - cb.lo[ax]) ax = k;
-            mid = first + count / 2;
-            std::nth_element(prims.begin() + first, prims.begin() + mid, prims.begin() + first + count,
-                             [&](const Prim &a, const Prim &b) { return a.cen[ax] < b.cen[ax]; });
+        return best_axis;
+    }
+
+    static double box_area_d(const Box &b) {
+        const double dx = (double)b.hi[0] - b.lo[0], dy = (double)b.hi[1] - b.lo[1], dz = (double)b.hi[2] - b.lo[2];
+        return 2.0 * (dx * dy + dy * dz + dz * dx);
+    }
+    static double union_area(const Box &a, const Box &b) { Box u = a; box_grow(u, b); return box_area_d(u); }
+
+    // (b) Subtree reinsertion (Bittner, Hapala, Havran: "Fast insertion-based optimization of bounding volume hierarchies", CGF 2013).
+    // Under the surface-area model a query visits an inner node with a probability proportional to its box's area, and with
+    // single-sphere leaves the leaf tests do not depend on the tree, so the quantity to minimise is the SUM OF THE INNER NODES' AREAS.
+    // One move: take a subtree L out (its parent P goes with it, the sibling S takes P's place, the ancestors shrink), then put P back
+    // above the node X for which the area added -- area(X u L) for P plus the growth of X's ancestors -- is least, found by a bounded
+    // depth-first search from the root (a branch is left as soon as the growth already charged plus area(L) reaches the best known).
+    // The move is kept only when it beats putting L back where it was; S is always a legal X, so the total never rises and every kept
+    // move lowers it: the passes end.  A position counts only if it keeps every leaf at depth <= cap.
+    // Cost: set_scene is on the caller's path, so the pass has a WORK BUDGET of RTW_BVH_REINSERT_WORK search steps per tree node (a step
+    // is one node taken off the search stack); the branch-and-bound prunes well on real scenes (the bench scene uses a fraction of it)
+    // and not at all where the boxes coincide, and there the budget ends the pass with a valid, merely less optimised, tree.
+    void reinsertion(int32_t &root) {
+        const uint32_t nl = (uint32_t)prims.size();
+        std::vector<int32_t> order;
+        std::vector<char> above_s(t.size(), 0);
+        struct Item { int32_t x; double acc; uint32_t depth; };
+        std::vector<Item> todo;
+        std::vector<double> area(t.size());
+        uint64_t work = (uint64_t)RTW_BVH_REINSERT_WORK * t.size();
+        for (int pass = 0; pass < 64 && work; pass++) {
+            bool improved = false;
+            order.clear();
+            for (int32_t i = 0; i < (int32_t)t.size(); i++) if (i != root && t[i].parent != root) order.push_back(i);
+            // (non-finite spheres: nothing to optimise, the shim walks the list; std::min / std::max keep a NaN out of an ancestor's box, so
+            //  every node is looked at -- the order below needs finite keys)
+            for (size_t i = 0; i < t.size(); i++) { area[i] = box_area_d(t[i].box); if (!std::isfinite(area[i])) return; }
+            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return area[a] > area[b]; });
+            for (int32_t L : order) {
+                const int32_t P = t[L].parent;
+                if (P < 0 || P == root) continue;                  // (the tree moved under us during this pass)
+                if (!work) break;
+                const int32_t G = t[P].parent, S = t[P].c[0] == L ? t[P].c[1] : t[P].c[0];
+                // take L (and P) out
+                t[G].c[t[G].c[0] == P ? 0 : 1] = S; t[S].parent = G;
+                for (int32_t a = G; a >= 0; a = t[a].parent) refit(a);
+                for (int32_t a = S; a >= 0; a = t[a].parent) above_s[a] = 1;     // S and its ancestors: always searched, so that at_s is known
+                const Box &lb = t[L].box; const double la = box_area_d(lb);
+                double best = std::numeric_limits<double>::infinity(), at_s = best; int32_t best_x = -1;
+                todo.assign(1, Item{ root, 0.0, 0u });
+                while (!todo.empty()) {
+                    const Item it = todo.back(); todo.pop_back();
+                    if (!(it.acc + la < best) && !above_s[it.x]) continue;
+                    if (work) work--; else if (!above_s[it.x]) continue;       // (out of budget: only the way down to S is finished)
+                    const double direct = union_area(t[it.x].box, lb), total = it.acc + direct;
+                    if (it.x == S) at_s = total;
+                    const bool fits = it.depth + 1 + std::max(t[it.x].height, t[L].height) <= cap;
+                    if (fits && total < best) { best = total; best_x = it.x; }
+                    if ((uint32_t)it.x >= nl) {
+                        const double acc = it.acc + (direct - box_area_d(t[it.x].box));
+                        const int32_t a = t[it.x].c[0], b = t[it.x].c[1];
+                        const bool a_first = union_area(t[a].box, lb) <= union_area(t[b].box, lb);
+                        todo.push_back(Item{ a_first ? b : a, acc, it.depth + 1 }); todo.push_back(Item{ a_first ? a : b, acc, it.depth + 1 });   // (the likelier child comes off first)
+                    }
+                }
+                for (int32_t a = S; a >= 0; a = t[a].parent) above_s[a] = 0;
+                int32_t X = S;
+                if (best_x >= 0 && best_x != S && best < at_s * (1.0 - 1e-12)) { X = best_x; improved = true; }
+                // put P back above X
+                const int32_t XP = t[X].parent;
+                t[P].c[0] = X; t[P].c[1] = L; t[P].parent = XP; t[X].parent = P; t[L].parent = P;
+                if (XP >= 0) t[XP].c[t[XP].c[0] == X ? 0 : 1] = P; else root = P;
+                for (int32_t a = P; a >= 0; a = t[a].parent) refit(a);
+            }
+            if (!improved) break;
         }
-        uint32_t me = (uint32_t)nodes.size();
+    }
+
+    // pre-order flattening: nodes[0] is the root, each parent stores its children's boxes
+    int32_t flatten(int32_t i, uint32_t depth, std::vector<BvhNode> &nodes, uint32_t &max_depth) {
+        max_depth = std::max(max_depth, depth);
+        if ((uint32_t)i < prims.size()) return ~(int32_t)prims[i].sphere;
+        const uint32_t me = (uint32_t)nodes.size();
         nodes.push_back(BvhNode{});
-        Box b0, b1;
-        int32_t c0 = build(first, mid - first, depth + 1, b0);
-        int32_t c1 = build(mid, first + count - mid, depth + 1, b1);
+        const int32_t c0 = flatten(t[i].c[0], depth + 1, nodes, max_depth);
+        const int32_t c1 = flatten(t[i].c[1], depth + 1, nodes, max_depth);
         BvhNode &n = nodes[me];
+        const Box &b0 = t[t[i].c[0]].box, &b1 = t[t[i].c[1]].box;
         for (int k = 0; k < 3; k++) { n.lo0[k] = b0.lo[k]; n.hi0[k] = b0.hi[k]; n.lo1[k] = b1.lo[k]; n.hi1[k] = b1.hi[k]; }
         n.c0 = c0; n.c1 = c1; n.pad[0] = n.pad[1] = 0;
         return (int32_t)me;
@@ -625,11 +749,34 @@ uint16_t half_bits(float f, bool up) {
 }
 } // namespace
 
-void build_bvh(const RtwSphere *spheres, uint32_t n, float t_begin, float t_end, BvhBuild &out) {
+// Deepest level a leaf may sit on.  A tree that can live in LDS as f16 nodes shares the workgroup's LDS with the per-lane stack:
+// nodes * 32 + (depth + 3) * RTW_BLOCK * 2 bytes (rtw_shim.hip), and the render kernel keeps seven workgroups on a CU only while that
+// stays within a seventh of its 160 KiB -- one level too many costs the seventh workgroup (profiles/r03_ab_tau_lds.log).  So the cap is the
+// deepest tree that still fits that share, never above the device stack and never below what a balanced tree of n leaves needs.
+// The shim also puts the scene's sphere geometry (n_spheres * 16 bytes, big spheres included) behind the stack while the whole stays
+// within a SIXTH of the CU's LDS: where a balanced tree leaves room for it, the cap keeps that room too, so that a deeper tree never
+// pushes the geometry out.  (The stack has at least four levels, which only matters below depth 1.)
+uint32_t bvh_depth_cap(uint32_t n_leaves, uint32_t n_spheres, bool lds_candidate) {
+    uint32_t cap = RTW_BVH_STACK;
+    const uint32_t balanced = ceil_log2(std::max(n_leaves, 1u));
+    if (lds_candidate && n_leaves >= 2) {
+        const uint32_t node_bytes = ((n_leaves - 1u) * 32u + 15u) & ~15u, level_bytes = RTW_BVH_LDS_LEVEL_BYTES;
+        auto deepest = [&](uint32_t share, uint32_t fixed) {       // depth d with fixed + (d + 3) * level_bytes <= share, or 0
+            const uint32_t levels = share > fixed ? (share - fixed) / level_bytes : 0u;
+            return levels > 3u ? levels - 3u : 0u;
+        };
+        cap = std::min(cap, deepest(160u * 1024u / 7u, node_bytes));
+        const uint32_t with_geom = deepest(160u * 1024u / 6u, node_bytes + n_spheres * 16u);
+        if (with_geom >= balanced) cap = std::min(cap, with_geom);
+    }
+    return std::max(cap, balanced);
+}
+
+void build_bvh(const RtwSphere *spheres, uint32_t n, float t_begin, float t_end, BvhBuild &out, const BvhBuildOptions &opt) {
     out.nodes.clear(); out.nodes16.clear(); out.big.clear();
     out.root = std::numeric_limits<int32_t>::min();
     out.centre[0] = out.centre[1] = out.centre[2] = 0.0f;
-    out.centre_radius = 0.0f; out.r_min = 0.0f; out.r_max = 0.0f; out.abs_max = 0.0f; out.depth = 0;
+    out.centre_radius = 0.0f; out.r_min = 0.0f; out.r_max = 0.0f; out.abs_max = 0.0f; out.depth = 0; out.depth_cap = RTW_BVH_STACK;
     if (n == 0) return;
 
     // "big" spheres: radius >= 16 x the median radius, at most RTW_MAX_BIG of them (largest first)
@@ -666,6 +813,7 @@ void build_bvh(const RtwSphere *spheres, uint32_t n, float t_begin, float t_end,
             if (!(lo == lo) || !(hi == hi)) { lo = -FLT_MAX; hi = FLT_MAX; }
             centres.lo[k] = std::min(centres.lo[k], lo); centres.hi[k] = std::max(centres.hi[k], hi);
             p.cen[k] = 0.5f * lo + 0.5f * hi;
+            if (!std::isfinite(p.cen[k])) p.cen[k] = 0.0f;     // (-inf + inf: the comparators below need a strict weak order)
             p.box.lo[k] = std::nextafter(lo - radii[i], -FLT_MAX);
             p.box.hi[k] = std::nextafter(hi + radii[i], FLT_MAX);
         }
@@ -673,10 +821,26 @@ void build_bvh(const RtwSphere *spheres, uint32_t n, float t_begin, float t_end,
         b.prims.push_back(p);
     }
     if (b.prims.empty()) return;
-    Box root_box;
-    out.root = b.build(0, (uint32_t)b.prims.size(), 0, root_box);
-    out.nodes.swap(b.nodes);
-    out.depth = b.max_depth;
+    const uint32_t nl = (uint32_t)b.prims.size();
+    Box root_box; box_empty(root_box);
+    for (const Prim &p : b.prims) box_grow(root_box, p.box);
+    float box_abs = 0.0f;
+    for (int k = 0; k < 3; k++) box_abs = std::max(box_abs, std::max(std::fabs(root_box.lo[k]), std::fabs(root_box.hi[k])));
+    // (the same three conditions as the f16 copy below, known before the tree is)
+    const bool lds_candidate = nl >= 2 && nl - 1 <= RTW_LDS_NODES_MAX && n <= RTW_LDS_GEOM_MAX && box_abs < 30000.0f;
+    b.cap = out.depth_cap = opt.depth_cap ? std::max(opt.depth_cap, ceil_log2(nl)) : bvh_depth_cap(nl, n, lds_candidate);
+    b.sweep = opt.sweep && nl <= RTW_BVH_OPTIMISE_MAX;
+    b.t.resize(nl);
+    for (uint32_t i = 0; i < nl; i++) { b.t[i].box = b.prims[i].box; b.t[i].parent = -1; b.t[i].c[0] = b.t[i].c[1] = -1; b.t[i].height = 0; }
+    b.t.reserve(2 * (size_t)nl);
+    int32_t troot = b.build(0, nl, 0);
+    // (build() permutes prims while it recurses, but a leaf's id is its final position, which is fixed once its range has one member:
+    //  the boxes copied above are those of the unpermuted order and are set again here)
+    for (uint32_t i = 0; i < nl; i++) b.t[i].box = b.prims[i].box;
+    for (int32_t i = (int32_t)b.t.size() - 1; i >= (int32_t)nl; i--) b.refit(i);      // (children are created after their parent: bottom-up)
+    if (opt.reinsert && nl > 2 && nl <= RTW_BVH_OPTIMISE_MAX) b.reinsertion(troot);
+    out.nodes.reserve(nl - 1);
+    out.root = b.flatten(troot, 0, out.nodes, out.depth);
     double r2 = 0.0;
     for (int k = 0; k < 3; k++) {
         out.centre[k] = 0.5f * centres.lo[k] + 0.5f * centres.hi[k];
@@ -705,6 +869,110 @@ void build_bvh(const RtwSphere *spheres, uint32_t n, float t_begin, float t_end,
 }
 
 } // namespace rtw
+
+// ---- host twin of the device query -------------------------------------------------------------------------------------------
+namespace rtw {
+namespace {
+inline float half_value(uint16_t x) { _Float16 v; std::memcpy(&v, &x, 2); return (float)v; }
+inline void host_sphere(const RtwSphere &s, uint32_t idx, const float o[3], const float d[3], float tm, float a, float mint, float maxt, int32_t &best, float &best_t) {
+    float oc[3];
+    for (int k = 0; k < 3; k++) oc[k] = o[k] - (s.center[k] + s.velocity[k] * tm);
+    const float b = oc[0] * d[0] + oc[1] * d[1] + oc[2] * d[2], c = (oc[0] * oc[0] + oc[1] * oc[1] + oc[2] * oc[2]) - s.radius * s.radius;
+    const float disc = b * b - a * c;
+    if (!(disc >= 0.0f)) return;
+    const float sq = std::sqrt(disc);
+    float x = (-b - sq) / a;
+    if (x < mint || x > maxt) x = (-b + sq) / a;
+    if (x < mint || x > maxt) return;
+    if (best < 0 || x < best_t || (x == best_t && (int32_t)idx < best)) { best = (int32_t)idx; best_t = x; }
+}
+} // namespace
+
+HostHit bvh_closest_host(const BvhBuild &bb, const RtwSphere *spheres, uint32_t n, const float o[3], const float d[3], float tm,
+                         float mint, float maxt, bool use_tree, std::string *ops) {
+    HostHit h; h.sphere = -1; h.t = maxt; h.node_visits = h.leaf_tests = 0;
+    const float a = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    if (!use_tree) { for (uint32_t i = 0; i < n; i++) host_sphere(spheres[i], i, o, d, tm, a, mint, maxt, h.sphere, h.t); return h; }
+    for (uint32_t i : bb.big) host_sphere(spheres[i], i, o, d, tm, a, mint, maxt, h.sphere, h.t);
+    if (bb.root == std::numeric_limits<int32_t>::min()) return h;
+    // per-ray constants: trav_begin (rtw_kernels.hip), with the correctly rounded root and reciprocals in place of the hardware's
+    const float M = (std::fabs(o[0] - bb.centre[0]) + std::fabs(o[1] - bb.centre[1]) + std::fabs(o[2] - bb.centre[2])) * 1.0001f + bb.centre_radius;
+    const float q = (M * M + bb.r_max * bb.r_max) * 1.4305115e-6f;
+    const float sq_q = std::sqrt(q) * 1.0001f;
+    float rho = std::fmin(q * (bb.r_min > 0.0f ? 1.0f / (2.0f * bb.r_min) : FLT_MAX), sq_q);
+    rho = rho * 1.0001f + 4.8e-7f * (std::fabs(o[0]) + std::fabs(o[1]) + std::fabs(o[2]) + bb.abs_max);
+    const float tau = sq_q * 1.0002f / std::sqrt(a) + 1e-30f;
+    float inv[3], kp[3], km[3];
+    for (int k = 0; k < 3; k++) {
+        inv[k] = std::fabs(d[k]) >= 1e-20f ? 1.0f / d[k] : std::copysign(1e20f, d[k]);
+        kp[k] = -(o[k] + rho) * inv[k]; km[k] = -(o[k] - rho) * inv[k];
+    }
+    const float lo_lim = mint - tau;
+    const bool f16 = !bb.nodes16.empty();
+    std::vector<int32_t> stack; stack.reserve(RTW_BVH_STACK + 2);
+    int32_t node = bb.root;
+    for (;;) {
+        if (node >= 0) {
+            h.node_visits++; if (ops) ops->push_back('N');
+            const BvhNode &nd = bb.nodes[(size_t)node];
+            float e[2], x[2];
+            for (int c = 0; c < 2; c++) {
+                e[c] = -FLT_MAX; x[c] = FLT_MAX;
+                for (int k = 0; k < 3; k++) {
+                    const float lo = f16 ? half_value(bb.nodes16[(size_t)node].plane[c][k][0]) : (c ? nd.lo1[k] : nd.lo0[k]);
+                    const float hi = f16 ? half_value(bb.nodes16[(size_t)node].plane[c][k][1]) : (c ? nd.hi1[k] : nd.hi0[k]);
+                    const float t1 = std::fma(lo, inv[k], kp[k]), t2 = std::fma(hi, inv[k], km[k]);
+                    e[c] = std::fmax(e[c], std::fmin(t1, t2)); x[c] = std::fmin(x[c], std::fmax(t1, t2));
+                }
+            }
+            const float hi_lim = h.t + tau;
+            const float m0 = std::fmax(e[0], lo_lim), m1 = std::fmax(e[1], lo_lim);
+            const bool h0 = m0 <= std::fmin(x[0], hi_lim), h1 = m1 <= std::fmin(x[1], hi_lim);
+            if (h0 && h1) { const bool near0 = m0 <= m1; stack.push_back(near0 ? nd.c1 : nd.c0); node = near0 ? nd.c0 : nd.c1; continue; }
+            if (h0 || h1) { node = h0 ? nd.c0 : nd.c1; continue; }
+        } else {
+            h.leaf_tests++; if (ops) ops->push_back('L');
+            const uint32_t s = (uint32_t)~node;
+            if (s < n) host_sphere(spheres[s], s, o, d, tm, a, mint, maxt, h.sphere, h.t);
+        }
+        if (stack.empty()) break;
+        node = stack.back(); stack.pop_back();
+    }
+    return h;
+}
+} // namespace rtw
+
+// Exposed for the CPU tests: the tree rtw_ctx_set_scene would build, and the host twin of the device
+// query over it.  rays: n x {origin, direction}; hit / t / visits: n each (visits may be NULL).  use_tree == 0 walks the list.
+extern "C" int rtw_bvh_dump(const RtwScene *sc, float t_begin, float t_end, void *nodes, uint32_t node_cap, uint32_t *n_nodes, int32_t *root,
+                            uint32_t *depth, uint32_t *depth_cap, uint32_t *big, uint32_t big_cap, uint32_t *n_big, uint16_t *nodes16) {
+    using namespace rtw;
+    if (!sc || (sc->n_spheres && !sc->spheres)) return RTW_E_INVALID;
+    BvhBuild b;
+    build_bvh(sc->spheres, sc->n_spheres, t_begin, t_end, b);
+    if (n_nodes) *n_nodes = (uint32_t)b.nodes.size();
+    if (root) *root = b.root;
+    if (depth) *depth = b.depth;
+    if (depth_cap) *depth_cap = b.depth_cap;
+    if (n_big) *n_big = (uint32_t)b.big.size();
+    if (nodes) { if (node_cap < b.nodes.size()) return RTW_E_INVALID; std::memcpy(nodes, b.nodes.data(), b.nodes.size() * sizeof(BvhNode)); }
+    if (big) { if (big_cap < b.big.size()) return RTW_E_INVALID; std::copy(b.big.begin(), b.big.end(), big); }
+    if (nodes16 && !b.nodes16.empty()) { if (node_cap < b.nodes16.size()) return RTW_E_INVALID; std::memcpy(nodes16, b.nodes16.data(), b.nodes16.size() * sizeof(BvhNode16)); }
+    return RTW_OK;
+}
+
+extern "C" int rtw_bvh_query_host(const RtwScene *sc, float t_begin, float t_end, const float *rays, uint32_t n, float time, float mint, float maxt,
+                                  uint32_t use_tree, int32_t *hit, float *t, uint32_t *visits) {
+    using namespace rtw;
+    if (!sc || (sc->n_spheres && !sc->spheres) || (n && (!rays || !hit || !t))) return RTW_E_INVALID;
+    BvhBuild b;
+    if (use_tree) build_bvh(sc->spheres, sc->n_spheres, t_begin, t_end, b);
+    for (uint32_t i = 0; i < n; i++) {
+        const HostHit h = bvh_closest_host(b, sc->spheres, sc->n_spheres, rays + 6 * (size_t)i, rays + 6 * (size_t)i + 3, time, mint, maxt, use_tree != 0);
+        hit[i] = h.sphere; t[i] = h.t; if (visits) visits[i] = h.node_visits;
+    }
+    return RTW_OK;
+}
 
 // ---- queue order of the tiles ------------------------------------------------------------------------------------------------
 namespace rtw {

@@ -2,6 +2,7 @@
 // Scene::new_sphere's acceleration build) and the BASELINE scene generators.  Pure host code.
 #pragma once
 #include <cstdint>
+#include <string>
 #include <vector>
 #include "rtw.h"
 
@@ -40,6 +41,12 @@ static_assert(sizeof(BvhNode16) == 32, "BvhNode16 must be 32 bytes");
 
 #define RTW_MAX_BIG 16        // spheres far larger than the rest are tested exactly, outside the tree
 #define RTW_BVH_STACK 24      // builder guarantees depth <= RTW_BVH_STACK (median-split fallback near the limit)
+#define RTW_BVH_LDS_LEVEL_BYTES 512u   // one level of the LDS-variant's per-lane stack: RTW_BLOCK (256) lanes x a 16-bit entry
+#define RTW_BVH_OPTIMISE_MAX 1024u     // tree spheres up to which the builder sweeps every split (n log n per level) and runs the reinsertion pass.
+                                       // Larger scenes get the binned top-down tree alone.
+#ifndef RTW_BVH_REINSERT_WORK
+#define RTW_BVH_REINSERT_WORK 128u     // the reinsertion pass's work budget: search steps per tree node (set_scene is on the caller's path)
+#endif
 
 struct BvhBuild {
     std::vector<BvhNode> nodes;          // nodes[0] is the root (absent when < 2 tree spheres)
@@ -52,11 +59,33 @@ struct BvhBuild {
     float r_min, r_max;                  // radius range of the tree spheres
     float abs_max;                       // largest |coordinate| of any tree box
     uint32_t depth;
+    uint32_t depth_cap;                  // the deepest level the builder allowed itself for this scene (bvh_depth_cap, or the caller's)
 };
+
+// How build_bvh builds.  The defaults are the product's; the others exist so that `scripts/sim/wave_sim visits` can price the alternatives.
+struct BvhBuildOptions {
+    bool sweep = true;                   // full-sweep SAH over all three axes (false: the 16-bin centroid SAH of the earlier builder)
+    bool reinsert = true;                // subtree-reinsertion pass over the finished tree
+    uint32_t depth_cap = 0;              // 0: bvh_depth_cap()
+};
+// The deepest level a leaf may sit on: for a tree that may live in LDS, the deepest at which the f16 nodes plus the per-lane stack
+// still fit a seventh of a CU's LDS (the render kernel's seven workgroups per CU) and, where the shim would also keep the scene's
+// n_spheres x 16 bytes of sphere geometry in LDS for a balanced tree (its sixth-of-a-CU rule), the deepest at which it still does;
+// RTW_BVH_STACK otherwise; never less than a balanced tree needs.
+uint32_t bvh_depth_cap(uint32_t n_leaves, uint32_t n_spheres, bool lds_candidate);
 
 // Bounds cover centre(t) = origin + velocity * t for t in [t_begin, t_end] (sphere.rs:100); the
 // reference's own AABB ignores velocity (aabb/aabb.rs:27-39) and so culls moving spheres wrongly.
-void build_bvh(const RtwSphere *spheres, uint32_t n, float t_begin, float t_end, BvhBuild &out);
+void build_bvh(const RtwSphere *spheres, uint32_t n, float t_begin, float t_end, BvhBuild &out, const BvhBuildOptions &opt = BvhBuildOptions());
+
+// Host twin of the render kernel's closest-hit query over a built tree (a measuring and testing tool: the product traverses on the
+// GPU).  Same order of events: the big list first, per-ray rho / tau, boxes inflated by rho, the f16 outward-rounded planes when the
+// tree has them, the nearer child first (ties: child 0), pruning against best_t + tau; `node_visits` counts what RtwStats.node_tests
+// counts.  The sphere test is a plain f32 quadratic with ties to the lower index, the same one `use_tree = false` walks the list with.
+struct HostHit { int32_t sphere; float t; uint32_t node_visits, leaf_tests; };
+HostHit bvh_closest_host(const BvhBuild &bb, const RtwSphere *spheres, uint32_t n, const float o[3], const float d[3], float time,
+                         float mint, float maxt, bool use_tree, std::string *ops = nullptr);
+
 
 // ---- queue order of the 8x8 tiles (RTW_OPT_TILE_ORDER) -------------------------------------------------------------------
 // What the ordering heuristic may know about the scene: the spheres kept outside the tree (the ground) and the root box of

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <random>
 #include <string>
 #include <vector>
@@ -40,46 +41,19 @@ static bool hit_sphere(const RtwSphere &s, V o, V d, float mint, float maxt, flo
     if (x < mint || x > maxt) return false;
     t = x; return true;
 }
-static bool hit_box(const float *lo, const float *hi, V o, V inv, float tmin, float tmax, float &entry) {
-    float t0 = tmin, t1 = tmax;
-    const float oo[3] = { o.x, o.y, o.z }, ii[3] = { inv.x, inv.y, inv.z };
-    for (int k = 0; k < 3; k++) {
-        float a = (lo[k] - oo[k]) * ii[k], b = (hi[k] - oo[k]) * ii[k];
-        if (a > b) std::swap(a, b);
-        t0 = std::max(t0, a); t1 = std::min(t1, b);
-    }
-    entry = t0;
-    return t0 <= t1;
-}
-
-// One closest-hit query; `ops` receives 'N' per inner-node visit and 'L' per leaf test, in execution order.
+// One closest-hit query; `ops` receives 'N' per inner-node visit and 'L' per leaf test, in execution order.  The walk is the product's
+// host twin of the device query (bvh_closest_host, rtw_host.cpp): rho / tau paddings, f16 planes, near child first, the big list first.
+// (Every mode walks with it.  The figures of profiles/r02_lane_utilisation.md were taken with the plain f32-box walk this replaced, over the 16-bin
+//  tree: today's runs of those modes see ~1 % more visits per query from the paddings and a different tree, and do not reproduce them digit for digit.)
+struct Seg { float o[3], d[3]; };
+static std::vector<Seg> *g_record = nullptr;          // when set, every query's ray is kept (the `visits` yardstick)
 static int closest(const Scene &S, V o, V d, float &best_t, std::string &ops) {
-    const float mint = 0.001f;
-    int best = -1; best_t = 1e5f;
-    for (uint32_t i : S.bvh.big) { float t; if (hit_sphere(S.sp[i], o, d, mint, best_t, t) && t < best_t) { best_t = t; best = (int)i; } }
-    if (S.bvh.root == std::numeric_limits<int32_t>::min()) return best;
-    V inv = { 1.0f / d.x, 1.0f / d.y, 1.0f / d.z };
-    int32_t stack[64]; int sp = 0; int32_t node = S.bvh.root;
-    for (;;) {
-        if (node >= 0) {
-            ops.push_back('N');
-            const BvhNode &n = S.bvh.nodes[node];
-            float e0, e1;
-            bool h0 = hit_box(n.lo0, n.hi0, o, inv, mint, best_t, e0), h1 = hit_box(n.lo1, n.hi1, o, inv, mint, best_t, e1);
-            if (h0 && h1) { if (e0 <= e1) { stack[sp++] = n.c1; node = n.c0; } else { stack[sp++] = n.c0; node = n.c1; } continue; }
-            if (h0) { node = n.c0; continue; }
-            if (h1) { node = n.c1; continue; }
-        } else {
-            ops.push_back('L');
-            uint32_t s = (uint32_t)~node; float t;
-            if (hit_sphere(S.sp[s], o, d, mint, best_t, t) && t < best_t) { best_t = t; best = (int)s; }
-        }
-        if (sp == 0) break;
-        node = stack[--sp];
-    }
-    return best;
+    const float oo[3] = { o.x, o.y, o.z }, dd[3] = { d.x, d.y, d.z };
+    if (g_record) g_record->push_back(Seg{ { o.x, o.y, o.z }, { d.x, d.y, d.z } });
+    const HostHit h = bvh_closest_host(S.bvh, S.sp.data(), (uint32_t)S.sp.size(), oo, dd, 0.0f, 0.001f, 1e5f, true, &ops);
+    best_t = h.t;
+    return h.sphere;
 }
-
 
 // ---- uniform grid over the tree spheres (design study): cells hold sphere lists; a query = DDA steps ('N') + exact tests ('L') ----
 struct Grid {
@@ -461,7 +435,86 @@ static Result simulate_split(const std::vector<std::vector<std::vector<PathTrace
     return R;
 }
 
+// ---- `visits`: the builder's yardstick.  Traces a subsample of the bench frame once (camera rays and bounces in their natural
+// proportion), keeps every query's ray, and replays the rays over each candidate tree with the device's own traversal rules:
+// inner-node visits per segment, to be set against RtwStats.node_tests / segments of the GPU.
+static double inner_area(const BvhBuild &b) {
+    double s = 0;
+    for (size_t i = 0; i < b.nodes.size(); i++) {
+        const BvhNode &n = b.nodes[i];
+        if (i == 0) { double e[3]; for (int k = 0; k < 3; k++) e[k] = (double)std::max(n.hi0[k], n.hi1[k]) - std::min(n.lo0[k], n.lo1[k]); s += 2 * (e[0] * e[1] + e[1] * e[2] + e[2] * e[0]); }
+        if (n.c0 >= 0) s += 2 * (((double)n.hi0[0] - n.lo0[0]) * ((double)n.hi0[1] - n.lo0[1]) + ((double)n.hi0[1] - n.lo0[1]) * ((double)n.hi0[2] - n.lo0[2]) + ((double)n.hi0[2] - n.lo0[2]) * ((double)n.hi0[0] - n.lo0[0]));
+        if (n.c1 >= 0) s += 2 * (((double)n.hi1[0] - n.lo1[0]) * ((double)n.hi1[1] - n.lo1[1]) + ((double)n.hi1[1] - n.lo1[1]) * ((double)n.hi1[2] - n.lo1[2]) + ((double)n.hi1[2] - n.lo1[2]) * ((double)n.hi1[0] - n.lo1[0]));
+    }
+    return s;
+}
+// where the spheres of radius >= 5 x the smallest sit: depth, and how many of their ancestors' boxes are taller than 2.5 x the small spheres' diameter
+static void report_large(const Scene &S, const BvhBuild &b) {
+    struct It { int32_t node; uint32_t depth; uint32_t tall; };
+    std::vector<It> path, st; st.push_back(It{ b.root, 0, 0 });
+    while (!st.empty()) {
+        It it = st.back(); st.pop_back();
+        if (it.node < 0) {
+            const RtwSphere &s = S.sp[(uint32_t)~it.node];
+            if (s.radius >= 5 * b.r_min) printf("    sphere %u (r %.2f at %.1f %.1f %.1f): leaf depth %u, %u inner ancestors hold a box taller than %.2f\n", (uint32_t)~it.node, s.radius,
+                                                s.center[0], s.center[1], s.center[2], it.depth, it.tall, 5 * b.r_min);
+            continue;
+        }
+        const BvhNode &n = b.nodes[it.node];
+        st.push_back(It{ n.c0, it.depth + 1, it.tall + (n.c0 >= 0 && n.hi0[1] - n.lo0[1] > 5 * b.r_min ? 1u : 0u) });
+        st.push_back(It{ n.c1, it.depth + 1, it.tall + (n.c1 >= 0 && n.hi1[1] - n.lo1[1] > 5 * b.r_min ? 1u : 0u) });
+    }
+    uint32_t tall = 0, inner = 0;
+    for (const BvhNode &n : b.nodes) { if (n.c0 >= 0) { inner++; tall += n.hi0[1] - n.lo0[1] > 5 * b.r_min; } if (n.c1 >= 0) { inner++; tall += n.hi1[1] - n.lo1[1] > 5 * b.r_min; } }
+    printf("    %u of %u inner nodes below the root hold such a tall box\n", tall, inner);
+}
+static int visits_main(int argc, char **argv) {
+    const uint32_t n_tiles = argc > 2 ? atoi(argv[2]) : 400, spp = argc > 3 ? atoi(argv[3]) : 2;
+    const uint32_t which = getenv("SIM_SCENE") ? (uint32_t)atoi(getenv("SIM_SCENE")) : (uint32_t)RTW_SCENE_C2_BOOK1_FINAL;
+    uint32_t ns = 0, nt = 0, nx = 0;
+    rtw_scene_generate(which, 42, nullptr, 0, &ns, nullptr, 0, &nt, nullptr, 0, &nx);
+    Scene S; S.sp.resize(ns); std::vector<RtwTexture> tx(nt ? nt : 1); std::vector<float> tl(3 * (nx ? nx : 1));
+    rtw_scene_generate(which, 42, S.sp.data(), ns, &ns, tx.data(), nt, &nt, tl.data(), nx, &nx);
+    RtwCamera cam; RtwParams p;
+    rtw_scene_default_view(which == RTW_SCENE_C2_BOOK1_FINAL ? (uint32_t)RTW_SCENE_C5_MOTION_CHECKER : which, &cam, &p);     // (the bench frame: C2's scene in C5's 1920 x 1080 framing)
+    if (which == RTW_SCENE_C2_BOOK1_FINAL) cam.shutter = 0.0f;
+    for (RtwSphere &s : S.sp) s.velocity[0] = s.velocity[1] = s.velocity[2] = 0.0f;      // (the tracer here is static)
+    build_bvh(S.sp.data(), ns, 0, 0, S.bvh);
+    std::vector<Seg> rays; g_record = &rays;
+    std::mt19937 pick(7);
+    for (uint32_t t = 0; t < n_tiles; t++) {
+        const uint32_t tx0 = pick() % (p.width / 8), ty0 = pick() % (p.height / 8);
+        for (uint32_t q = 0; q < 64; q++) for (uint32_t s = 0; s < spp; s++) trace_path(S, cam, tx0 * 8 + (q & 7), ty0 * 8 + (q >> 3), p.depth);
+    }
+    g_record = nullptr;
+    printf("scene %u: %u spheres, %zu query rays of %u paths (%.2f segments per path)\n", which, ns, rays.size(), n_tiles * 64 * spp, (double)rays.size() / (n_tiles * 64.0 * spp));
+    struct Cand { const char *name; BvhBuildOptions o; };
+    std::vector<Cand> cands;
+    { BvhBuildOptions o; o.sweep = false; o.reinsert = false; o.depth_cap = RTW_BVH_STACK; cands.push_back({ "16-bin SAH, cap 24 (the earlier builder)", o }); }
+    { BvhBuildOptions o; o.sweep = true; o.reinsert = false; cands.push_back({ "(a) full-sweep SAH", o }); }
+    { BvhBuildOptions o; o.sweep = false; o.reinsert = true; cands.push_back({ "(b) 16-bin SAH + reinsertion", o }); }
+    { BvhBuildOptions o; cands.push_back({ "(a)+(b) full-sweep SAH + reinsertion (the product)", o }); }
+    { BvhBuildOptions o; o.depth_cap = RTW_BVH_STACK; cands.push_back({ "(a)+(b) with the cap at 24", o }); }
+    double base = 0;
+    for (const Cand &c : cands) {
+        BvhBuild b; build_bvh(S.sp.data(), ns, 0, 0, b, c.o);
+        unsigned long long nv = 0, nl = 0, mism = 0;
+        for (const Seg &r : rays) {
+            const HostHit h = bvh_closest_host(b, S.sp.data(), ns, r.o, r.d, 0.0f, 0.001f, 1e5f, true);
+            nv += h.node_visits; nl += h.leaf_tests;
+            if (getenv("SIM_CHECK")) { const HostHit l = bvh_closest_host(b, S.sp.data(), ns, r.o, r.d, 0.0f, 0.001f, 1e5f, false); mism += l.sphere != h.sphere || (l.sphere >= 0 && l.t != h.t); }
+        }
+        const double v = (double)nv / rays.size();
+        if (base == 0) base = v;
+        printf("%-52s nodes %4zu depth %2u (cap %2u) f16 %d  inner area %9.1f  visits/segment %6.3f (%+6.2f %%)  leaf tests/segment %5.3f%s\n", c.name, b.nodes.size(), b.depth, b.depth_cap,
+               (int)!b.nodes16.empty(), inner_area(b), v, 100 * (v / base - 1), (double)nl / rays.size(), getenv("SIM_CHECK") ? (mism ? "  LIST-WALK MISMATCH" : "  == list walk") : "");
+        if (getenv("SIM_LARGE")) report_large(S, b);
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "visits")) return visits_main(argc, argv);
     uint32_t ns = 0, nt = 0, nx = 0;
     rtw_scene_generate(RTW_SCENE_C2_BOOK1_FINAL, 42, nullptr, 0, &ns, nullptr, 0, &nt, nullptr, 0, &nx);
     Scene S; S.sp.resize(ns);
