@@ -25,6 +25,13 @@ pub struct RtwQuad { pub origin: [f32; 3], pub u: [f32; 3], pub v: [f32; 3], pub
 pub struct RtwTriangle { pub origin: [f32; 3], pub u: [f32; 3], pub v: [f32; 3], pub normal: [f32; 3], pub d: f32, pub w: [f32; 3],
     pub tex_color: [f32; 3], pub metallicness: f32, pub opacity: f32, pub ir: f32, pub emitted: [f32; 3], pub tex: i32 }
 
+/// One placement of the context's triangle mesh (rtw.h "mesh placements"): Rust2's `Instance` of triangles; quat = (w, x, y, z).
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RtwMeshInstance { pub position: [f32; 3], pub quat: [f32; 4] }
+pub const RTW_MAX_MESH_INSTANCES: u32 = 65536;
+/// (t or +inf, placement or -1, triangle or -1, normal or 0) per ray
+pub type MeshHits = (Vec<f32>, Vec<i32>, Vec<i32>, Vec<[f32; 3]>);
+
 /// `Instance` (objects/instance.rs:27-38): member ranges into the scene's instance pools; medium 1 = const_density.
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct RtwInstance { pub first_sphere: u32, pub n_spheres: u32, pub first_quad: u32, pub n_quads: u32,
@@ -123,6 +130,13 @@ extern "C" {
     fn rtw_mgpu_set_triangles(m: *mut RtwMgpu, tris: *const RtwTriangle, n: u32) -> i32;
     fn rtw_ctx_set_instance_rotations(ctx: *mut RtwCtx, quat: *const [f32; 4], n: u32) -> i32;
     fn rtw_mgpu_set_instance_rotations(m: *mut RtwMgpu, quat: *const [f32; 4], n: u32) -> i32;
+    fn rtw_ctx_set_mesh_instances(ctx: *mut RtwCtx, p: *const RtwMeshInstance, n: u32) -> i32;
+    fn rtw_mgpu_set_mesh_instances(m: *mut RtwMgpu, p: *const RtwMeshInstance, n: u32) -> i32;
+    fn rtw_mesh_instances_validate(tris: *const RtwTriangle, n_tris: u32, p: *const RtwMeshInstance, n: u32) -> i32;
+    fn rtw_mesh_instance_hits(tris: *const RtwTriangle, n_tris: u32, p: *const RtwMeshInstance, n: u32, rays: *const f32, n_rays: u32,
+                              mint: f32, maxt: f32, t_out: *mut f32, placement_out: *mut i32, tri_out: *mut i32, normal_out: *mut f32) -> i32;
+    fn rtw_ctx_mesh_instance_hits(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, mint: f32, maxt: f32, accel: u32, t_out: *mut f32,
+                                  placement_out: *mut i32, tri_out: *mut i32, normal_out: *mut f32, stats: *mut RtwStats) -> i32;
     fn rtw_quat_rotate(q: *const f32, v: *const f32, out: *mut f32) -> i32;
     fn rtw_quat_mul(a: *const f32, b: *const f32, out: *mut f32) -> i32;
     fn rtw_quat_from_axis(angle: f32, axis: *const f32, out: *mut f32) -> i32;
@@ -205,6 +219,20 @@ impl Renderer {
     pub fn set_instance_rotations(&mut self, quats: &[[f32; 4]]) -> Result<(), RtwError> {
         let p = if quats.is_empty() { std::ptr::null() } else { quats.as_ptr() };
         check(unsafe { rtw_ctx_set_instance_rotations(self.ctx, p, quats.len() as u32) })
+    }
+    /// rtw_ctx_set_mesh_instances: place the context's triangle mesh at every placement (empty: clear).  Renders under
+    /// RTW_INTEGRATOR_RUST2 and the scene queries honour them; set_scene and set_triangles clear them.
+    pub fn set_mesh_instances(&mut self, placements: &[RtwMeshInstance]) -> Result<(), RtwError> {
+        let p = if placements.is_empty() { std::ptr::null() } else { placements.as_ptr() };
+        check(unsafe { rtw_ctx_set_mesh_instances(self.ctx, p, placements.len() as u32) })
+    }
+    /// The closest placement of this context's mesh per ray on its GPU (rtw_ctx_mesh_instance_hits).
+    pub fn mesh_instance_hits(&mut self, rays: &[[f32; 6]], mint: f32, maxt: f32, accel: u32) -> Result<MeshHits, RtwError> {
+        let n = rays.len();
+        let (mut t, mut p, mut i, mut nr) = (vec![0f32; n], vec![0i32; n], vec![0i32; n], vec![[0f32; 3]; n]);
+        check(unsafe { rtw_ctx_mesh_instance_hits(self.ctx, rays.as_ptr() as *const f32, n as u32, mint, maxt, accel, t.as_mut_ptr(),
+                                                  p.as_mut_ptr(), i.as_mut_ptr(), nr.as_mut_ptr() as *mut f32, std::ptr::null_mut()) })?;
+        Ok((t, p, i, nr))
     }
     /// The closest of this context's triangles per ray ([origin, direction]) on its GPU: (t, index or -1) per ray.
     pub fn triangle_hits(&mut self, rays: &[[f32; 6]], mint: f32, maxt: f32, accel: u32) -> Result<(Vec<f32>, Vec<i32>), RtwError> {
@@ -297,6 +325,11 @@ impl MultiRenderer {
         let p = if quats.is_empty() { std::ptr::null() } else { quats.as_ptr() };
         check(unsafe { rtw_mgpu_set_instance_rotations(self.m, p, quats.len() as u32) })
     }
+    /// rtw_mgpu_set_mesh_instances: `Renderer::set_mesh_instances` on every device.
+    pub fn set_mesh_instances(&mut self, placements: &[RtwMeshInstance]) -> Result<(), RtwError> {
+        let p = if placements.is_empty() { std::ptr::null() } else { placements.as_ptr() };
+        check(unsafe { rtw_mgpu_set_mesh_instances(self.m, p, placements.len() as u32) })
+    }
     pub fn render(&mut self, cam: &RtwCamera, p: &RtwParams) -> Result<(Vec<Vec<[f32; 3]>>, Vec<RtwStats>), RtwError> {
         let mut flat = vec![[0f32; 3]; (p.width as usize) * (p.height as usize)];
         let mut per = vec![RtwStats::default(); self.n];
@@ -380,6 +413,22 @@ pub fn triangle_hits(tris: &[RtwTriangle], rays: &[[f32; 6]], mint: f32, maxt: f
     check(unsafe { rtw_triangle_hits(tris.as_ptr(), tris.len() as u32, rays.as_ptr() as *const f32, rays.len() as u32, mint, maxt,
                                      t.as_mut_ptr(), i.as_mut_ptr()) })?;
     Ok((t, i))
+}
+
+/// rtw_mesh_instances_validate: the status rtw_ctx_set_mesh_instances answers for `placements` of the mesh `tris` (host only).
+pub fn mesh_instances_validate(tris: &[RtwTriangle], placements: &[RtwMeshInstance]) -> i32 {
+    let t = if tris.is_empty() { std::ptr::null() } else { tris.as_ptr() };
+    let p = if placements.is_empty() { std::ptr::null() } else { placements.as_ptr() };
+    unsafe { rtw_mesh_instances_validate(t, tris.len() as u32, p, placements.len() as u32) }
+}
+
+/// The closest placement of the mesh per ray on the host (rtw_mesh_instance_hits, the list walk).
+pub fn mesh_instance_hits(tris: &[RtwTriangle], placements: &[RtwMeshInstance], rays: &[[f32; 6]], mint: f32, maxt: f32) -> Result<MeshHits, RtwError> {
+    let n = rays.len();
+    let (mut t, mut p, mut i, mut nr) = (vec![0f32; n], vec![0i32; n], vec![0i32; n], vec![[0f32; 3]; n]);
+    check(unsafe { rtw_mesh_instance_hits(tris.as_ptr(), tris.len() as u32, placements.as_ptr(), placements.len() as u32, rays.as_ptr() as *const f32,
+                                          n as u32, mint, maxt, t.as_mut_ptr(), p.as_mut_ptr(), i.as_mut_ptr(), nr.as_mut_ptr() as *mut f32) })?;
+    Ok((t, p, i, nr))
 }
 
 /// Rust2's `Camera::new(aspect, origin, vup, dir, vfov, lens_radius)` (Rust2/src/viewport/camera.rs:19-53).

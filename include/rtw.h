@@ -635,6 +635,49 @@ int rtw_quat_mul(const float a[4], const float b[4], float out[4]);
 int rtw_quat_from_axis(float angle, const float axis[3], float out[4]);
 int rtw_quat_from_euler(const float euler[3], float out[4]);
 
+/* ---- mesh placements: Rust2 instances of triangles (Rust2/src/objects/instance.rs:21-47, 215-255, triangle.rs) ---------------------------
+ * A Rust2 `Instance` holds any Object, triangles included: a mesh is built once, translated, rotated and put into the scene several times.
+ * Here the context's triangle mesh (rtw_ctx_set_triangles) is PLACED n times; placement k = {position, quat {w, x, y, z}}; all share one tree.
+ * Replacement of the triangle group: with placements set the triangles are no longer a world-space group; the fourth group of the closest-hit
+ * rule is the placements, tried in list order.
+ * The test of placement k is Instance::get_hit: o' = q.rotate(o - position), d' = q.rotate(d) (Quaternion::rotate as in the section above; qn is
+ * formed once per placement on the host with the same operations); the triangle group rule applies in that frame with the render's mint / maxt
+ * (closest in list order, a later triangle only when strictly closer); t is untouched; the winner returns as p = q.rotate(p') + position,
+ * n = q.rotate(n') -- the SAME q both ways, as for the quaternion instances.
+ * Ordering: a later placement replaces an earlier one only when strictly closer; the group replaces the result so far (spheres, quads,
+ * instances) only when strictly closer.
+ * Hit.r stays local: under RTW_INTEGRATOR_RUST2 the material of a placed triangle reads the direction in the placement's frame -- a Mirror
+ * reflects d' about the turned normal, MirrorGlass refracts d' -- and the next ray starts at the turned-back p.
+ * Top-level index (rtw_ctx_scene_hits / rtw_ctx_depth_map): placement k reports n_spheres + n_quads + n_instances + k, normal q.rotate(n').
+ * rtw_ctx_set_mesh_instances: rtw_ctx_set_scene and rtw_ctx_set_triangles clear the placements; NULL with n == 0 clears them; RTW_E_NO_SCENE
+ * without triangles in the context; RTW_E_INVALID for n > RTW_MAX_MESH_INSTANCES, a NULL / n mismatch, a component that is not finite, a
+ * quaternion whose len is 0 or not finite, any triangle with tex >= 0, and while a render is pending.  (Textured triangles: Triangle::color
+ * reads alfa / beta from the turned-back h.p, triangle.rs:130-136, which for a member of a moved instance leaves [0, 1]; ImageTexture::color_at
+ * then indexes outside the image -- a panic in the reference, so not expressible here.)
+ * Renders: RTW_INTEGRATOR_RUST2 is served, with every sampler, flag and accel; everything the triangle build serves under that integrator next
+ * to plain triangles stays legal next to placements.  NOT BUILT, RTW_E_INVALID at the render: every other integrator,
+ * RTW_FLAG_MIXED_MATERIAL with a mixed object, instance rotations in the same context.  (Texture noise and lights are refused next to
+ * triangles already.)  The one-shot rtw_render / rtw_render_multi_gpu carry no placements.  Without placements nothing changes. */
+typedef struct RtwMeshInstance { float position[3]; float quat[4]; /* w,x,y,z */ } RtwMeshInstance;
+#define RTW_MAX_MESH_INSTANCES 65536u
+int rtw_ctx_set_mesh_instances(rtw_ctx *ctx, const RtwMeshInstance *placements, uint32_t n);
+int rtw_mgpu_set_mesh_instances(rtw_mgpu *m, const RtwMeshInstance *placements, uint32_t n);
+/* Host only (no context, no GPU): the status rtw_ctx_set_mesh_instances answers for `placements` on a context that holds `tris`
+ * (RTW_E_NO_SCENE for n_tris == 0). */
+int rtw_mesh_instances_validate(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *placements, uint32_t n);
+/* Host only: the placement group by the list walk.  rays [n_rays][6] = origin, direction.  t_out: the hit's t, +inf on a miss;
+ * placement_out / tri_out: the winning placement and its triangle (caller's list), -1 on a miss; normal_out ([n_rays][3], may be NULL):
+ * q.rotate(n'), 0 on a miss.  RTW_E_INVALID for a NULL pointer, n_rays == 0, n == 0 or placements the validation refuses. */
+int rtw_mesh_instance_hits(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *placements, uint32_t n,
+                           const float *rays, uint32_t n_rays, float mint, float maxt,
+                           float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out /* may be NULL */);
+/* The same on the context's GPU through the function the render's closest-hit stage calls (host buffers in and out, blocking, as
+ * rtw_ctx_triangle_hits): accel = RTW_ACCEL_BVH walks the mesh's tree per placement (rays the cull does not cover in a placement's frame
+ * walk the list there), RTW_ACCEL_BRUTE the list.  stats (may be NULL): quad_tests = triangle tests, node_tests = node visits.
+ * RTW_E_NO_SCENE without placements. */
+int rtw_ctx_mesh_instance_hits(rtw_ctx *ctx, const float *rays, uint32_t n_rays, float mint, float maxt, uint32_t accel,
+                               float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out /* may be NULL */, RtwStats *stats);
+
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 
 /* Viewport::new (viewport.rs:308-401).  Options the reference takes as Option<> are pointers

@@ -41,6 +41,7 @@ INTEGRATOR_GRADIENT, INTEGRATOR_BG_COLOR, INTEGRATOR_NORMAL, INTEGRATOR_FLAG, IN
 INTEGRATOR_LIGHT_CAST, INTEGRATOR_LIGHT_BIASED = 5, 6   # Rust2 light_biased_ray_cast / light_biased_ray_color (set_lights)
 LIGHT_SPHERE, LIGHT_QUAD = 0, 1                         # RtwLight.kind
 MAX_LIGHTS = 16
+MAX_MESH_INSTANCES = 65536
 SAMPLER_ROW, SAMPLER_STRATIFIED, SAMPLER_CENTRES, SAMPLER_NO_RAND = 0, 1, 2, 3
 ACCEL_BRUTE, ACCEL_BVH = 0, 1
 FLAG_RECURSIVE_ORDER, FLAG_CPP_DIELECTRIC, FLAG_GLOBAL_NODES, FLAG_CPP_DIFFUSE, FLAG_CHUNK_SUMS = 1, 2, 4, 8, 16
@@ -98,6 +99,10 @@ class RtwTriangle(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3), ("normal", C.c_float * 3), ("d", C.c_float),
                 ("w", C.c_float * 3), ("tex_color", C.c_float * 3), ("metallicness", C.c_float), ("opacity", C.c_float), ("ir", C.c_float),
                 ("emitted", C.c_float * 3), ("tex", C.c_int32)]
+
+
+class RtwMeshInstance(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("quat", C.c_float * 4)]
 
 
 class RtwLight(C.Structure):
@@ -271,6 +276,13 @@ def lib() -> C.CDLL:
     L.rtw_ctx_set_instance_rotations.argtypes = [C.c_void_p, fp, C.c_uint32]
     L.rtw_mgpu_set_instance_rotations.argtypes = [C.c_void_p, fp, C.c_uint32]
     L.rtw_instance_rotations_validate.argtypes = [C.POINTER(RtwScene), fp, C.c_uint32]
+    L.rtw_ctx_set_mesh_instances.argtypes = [C.c_void_p, C.POINTER(RtwMeshInstance), C.c_uint32]
+    L.rtw_mgpu_set_mesh_instances.argtypes = [C.c_void_p, C.POINTER(RtwMeshInstance), C.c_uint32]
+    L.rtw_mesh_instances_validate.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, C.POINTER(RtwMeshInstance), C.c_uint32]
+    L.rtw_mesh_instance_hits.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, C.POINTER(RtwMeshInstance), C.c_uint32, fp, C.c_uint32, C.c_float,
+                                         C.c_float, fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), fp]
+    L.rtw_ctx_mesh_instance_hits.argtypes = [C.c_void_p, fp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, fp, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32), fp, C.POINTER(RtwStats)]
     L.rtw_quat_rotate.argtypes = [fp, fp, fp]
     L.rtw_quat_mul.argtypes = [fp, fp, fp]
     L.rtw_quat_from_axis.argtypes = [C.c_float, fp, fp]
@@ -564,6 +576,46 @@ def triangle_hits(triangles, rays, mint: float, maxt: float):
     _check(lib().rtw_triangle_hits(arr, n, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt),
                                    t.ctypes.data_as(C.POINTER(C.c_float)), idx.ctypes.data_as(C.POINTER(C.c_int32))), "rtw_triangle_hits")
     return t, idx
+
+
+def _placement_array(placements):
+    """(ctypes array of RtwMeshInstance or None, count) of a sequence of (position, (w, x, y, z)) pairs."""
+    if placements is None or len(placements) == 0:
+        return None, 0
+    arr = (RtwMeshInstance * len(placements))()
+    for k, (pos, quat) in enumerate(placements):
+        assert len(pos) == 3 and len(quat) == 4, "a placement is (position [3], quaternion [4] = w, x, y, z)"
+        arr[k].position[:] = [float(np.float32(x)) for x in pos]
+        arr[k].quat[:] = [float(np.float32(x)) for x in quat]
+    return arr, len(placements)
+
+
+def mesh_instances_validate(triangles, placements) -> int:
+    """rtw_mesh_instances_validate: the status rtw_ctx_set_mesh_instances answers for `placements` of the mesh `triangles` (host only)."""
+    arr, n = _triangle_array(triangles) if triangles is not None and len(triangles) else (None, 0)
+    parr, pn = _placement_array(placements)
+    return int(lib().rtw_mesh_instances_validate(arr, n, parr, pn))
+
+
+def _mesh_hit_buffers(n, normals):
+    t = np.empty(n, np.float32)
+    pl = np.empty(n, np.int32)
+    tri = np.empty(n, np.int32)
+    nrm = np.empty((n, 3), np.float32) if normals else None
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    return (t, pl, tri, nrm), (t.ctypes.data_as(fp), pl.ctypes.data_as(ip), tri.ctypes.data_as(ip), nrm.ctypes.data_as(fp) if normals else None)
+
+
+def mesh_instance_hits(triangles, placements, rays, mint: float, maxt: float, normals: bool = True):
+    """The closest placement of the mesh per ray on the host (rtw_mesh_instance_hits, the list walk): rays [n][6] = origin, direction.
+    Returns (t [n] float32, +inf on a miss; placement [n] int32 and triangle [n] int32, -1 on a miss[; normals [n][3] float32, 0 on a miss])."""
+    arr, n = _triangle_array(triangles)
+    parr, pn = _placement_array(placements)
+    r = _rays(rays)
+    out, ptrs = _mesh_hit_buffers(len(r), normals)
+    _check(lib().rtw_mesh_instance_hits(arr, n, parr, pn, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt), *ptrs),
+           "rtw_mesh_instance_hits")
+    return out if normals else out[:3]
 
 
 def depth_rays(cam: RtwCamera, width: int, height: int) -> np.ndarray:
@@ -1014,6 +1066,22 @@ class Renderer:
         ptr, n, _keep = _quat_array(quats)
         _check(lib().rtw_ctx_set_instance_rotations(self._h, ptr, n), "rtw_ctx_set_instance_rotations")
 
+    def set_mesh_instances(self, placements=None):
+        """rtw_ctx_set_mesh_instances: place the context's triangle mesh at every (position, (w, x, y, z)) of `placements` (None: clear).  Rust2's
+        Instance of triangles; renders under INTEGRATOR_RUST2 and the scene queries honour it; set_scene and set_triangles clear it."""
+        arr, n = _placement_array(placements)
+        _check(lib().rtw_ctx_set_mesh_instances(self._h, arr, n), "rtw_ctx_set_mesh_instances")
+
+    def mesh_instance_hits(self, rays, mint: float, maxt: float, accel: int = ACCEL_BVH, normals: bool = True):
+        """The closest placement of this context's mesh per ray on its GPU (rtw_ctx_mesh_instance_hits): (t, placement, triangle[, normals],
+        RtwStats) as mesh_instance_hits."""
+        r = _rays(rays)
+        out, ptrs = _mesh_hit_buffers(len(r), normals)
+        st = RtwStats()
+        _check(lib().rtw_ctx_mesh_instance_hits(self._h, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt), int(accel), *ptrs,
+                                                C.byref(st)), "rtw_ctx_mesh_instance_hits")
+        return (out if normals else out[:3]) + (st,)
+
     def triangle_hits(self, rays, mint: float, maxt: float, accel: int = ACCEL_BVH):
         """The closest of this context's triangles per ray on its GPU (rtw_ctx_triangle_hits): (t, index, RtwStats) as triangle_hits."""
         r = _rays(rays)
@@ -1167,6 +1235,11 @@ class MultiRenderer:
         """rtw_mgpu_set_instance_rotations on every device (None: clear them)."""
         ptr, n, _keep = _quat_array(quats)
         _check(lib().rtw_mgpu_set_instance_rotations(self._h, ptr, n), "rtw_mgpu_set_instance_rotations")
+
+    def set_mesh_instances(self, placements=None):
+        """rtw_mgpu_set_mesh_instances: Renderer.set_mesh_instances for every context (checked against all before any is touched)."""
+        arr, n = _placement_array(placements)
+        _check(lib().rtw_mgpu_set_mesh_instances(self._h, arr, n), "rtw_mgpu_set_mesh_instances")
 
     def set_option(self, key: int, value: float):
         _check(lib().rtw_mgpu_set_option(self._h, int(key), float(value)), "rtw_mgpu_set_option")

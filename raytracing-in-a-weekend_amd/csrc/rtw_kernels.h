@@ -85,6 +85,8 @@ struct KArgs {
                                   // _LIGHT_BIASED select
     const f4 *inst_quats;         // Rust2's instance rotations (rtw_ctx_set_instance_rotations): one normalised {w, x, y, z} per instance; non-null selects
                                   // the quaternion build (SPEC 11), which alone reads it (and the lights, for every integrator it serves)
+    const f4 *mesh_rows;          // mesh placements (rtw_ctx_set_mesh_instances): two rows {qn}, {position, 0} per placement (rtw_mesh.h); non-null selects
+    uint32_t n_mesh;              // the placement build (SPEC 12), which alone reads them: tris is then the mesh every placement shares
 };
 
 // accel: RTW_ACCEL_BRUTE, RTW_ACCEL_BVH; the BVH launch picks the LDS-resident variant when a.bvh.nodes16 != null
@@ -102,6 +104,8 @@ struct QueryArgs {
     DevGeom  geom;
     DevTris  tris;                // tris.n == 0: none; tris.nodes == null: walk the triangle list
     const f4 *inst_quats;         // Rust2's instance rotations, one normalised {w, x, y, z} per instance, or null: the Euler rotation of DevInstance
+    const f4 *mesh_rows;          // mesh placements, two rows per placement (rtw_mesh.h), or null: tris is a world-space group
+    uint32_t n_mesh;
     RtwCamera cam;                // from_camera: Rust2's camera (rtw_camera2_new), pixel i = (i % width, i / width)
     uint32_t width, height;
     const float *rays;            // else: [n][6] = o, d (device)
@@ -120,6 +124,10 @@ struct QueryArgs {
 #define RTW_QUERY_STRIDE 16u      // counters (u64) per line: 128 bytes
 // from_camera: rays built from q.cam, else read from q.rays; tree: the sphere group through DevBvh.nodes (dynamic LDS = levels * RTW_BLOCK * 4)
 void launch_scene_hits(const QueryArgs &q, bool from_camera, bool tree, hipStream_t stream);
+// rtw_ctx_mesh_instance_hits: the closest placement of mesh T for each of n rays through mesh_closest (rtw_mesh.h); placement / triangle
+// -1 and t +inf on a miss; normal_out ([n][3]) may be null; counters as launch_tri_hits
+void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const float *rays, uint32_t n, float mint, float maxt, float *t_out,
+                      int32_t *placement_out, int32_t *tri_out, float *normal_out, unsigned long long *counters, hipStream_t stream);
 // Resident workgroups per CU for the kernel variant (occupancy API), >= 1.
 uint32_t kernel_blocks_per_cu(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);
 // Is there a build of the BVH kernel for this configuration that reads the spheres' {centre, r^2} from LDS?  (KArgs.lds_geom_off may only be set then)

@@ -29,6 +29,7 @@
 //  -- so uniform work is kept on the scalar unit (lane-mask logic, counters as ballot popcounts,
 // the work-unit decode once per 64 items) and the divergent branches share what they can (one unit(direction)).
 #include "rtw_kernels.h"
+#include "rtw_mesh.h"
 #include <type_traits>
 
 #ifndef RTW_MAX_TRIPS
@@ -60,15 +61,19 @@ namespace rtw {
 // (rtw_quat.h) in every instance walk -- the path's closest hit and the shadow queries; only a context that holds instance rotations
 // (rtw_ctx_set_instance_rotations) selects it, for RUST2 / LIGHT_CAST / LIGHT_BIASED.  It serves renders with and without
 // RTW_FLAG_MIXED_MATERIAL, so it asks the flag at run time where SPEC == 10 knows it is set.  GEOM variants only: rotations imply instances.
+// SPEC == 12 is SPEC == 8's step with the mesh placed n times (rtw_mesh.h, rtw_ctx_set_mesh_instances): mesh_closest in place of tri_closest, and
+// the material of a placed hit reads the direction in the placement's frame.  Only a context that holds placements selects it, under
+// RTW_INTEGRATOR_RUST2 (rtw_shim.hip refuses every other integrator).  GEOM variants only, as SPEC == 8.
 constexpr bool gradient_spec(int spec) { return spec >= 1 && spec <= 3; }
-constexpr bool generic_spec(int spec) { return spec == 0 || spec == 7 || spec == 8 || spec == 9 || spec == 10 || spec == 11; }
+constexpr bool generic_spec(int spec) { return spec == 0 || spec == 7 || spec == 8 || spec == 9 || spec == 10 || spec == 11 || spec == 12; }
 constexpr bool light_spec(int spec) { return spec == 9 || spec == 10 || spec == 11; }
 constexpr int mixed_spec(int spec) { return spec == 10 ? 1 : spec == 11 ? 2 : 0; }     // 1: the flag is known to be set; 2: KArgs.flags says
 constexpr bool quat_spec(int spec) { return spec == 11; }
 constexpr bool noise_spec(int spec) { return spec == 7; }
-constexpr bool tri_spec(int spec) { return spec == 8; }
+constexpr bool tri_spec(int spec) { return spec == 8 || spec == 12; }     // (the workgroup's node-visit counter)
+constexpr bool mesh_spec(int spec) { return spec == 12; }
 template <int SPEC> __device__ __forceinline__ uint32_t integ(const KArgs &A) {
-    return SPEC == 5 ? (uint32_t)RTW_INTEGRATOR_RUST2 : SPEC == 4 ? (uint32_t)RTW_INTEGRATOR_BG_COLOR : !generic_spec(SPEC) ? (uint32_t)RTW_INTEGRATOR_GRADIENT : A.integrator;
+    return (SPEC == 5 || SPEC == 12) ? (uint32_t)RTW_INTEGRATOR_RUST2 : SPEC == 4 ? (uint32_t)RTW_INTEGRATOR_BG_COLOR : !generic_spec(SPEC) ? (uint32_t)RTW_INTEGRATOR_GRADIENT : A.integrator;
 }
 template <int SPEC> __device__ __forceinline__ uint32_t samp(const KArgs &A) {
     return SPEC == 6 ? (uint32_t)RTW_SAMPLER_STRATIFIED : SPEC == 5 ? (uint32_t)RTW_SAMPLER_CENTRES : !generic_spec(SPEC) ? (uint32_t)RTW_SAMPLER_ROW : A.sampler;
@@ -412,7 +417,22 @@ template <bool MOVING, int SPEC>
 __device__ __forceinline__ bool shade_geom(const KArgs &A, Path &pt, int best, float best_t, uint32_t &n_sph, uint32_t &n_quad) {
     GeomHit h;
     bool won = geom_closest<noise_spec(SPEC)>(A.sc, A.noise, A.geom, pt.o, pt.d, pt.tm, A.mint, A.maxt, best >= 0, best_t, pt.rng, h, n_sph, n_quad);
-    if constexpr (tri_spec(SPEC)) {          // the triangles last (rtw.h): the closest one replaces the result so far when strictly closer
+    if constexpr (mesh_spec(SPEC)) {         // the placements last (rtw.h "mesh placements"): the closest one replaces the result so far when strictly closer
+        float tt;
+        int tk;
+        uint32_t n_nodes = 0;
+        const int mp = mesh_closest(A.tris, A.mesh_rows, A.n_mesh, pt.o, pt.d, A.mint, A.maxt, won || best >= 0, won ? h.t : best_t, tk, tt, n_quad, n_nodes);
+        if (n_nodes) atomicAdd(tri_node_counter(A.tris), n_nodes);
+        if (mp >= 0) {                       // Instance::get_hit: the record in the placement's frame, p and n turned back by the SAME q, Hit.r left local
+            quat qn; v3 pos;
+            mesh_row_lane(A.mesh_rows, (uint32_t)mp, qn, pos);
+            const v3 lo = mesh_rot(qn, pt.o - pos), ld = mesh_rot(qn, pt.d);
+            tri_record(A.sc, A.tris, (uint32_t)tk, lo, ld, tt, true, h);
+            h.point = mesh_rot(qn, h.point) + pos; h.normal = mesh_rot(qn, h.normal);
+            pt.d = ld;                       // (RUST2's on_hit reads pt.d: the material sees the local direction; the next ray starts at the turned-back p)
+            won = true;
+        }
+    } else if constexpr (tri_spec(SPEC)) {   // the triangles last (rtw.h): the closest one replaces the result so far when strictly closer
         float tt;
         uint32_t n_nodes = 0;
         const int k = tri_closest(A.tris, pt.o, pt.d, A.mint, A.maxt, won || best >= 0, won ? h.t : best_t, tt, n_quad, n_nodes);
@@ -1525,6 +1545,8 @@ static kernel_fn pick_kernel(const KArgs &a, bool moving, uint32_t accel, bool l
     // instance rotations (rtw_shim.hip sets inst_quats only then, for a scene with instances under RUST2 / LIGHT_CAST / LIGHT_BIASED): the
     // quaternion build, for every sampler and flag, with or without RTW_FLAG_MIXED_MATERIAL
     if (a.inst_quats) return pick_kernel_geom<11>(moving, accel, nodes);
+    // mesh placements (rtw_shim.hip sets mesh_rows only for a context that holds them, and serves RTW_INTEGRATOR_RUST2 alone): the placement build
+    if (a.mesh_rows) return pick_kernel_geom<12>(moving, accel, nodes);
     // RTW_FLAG_MIXED_MATERIAL on a scene with a MixedMaterial object (rtw_shim.hip clears the bit otherwise, and refuses the flag under any
     // integrator but RUST2 / LIGHT_CAST / LIGHT_BIASED): the mixed build, for every sampler and flag
     if (a.flags & RTW_FLAG_MIXED_MATERIAL)
@@ -1586,6 +1608,41 @@ __global__ __launch_bounds__(RTW_BLOCK) void tri_hits_kernel(const DevTris T, co
 void launch_tri_hits(const DevTris &T, const float *rays, uint32_t n, float mint, float maxt, float *t_out, int32_t *idx_out,
                      unsigned long long *counters, hipStream_t stream) {
     hipLaunchKernelGGL(tri_hits_kernel, dim3((n + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, T, rays, n, mint, maxt, t_out, idx_out, counters);
+}
+
+// The closest placement per ray through mesh_closest, the function the placement build's closest-hit stage calls (rtw_ctx_mesh_instance_hits)
+__global__ __launch_bounds__(RTW_BLOCK) void mesh_hits_kernel(const DevTris T, const f4 *rows, uint32_t n_mesh, const float *rays, uint32_t n, float mint,
+                                                              float maxt, float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out,
+                                                              unsigned long long *counters) {
+    const uint32_t i = blockIdx.x * RTW_BLOCK + threadIdx.x;
+    uint32_t n_tests = 0, n_nodes = 0;
+    if (i < n) {
+        const float *r = rays + 6 * (size_t)i;
+        float t;
+        int tk;
+        const int mp = mesh_closest(T, rows, n_mesh, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), mint, maxt, false, 0.0f, tk, t, n_tests, n_nodes);
+        t_out[i] = mp >= 0 ? t : __builtin_inff();
+        placement_out[i] = mp;
+        tri_out[i] = mp >= 0 ? tk : -1;
+        if (normal_out) {
+            v3 nrm = mk(0.0f, 0.0f, 0.0f);
+            if (mp >= 0) {
+                quat qn; v3 pos;
+                mesh_row_lane(rows, (uint32_t)mp, qn, pos);
+                nrm = mesh_rot(qn, ld3(T.list[tk].normal));
+            }
+            normal_out[3 * (size_t)i] = nrm.x; normal_out[3 * (size_t)i + 1] = nrm.y; normal_out[3 * (size_t)i + 2] = nrm.z;
+        }
+    }
+    unsigned long long a = n_tests, b = n_nodes;
+    for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
+    if ((threadIdx.x & 63u) == 0) { atomicAdd(&counters[0], a); atomicAdd(&counters[1], b); }
+}
+
+void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const float *rays, uint32_t n, float mint, float maxt, float *t_out,
+                      int32_t *placement_out, int32_t *tri_out, float *normal_out, unsigned long long *counters, hipStream_t stream) {
+    hipLaunchKernelGGL(mesh_hits_kernel, dim3((n + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, T, rows, n_mesh, rays, n, mint, maxt, t_out,
+                       placement_out, tri_out, normal_out, counters);
 }
 
 bool kernel_has_lds_geom(const KArgs &a) { return !(a.geom.n_quads || a.geom.n_inst || a.tris.n); }

@@ -3,12 +3,13 @@
 // A kernel of its own: no render kernel reads this file.
 //
 // Every value reported is the render's: the sphere root is sphere_root() (rtw_device.h), quads and instances go through quad_pick /
-// instance_pick, triangles through tri_closest (rtw_tri.h) or its tree walk restated below (q_tri_tree), and the tie rule is Scene::collision_normal's as the oracle restates it
+// instance_pick, triangles through tri_closest (rtw_tri.h) or the zero-safe tree walk (tri_tree_walk, rtw_mesh.h), mesh placements through mesh_closest, and the tie rule is Scene::collision_normal's as the oracle restates it
 // (closest_hit): within a group the first of equal t in list order, a later group only when strictly closer.  The sphere tree only prunes
 // (DESIGN.md "Conservative traversal"; the per-ray paddings below are those of render_bvh's trav_begin, global-node variant), and every
 // surviving candidate runs the exact test with ties to the lower index, so RTW_ACCEL_BVH answers bit for bit what RTW_ACCEL_BRUTE answers.
 // Constant-density instances are skipped: their hit is a random free path, and a query has no sample stream.
 #include "rtw_kernels.h"
+#include "rtw_mesh.h"
 
 namespace rtw {
 
@@ -138,58 +139,6 @@ __device__ __forceinline__ bool q_ray_ordinary(v3 o, v3 d, float a, float span) 
     return no + nd < 0x1p60f && a >= 1e-30f && a <= 1e30f && fmaxf(nd, 2.0f) * (span + no + 1.0f) <= 1e18f;      // (nd >= |d|; NaN fails)
 }
 
-// The triangle group through its tree: tri_closest's stackless walk (rtw_tri.h) -- the same boxes, paddings, candidates and tie rule --
-// with the slab of an axis along which the direction is EXACTLY zero decided by where the origin lies instead of by 1 / 0.  There
-// (lo - o) * inf is +-inf, the widening `ne - |ne| * pad` makes inf - inf = NaN, fmaxf / fminf drop the NaN and NO box is pruned any more: the
-// ray visits every node and tests every triangle -- the right answer, a 200k-triangle list walk late.  A depth map meets such rays as a
-// matter of course (pixel width / 2 of an axis-aligned camera has d.x == 0 down the whole column; DESIGN.md 4.8 has the measurement).  With d.x == 0 the
-// point o + d t keeps x = o.x for every t, so a box whose padded x-range does not hold o.x cannot hold a hit: pruning it is exact.
-// Only called for rays tri_ray_ordinary() accepts (finite, within the cull's reach) with the tree present; the others go through tri_closest.
-__device__ __forceinline__ int q_tri_tree(const DevTris &T, v3 o, v3 d, float mint, float maxt, bool found, float ht, float &bt,
-                                          uint32_t &n_tests, uint32_t &n_nodes) {
-    int best = -1; bt = 0.0f;
-    const float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
-    const bool zx = d.x == 0.0f, zy = d.y == 0.0f, zz = d.z == 0.0f;
-    const bool any_zero = ballot64(zx || zy || zz) != 0ull;             // wave-uniform: the selects below run only in waves that hold such a ray
-    const float ao = fmaxf(fmaxf(__builtin_fabsf(o.x), __builtin_fabsf(o.y)), __builtin_fabsf(o.z));
-    const float rr = ao * RTW_TRI_RAY_PAD;
-    const float BIG = 0x1.fffffep127f;
-    float lim = found ? ht : maxt;
-    uint32_t ni = 0;
-    while (ni < T.n_nodes) {
-        const f4 *q = (const f4 *)(T.nodes + ni);
-        const f4 a = q[0], b = q[1];
-        n_nodes++;
-        float x0 = ((a.x - rr) - o.x) * ix, x1 = ((b.x + rr) - o.x) * ix;
-        float y0 = ((a.y - rr) - o.y) * iy, y1 = ((b.y + rr) - o.y) * iy;
-        float z0 = ((a.z - rr) - o.z) * iz, z1 = ((b.z + rr) - o.z) * iz;
-        if (any_zero) {
-            if (zx) { const bool in = (a.x - rr) <= o.x && o.x <= (b.x + rr); x0 = in ? -BIG : BIG; x1 = BIG; }
-            if (zy) { const bool in = (a.y - rr) <= o.y && o.y <= (b.y + rr); y0 = in ? -BIG : BIG; y1 = BIG; }
-            if (zz) { const bool in = (a.z - rr) <= o.z && o.z <= (b.z + rr); z0 = in ? -BIG : BIG; z1 = BIG; }
-        }
-        float ne = fminf(x0, x1), fa = fmaxf(x0, x1);
-        ne = fmaxf(ne, fminf(y0, y1)); fa = fminf(fa, fmaxf(y0, y1));
-        ne = fmaxf(ne, fminf(z0, z1)); fa = fminf(fa, fmaxf(z0, z1));
-        ne = ne - __builtin_fabsf(ne) * RTW_TRI_T_PAD;
-        fa = fa + __builtin_fabsf(fa) * RTW_TRI_T_PAD;
-        const uint32_t skip = __float_as_uint(a.w), leaf = __float_as_uint(b.w);
-        if (!(fmaxf(ne, mint) <= fminf(fa, lim))) { ni = skip; continue; }
-        if (leaf == 0u) { ni++; continue; }
-        const uint32_t first = leaf >> 3, cnt = leaf & 7u;
-        for (uint32_t j = 0; j < cnt; ++j) {
-            const DevTri r = tri_load(T.leaf, first + j);
-            const int idx = (int)r.index;
-            float t;
-            auto could_win = [&](float x) { return best < 0 ? (!found || x < ht) : (x < bt || (x == bt && idx < best)); };
-            if (tri_test(r, o.x, o.y, o.z, d.x, d.y, d.z, mint, maxt, could_win, t)) { best = idx; bt = t; lim = t; }
-        }
-        n_tests += cnt;
-        ni = skip;
-    }
-    return best;
-}
-
 } // namespace
 
 // CAM: the ray of pixel i is built from the camera by the rule of rtw_depth_rays; else it is read from A.rays.  NORMALS: normal_out is
@@ -232,7 +181,7 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
         bool found = best >= 0;
         float ht = best_t;
         int idx = best;
-        int win = 0;                                               // 0: sphere `best`, 1: quad qk, 2: instance ii (member icode), 3: triangle tk
+        int win = 0;                                               // 0: sphere `best`, 1: quad qk, 2: instance ii (member icode), 3: triangle tk, 4: triangle tk of placement mk
         // ---- quads: the closest in list order, then against the spheres (strictly closer) ----
         const DevGeom &g = A.geom;
         uint32_t qk = 0;
@@ -260,10 +209,14 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
         }
         if (ifound && (!found || ht > it)) { ht = it; found = true; win = 2; idx = (int)(A.sc.n + g.n_quads + ii); }
         // ---- triangles last ----
-        int tk = -1;
-        if (A.tris.n) {
+        int tk = -1, mp = -1;
+        if (A.mesh_rows) {                                         // (a wave-uniform branch) the placements stand in for the world-space triangles
             float tt;
-            if (A.tris.nodes != nullptr && tri_ray_ordinary(A.tris, o, d)) tk = q_tri_tree(A.tris, o, d, mint, maxt, found, ht, tt, n_quad, n_nodes);
+            mp = mesh_closest(A.tris, A.mesh_rows, A.n_mesh, o, d, mint, maxt, found, ht, tk, tt, n_quad, n_nodes);
+            if (mp >= 0) { ht = tt; found = true; win = 4; idx = (int)(A.sc.n + g.n_quads + g.n_inst) + mp; }
+        } else if (A.tris.n) {
+            float tt;
+            if (A.tris.nodes != nullptr && tri_ray_ordinary(A.tris, o, d)) tk = tri_tree_walk(A.tris, o, d, mint, maxt, found, ht, tt, n_quad, n_nodes);
             else tk = tri_closest(A.tris, o, d, mint, maxt, found, ht, tt, n_quad, n_nodes);          // (the list walk)
             if (tk >= 0) { ht = tt; found = true; win = 3; idx = (int)(A.sc.n + g.n_quads + g.n_inst) + tk; }
         }
@@ -293,8 +246,12 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
                         ln = unit((lo + ld * ht) - c);
                     } else ln = ld3(g.iquads[(uint32_t)~icode].normal);
                     nrm = rq ? quat_rot(qn, ln) : rotated(ln, in.fwd, in.fwd_k);      // Rust2: q.rotate(n), the same q as on the way in
-                } else {
+                } else if (win == 3) {
                     nrm = ld3(A.tris.list[tk].normal);
+                } else {                                           // q.rotate(n'), the same q as on the way in
+                    quat qn; v3 pos;
+                    mesh_row_lane(A.mesh_rows, (uint32_t)mp, qn, pos);
+                    nrm = mesh_rot(qn, ld3(A.tris.list[tk].normal));
                 }
             }
             *reinterpret_cast<float3 *>(A.normal_out + 3 * (size_t)i) = make_float3(nrm.x, nrm.y, nrm.z);

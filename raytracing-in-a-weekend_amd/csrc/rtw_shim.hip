@@ -2,6 +2,7 @@
 // blocking render.  Host code only; kernels live in rtw_kernels.hip.  No CPU fallback of any kind:
 // without a HIP device every render entry point fails with RTW_E_NO_DEVICE / RTW_E_HIP.
 #include "rtw_kernels.h"
+#include "rtw_mesh.h"
 #include "rtw_host.h"
 #include "rtw_filter.h"
 #include "rtw_devmem.h"
@@ -40,6 +41,7 @@ struct SceneMem {
 struct NoiseMem { DevMem perlin, tex_noise; };
 struct TriMem { DevMem list, leaf, nodes; };
 struct QuatMem { DevMem rows; };
+struct MeshMem { DevMem rows; };
 struct ScratchMem {
     DevMem queue, stats;
     PinnedMem h_stats;                   // pinned: the counter read-back is a true async copy
@@ -89,6 +91,11 @@ struct rtw_ctx {
     std::vector<RtwInstance> h_instances;   // host copy of the instances: the checks of the setter read them
     const f4 *inst_quats = nullptr;      // non-null: renders take the quaternion build (SPEC 11), the queries rotate by them
     QuatMem quat_mem;
+    // mesh placements (rtw_ctx_set_mesh_instances; cleared by rtw_ctx_set_scene and rtw_ctx_set_triangles): two rows per placement (rtw_mesh.h)
+    const f4 *mesh_rows = nullptr;       // non-null: renders take the placement build (SPEC 12), the queries place the mesh
+    uint32_t n_mesh = 0;
+    bool tri_textured = false;           // a triangle of the context reads an image texture (placements refuse such a mesh)
+    MeshMem mesh_mem;
     // MixedMaterial (RTW_FLAG_MIXED_MATERIAL): does the scene hold an object with opacity < 0, and is the exponent (ir) of every such object
     // finite and >= 0?  Computed once by rtw_ctx_set_scene.
     bool has_mixed = false, mixed_bad = false;
@@ -264,7 +271,15 @@ static void free_noise(rtw_ctx *c) {
     c->noise_active = false;
 }
 
+static void free_mesh(rtw_ctx *c) {
+    c->mesh_mem = MeshMem{};
+    c->mesh_rows = nullptr;
+    c->n_mesh = 0;
+}
+
 static void free_tris(rtw_ctx *c) {
+    free_mesh(c);                        // (placements are placements of these triangles)
+    c->tri_textured = false;
     c->tri_mem = TriMem{};
     c->tris = DevTris{};
     c->tri_tree = false;
@@ -731,6 +746,36 @@ int rtw_ctx_set_triangles(rtw_ctx *c, const RtwTriangle *tris, uint32_t n) {
     c->tris.n = n; c->tris.n_nodes = b.n_nodes;
     c->tri_tree = !b.list_walk;
     c->tri_mem = std::move(m);
+    for (uint32_t i = 0; i < n; i++) if (tris[i].tex >= 0) c->tri_textured = true;
+    return RTW_OK;
+}
+
+// ---- mesh placements (rtw.h "mesh placements"; device code: rtw_mesh.h) -----------------------------------------------------------------
+int rtw_ctx_set_mesh_instances(rtw_ctx *c, const RtwMeshInstance *p, uint32_t n) {
+    if (!c) return RTW_E_INVALID;
+    if (!c->tris.n) return RTW_E_NO_SCENE;
+    if (c->pend.active || (n && !p) || (!n && p) || n > RTW_MAX_MESH_INSTANCES) return RTW_E_INVALID;
+    std::vector<f4> rows;
+    if (n) {
+        if (c->tri_textured) return RTW_E_INVALID;
+        try { rows.resize(2 * (size_t)n); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+        if (!mesh_rows(p, n, rows.data())) return RTW_E_INVALID;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    free_mesh(c);
+    if (!n) return RTW_OK;
+    MeshMem m;
+    if (const int rc = upload(m.rows, rows)) return rc;
+    c->mesh_rows = m.rows.as<f4>(); c->n_mesh = n;
+    c->mesh_mem = std::move(m);
+    return RTW_OK;
+}
+
+// What a render answers while placements are set: the placement build serves RTW_INTEGRATOR_RUST2; nothing is built for a MixedMaterial
+// object or instance rotations next to it.
+static int mesh_render_check(bool placements, uint32_t integrator, bool mixed_active, bool rotations) {
+    if (!placements) return RTW_OK;
+    if (integrator != RTW_INTEGRATOR_RUST2 || mixed_active || rotations) return RTW_E_INVALID;
     return RTW_OK;
 }
 
@@ -783,6 +828,40 @@ int rtw_ctx_triangle_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float 
     return RTW_OK;
 }
 
+int rtw_ctx_mesh_instance_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float mint, float maxt, uint32_t accel,
+                               float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out, RtwStats *stats) {
+    if (!c || !rays || !t_out || !placement_out || !tri_out || n_rays == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    if (!c->mesh_rows) return RTW_E_NO_SCENE;
+    HIP_TRY(hipSetDevice(c->device));
+    const DevTris T = tri_view(c, accel, mint, maxt);
+    const size_t ray_bytes = 6 * sizeof(float) * (size_t)n_rays, t_bytes = sizeof(float) * (size_t)n_rays, i_bytes = sizeof(int32_t) * (size_t)n_rays;
+    DevMem d_r, d_t, d_p, d_i, d_n, d_c;
+    unsigned long long cnt[2] = { 0, 0 };
+    hipError_t e = d_r.reserve(ray_bytes);
+    if (e == hipSuccess) e = d_t.reserve(t_bytes);
+    if (e == hipSuccess) e = d_p.reserve(i_bytes);
+    if (e == hipSuccess) e = d_i.reserve(i_bytes);
+    if (e == hipSuccess && normal_out) e = d_n.reserve(3 * t_bytes);
+    if (e == hipSuccess) e = d_c.reserve(sizeof cnt);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_r.ptr, rays, ray_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_c.ptr, 0, sizeof cnt, c->stream);
+    if (e == hipSuccess) {
+        launch_mesh_hits(T, c->mesh_rows, c->n_mesh, d_r.as<const float>(), n_rays, mint, maxt, d_t.as<float>(), d_p.as<int32_t>(), d_i.as<int32_t>(),
+                         normal_out ? d_n.as<float>() : nullptr, d_c.as<unsigned long long>(), c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(t_out, d_t.ptr, t_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(placement_out, d_p.ptr, i_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(tri_out, d_i.ptr, i_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && normal_out) e = hipMemcpyAsync(normal_out, d_n.ptr, 3 * t_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt, d_c.ptr, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (const int rc = call_status(c, e)) return rc;
+    if (stats) { std::memset(stats, 0, sizeof *stats); stats->quad_tests = cnt[0]; stats->node_tests = cnt[1]; }
+    return RTW_OK;
+}
+
 // ---- scene ray queries (rtw.h "scene ray queries"; kernel: rtw_query.hip) ------------------------------------------------------------
 // Is `p` memory this context's kernels can address (device or managed memory of its GPU)?  Anything else is staged.
 static bool query_on_device(const rtw_ctx *c, const void *p) {
@@ -807,6 +886,7 @@ static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_
     std::memset(&q, 0, sizeof q);
     q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom; q.inst_quats = c->inst_quats;
     if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
+    q.mesh_rows = c->mesh_rows; q.n_mesh = c->n_mesh;
     if (cam) { q.cam = *cam; q.width = width; q.height = height; }
     q.n = n; q.levels = c->bvh.depth + 2u;
     q.time = time; q.mint = mint; q.maxt = maxt; q.miss_t = miss_t; q.span = (float)c->scene_span;
@@ -981,6 +1061,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     if (p->part_count > 1 && (p->row_block == 0 || p->part_index >= p->part_count)) return RTW_E_INVALID;
     if (p->width > 65535u || p->height > 65535u) return RTW_E_INVALID;      // a lane keeps (column, row) in one register (rtw_kernels.hip Pixel)
     if (const int qrc = quats_render_check(c->inst_quats != nullptr, p->integrator, c->noise_active, c->tris.n != 0u)) return qrc;
+    if (const int prc = mesh_render_check(c->mesh_rows != nullptr, p->integrator, (p->flags & RTW_FLAG_MIXED_MATERIAL) && c->has_mixed, c->inst_quats != nullptr)) return prc;
     if (c->noise_active && p->integrator == RTW_INTEGRATOR_RUST2) return RTW_E_UNSUPPORTED;   // Rust2's textures have no noise
     if (c->noise_active && c->tris.n) return RTW_E_UNSUPPORTED;                              // (rtw_ctx_set_triangles / _set_texture_noise refuse it too)
     const bool light_integrator = p->integrator == RTW_INTEGRATOR_LIGHT_CAST || p->integrator == RTW_INTEGRATOR_LIGHT_BIASED;
@@ -1052,6 +1133,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     if (c->tris.n) a.tris = tri_view(c, p->accel, p->mint, p->maxt);   // (selects the triangle build; the tree for RTW_ACCEL_BVH requests)
     if (light_integrator) a.lights = c->lights;                    // (the integrator selects the light build, which alone reads them)
     a.inst_quats = c->inst_quats;                                  // (selects the quaternion build, whatever the integrator of the three it serves)
+    a.mesh_rows = c->mesh_rows; a.n_mesh = c->n_mesh;              // (selects the placement build)
 #ifdef RTW_ENDTIMES
     if (const char *e = getenv("RTW_ENDTIMES_REF")) a.endtimes_ref = std::strtoull(e, nullptr, 10);       // diagnostic build only
 #endif
@@ -1432,6 +1514,18 @@ int rtw_mgpu_set_instance_rotations(rtw_mgpu *m, const float (*qs)[4], uint32_t 
 int rtw_mgpu_set_triangles(rtw_mgpu *m, const RtwTriangle *tris, uint32_t n) {
     if (!m) return RTW_E_INVALID;
     for (rtw_ctx *c : m->ctx) { int rc = rtw_ctx_set_triangles(c, tris, n); if (rc != RTW_OK) return rc; }
+    return RTW_OK;
+}
+
+int rtw_mgpu_set_mesh_instances(rtw_mgpu *m, const RtwMeshInstance *p, uint32_t n) {
+    if (!m) return RTW_E_INVALID;
+    // every context holds the same triangles: the list is checked against each before any context is touched, so a refusal leaves all as they were
+    for (rtw_ctx *c : m->ctx) {
+        if (!c->tris.n) return RTW_E_NO_SCENE;
+        if (c->pend.active || (n && !p) || (!n && p) || n > RTW_MAX_MESH_INSTANCES) return RTW_E_INVALID;
+        if (n && (c->tri_textured || !mesh_rows(p, n, nullptr))) return RTW_E_INVALID;
+    }
+    for (rtw_ctx *c : m->ctx) { int rc = rtw_ctx_set_mesh_instances(c, p, n); if (rc != RTW_OK) return rc; }
     return RTW_OK;
 }
 

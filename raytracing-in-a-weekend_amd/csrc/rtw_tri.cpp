@@ -1,6 +1,7 @@
 // rtw_tri.cpp -- host side of Rust2's triangles: Triangle::new, the tree builder (binned SAH, leaves of <= 4, bounded depth), its
 // self-check and the host list walk (DESIGN.md "Rust2 triangles").
 #include "rtw_tri.h"
+#include "rtw_mesh.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -217,6 +218,44 @@ int rtw_triangle_hits(const RtwTriangle *tris, uint32_t n, const float *rays, ui
         const int k = tri_closest_host(list.data(), n, r[0], r[1], r[2], r[3], r[4], r[5], mint, maxt, t);
         t_out[i] = k >= 0 ? t : INFINITY;
         idx_out[i] = k;
+    }
+    return RTW_OK;
+}
+
+// The argument checks rtw_ctx_set_mesh_instances makes, in its order (rtw_shim.hip), without a context
+int rtw_mesh_instances_validate(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *p, uint32_t n) {
+    if (n_tris && !tris) return RTW_E_INVALID;
+    if (!n_tris) return RTW_E_NO_SCENE;
+    if ((n && !p) || (!n && p) || n > RTW_MAX_MESH_INSTANCES) return RTW_E_INVALID;
+    if (!n) return RTW_OK;
+    for (uint32_t i = 0; i < n_tris; i++) if (tris[i].tex >= 0) return RTW_E_INVALID;
+    return mesh_rows(p, n, nullptr) ? RTW_OK : RTW_E_INVALID;
+}
+
+int rtw_mesh_instance_hits(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *p, uint32_t n, const float *rays, uint32_t n_rays,
+                           float mint, float maxt, float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out) {
+    if (!rays || !t_out || !placement_out || !tri_out || n_rays == 0 || n == 0) return RTW_E_INVALID;
+    if (const int rc = rtw_mesh_instances_validate(tris, n_tris, p, n)) return rc;
+    std::vector<DevTri> list;
+    std::vector<f4> rows;
+    try { list.resize(n_tris); rows.resize(2 * (size_t)n); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+    tri_prepare(tris, n_tris, list.data());
+    mesh_rows(p, n, rows.data());
+    for (uint32_t i = 0; i < n_rays; i++) {
+        float t;
+        int j;
+        const int k = mesh_closest_host(list.data(), n_tris, rows.data(), n, rays + 6 * (size_t)i, mint, maxt, j, t);
+        t_out[i] = k >= 0 ? t : INFINITY;
+        placement_out[i] = k;
+        tri_out[i] = k >= 0 ? j : -1;
+        if (normal_out) {
+            float *o = normal_out + 3 * (size_t)i;
+            o[0] = o[1] = o[2] = 0.0f;
+            if (k >= 0) {
+                const f4 a = rows[2 * (size_t)k];
+                quat_rotate_n(qmk(a.x, a.y, a.z, a.w), list[j].normal[0], list[j].normal[1], list[j].normal[2], o[0], o[1], o[2]);
+            }
+        }
     }
     return RTW_OK;
 }

@@ -123,7 +123,7 @@ __device__ __forceinline__ bool tri_ray_ordinary(const DevTris &T, v3 o, v3 d) {
     return finite && ao + ad * T.t_bound <= RTW_TRI_COORD_MAX;
 }
 
-// (The tree half below has a TWIN, q_tri_tree in rtw_query.hip: the same boxes, paddings, skip links and tie rule, plus an exact slab for a
+// (The tree half below has a TWIN, tri_tree_walk in rtw_mesh.h: the same boxes, paddings, skip links and tie rule, plus an exact slab for a
 //  direction component that is exactly zero -- here such a ray prunes nothing, DESIGN.md 4.8.  Change the two together.)
 // The closest triangle (group rule, rtw.h): returns its index in the caller's list, or -1; bt = its t.  `found` / `ht`: the result so far.
 // With the tree the group winner is taken only when it would replace (ht > t), which is all the caller uses of it: the list walk's
