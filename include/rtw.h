@@ -305,6 +305,11 @@ enum {
                                      1 table and guides in LDS, 2 guides only, 3 table only, 4 neither -- followed where it fits in LDS  */
 };
 int  rtw_ctx_set_option(rtw_ctx *ctx, uint32_t key, double value);
+/* Which compiled build of the render kernel the context's last render launched, as text in template-argument order:
+ * "render_brute<MOVING,SPEC,GEOM>" or "render_bvh<MOVING,NODES,SPEC,GEOM>", e.g. "render_bvh<1,2,5,0>" (every band of one render runs the
+ * same build).  Host only: no device work.  RTW_E_INVALID before the context's first render, or when the n bytes of buf are too few (32 are
+ * enough).  For tests and diagnostics: which build serves a request is not part of the contract.  (added within v4) */
+int  rtw_ctx_last_render_build(rtw_ctx *ctx, char *buf, size_t n);
 
 /* ---- one frame over several GPUs of a node ------------------------------------------------------
  * The reference forks one task per image row and joins them in order (tokio: Rust/src/viewport.rs:236-244; rayon:

@@ -198,6 +198,7 @@ def lib() -> C.CDLL:
                                        C.c_void_p, C.POINTER(RtwStats)]
     L.rtw_render.argtypes = [C.POINTER(RtwCamera), C.POINTER(RtwScene), C.POINTER(RtwParams), C.c_void_p, C.POINTER(RtwStats)]
     L.rtw_ctx_set_option.argtypes = [C.c_void_p, C.c_uint32, C.c_double]
+    L.rtw_ctx_last_render_build.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rtw_mgpu_create.argtypes = [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)]
     L.rtw_mgpu_destroy.argtypes = [C.c_void_p]
     L.rtw_mgpu_destroy.restype = None
@@ -1134,6 +1135,13 @@ class Renderer:
     def set_option(self, key: int, value: float):
         """Tuning knobs (OPT_*); none of them changes the image."""
         _check(lib().rtw_ctx_set_option(self._h, int(key), float(value)), "rtw_ctx_set_option")
+
+    def last_render_build(self) -> str:
+        """Which compiled build of the render kernel this context's last render launched (rtw_ctx_last_render_build), template arguments
+        in order: "render_brute<MOVING,SPEC,GEOM>" or "render_bvh<MOVING,NODES,SPEC,GEOM>".  Raises RtwError before the first render."""
+        buf = C.create_string_buffer(64)
+        _check(lib().rtw_ctx_last_render_build(self._h, buf, len(buf)), "rtw_ctx_last_render_build")
+        return buf.value.decode()
 
     def bilateral_filter(self, img, size: int, proximity: int = PROXIMITY_SQUARE, avg_gradient: float = 0.0, out=None, shape=None,
                          in_format: Optional[int] = None):

@@ -89,8 +89,11 @@ struct KArgs {
     uint32_t n_mesh;              // the placement build (SPEC 12), which alone reads them: tris is then the mesh every placement shares
 };
 
-// accel: RTW_ACCEL_BRUTE, RTW_ACCEL_BVH; the BVH launch picks the LDS-resident variant when a.bvh.nodes16 != null
-void launch_render(const KArgs &a, bool moving, uint32_t accel, uint32_t grid, hipStream_t stream);
+// Which instantiation of render_brute<MOVING, SPEC, GEOM> / render_bvh<MOVING, NODES, SPEC, GEOM> a launch ran (nodes: 0 for render_brute)
+struct RenderBuild { bool bvh, moving, geom; int nodes, spec; };
+// accel: RTW_ACCEL_BRUTE, RTW_ACCEL_BVH; the BVH launch picks the LDS-resident variant when a.bvh.nodes16 != null; *build (if not null) receives
+// the build that was launched
+void launch_render(const KArgs &a, bool moving, uint32_t accel, uint32_t grid, hipStream_t stream, RenderBuild *build);
 // rtw_ctx_perlin_eval: out[i] = perlin_eval(*t, points[i], depth) for i < n (device pointers), on `stream`
 void launch_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t depth, float *out, hipStream_t stream);
 // rtw_ctx_triangle_hits: the closest triangle of T for each of n rays ([n][6] = o, d; device pointers), on `stream`; counters[0] triangle

@@ -1520,61 +1520,67 @@ static bool is_rust2_config(const KArgs &a) {                  // Rust2's: ray_c
     return a.integrator == RTW_INTEGRATOR_RUST2 && a.sampler == RTW_SAMPLER_CENTRES && a.depth >= 1 &&
            (a.flags & (RTW_FLAG_CPP_DIELECTRIC | RTW_FLAG_CPP_DIFFUSE)) == 0u;
 }
+// Every return site of pick_kernel_spec / pick_kernel_geom names its build twice: the function, and the tag rtw_ctx_last_render_build reports
+// (RenderBuild, rtw_kernels.h), from the same template parameter and the same runtime arguments.  `tag` may be null (occupancy query, kernel_id).
+static kernel_fn tagged(kernel_fn f, RenderBuild *tag, bool bvh, bool moving, int nodes, int spec, bool geom) {
+    if (tag) *tag = RenderBuild{ bvh, moving, geom, nodes, spec };
+    return f;
+}
 template <int SPEC>
-static kernel_fn pick_kernel_spec(bool moving, uint32_t accel, int nodes) {
+static kernel_fn pick_kernel_spec(bool moving, uint32_t accel, int nodes, RenderBuild *tag) {
     if (accel == RTW_ACCEL_BVH) {
-        if (nodes == 2) return moving ? render_bvh<true, 2, SPEC, false> : render_bvh<false, 2, SPEC, false>;
-        if (nodes == 1) return moving ? render_bvh<true, 1, SPEC, false> : render_bvh<false, 1, SPEC, false>;
-        return moving ? render_bvh<true, 0, SPEC, false> : render_bvh<false, 0, SPEC, false>;
+        if (nodes == 2) return tagged(moving ? render_bvh<true, 2, SPEC, false> : render_bvh<false, 2, SPEC, false>, tag, true, moving, 2, SPEC, false);
+        if (nodes == 1) return tagged(moving ? render_bvh<true, 1, SPEC, false> : render_bvh<false, 1, SPEC, false>, tag, true, moving, 1, SPEC, false);
+        return tagged(moving ? render_bvh<true, 0, SPEC, false> : render_bvh<false, 0, SPEC, false>, tag, true, moving, 0, SPEC, false);
     }
-    return moving ? render_brute<true, SPEC, false> : render_brute<false, SPEC, false>;
+    return tagged(moving ? render_brute<true, SPEC, false> : render_brute<false, SPEC, false>, tag, false, moving, 0, SPEC, false);
 }
 // quads / instances in the scene: the step of the generic build (SPEC == 0: everything from the kernel arguments; SPEC == 2: the common configuration folded
 // in at compile time, sphere textures kept; SPEC == 7: SPEC == 0 with texture noise) with the extra closest-hit stage (sphere geometry always global:
 // kernel_has_lds_geom)
 template <int SPEC>
-static kernel_fn pick_kernel_geom(bool moving, uint32_t accel, int nodes) {
+static kernel_fn pick_kernel_geom(bool moving, uint32_t accel, int nodes, RenderBuild *tag) {
     if (accel == RTW_ACCEL_BVH) {
-        if (nodes) return moving ? render_bvh<true, 1, SPEC, true> : render_bvh<false, 1, SPEC, true>;
-        return moving ? render_bvh<true, 0, SPEC, true> : render_bvh<false, 0, SPEC, true>;
+        if (nodes) return tagged(moving ? render_bvh<true, 1, SPEC, true> : render_bvh<false, 1, SPEC, true>, tag, true, moving, 1, SPEC, true);
+        return tagged(moving ? render_bvh<true, 0, SPEC, true> : render_bvh<false, 0, SPEC, true>, tag, true, moving, 0, SPEC, true);
     }
-    return moving ? render_brute<true, SPEC, true> : render_brute<false, SPEC, true>;
+    return tagged(moving ? render_brute<true, SPEC, true> : render_brute<false, SPEC, true>, tag, false, moving, 0, SPEC, true);
 }
-static kernel_fn pick_kernel(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
+static kernel_fn pick_kernel(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes, RenderBuild *tag = nullptr) {
     const int nodes = lds_nodes ? (a.lds_geom_off ? 2 : 1) : 0;
     // instance rotations (rtw_shim.hip sets inst_quats only then, for a scene with instances under RUST2 / LIGHT_CAST / LIGHT_BIASED): the
     // quaternion build, for every sampler and flag, with or without RTW_FLAG_MIXED_MATERIAL
-    if (a.inst_quats) return pick_kernel_geom<11>(moving, accel, nodes);
+    if (a.inst_quats) return pick_kernel_geom<11>(moving, accel, nodes, tag);
     // mesh placements (rtw_shim.hip sets mesh_rows only for a context that holds them, and serves RTW_INTEGRATOR_RUST2 alone): the placement build
-    if (a.mesh_rows) return pick_kernel_geom<12>(moving, accel, nodes);
+    if (a.mesh_rows) return pick_kernel_geom<12>(moving, accel, nodes, tag);
     // RTW_FLAG_MIXED_MATERIAL on a scene with a MixedMaterial object (rtw_shim.hip clears the bit otherwise, and refuses the flag under any
     // integrator but RUST2 / LIGHT_CAST / LIGHT_BIASED): the mixed build, for every sampler and flag
     if (a.flags & RTW_FLAG_MIXED_MATERIAL)
-        return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<10>(moving, accel, nodes) : pick_kernel_spec<10>(moving, accel, nodes);
+        return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<10>(moving, accel, nodes, tag) : pick_kernel_spec<10>(moving, accel, nodes, tag);
     // Rust2's light-biased integrators: the light build, for every sampler and flag (rtw_shim.hip refuses them with noise or triangles)
     if (a.integrator == RTW_INTEGRATOR_LIGHT_CAST || a.integrator == RTW_INTEGRATOR_LIGHT_BIASED)
-        return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<9>(moving, accel, nodes) : pick_kernel_spec<9>(moving, accel, nodes);
+        return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<9>(moving, accel, nodes, tag) : pick_kernel_spec<9>(moving, accel, nodes, tag);
     // a texture that a sphere, quad or member uses has noise (rtw_shim.hip sets noise.tex only then): the noise build, for every integrator, sampler and flag
-    if (a.noise.tex) return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<7>(moving, accel, nodes) : pick_kernel_spec<7>(moving, accel, nodes);
+    if (a.noise.tex) return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<7>(moving, accel, nodes, tag) : pick_kernel_spec<7>(moving, accel, nodes, tag);
     // triangles (rtw_shim.hip sets tris.n only then; never together with noise): the triangle build, for every integrator, sampler and flag
-    if (a.tris.n) return pick_kernel_geom<8>(moving, accel, nodes);
+    if (a.tris.n) return pick_kernel_geom<8>(moving, accel, nodes, tag);
     if (a.geom.n_quads || a.geom.n_inst) {
 #ifndef RTW_GEOM_GENERIC_ONLY
-        if (is_common_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<2>(moving, accel, nodes);
-        if (is_demo_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<4>(moving, accel, nodes);
-        if (is_rust2_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<5>(moving, accel, nodes);
-        if (is_serial_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<6>(moving, accel, nodes);
+        if (is_common_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<2>(moving, accel, nodes, tag);
+        if (is_demo_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<4>(moving, accel, nodes, tag);
+        if (is_rust2_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<5>(moving, accel, nodes, tag);
+        if (is_serial_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<6>(moving, accel, nodes, tag);
 #endif
-        return pick_kernel_geom<0>(moving, accel, nodes);
+        return pick_kernel_geom<0>(moving, accel, nodes, tag);
     }
 #ifndef RTW_GEOM_GENERIC_ONLY
-    if (is_demo_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_spec<4>(moving, accel, nodes);    // (the generic build's step, switches folded in)
-    if (is_rust2_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_spec<5>(moving, accel, nodes);
-    if (is_serial_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_spec<6>(moving, accel, nodes);
+    if (is_demo_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_spec<4>(moving, accel, nodes, tag);    // (the generic build's step, switches folded in)
+    if (is_rust2_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_spec<5>(moving, accel, nodes, tag);
+    if (is_serial_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_spec<6>(moving, accel, nodes, tag);
 #endif
-    if (!is_common_config(a)) return pick_kernel_spec<0>(moving, accel, nodes);
-    if (a.flags & RTW_FLAG_CHUNK_SUMS) return a.has_textures ? pick_kernel_spec<0>(moving, accel, nodes) : pick_kernel_spec<3>(moving, accel, nodes);
-    return a.has_textures ? pick_kernel_spec<2>(moving, accel, nodes) : pick_kernel_spec<1>(moving, accel, nodes);
+    if (!is_common_config(a)) return pick_kernel_spec<0>(moving, accel, nodes, tag);
+    if (a.flags & RTW_FLAG_CHUNK_SUMS) return a.has_textures ? pick_kernel_spec<0>(moving, accel, nodes, tag) : pick_kernel_spec<3>(moving, accel, nodes, tag);
+    return a.has_textures ? pick_kernel_spec<2>(moving, accel, nodes, tag) : pick_kernel_spec<1>(moving, accel, nodes, tag);
 }
 
 // PerlinNoise::noise / turb at n points (rtw_ctx_perlin_eval): the function the noise build's texel lookups call
@@ -1647,8 +1653,8 @@ void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const f
 
 bool kernel_has_lds_geom(const KArgs &a) { return !(a.geom.n_quads || a.geom.n_inst || a.tris.n); }
 
-void launch_render(const KArgs &a, bool moving, uint32_t accel, uint32_t grid, hipStream_t stream) {
-    hipLaunchKernelGGL(pick_kernel(a, moving, accel, a.bvh.nodes16 != nullptr), dim3(grid), dim3(RTW_BLOCK), a.lds_bytes, stream, a);
+void launch_render(const KArgs &a, bool moving, uint32_t accel, uint32_t grid, hipStream_t stream, RenderBuild *build) {
+    hipLaunchKernelGGL(pick_kernel(a, moving, accel, a.bvh.nodes16 != nullptr, build), dim3(grid), dim3(RTW_BLOCK), a.lds_bytes, stream, a);
     hipLaunchKernelGGL(resolve_kernel, dim3((a.n_tiles * 64u + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, a);
 }
 

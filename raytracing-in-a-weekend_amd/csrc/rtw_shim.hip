@@ -118,6 +118,8 @@ struct rtw_ctx {
     uint32_t opt_guided_layout = 0;      // RTW_OPT_GUIDED_LAYOUT: where rtw_ctx_guided_filter keeps its table and guide tile (0 = by size)
     uint32_t opt_grab_blocks = 2;        // RTW_OPT_GRAB_BLOCKS (profiles/r02_grab_sweep.log: 1 / 2 / 4 / 8 / a tile's 42 blocks = 83.9 / 82.9 / 83.7 / 86.8 / 107.9 ms on the bench frame)
 
+    RenderBuild last_build{};            // the render kernel the last launch ran (rtw_ctx_last_render_build); every band of a render runs the same one
+    bool has_last_build = false;
     // cache of a per-call driver query (tens of microseconds: visible on small frames)
     std::map<std::pair<const void *, uint32_t>, uint32_t> occupancy;    // (kernel, dynamic LDS bytes) -> resident workgroups per CU
     bool attr_on_device = false; int attr_device = -1;   // memory kind of this call's out_rgb
@@ -1321,7 +1323,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
             a.grab_max = (blocks ? blocks : 1u) * 64u;
         }
         HIP_TRY(hipMemsetAsync(a.queue, 0, RTW_QUEUE_BYTES, c->stream));
-        if (a.n_tiles) launch_render(a, c->sc.moving != 0, accel, grid, c->stream);
+        if (a.n_tiles) { launch_render(a, c->sc.moving != 0, accel, grid, c->stream, &c->last_build); c->has_last_build = true; }
         HIP_TRY(hipGetLastError());
         if (tile_rows == 0) break;
     }
@@ -1423,6 +1425,15 @@ struct rtw_mgpu {
 };
 
 extern "C" {
+
+// Host only: the tag launch_render left in the context, printed in template order.
+int rtw_ctx_last_render_build(rtw_ctx *c, char *buf, size_t n) {
+    if (!c || !buf || n == 0 || !c->has_last_build) return RTW_E_INVALID;
+    const RenderBuild &b = c->last_build;
+    const int len = b.bvh ? std::snprintf(buf, n, "render_bvh<%d,%d,%d,%d>", (int)b.moving, b.nodes, b.spec, (int)b.geom)
+                          : std::snprintf(buf, n, "render_brute<%d,%d,%d>", (int)b.moving, b.spec, (int)b.geom);
+    return len > 0 && (size_t)len < n ? RTW_OK : RTW_E_INVALID;
+}
 
 int rtw_ctx_set_option(rtw_ctx *c, uint32_t key, double v) {
     if (!c || !(v == v)) return RTW_E_INVALID;

@@ -20,12 +20,12 @@ CAST, BIASED, RUST2 = E.CAST, E.BIASED, E.RUST2
 TREE = ("tree, lds nodes", "tree, global nodes")
 
 
-def compare(gpu, ms, cam, p, lds_geom=False, what=""):
+def compare(gpu, ms, cam, p, lds_geom=False, what="", build=None):
     """The frame of p through every closest-hit path (list walk first) == the restatement: bit-equal or NaN in both, segments, camera rays.
     The scene and the lights are set by the caller.  Returns (reference frame, restatement's info, {variant: (image, stats)})."""
     ref, seg, info = MC.render(ms, cam, p)
     rays = p.width * p.height * LC.sampler_count(p.sampler, p.samples)[0]
-    res = variants(gpu, cam, p, lds_geom=lds_geom)
+    res = variants(gpu, cam, p, lds_geom=lds_geom, build=build)
     assert list(res)[0] == "list"
     for name, (img, st) in res.items():
         diff = ~((img.view(np.uint32) == ref.view(np.uint32)) | (np.isnan(img) & np.isnan(ref)))
@@ -84,7 +84,7 @@ def test_instances_under_lights(gpu, moving):
     ms, cam, ps = E.instance_cases(moving)
     install(gpu, ms, 0.0, 1.0)
     for p in ps:
-        ref, info, res = compare(gpu, ms, cam, p, what=f"instances moving={moving}")
+        ref, info, res = compare(gpu, ms, cam, p, what=f"instances moving={moving}", build=(9, moving, True))
         E.check_instance_info(info, moving)
         assert np.isfinite(ref).all()
         assert res["list"][1].node_tests == 0
@@ -94,7 +94,7 @@ def test_instances_under_lights(gpu, moving):
                 assert st.node_tests > 0, name
         q = R.RtwParams.from_buffer_copy(p)
         q.flags |= R.FLAG_MIXED_MATERIAL
-        for name, (img, st) in variants(gpu, cam, q).items():
+        for name, (img, st) in variants(gpu, cam, q, build=(9, moving, True)).items():
             assert np.array_equal(img, res[name][0], equal_nan=True), (moving, p.integrator, name)
             assert counters(st)[:5] == counters(res[name][1])[:5], (moving, p.integrator, name)
             if name == "list":

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import rtw_amd as R
+from tests import builds_common as B
 from tests import lights_common as LC
 from tests import oracle_binding as O
 
@@ -13,25 +14,46 @@ F = np.float32
 LIGHT = (R.INTEGRATOR_LIGHT_CAST, R.INTEGRATOR_LIGHT_BIASED)
 
 
-def variants(gpu, cam, p, lds_geom=False):
+# The kernels the enumerations through variants() declare and run (tests/test_render_builds_cpu.py holds the tables against the library),
+# each where a test passes variants() its build: the light build (SPEC 9) without quads or instances -- test_restatement_sphere_only_scene
+# here -- and with them -- test_gpu_light_edges.test_instances_under_lights --; the mixed build (SPEC 10) -- test_gpu_mixed's sphere-only
+# and GEOM restatements --; the quaternion build (SPEC 11) -- test_gpu_quat_instances.test_bounce_for_bounce --; the placement build (SPEC
+# 12) -- test_gpu_mesh_instances.test_bounce_for_bounce.
+BUILDS = B.family(9, False) | B.family(9, True) | B.family(10, False) | B.family(10, True) | B.family(11, True) | B.family(12, True)
+
+
+def variants(gpu, cam, p, lds_geom=False, build=None):
     """The frame through every closest-hit path: list walk, BVH request as shipped, tree forced with the nodes in LDS / in global memory
-    (and, sphere-only scenes, the spheres in LDS or not).  {name: (image, stats)}"""
+    (and, sphere-only scenes, the spheres in LDS or not).  {name: (image, stats)}
+    build = (SPEC, MOVING, GEOM), the build the caller declares for its scene and request: every render is then asked which kernel it ran.
+    The forced requests name theirs -- render_brute, render_bvh at NODES 1, 0, and 1 + v under RTW_OPT_LDS_GEOM = v --; with the knobs as
+    shipped the request may walk the list, and a tree without quads or instances may or may not keep its spheres in LDS."""
     out = {}
+
+    def render(name, *nodes):
+        out[name] = gpu.render(cam, p)
+        if build is not None:
+            spec, moving, geom = build
+            want = [B.tag(moving, n, spec, geom) for n in nodes]
+            got = gpu.last_render_build()
+            assert got in want and set(want) <= BUILDS, (name, got, want)
+
     p = R.RtwParams.from_buffer_copy(p)
+    auto = (1,) if build is not None and build[2] else (1, 2)
     p.accel = R.ACCEL_BRUTE
-    out["list"] = gpu.render(cam, p)
+    render("list", None)
     p.accel = R.ACCEL_BVH
-    out["bvh as shipped"] = gpu.render(cam, p)
+    render("bvh as shipped", None, *auto)
     gpu.set_option(R.OPT_LIST_WALK_MAX, 0)
     try:
-        out["tree, lds nodes"] = gpu.render(cam, p)
+        render("tree, lds nodes", *auto)
         if lds_geom:
             for v in (0, 1):
                 gpu.set_option(R.OPT_LDS_GEOM, v)
-                out[f"tree, lds geom {v}"] = gpu.render(cam, p)
+                render(f"tree, lds geom {v}", 1 + v)
             gpu.set_option(R.OPT_LDS_GEOM, -1)
         p.flags |= R.FLAG_GLOBAL_NODES
-        out["tree, global nodes"] = gpu.render(cam, p)
+        render("tree, global nodes", 0)
     finally:
         gpu.set_option(R.OPT_LIST_WALK_MAX, 48)
         gpu.set_option(R.OPT_LDS_GEOM, -1)
@@ -216,7 +238,7 @@ def test_restatement_sphere_only_scene(gpu, moving):
         plain, _ = O.render(cam, ls.scene, p, 16)
         p.integrator = integ
         assert np.isfinite(ref).all() and not np.array_equal(ref, plain)          # the lights add something
-        res = variants(gpu, cam, p, lds_geom=True)
+        res = variants(gpu, cam, p, lds_geom=True, build=(9, moving, False))
         assert res["tree, lds nodes"][1].node_tests > 0
         for name, (img, st) in res.items():
             assert np.array_equal(img, ref), (moving, integ, name, int((img != ref).sum()))

@@ -187,7 +187,7 @@ def test_bounce_for_bounce(gpu, moving, sampler):
     cam, p = frame_camera(moving), frame_params(ms, sampler)
     ref, seg = M.render(ms, cam, p, ("frame", moving))
     assert np.isfinite(ref).all()
-    res = variants(gpu, cam, p)
+    res = variants(gpu, cam, p, build=(12, moving, True))
     for name, (img, st) in res.items():
         bad = differ(img, ref)
         print(f"moving {moving} sampler {sampler} [{name}]: {int(bad.sum())} values differ, segments {st.segments} / {seg}, node tests {st.node_tests}")

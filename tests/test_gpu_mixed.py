@@ -23,11 +23,11 @@ def flagged(ms, w, h, integ, depth, **kw):
     return p
 
 
-def compare(gpu, ms, cam, p, lds_geom=False, want_tree=False):
+def compare(gpu, ms, cam, p, lds_geom=False, want_tree=False, build=None):
     """The frame of p through every closest-hit path == the restatement, bit for bit, with its segment count."""
     ref, seg, info = MC.render(ms, cam, p)
     assert np.isfinite(ref).all() and ref.max() > 0 and info["mixed_hits"] > 0
-    res = variants(gpu, cam, p, lds_geom=lds_geom)
+    res = variants(gpu, cam, p, lds_geom=lds_geom, build=build)
     if want_tree:
         assert res["tree, lds nodes"][1].node_tests > 0 and res["tree, global nodes"][1].node_tests > 0 and res["list"][1].node_tests == 0
     for name, (img, st) in res.items():
@@ -78,7 +78,7 @@ def test_restatement_geom_builds_sphere_field_and_box_instance(gpu, moving):
     gpu.set_lights(ms.lights, ms.weight)
     for integ in (R.INTEGRATOR_LIGHT_BIASED, R.INTEGRATOR_RUST2):
         p = flagged(ms, W, H, integ, 9, seed=5, sampler=R.SAMPLER_ROW if moving else R.SAMPLER_NO_RAND)
-        _, info = compare(gpu, ms, cam, p, want_tree=True)
+        _, info = compare(gpu, ms, cam, p, want_tree=True, build=(10, moving, True))
         assert (info["nonzero_time_queries"] > 0) == moving
 
 
@@ -112,7 +112,7 @@ def test_restatement_sphere_only_builds_and_the_time_of_the_scattered_ray(gpu, m
     gpu.set_lights(ms.lights, ms.weight)
     for integ in (R.INTEGRATOR_LIGHT_BIASED, R.INTEGRATOR_RUST2):
         p = flagged(ms, W, H, integ, 9, seed=8, sampler=R.SAMPLER_ROW if moving else R.SAMPLER_NO_RAND)
-        ref, info = compare(gpu, ms, cam, p, lds_geom=True, want_tree=True)
+        ref, info = compare(gpu, ms, cam, p, lds_geom=True, want_tree=True, build=(10, moving, False))
         if moving:
             assert info["time_reset"] > 0
             MC.KEEP_TIME = True

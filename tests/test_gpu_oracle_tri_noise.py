@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import rtw_amd as R
+from tests import builds_common as B
 from tests import oracle_binding as O
 from tests.test_gpu_perlin import noised_c5
 from tests.test_gpu_triangles import CONFIGS, mixed_scene, params, view
@@ -36,24 +37,31 @@ def where(img, ref):
     return f"{int(bad.sum())} pixels differ, first {np.argwhere(bad)[:3].tolist()}"
 
 
-# the builds: (name, accel, flags added, RTW_OPT_LDS_GEOM)
-LIST = ("list walk", R.ACCEL_BRUTE, 0, -1)
-NODES0 = ("tree, global nodes", R.ACCEL_BVH, R.FLAG_GLOBAL_NODES, -1)
-NODES1 = ("tree, LDS nodes", R.ACCEL_BVH, 0, 0)
-NODES2 = ("tree, LDS nodes + LDS spheres", R.ACCEL_BVH, 0, 1)
+# the builds: (name, accel, flags added, RTW_OPT_LDS_GEOM, NODES of render_bvh or None for render_brute)
+LIST = ("list walk", R.ACCEL_BRUTE, 0, -1, None)
+NODES0 = ("tree, global nodes", R.ACCEL_BVH, R.FLAG_GLOBAL_NODES, -1, 0)
+NODES1 = ("tree, LDS nodes", R.ACCEL_BVH, 0, 0, 1)
+NODES2 = ("tree, LDS nodes + LDS spheres", R.ACCEL_BVH, 0, 1, 2)
+
+# the kernels these tests declare and run (tests/test_render_builds_cpu.py holds the tables against the library): the noise build without
+# and with quads / instances, and the triangle build
+BUILDS = B.family(7, False) | B.family(7, True) | B.family(8, True)
 
 
-def against_oracle(gpu, scene, cam, p, builds, list_quad_tests=True):
-    """Render `scene` through each of `builds` and compare every image and segment count with the oracle's; the list walk's quad_tests too."""
+def against_oracle(gpu, scene, cam, p, builds, spec, moving, geom, list_quad_tests=True):
+    """Render `scene` through each of `builds` and compare every image and segment count with the oracle's; the list walk's quad_tests too.
+    Every render ran render_brute / render_bvh<moving, NODES of the build, spec, geom>."""
     ref, st_ref = O.render(cam, scene, p, THREADS, device_uv=True)
     gpu.set_scene(scene, cam.time0, cam.time0 + cam.shutter)
     gpu.set_option(R.OPT_LIST_WALK_MAX, 0)
     flags = p.flags
     try:
-        for name, accel, extra, lds_geom in builds:
+        for name, accel, extra, lds_geom, nodes in builds:
             gpu.set_option(R.OPT_LDS_GEOM, lds_geom)
             p.accel, p.flags = accel, flags | extra
             img, st = gpu.render(cam, p)
+            assert B.tag(moving, nodes, spec, geom) in BUILDS
+            B.ran(gpu, B.tag(moving, nodes, spec, geom), name)
             assert exact(img, ref), (name, where(img, ref))
             assert st.segments == st_ref.segments, (name, st.segments, st_ref.segments)
             if accel == R.ACCEL_BRUTE and list_quad_tests:
@@ -97,7 +105,7 @@ def tri_scene(moving):
 @pytest.mark.parametrize("integ,samp,flags", CONFIGS)
 def test_triangle_build_against_the_oracle(gpu, moving, integ, samp, flags):
     scene, cam = tri_scene(moving)
-    ref, st = against_oracle(gpu, scene, cam, params(integ, samp, flags), (LIST, NODES0, NODES1))
+    ref, st = against_oracle(gpu, scene, cam, params(integ, samp, flags), (LIST, NODES0, NODES1), 8, moving, True)
     assert st.segments > 0 and np.isfinite(ref).mean() > 0.99
 
 
@@ -188,7 +196,7 @@ def noise_field(moving, geom):
 def test_noise_build_against_the_oracle(gpu, moving, geom, integ, samp, flags):
     scene, cam = noise_field(moving, geom)
     builds = (LIST, NODES0, NODES1) if geom else (LIST, NODES0, NODES1, NODES2)
-    ref, st = against_oracle(gpu, scene, cam, params(integ, samp, flags), builds)
+    ref, st = against_oracle(gpu, scene, cam, params(integ, samp, flags), builds, 7, moving, geom)
     if integ in (R.INTEGRATOR_GRADIENT, R.INTEGRATOR_BG_COLOR):     # (NORMAL and FLAG read no texture)
         assert np.isnan(ref).any(axis=2).sum() > 0 and np.isfinite(ref).all(axis=2).mean() > 0.5     # the scale-0 texture is in view
 
@@ -196,7 +204,8 @@ def test_noise_build_against_the_oracle(gpu, moving, geom, integ, samp, flags):
 def test_noised_c5_against_the_oracle(gpu):
     _, noised, cam, p = noised_c5()
     p.gamma = 1.0
-    ref, st = against_oracle(gpu, noised, cam, p, (LIST, NODES0, NODES1))
+    assert any(noised._spheres[i].velocity[1] != 0 for i in range(noised.n_spheres)) and noised.n_quads == noised.n_instances == 0
+    ref, st = against_oracle(gpu, noised, cam, p, (LIST, NODES0, NODES1), 7, True, False)
     assert st.nan_pixels > 0 and np.isfinite(ref).all(axis=2).mean() > 0.1
 
 
@@ -214,6 +223,6 @@ def test_noise_seen_after_a_metal_bounce(gpu):
     plain = R.Scene(spheres, textures=[tex], background=(0.2, 0.3, 0.4))
     for integ in (R.INTEGRATOR_GRADIENT, R.INTEGRATOR_BG_COLOR):
         p = params(integ, R.SAMPLER_ROW, 0)
-        ref, _ = against_oracle(gpu, scene, cam, p, (LIST, NODES0, NODES1, NODES2))
+        ref, _ = against_oracle(gpu, scene, cam, p, (LIST, NODES0, NODES1, NODES2), 7, False, False)
         without, _ = O.render(cam, plain, p, THREADS, device_uv=True)
         assert not np.array_equal(ref, without)                    # the noise reaches the image

@@ -150,9 +150,9 @@ def test_depth_one_known_answer(gpu):
 
 
 # ---- 4. bounce for bounce, through every kernel of the build -------------------------------------------------------------------------------------
-def compare_frames(gpu, qs, cam, p, key, names=None):
+def compare_frames(gpu, qs, cam, p, key, names=None, build=None):
     ref, seg, info = Q.render(qs, cam, p, key=key)
-    res = variants(gpu, cam, p)
+    res = variants(gpu, cam, p, build=build)
     for name, (img, st) in res.items():
         bad = differ(img, ref)
         print(f"{key} integrator {p.integrator} depth {p.depth} flags {p.flags} [{name}]: {int(bad.sum())} values differ, segments {st.segments} / {seg}, "
@@ -187,7 +187,7 @@ def test_bounce_for_bounce(gpu, integrator, moving):
     qs.install(gpu, 0.0, 1.0)
     cam = Q.camera(g, 24, 24)
     for depth in (2, 6):                                             # (LIGHT_CAST ignores the depth: the same frame twice)
-        ref, info, res = compare_frames(gpu, qs, cam, qs.params(24, 24, integrator, depth, seed=7), ("lit", moving))
+        ref, info, res = compare_frames(gpu, qs, cam, qs.params(24, 24, integrator, depth, seed=7), ("lit", moving), build=(11, moving, True))
         assert np.isfinite(ref).all()
         assert res["list"][1].node_tests == 0 and res["tree, lds nodes"][1].node_tests > 0 and res["tree, global nodes"][1].node_tests > 0
         if integrator != RUST2:

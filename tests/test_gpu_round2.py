@@ -10,9 +10,14 @@ import pytest
 import rtw_amd as R
 from tests import oracle_binding as O
 from tests.test_oracle_golden import small_view, flag_params, GOLD
+from tests import builds_common as B
 from tests.test_abi_and_host import geometric_scene
 
 pytestmark = pytest.mark.gpu
+
+# the builds test_every_build_of_the_traversal_kernel declares and runs (tests/test_render_builds_cpu.py holds the tables against the library):
+# SPEC 0 (generic), 1 (common configuration), 2 (... with textures), 3 (... with chunk sums) without quads or instances
+BUILDS = B.family(0, False) | B.family(1, False) | B.family(2, False) | B.family(3, False)
 
 
 # ---- rtw_mgpu: fork / ordered join of the row tasks over GPUs (Rust/src/viewport.rs:236-244) ------------------------
@@ -431,10 +436,12 @@ def test_grab_size_never_changes_the_image(rtw, blocks):
 @pytest.mark.parametrize("moving", [False, True])
 @pytest.mark.parametrize("textured", [False, True])
 def test_every_build_of_the_traversal_kernel(gpu, moving, textured):
-    """render_bvh is compiled 28 times (MOVING x NODES {global f32 nodes, LDS f16 nodes, LDS nodes + LDS sphere geometry} x SPEC
-    {generic, common, textured, chunk sums} + the GEOM builds); which build a request runs depends on the scene's size, motion and
-    textures, on the integrator and on three knobs.  A scene of 130 spheres (small enough for its geometry to fit in LDS, large
-    enough to be given to the tree) is rendered through every build it can reach and each image compared with the oracle."""
+    """The render kernels are templates over MOVING, NODES {global f32 nodes, LDS f16 nodes, LDS nodes + LDS sphere geometry}, SPEC and
+    GEOM, compiled once per combination in use (tests/test_render_builds_cpu.py reads the list from the library); which build a request
+    runs depends on the scene's size, motion and textures, on the integrator and on three knobs.  A scene of 130 spheres (small enough
+    for its geometry to fit in LDS, large enough to be given to the tree) is rendered through the 32 builds of SPEC 0..3 without quads
+    or instances (BUILDS above: render_brute and render_bvh at each NODES, static and MOVING), each image compared with the oracle and
+    each render asked which build it ran."""
     rng = np.random.default_rng(5 + 2 * moving + textured)
     tex = rng.uniform(0.1, 0.9, size=(4, 6, 3)).astype(np.float32)
     mats = [R.SCATTER_M, R.METALLIC_M, R.GLASS_M, R.FUZZY3_M]
@@ -455,9 +462,10 @@ def test_every_build_of_the_traversal_kernel(gpu, moving, textured):
         same = (img == ref).all(axis=2)                       # (atan2f / acosf: a hit may fall on the other side of a texel edge)
         return same.mean() > 0.998 and np.abs(img - ref).max() < 1.0
 
-    seen = set()
+    seen, ran = set(), set()
     for integrator in (R.INTEGRATOR_GRADIENT, R.INTEGRATOR_NORMAL):          # SPEC 1 / 2 builds, and the generic build
         for flags in (0, R.FLAG_CHUNK_SUMS):                                   # ... SPEC 3 (gradient, untextured) or generic
+            spec = 0 if integrator == R.INTEGRATOR_NORMAL else ((0 if textured else 3) if flags else (2 if textured else 1))
             p = vp.params(integrator, R.SAMPLER_ROW)
             p.gamma, p.flags = 1.0, flags
             ref, st_ref = O.render(cam, scene, p, threads=16)
@@ -467,13 +475,19 @@ def test_every_build_of_the_traversal_kernel(gpu, moving, textured):
                     gpu.set_option(R.OPT_LDS_GEOM, lds_geom)
                     p.accel, p.flags = R.ACCEL_BVH, flags | extra
                     img, st = gpu.render(cam, p)
+                    want = B.bvh(moving, 0 if extra else 1 + lds_geom, spec, False)
+                    B.ran(gpu, want, (integrator, flags, lds_geom, extra))
+                    ran.add(want)
                     assert st.node_tests > 0 and st.segments == st_ref.segments, (integrator, flags, lds_geom, extra)
                     assert close(img, ref), (integrator, flags, lds_geom, extra)
                     assert np.array_equal(img.view(np.uint32), dev.view(np.uint32)), (integrator, flags, lds_geom, extra)
                     seen.add((integrator, flags, lds_geom, extra))
             p.accel, p.flags = R.ACCEL_BRUTE, flags
             img, st = gpu.render(cam, p)
+            B.ran(gpu, B.brute(moving, spec, False), (integrator, flags))
+            ran.add(B.brute(moving, spec, False))
             assert st.segments == st_ref.segments and close(img, ref)
             assert np.array_equal(img.view(np.uint32), dev.view(np.uint32)), (integrator, flags)
     gpu.set_option(R.OPT_LDS_GEOM, -1)
     assert len(seen) == 16
+    assert ran <= BUILDS and len(ran) == (8 if textured else 12)      # (textured: SPEC 0 and 2; plain: SPEC 0, 1 and 3 -- x the list walk and NODES 0, 1, 2)
