@@ -301,8 +301,13 @@ enum {
                                      0 (default) = one unit length for the whole launch.  Measured: no gain.  v4                 */
     RTW_OPT_SUB_QUEUES       = 8, /* 0 (default): the work queue is eight sub-queues with a counter each (a wave starts on the one of its
                                      XCD and helps out on the others when it is empty), a single one for tiny launches; 1: always single */
-    RTW_OPT_GUIDED_LAYOUT    = 10 /* rtw_ctx_guided_filter: 0 (default) places the weight table and the guide tile by size;
+    RTW_OPT_GUIDED_LAYOUT    = 10,/* rtw_ctx_guided_filter: 0 (default) places the weight table and the guide tile by size;
                                      1 table and guides in LDS, 2 guides only, 3 table only, 4 neither -- followed where it fits in LDS  */
+    RTW_OPT_NODE_FORMAT      = 11 /* how a static sphere scene's tree lives in LDS where the common-configuration builds of the BVH render
+                                     kernel serve it: 0 (default) as f32 planes, walked by workgroups of 768 threads, where two of them fit a
+                                     CU's LDS, else as f16 nodes; 1 f16 nodes (the build that keeps the sphere geometry in LDS too, whatever
+                                     RTW_OPT_LDS_GEOM says); 2 f32 planes wherever one workgroup fits.  Other builds walk f16 nodes whatever
+                                     it says.  Any other value: RTW_E_INVALID.  The walk, the counters and the image are the same */
 };
 int  rtw_ctx_set_option(rtw_ctx *ctx, uint32_t key, double value);
 /* Which compiled build of the render kernel the context's last render launched, as text in template-argument order:
@@ -310,6 +315,9 @@ int  rtw_ctx_set_option(rtw_ctx *ctx, uint32_t key, double value);
  * same build).  Host only: no device work.  RTW_E_INVALID before the context's first render, or when the n bytes of buf are too few (32 are
  * enough).  For tests and diagnostics: which build serves a request is not part of the contract.  (added within v4) */
 int  rtw_ctx_last_render_build(rtw_ctx *ctx, char *buf, size_t n);
+/* ... and the format of the tree that build read from LDS: 0 none (list walk, or nodes in global memory), 1 f16 nodes, 2 f32 planes
+ * (RTW_OPT_NODE_FORMAT).  Host only.  RTW_E_INVALID before the context's first render.  (added within v4) */
+int  rtw_ctx_last_node_format(rtw_ctx *ctx);
 
 /* ---- one frame over several GPUs of a node ------------------------------------------------------
  * The reference forks one task per image row and joins them in order (tokio: Rust/src/viewport.rs:236-244; rayon:
@@ -754,6 +762,11 @@ int rtw_bvh_validate(const RtwScene *scene, float t_begin, float t_end,
  * spheres kept outside the tree; depth_cap is the depth the builder allowed itself.  Every output pointer may be NULL. */
 int rtw_bvh_dump(const RtwScene *scene, float t_begin, float t_end, void *nodes, uint32_t node_cap, uint32_t *n_nodes, int32_t *root,
                  uint32_t *depth, uint32_t *depth_cap, uint32_t *big, uint32_t big_cap, uint32_t *n_big, uint16_t *nodes16);
+/* The f32 plane format of those f16 nodes, as the large-workgroup builds of the render kernel hold a tree in LDS (RTW_OPT_NODE_FORMAT): every
+ * plane widened exactly, laid out so that a ray reads {near, far} of a (box, axis) at a per-ray offset.  out: n_nodes * layout[0] dwords (may
+ * be NULL: layout only); layout[4] = dwords per node, dwords per (box, axis) group, the byte offset at which a ray along +axis reads its
+ * pair (a ray along -axis reads at 0), the code of an inner child per node index.  A testing tool, no GPU. */
+int rtw_bvh_pack_nodes32(const uint16_t *nodes16, uint32_t n_nodes, uint32_t *out, uint32_t out_cap, uint32_t *layout);
 /* Host twin of the render kernel's closest-hit query over that tree (a measuring and testing tool, no GPU): rays = n x {origin[3],
  * direction[3]}; hit[i] = sphere index or -1, t[i] its parameter, visits[i] (optional) the inner-node visits, counted as
  * RtwStats.node_tests counts them.  use_tree == 0 walks the sphere list with the same sphere test.  The tree is built once per CALL:

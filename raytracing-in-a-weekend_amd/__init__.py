@@ -49,6 +49,8 @@ FLAG_CPP = FLAG_CPP_DIELECTRIC | FLAG_CPP_DIFFUSE      # what Viewport::RenderGP
 FLAG_MIXED_MATERIAL = 32   # Rust2's integrators: an object with opacity < 0 is MixedMaterial::new(ir) (see mixed())
 OPT_CHUNK_LEN, OPT_SAMPLE_BANK_GB, OPT_LDS_GEOM, OPT_BLOCKS_PER_CU, OPT_LIST_WALK_MAX, OPT_TILE_ORDER, OPT_GRAB_BLOCKS, OPT_SUB_QUEUES = 1, 2, 3, 4, 5, 6, 7, 8
 OPT_TAIL_UNITS = 9
+OPT_NODE_FORMAT = 11                                 # the large-workgroup BVH builds' tree in LDS: 0 f32 planes where they fit, 1 f16 nodes, 2 f32 planes
+NODE_FORMAT_NONE, NODE_FORMAT_F16, NODE_FORMAT_F32 = 0, 1, 2   # Renderer.last_node_format
 OPT_GUIDED_LAYOUT = 10                               # Renderer.guided_filter: 0 by size, 1 table + guides in LDS, 2 guides, 3 table, 4 neither
 SCENE_C1, SCENE_C2, SCENE_C4, SCENE_C5, SCENE_METAL_TEST, SCENE_QUAD_TEST, SCENE_PRESENTATION, SCENE_FIRST_FRAME = 1, 2, 4, 5, 6, 7, 8, 9
 MEDIUM_SURFACE, MEDIUM_CONST_DENSITY = 0, 1
@@ -199,6 +201,7 @@ def lib() -> C.CDLL:
     L.rtw_render.argtypes = [C.POINTER(RtwCamera), C.POINTER(RtwScene), C.POINTER(RtwParams), C.c_void_p, C.POINTER(RtwStats)]
     L.rtw_ctx_set_option.argtypes = [C.c_void_p, C.c_uint32, C.c_double]
     L.rtw_ctx_last_render_build.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.rtw_ctx_last_node_format.argtypes = [C.c_void_p]
     L.rtw_mgpu_create.argtypes = [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)]
     L.rtw_mgpu_destroy.argtypes = [C.c_void_p]
     L.rtw_mgpu_destroy.restype = None
@@ -230,6 +233,7 @@ def lib() -> C.CDLL:
     L.rtw_bvh_validate.argtypes = [C.POINTER(RtwScene), C.c_float, C.c_float] + [C.POINTER(C.c_uint32)] * 4
     L.rtw_bvh_dump.argtypes = [C.POINTER(RtwScene), C.c_float, C.c_float, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]
+    L.rtw_bvh_pack_nodes32.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
     L.rtw_bvh_query_host.argtypes = [C.POINTER(RtwScene), C.c_float, C.c_float, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float,
                                      C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rtw_scene_generate.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(RtwSphere), C.c_uint32, C.POINTER(C.c_uint32),
@@ -1142,6 +1146,14 @@ class Renderer:
         buf = C.create_string_buffer(64)
         _check(lib().rtw_ctx_last_render_build(self._h, buf, len(buf)), "rtw_ctx_last_render_build")
         return buf.value.decode()
+
+    def last_node_format(self) -> int:
+        """The format of the tree that build read from LDS (rtw_ctx_last_node_format): NODE_FORMAT_NONE (list walk, or nodes in global
+        memory), NODE_FORMAT_F16 or NODE_FORMAT_F32 (OPT_NODE_FORMAT).  Raises RtwError before the first render."""
+        rc = lib().rtw_ctx_last_node_format(self._h)
+        if rc < 0:
+            _check(rc, "rtw_ctx_last_node_format")
+        return rc
 
     def bilateral_filter(self, img, size: int, proximity: int = PROXIMITY_SQUARE, avg_gradient: float = 0.0, out=None, shape=None,
                          in_format: Optional[int] = None):

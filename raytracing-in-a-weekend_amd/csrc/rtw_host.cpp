@@ -868,6 +868,24 @@ void build_bvh(const RtwSphere *spheres, uint32_t n, float t_begin, float t_end,
     }
 }
 
+void pack_nodes32(const std::vector<BvhNode16> &nodes16, std::vector<uint32_t> &out) {
+    const uint32_t AX = RTW_NODE32_AXIS_DWORDS, ND = RTW_NODE32_DWORDS;
+    out.assign(nodes16.size() * ND, 0u);
+    auto widen = [](uint16_t h) { _Float16 v; std::memcpy(&v, &h, 2); const float f = (float)v; uint32_t u; std::memcpy(&u, &f, 4); return u; };
+    auto code = [](int16_t c) { return (uint32_t)(uint16_t)(c >= 0 ? (c / 32) * (int)RTW_NODE32_CODE : (int)c); };   // (BvhNode16: inner child = index * 32)
+    for (size_t i = 0; i < nodes16.size(); i++) {
+        const BvhNode16 &a = nodes16[i];
+        uint32_t *d = out.data() + i * ND;
+        for (int c = 0; c < 2; c++) for (int k = 0; k < 3; k++) {
+            const uint32_t lo = widen(a.plane[c][k][0]), hi = widen(a.plane[c][k][1]);
+            uint32_t *q = d + (size_t)(c * 3 + k) * AX;
+            q[0] = hi; q[1] = lo; q[2] = lo; q[3] = hi;
+        }
+        const uint32_t cc = code(a.c0) | (code(a.c1) << 16);
+        d[6u * AX] = cc; d[6u * AX + RTW_NODE32_OFF / 4u] = cc;          // (read at plane offset 6 * AX + the ray's x offset, 0 or RTW_NODE32_OFF)
+    }
+}
+
 } // namespace rtw
 
 // ---- host twin of the device query -------------------------------------------------------------------------------------------
@@ -958,6 +976,22 @@ extern "C" int rtw_bvh_dump(const RtwScene *sc, float t_begin, float t_end, void
     if (nodes) { if (node_cap < b.nodes.size()) return RTW_E_INVALID; std::memcpy(nodes, b.nodes.data(), b.nodes.size() * sizeof(BvhNode)); }
     if (big) { if (big_cap < b.big.size()) return RTW_E_INVALID; std::copy(b.big.begin(), b.big.end(), big); }
     if (nodes16 && !b.nodes16.empty()) { if (node_cap < b.nodes16.size()) return RTW_E_INVALID; std::memcpy(nodes16, b.nodes16.data(), b.nodes16.size() * sizeof(BvhNode16)); }
+    return RTW_OK;
+}
+
+// The f32 plane format of n_nodes f16 nodes as the render kernel's large-workgroup builds copy it into LDS (rtw_host.h pack_nodes32).
+// layout (4 values): dwords per node, dwords per (box, axis) group, a +axis ray's read offset in bytes, an inner child's code per node index.
+// out may be NULL (layout only); out_cap in dwords.
+extern "C" int rtw_bvh_pack_nodes32(const uint16_t *nodes16, uint32_t n_nodes, uint32_t *out, uint32_t out_cap, uint32_t *layout) {
+    using namespace rtw;
+    if (layout) { layout[0] = RTW_NODE32_DWORDS; layout[1] = RTW_NODE32_AXIS_DWORDS; layout[2] = RTW_NODE32_OFF; layout[3] = RTW_NODE32_CODE; }
+    if (!out) return RTW_OK;
+    if (!nodes16 || out_cap < (uint64_t)n_nodes * RTW_NODE32_DWORDS) return RTW_E_INVALID;
+    std::vector<BvhNode16> in(n_nodes);
+    std::memcpy(in.data(), nodes16, (size_t)n_nodes * sizeof(BvhNode16));
+    std::vector<uint32_t> packed;
+    pack_nodes32(in, packed);
+    std::memcpy(out, packed.data(), packed.size() * sizeof(uint32_t));
     return RTW_OK;
 }
 

@@ -39,6 +39,23 @@ static_assert(sizeof(BvhNode16) == 32, "BvhNode16 must be 32 bytes");
 #define RTW_LDS_NODES_MAX 512 // inner nodes the LDS variant holds (16 KB)
 #define RTW_LDS_GEOM_MAX 640  // spheres whose {centre, r^2} the LDS variant also keeps on chip for the leaf tests (10 KB)
 
+// The same node with its planes widened to f32 (exactly: every f16 value is an f32 value), for the render builds that read a ray's
+// {near, far} pair straight out of LDS at a per-ray address instead of permuting and widening it (rtw_kernels.hip trav_node_lds32).
+// RTW_NODE32_DWORDS (28) dwords per node: per (box, axis), in BvhNode16's order, a group of four planes {hi, lo, lo, hi} -- a pair read
+// RTW_NODE32_OFF (8) bytes into the group is {lo, hi} (a ray along +axis), one read at its start {hi, lo} (along -axis); either read is
+// 8-byte aligned (pairs at 4-byte alignment, out of {hi, lo, hi}, were measured ruinous: profiles/f32_planes_ab.log) -- then the dword
+// {c0, c1} of 16-bit child codes at dwords 24 and 26, where a read at either per-ray offset finds it, so that it needs no address of its own.
+// A leaf's code is BvhNode16's (~sphere); an inner child is named by its LDS offset in units of 8 bytes (1 << RTW_NODE32_UNIT_SHIFT):
+// index * RTW_NODE32_CODE.  In bytes, as the f16 format names them, the last of Book-1's 480 nodes (53648) would not fit below the END /
+// DEAD codes 0x7FFF / 0x7FFE of the 16-bit stack entries; in these units every tree with f16 nodes does (511 * 14 = 7154).
+#define RTW_NODE32_AXIS_DWORDS 4u
+#define RTW_NODE32_OFF 8u
+#define RTW_NODE32_DWORDS 28u
+#define RTW_NODE32_UNIT_SHIFT 3u
+#define RTW_NODE32_CODE (RTW_NODE32_DWORDS * 4u >> RTW_NODE32_UNIT_SHIFT)   // 14
+#define RTW_NODE32_NODES_MAX (0x7FFDu / RTW_NODE32_CODE + 1u)             // the code range's limit (2341 nodes); RTW_LDS_NODES_MAX binds first
+static_assert(RTW_LDS_NODES_MAX <= RTW_NODE32_NODES_MAX, "every tree with f16 nodes has f32 planes");
+
 #define RTW_MAX_BIG 16        // spheres far larger than the rest are tested exactly, outside the tree
 #define RTW_BVH_STACK 24      // builder guarantees depth <= RTW_BVH_STACK (median-split fallback near the limit)
 #define RTW_BVH_LDS_LEVEL_BYTES 512u   // one level of the LDS-variant's per-lane stack: RTW_BLOCK (256) lanes x a 16-bit entry
@@ -77,6 +94,10 @@ uint32_t bvh_depth_cap(uint32_t n_leaves, uint32_t n_spheres, bool lds_candidate
 // Bounds cover centre(t) = origin + velocity * t for t in [t_begin, t_end] (sphere.rs:100); the
 // reference's own AABB ignores velocity (aabb/aabb.rs:27-39) and so culls moving spheres wrongly.
 void build_bvh(const RtwSphere *spheres, uint32_t n, float t_begin, float t_end, BvhBuild &out, const BvhBuildOptions &opt = BvhBuildOptions());
+
+// The f32 plane format of a tree's f16 nodes (above): derived from nodes16 by widening, never a second rounding of the f32 boxes -- the
+// walk over it is then the walk over nodes16, decision for decision.  Empty in, empty out.
+void pack_nodes32(const std::vector<BvhNode16> &nodes16, std::vector<uint32_t> &out);
 
 // Host twin of the render kernel's closest-hit query over a built tree (a measuring and testing tool: the product traverses on the
 // GPU).  Same order of events: the big list first, per-ray rho / tau, boxes inflated by rho, the f16 outward-rounded planes when the

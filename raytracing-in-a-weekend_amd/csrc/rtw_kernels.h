@@ -14,6 +14,7 @@
 #ifndef RTW_BLOCK
 #define RTW_BLOCK 256   // 4 waves per workgroup
 #endif
+#define RTW_BLOCK_LARGE 768   // 12 waves: the static LDS-node builds that walk f32 planes (rtw_kernels.hip bvh_block); two per CU
 #define RTW_N_STATS 64  // 64-bit counters a render launch accumulates (KArgs.stats); [32..63] are used by the -DRTW_CENSUS diagnostic build only
 #ifndef RTW_LIST_WALK_MAX_DEFAULT
 #define RTW_LIST_WALK_MAX_DEFAULT 48u  // RTW_OPT_LIST_WALK_MAX: scenes this small walk the list even when the BVH is asked for (measured crossover ~56 spheres: profiles/r02_crossover.log)
@@ -87,6 +88,8 @@ struct KArgs {
                                   // the quaternion build (SPEC 11), which alone reads it (and the lights, for every integrator it serves)
     const f4 *mesh_rows;          // mesh placements (rtw_ctx_set_mesh_instances): two rows {qn}, {position, 0} per placement (rtw_mesh.h); non-null selects
     uint32_t n_mesh;              // the placement build (SPEC 12), which alone reads them: tris is then the mesh every placement shares
+    const uint32_t *nodes32;      // the tree's f32 plane format (rtw_host.h pack_nodes32): what the large-workgroup builds (kernel_block() !=
+                                  // RTW_BLOCK) copy into LDS instead of bvh.nodes16; they alone read it
 };
 
 // Which instantiation of render_brute<MOVING, SPEC, GEOM> / render_bvh<MOVING, NODES, SPEC, GEOM> a launch ran (nodes: 0 for render_brute)
@@ -133,6 +136,12 @@ void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const f
                       int32_t *placement_out, int32_t *tri_out, float *normal_out, unsigned long long *counters, hipStream_t stream);
 // Resident workgroups per CU for the kernel variant (occupancy API), >= 1.
 uint32_t kernel_blocks_per_cu(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);
+// Threads per workgroup of the kernel variant launch_render would pick: RTW_BLOCK, or RTW_BLOCK_LARGE for the builds that walk the f32 plane
+// format (KArgs.nodes32).  The shim sizes the LDS stack, the grid and the queue's grabs by it.
+uint32_t kernel_block(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);
+// Let that kernel variant be launched with a.lds_bytes of dynamic LDS where they exceed the 64 KiB a workgroup gets by default (a large
+// workgroup's f32 planes and stack do: Book-1 73.5 KB).  Per kernel and device; the shim calls it once per (kernel, size).
+hipError_t kernel_allow_lds(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);
 // Is there a build of the BVH kernel for this configuration that reads the spheres' {centre, r^2} from LDS?  (KArgs.lds_geom_off may only be set then)
 bool kernel_has_lds_geom(const KArgs &a);
 // The kernel variant launch_render would pick, as an opaque id (key of the per-context occupancy cache).

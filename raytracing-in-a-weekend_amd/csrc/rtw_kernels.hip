@@ -869,14 +869,15 @@ struct Trav {                // traversal state of one lane
     int node;                // the lane's PHASE is encoded here: 0 <= node < DEAD an inner node to visit (TRAVERSE; LDS variant: its byte offset);
                              // above END (as unsigned) the leaf ~node to test (LEAF; LDS variant: 16-bit codes, zero-extended);
                              // END: no query pending, the lane waits for a SHADE step; DEAD: finished
-    uint32_t sp;             // LDS byte ADDRESS of the TOP entry of this lane's stack, base + (level * RTW_BLOCK + threadIdx.x) * sizeof(entry);
+    uint32_t sp;             // LDS byte ADDRESS of the TOP entry of this lane's stack, base + (level * workgroup size + threadIdx.x) * sizeof(entry);
                              // level 0 holds the END sentinel, so a pop never has to ask whether the stack is empty
     int best; float best_t;  // closest accepted hit so far (best_t starts at maxt)
     float a, ra;             // d.d and rcp_refined(d.d) (sphere_root)
     float ix, iy, iz;        // 1/d
     float kpx, kpy, kpz;     // global-node variant: -(o + rho) / d (goes with a box's lo planes); LDS variant: the NEAR planes' constant
     float kmx, kmy, kmz;     // global-node variant: -(o - rho) / d (hi planes);                    LDS variant: the FAR planes' constant
-    uint32_t selx, sely, selz;   // LDS variant: v_perm_b32 selector per axis, identity when the ray runs along +axis, half-swap otherwise
+    uint32_t selx, sely, selz;   // LDS variant: v_perm_b32 selector per axis, identity when the ray runs along +axis, half-swap otherwise;
+                                 // f32 plane format: the byte offset per axis at which the ray reads its {near, far} pair (trav_node_lds32)
     float tau_t, lo_lim, hi_lim;
 };
 
@@ -930,7 +931,8 @@ template <class T> __device__ __forceinline__ T lds_get(uint32_t addr) { return 
 template <class T> __device__ __forceinline__ void lds_put(uint32_t addr, T v) { *(__attribute__((address_space(3))) T *)(uintptr_t)addr = v; }
 __device__ __forceinline__ uint32_t lds_addr(const void *p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p; }
 
-template <bool MOVING, class S>
+// F32: the LDS copy is the f32 plane format (the builds that visit nodes with trav_node_lds32)
+template <bool MOVING, class S, bool F32 = false>
 __device__ __forceinline__ void trav_begin(const KArgs &A, const Path &pt, Trav &tr, uint32_t sp0, bool a_plain_wave, bool &a_odd, Cen *cn = nullptr) {
     RTW_CEN(cn, CEN_TRAV_BEGIN);
     const BvhBegin bv = load_bvh_begin();
@@ -954,7 +956,7 @@ __device__ __forceinline__ void trav_begin(const KArgs &A, const Path &pt, Trav 
     }
     if (bv.root == (int)0x80000000) { tr.node = (int)Code<S>::END; return; }   // no tree: the query is complete
     // (LDS variant: inner nodes by byte offset, trav_node_lds; every code zero-extended from 16 bits)
-    tr.node = sizeof(S) == 2 ? (bv.root >= 0 ? bv.root * 32 : (int)((uint32_t)bv.root & 0xFFFFu)) : bv.root;
+    tr.node = sizeof(S) == 2 ? (bv.root >= 0 ? bv.root * (F32 ? (int)RTW_NODE32_CODE : 32) : (int)((uint32_t)bv.root & 0xFFFFu)) : bv.root;
     // per-ray constants of the thick-ray slab test.  Everything here only feeds CONSERVATIVE bounds, so
     // the hardware approximations (v_sqrt_f32 / v_rcp_f32 / v_rsq_f32, <= 1 ulp) are used with the
     // 1e-4 relative safety factors below instead of the correctly-rounded sequences.
@@ -996,9 +998,17 @@ __device__ __forceinline__ void trav_begin(const KArgs &A, const Path &pt, Trav 
         tr.kpx = ox - rx; tr.kpy = oy - ry; tr.kpz = oz - rz;
         tr.kmx = ox + rx; tr.kmy = oy + ry; tr.kmz = oz + rz;
         const uint32_t ID = 0x03020100u, FLIP = 0x03020100u ^ 0x01000302u;      // selector XOR mask: all ones where 1/d < 0
+        if (F32) {
+            // f32 plane format: the same choice by the same bit, made by WHERE the pair is read -- {lo, hi} sits RTW_NODE32_OFF bytes into the
+            // (box, axis) group, {hi, lo} at its start (rtw_host.h)
+            tr.selx = ~(uint32_t)((int32_t)__float_as_uint(ix) >> 31) & RTW_NODE32_OFF;
+            tr.sely = ~(uint32_t)((int32_t)__float_as_uint(iy) >> 31) & RTW_NODE32_OFF;
+            tr.selz = ~(uint32_t)((int32_t)__float_as_uint(iz) >> 31) & RTW_NODE32_OFF;
+        } else {
         tr.selx = ID ^ ((uint32_t)((int32_t)__float_as_uint(ix) >> 31) & FLIP);
         tr.sely = ID ^ ((uint32_t)((int32_t)__float_as_uint(iy) >> 31) & FLIP);
         tr.selz = ID ^ ((uint32_t)((int32_t)__float_as_uint(iz) >> 31) & FLIP);
+        }
     } else {
         // t(lo) = (lo - rho - o) * inv = fma(lo, inv, -(o + rho) * inv);  t(hi) = fma(hi, inv, -(o - rho) * inv)
         tr.kpx = -(o.x + rho) * ix; tr.kpy = -(o.y + rho) * iy; tr.kpz = -(o.z + rho) * iz;
@@ -1010,10 +1020,10 @@ __device__ __forceinline__ void trav_begin(const KArgs &A, const Path &pt, Trav 
 
 
 // After a leaf test: take the next entry off the stack (the sentinel of level 0 ends the query).
-template <class S>
+template <class S, uint32_t BLOCK = RTW_BLOCK>
 __device__ __forceinline__ void trav_pop(Trav &tr) {
     tr.node = (int)(uint32_t)lds_get<typename std::make_unsigned<S>::type>(tr.sp);
-    tr.sp -= RTW_BLOCK * (uint32_t)sizeof(S);      // (may step below level 0 when the sentinel came off: sp is not used again before trav_begin)
+    tr.sp -= BLOCK * (uint32_t)sizeof(S);      // (may step below level 0 when the sentinel came off: sp is not used again before trav_begin)
 }
 
 template <class S> __device__ __forceinline__ int entry_to_node(uint32_t raw);
@@ -1024,7 +1034,7 @@ template <> __device__ __forceinline__ int entry_to_node<int>(uint32_t raw) { re
 // the farther child is stored ABOVE the top unconditionally (it only counts when sp moves up), and the entry a pop would
 // return was read by the caller before the box tests (`popped`), so its LDS latency hides behind them.
 // c0 / c1 / popped are raw stack entries (for 16-bit entries: the id in the low half, upper bits ignored).
-template <class S>
+template <class S, uint32_t BLOCK = RTW_BLOCK>
 __device__ __forceinline__ void trav_descend(Trav &tr, float e0, float x0, float e1, float x1,
                                              uint32_t c0, uint32_t c1, uint32_t popped) {
     // hit <=> [max(entry, lo_lim), min(exit, hi_lim)] is non-empty (lo_lim <= hi_lim always: best_t >= mint): two min/max and
@@ -1036,7 +1046,7 @@ __device__ __forceinline__ void trav_descend(Trav &tr, float e0, float x0, float
     const bool le = n0 <= n1;
     const bool both = h0 && h1, none = !(h0 || h1);
     const bool near0 = h0 && (!h1 || le);
-    const uint32_t level = RTW_BLOCK * (uint32_t)sizeof(S);
+    const uint32_t level = BLOCK * (uint32_t)sizeof(S);
     if (sizeof(S) == 2) {
         // c0 holds {c0, c1} as halves: rotate the nearer child into the low half (one select of the rotate amount + v_alignbit), the
         // farther one is then stored straight from the high half (ds_write_b16_d16_hi) -- 2 VALU for near AND far instead of 3.
@@ -1087,6 +1097,27 @@ __device__ __forceinline__ void trav_node_lds(const u4 *lnodes, Trav &tr) {
     const float e1 = fmaxf(fmaxf(__builtin_fmaf(h_lo(bx), tr.ix, tr.kpx), __builtin_fmaf(h_lo(by), tr.iy, tr.kpy)), __builtin_fmaf(h_lo(bz), tr.iz, tr.kpz));
     const float x1 = fminf(fminf(__builtin_fmaf(h_hi(bx), tr.ix, tr.kmx), __builtin_fmaf(h_hi(by), tr.iy, tr.kmy)), __builtin_fmaf(h_hi(bz), tr.iz, tr.kmz));
     trav_descend<short>(tr, e0, x0, e1, x1, c0, c1, popped);
+}
+
+// The same visit over the f32 plane format (rtw_host.h pack_nodes32): tr.node is the node's LDS offset in units of 8 bytes, and
+// the lane reads each {near, far} pair where its ray's direction along the axis says (tr.sel*, 0 or RTW_NODE32_OFF bytes into the group):
+// three address adds in place of six v_perm_b32, twelve plain v_fma_f32 in place of twelve v_fma_mix_f32.  fma(widen(plane), 1/d, k) is
+// what v_fma_mix_f32 computes from the f16 plane, so every box decision is the f16 visit's.
+typedef float f2a __attribute__((ext_vector_type(2), aligned(RTW_NODE32_OFF)));
+template <uint32_t BLOCK>
+__device__ __forceinline__ void trav_node_lds32(Trav &tr) {
+    const uint32_t popped = lds_get<unsigned short>(tr.sp);
+    constexpr uint32_t G = RTW_NODE32_AXIS_DWORDS * 4u;               // bytes per (box, axis) group
+    const uint32_t ax = ((uint32_t)tr.node << RTW_NODE32_UNIT_SHIFT) + tr.selx, ay = ((uint32_t)tr.node << RTW_NODE32_UNIT_SHIFT) + tr.sely,
+                   az = ((uint32_t)tr.node << RTW_NODE32_UNIT_SHIFT) + tr.selz;
+    const f2a px0 = lds_get<f2a>(ax), py0 = lds_get<f2a>(ay + G), pz0 = lds_get<f2a>(az + 2u * G);
+    const f2a px1 = lds_get<f2a>(ax + 3u * G), py1 = lds_get<f2a>(ay + 4u * G), pz1 = lds_get<f2a>(az + 5u * G);
+    const uint32_t c0 = lds_get<uint32_t>(ax + 6u * G), c1 = 0;       // {c0, c1}: stored at both x offsets
+    const float e0 = fmaxf(fmaxf(__builtin_fmaf(px0.x, tr.ix, tr.kpx), __builtin_fmaf(py0.x, tr.iy, tr.kpy)), __builtin_fmaf(pz0.x, tr.iz, tr.kpz));
+    const float x0 = fminf(fminf(__builtin_fmaf(px0.y, tr.ix, tr.kmx), __builtin_fmaf(py0.y, tr.iy, tr.kmy)), __builtin_fmaf(pz0.y, tr.iz, tr.kmz));
+    const float e1 = fmaxf(fmaxf(__builtin_fmaf(px1.x, tr.ix, tr.kpx), __builtin_fmaf(py1.x, tr.iy, tr.kpy)), __builtin_fmaf(pz1.x, tr.iz, tr.kpz));
+    const float x1 = fminf(fminf(__builtin_fmaf(px1.y, tr.ix, tr.kmx), __builtin_fmaf(py1.y, tr.iy, tr.kmy)), __builtin_fmaf(pz1.y, tr.iz, tr.kmz));
+    trav_descend<short, BLOCK>(tr, e0, x0, e1, x1, c0, c1, popped);
 }
 
 // One inner-node visit: two slab tests, descend into the nearer child, push the farther.
@@ -1166,13 +1197,25 @@ constexpr bool two_halves_step(int spec, bool geom, bool moving) {
     return gradient_spec(spec) && !geom && !(moving && spec == 2);
 #endif
 }
+// Threads per workgroup of a render_bvh build.  The static LDS-node builds compiled for seven waves per SIMD run as 12-wave workgroups, two
+// to a CU, so that one copy of the nodes serves 12 waves and the tree fits LDS in the f32 plane format (rtw_host.h), the only one these
+// builds walk.  That is 6 waves per SIMD, not 7: two workgroups of 14 waves never shared a CU when measured, and a seventh wave is worth
+// 2.4 % where the f32 planes are worth 7.6 % (profiles/f32_planes_ab.log).  As a run-time choice next to the f16 walk the format kept
+// a third less of its gain.  A tree that cannot live in LDS this way goes to the NODES == 2 build (rtw_shim.hip).  Nothing but the
+// __syncthreads() after the node copy couples the waves of a workgroup.  Every other build keeps RTW_BLOCK and the f16 format.
+constexpr uint32_t bvh_block(bool moving, int nodes, int spec, bool geom) {
+    return !moving && !geom && nodes == 1 && two_halves_step(spec, geom, moving) ? RTW_BLOCK_LARGE : RTW_BLOCK;
+}
 template <bool MOVING, int NODES, int SPEC, bool GEOM>
-__global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WAVES_GEOM_SPEC : RTW_BVH_WAVES_GEOM) : (two_halves_step(SPEC, GEOM, MOVING) ? (SPEC == 2 ? RTW_BVH_WAVES_SPEC2 : RTW_BVH_WAVES_SPEC) : (gradient_spec(SPEC) ? RTW_BVH_WAVES_SPEC2 : (!generic_spec(SPEC) ? RTW_BVH_WAVES_FOLDED : RTW_BVH_WAVES)))) void render_bvh(const KArgs A) {
+__global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WAVES_GEOM_SPEC : RTW_BVH_WAVES_GEOM) : (two_halves_step(SPEC, GEOM, MOVING) ? (SPEC == 2 ? RTW_BVH_WAVES_SPEC2 : RTW_BVH_WAVES_SPEC) : (gradient_spec(SPEC) ? RTW_BVH_WAVES_SPEC2 : (!generic_spec(SPEC) ? RTW_BVH_WAVES_FOLDED : RTW_BVH_WAVES)))) void render_bvh(const KArgs A) {
     constexpr bool LDSN = NODES != 0, geom_in_lds = NODES == 2;
+    constexpr uint32_t BLOCK = bvh_block(MOVING, NODES, SPEC, GEOM);
+    constexpr bool F32 = BLOCK != RTW_BLOCK;         // the large-workgroup builds walk the f32 plane format, and that alone
     // LDS is all dynamic, sized by the host for THIS tree (rtw_shim.hip, render_enqueue_impl): -- LDS-node variants -- the f16 nodes at
     // offset 0, then the per-lane traversal stack [level][thread] (a level is one conflict-free row; depth + 3 levels: the sentinel,
     // one per tree level, and the slot above the top that the select-form descend always writes; 16-bit entries in the LDS-node
-    // variants), then -- NODES == 2 -- {centre, r^2} of every sphere for the leaf tests.  Book-1: 15.5 KB + 7 KB (+ 7.8 KB).
+    // variants), then -- NODES == 2 -- {centre, r^2} of every sphere for the leaf tests.  Book-1: 15 KB + 7 KB (+ 7.8 KB) per 256 threads;
+    // in the 768-thread builds 52.5 KB of f32 planes + 21 KB, twice per CU.
     typedef typename std::conditional<LDSN, short, int>::type stack_t;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     *(stack_t *)(lds_raw + A.lds_stack_off + threadIdx.x * (uint32_t)sizeof(stack_t)) = (stack_t)Code<stack_t>::END;   // level 0: the sentinel (own slot, no sync needed)
@@ -1183,9 +1226,10 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
     f4 *lgeom = (f4 *)(lds_raw + A.lds_geom_off);
     const DevScene &sc = A.sc;
     if (LDSN) {
-        const u4 *src = (const u4 *)A.bvh.nodes16;
-        for (uint32_t i = threadIdx.x; i < A.bvh.n_nodes * 2u; i += RTW_BLOCK) lnodes[i] = src[i];
-        if (geom_in_lds) for (uint32_t i = threadIdx.x; i < sc.n; i += RTW_BLOCK) lgeom[i] = sc.geom[i];
+        const u4 *src = F32 ? (const u4 *)A.nodes32 : (const u4 *)A.bvh.nodes16;
+        const uint32_t n16 = A.bvh.n_nodes * (F32 ? RTW_NODE32_DWORDS / 4u : 2u);
+        for (uint32_t i = threadIdx.x; i < n16; i += BLOCK) lnodes[i] = src[i];
+        if (geom_in_lds) for (uint32_t i = threadIdx.x; i < sc.n; i += BLOCK) lgeom[i] = sc.geom[i];
         __syncthreads();
     }
     if constexpr (tri_spec(SPEC)) tri_nodes_begin(A);
@@ -1325,7 +1369,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
             RTW_SUB_STAMP(2);
             // e. start the next closest-hit query
             if (shading && (fl & F_HAVE)) {
-                trav_begin<MOVING, stack_t>(A, pt, tr, lds_addr(lds_raw) + A.lds_stack_off + threadIdx.x * (uint32_t)sizeof(stack_t), a_plain, a_odd, cn);
+                trav_begin<MOVING, stack_t, F32>(A, pt, tr, lds_addr(lds_raw) + A.lds_stack_off + threadIdx.x * (uint32_t)sizeof(stack_t), a_plain, a_odd, cn);
                 fl |= F_INFLIGHT;
             }
             RTW_SUB_STAMP(3);
@@ -1378,7 +1422,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
                         pt.L = (light_spec(SPEC) || A.integrator == RTW_INTEGRATOR_RUST2) ? ld3(A.bg) : mk(0, 0, 0);
                         fl |= F_DONE;                                      // banked on the next SHADE trip
                     } else {
-                        trav_begin<MOVING, stack_t>(A, pt, tr, lds_addr(lds_raw) + A.lds_stack_off + threadIdx.x * (uint32_t)sizeof(stack_t), a_plain, a_odd, cn);
+                        trav_begin<MOVING, stack_t, F32>(A, pt, tr, lds_addr(lds_raw) + A.lds_stack_off + threadIdx.x * (uint32_t)sizeof(stack_t), a_plain, a_odd, cn);
                         // (the light build asks for it without quads too: a hit point that IS a light's mid-point makes the shadow direction NaN)
                         if constexpr (GEOM || light_spec(SPEC)) wild_ray_query<MOVING, stack_t>(A, pt, tr, n_isph);
                         fl |= F_INFLIGHT;
@@ -1403,7 +1447,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
                     const f4 gs = geom_in_lds ? lgeom[s] : sc.geom[s];
                     exact_sphere<MOVING>(gs, MOVING ? sc.vel[s] : f4{ 0, 0, 0, 0 }, s, pt.o, pt.d, pt.tm, tr.a, tr.ra, a_plain, A.mint, A.maxt, tr.best, tr.best_t);
                     tr.hi_lim = tr.best_t + tr.tau_t;
-                    trav_pop<stack_t>(tr);
+                    trav_pop<stack_t, BLOCK>(tr);
                 }
 #ifndef RTW_STAMP
                 // straight on to the bursts, without asking the scheduler, when more than half of the lanes are in TRAVERSE after the pops
@@ -1427,7 +1471,10 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WA
                 uint32_t b_steps = 0, b_lanes = 0;
                 for (int u = 0; u < RTW_TRAV_UNROLL; u++) {
                     b_steps++; b_lanes += live;
-                    if (in_trav<stack_t>(tr.node)) { if (LDSN) trav_node_lds((const u4 *)lnodes, tr); else trav_node(A.bvh, tr); }
+                    if (in_trav<stack_t>(tr.node)) {
+                        if constexpr (F32) trav_node_lds32<BLOCK>(tr);
+                        else if (LDSN) trav_node_lds((const u4 *)lnodes, tr); else trav_node(A.bvh, tr);
+                    }
                     if (u + 1 >= RTW_TRAV_UNROLL) break;
                     live = lanes_in(in_trav<stack_t>(tr.node));
                     if (live == 0u) break;
@@ -1653,15 +1700,32 @@ void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const f
 
 bool kernel_has_lds_geom(const KArgs &a) { return !(a.geom.n_quads || a.geom.n_inst || a.tris.n); }
 
+static uint32_t build_block(const RenderBuild &b) { return b.bvh ? bvh_block(b.moving, b.nodes, b.spec, b.geom) : RTW_BLOCK; }
+
 void launch_render(const KArgs &a, bool moving, uint32_t accel, uint32_t grid, hipStream_t stream, RenderBuild *build) {
-    hipLaunchKernelGGL(pick_kernel(a, moving, accel, a.bvh.nodes16 != nullptr, build), dim3(grid), dim3(RTW_BLOCK), a.lds_bytes, stream, a);
+    RenderBuild b;
+    const kernel_fn fn = pick_kernel(a, moving, accel, a.bvh.nodes16 != nullptr, &b);
+    if (build) *build = b;
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(build_block(b)), a.lds_bytes, stream, a);
     hipLaunchKernelGGL(resolve_kernel, dim3((a.n_tiles * 64u + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, a);
 }
 
 uint32_t kernel_blocks_per_cu(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pick_kernel(a, moving, accel, lds_nodes), RTW_BLOCK, a.lds_bytes) != hipSuccess || n < 1) n = 1;
+    RenderBuild b;
+    const kernel_fn fn = pick_kernel(a, moving, accel, lds_nodes, &b);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, build_block(b), a.lds_bytes) != hipSuccess || n < 1) n = 1;
     return (uint32_t)(n > 8 ? 8 : n);
+}
+
+hipError_t kernel_allow_lds(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
+    return hipFuncSetAttribute((const void *)pick_kernel(a, moving, accel, lds_nodes), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_bytes);
+}
+
+uint32_t kernel_block(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
+    RenderBuild b;
+    pick_kernel(a, moving, accel, lds_nodes, &b);
+    return build_block(b);
 }
 
 const void *kernel_id(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {

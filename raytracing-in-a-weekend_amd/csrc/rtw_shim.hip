@@ -36,7 +36,7 @@ static thread_local int g_last_hip = 0;
 struct SceneMem {
     DevMem geom, vel, mat, tex, texels;
     DevMem quads, inst, igeom, ivel, imat, iquads;
-    DevMem nodes, nodes16, big_geom, big_vel, big_index;
+    DevMem nodes, nodes16, nodes32, big_geom, big_vel, big_index;
 };
 struct NoiseMem { DevMem perlin, tex_noise; };
 struct TriMem { DevMem list, leaf, nodes; };
@@ -70,6 +70,7 @@ struct rtw_ctx {
     float bg[3] = { 0, 0, 0 };
     DevGeom geom{};
     DevBvh bvh{};
+    const uint32_t *nodes32 = nullptr;   // the f32 plane format of bvh.nodes16 (pack_nodes32), or null: no f16 nodes, or too many for its 16-bit codes
     SceneMem scene_mem;
     // texture noise of the scene (rtw_ctx_set_texture_noise; cleared by rtw_ctx_set_scene)
     uint32_t n_textures = 0;
@@ -116,11 +117,14 @@ struct rtw_ctx {
     double opt_tail_units = 0.0;         // RTW_OPT_TAIL_UNITS: blocks of short units per resident wave at the end of the queue (render_enqueue); 0 = off.
                                          // OFF by default: measured, it does not shorten a launch (profiles/r03_tail_units.log, r03_endtimes.log)
     uint32_t opt_guided_layout = 0;      // RTW_OPT_GUIDED_LAYOUT: where rtw_ctx_guided_filter keeps its table and guide tile (0 = by size)
+    uint32_t opt_node_format = 0;        // RTW_OPT_NODE_FORMAT: 0 = f32 planes where a build walks them and two of its workgroups fit a CU's LDS, 1 = f16, 2 = f32
     uint32_t opt_grab_blocks = 2;        // RTW_OPT_GRAB_BLOCKS (profiles/r02_grab_sweep.log: 1 / 2 / 4 / 8 / a tile's 42 blocks = 83.9 / 82.9 / 83.7 / 86.8 / 107.9 ms on the bench frame)
 
     RenderBuild last_build{};            // the render kernel the last launch ran (rtw_ctx_last_render_build); every band of a render runs the same one
     bool has_last_build = false;
+    uint32_t last_node_format = 0;       // ... and the LDS node format it read (rtw_ctx_last_node_format)
     // cache of a per-call driver query (tens of microseconds: visible on small frames)
+    std::map<const void *, uint32_t> lds_allowed;        // kernel -> the largest dynamic LDS it has been allowed beyond 64 KiB (kernel_allow_lds)
     std::map<std::pair<const void *, uint32_t>, uint32_t> occupancy;    // (kernel, dynamic LDS bytes) -> resident workgroups per CU
     bool attr_on_device = false; int attr_device = -1;   // memory kind of this call's out_rgb
     // the render in flight between render_enqueue and render_wait
@@ -470,6 +474,10 @@ int rtw_ctx_set_scene(rtw_ctx *c, const RtwScene *s, float t_begin, float t_end)
     build_bvh(s->spheres, s->n_spheres, std::fmin(t_begin, t_end), std::fmax(t_begin, t_end), bb);
     std::vector<f4> big_geom, big_vel;
     for (uint32_t i : bb.big) { big_geom.push_back(geom[i]); big_vel.push_back(vel[i]); }
+    std::vector<uint32_t> nodes32;
+    if (bb.nodes16.size() <= RTW_NODE32_NODES_MAX) pack_nodes32(bb.nodes16, nodes32);
+    if ((rc = upload(m.nodes32, nodes32))) return rc;
+    c->nodes32 = nodes32.empty() ? nullptr : m.nodes32.as<uint32_t>();
     if ((rc = upload(m.nodes16, bb.nodes16)) || (rc = upload(m.nodes, bb.nodes)) || (rc = upload(m.big_geom, big_geom)) ||
         (rc = upload(m.big_vel, big_vel)) || (rc = upload(m.big_index, bb.big))) return rc;
     c->bvh.nodes16 = bb.nodes16.empty() ? nullptr : m.nodes16.as<BvhNode16>();     // (null = "this tree has no f16 nodes": the kernels' builds differ)
@@ -1200,6 +1208,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     }
 
     // dynamic LDS layout of the BVH kernel for this tree
+    uint32_t block = RTW_BLOCK, node_format = 0u;      // threads per workgroup of the render kernel this launch runs; its LDS node format
     if (accel == RTW_ACCEL_BVH) {
         const bool ldsn = a.bvh.nodes16 != nullptr;
         // sentinel + one entry per tree level + the slot above the top the descend step always writes
@@ -1217,12 +1226,39 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
             // it does not cost a resident workgroup at the kernel's register budget (6 waves/SIMD)
             bool geom = off + c->sc.n * 16u <= 160u * 1024u / (1536u / RTW_BLOCK);
             if (c->opt_lds_geom >= 0) geom = c->opt_lds_geom != 0 && c->sc.n <= RTW_LDS_GEOM_MAX;
+            if (c->opt_node_format == 2u) geom = false;           // (f32 planes asked for: the builds that walk them keep the geometry in global memory)
             if (geom && kernel_has_lds_geom(a)) { a.lds_geom_off = off; off += c->sc.n * 16u; }
         }
         a.lds_bytes = off;
+        block = kernel_block(a, c->sc.moving != 0, accel, ldsn);
+        node_format = ldsn ? 1u : 0u;
+        if (block != RTW_BLOCK) {
+            // A large-workgroup build (rtw_kernels.hip bvh_block): it walks the tree as f32 planes, its stack's rows are `block` entries, and it is
+            // meant to run two workgroups per CU (24 waves, 6 per SIMD).  Both fit the CU's 160 KiB for every tree build_bvh gives f16 nodes within its depth
+            // cap: 3.5 x the node bytes + 3 x the stack bytes of a layout that fits a seventh.  A tree that does not fit, or
+            // RTW_OPT_NODE_FORMAT = 1, takes the f16 walk at RTW_BLOCK threads in the build that holds the spheres' geometry in LDS too
+            // (NODES == 2: kernel_has_lds_geom(a) holds for every scene a large-workgroup build serves, and a tree with f16 nodes has at most
+            // RTW_LDS_GEOM_MAX spheres) -- whatever RTW_OPT_LDS_GEOM says.
+            const uint32_t stack = (levels * block * 2u + 15u) & ~15u;
+            const uint32_t bytes32 = c->bvh.n_nodes * RTW_NODE32_DWORDS * 4u;       // (a multiple of 16)
+            const bool one = c->nodes32 != nullptr && bytes32 + stack <= 160u * 1024u, two = c->nodes32 != nullptr && 2u * (bytes32 + stack) <= 160u * 1024u;
+            if (c->opt_node_format == 2u ? one : (c->opt_node_format == 0u && two)) {
+                a.nodes32 = c->nodes32;
+                a.lds_stack_off = bytes32; a.lds_bytes = bytes32 + stack;
+                node_format = 2u;
+            } else {
+                a.lds_geom_off = off; a.lds_bytes = off + c->sc.n * 16u;
+                block = kernel_block(a, c->sc.moving != 0, accel, ldsn);
+            }
+        }
     }
     if (a.tris.n) { a.tris.lds_off = (a.lds_bytes + 15u) & ~15u; a.lds_bytes = a.tris.lds_off + 16u; }   // the triangle build's node-visit counter
 
+    if (accel == RTW_ACCEL_BVH && a.lds_bytes > 64u * 1024u) {
+        const bool ldsn = a.bvh.nodes16 != nullptr;
+        uint32_t &allowed = c->lds_allowed[kernel_id(a, c->sc.moving != 0, accel, ldsn)];
+        if (allowed < a.lds_bytes) { HIP_TRY(kernel_allow_lds(a, c->sc.moving != 0, accel, ldsn)); allowed = a.lds_bytes; }
+    }
     // persistent grid: as many workgroups as the kernel's registers let be resident, capped by the work
     uint32_t per_cu = c->opt_blocks_per_cu;
     if (per_cu == 0) {
@@ -1261,7 +1297,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
             key.cam.time0 = key.cam.shutter = key.cam.lens_radius = 0.0f;     // (the estimate uses the centre rays only: the frames of a clip share one order)
             // tiles worth of work in flight when the queue runs dry: four units for every lane of the full grid
             const uint64_t per_tile = 64ull * a.n_chunks;
-            key.tail_tiles = (uint32_t)std::min<uint64_t>(a.n_tiles, ((uint64_t)c->n_cu * per_cu * RTW_BLOCK * 4ull + per_tile - 1) / per_tile);
+            key.tail_tiles = (uint32_t)std::min<uint64_t>(a.n_tiles, ((uint64_t)c->n_cu * per_cu * block * 4ull + per_tile - 1) / per_tile);
             if (!c->scr.order.ptr || std::memcmp(&key, &c->order_key, sizeof key) != 0) {
                 std::vector<uint32_t> order;
                 build_tile_order(c->opt_tile_order, a.tiles_x, tiles_y, a.k_base, a.row_block, a.part_index, a.part_count, *cam, c->cull, key.tail_tiles, order);
@@ -1277,7 +1313,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
         // frame` 3.15 -> 2.68 ms with 4; the 1080p frames are indifferent).  An explicit RTW_OPT_BLOCKS_PER_CU wins.
         uint32_t wg_per_cu = per_cu;
         if (c->opt_blocks_per_cu == 0) {
-            const uint64_t lanes_per_wg_row = (uint64_t)c->n_cu * RTW_BLOCK * 16ull;
+            const uint64_t lanes_per_wg_row = (uint64_t)c->n_cu * block * 16ull;
             const uint64_t want = ((uint64_t)a.total_work + lanes_per_wg_row - 1) / lanes_per_wg_row;
             if (want < wg_per_cu) wg_per_cu = (uint32_t)(want ? want : 1);
             // The specialised BVH builds are compiled for 7 waves/SIMD (72 VGPRs); the seventh workgroup per CU pays on the full 1080p frames
@@ -1285,11 +1321,12 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
             // 11.1 ms, C2 7.18 -> 7.35: one more wave per SIMD to drain at the end): it is used from ~40 work units per lane
             // (profiles/r02_ab_waves7.log; profiles/r02_wg_per_cu.log: 6 / 7 workgroups per CU = 78.2 / 76.1 ms for the bench frame, 39.8 / 38.8 for
             // half of it, 20.75 / 20.40 for a quarter, 10.95 / 10.95 for an eighth, 7.07 / 7.11 for C2).
+            // (a large-workgroup build holds 24 waves per CU in its two workgroups: the rule never applies to it)
             if (wg_per_cu > 6u && (uint64_t)a.total_work < 40ull * c->n_cu * RTW_BLOCK * wg_per_cu) wg_per_cu = 6u;
         }
         uint32_t grid = (uint32_t)c->n_cu * wg_per_cu;
         {
-            const uint32_t need = (a.total_work + RTW_BLOCK - 1) / RTW_BLOCK;
+            const uint32_t need = (a.total_work + block - 1) / block;
             if (grid > need) grid = need ? need : 1;
         }
         // Guided unit length (RTW_OPT_TAIL_UNITS = k; 0, the default, = one length for the whole launch).  The idea: the end of a
@@ -1303,7 +1340,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
         // dry, at ~20 us per segment with seven busy waves per SIMD -- and a path cannot be split.  Handing the sky tiles out last so that no such
         // path starts late (RTW_OPT_TILE_ORDER 5) does not help either.  Kept as an option; off.
         if (!sums && c->opt_tail_units > 0.0 && a.chunk_len > 1u && a.n_tiles > 1u) {
-            const double waves = (double)grid * (RTW_BLOCK / 64u);
+            const double waves = (double)grid * (block / 64u);
             const uint32_t L1 = a.chunk_len, L2 = L1 >= 12u ? 4u : (L1 >= 6u ? 2u : 1u), L3 = 1u;
             uint64_t t3 = (uint64_t)std::ceil(c->opt_tail_units * waves * L3 / (double)a.n_samples);
             uint64_t t2 = L2 > L3 ? (uint64_t)std::ceil(c->opt_tail_units * waves * L2 / (double)a.n_samples) : 0;
@@ -1316,14 +1353,14 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
         }
         {   // guided grabs (fetch_pixel): work left / (4 x resident waves), as a shift; at most RTW_OPT_GRAB_BLOCKS blocks (0: the blocks of one tile)
             a.sub_shift = (c->opt_sub_queues != 1u && a.n_tiles >= 64u && grid >= 64u) ? RTW_SUB_SHIFT : 0u;       // one sub-queue per XCD, unless the launch is tiny
-            const uint32_t waves4 = (grid * (RTW_BLOCK / 64u) * 4u) >> a.sub_shift;
+            const uint32_t waves4 = (grid * (block / 64u) * 4u) >> a.sub_shift;
             a.grab_shift = 0; while (a.grab_shift < 31u && (1u << a.grab_shift) < waves4) a.grab_shift++;
             uint32_t blocks = c->opt_grab_blocks ? c->opt_grab_blocks : a.n_chunks;
             if (blocks > a.n_chunks) blocks = a.n_chunks;
             a.grab_max = (blocks ? blocks : 1u) * 64u;
         }
         HIP_TRY(hipMemsetAsync(a.queue, 0, RTW_QUEUE_BYTES, c->stream));
-        if (a.n_tiles) { launch_render(a, c->sc.moving != 0, accel, grid, c->stream, &c->last_build); c->has_last_build = true; }
+        if (a.n_tiles) { launch_render(a, c->sc.moving != 0, accel, grid, c->stream, &c->last_build); c->has_last_build = true; c->last_node_format = node_format; }
         HIP_TRY(hipGetLastError());
         if (tile_rows == 0) break;
     }
@@ -1435,6 +1472,12 @@ int rtw_ctx_last_render_build(rtw_ctx *c, char *buf, size_t n) {
     return len > 0 && (size_t)len < n ? RTW_OK : RTW_E_INVALID;
 }
 
+// Host only: the LDS node format the last launch's kernel read.
+int rtw_ctx_last_node_format(rtw_ctx *c) {
+    if (!c || !c->has_last_build) return RTW_E_INVALID;
+    return (int)c->last_node_format;
+}
+
 int rtw_ctx_set_option(rtw_ctx *c, uint32_t key, double v) {
     if (!c || !(v == v)) return RTW_E_INVALID;
     switch (key) {
@@ -1448,6 +1491,7 @@ int rtw_ctx_set_option(rtw_ctx *c, uint32_t key, double v) {
     case RTW_OPT_TAIL_UNITS:     if (!(v >= 0.0 && v <= 1024.0)) return RTW_E_INVALID; c->opt_tail_units = v; return RTW_OK;
     case RTW_OPT_GUIDED_LAYOUT:  if (!(v >= 0.0 && v <= 4.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_guided_layout = (uint32_t)v; return RTW_OK;
     case RTW_OPT_GRAB_BLOCKS:    if (!(v >= 0.0 && v <= 65536.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_grab_blocks = (uint32_t)v; return RTW_OK;
+    case RTW_OPT_NODE_FORMAT:    if (!(v == 0.0 || v == 1.0 || v == 2.0)) return RTW_E_INVALID; c->opt_node_format = (uint32_t)v; return RTW_OK;
     default: return RTW_E_INVALID;
     }
 }
