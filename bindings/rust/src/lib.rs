@@ -95,6 +95,13 @@ pub const RTW_FLAG_MIXED_MATERIAL: u32 = 32;
 #[repr(u32)] #[derive(Clone, Copy)]
 pub enum Sampler { Row = 0, Stratified = 1, Centres = 2, NoRand = 3 }      // viewport.rs:270-305, 430-516
 
+/// `RTW_OPT_MESH_LIST_MAX` (rtw.h): the option key of the placement count up to which placements are met in list order.
+pub const RTW_OPT_MESH_LIST_MAX: u32 = 12;
+/// A node of the top-level tree over mesh placements (rtw.h `RtwTriNode`): leaf = (first << 3) | count, 0 for an inner node.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct RtwTriNode { pub lo: [f32; 3], pub skip: u32, pub hi: [f32; 3], pub leaf: u32 }
+
 extern "C" {
     fn rtw_ctx_create(device: i32, out: *mut *mut RtwCtx) -> i32;
     fn rtw_ctx_destroy(ctx: *mut RtwCtx);
@@ -138,6 +145,12 @@ extern "C" {
                               mint: f32, maxt: f32, t_out: *mut f32, placement_out: *mut i32, tri_out: *mut i32, normal_out: *mut f32) -> i32;
     fn rtw_ctx_mesh_instance_hits(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, mint: f32, maxt: f32, accel: u32, t_out: *mut f32,
                                   placement_out: *mut i32, tri_out: *mut i32, normal_out: *mut f32, stats: *mut RtwStats) -> i32;
+    fn rtw_mesh_list_max_default() -> u32;
+    fn rtw_mesh_top_dump(tris: *const RtwTriangle, n_tris: u32, p: *const RtwMeshInstance, n: u32, nodes_out: *mut RtwTriNode, node_cap: u32,
+                         n_nodes: *mut u32, order_out: *mut u32, depth: *mut u32, list_walk: *mut u32) -> i32;
+    fn rtw_mesh_instance_hits_tree(tris: *const RtwTriangle, n_tris: u32, p: *const RtwMeshInstance, n: u32, rays: *const f32, n_rays: u32,
+                                   mint: f32, maxt: f32, t_out: *mut f32, placement_out: *mut i32, tri_out: *mut i32, normal_out: *mut f32,
+                                   stats: *mut RtwStats) -> i32;
     fn rtw_quat_rotate(q: *const f32, v: *const f32, out: *mut f32) -> i32;
     fn rtw_quat_mul(a: *const f32, b: *const f32, out: *mut f32) -> i32;
     fn rtw_quat_from_axis(angle: f32, axis: *const f32, out: *mut f32) -> i32;
@@ -283,7 +296,8 @@ impl Renderer {
         Ok((out, st))
     }
     /// Tuning knobs (`RTW_OPT_*` of rtw.h: 1 chunk length, 2 sample bank GiB, 3 LDS geometry, 4 workgroups per CU, 5 list-walk
-    /// threshold, 11 = `RTW_OPT_NODE_FORMAT`: the tree in LDS as 0 f32 planes where they fit, 1 f16 nodes, 2 f32 planes); none of them
+    /// threshold, 11 = `RTW_OPT_NODE_FORMAT`: the tree in LDS as 0 f32 planes where they fit, 1 f16 nodes, 2 f32 planes, 12 =
+    /// `RTW_OPT_MESH_LIST_MAX`: at most this many mesh placements are met in list order, more through the top-level tree); none of them
     /// changes the image.
     pub fn set_option(&mut self, key: u32, value: f64) -> Result<(), RtwError> { check(unsafe { rtw_ctx_set_option(self.ctx, key, value) }) }
     /// The format of the tree the last render's kernel read from LDS (rtw_ctx_last_node_format): 0 none, 1 f16 nodes, 2 f32 planes.

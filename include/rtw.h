@@ -303,11 +303,15 @@ enum {
                                      XCD and helps out on the others when it is empty), a single one for tiny launches; 1: always single */
     RTW_OPT_GUIDED_LAYOUT    = 10,/* rtw_ctx_guided_filter: 0 (default) places the weight table and the guide tile by size;
                                      1 table and guides in LDS, 2 guides only, 3 table only, 4 neither -- followed where it fits in LDS  */
-    RTW_OPT_NODE_FORMAT      = 11 /* how a static sphere scene's tree lives in LDS where the common-configuration builds of the BVH render
+    RTW_OPT_NODE_FORMAT      = 11,/* how a static sphere scene's tree lives in LDS where the common-configuration builds of the BVH render
                                      kernel serve it: 0 (default) as f32 planes, walked by workgroups of 768 threads, where two of them fit a
                                      CU's LDS, else as f16 nodes; 1 f16 nodes (the build that keeps the sphere geometry in LDS too, whatever
                                      RTW_OPT_LDS_GEOM says); 2 f32 planes wherever one workgroup fits.  Other builds walk f16 nodes whatever
                                      it says.  Any other value: RTW_E_INVALID.  The walk, the counters and the image are the same */
+    RTW_OPT_MESH_LIST_MAX    = 12 /* contexts with at most this many mesh placements meet them in list order even under RTW_ACCEL_BVH
+                                     (result-invariant; the "mesh placements" section); more walk the top-level tree over the placements.
+                                     Default RTW_MESH_LIST_MAX_DEFAULT, the measured crossover; 0 = always the top-level
+                                     tree, 4294967295 = never; a value that is not a whole number: RTW_E_INVALID.  (added within v4)                                                         */
 };
 int  rtw_ctx_set_option(rtw_ctx *ctx, uint32_t key, double value);
 /* Which compiled build of the render kernel the context's last render launched, as text in template-argument order:
@@ -670,7 +674,16 @@ int rtw_quat_from_euler(const float euler[3], float out[4]);
  * Renders: RTW_INTEGRATOR_RUST2 is served, with every sampler, flag and accel; everything the triangle build serves under that integrator next
  * to plain triangles stays legal next to placements.  NOT BUILT, RTW_E_INVALID at the render: every other integrator,
  * RTW_FLAG_MIXED_MATERIAL with a mixed object, instance rotations in the same context.  (Texture noise and lights are refused next to
- * triangles already.)  The one-shot rtw_render / rtw_render_multi_gpu carry no placements.  Without placements nothing changes. */
+ * triangles already.)  The one-shot rtw_render / rtw_render_multi_gpu carry no placements.  Without placements nothing changes.
+ * The top-level tree (added within v4; Rust2 keeps its instances in an AABB tree, objects/aabb.rs:141-248): rtw_ctx_set_mesh_instances
+ * builds a BVH over the placements' world boxes for every n >= 2 -- binned SAH, deterministic, nodes in the triangle tree's format, leaves
+ * of up to 4 placements.  Placement k's box bounds conj(qn_k).rotate(x') + position_k over the mesh tree's root box -- where the geometry
+ * stands for a ray; not the q.rotate(p') + position of the hit record, and not the reference's Instance::get_aabb, which turns the box the
+ * wrong way -- padded for the rounding of the transform.  Under RTW_ACCEL_BVH a context with more than RTW_OPT_MESH_LIST_MAX placements
+ * walks it and enters only placements whose box the ray meets.  The answer is the list order's ON THE BITS: the closest placement, of equal t
+ * the lowest index, the group against the result so far only when strictly closer.  Where the bound's derivation does not hold the
+ * placements are met in list order as before: a |position| or mesh extent beyond 2^38, a mesh whose own tree is refused, RTW_ACCEL_BRUTE, a
+ * mint / maxt the triangle tree refuses; and per ray a non-finite component or |o|_inf + |d|_inf max(|mint|, |maxt|) > 2^38. */
 typedef struct RtwMeshInstance { float position[3]; float quat[4]; /* w,x,y,z */ } RtwMeshInstance;
 #define RTW_MAX_MESH_INSTANCES 65536u
 int rtw_ctx_set_mesh_instances(rtw_ctx *ctx, const RtwMeshInstance *placements, uint32_t n);
@@ -685,11 +698,30 @@ int rtw_mesh_instance_hits(const RtwTriangle *tris, uint32_t n_tris, const RtwMe
                            const float *rays, uint32_t n_rays, float mint, float maxt,
                            float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out /* may be NULL */);
 /* The same on the context's GPU through the function the render's closest-hit stage calls (host buffers in and out, blocking, as
- * rtw_ctx_triangle_hits): accel = RTW_ACCEL_BVH walks the mesh's tree per placement (rays the cull does not cover in a placement's frame
- * walk the list there), RTW_ACCEL_BRUTE the list.  stats (may be NULL): quad_tests = triangle tests, node_tests = node visits.
- * RTW_E_NO_SCENE without placements. */
+ * rtw_ctx_triangle_hits): accel = RTW_ACCEL_BVH walks the mesh's tree in each placement it enters (rays the cull does not cover in a
+ * placement's frame walk the list there) and reaches the placements through the top-level tree where the context has more than
+ * RTW_OPT_MESH_LIST_MAX of them, else in list order; RTW_ACCEL_BRUTE walks the list of placements and in each the list of triangles.
+ * stats (may be NULL): quad_tests = triangle tests, node_tests = node visits, the top-level tree's included.  RTW_E_NO_SCENE without placements. */
 int rtw_ctx_mesh_instance_hits(rtw_ctx *ctx, const float *rays, uint32_t n_rays, float mint, float maxt, uint32_t accel,
                                float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out /* may be NULL */, RtwStats *stats);
+/* A node of the top-level tree (and of the triangle tree), depth-first: the left child of an inner node follows it, `skip` is the node after
+ * its subtree (n_nodes: the end); leaf = (first << 3) | count names count <= 4 entries of the order array from `first`, 0: an inner node. */
+typedef struct RtwTriNode { float lo[3]; uint32_t skip; float hi[3]; uint32_t leaf; } RtwTriNode;
+/* Host only (added within v4): the top-level tree a context would build for `placements` of the mesh `tris`, as the device reads it.
+ * nodes_out (may be NULL; node_cap entries, RTW_E_INVALID when too few -- 2 n - 1 always suffice: every leaf holds a placement, and SAH may
+ * split one off per level; call with NULL first for the exact count) and *n_nodes; order_out ([n], may be NULL): the
+ * placement indices in leaf order; *depth; *list_walk = 1: the context meets its placements in list order whatever the option says (a
+ * placement or the mesh beyond the bound's reach, or the mesh's own tree refused).  Statuses as rtw_mesh_instance_hits. */
+/* RTW_OPT_MESH_LIST_MAX as a new context holds it (host only; added within v4). */
+uint32_t rtw_mesh_list_max_default(void);
+int rtw_mesh_top_dump(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *placements, uint32_t n,
+                      RtwTriNode *nodes_out, uint32_t node_cap, uint32_t *n_nodes, uint32_t *order_out, uint32_t *depth, uint32_t *list_walk);
+/* Host only (added within v4): rtw_mesh_instance_hits' arguments and outputs through the walk the kernels run under RTW_ACCEL_BVH with
+ * RTW_OPT_MESH_LIST_MAX = 0 -- the same source, compiled for the host: the top-level tree, in each entered placement the mesh's tree.  The
+ * same bits as rtw_mesh_instance_hits.  stats (may be NULL): node_tests = node visits of both trees, quad_tests = triangle tests. */
+int rtw_mesh_instance_hits_tree(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *placements, uint32_t n,
+                                const float *rays, uint32_t n_rays, float mint, float maxt,
+                                float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out /* may be NULL */, RtwStats *stats);
 
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 

@@ -51,6 +51,8 @@ OPT_CHUNK_LEN, OPT_SAMPLE_BANK_GB, OPT_LDS_GEOM, OPT_BLOCKS_PER_CU, OPT_LIST_WAL
 OPT_TAIL_UNITS = 9
 OPT_NODE_FORMAT = 11                                 # the large-workgroup BVH builds' tree in LDS: 0 f32 planes where they fit, 1 f16 nodes, 2 f32 planes
 NODE_FORMAT_NONE, NODE_FORMAT_F16, NODE_FORMAT_F32 = 0, 1, 2   # Renderer.last_node_format
+OPT_MESH_LIST_MAX = 12                               # at most this many mesh placements: list order even under ACCEL_BVH; more: the top-level tree
+MESH_LIST_MAX_DEFAULT = 16                           # its default (csrc/rtw_kernels.h RTW_MESH_LIST_MAX_DEFAULT): the measured crossover, DESIGN.md 4.11
 OPT_GUIDED_LAYOUT = 10                               # Renderer.guided_filter: 0 by size, 1 table + guides in LDS, 2 guides, 3 table, 4 neither
 SCENE_C1, SCENE_C2, SCENE_C4, SCENE_C5, SCENE_METAL_TEST, SCENE_QUAD_TEST, SCENE_PRESENTATION, SCENE_FIRST_FRAME = 1, 2, 4, 5, 6, 7, 8, 9
 MEDIUM_SURFACE, MEDIUM_CONST_DENSITY = 0, 1
@@ -288,6 +290,11 @@ def lib() -> C.CDLL:
                                          C.c_float, fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), fp]
     L.rtw_ctx_mesh_instance_hits.argtypes = [C.c_void_p, fp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, fp, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int32), fp, C.POINTER(RtwStats)]
+    L.rtw_mesh_top_dump.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, C.POINTER(RtwMeshInstance), C.c_uint32, C.c_void_p, C.c_uint32,
+                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.rtw_mesh_list_max_default.restype = C.c_uint32
+    L.rtw_mesh_list_max_default.argtypes = []
+    L.rtw_mesh_instance_hits_tree.argtypes = L.rtw_mesh_instance_hits.argtypes + [C.POINTER(RtwStats)]
     L.rtw_quat_rotate.argtypes = [fp, fp, fp]
     L.rtw_quat_mul.argtypes = [fp, fp, fp]
     L.rtw_quat_from_axis.argtypes = [C.c_float, fp, fp]
@@ -621,6 +628,35 @@ def mesh_instance_hits(triangles, placements, rays, mint: float, maxt: float, no
     _check(lib().rtw_mesh_instance_hits(arr, n, parr, pn, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt), *ptrs),
            "rtw_mesh_instance_hits")
     return out if normals else out[:3]
+
+
+def mesh_instance_hits_tree(triangles, placements, rays, mint: float, maxt: float, normals: bool = True):
+    """mesh_instance_hits through the walk the kernels run (rtw_mesh_instance_hits_tree: the top-level tree over the placements, the mesh's tree
+    in each placement entered), on the host: (t, placement, triangle, normals or None, RtwStats) -- node_tests counts both trees' visits."""
+    arr, n = _triangle_array(triangles)
+    parr, pn = _placement_array(placements)
+    r = _rays(rays)
+    out, ptrs = _mesh_hit_buffers(len(r), normals)
+    st = RtwStats()
+    _check(lib().rtw_mesh_instance_hits_tree(arr, n, parr, pn, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt), *ptrs,
+                                             C.byref(st)), "rtw_mesh_instance_hits_tree")
+    return out + (st,)
+
+
+TOP_NODE = np.dtype([("lo", np.float32, 3), ("skip", np.uint32), ("hi", np.float32, 3), ("leaf", np.uint32)])
+
+
+def mesh_top_dump(triangles, placements):
+    """rtw_mesh_top_dump: the top-level tree over `placements` of the mesh `triangles` as the device reads it -- (nodes [n_nodes] of TOP_NODE,
+    order [n] uint32: the placement indices in leaf order, depth, list_walk)."""
+    arr, n = _triangle_array(triangles)
+    parr, pn = _placement_array(placements)
+    nodes = np.zeros(max(2 * pn, 1), TOP_NODE)                   # (2 n - 1 nodes at the most: SAH may split one placement off per level)
+    order = np.zeros(max(pn, 1), np.uint32)
+    nn, dp, lw = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().rtw_mesh_top_dump(arr, n, parr, pn, nodes.ctypes.data, len(nodes), C.byref(nn), order.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                   C.byref(dp), C.byref(lw)), "rtw_mesh_top_dump")
+    return nodes[:nn.value].copy(), order[:pn].copy(), dp.value, lw.value
 
 
 def depth_rays(cam: RtwCamera, width: int, height: int) -> np.ndarray:

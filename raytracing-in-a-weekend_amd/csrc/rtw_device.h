@@ -40,20 +40,20 @@ typedef const f4 __attribute__((address_space(4))) *cf4_ptr;
 // state into <1 x float> pieces that mem2reg then refuses to promote (24 B of scratch per lane).
 struct v3 {
     float x, y, z;
-    __device__ __forceinline__ v3() {}
-    __device__ __forceinline__ v3(const v3 &o) : x(o.x), y(o.y), z(o.z) {}
-    __device__ __forceinline__ v3 &operator=(const v3 &o) { x = o.x; y = o.y; z = o.z; return *this; }
+    __host__ __device__ __forceinline__ v3() {}
+    __host__ __device__ __forceinline__ v3(const v3 &o) : x(o.x), y(o.y), z(o.z) {}
+    __host__ __device__ __forceinline__ v3 &operator=(const v3 &o) { x = o.x; y = o.y; z = o.z; return *this; }
 };
 
-__device__ __forceinline__ v3 mk(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
-__device__ __forceinline__ v3 ld3(const float *p) { return mk(p[0], p[1], p[2]); }
-__device__ __forceinline__ v3 operator+(v3 a, v3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ v3 operator-(v3 a, v3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ v3 operator*(v3 a, v3 b) { return mk(a.x * b.x, a.y * b.y, a.z * b.z); }
-__device__ __forceinline__ v3 operator*(v3 a, float s) { return mk(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ v3 operator/(v3 a, float s) { return mk(a.x / s, a.y / s, a.z / s); }
-__device__ __forceinline__ v3 operator-(v3 a) { return mk(-a.x, -a.y, -a.z); }
-__device__ __forceinline__ float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__host__ __device__ __forceinline__ v3 mk(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
+__host__ __device__ __forceinline__ v3 ld3(const float *p) { return mk(p[0], p[1], p[2]); }
+__host__ __device__ __forceinline__ v3 operator+(v3 a, v3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
+__host__ __device__ __forceinline__ v3 operator-(v3 a, v3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
+__host__ __device__ __forceinline__ v3 operator*(v3 a, v3 b) { return mk(a.x * b.x, a.y * b.y, a.z * b.z); }
+__host__ __device__ __forceinline__ v3 operator*(v3 a, float s) { return mk(a.x * s, a.y * s, a.z * s); }
+__host__ __device__ __forceinline__ v3 operator/(v3 a, float s) { return mk(a.x / s, a.y / s, a.z / s); }
+__host__ __device__ __forceinline__ v3 operator-(v3 a) { return mk(-a.x, -a.y, -a.z); }
+__host__ __device__ __forceinline__ float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ __forceinline__ float len2(v3 a) { return a.x * a.x + a.y * a.y + a.z * a.z; }
 __device__ __forceinline__ float len(v3 a) { return __builtin_sqrtf(a.x * a.x + a.y * a.y + a.z * a.z); }
 // ---- IEEE sqrt and division without the exponent-range machinery -----------------------------------------------------

@@ -19,6 +19,9 @@
 #ifndef RTW_LIST_WALK_MAX_DEFAULT
 #define RTW_LIST_WALK_MAX_DEFAULT 48u  // RTW_OPT_LIST_WALK_MAX: scenes this small walk the list even when the BVH is asked for (measured crossover ~56 spheres: profiles/r02_crossover.log)
 #endif
+#ifndef RTW_MESH_LIST_MAX_DEFAULT
+#define RTW_MESH_LIST_MAX_DEFAULT 16u  // RTW_OPT_MESH_LIST_MAX: this few placements are met in list order even when the BVH is asked for (measured: the largest count at which the list is not slower, profiles/mesh_top_tree.log)
+#endif
 
 namespace rtw {
 
@@ -90,6 +93,8 @@ struct KArgs {
     uint32_t n_mesh;              // the placement build (SPEC 12), which alone reads them: tris is then the mesh every placement shares
     const uint32_t *nodes32;      // the tree's f32 plane format (rtw_host.h pack_nodes32): what the large-workgroup builds (kernel_block() !=
                                   // RTW_BLOCK) copy into LDS instead of bvh.nodes16; they alone read it
+    const TriNode *mesh_top;      // the top-level tree over the placements (rtw_mesh.h mesh_top_walk; the order array sits behind the nodes), or
+    uint32_t n_mesh_top;          // null: the placements are met in list order.  Read by the placement build alone
 };
 
 // Which instantiation of render_brute<MOVING, SPEC, GEOM> / render_bvh<MOVING, NODES, SPEC, GEOM> a launch ran (nodes: 0 for render_brute)
@@ -112,6 +117,8 @@ struct QueryArgs {
     const f4 *inst_quats;         // Rust2's instance rotations, one normalised {w, x, y, z} per instance, or null: the Euler rotation of DevInstance
     const f4 *mesh_rows;          // mesh placements, two rows per placement (rtw_mesh.h), or null: tris is a world-space group
     uint32_t n_mesh;
+    const TriNode *mesh_top;      // the top-level tree over the placements, or null (as in KArgs)
+    uint32_t n_mesh_top;
     RtwCamera cam;                // from_camera: Rust2's camera (rtw_camera2_new), pixel i = (i % width, i / width)
     uint32_t width, height;
     const float *rays;            // else: [n][6] = o, d (device)
@@ -132,7 +139,7 @@ struct QueryArgs {
 void launch_scene_hits(const QueryArgs &q, bool from_camera, bool tree, hipStream_t stream);
 // rtw_ctx_mesh_instance_hits: the closest placement of mesh T for each of n rays through mesh_closest (rtw_mesh.h); placement / triangle
 // -1 and t +inf on a miss; normal_out ([n][3]) may be null; counters as launch_tri_hits
-void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const float *rays, uint32_t n, float mint, float maxt, float *t_out,
+void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const TriNode *top, uint32_t n_top, const float *rays, uint32_t n, float mint, float maxt, float *t_out,
                       int32_t *placement_out, int32_t *tri_out, float *normal_out, unsigned long long *counters, hipStream_t stream);
 // Resident workgroups per CU for the kernel variant (occupancy API), >= 1.
 uint32_t kernel_blocks_per_cu(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);

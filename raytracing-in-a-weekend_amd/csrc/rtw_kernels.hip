@@ -421,7 +421,7 @@ __device__ __forceinline__ bool shade_geom(const KArgs &A, Path &pt, int best, f
         float tt;
         int tk;
         uint32_t n_nodes = 0;
-        const int mp = mesh_closest(A.tris, A.mesh_rows, A.n_mesh, pt.o, pt.d, A.mint, A.maxt, won || best >= 0, won ? h.t : best_t, tk, tt, n_quad, n_nodes);
+        const int mp = mesh_closest(A.tris, A.mesh_rows, A.n_mesh, A.mesh_top, A.n_mesh_top, pt.o, pt.d, A.mint, A.maxt, won || best >= 0, won ? h.t : best_t, tk, tt, n_quad, n_nodes);
         if (n_nodes) atomicAdd(tri_node_counter(A.tris), n_nodes);
         if (mp >= 0) {                       // Instance::get_hit: the record in the placement's frame, p and n turned back by the SAME q, Hit.r left local
             quat qn; v3 pos;
@@ -1664,7 +1664,7 @@ void launch_tri_hits(const DevTris &T, const float *rays, uint32_t n, float mint
 }
 
 // The closest placement per ray through mesh_closest, the function the placement build's closest-hit stage calls (rtw_ctx_mesh_instance_hits)
-__global__ __launch_bounds__(RTW_BLOCK) void mesh_hits_kernel(const DevTris T, const f4 *rows, uint32_t n_mesh, const float *rays, uint32_t n, float mint,
+__global__ __launch_bounds__(RTW_BLOCK) void mesh_hits_kernel(const DevTris T, const f4 *rows, uint32_t n_mesh, const TriNode *top, uint32_t n_top, const float *rays, uint32_t n, float mint,
                                                               float maxt, float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out,
                                                               unsigned long long *counters) {
     const uint32_t i = blockIdx.x * RTW_BLOCK + threadIdx.x;
@@ -1673,7 +1673,7 @@ __global__ __launch_bounds__(RTW_BLOCK) void mesh_hits_kernel(const DevTris T, c
         const float *r = rays + 6 * (size_t)i;
         float t;
         int tk;
-        const int mp = mesh_closest(T, rows, n_mesh, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), mint, maxt, false, 0.0f, tk, t, n_tests, n_nodes);
+        const int mp = mesh_closest(T, rows, n_mesh, top, n_top, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), mint, maxt, false, 0.0f, tk, t, n_tests, n_nodes);
         t_out[i] = mp >= 0 ? t : __builtin_inff();
         placement_out[i] = mp;
         tri_out[i] = mp >= 0 ? tk : -1;
@@ -1692,9 +1692,9 @@ __global__ __launch_bounds__(RTW_BLOCK) void mesh_hits_kernel(const DevTris T, c
     if ((threadIdx.x & 63u) == 0) { atomicAdd(&counters[0], a); atomicAdd(&counters[1], b); }
 }
 
-void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const float *rays, uint32_t n, float mint, float maxt, float *t_out,
+void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const TriNode *top, uint32_t n_top, const float *rays, uint32_t n, float mint, float maxt, float *t_out,
                       int32_t *placement_out, int32_t *tri_out, float *normal_out, unsigned long long *counters, hipStream_t stream) {
-    hipLaunchKernelGGL(mesh_hits_kernel, dim3((n + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, T, rows, n_mesh, rays, n, mint, maxt, t_out,
+    hipLaunchKernelGGL(mesh_hits_kernel, dim3((n + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, T, rows, n_mesh, top, n_top, rays, n, mint, maxt, t_out,
                        placement_out, tri_out, normal_out, counters);
 }
 

@@ -212,7 +212,7 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
         int tk = -1, mp = -1;
         if (A.mesh_rows) {                                         // (a wave-uniform branch) the placements stand in for the world-space triangles
             float tt;
-            mp = mesh_closest(A.tris, A.mesh_rows, A.n_mesh, o, d, mint, maxt, found, ht, tk, tt, n_quad, n_nodes);
+            mp = mesh_closest(A.tris, A.mesh_rows, A.n_mesh, A.mesh_top, A.n_mesh_top, o, d, mint, maxt, found, ht, tk, tt, n_quad, n_nodes);
             if (mp >= 0) { ht = tt; found = true; win = 4; idx = (int)(A.sc.n + g.n_quads + g.n_inst) + mp; }
         } else if (A.tris.n) {
             float tt;

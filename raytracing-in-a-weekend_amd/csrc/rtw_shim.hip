@@ -41,7 +41,7 @@ struct SceneMem {
 struct NoiseMem { DevMem perlin, tex_noise; };
 struct TriMem { DevMem list, leaf, nodes; };
 struct QuatMem { DevMem rows; };
-struct MeshMem { DevMem rows; };
+struct MeshMem { DevMem rows, top; };     // top: the top-level tree's nodes, the leaf-order placement indices behind them
 struct ScratchMem {
     DevMem queue, stats;
     PinnedMem h_stats;                   // pinned: the counter read-back is a true async copy
@@ -82,6 +82,7 @@ struct rtw_ctx {
     // Rust2 triangles of the scene (rtw_ctx_set_triangles; cleared by rtw_ctx_set_scene)
     DevTris tris{};                      // tris.nodes stays null here: a render sets it (tri_view) when the tree may be used
     bool tri_tree = false;               // no triangle breaks the cull's derivation (DESIGN.md "Rust2 triangles")
+    TriNode tri_root{};                  // the tree's root: the box every placement's world box is formed from (rtw_ctx_set_mesh_instances)
     TriMem tri_mem;
     // lights of the scene (rtw_ctx_set_lights; cleared by rtw_ctx_set_scene): the rows the light build reads from its arguments
     DevLights lights{};
@@ -95,6 +96,8 @@ struct rtw_ctx {
     // mesh placements (rtw_ctx_set_mesh_instances; cleared by rtw_ctx_set_scene and rtw_ctx_set_triangles): two rows per placement (rtw_mesh.h)
     const f4 *mesh_rows = nullptr;       // non-null: renders take the placement build (SPEC 12), the queries place the mesh
     uint32_t n_mesh = 0;
+    const TriNode *mesh_top = nullptr;   // the top-level tree over the placements, or null: none was built (n < 2), or a placement
+    uint32_t n_mesh_top = 0;             // lies beyond the reach of its bound.  A render or query takes it through mesh_top_view
     bool tri_textured = false;           // a triangle of the context reads an image texture (placements refuse such a mesh)
     MeshMem mesh_mem;
     // MixedMaterial (RTW_FLAG_MIXED_MATERIAL): does the scene hold an object with opacity < 0, and is the exponent (ir) of every such object
@@ -110,6 +113,7 @@ struct rtw_ctx {
     int opt_lds_geom = -1;
     uint32_t opt_blocks_per_cu = 0;
     uint32_t opt_list_walk_max = RTW_LIST_WALK_MAX_DEFAULT;
+    uint32_t opt_mesh_list_max = RTW_MESH_LIST_MAX_DEFAULT;   // RTW_OPT_MESH_LIST_MAX (profiles/mesh_top_tree.log)
     uint32_t opt_tile_order = 0;         // raster.  (The cost order, 2, was the default while units were 4 samples and grabs single blocks -- profiles/
                                          // r02_order_chunk_grid.log --; with today's units and grabs raster is 1.2 % ahead of it on the bench frame and ahead
                                          // on every other config too, profiles/r02_order_ab.log)
@@ -281,6 +285,8 @@ static void free_mesh(rtw_ctx *c) {
     c->mesh_mem = MeshMem{};
     c->mesh_rows = nullptr;
     c->n_mesh = 0;
+    c->mesh_top = nullptr;
+    c->n_mesh_top = 0;
 }
 
 static void free_tris(rtw_ctx *c) {
@@ -755,6 +761,7 @@ int rtw_ctx_set_triangles(rtw_ctx *c, const RtwTriangle *tris, uint32_t n) {
     c->tris.list = m.list.as<DevTri>(); c->tris.leaf = m.leaf.as<DevTri>();
     c->tris.n = n; c->tris.n_nodes = b.n_nodes;
     c->tri_tree = !b.list_walk;
+    c->tri_root = b.nodes[0];
     c->tri_mem = std::move(m);
     for (uint32_t i = 0; i < n; i++) if (tris[i].tex >= 0) c->tri_textured = true;
     return RTW_OK;
@@ -774,9 +781,19 @@ int rtw_ctx_set_mesh_instances(rtw_ctx *c, const RtwMeshInstance *p, uint32_t n)
     HIP_TRY(hipSetDevice(c->device));
     free_mesh(c);
     if (!n) return RTW_OK;
+    // the top-level tree, for every n >= 2 (whether a render walks it: mesh_top_view)
+    MeshTopBuild top;
+    std::vector<unsigned char> packed;
+    if (n >= 2) {
+        if (!mesh_top_build(c->tri_root, rows.data(), n, top)) return RTW_E_NOMEM;
+        try { packed = top.packed(); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+    }
     MeshMem m;
     if (const int rc = upload(m.rows, rows)) return rc;
+    const bool use_top = n >= 2 && !top.list_walk;
+    if (use_top) if (const int rc = upload(m.top, packed)) return rc;
     c->mesh_rows = m.rows.as<f4>(); c->n_mesh = n;
+    if (use_top) { c->mesh_top = m.top.as<TriNode>(); c->n_mesh_top = (uint32_t)top.nodes.size(); }
     c->mesh_mem = std::move(m);
     return RTW_OK;
 }
@@ -807,6 +824,12 @@ static DevTris tri_view(const rtw_ctx *c, uint32_t accel, float mint, float maxt
     const bool range_ok = std::isfinite(mint) && std::isfinite(maxt) && tb <= RTW_TRI_COORD_MAX;
     t.nodes = (accel == RTW_ACCEL_BVH && c->tri_tree && range_ok) ? c->tri_mem.nodes.as<TriNode>() : nullptr;
     return t;
+}
+
+// ... and the top-level tree over its placements: only next to the mesh's own tree (T = tri_view's answer: RTW_ACCEL_BVH, a mesh and a range
+// the cull covers) and for more than RTW_OPT_MESH_LIST_MAX placements; else null, and the placements are met in list order (the same answer)
+static const TriNode *mesh_top_view(const rtw_ctx *c, const DevTris &T) {
+    return (T.nodes != nullptr && c->n_mesh > c->opt_mesh_list_max) ? c->mesh_top : nullptr;
 }
 
 int rtw_ctx_triangle_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float mint, float maxt, uint32_t accel,
@@ -857,7 +880,7 @@ int rtw_ctx_mesh_instance_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, f
     if (e == hipSuccess) e = hipMemcpyAsync(d_r.ptr, rays, ray_bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_c.ptr, 0, sizeof cnt, c->stream);
     if (e == hipSuccess) {
-        launch_mesh_hits(T, c->mesh_rows, c->n_mesh, d_r.as<const float>(), n_rays, mint, maxt, d_t.as<float>(), d_p.as<int32_t>(), d_i.as<int32_t>(),
+        launch_mesh_hits(T, c->mesh_rows, c->n_mesh, mesh_top_view(c, T), c->n_mesh_top, d_r.as<const float>(), n_rays, mint, maxt, d_t.as<float>(), d_p.as<int32_t>(), d_i.as<int32_t>(),
                          normal_out ? d_n.as<float>() : nullptr, d_c.as<unsigned long long>(), c->stream);
         e = hipGetLastError();
     }
@@ -897,6 +920,7 @@ static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_
     q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom; q.inst_quats = c->inst_quats;
     if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
     q.mesh_rows = c->mesh_rows; q.n_mesh = c->n_mesh;
+    if (c->mesh_rows) { q.mesh_top = mesh_top_view(c, q.tris); q.n_mesh_top = c->n_mesh_top; }
     if (cam) { q.cam = *cam; q.width = width; q.height = height; }
     q.n = n; q.levels = c->bvh.depth + 2u;
     q.time = time; q.mint = mint; q.maxt = maxt; q.miss_t = miss_t; q.span = (float)c->scene_span;
@@ -1144,6 +1168,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     if (light_integrator) a.lights = c->lights;                    // (the integrator selects the light build, which alone reads them)
     a.inst_quats = c->inst_quats;                                  // (selects the quaternion build, whatever the integrator of the three it serves)
     a.mesh_rows = c->mesh_rows; a.n_mesh = c->n_mesh;              // (selects the placement build)
+    if (c->mesh_rows) { a.mesh_top = mesh_top_view(c, a.tris); a.n_mesh_top = c->n_mesh_top; }   // (the same build: the walk behind the pointer)
 #ifdef RTW_ENDTIMES
     if (const char *e = getenv("RTW_ENDTIMES_REF")) a.endtimes_ref = std::strtoull(e, nullptr, 10);       // diagnostic build only
 #endif
@@ -1478,6 +1503,8 @@ int rtw_ctx_last_node_format(rtw_ctx *c) {
     return (int)c->last_node_format;
 }
 
+uint32_t rtw_mesh_list_max_default(void) { return RTW_MESH_LIST_MAX_DEFAULT; }
+
 int rtw_ctx_set_option(rtw_ctx *c, uint32_t key, double v) {
     if (!c || !(v == v)) return RTW_E_INVALID;
     switch (key) {
@@ -1491,6 +1518,7 @@ int rtw_ctx_set_option(rtw_ctx *c, uint32_t key, double v) {
     case RTW_OPT_TAIL_UNITS:     if (!(v >= 0.0 && v <= 1024.0)) return RTW_E_INVALID; c->opt_tail_units = v; return RTW_OK;
     case RTW_OPT_GUIDED_LAYOUT:  if (!(v >= 0.0 && v <= 4.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_guided_layout = (uint32_t)v; return RTW_OK;
     case RTW_OPT_GRAB_BLOCKS:    if (!(v >= 0.0 && v <= 65536.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_grab_blocks = (uint32_t)v; return RTW_OK;
+    case RTW_OPT_MESH_LIST_MAX:  if (!(v >= 0.0 && v <= 4294967295.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_mesh_list_max = (uint32_t)v; return RTW_OK;
     case RTW_OPT_NODE_FORMAT:    if (!(v == 0.0 || v == 1.0 || v == 2.0)) return RTW_E_INVALID; c->opt_node_format = (uint32_t)v; return RTW_OK;
     default: return RTW_E_INVALID;
     }

@@ -66,12 +66,13 @@ bool tri_box(const DevTri &t, TriBox &b) {
     return ok;
 }
 
+// Binned SAH over box centres with a median fallback, leaves of <= 4: the triangle tree's builder, and the top-level tree's over the
+// placements' world boxes (mesh_top_build).  `order`: the items in leaf order; a leaf names a run of it.  Deterministic: no RNG, ties by index.
 struct Builder {
-    const DevTri *list;
     const std::vector<TriBox> &box;
     std::vector<uint32_t> idx;
     std::vector<TriNode> nodes;
-    std::vector<DevTri> leaf;
+    std::vector<uint32_t> order;
     uint32_t depth = 0;
 
     static float down(double x) { float f = (float)x; if ((double)f > x) f = std::nextafter(f, -INFINITY); return f; }
@@ -97,8 +98,8 @@ struct Builder {
         for (int k = 0; k < 3; k++) { nodes[me].lo[k] = down(lo[k]); nodes[me].hi[k] = up(hi[k]); }
         const uint32_t n = end - begin;
         if (n <= 4) {
-            nodes[me].leaf = ((uint32_t)leaf.size() << 3) | n;
-            for (uint32_t i = begin; i < end; i++) leaf.push_back(list[idx[i]]);
+            nodes[me].leaf = ((uint32_t)order.size() << 3) | n;
+            for (uint32_t i = begin; i < end; i++) order.push_back(idx[i]);
             nodes[me].skip = (uint32_t)nodes.size();
             return;
         }
@@ -165,17 +166,80 @@ bool tri_build(const DevTri *list, uint32_t n, TriBuild &out) {
         std::vector<TriBox> box(n);
         bool ok = true;
         for (uint32_t i = 0; i < n; i++) if (!tri_box(list[i], box[i])) ok = false;
-        Builder b{ list, box, {}, {}, {} };
+        Builder b{ box, {}, {}, {} };
         b.idx.resize(n);
         for (uint32_t i = 0; i < n; i++) b.idx[i] = i;
         b.nodes.reserve(n > 0 ? 2 * ((size_t)n / 2 + 1) : 0);
-        b.leaf.reserve(n);
+        b.order.reserve(n);
         if (n) b.build(0, n, 0);
         out.n_nodes = (uint32_t)b.nodes.size();
         out.nodes = new TriNode[b.nodes.size() + 1];
-        out.leaf = new DevTri[b.leaf.size() + 1];
+        out.leaf = new DevTri[b.order.size() + 1];
         std::copy(b.nodes.begin(), b.nodes.end(), out.nodes);
-        std::copy(b.leaf.begin(), b.leaf.end(), out.leaf);
+        for (size_t i = 0; i < b.order.size(); i++) out.leaf[i] = list[b.order[i]];
+        out.depth = b.depth;
+        out.list_walk = !ok;
+        return true;
+    } catch (const std::bad_alloc &) {
+        return false;
+    }
+}
+
+// ---- the top-level tree over mesh placements ---------------------------------------------------------------------------
+std::vector<unsigned char> MeshTopBuild::packed() const {
+    std::vector<unsigned char> out(nodes.size() * sizeof(TriNode) + order.size() * sizeof(uint32_t));
+    if (!nodes.empty()) std::memcpy(out.data(), nodes.data(), nodes.size() * sizeof(TriNode));
+    if (!order.empty()) std::memcpy(out.data() + nodes.size() * sizeof(TriNode), order.data(), order.size() * sizeof(uint32_t));
+    return out;
+}
+
+// The world box of one placement.  The local frame is x' = qn.rotate(x - position), so the geometry a ray meets stands at
+// conj(qn).rotate(x') + position -- the CONJUGATE rotation, not the q.rotate(p') + position of the hit record.  The eight corners of the mesh
+// tree's root box (padded by r_static already) are turned in double precision (qn's f32 components are exact doubles; the map is linear, so
+// the image of the box lies in the corners' hull), then the box is padded by the static part of 4.11's bound, c2 u (|position|_inf + rho)
+// with c2 = 512 and rho the largest corner norm, plus 2^-40 of its size for the double arithmetic itself.
+static bool placement_box(const TriNode &root, const f4 &qrow, const f4 &prow, TriBox &b) {
+    const double w = qrow.x, x = qrow.y, y = qrow.z, z = qrow.w;
+    const double pos[3] = { prow.x, prow.y, prow.z };
+    double rho = 0.0, pmax = 0.0, amax = 0.0;
+    for (int k = 0; k < 3; k++) { b.lo[k] = HUGE_VAL; b.hi[k] = -HUGE_VAL; pmax = std::max(pmax, std::fabs(pos[k])); }
+    for (int c = 0; c < 8; c++) {
+        const double v[3] = { (c & 1) ? root.hi[0] : root.lo[0], (c & 2) ? root.hi[1] : root.lo[1], (c & 4) ? root.hi[2] : root.lo[2] };
+        rho = std::max(rho, std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+        // conj(qn) (0, v) qn, the vector part: with r = -(x, y, z) it is v (w^2 - r.r) + 2 r (r.v) + 2 w (r x v)
+        const double r[3] = { -x, -y, -z };
+        const double rr = r[0] * r[0] + r[1] * r[1] + r[2] * r[2], rv = r[0] * v[0] + r[1] * v[1] + r[2] * v[2];
+        const double cx[3] = { r[1] * v[2] - r[2] * v[1], r[2] * v[0] - r[0] * v[2], r[0] * v[1] - r[1] * v[0] };
+        for (int k = 0; k < 3; k++) {
+            const double p = v[k] * (w * w - rr) + 2.0 * r[k] * rv + 2.0 * w * cx[k] + pos[k];
+            b.lo[k] = std::min(b.lo[k], p); b.hi[k] = std::max(b.hi[k], p);
+        }
+    }
+    const double pad = 0x1p-24 * 512.0 * (pmax + rho);
+    for (int k = 0; k < 3; k++) amax = std::max(amax, std::max(std::fabs(b.lo[k]), std::fabs(b.hi[k])));
+    const double slack = pad + 0x1p-40 * amax + 0x1p-100;
+    for (int k = 0; k < 3; k++) { b.lo[k] -= slack; b.hi[k] += slack; b.c[k] = 0.5 * (b.lo[k] + b.hi[k]); }
+    // the reach of the bound: the placement and the mesh within RTW_MESH_TOP_REACH of their origins (the per-ray test of mesh_top_ray_ordinary
+    // then implies tri_ray_ordinary in this placement's frame)
+    return std::isfinite(rho) && pmax <= (double)RTW_MESH_TOP_REACH && rho <= (double)RTW_MESH_TOP_REACH;
+}
+
+bool mesh_top_build(const TriNode &root, const f4 *rows, uint32_t n, MeshTopBuild &out) {
+    try {
+        std::vector<TriBox> box(n);
+        bool ok = true;
+        for (uint32_t i = 0; i < n; i++) if (!placement_box(root, rows[2 * (size_t)i], rows[2 * (size_t)i + 1], box[i])) ok = false;
+        if (!ok) for (uint32_t i = 0; i < n; i++) for (int k = 0; k < 3; k++) if (!std::isfinite(box[i].lo[k]) || !std::isfinite(box[i].hi[k])) {
+            box[i].lo[k] = box[i].hi[k] = box[i].c[k] = 0.0;      // (a refused context's tree is never walked: any finite box will do)
+        }
+        Builder b{ box, {}, {}, {} };
+        b.idx.resize(n);
+        for (uint32_t i = 0; i < n; i++) b.idx[i] = i;
+        b.nodes.reserve(2 * ((size_t)n / 2 + 1));
+        b.order.reserve(n);
+        if (n) b.build(0, n, 0);
+        out.nodes = std::move(b.nodes);
+        out.order = std::move(b.order);
         out.depth = b.depth;
         out.list_walk = !ok;
         return true;
@@ -257,6 +321,83 @@ int rtw_mesh_instance_hits(const RtwTriangle *tris, uint32_t n_tris, const RtwMe
             }
         }
     }
+    return RTW_OK;
+}
+
+// What a context holds for the placements `p` of the mesh `tris`: the rows, the mesh's tree and the top-level tree (rtw_ctx_set_triangles +
+// rtw_ctx_set_mesh_instances, without a context)
+namespace {
+struct HostMesh {
+    std::vector<DevTri> list;
+    std::vector<f4> rows;
+    TriBuild tree;
+    MeshTopBuild top;
+    std::vector<unsigned char> packed;
+};
+int host_mesh(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *p, uint32_t n, HostMesh &m) {
+    if (n == 0) return RTW_E_INVALID;
+    if (const int rc = rtw_mesh_instances_validate(tris, n_tris, p, n)) return rc;
+    try { m.list.resize(n_tris); m.rows.resize(2 * (size_t)n); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+    tri_prepare(tris, n_tris, m.list.data());
+    mesh_rows(p, n, m.rows.data());
+    if (!tri_build(m.list.data(), n_tris, m.tree)) return RTW_E_NOMEM;
+    if (!mesh_top_build(m.tree.nodes[0], m.rows.data(), n, m.top)) return RTW_E_NOMEM;
+    return RTW_OK;
+}
+} // namespace
+
+int rtw_mesh_top_dump(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *p, uint32_t n, RtwTriNode *nodes_out, uint32_t node_cap,
+                      uint32_t *n_nodes, uint32_t *order_out, uint32_t *depth, uint32_t *list_walk) {
+    static_assert(sizeof(RtwTriNode) == sizeof(TriNode), "the public node is the device's");
+    HostMesh m;
+    if (const int rc = host_mesh(tris, n_tris, p, n, m)) return rc;
+    const uint32_t nn = (uint32_t)m.top.nodes.size();
+    if (n_nodes) *n_nodes = nn;
+    if (depth) *depth = m.top.depth;
+    if (list_walk) *list_walk = (m.top.list_walk || m.tree.list_walk) ? 1u : 0u;
+    if (nodes_out) {
+        if (node_cap < nn) return RTW_E_INVALID;
+        std::memcpy(nodes_out, m.top.nodes.data(), nn * sizeof(TriNode));
+    }
+    if (order_out) std::memcpy(order_out, m.top.order.data(), n * sizeof(uint32_t));
+    return RTW_OK;
+}
+
+int rtw_mesh_instance_hits_tree(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *p, uint32_t n, const float *rays, uint32_t n_rays,
+                                float mint, float maxt, float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out, RtwStats *stats) {
+    if (!rays || !t_out || !placement_out || !tri_out || n_rays == 0 || n == 0) return RTW_E_INVALID;
+    HostMesh m;
+    if (const int rc = host_mesh(tris, n_tris, p, n, m)) return rc;
+    try { m.packed = m.top.packed(); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+    // the views a context forms under RTW_ACCEL_BVH with RTW_OPT_MESH_LIST_MAX = 0 (rtw_shim.hip: tri_view, mesh_top_view)
+    DevTris T{};
+    T.list = m.list.data(); T.leaf = m.tree.leaf; T.n = n_tris; T.n_nodes = m.tree.n_nodes;
+    T.t_bound = std::fmax(std::fabs(mint), std::fabs(maxt));
+    const bool range_ok = std::isfinite(mint) && std::isfinite(maxt) && T.t_bound <= RTW_TRI_COORD_MAX;
+    T.nodes = (!m.tree.list_walk && range_ok) ? m.tree.nodes : nullptr;
+    const TriNode *top = (T.nodes != nullptr && !m.top.list_walk) ? (const TriNode *)m.packed.data() : nullptr;
+    const uint32_t n_top = (uint32_t)m.top.nodes.size();
+    unsigned long long tests = 0, visits = 0;
+    for (uint32_t i = 0; i < n_rays; i++) {
+        const float *r = rays + 6 * (size_t)i;
+        float t;
+        int j;
+        uint32_t n_tests = 0, n_nodes = 0;
+        const int k = mesh_closest(T, m.rows.data(), n, top, n_top, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), mint, maxt, false, 0.0f, j, t, n_tests, n_nodes);
+        tests += n_tests; visits += n_nodes;
+        t_out[i] = k >= 0 ? t : INFINITY;
+        placement_out[i] = k;
+        tri_out[i] = k >= 0 ? j : -1;
+        if (normal_out) {
+            float *o = normal_out + 3 * (size_t)i;
+            o[0] = o[1] = o[2] = 0.0f;
+            if (k >= 0) {
+                const f4 a = m.rows[2 * (size_t)k];
+                quat_rotate_n(qmk(a.x, a.y, a.z, a.w), m.list[j].normal[0], m.list[j].normal[1], m.list[j].normal[2], o[0], o[1], o[2]);
+            }
+        }
+    }
+    if (stats) { std::memset(stats, 0, sizeof *stats); stats->quad_tests = tests; stats->node_tests = visits; }
     return RTW_OK;
 }
 

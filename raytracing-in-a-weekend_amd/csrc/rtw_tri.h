@@ -3,6 +3,7 @@
 // kernel of rtw_ctx_triangle_hits compile any of the device code.
 #pragma once
 #include "rtw_device.h"
+#include <vector>
 
 namespace rtw {
 
@@ -116,7 +117,7 @@ __device__ __forceinline__ DevTri tri_load(const DevTri *base, uint32_t k) {
 }
 
 // Can the tree answer this ray?  (DESIGN.md "Rust2 triangles": the derivation needs |o| + |d| max(|mint|, |maxt|) <= 2^40; NaN fails it)
-__device__ __forceinline__ bool tri_ray_ordinary(const DevTris &T, v3 o, v3 d) {
+__host__ __device__ __forceinline__ bool tri_ray_ordinary(const DevTris &T, v3 o, v3 d) {
     const float ao = fmaxf(fmaxf(__builtin_fabsf(o.x), __builtin_fabsf(o.y)), __builtin_fabsf(o.z));
     const float ad = fmaxf(fmaxf(__builtin_fabsf(d.x), __builtin_fabsf(d.y)), __builtin_fabsf(d.z));
     const bool finite = (o.x - o.x == 0.0f) && (o.y - o.y == 0.0f) && (o.z - o.z == 0.0f) && (d.x - d.x == 0.0f) && (d.y - d.y == 0.0f) && (d.z - d.z == 0.0f);
@@ -226,5 +227,16 @@ struct TriBuild {
     ~TriBuild();
 };
 bool tri_build(const DevTri *list, uint32_t n, TriBuild &out);
+// The top-level tree over n placements of a mesh whose tree's root is `root` (rows: mesh_rows' output): DESIGN.md 4.11.  nodes in the TriNode
+// format, leaf = (first << 3) | count names a run of `order`, the placement indices in leaf order; `packed` is what the device reads: the
+// nodes, then the order array behind them.  list_walk: a placement lies beyond the reach of the bound (the tree is built anyway).
+struct MeshTopBuild {
+    std::vector<TriNode> nodes;
+    std::vector<uint32_t> order;
+    uint32_t depth = 0;
+    bool list_walk = false;
+    std::vector<unsigned char> packed() const;
+};
+bool mesh_top_build(const TriNode &root, const f4 *rows, uint32_t n, MeshTopBuild &out);
 
 } // namespace rtw
