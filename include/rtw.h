@@ -255,7 +255,14 @@ int         rtw_hip_runtime_count(void);   /* copies of libamdhip64 mapped into 
 /* One context per GPU.  `device` is the HIP device ordinal. */
 int  rtw_ctx_create(int device, rtw_ctx **out);
 void rtw_ctx_destroy(rtw_ctx *ctx);
-/* Launch on this HIP stream (a hipStream_t passed as void*), NULL = the context's own stream. */
+/* Launch on this HIP stream (a hipStream_t passed as void*): every copy, kernel and event of every later rtw_ctx_* call is enqueued on
+ * it, so the call is ordered behind the work the caller enqueued there before it, and each call still returns only when its own work
+ * is done.  NULL = the context's own stream.  That stream is created hipStreamNonBlocking: it orders with NO other stream, the
+ * default stream included, so whatever produces a device buffer handed to a call on it must have finished before the call.
+ * The handle 0 is therefore NOT the default stream (which PyTorch calls its default stream and hands out as cuda_stream == 0): name
+ * that one with RTW_STREAM_LEGACY, HIP's hipStreamLegacy.  Any other non-NULL handle is passed to HIP as it is; the caller keeps the
+ * stream alive while it is set. */
+#define RTW_STREAM_LEGACY ((void *)1)
 int  rtw_ctx_set_stream(rtw_ctx *ctx, void *hip_stream);
 /* == Scene::new_sphere(spheres) (viewport.rs:90-105): copies the scene to the GPU and builds the
  * acceleration structure.  [t_begin, t_end] is the ray.time range the bounds must cover

@@ -59,6 +59,7 @@ MEDIUM_SURFACE, MEDIUM_CONST_DENSITY = 0, 1
 PROXIMITY_SQUARE, PROXIMITY_EDGES = 0, 1             # Rust2 ProximityType (postprocessing.rs:12-15)
 PIXELS_U8, PIXELS_F32_RUST2 = 0, 1                   # RtwBilateral.in_format
 BILATERAL_MAX_SIZE = 64
+STREAM_LEGACY = 1                                    # RTW_STREAM_LEGACY: HIP's legacy default stream, the one torch calls its default stream
 
 # materials.rs:157-212 presets as (metallicness, opacity, ir)
 METALLIC_M = (1.0, 0.0, 1.0)
@@ -1050,13 +1051,27 @@ class Viewport:
         return img
 
 
+def raw_stream_handle(hip_stream) -> int:
+    """What Renderer.set_stream hands to rtw_ctx_set_stream: the handle as it is; None is 0, the context's own stream."""
+    return 0 if hip_stream is None else int(hip_stream)
+
+
+def torch_stream_handle(stream) -> int:
+    """What Renderer.use_torch_stream hands to rtw_ctx_set_stream for a torch.cuda.Stream (anything with a `cuda_stream` handle): the
+    handle, or STREAM_LEGACY for torch's default stream, whose handle 0 would select the context's own stream."""
+    handle = int(stream.cuda_stream)
+    return handle if handle else STREAM_LEGACY
+
+
 class Renderer:
     """One `rtw_ctx`: one GPU, one stream, device-resident scene + BVH."""
 
     def __init__(self, device: int = 0):
         self._h = C.c_void_p()
         _check(lib().rtw_ctx_create(int(device), C.byref(self._h)), "rtw_ctx_create")
+        self._device = int(device)
         self._scene = None
+        self._stream = None     # the torch stream of use_torch_stream, kept alive while it is set
 
     def close(self):
         if self._h:
@@ -1075,8 +1090,22 @@ class Renderer:
         except Exception:
             pass
 
-    def set_stream(self, hip_stream: int):
-        _check(lib().rtw_ctx_set_stream(self._h, C.c_void_p(hip_stream)), "rtw_ctx_set_stream")
+    def set_stream(self, hip_stream: Optional[int]):
+        """rtw_ctx_set_stream with a raw HIP stream handle, passed on as it is.  0 / None select the context's OWN stream, which is
+        non-blocking and orders with no other stream -- not torch's default stream, whose handle reads 0 as well: that one is
+        STREAM_LEGACY, and use_torch_stream picks it."""
+        _check(lib().rtw_ctx_set_stream(self._h, C.c_void_p(raw_stream_handle(hip_stream))), "rtw_ctx_set_stream")
+        self._stream = None
+
+    def use_torch_stream(self, stream=None):
+        """Order every later call of this context on a torch.cuda.Stream: behind what torch has enqueued there, with no synchronise in
+        between.  None takes torch.cuda.current_stream of the context's device at the time of this call.  The default stream (handle 0)
+        is set as STREAM_LEGACY.  The stream is kept alive by the renderer until another is set."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self._device)
+        _check(lib().rtw_ctx_set_stream(self._h, C.c_void_p(torch_stream_handle(stream))), "rtw_ctx_set_stream")
+        self._stream = stream
 
     def set_scene(self, scene: Scene, t_begin: float = 0.0, t_end: float = 0.0):
         self._scene = scene     # keep host arrays alive

@@ -434,3 +434,57 @@ def test_one_hip_runtime_in_this_process():
     """conftest imports torch before the library is loaded, so both share ONE copy of libamdhip64 (rtw_ctx_create refuses a process with two)."""
     assert R.lib().rtw_hip_runtime_count() == 1
     assert "libamdhip64" in R.lib().rtw_strerror(-8).decode() and "torch" in R.lib().rtw_strerror(-8).decode()
+
+
+# ---- rtw_ctx_set_stream: which handle reaches the library -------------------------------------------------------------------------------
+def test_set_stream_refuses_a_null_context():
+    L = R.lib()
+    for handle in (None, 1, 0x1000):
+        assert L.rtw_ctx_set_stream(None, handle) == -1
+
+
+def test_stream_legacy_is_the_header_constant():
+    txt = open(os.path.join(ROOT, "include", "rtw.h")).read()
+    m = re.search(r"#define\s+RTW_STREAM_LEGACY\s+\(\(void \*\)(\d+)\)", txt)
+    assert m and int(m.group(1)) == R.STREAM_LEGACY == 1          # HIP's hipStreamLegacy is ((hipStream_t)1)
+
+
+class _Stream:
+    """What use_torch_stream reads of a torch.cuda.Stream."""
+
+    def __init__(self, handle):
+        self.cuda_stream = handle
+
+
+def test_stream_handle_choice(monkeypatch):
+    """A torch stream whose handle is 0 (torch's default stream) is set as STREAM_LEGACY, any other by its handle; a raw 0 / None through
+    set_stream stays 0, the context's own stream, and a raw handle stays what it is."""
+    assert R.torch_stream_handle(_Stream(0)) == R.STREAM_LEGACY
+    assert R.torch_stream_handle(_Stream(0x7F00DEADBEE0)) == 0x7F00DEADBEE0
+    assert R.raw_stream_handle(0) == 0 and R.raw_stream_handle(None) == 0
+    assert R.raw_stream_handle(0x7F00DEADBEE0) == 0x7F00DEADBEE0 and R.raw_stream_handle(R.STREAM_LEGACY) == 1
+
+    # ... and that is what the two setters hand to rtw_ctx_set_stream
+    seen = []
+
+    class Lib:
+        @staticmethod
+        def rtw_ctx_set_stream(ctx, handle):
+            seen.append(handle.value)                              # (a c_void_p of 0 reads None)
+            return 0
+    monkeypatch.setattr(R.pkg, "lib", lambda: Lib)                 # (rtw_amd re-exports the names of the package R.pkg, where Renderer looks `lib` up)
+    r = R.Renderer.__new__(R.Renderer)                             # no context: nothing here reaches a device
+    r._h, r._device, r._stream = None, 0, None
+    side, default = _Stream(0x7F00DEADBEE0), _Stream(0)
+    r.set_stream(0)
+    r.set_stream(None)
+    r.set_stream(side.cuda_stream)
+    r.set_stream(default.cuda_stream)                              # the pitfall: torch's default stream by its raw handle is the OWN stream
+    assert seen == [None, None, 0x7F00DEADBEE0, None] and r._stream is None
+    del seen[:]
+    r.use_torch_stream(side)
+    assert r._stream is side                                       # kept alive while it is set
+    r.use_torch_stream(default)
+    assert seen == [0x7F00DEADBEE0, R.STREAM_LEGACY] and r._stream is default
+    r.set_stream(0)
+    assert r._stream is None
