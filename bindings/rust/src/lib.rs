@@ -148,6 +148,12 @@ extern "C" {
     fn rtw_mesh_list_max_default() -> u32;
     fn rtw_mesh_top_dump(tris: *const RtwTriangle, n_tris: u32, p: *const RtwMeshInstance, n: u32, nodes_out: *mut RtwTriNode, node_cap: u32,
                          n_nodes: *mut u32, order_out: *mut u32, depth: *mut u32, list_walk: *mut u32) -> i32;
+    fn rtw_ctx_refit_triangles(ctx: *mut RtwCtx, ouv: *const f32, n: u32, list_walk_out: *mut u32) -> i32;
+    fn rtw_ctx_triangle_bvh_dump(ctx: *mut RtwCtx, nodes_out: *mut RtwTriNode, node_cap: u32, n_nodes: *mut u32) -> i32;
+    fn rtw_triangle_bvh_dump(tris: *const RtwTriangle, n: u32, nodes_out: *mut RtwTriNode, node_cap: u32, n_nodes: *mut u32, order_out: *mut u32,
+                             depth: *mut u32, list_walk: *mut u32) -> i32;
+    fn rtw_triangle_bvh_refit(tris: *const RtwTriangle, n: u32, ouv: *const f32, nodes_out: *mut RtwTriNode, node_cap: u32, n_nodes: *mut u32,
+                              list_walk: *mut u32) -> i32;
     fn rtw_mesh_instance_hits_tree(tris: *const RtwTriangle, n_tris: u32, p: *const RtwMeshInstance, n: u32, rays: *const f32, n_rays: u32,
                                    mint: f32, maxt: f32, t_out: *mut f32, placement_out: *mut i32, tri_out: *mut i32, normal_out: *mut f32,
                                    stats: *mut RtwStats) -> i32;
@@ -220,6 +226,22 @@ impl Renderer {
     pub fn set_triangles(&mut self, tris: &[RtwTriangle]) -> Result<(), RtwError> {
         let p = if tris.is_empty() { std::ptr::null() } else { tris.as_ptr() };
         check(unsafe { rtw_ctx_set_triangles(self.ctx, p, tris.len() as u32) })
+    }
+    /// rtw_ctx_refit_triangles: move the context's triangles to `ouv` (origin, u, v per triangle, list order; host memory here, staged) and
+    /// refit their tree on the GPU; topology, materials and order stay.  Ok(true): a triangle now breaks a condition of the tree and the
+    /// context walks the list.  Refused (RTW_E_INVALID) for another count than the context's and while placements are set.
+    pub fn refit_triangles(&mut self, ouv: &[[f32; 9]]) -> Result<bool, RtwError> {
+        let mut walk = 0u32;
+        check(unsafe { rtw_ctx_refit_triangles(self.ctx, ouv.as_ptr() as *const f32, ouv.len() as u32, &mut walk) })?;
+        Ok(walk != 0)
+    }
+    /// rtw_ctx_triangle_bvh_dump: the nodes of the context's triangle tree as the device holds them now.
+    pub fn triangle_bvh_dump(&mut self) -> Result<Vec<RtwTriNode>, RtwError> {
+        let mut n = 0u32;
+        check(unsafe { rtw_ctx_triangle_bvh_dump(self.ctx, std::ptr::null_mut(), 0, &mut n) })?;
+        let mut nodes = vec![RtwTriNode::default(); n as usize];
+        check(unsafe { rtw_ctx_triangle_bvh_dump(self.ctx, nodes.as_mut_ptr(), n, std::ptr::null_mut()) })?;
+        Ok(nodes)
     }
     /// The `lights` / `biased_weight` captures of Rust2's light_biased_ray_cast / light_biased_ray_color closures (an empty slice clears
     /// them; set_scene clears them): Integrator::LightCast / LightBiased then send one shadow ray per light from every surface hit.

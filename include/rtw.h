@@ -730,6 +730,32 @@ int rtw_mesh_instance_hits_tree(const RtwTriangle *tris, uint32_t n_tris, const 
                                 const float *rays, uint32_t n_rays, float mint, float maxt,
                                 float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out /* may be NULL */, RtwStats *stats);
 
+/* ---- refit: a deforming mesh (added within v4) -------------------------------------------------------------------------
+ * The triangles of rtw_ctx_set_triangles move; the tree keeps its topology.  ouv: [n][9] f32 = origin, u, v of every triangle in the
+ * caller's list order, n the context's triangle count; a device or managed pointer of the context's GPU is read in place, anything else is
+ * staged.  On the device, on the context's stream (rtw_ctx_set_stream: behind the caller's producers of `ouv`), every triangle's derived
+ * fields are recomputed (Triangle::new) and every box of the tree from its triangles, inflated and rounded outward as the builder does.
+ * Materials, `tex`, the leaf order and the skip links stay.  The tree only prunes and every candidate runs the exact test, so a render or
+ * query after a refit gives what rtw_ctx_set_triangles of the same triangles gives, bit for bit; what a refit may cost is node visits (the
+ * splits were chosen for the old shape).  rtw_ctx_set_triangles remains the way to rebuild.  The call ends with one stream synchronise;
+ * *list_walk_out (may be NULL) = 1 when a triangle now breaks a condition of the tree (rtw_ctx_set_triangles' list) and the context walks
+ * the list until a later refit or set brings 0.  It reserves no memory.  RTW_E_NO_SCENE without triangles; RTW_E_INVALID for a NULL
+ * pointer, n other than the context's count, a pending render, and while placements are set (their top-level tree was built over the old
+ * root box: clear them, refit, set them again).  After RTW_E_HIP the triangles may be partly moved: placements are refused until a refit
+ * or rtw_ctx_set_triangles succeeds.  No rtw_mgpu_* form. */
+int rtw_ctx_refit_triangles(rtw_ctx *ctx, const float *ouv, uint32_t n, uint32_t *list_walk_out);
+/* The nodes of the context's triangle tree as the device holds them now.  nodes_out (may be NULL; node_cap entries, RTW_E_INVALID when too
+ * few) and *n_nodes (may be NULL).  RTW_E_NO_SCENE without triangles. */
+int rtw_ctx_triangle_bvh_dump(rtw_ctx *ctx, RtwTriNode *nodes_out, uint32_t node_cap, uint32_t *n_nodes);
+/* Host only: the tree rtw_ctx_set_triangles builds for `tris` -- nodes_out / node_cap / *n_nodes as above (2 n - 1 always suffice);
+ * order_out ([n], may be NULL): the triangle indices in leaf order; *depth; *list_walk.  RTW_E_INVALID for no triangles. */
+int rtw_triangle_bvh_dump(const RtwTriangle *tris, uint32_t n, RtwTriNode *nodes_out, uint32_t node_cap, uint32_t *n_nodes,
+                          uint32_t *order_out, uint32_t *depth, uint32_t *list_walk);
+/* Host only: that tree after a refit to `ouv` ([n][9]) -- the functions and the schedule the device runs, compiled for the host: the bytes
+ * rtw_ctx_triangle_bvh_dump returns after rtw_ctx_refit_triangles(ouv).  *list_walk as rtw_ctx_refit_triangles gives it. */
+int rtw_triangle_bvh_refit(const RtwTriangle *tris, uint32_t n, const float *ouv, RtwTriNode *nodes_out, uint32_t node_cap,
+                           uint32_t *n_nodes, uint32_t *list_walk);
+
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 
 /* Viewport::new (viewport.rs:308-401).  Options the reference takes as Option<> are pointers

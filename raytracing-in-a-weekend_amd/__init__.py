@@ -263,6 +263,10 @@ def lib() -> C.CDLL:
     L.rtw_ctx_set_triangles.argtypes = [C.c_void_p, C.POINTER(RtwTriangle), C.c_uint32]
     L.rtw_mgpu_set_triangles.argtypes = [C.c_void_p, C.POINTER(RtwTriangle), C.c_uint32]
     L.rtw_triangle_bvh_validate.argtypes = [C.POINTER(RtwTriangle), C.c_uint32] + [C.POINTER(C.c_uint32)] * 3
+    L.rtw_ctx_refit_triangles.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.rtw_ctx_triangle_bvh_dump.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.rtw_triangle_bvh_dump.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, C.c_void_p, C.c_uint32] + [C.POINTER(C.c_uint32)] * 4
+    L.rtw_triangle_bvh_refit.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, fp, C.c_void_p, C.c_uint32] + [C.POINTER(C.c_uint32)] * 2
     L.rtw_triangle_hits.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, fp, C.c_uint32, C.c_float, C.c_float, fp, C.POINTER(C.c_int32)]
     L.rtw_ctx_triangle_hits.argtypes = [C.c_void_p, fp, C.c_uint32, C.c_float, C.c_float, C.c_uint32, fp, C.POINTER(C.c_int32),
                                         C.POINTER(RtwStats)]
@@ -675,6 +679,49 @@ def triangle_bvh_validate(triangles):
     nn, dp, lw = C.c_uint32(), C.c_uint32(), C.c_uint32()
     rc = lib().rtw_triangle_bvh_validate(arr, n, C.byref(nn), C.byref(dp), C.byref(lw))
     return rc, nn.value, dp.value, lw.value
+
+
+def triangle_bvh_dump(triangles):
+    """rtw_triangle_bvh_dump: the tree set_triangles builds for `triangles` -- (nodes [n_nodes] of TOP_NODE, order [n] uint32: the triangle
+    indices in leaf order, depth, list_walk)."""
+    arr, n = _triangle_array(triangles)
+    nodes = np.zeros(max(2 * n, 1), TOP_NODE)
+    order = np.zeros(max(n, 1), np.uint32)
+    nn, dp, lw = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().rtw_triangle_bvh_dump(arr if n else None, n, nodes.ctypes.data, len(nodes), C.byref(nn), order.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       C.byref(dp), C.byref(lw)), "rtw_triangle_bvh_dump")
+    return nodes[:nn.value].copy(), order[:n].copy(), dp.value, lw.value
+
+
+def _ouv(ouv, n=None):
+    a = np.ascontiguousarray(ouv, np.float32).reshape(-1, 9)
+    if n is not None and len(a) != n:
+        raise ValueError(f"ouv holds {len(a)} triangles, the mesh {n}")
+    return a
+
+
+def triangle_bvh_refit(triangles, ouv):
+    """rtw_triangle_bvh_refit: the tree of `triangles` refitted on the host to ouv [n][9] = origin, u, v (mesh_ouv) -- the bytes
+    Renderer.triangle_bvh_dump returns after Renderer.refit_triangles(ouv): (nodes [n_nodes] of TOP_NODE, list_walk)."""
+    arr, n = _triangle_array(triangles)
+    a = _ouv(ouv, n)
+    nodes = np.zeros(max(2 * n, 1), TOP_NODE)
+    nn, lw = C.c_uint32(), C.c_uint32()
+    _check(lib().rtw_triangle_bvh_refit(arr if n else None, n, a.ctypes.data_as(C.POINTER(C.c_float)), nodes.ctypes.data, len(nodes), C.byref(nn),
+                                        C.byref(lw)), "rtw_triangle_bvh_refit")
+    return nodes[:nn.value].copy(), lw.value
+
+
+def mesh_ouv(vertices, faces) -> np.ndarray:
+    """An indexed mesh as Renderer.refit_triangles reads it: [n][9] float32 = origin, u, v per face, Triangle.from_mesh's arithmetic (face
+    (a, b, c) -> v[a], v[b] - v[a], v[c] - v[a] in f32).  With torch, on the device:
+        torch.cat([v[f[:,0]], v[f[:,1]] - v[f[:,0]], v[f[:,2]] - v[f[:,0]]], 1)"""
+    vtx = np.asarray(vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    if len(f) and (f.min() < 0 or f.max() >= len(vtx)):
+        raise ValueError("mesh_ouv: a face index is outside the vertex array")
+    o = vtx[f[:, 0]]
+    return np.ascontiguousarray(np.concatenate([o, vtx[f[:, 1]] - o, vtx[f[:, 2]] - o], 1), np.float32)
 
 
 def mesh_icosphere(level: int = 2, centre=(0.0, 0.0, 0.0), radius: float = 1.0):
@@ -1123,6 +1170,43 @@ class Renderer:
             return
         self._tris = _triangle_array(triangles)
         _check(lib().rtw_ctx_set_triangles(self._h, *self._tris), "rtw_ctx_set_triangles")
+
+    def refit_triangles(self, ouv, n: Optional[int] = None) -> int:
+        """rtw_ctx_refit_triangles: move the context's triangles to ouv [n][9] = origin, u, v (mesh_ouv) and refit their tree on the GPU, on
+        the context's stream; the topology, the materials and the list order stay, every answer is set_triangles' of the moved mesh.  `ouv`:
+        a numpy array (staged); an int device pointer with n= triangles; or anything with data_ptr() -- a torch tensor, float32, contiguous,
+        on the context's device, read in place behind its producers on the stream of use_torch_stream, e.g. for vertices v and faces f
+            r.refit_triangles(torch.cat([v[f[:,0]], v[f[:,1]] - v[f[:,0]], v[f[:,2]] - v[f[:,0]]], 1))
+        Returns list_walk: 1 when a triangle now breaks a condition of the tree and the context walks the list.  Not while placements are set."""
+        keep = ouv
+        if hasattr(ouv, "data_ptr"):
+            import torch
+            if ouv.dtype != torch.float32 or not ouv.is_contiguous() or not ouv.is_cuda or ouv.device.index != self._device:
+                raise ValueError("refit_triangles: the tensor must be float32, contiguous and on the context's device")
+            if ouv.numel() % 9:
+                raise ValueError("refit_triangles: the tensor must hold [n][9] floats")
+            ptr, cnt = int(ouv.data_ptr()), ouv.numel() // 9
+        elif isinstance(ouv, int):
+            if n is None:
+                raise ValueError("refit_triangles: a device pointer needs n=")
+            ptr, cnt = ouv, int(n)
+        else:
+            keep = _ouv(ouv)
+            ptr, cnt = keep.ctypes.data, len(keep)
+        if n is not None and int(n) != cnt:
+            raise ValueError(f"refit_triangles: ouv holds {cnt} triangles, n = {n}")
+        lw = C.c_uint32()
+        _check(lib().rtw_ctx_refit_triangles(self._h, C.c_void_p(ptr), cnt, C.byref(lw)), "rtw_ctx_refit_triangles")
+        del keep
+        return lw.value
+
+    def triangle_bvh_dump(self) -> np.ndarray:
+        """rtw_ctx_triangle_bvh_dump: the nodes of the context's triangle tree as the device holds them now ([n_nodes] of TOP_NODE)."""
+        nn = C.c_uint32()
+        _check(lib().rtw_ctx_triangle_bvh_dump(self._h, None, 0, C.byref(nn)), "rtw_ctx_triangle_bvh_dump")
+        nodes = np.zeros(nn.value, TOP_NODE)
+        _check(lib().rtw_ctx_triangle_bvh_dump(self._h, nodes.ctypes.data, len(nodes), None), "rtw_ctx_triangle_bvh_dump")
+        return nodes
 
     def set_lights(self, lights=None, biased_weight: float = 100.0):
         """rtw_ctx_set_lights for the current scene: (kind, index) pairs naming top-level spheres / quads (None: clear).  The lights of

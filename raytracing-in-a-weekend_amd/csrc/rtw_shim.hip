@@ -3,6 +3,7 @@
 // without a HIP device every render entry point fails with RTW_E_NO_DEVICE / RTW_E_HIP.
 #include "rtw_kernels.h"
 #include "rtw_mesh.h"
+#include "rtw_refit.h"
 #include "rtw_host.h"
 #include "rtw_filter.h"
 #include "rtw_devmem.h"
@@ -39,12 +40,18 @@ struct SceneMem {
     DevMem nodes, nodes16, nodes32, big_geom, big_vel, big_index;
 };
 struct NoiseMem { DevMem perlin, tex_noise; };
-struct TriMem { DevMem list, leaf, nodes; };
+struct TriMem {
+    DevMem list, leaf, nodes;
+    DevMem order, ouv, bad;              // the refit's (rtw_ctx_refit_triangles): its schedule, the staging of a host `ouv`, the count of refused triangles
+};
+#define REFIT_OUV_BYTES (9 * sizeof(float))      // one triangle of a refit's input: origin, u, v
+#define REFIT_READBACK_BYTES 64u                 // u32 count at 0, TriNode at 32
 struct QuatMem { DevMem rows; };
 struct MeshMem { DevMem rows, top; };     // top: the top-level tree's nodes, the leaf-order placement indices behind them
 struct ScratchMem {
     DevMem queue, stats;
     PinnedMem h_stats;                   // pinned: the counter read-back is a true async copy
+    PinnedMem h_refit;                   // a refit's read-back: the count of refused triangles, then node 0
     DevMem qstats; PinnedMem h_qstats;   // counters of the scene queries: RTW_QUERY_SLOTS lines of RTW_QUERY_STRIDE (rtw_kernels.h)
     DevMem out;                          // compact rows of a render whose destination the kernels cannot write
     PinnedMem h_out;                     // pinned staging for a multi-GPU frame in PAGEABLE host memory: a device-to-host copy into pageable memory returns only
@@ -84,6 +91,9 @@ struct rtw_ctx {
     bool tri_tree = false;               // no triangle breaks the cull's derivation (DESIGN.md "Rust2 triangles")
     TriNode tri_root{};                  // the tree's root: the box every placement's world box is formed from (rtw_ctx_set_mesh_instances)
     TriMem tri_mem;
+    bool tri_root_stale = false;         // a refit stopped half-way (a HIP error): tri_root no longer bounds the triangles; placements are refused until
+                                         // a refit or rtw_ctx_set_triangles succeeds
+    std::vector<uint32_t> refit_first;   // RefitSchedule.first of the tree in tri_mem (rtw_refit.h): the refit's launches
     // lights of the scene (rtw_ctx_set_lights; cleared by rtw_ctx_set_scene): the rows the light build reads from its arguments
     DevLights lights{};
     std::vector<RtwSphere> h_spheres;    // host copies of the top-level spheres and quads: a light's mid-point is formed from them
@@ -293,6 +303,8 @@ static void free_tris(rtw_ctx *c) {
     free_mesh(c);                        // (placements are placements of these triangles)
     c->tri_textured = false;
     c->tri_mem = TriMem{};
+    c->refit_first.clear();
+    c->tri_root_stale = false;
     c->tris = DevTris{};
     c->tri_tree = false;
 }
@@ -755,9 +767,17 @@ int rtw_ctx_set_triangles(rtw_ctx *c, const RtwTriangle *tris, uint32_t n) {
     if (!tri_build(list.data(), n, b)) return RTW_E_NOMEM;
     std::vector<DevTri> leaf(b.leaf, b.leaf + n);
     std::vector<TriNode> nodes(b.nodes, b.nodes + b.n_nodes);
+    RefitSchedule sched;
+    if (!tri_refit_schedule(b.nodes, b.n_nodes, sched)) return RTW_E_NOMEM;
     TriMem m;
     int rc;
     if ((rc = upload(m.list, list)) || (rc = upload(m.leaf, leaf)) || (rc = upload(m.nodes, nodes))) return rc;
+    // everything a refit needs, now: rtw_ctx_refit_triangles reserves nothing
+    if ((rc = upload(m.order, sched.order))) return rc;
+    HIP_TRY(m.ouv.reserve(REFIT_OUV_BYTES * (size_t)n));
+    HIP_TRY(m.bad.reserve(sizeof(uint32_t)));
+    HIP_TRY(c->scr.h_refit.reserve(REFIT_READBACK_BYTES));
+    c->refit_first = std::move(sched.first);
     c->tris.list = m.list.as<DevTri>(); c->tris.leaf = m.leaf.as<DevTri>();
     c->tris.n = n; c->tris.n_nodes = b.n_nodes;
     c->tri_tree = !b.list_walk;
@@ -767,6 +787,58 @@ int rtw_ctx_set_triangles(rtw_ctx *c, const RtwTriangle *tris, uint32_t n) {
     return RTW_OK;
 }
 
+// The triangles move, the tree's topology stays (rtw.h "refit"; device code: rtw_refit.hip).  On the context's stream, behind the caller's
+// producers of `ouv`; one synchronise at the end for the count of refused triangles and the new root.
+static int call_status(rtw_ctx *c, hipError_t e);
+static bool query_on_device(const rtw_ctx *c, const void *p);
+int rtw_ctx_refit_triangles(rtw_ctx *c, const float *ouv, uint32_t n, uint32_t *list_walk_out) {
+    if (!c) return RTW_E_INVALID;
+    if (!c->tris.n) return RTW_E_NO_SCENE;
+    if (!ouv || n != c->tris.n || c->pend.active || c->mesh_rows) return RTW_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    TriMem &m = c->tri_mem;
+    unsigned char *back = c->scr.h_refit.as<unsigned char>();
+    hipError_t e = hipSuccess;
+    const float *src = ouv;
+    if (!query_on_device(c, ouv)) {
+        e = hipMemcpyAsync(m.ouv.ptr, ouv, REFIT_OUV_BYTES * (size_t)n, hipMemcpyDefault, c->stream);
+        src = m.ouv.as<const float>();
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(m.bad.ptr, 0, sizeof(uint32_t), c->stream);
+    if (e == hipSuccess) {
+        launch_tri_refit(m.nodes.as<TriNode>(), m.leaf.as<DevTri>(), m.list.as<DevTri>(), src, m.order.as<const uint32_t>(), c->refit_first.data(),
+                         (uint32_t)c->refit_first.size() - 1u, m.bad.as<uint32_t>(), c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(back, m.bad.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(back + 32, m.nodes.ptr, sizeof(TriNode), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    // a refit that stopped half-way: the records may be partly moved, so the tree is not walked (the list answers from whatever the records
+    // hold) and tri_root is marked stale -- rtw_ctx_set_mesh_instances would form its world boxes from it
+    if (const int rc = call_status(c, e)) { c->tri_tree = false; c->tri_root_stale = true; return rc; }
+    uint32_t bad;
+    std::memcpy(&bad, back, sizeof bad);
+    std::memcpy(&c->tri_root, back + 32, sizeof(TriNode));
+    c->tri_tree = bad == 0;
+    c->tri_root_stale = false;
+    if (list_walk_out) *list_walk_out = bad ? 1u : 0u;
+    return RTW_OK;
+}
+
+int rtw_ctx_triangle_bvh_dump(rtw_ctx *c, RtwTriNode *nodes_out, uint32_t node_cap, uint32_t *n_nodes) {
+    static_assert(sizeof(RtwTriNode) == sizeof(TriNode), "the public node is the device's");
+    if (!c) return RTW_E_INVALID;
+    if (!c->tris.n) return RTW_E_NO_SCENE;
+    if (c->pend.active) return RTW_E_INVALID;
+    if (n_nodes) *n_nodes = c->tris.n_nodes;
+    if (!nodes_out) return RTW_OK;
+    if (node_cap < c->tris.n_nodes) return RTW_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    hipError_t e = hipMemcpyAsync(nodes_out, c->tri_mem.nodes.ptr, c->tris.n_nodes * sizeof(TriNode), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return call_status(c, e);
+}
+
 // ---- mesh placements (rtw.h "mesh placements"; device code: rtw_mesh.h) -----------------------------------------------------------------
 int rtw_ctx_set_mesh_instances(rtw_ctx *c, const RtwMeshInstance *p, uint32_t n) {
     if (!c) return RTW_E_INVALID;
@@ -774,7 +846,7 @@ int rtw_ctx_set_mesh_instances(rtw_ctx *c, const RtwMeshInstance *p, uint32_t n)
     if (c->pend.active || (n && !p) || (!n && p) || n > RTW_MAX_MESH_INSTANCES) return RTW_E_INVALID;
     std::vector<f4> rows;
     if (n) {
-        if (c->tri_textured) return RTW_E_INVALID;
+        if (c->tri_textured || c->tri_root_stale) return RTW_E_INVALID;
         try { rows.resize(2 * (size_t)n); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
         if (!mesh_rows(p, n, rows.data())) return RTW_E_INVALID;
     }

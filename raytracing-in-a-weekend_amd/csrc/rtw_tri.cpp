@@ -2,6 +2,7 @@
 // self-check and the host list walk (DESIGN.md "Rust2 triangles").
 #include "rtw_tri.h"
 #include "rtw_mesh.h"
+#include "rtw_refit.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -32,39 +33,7 @@ TriBuild::~TriBuild() { delete[] nodes; delete[] leaf; }
 
 namespace {
 
-// The static part of the cull's error radius (DESIGN.md "Rust2 triangles"), and the conditions under which the derivation holds.
-struct TriBox { double lo[3], hi[3], c[3]; };
-
-bool tri_box(const DevTri &t, TriBox &b) {
-    bool ok = true;
-    const float *f[] = { t.origin, t.u, t.v, t.normal, t.w };
-    for (const float *p : f) for (int k = 0; k < 3; k++) if (!std::isfinite(p[k])) ok = false;
-    if (!std::isfinite(t.d)) ok = false;
-    if (!ok) {
-        for (int k = 0; k < 3; k++) { b.lo[k] = b.hi[k] = b.c[k] = 0.0; }
-        return false;
-    }
-    double amax = 0.0;
-    for (int k = 0; k < 3; k++) {
-        const double a = t.origin[k], p = a + (double)t.u[k], q = a + (double)t.v[k];
-        b.lo[k] = std::min(a, std::min(p, q)); b.hi[k] = std::max(a, std::max(p, q));
-        amax = std::max(amax, std::max(std::fabs(b.lo[k]), std::fabs(b.hi[k])));
-        if (!(std::fabs((double)t.w[k]) <= 0x1p40)) ok = false;
-    }
-    const double lu = std::sqrt((double)t.u[0] * t.u[0] + (double)t.u[1] * t.u[1] + (double)t.u[2] * t.u[2]);
-    const double lv = std::sqrt((double)t.v[0] * t.v[0] + (double)t.v[1] * t.v[1] + (double)t.v[2] * t.v[2]);
-    const double nx = (double)t.u[1] * t.v[2] - (double)t.u[2] * t.v[1], ny = (double)t.u[2] * t.v[0] - (double)t.u[0] * t.v[2],
-                 nz = (double)t.u[0] * t.v[1] - (double)t.u[1] * t.v[0];
-    const double nl = std::sqrt(nx * nx + ny * ny + nz * nz), e = std::max(lu, lv);
-    const double kappa = nl > 0.0 ? e * e / nl : HUGE_VAL;
-    if (!(amax <= 0x1p40) || !(kappa <= 256.0)) ok = false;
-    const double r = 0x1p-24 * (256.0 * amax + 4096.0 * kappa * (1.0 + kappa) * e) + 0x1p-100;
-    for (int k = 0; k < 3; k++) {
-        b.lo[k] -= r; b.hi[k] += r;
-        b.c[k] = 0.5 * (b.lo[k] + b.hi[k]);
-    }
-    return ok;
-}
+// (The per-triangle box, tri_box, and the outward roundings live in rtw_refit.h: the refit on the device runs the same definitions.)
 
 // Binned SAH over box centres with a median fallback, leaves of <= 4: the triangle tree's builder, and the top-level tree's over the
 // placements' world boxes (mesh_top_build).  `order`: the items in leaf order; a leaf names a run of it.  Deterministic: no RNG, ties by index.
@@ -75,8 +44,8 @@ struct Builder {
     std::vector<uint32_t> order;
     uint32_t depth = 0;
 
-    static float down(double x) { float f = (float)x; if ((double)f > x) f = std::nextafter(f, -INFINITY); return f; }
-    static float up(double x) { float f = (float)x; if ((double)f < x) f = std::nextafter(f, INFINITY); return f; }
+    static float down(double x) { return box_down(x); }
+    static float up(double x) { return box_up(x); }
     static double area(const double *lo, const double *hi) {
         const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
         return dx * dy + dy * dz + dz * dx;
@@ -183,6 +152,38 @@ bool tri_build(const DevTri *list, uint32_t n, TriBuild &out) {
     } catch (const std::bad_alloc &) {
         return false;
     }
+}
+
+// ---- the refit of the triangle tree ----------------------------------------------------------------------------------------
+bool tri_refit_schedule(const TriNode *nodes, uint32_t n_nodes, RefitSchedule &out) {
+    try {
+        // depth-first order: both children of a node come after it, so one backward sweep knows them
+        std::vector<uint32_t> height(n_nodes, 0);
+        uint32_t top = 0;
+        for (uint32_t i = n_nodes; i-- > 0;) {
+            if (!nodes[i].leaf) height[i] = 1u + std::max(height[i + 1], height[nodes[i + 1].skip]);
+            top = std::max(top, height[i]);
+        }
+        out.first.assign(n_nodes ? (size_t)top + 2 : 1, 0);
+        for (uint32_t i = 0; i < n_nodes; i++) out.first[height[i] + 1]++;
+        for (size_t h = 1; h < out.first.size(); h++) out.first[h] += out.first[h - 1];
+        out.order.resize(n_nodes);
+        std::vector<uint32_t> at(out.first.begin(), out.first.end() - (n_nodes ? 1 : 0));
+        for (uint32_t i = 0; i < n_nodes; i++) out.order[at[height[i]]++] = i;
+        return true;
+    } catch (const std::bad_alloc &) {
+        return false;
+    }
+}
+
+uint32_t tri_refit_host(TriNode *nodes, DevTri *leaf, DevTri *list, const float *ouv, const RefitSchedule &s) {
+    uint32_t bad = 0;
+    for (size_t h = 0; h + 1 < s.first.size(); h++)
+        for (uint32_t k = s.first[h]; k < s.first[h + 1]; k++) {
+            if (h == 0) bad += refit_leaf_node(nodes, leaf, list, ouv, s.order[k]);
+            else refit_inner_node(nodes, s.order[k]);
+        }
+    return bad;
 }
 
 // ---- the top-level tree over mesh placements ---------------------------------------------------------------------------
@@ -452,6 +453,43 @@ int rtw_triangle_bvh_validate(const RtwTriangle *tris, uint32_t n, uint32_t *n_n
     if (depth) *depth = b.depth;
     if (list_walk) *list_walk = b.list_walk ? 1u : 0u;
     return ok ? RTW_OK : RTW_E_INVALID;
+}
+
+// The tree rtw_ctx_set_triangles builds, and its refit, without a context
+int rtw_triangle_bvh_dump(const RtwTriangle *tris, uint32_t n, RtwTriNode *nodes_out, uint32_t node_cap, uint32_t *n_nodes, uint32_t *order_out,
+                          uint32_t *depth, uint32_t *list_walk) {
+    if (!tris || n == 0) return RTW_E_INVALID;
+    std::vector<DevTri> list;
+    try { list.resize(n); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+    tri_prepare(tris, n, list.data());
+    TriBuild b;
+    if (!tri_build(list.data(), n, b)) return RTW_E_NOMEM;
+    if (n_nodes) *n_nodes = b.n_nodes;
+    if (depth) *depth = b.depth;
+    if (list_walk) *list_walk = b.list_walk ? 1u : 0u;
+    if (nodes_out) {
+        if (node_cap < b.n_nodes) return RTW_E_INVALID;
+        std::memcpy(nodes_out, b.nodes, b.n_nodes * sizeof(TriNode));
+    }
+    if (order_out) for (uint32_t j = 0; j < n; j++) order_out[j] = b.leaf[j].index;
+    return RTW_OK;
+}
+
+int rtw_triangle_bvh_refit(const RtwTriangle *tris, uint32_t n, const float *ouv, RtwTriNode *nodes_out, uint32_t node_cap, uint32_t *n_nodes,
+                           uint32_t *list_walk) {
+    if (!tris || n == 0 || !ouv) return RTW_E_INVALID;
+    std::vector<DevTri> list;
+    try { list.resize(n); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+    tri_prepare(tris, n, list.data());
+    TriBuild b;
+    RefitSchedule s;
+    if (!tri_build(list.data(), n, b) || !tri_refit_schedule(b.nodes, b.n_nodes, s)) return RTW_E_NOMEM;
+    if (n_nodes) *n_nodes = b.n_nodes;
+    if (nodes_out && node_cap < b.n_nodes) return RTW_E_INVALID;
+    const uint32_t bad = tri_refit_host(b.nodes, b.leaf, list.data(), ouv, s);
+    if (list_walk) *list_walk = bad ? 1u : 0u;
+    if (nodes_out) std::memcpy(nodes_out, b.nodes, b.n_nodes * sizeof(TriNode));
+    return RTW_OK;
 }
 
 } // extern "C"
