@@ -1103,15 +1103,22 @@ __device__ __forceinline__ void trav_node_lds(const u4 *lnodes, Trav &tr) {
 // the lane reads each {near, far} pair where its ray's direction along the axis says (tr.sel*, 0 or RTW_NODE32_OFF bytes into the group):
 // three address adds in place of six v_perm_b32, twelve plain v_fma_f32 in place of twelve v_fma_mix_f32.  fma(widen(plane), 1/d, k) is
 // what v_fma_mix_f32 computes from the f16 plane, so every box decision is the f16 visit's.
+//
+// Each pair is read by a ds_read_b64 of its own.  Left to itself the compiler fuses the two pairs of an axis into one ds_read2_b64, which
+// the LDS serves in its narrow mode: 32 banks in groups of 16 lanes, 8 array cycles per wave, where a ds_read_b64 takes 2 over 64 banks in
+// groups of 32 lanes.  Measured on the bench frame: the LDS array busy for 40 % of the CU's cycles instead of 62 %, bank-conflict cycles
+// -28 %, frame -1.0 % (profiles/large_block_budget_ab.log).  A volatile access is one the compiler may not fuse; unlike inline assembly
+// it leaves the waits to the compiler, which still counts them (s_waitcnt lgkmcnt(n) per pair, not one wait for all).
 typedef float f2a __attribute__((ext_vector_type(2), aligned(RTW_NODE32_OFF)));
+__device__ __forceinline__ f2a lds_get_pair(uint32_t addr) { return *(const volatile __attribute__((address_space(3))) f2a *)(uintptr_t)addr; }
 template <uint32_t BLOCK>
 __device__ __forceinline__ void trav_node_lds32(Trav &tr) {
     const uint32_t popped = lds_get<unsigned short>(tr.sp);
     constexpr uint32_t G = RTW_NODE32_AXIS_DWORDS * 4u;               // bytes per (box, axis) group
     const uint32_t ax = ((uint32_t)tr.node << RTW_NODE32_UNIT_SHIFT) + tr.selx, ay = ((uint32_t)tr.node << RTW_NODE32_UNIT_SHIFT) + tr.sely,
                    az = ((uint32_t)tr.node << RTW_NODE32_UNIT_SHIFT) + tr.selz;
-    const f2a px0 = lds_get<f2a>(ax), py0 = lds_get<f2a>(ay + G), pz0 = lds_get<f2a>(az + 2u * G);
-    const f2a px1 = lds_get<f2a>(ax + 3u * G), py1 = lds_get<f2a>(ay + 4u * G), pz1 = lds_get<f2a>(az + 5u * G);
+    const f2a px0 = lds_get_pair(ax), py0 = lds_get_pair(ay + G), pz0 = lds_get_pair(az + 2u * G);
+    const f2a px1 = lds_get_pair(ax + 3u * G), py1 = lds_get_pair(ay + 4u * G), pz1 = lds_get_pair(az + 5u * G);
     const uint32_t c0 = lds_get<uint32_t>(ax + 6u * G), c1 = 0;       // {c0, c1}: stored at both x offsets
     const float e0 = fmaxf(fmaxf(__builtin_fmaf(px0.x, tr.ix, tr.kpx), __builtin_fmaf(py0.x, tr.iy, tr.kpy)), __builtin_fmaf(pz0.x, tr.iz, tr.kpz));
     const float x0 = fminf(fminf(__builtin_fmaf(px0.y, tr.ix, tr.kmx), __builtin_fmaf(py0.y, tr.iy, tr.kmy)), __builtin_fmaf(pz0.y, tr.iz, tr.kmz));
