@@ -329,6 +329,28 @@ int  rtw_ctx_last_render_build(rtw_ctx *ctx, char *buf, size_t n);
 /* ... and the format of the tree that build read from LDS: 0 none (list walk, or nodes in global memory), 1 f16 nodes, 2 f32 planes
  * (RTW_OPT_NODE_FORMAT).  Host only.  RTW_E_INVALID before the context's first render.  (added within v4) */
 int  rtw_ctx_last_node_format(rtw_ctx *ctx);
+/* Host only (no context, no GPU), for tests and diagnostics: the build and the dynamic LDS layout a render would launch, from plain facts
+ * -- the same functions the render itself calls, once each.  RtwRenderFacts: what the request needs -- the integrator, sampler, depth and
+ * flags of RtwParams (RTW_FLAG_MIXED_MATERIAL only where the scene holds a MixedMaterial object), whether a sphere has an image texture,
+ * and counts (or 0 / 1) of quads, instances, textures with noise in use, triangles, instance rotations and mesh placements.  RtwTreeFacts:
+ * the sphere tree as rtw_bvh_dump describes it (has_planes: 1 wherever has_f16 is), and the scene's sphere count.  opt_lds_geom /
+ * opt_node_format: RTW_OPT_LDS_GEOM and RTW_OPT_NODE_FORMAT.  moving: a sphere moves.  accel: the strategy actually walked, i.e. after the
+ * downgrades of a BVH request to the list walk (RTW_OPT_LIST_WALK_MAX, cameras and ranges the tree does not serve).  out->build is the
+ * text rtw_ctx_last_render_build prints, node_format what rtw_ctx_last_node_format answers, block the threads per workgroup; the LDS
+ * numbers are bytes (lds_geom_off 0: the sphere geometry stays in global memory; lds_tri_off: the triangle build's counter, the last 16 bytes of a
+ * request with triangles).  RTW_E_INVALID on a null pointer or an accel / option out of range, RTW_E_UNSUPPORTED when no such build is compiled.
+ * (added within v4) */
+typedef struct RtwRenderFacts {
+    uint32_t integrator, sampler, depth, flags, has_textures;
+    uint32_t n_quads, n_instances, noise, n_triangles, rotations, placements;
+} RtwRenderFacts;
+typedef struct RtwTreeFacts { uint32_t n_nodes, depth, n_spheres, has_f16, has_planes; } RtwTreeFacts;
+typedef struct RtwRenderChoice {
+    char build[32];
+    uint32_t node_format, block, lds_stack_off, lds_geom_off, lds_tri_off, lds_bytes;
+} RtwRenderChoice;
+int  rtw_render_choice(const RtwRenderFacts *request, const RtwTreeFacts *tree, int32_t opt_lds_geom, uint32_t opt_node_format,
+                       uint32_t moving, uint32_t accel, RtwRenderChoice *out);
 
 /* ---- one frame over several GPUs of a node ------------------------------------------------------
  * The reference forks one task per image row and joins them in order (tokio: Rust/src/viewport.rs:236-244; rayon:

@@ -175,6 +175,21 @@ class RtwFilterStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RtwRenderFacts(C.Structure):
+    """What a render request needs of its build (include/rtw.h rtw_render_choice): RtwParams' four, and counts (or 0 / 1) of what the scene holds."""
+    _fields_ = [(k, C.c_uint32) for k in ("integrator", "sampler", "depth", "flags", "has_textures", "n_quads", "n_instances", "noise",
+                                          "n_triangles", "rotations", "placements")]
+
+
+class RtwTreeFacts(C.Structure):
+    """The sphere tree as rtw_bvh_dump describes it, and the scene's sphere count."""
+    _fields_ = [(k, C.c_uint32) for k in ("n_nodes", "depth", "n_spheres", "has_f16", "has_planes")]
+
+
+class RtwRenderChoice(C.Structure):
+    _fields_ = [("build", C.c_char * 32)] + [(k, C.c_uint32) for k in ("node_format", "block", "lds_stack_off", "lds_geom_off", "lds_tri_off", "lds_bytes")]
+
+
 _lib = None
 
 
@@ -205,6 +220,9 @@ def lib() -> C.CDLL:
     L.rtw_ctx_set_option.argtypes = [C.c_void_p, C.c_uint32, C.c_double]
     L.rtw_ctx_last_render_build.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rtw_ctx_last_node_format.argtypes = [C.c_void_p]
+    if hasattr(L, "rtw_render_choice"):     # (added within v4: an RTW_HIP_LIB build of the same ABI may predate it)
+        L.rtw_render_choice.argtypes = [C.POINTER(RtwRenderFacts), C.POINTER(RtwTreeFacts), C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.POINTER(RtwRenderChoice)]
     L.rtw_mgpu_create.argtypes = [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)]
     L.rtw_mgpu_destroy.argtypes = [C.c_void_p]
     L.rtw_mgpu_destroy.restype = None
@@ -471,6 +489,16 @@ def light_term(integrator: int, pdf, e, t, direction, weight, S, count):
 def mixed(exp: float):
     """The material triple of Rust2's MixedMaterial::new(exp) under FLAG_MIXED_MATERIAL: (metallicness, opacity, ir) = (0, -1, exp)."""
     return (0.0, -1.0, float(exp))
+
+
+def render_choice(request: RtwRenderFacts, tree: RtwTreeFacts, lds_geom: int = -1, node_format: int = 0, moving: bool = False,
+                  accel: int = ACCEL_BVH) -> dict:
+    """rtw_render_choice: the build a render of these facts launches and its dynamic LDS (host only) -- `build` as Renderer.last_render_build()
+    writes it, `node_format` as last_node_format(), `block` threads per workgroup, the LDS offsets and size in bytes."""
+    out = RtwRenderChoice()
+    _check(lib().rtw_render_choice(C.byref(request), C.byref(tree), int(lds_geom), int(node_format), 1 if moving else 0, int(accel), C.byref(out)),
+           "rtw_render_choice")
+    return {"build": out.build.decode(), **{k: int(getattr(out, k)) for k, _ in RtwRenderChoice._fields_[1:]}}
 
 
 def mixed_validate(scene: "Scene", params: "RtwParams", n_triangles: int = 0, texture_noise: bool = False) -> int:

@@ -749,27 +749,86 @@ uint16_t half_bits(float f, bool up) {
 }
 } // namespace
 
-// Deepest level a leaf may sit on.  A tree that can live in LDS as f16 nodes shares the workgroup's LDS with the per-lane stack:
-// nodes * 32 + (depth + 3) * RTW_BLOCK * 2 bytes (rtw_shim.hip), and the render kernel keeps seven workgroups on a CU only while that
-// stays within a seventh of its 160 KiB -- one level too many costs the seventh workgroup (profiles/r03_ab_tau_lds.log).  So the cap is the
+// Deepest level a leaf may sit on.  A tree that can live in LDS as f16 nodes shares the workgroup's LDS with the per-lane stack
+// (render_lds_layout below), and the render kernel keeps seven workgroups on a CU only while that stays within a seventh of the CU's LDS
+// -- one level too many costs the seventh workgroup (profiles/r03_ab_tau_lds.log).  So the cap is the
 // deepest tree that still fits that share, never above the device stack and never below what a balanced tree of n leaves needs.
-// The shim also puts the scene's sphere geometry (n_spheres * 16 bytes, big spheres included) behind the stack while the whole stays
+// The layout also puts the scene's sphere geometry (n_spheres * 16 bytes, big spheres included) behind the stack while the whole stays
 // within a SIXTH of the CU's LDS: where a balanced tree leaves room for it, the cap keeps that room too, so that a deeper tree never
 // pushes the geometry out.  (The stack has at least four levels, which only matters below depth 1.)
 uint32_t bvh_depth_cap(uint32_t n_leaves, uint32_t n_spheres, bool lds_candidate) {
     uint32_t cap = RTW_BVH_STACK;
     const uint32_t balanced = ceil_log2(std::max(n_leaves, 1u));
     if (lds_candidate && n_leaves >= 2) {
-        const uint32_t node_bytes = ((n_leaves - 1u) * 32u + 15u) & ~15u, level_bytes = RTW_BVH_LDS_LEVEL_BYTES;
+        const uint32_t node_bytes = lds_align16((n_leaves - 1u) * 32u), level_bytes = lds_stack_bytes(1u, RTW_BLOCK, 2u);
         auto deepest = [&](uint32_t share, uint32_t fixed) {       // depth d with fixed + (d + 3) * level_bytes <= share, or 0
             const uint32_t levels = share > fixed ? (share - fixed) / level_bytes : 0u;
             return levels > 3u ? levels - 3u : 0u;
         };
-        cap = std::min(cap, deepest(160u * 1024u / 7u, node_bytes));
-        const uint32_t with_geom = deepest(160u * 1024u / 6u, node_bytes + n_spheres * 16u);
+        cap = std::min(cap, deepest(RTW_CU_LDS_BYTES / RTW_LDS_SHARE_TREE, node_bytes));
+        const uint32_t with_geom = deepest(RTW_CU_LDS_BYTES / RTW_LDS_SHARE_GEOM, node_bytes + n_spheres * 16u);
         if (with_geom >= balanced) cap = std::min(cap, with_geom);
     }
     return std::max(cap, balanced);
+}
+
+RenderNeed render_need(const RtwRenderFacts &f) {
+    const bool objects = f.n_quads || f.n_instances;
+    // instance rotations (set only for a scene with instances, under RUST2 / LIGHT_CAST / LIGHT_BIASED): the quaternion build, for every
+    // sampler and flag, with or without RTW_FLAG_MIXED_MATERIAL
+    if (f.rotations) return { 11, true };
+    // mesh placements (RTW_INTEGRATOR_RUST2 alone): the placement build
+    if (f.placements) return { 12, true };
+    // RTW_FLAG_MIXED_MATERIAL on a scene with a MixedMaterial object (the caller clears the bit otherwise): the mixed build, for every sampler and flag
+    if (f.flags & RTW_FLAG_MIXED_MATERIAL) return { 10, objects };
+    // Rust2's light-biased integrators: the light build, for every sampler and flag (never with noise or triangles)
+    if (f.integrator == RTW_INTEGRATOR_LIGHT_CAST || f.integrator == RTW_INTEGRATOR_LIGHT_BIASED) return { 9, objects };
+    // a texture that a sphere, quad or member uses has noise: the noise build, for every integrator, sampler and flag
+    if (f.noise) return { 7, objects };
+    // triangles (never together with noise): the triangle build, for every integrator, sampler and flag
+    if (f.n_triangles) return { 8, true };
+    // The configurations with builds of their own, switches folded in at compile time: the common one (ray_color_gradient through render_row),
+    // presentation_image's (ray_color_bg_color through render_row), Rust2's (ray_color through its fixed-centre render_row) and
+    // Viewport::render's (ray_color_gradient, stratified).  RTW_FLAG_CHUNK_SUMS has a build (3) for the common one without textures alone.
+    const bool plain = f.depth >= 1 && (f.flags & (RTW_FLAG_CPP_DIELECTRIC | RTW_FLAG_CPP_DIFFUSE)) == 0u, sums = (f.flags & RTW_FLAG_CHUNK_SUMS) != 0u;
+    const bool common = plain && f.integrator == RTW_INTEGRATOR_GRADIENT && f.sampler == RTW_SAMPLER_ROW;
+    int folded = 0;
+#ifndef RTW_GEOM_GENERIC_ONLY
+    if (plain && !sums) {
+        if (f.integrator == RTW_INTEGRATOR_BG_COLOR && f.sampler == RTW_SAMPLER_ROW) folded = 4;
+        if (f.integrator == RTW_INTEGRATOR_RUST2 && f.sampler == RTW_SAMPLER_CENTRES) folded = 5;
+        if (f.integrator == RTW_INTEGRATOR_GRADIENT && f.sampler == RTW_SAMPLER_STRATIFIED) folded = 6;
+        if (common && objects) folded = 2;          // (sphere textures kept: has_textures does not matter with GEOM)
+    }
+#endif
+    if (objects || folded) return { folded, objects };
+    if (!common) return { 0, false };
+    if (sums) return { f.has_textures ? 0 : 3, false };
+    return { f.has_textures ? 2 : 1, false };
+}
+
+LdsLayout render_lds_layout(const RtwTreeFacts &t, int opt_lds_geom, uint32_t opt_node_format, bool bvh, bool global_nodes, bool geom, bool large,
+                            bool triangles) {
+    LdsLayout L{ 0, 0u, RTW_BLOCK, 0u, 0u, 0u, 0u };
+    if (bvh) {
+        const bool ldsn = t.has_f16 && !global_nodes;
+        const uint32_t levels = std::max(t.depth + 3u, 4u), geom_bytes = t.n_spheres * 16u;
+        if (ldsn) L.stack_off = lds_align16(t.n_nodes * 32u);
+        const uint32_t end = L.stack_off + lds_stack_bytes(levels, RTW_BLOCK, ldsn ? 2u : 4u);      // of the f16 nodes and a 256-thread stack
+        bool geom_lds = end + geom_bytes <= RTW_CU_LDS_BYTES / RTW_LDS_SHARE_GEOM;
+        if (opt_lds_geom >= 0) geom_lds = opt_lds_geom != 0 && t.n_spheres <= RTW_LDS_GEOM_MAX;
+        geom_lds = geom_lds && ldsn && !geom && opt_node_format != 2u;
+        L.nodes = ldsn ? 1 : 0; L.node_format = ldsn ? 1u : 0u; L.bytes = end;
+        if (ldsn && large && !geom_lds) {
+            const uint32_t planes = t.n_nodes * RTW_NODE32_DWORDS * 4u, need = planes + lds_stack_bytes(levels, RTW_BLOCK_LARGE, 2u);      // (planes: a multiple of 16)
+            if (t.has_planes && (opt_node_format == 2u ? need <= RTW_CU_LDS_BYTES : (opt_node_format == 0u && 2u * need <= RTW_CU_LDS_BYTES))) {
+                L.node_format = 2u; L.block = RTW_BLOCK_LARGE; L.stack_off = planes; L.bytes = need;
+            } else geom_lds = true;
+        }
+        if (geom_lds) { L.nodes = 2; L.geom_off = end; L.bytes = end + geom_bytes; }
+    }
+    if (triangles) { L.tri_off = lds_align16(L.bytes); L.bytes = L.tri_off + 16u; }   // the triangle build's node-visit counter
+    return L;
 }
 
 void build_bvh(const RtwSphere *spheres, uint32_t n, float t_begin, float t_end, BvhBuild &out, const BvhBuildOptions &opt) {

@@ -58,8 +58,7 @@ static_assert(RTW_LDS_NODES_MAX <= RTW_NODE32_NODES_MAX, "every tree with f16 no
 
 #define RTW_MAX_BIG 16        // spheres far larger than the rest are tested exactly, outside the tree
 #define RTW_BVH_STACK 24      // builder guarantees depth <= RTW_BVH_STACK (median-split fallback near the limit)
-#define RTW_BVH_LDS_LEVEL_BYTES 512u   // one level of the LDS-variant's per-lane stack: RTW_BLOCK (256) lanes x a 16-bit entry
-#define RTW_BVH_OPTIMISE_MAX 1024u     // tree spheres up to which the builder sweeps every split (n log n per level) and runs the reinsertion pass.
+#define RTW_BVH_OPTIMISE_MAX 1024u    // tree spheres up to which the builder sweeps every split (n log n per level) and runs the reinsertion pass.
                                        // Larger scenes get the binned top-down tree alone.
 #ifndef RTW_BVH_REINSERT_WORK
 #define RTW_BVH_REINSERT_WORK 128u     // the reinsertion pass's work budget: search steps per tree node (set_scene is on the caller's path)
@@ -98,6 +97,47 @@ void build_bvh(const RtwSphere *spheres, uint32_t n, float t_begin, float t_end,
 // The f32 plane format of a tree's f16 nodes (above): derived from nodes16 by widening, never a second rounding of the f32 boxes -- the
 // walk over it is then the walk over nodes16, decision for decision.  Empty in, empty out.
 void pack_nodes32(const std::vector<BvhNode16> &nodes16, std::vector<uint32_t> &out);
+
+// ---- which render build a launch runs, and its dynamic LDS --------------------------------------------------------------------
+// Three steps, each a function of plain values: render_need -- what the request needs --, render_lds_layout -- what the
+// tree allows --, and the kernel of the RenderBuild the two name (rtw_kernels.h render_kernel).  rtw_shim.hip calls each once per render;
+// rtw_render_choice (rtw.h) runs the same three without a device.
+#ifndef RTW_BLOCK
+#define RTW_BLOCK 256         // 4 waves per workgroup
+#endif
+#define RTW_BLOCK_LARGE 768   // 12 waves: the static LDS-node builds that walk f32 planes (rtw_kernels.hip bvh_block); two per CU
+// A CU's LDS, and the shares of it the 256-thread builds are laid out for: a tree's f16 nodes and stack within a seventh (seven workgroups
+// per CU, 7 waves per SIMD), the same with the spheres' geometry behind them within a sixth (six, the kernel's register budget).
+#define RTW_CU_LDS_BYTES (160u * 1024u)
+#define RTW_LDS_SHARE_TREE 7u
+#define RTW_LDS_SHARE_GEOM 6u
+static inline uint32_t lds_align16(uint32_t bytes) { return (bytes + 15u) & ~15u; }
+// The per-lane traversal stack, [level][thread]: `levels` rows of `block` entries
+static inline uint32_t lds_stack_bytes(uint32_t levels, uint32_t block, uint32_t entry_bytes) { return lds_align16(levels * block * entry_bytes); }
+
+// The SPEC a request runs and whether it needs the GEOM stage (quads, instances, triangles, rotations, placements).  !geom is also
+// "there is a build that reads the spheres' {centre, r^2} from LDS" (NODES == 2 exists without GEOM only).
+struct RenderNeed { int spec; bool geom; };
+RenderNeed render_need(const RtwRenderFacts &f);
+
+// NODES and the dynamic LDS of a launch.  nodes / node_format / block: the NODES template argument, the LDS node format (0 none, 1 f16
+// nodes, 2 f32 planes) and the threads per workgroup; stack_off / geom_off / tri_off / bytes: KArgs.lds_stack_off / lds_geom_off /
+// tris.lds_off / lds_bytes (geom_off 0: the geometry stays in global memory; tri_off: the last 16 bytes of a request with triangles).
+struct LdsLayout { int nodes; uint32_t node_format, block, stack_off, geom_off, tri_off, bytes; };
+// bvh: the tree is walked (else the list: no LDS but the triangle counter's); global_nodes: RTW_FLAG_GLOBAL_NODES; geom: RenderNeed.geom;
+// large: the request's NODES == 1 build is a large-workgroup one (bvh_block); triangles: the request has some.
+// The layout: f16 nodes FIRST (LDS offset 0: the hottest address of the kernel, the node fetch of every visit, then needs no base register
+// -- as the second block its offset was an SGPR the allocator spilled, one v_readlane per visit), then the per-lane stack (sentinel + one
+// entry per tree level + the slot above the top the descend step always writes, at least four levels; 16-bit entries beside LDS nodes),
+// then the optional sphere geometry: it rides along (NODES == 2) only while the workgroup stays under a sixth of the CU, i.e. while it does
+// not cost a resident workgroup, or as RTW_OPT_LDS_GEOM says (n_spheres <= RTW_LDS_GEOM_MAX), never under RTW_OPT_NODE_FORMAT = 2.
+// A large-workgroup build walks the tree as f32 planes, its stack's rows are RTW_BLOCK_LARGE entries, and it is meant to run two workgroups
+// per CU (24 waves, 6 per SIMD).  Both fit the CU for every tree build_bvh gives f16 nodes within its depth cap: 3.5 x the node bytes + 3 x the
+// stack bytes of a layout that fits a seventh.  A tree that does not fit (once, under RTW_OPT_NODE_FORMAT = 2), or RTW_OPT_NODE_FORMAT = 1,
+// takes the f16 walk at RTW_BLOCK threads in the build that holds the spheres' geometry in LDS too (NODES == 2: a large build has no GEOM
+// stage, and a tree with f16 nodes has at most RTW_LDS_GEOM_MAX spheres) -- whatever RTW_OPT_LDS_GEOM says.
+LdsLayout render_lds_layout(const RtwTreeFacts &t, int opt_lds_geom, uint32_t opt_node_format, bool bvh, bool global_nodes, bool geom, bool large,
+                            bool triangles);
 
 // Host twin of the render kernel's closest-hit query over a built tree (a measuring and testing tool: the product traverses on the
 // GPU).  Same order of events: the big list first, per-ray rho / tau, boxes inflated by rho, the f16 outward-rounded planes when the

@@ -11,10 +11,6 @@
 #ifndef RTW_SUB_SHIFT
 #define RTW_SUB_SHIFT 3u        // log2 of the number of sub-queues (8: one per XCD; 16 and 32 measured no better, profiles/r02_subq_count.log)
 #endif
-#ifndef RTW_BLOCK
-#define RTW_BLOCK 256   // 4 waves per workgroup
-#endif
-#define RTW_BLOCK_LARGE 768   // 12 waves: the static LDS-node builds that walk f32 planes (rtw_kernels.hip bvh_block); two per CU
 #define RTW_N_STATS 64  // 64-bit counters a render launch accumulates (KArgs.stats); [32..63] are used by the -DRTW_CENSUS diagnostic build only
 #ifndef RTW_LIST_WALK_MAX_DEFAULT
 #define RTW_LIST_WALK_MAX_DEFAULT 48u  // RTW_OPT_LIST_WALK_MAX: scenes this small walk the list even when the BVH is asked for (measured crossover ~56 spheres: profiles/r02_crossover.log)
@@ -70,10 +66,10 @@ struct KArgs {
     uint32_t n_samples;           // rays per pixel actually traced (sampler-dependent)
     uint32_t s_root;              // strata per axis (STRATIFIED / CENTRES)
     uint32_t sampler, integrator, depth;
-    uint32_t has_textures;        // any sphere with an image texture (selects the generic kernel)
-    uint32_t lds_bytes;           // dynamic LDS of the BVH kernel: f16 nodes | stack | sphere geometry
-    uint32_t lds_stack_off, lds_geom_off;   // byte offsets (16-aligned) of the per-lane stack and of the sphere geometry (0: geometry stays in
-                                            // global memory); the f16 nodes sit at offset 0
+    uint32_t has_textures;        // any sphere with an image texture (a fact render_need reads: the common configuration's build that keeps the lookup)
+    uint32_t lds_bytes;           // dynamic LDS of the BVH kernel: nodes | stack | sphere geometry (rtw_host.h render_lds_layout, which sets all three)
+    uint32_t lds_stack_off, lds_geom_off;   // byte offsets (16-aligned) of the per-lane stack and of the sphere geometry, which the NODES == 2
+                                            // builds alone read; the nodes sit at offset 0
     uint32_t seed_lo, seed_hi;
     float inv_gamma, mint, maxt;
     float bg[3];
@@ -91,17 +87,22 @@ struct KArgs {
                                   // the quaternion build (SPEC 11), which alone reads it (and the lights, for every integrator it serves)
     const f4 *mesh_rows;          // mesh placements (rtw_ctx_set_mesh_instances): two rows {qn}, {position, 0} per placement (rtw_mesh.h); non-null selects
     uint32_t n_mesh;              // the placement build (SPEC 12), which alone reads them: tris is then the mesh every placement shares
-    const uint32_t *nodes32;      // the tree's f32 plane format (rtw_host.h pack_nodes32): what the large-workgroup builds (kernel_block() !=
-                                  // RTW_BLOCK) copy into LDS instead of bvh.nodes16; they alone read it
+    const uint32_t *nodes32;      // the tree's f32 plane format (rtw_host.h pack_nodes32): what the large-workgroup builds copy into LDS instead of
+                                  // bvh.nodes16; they alone read it, and it is set for them alone (LdsLayout.node_format == 2)
     const TriNode *mesh_top;      // the top-level tree over the placements (rtw_mesh.h mesh_top_walk; the order array sits behind the nodes), or
     uint32_t n_mesh_top;          // null: the placements are met in list order.  Read by the placement build alone
 };
 
-// Which instantiation of render_brute<MOVING, SPEC, GEOM> / render_bvh<MOVING, NODES, SPEC, GEOM> a launch ran (nodes: 0 for render_brute)
+// One instantiation of render_brute<MOVING, SPEC, GEOM> / render_bvh<MOVING, NODES, SPEC, GEOM> (nodes: 0 for render_brute): what a launch
+// runs and what rtw_ctx_last_render_build reports are this one value.
 struct RenderBuild { bool bvh, moving, geom; int nodes, spec; };
-// accel: RTW_ACCEL_BRUTE, RTW_ACCEL_BVH; the BVH launch picks the LDS-resident variant when a.bvh.nodes16 != null; *build (if not null) receives
-// the build that was launched
-void launch_render(const KArgs &a, bool moving, uint32_t accel, uint32_t grid, hipStream_t stream, RenderBuild *build);
+typedef void (*render_fn)(const KArgs);
+// The kernel of a build, or null: none is compiled for these five values
+render_fn render_kernel(const RenderBuild &b);
+// Its threads per workgroup: RTW_BLOCK, or RTW_BLOCK_LARGE for the builds that walk the f32 plane format (bvh_block of the same five values)
+uint32_t render_block(const RenderBuild &b);
+// The render kernel with a.lds_bytes of dynamic LDS, then the in-order resolve of the band, on `stream`
+void launch_render(render_fn fn, uint32_t block, const KArgs &a, uint32_t grid, hipStream_t stream);
 // rtw_ctx_perlin_eval: out[i] = perlin_eval(*t, points[i], depth) for i < n (device pointers), on `stream`
 void launch_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t depth, float *out, hipStream_t stream);
 // rtw_ctx_triangle_hits: the closest triangle of T for each of n rays ([n][6] = o, d; device pointers), on `stream`; counters[0] triangle
@@ -141,17 +142,5 @@ void launch_scene_hits(const QueryArgs &q, bool from_camera, bool tree, hipStrea
 // -1 and t +inf on a miss; normal_out ([n][3]) may be null; counters as launch_tri_hits
 void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const TriNode *top, uint32_t n_top, const float *rays, uint32_t n, float mint, float maxt, float *t_out,
                       int32_t *placement_out, int32_t *tri_out, float *normal_out, unsigned long long *counters, hipStream_t stream);
-// Resident workgroups per CU for the kernel variant (occupancy API), >= 1.
-uint32_t kernel_blocks_per_cu(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);
-// Threads per workgroup of the kernel variant launch_render would pick: RTW_BLOCK, or RTW_BLOCK_LARGE for the builds that walk the f32 plane
-// format (KArgs.nodes32).  The shim sizes the LDS stack, the grid and the queue's grabs by it.
-uint32_t kernel_block(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);
-// Let that kernel variant be launched with a.lds_bytes of dynamic LDS where they exceed the 64 KiB a workgroup gets by default (a large
-// workgroup's f32 planes and stack do: Book-1 73.5 KB).  Per kernel and device; the shim calls it once per (kernel, size).
-hipError_t kernel_allow_lds(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);
-// Is there a build of the BVH kernel for this configuration that reads the spheres' {centre, r^2} from LDS?  (KArgs.lds_geom_off may only be set then)
-bool kernel_has_lds_geom(const KArgs &a);
-// The kernel variant launch_render would pick, as an opaque id (key of the per-context occupancy cache).
-const void *kernel_id(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes);
 
 } // namespace rtw

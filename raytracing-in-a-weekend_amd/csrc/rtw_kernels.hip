@@ -1208,8 +1208,9 @@ constexpr bool two_halves_step(int spec, bool geom, bool moving) {
 // to a CU, so that one copy of the nodes serves 12 waves and the tree fits LDS in the f32 plane format (rtw_host.h), the only one these
 // builds walk.  That is 6 waves per SIMD, not 7: two workgroups of 14 waves never shared a CU when measured, and a seventh wave is worth
 // 2.4 % where the f32 planes are worth 7.6 % (profiles/f32_planes_ab.log).  As a run-time choice next to the f16 walk the format kept
-// a third less of its gain.  A tree that cannot live in LDS this way goes to the NODES == 2 build (rtw_shim.hip).  Nothing but the
-// __syncthreads() after the node copy couples the waves of a workgroup.  Every other build keeps RTW_BLOCK and the f16 format.
+// a third less of its gain.  A tree that cannot live in LDS this way goes to the NODES == 2 build (rtw_host.h render_lds_layout, which
+// is told whether a request's NODES == 1 build is one of these).  Nothing but the __syncthreads() after the node copy couples the waves
+// of a workgroup.  Every other build keeps RTW_BLOCK and the f16 format.  The host reads a build's size through render_block().
 constexpr uint32_t bvh_block(bool moving, int nodes, int spec, bool geom) {
     return !moving && !geom && nodes == 1 && two_halves_step(spec, geom, moving) ? RTW_BLOCK_LARGE : RTW_BLOCK;
 }
@@ -1218,7 +1219,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
     constexpr bool LDSN = NODES != 0, geom_in_lds = NODES == 2;
     constexpr uint32_t BLOCK = bvh_block(MOVING, NODES, SPEC, GEOM);
     constexpr bool F32 = BLOCK != RTW_BLOCK;         // the large-workgroup builds walk the f32 plane format, and that alone
-    // LDS is all dynamic, sized by the host for THIS tree (rtw_shim.hip, render_enqueue_impl): -- LDS-node variants -- the f16 nodes at
+    // LDS is all dynamic, sized by the host for THIS tree (rtw_host.h, render_lds_layout): -- LDS-node variants -- the f16 nodes at
     // offset 0, then the per-lane traversal stack [level][thread] (a level is one conflict-free row; depth + 3 levels: the sentinel,
     // one per tree level, and the slot above the top that the select-form descend always writes; 16-bit entries in the LDS-node
     // variants), then -- NODES == 2 -- {centre, r^2} of every sphere for the leaf tests.  Book-1: 15 KB + 7 KB (+ 7.8 KB) per 256 threads;
@@ -1557,84 +1558,32 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
 // ================================================================================================
 // host side
 // ================================================================================================
-typedef void (*kernel_fn)(const KArgs);
-static bool is_common_config(const KArgs &a) {
-    return a.integrator == RTW_INTEGRATOR_GRADIENT && a.sampler == RTW_SAMPLER_ROW && a.depth >= 1 &&
-           (a.flags & (RTW_FLAG_CPP_DIELECTRIC | RTW_FLAG_CPP_DIFFUSE)) == 0u;
+// One lookup from the five values of a RenderBuild to its kernel: exactly the compiled instantiations -- SPEC 0-7, 9, 10 without GEOM at
+// NODES 0 / 1 / 2, SPEC 0, 2, 4-12 with GEOM at NODES 0 / 1 (the GEOM builds keep the sphere geometry in global memory), the list walk of each.
+template <int SPEC, bool GEOM>
+static render_fn kernel_of(bool bvh, bool moving, int nodes) {
+    if (!bvh) return moving ? render_brute<true, SPEC, GEOM> : render_brute<false, SPEC, GEOM>;
+    if (nodes == 0) return moving ? render_bvh<true, 0, SPEC, GEOM> : render_bvh<false, 0, SPEC, GEOM>;
+    if (nodes == 1) return moving ? render_bvh<true, 1, SPEC, GEOM> : render_bvh<false, 1, SPEC, GEOM>;
+    if constexpr (!GEOM) if (nodes == 2) return moving ? render_bvh<true, 2, SPEC, false> : render_bvh<false, 2, SPEC, false>;
+    return nullptr;
 }
-static bool is_demo_config(const KArgs &a) {                   // presentation_image's: ray_color_bg_color through render_row
-    return a.integrator == RTW_INTEGRATOR_BG_COLOR && a.sampler == RTW_SAMPLER_ROW && a.depth >= 1 &&
-           (a.flags & (RTW_FLAG_CPP_DIELECTRIC | RTW_FLAG_CPP_DIFFUSE)) == 0u;
-}
-static bool is_serial_config(const KArgs &a) {                 // Viewport::render's: ray_color_gradient, stratified
-    return a.integrator == RTW_INTEGRATOR_GRADIENT && a.sampler == RTW_SAMPLER_STRATIFIED && a.depth >= 1 &&
-           (a.flags & (RTW_FLAG_CPP_DIELECTRIC | RTW_FLAG_CPP_DIFFUSE)) == 0u;
-}
-static bool is_rust2_config(const KArgs &a) {                  // Rust2's: ray_color through its fixed-centre render_row
-    return a.integrator == RTW_INTEGRATOR_RUST2 && a.sampler == RTW_SAMPLER_CENTRES && a.depth >= 1 &&
-           (a.flags & (RTW_FLAG_CPP_DIELECTRIC | RTW_FLAG_CPP_DIFFUSE)) == 0u;
-}
-// Every return site of pick_kernel_spec / pick_kernel_geom names its build twice: the function, and the tag rtw_ctx_last_render_build reports
-// (RenderBuild, rtw_kernels.h), from the same template parameter and the same runtime arguments.  `tag` may be null (occupancy query, kernel_id).
-static kernel_fn tagged(kernel_fn f, RenderBuild *tag, bool bvh, bool moving, int nodes, int spec, bool geom) {
-    if (tag) *tag = RenderBuild{ bvh, moving, geom, nodes, spec };
-    return f;
-}
-template <int SPEC>
-static kernel_fn pick_kernel_spec(bool moving, uint32_t accel, int nodes, RenderBuild *tag) {
-    if (accel == RTW_ACCEL_BVH) {
-        if (nodes == 2) return tagged(moving ? render_bvh<true, 2, SPEC, false> : render_bvh<false, 2, SPEC, false>, tag, true, moving, 2, SPEC, false);
-        if (nodes == 1) return tagged(moving ? render_bvh<true, 1, SPEC, false> : render_bvh<false, 1, SPEC, false>, tag, true, moving, 1, SPEC, false);
-        return tagged(moving ? render_bvh<true, 0, SPEC, false> : render_bvh<false, 0, SPEC, false>, tag, true, moving, 0, SPEC, false);
+render_fn render_kernel(const RenderBuild &b) {
+    if (!b.bvh && b.nodes != 0) return nullptr;
+    switch (b.spec * 2 + (b.geom ? 1 : 0)) {
+#define RTW_BUILD(SPEC, GEOM) case SPEC * 2 + GEOM: return kernel_of<SPEC, GEOM != 0>(b.bvh, b.moving, b.nodes);
+    RTW_BUILD(0, 0) RTW_BUILD(1, 0) RTW_BUILD(2, 0) RTW_BUILD(3, 0) RTW_BUILD(4, 0) RTW_BUILD(5, 0) RTW_BUILD(6, 0) RTW_BUILD(7, 0) RTW_BUILD(9, 0) RTW_BUILD(10, 0)
+    RTW_BUILD(0, 1) RTW_BUILD(2, 1) RTW_BUILD(4, 1) RTW_BUILD(5, 1) RTW_BUILD(6, 1) RTW_BUILD(7, 1) RTW_BUILD(8, 1) RTW_BUILD(9, 1) RTW_BUILD(10, 1) RTW_BUILD(11, 1) RTW_BUILD(12, 1)
+#undef RTW_BUILD
+    default: return nullptr;
     }
-    return tagged(moving ? render_brute<true, SPEC, false> : render_brute<false, SPEC, false>, tag, false, moving, 0, SPEC, false);
 }
-// quads / instances in the scene: the step of the generic build (SPEC == 0: everything from the kernel arguments; SPEC == 2: the common configuration folded
-// in at compile time, sphere textures kept; SPEC == 7: SPEC == 0 with texture noise) with the extra closest-hit stage (sphere geometry always global:
-// kernel_has_lds_geom)
-template <int SPEC>
-static kernel_fn pick_kernel_geom(bool moving, uint32_t accel, int nodes, RenderBuild *tag) {
-    if (accel == RTW_ACCEL_BVH) {
-        if (nodes) return tagged(moving ? render_bvh<true, 1, SPEC, true> : render_bvh<false, 1, SPEC, true>, tag, true, moving, 1, SPEC, true);
-        return tagged(moving ? render_bvh<true, 0, SPEC, true> : render_bvh<false, 0, SPEC, true>, tag, true, moving, 0, SPEC, true);
-    }
-    return tagged(moving ? render_brute<true, SPEC, true> : render_brute<false, SPEC, true>, tag, false, moving, 0, SPEC, true);
-}
-static kernel_fn pick_kernel(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes, RenderBuild *tag = nullptr) {
-    const int nodes = lds_nodes ? (a.lds_geom_off ? 2 : 1) : 0;
-    // instance rotations (rtw_shim.hip sets inst_quats only then, for a scene with instances under RUST2 / LIGHT_CAST / LIGHT_BIASED): the
-    // quaternion build, for every sampler and flag, with or without RTW_FLAG_MIXED_MATERIAL
-    if (a.inst_quats) return pick_kernel_geom<11>(moving, accel, nodes, tag);
-    // mesh placements (rtw_shim.hip sets mesh_rows only for a context that holds them, and serves RTW_INTEGRATOR_RUST2 alone): the placement build
-    if (a.mesh_rows) return pick_kernel_geom<12>(moving, accel, nodes, tag);
-    // RTW_FLAG_MIXED_MATERIAL on a scene with a MixedMaterial object (rtw_shim.hip clears the bit otherwise, and refuses the flag under any
-    // integrator but RUST2 / LIGHT_CAST / LIGHT_BIASED): the mixed build, for every sampler and flag
-    if (a.flags & RTW_FLAG_MIXED_MATERIAL)
-        return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<10>(moving, accel, nodes, tag) : pick_kernel_spec<10>(moving, accel, nodes, tag);
-    // Rust2's light-biased integrators: the light build, for every sampler and flag (rtw_shim.hip refuses them with noise or triangles)
-    if (a.integrator == RTW_INTEGRATOR_LIGHT_CAST || a.integrator == RTW_INTEGRATOR_LIGHT_BIASED)
-        return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<9>(moving, accel, nodes, tag) : pick_kernel_spec<9>(moving, accel, nodes, tag);
-    // a texture that a sphere, quad or member uses has noise (rtw_shim.hip sets noise.tex only then): the noise build, for every integrator, sampler and flag
-    if (a.noise.tex) return (a.geom.n_quads || a.geom.n_inst) ? pick_kernel_geom<7>(moving, accel, nodes, tag) : pick_kernel_spec<7>(moving, accel, nodes, tag);
-    // triangles (rtw_shim.hip sets tris.n only then; never together with noise): the triangle build, for every integrator, sampler and flag
-    if (a.tris.n) return pick_kernel_geom<8>(moving, accel, nodes, tag);
-    if (a.geom.n_quads || a.geom.n_inst) {
-#ifndef RTW_GEOM_GENERIC_ONLY
-        if (is_common_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<2>(moving, accel, nodes, tag);
-        if (is_demo_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<4>(moving, accel, nodes, tag);
-        if (is_rust2_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<5>(moving, accel, nodes, tag);
-        if (is_serial_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_geom<6>(moving, accel, nodes, tag);
-#endif
-        return pick_kernel_geom<0>(moving, accel, nodes, tag);
-    }
-#ifndef RTW_GEOM_GENERIC_ONLY
-    if (is_demo_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_spec<4>(moving, accel, nodes, tag);    // (the generic build's step, switches folded in)
-    if (is_rust2_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_spec<5>(moving, accel, nodes, tag);
-    if (is_serial_config(a) && !(a.flags & RTW_FLAG_CHUNK_SUMS)) return pick_kernel_spec<6>(moving, accel, nodes, tag);
-#endif
-    if (!is_common_config(a)) return pick_kernel_spec<0>(moving, accel, nodes, tag);
-    if (a.flags & RTW_FLAG_CHUNK_SUMS) return a.has_textures ? pick_kernel_spec<0>(moving, accel, nodes, tag) : pick_kernel_spec<3>(moving, accel, nodes, tag);
-    return a.has_textures ? pick_kernel_spec<2>(moving, accel, nodes, tag) : pick_kernel_spec<1>(moving, accel, nodes, tag);
+
+uint32_t render_block(const RenderBuild &b) { return b.bvh ? bvh_block(b.moving, b.nodes, b.spec, b.geom) : RTW_BLOCK; }
+
+void launch_render(render_fn fn, uint32_t block, const KArgs &a, uint32_t grid, hipStream_t stream) {
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(block), a.lds_bytes, stream, a);
+    hipLaunchKernelGGL(resolve_kernel, dim3((a.n_tiles * 64u + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, a);
 }
 
 // PerlinNoise::noise / turb at n points (rtw_ctx_perlin_eval): the function the noise build's texel lookups call
@@ -1703,40 +1652,6 @@ void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const T
                       int32_t *placement_out, int32_t *tri_out, float *normal_out, unsigned long long *counters, hipStream_t stream) {
     hipLaunchKernelGGL(mesh_hits_kernel, dim3((n + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, T, rows, n_mesh, top, n_top, rays, n, mint, maxt, t_out,
                        placement_out, tri_out, normal_out, counters);
-}
-
-bool kernel_has_lds_geom(const KArgs &a) { return !(a.geom.n_quads || a.geom.n_inst || a.tris.n); }
-
-static uint32_t build_block(const RenderBuild &b) { return b.bvh ? bvh_block(b.moving, b.nodes, b.spec, b.geom) : RTW_BLOCK; }
-
-void launch_render(const KArgs &a, bool moving, uint32_t accel, uint32_t grid, hipStream_t stream, RenderBuild *build) {
-    RenderBuild b;
-    const kernel_fn fn = pick_kernel(a, moving, accel, a.bvh.nodes16 != nullptr, &b);
-    if (build) *build = b;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(build_block(b)), a.lds_bytes, stream, a);
-    hipLaunchKernelGGL(resolve_kernel, dim3((a.n_tiles * 64u + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), 0, stream, a);
-}
-
-uint32_t kernel_blocks_per_cu(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
-    int n = 0;
-    RenderBuild b;
-    const kernel_fn fn = pick_kernel(a, moving, accel, lds_nodes, &b);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, build_block(b), a.lds_bytes) != hipSuccess || n < 1) n = 1;
-    return (uint32_t)(n > 8 ? 8 : n);
-}
-
-hipError_t kernel_allow_lds(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
-    return hipFuncSetAttribute((const void *)pick_kernel(a, moving, accel, lds_nodes), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_bytes);
-}
-
-uint32_t kernel_block(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
-    RenderBuild b;
-    pick_kernel(a, moving, accel, lds_nodes, &b);
-    return build_block(b);
-}
-
-const void *kernel_id(const KArgs &a, bool moving, uint32_t accel, bool lds_nodes) {
-    return (const void *)pick_kernel(a, moving, accel, lds_nodes);
 }
 
 } // namespace rtw

@@ -138,7 +138,7 @@ struct rtw_ctx {
     bool has_last_build = false;
     uint32_t last_node_format = 0;       // ... and the LDS node format it read (rtw_ctx_last_node_format)
     // cache of a per-call driver query (tens of microseconds: visible on small frames)
-    std::map<const void *, uint32_t> lds_allowed;        // kernel -> the largest dynamic LDS it has been allowed beyond 64 KiB (kernel_allow_lds)
+    std::map<const void *, uint32_t> lds_allowed;        // kernel -> the largest dynamic LDS it has been allowed beyond 64 KiB
     std::map<std::pair<const void *, uint32_t>, uint32_t> occupancy;    // (kernel, dynamic LDS bytes) -> resident workgroups per CU
     bool attr_on_device = false; int attr_device = -1;   // memory kind of this call's out_rgb
     // the render in flight between render_enqueue and render_wait
@@ -1158,6 +1158,18 @@ static int render_enqueue(rtw_ctx *c, const RtwCamera *cam, const RtwParams *p, 
     return rc;
 }
 
+// The build a render runs and its dynamic LDS, from plain facts: what the request needs, what the tree allows, the kernel of the two
+// (rtw_host.h, rtw_kernels.h), each asked once.  fn is null when no such build is compiled.  Shared with rtw_render_choice.
+struct RenderChoice { RenderBuild build; LdsLayout lds; render_fn fn; };
+static RenderChoice render_choice(const RtwRenderFacts &f, const RtwTreeFacts &t, int opt_lds_geom, uint32_t opt_node_format, bool moving, bool bvh) {
+    const RenderNeed need = render_need(f);
+    const bool large = render_block(RenderBuild{ true, moving, need.geom, 1, need.spec }) != RTW_BLOCK;      // its NODES == 1 build walks f32 planes
+    const LdsLayout lds = render_lds_layout(t, opt_lds_geom, opt_node_format, bvh, (f.flags & RTW_FLAG_GLOBAL_NODES) != 0u, need.geom, large, f.n_triangles != 0u);
+    const RenderBuild build{ bvh, moving, need.geom, lds.nodes, need.spec };
+    const render_fn fn = render_kernel(build);
+    return RenderChoice{ build, lds, fn && render_block(build) == lds.block ? fn : nullptr };
+}
+
 static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams *p, OutSpec out, unsigned phases) {
     if (!c || !cam || !p || !out.base) return RTW_E_INVALID;
     if (c->pend.active) return RTW_E_INVALID;
@@ -1221,7 +1233,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     a.cam = *cam; a.sc = c->sc; a.bvh = c->bvh; a.geom = c->geom;
     if (p->flags & RTW_FLAG_GLOBAL_NODES) a.bvh.nodes16 = nullptr;
     a.flags = p->flags;
-    if (!mixed_active) a.flags &= ~RTW_FLAG_MIXED_MATERIAL;       // (the bit selects the mixed build: pick_kernel; without a MixedMaterial object every build is as it was)
+    if (!mixed_active) a.flags &= ~RTW_FLAG_MIXED_MATERIAL;       // (the bit selects the mixed build: render_need; without a MixedMaterial object every build is as it was)
     a.width = p->width; a.height = p->height;
     const uint32_t n_rows = rtw_part_rows(p->height, p->row_block, p->part_index, p->part_count);
     a.row_block = p->row_block ? p->row_block : 1; a.part_index = p->part_index; a.part_count = p->part_count;
@@ -1235,7 +1247,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     a.mint = p->mint; a.maxt = p->maxt;
     std::memcpy(a.bg, c->bg, sizeof a.bg);
     a.queue = c->scr.queue.as<uint32_t>(); a.stats = c->scr.stats.as<unsigned long long>();
-    if (c->noise_active) a.noise = c->noise;                       // (selects the noise build: pick_kernel)
+    if (c->noise_active) a.noise = c->noise;                       // (selects the noise build: render_need)
     if (c->tris.n) a.tris = tri_view(c, p->accel, p->mint, p->maxt);   // (selects the triangle build; the tree for RTW_ACCEL_BVH requests)
     if (light_integrator) a.lights = c->lights;                    // (the integrator selects the light build, which alone reads them)
     a.inst_quats = c->inst_quats;                                  // (selects the quaternion build, whatever the integrator of the three it serves)
@@ -1304,65 +1316,38 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
         a.out = c->scr.out.as<float>();
     }
 
-    // dynamic LDS layout of the BVH kernel for this tree
-    uint32_t block = RTW_BLOCK, node_format = 0u;      // threads per workgroup of the render kernel this launch runs; its LDS node format
-    if (accel == RTW_ACCEL_BVH) {
-        const bool ldsn = a.bvh.nodes16 != nullptr;
-        // sentinel + one entry per tree level + the slot above the top the descend step always writes
-        uint32_t levels = c->bvh.depth + 3; if (levels < 4) levels = 4;
-        // Layout: f16 nodes FIRST (LDS offset 0: the hottest address of the kernel, the node fetch of every visit, then needs no base
-        // register -- as the second block its offset was an SGPR the allocator spilled, one v_readlane per visit), then the per-lane
-        // stack, then the optional sphere geometry.
-        uint32_t off = 0;
-        if (ldsn) { off = c->bvh.n_nodes * 32u; off = (off + 15u) & ~15u; }
-        a.lds_stack_off = off;
-        off += levels * RTW_BLOCK * (ldsn ? 2u : 4u);
-        off = (off + 15u) & ~15u;
-        if (ldsn) {
-            // sphere geometry rides along only while the workgroup stays under its share (1/6 with 256 threads) of the CU's 160 KiB, i.e. while
-            // it does not cost a resident workgroup at the kernel's register budget (6 waves/SIMD)
-            bool geom = off + c->sc.n * 16u <= 160u * 1024u / (1536u / RTW_BLOCK);
-            if (c->opt_lds_geom >= 0) geom = c->opt_lds_geom != 0 && c->sc.n <= RTW_LDS_GEOM_MAX;
-            if (c->opt_node_format == 2u) geom = false;           // (f32 planes asked for: the builds that walk them keep the geometry in global memory)
-            if (geom && kernel_has_lds_geom(a)) { a.lds_geom_off = off; off += c->sc.n * 16u; }
-        }
-        a.lds_bytes = off;
-        block = kernel_block(a, c->sc.moving != 0, accel, ldsn);
-        node_format = ldsn ? 1u : 0u;
-        if (block != RTW_BLOCK) {
-            // A large-workgroup build (rtw_kernels.hip bvh_block): it walks the tree as f32 planes, its stack's rows are `block` entries, and it is
-            // meant to run two workgroups per CU (24 waves, 6 per SIMD).  Both fit the CU's 160 KiB for every tree build_bvh gives f16 nodes within its depth
-            // cap: 3.5 x the node bytes + 3 x the stack bytes of a layout that fits a seventh.  A tree that does not fit, or
-            // RTW_OPT_NODE_FORMAT = 1, takes the f16 walk at RTW_BLOCK threads in the build that holds the spheres' geometry in LDS too
-            // (NODES == 2: kernel_has_lds_geom(a) holds for every scene a large-workgroup build serves, and a tree with f16 nodes has at most
-            // RTW_LDS_GEOM_MAX spheres) -- whatever RTW_OPT_LDS_GEOM says.
-            const uint32_t stack = (levels * block * 2u + 15u) & ~15u;
-            const uint32_t bytes32 = c->bvh.n_nodes * RTW_NODE32_DWORDS * 4u;       // (a multiple of 16)
-            const bool one = c->nodes32 != nullptr && bytes32 + stack <= 160u * 1024u, two = c->nodes32 != nullptr && 2u * (bytes32 + stack) <= 160u * 1024u;
-            if (c->opt_node_format == 2u ? one : (c->opt_node_format == 0u && two)) {
-                a.nodes32 = c->nodes32;
-                a.lds_stack_off = bytes32; a.lds_bytes = bytes32 + stack;
-                node_format = 2u;
-            } else {
-                a.lds_geom_off = off; a.lds_bytes = off + c->sc.n * 16u;
-                block = kernel_block(a, c->sc.moving != 0, accel, ldsn);
-            }
-        }
-    }
-    if (a.tris.n) { a.tris.lds_off = (a.lds_bytes + 15u) & ~15u; a.lds_bytes = a.tris.lds_off + 16u; }   // the triangle build's node-visit counter
+    // The build this render runs and its dynamic LDS, chosen once: everything below -- the LDS allowance, the occupancy, the grid, the grabs,
+    // the launch -- uses `build`, `fn` and `block`.
+    RtwRenderFacts facts{};
+    facts.integrator = a.integrator; facts.sampler = a.sampler; facts.depth = a.depth; facts.flags = a.flags; facts.has_textures = a.has_textures;
+    facts.n_quads = a.geom.n_quads; facts.n_instances = a.geom.n_inst; facts.noise = a.noise.tex != nullptr; facts.n_triangles = a.tris.n;
+    facts.rotations = a.inst_quats != nullptr; facts.placements = a.mesh_rows != nullptr;
+    const RenderChoice choice = render_choice(facts, RtwTreeFacts{ c->bvh.n_nodes, c->bvh.depth, c->sc.n, c->bvh.nodes16 != nullptr, c->nodes32 != nullptr },
+                                              c->opt_lds_geom, c->opt_node_format, c->sc.moving != 0, accel == RTW_ACCEL_BVH);
+    if (!choice.fn) return RTW_E_UNSUPPORTED;          // (no such build: an error, never another kernel)
+    const RenderBuild &build = choice.build;
+    const LdsLayout &lds = choice.lds;
+    const render_fn fn = choice.fn;
+    const uint32_t block = lds.block;                  // threads per workgroup of the render kernel this launch runs
+    a.lds_stack_off = lds.stack_off; a.lds_geom_off = lds.geom_off; a.lds_bytes = lds.bytes;
+    if (a.tris.n) a.tris.lds_off = lds.tri_off;
+    if (lds.node_format == 2u) a.nodes32 = c->nodes32;
 
-    if (accel == RTW_ACCEL_BVH && a.lds_bytes > 64u * 1024u) {
-        const bool ldsn = a.bvh.nodes16 != nullptr;
-        uint32_t &allowed = c->lds_allowed[kernel_id(a, c->sc.moving != 0, accel, ldsn)];
-        if (allowed < a.lds_bytes) { HIP_TRY(kernel_allow_lds(a, c->sc.moving != 0, accel, ldsn)); allowed = a.lds_bytes; }
+    if (build.bvh && a.lds_bytes > 64u * 1024u) {
+        // more than the 64 KiB a workgroup gets by default (a large workgroup's f32 planes and stack: Book-1 73.5 KB): allowed per kernel and device, once per size
+        uint32_t &allowed = c->lds_allowed[(const void *)fn];
+        if (allowed < a.lds_bytes) { HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_bytes)); allowed = a.lds_bytes; }
     }
     // persistent grid: as many workgroups as the kernel's registers let be resident, capped by the work
     uint32_t per_cu = c->opt_blocks_per_cu;
     if (per_cu == 0) {
-        const bool ldsn = c->bvh.nodes16 != nullptr && !(p->flags & RTW_FLAG_GLOBAL_NODES);
-        const auto key = std::make_pair(kernel_id(a, c->sc.moving != 0, accel, ldsn), a.lds_bytes);
+        const auto key = std::make_pair((const void *)fn, a.lds_bytes);
         auto it = c->occupancy.find(key);
-        if (it == c->occupancy.end()) it = c->occupancy.emplace(key, kernel_blocks_per_cu(a, c->sc.moving != 0, accel, ldsn)).first;
+        if (it == c->occupancy.end()) {
+            int n = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)fn, (int)block, a.lds_bytes) != hipSuccess || n < 1) n = 1;
+            it = c->occupancy.emplace(key, (uint32_t)(n > 8 ? 8 : n)).first;
+        }
         per_cu = it->second;
     }
 
@@ -1457,7 +1442,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
             a.grab_max = (blocks ? blocks : 1u) * 64u;
         }
         HIP_TRY(hipMemsetAsync(a.queue, 0, RTW_QUEUE_BYTES, c->stream));
-        if (a.n_tiles) { launch_render(a, c->sc.moving != 0, accel, grid, c->stream, &c->last_build); c->has_last_build = true; c->last_node_format = node_format; }
+        if (a.n_tiles) { launch_render(fn, block, a, grid, c->stream); c->last_build = build; c->has_last_build = true; c->last_node_format = lds.node_format; }
         HIP_TRY(hipGetLastError());
         if (tile_rows == 0) break;
     }
@@ -1560,13 +1545,28 @@ struct rtw_mgpu {
 
 extern "C" {
 
-// Host only: the tag launch_render left in the context, printed in template order.
-int rtw_ctx_last_render_build(rtw_ctx *c, char *buf, size_t n) {
-    if (!c || !buf || n == 0 || !c->has_last_build) return RTW_E_INVALID;
-    const RenderBuild &b = c->last_build;
+// A build printed in template order.
+static int print_build(const RenderBuild &b, char *buf, size_t n) {
     const int len = b.bvh ? std::snprintf(buf, n, "render_bvh<%d,%d,%d,%d>", (int)b.moving, b.nodes, b.spec, (int)b.geom)
                           : std::snprintf(buf, n, "render_brute<%d,%d,%d>", (int)b.moving, b.spec, (int)b.geom);
     return len > 0 && (size_t)len < n ? RTW_OK : RTW_E_INVALID;
+}
+
+// Host only: the build the last launch ran.
+int rtw_ctx_last_render_build(rtw_ctx *c, char *buf, size_t n) {
+    if (!c || !buf || n == 0 || !c->has_last_build) return RTW_E_INVALID;
+    return print_build(c->last_build, buf, n);
+}
+
+// Host only: render_enqueue_impl's three steps on the caller's facts.
+int rtw_render_choice(const RtwRenderFacts *f, const RtwTreeFacts *t, int32_t opt_lds_geom, uint32_t opt_node_format, uint32_t moving, uint32_t accel,
+                      RtwRenderChoice *out) {
+    if (!f || !t || !out || accel > RTW_ACCEL_BVH || opt_lds_geom < -1 || opt_lds_geom > 1 || opt_node_format > 2u) return RTW_E_INVALID;
+    const RenderChoice choice = render_choice(*f, *t, opt_lds_geom, opt_node_format, moving != 0u, accel == RTW_ACCEL_BVH);
+    if (!choice.fn) return RTW_E_UNSUPPORTED;
+    const LdsLayout &lds = choice.lds;
+    *out = RtwRenderChoice{ {}, lds.node_format, lds.block, lds.stack_off, lds.geom_off, lds.tri_off, lds.bytes };
+    return print_build(choice.build, out->build, sizeof out->build);
 }
 
 // Host only: the LDS node format the last launch's kernel read.

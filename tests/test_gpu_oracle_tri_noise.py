@@ -4,12 +4,12 @@ emissive triangles, a triangle that ties a quad, noise seen after a bounce, on m
 scene can reach.  Textured spheres are compared under RTW_ORACLE_FLAG_DEVICE_UV (the device's atan2 / acos sequences), which makes the texel
 choice the device's: nothing is left to a tolerance.
 
-Which build runs is argued from pick_kernel (rtw_kernels.hip), as in test_every_build_of_the_traversal_kernel: triangles select
-pick_kernel_geom<8> for every integrator, sampler and flag, and noise in use selects <7> (pick_kernel_geom<7> when the scene has quads or
-instances, pick_kernel_spec<7> otherwise); a scene with a moving sphere runs the MOVING half.  Within a build: RTW_ACCEL_BRUTE is the list walk;
+Which build runs is argued from render_need (rtw_host.cpp), as in test_every_build_of_the_traversal_kernel: triangles select
+SPEC 8 with GEOM for every integrator, sampler and flag, and noise in use selects SPEC 7 (with GEOM when the scene has quads or
+instances, without otherwise); a scene with a moving sphere runs the MOVING half.  Within a build: RTW_ACCEL_BRUTE is the list walk;
 RTW_ACCEL_BVH with RTW_OPT_LIST_WALK_MAX = 0 (so that the sphere count does not send the request to the list walk) is render_bvh, whose node
 argument is 0 under RTW_FLAG_GLOBAL_NODES (f32 nodes in global memory), else 1 (f16 nodes in LDS), or 2 (LDS nodes plus the sphere geometry in
-LDS: RTW_OPT_LDS_GEOM = 1, the spheres-only builds; the GEOM builds have no such variant, kernel_has_lds_geom)."""
+LDS: RTW_OPT_LDS_GEOM = 1, the spheres-only builds; the GEOM builds have no such variant)."""
 import numpy as np
 import pytest
 

@@ -52,7 +52,8 @@ def test_every_tree_with_f16_nodes_fits_two_large_workgroups(n_leaves):
     """The shim runs the f32 planes only where two 768-thread workgroups fit a CU's 160 KiB: nodes * 112 + (depth + 3 levels, at least 4)
     * 768 * 2 bytes, twice.  The builder caps the depth of a tree with f16 nodes so that nodes * 32 + levels * 512 fits a seventh of the
     160 KiB, and 3.5 x the one plus 3 x the other stays within half of it -- restated here for the deepest tree the builder may return at
-    every size, from its own cap (bvh_depth_cap, through a scene of that many tree spheres)."""
+    every size, from its own cap (bvh_depth_cap, through a scene of that many tree spheres).  And the rule itself (rtw_render_choice) answers
+    f32 planes for each of them under the default options."""
     rng = np.random.default_rng(n_leaves)
     sp = [R.Sphere.with_albedo((0.0, -1000.0, 0.0), 1000.0, (0.5, 0.5, 0.5), R.SCATTER_M)]
     sp += [R.Sphere.with_albedo((float(rng.uniform(-8, 8)), 0.2, float(rng.uniform(-8, 8))), 0.2, (0.5, 0.5, 0.5), R.SCATTER_M) for _ in range(n_leaves)]
@@ -61,6 +62,17 @@ def test_every_tree_with_f16_nodes_fits_two_large_workgroups(n_leaves):
     for depth in (d["depth"], d["cap"]):
         levels = max(depth + 3, 4)
         assert 2 * ((n_leaves - 1) * 28 * 4 + ((levels * 768 * 2 + 15) & ~15)) <= 160 * 1024, (n_leaves, depth)
+        # RTW_OPT_NODE_FORMAT at its default throughout.  RTW_OPT_LDS_GEOM at its default (-1) sends a scene whose f16 nodes, 256-thread stack
+        # and sphere geometry fit a sixth of the CU to the build that keeps all three in LDS (NODES == 2, f16), before the planes are asked
+        # about; every other tree, and every tree with RTW_OPT_LDS_GEOM = 0, walks f32 planes.
+        for lds_geom in (-1, 0):
+            choice = R.render_choice(R.RtwRenderFacts(integrator=R.INTEGRATOR_GRADIENT, sampler=R.SAMPLER_ROW, depth=50),
+                                     R.RtwTreeFacts(n_nodes=n_leaves - 1, depth=depth, n_spheres=len(sp), has_f16=1, has_planes=1), lds_geom=lds_geom)
+            rides = lds_geom < 0 and (((n_leaves - 1) * 32 + 15) & ~15) + levels * 512 + len(sp) * 16 <= 160 * 1024 // 6
+            want = ("render_bvh<0,2,1,0>", R.NODE_FORMAT_F16, 256) if rides else ("render_bvh<0,1,1,0>", R.NODE_FORMAT_F32, 768)
+            assert (choice["build"], choice["node_format"], choice["block"]) == want, (n_leaves, depth, lds_geom, choice)
+            if not rides:
+                assert choice["lds_bytes"] == (n_leaves - 1) * 28 * 4 + ((levels * 768 * 2 + 15) & ~15)
 
 
 @pytest.mark.parametrize("name", list(SCENES))
