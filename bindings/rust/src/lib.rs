@@ -102,7 +102,39 @@ pub const RTW_OPT_MESH_LIST_MAX: u32 = 12;
 #[derive(Clone, Copy, Debug, Default)]
 pub struct RtwTriNode { pub lo: [f32; 3], pub skip: u32, pub hi: [f32; 3], pub leaf: u32 }
 
+/// One wrong result of a device sweep (rtw.h `RtwSweepResult.records`): bit patterns of the arguments (b = 0 for sqrt) and of what came back.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct RtwSweepRecord { pub a: u32, pub b: u32, pub got: u32, pub reserved: u32 }
+/// What `rtw_ctx_device_sweep` reports (rtw.h "device math, for tests").
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct RtwSweepResult {
+    pub tested: u64, pub wrong: u64, pub n_records: u32, pub reserved: u32, pub records: [RtwSweepRecord; 16], pub kernel_ms: f32, pub reserved2: u32,
+}
+/// `rtw_ctx_device_math`'s functions: (fn, columns read, columns written)
+pub const RTW_MATH_SQRT_PLAIN: (u32, u32, u32) = (0, 1, 1);
+pub const RTW_MATH_SQRT_IEEE: (u32, u32, u32) = (1, 1, 1);
+pub const RTW_MATH_DIV: (u32, u32, u32) = (2, 2, 1);
+pub const RTW_MATH_UNIT: (u32, u32, u32) = (3, 3, 3);
+pub const RTW_MATH_UNIT_BALL: (u32, u32, u32) = (4, 4, 3);
+pub const RTW_MATH_SPHERE_ROOT: (u32, u32, u32) = (5, 4, 1);
+pub const RTW_MATH_ATAN2: (u32, u32, u32) = (6, 2, 1);
+pub const RTW_MATH_ACOS: (u32, u32, u32) = (7, 1, 1);
+pub const RTW_MATH_SPHERE_UV: (u32, u32, u32) = (8, 3, 2);
+pub const RTW_MATH_LN: (u32, u32, u32) = (9, 1, 1);
+pub const RTW_MATH_POW: (u32, u32, u32) = (10, 2, 1);
+pub const RTW_MATH_SINCOS: (u32, u32, u32) = (11, 1, 2);
+pub const RTW_MATH_EXP: (u32, u32, u32) = (12, 1, 1);
+pub const RTW_SWEEP_SQRT: u32 = 0;
+pub const RTW_SWEEP_DIV_RANDOM: u32 = 1;
+pub const RTW_SWEEP_DIV_MIDPOINT: u32 = 2;
+
 extern "C" {
+    fn rtw_ctx_device_math(ctx: *mut RtwCtx, func: u32, input: *const f32, n_cols: u32, n: u32, out: *mut f32, out_cols: u32) -> i32;
+    fn rtw_ctx_device_sweep(ctx: *mut RtwCtx, which: u32, first: u64, count: u64, seed: u32, result: *mut RtwSweepResult) -> i32;
+    fn rtw_rounding_check(which: u32, a: *const u32, b: *const u32, got: *const u32, n: usize, ok: *mut u8) -> i32;
+    fn rtw_sweep_operands(which: u32, first: u64, n: usize, seed: u32, out: *mut u32) -> i32;
     fn rtw_ctx_create(device: i32, out: *mut *mut RtwCtx) -> i32;
     fn rtw_ctx_destroy(ctx: *mut RtwCtx);
     fn rtw_ctx_set_scene(ctx: *mut RtwCtx, scene: *const RtwScene, t_begin: f32, t_end: f32) -> i32;
@@ -299,6 +331,20 @@ impl Renderer {
         let mut out = vec![0f32; points.len()];
         check(unsafe { rtw_ctx_perlin_eval(self.ctx, t, points.as_ptr() as *const f32, points.len() as u32, turb_depth, out.as_mut_ptr()) })?;
         Ok(out)
+    }
+    /// For tests: one of the hot path's arithmetic sequences (`RTW_MATH_*`) on this context's GPU, element i by thread i; `input` is
+    /// [n][columns read], the result [n][columns written].
+    pub fn device_math(&mut self, func: (u32, u32, u32), input: &[f32]) -> Result<Vec<f32>, RtwError> {
+        let n = input.len() / func.1 as usize;
+        let mut out = vec![0f32; n * func.2 as usize];
+        check(unsafe { rtw_ctx_device_math(self.ctx, func.0, input.as_ptr(), func.1, n as u32, out.as_mut_ptr(), func.2) })?;
+        Ok(out)
+    }
+    /// For tests: sqrt_plain / div_plain over `count` generated arguments from index `first`, each judged exactly on the GPU (`RTW_SWEEP_*`).
+    pub fn device_sweep(&mut self, which: u32, first: u64, count: u64, seed: u32) -> Result<RtwSweepResult, RtwError> {
+        let mut r = RtwSweepResult::default();
+        check(unsafe { rtw_ctx_device_sweep(self.ctx, which, first, count, seed, &mut r) })?;
+        Ok(r)
     }
     /// Rust2 `bilateral_filter` on this context's GPU: `rgb` is [h][w][3] u8 (`ImageBuffer<Rgb<u8>>::as_raw()`) or, with
     /// in_format 1, the f32 frame of `render` flattened; bit-identical to the reference.
@@ -526,3 +572,17 @@ pub fn bilateral_filter_gpu(rgb: &[u8], w: u32, h: u32, proximity: Proximity) ->
 //     let raw = rtw::bilateral_filter_gpu(img.as_raw(), w, h, proximity)?;
 //     Ok(ImageBuffer::from_raw(w, h, raw).unwrap())
 // }
+
+/// Host only, for tests: is got[i] the correctly rounded f32 sqrt(a[i]) (`RTW_SWEEP_SQRT`, `b` unused) or a[i] / b[i]?  Bit patterns.
+pub fn rounding_check(which: u32, a: &[u32], b: &[u32], got: &[u32]) -> Result<Vec<bool>, RtwError> {
+    let mut ok = vec![0u8; a.len()];
+    let bp = if b.is_empty() { std::ptr::null() } else { b.as_ptr() };
+    check(unsafe { rtw_rounding_check(which, a.as_ptr(), bp, got.as_ptr(), a.len(), ok.as_mut_ptr()) })?;
+    Ok(ok.into_iter().map(|v| v != 0).collect())
+}
+/// Host only, for tests: the (n, d) bit patterns a quotient sweep forms for indices first .. first + n - 1.
+pub fn sweep_operands(which: u32, first: u64, n: usize, seed: u32) -> Result<Vec<[u32; 2]>, RtwError> {
+    let mut out = vec![[0u32; 2]; n];
+    check(unsafe { rtw_sweep_operands(which, first, n, seed, out.as_mut_ptr() as *mut u32) })?;
+    Ok(out)
+}

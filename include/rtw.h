@@ -648,6 +648,74 @@ int rtw_exp_plain(const float *x, size_t n, float *out);
 int rtw_sin_plain(const float *phi, size_t n, float *out);
 int rtw_cos_plain(const float *phi, size_t n, float *out);
 
+/* ---- device math, for tests (csrc/rtw_probe.hip) -------------------------------------------------------------------------------------
+ * The arithmetic sequences of the hot path (csrc/rtw_device.h, rtw_mixed.h, rtw_exp.h) evaluated directly on the GPU, the same definitions
+ * the render, query and filter kernels compile.  Nothing here is needed to render.
+ * rtw_ctx_device_math: out[i][0 .. out_cols) = fn(in[i][0 .. n_cols)) for i < n; element i is evaluated by thread i of a 1-D grid of
+ * 256-thread blocks, so elements 64 w .. 64 w + 63 share a wave and a caller decides which path a wave-uniform range check takes.  in / out
+ * are host memory (staged); n_cols / out_cols must be the function's (below), n >= 1.  On the context's stream, synchronised before it
+ * returns; RTW_E_INVALID for a null pointer, n == 0, an unknown fn, wrong column counts, or while a render is pending.
+ *   fn                        in                      out
+ *   RTW_MATH_SQRT_PLAIN       x                       sqrt_plain(x)                       (meant for x in [2^-96, 2^127))
+ *   RTW_MATH_SQRT_IEEE        x                       sqrt_ieee(x)
+ *   RTW_MATH_DIV              n, d                    div_plain(n, d, rcp_refined(d))     (|d| in [2^-40, 2^40], |n| in [2^-60, 2^40] or 0)
+ *   RTW_MATH_UNIT             x, y, z                 unit(a)  [3]
+ *   RTW_MATH_UNIT_BALL        x, y, z, l2             unit_of_ball_point(p, l2)  [3]
+ *   RTW_MATH_SPHERE_ROOT      b, disc, a, mint        sphere_root(b, disc, a, rcp_refined(a), a_plain, mint) with a_plain formed per wave as the
+ *                                                     render kernels form it; NaN where disc < 0 (the kernels do not call it there)
+ *   RTW_MATH_ATAN2            y, x                    atan2_plain(y, x)
+ *   RTW_MATH_ACOS             x                       acos_plain(x)
+ *   RTW_MATH_SPHERE_UV        x, y, z (a normal)      u, v  [2]
+ *   RTW_MATH_LN               x                       ln_f32(x)
+ *   RTW_MATH_POW              x, y                    pow_plain(x, y)
+ *   RTW_MATH_SINCOS           phi                     sin, cos  [2]
+ *   RTW_MATH_EXP              x                       exp_plain(x)
+ * An argument outside a function's range gives a wrong number, never a fault. */
+#define RTW_MATH_SQRT_PLAIN   0u
+#define RTW_MATH_SQRT_IEEE    1u
+#define RTW_MATH_DIV          2u
+#define RTW_MATH_UNIT         3u
+#define RTW_MATH_UNIT_BALL    4u
+#define RTW_MATH_SPHERE_ROOT  5u
+#define RTW_MATH_ATAN2        6u
+#define RTW_MATH_ACOS         7u
+#define RTW_MATH_SPHERE_UV    8u
+#define RTW_MATH_LN           9u
+#define RTW_MATH_POW         10u
+#define RTW_MATH_SINCOS      11u
+#define RTW_MATH_EXP         12u
+#define RTW_MATH_COUNT       13u
+int rtw_ctx_device_math(rtw_ctx *ctx, uint32_t fn, const float *in, uint32_t n_cols, uint32_t n, float *out, uint32_t out_cols);
+/* rtw_ctx_device_sweep: argument sets too large to copy back.  Thread by thread the kernel forms the arguments of global index
+ * first .. first + count - 1, evaluates the sequence and decides EXACTLY, in 64-bit integers, whether the result is the correctly rounded one.
+ *   RTW_SWEEP_SQRT          sqrt_plain of the f32 whose bit pattern is the index (first + count <= 2^32; meant for 0x0F800000 .. 0x7F000000)
+ *   RTW_SWEEP_DIV_RANDOM    div_plain_nz(n, d, rcp_refined(d)), which must also be div_plain's bits, of the pair a counter hash (lowbias32) of (seed, index) picks: independent signs,
+ *                           24-bit mantissas, exponents uniform over |d| in [2^-40, 2^40) and |n| in [2^-60, 2^40)
+ *   RTW_SWEEP_DIV_MIDPOINT  the same with mantissas whose exact quotient lies 1 / (2 md) < 2^-24 of an ulp from a rounding boundary, the
+ *                           closest f32 operands allow: md an odd draw, c the odd 25-bit integer with c md = +-1 (mod 2^k), mn = (c md -+ 1) / 2^k
+ *                           (the integer nearest to c md / 2^k), k = 24 or 25 so that mn has 24 bits
+ * result: how many were tested, how many were wrong, and the first RTW_SWEEP_RECORDS wrong ones in the order the GPU met them -- the
+ * arguments and the bits returned -- so that a failure can be read from the result alone.  count >= 1 and at most 2^32. */
+#define RTW_SWEEP_SQRT          0u
+#define RTW_SWEEP_DIV_RANDOM    1u
+#define RTW_SWEEP_DIV_MIDPOINT  2u
+#define RTW_SWEEP_COUNT         3u
+#define RTW_SWEEP_RECORDS      16u
+typedef struct RtwSweepResult {
+    uint64_t tested, wrong;
+    uint32_t n_records, reserved;                 /* min(wrong, RTW_SWEEP_RECORDS) */
+    struct { uint32_t a, b, got, reserved; } records[RTW_SWEEP_RECORDS];   /* bit patterns: a = x or n, b = d (0 for sqrt), got = the result */
+    float    kernel_ms;                           /* the sweep kernel alone, by HIP events */
+    uint32_t reserved2;
+} RtwSweepResult;
+int rtw_ctx_device_sweep(rtw_ctx *ctx, uint32_t which, uint64_t first, uint64_t count, uint32_t seed, RtwSweepResult *result);
+/* Host only: the sweeps' reference, so that it can itself be tested.  ok[i] = 1 when got[i] is the correctly rounded f32 result, else 0 (bit
+ * patterns throughout).  RTW_SWEEP_SQRT: sqrt of a[i], b unused (may be null); a positive normal f32.  Otherwise got[i] against a[i] / b[i]:
+ * a normal or a zero, b normal, and a right quotient that is normal or zero -- anything else is answered 0. */
+int rtw_rounding_check(uint32_t which, const uint32_t *a, const uint32_t *b, const uint32_t *got, size_t n, uint8_t *ok);
+/* Host only: the pairs a quotient sweep forms for indices first .. first + n - 1: out[i] = { n bits, d bits }. */
+int rtw_sweep_operands(uint32_t which, uint64_t first, size_t n, uint32_t seed, uint32_t *out /* [n][2] */);
+
 /* ---- quaternion-rotated instances (Rust2/src/objects/instance.rs:21-47, 215-255, quaternions.rs, rotation.rs) -------------------------
  * A Rust2 `Instance` carries a position and a QUATERNION rotation, where RtwInstance.rotation is Rust/'s Euler Vec3::rotated (another formula,
  * other bits).  With rotations set, an instance is hit as Rust2's Instance::get_hit writes it: r.origin -= position; r = r.rotated(q) (origin

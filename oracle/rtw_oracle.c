@@ -194,7 +194,10 @@ typedef struct {
 } world_t;
 
 /* TEST ONLY: the device's lean atan2 / acos for the spherical UV (csrc/rtw_device.h atan2_plain / acos_plain), restated operation for operation --
- * `/` and sqrtf are correctly rounded here, as div_plain / sqrt_plain are on the device for the arguments they are used with -- so that their
+ * `/` and sqrtf are correctly rounded here, as sqrt_plain is on the device for every argument acos_plain hands it and the device's quotient
+ * (div_plain, its numerator rescaled where it is below 2^-60) for every quotient min / max that is zero or a normal number; a subnormal quotient
+ * is rounded twice on the device and can differ from this copy's in its last place, 2^-149, and (u, v) are still the same bits
+ * (measured on the device: tests/test_gpu_device_math.py) -- so that their
  * accuracy and their effect on the texel choice can be measured on the CPU (tests/test_round3_cpu.py), and so that renders under
  * RTW_ORACLE_FLAG_DEVICE_UV pick the device's texels.  The oracle's own renders use libm (sphere_uv below), like the reference (Rust's
  * f32::atan2 / f32::acos). */

@@ -190,6 +190,29 @@ class RtwRenderChoice(C.Structure):
     _fields_ = [("build", C.c_char * 32)] + [(k, C.c_uint32) for k in ("node_format", "block", "lds_stack_off", "lds_geom_off", "lds_tri_off", "lds_bytes")]
 
 
+# rtw_ctx_device_math's functions and rtw_ctx_device_sweep's sweeps (include/rtw.h "device math, for tests")
+(MATH_SQRT_PLAIN, MATH_SQRT_IEEE, MATH_DIV, MATH_UNIT, MATH_UNIT_BALL, MATH_SPHERE_ROOT, MATH_ATAN2, MATH_ACOS, MATH_SPHERE_UV, MATH_LN, MATH_POW,
+ MATH_SINCOS, MATH_EXP) = range(13)
+MATH_COLS = {MATH_SQRT_PLAIN: (1, 1), MATH_SQRT_IEEE: (1, 1), MATH_DIV: (2, 1), MATH_UNIT: (3, 3), MATH_UNIT_BALL: (4, 3), MATH_SPHERE_ROOT: (4, 1),
+             MATH_ATAN2: (2, 1), MATH_ACOS: (1, 1), MATH_SPHERE_UV: (3, 2), MATH_LN: (1, 1), MATH_POW: (2, 1), MATH_SINCOS: (1, 2), MATH_EXP: (1, 1)}
+SWEEP_SQRT, SWEEP_DIV_RANDOM, SWEEP_DIV_MIDPOINT = 0, 1, 2
+SWEEP_RECORDS = 16
+
+
+class RtwSweepRecord(C.Structure):
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("got", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RtwSweepResult(C.Structure):
+    """What rtw_ctx_device_sweep reports: counts, the first wrong results (bit patterns) and the kernel's time."""
+    _fields_ = [("tested", C.c_uint64), ("wrong", C.c_uint64), ("n_records", C.c_uint32), ("reserved", C.c_uint32),
+                ("records", RtwSweepRecord * SWEEP_RECORDS), ("kernel_ms", C.c_float), ("reserved2", C.c_uint32)]
+
+    def failures(self):
+        """[(a, b, got)] as hex strings, for a test's message."""
+        return [(f"{r.a:#010x}", f"{r.b:#010x}", f"{r.got:#010x}") for r in self.records[:self.n_records]]
+
+
 _lib = None
 
 
@@ -326,6 +349,10 @@ def lib() -> C.CDLL:
     L.rtw_sin_plain.argtypes = [fp, C.c_size_t, fp]
     L.rtw_exp_plain.argtypes = [fp, C.c_size_t, fp]
     L.rtw_cos_plain.argtypes = [fp, C.c_size_t, fp]
+    L.rtw_ctx_device_math.argtypes = [C.c_void_p, C.c_uint32, fp, C.c_uint32, C.c_uint32, fp, C.c_uint32]
+    L.rtw_ctx_device_sweep.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(RtwSweepResult)]
+    L.rtw_rounding_check.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.rtw_sweep_operands.argtypes = [C.c_uint32, C.c_uint64, C.c_size_t, C.c_uint32, C.c_void_p]
     _lib = L
     return L
 
@@ -594,6 +621,30 @@ def sin_plain(phi) -> np.ndarray:
 def cos_plain(phi) -> np.ndarray:
     """rtw_cos_plain over an array: the library's f32 cos for phi in [0, 2 pi]."""
     return _plain1(lib().rtw_cos_plain, "rtw_cos_plain", phi)
+
+
+def _bits(a) -> np.ndarray:
+    """f32 values or uint32 bit patterns as a contiguous uint32 array of bit patterns."""
+    a = np.asarray(a)
+    return np.ascontiguousarray(a.view(np.uint32) if a.dtype == np.float32 else a.astype(np.uint32))
+
+
+def rounding_check(which: int, a, b, got) -> np.ndarray:
+    """rtw_rounding_check (host only): is got[i] the correctly rounded f32 sqrt(a[i]) (SWEEP_SQRT, b ignored) or a[i] / b[i]?  float32 arrays
+    or uint32 bit patterns; returns a bool array."""
+    a, got = _bits(a), _bits(got)
+    b = None if b is None else _bits(b)
+    ok = np.empty(a.size, np.uint8)
+    _check(lib().rtw_rounding_check(int(which), a.ctypes.data, None if b is None else b.ctypes.data, got.ctypes.data, a.size, ok.ctypes.data),
+           "rtw_rounding_check")
+    return ok.astype(bool).reshape(a.shape)
+
+
+def sweep_operands(which: int, first: int, n: int, seed: int):
+    """rtw_sweep_operands (host only): the (n, d) pairs a quotient sweep forms for indices first .. first + n - 1, as float32 arrays."""
+    out = np.empty((int(n), 2), np.uint32)
+    _check(lib().rtw_sweep_operands(int(which), int(first), int(n), int(seed) & 0xFFFFFFFF, out.ctypes.data), "rtw_sweep_operands")
+    return out[:, 0].copy().view(np.float32), out[:, 1].copy().view(np.float32)
 
 
 def _triangle_array(triangles):
@@ -1312,6 +1363,27 @@ class Renderer:
         _check(lib().rtw_ctx_perlin_eval(self._h, C.byref(perlin.pod), pts.ctypes.data_as(C.POINTER(C.c_float)), len(pts), int(depth),
                                          out.ctypes.data_as(C.POINTER(C.c_float))), "rtw_ctx_perlin_eval")
         return out
+
+    def device_math(self, fn: int, *columns) -> np.ndarray:
+        """rtw_ctx_device_math: one of the hot path's arithmetic sequences (MATH_*) on this context's GPU, element i by thread i (64 consecutive
+        elements share a wave).  columns: the function's arguments as arrays (broadcast), or one [n, n_cols] array; returns [n] or
+        [n, out_cols] float32."""
+        n_cols, out_cols = MATH_COLS[fn]
+        if len(columns) == 1 and n_cols > 1:
+            arg = np.ascontiguousarray(columns[0], np.float32).reshape(-1, n_cols)
+        else:
+            arg = np.ascontiguousarray(np.stack(np.broadcast_arrays(*[np.asarray(c, np.float32).ravel() for c in columns]), axis=1), np.float32)
+        out = np.empty((len(arg), out_cols), np.float32)
+        fp = C.POINTER(C.c_float)
+        _check(lib().rtw_ctx_device_math(self._h, int(fn), arg.ctypes.data_as(fp), n_cols, len(arg), out.ctypes.data_as(fp), out_cols),
+               "rtw_ctx_device_math")
+        return out[:, 0] if out_cols == 1 else out
+
+    def device_sweep(self, which: int, first: int, count: int, seed: int = 0) -> RtwSweepResult:
+        """rtw_ctx_device_sweep: sqrt_plain / div_plain over `count` generated arguments from index `first`, each judged exactly on the GPU."""
+        res = RtwSweepResult()
+        _check(lib().rtw_ctx_device_sweep(self._h, int(which), int(first), int(count), int(seed) & 0xFFFFFFFF, C.byref(res)), "rtw_ctx_device_sweep")
+        return res
 
     def set_option(self, key: int, value: float):
         """Tuning knobs (OPT_*); none of them changes the image."""

@@ -64,6 +64,9 @@ __device__ __forceinline__ float len(v3 a) { return __builtin_sqrtf(a.x * a.x + 
 //   sqrt_plain(x):  x in [2^-96, 2^127)        v_sqrt_f32 (<= 1 ulp) + the two one-ulp residual corrections
 //   rcp_refined(d), div_plain(n, d, r):  |d| in [2^-40, 2^40], |n| in [2^-60, 2^40]    v_rcp_f32 + one Newton step (shared by every
 //                   quotient over d), then the three-fma refinement of n * r
+// Checked on the device itself (rtw_probe.hip, tests/test_gpu_device_math.py): sqrt_plain on every f32 of its range, div_plain on 2^32 pairs of
+// its ranges, half of them 2^-24 ulp from a rounding boundary (div_plain and div_plain_nz, which must agree), div_plain on zeros of either sign: no wrong result.  Below |n| = 2^-102 or so
+// the residual n - d q, a multiple of ulp(d) ulp(q), is no longer a float and the quotient can be one ulp off: atan2_plain rescales such numerators.
 __device__ __forceinline__ float sqrt_plain(float x) {
     const float s = __builtin_amdgcn_sqrtf(x);
     const float s_dn = __uint_as_float(__float_as_uint(s) - 1u), s_up = __uint_as_float(__float_as_uint(s) + 1u);
@@ -81,11 +84,17 @@ __device__ __forceinline__ float rcp_refined(float d) {
     const float r = __builtin_amdgcn_rcpf(d);
     return __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
 }
-__device__ __forceinline__ float div_plain(float n, float d, float r) {
+// The refinement alone, for a numerator that is not a zero, or is +0 over a positive d (every caller on the hot path: unit's components are
+// not zero, sphere_root's numerator is a sum that cancelled, which is +0 under round-to-nearest, over a = d.d > 0, atan2_plain's is a minimum of
+// magnitudes).  For the other zeros the residuals -d q + n add zeros of opposite sign, which is +0: -0 / d comes out as +0 for a positive d.
+__device__ __forceinline__ float div_plain_nz(float n, float d, float r) {
     float q = n * r;
     q = __builtin_fmaf(__builtin_fmaf(-d, q, n), r, q);
     return __builtin_fmaf(__builtin_fmaf(-d, q, n), r, q);
 }
+// ... and for any numerator of the range, a zero of either sign included: n * r has IEEE's sign (one more instruction, v_bfi_b32; on the bench
+// frame it cost 0.9 % when every quotient of the hot path paid it, DESIGN.md 2, hence the two functions)
+__device__ __forceinline__ float div_plain(float n, float d, float r) { return __builtin_copysignf(div_plain_nz(n, d, r), n * r); }
 // The accepted root of a sphere test, `(-b - sqrt(disc)) / a`, or `(-b + sqrt(disc)) / a` when that one lies before mint (sphere.rs:106-116),
 // for lanes with disc >= 0 (the caller's exec mask).  `ra` = rcp_refined(a); `a_plain` (wave-uniform) says every lane's a is in
 // [2^-20, 2^20].  With disc in [2^-60, 2^96] in every active lane as well, the plain sequences give the bits of the generic expansions:
@@ -98,8 +107,8 @@ __device__ __forceinline__ float sphere_root(float b, float disc, float a, float
     float x;
     if (a_plain && ballot64(!plain) == 0ull) {
         const float sq = sqrt_plain(disc);
-        x = div_plain(-b - sq, a, ra);
-        if (x < mint) x = div_plain(-b + sq, a, ra);
+        x = div_plain_nz(-b - sq, a, ra);
+        if (x < mint) x = div_plain_nz(-b + sq, a, ra);
     } else {
         const float sq = __builtin_sqrtf(disc);
         x = (-b - sq) / a;
@@ -141,7 +150,7 @@ __device__ __forceinline__ v3 unit(v3 a) {
     if (ballot64(!plain) == 0ull) {
         const float s = sqrt_plain(a.x * a.x + a.y * a.y + a.z * a.z);          // argument in [2^-80, 2^82)
         const float r = rcp_refined(s);
-        return mk(div_plain(a.x, s, r), div_plain(a.y, s, r), div_plain(a.z, s, r));
+        return mk(div_plain_nz(a.x, s, r), div_plain_nz(a.y, s, r), div_plain_nz(a.z, s, r));
     }
     return a / len(a);
 }
@@ -416,11 +425,16 @@ __device__ __forceinline__ uint32_t tex_index(float f, uint32_t last) {
 // from 52 to 80 bytes of scratch and from 93.3 to 101.6 ms, profiles/r03_ab_c5_uv.log): the two functions are total -- atan2(+-0, +-0) and NaN
 // arguments give libm's answers, tiny arguments are rescaled, acos of |x| > 1 is NaN.
 //   atan2(y, x):  t = min / max (correctly rounded), atan t = t + t s P(s), s = t^2, then the octant fix-ups
+//   (A numerator below 2^-60 is scaled by 2^64 for the division and the quotient back: div_plain's residuals need it, see there.  With that the
+//   device equals the oracle's copy, which divides with `/`, for every quotient that is zero or a normal number; a SUBNORMAL quotient is rounded
+//   twice here and can differ from it in its last place, 2^-149 -- figures in DESIGN.md 2.  u and v are identical for every input.)
 __device__ __forceinline__ float atan2_plain(float y, float x) {
     const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
     const float k = fmaxf(ax, ay) < 0x1p-60f ? 0x1p80f : 1.0f;                      // (a direction's arctangent does not depend on its length)
     const float mx = fmaxf(ax, ay) * k, mn = fminf(ax, ay) * k;
-    const float t = mx == 0.0f ? 0.0f : div_plain(mn, mx, rcp_refined(mx));           // atan2(+-0, +-0) = +-0 or +-pi: t = 0
+    const bool tiny = mn < 0x1p-60f;
+    const float tq = div_plain_nz(mn * (tiny ? 0x1p64f : 1.0f), mx, rcp_refined(mx)) * (tiny ? 0x1p-64f : 1.0f);
+    const float t = mx == 0.0f ? 0.0f : tq;                                          // atan2(+-0, +-0) = +-0 or +-pi: t = 0
     const float s = t * t;
     float p = 0.002974563976749778f;
     p = __builtin_fmaf(p, s, -0.016581078991293907f); p = __builtin_fmaf(p, s, 0.043553370982408524f); p = __builtin_fmaf(p, s, -0.07580564171075821f);
@@ -668,7 +682,7 @@ __device__ __forceinline__ v3 unit_of_ball_point(v3 p, float l2) {
     if (ballot64(!(lo > 0.0f)) == 0ull) {
         const float s = sqrt_plain(l2);
         const float r = rcp_refined(s);
-        return mk(div_plain(p.x, s, r), div_plain(p.y, s, r), div_plain(p.z, s, r));
+        return mk(div_plain_nz(p.x, s, r), div_plain_nz(p.y, s, r), div_plain_nz(p.z, s, r));
     }
     return p / __builtin_sqrtf(l2);
 }

@@ -8,6 +8,7 @@
 #include "rtw_filter.h"
 #include "rtw_devmem.h"
 #include "rtw_exp.h"
+#include "rtw_probe.h"
 
 #include <link.h>
 
@@ -1099,6 +1100,18 @@ int rtw_ctx_guided_filter(rtw_ctx *c, const void *in, uint32_t w, uint32_t h, co
     if (!c) return RTW_E_INVALID;
     if (c->pend.active) return RTW_E_INVALID;
     return guided_filter_device(c->device, c->stream, &c->filter, c->opt_guided_layout, in, w, h, depth, normal, idx, p, out, stats, &g_last_hip);
+}
+
+// The device-math probe (rtw_probe.hip, rtw.h "device math, for tests") on this context's GPU and stream; the scene is not involved.
+int rtw_ctx_device_math(rtw_ctx *c, uint32_t fn, const float *in, uint32_t n_cols, uint32_t n, float *out, uint32_t out_cols) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return device_math_device(c->device, c->stream, fn, in, n_cols, n, out, out_cols, &g_last_hip);
+}
+int rtw_ctx_device_sweep(rtw_ctx *c, uint32_t which, uint64_t first, uint64_t count, uint32_t seed, RtwSweepResult *result) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return device_sweep_device(c->device, c->stream, which, first, count, seed, result, &g_last_hip);
 }
 
 } // extern "C"

@@ -13,25 +13,38 @@ from tests.test_bilateral_cpu import F, random_image, smooth_image
 
 
 # ---- 1. exp_plain ----------------------------------------------------------------------------------------------------------------------
+# The argument sets of the two tests below, as functions: tests/test_gpu_device_math.py runs the device compile of exp_plain on them.
+EXP_SPECIAL_X = np.array([0.0, -0.0, -np.inf, np.nan, -88.0, -104.0, -1e30], F)
+
+
+def exp_threshold_arguments():
+    """every f32 from -87 down to -88: around exp(x) = 2^-126 (x = -87.3365...), where results start to be flushed to +0"""
+    lo, hi = (int(F(v).view(np.uint32)) for v in (-87.0, -88.0))
+    return np.arange(lo, hi, dtype=np.uint32).view(F)
+
+
+def exp_arguments():
+    rng = np.random.default_rng(11)
+    return np.concatenate([np.linspace(-104.0, 0.0, 2 ** 22 + 1).astype(F), (-104.0 * rng.random(2 ** 20)).astype(F),
+                           -np.exp(rng.uniform(np.log(1e-30), np.log(104.0), 2 ** 18)).astype(F)])       # ... and small arguments, log-spaced
+
+
 def test_exp_plain_special_cases():
-    x = np.array([0.0, -0.0, -np.inf, np.nan, -88.0, -104.0, -1e30], F)
+    x = EXP_SPECIAL_X
     got = R.exp_plain(x)
     assert got[0] == 1.0 and got[1] == 1.0
     assert got[2] == 0.0 and not np.signbit(got[2])
     assert np.isnan(got[3])
     assert not got[4:].any() and not np.signbit(got[4:]).any()
     # nothing below 2^-126 ever comes back: around the threshold (exp(x) = 2^-126 at x = -87.3365...) every result is +0 or normal
-    lo, hi = (int(F(v).view(np.uint32)) for v in (-87.0, -88.0))
-    near = R.exp_plain(np.arange(lo, hi, dtype=np.uint32).view(F))
+    near = R.exp_plain(exp_threshold_arguments())
     assert ((near == 0.0) | (near >= F(2.0 ** -126))).all() and not np.signbit(near).any()
-    exact = np.exp(np.arange(lo, hi, dtype=np.uint32).view(F).astype(np.float64))
+    exact = np.exp(exp_threshold_arguments().astype(np.float64))
     assert np.array_equal(near == 0.0, exact < 2.0 ** -126)
 
 
 def test_exp_plain_error_bound():
-    rng = np.random.default_rng(11)
-    x = np.concatenate([np.linspace(-104.0, 0.0, 2 ** 22 + 1).astype(F), (-104.0 * rng.random(2 ** 20)).astype(F),
-                        -np.exp(rng.uniform(np.log(1e-30), np.log(104.0), 2 ** 18)).astype(F)])       # ... and small arguments, log-spaced
+    x = exp_arguments()
     got = R.exp_plain(x)
     err, early, late = ulp_error(x, got)
     assert not early.any() and not late.any()          # +0 exactly where exp(x) < 2^-126

@@ -43,13 +43,25 @@ def test_python_surface():
 
 
 # ---- host functions == the restatement, bit for bit -------------------------------------------------------------------------------------
-def test_elementary_functions_equal_the_restatement():
+# The argument sets of the tests below, as functions: tests/test_gpu_device_math.py runs the device compile of the same functions on them.
+POW_SPECIAL_X = np.array([0.0, -0.0, 1.0, UP, 1.0000005, np.inf, np.nan, 1e-40, 1.4e-45, 2.0, 3.0e38, 0.99999994, 0.5, 0.70710677, 0.7071068], F)
+POW_SPECIAL_Y = (0.0, 0.5, 1.0, 3.0, 10.0, 1.0 / 11.0, 1e-30, 127.0, 3.0e38)
+
+
+def elementary_arguments():
+    """(x, y) for pow_plain and phi for sin_plain / cos_plain: random, near 1, through the subnormals; the quadrant ends and tiny angles."""
     rng = np.random.default_rng(5)
     x = np.concatenate([rng.random(300000), 1.0 - rng.random(100000) * 1e-5, 2.0 ** rng.uniform(-149, 4, 100000)]).astype(F)
     y = np.concatenate([rng.random(250000) * 12.0, 1.0 / (1.0 + rng.integers(0, 40, 250000))]).astype(F)
+    phi = np.concatenate([rng.random(400000) * 2 * np.pi, np.arange(5) * (np.pi / 2), [2 * np.pi, np.nan, 1e-30, 1.4e-45]]).astype(F)
+    return x, y, phi
+
+
+def test_elementary_functions_equal_the_restatement():
+    x, y, phi = elementary_arguments()
     assert same_bits(R.pow_plain(x, y), MC.pow_plain(x, y))
-    sx = np.array([0.0, -0.0, 1.0, UP, 1.0000005, np.inf, np.nan, 1e-40, 1.4e-45, 2.0, 3.0e38, 0.99999994, 0.5, 0.70710677, 0.7071068], F)
-    for yy in (0.0, 0.5, 1.0, 3.0, 10.0, 1.0 / 11.0, 1e-30, 127.0, 3.0e38):
+    sx = POW_SPECIAL_X
+    for yy in POW_SPECIAL_Y:
         got = R.pow_plain(sx, F(yy))
         assert same_bits(got, MC.pow_plain(sx, F(yy))), yy
         if yy == 0.0:
@@ -57,7 +69,6 @@ def test_elementary_functions_equal_the_restatement():
         else:
             assert got[0] == 0.0 and got[1] == 0.0 and got[2] == 1.0 and got[5] == np.inf and np.isnan(got[6]), (yy, got)
             assert got[3] >= 1.0 and (yy > 127.0 or np.isfinite(got[:5]).all())       # ((1 + 2^-23)^3e38 is inf, as libm's)
-    phi = np.concatenate([rng.random(400000) * 2 * np.pi, np.arange(5) * (np.pi / 2), [2 * np.pi, np.nan, 1e-30, 1.4e-45]]).astype(F)
     assert same_bits(R.sin_plain(phi), MC.sin_plain(phi)) and same_bits(R.cos_plain(phi), MC.cos_plain(phi))
     assert np.isnan(R.sin_plain([np.nan])[0]) and np.isnan(R.cos_plain([np.nan])[0])
     assert R.sin_plain([0.0])[0] == 0.0 and R.cos_plain([0.0])[0] == 1.0
@@ -108,6 +119,14 @@ def stream_values():
     return (np.arange(2 ** 24, dtype=np.float64) / 2 ** 24).astype(F)
 
 
+def pow_cosines():
+    return np.concatenate([np.linspace(0, 1, 2 ** 22 + 1), np.random.default_rng(1).random(2 ** 20)]).astype(F)
+
+
+def stream_phi():
+    return ((stream_values() * F(2.0)).astype(F) * MC.PI).astype(F)
+
+
 def test_pow_error_against_f64():
     base = (F(1.0) - stream_values()).astype(F)
     for ge, bound in POW_GEN.items():
@@ -115,7 +134,7 @@ def test_pow_error_against_f64():
         e = ulps(R.pow_plain(base, ge), np.power(base.astype(np.float64), float(ge)))
         print(f"pow_plain(1 - xi, {float(ge):.6f}): max {e.max():.4f} ulp at base {float(base[e.argmax()])!r} (recorded {bound})")
         assert e.max() <= bound
-    cs = np.concatenate([np.linspace(0, 1, 2 ** 22 + 1), np.random.default_rng(1).random(2 ** 20)]).astype(F)
+    cs = pow_cosines()
     for ex, bound in POW_EXP.items():
         e = ulps(R.pow_plain(cs, F(ex)), np.power(cs.astype(np.float64), ex))
         print(f"pow_plain(cos, {ex}): max {e.max():.4f} ulp at cos {float(cs[e.argmax()])!r} (recorded {bound})")
@@ -123,7 +142,7 @@ def test_pow_error_against_f64():
 
 
 def test_sin_cos_error_against_f64():
-    phi = ((stream_values() * F(2.0)).astype(F) * MC.PI).astype(F)
+    phi = stream_phi()
     for name, fn, ref, bound in (("sin", R.sin_plain, np.sin, SIN_ULP), ("cos", R.cos_plain, np.cos, COS_ULP)):
         e = ulps(fn(phi), ref(phi.astype(np.float64)))
         print(f"{name}_plain: max {e.max():.4f} ulp at phi {float(phi[e.argmax()])!r} (recorded {bound})")
