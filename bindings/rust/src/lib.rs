@@ -97,6 +97,8 @@ pub enum Sampler { Row = 0, Stratified = 1, Centres = 2, NoRand = 3 }      // vi
 
 /// `RTW_OPT_MESH_LIST_MAX` (rtw.h): the option key of the placement count up to which placements are met in list order.
 pub const RTW_OPT_MESH_LIST_MAX: u32 = 12;
+/// `RTW_OPT_MESH_CLIMB` (rtw.h): how `move_mesh_instances` climbs the top-level tree (0 by node count, 1 per height, 2 one workgroup).
+pub const RTW_OPT_MESH_CLIMB: u32 = 13;
 /// A node of the top-level tree over mesh placements (rtw.h `RtwTriNode`): leaf = (first << 3) | count, 0 for an inner node.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -186,6 +188,11 @@ extern "C" {
                              depth: *mut u32, list_walk: *mut u32) -> i32;
     fn rtw_triangle_bvh_refit(tris: *const RtwTriangle, n: u32, ouv: *const f32, nodes_out: *mut RtwTriNode, node_cap: u32, n_nodes: *mut u32,
                               list_walk: *mut u32) -> i32;
+    fn rtw_ctx_move_mesh_instances(ctx: *mut RtwCtx, poses: *const f32, n: u32, ouv: *const f32, n_tris: u32, list_walk_out: *mut u32) -> i32;
+    fn rtw_ctx_mesh_top_dump(ctx: *mut RtwCtx, nodes_out: *mut RtwTriNode, node_cap: u32, n_nodes: *mut u32, rows_out: *mut f32) -> i32;
+    fn rtw_mesh_top_refit(tris: *const RtwTriangle, n_tris: u32, p: *const RtwMeshInstance, n: u32, moved: *const f32, ouv: *const f32,
+                          nodes_out: *mut RtwTriNode, node_cap: u32, n_nodes: *mut u32, rows_out: *mut f32, list_walk: *mut u32,
+                          n_invalid: *mut u32) -> i32;
     fn rtw_mesh_instance_hits_tree(tris: *const RtwTriangle, n_tris: u32, p: *const RtwMeshInstance, n: u32, rays: *const f32, n_rays: u32,
                                    mint: f32, maxt: f32, t_out: *mut f32, placement_out: *mut i32, tri_out: *mut i32, normal_out: *mut f32,
                                    stats: *mut RtwStats) -> i32;
@@ -266,6 +273,17 @@ impl Renderer {
         let mut walk = 0u32;
         check(unsafe { rtw_ctx_refit_triangles(self.ctx, ouv.as_ptr() as *const f32, ouv.len() as u32, &mut walk) })?;
         Ok(walk != 0)
+    }
+    /// rtw_ctx_move_mesh_instances: give the context's placements new poses (position xyz, quat wxyz each; None: they stay) and / or its mesh
+    /// new triangles (`ouv` as refit_triangles takes it; None: the mesh stays) and refit both trees on the GPU; host memory here, staged.
+    /// Ok(list_walk): bit 0 a triangle breaks a condition of the mesh's tree, bit 1 a placement lies beyond reach and the placements are met
+    /// in list order.  An invalid pose leaves its placement where it was and the call answers RTW_E_INVALID.
+    pub fn move_mesh_instances(&mut self, poses: Option<&[[f32; 7]]>, ouv: Option<&[[f32; 9]]>) -> Result<u32, RtwError> {
+        let mut walk = 0u32;
+        let (pp, pn) = poses.map_or((std::ptr::null(), 0), |p| (p.as_ptr() as *const f32, p.len() as u32));
+        let (op, on) = ouv.map_or((std::ptr::null(), 0), |o| (o.as_ptr() as *const f32, o.len() as u32));
+        check(unsafe { rtw_ctx_move_mesh_instances(self.ctx, pp, pn, op, on, &mut walk) })?;
+        Ok(walk)
     }
     /// rtw_ctx_triangle_bvh_dump: the nodes of the context's triangle tree as the device holds them now.
     pub fn triangle_bvh_dump(&mut self) -> Result<Vec<RtwTriNode>, RtwError> {

@@ -315,10 +315,13 @@ enum {
                                      CU's LDS, else as f16 nodes; 1 f16 nodes (the build that keeps the sphere geometry in LDS too, whatever
                                      RTW_OPT_LDS_GEOM says); 2 f32 planes wherever one workgroup fits.  Other builds walk f16 nodes whatever
                                      it says.  Any other value: RTW_E_INVALID.  The walk, the counters and the image are the same */
-    RTW_OPT_MESH_LIST_MAX    = 12 /* contexts with at most this many mesh placements meet them in list order even under RTW_ACCEL_BVH
+    RTW_OPT_MESH_LIST_MAX    = 12,/* contexts with at most this many mesh placements meet them in list order even under RTW_ACCEL_BVH
                                      (result-invariant; the "mesh placements" section); more walk the top-level tree over the placements.
                                      Default RTW_MESH_LIST_MAX_DEFAULT, the measured crossover; 0 = always the top-level
                                      tree, 4294967295 = never; a value that is not a whole number: RTW_E_INVALID.  (added within v4)                                                         */
+    RTW_OPT_MESH_CLIMB       = 13,/* how rtw_ctx_move_mesh_instances climbs the top-level tree: 0 (default) by the tree's node count, the
+                                     measured choice; 1 one launch per height; 2 one launch of one workgroup.  The bytes are the
+                                     same.  Any other value: RTW_E_INVALID.  (added within v4)                                              */
 };
 int  rtw_ctx_set_option(rtw_ctx *ctx, uint32_t key, double value);
 /* Which compiled build of the render kernel the context's last render launched, as text in template-argument order:
@@ -831,7 +834,7 @@ int rtw_mesh_instance_hits_tree(const RtwTriangle *tris, uint32_t n_tris, const 
  * *list_walk_out (may be NULL) = 1 when a triangle now breaks a condition of the tree (rtw_ctx_set_triangles' list) and the context walks
  * the list until a later refit or set brings 0.  It reserves no memory.  RTW_E_NO_SCENE without triangles; RTW_E_INVALID for a NULL
  * pointer, n other than the context's count, a pending render, and while placements are set (their top-level tree was built over the old
- * root box: clear them, refit, set them again).  After RTW_E_HIP the triangles may be partly moved: placements are refused until a refit
+ * root box: rtw_ctx_move_mesh_instances refits both).  After RTW_E_HIP the triangles may be partly moved: placements are refused until a refit
  * or rtw_ctx_set_triangles succeeds.  No rtw_mgpu_* form. */
 int rtw_ctx_refit_triangles(rtw_ctx *ctx, const float *ouv, uint32_t n, uint32_t *list_walk_out);
 /* The nodes of the context's triangle tree as the device holds them now.  nodes_out (may be NULL; node_cap entries, RTW_E_INVALID when too
@@ -845,6 +848,38 @@ int rtw_triangle_bvh_dump(const RtwTriangle *tris, uint32_t n, RtwTriNode *nodes
  * rtw_ctx_triangle_bvh_dump returns after rtw_ctx_refit_triangles(ouv).  *list_walk as rtw_ctx_refit_triangles gives it. */
 int rtw_triangle_bvh_refit(const RtwTriangle *tris, uint32_t n, const float *ouv, RtwTriNode *nodes_out, uint32_t node_cap,
                            uint32_t *n_nodes, uint32_t *list_walk);
+
+/* ---- moving placements (added within v4) -----------------------------------------------------------------------------------
+ * The placements of rtw_ctx_set_mesh_instances take new poses and / or the mesh new triangles; both trees keep their topology.
+ * poses: [n][7] f32 = position xyz, quat wxyz (the layout of RtwMeshInstance), n = the context's placement count, or NULL: the poses stay.
+ * ouv:   [n_tris][9] f32 as rtw_ctx_refit_triangles takes it, or NULL: the mesh stays.  Not both NULL.  A device or managed pointer of the
+ * context's GPU is read in place, anything else is staged into memory the setters reserved: the call reserves none.  On the context's
+ * stream, behind the caller's producers: the triangle refit (ouv given), then one thread per leaf of the top-level tree forms the rows of
+ * its placements and their world boxes from the mesh's root box as the device holds it, then the inner boxes bottom-up; one stream
+ * synchronise at the end.  The tree only prunes and the winner among placements is the least (t, index) in any visiting order, so a render
+ * or query afterwards gives what rtw_ctx_set_triangles + rtw_ctx_set_mesh_instances of the moved mesh and poses give, bit for bit; a moved
+ * tree may cost node visits, rtw_ctx_set_mesh_instances rebuilds.
+ * An INVALID pose (a component that is not finite, a quaternion whose len is 0 or not finite -- decided on the device, for host and device
+ * input alike) leaves its placement where it was; every other placement moves, the context is consistent (it holds the list with the bad
+ * entries replaced by their old poses) and the call returns RTW_E_INVALID.
+ * *list_walk_out (may be NULL; also written with that RTW_E_INVALID): bit 0 = a triangle breaks a condition of the mesh's tree
+ * (rtw_ctx_refit_triangles' answer); bit 1 = a placement or the mesh lies beyond 2^38 and the placements are met in list order until a later
+ * move brings 0 (rtw_ctx_set_mesh_instances keeps the tree in that case too, so that a move can recover it).
+ * RTW_E_NO_SCENE without placements; RTW_E_INVALID for both pointers NULL, n / n_tris other than the context's counts for a given pointer, a
+ * pending render, and a stale mesh root (rtw_ctx_refit_triangles) with ouv == NULL.  After RTW_E_HIP neither tree is walked and the root is
+ * stale, as after a refit that stopped.  No rtw_mgpu_* form. */
+int rtw_ctx_move_mesh_instances(rtw_ctx *ctx, const float *poses, uint32_t n, const float *ouv, uint32_t n_tris, uint32_t *list_walk_out);
+/* The context's top-level tree and placement rows as the device holds them now: nodes_out (may be NULL; node_cap entries, RTW_E_INVALID when
+ * too few) and *n_nodes (may be NULL; one leaf for a single placement); rows_out ([n][8] f32, may be NULL): per placement the normalised
+ * quaternion w, x, y, z, then position, 0.  RTW_E_NO_SCENE without placements. */
+int rtw_ctx_mesh_top_dump(rtw_ctx *ctx, RtwTriNode *nodes_out, uint32_t node_cap, uint32_t *n_nodes, float *rows_out /* [n][8], may be NULL */);
+/* Host only: the top-level tree built for `placements`, refitted to `moved` ([n][7], may be NULL) with the mesh refitted to `ouv` (may be
+ * NULL) -- the functions and the schedules the device runs, compiled for the host: the bytes rtw_ctx_mesh_top_dump returns after
+ * rtw_ctx_set_mesh_instances(placements) and rtw_ctx_move_mesh_instances(moved, ouv).  *list_walk as the move gives it; *n_invalid: the
+ * invalid poses of `moved` (the status stays RTW_OK: their placements keep their rows).  Statuses as rtw_mesh_top_dump. */
+int rtw_mesh_top_refit(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *placements, uint32_t n, const float *moved /* [n][7] */,
+                       const float *ouv, RtwTriNode *nodes_out, uint32_t node_cap, uint32_t *n_nodes, float *rows_out /* [n][8], may be NULL */,
+                       uint32_t *list_walk, uint32_t *n_invalid);
 
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 

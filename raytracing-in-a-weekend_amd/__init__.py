@@ -51,6 +51,7 @@ OPT_CHUNK_LEN, OPT_SAMPLE_BANK_GB, OPT_LDS_GEOM, OPT_BLOCKS_PER_CU, OPT_LIST_WAL
 OPT_TAIL_UNITS = 9
 OPT_NODE_FORMAT = 11                                 # the large-workgroup BVH builds' tree in LDS: 0 f32 planes where they fit, 1 f16 nodes, 2 f32 planes
 NODE_FORMAT_NONE, NODE_FORMAT_F16, NODE_FORMAT_F32 = 0, 1, 2   # Renderer.last_node_format
+OPT_MESH_CLIMB = 13                                   # how move_mesh_instances climbs the top-level tree: 0 by node count, 1 per height, 2 one workgroup
 OPT_MESH_LIST_MAX = 12                               # at most this many mesh placements: list order even under ACCEL_BVH; more: the top-level tree
 MESH_LIST_MAX_DEFAULT = 16                           # its default (csrc/rtw_kernels.h RTW_MESH_LIST_MAX_DEFAULT): the measured crossover, DESIGN.md 4.11
 OPT_GUIDED_LAYOUT = 10                               # Renderer.guided_filter: 0 by size, 1 table + guides in LDS, 2 guides, 3 table, 4 neither
@@ -338,6 +339,10 @@ def lib() -> C.CDLL:
                                              C.POINTER(C.c_int32), fp, C.POINTER(RtwStats)]
     L.rtw_mesh_top_dump.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, C.POINTER(RtwMeshInstance), C.c_uint32, C.c_void_p, C.c_uint32,
                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.rtw_ctx_move_mesh_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.rtw_ctx_mesh_top_dump.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]
+    L.rtw_mesh_top_refit.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, C.POINTER(RtwMeshInstance), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.rtw_mesh_list_max_default.restype = C.c_uint32
     L.rtw_mesh_list_max_default.argtypes = []
     L.rtw_mesh_instance_hits_tree.argtypes = L.rtw_mesh_instance_hits.argtypes + [C.POINTER(RtwStats)]
@@ -741,6 +746,33 @@ def mesh_top_dump(triangles, placements):
     _check(lib().rtw_mesh_top_dump(arr, n, parr, pn, nodes.ctypes.data, len(nodes), C.byref(nn), order.ctypes.data_as(C.POINTER(C.c_uint32)),
                                    C.byref(dp), C.byref(lw)), "rtw_mesh_top_dump")
     return nodes[:nn.value].copy(), order[:pn].copy(), dp.value, lw.value
+
+
+def _poses(poses, n=None):
+    """[n][7] float32 = position, (w, x, y, z) of a list of (position, quat) pairs or an array of that shape."""
+    if isinstance(poses, (list, tuple)) and len(poses) and len(poses[0]) == 2:
+        poses = [list(pos) + list(quat) for pos, quat in poses]
+    a = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
+    if n is not None and len(a) != n:
+        raise ValueError(f"poses holds {len(a)} placements, the context {n}")
+    return a
+
+
+def mesh_top_refit(triangles, placements, moved=None, ouv=None):
+    """rtw_mesh_top_refit: the top-level tree built for `placements` of the mesh `triangles`, refitted on the host to the poses `moved`
+    ((position, quat) pairs or [n][7]; None: they stay) with the mesh refitted to ouv (None: it stays) -- the bytes Renderer.mesh_top_dump
+    returns after set_mesh_instances(placements) and move_mesh_instances(moved, ouv): (nodes [n_nodes] of TOP_NODE, rows [n][8] float32 =
+    normalised quaternion, position, 0; list_walk; n_invalid: the invalid poses of `moved`, whose placements keep their rows)."""
+    arr, n = _triangle_array(triangles)
+    parr, pn = _placement_array(placements)
+    mv = None if moved is None else _poses(moved, pn)
+    a = None if ouv is None else _ouv(ouv, n)
+    nodes = np.zeros(max(2 * pn, 1), TOP_NODE)
+    rows = np.zeros((max(pn, 1), 8), np.float32)
+    nn, lw, bad = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().rtw_mesh_top_refit(arr, n, parr, pn, None if mv is None else mv.ctypes.data, None if a is None else a.ctypes.data,
+                                    nodes.ctypes.data, len(nodes), C.byref(nn), rows.ctypes.data, C.byref(lw), C.byref(bad)), "rtw_mesh_top_refit")
+    return nodes[:nn.value].copy(), rows[:pn].copy(), lw.value, bad.value
 
 
 def depth_rays(cam: RtwCamera, width: int, height: int) -> np.ndarray:
@@ -1304,6 +1336,56 @@ class Renderer:
         Instance of triangles; renders under INTEGRATOR_RUST2 and the scene queries honour it; set_scene and set_triangles clear it."""
         arr, n = _placement_array(placements)
         _check(lib().rtw_ctx_set_mesh_instances(self._h, arr, n), "rtw_ctx_set_mesh_instances")
+
+    def _device_floats(self, x, per, n, what, name):
+        """(pointer, count, keep-alive) of a move's input of `per` floats an entry: a tensor (read in place), an int device pointer with
+        its count, or anything numpy reads (staged)."""
+        if hasattr(x, "data_ptr"):
+            import torch
+            if x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda or x.device.index != self._device:
+                raise ValueError(f"{what}: the tensor must be float32, contiguous and on the context's device")
+            if x.numel() % per:
+                raise ValueError(f"{what}: the tensor must hold [n][{per}] floats")
+            return int(x.data_ptr()), x.numel() // per, x
+        if isinstance(x, int):
+            if n is None:
+                raise ValueError(f"{what}: a device pointer needs {name}=")
+            return x, int(n), None
+        keep = _poses(x) if per == 7 else _ouv(x)
+        return keep.ctypes.data, len(keep), keep
+
+    def move_mesh_instances(self, poses=None, ouv=None, n: Optional[int] = None, n_tris: Optional[int] = None) -> int:
+        """rtw_ctx_move_mesh_instances: give the context's placements new poses and / or its mesh new triangles and refit the top-level tree
+        (and the mesh's) on the GPU, on the context's stream; both topologies stay, every answer is that of set_triangles + set_mesh_instances
+        of the moved mesh and poses.  `poses` (None: they stay): a list of (position, quat) as set_mesh_instances takes it; a numpy [n][7]
+        array = position, (w, x, y, z) (staged); an int device pointer with n=; or anything with data_ptr() -- a torch tensor, float32,
+        contiguous, on the context's device, read in place behind its producers on the stream of use_torch_stream.  `ouv` (None: the mesh
+        stays) as refit_triangles takes it (n_tris= with a device pointer).  Returns list_walk: bit 0 a triangle breaks a condition of the
+        mesh's tree, bit 1 a placement or the mesh lies beyond reach and the placements are met in list order.  An invalid pose leaves its
+        placement where it was, the others move, and RtwError(E_INVALID) is raised."""
+        if poses is None and ouv is None:
+            raise ValueError("move_mesh_instances: poses, ouv or both")
+        pp, pn, keep_p = (None, 0, None) if poses is None else self._device_floats(poses, 7, n, "move_mesh_instances", "n")
+        op, on, keep_o = (None, 0, None) if ouv is None else self._device_floats(ouv, 9, n_tris, "move_mesh_instances", "n_tris")
+        if poses is not None and n is not None and int(n) != pn:
+            raise ValueError(f"move_mesh_instances: poses holds {pn} placements, n = {n}")
+        if ouv is not None and n_tris is not None and int(n_tris) != on:
+            raise ValueError(f"move_mesh_instances: ouv holds {on} triangles, n_tris = {n_tris}")
+        lw = C.c_uint32()
+        _check(lib().rtw_ctx_move_mesh_instances(self._h, C.c_void_p(pp), pn, C.c_void_p(op), on, C.byref(lw)), "rtw_ctx_move_mesh_instances")
+        del keep_p, keep_o
+        return lw.value
+
+    def mesh_top_dump(self):
+        """rtw_ctx_mesh_top_dump: the context's top-level tree and placement rows as the device holds them now -- (nodes [n_nodes] of TOP_NODE,
+        rows [n][8] float32 = normalised quaternion w, x, y, z, position, 0)."""
+        nn = C.c_uint32()
+        _check(lib().rtw_ctx_mesh_top_dump(self._h, None, 0, C.byref(nn), None), "rtw_ctx_mesh_top_dump")
+        nodes = np.zeros(nn.value, TOP_NODE)
+        _check(lib().rtw_ctx_mesh_top_dump(self._h, nodes.ctypes.data, len(nodes), None, None), "rtw_ctx_mesh_top_dump")
+        rows = np.zeros((int((nodes["leaf"] & 7).sum()), 8), np.float32)         # (every placement sits in exactly one leaf)
+        _check(lib().rtw_ctx_mesh_top_dump(self._h, None, 0, None, rows.ctypes.data), "rtw_ctx_mesh_top_dump")
+        return nodes, rows
 
     def mesh_instance_hits(self, rays, mint: float, maxt: float, accel: int = ACCEL_BVH, normals: bool = True):
         """The closest placement of this context's mesh per ray on its GPU (rtw_ctx_mesh_instance_hits): (t, placement, triangle[, normals],

@@ -14,20 +14,27 @@ namespace rtw {
 
 // ---- host and device: the rows of a placement list, and one placement's list walk ------------------------------------------------------
 // The checks of rtw_ctx_set_mesh_instances on the placements themselves; rows ([2 n] f4, may be null) receives what the kernels read.
+// One pose ([7] f32 = position xyz, quat wxyz: the layout of RtwMeshInstance): false for a component that is not finite or a quaternion whose
+// len is 0 or not finite, else its two rows.  The host forms the rows of a list with it (mesh_rows), the device those of a moved placement
+// (mesh_top_refit_leaf, rtw_refit.h): one definition, the same bits (1.0f / sqrtf correctly rounded on both sides, denormals kept).
+__host__ __device__ inline bool mesh_pose_rows(const float *pose, f4 &a, f4 &b) {
+    const quat q = qmk(pose[3], pose[4], pose[5], pose[6]);
+    for (int k = 0; k < 3; k++) if (!(pose[k] - pose[k] == 0.0f)) return false;
+    if (!(q.w - q.w == 0.0f) || !(q.x - q.x == 0.0f) || !(q.y - q.y == 0.0f) || !(q.z - q.z == 0.0f)) return false;
+    const float l = quat_len(q);
+    if (!(l > 0.0f) || !(l - l == 0.0f)) return false;
+    const quat qn = quat_normalised(q);
+    a.x = qn.w; a.y = qn.x; a.z = qn.y; a.w = qn.z;
+    b.x = pose[0]; b.y = pose[1]; b.z = pose[2]; b.w = 0.0f;
+    return true;
+}
+
 inline bool mesh_rows(const RtwMeshInstance *p, uint32_t n, f4 *rows) {
+    static_assert(sizeof(RtwMeshInstance) == 7 * sizeof(float), "a placement is one pose");
     for (uint32_t i = 0; i < n; i++) {
-        const quat q = qmk(p[i].quat[0], p[i].quat[1], p[i].quat[2], p[i].quat[3]);
-        for (int k = 0; k < 3; k++) if (!(p[i].position[k] - p[i].position[k] == 0.0f)) return false;
-        if (!(q.w - q.w == 0.0f) || !(q.x - q.x == 0.0f) || !(q.y - q.y == 0.0f) || !(q.z - q.z == 0.0f)) return false;
-        const float l = quat_len(q);
-        if (!(l > 0.0f) || !(l - l == 0.0f)) return false;
-        if (rows) {
-            const quat qn = quat_normalised(q);
-            f4 a, b;
-            a.x = qn.w; a.y = qn.x; a.z = qn.y; a.w = qn.z;
-            b.x = p[i].position[0]; b.y = p[i].position[1]; b.z = p[i].position[2]; b.w = 0.0f;
-            rows[2 * (size_t)i] = a; rows[2 * (size_t)i + 1] = b;
-        }
+        f4 a, b;
+        if (!mesh_pose_rows(reinterpret_cast<const float *>(p + i), a, b)) return false;
+        if (rows) { rows[2 * (size_t)i] = a; rows[2 * (size_t)i + 1] = b; }
     }
     return true;
 }

@@ -1,8 +1,11 @@
 // rtw_refit.h -- what the triangle tree's builder (rtw_tri.cpp) and its refit (host: rtw_tri.cpp, device: rtw_refit.hip) share: the inflated
-// box of one triangle, the outward roundings, and the two steps of a refit -- one leaf node, one inner node.  One
-// __host__ __device__ definition each; every translation unit that includes this is built with -ffp-contract=off.
+// box of one triangle, the outward roundings, and the two steps of a refit -- one leaf node, one inner node; and the same
+// for the top-level tree over mesh placements (builder: mesh_top_build; refit: rtw_tri.cpp / rtw_mesh_move.hip): the world box of one placement
+// and the leaf step of its refit.  One __host__ __device__ definition each; every translation unit that includes this is
+// built with -ffp-contract=off.
 #pragma once
 #include "rtw_tri.h"
+#include "rtw_mesh.h"
 
 namespace rtw {
 
@@ -106,6 +109,70 @@ __host__ __device__ inline void refit_inner_node(TriNode *nodes, uint32_t node) 
     for (int k = 0; k < 3; k++) { nd.lo[k] = box_minf(l.lo[k], r.lo[k]); nd.hi[k] = box_maxf(l.hi[k], r.hi[k]); }
 }
 
+// ---- the top-level tree over mesh placements ---------------------------------------------------------------------------
+// The world box of one placement {qrow = qn as w, x, y, z; prow = position, 0}.  The local frame is x' = qn.rotate(x - position), so the
+// geometry a ray meets stands at conj(qn).rotate(x') + position -- the CONJUGATE rotation, not the q.rotate(p') + position of the hit record.
+// The eight corners of the mesh tree's root box (padded by r_static already) are turned in double precision (qn's f32 components are exact
+// doubles; the map is linear, so the image of the box lies in the corners' hull), then the box is padded by the static part of 4.11's bound,
+// c2 u (|position|_inf + rho) with c2 = 512 and rho the largest corner norm, plus 2^-40 of its size for the double arithmetic itself.
+// The builder (mesh_top_build) and the refit on either side (mesh_top_refit_leaf) call this one definition.
+__host__ __device__ inline bool placement_box(const TriNode &root, const f4 &qrow, const f4 &prow, TriBox &b) {
+    const double w = qrow.x, x = qrow.y, y = qrow.z, z = qrow.w;
+    const double pos[3] = { prow.x, prow.y, prow.z };
+    double rho = 0.0, pmax = 0.0, amax = 0.0;
+    for (int k = 0; k < 3; k++) { b.lo[k] = __builtin_huge_val(); b.hi[k] = -__builtin_huge_val(); pmax = box_max(pmax, __builtin_fabs(pos[k])); }
+    for (int c = 0; c < 8; c++) {
+        const double v[3] = { (c & 1) ? root.hi[0] : root.lo[0], (c & 2) ? root.hi[1] : root.lo[1], (c & 4) ? root.hi[2] : root.lo[2] };
+        rho = box_max(rho, __builtin_sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+        // conj(qn) (0, v) qn, the vector part: with r = -(x, y, z) it is v (w^2 - r.r) + 2 r (r.v) + 2 w (r x v)
+        const double r[3] = { -x, -y, -z };
+        const double rr = r[0] * r[0] + r[1] * r[1] + r[2] * r[2], rv = r[0] * v[0] + r[1] * v[1] + r[2] * v[2];
+        const double cx[3] = { r[1] * v[2] - r[2] * v[1], r[2] * v[0] - r[0] * v[2], r[0] * v[1] - r[1] * v[0] };
+        for (int k = 0; k < 3; k++) {
+            const double p = v[k] * (w * w - rr) + 2.0 * r[k] * rv + 2.0 * w * cx[k] + pos[k];
+            b.lo[k] = box_min(b.lo[k], p); b.hi[k] = box_max(b.hi[k], p);
+        }
+    }
+    const double pad = 0x1p-24 * 512.0 * (pmax + rho);
+    for (int k = 0; k < 3; k++) amax = box_max(amax, box_max(__builtin_fabs(b.lo[k]), __builtin_fabs(b.hi[k])));
+    const double slack = pad + 0x1p-40 * amax + 0x1p-100;
+    for (int k = 0; k < 3; k++) { b.lo[k] -= slack; b.hi[k] += slack; b.c[k] = 0.5 * (b.lo[k] + b.hi[k]); }
+    // the reach of the bound: the placement and the mesh within RTW_MESH_TOP_REACH of their origins (the per-ray test of mesh_top_ray_ordinary
+    // then implies tri_ray_ordinary in this placement's frame)
+    return __builtin_isfinite(rho) && pmax <= (double)RTW_MESH_TOP_REACH && rho <= (double)RTW_MESH_TOP_REACH;
+}
+
+// One leaf node of the top-level tree, the whole of what either side runs for it: each of its at most 4 placements k = order[first + j]
+// takes its rows from poses[7 k ..] (mesh_pose_rows; `poses` null: the rows stay) -- an INVALID pose writes nothing, the placement keeps its
+// previous rows -- and its world box from the rows it now has and `root`, the mesh tree's node 0; the node's box becomes the union of the
+// boxes rounded outward.  Each placement sits in exactly one leaf: its rows have one writer.  Counts the invalid poses and the placements
+// placement_box puts beyond the reach of its bound.
+struct MeshMoveCount { uint32_t invalid, beyond; };
+__host__ __device__ inline MeshMoveCount mesh_top_refit_leaf(TriNode *nodes, const uint32_t *order, f4 *rows, const float *poses, const TriNode &root,
+                                                            uint32_t node) {
+    TriNode &nd = nodes[node];
+    const uint32_t first = nd.leaf >> 3, cnt = nd.leaf & 7u;
+    float lo[3] = { 0.0f, 0.0f, 0.0f }, hi[3] = { 0.0f, 0.0f, 0.0f };
+    MeshMoveCount n = { 0u, 0u };
+    for (uint32_t j = first; j < first + cnt; j++) {
+        const uint32_t k = order[j];
+        f4 a = rows[2 * (size_t)k], b = rows[2 * (size_t)k + 1];
+        if (poses) {
+            if (mesh_pose_rows(poses + 7 * (size_t)k, a, b)) { rows[2 * (size_t)k] = a; rows[2 * (size_t)k + 1] = b; }
+            else n.invalid++;
+        }
+        TriBox box;
+        if (!placement_box(root, a, b, box)) n.beyond++;
+        for (int c = 0; c < 3; c++) {
+            const float l = box_down(box.lo[c]), h = box_up(box.hi[c]);
+            lo[c] = j == first ? l : box_minf(lo[c], l); hi[c] = j == first ? h : box_maxf(hi[c], h);
+        }
+    }
+    for (int c = 0; c < 3; c++) { nd.lo[c] = lo[c]; nd.hi[c] = hi[c]; }
+    return n;
+}
+// (The inner step is refit_inner_node, above.)
+
 // ---- host (rtw_tri.cpp) ---------------------------------------------------------------------------------------------------------------------
 // The order a refit visits the nodes in: `order` holds every node index sorted by height (a leaf: 0; an inner node: 1 + the higher child),
 // ties by index; height h owns order[first[h] .. first[h + 1]), first.size() = heights + 1.  Height 0 is the leaf pass, each further height
@@ -116,11 +183,29 @@ struct RefitSchedule {
 bool tri_refit_schedule(const TriNode *nodes, uint32_t n_nodes, RefitSchedule &out);
 // The refit on the host, over the same schedule: returns the number of triangles tri_box refuses
 uint32_t tri_refit_host(TriNode *nodes, DevTri *leaf, DevTri *list, const float *ouv, const RefitSchedule &s);
+// The top-level tree's refit on the host, over its schedule (`top_order`: the placement indices in leaf order)
+MeshMoveCount mesh_top_refit_host(TriNode *nodes, const uint32_t *top_order, f4 *rows, const float *poses, const TriNode &root, const RefitSchedule &s);
 
 // ---- device (rtw_refit.hip) -----------------------------------------------------------------------------------------------------------------
 // The refit on `stream`: the leaf pass, then one launch per height; device pointers, `order` = RefitSchedule.order uploaded, `first` the host
 // array; *bad (device u32, zeroed by the caller) receives the count.  Allocates nothing.
 void launch_tri_refit(TriNode *nodes, DevTri *leaf, DevTri *list, const float *ouv, const uint32_t *order, const uint32_t *first,
                       uint32_t n_heights, uint32_t *bad, hipStream_t stream);
+// The climb alone, one launch of the inner kernel per height 1 .. n_heights - 1 (`first` the host array): the form the triangle refit runs,
+// for any tree in the TriNode format
+void launch_refit_climb(TriNode *nodes, const uint32_t *order, const uint32_t *first, uint32_t n_heights, hipStream_t stream);
+
+// ---- device (rtw_mesh_move.hip) -------------------------------------------------------------------------------------------------------------
+// The top-level tree's refit on `stream` (rtw_ctx_move_mesh_instances): the placement pass -- one thread per leaf node,
+// mesh_top_refit_leaf with `root` = the mesh tree's node 0 ON THE DEVICE --, then the climb: one_group false: launch_refit_climb; true: ONE
+// launch of one workgroup that loops over the heights itself (d_first: `first` on the device).  counts: two device u32 (invalid, beyond),
+// zeroed by the caller.  Allocates nothing.
+// Which climb: measured (profiles/mesh_move.log), the one workgroup is ahead of the launches per height at 31, 511, 2047
+// and 8191 nodes (by 8 to 19 %) and 39 % behind them at 32 767.  It serves trees of up to 8192 nodes, the largest size at which it was seen
+// ahead; where between 8191 and 32 767 nodes the two cross was not resolved.
+#define RTW_MESH_CLIMB_ONE_GROUP_MAX 8192u
+inline bool mesh_climb_one_group(uint32_t n_nodes) { return n_nodes <= RTW_MESH_CLIMB_ONE_GROUP_MAX; }
+void launch_mesh_move(TriNode *top, const uint32_t *top_order, f4 *rows, const float *poses, const TriNode *root, const uint32_t *order,
+                      const uint32_t *first, const uint32_t *d_first, uint32_t n_heights, bool one_group, uint32_t *counts, hipStream_t stream);
 
 } // namespace rtw

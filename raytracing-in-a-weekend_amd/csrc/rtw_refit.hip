@@ -38,4 +38,13 @@ void launch_tri_refit(TriNode *nodes, DevTri *leaf, DevTri *list, const float *o
     }
 }
 
+// The same climb for another tree of the format (the top-level tree over placements, rtw_mesh_move.hip)
+void launch_refit_climb(TriNode *nodes, const uint32_t *order, const uint32_t *first, uint32_t n_heights, hipStream_t stream) {
+    for (uint32_t h = 1; h < n_heights; h++) {
+        const uint32_t count = first[h + 1] - first[h];
+        hipLaunchKernelGGL(tri_refit_inner_kernel, dim3((count + RTW_REFIT_BLOCK - 1) / RTW_REFIT_BLOCK), dim3(RTW_REFIT_BLOCK), 0, stream,
+                           nodes, order + first[h], count);
+    }
+}
+
 } // namespace rtw

@@ -48,7 +48,12 @@ struct TriMem {
 #define REFIT_OUV_BYTES (9 * sizeof(float))      // one triangle of a refit's input: origin, u, v
 #define REFIT_READBACK_BYTES 64u                 // u32 count at 0, TriNode at 32
 struct QuatMem { DevMem rows; };
-struct MeshMem { DevMem rows, top; };     // top: the top-level tree's nodes, the leaf-order placement indices behind them
+struct MeshMem {
+    DevMem rows, top;                    // top: the top-level tree's nodes, the leaf-order placement indices behind them
+    DevMem order, first, poses, counts;  // the move's (rtw_ctx_move_mesh_instances): the top-level tree's height schedule and its `first` on the device,
+                                         // the staging of host poses, the counts of invalid poses and of placements beyond reach
+};
+#define MOVE_POSE_BYTES (7 * sizeof(float))      // one placement of a move's input: position, quaternion
 struct ScratchMem {
     DevMem queue, stats;
     PinnedMem h_stats;                   // pinned: the counter read-back is a true async copy
@@ -107,8 +112,11 @@ struct rtw_ctx {
     // mesh placements (rtw_ctx_set_mesh_instances; cleared by rtw_ctx_set_scene and rtw_ctx_set_triangles): two rows per placement (rtw_mesh.h)
     const f4 *mesh_rows = nullptr;       // non-null: renders take the placement build (SPEC 12), the queries place the mesh
     uint32_t n_mesh = 0;
-    const TriNode *mesh_top = nullptr;   // the top-level tree over the placements, or null: none was built (n < 2), or a placement
-    uint32_t n_mesh_top = 0;             // lies beyond the reach of its bound.  A render or query takes it through mesh_top_view
+    const TriNode *mesh_top = nullptr;   // the top-level tree over the placements, or null: n < 2.  A render or query takes it
+    uint32_t n_mesh_top = 0;             // through mesh_top_view
+    bool mesh_top_ok = false;            // no placement lies beyond the reach of the tree's bound (and no move stopped half-way): the tree may be walked
+    uint32_t n_top_nodes = 0;            // the nodes in mesh_mem.top (one leaf for n == 1, which no walk reads: the move's placement pass runs on it)
+    std::vector<uint32_t> move_first;    // RefitSchedule.first of the top-level tree: the move's launches
     bool tri_textured = false;           // a triangle of the context reads an image texture (placements refuse such a mesh)
     MeshMem mesh_mem;
     // MixedMaterial (RTW_FLAG_MIXED_MATERIAL): does the scene hold an object with opacity < 0, and is the exponent (ir) of every such object
@@ -125,6 +133,7 @@ struct rtw_ctx {
     uint32_t opt_blocks_per_cu = 0;
     uint32_t opt_list_walk_max = RTW_LIST_WALK_MAX_DEFAULT;
     uint32_t opt_mesh_list_max = RTW_MESH_LIST_MAX_DEFAULT;   // RTW_OPT_MESH_LIST_MAX (profiles/mesh_top_tree.log)
+    uint32_t opt_mesh_climb = 0;         // RTW_OPT_MESH_CLIMB: 0 = by node count (mesh_climb_one_group), 1 = one launch per height, 2 = one workgroup
     uint32_t opt_tile_order = 0;         // raster.  (The cost order, 2, was the default while units were 4 samples and grabs single blocks -- profiles/
                                          // r02_order_chunk_grid.log --; with today's units and grabs raster is 1.2 % ahead of it on the bench frame and ahead
                                          // on every other config too, profiles/r02_order_ab.log)
@@ -298,6 +307,9 @@ static void free_mesh(rtw_ctx *c) {
     c->n_mesh = 0;
     c->mesh_top = nullptr;
     c->n_mesh_top = 0;
+    c->mesh_top_ok = false;
+    c->n_top_nodes = 0;
+    c->move_first.clear();
 }
 
 static void free_tris(rtw_ctx *c) {
@@ -854,21 +866,95 @@ int rtw_ctx_set_mesh_instances(rtw_ctx *c, const RtwMeshInstance *p, uint32_t n)
     HIP_TRY(hipSetDevice(c->device));
     free_mesh(c);
     if (!n) return RTW_OK;
-    // the top-level tree, for every n >= 2 (whether a render walks it: mesh_top_view)
+    // the top-level tree and its height schedule, always -- beyond reach too: a later move may bring the placements back (whether a render
+    // walks it: mesh_top_view; n == 1: one leaf that only the move's placement pass reads)
     MeshTopBuild top;
     std::vector<unsigned char> packed;
-    if (n >= 2) {
-        if (!mesh_top_build(c->tri_root, rows.data(), n, top)) return RTW_E_NOMEM;
-        try { packed = top.packed(); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
-    }
+    RefitSchedule sched;
+    if (!mesh_top_build(c->tri_root, rows.data(), n, top)) return RTW_E_NOMEM;
+    try { packed = top.packed(); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+    if (!tri_refit_schedule(top.nodes.data(), (uint32_t)top.nodes.size(), sched)) return RTW_E_NOMEM;
     MeshMem m;
-    if (const int rc = upload(m.rows, rows)) return rc;
-    const bool use_top = n >= 2 && !top.list_walk;
-    if (use_top) if (const int rc = upload(m.top, packed)) return rc;
+    int rc;
+    if ((rc = upload(m.rows, rows)) || (rc = upload(m.top, packed))) return rc;
+    // everything a move needs, now: rtw_ctx_move_mesh_instances reserves nothing
+    if ((rc = upload(m.order, sched.order)) || (rc = upload(m.first, sched.first))) return rc;
+    HIP_TRY(m.poses.reserve(MOVE_POSE_BYTES * (size_t)n));
+    HIP_TRY(m.counts.reserve(2 * sizeof(uint32_t)));
     c->mesh_rows = m.rows.as<f4>(); c->n_mesh = n;
-    if (use_top) { c->mesh_top = m.top.as<TriNode>(); c->n_mesh_top = (uint32_t)top.nodes.size(); }
+    c->n_top_nodes = (uint32_t)top.nodes.size();
+    if (n >= 2) { c->mesh_top = m.top.as<TriNode>(); c->n_mesh_top = c->n_top_nodes; }
+    c->mesh_top_ok = !top.list_walk;
+    c->move_first = std::move(sched.first);
     c->mesh_mem = std::move(m);
     return RTW_OK;
+}
+
+// The placements move, the mesh may move with them, both trees keep their topology (rtw.h "moving placements"; device code: rtw_mesh_move.hip).
+// On the context's stream, behind the caller's producers of `poses` and `ouv`: the triangle refit (when ouv is given), the placement pass
+// -- which reads the mesh's root from the device's node 0, so no host round trip stands between the two --, the climb; one synchronise at
+// the end for the counts and the mesh's root.
+static bool mesh_climb_choice(const rtw_ctx *c) {
+    return c->opt_mesh_climb == 0 ? mesh_climb_one_group(c->n_top_nodes) : c->opt_mesh_climb == 2;
+}
+int rtw_ctx_move_mesh_instances(rtw_ctx *c, const float *poses, uint32_t n, const float *ouv, uint32_t n_tris, uint32_t *list_walk_out) {
+    if (!c) return RTW_E_INVALID;
+    if (!c->mesh_rows) return RTW_E_NO_SCENE;
+    if ((!poses && !ouv) || (poses && n != c->n_mesh) || (ouv && n_tris != c->tris.n) || c->pend.active || (!ouv && c->tri_root_stale)) return RTW_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    TriMem &t = c->tri_mem;
+    MeshMem &m = c->mesh_mem;
+    unsigned char *back = c->scr.h_refit.as<unsigned char>();
+    hipError_t e = hipSuccess;
+    const float *src_ouv = ouv, *src_poses = poses;
+    if (ouv && !query_on_device(c, ouv)) {
+        e = hipMemcpyAsync(t.ouv.ptr, ouv, REFIT_OUV_BYTES * (size_t)n_tris, hipMemcpyDefault, c->stream);
+        src_ouv = t.ouv.as<const float>();
+    }
+    if (e == hipSuccess && poses && !query_on_device(c, poses)) {
+        e = hipMemcpyAsync(m.poses.ptr, poses, MOVE_POSE_BYTES * (size_t)n, hipMemcpyDefault, c->stream);
+        src_poses = m.poses.as<const float>();
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(t.bad.ptr, 0, sizeof(uint32_t), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(m.counts.ptr, 0, 2 * sizeof(uint32_t), c->stream);
+    if (e == hipSuccess) {
+        if (ouv) launch_tri_refit(t.nodes.as<TriNode>(), t.leaf.as<DevTri>(), t.list.as<DevTri>(), src_ouv, t.order.as<const uint32_t>(), c->refit_first.data(),
+                                  (uint32_t)c->refit_first.size() - 1u, t.bad.as<uint32_t>(), c->stream);
+        launch_mesh_move(m.top.as<TriNode>(), (const uint32_t *)(m.top.as<TriNode>() + c->n_top_nodes), m.rows.as<f4>(), src_poses, t.nodes.as<const TriNode>(),
+                         m.order.as<const uint32_t>(), c->move_first.data(), m.first.as<const uint32_t>(), (uint32_t)c->move_first.size() - 1u,
+                         mesh_climb_choice(c), m.counts.as<uint32_t>(), c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(back, t.bad.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(back + 8, m.counts.ptr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(back + 32, t.nodes.ptr, sizeof(TriNode), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    // a move that stopped half-way: rows and boxes may be partly moved, so neither tree is walked (the lists answer from whatever the records
+    // hold) and tri_root is marked stale, as after a refit that stopped
+    if (const int rc = call_status(c, e)) { c->tri_tree = false; c->tri_root_stale = true; c->mesh_top_ok = false; return rc; }
+    uint32_t bad, counts[2];
+    std::memcpy(&bad, back, sizeof bad);
+    std::memcpy(counts, back + 8, sizeof counts);
+    std::memcpy(&c->tri_root, back + 32, sizeof(TriNode));
+    if (ouv) { c->tri_tree = bad == 0; c->tri_root_stale = false; }
+    c->mesh_top_ok = counts[1] == 0;
+    if (list_walk_out) *list_walk_out = (c->tri_tree ? 0u : 1u) | (counts[1] ? 2u : 0u);
+    return counts[0] ? RTW_E_INVALID : RTW_OK;
+}
+
+int rtw_ctx_mesh_top_dump(rtw_ctx *c, RtwTriNode *nodes_out, uint32_t node_cap, uint32_t *n_nodes, float *rows_out) {
+    if (!c) return RTW_E_INVALID;
+    if (!c->mesh_rows) return RTW_E_NO_SCENE;
+    if (c->pend.active) return RTW_E_INVALID;
+    if (n_nodes) *n_nodes = c->n_top_nodes;
+    if (!nodes_out && !rows_out) return RTW_OK;
+    if (nodes_out && node_cap < c->n_top_nodes) return RTW_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    hipError_t e = hipSuccess;
+    if (nodes_out) e = hipMemcpyAsync(nodes_out, c->mesh_mem.top.ptr, c->n_top_nodes * sizeof(TriNode), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && rows_out) e = hipMemcpyAsync(rows_out, c->mesh_mem.rows.ptr, 2 * (size_t)c->n_mesh * sizeof(f4), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return call_status(c, e);
 }
 
 // What a render answers while placements are set: the placement build serves RTW_INTEGRATOR_RUST2; nothing is built for a MixedMaterial
@@ -900,9 +986,10 @@ static DevTris tri_view(const rtw_ctx *c, uint32_t accel, float mint, float maxt
 }
 
 // ... and the top-level tree over its placements: only next to the mesh's own tree (T = tri_view's answer: RTW_ACCEL_BVH, a mesh and a range
-// the cull covers) and for more than RTW_OPT_MESH_LIST_MAX placements; else null, and the placements are met in list order (the same answer)
+// the cull covers), for more than RTW_OPT_MESH_LIST_MAX placements and while none of them lies beyond the reach of the tree's bound; else null,
+// and the placements are met in list order (the same answer)
 static const TriNode *mesh_top_view(const rtw_ctx *c, const DevTris &T) {
-    return (T.nodes != nullptr && c->n_mesh > c->opt_mesh_list_max) ? c->mesh_top : nullptr;
+    return (T.nodes != nullptr && c->n_mesh > c->opt_mesh_list_max && c->mesh_top_ok) ? c->mesh_top : nullptr;
 }
 
 int rtw_ctx_triangle_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float mint, float maxt, uint32_t accel,
@@ -1604,6 +1691,7 @@ int rtw_ctx_set_option(rtw_ctx *c, uint32_t key, double v) {
     case RTW_OPT_GUIDED_LAYOUT:  if (!(v >= 0.0 && v <= 4.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_guided_layout = (uint32_t)v; return RTW_OK;
     case RTW_OPT_GRAB_BLOCKS:    if (!(v >= 0.0 && v <= 65536.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_grab_blocks = (uint32_t)v; return RTW_OK;
     case RTW_OPT_MESH_LIST_MAX:  if (!(v >= 0.0 && v <= 4294967295.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_mesh_list_max = (uint32_t)v; return RTW_OK;
+    case RTW_OPT_MESH_CLIMB:     if (!(v == 0.0 || v == 1.0 || v == 2.0)) return RTW_E_INVALID; c->opt_mesh_climb = (uint32_t)v; return RTW_OK;
     case RTW_OPT_NODE_FORMAT:    if (!(v == 0.0 || v == 1.0 || v == 2.0)) return RTW_E_INVALID; c->opt_node_format = (uint32_t)v; return RTW_OK;
     default: return RTW_E_INVALID;
     }

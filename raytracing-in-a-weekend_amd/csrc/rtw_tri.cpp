@@ -186,6 +186,18 @@ uint32_t tri_refit_host(TriNode *nodes, DevTri *leaf, DevTri *list, const float 
     return bad;
 }
 
+MeshMoveCount mesh_top_refit_host(TriNode *nodes, const uint32_t *top_order, f4 *rows, const float *poses, const TriNode &root, const RefitSchedule &s) {
+    MeshMoveCount n = { 0u, 0u };
+    for (size_t h = 0; h + 1 < s.first.size(); h++)
+        for (uint32_t k = s.first[h]; k < s.first[h + 1]; k++) {
+            if (h == 0) {
+                const MeshMoveCount m = mesh_top_refit_leaf(nodes, top_order, rows, poses, root, s.order[k]);
+                n.invalid += m.invalid; n.beyond += m.beyond;
+            } else refit_inner_node(nodes, s.order[k]);
+        }
+    return n;
+}
+
 // ---- the top-level tree over mesh placements ---------------------------------------------------------------------------
 std::vector<unsigned char> MeshTopBuild::packed() const {
     std::vector<unsigned char> out(nodes.size() * sizeof(TriNode) + order.size() * sizeof(uint32_t));
@@ -194,37 +206,7 @@ std::vector<unsigned char> MeshTopBuild::packed() const {
     return out;
 }
 
-// The world box of one placement.  The local frame is x' = qn.rotate(x - position), so the geometry a ray meets stands at
-// conj(qn).rotate(x') + position -- the CONJUGATE rotation, not the q.rotate(p') + position of the hit record.  The eight corners of the mesh
-// tree's root box (padded by r_static already) are turned in double precision (qn's f32 components are exact doubles; the map is linear, so
-// the image of the box lies in the corners' hull), then the box is padded by the static part of 4.11's bound, c2 u (|position|_inf + rho)
-// with c2 = 512 and rho the largest corner norm, plus 2^-40 of its size for the double arithmetic itself.
-static bool placement_box(const TriNode &root, const f4 &qrow, const f4 &prow, TriBox &b) {
-    const double w = qrow.x, x = qrow.y, y = qrow.z, z = qrow.w;
-    const double pos[3] = { prow.x, prow.y, prow.z };
-    double rho = 0.0, pmax = 0.0, amax = 0.0;
-    for (int k = 0; k < 3; k++) { b.lo[k] = HUGE_VAL; b.hi[k] = -HUGE_VAL; pmax = std::max(pmax, std::fabs(pos[k])); }
-    for (int c = 0; c < 8; c++) {
-        const double v[3] = { (c & 1) ? root.hi[0] : root.lo[0], (c & 2) ? root.hi[1] : root.lo[1], (c & 4) ? root.hi[2] : root.lo[2] };
-        rho = std::max(rho, std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
-        // conj(qn) (0, v) qn, the vector part: with r = -(x, y, z) it is v (w^2 - r.r) + 2 r (r.v) + 2 w (r x v)
-        const double r[3] = { -x, -y, -z };
-        const double rr = r[0] * r[0] + r[1] * r[1] + r[2] * r[2], rv = r[0] * v[0] + r[1] * v[1] + r[2] * v[2];
-        const double cx[3] = { r[1] * v[2] - r[2] * v[1], r[2] * v[0] - r[0] * v[2], r[0] * v[1] - r[1] * v[0] };
-        for (int k = 0; k < 3; k++) {
-            const double p = v[k] * (w * w - rr) + 2.0 * r[k] * rv + 2.0 * w * cx[k] + pos[k];
-            b.lo[k] = std::min(b.lo[k], p); b.hi[k] = std::max(b.hi[k], p);
-        }
-    }
-    const double pad = 0x1p-24 * 512.0 * (pmax + rho);
-    for (int k = 0; k < 3; k++) amax = std::max(amax, std::max(std::fabs(b.lo[k]), std::fabs(b.hi[k])));
-    const double slack = pad + 0x1p-40 * amax + 0x1p-100;
-    for (int k = 0; k < 3; k++) { b.lo[k] -= slack; b.hi[k] += slack; b.c[k] = 0.5 * (b.lo[k] + b.hi[k]); }
-    // the reach of the bound: the placement and the mesh within RTW_MESH_TOP_REACH of their origins (the per-ray test of mesh_top_ray_ordinary
-    // then implies tri_ray_ordinary in this placement's frame)
-    return std::isfinite(rho) && pmax <= (double)RTW_MESH_TOP_REACH && rho <= (double)RTW_MESH_TOP_REACH;
-}
-
+// (The world box of one placement, placement_box, lives in rtw_refit.h: the refit on the device runs the same definition.)
 bool mesh_top_build(const TriNode &root, const f4 *rows, uint32_t n, MeshTopBuild &out) {
     try {
         std::vector<TriBox> box(n);
@@ -361,6 +343,27 @@ int rtw_mesh_top_dump(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshIns
         std::memcpy(nodes_out, m.top.nodes.data(), nn * sizeof(TriNode));
     }
     if (order_out) std::memcpy(order_out, m.top.order.data(), n * sizeof(uint32_t));
+    return RTW_OK;
+}
+
+// What a context holds after rtw_ctx_set_triangles + rtw_ctx_set_mesh_instances(p) + rtw_ctx_move_mesh_instances(moved, ouv), without a context:
+// the functions and the schedules the device runs, in its order -- the mesh's refit, the placement pass from the refitted root, the climb
+int rtw_mesh_top_refit(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *p, uint32_t n, const float *moved, const float *ouv,
+                       RtwTriNode *nodes_out, uint32_t node_cap, uint32_t *n_nodes, float *rows_out, uint32_t *list_walk, uint32_t *n_invalid) {
+    HostMesh m;
+    if (const int rc = host_mesh(tris, n_tris, p, n, m)) return rc;
+    const uint32_t nn = (uint32_t)m.top.nodes.size();
+    if (n_nodes) *n_nodes = nn;
+    if (nodes_out && node_cap < nn) return RTW_E_INVALID;
+    RefitSchedule ts, s;
+    if ((ouv && !tri_refit_schedule(m.tree.nodes, m.tree.n_nodes, ts)) || !tri_refit_schedule(m.top.nodes.data(), nn, s)) return RTW_E_NOMEM;
+    uint32_t bad = m.tree.list_walk ? 1u : 0u;
+    if (ouv) bad = tri_refit_host(m.tree.nodes, m.tree.leaf, m.list.data(), ouv, ts) ? 1u : 0u;
+    const MeshMoveCount c = mesh_top_refit_host(m.top.nodes.data(), m.top.order.data(), m.rows.data(), moved, m.tree.nodes[0], s);
+    if (list_walk) *list_walk = bad | (c.beyond ? 2u : 0u);
+    if (n_invalid) *n_invalid = c.invalid;
+    if (nodes_out) std::memcpy(nodes_out, m.top.nodes.data(), nn * sizeof(TriNode));
+    if (rows_out) std::memcpy(rows_out, m.rows.data(), 2 * (size_t)n * sizeof(f4));
     return RTW_OK;
 }
 
