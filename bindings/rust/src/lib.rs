@@ -208,6 +208,8 @@ extern "C" {
     fn rtw_depth_rays(cam: *const RtwCamera, width: u32, height: u32, rays_out: *mut f32) -> i32;
     fn rtw_ctx_scene_hits(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, time: f32, mint: f32, maxt: f32, accel: u32,
                           t_out: *mut f32, idx_out: *mut i32, normal_out: *mut f32, stats: *mut RtwStats) -> i32;
+    fn rtw_ctx_scene_occluded(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, time: f32, mint: f32, maxt: f32, accel: u32,
+                              occluded_out: *mut u8, stats: *mut RtwStats) -> i32;
     fn rtw_ctx_depth_map(ctx: *mut RtwCtx, cam: *const RtwCamera, width: u32, height: u32, time: f32, mint: f32, maxt: f32, accel: u32,
                          depth_out: *mut f32, idx_out: *mut i32, normal_out: *mut f32, stats: *mut RtwStats) -> i32;
     fn rtw_mgpu_render(m: *mut RtwMgpu, cam: *const RtwCamera, p: *const RtwParams, out_rgb: *mut c_void,
@@ -335,6 +337,14 @@ impl Renderer {
         check(unsafe { rtw_ctx_scene_hits(self.ctx, rays.as_ptr() as *const f32, rays.len() as u32, time, mint, maxt, accel,
                                           t.as_mut_ptr(), i.as_mut_ptr(), n.as_mut_ptr() as *mut f32, std::ptr::null_mut()) })?;
         Ok((t, i, n))
+    }
+    /// Is anything of the whole scene in the way of each ray within [mint, maxt]?  The any-hit pass: `true` exactly where `scene_hits`
+    /// reports an index >= 0, with the early exit a closest-hit query cannot take.
+    pub fn scene_occluded(&mut self, rays: &[[f32; 6]], time: f32, mint: f32, maxt: f32, accel: u32) -> Result<Vec<bool>, RtwError> {
+        let mut o = vec![0u8; rays.len()];
+        check(unsafe { rtw_ctx_scene_occluded(self.ctx, rays.as_ptr() as *const f32, rays.len() as u32, time, mint, maxt, accel,
+                                              o.as_mut_ptr(), std::ptr::null_mut()) })?;
+        Ok(o.into_iter().map(|b| b != 0).collect())
     }
     /// Rust2's `Viewport::depth_map` in one launch, for a camera of `rtw_camera2_new`: row-major [height][width] hit.t, maxt * 1.6 on a
     /// miss (row j is row j of the image: the reference's leading empty row is not reproduced).

@@ -881,6 +881,31 @@ int rtw_mesh_top_refit(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshIn
                        const float *ouv, RtwTriNode *nodes_out, uint32_t node_cap, uint32_t *n_nodes, float *rows_out /* [n][8], may be NULL */,
                        uint32_t *list_walk, uint32_t *n_invalid);
 
+/* ---- occlusion queries: any-hit over the whole scene (added within v4) -------------------------------------------------
+ * "Is anything in the way?" for shadow tests, line of sight, visibility masks and ambient occlusion: one byte per ray, with the early exit a
+ * closest-hit query cannot take.  THE CONTRACT: occluded_out[i] == 1 exactly when rtw_ctx_scene_hits with the same rays, time, mint, maxt and
+ * accel reports an index >= 0 for ray i, else 0 -- for every ray (NaN rays, zero directions, the rays the trees refuse, a root exactly at
+ * mint or maxt, mint > maxt), under both accels and every fall-back to the lists, RTW_OPT_LIST_WALK_MAX and RTW_OPT_MESH_LIST_MAX honoured as
+ * there.  It is exact, not approximate: every group's acceptance of a candidate with nothing found so far depends on the candidate and on
+ * [mint, maxt] alone, and the trees only prune.  Constant-density instances are skipped, the direction is used as given (t in units of |d|),
+ * every group is served (spheres, quads, instances with either rotation, triangles, mesh placements), and a refit or a move is seen by the
+ * next query.  A lane stops at its first accepted candidate, so every counter is <= rtw_ctx_scene_hits' on the same rays.
+ * rays ([n_rays][6] = origin, direction) and occluded_out ([n_rays] bytes) may each be host memory or device memory of ctx's GPU (host memory
+ * is staged); the work runs on the stream of rtw_ctx_set_stream; blocking.  stats (may be NULL): segments (= n_rays), sphere_tests,
+ * node_tests, quad_tests, kernel_ms.  RTW_E_INVALID for a NULL ctx / rays / occluded_out, n_rays == 0 or an unknown accel; RTW_E_NO_SCENE
+ * before rtw_ctx_set_scene.  No per-ray ranges, no camera form and no rtw_mgpu_* form. */
+int rtw_ctx_scene_occluded(rtw_ctx *ctx, const float *rays, uint32_t n_rays, float time, float mint, float maxt,
+                           uint32_t accel, uint8_t *occluded_out, RtwStats *stats);
+/* Host only: the kernel's triangle group and placement group, the same source compiled for the host -- the mesh's tree where the device would
+ * take it under RTW_ACCEL_BVH, the top-level tree as under RTW_OPT_MESH_LIST_MAX = 0, the lists otherwise.  occluded_out[i] == 1 exactly when
+ * rtw_triangle_hits / rtw_mesh_instance_hits reports an index >= 0.  stats (may be NULL): segments, node_tests = node visits of both trees,
+ * quad_tests = triangle tests.  Statuses as rtw_triangle_hits / rtw_mesh_instance_hits.  (The library has no CPU path for spheres, quads or
+ * instances, so there is no host form of the whole query.) */
+int rtw_triangle_occluded(const RtwTriangle *tris, uint32_t n, const float *rays, uint32_t n_rays, float mint, float maxt,
+                          uint8_t *occluded_out, RtwStats *stats);
+int rtw_mesh_instance_occluded(const RtwTriangle *tris, uint32_t n, const RtwMeshInstance *placements, uint32_t n_placements,
+                               const float *rays, uint32_t n_rays, float mint, float maxt, uint8_t *occluded_out, RtwStats *stats);
+
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 
 /* Viewport::new (viewport.rs:308-401).  Options the reference takes as Option<> are pointers

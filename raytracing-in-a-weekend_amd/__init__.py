@@ -315,6 +315,11 @@ def lib() -> C.CDLL:
     L.rtw_depth_rays.argtypes = [C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, fp]
     L.rtw_ctx_scene_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.POINTER(RtwStats)]
+    L.rtw_ctx_scene_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_void_p,
+                                         C.POINTER(RtwStats)]
+    L.rtw_triangle_occluded.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, fp, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.POINTER(RtwStats)]
+    L.rtw_mesh_instance_occluded.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, C.POINTER(RtwMeshInstance), C.c_uint32, fp, C.c_uint32, C.c_float,
+                                             C.c_float, C.c_void_p, C.POINTER(RtwStats)]
     L.rtw_ctx_depth_map.argtypes = [C.c_void_p, C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtwStats)]
     L.rtw_ctx_set_lights.argtypes = [C.c_void_p, C.POINTER(RtwLight), C.c_uint32, C.c_float]
@@ -730,6 +735,33 @@ def mesh_instance_hits_tree(triangles, placements, rays, mint: float, maxt: floa
     _check(lib().rtw_mesh_instance_hits_tree(arr, n, parr, pn, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt), *ptrs,
                                              C.byref(st)), "rtw_mesh_instance_hits_tree")
     return out + (st,)
+
+
+def triangle_occluded(triangles, rays, mint: float, maxt: float):
+    """Is any triangle in the way of each ray within [mint, maxt]?  On the host (rtw_triangle_occluded: the any-hit walk of the scene
+    query's triangle group, through the mesh's tree where the device would take it): (occluded [n] bool, RtwStats).  occluded[i] is
+    triangle_hits(...)[1][i] >= 0."""
+    arr, n = _triangle_array(triangles)
+    r = _rays(rays)
+    occ = np.empty(len(r), np.uint8)
+    st = RtwStats()
+    _check(lib().rtw_triangle_occluded(arr, n, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt), occ.ctypes.data,
+                                       C.byref(st)), "rtw_triangle_occluded")
+    return occ.view(np.bool_), st
+
+
+def mesh_instance_occluded(triangles, placements, rays, mint: float, maxt: float):
+    """Is any placement of the mesh in the way of each ray?  On the host (rtw_mesh_instance_occluded: the any-hit walk of the scene query's
+    placement group through the top-level tree and the mesh's tree): (occluded [n] bool, RtwStats).  occluded[i] is
+    mesh_instance_hits(...)[1][i] >= 0."""
+    arr, n = _triangle_array(triangles)
+    parr, pn = _placement_array(placements)
+    r = _rays(rays)
+    occ = np.empty(len(r), np.uint8)
+    st = RtwStats()
+    _check(lib().rtw_mesh_instance_occluded(arr, n, parr, pn, r.ctypes.data_as(C.POINTER(C.c_float)), len(r), float(mint), float(maxt),
+                                            occ.ctypes.data, C.byref(st)), "rtw_mesh_instance_occluded")
+    return occ.view(np.bool_), st
 
 
 TOP_NODE = np.dtype([("lo", np.float32, 3), ("skip", np.uint32), ("hi", np.float32, 3), ("leaf", np.uint32)])
@@ -1420,6 +1452,51 @@ class Renderer:
         _check(lib().rtw_ctx_scene_hits(self._h, r.ctypes.data, len(r), float(time), float(mint), float(maxt), int(accel), t.ctypes.data,
                                         idx.ctypes.data, nrm.ctypes.data if normals else None, C.byref(st)), "rtw_ctx_scene_hits")
         return (t, idx, nrm, st) if normals else (t, idx, st)
+
+    def scene_occluded(self, rays, mint: float, maxt: float, time: float = 0.0, accel: int = ACCEL_BVH, out=None):
+        """Is anything of this context's whole scene in the way of each ray ([n][6] = origin, direction; the direction is not normalised)
+        within [mint, maxt]?  The any-hit pass (rtw_ctx_scene_occluded): (occluded, RtwStats), occluded[i] exactly scene_hits(...)[1][i] >= 0,
+        with the early exit a closest-hit query cannot take.  Constant-density instances are skipped.
+        rays: anything numpy reads (staged; occluded is a numpy bool array [n]), or a contiguous float32 torch tensor [n, 6] on the context's
+        device: then `out` is a torch.uint8 or torch.bool tensor [n] on the same device (allocated when None), and both are read and written
+        in place on the context's stream (use_torch_stream), as refit_triangles reads its tensor."""
+        st = RtwStats()
+        if hasattr(rays, "data_ptr"):
+            import torch
+            if rays.dtype != torch.float32 or not rays.is_contiguous() or not rays.is_cuda or rays.device.index != self._device:
+                raise ValueError("scene_occluded: the rays tensor must be float32, contiguous and on the context's device")
+            if rays.numel() == 0 or rays.numel() % 6:
+                raise ValueError("scene_occluded: the rays tensor must hold [n][6] floats, n > 0")
+            n = rays.numel() // 6
+            if out is None:
+                out = torch.empty(n, dtype=torch.uint8, device=rays.device)
+            if (out.dtype not in (torch.uint8, torch.bool) or not out.is_contiguous() or not out.is_cuda or out.device.index != self._device
+                    or out.numel() != n):
+                raise ValueError("scene_occluded: out must be a contiguous torch.uint8 or torch.bool tensor [n] on the context's device")
+            _check(lib().rtw_ctx_scene_occluded(self._h, C.c_void_p(int(rays.data_ptr())), n, float(time), float(mint), float(maxt), int(accel),
+                                                C.c_void_p(int(out.data_ptr())), C.byref(st)), "rtw_ctx_scene_occluded")
+            return out, st
+        if out is not None:
+            raise ValueError("scene_occluded: out= goes with a torch tensor of rays")
+        r = _rays(rays)
+        occ = np.empty(len(r), np.uint8)
+        _check(lib().rtw_ctx_scene_occluded(self._h, r.ctypes.data, len(r), float(time), float(mint), float(maxt), int(accel), occ.ctypes.data,
+                                            C.byref(st)), "rtw_ctx_scene_occluded")
+        return occ.view(np.bool_), st
+
+    def segments_occluded(self, p, q, lo: float = 1e-3, hi: float = 1.0 - 1e-3, time: float = 0.0, accel: int = ACCEL_BVH):
+        """Occlusion between point pairs: is anything between p[i] and q[i] ([n][3] each)?  The rays are (p, q - p) -- one float32 subtraction
+        per component, in numpy or in torch as given -- over [lo, hi] in units of the segment, so the defaults leave out both end points'
+        own surfaces.  Returns scene_occluded's pair."""
+        if hasattr(p, "data_ptr") or hasattr(q, "data_ptr"):
+            import torch
+            if not (hasattr(p, "data_ptr") and hasattr(q, "data_ptr")) or p.dtype != torch.float32 or q.dtype != torch.float32:
+                raise ValueError("segments_occluded: p and q must both be float32 tensors, or both numpy")
+            p, q = p.reshape(-1, 3), q.reshape(-1, 3)
+            return self.scene_occluded(torch.cat([p, q - p], 1).contiguous(), lo, hi, time, accel)
+        p = np.asarray(p, np.float32).reshape(-1, 3)
+        q = np.asarray(q, np.float32).reshape(-1, 3)
+        return self.scene_occluded(np.concatenate([p, q - p], 1), lo, hi, time, accel)
 
     def depth_map(self, cam: RtwCamera, width: int, height: int, mint: float, maxt: float, time: float = 0.0, accel: int = ACCEL_BVH,
                   ids: bool = False, normals: bool = False):

@@ -138,6 +138,27 @@ struct QueryArgs {
 #define RTW_QUERY_STRIDE 16u      // counters (u64) per line: 128 bytes
 // from_camera: rays built from q.cam, else read from q.rays; tree: the sphere group through DevBvh.nodes (dynamic LDS = levels * RTW_BLOCK * 4)
 void launch_scene_hits(const QueryArgs &q, bool from_camera, bool tree, hipStream_t stream);
+// rtw_ctx_scene_occluded (rtw_occluded.hip): one any-hit query per ray over the same four groups; the fields are QueryArgs' of the same names.
+struct OccludedArgs {
+    DevScene sc;
+    DevBvh   bvh;
+    DevGeom  geom;
+    DevTris  tris;
+    const f4 *inst_quats;
+    const f4 *mesh_rows;
+    uint32_t n_mesh;
+    const TriNode *mesh_top;
+    uint32_t n_mesh_top;
+    const float *rays;            // [n][6] = o, d (device)
+    uint32_t n;
+    uint32_t levels;
+    float time, mint, maxt;
+    float span;
+    uint8_t *out;                 // [n]: 1 = something accepts the ray within [mint, maxt], else 0
+    unsigned long long *counters; // as QueryArgs.counters
+};
+// tree: the sphere group through DevBvh.nodes (dynamic LDS = levels * RTW_BLOCK * 4)
+void launch_scene_occluded(const OccludedArgs &q, bool tree, hipStream_t stream);
 // rtw_ctx_mesh_instance_hits: the closest placement of mesh T for each of n rays through mesh_closest (rtw_mesh.h); placement / triangle
 // -1 and t +inf on a miss; normal_out ([n][3]) may be null; counters as launch_tri_hits
 void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const TriNode *top, uint32_t n_top, const float *rays, uint32_t n, float mint, float maxt, float *t_out,

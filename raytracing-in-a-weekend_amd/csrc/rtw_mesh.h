@@ -1,7 +1,8 @@
 // rtw_mesh.h -- mesh placements: Rust2's `Instance` of triangles (Rust2/src/objects/instance.rs:215-255 around triangle.rs).  The context's
 // triangle mesh is placed n times, each placement a position and a quaternion, all sharing the mesh's one tree (rtw.h "mesh
 // placements").  Compiled by the placement build of the render kernels (SPEC 12), by the query kernel (rtw_query.hip) and by the kernel of
-// rtw_ctx_mesh_instance_hits; the host pieces by rtw_tri.cpp.  No other kernel reads this file.
+// rtw_ctx_mesh_instance_hits; the host pieces by rtw_tri.cpp.  The any-hit kernel (rtw_occluded.hip) reads it through rtw_occl.h, which holds
+// the any-hit twins of the walks below.  No other kernel reads this file.
 // The placement group's walk -- mesh_closest, with the top-level tree over the placements -- is ONE __host__ __device__
 // definition: rtw_mesh_instance_hits_tree (rtw_tri.cpp) runs on the host what the kernels run.
 #pragma once

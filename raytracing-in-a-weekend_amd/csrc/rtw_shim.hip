@@ -1063,17 +1063,38 @@ static bool query_on_device(const rtw_ctx *c, const void *p) {
     return (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) && attr.device == c->device;
 }
 
+// Does a query's sphere group go through the tree?  The conditions a render puts on it (render_enqueue_impl); the per-ray ones are checked by
+// the kernels, ray by ray.  ONE definition for the closest-hit and the any-hit query: rtw_ctx_scene_occluded's contract is stated against
+// rtw_ctx_scene_hits with the same arguments.
+static bool query_uses_tree(const rtw_ctx *c, uint32_t accel, float time, float mint, float maxt) {
+    bool tree = accel == RTW_ACCEL_BVH && c->bvh_ok && c->sc.n > c->opt_list_walk_max;
+    if (mint != mint || maxt != maxt || time != time) tree = false;
+    if (!(c->scene_span <= 1e18)) tree = false;
+    if (c->sc.moving && !(time >= c->t_begin && time <= c->t_end)) tree = false;
+    return tree;
+}
+
+// The counters of a query launch (scr.h_qstats: RTW_QUERY_SLOTS lines) summed into `stats`; RTW_E_INTERNAL when a wave's stack was too short
+static int query_stats(const rtw_ctx *c, uint32_t n, float ms, RtwStats *stats) {
+    const unsigned long long *h_qstats = c->scr.h_qstats.as<unsigned long long>();
+    unsigned long long sum[4] = { 0, 0, 0, 0 };
+    for (uint32_t s = 0; s < RTW_QUERY_SLOTS; s++) for (int k = 0; k < 4; k++) sum[k] += h_qstats[s * RTW_QUERY_STRIDE + k];
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        stats->segments = n;
+        stats->sphere_tests = sum[0]; stats->node_tests = sum[1]; stats->quad_tests = sum[2];
+        stats->kernel_ms = ms;
+    }
+    return sum[3] ? RTW_E_INTERNAL : RTW_OK;
+}
+
 // Both calls: cam != null builds the rays of a width x height map in the kernel, else `rays` [n][6] are read.
 static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, const float *rays, uint32_t n, float time, float mint,
                        float maxt, uint32_t accel, float miss_t, float *t_out, int32_t *idx_out, float *normal_out, RtwStats *stats) {
     if (c->pend.active) return RTW_E_INVALID;
     if (!c->has_scene) return RTW_E_NO_SCENE;
     HIP_TRY(hipSetDevice(c->device));
-    // The tree under the conditions a render puts on it (render_enqueue_impl); the per-ray ones are checked by the kernel, ray by ray
-    bool tree = accel == RTW_ACCEL_BVH && c->bvh_ok && c->sc.n > c->opt_list_walk_max;
-    if (mint != mint || maxt != maxt || time != time) tree = false;
-    if (!(c->scene_span <= 1e18)) tree = false;
-    if (c->sc.moving && !(time >= c->t_begin && time <= c->t_end)) tree = false;
+    const bool tree = query_uses_tree(c, accel, time, mint, maxt);
 
     QueryArgs q;
     std::memset(&q, 0, sizeof q);
@@ -1123,16 +1144,7 @@ static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_
     float ms = 0.0f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
     if (const int rc = call_status(c, e)) return rc;
-    const unsigned long long *h_qstats = c->scr.h_qstats.as<unsigned long long>();
-    unsigned long long sum[4] = { 0, 0, 0, 0 };
-    for (uint32_t s = 0; s < RTW_QUERY_SLOTS; s++) for (int k = 0; k < 4; k++) sum[k] += h_qstats[s * RTW_QUERY_STRIDE + k];
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->segments = n;
-        stats->sphere_tests = sum[0]; stats->node_tests = sum[1]; stats->quad_tests = sum[2];
-        stats->kernel_ms = ms;
-    }
-    return sum[3] ? RTW_E_INTERNAL : RTW_OK;
+    return query_stats(c, n, ms, stats);
 }
 
 int rtw_ctx_scene_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float time, float mint, float maxt, uint32_t accel,
@@ -1146,6 +1158,53 @@ int rtw_ctx_depth_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t
     if (!c || !cam || !depth_out || width == 0 || height == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
     if ((uint64_t)width * height > 0xFFFFFFFFull) return RTW_E_INVALID;
     return scene_query(c, cam, width, height, nullptr, width * height, time, mint, maxt, accel, host_mul(maxt, 1.6f), depth_out, idx_out, normal_out, stats);
+}
+
+// The any-hit pass (rtw.h "occlusion queries"; kernel: rtw_occluded.hip): scene_query's conditions, views, staging and stream order
+int rtw_ctx_scene_occluded(rtw_ctx *c, const float *rays, uint32_t n, float time, float mint, float maxt, uint32_t accel, uint8_t *occluded_out,
+                           RtwStats *stats) {
+    if (!c || !rays || !occluded_out || n == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    if (!c->has_scene) return RTW_E_NO_SCENE;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool tree = query_uses_tree(c, accel, time, mint, maxt);
+
+    OccludedArgs q;
+    std::memset(&q, 0, sizeof q);
+    q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom; q.inst_quats = c->inst_quats;
+    if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
+    q.mesh_rows = c->mesh_rows; q.n_mesh = c->n_mesh;
+    if (c->mesh_rows) { q.mesh_top = mesh_top_view(c, q.tris); q.n_mesh_top = c->n_mesh_top; }
+    q.n = n; q.levels = c->bvh.depth + 2u;
+    q.time = time; q.mint = mint; q.maxt = maxt; q.span = (float)c->scene_span;
+    q.counters = c->scr.qstats.as<unsigned long long>();
+
+    const size_t ray_bytes = 6 * sizeof(float) * (size_t)n;
+    DevMem d_r, d_o;                     // staging, for whatever is not this GPU's memory
+    hipError_t e = hipSuccess;
+    if (query_on_device(c, rays)) q.rays = rays;
+    else {
+        e = d_r.reserve(ray_bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_r.ptr, rays, ray_bytes, hipMemcpyDefault, c->stream);
+        q.rays = d_r.as<const float>();
+    }
+    if (query_on_device(c, occluded_out)) q.out = occluded_out;
+    else { if (e == hipSuccess) e = d_o.reserve(n); q.out = d_o.as<uint8_t>(); }
+    const size_t q_bytes = RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long);
+    if (e == hipSuccess) e = hipMemsetAsync(c->scr.qstats.ptr, 0, q_bytes, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    if (e == hipSuccess) {
+        launch_scene_occluded(q, tree, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess && d_o.ptr) e = hipMemcpyAsync(occluded_out, d_o.ptr, n, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->scr.h_qstats.ptr, c->scr.qstats.ptr, q_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    if (const int rc = call_status(c, e)) return rc;
+    return query_stats(c, n, ms, stats);
 }
 
 int rtw_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t turb_depth, float *out) {

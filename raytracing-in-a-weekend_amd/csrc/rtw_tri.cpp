@@ -2,6 +2,7 @@
 // self-check and the host list walk (DESIGN.md "Rust2 triangles").
 #include "rtw_tri.h"
 #include "rtw_mesh.h"
+#include "rtw_occl.h"
 #include "rtw_refit.h"
 #include <algorithm>
 #include <cmath>
@@ -402,6 +403,56 @@ int rtw_mesh_instance_hits_tree(const RtwTriangle *tris, uint32_t n_tris, const 
         }
     }
     if (stats) { std::memset(stats, 0, sizeof *stats); stats->quad_tests = tests; stats->node_tests = visits; }
+    return RTW_OK;
+}
+
+// The any-hit host forms (rtw_occl.h): the triangle and the placement group of rtw_ctx_scene_occluded's kernel, the same source,
+// under the views a context forms with RTW_ACCEL_BVH (and RTW_OPT_MESH_LIST_MAX = 0): the trees where the device would take them, else the lists
+int rtw_triangle_occluded(const RtwTriangle *tris, uint32_t n, const float *rays, uint32_t n_rays, float mint, float maxt, uint8_t *occluded_out,
+                          RtwStats *stats) {
+    if ((n && !tris) || !rays || !occluded_out || n_rays == 0) return RTW_E_INVALID;
+    std::vector<DevTri> list;
+    try { list.resize(n); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+    tri_prepare(tris, n, list.data());
+    TriBuild tree;
+    if (n && !tri_build(list.data(), n, tree)) return RTW_E_NOMEM;
+    DevTris T{};
+    T.list = list.data(); T.leaf = tree.leaf; T.n = n; T.n_nodes = tree.n_nodes;
+    T.t_bound = std::fmax(std::fabs(mint), std::fabs(maxt));
+    const bool range_ok = std::isfinite(mint) && std::isfinite(maxt) && T.t_bound <= RTW_TRI_COORD_MAX;
+    T.nodes = (n && !tree.list_walk && range_ok) ? tree.nodes : nullptr;
+    unsigned long long tests = 0, visits = 0;
+    for (uint32_t i = 0; i < n_rays; i++) {
+        const float *r = rays + 6 * (size_t)i;
+        uint32_t n_tests = 0, n_nodes = 0;
+        occluded_out[i] = tri_any(T, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), mint, maxt, true, n_tests, n_nodes) ? 1 : 0;
+        tests += n_tests; visits += n_nodes;
+    }
+    if (stats) { std::memset(stats, 0, sizeof *stats); stats->segments = n_rays; stats->quad_tests = tests; stats->node_tests = visits; }
+    return RTW_OK;
+}
+
+int rtw_mesh_instance_occluded(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *p, uint32_t n, const float *rays, uint32_t n_rays,
+                               float mint, float maxt, uint8_t *occluded_out, RtwStats *stats) {
+    if (!rays || !occluded_out || n_rays == 0 || n == 0) return RTW_E_INVALID;
+    HostMesh m;
+    if (const int rc = host_mesh(tris, n_tris, p, n, m)) return rc;
+    try { m.packed = m.top.packed(); } catch (const std::bad_alloc &) { return RTW_E_NOMEM; }
+    DevTris T{};                                                   // (the views of rtw_mesh_instance_hits_tree)
+    T.list = m.list.data(); T.leaf = m.tree.leaf; T.n = n_tris; T.n_nodes = m.tree.n_nodes;
+    T.t_bound = std::fmax(std::fabs(mint), std::fabs(maxt));
+    const bool range_ok = std::isfinite(mint) && std::isfinite(maxt) && T.t_bound <= RTW_TRI_COORD_MAX;
+    T.nodes = (!m.tree.list_walk && range_ok) ? m.tree.nodes : nullptr;
+    const TriNode *top = (T.nodes != nullptr && !m.top.list_walk) ? (const TriNode *)m.packed.data() : nullptr;
+    const uint32_t n_top = (uint32_t)m.top.nodes.size();
+    unsigned long long tests = 0, visits = 0;
+    for (uint32_t i = 0; i < n_rays; i++) {
+        const float *r = rays + 6 * (size_t)i;
+        uint32_t n_tests = 0, n_nodes = 0;
+        occluded_out[i] = mesh_any(T, m.rows.data(), n, top, n_top, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), mint, maxt, true, n_tests, n_nodes) ? 1 : 0;
+        tests += n_tests; visits += n_nodes;
+    }
+    if (stats) { std::memset(stats, 0, sizeof *stats); stats->segments = n_rays; stats->quad_tests = tests; stats->node_tests = visits; }
     return RTW_OK;
 }
 
