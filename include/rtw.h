@@ -980,7 +980,8 @@ int rtw_bvh_dump(const RtwScene *scene, float t_begin, float t_end, void *nodes,
 /* The f32 plane format of those f16 nodes, as the large-workgroup builds of the render kernel hold a tree in LDS (RTW_OPT_NODE_FORMAT): every
  * plane widened exactly, laid out so that a ray reads {near, far} of a (box, axis) at a per-ray offset.  out: n_nodes * layout[0] dwords (may
  * be NULL: layout only); layout[4] = dwords per node, dwords per (box, axis) group, the byte offset at which a ray along +axis reads its
- * pair (a ray along -axis reads at 0), the code of an inner child per node index.  A testing tool, no GPU. */
+ * pair (a ray along -axis reads at 0), the code of an inner child per node index.  After the six groups: the dword {c0, c1} of 16-bit child codes
+ * at both read offsets of the x group, each followed by the same two codes swapped, {c1, c0}.  A testing tool, no GPU. */
 int rtw_bvh_pack_nodes32(const uint16_t *nodes16, uint32_t n_nodes, uint32_t *out, uint32_t out_cap, uint32_t *layout);
 /* Host twin of the render kernel's closest-hit query over that tree (a measuring and testing tool, no GPU): rays = n x {origin[3],
  * direction[3]}; hit[i] = sphere index or -1, t[i] its parameter, visits[i] (optional) the inner-node visits, counted as

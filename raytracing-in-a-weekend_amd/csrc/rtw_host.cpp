@@ -942,6 +942,10 @@ void pack_nodes32(const std::vector<BvhNode16> &nodes16, std::vector<uint32_t> &
         }
         const uint32_t cc = code(a.c0) | (code(a.c1) << 16);
         d[6u * AX] = cc; d[6u * AX + RTW_NODE32_OFF / 4u] = cc;          // (read at plane offset 6 * AX + the ray's x offset, 0 or RTW_NODE32_OFF)
+        // ... each followed by the same two codes the other way round, {c1, c0}: the visit reads both orders with one 8-byte read and
+        // SELECTS the one whose low half is the nearer child, where it used to rotate the one dword
+        const uint32_t sw = (cc >> 16) | (cc << 16);
+        d[6u * AX + 1u] = sw; d[6u * AX + RTW_NODE32_OFF / 4u + 1u] = sw;
     }
 }
 

@@ -44,7 +44,8 @@ static_assert(sizeof(BvhNode16) == 32, "BvhNode16 must be 32 bytes");
 // RTW_NODE32_DWORDS (28) dwords per node: per (box, axis), in BvhNode16's order, a group of four planes {hi, lo, lo, hi} -- a pair read
 // RTW_NODE32_OFF (8) bytes into the group is {lo, hi} (a ray along +axis), one read at its start {hi, lo} (along -axis); either read is
 // 8-byte aligned (pairs at 4-byte alignment, out of {hi, lo, hi}, were measured ruinous: profiles/f32_planes_ab.log) -- then the dword
-// {c0, c1} of 16-bit child codes at dwords 24 and 26, where a read at either per-ray offset finds it, so that it needs no address of its own.
+// {c0, c1} of 16-bit child codes at dwords 24 and 26, where a read at either per-ray offset finds it, so that it needs no address of its own,
+// each followed (dwords 25 and 27) by the same two codes swapped, {c1, c0}: one 8-byte read hands the visit the pair in both orders.
 // A leaf's code is BvhNode16's (~sphere); an inner child is named by its LDS offset in units of 8 bytes (1 << RTW_NODE32_UNIT_SHIFT):
 // index * RTW_NODE32_CODE.  In bytes, as the f16 format names them, the last of Book-1's 480 nodes (53648) would not fit below the END /
 // DEAD codes 0x7FFF / 0x7FFE of the 16-bit stack entries; in these units every tree with f16 nodes does (511 * 14 = 7154).

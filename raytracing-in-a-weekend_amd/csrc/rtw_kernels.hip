@@ -865,6 +865,34 @@ __device__ __forceinline__ void exact_sphere(f4 g, f4 vv, uint32_t s, v3 o, v3 d
                                    lose 0.6 %, C2 gains 1.6 %, `First frame` 5 %, an eighth of the bench frame nothing (profiles/r02_drain_ab.log) */
 #endif
 
+#ifndef RTW_CHAIN
+#define RTW_CHAIN 33u           /* lanes in TRAVERSE from which bursts follow one another without a trip through the scheduler */
+#endif
+// The scheduler's constants as a build of render_bvh sees them.  The values above were tuned on the f16 walk in 256-thread workgroups at
+// seven waves per SIMD and stay what every such build runs; the 768-thread builds (f32 planes, six waves per SIMD, a cheaper visit) have a
+// set of their own, swept on the bench frame one at a time (profiles/visit_class_sched_sweep.log).  Scheduling decides WHEN a lane's
+// steps run, never what they compute: every set renders the same frame.
+#ifndef RTW_S_HI_LARGE
+#define RTW_S_HI_LARGE RTW_S_HI /* 44 / 48 / 52 / 56 / 60 = 68.03 / 67.42 / 67.36 / 67.94 / 68.60 ms of the bench frame */
+#endif
+#ifndef RTW_T_LO_LARGE
+#define RTW_T_LO_LARGE 8u       /* 4 / 6 / 8 = 67.16 / 67.36 / 67.17 ms of the bench frame beside chain 33; 8 beside chain 21 and 17: -0.18 and -0.17 ms */
+#endif
+#ifndef RTW_TRAV_UNROLL_LARGE
+#define RTW_TRAV_UNROLL_LARGE RTW_TRAV_UNROLL   /* 2 / 3 / 4 = 69.68 / 67.36 / 68.77 ms */
+#endif
+#ifndef RTW_CHAIN_LARGE
+#define RTW_CHAIN_LARGE 13u     /* 37 / 33 / 29 / 25 / 21 / 17 / 13 = 67.60 / 67.36 / 67.15 / 66.85 / 66.68 / 66.43 / 66.33 ms: bursts follow one another while 13 lanes
+                                   still traverse, so LEAF waits for fuller steps (0.52 -> 0.58 of its lanes live, 10 % fewer of them) and a wave asks the scheduler less often; TRAVERSE
+                                   takes 4 % more steps, each without the scheduler's three ballots and the copies at its joins.  13 is the lowest threshold at which
+                                   SHADE cannot be due meanwhile (64 - 13 < S_HI) */
+#endif
+struct Sched { uint32_t s_hi, t_lo, t_lo_drain; int burst; uint32_t chain; };
+constexpr Sched sched_of(uint32_t block) {
+    return block == RTW_BLOCK_LARGE ? Sched{ RTW_S_HI_LARGE, RTW_T_LO_LARGE, RTW_T_LO_LARGE, RTW_TRAV_UNROLL_LARGE, RTW_CHAIN_LARGE }
+                                    : Sched{ RTW_S_HI, RTW_T_LO, RTW_T_LO_DRAIN, RTW_TRAV_UNROLL, RTW_CHAIN };
+}
+
 struct Trav {                // traversal state of one lane
     int node;                // the lane's PHASE is encoded here: 0 <= node < DEAD an inner node to visit (TRAVERSE; LDS variant: its byte offset);
                              // above END (as unsigned) the leaf ~node to test (LEAF; LDS variant: 16-bit codes, zero-extended);
@@ -1054,7 +1082,11 @@ __device__ __forceinline__ void trav_descend(Trav &tr, float e0, float x0, float
         // select(a && b, ..) becomes two nested v_cndmask.
         const uint64_t H0 = __builtin_amdgcn_ballot_w64(h0), H1 = __builtin_amdgcn_ballot_w64(h1), LE = __builtin_amdgcn_ballot_w64(le);
         const bool far0 = __builtin_amdgcn_inverse_ballot_w64(~H0 | (H1 & ~LE));
-        const uint32_t nf = __builtin_amdgcn_alignbit(c0, c0, far0 ? 16u : 0u);
+        // The f32 plane format stores the pair in BOTH orders (c1 = {c1, c0}, rtw_host.h): there the select picks the order itself and
+        // the v_alignbit, an instruction of the slow class (profiles/r01_ubench_valu_mix.txt), goes.
+        uint32_t nf;
+        if constexpr (BLOCK != RTW_BLOCK) nf = far0 ? c1 : c0;
+        else nf = __builtin_amdgcn_alignbit(c0, c0, far0 ? 16u : 0u);
         lds_put<unsigned short>(tr.sp + level, (unsigned short)(nf >> 16));
         tr.node = entry_to_node<S>(none ? popped : nf);
     } else {
@@ -1119,7 +1151,8 @@ __device__ __forceinline__ void trav_node_lds32(Trav &tr) {
                    az = ((uint32_t)tr.node << RTW_NODE32_UNIT_SHIFT) + tr.selz;
     const f2a px0 = lds_get_pair(ax), py0 = lds_get_pair(ay + G), pz0 = lds_get_pair(az + 2u * G);
     const f2a px1 = lds_get_pair(ax + 3u * G), py1 = lds_get_pair(ay + 4u * G), pz1 = lds_get_pair(az + 5u * G);
-    const uint32_t c0 = lds_get<uint32_t>(ax + 6u * G), c1 = 0;       // {c0, c1}: stored at both x offsets
+    const f2a cc = lds_get_pair(ax + 6u * G);                         // {c0, c1} and {c1, c0}: stored at both x offsets
+    const uint32_t c0 = __float_as_uint(cc.x), c1 = __float_as_uint(cc.y);
     const float e0 = fmaxf(fmaxf(__builtin_fmaf(px0.x, tr.ix, tr.kpx), __builtin_fmaf(py0.x, tr.iy, tr.kpy)), __builtin_fmaf(pz0.x, tr.iz, tr.kpz));
     const float x0 = fminf(fminf(__builtin_fmaf(px0.y, tr.ix, tr.kmx), __builtin_fmaf(py0.y, tr.iy, tr.kmy)), __builtin_fmaf(pz0.y, tr.iz, tr.kmz));
     const float e1 = fmaxf(fmaxf(__builtin_fmaf(px1.x, tr.ix, tr.kpx), __builtin_fmaf(py1.x, tr.iy, tr.kpy)), __builtin_fmaf(pz1.x, tr.iz, tr.kpz));
@@ -1219,6 +1252,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
     constexpr bool LDSN = NODES != 0, geom_in_lds = NODES == 2;
     constexpr uint32_t BLOCK = bvh_block(MOVING, NODES, SPEC, GEOM);
     constexpr bool F32 = BLOCK != RTW_BLOCK;         // the large-workgroup builds walk the f32 plane format, and that alone
+    constexpr Sched SC = sched_of(BLOCK);            // the scheduler's thresholds, burst length and chain threshold of this build
     // LDS is all dynamic, sized by the host for THIS tree (rtw_host.h, render_lds_layout): -- LDS-node variants -- the f16 nodes at
     // offset 0, then the per-lane traversal stack [level][thread] (a level is one conflict-free row; depth + 3 levels: the sentinel,
     // one per tree level, and the slot above the top that the select-form descend always writes; 16-bit entries in the LDS-node
@@ -1264,7 +1298,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
     // lanes live in TRAVERSE steps, leaf tests == lanes live in LEAF steps), which keeps four VGPRs out of the loop.
     // (32-bit: one wave's share of a launch -- at most 2^32 sample slots per launch, rtw_ctx_render -- stays far below 2^32)
     uint32_t w_seg = 0, w_rays = 0;
-    uint32_t t_lo = RTW_T_LO;                       // wave-uniform: drops to RTW_T_LO_DRAIN once the queue is empty
+    uint32_t t_lo = SC.t_lo;                        // wave-uniform: drops to RTW_T_LO_DRAIN once the queue is empty
     uint32_t trips = 0; bool aborted = false;       // wave-uniform
     bool a_plain = true;                            // wave-uniform, sticky (trav_begin)
     uint32_t n_isph = 0, n_quad = 0;                // GEOM builds only: member-sphere and quad tests of the extra stage
@@ -1300,7 +1334,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
         // wave) gives up instead of hanging the GPU; the launch then reports RTW_E_INTERNAL (stats[23] counts such waves).
         if (++trips > RTW_MAX_TRIPS) { aborted = true; break; }
         RTW_CEN(cn, CEN_BIG_ROOT);                 // (census build: trips through the scheduler)
-        const bool run_shade = nS >= RTW_S_HI || (nT < t_lo && nL < t_lo && nS > 0u);
+        const bool run_shade = nS >= SC.s_hi || (nT < t_lo && nL < t_lo && nS > 0u);
         const bool run_leaf = nL > nT;
 #ifdef RTW_ENDTIMES
         if (rs.t_dry) {
@@ -1359,7 +1393,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
             // b. next work unit (every lane of the wave: the reserve stays wave-uniform; see the generic path below)
             bool exhausted = false;
             const bool got = fetch_pixel(A, need_unit, px, exhausted, rs);
-            if (ballot64(exhausted) != 0ull) t_lo = RTW_T_LO_DRAIN;
+            if (ballot64(exhausted) != 0ull) t_lo = SC.t_lo_drain;
             RTW_SUB_STAMP(1);
             if (shading) {
                 if (got) fl |= F_HAVE | F_NEWPATH;
@@ -1408,7 +1442,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
             // "few lanes traverse" rule alone -- after finding the queue empty a wave runs on for 0.38 ms on average and 1.2 ms at most
             // (profiles/r02_endtimes.log).  The threshold of that rule can differ while draining (RTW_T_LO_DRAIN; measured, not better).
             // (HERE, where every lane of the wave is active: t_lo steers the scheduler and must stay wave-uniform.)
-            if (ballot64(exhausted) != 0ull) t_lo = RTW_T_LO_DRAIN;
+            if (ballot64(exhausted) != 0ull) t_lo = SC.t_lo_drain;
             RTW_SUB_STAMP(1);
 #ifdef RTW_STAMP
             if (shading) {
@@ -1444,7 +1478,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
             // has left [2^-20, 2^20] the wave stays on the generic sqrt / division (same bits, a few more instructions) for good.
             if (ballot64(a_odd) != 0ull) a_plain = false;
 #ifndef RTW_STAMP
-            nT = lanes_in(in_trav<stack_t>(tr.node)); burst = nT >= 33u;      // (as after a LEAF step)
+            nT = lanes_in(in_trav<stack_t>(tr.node)); burst = nT >= SC.chain;      // (as after a LEAF step)
 #endif
         } else {
             burst = !run_leaf;
@@ -1460,7 +1494,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
 #ifndef RTW_STAMP
                 // straight on to the bursts, without asking the scheduler, when more than half of the lanes are in TRAVERSE after the pops
                 // (the same shortcut, and the same argument, as between bursts)
-                nT = lanes_in(in_trav<stack_t>(tr.node)); burst = nT >= 33u;
+                nT = lanes_in(in_trav<stack_t>(tr.node)); burst = nT >= SC.chain;
 #endif
             }
         }
@@ -1471,19 +1505,22 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
             // 33 or more lanes there, LEAF and SHADE hold at most 31 between them, so neither "nL > nT" nor "nS >= RTW_S_HI" (52) can be true
             // and the scheduler would say TRAVERSE again -- the same decisions from one ballot instead of three, and without the register
             // copies the compiler puts at the joins of the three-way branch for state that only LEAF and SHADE change (~16 v_mov per burst).
-            static_assert(RTW_S_HI > 31u && RTW_T_LO <= 33u, "the shortcut below assumes the thresholds of the scheduler");
+            // The 768-thread builds chain from 13 lanes on (SC.chain, swept: profiles/visit_class_sched_sweep.log): below 33 the bursts also go on where
+            // the scheduler would have said LEAF ("nL > nT"), never where it would have said SHADE (the assertion below) -- a different WHEN for the
+            // leaf tests, the same frame.
+            static_assert(SC.s_hi > 64u - SC.chain && SC.t_lo <= SC.chain, "the shortcut below assumes the thresholds of the scheduler");
             uint32_t live = nT;
             for (;;) {
                 // (the burst's census is summed in two scalars of its own and added once: kept in c_steps / c_lanes directly, the register
                 // allocator -- out of SGPRs in this kernel -- holds the totals in VGPRs and every visit paid a v_add for each)
                 uint32_t b_steps = 0, b_lanes = 0;
-                for (int u = 0; u < RTW_TRAV_UNROLL; u++) {
+                for (int u = 0; u < SC.burst; u++) {
                     b_steps++; b_lanes += live;
                     if (in_trav<stack_t>(tr.node)) {
                         if constexpr (F32) trav_node_lds32<BLOCK>(tr);
                         else if (LDSN) trav_node_lds((const u4 *)lnodes, tr); else trav_node(A.bvh, tr);
                     }
-                    if (u + 1 >= RTW_TRAV_UNROLL) break;
+                    if (u + 1 >= SC.burst) break;
                     live = lanes_in(in_trav<stack_t>(tr.node));
                     if (live == 0u) break;
                 }
@@ -1494,7 +1531,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
 #else
                 if (live == 0u) break;
                 live = lanes_in(in_trav<stack_t>(tr.node));
-                if (live < 33u) break;
+                if (live < SC.chain) break;
                 if (++trips > RTW_MAX_TRIPS) break;          // (the outer loop's valve fires on its next trip)
 #endif
             }
