@@ -332,6 +332,25 @@ int  rtw_ctx_last_render_build(rtw_ctx *ctx, char *buf, size_t n);
 /* ... and the format of the tree that build read from LDS: 0 none (list walk, or nodes in global memory), 1 f16 nodes, 2 f32 planes
  * (RTW_OPT_NODE_FORMAT).  Host only.  RTW_E_INVALID before the context's first render.  (added within v4) */
 int  rtw_ctx_last_node_format(rtw_ctx *ctx);
+/* ... and the work queue that render handed to its kernel, one record per band of tile rows, as launched: the band's compact
+ * rows [k_base, k_end) and tiles, the samples per pixel and how they are cut into units (chunk_len, n_chunks: the first region's; bank_len 1:
+ * one bank slot per unit, RTW_FLAG_CHUNK_SUMS), the three regions of unit length over the queue positions [0, reg_q1), [reg_q1, reg_q2),
+ * [reg_q2, n_tiles) with reg_len[r] samples per unit and reg_nc[r] units per pixel, total_work = 64 items per (tile, unit), 2^sub_shift
+ * sub-queues, the guided grab (grab_shift, grab_max items), the grid and the threads per workgroup, whether a tile order was handed over
+ * (0 / 1), and the row partition.  bands: how many bands the render had (the same in every record).  Host only: no device work; a copy of
+ * what was launched, nothing is computed again.  RTW_E_INVALID for a NULL pointer, before the context's first render, and for
+ * band >= bands; a render that is refused leaves the records of the last one that was launched.  For tests and diagnostics: how a render
+ * is cut into work is not part of the contract.  (added within v4) */
+typedef struct RtwQueuePlan {
+    uint32_t bands, n_tiles, tiles_x, k_base, k_end;
+    uint32_t n_samples, chunk_len, n_chunks, bank_len;
+    uint32_t reg_q1, reg_q2, reg_len[3], reg_nc[3], total_work;
+    uint32_t sub_shift, grab_shift, grab_max;
+    uint32_t grid, block;
+    uint32_t has_tile_order;
+    uint32_t row_block, part_index, part_count;
+} RtwQueuePlan;
+int  rtw_ctx_last_queue_plan(rtw_ctx *ctx, uint32_t band, RtwQueuePlan *out);
 /* Host only (no context, no GPU), for tests and diagnostics: the build and the dynamic LDS layout a render would launch, from plain facts
  * -- the same functions the render itself calls, once each.  RtwRenderFacts: what the request needs -- the integrator, sampler, depth and
  * flags of RtwParams (RTW_FLAG_MIXED_MATERIAL only where the scene holds a MixedMaterial object), whether a sphere has an image texture,

@@ -191,6 +191,18 @@ class RtwRenderChoice(C.Structure):
     _fields_ = [("build", C.c_char * 32)] + [(k, C.c_uint32) for k in ("node_format", "block", "lds_stack_off", "lds_geom_off", "lds_tri_off", "lds_bytes")]
 
 
+class RtwQueuePlan(C.Structure):
+    """The work queue of one band of a render as its launch was handed it (include/rtw.h rtw_ctx_last_queue_plan)."""
+    _fields_ = ([(k, C.c_uint32) for k in ("bands", "n_tiles", "tiles_x", "k_base", "k_end", "n_samples", "chunk_len", "n_chunks", "bank_len",
+                                           "reg_q1", "reg_q2")]
+                + [("reg_len", C.c_uint32 * 3), ("reg_nc", C.c_uint32 * 3)]
+                + [(k, C.c_uint32) for k in ("total_work", "sub_shift", "grab_shift", "grab_max", "grid", "block", "has_tile_order",
+                                             "row_block", "part_index", "part_count")])
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k in ("reg_len", "reg_nc") else int(getattr(self, k))) for k, _ in self._fields_}
+
+
 # rtw_ctx_device_math's functions and rtw_ctx_device_sweep's sweeps (include/rtw.h "device math, for tests")
 (MATH_SQRT_PLAIN, MATH_SQRT_IEEE, MATH_DIV, MATH_UNIT, MATH_UNIT_BALL, MATH_SPHERE_ROOT, MATH_ATAN2, MATH_ACOS, MATH_SPHERE_UV, MATH_LN, MATH_POW,
  MATH_SINCOS, MATH_EXP) = range(13)
@@ -244,6 +256,7 @@ def lib() -> C.CDLL:
     L.rtw_ctx_set_option.argtypes = [C.c_void_p, C.c_uint32, C.c_double]
     L.rtw_ctx_last_render_build.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.rtw_ctx_last_node_format.argtypes = [C.c_void_p]
+    L.rtw_ctx_last_queue_plan.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtwQueuePlan)]
     if hasattr(L, "rtw_render_choice"):     # (added within v4: an RTW_HIP_LIB build of the same ABI may predate it)
         L.rtw_render_choice.argtypes = [C.POINTER(RtwRenderFacts), C.POINTER(RtwTreeFacts), C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32,
                                         C.POINTER(RtwRenderChoice)]
@@ -1562,6 +1575,17 @@ class Renderer:
         if rc < 0:
             _check(rc, "rtw_ctx_last_node_format")
         return rc
+
+    def last_queue_plan(self, band: int = 0) -> dict:
+        """The work queue the last render handed to its kernel for band `band` (rtw_ctx_last_queue_plan), field by field as RtwQueuePlan;
+        reg_len / reg_nc are lists of three.  Raises RtwError before the first render and for band >= last_queue_bands()."""
+        q = RtwQueuePlan()
+        _check(lib().rtw_ctx_last_queue_plan(self._h, int(band), C.byref(q)), "rtw_ctx_last_queue_plan")
+        return q.as_dict()
+
+    def last_queue_bands(self) -> int:
+        """How many bands of tile rows the last render was launched in.  Raises RtwError before the first render."""
+        return self.last_queue_plan(0)["bands"]
 
     def bilateral_filter(self, img, size: int, proximity: int = PROXIMITY_SQUARE, avg_gradient: float = 0.0, out=None, shape=None,
                          in_format: Optional[int] = None):

@@ -147,6 +147,7 @@ struct rtw_ctx {
     RenderBuild last_build{};            // the render kernel the last launch ran (rtw_ctx_last_render_build); every band of a render runs the same one
     bool has_last_build = false;
     uint32_t last_node_format = 0;       // ... and the LDS node format it read (rtw_ctx_last_node_format)
+    std::vector<RtwQueuePlan> last_plans;   // ... and the work queue of each of its bands as launched (rtw_ctx_last_queue_plan)
     // cache of a per-call driver query (tens of microseconds: visible on small frames)
     std::map<const void *, uint32_t> lds_allowed;        // kernel -> the largest dynamic LDS it has been allowed beyond 64 KiB
     std::map<std::pair<const void *, uint32_t>, uint32_t> occupancy;    // (kernel, dynamic LDS bytes) -> resident workgroups per CU
@@ -1329,6 +1330,22 @@ static RenderChoice render_choice(const RtwRenderFacts &f, const RtwTreeFacts &t
     return RenderChoice{ build, lds, fn && render_block(build) == lds.block ? fn : nullptr };
 }
 
+// The work queue of one band as its launch was handed it (rtw_ctx_last_queue_plan): copies of KArgs' fields, nothing computed again.
+static RtwQueuePlan queue_plan(const KArgs &a, uint32_t grid, uint32_t block) {
+    RtwQueuePlan q;
+    std::memset(&q, 0, sizeof q);
+    q.n_tiles = a.n_tiles; q.tiles_x = a.tiles_x; q.k_base = a.k_base; q.k_end = a.k_end;
+    q.n_samples = a.n_samples; q.chunk_len = a.chunk_len; q.n_chunks = a.n_chunks; q.bank_len = a.bank_len;
+    q.reg_q1 = a.reg_q1; q.reg_q2 = a.reg_q2;
+    for (int r = 0; r < 3; r++) { q.reg_len[r] = a.reg_len[r]; q.reg_nc[r] = a.reg_nc[r]; }
+    q.total_work = a.total_work;
+    q.sub_shift = a.sub_shift; q.grab_shift = a.grab_shift; q.grab_max = a.grab_max;
+    q.grid = grid; q.block = block;
+    q.has_tile_order = a.tile_order ? 1u : 0u;
+    q.row_block = a.row_block; q.part_index = a.part_index; q.part_count = a.part_count;
+    return q;
+}
+
 static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams *p, OutSpec out, unsigned phases) {
     if (!c || !cam || !p || !out.base) return RTW_E_INVALID;
     if (c->pend.active) return RTW_E_INVALID;
@@ -1520,6 +1537,7 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
     HIP_TRY(hipMemsetAsync(a.stats + 28, 0xFF, sizeof(unsigned long long), c->stream));
 #endif
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    std::vector<RtwQueuePlan> plans;                   // what each band's launch is handed (rtw_ctx_last_queue_plan): kept once all are issued
     for (uint32_t tr0 = 0; tr0 < tile_rows || tr0 == 0; tr0 += (uint32_t)band_tile_rows) {
         const uint32_t tr1 = tr0 + (uint32_t)band_tile_rows < tile_rows ? tr0 + (uint32_t)band_tile_rows : tile_rows;
         a.k_base = tr0 * 8; a.k_end = tr1 * 8 < n_rows ? tr1 * 8 : n_rows;
@@ -1603,8 +1621,11 @@ static int render_enqueue_impl(rtw_ctx *c, const RtwCamera *cam, const RtwParams
         HIP_TRY(hipMemsetAsync(a.queue, 0, RTW_QUEUE_BYTES, c->stream));
         if (a.n_tiles) { launch_render(fn, block, a, grid, c->stream); c->last_build = build; c->has_last_build = true; c->last_node_format = lds.node_format; }
         HIP_TRY(hipGetLastError());
+        if (a.n_tiles) plans.push_back(queue_plan(a, grid, block));
         if (tile_rows == 0) break;
     }
+    for (RtwQueuePlan &q : plans) q.bands = (uint32_t)plans.size();
+    c->last_plans.swap(plans);
     HIP_TRY(hipEventRecord(c->ev1, c->stream));
     HIP_TRY(hipMemcpyAsync(c->scr.h_stats.ptr, a.stats, RTW_N_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     c->pend.active = true; c->pend.n_rows = n_rows;
@@ -1732,6 +1753,13 @@ int rtw_render_choice(const RtwRenderFacts *f, const RtwTreeFacts *t, int32_t op
 int rtw_ctx_last_node_format(rtw_ctx *c) {
     if (!c || !c->has_last_build) return RTW_E_INVALID;
     return (int)c->last_node_format;
+}
+
+// Host only: the work queue of band `band` of the last render, as launched.
+int rtw_ctx_last_queue_plan(rtw_ctx *c, uint32_t band, RtwQueuePlan *out) {
+    if (!c || !out || band >= c->last_plans.size()) return RTW_E_INVALID;
+    *out = c->last_plans[band];
+    return RTW_OK;
 }
 
 uint32_t rtw_mesh_list_max_default(void) { return RTW_MESH_LIST_MAX_DEFAULT; }

@@ -12,6 +12,7 @@ from tests import oracle_binding as O
 from tests.test_oracle_golden import small_view, flag_params, GOLD
 from tests import builds_common as B
 from tests.test_abi_and_host import geometric_scene
+from tests.queue_common import poison
 
 pytestmark = pytest.mark.gpu
 
@@ -325,7 +326,8 @@ def test_example_program_multi_gpu_entry(gpu, tmp_path):
 @pytest.mark.parametrize("mode", [0, 1, 2, 3, 4])
 def test_tile_order_never_changes_the_image(rtw, mode):
     """RTW_OPT_TILE_ORDER only permutes the work queue: frames, row partitions (whose tiles map to other image rows) and banded
-    renders are bit-identical under every order."""
+    renders are bit-identical under every order.  Every compared render follows a poison render (tests/queue_common.py): the bank and the
+    output buffer are not cleared between renders, and a dropped unit would otherwise find the previous render's right value in place."""
     scene, cam, p = small_view(R.SCENE_C2, 200, 120, 6)
     p.gamma = 1.0
     ref, st_ref = O.render(cam, scene, p, threads=16)
@@ -334,14 +336,17 @@ def test_tile_order_never_changes_the_image(rtw, mode):
         r.set_option(R.OPT_TILE_ORDER, mode)
         for accel in (R.ACCEL_BVH, R.ACCEL_BRUTE):
             p.accel = accel
+            poison(r, cam, p)
             img, st = r.render(cam, p)
             assert st.segments == st_ref.segments and np.array_equal(img, ref), (mode, accel)
         p.accel = R.ACCEL_BVH
         r.set_option(R.OPT_SAMPLE_BANK_GB, 0.004)                 # several bands of tile rows
+        poison(r, cam, p)
         img, _ = r.render(cam, p)
         assert np.array_equal(img, ref)
         r.set_option(R.OPT_SAMPLE_BANK_GB, 48)
         p.row_block, p.part_index, p.part_count = 8, 2, 3
+        poison(r, cam, p)
         part, _ = r.render(cam, p)
         rows = [j for j in range(120) if (j // 8) % 3 == 2]
         assert np.array_equal(part, ref[rows])
@@ -408,7 +413,8 @@ def test_sphere_tests_outside_the_plain_range(gpu, log2_scale):
 def test_grab_size_never_changes_the_image(rtw, blocks):
     """RTW_OPT_GRAB_BLOCKS only changes how many 64-unit blocks a wave takes from the work queue per atomic (0: up to a tile's worth):
     full frames, banded renders and row partitions are bit-identical, with both kernels, for a frame large enough that the guided rule
-    really hands out several blocks at a time, and every unit is rendered exactly once (camera-ray count)."""
+    really hands out several blocks at a time, and every unit is rendered exactly once (camera-ray count).  Every compared render follows a
+    poison render -- same frame and options, another seed --, so that nothing of the reference render is left in the bank to be read again."""
     scene, cam, p = small_view(R.SCENE_C2, 320, 184, 40)
     p.gamma, p.depth = 1.0, 6
     with rtw.Renderer(0) as r:
@@ -419,14 +425,17 @@ def test_grab_size_never_changes_the_image(rtw, blocks):
         r.set_option(R.OPT_GRAB_BLOCKS, blocks)
         for accel in (R.ACCEL_BVH, R.ACCEL_BRUTE):
             p.accel = accel
+            poison(r, cam, p)
             img, st = r.render(cam, p)
             assert st.camera_rays == 320 * 184 * 40 and st.segments == st_ref.segments and np.array_equal(img, ref), (blocks, accel)
         p.accel = R.ACCEL_BVH
         r.set_option(R.OPT_SAMPLE_BANK_GB, 0.01)                  # several bands of tile rows
+        poison(r, cam, p)
         img, _ = r.render(cam, p)
         assert np.array_equal(img, ref)
         r.set_option(R.OPT_SAMPLE_BANK_GB, 48)
         p.row_block, p.part_index, p.part_count = 8, 1, 3
+        poison(r, cam, p)
         part, _ = r.render(cam, p)
         rows = [j for j in range(184) if (j // 8) % 3 == 1]
         assert np.array_equal(part, ref[rows])

@@ -10,6 +10,7 @@ import pytest
 import rtw_amd as R
 from tests import oracle_binding as O
 from tests.test_oracle_golden import small_view
+from tests.queue_common import poison
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -147,7 +148,8 @@ def test_second_hip_runtime_is_refused_loudly(gpu):
 def test_guided_unit_lengths_never_change_the_image(rtw, k):
     """RTW_OPT_TAIL_UNITS cuts the last tiles of the queue into units of one sample and the ones before into shorter units than the rest; the
     bank is indexed by (tile, sample, pixel) and the resolve adds in sample order, so full frames, banded renders, row partitions, a permuted
-    tile order and both kernels give the same bits, and every sample is traced exactly once."""
+    tile order and both kernels give the same bits, and every sample is traced exactly once.  Every compared render follows a poison render
+    (tests/queue_common.py): a sample that no unit banks must not find the reference render's value in its slot."""
     scene, cam, p = small_view(R.SCENE_C2, 320, 184, 40)
     p.gamma, p.depth = 1.0, 6
     with rtw.Renderer(0) as r:
@@ -159,19 +161,23 @@ def test_guided_unit_lengths_never_change_the_image(rtw, k):
             r.set_option(R.OPT_CHUNK_LEN, chunk)
             for accel in (R.ACCEL_BVH, R.ACCEL_BRUTE):
                 p.accel = accel
+                poison(r, cam, p)
                 img, st = r.render(cam, p)
                 assert st.camera_rays == 320 * 184 * 40 and st.segments == st_ref.segments and np.array_equal(img, ref), (k, chunk, accel)
         p.accel = R.ACCEL_BVH
         for order in (2, 5):
             r.set_option(R.OPT_TILE_ORDER, order)
+            poison(r, cam, p)
             img, _ = r.render(cam, p)
             assert np.array_equal(img, ref), order
         r.set_option(R.OPT_TILE_ORDER, 0)
         r.set_option(R.OPT_SAMPLE_BANK_GB, 0.01)                      # several bands of tile rows, each with its own regions
+        poison(r, cam, p)
         img, _ = r.render(cam, p)
         assert np.array_equal(img, ref)
         r.set_option(R.OPT_SAMPLE_BANK_GB, 48)
         p.row_block, p.part_index, p.part_count = 8, 1, 3
+        poison(r, cam, p)
         part, _ = r.render(cam, p)
         rows = [j for j in range(184) if (j // 8) % 3 == 1]
         assert np.array_equal(part, ref[rows])
