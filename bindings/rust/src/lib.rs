@@ -210,6 +210,12 @@ extern "C" {
                           t_out: *mut f32, idx_out: *mut i32, normal_out: *mut f32, stats: *mut RtwStats) -> i32;
     fn rtw_ctx_scene_occluded(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, time: f32, mint: f32, maxt: f32, accel: u32,
                               occluded_out: *mut u8, stats: *mut RtwStats) -> i32;
+    fn rtw_ao_rays(points: *const f32, normals: *const f32, n: u32, samples: u32, seed: u32, rays_out: *mut f32) -> i32;
+    fn rtw_ctx_ambient_occlusion(ctx: *mut RtwCtx, points: *const f32, normals: *const f32, n: u32, samples: u32, seed: u32, time: f32,
+                                 mint: f32, maxt: f32, accel: u32, ao_out: *mut f32, stats: *mut RtwStats) -> i32;
+    fn rtw_ctx_ao_map(ctx: *mut RtwCtx, cam: *const RtwCamera, width: u32, height: u32, time: f32, mint: f32, maxt: f32, samples: u32,
+                      seed: u32, ao_mint: f32, ao_maxt: f32, accel: u32, ao_out: *mut f32, depth_out: *mut f32, idx_out: *mut i32,
+                      normal_out: *mut f32, stats: *mut RtwStats) -> i32;
     fn rtw_ctx_depth_map(ctx: *mut RtwCtx, cam: *const RtwCamera, width: u32, height: u32, time: f32, mint: f32, maxt: f32, accel: u32,
                          depth_out: *mut f32, idx_out: *mut i32, normal_out: *mut f32, stats: *mut RtwStats) -> i32;
     fn rtw_mgpu_render(m: *mut RtwMgpu, cam: *const RtwCamera, p: *const RtwParams, out_rgb: *mut c_void,
@@ -345,6 +351,25 @@ impl Renderer {
         check(unsafe { rtw_ctx_scene_occluded(self.ctx, rays.as_ptr() as *const f32, rays.len() as u32, time, mint, maxt, accel,
                                               o.as_mut_ptr(), std::ptr::null_mut()) })?;
         Ok(o.into_iter().map(|b| b != 0).collect())
+    }
+    /// Ambient occlusion of `points` with `normals`: the share of `samples` cosine-weighted rays about each normal that nothing stops
+    /// within [mint, maxt], made and walked in one kernel.  `samples`: a power of two in 1 ..= 1024.
+    pub fn ambient_occlusion(&mut self, points: &[[f32; 3]], normals: &[[f32; 3]], samples: u32, seed: u32, time: f32, mint: f32, maxt: f32,
+                             accel: u32) -> Result<Vec<f32>, RtwError> {
+        if points.len() != normals.len() { return Err(RtwError(-1)); }
+        let mut ao = vec![0f32; points.len()];
+        check(unsafe { rtw_ctx_ambient_occlusion(self.ctx, points.as_ptr() as *const f32, normals.as_ptr() as *const f32, points.len() as u32,
+                                                 samples, seed, time, mint, maxt, accel, ao.as_mut_ptr(), std::ptr::null_mut()) })?;
+        Ok(ao)
+    }
+    /// `depth_map` and then `ambient_occlusion` of its hit points over [ao_mint, ao_maxt], in two launches: row-major [height][width],
+    /// 1.0 for a miss pixel.
+    pub fn ao_map(&mut self, cam: &RtwCamera, width: u32, height: u32, time: f32, mint: f32, maxt: f32, samples: u32, seed: u32, ao_mint: f32,
+                  ao_maxt: f32, accel: u32) -> Result<Vec<f32>, RtwError> {
+        let mut ao = vec![0f32; width as usize * height as usize];
+        check(unsafe { rtw_ctx_ao_map(self.ctx, cam, width, height, time, mint, maxt, samples, seed, ao_mint, ao_maxt, accel, ao.as_mut_ptr(),
+                                      std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut()) })?;
+        Ok(ao)
     }
     /// Rust2's `Viewport::depth_map` in one launch, for a camera of `rtw_camera2_new`: row-major [height][width] hit.t, maxt * 1.6 on a
     /// miss (row j is row j of the image: the reference's leading empty row is not reproduced).
@@ -579,6 +604,15 @@ pub fn quat_from_euler(euler: [f32; 3]) -> [f32; 4] {
     let mut out = [0f32; 4];
     unsafe { rtw_quat_from_euler(euler.as_ptr(), out.as_mut_ptr()) };
     out
+}
+
+/// The rays of ambient occlusion (host only): `samples` [origin, direction] per point, point-major; six zeros for a skipped point's.
+pub fn ao_rays(points: &[[f32; 3]], normals: &[[f32; 3]], samples: u32, seed: u32) -> Result<Vec<[f32; 6]>, RtwError> {
+    if points.len() != normals.len() || samples == 0 || samples > 1024 { return Err(RtwError(-1)); }
+    let mut r = vec![[0f32; 6]; points.len() * samples as usize];
+    check(unsafe { rtw_ao_rays(points.as_ptr() as *const f32, normals.as_ptr() as *const f32, points.len() as u32, samples, seed,
+                               r.as_mut_ptr() as *mut f32) })?;
+    Ok(r)
 }
 
 /// The rays of Rust2's `Viewport::depth_map` for a camera of `rtw_camera2_new` (host only): [origin, unit direction] per pixel, row-major.

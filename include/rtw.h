@@ -912,7 +912,7 @@ int rtw_mesh_top_refit(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshIn
  * rays ([n_rays][6] = origin, direction) and occluded_out ([n_rays] bytes) may each be host memory or device memory of ctx's GPU (host memory
  * is staged); the work runs on the stream of rtw_ctx_set_stream; blocking.  stats (may be NULL): segments (= n_rays), sphere_tests,
  * node_tests, quad_tests, kernel_ms.  RTW_E_INVALID for a NULL ctx / rays / occluded_out, n_rays == 0 or an unknown accel; RTW_E_NO_SCENE
- * before rtw_ctx_set_scene.  No per-ray ranges, no camera form and no rtw_mgpu_* form. */
+ * before rtw_ctx_set_scene.  No per-ray ranges and no rtw_mgpu_* form (the camera form is rtw_ctx_ao_map, below). */
 int rtw_ctx_scene_occluded(rtw_ctx *ctx, const float *rays, uint32_t n_rays, float time, float mint, float maxt,
                            uint32_t accel, uint8_t *occluded_out, RtwStats *stats);
 /* Host only: the kernel's triangle group and placement group, the same source compiled for the host -- the mesh's tree where the device would
@@ -924,6 +924,43 @@ int rtw_triangle_occluded(const RtwTriangle *tris, uint32_t n, const float *rays
                           uint8_t *occluded_out, RtwStats *stats);
 int rtw_mesh_instance_occluded(const RtwTriangle *tris, uint32_t n, const RtwMeshInstance *placements, uint32_t n_placements,
                                const float *rays, uint32_t n_rays, float mint, float maxt, uint8_t *occluded_out, RtwStats *stats);
+
+/* ---- ambient occlusion: hemisphere any-hit rays, fused (added within v4) ------------------------------------------------
+ * For each point, `samples` cosine-weighted rays about its normal, walked by the any-hit pass in the kernel that makes them, one float out:
+ * the share of the rays that nothing stops within [mint, maxt] (maxt is the AO radius: the directions are unit to rounding).  No ray is
+ * stored anywhere.
+ * THE RULE (rtw_ao_rays; csrc/rtw_ao.h): ray [i][k] of point i, sample k under `seed` has the origin points[i] as given (no bias: mint keeps
+ * the ray off its own surface) and the direction rtw_mixed_dir(1.0, xi_phi, xi_cos, normals[i]) -- exp = 1 is the cosine lobe --, where
+ * xi_phi, xi_cos are the first two draws of the render's counter-based stream started at sample k of
+ * base = mix32(mix32(mix32(seed + 0x9E3779B9) ^ 0x414F5241) ^ i).  Ray [i][k] depends on (seed, i, k, point, normal) alone: not on n, not
+ * on samples.  A point whose normal is exactly (0, 0, 0) is SKIPPED: it casts no rays and answers 1.0 (rtw_ctx_depth_map's miss pixels have
+ * this normal); rtw_ao_rays writes six zeros for each of its rays.  Everything else flows: a NaN point or normal gives NaN rays.
+ * THE CONTRACT: for a point that is not skipped, ao_out[i] == (float)(samples - c_i) * (1.0f / samples), c_i the number of k < samples for
+ * which rtw_ctx_scene_occluded answers 1 for ray [i][k] of rtw_ao_rays with the same time, mint, maxt and accel -- exactly, for every input,
+ * under both accels and every fall-back: an any-hit answer depends on the ray alone, never on the lanes that share its wave.  samples must be
+ * a power of two in 1 .. 1024, so the product is exact.
+ * points, normals ([n][3]) and ao_out ([n]) may each be host memory or device memory of ctx's GPU (host memory is staged); the work runs on
+ * the stream of rtw_ctx_set_stream; blocking.  stats (may be NULL): segments = the rays cast (samples x the points not skipped),
+ * sphere_tests, node_tests, quad_tests = rtw_ctx_scene_occluded's on those rays, kernel_ms.  RTW_E_INVALID for a NULL ctx / points /
+ * normals / ao_out, n == 0, a samples that is not a power of two in 1 .. 1024, n x samples above 2^32 - 1, an unknown accel or a call while
+ * a render is pending; RTW_E_NO_SCENE before rtw_ctx_set_scene.  No bent normals, no per-point radii and no rtw_mgpu_* form. */
+/* host only, pure */
+int rtw_ao_rays(const float *points, const float *normals, uint32_t n, uint32_t samples, uint32_t seed,
+                float *rays_out /* [n][samples][6]; six zeros for every ray of a skipped point */);
+int rtw_ctx_ambient_occlusion(rtw_ctx *ctx, const float *points /*[n][3]*/, const float *normals /*[n][3]*/, uint32_t n,
+                              uint32_t samples, uint32_t seed, float time, float mint, float maxt, uint32_t accel,
+                              float *ao_out /*[n]*/, RtwStats *stats);
+/* The camera form, defined as a composition: rtw_ctx_depth_map(cam, width, height, time, mint, maxt, accel) with ids and normals, then
+ * rtw_ctx_ambient_occlusion over [ao_mint, ao_maxt] with point index j * width + i, the points p = o + d * depth for idx >= 0 (o, d by the
+ * rule of rtw_depth_rays; one f32 rounding per operation, no FMA), the normals faced towards the viewer (dot(d, n) > 0 ? -n : n), a miss
+ * pixel (idx < 0) skipped.  depth_out, idx_out and normal_out (each may be NULL) receive exactly rtw_ctx_depth_map's bytes -- the normal as
+ * that call writes it, not faced.  Two launches between one pair of events: stats adds the depth pass's counters and its width x height
+ * rays to the AO's.  Memory kinds, stream and blocking as above; RTW_E_INVALID also for a NULL cam, a zero width or height, or
+ * width x height x samples above 2^32 - 1. */
+int rtw_ctx_ao_map(rtw_ctx *ctx, const RtwCamera *cam, uint32_t width, uint32_t height, float time, float mint, float maxt,
+                   uint32_t samples, uint32_t seed, float ao_mint, float ao_maxt, uint32_t accel,
+                   float *ao_out /*[h][w]*/, float *depth_out, int32_t *idx_out, float *normal_out /* each may be NULL */,
+                   RtwStats *stats);
 
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 

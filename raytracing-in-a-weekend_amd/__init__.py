@@ -333,6 +333,11 @@ def lib() -> C.CDLL:
     L.rtw_triangle_occluded.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, fp, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.POINTER(RtwStats)]
     L.rtw_mesh_instance_occluded.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, C.POINTER(RtwMeshInstance), C.c_uint32, fp, C.c_uint32, C.c_float,
                                              C.c_float, C.c_void_p, C.POINTER(RtwStats)]
+    L.rtw_ao_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.rtw_ctx_ambient_occlusion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                            C.c_uint32, C.c_void_p, C.POINTER(RtwStats)]
+    L.rtw_ctx_ao_map.argtypes = [C.c_void_p, C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32,
+                                 C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtwStats)]
     L.rtw_ctx_depth_map.argtypes = [C.c_void_p, C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtwStats)]
     L.rtw_ctx_set_lights.argtypes = [C.c_void_p, C.POINTER(RtwLight), C.c_uint32, C.c_float]
@@ -826,6 +831,24 @@ def depth_rays(cam: RtwCamera, width: int, height: int) -> np.ndarray:
     width, height = int(width), int(height)
     out = np.empty((max(0, width * height), 6), np.float32)
     _check(lib().rtw_depth_rays(C.byref(cam), width, height, out.ctypes.data_as(C.POINTER(C.c_float))), "rtw_depth_rays")
+    return out
+
+
+def _points_normals(what, points, normals):
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if len(p) == 0 or len(p) != len(n):
+        raise ValueError(f"{what}: points and normals must both hold [n][3] floats, n > 0")
+    return p, n
+
+
+def ao_rays(points, normals, samples: int, seed: int = 0) -> np.ndarray:
+    """The rays of ambient occlusion (rtw_ao_rays, host only): [n][samples][6] float32 = origin, direction -- sample k of point i is a
+    cosine-weighted direction about normals[i] from points[i], a function of (seed, i, k, point, normal) alone.  A point whose normal is
+    exactly (0, 0, 0) is skipped: six zeros for each of its rays.  samples: a power of two in 1 .. 1024."""
+    p, n = _points_normals("ao_rays", points, normals)
+    out = np.empty((len(p), int(samples), 6), np.float32) if 0 < int(samples) <= 1024 else np.empty((1, 1, 6), np.float32)
+    _check(lib().rtw_ao_rays(p.ctypes.data, n.ctypes.data, len(p), int(samples), int(seed) & 0xFFFFFFFF, out.ctypes.data), "rtw_ao_rays")
     return out
 
 
@@ -1523,6 +1546,62 @@ class Renderer:
         _check(lib().rtw_ctx_depth_map(self._h, C.byref(cam), width, height, float(time), float(mint), float(maxt), int(accel), depth.ctypes.data,
                                        idx.ctypes.data if ids else None, nrm.ctypes.data if normals else None, C.byref(st)), "rtw_ctx_depth_map")
         return (depth,) + ((idx,) if ids else ()) + ((nrm,) if normals else ()) + (st,)
+
+    def ambient_occlusion(self, points, normals, samples: int = 16, radius: float = 1.0, mint: float = 1e-3, seed: int = 0, time: float = 0.0,
+                          accel: int = ACCEL_BVH, out=None):
+        """Ambient occlusion of points ([n][3]) with normals ([n][3]) against this context's whole scene (rtw_ctx_ambient_occlusion): (ao [n]
+        float32, RtwStats), ao[i] the share of `samples` cosine-weighted rays about normals[i] that nothing stops within [mint, radius] --
+        exactly (samples - c) / samples, c the count scene_occluded gives for ao_rays(points, normals, samples, seed)[i].  The rays are made and
+        walked in one kernel; none is stored.  A point with the normal (0, 0, 0) casts none and answers 1.0.  samples: a power of two in
+        1 .. 1024.
+        points, normals: anything numpy reads (staged; ao is a numpy array), or contiguous float32 torch tensors on the context's device: then
+        `out` is a float32 tensor [n] on the same device (allocated when None), and all three are read and written in place on the
+        context's stream (use_torch_stream), as scene_occluded reads its tensor."""
+        st = RtwStats()
+        args = (int(samples), int(seed) & 0xFFFFFFFF, float(time), float(mint), float(radius), int(accel))
+        if hasattr(points, "data_ptr") or hasattr(normals, "data_ptr"):
+            import torch
+            for t in (points, normals):
+                if (not hasattr(t, "data_ptr") or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda
+                        or t.device.index != self._device):
+                    raise ValueError("ambient_occlusion: points and normals must both be float32 tensors, contiguous and on the context's device")
+            if points.numel() == 0 or points.numel() % 3 or normals.numel() != points.numel():
+                raise ValueError("ambient_occlusion: points and normals must both hold [n][3] floats, n > 0")
+            n = points.numel() // 3
+            if out is None:
+                out = torch.empty(n, dtype=torch.float32, device=points.device)
+            if (not hasattr(out, "data_ptr") or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda
+                    or out.device.index != self._device or out.numel() != n):
+                raise ValueError("ambient_occlusion: out must be a contiguous torch.float32 tensor [n] on the context's device")
+            _check(lib().rtw_ctx_ambient_occlusion(self._h, C.c_void_p(int(points.data_ptr())), C.c_void_p(int(normals.data_ptr())), n, *args,
+                                                   C.c_void_p(int(out.data_ptr())), C.byref(st)), "rtw_ctx_ambient_occlusion")
+            return out, st
+        if out is not None:
+            raise ValueError("ambient_occlusion: out= goes with torch tensors of points and normals")
+        p, nrm = _points_normals("ambient_occlusion", points, normals)
+        ao = np.empty(len(p), np.float32)
+        _check(lib().rtw_ctx_ambient_occlusion(self._h, p.ctypes.data, nrm.ctypes.data, len(p), *args, ao.ctypes.data, C.byref(st)),
+               "rtw_ctx_ambient_occlusion")
+        return ao, st
+
+    def ao_map(self, cam: RtwCamera, width: int, height: int, mint: float, maxt: float, samples: int = 16, radius: float = 1.0,
+               ao_mint: float = 1e-3, seed: int = 0, time: float = 0.0, accel: int = ACCEL_BVH, depth: bool = False, ids: bool = False,
+               normals: bool = False):
+        """Ambient occlusion of what a camera of camera2_new sees (rtw_ctx_ao_map): depth_map(cam, width, height, mint, maxt) and then
+        ambient_occlusion of its hit points, with the normals faced towards the viewer, over [ao_mint, radius], in two launches and with no
+        buffer in between on the host: (ao [height][width] float32, 1.0 for a miss pixel[, depth][, ids][, normals] -- depth_map's arrays,
+        the normals as it writes them --; RtwStats, the depth pass's counters and rays included)."""
+        width, height = int(width), int(height)
+        ao = np.empty((height, width), np.float32)
+        dep = np.empty((height, width), np.float32) if depth else None
+        idx = np.empty((height, width), np.int32) if ids else None
+        nrm = np.empty((height, width, 3), np.float32) if normals else None
+        st = RtwStats()
+        _check(lib().rtw_ctx_ao_map(self._h, C.byref(cam), width, height, float(time), float(mint), float(maxt), int(samples),
+                                    int(seed) & 0xFFFFFFFF, float(ao_mint), float(radius), int(accel), ao.ctypes.data,
+                                    dep.ctypes.data if depth else None, idx.ctypes.data if ids else None, nrm.ctypes.data if normals else None,
+                                    C.byref(st)), "rtw_ctx_ao_map")
+        return (ao,) + ((dep,) if depth else ()) + ((idx,) if ids else ()) + ((nrm,) if normals else ()) + (st,)
 
     def set_texture_noise(self, tables=None, n_tables: int = 0, per_texture=None, n_textures: int = 0):
         """rtw_ctx_set_texture_noise as is (no arguments: clear the noise of the current scene)."""

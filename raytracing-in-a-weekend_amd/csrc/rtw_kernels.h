@@ -159,6 +159,23 @@ struct OccludedArgs {
 };
 // tree: the sphere group through DevBvh.nodes (dynamic LDS = levels * RTW_BLOCK * 4)
 void launch_scene_occluded(const OccludedArgs &q, bool tree, hipStream_t stream);
+// rtw_ctx_ambient_occlusion / rtw_ctx_ao_map (rtw_occluded.hip): `samples` any-hit rays per point, made in the kernel by
+// the rule of rtw_ao.h, one float per point.  q: the scene views, [mint, maxt] of the AO rays, the counters ([4]: the points that cast
+// rays); q.n is the number of POINTS, q.rays and q.out are not read.
+struct AoArgs {
+    OccludedArgs q;
+    const float *points;          // [n][3] (device); from_camera: not read
+    const float *normals;         // [n][3] (device); from_camera: the depth pass's normals of the pixels
+    uint32_t samples, seed;       // samples: a power of two in 1 .. 1024
+    uint32_t lg_group;            // log2 of the lanes that share a point: min(samples, 64)
+    float *ao_out;                // [n]
+    RtwCamera cam;                // from_camera: as QueryArgs.cam, point j * width + i is pixel (i, j) ...
+    uint32_t width, height;
+    const float *depth;           // ... at p = o + d * depth[pixel] with the normal faced towards the viewer,
+    const int32_t *idx;           // skipped where idx[pixel] < 0 (device, what launch_scene_hits wrote)
+};
+// from_camera: the points come from the depth pass's outputs; tree: as launch_scene_occluded.  (samples <= 64 runs the single-round build)
+void launch_ambient_occlusion(const AoArgs &q, bool from_camera, bool tree, hipStream_t stream);
 // rtw_ctx_mesh_instance_hits: the closest placement of mesh T for each of n rays through mesh_closest (rtw_mesh.h); placement / triangle
 // -1 and t +inf on a miss; normal_out ([n][3]) may be null; counters as launch_tri_hits
 void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const TriNode *top, uint32_t n_top, const float *rays, uint32_t n, float mint, float maxt, float *t_out,

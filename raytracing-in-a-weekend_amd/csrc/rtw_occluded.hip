@@ -1,6 +1,7 @@
 // rtw_occluded.hip -- any-hit occlusion queries over the whole scene of a context (rtw_ctx_scene_occluded): for each ray,
 // "is anything in the way within [mint, maxt]?" -- one byte, 1 exactly when rtw_ctx_scene_hits (rtw_query.hip) reports an index >= 0.
-// A kernel of its own: no render kernel and no closest-hit query reads this file.
+// A kernel of its own: no render kernel and no closest-hit query reads this file.  ambient_occlusion_kernel (rtw_ctx_ambient_occlusion /
+// rtw_ctx_ao_map) lives here too: it makes its rays in registers (rtw_ao.h) and walks them with the same function.
 //
 // Why the bit is exact: in every group the acceptance of a candidate with nothing found so far depends on that candidate and on
 // [mint, maxt] alone, a later group's result never takes a hit away, and the trees only prune.  So "some candidate is accepted" is "the
@@ -12,6 +13,7 @@
 // kernels do not change, so they keep their copies).  Change them together.
 #include "rtw_kernels.h"
 #include "rtw_occl.h"
+#include "rtw_ao.h"
 
 namespace rtw {
 
@@ -151,9 +153,81 @@ __device__ __forceinline__ bool q_ray_ordinary(v3 o, v3 d, float a, float span) 
     return no + nd < 0x1p60f && a >= 1e-30f && a <= 1e30f && fmaxf(nd, 2.0f) * (span + no + 1.0f) <= 1e18f;      // (nd >= |d|; NaN fails)
 }
 
+// The per-ray sequence of the any-hit pass, ONE definition for scene_occluded_kernel and ambient_occlusion_kernel: spheres by tree or list
+// under q_ray_ordinary, then quads, then instances with media skipped, then the triangles or their placements.  `open`: nothing has accepted
+// the lane's ray yet; a lane that comes in closed (it has no ray) tests and counts nothing.  Returns `open`.  The ballots see the lanes
+// that are active at the call, so a lane outside the call and a lane that comes in closed weigh the same: nothing.
+template <bool TREE, bool MOVING>
+__device__ __forceinline__ bool occluded_walk(const OccludedArgs &A, const unsigned char *q_lds, v3 o, v3 d, bool open, uint32_t &n_sph,
+                                              uint32_t &n_nodes, uint32_t &n_quad, bool &overflow) {
+    const float tm = A.time, mint = A.mint, maxt = A.maxt;
+    const float a = dot(d, d);
+    const float ra = rcp_refined(a);
+    const bool a_plain = ballot64(open && !in_range(a, 0x1p-20f, 0x1p20f)) == 0ull;  // see sphere_root()
+    // ---- spheres ----
+    bool listed = true;
+    if (TREE) {
+        if (open && q_ray_ordinary(o, d, a, A.span)) {
+            const uint32_t sp0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)q_lds + threadIdx.x * 4u;
+            if (q_sphere_tree_any<MOVING>(A.sc, A.bvh, o, d, tm, a, ra, a_plain, mint, maxt, sp0, sp0 + (A.levels - 1u) * (RTW_BLOCK * 4u),
+                                          n_sph, n_nodes, overflow)) open = false;
+            listed = false;
+        }
+    }
+    if (listed) { if (q_sphere_list_any<MOVING>(A.sc, o, d, tm, a, ra, a_plain, mint, maxt, open, n_sph)) open = false; }
+    // ---- quads in list order ----
+    const DevGeom &g = A.geom;
+    for (uint32_t k = 0; k < g.n_quads; ++k) {
+        if (ballot64(open) == 0ull) break;
+        if (open) {
+            float t;
+            n_quad++;
+            if (quad_pick(g.quads, k, o, d, mint, maxt, false, 0.0f, t)) open = false;
+        }
+    }
+    // ---- instances (instance.rs:250-310), media skipped: any member accepted is the instance accepted ----
+    for (uint32_t k = 0; k < g.n_inst; ++k) {
+        if (ballot64(open) == 0ull) break;
+        const DevInstance in = g.inst[k];
+        if (in.medium == RTW_MEDIUM_CONST_DENSITY) continue;
+        if (open) {
+            const v3 tr = ld3(in.tr);
+            v3 lo, ld;
+            if (A.inst_quats) { const quat qn = inst_quat(A.inst_quats, k); lo = quat_rot(qn, o - tr); ld = quat_rot(qn, d); }   // (a wave-uniform branch)
+            else { lo = rotated(o - tr, in.back, in.back_k); ld = rotated(d, in.back, in.back_k); }
+            float ct; int code;
+            if (instance_pick(g, in, lo, ld, tm, mint, maxt, ct, code, n_sph, n_quad)) open = false;
+        }
+    }
+    // ---- triangles last ----
+    if (A.mesh_rows) {                                             // (a wave-uniform branch) the placements stand in for the world-space triangles
+        if (mesh_any(A.tris, A.mesh_rows, A.n_mesh, A.mesh_top, A.n_mesh_top, o, d, mint, maxt, open, n_quad, n_nodes)) open = false;
+    } else if (A.tris.n) {
+        if (tri_any(A.tris, o, d, mint, maxt, open, n_quad, n_nodes)) open = false;
+    }
+    return open;
+}
+
+// The counters of a lane summed over the wave, one atomic per wave and counter (as scene_hits_kernel), on the workgroup's line of `counters`.
+// n_points: the points that cast rays (ambient_occlusion_kernel; [4]), 0 elsewhere.
+__device__ __forceinline__ void occluded_count(unsigned long long *counters, uint32_t n_sph, uint32_t n_nodes, uint32_t n_quad, bool overflow,
+                                               uint32_t n_points) {
+    unsigned long long s0 = n_sph, s1 = n_nodes, s2 = n_quad;
+    for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); s2 += __shfl_down(s2, off); }
+    const bool any_overflow = ballot64(overflow) != 0ull;
+    if ((threadIdx.x & 63u) == 0) {
+        unsigned long long *line = counters + (blockIdx.x % RTW_QUERY_SLOTS) * RTW_QUERY_STRIDE;
+        if (s0) atomicAdd(&line[0], s0);
+        if (s1) atomicAdd(&line[1], s1);
+        if (s2) atomicAdd(&line[2], s2);
+        if (any_overflow) atomicAdd(&line[3], 1ull);
+        if (n_points) atomicAdd(&line[4], (unsigned long long)n_points);
+    }
+}
+
 } // namespace
 
-// TREE: the sphere group goes through the tree (stack in dynamic LDS).  One ray per lane; `open`: nothing has accepted the lane's ray yet.
+// TREE: the sphere group goes through the tree (stack in dynamic LDS).  One ray per lane.
 template <bool TREE, bool MOVING>
 __global__ __launch_bounds__(RTW_BLOCK) void scene_occluded_kernel(const OccludedArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char q_lds[];
@@ -164,65 +238,65 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_occluded_kernel(const Occlude
         const float2 *r = (const float2 *)(A.rays + 6 * (size_t)i);
         const float2 r0 = r[0], r1 = r[1], r2 = r[2];
         const v3 o = mk(r0.x, r0.y, r1.x), d = mk(r1.y, r2.x, r2.y);
-        const float tm = A.time, mint = A.mint, maxt = A.maxt;
-        const float a = dot(d, d);
-        const float ra = rcp_refined(a);
-        const bool a_plain = ballot64(!in_range(a, 0x1p-20f, 0x1p20f)) == 0ull;          // see sphere_root()
-        bool open = true;
-        // ---- spheres ----
-        bool listed = true;
-        if (TREE) {
-            if (q_ray_ordinary(o, d, a, A.span)) {
-                const uint32_t sp0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)q_lds + threadIdx.x * 4u;
-                if (q_sphere_tree_any<MOVING>(A.sc, A.bvh, o, d, tm, a, ra, a_plain, mint, maxt, sp0, sp0 + (A.levels - 1u) * (RTW_BLOCK * 4u),
-                                              n_sph, n_nodes, overflow)) open = false;
-                listed = false;
-            }
-        }
-        if (listed) { if (q_sphere_list_any<MOVING>(A.sc, o, d, tm, a, ra, a_plain, mint, maxt, true, n_sph)) open = false; }
-        // ---- quads in list order ----
-        const DevGeom &g = A.geom;
-        for (uint32_t k = 0; k < g.n_quads; ++k) {
-            if (ballot64(open) == 0ull) break;
-            if (open) {
-                float t;
-                n_quad++;
-                if (quad_pick(g.quads, k, o, d, mint, maxt, false, 0.0f, t)) open = false;
-            }
-        }
-        // ---- instances (instance.rs:250-310), media skipped: any member accepted is the instance accepted ----
-        for (uint32_t k = 0; k < g.n_inst; ++k) {
-            if (ballot64(open) == 0ull) break;
-            const DevInstance in = g.inst[k];
-            if (in.medium == RTW_MEDIUM_CONST_DENSITY) continue;
-            if (open) {
-                const v3 tr = ld3(in.tr);
-                v3 lo, ld;
-                if (A.inst_quats) { const quat qn = inst_quat(A.inst_quats, k); lo = quat_rot(qn, o - tr); ld = quat_rot(qn, d); }   // (a wave-uniform branch)
-                else { lo = rotated(o - tr, in.back, in.back_k); ld = rotated(d, in.back, in.back_k); }
-                float ct; int code;
-                if (instance_pick(g, in, lo, ld, tm, mint, maxt, ct, code, n_sph, n_quad)) open = false;
-            }
-        }
-        // ---- triangles last ----
-        if (A.mesh_rows) {                                         // (a wave-uniform branch) the placements stand in for the world-space triangles
-            if (mesh_any(A.tris, A.mesh_rows, A.n_mesh, A.mesh_top, A.n_mesh_top, o, d, mint, maxt, open, n_quad, n_nodes)) open = false;
-        } else if (A.tris.n) {
-            if (tri_any(A.tris, o, d, mint, maxt, open, n_quad, n_nodes)) open = false;
-        }
+        const bool open = occluded_walk<TREE, MOVING>(A, q_lds, o, d, true, n_sph, n_nodes, n_quad, overflow);
         A.out[i] = open ? (uint8_t)0 : (uint8_t)1;
     }
-    // counters: summed over the wave, one atomic per wave and counter (as scene_hits_kernel), on the workgroup's line of A.counters
-    unsigned long long s0 = n_sph, s1 = n_nodes, s2 = n_quad;
-    for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); s2 += __shfl_down(s2, off); }
-    const bool any_overflow = ballot64(overflow) != 0ull;
-    if ((threadIdx.x & 63u) == 0) {
-        unsigned long long *line = A.counters + (blockIdx.x % RTW_QUERY_SLOTS) * RTW_QUERY_STRIDE;
-        if (s0) atomicAdd(&line[0], s0);
-        if (s1) atomicAdd(&line[1], s1);
-        if (s2) atomicAdd(&line[2], s2);
-        if (any_overflow) atomicAdd(&line[3], 1ull);
+    occluded_count(A.counters, n_sph, n_nodes, n_quad, overflow, 0u);
+}
+
+// Ambient occlusion (rtw_ctx_ambient_occlusion / rtw_ctx_ao_map): L = min(samples, 64) lanes form a group that owns one
+// point, a wave holds 64 / L points, and a lane takes sample k = lane_in_group + round * L in samples / L rounds.  Lane 0 of a group loads
+// the point and its normal -- CAM: forms them from the depth pass's depth, index and normal of pixel i and the pixel's ray, by the rule of
+// rtw_depth_rays -- and the group gets them by a cross-lane read.  Every lane makes its ray in registers (rtw_ao.h) and walks it with
+// occluded_walk; a round's occluded count is the popcount of a ballot under the group's lane mask.  No lane leaves before the end: every
+// cross-lane read below finds its source lane active.
+// ONE: samples <= 64, a single round.  Nothing of the point then lives across the walk (the point, the normal, the stream's prefix and the
+// frame the compiler hoists out of the round loop: up to 37 VGPRs), and the build keeps the 7 waves per SIMD of scene_occluded_kernel; the
+// build with the loop runs at 4 - 5.
+template <bool CAM, bool TREE, bool MOVING, bool ONE>
+__global__ __launch_bounds__(RTW_BLOCK) void ambient_occlusion_kernel(const AoArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char q_lds[];
+    const uint32_t lg = A.lg_group, L = 1u << lg;                  // (wave-uniform: samples is a kernel argument)
+    const uint32_t lane = threadIdx.x & 63u, g_lane = lane & (L - 1u), g_first = lane - g_lane;
+    const unsigned long long point = (unsigned long long)blockIdx.x * (RTW_BLOCK >> lg) + (threadIdx.x >> lg);
+    const bool in = point < A.q.n;
+    const uint32_t i = (uint32_t)point;
+    uint32_t n_sph = 0, n_nodes = 0, n_quad = 0;
+    bool overflow = false;
+    v3 p = mk(0.0f, 0.0f, 0.0f), nrm = p;
+    if (in && g_lane == 0u) {
+        if (CAM) {
+            if (A.idx[i] >= 0) {                                   // (a miss pixel is skipped: its normal stays 0 0 0)
+                const uint32_t px = i % A.width, py = i / A.width;
+                const float fx = (float)px / (float)A.width, fy = (float)py / (float)A.height;
+                const v3 o = ld3(A.cam.origin);
+                const v3 d = unit((ld3(A.cam.pixel00) + ld3(A.cam.delta_u) * fx) + ld3(A.cam.delta_v) * fy);
+                const v3 nn = ld3(A.normals + 3 * (size_t)i);
+                p = o + d * A.depth[i];
+                nrm = dot(d, nn) > 0.0f ? -nn : nn;                // faced towards the viewer
+            }
+        } else {
+            p = ld3(A.points + 3 * (size_t)i);
+            nrm = ld3(A.normals + 3 * (size_t)i);
+        }
     }
+    if (L > 1u) {
+        p.x = __shfl(p.x, (int)g_first); p.y = __shfl(p.y, (int)g_first); p.z = __shfl(p.z, (int)g_first);
+        nrm.x = __shfl(nrm.x, (int)g_first); nrm.y = __shfl(nrm.y, (int)g_first); nrm.z = __shfl(nrm.z, (int)g_first);
+    }
+    const lv3 ln = lmk(nrm.x, nrm.y, nrm.z);
+    const bool casts = in && !ao_skipped(ln);                      // (a point past n has the normal 0 0 0 as well)
+    const uint32_t base = ao_point_base(A.seed, i);
+    const unsigned long long g_mask = (L == 64u ? ~0ull : ((1ull << L) - 1ull)) << g_first;
+    uint32_t occluded = 0;
+    for (uint32_t round = 0; round < (ONE ? 1u : A.samples); round += (ONE ? 1u : L)) {     // (samples / L rounds, wave-uniform; ONE: no loop)
+        const lv3 dir = ao_dir(base, round + g_lane, ln);
+        const bool open = occluded_walk<TREE, MOVING>(A.q, q_lds, p, mk(dir.x, dir.y, dir.z), casts, n_sph, n_nodes, n_quad, overflow);
+        occluded += (uint32_t)__builtin_popcountll(ballot64(!open) & g_mask);
+    }
+    if (in && g_lane == 0u) A.ao_out[i] = casts ? (float)(A.samples - occluded) * (1.0f / (float)A.samples) : 1.0f;
+    const uint32_t n_points = (uint32_t)__builtin_popcountll(ballot64(casts && g_lane == 0u));
+    occluded_count(A.q.counters, n_sph, n_nodes, n_quad, overflow, n_points);
 }
 
 void launch_scene_occluded(const OccludedArgs &q, bool tree, hipStream_t stream) {
@@ -232,6 +306,21 @@ void launch_scene_occluded(const OccludedArgs &q, bool tree, hipStream_t stream)
                             : (moving ? scene_occluded_kernel<false, true> : scene_occluded_kernel<false, false>);
     const uint32_t lds = tree ? q.levels * RTW_BLOCK * 4u : 0u;
     hipLaunchKernelGGL(fn, dim3((q.n + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), lds, stream, q);
+}
+
+typedef void (*ao_fn)(const AoArgs);
+template <bool CAM, bool TREE, bool MOVING>
+static ao_fn pick_ao(bool one) { return one ? ambient_occlusion_kernel<CAM, TREE, MOVING, true> : ambient_occlusion_kernel<CAM, TREE, MOVING, false>; }
+
+void launch_ambient_occlusion(const AoArgs &q, bool from_camera, bool tree, hipStream_t stream) {
+    const bool moving = q.q.sc.moving != 0u;
+    const bool one = q.samples <= 64u;
+    const ao_fn fns[2][2][2] = {
+        { { pick_ao<false, false, false>(one), pick_ao<false, false, true>(one) }, { pick_ao<false, true, false>(one), pick_ao<false, true, true>(one) } },
+        { { pick_ao<true, false, false>(one), pick_ao<true, false, true>(one) }, { pick_ao<true, true, false>(one), pick_ao<true, true, true>(one) } } };
+    const uint32_t lds = tree ? q.q.levels * RTW_BLOCK * 4u : 0u;
+    const uint32_t per_block = RTW_BLOCK >> q.lg_group;            // points of a workgroup
+    hipLaunchKernelGGL(fns[from_camera][tree][moving], dim3((uint32_t)(((unsigned long long)q.q.n + per_block - 1u) / per_block)), dim3(RTW_BLOCK), lds, stream, q);
 }
 
 } // namespace rtw

@@ -9,6 +9,7 @@
 #include "rtw_devmem.h"
 #include "rtw_exp.h"
 #include "rtw_probe.h"
+#include "rtw_ao.h"
 
 #include <link.h>
 
@@ -1161,6 +1162,18 @@ int rtw_ctx_depth_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t
     return scene_query(c, cam, width, height, nullptr, width * height, time, mint, maxt, accel, host_mul(maxt, 1.6f), depth_out, idx_out, normal_out, stats);
 }
 
+// The views and the range of an any-hit launch over n rays (rtw_ctx_scene_occluded) or n points (ambient occlusion, below)
+static void occluded_views(const rtw_ctx *c, uint32_t n, float time, float mint, float maxt, uint32_t accel, OccludedArgs &q) {
+    std::memset(&q, 0, sizeof q);
+    q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom; q.inst_quats = c->inst_quats;
+    if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
+    q.mesh_rows = c->mesh_rows; q.n_mesh = c->n_mesh;
+    if (c->mesh_rows) { q.mesh_top = mesh_top_view(c, q.tris); q.n_mesh_top = c->n_mesh_top; }
+    q.n = n; q.levels = c->bvh.depth + 2u;
+    q.time = time; q.mint = mint; q.maxt = maxt; q.span = (float)c->scene_span;
+    q.counters = c->scr.qstats.as<unsigned long long>();
+}
+
 // The any-hit pass (rtw.h "occlusion queries"; kernel: rtw_occluded.hip): scene_query's conditions, views, staging and stream order
 int rtw_ctx_scene_occluded(rtw_ctx *c, const float *rays, uint32_t n, float time, float mint, float maxt, uint32_t accel, uint8_t *occluded_out,
                            RtwStats *stats) {
@@ -1171,14 +1184,7 @@ int rtw_ctx_scene_occluded(rtw_ctx *c, const float *rays, uint32_t n, float time
     const bool tree = query_uses_tree(c, accel, time, mint, maxt);
 
     OccludedArgs q;
-    std::memset(&q, 0, sizeof q);
-    q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom; q.inst_quats = c->inst_quats;
-    if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
-    q.mesh_rows = c->mesh_rows; q.n_mesh = c->n_mesh;
-    if (c->mesh_rows) { q.mesh_top = mesh_top_view(c, q.tris); q.n_mesh_top = c->n_mesh_top; }
-    q.n = n; q.levels = c->bvh.depth + 2u;
-    q.time = time; q.mint = mint; q.maxt = maxt; q.span = (float)c->scene_span;
-    q.counters = c->scr.qstats.as<unsigned long long>();
+    occluded_views(c, n, time, mint, maxt, accel, q);
 
     const size_t ray_bytes = 6 * sizeof(float) * (size_t)n;
     DevMem d_r, d_o;                     // staging, for whatever is not this GPU's memory
@@ -1206,6 +1212,139 @@ int rtw_ctx_scene_occluded(rtw_ctx *c, const float *rays, uint32_t n, float time
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
     if (const int rc = call_status(c, e)) return rc;
     return query_stats(c, n, ms, stats);
+}
+
+// ---- ambient occlusion (rtw.h "ambient occlusion"; kernel: rtw_occluded.hip; the rule: rtw_ao.h) ----------------------------------------
+static uint32_t ao_lg_group(uint32_t samples) {
+    uint32_t lg = 0;
+    while ((1u << lg) < samples && lg < 6u) lg++;
+    return lg;
+}
+// query_stats with the rays counted by the kernel: `samples` per point that cast rays, plus `extra` (the depth pass's)
+static int ao_stats(const rtw_ctx *c, uint32_t samples, uint64_t extra, float ms, RtwStats *stats) {
+    const unsigned long long *h_qstats = c->scr.h_qstats.as<unsigned long long>();
+    unsigned long long sum[5] = { 0, 0, 0, 0, 0 };
+    for (uint32_t s = 0; s < RTW_QUERY_SLOTS; s++) for (int k = 0; k < 5; k++) sum[k] += h_qstats[s * RTW_QUERY_STRIDE + k];
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        stats->segments = sum[4] * samples + extra;
+        stats->sphere_tests = sum[0]; stats->node_tests = sum[1]; stats->quad_tests = sum[2];
+        stats->kernel_ms = ms;
+    }
+    return sum[3] ? RTW_E_INTERNAL : RTW_OK;
+}
+
+int rtw_ctx_ambient_occlusion(rtw_ctx *c, const float *points, const float *normals, uint32_t n, uint32_t samples, uint32_t seed, float time,
+                              float mint, float maxt, uint32_t accel, float *ao_out, RtwStats *stats) {
+    if (!c || !points || !normals || !ao_out || n == 0 || !ao_samples_ok(samples) || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    if ((uint64_t)n * samples > 0xFFFFFFFFull) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    if (!c->has_scene) return RTW_E_NO_SCENE;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool tree = query_uses_tree(c, accel, time, mint, maxt);
+
+    AoArgs a;
+    std::memset(&a, 0, sizeof a);
+    occluded_views(c, n, time, mint, maxt, accel, a.q);
+    a.samples = samples; a.seed = seed; a.lg_group = ao_lg_group(samples);
+
+    const size_t v_bytes = 3 * sizeof(float) * (size_t)n, o_bytes = sizeof(float) * (size_t)n;
+    DevMem d_p, d_n, d_o;                // staging, for whatever is not this GPU's memory
+    hipError_t e = hipSuccess;
+    if (query_on_device(c, points)) a.points = points;
+    else {
+        e = d_p.reserve(v_bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_p.ptr, points, v_bytes, hipMemcpyDefault, c->stream);
+        a.points = d_p.as<const float>();
+    }
+    if (query_on_device(c, normals)) a.normals = normals;
+    else {
+        if (e == hipSuccess) e = d_n.reserve(v_bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_n.ptr, normals, v_bytes, hipMemcpyDefault, c->stream);
+        a.normals = d_n.as<const float>();
+    }
+    if (query_on_device(c, ao_out)) a.ao_out = ao_out;
+    else { if (e == hipSuccess) e = d_o.reserve(o_bytes); a.ao_out = d_o.as<float>(); }
+    const size_t q_bytes = RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long);
+    if (e == hipSuccess) e = hipMemsetAsync(c->scr.qstats.ptr, 0, q_bytes, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    if (e == hipSuccess) {
+        launch_ambient_occlusion(a, false, tree, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess && d_o.ptr) e = hipMemcpyAsync(ao_out, d_o.ptr, o_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->scr.h_qstats.ptr, c->scr.qstats.ptr, q_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    if (const int rc = call_status(c, e)) return rc;
+    return ao_stats(c, samples, 0, ms, stats);
+}
+
+// rtw_ctx_depth_map with ids and normals into the caller's device buffers or scratch, then the AO kernel's camera form over them: two launches
+// on the context's stream between one pair of events, one set of counters
+int rtw_ctx_ao_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, float time, float mint, float maxt, uint32_t samples,
+                   uint32_t seed, float ao_mint, float ao_maxt, uint32_t accel, float *ao_out, float *depth_out, int32_t *idx_out,
+                   float *normal_out, RtwStats *stats) {
+    if (!c || !cam || !ao_out || width == 0 || height == 0 || !ao_samples_ok(samples) || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    if ((uint64_t)width * height * samples > 0xFFFFFFFFull) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    if (!c->has_scene) return RTW_E_NO_SCENE;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t n = width * height;
+
+    QueryArgs q;                         // the depth pass: scene_query's launch
+    std::memset(&q, 0, sizeof q);
+    q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom; q.inst_quats = c->inst_quats;
+    if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
+    q.mesh_rows = c->mesh_rows; q.n_mesh = c->n_mesh;
+    if (c->mesh_rows) { q.mesh_top = mesh_top_view(c, q.tris); q.n_mesh_top = c->n_mesh_top; }
+    q.cam = *cam; q.width = width; q.height = height;
+    q.n = n; q.levels = c->bvh.depth + 2u;
+    q.time = time; q.mint = mint; q.maxt = maxt; q.miss_t = host_mul(maxt, 1.6f); q.span = (float)c->scene_span;
+    q.counters = c->scr.qstats.as<unsigned long long>();
+
+    AoArgs a;
+    std::memset(&a, 0, sizeof a);
+    occluded_views(c, n, time, ao_mint, ao_maxt, accel, a.q);
+    a.samples = samples; a.seed = seed; a.lg_group = ao_lg_group(samples);
+    a.cam = *cam; a.width = width; a.height = height;
+
+    const size_t t_bytes = sizeof(float) * (size_t)n, i_bytes = sizeof(int32_t) * (size_t)n;
+    DevMem d_t, d_i, d_n, d_o;           // the depth pass's outputs where the caller gave no device memory for them, and staging
+    hipError_t e = hipSuccess;
+    if (depth_out && query_on_device(c, depth_out)) q.t_out = depth_out;
+    else { e = d_t.reserve(t_bytes); q.t_out = d_t.as<float>(); }
+    if (idx_out && query_on_device(c, idx_out)) q.idx_out = idx_out;
+    else { if (e == hipSuccess) e = d_i.reserve(i_bytes); q.idx_out = d_i.as<int32_t>(); }
+    if (normal_out && query_on_device(c, normal_out)) q.normal_out = normal_out;
+    else { if (e == hipSuccess) e = d_n.reserve(3 * t_bytes); q.normal_out = d_n.as<float>(); }
+    if (query_on_device(c, ao_out)) a.ao_out = ao_out;
+    else { if (e == hipSuccess) e = d_o.reserve(t_bytes); a.ao_out = d_o.as<float>(); }
+    a.depth = q.t_out; a.idx = q.idx_out; a.normals = q.normal_out;
+    const size_t q_bytes = RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long);
+    if (e == hipSuccess) e = hipMemsetAsync(c->scr.qstats.ptr, 0, q_bytes, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    if (e == hipSuccess) {
+        launch_scene_hits(q, true, query_uses_tree(c, accel, time, mint, maxt), c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        launch_ambient_occlusion(a, true, query_uses_tree(c, accel, time, ao_mint, ao_maxt), c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess && d_o.ptr) e = hipMemcpyAsync(ao_out, d_o.ptr, t_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess && d_t.ptr && depth_out) e = hipMemcpyAsync(depth_out, d_t.ptr, t_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess && d_i.ptr && idx_out) e = hipMemcpyAsync(idx_out, d_i.ptr, i_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess && d_n.ptr && normal_out) e = hipMemcpyAsync(normal_out, d_n.ptr, 3 * t_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->scr.h_qstats.ptr, c->scr.qstats.ptr, q_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    if (const int rc = call_status(c, e)) return rc;
+    return ao_stats(c, samples, n, ms, stats);
 }
 
 int rtw_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t turb_depth, float *out) {
