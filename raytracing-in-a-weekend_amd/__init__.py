@@ -1359,8 +1359,7 @@ class Renderer:
         Returns list_walk: 1 when a triangle now breaks a condition of the tree and the context walks the list.  Not while placements are set."""
         keep = ouv
         if hasattr(ouv, "data_ptr"):
-            import torch
-            if ouv.dtype != torch.float32 or not ouv.is_contiguous() or not ouv.is_cuda or ouv.device.index != self._device:
+            if not self._on_device(ouv):
                 raise ValueError("refit_triangles: the tensor must be float32, contiguous and on the context's device")
             if ouv.numel() % 9:
                 raise ValueError("refit_triangles: the tensor must hold [n][9] floats")
@@ -1405,12 +1404,19 @@ class Renderer:
         arr, n = _placement_array(placements)
         _check(lib().rtw_ctx_set_mesh_instances(self._h, arr, n), "rtw_ctx_set_mesh_instances")
 
+    def _on_device(self, t, *dtypes) -> bool:
+        """Is `t` a torch tensor the C ABI can read or write in place: of one of `dtypes` (none given: float32), contiguous and on the
+        context's device?"""
+        if not hasattr(t, "data_ptr"):
+            return False
+        import torch
+        return t.dtype in (dtypes or (torch.float32,)) and t.is_contiguous() and t.is_cuda and t.device.index == self._device
+
     def _device_floats(self, x, per, n, what, name):
         """(pointer, count, keep-alive) of a move's input of `per` floats an entry: a tensor (read in place), an int device pointer with
         its count, or anything numpy reads (staged)."""
         if hasattr(x, "data_ptr"):
-            import torch
-            if x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda or x.device.index != self._device:
+            if not self._on_device(x):
                 raise ValueError(f"{what}: the tensor must be float32, contiguous and on the context's device")
             if x.numel() % per:
                 raise ValueError(f"{what}: the tensor must hold [n][{per}] floats")
@@ -1499,15 +1505,14 @@ class Renderer:
         st = RtwStats()
         if hasattr(rays, "data_ptr"):
             import torch
-            if rays.dtype != torch.float32 or not rays.is_contiguous() or not rays.is_cuda or rays.device.index != self._device:
+            if not self._on_device(rays):
                 raise ValueError("scene_occluded: the rays tensor must be float32, contiguous and on the context's device")
             if rays.numel() == 0 or rays.numel() % 6:
                 raise ValueError("scene_occluded: the rays tensor must hold [n][6] floats, n > 0")
             n = rays.numel() // 6
             if out is None:
                 out = torch.empty(n, dtype=torch.uint8, device=rays.device)
-            if (out.dtype not in (torch.uint8, torch.bool) or not out.is_contiguous() or not out.is_cuda or out.device.index != self._device
-                    or out.numel() != n):
+            if not self._on_device(out, torch.uint8, torch.bool) or out.numel() != n:
                 raise ValueError("scene_occluded: out must be a contiguous torch.uint8 or torch.bool tensor [n] on the context's device")
             _check(lib().rtw_ctx_scene_occluded(self._h, C.c_void_p(int(rays.data_ptr())), n, float(time), float(mint), float(maxt), int(accel),
                                                 C.c_void_p(int(out.data_ptr())), C.byref(st)), "rtw_ctx_scene_occluded")
@@ -1561,17 +1566,14 @@ class Renderer:
         args = (int(samples), int(seed) & 0xFFFFFFFF, float(time), float(mint), float(radius), int(accel))
         if hasattr(points, "data_ptr") or hasattr(normals, "data_ptr"):
             import torch
-            for t in (points, normals):
-                if (not hasattr(t, "data_ptr") or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda
-                        or t.device.index != self._device):
-                    raise ValueError("ambient_occlusion: points and normals must both be float32 tensors, contiguous and on the context's device")
+            if not (self._on_device(points) and self._on_device(normals)):
+                raise ValueError("ambient_occlusion: points and normals must both be float32 tensors, contiguous and on the context's device")
             if points.numel() == 0 or points.numel() % 3 or normals.numel() != points.numel():
                 raise ValueError("ambient_occlusion: points and normals must both hold [n][3] floats, n > 0")
             n = points.numel() // 3
             if out is None:
                 out = torch.empty(n, dtype=torch.float32, device=points.device)
-            if (not hasattr(out, "data_ptr") or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda
-                    or out.device.index != self._device or out.numel() != n):
+            if not self._on_device(out) or out.numel() != n:
                 raise ValueError("ambient_occlusion: out must be a contiguous torch.float32 tensor [n] on the context's device")
             _check(lib().rtw_ctx_ambient_occlusion(self._h, C.c_void_p(int(points.data_ptr())), C.c_void_p(int(normals.data_ptr())), n, *args,
                                                    C.c_void_p(int(out.data_ptr())), C.byref(st)), "rtw_ctx_ambient_occlusion")

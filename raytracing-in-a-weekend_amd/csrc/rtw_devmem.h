@@ -31,4 +31,11 @@ struct Mem {
 using DevMem = Mem<false>;
 using PinnedMem = Mem<true>;
 
+// Is `p` memory the kernels of GPU `device` can address (device or managed memory of that GPU)?  Anything else is staged.
+inline bool on_device(const void *p, int device) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged) && a.device == device;
+}
+
 } // namespace rtw

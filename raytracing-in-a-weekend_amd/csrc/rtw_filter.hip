@@ -512,12 +512,6 @@ void filter_scratch_free(FilterScratch *f) {
 }
 
 namespace {
-bool on_device(const void *p, int device) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged) && a.device == device;
-}
-
 float event_ms(hipEvent_t a, hipEvent_t b) {
     float ms = 0.0f;
     return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f;

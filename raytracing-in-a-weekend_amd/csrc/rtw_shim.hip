@@ -236,6 +236,139 @@ static int count_hip_runtimes_cb(struct dl_phdr_info *info, size_t, void *data) 
     return 0;
 }
 
+// ---- what the calls that stage and the scene query passes share ----------------------------------------------------------------------
+// The end of a call that works through temporaries of its own (a Staging): `e` is what its chain of HIP calls came to.  After a failure the
+// stream is waited for first -- part of the chain may have been enqueued, and nothing may still use the temporaries when the caller's scope frees them.
+static int call_status(rtw_ctx *c, hipError_t e) {
+    if (e == hipSuccess) return RTW_OK;
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipGetLastError();
+    g_last_hip = (int)e;
+    return e == hipErrorOutOfMemory ? RTW_E_NOMEM : RTW_E_HIP;
+}
+
+// The caller pointers of one call, as addresses this context's kernels can use: the caller's own where it is this GPU's memory (on_device, asked
+// once per pointer), else a temporary -- always one with `always` (the calls whose documented arrays are host arrays).  Everything is enqueued on
+// c->stream, so an input is read behind the caller's producers; `e` is the call's chain of HIP results, and after a failure nothing more is
+// enqueued.  The temporaries live as long as the object: declare it in the entry point, so that they die after call_status has run.
+struct Staging {
+    hipError_t e = hipSuccess;
+
+    explicit Staging(rtw_ctx *ctx, bool always_stage = false) : c(ctx), always(always_stage) {}
+    // a temporary of `bytes` that nobody gets back
+    template <class T = void> T *scratch(size_t bytes) {
+        if (n_tmp == MAX) { if (e == hipSuccess) e = hipErrorInvalidValue; return nullptr; }
+        DevMem &m = tmp[n_tmp++];
+        if (e == hipSuccess) e = m.reserve(bytes);
+        return m.as<T>();
+    }
+    // an input of `bytes`: a temporary gets the copy in enqueued
+    template <class T> const T *in(const T *p, size_t bytes) {
+        if (!always && on_device(p, c->device)) return p;
+        T *d = scratch<T>(bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d, p, bytes, hipMemcpyDefault, c->stream);
+        return d;
+    }
+    // an output of `bytes`: a temporary is noted for copy_out
+    template <class T> T *out(T *p, size_t bytes) {
+        if (!always && on_device(p, c->device)) return p;
+        T *d = scratch<T>(bytes);
+        if (d) back[n_back++] = { p, d, bytes };
+        return d;
+    }
+    // enqueue the copies of all staged outputs to their callers, in the order they were asked for
+    hipError_t copy_out() {
+        for (int i = 0; i < n_back; i++)
+            if (e == hipSuccess) e = hipMemcpyAsync(back[i].dst, back[i].src, back[i].bytes, hipMemcpyDefault, c->stream);
+        return e;
+    }
+    // the end of a call without counters: the copies out, the call's one synchronise, its status
+    int finish() {
+        if (copy_out() == hipSuccess) e = hipStreamSynchronize(c->stream);
+        return call_status(c, e);
+    }
+
+private:
+    static constexpr int MAX = 6;        // (rtw_ctx_mesh_instance_hits stages six)
+    struct Back { void *dst; const void *src; size_t bytes; };
+    rtw_ctx *c;
+    bool always;
+    DevMem tmp[MAX];
+    Back back[MAX];
+    int n_tmp = 0, n_back = 0;
+};
+
+// The triangle view a render or query of this context uses: the tree only for RTW_ACCEL_BVH and a range the cull's derivation covers
+static DevTris tri_view(const rtw_ctx *c, uint32_t accel, float mint, float maxt) {
+    DevTris t = c->tris;
+    const float tb = std::fmax(std::fabs(mint), std::fabs(maxt));
+    t.t_bound = tb;
+    const bool range_ok = std::isfinite(mint) && std::isfinite(maxt) && tb <= RTW_TRI_COORD_MAX;
+    t.nodes = (accel == RTW_ACCEL_BVH && c->tri_tree && range_ok) ? c->tri_mem.nodes.as<TriNode>() : nullptr;
+    return t;
+}
+
+// ... and the top-level tree over its placements: only next to the mesh's own tree (T = tri_view's answer: RTW_ACCEL_BVH, a mesh and a range
+// the cull covers), for more than RTW_OPT_MESH_LIST_MAX placements and while none of them lies beyond the reach of the tree's bound; else null,
+// and the placements are met in list order (the same answer)
+static const TriNode *mesh_top_view(const rtw_ctx *c, const DevTris &T) {
+    return (T.nodes != nullptr && c->n_mesh > c->opt_mesh_list_max && c->mesh_top_ok) ? c->mesh_top : nullptr;
+}
+
+// Does a query's sphere group go through the tree?  The conditions a render puts on it (render_enqueue_impl); the per-ray ones are checked by
+// the kernels, ray by ray.  ONE definition for the closest-hit and the any-hit query: rtw_ctx_scene_occluded's contract is stated against
+// rtw_ctx_scene_hits with the same arguments.
+static bool query_uses_tree(const rtw_ctx *c, uint32_t accel, float time, float mint, float maxt) {
+    bool tree = accel == RTW_ACCEL_BVH && c->bvh_ok && c->sc.n > c->opt_list_walk_max;
+    if (mint != mint || maxt != maxt || time != time) tree = false;
+    if (!(c->scene_span <= 1e18)) tree = false;
+    if (c->sc.moving && !(time >= c->t_begin && time <= c->t_end)) tree = false;
+    return tree;
+}
+
+// The scene views, the range and the counters of a launch over n rays or points: everything QueryArgs and OccludedArgs share by name, the rest
+// zero.  ONE definition for the closest-hit, the any-hit and the AO kernels, so that they walk the same groups through the same trees.
+template <class A>
+static void scene_views(const rtw_ctx *c, uint32_t n, float time, float mint, float maxt, uint32_t accel, A &q) {
+    std::memset(&q, 0, sizeof q);
+    q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom; q.inst_quats = c->inst_quats;
+    if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
+    q.mesh_rows = c->mesh_rows; q.n_mesh = c->n_mesh;
+    if (c->mesh_rows) { q.mesh_top = mesh_top_view(c, q.tris); q.n_mesh_top = c->n_mesh_top; }
+    q.n = n; q.levels = c->bvh.depth + 2u;
+    q.time = time; q.mint = mint; q.maxt = maxt; q.span = (float)c->scene_span;
+    q.counters = c->scr.qstats.as<unsigned long long>();
+}
+
+// The frame of a pass that counts (scr.qstats), on c->stream: the counters zeroed, ev0, each of `launch` in turn, ev1, the staged outputs to
+// their callers, the counters to scr.h_qstats, the call's one synchronise; then the counter lines (RTW_QUERY_SLOTS) summed into `stats` with
+// segments = `samples` per point that cast rays (counter 4) + `extra`.  RTW_E_INTERNAL when a wave's stack was too short (counter 3).
+template <class... Launch>
+static int counted_pass(rtw_ctx *c, Staging &st, uint32_t samples, uint64_t extra, RtwStats *stats, Launch &&...launch) {
+    const size_t q_bytes = RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long);
+    hipError_t &e = st.e;
+    if (e == hipSuccess) e = hipMemsetAsync(c->scr.qstats.ptr, 0, q_bytes, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+    const auto run = [&e](auto &one) { if (e == hipSuccess) { one(); e = hipGetLastError(); } };
+    (run(launch), ...);
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (st.copy_out() == hipSuccess) e = hipMemcpyAsync(c->scr.h_qstats.ptr, c->scr.qstats.ptr, q_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    if (const int rc = call_status(c, e)) return rc;
+    const unsigned long long *h_qstats = c->scr.h_qstats.as<unsigned long long>();
+    unsigned long long sum[5] = { 0, 0, 0, 0, 0 };
+    for (uint32_t s = 0; s < RTW_QUERY_SLOTS; s++) for (int k = 0; k < 5; k++) sum[k] += h_qstats[s * RTW_QUERY_STRIDE + k];
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        stats->segments = sum[4] * samples + extra;
+        stats->sphere_tests = sum[0]; stats->node_tests = sum[1]; stats->quad_tests = sum[2];
+        stats->kernel_ms = ms;
+    }
+    return sum[3] ? RTW_E_INTERNAL : RTW_OK;
+}
+
 extern "C" {
 
 int rtw_abi_version(void) { return RTW_ABI_VERSION; }
@@ -804,8 +937,6 @@ int rtw_ctx_set_triangles(rtw_ctx *c, const RtwTriangle *tris, uint32_t n) {
 
 // The triangles move, the tree's topology stays (rtw.h "refit"; device code: rtw_refit.hip).  On the context's stream, behind the caller's
 // producers of `ouv`; one synchronise at the end for the count of refused triangles and the new root.
-static int call_status(rtw_ctx *c, hipError_t e);
-static bool query_on_device(const rtw_ctx *c, const void *p);
 int rtw_ctx_refit_triangles(rtw_ctx *c, const float *ouv, uint32_t n, uint32_t *list_walk_out) {
     if (!c) return RTW_E_INVALID;
     if (!c->tris.n) return RTW_E_NO_SCENE;
@@ -815,7 +946,7 @@ int rtw_ctx_refit_triangles(rtw_ctx *c, const float *ouv, uint32_t n, uint32_t *
     unsigned char *back = c->scr.h_refit.as<unsigned char>();
     hipError_t e = hipSuccess;
     const float *src = ouv;
-    if (!query_on_device(c, ouv)) {
+    if (!on_device(ouv, c->device)) {
         e = hipMemcpyAsync(m.ouv.ptr, ouv, REFIT_OUV_BYTES * (size_t)n, hipMemcpyDefault, c->stream);
         src = m.ouv.as<const float>();
     }
@@ -909,11 +1040,11 @@ int rtw_ctx_move_mesh_instances(rtw_ctx *c, const float *poses, uint32_t n, cons
     unsigned char *back = c->scr.h_refit.as<unsigned char>();
     hipError_t e = hipSuccess;
     const float *src_ouv = ouv, *src_poses = poses;
-    if (ouv && !query_on_device(c, ouv)) {
+    if (ouv && !on_device(ouv, c->device)) {
         e = hipMemcpyAsync(t.ouv.ptr, ouv, REFIT_OUV_BYTES * (size_t)n_tris, hipMemcpyDefault, c->stream);
         src_ouv = t.ouv.as<const float>();
     }
-    if (e == hipSuccess && poses && !query_on_device(c, poses)) {
+    if (e == hipSuccess && poses && !on_device(poses, c->device)) {
         e = hipMemcpyAsync(m.poses.ptr, poses, MOVE_POSE_BYTES * (size_t)n, hipMemcpyDefault, c->stream);
         src_poses = m.poses.as<const float>();
     }
@@ -967,33 +1098,6 @@ static int mesh_render_check(bool placements, uint32_t integrator, bool mixed_ac
     return RTW_OK;
 }
 
-// The end of a call that works through temporaries of its own (DevMem locals): `e` is what its chain of HIP calls came to.  After a failure the
-// stream is waited for first -- part of the chain may have been enqueued, and nothing may still use the temporaries when the caller's scope frees them.
-static int call_status(rtw_ctx *c, hipError_t e) {
-    if (e == hipSuccess) return RTW_OK;
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipGetLastError();
-    g_last_hip = (int)e;
-    return e == hipErrorOutOfMemory ? RTW_E_NOMEM : RTW_E_HIP;
-}
-
-// The triangle view a render or query of this context uses: the tree only for RTW_ACCEL_BVH and a range the cull's derivation covers
-static DevTris tri_view(const rtw_ctx *c, uint32_t accel, float mint, float maxt) {
-    DevTris t = c->tris;
-    const float tb = std::fmax(std::fabs(mint), std::fabs(maxt));
-    t.t_bound = tb;
-    const bool range_ok = std::isfinite(mint) && std::isfinite(maxt) && tb <= RTW_TRI_COORD_MAX;
-    t.nodes = (accel == RTW_ACCEL_BVH && c->tri_tree && range_ok) ? c->tri_mem.nodes.as<TriNode>() : nullptr;
-    return t;
-}
-
-// ... and the top-level tree over its placements: only next to the mesh's own tree (T = tri_view's answer: RTW_ACCEL_BVH, a mesh and a range
-// the cull covers), for more than RTW_OPT_MESH_LIST_MAX placements and while none of them lies beyond the reach of the tree's bound; else null,
-// and the placements are met in list order (the same answer)
-static const TriNode *mesh_top_view(const rtw_ctx *c, const DevTris &T) {
-    return (T.nodes != nullptr && c->n_mesh > c->opt_mesh_list_max && c->mesh_top_ok) ? c->mesh_top : nullptr;
-}
-
 int rtw_ctx_triangle_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float mint, float maxt, uint32_t accel,
                           float *t_out, int32_t *idx_out, RtwStats *stats) {
     if (!c || !rays || !t_out || !idx_out || n_rays == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
@@ -1001,24 +1105,19 @@ int rtw_ctx_triangle_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float 
     if (!c->tris.n) return RTW_E_NO_SCENE;
     HIP_TRY(hipSetDevice(c->device));
     const DevTris T = tri_view(c, accel, mint, maxt);
-    const size_t ray_bytes = 6 * sizeof(float) * (size_t)n_rays, t_bytes = sizeof(float) * (size_t)n_rays, i_bytes = sizeof(int32_t) * (size_t)n_rays;
-    DevMem d_r, d_t, d_i, d_c;
+    const size_t t_bytes = sizeof(float) * (size_t)n_rays, i_bytes = sizeof(int32_t) * (size_t)n_rays;
+    Staging st(c, true);
     unsigned long long cnt[2] = { 0, 0 };
-    hipError_t e = d_r.reserve(ray_bytes);
-    if (e == hipSuccess) e = d_t.reserve(t_bytes);
-    if (e == hipSuccess) e = d_i.reserve(i_bytes);
-    if (e == hipSuccess) e = d_c.reserve(sizeof cnt);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_r.ptr, rays, ray_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_c.ptr, 0, sizeof cnt, c->stream);
-    if (e == hipSuccess) {
-        launch_tri_hits(T, d_r.as<const float>(), n_rays, mint, maxt, d_t.as<float>(), d_i.as<int32_t>(), d_c.as<unsigned long long>(), c->stream);
-        e = hipGetLastError();
+    const float *d_r = st.in(rays, 6 * t_bytes);
+    float *d_t = st.out(t_out, t_bytes);
+    int32_t *d_i = st.out(idx_out, i_bytes);
+    unsigned long long *d_c = st.out(cnt, sizeof cnt);
+    if (st.e == hipSuccess) st.e = hipMemsetAsync(d_c, 0, sizeof cnt, c->stream);
+    if (st.e == hipSuccess) {
+        launch_tri_hits(T, d_r, n_rays, mint, maxt, d_t, d_i, d_c, c->stream);
+        st.e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(t_out, d_t.ptr, t_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(idx_out, d_i.ptr, i_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt, d_c.ptr, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (const int rc = call_status(c, e)) return rc;
+    if (const int rc = st.finish()) return rc;
     if (stats) { std::memset(stats, 0, sizeof *stats); stats->quad_tests = cnt[0]; stats->node_tests = cnt[1]; }
     return RTW_OK;
 }
@@ -1030,66 +1129,26 @@ int rtw_ctx_mesh_instance_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, f
     if (!c->mesh_rows) return RTW_E_NO_SCENE;
     HIP_TRY(hipSetDevice(c->device));
     const DevTris T = tri_view(c, accel, mint, maxt);
-    const size_t ray_bytes = 6 * sizeof(float) * (size_t)n_rays, t_bytes = sizeof(float) * (size_t)n_rays, i_bytes = sizeof(int32_t) * (size_t)n_rays;
-    DevMem d_r, d_t, d_p, d_i, d_n, d_c;
+    const size_t t_bytes = sizeof(float) * (size_t)n_rays, i_bytes = sizeof(int32_t) * (size_t)n_rays;
+    Staging st(c, true);
     unsigned long long cnt[2] = { 0, 0 };
-    hipError_t e = d_r.reserve(ray_bytes);
-    if (e == hipSuccess) e = d_t.reserve(t_bytes);
-    if (e == hipSuccess) e = d_p.reserve(i_bytes);
-    if (e == hipSuccess) e = d_i.reserve(i_bytes);
-    if (e == hipSuccess && normal_out) e = d_n.reserve(3 * t_bytes);
-    if (e == hipSuccess) e = d_c.reserve(sizeof cnt);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_r.ptr, rays, ray_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_c.ptr, 0, sizeof cnt, c->stream);
-    if (e == hipSuccess) {
-        launch_mesh_hits(T, c->mesh_rows, c->n_mesh, mesh_top_view(c, T), c->n_mesh_top, d_r.as<const float>(), n_rays, mint, maxt, d_t.as<float>(), d_p.as<int32_t>(), d_i.as<int32_t>(),
-                         normal_out ? d_n.as<float>() : nullptr, d_c.as<unsigned long long>(), c->stream);
-        e = hipGetLastError();
+    const float *d_r = st.in(rays, 6 * t_bytes);
+    float *d_t = st.out(t_out, t_bytes);
+    int32_t *d_p = st.out(placement_out, i_bytes);
+    int32_t *d_i = st.out(tri_out, i_bytes);
+    float *d_n = normal_out ? st.out(normal_out, 3 * t_bytes) : nullptr;
+    unsigned long long *d_c = st.out(cnt, sizeof cnt);
+    if (st.e == hipSuccess) st.e = hipMemsetAsync(d_c, 0, sizeof cnt, c->stream);
+    if (st.e == hipSuccess) {
+        launch_mesh_hits(T, c->mesh_rows, c->n_mesh, mesh_top_view(c, T), c->n_mesh_top, d_r, n_rays, mint, maxt, d_t, d_p, d_i, d_n, d_c, c->stream);
+        st.e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(t_out, d_t.ptr, t_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(placement_out, d_p.ptr, i_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(tri_out, d_i.ptr, i_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && normal_out) e = hipMemcpyAsync(normal_out, d_n.ptr, 3 * t_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt, d_c.ptr, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (const int rc = call_status(c, e)) return rc;
+    if (const int rc = st.finish()) return rc;
     if (stats) { std::memset(stats, 0, sizeof *stats); stats->quad_tests = cnt[0]; stats->node_tests = cnt[1]; }
     return RTW_OK;
 }
 
 // ---- scene ray queries (rtw.h "scene ray queries"; kernel: rtw_query.hip) ------------------------------------------------------------
-// Is `p` memory this context's kernels can address (device or managed memory of its GPU)?  Anything else is staged.
-static bool query_on_device(const rtw_ctx *c, const void *p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) && attr.device == c->device;
-}
-
-// Does a query's sphere group go through the tree?  The conditions a render puts on it (render_enqueue_impl); the per-ray ones are checked by
-// the kernels, ray by ray.  ONE definition for the closest-hit and the any-hit query: rtw_ctx_scene_occluded's contract is stated against
-// rtw_ctx_scene_hits with the same arguments.
-static bool query_uses_tree(const rtw_ctx *c, uint32_t accel, float time, float mint, float maxt) {
-    bool tree = accel == RTW_ACCEL_BVH && c->bvh_ok && c->sc.n > c->opt_list_walk_max;
-    if (mint != mint || maxt != maxt || time != time) tree = false;
-    if (!(c->scene_span <= 1e18)) tree = false;
-    if (c->sc.moving && !(time >= c->t_begin && time <= c->t_end)) tree = false;
-    return tree;
-}
-
-// The counters of a query launch (scr.h_qstats: RTW_QUERY_SLOTS lines) summed into `stats`; RTW_E_INTERNAL when a wave's stack was too short
-static int query_stats(const rtw_ctx *c, uint32_t n, float ms, RtwStats *stats) {
-    const unsigned long long *h_qstats = c->scr.h_qstats.as<unsigned long long>();
-    unsigned long long sum[4] = { 0, 0, 0, 0 };
-    for (uint32_t s = 0; s < RTW_QUERY_SLOTS; s++) for (int k = 0; k < 4; k++) sum[k] += h_qstats[s * RTW_QUERY_STRIDE + k];
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->segments = n;
-        stats->sphere_tests = sum[0]; stats->node_tests = sum[1]; stats->quad_tests = sum[2];
-        stats->kernel_ms = ms;
-    }
-    return sum[3] ? RTW_E_INTERNAL : RTW_OK;
-}
-
 // Both calls: cam != null builds the rays of a width x height map in the kernel, else `rays` [n][6] are read.
 static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, const float *rays, uint32_t n, float time, float mint,
                        float maxt, uint32_t accel, float miss_t, float *t_out, int32_t *idx_out, float *normal_out, RtwStats *stats) {
@@ -1099,54 +1158,17 @@ static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_
     const bool tree = query_uses_tree(c, accel, time, mint, maxt);
 
     QueryArgs q;
-    std::memset(&q, 0, sizeof q);
-    q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom; q.inst_quats = c->inst_quats;
-    if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
-    q.mesh_rows = c->mesh_rows; q.n_mesh = c->n_mesh;
-    if (c->mesh_rows) { q.mesh_top = mesh_top_view(c, q.tris); q.n_mesh_top = c->n_mesh_top; }
+    scene_views(c, n, time, mint, maxt, accel, q);
     if (cam) { q.cam = *cam; q.width = width; q.height = height; }
-    q.n = n; q.levels = c->bvh.depth + 2u;
-    q.time = time; q.mint = mint; q.maxt = maxt; q.miss_t = miss_t; q.span = (float)c->scene_span;
-    q.counters = c->scr.qstats.as<unsigned long long>();
+    q.miss_t = miss_t;
 
-    const size_t ray_bytes = 6 * sizeof(float) * (size_t)n, t_bytes = sizeof(float) * (size_t)n, i_bytes = sizeof(int32_t) * (size_t)n;
-    DevMem d_r, d_t, d_i, d_n;           // staging, for whatever is not this GPU's memory
-    hipError_t e = hipSuccess;
-    if (rays) {
-        if (query_on_device(c, rays)) q.rays = rays;
-        else {
-            e = d_r.reserve(ray_bytes);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_r.ptr, rays, ray_bytes, hipMemcpyDefault, c->stream);
-            q.rays = d_r.as<const float>();
-        }
-    }
-    if (query_on_device(c, t_out)) q.t_out = t_out;
-    else { if (e == hipSuccess) e = d_t.reserve(t_bytes); q.t_out = d_t.as<float>(); }
-    if (idx_out) {
-        if (query_on_device(c, idx_out)) q.idx_out = idx_out;
-        else { if (e == hipSuccess) e = d_i.reserve(i_bytes); q.idx_out = d_i.as<int32_t>(); }
-    }
-    if (normal_out) {
-        if (query_on_device(c, normal_out)) q.normal_out = normal_out;
-        else { if (e == hipSuccess) e = d_n.reserve(3 * t_bytes); q.normal_out = d_n.as<float>(); }
-    }
-    const size_t q_bytes = RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long);
-    if (e == hipSuccess) e = hipMemsetAsync(c->scr.qstats.ptr, 0, q_bytes, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-    if (e == hipSuccess) {
-        launch_scene_hits(q, cam != nullptr, tree, c->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess && d_t.ptr) e = hipMemcpyAsync(t_out, d_t.ptr, t_bytes, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess && d_i.ptr) e = hipMemcpyAsync(idx_out, d_i.ptr, i_bytes, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess && d_n.ptr) e = hipMemcpyAsync(normal_out, d_n.ptr, 3 * t_bytes, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->scr.h_qstats.ptr, c->scr.qstats.ptr, q_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    if (const int rc = call_status(c, e)) return rc;
-    return query_stats(c, n, ms, stats);
+    const size_t t_bytes = sizeof(float) * (size_t)n;
+    Staging st(c);
+    if (rays) q.rays = st.in(rays, 6 * t_bytes);
+    q.t_out = st.out(t_out, t_bytes);
+    if (idx_out) q.idx_out = st.out(idx_out, sizeof(int32_t) * (size_t)n);
+    if (normal_out) q.normal_out = st.out(normal_out, 3 * t_bytes);
+    return counted_pass(c, st, 0, n, stats, [&] { launch_scene_hits(q, cam != nullptr, tree, c->stream); });
 }
 
 int rtw_ctx_scene_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, float time, float mint, float maxt, uint32_t accel,
@@ -1162,18 +1184,6 @@ int rtw_ctx_depth_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t
     return scene_query(c, cam, width, height, nullptr, width * height, time, mint, maxt, accel, host_mul(maxt, 1.6f), depth_out, idx_out, normal_out, stats);
 }
 
-// The views and the range of an any-hit launch over n rays (rtw_ctx_scene_occluded) or n points (ambient occlusion, below)
-static void occluded_views(const rtw_ctx *c, uint32_t n, float time, float mint, float maxt, uint32_t accel, OccludedArgs &q) {
-    std::memset(&q, 0, sizeof q);
-    q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom; q.inst_quats = c->inst_quats;
-    if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
-    q.mesh_rows = c->mesh_rows; q.n_mesh = c->n_mesh;
-    if (c->mesh_rows) { q.mesh_top = mesh_top_view(c, q.tris); q.n_mesh_top = c->n_mesh_top; }
-    q.n = n; q.levels = c->bvh.depth + 2u;
-    q.time = time; q.mint = mint; q.maxt = maxt; q.span = (float)c->scene_span;
-    q.counters = c->scr.qstats.as<unsigned long long>();
-}
-
 // The any-hit pass (rtw.h "occlusion queries"; kernel: rtw_occluded.hip): scene_query's conditions, views, staging and stream order
 int rtw_ctx_scene_occluded(rtw_ctx *c, const float *rays, uint32_t n, float time, float mint, float maxt, uint32_t accel, uint8_t *occluded_out,
                            RtwStats *stats) {
@@ -1184,54 +1194,18 @@ int rtw_ctx_scene_occluded(rtw_ctx *c, const float *rays, uint32_t n, float time
     const bool tree = query_uses_tree(c, accel, time, mint, maxt);
 
     OccludedArgs q;
-    occluded_views(c, n, time, mint, maxt, accel, q);
-
-    const size_t ray_bytes = 6 * sizeof(float) * (size_t)n;
-    DevMem d_r, d_o;                     // staging, for whatever is not this GPU's memory
-    hipError_t e = hipSuccess;
-    if (query_on_device(c, rays)) q.rays = rays;
-    else {
-        e = d_r.reserve(ray_bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_r.ptr, rays, ray_bytes, hipMemcpyDefault, c->stream);
-        q.rays = d_r.as<const float>();
-    }
-    if (query_on_device(c, occluded_out)) q.out = occluded_out;
-    else { if (e == hipSuccess) e = d_o.reserve(n); q.out = d_o.as<uint8_t>(); }
-    const size_t q_bytes = RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long);
-    if (e == hipSuccess) e = hipMemsetAsync(c->scr.qstats.ptr, 0, q_bytes, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-    if (e == hipSuccess) {
-        launch_scene_occluded(q, tree, c->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess && d_o.ptr) e = hipMemcpyAsync(occluded_out, d_o.ptr, n, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->scr.h_qstats.ptr, c->scr.qstats.ptr, q_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    if (const int rc = call_status(c, e)) return rc;
-    return query_stats(c, n, ms, stats);
+    scene_views(c, n, time, mint, maxt, accel, q);
+    Staging st(c);
+    q.rays = st.in(rays, 6 * sizeof(float) * (size_t)n);
+    q.out = st.out(occluded_out, n);
+    return counted_pass(c, st, 0, n, stats, [&] { launch_scene_occluded(q, tree, c->stream); });
 }
 
 // ---- ambient occlusion (rtw.h "ambient occlusion"; kernel: rtw_occluded.hip; the rule: rtw_ao.h) ----------------------------------------
-static uint32_t ao_lg_group(uint32_t samples) {
-    uint32_t lg = 0;
-    while ((1u << lg) < samples && lg < 6u) lg++;
-    return lg;
-}
-// query_stats with the rays counted by the kernel: `samples` per point that cast rays, plus `extra` (the depth pass's)
-static int ao_stats(const rtw_ctx *c, uint32_t samples, uint64_t extra, float ms, RtwStats *stats) {
-    const unsigned long long *h_qstats = c->scr.h_qstats.as<unsigned long long>();
-    unsigned long long sum[5] = { 0, 0, 0, 0, 0 };
-    for (uint32_t s = 0; s < RTW_QUERY_SLOTS; s++) for (int k = 0; k < 5; k++) sum[k] += h_qstats[s * RTW_QUERY_STRIDE + k];
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->segments = sum[4] * samples + extra;
-        stats->sphere_tests = sum[0]; stats->node_tests = sum[1]; stats->quad_tests = sum[2];
-        stats->kernel_ms = ms;
-    }
-    return sum[3] ? RTW_E_INTERNAL : RTW_OK;
+// The sampling fields of an AO launch; a.q: scene_views over the points and the range of the AO rays
+static void ao_sampling(uint32_t samples, uint32_t seed, AoArgs &a) {
+    a.samples = samples; a.seed = seed; a.lg_group = 0;
+    while ((1u << a.lg_group) < samples && a.lg_group < 6u) a.lg_group++;
 }
 
 int rtw_ctx_ambient_occlusion(rtw_ctx *c, const float *points, const float *normals, uint32_t n, uint32_t samples, uint32_t seed, float time,
@@ -1245,41 +1219,15 @@ int rtw_ctx_ambient_occlusion(rtw_ctx *c, const float *points, const float *norm
 
     AoArgs a;
     std::memset(&a, 0, sizeof a);
-    occluded_views(c, n, time, mint, maxt, accel, a.q);
-    a.samples = samples; a.seed = seed; a.lg_group = ao_lg_group(samples);
+    scene_views(c, n, time, mint, maxt, accel, a.q);
+    ao_sampling(samples, seed, a);
 
-    const size_t v_bytes = 3 * sizeof(float) * (size_t)n, o_bytes = sizeof(float) * (size_t)n;
-    DevMem d_p, d_n, d_o;                // staging, for whatever is not this GPU's memory
-    hipError_t e = hipSuccess;
-    if (query_on_device(c, points)) a.points = points;
-    else {
-        e = d_p.reserve(v_bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_p.ptr, points, v_bytes, hipMemcpyDefault, c->stream);
-        a.points = d_p.as<const float>();
-    }
-    if (query_on_device(c, normals)) a.normals = normals;
-    else {
-        if (e == hipSuccess) e = d_n.reserve(v_bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_n.ptr, normals, v_bytes, hipMemcpyDefault, c->stream);
-        a.normals = d_n.as<const float>();
-    }
-    if (query_on_device(c, ao_out)) a.ao_out = ao_out;
-    else { if (e == hipSuccess) e = d_o.reserve(o_bytes); a.ao_out = d_o.as<float>(); }
-    const size_t q_bytes = RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long);
-    if (e == hipSuccess) e = hipMemsetAsync(c->scr.qstats.ptr, 0, q_bytes, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-    if (e == hipSuccess) {
-        launch_ambient_occlusion(a, false, tree, c->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess && d_o.ptr) e = hipMemcpyAsync(ao_out, d_o.ptr, o_bytes, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->scr.h_qstats.ptr, c->scr.qstats.ptr, q_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    if (const int rc = call_status(c, e)) return rc;
-    return ao_stats(c, samples, 0, ms, stats);
+    const size_t v_bytes = 3 * sizeof(float) * (size_t)n;
+    Staging st(c);
+    a.points = st.in(points, v_bytes);
+    a.normals = st.in(normals, v_bytes);
+    a.ao_out = st.out(ao_out, sizeof(float) * (size_t)n);
+    return counted_pass(c, st, samples, 0, stats, [&] { launch_ambient_occlusion(a, false, tree, c->stream); });
 }
 
 // rtw_ctx_depth_map with ids and normals into the caller's device buffers or scratch, then the AO kernel's camera form over them: two launches
@@ -1293,58 +1241,27 @@ int rtw_ctx_ao_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t he
     if (!c->has_scene) return RTW_E_NO_SCENE;
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t n = width * height;
+    const bool tree = query_uses_tree(c, accel, time, mint, maxt), ao_tree = query_uses_tree(c, accel, time, ao_mint, ao_maxt);
 
     QueryArgs q;                         // the depth pass: scene_query's launch
-    std::memset(&q, 0, sizeof q);
-    q.sc = c->sc; q.bvh = c->bvh; q.geom = c->geom; q.inst_quats = c->inst_quats;
-    if (c->tris.n) q.tris = tri_view(c, accel, mint, maxt);
-    q.mesh_rows = c->mesh_rows; q.n_mesh = c->n_mesh;
-    if (c->mesh_rows) { q.mesh_top = mesh_top_view(c, q.tris); q.n_mesh_top = c->n_mesh_top; }
+    scene_views(c, n, time, mint, maxt, accel, q);
     q.cam = *cam; q.width = width; q.height = height;
-    q.n = n; q.levels = c->bvh.depth + 2u;
-    q.time = time; q.mint = mint; q.maxt = maxt; q.miss_t = host_mul(maxt, 1.6f); q.span = (float)c->scene_span;
-    q.counters = c->scr.qstats.as<unsigned long long>();
+    q.miss_t = host_mul(maxt, 1.6f);
 
     AoArgs a;
     std::memset(&a, 0, sizeof a);
-    occluded_views(c, n, time, ao_mint, ao_maxt, accel, a.q);
-    a.samples = samples; a.seed = seed; a.lg_group = ao_lg_group(samples);
+    scene_views(c, n, time, ao_mint, ao_maxt, accel, a.q);
+    ao_sampling(samples, seed, a);
     a.cam = *cam; a.width = width; a.height = height;
 
     const size_t t_bytes = sizeof(float) * (size_t)n, i_bytes = sizeof(int32_t) * (size_t)n;
-    DevMem d_t, d_i, d_n, d_o;           // the depth pass's outputs where the caller gave no device memory for them, and staging
-    hipError_t e = hipSuccess;
-    if (depth_out && query_on_device(c, depth_out)) q.t_out = depth_out;
-    else { e = d_t.reserve(t_bytes); q.t_out = d_t.as<float>(); }
-    if (idx_out && query_on_device(c, idx_out)) q.idx_out = idx_out;
-    else { if (e == hipSuccess) e = d_i.reserve(i_bytes); q.idx_out = d_i.as<int32_t>(); }
-    if (normal_out && query_on_device(c, normal_out)) q.normal_out = normal_out;
-    else { if (e == hipSuccess) e = d_n.reserve(3 * t_bytes); q.normal_out = d_n.as<float>(); }
-    if (query_on_device(c, ao_out)) a.ao_out = ao_out;
-    else { if (e == hipSuccess) e = d_o.reserve(t_bytes); a.ao_out = d_o.as<float>(); }
-    a.depth = q.t_out; a.idx = q.idx_out; a.normals = q.normal_out;
-    const size_t q_bytes = RTW_QUERY_SLOTS * RTW_QUERY_STRIDE * sizeof(unsigned long long);
-    if (e == hipSuccess) e = hipMemsetAsync(c->scr.qstats.ptr, 0, q_bytes, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-    if (e == hipSuccess) {
-        launch_scene_hits(q, true, query_uses_tree(c, accel, time, mint, maxt), c->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        launch_ambient_occlusion(a, true, query_uses_tree(c, accel, time, ao_mint, ao_maxt), c->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (e == hipSuccess && d_o.ptr) e = hipMemcpyAsync(ao_out, d_o.ptr, t_bytes, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess && d_t.ptr && depth_out) e = hipMemcpyAsync(depth_out, d_t.ptr, t_bytes, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess && d_i.ptr && idx_out) e = hipMemcpyAsync(idx_out, d_i.ptr, i_bytes, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess && d_n.ptr && normal_out) e = hipMemcpyAsync(normal_out, d_n.ptr, 3 * t_bytes, hipMemcpyDefault, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->scr.h_qstats.ptr, c->scr.qstats.ptr, q_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    if (const int rc = call_status(c, e)) return rc;
-    return ao_stats(c, samples, n, ms, stats);
+    Staging st(c);                       // the depth pass's outputs are scratch where the caller did not ask for them
+    a.ao_out = st.out(ao_out, t_bytes);
+    a.depth = q.t_out = depth_out ? st.out(depth_out, t_bytes) : st.scratch<float>(t_bytes);
+    a.idx = q.idx_out = idx_out ? st.out(idx_out, i_bytes) : st.scratch<int32_t>(i_bytes);
+    a.normals = q.normal_out = normal_out ? st.out(normal_out, 3 * t_bytes) : st.scratch<float>(3 * t_bytes);
+    return counted_pass(c, st, samples, n, stats, [&] { launch_scene_hits(q, true, tree, c->stream); },
+                        [&] { launch_ambient_occlusion(a, true, ao_tree, c->stream); });
 }
 
 int rtw_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t turb_depth, float *out) {
@@ -1357,20 +1274,15 @@ int rtw_ctx_perlin_eval(rtw_ctx *c, const RtwPerlin *t, const float *points, uin
     if (!c || !t || !points || !out || n == 0) return RTW_E_INVALID;
     if (c->pend.active) return RTW_E_INVALID;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t pts_bytes = 3 * sizeof(float) * (size_t)n, out_bytes = sizeof(float) * (size_t)n;
-    DevMem d_t, d_p, d_o;
-    hipError_t e = d_t.reserve(sizeof(RtwPerlin));
-    if (e == hipSuccess) e = d_p.reserve(pts_bytes);
-    if (e == hipSuccess) e = d_o.reserve(out_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_t.ptr, t, sizeof(RtwPerlin), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_p.ptr, points, pts_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        launch_perlin_eval(d_t.as<const RtwPerlin>(), d_p.as<const float>(), n, turb_depth, d_o.as<float>(), c->stream);
-        e = hipGetLastError();
+    Staging st(c, true);
+    const RtwPerlin *d_t = st.in(t, sizeof(RtwPerlin));
+    const float *d_p = st.in(points, 3 * sizeof(float) * (size_t)n);
+    float *d_o = st.out(out, sizeof(float) * (size_t)n);
+    if (st.e == hipSuccess) {
+        launch_perlin_eval(d_t, d_p, n, turb_depth, d_o, c->stream);
+        st.e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_o.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    return call_status(c, e);
+    return st.finish();
 }
 
 // The bilateral post-process (rtw_filter.hip) on this context's GPU and stream; the scene is not involved.

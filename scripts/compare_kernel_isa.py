@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Compare the gfx950 kernels of two `make -C raytracing-in-a-weekend_amd/csrc asm` outputs.
 
-    python scripts/compare_kernel_isa.py BEFORE_BUILD_DIR AFTER_BUILD_DIR
+    python scripts/compare_kernel_isa.py BEFORE_BUILD_DIR AFTER_BUILD_DIR [STEM [RESOURCE_FILE]]
 
 Each directory holds what `make asm` writes to csrc/build/: rtw_kernels-hip-amdgcn-amd-amdhsa-gfx950.s and resource_usage.txt.
+STEM names another translation unit of `make asm` (rtw_filter, rtw_query, rtw_occluded, rtw_refit, rtw_mesh_move): its
+STEM-hip-amdgcn-amd-amdhsa-gfx950.s and RESOURCE_FILE, by default make asm's name for it (resource_usage_query.txt for rtw_query).
 For every kernel of BEFORE, its body in AFTER (label to .Lfunc_end, with the .LBB<n>_ / .Lfunc_end<n> numbering normalised) and
 its resource lines (VGPRs / SGPRs / scratch / occupancy / spills / LDS; source line numbers ignored) must be identical.  Assembler
 comments are dropped before the comparison (their loop annotations carry the function's number too).  The
@@ -14,8 +16,12 @@ import os
 import re
 import sys
 
-ASM = "rtw_kernels-hip-amdgcn-amd-amdhsa-gfx950.s"
-RES = "resource_usage.txt"
+STEM = "rtw_kernels"
+
+
+def file_names(stem, res=None):
+    """The assembly and the resource file of a translation unit as `make asm` names them."""
+    return stem + "-hip-amdgcn-amd-amdhsa-gfx950.s", res or ("resource_usage.txt" if stem == STEM else "resource_usage_" + stem[len("rtw_"):] + ".txt")
 
 
 def kernels(text):
@@ -52,8 +58,9 @@ def resources(text):
 
 def main():
     a_dir, b_dir = sys.argv[1], sys.argv[2]
-    ta, tb = (open(os.path.join(d, ASM)).read() for d in (a_dir, b_dir))
-    ra, rb = (resources(open(os.path.join(d, RES)).read()) for d in (a_dir, b_dir))
+    asm, res = file_names(*(sys.argv[3:5] or [STEM]))
+    ta, tb = (open(os.path.join(d, asm)).read() for d in (a_dir, b_dir))
+    ra, rb = (resources(open(os.path.join(d, res)).read()) for d in (a_dir, b_dir))
     na, ba, da = kernels(ta)
     nb, bb, db = kernels(tb)
     same_body = same_res = same_desc = 0
