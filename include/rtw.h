@@ -962,6 +962,60 @@ int rtw_ctx_ao_map(rtw_ctx *ctx, const RtwCamera *cam, uint32_t width, uint32_t 
                    float *ao_out /*[h][w]*/, float *depth_out, int32_t *idx_out, float *normal_out /* each may be NULL */,
                    RtwStats *stats);
 
+/* ---- direct lighting: area-light shadow rays, fused (added within v4) --------------------------------------------------
+ * "How much of each light does this point see?"  For every (point, light) pair -- the lights of rtw_ctx_set_lights --, `samples` any-hit
+ * segments from the point to points sampled on the light's surface, walked in the kernel that makes them, two floats out: vis, the share of
+ * the samples that are cast and reach the light, and irr, the mean of their geometric terms (an estimate of the irradiance for unit
+ * radiance; neither the emitted colour nor 1 / pi is applied -- the caller multiplies).  No ray is stored anywhere.
+ * THE RULE (rtw_light_samples; csrc/rtw_direct.h; f32, one rounding per written operation, no FMA).  Item (i, l) is point i under light l of
+ * the list; xi1, xi2 are the first two draws of the render's counter-based stream started at sample k of
+ * base = mix32(mix32(mix32(mix32(seed + 0x9E3779B9) ^ 0x4C495445) ^ i) ^ (l + 1)).
+ *   quad light (RtwQuad origin o, edges u, v):  y = (o + u * xi1) + v * xi2
+ *   sphere light (c = RtwSphere.center, its place at time 0 as rtw_light_mid reads it; radius r):  z = 1 - 2 * xi1, s = sqrt(1 - z * z),
+ *     phi = 6.2831855f * xi2, w = (s * cos_plain(phi), s * sin_plain(phi), z), w = -w when dot(w, p - c) < 0, y = c + w * r
+ * The ray has the origin p as given and the direction d = y - p, NOT normalised, and is walked over [lo, hi] in units of the segment
+ * (1e-3 and 1 - 1e-3 leave out both end points' own surfaces: the light itself at t = 1 lies outside the range).  A sphere light hides the
+ * part of its facing hemisphere beyond its own horizon: those samples are blocked by the light's near side and count as blocked.
+ * A sample is CAST when the normal is not exactly (0, 0, 0) and dot(n, d) > 0 (a NaN fails); a sample that is not cast walks nothing and
+ * counts nothing.  Its weight, with dd = dot(d, d) and the normal as given (a unit normal gives the geometric term):
+ *   quad:    G = (dot(n, d) * fabs(dot(cross(u, v), d))) / (dd * dd)                     (the quad emits to both sides)
+ *   sphere:  G = ((dot(n, d) * cl) * (6.2831855f * (r * r))) / (dd * dd),  cl = -dot(w, d) > 0 ? -dot(w, d) : 0
+ * Ray [i][l][k] depends on (seed, i, l, k, point, normal, the light's geometry) alone: not on n, samples or the number of lights.
+ * OUTPUTS: vis[i][l] = (float)v * (1.0f / samples), v the cast samples that nothing stops; irr[i][l] = S * (1.0f / samples), S the sum of
+ * w_k (G_k for a cast and free sample, +0 otherwise) in this association: with L = min(samples, 64), s_g = ((0 + w_g) + w_{g+L}) + ... for
+ * g < L, then s_g = s_g + s_{g+off} for g < off, off = L/2, L/4, ..., 1, S = s_0 (rtw_light_reduce).  samples: a power of two in 1 .. 1024.
+ * THE CONTRACT: v is the number of cast k for which rtw_ctx_scene_occluded answers 0 for ray [i][l][k] of rtw_light_samples with the same
+ * time, mint = lo, maxt = hi and accel -- exactly, for every input, under both accels and every fall-back --, and irr is rtw_light_reduce
+ * of rtw_light_samples' weights with the blocked ones set to +0, bit for bit. */
+/* host only, pure: the light list is checked as rtw_lights_validate checks it (an empty list is refused as well); RTW_E_INVALID also for a
+ * NULL pointer, n == 0 or a samples that is not a power of two in 1 .. 1024.  A sample that is not cast gets six zeros and the weight 0. */
+int rtw_light_samples(const RtwScene *scene, const RtwLight *lights, uint32_t n_lights, const float *points /*[n][3]*/,
+                      const float *normals /*[n][3]*/, uint32_t n, uint32_t samples, uint32_t seed,
+                      float *rays_out /*[n][n_lights][samples][6]*/, float *weight_out /*[n][n_lights][samples]*/);
+/* host only, pure: *out = S * (1.0f / samples) of weights[0 .. samples) in the association above */
+int rtw_light_reduce(const float *weights, uint32_t samples, float *out);
+/* n_lights of the two calls below: the lights of the last rtw_ctx_set_lights (0: none set, or a NULL ctx) -- what sizes their outputs */
+uint32_t rtw_ctx_light_count(const rtw_ctx *ctx);
+/* points, normals ([n][3]), vis_out and irr_out ([n][n_lights]; irr_out may be NULL) may each be host memory or device memory of ctx's GPU
+ * (host memory is staged); the work runs on the stream of rtw_ctx_set_stream; blocking.  stats (may be NULL): segments = the rays cast,
+ * sphere_tests, node_tests, quad_tests = rtw_ctx_scene_occluded's over exactly those rays, kernel_ms.  RTW_E_INVALID for a NULL ctx /
+ * points / normals / vis_out, n == 0, a samples that is not a power of two in 1 .. 1024, an unknown accel, a call while a render is
+ * pending, no lights set, or n x n_lights x samples above 2^32 - 1; RTW_E_NO_SCENE before rtw_ctx_set_scene.  An invalid call writes
+ * nothing.  No per-light sample counts, no emission or textures applied, no triangle lights and no rtw_mgpu_* form. */
+int rtw_ctx_direct_light(rtw_ctx *ctx, const float *points /*[n][3]*/, const float *normals /*[n][3]*/, uint32_t n, uint32_t samples,
+                         uint32_t seed, float time, float lo, float hi, uint32_t accel, float *vis_out /*[n][n_lights]*/,
+                         float *irr_out /*[n][n_lights], may be NULL*/, RtwStats *stats);
+/* The camera form, defined as a composition exactly as rtw_ctx_ao_map is: rtw_ctx_depth_map(cam, width, height, time, mint, maxt, accel)
+ * with ids and normals, then rtw_ctx_direct_light over [lo, hi] with point index j * width + i, the points p = o + d * depth for idx >= 0,
+ * the normals faced towards the viewer, a miss pixel skipped (its normal is 0 0 0: vis and irr 0).  depth_out, idx_out and normal_out
+ * (each may be NULL) receive exactly rtw_ctx_depth_map's bytes.  Two launches between one pair of events: stats adds the depth pass's
+ * counters and its width x height rays.  RTW_E_INVALID also for a NULL cam, a zero width or height, or
+ * width x height x n_lights x samples above 2^32 - 1. */
+int rtw_ctx_direct_light_map(rtw_ctx *ctx, const RtwCamera *cam, uint32_t width, uint32_t height, float time, float mint, float maxt,
+                             uint32_t samples, uint32_t seed, float lo, float hi, uint32_t accel,
+                             float *vis_out /*[h][w][n_lights]*/, float *irr_out, float *depth_out, int32_t *idx_out,
+                             float *normal_out /* each but vis_out may be NULL */, RtwStats *stats);
+
 /* ---- host mirror of the reference constructors (same library, no GPU needed) ---------------- */
 
 /* Viewport::new (viewport.rs:308-401).  Options the reference takes as Option<> are pointers

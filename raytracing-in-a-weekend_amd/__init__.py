@@ -340,6 +340,16 @@ def lib() -> C.CDLL:
                                  C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtwStats)]
     L.rtw_ctx_depth_map.argtypes = [C.c_void_p, C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtwStats)]
+    L.rtw_light_samples.argtypes = [C.POINTER(RtwScene), C.POINTER(RtwLight), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                    C.c_void_p, C.c_void_p]
+    L.rtw_light_reduce.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    L.rtw_ctx_light_count.argtypes = [C.c_void_p]
+    L.rtw_ctx_light_count.restype = C.c_uint32
+    L.rtw_ctx_direct_light.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                       C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RtwStats)]
+    L.rtw_ctx_direct_light_map.argtypes = [C.c_void_p, C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32,
+                                           C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(RtwStats)]
     L.rtw_ctx_set_lights.argtypes = [C.c_void_p, C.POINTER(RtwLight), C.c_uint32, C.c_float]
     L.rtw_mgpu_set_lights.argtypes = [C.c_void_p, C.POINTER(RtwLight), C.c_uint32, C.c_float]
     L.rtw_lights_validate.argtypes = [C.POINTER(RtwScene), C.POINTER(RtwLight), C.c_uint32]
@@ -850,6 +860,37 @@ def ao_rays(points, normals, samples: int, seed: int = 0) -> np.ndarray:
     out = np.empty((len(p), int(samples), 6), np.float32) if 0 < int(samples) <= 1024 else np.empty((1, 1, 6), np.float32)
     _check(lib().rtw_ao_rays(p.ctypes.data, n.ctypes.data, len(p), int(samples), int(seed) & 0xFFFFFFFF, out.ctypes.data), "rtw_ao_rays")
     return out
+
+
+def light_samples(scene: "Scene", lights, points, normals, samples: int, seed: int = 0):
+    """The segments of direct lighting and their weights (rtw_light_samples, host only): (rays [n][n_lights][samples][6] float32 = origin,
+    direction; weights [n][n_lights][samples] float32).  Sample k of point i under light l of `lights` ((kind, index) pairs naming top-level
+    spheres / quads of `scene`) runs from points[i] to a point sampled on the light, direction not normalised, a function of
+    (seed, i, l, k, point, normal, the light) alone; its weight is the geometric term.  A sample that is not cast (a zero normal, or
+    dot(normal, direction) > 0 fails) gets six zeros and the weight 0.  samples: a power of two in 1 .. 1024."""
+    p, n = _points_normals("light_samples", points, normals)
+    arr, nl = _light_array(lights)
+    ok = 0 < int(samples) <= 1024 and 0 < nl <= 16
+    rays = np.empty((len(p), nl, int(samples), 6), np.float32) if ok else np.empty((1, 1, 1, 6), np.float32)
+    w = np.empty(rays.shape[:3], np.float32)
+    _check(lib().rtw_light_samples(C.byref(scene.pod), arr, nl, p.ctypes.data, n.ctypes.data, len(p), int(samples), int(seed) & 0xFFFFFFFF,
+                                   rays.ctypes.data, w.ctypes.data), "rtw_light_samples")
+    return rays, w
+
+
+def light_reduce(weights) -> np.ndarray:
+    """rtw_light_reduce over the last axis of `weights` ([...][samples] float32): the sum in direct_light's fixed association (lane partials
+    over min(samples, 64) lanes, then a halving tree) times 1 / samples.  samples: a power of two in 1 .. 1024."""
+    w = np.ascontiguousarray(weights, np.float32)
+    if w.ndim == 0 or w.size == 0:
+        raise ValueError("light_reduce: weights must hold [...][samples] floats")
+    samples = w.shape[-1]
+    flat = w.reshape(-1, samples)
+    out = np.empty(len(flat), np.float32)
+    reduce, src, dst = lib().rtw_light_reduce, flat.ctypes.data, out.ctypes.data
+    for j in range(len(flat)):
+        _check(reduce(src + 4 * samples * j, samples, dst + 4 * j), "rtw_light_reduce")
+    return out.reshape(w.shape[:-1])
 
 
 def triangle_bvh_validate(triangles):
@@ -1604,6 +1645,76 @@ class Renderer:
                                     dep.ctypes.data if depth else None, idx.ctypes.data if ids else None, nrm.ctypes.data if normals else None,
                                     C.byref(st)), "rtw_ctx_ao_map")
         return (ao,) + ((dep,) if depth else ()) + ((idx,) if ids else ()) + ((nrm,) if normals else ()) + (st,)
+
+    def light_count(self) -> int:
+        """rtw_ctx_light_count: the lights of the last set_lights (a new scene clears them)."""
+        return int(lib().rtw_ctx_light_count(self._h))
+
+    def direct_light(self, points, normals, samples: int = 16, lo: float = 1e-3, hi: float = 1.0 - 1e-3, seed: int = 0, time: float = 0.0,
+                     accel: int = ACCEL_BVH, irradiance: bool = True, out_vis=None, out_irr=None):
+        """How much of each light of set_lights every point ([n][3], with normals [n][3]) sees (rtw_ctx_direct_light): (vis [n][n_lights]
+        float32[, irr [n][n_lights] float32], RtwStats).  Per (point, light) pair, `samples` segments to points sampled on the light's surface
+        are made and walked in one kernel over [lo, hi] in units of the segment (segments_occluded's convention); vis is the share that is
+        cast (dot(normal, direction) > 0) and reaches the light -- exactly what scene_occluded answers for light_samples' rays --, irr
+        light_reduce of their geometric terms: the irradiance for unit radiance, neither the emitted colour nor 1 / pi applied.  A sphere
+        light hides the part of its facing hemisphere beyond its own horizon: those samples count as blocked.  samples: a power of two in
+        1 .. 1024.
+        points, normals: anything numpy reads (staged; numpy arrays come back), or contiguous float32 torch tensors on the context's device:
+        then out_vis / out_irr are float32 tensors [n][n_lights] on the same device (allocated when None), and all are read and written in
+        place on the context's stream (use_torch_stream), as ambient_occlusion does."""
+        st = RtwStats()
+        nl = self.light_count()
+        args = (int(samples), int(seed) & 0xFFFFFFFF, float(time), float(lo), float(hi), int(accel))
+        if hasattr(points, "data_ptr") or hasattr(normals, "data_ptr"):
+            import torch
+            if not (self._on_device(points) and self._on_device(normals)):
+                raise ValueError("direct_light: points and normals must both be float32 tensors, contiguous and on the context's device")
+            if points.numel() == 0 or points.numel() % 3 or normals.numel() != points.numel():
+                raise ValueError("direct_light: points and normals must both hold [n][3] floats, n > 0")
+            n = points.numel() // 3
+            if out_vis is None:
+                out_vis = torch.empty((n, nl), dtype=torch.float32, device=points.device)
+            if irradiance and out_irr is None:
+                out_irr = torch.empty((n, nl), dtype=torch.float32, device=points.device)
+            for o in (out_vis,) + ((out_irr,) if irradiance else ()):
+                if not self._on_device(o) or o.numel() != n * nl:
+                    raise ValueError("direct_light: out_vis / out_irr must be contiguous torch.float32 tensors [n][n_lights] on the context's device")
+            if not irradiance and out_irr is not None:
+                raise ValueError("direct_light: out_irr= goes with irradiance=True")
+            _check(lib().rtw_ctx_direct_light(self._h, C.c_void_p(int(points.data_ptr())), C.c_void_p(int(normals.data_ptr())), n, *args,
+                                              C.c_void_p(int(out_vis.data_ptr())), C.c_void_p(int(out_irr.data_ptr())) if irradiance else None,
+                                              C.byref(st)), "rtw_ctx_direct_light")
+            return (out_vis, out_irr, st) if irradiance else (out_vis, st)
+        if out_vis is not None or out_irr is not None:
+            raise ValueError("direct_light: out_vis= / out_irr= go with torch tensors of points and normals")
+        p, nrm = _points_normals("direct_light", points, normals)
+        vis = np.empty((len(p), nl), np.float32)
+        irr = np.empty((len(p), nl), np.float32) if irradiance else None
+        _check(lib().rtw_ctx_direct_light(self._h, p.ctypes.data, nrm.ctypes.data, len(p), *args, vis.ctypes.data,
+                                          irr.ctypes.data if irradiance else None, C.byref(st)), "rtw_ctx_direct_light")
+        return (vis, irr, st) if irradiance else (vis, st)
+
+    def direct_light_map(self, cam: RtwCamera, width: int, height: int, mint: float, maxt: float, samples: int = 16, lo: float = 1e-3,
+                         hi: float = 1.0 - 1e-3, seed: int = 0, time: float = 0.0, accel: int = ACCEL_BVH, irradiance: bool = True,
+                         depth: bool = False, ids: bool = False, normals: bool = False):
+        """Direct lighting of what a camera of camera2_new sees (rtw_ctx_direct_light_map): depth_map(cam, width, height, mint, maxt) and then
+        direct_light of its hit points, with the normals faced towards the viewer, in two launches and with no buffer in between on the
+        host: (vis [height][width][n_lights] float32, 0 for a miss pixel[, irr][, depth][, ids][, normals] -- depth_map's arrays, the normals
+        as it writes them --; RtwStats, the depth pass's counters and rays included)."""
+        width, height = int(width), int(height)
+        nl = self.light_count()
+        vis = np.empty((height, width, nl), np.float32)
+        irr = np.empty((height, width, nl), np.float32) if irradiance else None
+        dep = np.empty((height, width), np.float32) if depth else None
+        idx = np.empty((height, width), np.int32) if ids else None
+        nrm = np.empty((height, width, 3), np.float32) if normals else None
+        st = RtwStats()
+        _check(lib().rtw_ctx_direct_light_map(self._h, C.byref(cam), width, height, float(time), float(mint), float(maxt), int(samples),
+                                              int(seed) & 0xFFFFFFFF, float(lo), float(hi), int(accel), vis.ctypes.data,
+                                              irr.ctypes.data if irradiance else None, dep.ctypes.data if depth else None,
+                                              idx.ctypes.data if ids else None, nrm.ctypes.data if normals else None, C.byref(st)),
+               "rtw_ctx_direct_light_map")
+        return (vis,) + ((irr,) if irradiance else ()) + ((dep,) if depth else ()) + ((idx,) if ids else ()) + ((nrm,) if normals else ()) + (st,)
 
     def set_texture_noise(self, tables=None, n_tables: int = 0, per_texture=None, n_textures: int = 0):
         """rtw_ctx_set_texture_noise as is (no arguments: clear the noise of the current scene)."""

@@ -176,6 +176,26 @@ struct AoArgs {
 };
 // from_camera: the points come from the depth pass's outputs; tree: as launch_scene_occluded.  (samples <= 64 runs the single-round build)
 void launch_ambient_occlusion(const AoArgs &q, bool from_camera, bool tree, hipStream_t stream);
+// rtw_ctx_direct_light / rtw_ctx_direct_light_map (rtw_occluded.hip): `samples` any-hit segments per (point, light) pair,
+// made in the kernel by the rule of rtw_direct.h, two floats per pair.  q: the scene views, [lo, hi] of the segments, the counters ([4]: the
+// rays cast); q.n is the number of POINTS, q.rays and q.out are not read.  The other fields are AoArgs' of the same names.
+struct DirectRow;
+struct DirectArgs {
+    OccludedArgs q;
+    const float *points;          // [n][3] (device); from_camera: not read
+    const float *normals;         // [n][3] (device); from_camera: the depth pass's normals of the pixels
+    const DirectRow *lights;      // [n_lights] rows (device; rtw_direct.h)
+    uint32_t n_lights;            // 1 .. RTW_MAX_LIGHTS; item i * n_lights + l is point i under light l
+    uint32_t samples, seed;       // samples: a power of two in 1 .. 1024
+    uint32_t lg_group;            // log2 of the lanes that share an item: min(samples, 64)
+    float *vis_out;               // [n][n_lights]
+    float *irr_out;               // [n][n_lights] or null
+    RtwCamera cam;
+    uint32_t width, height;
+    const float *depth;
+    const int32_t *idx;
+};
+void launch_direct_light(const DirectArgs &q, bool from_camera, bool tree, hipStream_t stream);
 // rtw_ctx_mesh_instance_hits: the closest placement of mesh T for each of n rays through mesh_closest (rtw_mesh.h); placement / triangle
 // -1 and t +inf on a miss; normal_out ([n][3]) may be null; counters as launch_tri_hits
 void launch_mesh_hits(const DevTris &T, const f4 *rows, uint32_t n_mesh, const TriNode *top, uint32_t n_top, const float *rays, uint32_t n, float mint, float maxt, float *t_out,

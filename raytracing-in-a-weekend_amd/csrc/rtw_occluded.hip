@@ -1,7 +1,8 @@
 // rtw_occluded.hip -- any-hit occlusion queries over the whole scene of a context (rtw_ctx_scene_occluded): for each ray,
 // "is anything in the way within [mint, maxt]?" -- one byte, 1 exactly when rtw_ctx_scene_hits (rtw_query.hip) reports an index >= 0.
 // A kernel of its own: no render kernel and no closest-hit query reads this file.  ambient_occlusion_kernel (rtw_ctx_ambient_occlusion /
-// rtw_ctx_ao_map) lives here too: it makes its rays in registers (rtw_ao.h) and walks them with the same function.
+// rtw_ctx_ao_map) lives here too: it makes its rays in registers (rtw_ao.h) and walks them with the same function, and so
+// does direct_light_kernel (rtw_ctx_direct_light / rtw_ctx_direct_light_map; the rule: rtw_direct.h).
 //
 // Why the bit is exact: in every group the acceptance of a candidate with nothing found so far depends on that candidate and on
 // [mint, maxt] alone, a later group's result never takes a hit away, and the trees only prune.  So "some candidate is accepted" is "the
@@ -14,6 +15,7 @@
 #include "rtw_kernels.h"
 #include "rtw_occl.h"
 #include "rtw_ao.h"
+#include "rtw_direct.h"
 
 namespace rtw {
 
@@ -299,6 +301,70 @@ __global__ __launch_bounds__(RTW_BLOCK) void ambient_occlusion_kernel(const AoAr
     occluded_count(A.q.counters, n_sph, n_nodes, n_quad, overflow, n_points);
 }
 
+// Direct lighting (rtw_ctx_direct_light / rtw_ctx_direct_light_map): ambient_occlusion_kernel's lane mapping over ITEMS.  A
+// group of L = min(samples, 64) lanes owns item i * n_lights + l -- point i under light l --, so the groups of a wave may belong to different
+// points and lights.  Lane 0 of a group loads (CAM: forms) the point and its normal and the group gets them by a cross-lane read; every lane
+// reads the light's row, makes its segment and weight in registers (rtw_direct.h) and walks the segment with occluded_walk, coming in closed
+// when the sample is not cast.  The visible count is the popcount of a ballot under the group's lane mask; the weights are summed in the
+// fixed association of direct_sum: a lane's rounds in ascending order, then lane g adds lane g + off for off = L/2 .. 1 (a lane with
+// g >= off adds something that nobody reads).  No lane leaves before the end: every cross-lane read finds its source lane active.
+// ONE: samples <= 64, no round loop (as ambient_occlusion_kernel: nothing of the item but its weight lives across the walk).
+template <bool CAM, bool TREE, bool MOVING, bool ONE>
+__global__ __launch_bounds__(RTW_BLOCK) void direct_light_kernel(const DirectArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char q_lds[];
+    const uint32_t lg = A.lg_group, L = 1u << lg;                  // (wave-uniform: samples is a kernel argument)
+    const uint32_t lane = threadIdx.x & 63u, g_lane = lane & (L - 1u), g_first = lane - g_lane;
+    const unsigned long long item = (unsigned long long)blockIdx.x * (RTW_BLOCK >> lg) + (threadIdx.x >> lg);
+    const bool in = item < (unsigned long long)A.q.n * A.n_lights;
+    const uint32_t it = (uint32_t)item;
+    const uint32_t i = in ? it / A.n_lights : 0u, l = in ? it - i * A.n_lights : 0u;      // (an item past the end reads row 0 and casts nothing)
+    uint32_t n_sph = 0, n_nodes = 0, n_quad = 0;
+    bool overflow = false;
+    v3 p = mk(0.0f, 0.0f, 0.0f), nrm = p;
+    if (in && g_lane == 0u) {
+        if (CAM) {
+            if (A.idx[i] >= 0) {                                   // (a miss pixel is skipped: its normal stays 0 0 0)
+                const uint32_t px = i % A.width, py = i / A.width;
+                const float fx = (float)px / (float)A.width, fy = (float)py / (float)A.height;
+                const v3 o = ld3(A.cam.origin);
+                const v3 d = unit((ld3(A.cam.pixel00) + ld3(A.cam.delta_u) * fx) + ld3(A.cam.delta_v) * fy);
+                const v3 nn = ld3(A.normals + 3 * (size_t)i);
+                p = o + d * A.depth[i];
+                nrm = dot(d, nn) > 0.0f ? -nn : nn;                // faced towards the viewer
+            }
+        } else {
+            p = ld3(A.points + 3 * (size_t)i);
+            nrm = ld3(A.normals + 3 * (size_t)i);
+        }
+    }
+    if (L > 1u) {
+        p.x = __shfl(p.x, (int)g_first); p.y = __shfl(p.y, (int)g_first); p.z = __shfl(p.z, (int)g_first);
+        nrm.x = __shfl(nrm.x, (int)g_first); nrm.y = __shfl(nrm.y, (int)g_first); nrm.z = __shfl(nrm.z, (int)g_first);
+    }
+    const lv3 lp = lmk(p.x, p.y, p.z), ln = lmk(nrm.x, nrm.y, nrm.z);
+    const DirectRow row = A.lights[l];
+    const uint32_t base = direct_item_base(A.seed, i, l);
+    const unsigned long long g_mask = (L == 64u ? ~0ull : ((1ull << L) - 1ull)) << g_first;
+    uint32_t visible = 0, n_cast = 0;
+    float sum = 0.0f;
+    for (uint32_t round = 0; round < (ONE ? 1u : A.samples); round += (ONE ? 1u : L)) {     // (samples / L rounds, wave-uniform; ONE: no loop)
+        lv3 dir;
+        float G;
+        const bool cast = direct_sample(row, base, round + g_lane, lp, ln, dir, G) && in;
+        const bool open = occluded_walk<TREE, MOVING>(A.q, q_lds, p, mk(dir.x, dir.y, dir.z), cast, n_sph, n_nodes, n_quad, overflow);
+        visible += (uint32_t)__builtin_popcountll(ballot64(open) & g_mask);              // (open at the end: cast and free)
+        n_cast += (uint32_t)__builtin_popcountll(ballot64(cast));                        // (the wave's; wave-uniform)
+        sum = sum + (open ? G : 0.0f);
+    }
+    for (uint32_t off = L >> 1; off > 0u; off >>= 1) sum = sum + __shfl_down(sum, off);
+    if (in && g_lane == 0u) {
+        const float inv = 1.0f / (float)A.samples;
+        A.vis_out[it] = (float)visible * inv;
+        if (A.irr_out) A.irr_out[it] = sum * inv;
+    }
+    occluded_count(A.q.counters, n_sph, n_nodes, n_quad, overflow, n_cast);
+}
+
 void launch_scene_occluded(const OccludedArgs &q, bool tree, hipStream_t stream) {
     typedef void (*occl_fn)(const OccludedArgs);
     const bool moving = q.sc.moving != 0u;
@@ -321,6 +387,22 @@ void launch_ambient_occlusion(const AoArgs &q, bool from_camera, bool tree, hipS
     const uint32_t lds = tree ? q.q.levels * RTW_BLOCK * 4u : 0u;
     const uint32_t per_block = RTW_BLOCK >> q.lg_group;            // points of a workgroup
     hipLaunchKernelGGL(fns[from_camera][tree][moving], dim3((uint32_t)(((unsigned long long)q.q.n + per_block - 1u) / per_block)), dim3(RTW_BLOCK), lds, stream, q);
+}
+
+typedef void (*direct_fn)(const DirectArgs);
+template <bool CAM, bool TREE, bool MOVING>
+static direct_fn pick_direct(bool one) { return one ? direct_light_kernel<CAM, TREE, MOVING, true> : direct_light_kernel<CAM, TREE, MOVING, false>; }
+
+void launch_direct_light(const DirectArgs &q, bool from_camera, bool tree, hipStream_t stream) {
+    const bool moving = q.q.sc.moving != 0u;
+    const bool one = q.samples <= 64u;
+    const direct_fn fns[2][2][2] = {
+        { { pick_direct<false, false, false>(one), pick_direct<false, false, true>(one) }, { pick_direct<false, true, false>(one), pick_direct<false, true, true>(one) } },
+        { { pick_direct<true, false, false>(one), pick_direct<true, false, true>(one) }, { pick_direct<true, true, false>(one), pick_direct<true, true, true>(one) } } };
+    const uint32_t lds = tree ? q.q.levels * RTW_BLOCK * 4u : 0u;
+    const uint32_t per_block = RTW_BLOCK >> q.lg_group;            // items of a workgroup
+    const unsigned long long items = (unsigned long long)q.q.n * q.n_lights;
+    hipLaunchKernelGGL(fns[from_camera][tree][moving], dim3((uint32_t)((items + per_block - 1u) / per_block)), dim3(RTW_BLOCK), lds, stream, q);
 }
 
 } // namespace rtw

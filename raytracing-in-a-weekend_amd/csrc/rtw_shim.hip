@@ -10,6 +10,7 @@
 #include "rtw_exp.h"
 #include "rtw_probe.h"
 #include "rtw_ao.h"
+#include "rtw_direct.h"
 
 #include <link.h>
 
@@ -103,6 +104,8 @@ struct rtw_ctx {
     std::vector<uint32_t> refit_first;   // RefitSchedule.first of the tree in tri_mem (rtw_refit.h): the refit's launches
     // lights of the scene (rtw_ctx_set_lights; cleared by rtw_ctx_set_scene): the rows the light build reads from its arguments
     DevLights lights{};
+    std::vector<DirectRow> light_rows;   // ... and their geometry as the direct-lighting pass reads it (rtw_direct.h), one row per light: its device table
+                                         // is staged from here by every call of the pass
     std::vector<RtwSphere> h_spheres;    // host copies of the top-level spheres and quads: a light's mid-point is formed from them
     std::vector<RtwQuad> h_quads;
     bool has_medium = false;             // an instance of the scene is a constant-density medium (the light integrators refuse it)
@@ -469,6 +472,7 @@ static void free_scene(rtw_ctx *c) {
     free_quats(c);
     c->h_instances.clear();
     c->lights = DevLights{};
+    c->light_rows.clear();
     c->h_spheres.clear(); c->h_quads.clear(); c->has_medium = false;
     c->has_mixed = c->mixed_bad = false;
     c->n_textures = 0;
@@ -783,6 +787,12 @@ int rtw_ctx_set_lights(rtw_ctx *c, const RtwLight *lights, uint32_t n, float bia
     if (rc != RTW_OK) return rc;
     d.n = n; d.weight = biased_weight;
     c->lights = d;
+    c->light_rows.resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const RtwLight &l = lights[i];
+        c->light_rows[i] = l.kind == RTW_LIGHT_SPHERE ? direct_row_sphere(c->h_spheres[l.index].center, c->h_spheres[l.index].radius)
+                                                      : direct_row_quad(c->h_quads[l.index].origin, c->h_quads[l.index].u, c->h_quads[l.index].v);
+    }
     return RTW_OK;
 }
 
@@ -1262,6 +1272,81 @@ int rtw_ctx_ao_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t he
     a.normals = q.normal_out = normal_out ? st.out(normal_out, 3 * t_bytes) : st.scratch<float>(3 * t_bytes);
     return counted_pass(c, st, samples, n, stats, [&] { launch_scene_hits(q, true, tree, c->stream); },
                         [&] { launch_ambient_occlusion(a, true, ao_tree, c->stream); });
+}
+
+// ---- direct lighting (rtw.h "direct lighting"; kernel: rtw_occluded.hip; the rule: rtw_direct.h) -----------------------------------------
+// The statuses both calls share once their own arguments are in order; n: the points
+static int direct_ready(const rtw_ctx *c, uint64_t n, uint32_t samples) {
+    if (c->pend.active) return RTW_E_INVALID;
+    if (!c->has_scene) return RTW_E_NO_SCENE;
+    if (c->light_rows.empty()) return RTW_E_INVALID;
+    if (n * c->light_rows.size() * samples > 0xFFFFFFFFull) return RTW_E_INVALID;
+    return RTW_OK;
+}
+
+uint32_t rtw_ctx_light_count(const rtw_ctx *c) { return c ? (uint32_t)c->light_rows.size() : 0u; }
+
+// The sampling fields of a launch and the light table, staged from the context's rows; a.q: scene_views over the points and [lo, hi]
+static void direct_sampling(const rtw_ctx *c, Staging &st, uint32_t samples, uint32_t seed, DirectArgs &a) {
+    a.samples = samples; a.seed = seed; a.lg_group = 0;
+    while ((1u << a.lg_group) < samples && a.lg_group < 6u) a.lg_group++;
+    a.n_lights = (uint32_t)c->light_rows.size();
+    a.lights = st.in(c->light_rows.data(), sizeof(DirectRow) * c->light_rows.size());
+}
+
+int rtw_ctx_direct_light(rtw_ctx *c, const float *points, const float *normals, uint32_t n, uint32_t samples, uint32_t seed, float time, float lo,
+                         float hi, uint32_t accel, float *vis_out, float *irr_out, RtwStats *stats) {
+    if (!c || !points || !normals || !vis_out || n == 0 || !ao_samples_ok(samples) || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    if (const int rc = direct_ready(c, n, samples)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool tree = query_uses_tree(c, accel, time, lo, hi);
+
+    DirectArgs a;
+    std::memset(&a, 0, sizeof a);
+    scene_views(c, n, time, lo, hi, accel, a.q);
+    Staging st(c);
+    direct_sampling(c, st, samples, seed, a);
+
+    const size_t v_bytes = 3 * sizeof(float) * (size_t)n, o_bytes = sizeof(float) * (size_t)n * a.n_lights;
+    a.points = st.in(points, v_bytes);
+    a.normals = st.in(normals, v_bytes);
+    a.vis_out = st.out(vis_out, o_bytes);
+    if (irr_out) a.irr_out = st.out(irr_out, o_bytes);
+    return counted_pass(c, st, 1, 0, stats, [&] { launch_direct_light(a, false, tree, c->stream); });
+}
+
+// rtw_ctx_depth_map with ids and normals into the caller's device buffers or scratch, then the direct-lighting kernel's camera form over them
+// (rtw_ctx_ao_map's frame: two launches between one pair of events, one set of counters)
+int rtw_ctx_direct_light_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, float time, float mint, float maxt,
+                             uint32_t samples, uint32_t seed, float lo, float hi, uint32_t accel, float *vis_out, float *irr_out,
+                             float *depth_out, int32_t *idx_out, float *normal_out, RtwStats *stats) {
+    if (!c || !cam || !vis_out || width == 0 || height == 0 || !ao_samples_ok(samples) || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    if ((uint64_t)width * height > 0xFFFFFFFFull) return RTW_E_INVALID;
+    if (const int rc = direct_ready(c, (uint64_t)width * height, samples)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t n = width * height;
+    const bool tree = query_uses_tree(c, accel, time, mint, maxt), light_tree = query_uses_tree(c, accel, time, lo, hi);
+
+    QueryArgs q;                         // the depth pass: scene_query's launch
+    scene_views(c, n, time, mint, maxt, accel, q);
+    q.cam = *cam; q.width = width; q.height = height;
+    q.miss_t = host_mul(maxt, 1.6f);
+
+    DirectArgs a;
+    std::memset(&a, 0, sizeof a);
+    scene_views(c, n, time, lo, hi, accel, a.q);
+    Staging st(c);                       // the depth pass's outputs are scratch where the caller did not ask for them
+    direct_sampling(c, st, samples, seed, a);
+    a.cam = *cam; a.width = width; a.height = height;
+
+    const size_t t_bytes = sizeof(float) * (size_t)n, i_bytes = sizeof(int32_t) * (size_t)n, o_bytes = t_bytes * a.n_lights;
+    a.vis_out = st.out(vis_out, o_bytes);
+    if (irr_out) a.irr_out = st.out(irr_out, o_bytes);
+    a.depth = q.t_out = depth_out ? st.out(depth_out, t_bytes) : st.scratch<float>(t_bytes);
+    a.idx = q.idx_out = idx_out ? st.out(idx_out, i_bytes) : st.scratch<int32_t>(i_bytes);
+    a.normals = q.normal_out = normal_out ? st.out(normal_out, 3 * t_bytes) : st.scratch<float>(3 * t_bytes);
+    return counted_pass(c, st, 1, n, stats, [&] { launch_scene_hits(q, true, tree, c->stream); },
+                        [&] { launch_direct_light(a, true, light_tree, c->stream); });
 }
 
 int rtw_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uint32_t turb_depth, float *out) {
