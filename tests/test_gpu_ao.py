@@ -158,10 +158,10 @@ def test_spoilers_and_permutations(gpu, oracle, accel):
 
 
 # ---- ao_map equals its definition ------------------------------------------------------------------------------------------------------------------
-def definition(r, cam, width, height, mint, maxt, samples, radius, ao_mint=AO.AO_MINT, seed=0, accel=R.ACCEL_BVH):
-    """rtw_ctx_ao_map by its text: depth_map, then the points o + d * depth and the faced normals in numpy (one f32 rounding per operation),
-    then ambient_occlusion; (ao, depth, ids, normals, faced, (segments, counters...))."""
-    depth, ids, nrm, dst = r.depth_map(cam, width, height, mint, maxt, accel=accel, ids=True, normals=True)
+def map_points(r, cam, width, height, mint, maxt, time=0.0, accel=R.ACCEL_BVH):
+    """The points the camera forms shade, by their text: depth_map, then o + d * depth and the normals faced towards the viewer in numpy (one
+    f32 rounding per operation), zeros for a miss pixel; (points, faced normals, flipped, depth, ids, normals, depth_map's RtwStats)."""
+    depth, ids, nrm, dst = r.depth_map(cam, width, height, mint, maxt, time=time, accel=accel, ids=True, normals=True)
     rays = R.depth_rays(cam, width, height)
     o, d = rays[:, :3], rays[:, 3:]
     t, hit, n = depth.reshape(-1), ids.reshape(-1) >= 0, nrm.reshape(-1, 3)
@@ -171,20 +171,27 @@ def definition(r, cam, width, height, mint, maxt, samples, radius, ao_mint=AO.AO
     faced = np.where(flip[:, None], -n, n).astype(F)
     faced[~hit] = 0.0
     p[~hit] = 0.0
-    ao, ast = r.ambient_occlusion(p, faced, samples, radius, mint=ao_mint, seed=seed, accel=accel)
+    return p, faced, flip & hit, depth, ids, nrm, dst
+
+
+def definition(r, cam, width, height, mint, maxt, samples, radius, ao_mint=AO.AO_MINT, seed=0, accel=R.ACCEL_BVH, time=0.0):
+    """rtw_ctx_ao_map by its text: map_points, then ambient_occlusion; (ao, depth, ids, normals, faced, (segments, counters...))."""
+    p, faced, flipped, depth, ids, nrm, dst = map_points(r, cam, width, height, mint, maxt, time, accel)
+    ao, ast = r.ambient_occlusion(p, faced, samples, radius, mint=ao_mint, seed=seed, time=time, accel=accel)
     stats = (dst.segments + ast.segments,) + tuple(getattr(dst, k) + getattr(ast, k) for k in COUNTERS)
-    return ao.reshape(height, width), depth, ids, nrm, flip & hit, stats
+    return ao.reshape(height, width), depth, ids, nrm, flipped, stats
 
 
-def check_map(r, cam, width, height, what, mint=MINT, maxt=MAXT, samples=16, radius=5.0, accel=R.ACCEL_BVH):
-    want, depth, ids, nrm, flipped, stats = definition(r, cam, width, height, mint, maxt, samples, radius, accel=accel)
-    ao, d, i, n, st = r.ao_map(cam, width, height, mint, maxt, samples, radius, accel=accel, depth=True, ids=True, normals=True)
+def check_map(r, cam, width, height, what, mint=MINT, maxt=MAXT, samples=16, radius=5.0, accel=R.ACCEL_BVH, ao_mint=AO.AO_MINT, seed=0, time=0.0):
+    want, depth, ids, nrm, flipped, stats = definition(r, cam, width, height, mint, maxt, samples, radius, ao_mint, seed, accel, time)
+    kw = dict(ao_mint=ao_mint, seed=seed, time=time, accel=accel)
+    ao, d, i, n, st = r.ao_map(cam, width, height, mint, maxt, samples, radius, depth=True, ids=True, normals=True, **kw)
     assert ao.shape == (height, width) and same(ao, want), (what, "ao against the definition")
     assert same(d, depth) and same(i, ids) and same(n, nrm), (what, "depth, ids and normals are depth_map's bytes")
     assert (st.segments,) + tuple(getattr(st, k) for k in COUNTERS) == stats and st.kernel_ms > 0.0, (what, "counters")
     assert st.segments == width * height + samples * int((ids >= 0).sum())
     assert (ao[ids < 0] == 1.0).all()
-    alone, st0 = r.ao_map(cam, width, height, mint, maxt, samples, radius, accel=accel)      # no depth-pass output asked for
+    alone, st0 = r.ao_map(cam, width, height, mint, maxt, samples, radius, **kw)             # no depth-pass output asked for
     assert same(alone, ao) and st0.segments == st.segments
     return ao, ids, flipped
 

@@ -17,7 +17,7 @@ from tests import occluded_common as OC
 from tests import quat_common as QC
 from tests import query_edges_common as QE
 from tests import refit_common as RC
-from tests.test_gpu_ao import hit_points
+from tests.test_gpu_ao import hit_points, map_points
 from tests.test_gpu_occluded import MODES, Mode
 from tests.test_gpu_query_staging import N, TAIL, H, W, Entry, assert_answer, run
 from tests.test_gpu_scene_hits import MAXT, MINT, depth_camera, geom_scene
@@ -195,31 +195,25 @@ def test_spoilers_permutations_and_the_order_of_the_lights(gpu, oracle, accel):
 
 
 # ---- direct_light_map equals its definition ------------------------------------------------------------------------------------------------------
-def definition(r, cam, width, height, mint, maxt, samples, seed=0, accel=R.ACCEL_BVH):
+def definition(r, cam, width, height, mint, maxt, samples, seed=0, accel=R.ACCEL_BVH, time=0.0, lo=LO, hi=HI):
     """rtw_ctx_direct_light_map by its text: depth_map, then the points o + d * depth and the faced normals in numpy (one f32 rounding per
-    operation), then direct_light; (vis, irr, depth, ids, normals, (segments, counters...))."""
-    depth, ids, nrm, dst = r.depth_map(cam, width, height, mint, maxt, accel=accel, ids=True, normals=True)
-    rays = R.depth_rays(cam, width, height)
-    o, d = rays[:, :3], rays[:, 3:]
-    t, hit, n = depth.reshape(-1), ids.reshape(-1) >= 0, nrm.reshape(-1, 3)
-    p = (o + (d * t[:, None]).astype(F)).astype(F)
-    faced = np.where((DL.dot(d, n) > 0.0)[:, None], -n, n).astype(F)
-    faced[~hit] = 0.0
-    p[~hit] = 0.0
-    vis, irr, lst = r.direct_light(p, faced, samples, seed=seed, accel=accel)
+    operation; map_points of the ambient-occlusion tests), then direct_light; (vis, irr, depth, ids, normals, (segments, counters...))."""
+    p, faced, _, depth, ids, nrm, dst = map_points(r, cam, width, height, mint, maxt, time, accel)
+    vis, irr, lst = r.direct_light(p, faced, samples, lo=lo, hi=hi, seed=seed, time=time, accel=accel)
     nl = vis.shape[1]
     stats = tuple(a + b for a, b in zip(counters(dst), counters(lst)))
     return vis.reshape(height, width, nl), irr.reshape(height, width, nl), depth, ids, nrm, stats
 
 
-def check_map(r, cam, width, height, what, mint=MINT, maxt=MAXT, samples=16, accel=R.ACCEL_BVH):
-    want_vis, want_irr, depth, ids, nrm, stats = definition(r, cam, width, height, mint, maxt, samples, accel=accel)
-    vis, irr, d, i, n, st = r.direct_light_map(cam, width, height, mint, maxt, samples, accel=accel, depth=True, ids=True, normals=True)
+def check_map(r, cam, width, height, what, mint=MINT, maxt=MAXT, samples=16, accel=R.ACCEL_BVH, seed=0, time=0.0, lo=LO, hi=HI):
+    want_vis, want_irr, depth, ids, nrm, stats = definition(r, cam, width, height, mint, maxt, samples, seed, accel, time, lo, hi)
+    kw = dict(lo=lo, hi=hi, seed=seed, time=time, accel=accel)
+    vis, irr, d, i, n, st = r.direct_light_map(cam, width, height, mint, maxt, samples, depth=True, ids=True, normals=True, **kw)
     assert vis.shape == want_vis.shape and same(vis, want_vis) and same(irr, want_irr), (what, "vis and irr against the definition")
     assert same(d, depth) and same(i, ids) and same(n, nrm), (what, "depth, ids and normals are depth_map's bytes")
     assert counters(st) == stats and st.kernel_ms > 0.0, (what, "counters", counters(st), stats)
     assert not vis[ids < 0].any() and not irr[ids < 0].any(), (what, "a miss pixel is skipped")
-    alone, st0 = r.direct_light_map(cam, width, height, mint, maxt, samples, accel=accel, irradiance=False)      # nothing optional asked for
+    alone, st0 = r.direct_light_map(cam, width, height, mint, maxt, samples, irradiance=False, **kw)      # nothing optional asked for
     assert same(alone, vis) and st0.segments == st.segments
     return vis, irr, ids
 
