@@ -5,6 +5,7 @@
 #include "rtw_light.h"
 #include "rtw_mixed.h"
 #include "rtw_host.h"
+#include <type_traits>
 
 #define RTW_QUEUE_BYTES 4096u   // the work queue's counters (KArgs.queue): up to 8 sub-queues ...
 #define RTW_QUEUE_STRIDE 256u   // ... bytes apart
@@ -109,6 +110,12 @@ void launch_perlin_eval(const RtwPerlin *t, const float *points, uint32_t n, uin
 // tests, [1] node visits (device u64, accumulated)
 void launch_tri_hits(const DevTris &T, const float *rays, uint32_t n, float mint, float maxt, float *t_out, int32_t *idx_out,
                      unsigned long long *counters, hipStream_t stream);
+// N runtime bools as N compile-time ones: f(std::bool_constant<b0>{}, ..., std::bool_constant<bN-1>{}), all 2^N calls of one return type.
+// How every launch_* below gets from its arguments to the kernel instantiation.
+template <bool... Done, class F>
+auto with_bools(F f) { return f(std::bool_constant<Done>{}...); }
+template <bool... Done, class F, class... Rest>
+auto with_bools(F f, bool b, Rest... rest) { return b ? with_bools<Done..., true>(f, rest...) : with_bools<Done..., false>(f, rest...); }
 // rtw_ctx_scene_hits / rtw_ctx_depth_map (rtw_query.hip): one closest-hit query per ray over spheres, quads, instances and triangles.
 struct QueryArgs {
     DevScene sc;

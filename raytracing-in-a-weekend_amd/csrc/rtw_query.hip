@@ -5,39 +5,29 @@
 // Every value reported is the render's: the sphere root is sphere_root() (rtw_device.h), quads and instances go through quad_pick /
 // instance_pick, triangles through tri_closest (rtw_tri.h) or the zero-safe tree walk (tri_tree_walk, rtw_mesh.h), mesh placements through mesh_closest, and the tie rule is Scene::collision_normal's as the oracle restates it
 // (closest_hit): within a group the first of equal t in list order, a later group only when strictly closer.  The sphere tree only prunes
-// (DESIGN.md "Conservative traversal"; the per-ray paddings below are those of render_bvh's trav_begin, global-node variant), and every
-// surviving candidate runs the exact test with ties to the lower index, so RTW_ACCEL_BVH answers bit for bit what RTW_ACCEL_BRUTE answers.
-// Constant-density instances are skipped: their hit is a random free path, and a query has no sample stream.
-#include "rtw_kernels.h"
+// (DESIGN.md "Conservative traversal"), and every surviving candidate runs the exact test with ties to the lower index, so RTW_ACCEL_BVH
+// answers bit for bit what RTW_ACCEL_BRUTE answers.  Constant-density instances are skipped: their hit is a random free path, and a query
+// has no sample stream.
+//
+// The exact sphere test up to its root, the tree walk with its paddings, q_ray_ordinary, the pixel ray, the ray load and the counter flush
+// are rtw_scene_walk.h's, the ONE definition this file shares with the any-hit passes of rtw_occluded.hip.  What is this
+// pass's own stays here: the acceptance of a root in range (q_sphere) and the loop over all the spheres kept outside the tree.
+#include "rtw_scene_walk.h"
 #include "rtw_mesh.h"
 
 namespace rtw {
 
 namespace {
 
-#define RTW_Q_KU 1.4305115e-6f      /* 24 * 2^-24: the rounding bound of the reference's quadratic (rtw_kernels.hip RTW_KU) */
-#define RTW_Q_DONE ((int)0x80000000) /* stack sentinel / empty tree (DevBvh.root of an empty tree is the same value) */
-
-template <class T> __device__ __forceinline__ T q_lds_get(uint32_t addr) { return *(const __attribute__((address_space(3))) T *)(uintptr_t)addr; }
-template <class T> __device__ __forceinline__ void q_lds_put(uint32_t addr, T v) { *(__attribute__((address_space(3))) T *)(uintptr_t)addr = v; }
-
-// One exact sphere test (sphere.rs:99-121), the arithmetic of closest_brute / exact_sphere.  LIST: candidates come in list order, the
+// One sphere candidate of the closest-hit pass: q_sphere_root's root, then this pass's acceptance.  LIST: candidates come in list order, the
 // reference's `min_hit == None || min_hit > i` (a NaN root can only enter first); else: any order, ties to the lower index, best_t starts at maxt.
 template <bool MOVING, bool LIST>
 __device__ __forceinline__ void q_sphere(f4 g, f4 vv, uint32_t s, v3 o, v3 d, float tm, float a, float ra, bool a_plain, float mint, float maxt,
                                          int &best, float &best_t) {
-    float cx = g.x, cy = g.y, cz = g.z;
-    if (MOVING) { cx = cx + vv.x * tm; cy = cy + vv.y * tm; cz = cz + vv.z * tm; }       // sphere.rs:100
-    const float ocx = o.x - cx, ocy = o.y - cy, ocz = o.z - cz;
-    const float b = ocx * d.x + ocy * d.y + ocz * d.z;
-    const float c = (ocx * ocx + ocy * ocy + ocz * ocz) - g.w;
-    const float disc = b * b - a * c;
-    if (!(disc < 0.0f)) {
-        const float x = sphere_root(b, disc, a, ra, a_plain, mint);
-        const bool in = !(x < mint || x > maxt);
+    q_sphere_root<MOVING>(g, vv, o, d, tm, a, ra, a_plain, mint, maxt, [&](float x, bool in) {
         const bool take = in && (LIST ? (best < 0 || best_t > x) : (x < best_t || (x == best_t && s < (uint32_t)best)));
         best = take ? (int)s : best; best_t = take ? x : best_t;
-    }
+    });
 }
 
 // The sphere group in list order (wave-uniform index, scalar loads)
@@ -51,8 +41,8 @@ __device__ __forceinline__ void q_sphere_list(const DevScene &sc, v3 o, v3 d, fl
     for (uint32_t s = 0; s < sc.n; ++s) q_sphere<MOVING, true>(geom[s], MOVING ? vel[s] : zero, s, o, d, tm, a, ra, a_plain, mint, maxt, best, best_t);
 }
 
-// The sphere group through the tree: the spheres kept outside it first, then a per-lane walk with its stack in LDS ([level][thread], one
-// conflict-free row per level; level 0 holds the sentinel).  `sp0`: LDS byte address of the lane's level-0 slot, `sp_top` of its last level.
+// The sphere group through the tree: the spheres kept outside it first, all n_big of them, then q_tree_walk from the root.  The walk prunes
+// against the closest root so far, and no leaf ends the lane: a later sphere may be closer.
 template <bool MOVING>
 __device__ __forceinline__ void q_sphere_tree(const DevScene &sc, const DevBvh &bv, v3 o, v3 d, float tm, float a, float ra, bool a_plain,
                                               float mint, float maxt, uint32_t sp0, uint32_t sp_top, int &best, float &best_t,
@@ -67,76 +57,12 @@ __device__ __forceinline__ void q_sphere_tree(const DevScene &sc, const DevBvh &
             q_sphere<MOVING, false>(bg[k], MOVING ? bvel[k] : f4{ 0, 0, 0, 0 }, bidx[k], o, d, tm, a, ra, a_plain, mint, maxt, best, best_t);
         n_tests += bv.n_big;
     }
-    // per-ray constants of the thick-ray slab test: conservative bounds only, so the hardware approximations with safety factors
-    const float ex = o.x - bv.cx, ey = o.y - bv.cy, ez = o.z - bv.cz;
-    const float M = (__builtin_fabsf(ex) + __builtin_fabsf(ey) + __builtin_fabsf(ez)) * 1.0001f + bv.centre_radius;   // >= |o - C| + R_c
-    const float q = (M * M + bv.r_max2) * RTW_Q_KU;
-    const float sq_q = __builtin_amdgcn_sqrtf(q) * 1.0001f;
-    float rho = fminf(q * bv.inv_2rmin, sq_q);
-    rho = rho * 1.0001f + 4.8e-7f * (fabsf(o.x) + fabsf(o.y) + fabsf(o.z) + bv.abs_max);
-    const float tau = sq_q * 1.0002f * __builtin_amdgcn_rsqf(a) + 1e-30f;
-    float ix = __builtin_amdgcn_rcpf(d.x), iy = __builtin_amdgcn_rcpf(d.y), iz = __builtin_amdgcn_rcpf(d.z);
-    if (!(fabsf(d.x) >= 1e-20f)) ix = copysignf(1e20f, d.x);
-    if (!(fabsf(d.y) >= 1e-20f)) iy = copysignf(1e20f, d.y);
-    if (!(fabsf(d.z) >= 1e-20f)) iz = copysignf(1e20f, d.z);
-    const float kpx = -(o.x + rho) * ix, kpy = -(o.y + rho) * iy, kpz = -(o.z + rho) * iz;      // t(lo) = fma(lo, 1/d, -(o + rho) / d)
-    const float kmx = -(o.x - rho) * ix, kmy = -(o.y - rho) * iy, kmz = -(o.z - rho) * iz;      // t(hi) = fma(hi, 1/d, -(o - rho) / d)
-    const float lo_lim = mint - tau;
-
-    const uint32_t level = RTW_BLOCK * 4u;
-    uint32_t sp = sp0;
-    q_lds_put<int>(sp, RTW_Q_DONE);
-    int node = bv.root;
-    for (;;) {
-        if (ballot64(node != RTW_Q_DONE) == 0ull) break;
-        if (node >= 0) {                                           // an inner node: two slab tests, the nearer child next, the farther pushed
-            const f4 *np = (const f4 *)(bv.nodes + node);
-            const f4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
-            const int c0 = __float_as_int(n3.x), c1 = __float_as_int(n3.y);
-            n_nodes++;
-            float t1, t2;
-            t1 = __builtin_fmaf(n0.x, ix, kpx); t2 = __builtin_fmaf(n0.w, ix, kmx);
-            float e0 = fminf(t1, t2), x0 = fmaxf(t1, t2);
-            t1 = __builtin_fmaf(n0.y, iy, kpy); t2 = __builtin_fmaf(n1.x, iy, kmy);
-            e0 = fmaxf(e0, fminf(t1, t2)); x0 = fminf(x0, fmaxf(t1, t2));
-            t1 = __builtin_fmaf(n0.z, iz, kpz); t2 = __builtin_fmaf(n1.y, iz, kmz);
-            e0 = fmaxf(e0, fminf(t1, t2)); x0 = fminf(x0, fmaxf(t1, t2));
-            t1 = __builtin_fmaf(n1.z, ix, kpx); t2 = __builtin_fmaf(n2.y, ix, kmx);
-            float e1 = fminf(t1, t2), x1 = fmaxf(t1, t2);
-            t1 = __builtin_fmaf(n1.w, iy, kpy); t2 = __builtin_fmaf(n2.z, iy, kmy);
-            e1 = fmaxf(e1, fminf(t1, t2)); x1 = fminf(x1, fmaxf(t1, t2));
-            t1 = __builtin_fmaf(n2.x, iz, kpz); t2 = __builtin_fmaf(n2.w, iz, kmz);
-            e1 = fmaxf(e1, fminf(t1, t2)); x1 = fminf(x1, fmaxf(t1, t2));
-            const float hi_lim = best_t + tau;
-            const float m0 = fmaxf(e0, lo_lim), m1 = fmaxf(e1, lo_lim);
-            const bool h0 = m0 <= fminf(x0, hi_lim), h1 = m1 <= fminf(x1, hi_lim);
-            if (h0 && h1) {
-                const bool near0 = m0 <= m1;
-                if (sp < sp_top) { sp += level; q_lds_put<int>(sp, near0 ? c1 : c0); }
-                else overflow = true;                              // (never with build_bvh's depth; reported as RTW_E_INTERNAL)
-                node = near0 ? c0 : c1;
-            } else if (h0 || h1) {
-                node = h0 ? c0 : c1;
-            } else {
-                node = q_lds_get<int>(sp); sp -= level;
-            }
-        }
-        if (node < 0 && node != RTW_Q_DONE) {                      // a leaf: the exact test, then the next entry off the stack
-            const uint32_t s = (uint32_t)~node;
-            q_sphere<MOVING, false>(sc.geom[s], MOVING ? sc.vel[s] : f4{ 0, 0, 0, 0 }, s, o, d, tm, a, ra, a_plain, mint, maxt, best, best_t);
-            n_tests++;
-            node = q_lds_get<int>(sp); sp -= level;
-        }
-    }
-}
-
-// Can the tree answer this ray?  The pruning presumes the reference's quadratic in ORDINARY f32 (rtw_shim.hip decides the same for a
-// render from its camera): a finite ray, |o| + |d| below 2^60, d.d within [1e-30, 1e30], and |d| x (the farthest centre + |o|) below 1e18.
-// Any other ray (NaN roots pass the reference's range tests: an order-dependent answer) walks the list.
-__device__ __forceinline__ bool q_ray_ordinary(v3 o, v3 d, float a, float span) {
-    const float no = __builtin_fabsf(o.x) + __builtin_fabsf(o.y) + __builtin_fabsf(o.z);
-    const float nd = __builtin_fabsf(d.x) + __builtin_fabsf(d.y) + __builtin_fabsf(d.z);
-    return no + nd < 0x1p60f && a >= 1e-30f && a <= 1e30f && fmaxf(nd, 2.0f) * (span + no + 1.0f) <= 1e18f;      // (nd >= |d|; NaN fails)
+    q_tree_walk(bv, o, d, a, mint, sp0, sp_top, bv.root, [&] { return best_t; },
+                [&](uint32_t s) {
+                    q_sphere<MOVING, false>(sc.geom[s], MOVING ? sc.vel[s] : f4{ 0, 0, 0, 0 }, s, o, d, tm, a, ra, a_plain, mint, maxt, best, best_t);
+                    return false;
+                },
+                n_tests, n_nodes, overflow);
 }
 
 } // namespace
@@ -151,17 +77,8 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
     bool overflow = false;
     if (i < A.n) {
         v3 o, d;
-        if (CAM) {
-            // Rust2/src/viewport.rs:77-80 then :63: left_top + delta_x * (i / width) + delta_y * (j / height), normalised
-            const uint32_t px = i % A.width, py = i / A.width;
-            const float fx = (float)px / (float)A.width, fy = (float)py / (float)A.height;
-            o = ld3(A.cam.origin);
-            d = unit((ld3(A.cam.pixel00) + ld3(A.cam.delta_u) * fx) + ld3(A.cam.delta_v) * fy);
-        } else {
-            const float2 *r = (const float2 *)(A.rays + 6 * (size_t)i);
-            const float2 r0 = r[0], r1 = r[1], r2 = r[2];
-            o = mk(r0.x, r0.y, r1.x); d = mk(r1.y, r2.x, r2.y);
-        }
+        if (CAM) q_pixel_ray(A.cam, A.width, A.height, i, o, d);
+        else q_ray_load(A.rays, i, o, d);
         const float tm = A.time, mint = A.mint, maxt = A.maxt;
         const float a = dot(d, d);
         const float ra = rcp_refined(a);
@@ -171,9 +88,9 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
         bool listed = true;
         if (TREE) {
             if (q_ray_ordinary(o, d, a, A.span)) {
-                const uint32_t sp0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)q_lds + threadIdx.x * 4u;
-                q_sphere_tree<MOVING>(A.sc, A.bvh, o, d, tm, a, ra, a_plain, mint, maxt, sp0, sp0 + (A.levels - 1u) * (RTW_BLOCK * 4u), best, best_t,
-                                      n_sph, n_nodes, overflow);
+                const uint32_t sp0 = q_stack_base(q_lds);
+                q_sphere_tree<MOVING>(A.sc, A.bvh, o, d, tm, a, ra, a_plain, mint, maxt, sp0, q_stack_top(sp0, A.levels), best, best_t, n_sph, n_nodes,
+                                      overflow);
                 listed = false;
             }
         }
@@ -257,33 +174,14 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
             *reinterpret_cast<float3 *>(A.normal_out + 3 * (size_t)i) = make_float3(nrm.x, nrm.y, nrm.z);
         }
     }
-    // counters: summed over the wave, one atomic per wave and counter (as tri_hits_kernel), on the workgroup's line of A.counters
-    unsigned long long s0 = n_sph, s1 = n_nodes, s2 = n_quad;
-    for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); s2 += __shfl_down(s2, off); }
-    const bool any_overflow = ballot64(overflow) != 0ull;
-    if ((threadIdx.x & 63u) == 0) {
-        unsigned long long *line = A.counters + (blockIdx.x % RTW_QUERY_SLOTS) * RTW_QUERY_STRIDE;
-        if (s0) atomicAdd(&line[0], s0);
-        if (s1) atomicAdd(&line[1], s1);
-        if (s2) atomicAdd(&line[2], s2);
-        if (any_overflow) atomicAdd(&line[3], 1ull);
-    }
-}
-
-typedef void (*query_fn)(const QueryArgs);
-template <bool CAM, bool NORMALS, bool TREE>
-static query_fn pick_query_moving(bool moving) {
-    return moving ? scene_hits_kernel<CAM, NORMALS, TREE, true> : scene_hits_kernel<CAM, NORMALS, TREE, false>;
-}
-template <bool CAM, bool NORMALS>
-static query_fn pick_query_tree(bool tree, bool moving) {
-    return tree ? pick_query_moving<CAM, NORMALS, true>(moving) : pick_query_moving<CAM, NORMALS, false>(moving);
+    RTW_Q_COUNT_FLUSH(A.counters, n_sph, n_nodes, n_quad, overflow, 0u);
 }
 
 void launch_scene_hits(const QueryArgs &q, bool from_camera, bool tree, hipStream_t stream) {
-    const bool normals = q.normal_out != nullptr, moving = q.sc.moving != 0u;
-    const query_fn fn = from_camera ? (normals ? pick_query_tree<true, true>(tree, moving) : pick_query_tree<true, false>(tree, moving))
-                                    : (normals ? pick_query_tree<false, true>(tree, moving) : pick_query_tree<false, false>(tree, moving));
+    typedef void (*query_fn)(const QueryArgs);
+    const query_fn fn = with_bools([](auto cam, auto normals, auto tr, auto moving) -> query_fn {
+        return scene_hits_kernel<cam.value, normals.value, tr.value, moving.value>;
+    }, from_camera, q.normal_out != nullptr, tree, q.sc.moving != 0u);
     const uint32_t lds = tree ? q.levels * RTW_BLOCK * 4u : 0u;
     hipLaunchKernelGGL(fn, dim3((q.n + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), lds, stream, q);
 }

@@ -372,6 +372,35 @@ static int counted_pass(rtw_ctx *c, Staging &st, uint32_t samples, uint64_t extr
     return sum[3] ? RTW_E_INTERNAL : RTW_OK;
 }
 
+// ---- what the fused passes (ambient occlusion, direct lighting; kernels: rtw_occluded.hip) share on top of it ---------------------------
+// A fused launch over n points: everything zero, a.q the scene_views of the points and the range of its rays, and the sampling fields.
+// A: AoArgs or DirectArgs, which name these fields alike.
+template <class A>
+static void fused_args(const rtw_ctx *c, uint32_t n, uint32_t samples, uint32_t seed, float time, float mint, float maxt, uint32_t accel, A &a) {
+    std::memset(&a, 0, sizeof a);
+    scene_views(c, n, time, mint, maxt, accel, a.q);
+    a.samples = samples; a.seed = seed;
+    while ((1u << a.lg_group) < samples && a.lg_group < 6u) a.lg_group++;
+}
+
+// The depth pass of a map call -- rtw_ctx_depth_map's launch with ids and normals -- and the buffers it hands to the pass behind it: each of
+// the three outputs is the caller's where it was asked for (staged like any output) and scratch where not, and `src` reads all three for the
+// same camera.  The two launches then run on the context's stream between one pair of events, with one set of counters.
+template <class A>
+static QueryArgs depth_pass(const rtw_ctx *c, Staging &st, const RtwCamera *cam, uint32_t width, uint32_t height, float time, float mint, float maxt,
+                            uint32_t accel, float *depth_out, int32_t *idx_out, float *normal_out, A &src) {
+    const uint32_t n = width * height;
+    QueryArgs q;
+    scene_views(c, n, time, mint, maxt, accel, q);
+    src.cam = q.cam = *cam; src.width = q.width = width; src.height = q.height = height;
+    q.miss_t = host_mul(maxt, 1.6f);
+    const size_t t_bytes = sizeof(float) * (size_t)n, i_bytes = sizeof(int32_t) * (size_t)n;
+    src.depth = q.t_out = depth_out ? st.out(depth_out, t_bytes) : st.scratch<float>(t_bytes);
+    src.idx = q.idx_out = idx_out ? st.out(idx_out, i_bytes) : st.scratch<int32_t>(i_bytes);
+    src.normals = q.normal_out = normal_out ? st.out(normal_out, 3 * t_bytes) : st.scratch<float>(3 * t_bytes);
+    return q;
+}
+
 extern "C" {
 
 int rtw_abi_version(void) { return RTW_ABI_VERSION; }
@@ -1211,13 +1240,7 @@ int rtw_ctx_scene_occluded(rtw_ctx *c, const float *rays, uint32_t n, float time
     return counted_pass(c, st, 0, n, stats, [&] { launch_scene_occluded(q, tree, c->stream); });
 }
 
-// ---- ambient occlusion (rtw.h "ambient occlusion"; kernel: rtw_occluded.hip; the rule: rtw_ao.h) ----------------------------------------
-// The sampling fields of an AO launch; a.q: scene_views over the points and the range of the AO rays
-static void ao_sampling(uint32_t samples, uint32_t seed, AoArgs &a) {
-    a.samples = samples; a.seed = seed; a.lg_group = 0;
-    while ((1u << a.lg_group) < samples && a.lg_group < 6u) a.lg_group++;
-}
-
+// ---- ambient occlusion (rtw.h "ambient occlusion"; the rule: rtw_ao.h) ------------------------------------------------------------------
 int rtw_ctx_ambient_occlusion(rtw_ctx *c, const float *points, const float *normals, uint32_t n, uint32_t samples, uint32_t seed, float time,
                               float mint, float maxt, uint32_t accel, float *ao_out, RtwStats *stats) {
     if (!c || !points || !normals || !ao_out || n == 0 || !ao_samples_ok(samples) || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
@@ -1228,9 +1251,7 @@ int rtw_ctx_ambient_occlusion(rtw_ctx *c, const float *points, const float *norm
     const bool tree = query_uses_tree(c, accel, time, mint, maxt);
 
     AoArgs a;
-    std::memset(&a, 0, sizeof a);
-    scene_views(c, n, time, mint, maxt, accel, a.q);
-    ao_sampling(samples, seed, a);
+    fused_args(c, n, samples, seed, time, mint, maxt, accel, a);
 
     const size_t v_bytes = 3 * sizeof(float) * (size_t)n;
     Staging st(c);
@@ -1240,8 +1261,7 @@ int rtw_ctx_ambient_occlusion(rtw_ctx *c, const float *points, const float *norm
     return counted_pass(c, st, samples, 0, stats, [&] { launch_ambient_occlusion(a, false, tree, c->stream); });
 }
 
-// rtw_ctx_depth_map with ids and normals into the caller's device buffers or scratch, then the AO kernel's camera form over them: two launches
-// on the context's stream between one pair of events, one set of counters
+// depth_pass, then the AO kernel's camera form over its outputs
 int rtw_ctx_ao_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, float time, float mint, float maxt, uint32_t samples,
                    uint32_t seed, float ao_mint, float ao_maxt, uint32_t accel, float *ao_out, float *depth_out, int32_t *idx_out,
                    float *normal_out, RtwStats *stats) {
@@ -1253,28 +1273,17 @@ int rtw_ctx_ao_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t he
     const uint32_t n = width * height;
     const bool tree = query_uses_tree(c, accel, time, mint, maxt), ao_tree = query_uses_tree(c, accel, time, ao_mint, ao_maxt);
 
-    QueryArgs q;                         // the depth pass: scene_query's launch
-    scene_views(c, n, time, mint, maxt, accel, q);
-    q.cam = *cam; q.width = width; q.height = height;
-    q.miss_t = host_mul(maxt, 1.6f);
-
     AoArgs a;
-    std::memset(&a, 0, sizeof a);
-    scene_views(c, n, time, ao_mint, ao_maxt, accel, a.q);
-    ao_sampling(samples, seed, a);
-    a.cam = *cam; a.width = width; a.height = height;
+    fused_args(c, n, samples, seed, time, ao_mint, ao_maxt, accel, a);
 
-    const size_t t_bytes = sizeof(float) * (size_t)n, i_bytes = sizeof(int32_t) * (size_t)n;
-    Staging st(c);                       // the depth pass's outputs are scratch where the caller did not ask for them
-    a.ao_out = st.out(ao_out, t_bytes);
-    a.depth = q.t_out = depth_out ? st.out(depth_out, t_bytes) : st.scratch<float>(t_bytes);
-    a.idx = q.idx_out = idx_out ? st.out(idx_out, i_bytes) : st.scratch<int32_t>(i_bytes);
-    a.normals = q.normal_out = normal_out ? st.out(normal_out, 3 * t_bytes) : st.scratch<float>(3 * t_bytes);
+    Staging st(c);
+    a.ao_out = st.out(ao_out, sizeof(float) * (size_t)n);
+    const QueryArgs q = depth_pass(c, st, cam, width, height, time, mint, maxt, accel, depth_out, idx_out, normal_out, a);
     return counted_pass(c, st, samples, n, stats, [&] { launch_scene_hits(q, true, tree, c->stream); },
                         [&] { launch_ambient_occlusion(a, true, ao_tree, c->stream); });
 }
 
-// ---- direct lighting (rtw.h "direct lighting"; kernel: rtw_occluded.hip; the rule: rtw_direct.h) -----------------------------------------
+// ---- direct lighting (rtw.h "direct lighting"; the rule: rtw_direct.h) --------------------------------------------------------------------
 // The statuses both calls share once their own arguments are in order; n: the points
 static int direct_ready(const rtw_ctx *c, uint64_t n, uint32_t samples) {
     if (c->pend.active) return RTW_E_INVALID;
@@ -1286,12 +1295,13 @@ static int direct_ready(const rtw_ctx *c, uint64_t n, uint32_t samples) {
 
 uint32_t rtw_ctx_light_count(const rtw_ctx *c) { return c ? (uint32_t)c->light_rows.size() : 0u; }
 
-// The sampling fields of a launch and the light table, staged from the context's rows; a.q: scene_views over the points and [lo, hi]
-static void direct_sampling(const rtw_ctx *c, Staging &st, uint32_t samples, uint32_t seed, DirectArgs &a) {
-    a.samples = samples; a.seed = seed; a.lg_group = 0;
-    while ((1u << a.lg_group) < samples && a.lg_group < 6u) a.lg_group++;
+// The arguments of a launch over n points and [lo, hi]: views, sampling, and the light table, staged from the context's rows
+static DirectArgs direct_args(const rtw_ctx *c, Staging &st, uint32_t n, uint32_t samples, uint32_t seed, float time, float lo, float hi, uint32_t accel) {
+    DirectArgs a;
+    fused_args(c, n, samples, seed, time, lo, hi, accel, a);
     a.n_lights = (uint32_t)c->light_rows.size();
     a.lights = st.in(c->light_rows.data(), sizeof(DirectRow) * c->light_rows.size());
+    return a;
 }
 
 int rtw_ctx_direct_light(rtw_ctx *c, const float *points, const float *normals, uint32_t n, uint32_t samples, uint32_t seed, float time, float lo,
@@ -1301,12 +1311,8 @@ int rtw_ctx_direct_light(rtw_ctx *c, const float *points, const float *normals, 
     HIP_TRY(hipSetDevice(c->device));
     const bool tree = query_uses_tree(c, accel, time, lo, hi);
 
-    DirectArgs a;
-    std::memset(&a, 0, sizeof a);
-    scene_views(c, n, time, lo, hi, accel, a.q);
     Staging st(c);
-    direct_sampling(c, st, samples, seed, a);
-
+    DirectArgs a = direct_args(c, st, n, samples, seed, time, lo, hi, accel);
     const size_t v_bytes = 3 * sizeof(float) * (size_t)n, o_bytes = sizeof(float) * (size_t)n * a.n_lights;
     a.points = st.in(points, v_bytes);
     a.normals = st.in(normals, v_bytes);
@@ -1315,8 +1321,7 @@ int rtw_ctx_direct_light(rtw_ctx *c, const float *points, const float *normals, 
     return counted_pass(c, st, 1, 0, stats, [&] { launch_direct_light(a, false, tree, c->stream); });
 }
 
-// rtw_ctx_depth_map with ids and normals into the caller's device buffers or scratch, then the direct-lighting kernel's camera form over them
-// (rtw_ctx_ao_map's frame: two launches between one pair of events, one set of counters)
+// depth_pass, then the direct-lighting kernel's camera form over its outputs
 int rtw_ctx_direct_light_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, float time, float mint, float maxt,
                              uint32_t samples, uint32_t seed, float lo, float hi, uint32_t accel, float *vis_out, float *irr_out,
                              float *depth_out, int32_t *idx_out, float *normal_out, RtwStats *stats) {
@@ -1327,24 +1332,12 @@ int rtw_ctx_direct_light_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, u
     const uint32_t n = width * height;
     const bool tree = query_uses_tree(c, accel, time, mint, maxt), light_tree = query_uses_tree(c, accel, time, lo, hi);
 
-    QueryArgs q;                         // the depth pass: scene_query's launch
-    scene_views(c, n, time, mint, maxt, accel, q);
-    q.cam = *cam; q.width = width; q.height = height;
-    q.miss_t = host_mul(maxt, 1.6f);
-
-    DirectArgs a;
-    std::memset(&a, 0, sizeof a);
-    scene_views(c, n, time, lo, hi, accel, a.q);
-    Staging st(c);                       // the depth pass's outputs are scratch where the caller did not ask for them
-    direct_sampling(c, st, samples, seed, a);
-    a.cam = *cam; a.width = width; a.height = height;
-
-    const size_t t_bytes = sizeof(float) * (size_t)n, i_bytes = sizeof(int32_t) * (size_t)n, o_bytes = t_bytes * a.n_lights;
+    Staging st(c);
+    DirectArgs a = direct_args(c, st, n, samples, seed, time, lo, hi, accel);
+    const size_t o_bytes = sizeof(float) * (size_t)n * a.n_lights;
     a.vis_out = st.out(vis_out, o_bytes);
     if (irr_out) a.irr_out = st.out(irr_out, o_bytes);
-    a.depth = q.t_out = depth_out ? st.out(depth_out, t_bytes) : st.scratch<float>(t_bytes);
-    a.idx = q.idx_out = idx_out ? st.out(idx_out, i_bytes) : st.scratch<int32_t>(i_bytes);
-    a.normals = q.normal_out = normal_out ? st.out(normal_out, 3 * t_bytes) : st.scratch<float>(3 * t_bytes);
+    const QueryArgs q = depth_pass(c, st, cam, width, height, time, mint, maxt, accel, depth_out, idx_out, normal_out, a);
     return counted_pass(c, st, 1, n, stats, [&] { launch_scene_hits(q, true, tree, c->stream); },
                         [&] { launch_direct_light(a, true, light_tree, c->stream); });
 }

@@ -304,6 +304,26 @@ def test_the_camera_forms_whole_call_fallbacks(gpu, oracle):
                 assert depth > 0 and second == 0, (ao, "a NaN in the second pass's range", second_range, depth, second)
 
 
+@pytest.mark.parametrize("mode", BOTH)
+def test_the_camera_forms_round_loop_on_a_moving_scene(gpu, oracle, mode):
+    """128 samples (two rounds) from the camera at a time inside the shutter, through the tree and the lists: the builds <CAM, TREE or not,
+    MOVING, not ONE> of both fused kernels, which no other case launches.  A 65 x 2 map: a wave edge plus one."""
+    scene, lights, (t0, t1), _, _, _ = AE.dl_set(oracle, "moving 38+9")
+    width, height, samples = 65, 2, 128
+    cam = QE.forty_camera(width, height)
+    gpu.set_scene(scene, t0, t1)
+    gpu.set_lights(lights)
+    with Mode(gpu, mode) as accel:
+        what = (mode, samples, TIME)
+        ao, ids, _ = TA.check_map(gpu, cam, width, height, what, samples=samples, radius=1.0, accel=accel, time=TIME)
+        assert same(ao, ao_map_oracle(gpu, oracle, scene, cam, width, height, MINT, MAXT, samples, 1.0, AO.AO_MINT, 0, TIME, accel)), what
+        vis, irr, _ = TD.check_map(gpu, cam, width, height, what, samples=samples, accel=accel, time=TIME)
+        want = direct_map_oracle(gpu, oracle, scene, lights, cam, width, height, MINT, MAXT, samples, 0, TIME, DL.LO, DL.HI, accel)
+        assert same(vis, want[0]) and same(irr, want[1]), what
+        st = gpu.direct_light_map(cam, width, height, MINT, MAXT, samples, time=TIME, accel=accel)[-1]
+    assert (ids >= 0).sum() >= 8 and (st.node_tests > 0) == (mode == "tree forced"), (mode, int((ids >= 0).sum()), st.node_tests)
+
+
 # ---- 4. a light that moves ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", BOTH)
 @pytest.mark.parametrize("key", list(AE.MOVING_LIGHTS))
