@@ -871,7 +871,9 @@ __device__ __forceinline__ void exact_sphere(f4 g, f4 vv, uint32_t s, v3 o, v3 d
 // The scheduler's constants as a build of render_bvh sees them.  The values above were tuned on the f16 walk in 256-thread workgroups at
 // seven waves per SIMD and stay what every such build runs; the 768-thread builds (f32 planes, six waves per SIMD, a cheaper visit) have a
 // set of their own, swept on the bench frame one at a time (profiles/visit_class_sched_sweep.log).  Scheduling decides WHEN a lane's
-// steps run, never what they compute: every set renders the same frame.
+// steps run, never what they compute: every set renders the same frame.  Swept again after the SHADE step's trim by instruction class
+// (profiles/shade_class_ab.log, section 4): S_HI 44 (chain 21) / 48 (chain 17) / 52 / 56 = 65.96 / 65.16 / 65.08 / 65.39 ms,
+// T_LO 4 / 6 / 8 = 65.02 / 65.07 / 65.08 -- nothing moved.
 #ifndef RTW_S_HI_LARGE
 #define RTW_S_HI_LARGE RTW_S_HI /* 44 / 48 / 52 / 56 / 60 = 68.03 / 67.42 / 67.36 / 67.94 / 68.60 ms of the bench frame */
 #endif
@@ -926,6 +928,13 @@ __device__ __forceinline__ uint32_t lanes_in(bool c) {
     asm volatile("" : "+s"(n));
     return n;
 }
+// ... and the lane mask itself, for a step that wants it again: balloted a second time in another block it is a v_cndmask / v_cmp pair (4.2)
+__device__ __forceinline__ uint32_t lanes_in(bool c, unsigned long long &m) {
+    m = ballot64(c);
+    uint32_t n = (uint32_t)__popcll(m);
+    asm volatile("" : "+s"(n));
+    return n;
+}
 
 // Begin a closest-hit query: big spheres, per-ray constants, root (which sets the phase).
 // What a query's begin needs of DevBvh -- big_geom .. abs_max, 16 dwords -- read from the argument block with one scalar load, for the
@@ -959,15 +968,22 @@ template <class T> __device__ __forceinline__ T lds_get(uint32_t addr) { return 
 template <class T> __device__ __forceinline__ void lds_put(uint32_t addr, T v) { *(__attribute__((address_space(3))) T *)(uintptr_t)addr = v; }
 __device__ __forceinline__ uint32_t lds_addr(const void *p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p; }
 
+// d.d outside [2^-20, 2^20] (or NaN): !in_range(a, 0x1p-20f, 0x1p20f) as ONE unsigned compare of the bit pattern, so that a ballot of it is the
+// compare's own lane mask (the two float compares met in a scalar OR, and a ballot of that is a v_cndmask / v_cmp pair on top).  A sum of
+// squares has no sign bit unless it is a NaN, and anything with one counts as outside: the generic root, the same bits.
+__device__ __forceinline__ bool a_outside_plain(float a) { return __float_as_uint(a) - 0x35800000u > 0x49800000u - 0x35800000u; }
+
 // F32: the LDS copy is the f32 plane format (the builds that visit nodes with trav_node_lds32)
-template <bool MOVING, class S, bool F32 = false>
+// A_BITS: d.d's range test as a_outside_plain() (the builds with the two-halves step; the others keep the two float compares and their bytes)
+template <bool MOVING, class S, bool F32 = false, bool A_BITS = false>
 __device__ __forceinline__ void trav_begin(const KArgs &A, const Path &pt, Trav &tr, uint32_t sp0, bool a_plain_wave, bool &a_odd, Cen *cn = nullptr) {
     RTW_CEN(cn, CEN_TRAV_BEGIN);
     const BvhBegin bv = load_bvh_begin();
     const v3 o = pt.o, d = pt.d;
     tr.a = dot(d, d);
     tr.ra = rcp_refined(tr.a);
-    a_odd = !in_range(tr.a, 0x1p-20f, 0x1p20f);           // (per lane; the caller folds it into the wave's sticky flag where the wave is whole)
+    // (per lane, the lanes that begin a query here; the caller folds it -- A_BITS: the same test of tr.a -- into the wave's sticky flag where the wave is whole)
+    a_odd = A_BITS ? a_outside_plain(tr.a) : !in_range(tr.a, 0x1p-20f, 0x1p20f);
     const bool a_plain = a_plain_wave && ballot64(a_odd) == 0ull;
     tr.best = -1; tr.best_t = A.maxt; tr.sp = sp0;           // the lane's level-0 slot (the sentinel)
     {   // big spheres: uniform loop, scalar loads
@@ -1328,7 +1344,8 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
         // larger of the two traversal queues runs.
         uint32_t nT = lanes_in(in_trav<stack_t>(tr.node));
         const uint32_t nL = lanes_in(in_leaf<stack_t>(tr.node));
-        const uint32_t nS = lanes_in(in_shade<stack_t>(tr.node));
+        unsigned long long m_shade;
+        const uint32_t nS = lanes_in(in_shade<stack_t>(tr.node), m_shade);
         if ((nT | nL | nS) == 0u) break;                     // every lane is DEAD
         // Safety valve of the persistent loop: a wave that has taken an absurd number of scheduler trips (the bench frame needs ~130 k per
         // wave) gives up instead of hanging the GPU; the launch then reports RTW_E_INTERNAL (stats[23] counts such waves).
@@ -1352,9 +1369,10 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
         if (run_shade) {
             c_steps[2]++; c_lanes[2] += nS;
             // a. the closest-hit query this lane was waiting on is complete: scatter, or end the path
+            // (lane masks that count or steer are ballots of ONE compare each, met in scalar code: a ballot of a bool that comes out of a divergent
+            //  join or of an AND of two compares is a v_cndmask / v_cmp pair at full exec on top of the compares, 4.2)
             bool need_unit = false, started = false, a_odd = false;
             const bool shading = in_shade<stack_t>(tr.node);
-            w_seg += (uint32_t)__popcll(ballot64(shading && (fl & F_INFLIGHT) != 0u));
 #ifdef RTW_STAMP
             t_sub = t_begin;
 #endif
@@ -1364,45 +1382,57 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
             // a. the closest-hit query this lane was waiting on is complete.  Paths that END here -- the ray missed (sky), or its depth is
             //    exhausted (black) -- are finished first, so that their lanes' next camera rays and the hits' scatter directions meet in ONE
             //    rejection loop further down; the lanes that hit keep unit(direction) until then.
+            //    Whether the path ends is two compares met in scalar code, not a flag: these builds never carry F_DONE from one step to the
+            //    next, and setting it in three nested lane regions only to test it again below was a write of exec per region ahead of one
+            //    flag instruction each.
+            // (the empty asm keeps the masked bit ONE value: the optimiser otherwise tests it twice, as v_and / v_cmp for the branch and v_bfe / v_cmp for the ballot)
+            uint32_t fl_inflight = fl & F_INFLIGHT;
+            asm volatile("" : "+v"(fl_inflight));
+            const bool inflight = fl_inflight != 0u;
+            w_seg += (uint32_t)__popcll(m_shade & ballot64(inflight));
             v3 nrm, ud; float metal;
-            bool hit = false;
-            if (shading) {
-                RTW_CEN(cn, CEN_SHADING);
-                if (fl & F_INFLIGHT) {
-                    fl &= ~F_INFLIGHT;
-                    RTW_CEN(cn, CEN_INFLIGHT);
-                    ud = unit(pt.d);
-                    // (the radiance of a path that ends -- sky, or black at exhausted depth -- is formed in the bank block below, where it is
-                    //  stored: formed here it lived across the join, three registers that the MOVING builds spilled and reloaded in every step)
-                    if (tr.best < 0) { RTW_CEN(cn, CEN_MISS); fl |= F_DONE; }
-                    else if ((fl >> F_K_SHIFT) + 1u >= A.depth) { RTW_CEN(cn, CEN_DEPTH_END); fl |= F_DONE; }   // depth exhausted: the innermost call returns black
-                    else { hit = true; fl += 1u << F_K_SHIFT; }         // (the bounce count of these builds: Path.k is not carried)
-                }
+            bool hit = false, done = false;
+            if (shading) RTW_CEN(cn, CEN_SHADING);
+            if (shading && inflight) {
+                fl &= ~F_INFLIGHT;
+                RTW_CEN(cn, CEN_INFLIGHT);
+                ud = unit(pt.d);
+                // (the radiance of a path that ends -- sky, or black at exhausted depth -- is formed in the bank block below, where it is
+                //  stored: formed here it lived across the join, three registers that the MOVING builds spilled and reloaded in every step)
+                const bool miss = tr.best < 0;
+                const bool deep = (fl >> F_K_SHIFT) + 1u >= A.depth;       // depth exhausted: the innermost call returns black
+                if (miss) RTW_CEN(cn, CEN_MISS); else if (deep) RTW_CEN(cn, CEN_DEPTH_END);
+                done = miss | deep;
+                hit = !done;                                                // (its bounce is counted where the hit is shaded, below)
             }
             RTW_SUB_STAMP(0);
-            if (shading) {
-                if (fl & F_DONE) {
-                    fl &= ~F_DONE;
-                    // in these builds F_DONE is only ever set a few lines up, in this same step: tr.best still tells a miss from an exhausted depth
-                    if (tr.best < 0) shade_miss<SPEC>(A, pt, ud); else pt.L = mk(0, 0, 0);
-                    if (finish_path<SPEC>(A, px, pt, cn)) fl &= ~F_HAVE; else fl |= F_NEWPATH;
-                }
-                need_unit = (fl & F_HAVE) == 0u;
-                if (need_unit) RTW_CEN(cn, CEN_NEED_UNIT);
+            if (done) {
+                // tr.best still tells a miss from an exhausted depth
+                if (tr.best < 0) shade_miss<SPEC>(A, pt, ud); else pt.L = mk(0, 0, 0);
+                // (one select on the flag word: as two lane regions the update was four writes of exec around two instructions)
+                const bool unit_done = finish_path<SPEC>(A, px, pt, cn);
+                fl = unit_done ? fl & ~F_HAVE : fl | F_NEWPATH;
             }
-            // b. next work unit (every lane of the wave: the reserve stays wave-uniform; see the generic path below)
+            // b. next work unit (every lane of the wave: the reserve stays wave-uniform; see the generic path below).  Asked of the flag word
+            //    alone: a lane in TRAVERSE or LEAF owns a unit, and a DEAD lane -- there is none before the wave has found every sub-queue
+            //    empty, and then the reserve stays empty -- asks in vain and is told `exhausted` again, which only a lane in SHADE acts on.
+            need_unit = (fl & F_HAVE) == 0u;
+            if (need_unit && shading) RTW_CEN(cn, CEN_NEED_UNIT);
             bool exhausted = false;
             const bool got = fetch_pixel(A, need_unit, px, exhausted, rs);
             if (ballot64(exhausted) != 0ull) t_lo = SC.t_lo_drain;
             RTW_SUB_STAMP(1);
-            if (shading) {
-                if (got) fl |= F_HAVE | F_NEWPATH;
-                if (exhausted) tr.node = (int)Code<stack_t>::DEAD;
-                // c. next camera ray, up to its lens sample
-                if ((fl & F_HAVE) && (fl & F_NEWPATH)) { fl &= F_HAVE | F_INFLIGHT | F_DONE; start_path_first(px, pt, cn); need_disk = true; started = true; }   // (clears F_NEWPATH and the bounce count)
-            }
+            if (got) fl |= F_HAVE | F_NEWPATH;
+            if (shading && exhausted) tr.node = (int)Code<stack_t>::DEAD;
+            // c. next camera ray, up to its lens sample.  F_NEWPATH is only ever set on a lane in SHADE (above, in this step), so the flag word alone says it
+            started = (fl & (F_HAVE | F_NEWPATH)) == (F_HAVE | F_NEWPATH);
+            w_rays += (uint32_t)__popcll(ballot64(started));
+            if (started) { fl &= F_HAVE | F_INFLIGHT | F_DONE; start_path_first(px, pt, cn); need_disk = true; }   // (clears F_NEWPATH and the bounce count)
             //    ... the hit, up to its random unit vector
-            if (hit) shade_hit_first<MOVING, SPEC>(A, pt, ud, tr.best, tr.best_t, need_ball, nrm, metal, front, cn);
+            if (hit) {
+                fl += 1u << F_K_SHIFT;                   // (the bounce count of these builds: Path.k is not carried)
+                shade_hit_first<MOVING, SPEC>(A, pt, ud, tr.best, tr.best_t, need_ball, nrm, metal, front, cn);
+            }
             // d. ONE rejection loop: points of the unit ball for the lanes that scatter, of the unit disk for the lanes that start a path
             float sx, sy, sz, sl2;
             sample_ball_or_disk(pt.rng, need_ball || need_disk, need_ball, sx, sy, sz, sl2, cn);
@@ -1411,12 +1441,13 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
             RTW_SUB_STAMP(2);
             // e. start the next closest-hit query
             if (shading && (fl & F_HAVE)) {
-                trav_begin<MOVING, stack_t, F32>(A, pt, tr, lds_addr(lds_raw) + A.lds_stack_off + threadIdx.x * (uint32_t)sizeof(stack_t), a_plain, a_odd, cn);
+                trav_begin<MOVING, stack_t, F32, true>(A, pt, tr, lds_addr(lds_raw) + A.lds_stack_off + threadIdx.x * (uint32_t)sizeof(stack_t), a_plain, a_odd, cn);
                 fl |= F_INFLIGHT;
             }
             RTW_SUB_STAMP(3);
             } else {
             // ---- generic build (every integrator / sampler / dialect, quads and instances) ----
+            w_seg += (uint32_t)__popcll(ballot64(shading && (fl & F_INFLIGHT) != 0u));
             if (shading) {
                 RTW_CEN(cn, CEN_SHADING);
                 if (fl & F_INFLIGHT) {
@@ -1472,11 +1503,14 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
                 }
             }
             RTW_SUB_STAMP(3);
-            }
             w_rays += (uint32_t)__popcll(ballot64(started));
+            }
             // Wave-uniform and STICKY: lanes of this wave still test leaves of queries begun in earlier SHADE steps, so once any lane's d.d
-            // has left [2^-20, 2^20] the wave stays on the generic sqrt / division (same bits, a few more instructions) for good.
-            if (ballot64(a_odd) != 0ull) a_plain = false;
+            // has left [2^-20, 2^20] the wave stays on the generic sqrt / division (same bits, a few more instructions) for good.  The two-halves
+            // builds ask every lane's tr.a here, where the wave is whole (the lanes that did not begin a query in this step were asked when
+            // they did): one compare; a ballot of the bool that comes out of the join is a v_cndmask / v_cmp pair on top.
+            if constexpr (two_halves_step(SPEC, GEOM, MOVING)) { if (ballot64(a_outside_plain(tr.a)) != 0ull) a_plain = false; }
+            else if (ballot64(a_odd) != 0ull) a_plain = false;
 #ifndef RTW_STAMP
             nT = lanes_in(in_trav<stack_t>(tr.node)); burst = nT >= SC.chain;      // (as after a LEAF step)
 #endif
