@@ -112,6 +112,9 @@ struct Reserve {                             // wave-uniform
     uint32_t i0, k0;                         // the block's tile: first column, first compact row
     uint32_t s0, s1;                         // the block's chunk: samples [s0, s1)
     uint32_t slot0;                          // the block's place in the sample bank: slot of (its tile, its first sample, pixel 0)
+    // PER LANE, the unit table (fetch_pixel<true> only; every other build drops the two members): lane l holds pixel l of the block's tile,
+    uint32_t t_ij;                           // column | image row << 16 -- Pixel.ij --, 0xFFFFFFFF for a padding pixel (width, height < 2^16: no valid column is 0xFFFF)
+    uint32_t t_base;                         // rng_pixel_base of that pixel -- Pixel.rng_base
 #ifdef RTW_ENDTIMES
     unsigned long long t_dry;                // diagnostic build: device-wide time at which this wave first found the queue empty (0: not yet)
 #endif
@@ -123,6 +126,14 @@ struct Reserve {                             // wave-uniform
 // simply ask again on the next trip.
 // Sub-queue `sub` holds the tiles at queue positions sub, sub + S, .. (S = 2^sub_shift); its blocks are numbered tile by tile, a tile's units in
 // sample order.  With the three regions of unit length: t1 / t2 = its tiles in region 1 / regions 1 + 2, b1 / b2 = the blocks before region 2 / 3.
+//
+// TABLE: the form of the 768-thread render_bvh builds.  Everything the per-lane tail computes but `rank` -- column, row, the padding test, the row
+// map of a partition, the hash of (seed, pixel) -- depends on the tile and on the pixel's place in it alone, and the lanes of a wave drift apart
+// within a unit or two: "needs a unit" runs in 0.71 of all SHADE steps for 1.8 lanes (profiles/r03_census_final.txt), about 35 times per 64-unit
+// block, and for a VALU-bound wave an instruction costs its slot at one live lane as at 64.  So the block decode, which runs once per block with the
+// wave whole, has every lane l compute the entry of pixel l into two registers (Reserve.t_ij, t_base), and a lane that takes unit p pulls entry p
+// from lane p with two ds_bpermute.  The pulls stand where the wave is whole, ahead of the lane region: ds_bpermute reads only from lanes that
+// are enabled, and the lane that holds entry p is hardly ever one that asks.  Which lane gets which unit is the same in both forms.
 struct SubQ { uint32_t t1, t2, b1, b2, total; };
 __device__ __forceinline__ SubQ subq_layout(const KArgs &A, uint32_t sub) {
     const uint32_t up = (1u << A.sub_shift) - 1u - sub;            // (x + up) >> sub_shift = the queue positions below x that belong to this sub-queue
@@ -134,6 +145,16 @@ __device__ __forceinline__ SubQ subq_layout(const KArgs &A, uint32_t sub) {
     return q;
 }
 
+// compact row k of this partition -> image row (RtwParams row partition); k0 = the first compact row of k's tile, r = k - k0
+__device__ __forceinline__ uint32_t image_row(const KArgs &A, uint32_t k0, uint32_t r) {
+    const uint32_t k = k0 + r;
+    if (A.part_count <= 1u) return k;
+    // tiles are 8 rows tall and start on a multiple of 8, so with the usual 8-row blocks the block index is uniform too
+    if (A.row_block == 8u) return ((k0 >> 3) * A.part_count + A.part_index) * 8u + r;
+    return ((k / A.row_block) * A.part_count + A.part_index) * A.row_block + (k % A.row_block);
+}
+
+template <bool TABLE = false>
 __device__ __forceinline__ bool fetch_pixel(const KArgs &A, bool need, Pixel &px, bool &exhausted, Reserve &rs) {
     const unsigned long long m = ballot64(need);
     if (m == 0ull) return false;
@@ -201,6 +222,19 @@ __device__ __forceinline__ bool fetch_pixel(const KArgs &A, bool need, Pixel &px
             rs.s1 = rs.s0 + len < A.n_samples ? rs.s0 + len : A.n_samples;
             // [tile][sample][pixel] -- or, one partial sum per unit (RTW_FLAG_CHUNK_SUMS: a single region), [tile][chunk][pixel]
             rs.slot0 = (A.bank_len ? tile * A.n_chunks + chunk : tile * A.n_samples + rs.s0) * 64u;
+            if constexpr (TABLE) {
+                // the table of this block's tile: the arithmetic of the other form's tail, by 64 of 64 lanes once per block.  (Rebuilt for every
+                // block, also when the tile is the previous block's: a compare of two tiles and a uniform branch around ~20 instructions per 64 units.)
+                // (the lane's number is formed here each time, from a zero the optimiser cannot see through: as a loop invariant it is hoisted
+                //  and holds a register through every step of the persistent loop)
+                uint32_t zero = 0u;
+                asm volatile("" : "+v"(zero));
+                const uint32_t l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+                const uint32_t i = rs.i0 + (l & 7u);
+                const uint32_t j = image_row(A, rs.k0, l >> 3);
+                rs.t_ij = i < A.width && rs.k0 + (l >> 3) < A.k_end ? i | (j << 16) : 0xFFFFFFFFu;
+                rs.t_base = rng_pixel_base(A.seed_lo, A.seed_hi, j * A.width + i);
+            }
         }
     }
     const uint32_t avail = rs.end - rs.next;
@@ -208,6 +242,21 @@ __device__ __forceinline__ bool fetch_pixel(const KArgs &A, bool need, Pixel &px
     const uint32_t w = rs.next + rank;
     const uint32_t cnt = (uint32_t)__popcll(m);
     rs.next += cnt < avail ? cnt : avail;
+    if constexpr (TABLE) {
+        // (every lane pulls, the ones that do not ask too, and drops what it got: inside the lane region the source lanes would be off and the pull 0)
+        const uint32_t p = w & 63u;                                // pixel of the tile
+        const uint32_t e_ij = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(p << 2), (int)rs.t_ij);
+        const uint32_t e_base = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(p << 2), (int)rs.t_base);
+        exhausted = need && avail == 0u;                           // the queue is empty
+        // a lane past the reserve's end is refilled on the next trip; a padding item asks again then, too
+        // (`&` of the three: one lane region; with `&&` the asking lanes and the served ones are a region each)
+        if (!(need & (rank < avail) & (e_ij != 0xFFFFFFFFu))) return false;
+        px.ij = e_ij;
+        px.rng_base = e_base;
+        px.s = rs.s0 | ((rs.s1 - rs.s0) << 24);
+        px.slot = rs.slot0 + p;
+        return rs.s0 < rs.s1;
+    }
     if (!need) return false;
     if (avail == 0u) { exhausted = true; return false; }          // the queue is empty
     if (rank >= avail) return false;                              // reserve ran out: next trip refills
@@ -776,6 +825,7 @@ __global__ __launch_bounds__(RTW_BLOCK, GEOM ? RTW_GEOM_BRUTE_WAVES : 1) void re
     bool dead = false, have = false, newpath = false;
     Pixel px; px.ij = px.rng_base = px.s = px.slot = 0;
     Reserve rs; rs.next = rs.end = rs.limit = rs.i0 = rs.k0 = rs.s0 = rs.s1 = rs.slot0 = rs.tries = 0; rs.sub = blockIdx.x & ((1u << A.sub_shift) - 1u);
+    rs.t_ij = 0xFFFFFFFFu; rs.t_base = 0u;
 #ifdef RTW_ENDTIMES
     rs.t_dry = 0ull;
 #endif
@@ -1253,7 +1303,7 @@ constexpr bool two_halves_step(int spec, bool geom, bool moving) {
     return gradient_spec(spec) && !geom && !(moving && spec == 2);
 #endif
 }
-// Threads per workgroup of a render_bvh build.  The static LDS-node builds compiled for seven waves per SIMD run as 12-wave workgroups, two
+// Threads per workgroup of a render_bvh build.  The static LDS-node builds with the two-halves step run as 12-wave workgroups, two
 // to a CU, so that one copy of the nodes serves 12 waves and the tree fits LDS in the f32 plane format (rtw_host.h), the only one these
 // builds walk.  That is 6 waves per SIMD, not 7: two workgroups of 14 waves never shared a CU when measured, and a seventh wave is worth
 // 2.4 % where the f32 planes are worth 7.6 % (profiles/f32_planes_ab.log).  As a run-time choice next to the f16 walk the format kept
@@ -1263,8 +1313,24 @@ constexpr bool two_halves_step(int spec, bool geom, bool moving) {
 constexpr uint32_t bvh_block(bool moving, int nodes, int spec, bool geom) {
     return !moving && !geom && nodes == 1 && two_halves_step(spec, geom, moving) ? RTW_BLOCK_LARGE : RTW_BLOCK;
 }
+// The large-workgroup builds never hold more than two workgroups' waves on a CU's four SIMDs -- six each -- so they are compiled for six:
+// 80 VGPRs, which costs them no wave.  Alone that budget was measured as level (profiles/large_block_budget_ab.log); it is taken now because
+// two of the eight registers hold the unit table of fetch_pixel<true>, which these builds use (profiles/unit_table_ab.log), and the rest
+// ends their scratch.
+#ifndef RTW_BVH_WAVES_LARGE
+#define RTW_BVH_WAVES_LARGE 6
+#endif
+constexpr bool unit_table(bool moving, int nodes, int spec, bool geom) {
+#if defined(RTW_NO_UNIT_TABLE)
+    return false;
+#elif defined(RTW_UNIT_TABLE_ALL)
+    return two_halves_step(spec, geom, moving);      // A/B: the 256-thread two-halves builds too (72 VGPRs; profiles/unit_table_ab.log section 4)
+#else
+    return bvh_block(moving, nodes, spec, geom) == RTW_BLOCK_LARGE;
+#endif
+}
 template <bool MOVING, int NODES, int SPEC, bool GEOM>
-__global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WAVES_GEOM_SPEC : RTW_BVH_WAVES_GEOM) : (two_halves_step(SPEC, GEOM, MOVING) ? (SPEC == 2 ? RTW_BVH_WAVES_SPEC2 : RTW_BVH_WAVES_SPEC) : (gradient_spec(SPEC) ? RTW_BVH_WAVES_SPEC2 : (!generic_spec(SPEC) ? RTW_BVH_WAVES_FOLDED : RTW_BVH_WAVES)))) void render_bvh(const KArgs A) {
+__global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), bvh_block(MOVING, NODES, SPEC, GEOM) == RTW_BLOCK_LARGE ? RTW_BVH_WAVES_LARGE : GEOM ? (!generic_spec(SPEC) ? RTW_BVH_WAVES_GEOM_SPEC : RTW_BVH_WAVES_GEOM) : (two_halves_step(SPEC, GEOM, MOVING) ? (SPEC == 2 ? RTW_BVH_WAVES_SPEC2 : RTW_BVH_WAVES_SPEC) : (gradient_spec(SPEC) ? RTW_BVH_WAVES_SPEC2 : (!generic_spec(SPEC) ? RTW_BVH_WAVES_FOLDED : RTW_BVH_WAVES)))) void render_bvh(const KArgs A) {
     constexpr bool LDSN = NODES != 0, geom_in_lds = NODES == 2;
     constexpr uint32_t BLOCK = bvh_block(MOVING, NODES, SPEC, GEOM);
     constexpr bool F32 = BLOCK != RTW_BLOCK;         // the large-workgroup builds walk the f32 plane format, and that alone
@@ -1303,6 +1369,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
     uint32_t fl = 0u;
     Pixel px; px.ij = px.rng_base = px.s = px.slot = 0;
     Reserve rs; rs.next = rs.end = rs.limit = rs.i0 = rs.k0 = rs.s0 = rs.s1 = rs.slot0 = rs.tries = 0; rs.sub = blockIdx.x & ((1u << A.sub_shift) - 1u);
+    rs.t_ij = 0xFFFFFFFFu; rs.t_base = 0u;
 #ifdef RTW_ENDTIMES
     rs.t_dry = 0ull;
 #endif
@@ -1419,7 +1486,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), GEOM ? (!gene
             need_unit = (fl & F_HAVE) == 0u;
             if (need_unit && shading) RTW_CEN(cn, CEN_NEED_UNIT);
             bool exhausted = false;
-            const bool got = fetch_pixel(A, need_unit, px, exhausted, rs);
+            const bool got = fetch_pixel<unit_table(MOVING, NODES, SPEC, GEOM)>(A, need_unit, px, exhausted, rs);
             if (ballot64(exhausted) != 0ull) t_lo = SC.t_lo_drain;
             RTW_SUB_STAMP(1);
             if (got) fl |= F_HAVE | F_NEWPATH;
