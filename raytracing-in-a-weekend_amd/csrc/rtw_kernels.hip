@@ -937,12 +937,28 @@ __device__ __forceinline__ void exact_sphere(f4 g, f4 vv, uint32_t s, v3 o, v3 d
 #define RTW_CHAIN_LARGE 13u     /* 37 / 33 / 29 / 25 / 21 / 17 / 13 = 67.60 / 67.36 / 67.15 / 66.85 / 66.68 / 66.43 / 66.33 ms: bursts follow one another while 13 lanes
                                    still traverse, so LEAF waits for fuller steps (0.52 -> 0.58 of its lanes live, 10 % fewer of them) and a wave asks the scheduler less often; TRAVERSE
                                    takes 4 % more steps, each without the scheduler's three ballots and the copies at its joins.  13 is the lowest threshold at which
-                                   SHADE cannot be due meanwhile (64 - 13 < S_HI) */
+                                   SHADE cannot be due meanwhile (64 - 13 < S_HI).  That was with the leaf tests OUTSIDE the chain: lanes waited at their leaf until
+                                   fewer than 13 traversed.  With the leaf step inside it (RTW_LEAF_RULE_LARGE below; profiles/leaf_in_chain_ab.log) chain
+                                   9 (S_HI 56) / 13 / 17 = 61.96 / 61.93 / 62.01 ms, and S_HI 48 (chain 17) / 52 / 56 = 62.21 / 61.93 / 62.16, T_LO 6 / 8 = 61.93 / 61.93:
+                                   52 / 8 / 3 / 13 stay */
 #endif
-struct Sched { uint32_t s_hi, t_lo, t_lo_drain; int burst; uint32_t chain; };
+// When the leaf tests of lanes that wait at a leaf run INSIDE the chain of bursts (render_bvh): never (the leaf step runs only where the
+// scheduler says LEAF), when more lanes wait at a leaf than traverse, or -- any other value k -- when at least k lanes wait at a leaf.
+#define RTW_LEAF_RULE_OFF 0u
+#define RTW_LEAF_RULE_MORE 1u
+#ifndef RTW_LEAF_RULE_LARGE
+#define RTW_LEAF_RULE_LARGE RTW_LEAF_RULE_MORE /* off / nL > live / nL >= 12 / 16 / 24 = 64.05 / 61.93 / 62.48 / 62.60 / 62.95 ms of the bench frame (profiles/leaf_in_chain_ab.log;
+                                                  the replay of scripts/sim/wave_sim.cpp `chain` orders them the same way, profiles/leaf_in_chain_sim.log): 2.7 scheduler
+                                                  trips per SHADE step become 1.2, TRAVERSE takes 6 % fewer steps at 0.63 instead of 0.59 of its lanes live, LEAF 28 % more
+                                                  at 0.45 instead of 0.58 */
+#endif
+#ifndef RTW_LEAF_RULE
+#define RTW_LEAF_RULE RTW_LEAF_RULE_OFF        /* with chain 33, "more at a leaf than traverse" can never hold inside the chain */
+#endif
+struct Sched { uint32_t s_hi, t_lo, t_lo_drain; int burst; uint32_t chain, leaf_rule; };
 constexpr Sched sched_of(uint32_t block) {
-    return block == RTW_BLOCK_LARGE ? Sched{ RTW_S_HI_LARGE, RTW_T_LO_LARGE, RTW_T_LO_LARGE, RTW_TRAV_UNROLL_LARGE, RTW_CHAIN_LARGE }
-                                    : Sched{ RTW_S_HI, RTW_T_LO, RTW_T_LO_DRAIN, RTW_TRAV_UNROLL, RTW_CHAIN };
+    return block == RTW_BLOCK_LARGE ? Sched{ RTW_S_HI_LARGE, RTW_T_LO_LARGE, RTW_T_LO_LARGE, RTW_TRAV_UNROLL_LARGE, RTW_CHAIN_LARGE, RTW_LEAF_RULE_LARGE }
+                                    : Sched{ RTW_S_HI, RTW_T_LO, RTW_T_LO_DRAIN, RTW_TRAV_UNROLL, RTW_CHAIN, RTW_LEAF_RULE };
 }
 
 struct Trav {                // traversal state of one lane
@@ -1433,6 +1449,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), bvh_block(MOV
         const int which = run_shade ? 2 : (run_leaf ? 1 : 0);
 #endif
         bool burst = false;
+        bool leaf_due = false; uint32_t nLd = 0;            // (SC.leaf_rule: a leaf step is due in the walk loop, for nLd lanes)
         if (run_shade) {
             c_steps[2]++; c_lanes[2] += nS;
             // a. the closest-hit query this lane was waiting on is complete: scatter, or end the path
@@ -1581,6 +1598,9 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), bvh_block(MOV
 #ifndef RTW_STAMP
             nT = lanes_in(in_trav<stack_t>(tr.node)); burst = nT >= SC.chain;      // (as after a LEAF step)
 #endif
+        } else if constexpr (SC.leaf_rule != RTW_LEAF_RULE_OFF) {
+            // (the builds that test leaves inside the chain: the walk loop below holds their one leaf block, and LEAF enters it with "leaf due")
+            burst = true; leaf_due = run_leaf; nLd = nL;
         } else {
             burst = !run_leaf;
             if (run_leaf) {
@@ -1612,6 +1632,7 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), bvh_block(MOV
             static_assert(SC.s_hi > 64u - SC.chain && SC.t_lo <= SC.chain, "the shortcut below assumes the thresholds of the scheduler");
             uint32_t live = nT;
             for (;;) {
+                if constexpr (SC.leaf_rule == RTW_LEAF_RULE_OFF) {
                 // (the burst's census is summed in two scalars of its own and added once: kept in c_steps / c_lanes directly, the register
                 // allocator -- out of SGPRs in this kernel -- holds the totals in VGPRs and every visit paid a v_add for each)
                 uint32_t b_steps = 0, b_lanes = 0;
@@ -1635,6 +1656,53 @@ __global__ __launch_bounds__(bvh_block(MOVING, NODES, SPEC, GEOM), bvh_block(MOV
                 if (live < SC.chain) break;
                 if (++trips > RTW_MAX_TRIPS) break;          // (the outer loop's valve fires on its next trip)
 #endif
+                } else {
+                    // The builds that test leaves INSIDE the chain (SC.leaf_rule; the 768-thread builds): one walk loop of a burst and, when it is
+                    // due, a leaf step.  After a burst one more ballot counts the lanes at a leaf, and when the rule holds they are tested and popped
+                    // here, without the trip through the scheduler that the end of the chain would cost -- lanes no longer wait at their leaf until
+                    // fewer than SC.chain lanes traverse.  The scheduler's LEAF enters with the leaf step due, so the leaf block exists once and
+                    // the scheduler's branch is SHADE / walk.  SHADE cannot be due meanwhile (the assertion above), so the chain needs no ballot
+                    // for it.  Every iteration advances a lane: a burst runs with live > 0 (the scheduler says TRAVERSE only with nT >= nL and
+                    // not all three counts zero, and the chain goes on only with live >= SC.chain), a leaf step only with nLd > 0.
+                    if (!leaf_due) {
+                        uint32_t b_steps = 0, b_lanes = 0;       // (in two scalars of their own: see above)
+                        for (int u = 0; u < SC.burst; u++) {
+                            b_steps++; b_lanes += live;
+                            if (in_trav<stack_t>(tr.node)) {
+                                if constexpr (F32) trav_node_lds32<BLOCK>(tr);
+                                else if (LDSN) trav_node_lds((const u4 *)lnodes, tr); else trav_node(A.bvh, tr);
+                            }
+                            if (u + 1 >= SC.burst) break;
+                            live = lanes_in(in_trav<stack_t>(tr.node));
+                            if (live == 0u) break;
+                        }
+                        asm volatile("" : "+s"(b_steps), "+s"(b_lanes));
+                        c_steps[0] += b_steps; c_lanes[0] += b_lanes;
+#ifndef RTW_STAMP
+                        if (live != 0u) live = lanes_in(in_trav<stack_t>(tr.node));
+                        nLd = lanes_in(in_leaf<stack_t>(tr.node));
+                        leaf_due = SC.leaf_rule == RTW_LEAF_RULE_MORE ? nLd > live : nLd >= SC.leaf_rule;
+#endif
+                    }
+                    if (leaf_due) {
+                        leaf_due = false;
+                        c_steps[1]++; c_lanes[1] += nLd;
+                        if (in_leaf<stack_t>(tr.node)) {
+                            const uint32_t s = leaf_sphere<stack_t>(tr.node);
+                            const f4 gs = geom_in_lds ? lgeom[s] : sc.geom[s];
+                            exact_sphere<MOVING>(gs, MOVING ? sc.vel[s] : f4{ 0, 0, 0, 0 }, s, pt.o, pt.d, pt.tm, tr.a, tr.ra, a_plain, A.mint, A.maxt, tr.best, tr.best_t);
+                            tr.hi_lim = tr.best_t + tr.tau_t;
+                            trav_pop<stack_t, BLOCK>(tr);
+                        }
+                        live = lanes_in(in_trav<stack_t>(tr.node));
+                    }
+#ifdef RTW_STAMP
+                    break;                                   // (diagnostic build: every burst and every leaf step is timed as a trip of the outer loop)
+#else
+                    if (live < SC.chain) break;
+                    if (++trips > RTW_MAX_TRIPS) break;      // (the outer loop's valve fires on its next trip)
+#endif
+                }
             }
         }
 #ifdef RTW_STAMP

@@ -8,6 +8,9 @@
 //
 //   build:  /opt/rocm/lib/llvm/bin/clang++ -O2 -std=c++17 -I../../include -I../../raytracing-in-a-weekend_amd/csrc
 //           wave_sim.cpp ../../raytracing-in-a-weekend_amd/csrc/rtw_host.cpp -o wave_sim
+//   modes:  wave_sim [TILES [CHUNKS_PER_TILE [split | pool | leaf | grid1 | chain]]]  (SIM_CHUNK: samples per unit, default 4);  wave_sim visits ...
+//           `chain` replays the scheduler of the 768-thread builds (chain of bursts, their constants, a cost per scheduler trip) and the
+//           leaf-in-chain family: SIM_CHUNK=12 ./wave_sim 60 3 chain  ->  profiles/leaf_in_chain_sim.log
 #include "rtw_host.h"
 #include <algorithm>
 #include <cmath>
@@ -297,6 +300,83 @@ static Result simulate(const std::vector<std::vector<std::vector<PathTrace>>> &b
 }
 
 
+// ---- `chain`: the scheduler of render_bvh as the 768-thread builds run it (rtw_kernels.hip): a SHADE or LEAF step goes straight on to the
+// bursts when `chain` lanes traverse, bursts follow one another while they do, and -- the candidate family -- the lanes that wait at a leaf
+// are tested inside that chain when the rule holds (0 never, 1 more of them than lanes that traverse, k at least k of them).  Costs are
+// fast-VALU equivalents per wave-step; `trip` is one pass through the scheduler's three ballots and its three-way branch.
+struct ChainPolicy { unsigned s_hi = 52, t_lo = 8, burst = 3, chain = 13, leaf_rule = 0; };
+struct ChainCosts { double visit = 36, leaf = 60, shade = 560, trip = 27; };
+struct ChainResult : Result { unsigned long long trips = 0; };
+static ChainResult simulate_chain(const std::vector<std::vector<std::vector<PathTrace>>> &blocks, const ChainPolicy &P, const ChainCosts &C) {
+    ChainResult R;
+    size_t next_block = 0, next_in_block = 0;
+    struct Unit { const std::vector<PathTrace> *paths = nullptr; size_t next = 0; };
+    auto fetch = [&](Unit &u) -> bool {
+        if (next_block >= blocks.size()) return false;
+        u.paths = &blocks[next_block][next_in_block]; u.next = 0;
+        if (++next_in_block == 64) { next_in_block = 0; next_block++; }
+        return true;
+    };
+    // lane state: 0 in a query (TRAVERSE or LEAF by its next op), 2 waits for SHADE, 3 DEAD
+    struct L { int st = 2; Unit unit; const PathTrace *p = nullptr; size_t seg = 0, pos = 0; bool have = false; };
+    std::vector<L> lane(64);
+    auto op = [&](int l) { return lane[l].p->seg[lane[l].seg][lane[l].pos]; };
+    auto in_trav = [&](int l) { return lane[l].st == 0 && op(l) == 'N'; };
+    auto in_leaf = [&](int l) { return lane[l].st == 0 && op(l) == 'L'; };
+    auto count = [&](auto pred) { unsigned n = 0; for (int l = 0; l < 64; l++) n += pred(l) ? 1u : 0u; return n; };
+    auto advance = [&](int l) { if (++lane[l].pos >= lane[l].p->seg[lane[l].seg].size()) lane[l].st = 2; };
+    auto leaf_step = [&](unsigned nL) {
+        R.steps[1]++; R.lanes[1] += nL; R.cyc += C.leaf;
+        for (int l = 0; l < 64; l++) if (in_leaf(l)) advance(l);
+    };
+    for (;;) {
+        unsigned nT = count(in_trav), nL = count(in_leaf), nS = count([&](int l) { return lane[l].st == 2; });
+        if (!(nT | nL | nS)) break;
+        R.trips++; R.cyc += C.trip;
+        const bool run_shade = nS >= P.s_hi || (nT < P.t_lo && nL < P.t_lo && nS > 0);
+        bool burst;
+        if (run_shade) {
+            R.steps[2]++; R.lanes[2] += nS; R.cyc += C.shade;
+            for (int l = 0; l < 64; l++) if (lane[l].st == 2) {
+                L &a = lane[l];
+                bool new_path = !a.have;
+                if (a.have) { R.segments++; if (++a.seg >= a.p->seg.size()) new_path = true; }
+                if (new_path) {
+                    if (!a.have || a.unit.next >= a.unit.paths->size()) { if (!fetch(a.unit)) { a.st = 3; a.have = false; continue; } }
+                    a.p = &(*a.unit.paths)[a.unit.next++]; a.seg = 0; a.have = true;
+                }
+                a.pos = 0; a.st = a.p->seg[a.seg].empty() ? 2 : 0;
+            }
+            nT = count(in_trav); burst = nT >= P.chain;
+        } else if (nL > nT) {
+            leaf_step(nL);
+            nT = count(in_trav); burst = nT >= P.chain;
+        } else burst = true;
+        if (!burst) continue;
+        unsigned live = nT;
+        for (;;) {
+            for (unsigned u = 0; u < P.burst; u++) {
+                R.steps[0]++; R.lanes[0] += live; R.cyc += C.visit;
+                for (int l = 0; l < 64; l++) { if (lane[l].st == 3) R.idleT[2]++; else if (lane[l].st == 2) R.idleT[1]++; else if (in_leaf(l)) R.idleT[0]++; }
+                for (int l = 0; l < 64; l++) if (in_trav(l)) advance(l);
+                if (u + 1 >= P.burst) break;
+                live = count(in_trav);
+                if (live == 0) break;
+            }
+            if (P.leaf_rule == 0) {
+                if (live == 0) break;
+                live = count(in_trav);
+            } else {
+                if (live != 0) live = count(in_trav);
+                const unsigned nLc = count(in_leaf);
+                if (P.leaf_rule == 1 ? nLc > live : nLc >= P.leaf_rule) { leaf_step(nLc); live = count(in_trav); }
+            }
+            if (live < P.chain) break;
+        }
+    }
+    return R;
+}
+
 // ---- idealised intra-wave pool: K paths per wave live in a pool; a lane whose query is done drops the result into the pool and takes ANY
 // ready ray (step X, cost C.X); SHADE takes up to 64 finished paths from the pool (and refills empty pool slots with new paths).
 static Result simulate_pool(const std::vector<std::vector<std::vector<PathTrace>>> &blocks, unsigned K, unsigned s_hi, unsigned x_hi, unsigned t_lo, unsigned burst, const Costs &C) {
@@ -531,7 +611,7 @@ int main(int argc, char **argv) {
     }
     RtwCamera cam; RtwParams p;
     rtw_scene_default_view(RTW_SCENE_C5_MOTION_CHECKER, &cam, &p);
-    const uint32_t chunk = 4, n_tiles = argc > 1 ? atoi(argv[1]) : 40, chunks_per_tile = argc > 2 ? atoi(argv[2]) : 6;
+    const uint32_t chunk = getenv("SIM_CHUNK") ? (uint32_t)atoi(getenv("SIM_CHUNK")) : 4, n_tiles = argc > 1 ? atoi(argv[1]) : 40, chunks_per_tile = argc > 2 ? atoi(argv[2]) : 6;
     // blocks = (tile, chunk): 64 pixels x `chunk` paths, consecutive chunks of a tile are consecutive in the queue
     std::vector<std::vector<std::vector<PathTrace>>> blocks;
     std::mt19937 pick(7);
@@ -563,6 +643,53 @@ int main(int argc, char **argv) {
         if (R.idleT[0] + R.idleT[1] + R.idleT[2]) printf("    during T steps: %.3f of the lanes sit in LEAF, %.3f wait for SHADE, %.3f are dead\n",
             R.idleT[0] / (64.0 * R.steps[0]), R.idleT[1] / (64.0 * R.steps[0]), R.idleT[2] / (64.0 * R.steps[0]));
     };
+    if (argc > 3 && !strcmp(argv[3], "chain")) {
+        // the 768-thread builds' scheduler and the leaf-in-chain family (profiles/leaf_in_chain_sim.log):  SIM_CHUNK=12 ./wave_sim 60 3 chain
+        auto run = [&](const char *name, const ChainPolicy &P, const ChainCosts &K, double base) {
+            const ChainResult R = simulate_chain(blocks, P, K);
+            auto eff = [&](int k) { return R.steps[k] ? R.lanes[k] / (64.0 * R.steps[k]) : 0.0; };
+            const double cost = R.cyc / R.segments, sg = (double)R.segments;
+            printf("%-34s cost/seg %6.2f", name, cost);
+            if (base > 0) printf(" (%+5.1f %%)", 100 * (cost / base - 1)); else printf("          ");
+            printf(" | trips/SHADE %.2f | T %.3f live, %.4f steps/seg (at a leaf %.3f, wait for SHADE %.3f) | L %.3f, %.4f | S %.3f, %.5f\n",
+                   (double)R.trips / R.steps[2], eff(0), R.steps[0] / sg, R.idleT[0] / (64.0 * R.steps[0]), R.idleT[1] / (64.0 * R.steps[0]),
+                   eff(1), R.steps[1] / sg, eff(2), R.steps[2] / sg);
+            return cost;
+        };
+        ChainCosts K;
+        printf("-- the trip cost, fitted: chain 33 -> 13 measured -1.5 %% on the GPU (profiles/visit_class_sched_sweep.log)\n");
+        for (double trip : { 0.0, 9.0, 18.0, 27.0, 36.0, 45.0 }) {
+            ChainCosts k = K; k.trip = trip;
+            ChainPolicy a; a.chain = 33; ChainPolicy b;
+            char nm[64]; snprintf(nm, sizeof nm, "trip %2.0f: chain 33", trip);
+            const double base = run(nm, a, k, 0);
+            snprintf(nm, sizeof nm, "trip %2.0f: chain 13", trip);
+            run(nm, b, k, base);
+        }
+        struct Set { const char *name; ChainCosts k; };
+        ChainCosts leaf90 = K; leaf90.leaf = 90;
+        ChainCosts v40 = K; v40.visit = 40; v40.shade = 520;
+        for (const Set &s : { Set{ "visit 36, LEAF 60, SHADE 560, trip 27", K }, Set{ "LEAF 90", leaf90 }, Set{ "visit 40, SHADE 520", v40 } }) {
+            printf("-- the candidates, costs: %s\n", s.name);
+            ChainPolicy p;
+            const double base = run("shipped (rule off)", p, s.k, 0);
+            for (unsigned rule : { 1u, 12u, 16u, 24u, 32u }) {
+                p.leaf_rule = rule;
+                char nm[64];
+                if (rule == 1) snprintf(nm, sizeof nm, "leaf in chain: nL > live"); else snprintf(nm, sizeof nm, "leaf in chain: nL >= %u", rule);
+                run(nm, p, s.k, base);
+            }
+        }
+        printf("-- the other constants beside nL > live\n");
+        {
+            ChainPolicy p; const double base = run("shipped (rule off)", p, K, 0);
+            p.leaf_rule = 1;
+            for (unsigned ch : { 9u, 13u, 17u }) { ChainPolicy q = p; q.chain = ch; if (ch == 9) q.s_hi = 56; char nm[64]; snprintf(nm, sizeof nm, "chain %u%s", ch, ch == 9 ? " (s_hi 56)" : ""); run(nm, q, K, base); }
+            for (unsigned sh : { 48u, 56u }) { ChainPolicy q = p; q.s_hi = sh; if (sh == 48) q.chain = 17; char nm[64]; snprintf(nm, sizeof nm, "s_hi %u%s", sh, sh == 48 ? " (chain 17)" : ""); run(nm, q, K, base); }
+            { ChainPolicy q = p; q.t_lo = 6; run("t_lo 6", q, K, base); }
+        }
+        return 0;
+    }
     Policy base; report("1 path: s_hi 48 t_lo 6 (round 1)", base);
     if (argc > 3 && !strcmp(argv[3], "split")) {
         SplitCosts SC;
