@@ -72,6 +72,16 @@ pub struct RtwFilterStats { pub avg_gradient: f32, pub spatial: f32, pub gradien
 /// another object id weighs 0).
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct RtwGuidedFilter { pub base: RtwBilateral, pub sigma_depth: f32, pub sigma_normal: f32, pub same_object: u32 }
+/// Arguments of the a-trous filter (include/rtw.h): levels (1..8, level i steps by 2^i pixels), the three sigmas (0 = term off; level i uses
+/// sigma_color * 2^-i), same_object, and the floor below which an albedo channel is not demodulated.
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RtwAtrous { pub levels: u32, pub sigma_color: f32, pub sigma_depth: f32, pub sigma_normal: f32, pub same_object: u32, pub albedo_floor: f32 }
+pub const RTW_ATROUS_MAX_LEVELS: u32 = 8;
+/// `RTW_OPT_ATROUS_LAYOUT` (rtw.h): where a level of the a-trous filter reads its taps (0 the measured choice, 1 LDS tile, 2 global memory).
+pub const RTW_OPT_ATROUS_LAYOUT: u32 = 14;
+/// The ray rules of `rtw_ctx_surface_map` (rtw.h).
+pub const RTW_RAYS_DEPTH_MAP: u32 = 0;
+pub const RTW_RAYS_PIXEL: u32 = 1;
 /// Rust2 `ProximityType` (postprocessing.rs:12-15).
 #[repr(u32)] #[derive(Clone, Copy)]
 pub enum ProximityKind { Square = 0, Edges = 1 }
@@ -164,6 +174,10 @@ extern "C" {
                              p: *const RtwGuidedFilter, out: *mut u8, st: *mut RtwFilterStats) -> i32;
     fn rtw_ctx_guided_filter(ctx: *mut RtwCtx, img: *const c_void, w: u32, h: u32, depth: *const f32, normal: *const f32,
                                  idx: *const i32, p: *const RtwGuidedFilter, out: *mut u8, st: *mut RtwFilterStats) -> i32;
+    fn rtw_atrous_filter(img: *const f32, w: u32, h: u32, depth: *const f32, normal: *const f32, idx: *const i32, albedo: *const f32,
+                         emitted: *const f32, p: *const RtwAtrous, out: *mut f32, st: *mut RtwFilterStats) -> i32;
+    fn rtw_ctx_atrous_filter(ctx: *mut RtwCtx, img: *const f32, w: u32, h: u32, depth: *const f32, normal: *const f32, idx: *const i32,
+                             albedo: *const f32, emitted: *const f32, p: *const RtwAtrous, out: *mut f32, st: *mut RtwFilterStats) -> i32;
     fn rtw_triangle_new(origin: *const f32, u: *const f32, v: *const f32, mat3: *const f32, emitted: *const f32,
                         color: *const f32, tex: i32, out: *mut RtwTriangle) -> i32;
     fn rtw_ctx_set_triangles(ctx: *mut RtwCtx, tris: *const RtwTriangle, n: u32) -> i32;
@@ -208,6 +222,13 @@ extern "C" {
     fn rtw_depth_rays(cam: *const RtwCamera, width: u32, height: u32, rays_out: *mut f32) -> i32;
     fn rtw_ctx_scene_hits(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, time: f32, mint: f32, maxt: f32, accel: u32,
                           t_out: *mut f32, idx_out: *mut i32, normal_out: *mut f32, stats: *mut RtwStats) -> i32;
+    fn rtw_ctx_scene_surface(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, time: f32, mint: f32, maxt: f32, accel: u32, integrator: u32,
+                             t_out: *mut f32, idx_out: *mut i32, normal_out: *mut f32, albedo_out: *mut f32, emitted_out: *mut f32,
+                             material_out: *mut f32, stats: *mut RtwStats) -> i32;
+    fn rtw_pixel_rays(cam: *const RtwCamera, width: u32, height: u32, offset: *const f32, rays_out: *mut f32) -> i32;
+    fn rtw_ctx_surface_map(ctx: *mut RtwCtx, cam: *const RtwCamera, width: u32, height: u32, ray_rule: u32, offset: *const f32, time: f32,
+                           mint: f32, maxt: f32, accel: u32, integrator: u32, depth_out: *mut f32, idx_out: *mut i32, normal_out: *mut f32,
+                           albedo_out: *mut f32, emitted_out: *mut f32, material_out: *mut f32, stats: *mut RtwStats) -> i32;
     fn rtw_ctx_scene_occluded(ctx: *mut RtwCtx, rays: *const f32, n_rays: u32, time: f32, mint: f32, maxt: f32, accel: u32,
                               occluded_out: *mut u8, stats: *mut RtwStats) -> i32;
     fn rtw_ao_rays(points: *const f32, normals: *const f32, n: u32, samples: u32, seed: u32, rays_out: *mut f32) -> i32;
@@ -416,6 +437,40 @@ impl Renderer {
         check(unsafe { rtw_ctx_guided_filter(self.ctx, rgb, w, h, depth, normal, idx, p, out.as_mut_ptr(), &mut st) })?;
         Ok((out, st))
     }
+    /// The a-trous filter on this context's GPU (rtw_ctx_atrous_filter): a linear f32 frame [h][w][3], the guides of `guided_filter`, albedo
+    /// and emitted [h][w][3] f32; each host or device memory, null where its term is off or it is not given.
+    pub fn atrous_filter(&mut self, rgb: *const f32, w: u32, h: u32, depth: *const f32, normal: *const f32, idx: *const i32, albedo: *const f32,
+                         emitted: *const f32, p: &RtwAtrous) -> Result<(Vec<f32>, RtwFilterStats), RtwError> {
+        let mut out = vec![0f32; w as usize * h as usize * 3];
+        let mut st = RtwFilterStats::default();
+        check(unsafe { rtw_ctx_atrous_filter(self.ctx, rgb, w, h, depth, normal, idx, albedo, emitted, p, out.as_mut_ptr(), &mut st) })?;
+        Ok((out, st))
+    }
+    /// What a camera sees (rtw_ctx_surface_map): (depth, idx, normal, albedo, emitted, material) of every pixel's first surface under
+    /// `integrator`, rays by `ray_rule` (`RTW_RAYS_PIXEL` with `offset` inside the pixel for Viewport cameras).
+    #[allow(clippy::type_complexity)]
+    pub fn surface_map(&mut self, cam: &RtwCamera, width: u32, height: u32, ray_rule: u32, offset: [f32; 2], time: f32, mint: f32, maxt: f32,
+                       accel: u32, integrator: u32) -> Result<(Vec<f32>, Vec<i32>, Vec<f32>, Vec<f32>, Vec<f32>, Vec<f32>), RtwError> {
+        let n = width as usize * height as usize;
+        let (mut d, mut i) = (vec![0f32; n], vec![0i32; n]);
+        let (mut nr, mut al, mut em, mut mt) = (vec![0f32; 3 * n], vec![0f32; 3 * n], vec![0f32; 3 * n], vec![0f32; 3 * n]);
+        check(unsafe { rtw_ctx_surface_map(self.ctx, cam, width, height, ray_rule, offset.as_ptr(), time, mint, maxt, accel, integrator,
+                                           d.as_mut_ptr(), i.as_mut_ptr(), nr.as_mut_ptr(), al.as_mut_ptr(), em.as_mut_ptr(), mt.as_mut_ptr(),
+                                           std::ptr::null_mut()) })?;
+        Ok((d, i, nr, al, em, mt))
+    }
+    /// rtw_ctx_scene_surface: `scene_hits` with albedo, emitted and material of each ray's first surface ([n][6] rays).
+    #[allow(clippy::type_complexity)]
+    pub fn scene_surface(&mut self, rays: &[[f32; 6]], time: f32, mint: f32, maxt: f32, accel: u32, integrator: u32)
+                         -> Result<(Vec<f32>, Vec<i32>, Vec<f32>, Vec<f32>, Vec<f32>, Vec<f32>), RtwError> {
+        let n = rays.len();
+        let (mut t, mut i) = (vec![0f32; n], vec![0i32; n]);
+        let (mut nr, mut al, mut em, mut mt) = (vec![0f32; 3 * n], vec![0f32; 3 * n], vec![0f32; 3 * n], vec![0f32; 3 * n]);
+        check(unsafe { rtw_ctx_scene_surface(self.ctx, rays.as_ptr() as *const f32, n as u32, time, mint, maxt, accel, integrator, t.as_mut_ptr(),
+                                             i.as_mut_ptr(), nr.as_mut_ptr(), al.as_mut_ptr(), em.as_mut_ptr(), mt.as_mut_ptr(),
+                                             std::ptr::null_mut()) })?;
+        Ok((t, i, nr, al, em, mt))
+    }
     /// Tuning knobs (`RTW_OPT_*` of rtw.h: 1 chunk length, 2 sample bank GiB, 3 LDS geometry, 4 workgroups per CU, 5 list-walk
     /// threshold, 11 = `RTW_OPT_NODE_FORMAT`: the tree in LDS as 0 f32 planes where they fit, 1 f16 nodes, 2 f32 planes, 12 =
     /// `RTW_OPT_MESH_LIST_MAX`: at most this many mesh placements are met in list order, more through the top-level tree); none of them
@@ -538,6 +593,23 @@ pub fn guided_filter_host(rgb: &[u8], w: u32, h: u32, depth: &[f32], normal: &[f
                                      ptr(normal.len(), normal.as_ptr() as *const c_void) as *const f32,
                                      ptr(idx.len(), idx.as_ptr() as *const c_void) as *const i32, p, out.as_mut_ptr(), std::ptr::null_mut()) })?;
     Ok(out)
+}
+
+/// rtw_atrous_filter: the host form of the a-trous filter (a guide whose term is off, albedo and emitted may be empty).
+pub fn atrous_filter_host(rgb: &[f32], w: u32, h: u32, depth: &[f32], normal: &[f32], idx: &[i32], albedo: &[f32], emitted: &[f32],
+                          p: &RtwAtrous) -> Result<Vec<f32>, RtwError> {
+    let mut out = vec![0f32; rgb.len()];
+    let f = |s: &[f32]| if s.is_empty() { std::ptr::null() } else { s.as_ptr() };
+    let ids = if idx.is_empty() { std::ptr::null() } else { idx.as_ptr() };
+    check(unsafe { rtw_atrous_filter(rgb.as_ptr(), w, h, f(depth), f(normal), ids, f(albedo), f(emitted), p, out.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok(out)
+}
+
+/// rtw_pixel_rays: the pixel rays of a Viewport camera at `offset` inside the pixel, [h * w][6] = origin, direction (not normalised).
+pub fn pixel_rays(cam: &RtwCamera, width: u32, height: u32, offset: [f32; 2]) -> Result<Vec<[f32; 6]>, RtwError> {
+    let mut r = vec![[0f32; 6]; width as usize * height as usize];
+    check(unsafe { rtw_pixel_rays(cam, width, height, offset.as_ptr(), r.as_mut_ptr() as *mut f32) })?;
+    Ok(r)
 }
 
 /// Rust2 `bilateral_filter(img, proximity)` on GPU 0 for a [h][w][3] u8 image (`Img::as_raw()`), bit-identical to the reference.

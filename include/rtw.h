@@ -322,6 +322,9 @@ enum {
     RTW_OPT_MESH_CLIMB       = 13,/* how rtw_ctx_move_mesh_instances climbs the top-level tree: 0 (default) by the tree's node count, the
                                      measured choice; 1 one launch per height; 2 one launch of one workgroup.  The bytes are the
                                      same.  Any other value: RTW_E_INVALID.  (added within v4)                                              */
+    RTW_OPT_ATROUS_LAYOUT    = 14,/* where a level of rtw_ctx_atrous_filter reads its taps: 0 (default) the measured choice per level
+                                     (DESIGN.md 8c); 1 from an LDS tile of the workgroup's pixels and their halo wherever that tile fits; 2 from
+                                     global memory.  The bytes are the same.  Any other value: RTW_E_INVALID.  (added within v4)          */
 };
 int  rtw_ctx_set_option(rtw_ctx *ctx, uint32_t key, double value);
 /* Which compiled build of the render kernel the context's last render launched, as text in template-argument order:
@@ -501,6 +504,51 @@ int rtw_guided_filter(const void *in, uint32_t w, uint32_t h, const float *depth
 int rtw_ctx_guided_filter(rtw_ctx *ctx, const void *in, uint32_t w, uint32_t h, const float *depth, const float *normal,
                           const int32_t *idx, const RtwGuidedFilter *params, uint8_t *out, RtwFilterStats *stats);
 
+/* ---- a-trous filter: an edge-avoiding wavelet filter of linear f32 frames (Dammertz et al. 2010) -- added within v4 -------------------
+ * Multi-scale where the two filters above have one scale, on the linear frame where they work on its 8-bit quantisation, and steered by
+ * the same guide buffers (depth [h][w] f32, normal [h][w][3] f32, idx [h][w] i32: what rtw_ctx_depth_map / rtw_ctx_scene_hits write).  With
+ * `albedo` (and `emitted`) it filters (rgb - emitted) / albedo, so that texture is kept.  in, out, albedo, emitted are [h][w][3] f32,
+ * row-major.  Everything is f32 with one rounding per written operation (no fused multiply-add), exp_plain is rtw_exp_plain's:
+ *   demodulate:  a_c = (albedo && albedo[p][c] >= albedo_floor) ? albedo[p][c] : 1;  e_c = emitted ? emitted[p][c] : 0;
+ *                C0[p][c] = (in[p][c] - e_c) / a_c
+ *   level i = 0 .. levels-1, step s = 1 << i: the taps q = p + s * (dx, dy), dy = -2..2 outer, dx = -2..2 inner, those outside the frame
+ *   skipped;  hw = K[|dx|] * K[|dy|], K = {3/8, 1/4, 1/16};  a = 0
+ *     if sigma_color  > 0:  d = Ci[q] - Ci[p];                  a = a + inv_color_i * ((d.x*d.x + d.y*d.y) + d.z*d.z)
+ *     if sigma_depth  > 0:  dz = (depth[q] - depth[p]) * 2^-i;  a = a + inv_depth * (dz * dz)
+ *     if sigma_normal > 0:  d = normal[q] - normal[p];          a = a + inv_normal * ((d.x*d.x + d.y*d.y) + d.z*d.z)
+ *     g = (a >= 0) ? exp_plain(-a) : 0;   if same_object and idx[q] != idx[p]:  g = 0;   wt = hw * g
+ *     if wt > 0:  sum_c = sum_c + Ci[q][c] * wt;  wsum = wsum + wt
+ *   Ci+1[p] = wsum > 0 ? sum / wsum : Ci[p]
+ *   remodulate:  out[p][c] = C_levels[p][c] * a_c + e_c
+ * with inv_x = 0.5f / (sigma_x * sigma_x) and inv_color_i formed from sigma_color * 2^-i.  A tap of weight 0 adds nothing: for finite
+ * values that is the plain sum's bits, and with the colour term on it lets a NaN or infinite tap drop out (its a is NaN) while a NaN
+ * centre keeps its own value (every a is NaN, wsum stays 0).  A miss of rtw_ctx_depth_map is simply another depth, normal and object.
+ * `out` may be `in`.  A guide whose term is off, `albedo` and `emitted` may be NULL; an off guide is never read.
+ * RTW_E_INVALID, nothing written: in, out or params NULL; w or h zero or beyond RTW_ATROUS_MAX_SIDE, or w * h beyond 32 bits; levels
+ * outside 1 .. RTW_ATROUS_MAX_LEVELS; a sigma that is negative or not finite, or so small that its inv_* is not finite at some level;
+ * sigma_depth > 0 with depth NULL, sigma_normal > 0 with normal NULL, same_object with idx NULL; same_object > 1; with albedo given, an
+ * albedo_floor that is not finite or not > 0.  There is no rtw_mgpu_* form and no JSON form. */
+#define RTW_ATROUS_MAX_LEVELS 8u
+#define RTW_ATROUS_MAX_SIDE   0x7FFFFC00u   /* a pixel coordinate plus two steps of the last level stays a 32-bit integer */
+typedef struct RtwAtrous {
+    uint32_t levels;                /* 1 .. RTW_ATROUS_MAX_LEVELS; level i steps by 2^i pixels                        */
+    float    sigma_color;           /* 0 = no colour term; level i uses sigma_color * 2^-i                           */
+    float    sigma_depth;           /* 0 = no depth term; else in the units of `depth`                               */
+    float    sigma_normal;          /* 0 = no normal term; else in units of |n - n'|                                 */
+    uint32_t same_object;           /* 1 = a tap on another idx weighs 0                                             */
+    float    albedo_floor;          /* used when albedo != NULL: a channel below it is not demodulated               */
+} RtwAtrous;
+/* The host form (one thread).  RtwFilterStats: filter_ms and total_ms are the call's time, taps counts the taps inside the frame over all
+ * levels, the other fields are 0. */
+int rtw_atrous_filter(const float *in, uint32_t w, uint32_t h, const float *depth, const float *normal, const int32_t *idx,
+                      const float *albedo, const float *emitted, const RtwAtrous *params, float *out, RtwFilterStats *stats);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host form.  Every buffer may independently be host memory or device memory of
+ * ctx's GPU (host memory is staged).  One launch per level over two buffers the context owns (RTW_OPT_ATROUS_LAYOUT); filter_ms is the
+ * device time of all launches.  Needs no scene and leaves the scene, and every render, untouched. */
+int rtw_ctx_atrous_filter(rtw_ctx *ctx, const float *in, uint32_t w, uint32_t h, const float *depth, const float *normal,
+                          const int32_t *idx, const float *albedo, const float *emitted, const RtwAtrous *params, float *out,
+                          RtwFilterStats *stats);
+
 /* ---- Rust2 triangles (Rust2/src/objects/triangle.rs) ----------------------------------------------------------------------------
  * `Triangle{origin, u, v, mat, texture}` with the derived fields of Triangle::new (:28-50): n = u x v, normal = unit(n),
  * d = normal . origin, w = n / (n . n); the hit test of get_hit (:95-124) restated operation by operation in f32: reject when
@@ -588,6 +636,41 @@ int rtw_ctx_scene_hits(rtw_ctx *ctx, const float *rays, uint32_t n_rays, float t
  * ([height][width][3]) may be NULL; memory kinds, stats and statuses as rtw_ctx_scene_hits (width * height must fit 32 bits). */
 int rtw_ctx_depth_map(rtw_ctx *ctx, const RtwCamera *cam, uint32_t width, uint32_t height, float time, float mint, float maxt,
                       uint32_t accel, float *depth_out, int32_t *idx_out, float *normal_out, RtwStats *stats);
+
+/* ---- surface buffers: the render's hit record of the first surface -- added within v4 ---------------------------------------------------
+ * rtw_ctx_scene_hits with the rest of the winner's hit record: what the render's SHADE step reads of that hit under `integrator`, formed
+ * once per ray, after the walk, by the functions the render kernels call.  t_out, idx_out and normal_out are rtw_ctx_scene_hits' answers
+ * bit for bit -- ties, the tree-to-list equivalence under every fall-back, skipped constant-density instances, miss values.
+ *   albedo_out   [n][3]  the colour the path's throughput is multiplied by: a sphere's texel * col_mod, a quad's or triangle's texel (or
+ *                        their constant colours).  Under RTW_INTEGRATOR_RUST2, _LIGHT_CAST and _LIGHT_BIASED a textured sphere or triangle is
+ *                        looked up by Rust2's rule (transposed index, scaled by the size) and `emitted` comes from RtwTexture.emit_tex.
+ *   emitted_out  [n][3]  the emission of that hit (may be NULL)
+ *   material_out [n][3]  metallicness, opacity, ir as the scene holds them; RTW_FLAG_MIXED_MATERIAL is the caller's to interpret (may be NULL)
+ * An instance member, Euler or quaternion, is evaluated in the instance's frame, and a triangle of a placed mesh in the placement's.  A miss
+ * writes 0 0 0 to all three.  Memory kinds, stats and stream order as rtw_ctx_scene_hits.  RTW_E_INVALID: everything rtw_ctx_scene_hits
+ * refuses; albedo_out == NULL; an unknown integrator; NOT BUILT, also RTW_E_INVALID with nothing written: a context whose textures have
+ * noise (rtw_ctx_set_texture_noise).  There is no rtw_mgpu_* form and no JSON form. */
+int rtw_ctx_scene_surface(rtw_ctx *ctx, const float *rays, uint32_t n_rays, float time, float mint, float maxt, uint32_t accel,
+                          uint32_t integrator, float *t_out, int32_t *idx_out, float *normal_out /* may be NULL */,
+                          float *albedo_out /* [n][3] */, float *emitted_out /* [n][3], may be NULL */,
+                          float *material_out /* [n][3] = metallicness, opacity, ir; may be NULL */, RtwStats *stats);
+/* How rtw_ctx_surface_map makes the ray of pixel (i, j):
+ *   RTW_RAYS_DEPTH_MAP  rtw_depth_rays' rule (cameras of rtw_camera2_new); offset is not read
+ *   RTW_RAYS_PIXEL      for cameras of rtw_viewport_new: origin = cam.origin, direction = (pixel00 + delta_u * ((float)i + offset[0])) +
+ *                       delta_v * ((float)j + offset[1]), not normalised.  Offset 0 0 is RTW_SAMPLER_NO_RAND's ray exactly; 0.5 0.5 is the
+ *                       centre of the jittered samplers' pixel.  A NULL offset is 0 0. */
+enum { RTW_RAYS_DEPTH_MAP = 0, RTW_RAYS_PIXEL = 1 };
+/* Host only, pure: the rays of RTW_RAYS_PIXEL, f32 without FMA, row-major at rays_out[(j * width + i) * 6].  RTW_E_INVALID for a NULL cam
+ * or rays_out or a zero size. */
+int rtw_pixel_rays(const RtwCamera *cam, uint32_t width, uint32_t height, const float offset[2], float *rays_out /* [h*w][6] */);
+/* What a camera sees: rtw_ctx_scene_surface over the rays of `ray_rule`, built in the kernel.  depth_out is t, or maxt * 1.6f on a miss as
+ * rtw_ctx_depth_map writes it; with RTW_RAYS_DEPTH_MAP depth_out, idx_out and normal_out are rtw_ctx_depth_map's bytes; with RTW_RAYS_PIXEL
+ * everything equals rtw_ctx_scene_surface over rtw_pixel_rays (but for that miss value).  idx_out, normal_out, emitted_out and
+ * material_out may be NULL.  RTW_E_INVALID: everything rtw_ctx_depth_map and rtw_ctx_scene_surface refuse; an unknown ray_rule. */
+int rtw_ctx_surface_map(rtw_ctx *ctx, const RtwCamera *cam, uint32_t width, uint32_t height, uint32_t ray_rule, const float offset[2],
+                        float time, float mint, float maxt, uint32_t accel, uint32_t integrator,
+                        float *depth_out, int32_t *idx_out, float *normal_out, float *albedo_out, float *emitted_out,
+                        float *material_out, RtwStats *stats);
 
 /* ---- light-biased integrators (Rust2/src/viewport/ray_color.rs:55-164, objects/material.rs material_pdf) ---------------------------
  * RTW_INTEGRATOR_LIGHT_CAST / RTW_INTEGRATOR_LIGHT_BIASED send, from every surface hit h, one shadow ray per light: towards the MID-POINT of

@@ -18,6 +18,7 @@ Reference surface mirrored (names and argument meaning):
   ImageTexture::from_color_noise / new_with_noise      Rust/src/texture.rs:228-245 (texture_from_color_noise, texture_with_noise)
   bilateral_filter(img, Proximity::new(size, type))  Rust2/src/postprocessing.rs:12-131 (bilateral_filter; Renderer.bilateral_filter)
   (extension) guided_filter(img, size, depth=, normal=, ids=, ..)   the bilateral filter steered by depth_map's buffers (Renderer.guided_filter)
+  (extension) atrous_filter(frame, depth=, normal=, ids=, albedo=, emitted=, ..)   an edge-avoiding a-trous wavelet filter of linear f32 frames (Renderer.atrous_filter)
   Triangle.new (+ from_mesh), Scene(triangles=)       Rust2/src/objects/triangle.rs:28-124 (triangle_hits; Renderer.triangle_hits)
 
 The directory name carries a hyphen (it is fixed by the build contract); import it with
@@ -44,6 +45,7 @@ MAX_LIGHTS = 16
 MAX_MESH_INSTANCES = 65536
 SAMPLER_ROW, SAMPLER_STRATIFIED, SAMPLER_CENTRES, SAMPLER_NO_RAND = 0, 1, 2, 3
 ACCEL_BRUTE, ACCEL_BVH = 0, 1
+RAYS_DEPTH_MAP, RAYS_PIXEL = 0, 1                       # Renderer.surface_map's ray rule: depth_rays' (camera2_new) or pixel_rays' (Viewport cameras)
 FLAG_RECURSIVE_ORDER, FLAG_CPP_DIELECTRIC, FLAG_GLOBAL_NODES, FLAG_CPP_DIFFUSE, FLAG_CHUNK_SUMS = 1, 2, 4, 8, 16
 FLAG_CPP = FLAG_CPP_DIELECTRIC | FLAG_CPP_DIFFUSE      # what Viewport::RenderGPU of the C++ tree asks for
 FLAG_MIXED_MATERIAL = 32   # Rust2's integrators: an object with opacity < 0 is MixedMaterial::new(ir) (see mixed())
@@ -55,12 +57,17 @@ OPT_MESH_CLIMB = 13                                   # how move_mesh_instances 
 OPT_MESH_LIST_MAX = 12                               # at most this many mesh placements: list order even under ACCEL_BVH; more: the top-level tree
 MESH_LIST_MAX_DEFAULT = 16                           # its default (csrc/rtw_kernels.h RTW_MESH_LIST_MAX_DEFAULT): the measured crossover, DESIGN.md 4.11
 OPT_GUIDED_LAYOUT = 10                               # Renderer.guided_filter: 0 by size, 1 table + guides in LDS, 2 guides, 3 table, 4 neither
+OPT_ATROUS_LAYOUT = 14                               # Renderer.atrous_filter: 0 the measured choice per level, 1 LDS tile where it fits, 2 global memory
+ATROUS_MAX_LEVELS = 8
 SCENE_C1, SCENE_C2, SCENE_C4, SCENE_C5, SCENE_METAL_TEST, SCENE_QUAD_TEST, SCENE_PRESENTATION, SCENE_FIRST_FRAME = 1, 2, 4, 5, 6, 7, 8, 9
 MEDIUM_SURFACE, MEDIUM_CONST_DENSITY = 0, 1
 PROXIMITY_SQUARE, PROXIMITY_EDGES = 0, 1             # Rust2 ProximityType (postprocessing.rs:12-15)
 PIXELS_U8, PIXELS_F32_RUST2 = 0, 1                   # RtwBilateral.in_format
 BILATERAL_MAX_SIZE = 64
 STREAM_LEGACY = 1                                    # RTW_STREAM_LEGACY: HIP's legacy default stream, the one torch calls its default stream
+
+# Renderer.atrous_filter's defaults: the best row, with albedo and emission, of the sweep on the 4-spp Book-1 view (profiles/atrous.log)
+ATROUS_DEFAULTS = {"levels": 3, "sigma_color": 1.0, "sigma_depth": 0.25, "sigma_normal": 0.3, "albedo_floor": 1e-3}
 
 # materials.rs:157-212 presets as (metallicness, opacity, ir)
 METALLIC_M = (1.0, 0.0, 1.0)
@@ -166,6 +173,12 @@ class RtwBilateral(C.Structure):
 class RtwGuidedFilter(C.Structure):
     """Arguments of the guided filter: the bilateral ones, the two sigmas (0 = term off) and same_object (include/rtw.h)."""
     _fields_ = [("base", RtwBilateral), ("sigma_depth", C.c_float), ("sigma_normal", C.c_float), ("same_object", C.c_uint32)]
+
+
+class RtwAtrous(C.Structure):
+    """Arguments of the a-trous filter: levels, the three sigmas (0 = term off), same_object and the albedo floor (include/rtw.h)."""
+    _fields_ = [("levels", C.c_uint32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("sigma_normal", C.c_float),
+                ("same_object", C.c_uint32), ("albedo_floor", C.c_float)]
 
 
 class RtwFilterStats(C.Structure):
@@ -328,6 +341,11 @@ def lib() -> C.CDLL:
     L.rtw_depth_rays.argtypes = [C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, fp]
     L.rtw_ctx_scene_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.POINTER(RtwStats)]
+    L.rtw_ctx_scene_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [
+        C.POINTER(RtwStats)]
+    L.rtw_pixel_rays.argtypes = [C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, fp, fp]
+    L.rtw_ctx_surface_map.argtypes = [C.c_void_p, C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, C.c_uint32, fp, C.c_float, C.c_float, C.c_float, C.c_uint32,
+                                      C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(RtwStats)]
     L.rtw_ctx_scene_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_void_p,
                                          C.POINTER(RtwStats)]
     L.rtw_triangle_occluded.argtypes = [C.POINTER(RtwTriangle), C.c_uint32, fp, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.POINTER(RtwStats)]
@@ -385,6 +403,8 @@ def lib() -> C.CDLL:
     L.rtw_quat_from_euler.argtypes = [fp, fp]
     L.rtw_pow_plain.argtypes = [fp, fp, C.c_size_t, fp]
     L.rtw_sin_plain.argtypes = [fp, C.c_size_t, fp]
+    L.rtw_atrous_filter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.POINTER(RtwAtrous), C.c_void_p, C.POINTER(RtwFilterStats)]
+    L.rtw_ctx_atrous_filter.argtypes = [C.c_void_p] + L.rtw_atrous_filter.argtypes
     L.rtw_exp_plain.argtypes = [fp, C.c_size_t, fp]
     L.rtw_cos_plain.argtypes = [fp, C.c_size_t, fp]
     L.rtw_ctx_device_math.argtypes = [C.c_void_p, C.c_uint32, fp, C.c_uint32, C.c_uint32, fp, C.c_uint32]
@@ -841,6 +861,16 @@ def depth_rays(cam: RtwCamera, width: int, height: int) -> np.ndarray:
     width, height = int(width), int(height)
     out = np.empty((max(0, width * height), 6), np.float32)
     _check(lib().rtw_depth_rays(C.byref(cam), width, height, out.ctypes.data_as(C.POINTER(C.c_float))), "rtw_depth_rays")
+    return out
+
+
+def pixel_rays(cam: RtwCamera, width: int, height: int, offset=(0.0, 0.0)) -> np.ndarray:
+    """The pixel rays of a Viewport camera (rtw_pixel_rays): [height * width, 6] float32 = cam.origin, (pixel00 + delta_u * (i + offset[0])) +
+    delta_v * (j + offset[1]), not normalised, pixel (i, j) at row j * width + i.  Offset (0, 0) is SAMPLER_NO_RAND's ray."""
+    width, height = int(width), int(height)
+    out = np.empty((max(0, width * height), 6), np.float32)
+    off = (C.c_float * 2)(float(offset[0]), float(offset[1]))
+    _check(lib().rtw_pixel_rays(C.byref(cam), width, height, off, out.ctypes.data_as(C.POINTER(C.c_float))), "rtw_pixel_rays")
     return out
 
 
@@ -1593,6 +1623,56 @@ class Renderer:
                                        idx.ctypes.data if ids else None, nrm.ctypes.data if normals else None, C.byref(st)), "rtw_ctx_depth_map")
         return (depth,) + ((idx,) if ids else ()) + ((nrm,) if normals else ()) + (st,)
 
+    def scene_surface(self, rays, mint: float, maxt: float, integrator: int = INTEGRATOR_BG_COLOR, time: float = 0.0, accel: int = ACCEL_BVH):
+        """scene_hits with the rest of the winner's hit record as the render reads it under `integrator` (rtw_ctx_scene_surface): a dict of
+        t [n] float32 (+inf on a miss), idx [n] int32 (-1), normal [n][3], albedo [n][3] (the colour the throughput is multiplied by, textures
+        resolved), emitted [n][3], material [n][3] = metallicness, opacity, ir -- all 0 on a miss -- and stats."""
+        r = _rays(rays)
+        n = len(r)
+        out = dict(t=np.empty(n, np.float32), idx=np.empty(n, np.int32), normal=np.empty((n, 3), np.float32), albedo=np.empty((n, 3), np.float32),
+                   emitted=np.empty((n, 3), np.float32), material=np.empty((n, 3), np.float32))
+        st = RtwStats()
+        _check(lib().rtw_ctx_scene_surface(self._h, r.ctypes.data, n, float(time), float(mint), float(maxt), int(accel), int(integrator),
+                                           *(out[k].ctypes.data for k in ("t", "idx", "normal", "albedo", "emitted", "material")), C.byref(st)),
+               "rtw_ctx_scene_surface")
+        out["stats"] = st
+        return out
+
+    def surface_map(self, cam: RtwCamera, width: int, height: int, mint: float, maxt: float, integrator: int = INTEGRATOR_BG_COLOR,
+                    ray_rule: int = RAYS_PIXEL, offset=(0.5, 0.5), time: float = 0.0, accel: int = ACCEL_BVH):
+        """What a camera sees, in one launch (rtw_ctx_surface_map): a dict of depth [h][w] float32 (maxt * 1.6 on a miss), idx [h][w] int32,
+        normal, albedo, emitted, material [h][w][3] and stats.  ray_rule RAYS_PIXEL: a Viewport camera's pixel rays at `offset` inside the
+        pixel (pixel_rays); RAYS_DEPTH_MAP: depth_map's rays for a camera of camera2_new.  The guides of Renderer.atrous_filter."""
+        width, height = int(width), int(height)
+        out = dict(depth=np.empty((height, width), np.float32), idx=np.empty((height, width), np.int32))
+        for k in ("normal", "albedo", "emitted", "material"):
+            out[k] = np.empty((height, width, 3), np.float32)
+        off = (C.c_float * 2)(float(offset[0]), float(offset[1]))
+        st = RtwStats()
+        _check(lib().rtw_ctx_surface_map(self._h, C.byref(cam), width, height, int(ray_rule), off, float(time), float(mint), float(maxt), int(accel),
+                                         int(integrator), *(out[k].ctypes.data for k in ("depth", "idx", "normal", "albedo", "emitted", "material")),
+                                         C.byref(st)), "rtw_ctx_surface_map")
+        out["stats"] = st
+        return out
+
+    def render_denoised(self, cam: RtwCamera, params: RtwParams, **atrous):
+        """Python only: render `params` at gamma 1, take the guides from surface_map at the pixel centres under params' integrator, run
+        atrous_filter with albedo and emission (keyword arguments: atrous_filter's), then apply params.gamma as the render does
+        (v ** (1 / gamma)).  For Viewport cameras and whole frames (part_count 1).  Returns (frame [h][w][3] float32, RtwStats of the render)."""
+        if params.part_count != 1:
+            raise ValueError("render_denoised: whole frames only (part_count 1)")
+        gamma = float(params.gamma)
+        params.gamma = 1.0
+        try:
+            frame, st = self.render(cam, params)
+        finally:
+            params.gamma = gamma
+        g = self.surface_map(cam, params.width, params.height, params.mint, params.maxt, params.integrator, RAYS_PIXEL, (0.5, 0.5), accel=params.accel)
+        out = self.atrous_filter(frame, depth=g["depth"], normal=g["normal"], ids=g["idx"], albedo=g["albedo"], emitted=g["emitted"], **atrous)[0]
+        if gamma != 1.0:
+            out = np.power(np.maximum(out, np.float32(0.0)), np.float32(1.0 / gamma)).astype(np.float32)
+        return out, st
+
     def ambient_occlusion(self, points, normals, samples: int = 16, radius: float = 1.0, mint: float = 1e-3, seed: int = 0, time: float = 0.0,
                           accel: int = ACCEL_BVH, out=None):
         """Ambient occlusion of points ([n][3]) with normals ([n][3]) against this context's whole scene (rtw_ctx_ambient_occlusion): (ao [n]
@@ -1809,6 +1889,30 @@ class Renderer:
         _check(lib().rtw_ctx_guided_filter(self._h, src, w, h, *guides, C.byref(prm), dst, C.byref(st)), "rtw_ctx_guided_filter")
         return out, st
 
+    def atrous_filter(self, frame, depth=None, normal=None, ids=None, albedo=None, emitted=None, levels: int = ATROUS_DEFAULTS["levels"],
+                      sigma_color: float = ATROUS_DEFAULTS["sigma_color"], sigma_depth: float = ATROUS_DEFAULTS["sigma_depth"],
+                      sigma_normal: float = ATROUS_DEFAULTS["sigma_normal"], same_object: bool = True,
+                      albedo_floor: float = ATROUS_DEFAULTS["albedo_floor"], out=None):
+        """The edge-avoiding a-trous filter of a linear float32 frame [h][w][3] on this context's GPU (rtw_ctx_atrous_filter, include/rtw.h):
+        `levels` passes of a 5 x 5 B-spline kernel stepping by 1, 2, 4 .. pixels, every tap weighed by exp_plain(-(|dc|^2 / (2 sigma_color_i^2)
+        + (dz 2^-i)^2 / (2 sigma_depth^2) + |dn|^2 / (2 sigma_normal^2))) and by 0 on another object with same_object.  A sigma of 0 turns
+        its term off; a term whose guide is None is off too.  With `albedo` [h][w][3] (and `emitted`) it filters (frame - emitted) / albedo.
+        depth [h][w] float32, normal [h][w][3] float32, ids [h][w] int32: what depth_map writes.  Every argument is a numpy array (staged)
+        or a contiguous torch tensor on the context's device, read in place on the context's stream (use_torch_stream).  `out`: None -> a
+        new array or tensor like `frame`; an array or tensor of the frame's shape, which may be `frame` itself.  Returns (out, RtwFilterStats)."""
+        args, h, w, keep = _atrous_arguments(frame, depth, normal, ids, albedo, emitted, self._on_device)
+        if out is None:
+            if hasattr(frame, "data_ptr"):
+                import torch
+                out = torch.empty_like(frame)
+            else:
+                out = np.empty((h, w, 3), np.float32)
+        dst = _atrous_pointer("out", out, np.float32, (h, w, 3), self._on_device, keep, writable=True)
+        prm = _atrous_params(levels, sigma_color, sigma_depth, sigma_normal, same_object, albedo_floor, depth, normal, ids)
+        st = RtwFilterStats()
+        _check(lib().rtw_ctx_atrous_filter(self._h, *args, C.byref(prm), dst, C.byref(st)), "rtw_ctx_atrous_filter")
+        return out, st
+
     def render(self, cam: RtwCamera, params: RtwParams, out=None):
         """Render into `out`: None -> new numpy array; numpy array -> host buffer; int -> raw device pointer
         (e.g. torch_tensor.data_ptr()) of [rows][width][3] f32.  Returns (out, RtwStats)."""
@@ -2005,6 +2109,63 @@ def guided_filter(img: np.ndarray, size: int, depth=None, normal=None, ids=None,
     prm = RtwGuidedFilter(RtwBilateral(int(size), int(proximity), fmt, float(avg_gradient)), float(sigma_depth), float(sigma_normal),
                           int(same_object))
     _check(lib().rtw_guided_filter(src, w, h, *guides, C.byref(prm), dst, C.byref(st)), "rtw_guided_filter")
+    return out, st
+
+
+def _atrous_pointer(name, a, dtype, shape, on_device, keep, writable=False):
+    """The pointer of one a-trous argument: None -> NULL; a torch tensor on the context's device, in place; a numpy array, shape-checked."""
+    if a is None:
+        return None
+    if hasattr(a, "data_ptr"):
+        import torch
+        tdt = torch.float32 if dtype == np.float32 else torch.int32
+        if on_device is None or not on_device(a, tdt) or tuple(a.shape) != shape:
+            raise ValueError(f"atrous_filter: {name} must be a contiguous {tdt} tensor of shape {shape} on the context's device")
+        keep.append(a)
+        return C.c_void_p(int(a.data_ptr()))
+    if writable:
+        if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.flags["C_CONTIGUOUS"] and a.shape == shape):
+            raise ValueError(f"atrous_filter: {name} must be a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        return C.c_void_p(a.ctypes.data)
+    b = np.ascontiguousarray(a, dtype)
+    if b.shape != shape:
+        raise ValueError(f"atrous_filter: {name} of shape {b.shape}, expected {shape}")
+    keep.append(b)
+    return C.c_void_p(b.ctypes.data)
+
+
+def _atrous_arguments(frame, depth, normal, ids, albedo, emitted, on_device):
+    """(the C call's arguments from `in` to `emitted`, h, w, what they keep alive)."""
+    shp = tuple(frame.shape) if hasattr(frame, "shape") else np.shape(frame)
+    if len(shp) != 3 or shp[2] != 3:
+        raise ValueError(f"atrous_filter: frame of shape {shp}, expected [h][w][3]")
+    h, w = int(shp[0]), int(shp[1])
+    keep = []
+    ptr = lambda name, a, dtype, shape: _atrous_pointer(name, a, dtype, shape, on_device, keep)
+    args = [ptr("frame", frame, np.float32, (h, w, 3)), w, h, ptr("depth", depth, np.float32, (h, w)), ptr("normal", normal, np.float32, (h, w, 3)),
+            ptr("ids", ids, np.int32, (h, w)), ptr("albedo", albedo, np.float32, (h, w, 3)), ptr("emitted", emitted, np.float32, (h, w, 3))]
+    return args, h, w, keep
+
+
+def _atrous_params(levels, sigma_color, sigma_depth, sigma_normal, same_object, albedo_floor, depth, normal, ids) -> RtwAtrous:
+    """RtwAtrous of the Python calls: a term whose guide is None is off."""
+    return RtwAtrous(int(levels), float(sigma_color), float(sigma_depth) if depth is not None else 0.0,
+                     float(sigma_normal) if normal is not None else 0.0, int(bool(same_object) and ids is not None), float(albedo_floor))
+
+
+def atrous_filter(frame, depth=None, normal=None, ids=None, albedo=None, emitted=None, levels: int = ATROUS_DEFAULTS["levels"],
+                  sigma_color: float = ATROUS_DEFAULTS["sigma_color"], sigma_depth: float = ATROUS_DEFAULTS["sigma_depth"],
+                  sigma_normal: float = ATROUS_DEFAULTS["sigma_normal"], same_object: bool = True,
+                  albedo_floor: float = ATROUS_DEFAULTS["albedo_floor"], out=None):
+    """The a-trous filter on the host (rtw_atrous_filter), the bytes of Renderer.atrous_filter; numpy arrays only.  `out`: None -> a new
+    array, or a C-contiguous float32 array [h][w][3], which may be `frame` itself.  Returns (out, RtwFilterStats)."""
+    args, h, w, _keep = _atrous_arguments(frame, depth, normal, ids, albedo, emitted, None)
+    if out is None:
+        out = np.empty((h, w, 3), np.float32)
+    _atrous_pointer("out", out, np.float32, (h, w, 3), None, _keep, writable=True)
+    prm = _atrous_params(levels, sigma_color, sigma_depth, sigma_normal, same_object, albedo_floor, depth, normal, ids)
+    st = RtwFilterStats()
+    _check(lib().rtw_atrous_filter(*args, C.byref(prm), C.c_void_p(out.ctypes.data), C.byref(st)), "rtw_atrous_filter")
     return out, st
 
 

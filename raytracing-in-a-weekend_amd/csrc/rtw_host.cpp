@@ -183,6 +183,21 @@ int rtw_depth_rays(const RtwCamera *cam, uint32_t width, uint32_t height, float 
     return RTW_OK;
 }
 
+// The pixel rays of a Viewport camera (viewport.rs:498-503 with an offset inside the pixel): rtw_ctx_surface_map's RTW_RAYS_PIXEL rule
+int rtw_pixel_rays(const RtwCamera *cam, uint32_t width, uint32_t height, const float *offset, float *rays_out) {
+    if (!cam || !rays_out || width == 0 || height == 0) return RTW_E_INVALID;
+    const V pixel00 = ld(cam->pixel00), delta_u = ld(cam->delta_u), delta_v = ld(cam->delta_v);
+    const float ox = offset ? offset[0] : 0.0f, oy = offset ? offset[1] : 0.0f;
+    for (uint32_t j = 0; j < height; j++) {
+        for (uint32_t i = 0; i < width; i++) {
+            const V dir = (pixel00 + delta_u * ((float)i + ox)) + delta_v * ((float)j + oy);
+            float *r = rays_out + 6 * ((size_t)j * width + i);
+            st(r, ld(cam->origin)); st(r + 3, dir);
+        }
+    }
+    return RTW_OK;
+}
+
 // Viewport::new (viewport.rs:308-401)
 int rtw_viewport_new(uint32_t width, float aspect_ratio, const float *vfov, const float *origin,
                      const float *direction, const float *vup, const float *lens_radius,

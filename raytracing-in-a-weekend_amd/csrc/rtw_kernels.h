@@ -140,6 +140,13 @@ struct QueryArgs {
     float *normal_out;            // [n][3] or null
     unsigned long long *counters; // RTW_QUERY_SLOTS lines of RTW_QUERY_STRIDE counters, a workgroup adds to line blockIdx % RTW_QUERY_SLOTS (the host sums
                                   // the lines): [0] sphere tests [1] node visits (both trees) [2] quad + triangle tests [3] waves whose stack was too short
+    // rtw_ctx_scene_surface / rtw_ctx_surface_map: read by the SURF builds of scene_hits_kernel only, which albedo_out != null selects
+    float *albedo_out;            // [n][3]
+    float *emitted_out;           // [n][3] or null
+    float *material_out;          // [n][3] = metallicness, opacity, ir; or null
+    uint32_t rust2;               // the record follows Rust2's texel rules (RTW_INTEGRATOR_RUST2, _LIGHT_CAST, _LIGHT_BIASED)
+    uint32_t ray_rule;            // from_camera: RTW_RAYS_DEPTH_MAP | RTW_RAYS_PIXEL
+    float off_x, off_y;           // RTW_RAYS_PIXEL: the offset inside the pixel
 };
 #define RTW_QUERY_SLOTS 64u       // one atomic per wave and counter, spread over 64 cache lines: tens of thousands of waves adding to ONE line serialise
 #define RTW_QUERY_STRIDE 16u      // counters (u64) per line: 128 bytes

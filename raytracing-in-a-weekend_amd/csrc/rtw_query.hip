@@ -69,7 +69,10 @@ __device__ __forceinline__ void q_sphere_tree(const DevScene &sc, const DevBvh &
 
 // CAM: the ray of pixel i is built from the camera by the rule of rtw_depth_rays; else it is read from A.rays.  NORMALS: normal_out is
 // written (the stores and the winner's normal compile out otherwise).  TREE: the sphere group goes through the tree (stack in dynamic LDS).
-template <bool CAM, bool NORMALS, bool TREE, bool MOVING>
+// SURF (rtw_ctx_scene_surface / rtw_ctx_surface_map): the winner's hit record as the render's SHADE step reads it -- albedo,
+// emission, material -- is formed once, after the walk, by the render's own record functions, and written; the camera's ray may follow
+// RTW_RAYS_PIXEL; normal_out may be null.  Everything of it compiles out of the other builds.
+template <bool CAM, bool NORMALS, bool TREE, bool MOVING, bool SURF = false>
 __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char q_lds[];
     const uint32_t i = blockIdx.x * RTW_BLOCK + threadIdx.x;
@@ -77,8 +80,13 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
     bool overflow = false;
     if (i < A.n) {
         v3 o, d;
-        if (CAM) q_pixel_ray(A.cam, A.width, A.height, i, o, d);
-        else q_ray_load(A.rays, i, o, d);
+        if (CAM) {
+            if (SURF && A.ray_rule == RTW_RAYS_PIXEL) {            // (a wave-uniform branch) Viewport's pixel ray, RTW_SAMPLER_NO_RAND's at offset 0 0
+                const uint32_t px = i % A.width, py = i / A.width;
+                o = ld3(A.cam.origin);
+                d = (ld3(A.cam.pixel00) + ld3(A.cam.delta_u) * ((float)px + A.off_x)) + ld3(A.cam.delta_v) * ((float)py + A.off_y);
+            } else q_pixel_ray(A.cam, A.width, A.height, i, o, d);
+        } else q_ray_load(A.rays, i, o, d);
         const float tm = A.time, mint = A.mint, maxt = A.maxt;
         const float a = dot(d, d);
         const float ra = rcp_refined(a);
@@ -171,7 +179,44 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
                     nrm = mesh_rot(qn, ld3(A.tris.list[tk].normal));
                 }
             }
-            *reinterpret_cast<float3 *>(A.normal_out + 3 * (size_t)i) = make_float3(nrm.x, nrm.y, nrm.z);
+            if (!SURF || A.normal_out) *reinterpret_cast<float3 *>(A.normal_out + 3 * (size_t)i) = make_float3(nrm.x, nrm.y, nrm.z);
+        }
+        if (SURF) {                                                // the winner's record, with the operands the render gives the same functions
+            v3 cm = mk(0.0f, 0.0f, 0.0f), em = cm, mt = cm;
+            if (found) {
+                const DevNoise nz = { nullptr, nullptr };          // (never read: a context with texture noise is refused)
+                GeomHit h;
+                if (win == 0) {                                    // shade_hit (rtw_kernels.hip)
+                    const f4 gg = A.sc.geom[best];
+                    v3 c = mk(gg.x, gg.y, gg.z);
+                    if (MOVING) { const f4 vv = A.sc.vel[best]; c = c + mk(vv.x, vv.y, vv.z) * tm; }
+                    const v3 normal = unit((o + d * ht) - c);
+                    const DevMat mat = A.sc.mat[best];
+                    h.emitted = ld3(mat.emitted);
+                    if (A.rust2 && mat.tex >= 0) rust2_sphere_color(A.sc, mat, normal, h.cm, h.emitted);
+                    else h.cm = sphere_albedo(A.sc, mat, normal);
+                    h.m = mat_params(mat);
+                } else if (win == 1) {
+                    quad_record(A.sc, nz, g.quads, qk, o, d, ht, h);
+                } else if (win == 2) {                             // in the instance's frame (geom_closest)
+                    const DevInstance &in = g.inst[ii];
+                    const v3 tr = ld3(in.tr);
+                    v3 lo, ld;
+                    if (A.inst_quats) { const quat qn = inst_quat_lane(A.inst_quats, ii); lo = quat_rot(qn, o - tr); ld = quat_rot(qn, d); }
+                    else { lo = rotated(o - tr, in.back, in.back_k); ld = rotated(d, in.back, in.back_k); }
+                    member_record(A.sc, nz, g, icode, lo, ld, tm, ht, h);
+                } else if (win == 3) {
+                    tri_record(A.sc, A.tris, (uint32_t)tk, o, d, ht, A.rust2 != 0u, h);
+                } else {                                           // in the placement's frame (shade_geom)
+                    quat qn; v3 pos;
+                    mesh_row_lane(A.mesh_rows, (uint32_t)mp, qn, pos);
+                    tri_record(A.sc, A.tris, (uint32_t)tk, mesh_rot(qn, o - pos), mesh_rot(qn, d), ht, true, h);
+                }
+                cm = h.cm; em = h.emitted; mt = mk(h.m.metallicness, h.m.opacity, h.m.ir);
+            }
+            *reinterpret_cast<float3 *>(A.albedo_out + 3 * (size_t)i) = make_float3(cm.x, cm.y, cm.z);
+            if (A.emitted_out) *reinterpret_cast<float3 *>(A.emitted_out + 3 * (size_t)i) = make_float3(em.x, em.y, em.z);
+            if (A.material_out) *reinterpret_cast<float3 *>(A.material_out + 3 * (size_t)i) = make_float3(mt.x, mt.y, mt.z);
         }
     }
     RTW_Q_COUNT_FLUSH(A.counters, n_sph, n_nodes, n_quad, overflow, 0u);
@@ -179,9 +224,13 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
 
 void launch_scene_hits(const QueryArgs &q, bool from_camera, bool tree, hipStream_t stream) {
     typedef void (*query_fn)(const QueryArgs);
-    const query_fn fn = with_bools([](auto cam, auto normals, auto tr, auto moving) -> query_fn {
-        return scene_hits_kernel<cam.value, normals.value, tr.value, moving.value>;
-    }, from_camera, q.normal_out != nullptr, tree, q.sc.moving != 0u);
+    const query_fn fn = q.albedo_out != nullptr                    // the surface builds: the normal is always formed, its store is a run-time check
+        ? with_bools([](auto cam, auto tr, auto moving) -> query_fn {
+              return scene_hits_kernel<cam.value, true, tr.value, moving.value, true>;
+          }, from_camera, tree, q.sc.moving != 0u)
+        : with_bools([](auto cam, auto normals, auto tr, auto moving) -> query_fn {
+              return scene_hits_kernel<cam.value, normals.value, tr.value, moving.value>;
+          }, from_camera, q.normal_out != nullptr, tree, q.sc.moving != 0u);
     const uint32_t lds = tree ? q.levels * RTW_BLOCK * 4u : 0u;
     hipLaunchKernelGGL(fn, dim3((q.n + RTW_BLOCK - 1) / RTW_BLOCK), dim3(RTW_BLOCK), lds, stream, q);
 }

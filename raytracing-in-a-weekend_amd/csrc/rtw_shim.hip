@@ -6,6 +6,7 @@
 #include "rtw_refit.h"
 #include "rtw_host.h"
 #include "rtw_filter.h"
+#include "rtw_atrous_dev.h"
 #include "rtw_devmem.h"
 #include "rtw_exp.h"
 #include "rtw_probe.h"
@@ -93,6 +94,7 @@ struct rtw_ctx {
     bool noise_active = false;           // a used texture has noise: renders take the noise build (SPEC 7)
     DevNoise noise{};                    // device tables / per-texture entries (null when no noise is set)
     NoiseMem noise_mem;
+    AtrousScratch *atrous = nullptr;     // buffers of rtw_ctx_atrous_filter (rtw_atrous.hip), created on its first call
     FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
     // Rust2 triangles of the scene (rtw_ctx_set_triangles; cleared by rtw_ctx_set_scene)
     DevTris tris{};                      // tris.nodes stays null here: a render sets it (tri_view) when the tree may be used
@@ -145,6 +147,7 @@ struct rtw_ctx {
     double opt_tail_units = 0.0;         // RTW_OPT_TAIL_UNITS: blocks of short units per resident wave at the end of the queue (render_enqueue); 0 = off.
                                          // OFF by default: measured, it does not shorten a launch (profiles/r03_tail_units.log, r03_endtimes.log)
     uint32_t opt_guided_layout = 0;      // RTW_OPT_GUIDED_LAYOUT: where rtw_ctx_guided_filter keeps its table and guide tile (0 = by size)
+    uint32_t opt_atrous_layout = 0;      // RTW_OPT_ATROUS_LAYOUT: where a level of rtw_ctx_atrous_filter reads its taps (0 = the measured choice)
     uint32_t opt_node_format = 0;        // RTW_OPT_NODE_FORMAT: 0 = f32 planes where a build walks them and two of its workgroups fit a CU's LDS, 1 = f16, 2 = f32
     uint32_t opt_grab_blocks = 2;        // RTW_OPT_GRAB_BLOCKS (profiles/r02_grab_sweep.log: 1 / 2 / 4 / 8 / a tile's 42 blocks = 83.9 / 82.9 / 83.7 / 86.8 / 107.9 ms on the bench frame)
 
@@ -292,7 +295,7 @@ struct Staging {
     }
 
 private:
-    static constexpr int MAX = 6;        // (rtw_ctx_mesh_instance_hits stages six)
+    static constexpr int MAX = 7;        // (rtw_ctx_scene_surface stages seven)
     struct Back { void *dst; const void *src; size_t bytes; };
     rtw_ctx *c;
     bool always;
@@ -515,6 +518,7 @@ void rtw_ctx_destroy(rtw_ctx *c) {
     free_scene(c);                       // memory first, on its device, then the events and the stream: nothing is left for `delete` to free
     c->scr = ScratchMem{};
     filter_scratch_free(c->filter);
+    atrous_scratch_free(c->atrous);
     if (c->ev_mark) (void)hipEventDestroy(c->ev_mark);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1188,11 +1192,22 @@ int rtw_ctx_mesh_instance_hits(rtw_ctx *c, const float *rays, uint32_t n_rays, f
 }
 
 // ---- scene ray queries (rtw.h "scene ray queries"; kernel: rtw_query.hip) ------------------------------------------------------------
-// Both calls: cam != null builds the rays of a width x height map in the kernel, else `rays` [n][6] are read.
+// What the surface calls ask of the pass on top of a query (rtw.h "surface buffers"): the winner's record under `integrator`, and the rule of
+// the camera's rays.
+struct SurfaceAsk {
+    float *albedo, *emitted, *material;
+    uint32_t integrator, ray_rule;
+    float off_x, off_y;
+};
+
+// All four calls: cam != null builds the rays of a width x height map in the kernel, else `rays` [n][6] are read.  sf != null: the surface
+// builds of the kernel.
 static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, const float *rays, uint32_t n, float time, float mint,
-                       float maxt, uint32_t accel, float miss_t, float *t_out, int32_t *idx_out, float *normal_out, RtwStats *stats) {
+                       float maxt, uint32_t accel, float miss_t, float *t_out, int32_t *idx_out, float *normal_out, RtwStats *stats,
+                       const SurfaceAsk *sf = nullptr) {
     if (c->pend.active) return RTW_E_INVALID;
     if (!c->has_scene) return RTW_E_NO_SCENE;
+    if (sf && c->noise_active) return RTW_E_INVALID;               // not built: the record of a texture with noise
     HIP_TRY(hipSetDevice(c->device));
     const bool tree = query_uses_tree(c, accel, time, mint, maxt);
 
@@ -1207,6 +1222,14 @@ static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_
     q.t_out = st.out(t_out, t_bytes);
     if (idx_out) q.idx_out = st.out(idx_out, sizeof(int32_t) * (size_t)n);
     if (normal_out) q.normal_out = st.out(normal_out, 3 * t_bytes);
+    if (sf) {
+        q.albedo_out = st.out(sf->albedo, 3 * t_bytes);
+        if (sf->emitted) q.emitted_out = st.out(sf->emitted, 3 * t_bytes);
+        if (sf->material) q.material_out = st.out(sf->material, 3 * t_bytes);
+        q.rust2 = sf->integrator == RTW_INTEGRATOR_RUST2 || sf->integrator == RTW_INTEGRATOR_LIGHT_CAST || sf->integrator == RTW_INTEGRATOR_LIGHT_BIASED;
+        q.ray_rule = sf->ray_rule; q.off_x = sf->off_x; q.off_y = sf->off_y;
+        if (st.e == hipSuccess && !q.albedo_out) st.e = hipErrorInvalidValue;      // (albedo_out selects the build)
+    }
     return counted_pass(c, st, 0, n, stats, [&] { launch_scene_hits(q, cam != nullptr, tree, c->stream); });
 }
 
@@ -1221,6 +1244,28 @@ int rtw_ctx_depth_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t
     if (!c || !cam || !depth_out || width == 0 || height == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
     if ((uint64_t)width * height > 0xFFFFFFFFull) return RTW_E_INVALID;
     return scene_query(c, cam, width, height, nullptr, width * height, time, mint, maxt, accel, host_mul(maxt, 1.6f), depth_out, idx_out, normal_out, stats);
+}
+
+// The surface buffers (rtw.h "surface buffers"): the same pass, the winner's hit record written beside t, idx and normal
+int rtw_ctx_scene_surface(rtw_ctx *c, const float *rays, uint32_t n_rays, float time, float mint, float maxt, uint32_t accel, uint32_t integrator,
+                          float *t_out, int32_t *idx_out, float *normal_out, float *albedo_out, float *emitted_out, float *material_out,
+                          RtwStats *stats) {
+    if (!c || !rays || !t_out || !idx_out || n_rays == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    if (!albedo_out || integrator > RTW_INTEGRATOR_LIGHT_BIASED) return RTW_E_INVALID;
+    const SurfaceAsk sf = { albedo_out, emitted_out, material_out, integrator, RTW_RAYS_DEPTH_MAP, 0.0f, 0.0f };
+    return scene_query(c, nullptr, 0, 0, rays, n_rays, time, mint, maxt, accel, std::numeric_limits<float>::infinity(), t_out, idx_out, normal_out, stats,
+                       &sf);
+}
+
+int rtw_ctx_surface_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, uint32_t ray_rule, const float *offset, float time,
+                        float mint, float maxt, uint32_t accel, uint32_t integrator, float *depth_out, int32_t *idx_out, float *normal_out,
+                        float *albedo_out, float *emitted_out, float *material_out, RtwStats *stats) {
+    if (!c || !cam || !depth_out || width == 0 || height == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
+    if ((uint64_t)width * height > 0xFFFFFFFFull) return RTW_E_INVALID;
+    if (!albedo_out || integrator > RTW_INTEGRATOR_LIGHT_BIASED || ray_rule > RTW_RAYS_PIXEL) return RTW_E_INVALID;
+    const SurfaceAsk sf = { albedo_out, emitted_out, material_out, integrator, ray_rule, offset ? offset[0] : 0.0f, offset ? offset[1] : 0.0f };
+    return scene_query(c, cam, width, height, nullptr, width * height, time, mint, maxt, accel, host_mul(maxt, 1.6f), depth_out, idx_out, normal_out,
+                       stats, &sf);
 }
 
 // The any-hit pass (rtw.h "occlusion queries"; kernel: rtw_occluded.hip): scene_query's conditions, views, staging and stream order
@@ -1376,6 +1421,15 @@ int rtw_ctx_guided_filter(rtw_ctx *c, const void *in, uint32_t w, uint32_t h, co
     if (!c) return RTW_E_INVALID;
     if (c->pend.active) return RTW_E_INVALID;
     return guided_filter_device(c->device, c->stream, &c->filter, c->opt_guided_layout, in, w, h, depth, normal, idx, p, out, stats, &g_last_hip);
+}
+
+// The a-trous filter (rtw_atrous.hip) likewise.
+int rtw_ctx_atrous_filter(rtw_ctx *c, const float *in, uint32_t w, uint32_t h, const float *depth, const float *normal, const int32_t *idx,
+                          const float *albedo, const float *emitted, const RtwAtrous *p, float *out, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return atrous_filter_device(c->device, c->stream, &c->atrous, c->opt_atrous_layout, in, w, h, depth, normal, idx, albedo, emitted, p, out,
+                                stats, &g_last_hip);
 }
 
 // The device-math probe (rtw_probe.hip, rtw.h "device math, for tests") on this context's GPU and stream; the scene is not involved.
@@ -1905,6 +1959,7 @@ int rtw_ctx_set_option(rtw_ctx *c, uint32_t key, double v) {
     case RTW_OPT_SUB_QUEUES:     if (!(v == 0.0 || v == 1.0)) return RTW_E_INVALID; c->opt_sub_queues = (uint32_t)v; return RTW_OK;
     case RTW_OPT_TAIL_UNITS:     if (!(v >= 0.0 && v <= 1024.0)) return RTW_E_INVALID; c->opt_tail_units = v; return RTW_OK;
     case RTW_OPT_GUIDED_LAYOUT:  if (!(v >= 0.0 && v <= 4.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_guided_layout = (uint32_t)v; return RTW_OK;
+    case RTW_OPT_ATROUS_LAYOUT:  if (!(v == 0.0 || v == 1.0 || v == 2.0)) return RTW_E_INVALID; c->opt_atrous_layout = (uint32_t)v; return RTW_OK;
     case RTW_OPT_GRAB_BLOCKS:    if (!(v >= 0.0 && v <= 65536.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_grab_blocks = (uint32_t)v; return RTW_OK;
     case RTW_OPT_MESH_LIST_MAX:  if (!(v >= 0.0 && v <= 4294967295.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_mesh_list_max = (uint32_t)v; return RTW_OK;
     case RTW_OPT_MESH_CLIMB:     if (!(v == 0.0 || v == 1.0 || v == 2.0)) return RTW_E_INVALID; c->opt_mesh_climb = (uint32_t)v; return RTW_OK;
