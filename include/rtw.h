@@ -549,6 +549,76 @@ int rtw_ctx_atrous_filter(rtw_ctx *ctx, const float *in, uint32_t w, uint32_t h,
                           const int32_t *idx, const float *albedo, const float *emitted, const RtwAtrous *params, float *out,
                           RtwFilterStats *stats);
 
+/* ---- temporal accumulation: frames of a sequence blended along reprojected pixels -- added within v4 ------------------------------------
+ * The a-trous filter's temporal half (Schied et al. 2017, SVGF's accumulation): the previous call's accumulated colour, its two luminance
+ * moments and its history length are fetched where each pixel's surface point lay in the previous view, accepted or rejected per tap
+ * against the surface buffers, and blended with the new frame.  For cameras of rtw_viewport_new and the ray rule RTW_RAYS_PIXEL only; the
+ * world is taken as static between the two frames.  Everything is f32 with one rounding per written operation (no fused multiply-add); a
+ * dot product is (x*x' + y*y') + z*z', a cross product x x y = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0).
+ * Buffers, row-major: cur, *_color, *_normal [h][w][3] f32; *_moments [h][w][2] f32; *_len, *_depth, *_variance [h][w] f32; *_idx [h][w]
+ * i32.  depth, normal, idx are what rtw_ctx_surface_map(.., RTW_RAYS_PIXEL, offset, ..) writes for `cam`, prev_depth, prev_normal, prev_idx
+ * what it wrote for prev_cam; a miss is simply another depth, normal and object.  prev_color, prev_moments, prev_len are the previous
+ * call's out_color, out_moments, out_len.
+ *   The plan, once per call on the host, from prev_cam (p00 = pixel00, du = delta_u, dv = delta_v):
+ *     n = du x dv;  a = dv x n;  b = n x du;  pn = p00.n;  pa = p00.a;  pb = p00.b;  ua = du.a;  vb = dv.b
+ *     static = cam and prev_cam agree byte for byte in origin, pixel00, delta_u, delta_v
+ *   Pixel p = (i, j), (ox, oy) = params.offset:
+ *     L = (0.2126f r + 0.7152f g) + 0.0722f b of cur[p];   fin = r, g, b all finite
+ *     static:     fx = i;  fy = j;  s = depth[p]
+ *     otherwise:  dir = the direction of rtw_pixel_rays for `cam` at (i, j) with the offset;  P = cam.origin + dir * depth[p];
+ *                 d = P - prev_cam.origin;  s = (d.n) / pn;  fx = ((d.a) / s - pa) / ua - ox;  fy = ((d.b) / s - pb) / vb - oy
+ *                 (s is the t the previous depth buffer holds for a ray through (fx, fy) that meets P)
+ *     no history unless s > 0, fx > -1, fx < w, fy > -1, fy < h (all false for NaN)
+ *     x0 = floorf(fx), wx = fx - x0, y likewise; the taps q, in this order: (x0, y0) with wt = (1-wx)*(1-wy), (x0+1, y0) with wx*(1-wy),
+ *     (x0, y0+1) with (1-wx)*wy, (x0+1, y0+1) with wx*wy.  A tap counts when it lies inside the frame, prev_len[q] > 0,
+ *         depth_tol  > 0:  |prev_depth[q] - s| <= depth_tol * s
+ *         normal_cos > 0:  normal[p] . prev_normal[q] >= normal_cos
+ *         same_object:     prev_idx[q] == idx[p]
+ *     and wt > 0 (a tap of weight 0 adds nothing, as in the a-trous filter: it cannot enter as 0 * NaN).  Over the counted taps
+ *         wsum = wsum + wt;  sum_x = sum_x + wt * prev_x[q]   for the 3 colour channels, the 2 moments and the length
+ *     a history exists when wsum > 0: H = sum / wsum
+ *     with a history and fin:   n_ = H.len + 1 < max_history ? H.len + 1 : max_history;  a_ = 1 / n_, alpha when a_ < alpha;  am_ likewise
+ *                               with alpha_moments;  out_color = H.c + (cur - H.c) * a_;  m1 = H.m1 + (L - H.m1) * am_;
+ *                               m2 = H.m2 + (L*L - H.m2) * am_;  out_len = n_
+ *     no history, fin:          out_color = cur;  m1 = L;  m2 = L*L;  out_len = 1
+ *     a history, not fin:       the history is written back unchanged, out_len = H.len: one bad sample does not enter
+ *     no history, not fin:      out_color = cur;  m1 = m2 = 0;  out_len = 0: no later frame reads this pixel as history
+ *     out_moments = (m1, m2);   out_variance = m2 - m1*m1 when that is > 0, else 0
+ * The first frame passes NULL for prev_cam, prev_color, prev_moments, prev_len and the three prev_* guides: every pixel is without a
+ * history.  A guide whose term is off may be NULL and is never read (depth is always read).  out_color may be cur: a pixel reads only its
+ * own cur.  out_variance may be NULL.  History coverage is the caller's mean of out_len > 1.
+ * RTW_E_INVALID, nothing written: cur, cam, depth, params, out_color, out_moments or out_len NULL; w or h zero or beyond
+ * RTW_TEMPORAL_MAX_SIDE, or w * h beyond 32 bits; some but not all of prev_cam, prev_color, prev_moments, prev_len given, or a prev_* guide
+ * without them; a term that is on with its current guide NULL, or, with a history, its previous guide NULL; alpha or alpha_moments outside
+ * [0, 1] or not finite; max_history outside 1 .. 65535; depth_tol negative or not finite; normal_cos outside [0, 1] or not finite;
+ * same_object > 1; an offset that is not finite; a prev_cam whose pn, ua or vb is zero or not finite; out_color == prev_color,
+ * out_moments == prev_moments or out_len == prev_len (neighbours gather from prev_*).
+ * There is no rtw_mgpu_* form and no JSON form. */
+#define RTW_TEMPORAL_MAX_SIDE 65535u
+typedef struct RtwTemporal {
+    float    alpha;                 /* floor of the colour blend factor, 0 .. 1 (0: plain running mean up to max_history) */
+    float    alpha_moments;         /* the same for the two luminance moments                                         */
+    uint32_t max_history;           /* 1 .. 65535: history length saturates here                                      */
+    float    depth_tol;             /* 0 = no depth test; else a tap passes when |prev_depth[q] - s| <= depth_tol * s */
+    float    normal_cos;            /* 0 = no normal test; else in (0, 1]: normal[p] . prev_normal[q] >= normal_cos   */
+    uint32_t same_object;           /* 1 = a tap passes only when prev_idx[q] == idx[p]                               */
+    float    offset[2];             /* the RTW_RAYS_PIXEL offset both frames' guides were made with                   */
+} RtwTemporal;
+/* The host form (one thread).  RtwFilterStats: filter_ms and total_ms are the call's time, taps = 4 * w * h, the other fields are 0. */
+int rtw_temporal_accumulate(const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth, const float *normal,
+                            const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color, const float *prev_moments,
+                            const float *prev_len, const float *prev_depth, const float *prev_normal, const int32_t *prev_idx,
+                            const RtwTemporal *params, float *out_color, float *out_moments, float *out_len,
+                            float *out_variance /* may be NULL */, RtwFilterStats *stats);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host form.  Every buffer may independently be host memory or device memory of
+ * ctx's GPU (host memory is staged; results go straight into device buffers).  One launch, one thread per pixel; filter_ms is its device
+ * time.  Needs no scene and leaves the scene, and every render, untouched. */
+int rtw_ctx_temporal_accumulate(rtw_ctx *ctx, const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth,
+                                const float *normal, const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color,
+                                const float *prev_moments, const float *prev_len, const float *prev_depth, const float *prev_normal,
+                                const int32_t *prev_idx, const RtwTemporal *params, float *out_color, float *out_moments, float *out_len,
+                                float *out_variance /* may be NULL */, RtwFilterStats *stats);
+
 /* ---- Rust2 triangles (Rust2/src/objects/triangle.rs) ----------------------------------------------------------------------------
  * `Triangle{origin, u, v, mat, texture}` with the derived fields of Triangle::new (:28-50): n = u x v, normal = unit(n),
  * d = normal . origin, w = n / (n . n); the hit test of get_hit (:95-124) restated operation by operation in f32: reject when

@@ -19,6 +19,7 @@ Reference surface mirrored (names and argument meaning):
   bilateral_filter(img, Proximity::new(size, type))  Rust2/src/postprocessing.rs:12-131 (bilateral_filter; Renderer.bilateral_filter)
   (extension) guided_filter(img, size, depth=, normal=, ids=, ..)   the bilateral filter steered by depth_map's buffers (Renderer.guided_filter)
   (extension) atrous_filter(frame, depth=, normal=, ids=, albedo=, emitted=, ..)   an edge-avoiding a-trous wavelet filter of linear f32 frames (Renderer.atrous_filter)
+  (extension) temporal_accumulate(cur, cam, depth=, normal=, ids=, history=, ..)   frames of a sequence blended along reprojected pixels (Renderer.temporal_accumulate, TemporalDenoiser)
   Triangle.new (+ from_mesh), Scene(triangles=)       Rust2/src/objects/triangle.rs:28-124 (triangle_hits; Renderer.triangle_hits)
 
 The directory name carries a hyphen (it is fixed by the build contract); import it with
@@ -67,6 +68,10 @@ BILATERAL_MAX_SIZE = 64
 STREAM_LEGACY = 1                                    # RTW_STREAM_LEGACY: HIP's legacy default stream, the one torch calls its default stream
 
 # Renderer.atrous_filter's defaults: the best row, with albedo and emission, of the sweep on the 4-spp Book-1 view (profiles/atrous.log)
+TEMPORAL_MAX_SIDE = 65535
+# Renderer.temporal_accumulate's defaults: the best row, by the accumulated colour, of the sweep on the 4-spp Book-1 orbit (DESIGN.md 8d,
+# profiles/temporal.log); max_history and same_object were not swept
+TEMPORAL_DEFAULTS = {"alpha": 0.1, "alpha_moments": 0.1, "max_history": 32, "depth_tol": 0.05, "normal_cos": 0.9, "same_object": 1}
 ATROUS_DEFAULTS = {"levels": 3, "sigma_color": 1.0, "sigma_depth": 0.25, "sigma_normal": 0.3, "albedo_floor": 1e-3}
 
 # materials.rs:157-212 presets as (metallicness, opacity, ir)
@@ -179,6 +184,13 @@ class RtwAtrous(C.Structure):
     """Arguments of the a-trous filter: levels, the three sigmas (0 = term off), same_object and the albedo floor (include/rtw.h)."""
     _fields_ = [("levels", C.c_uint32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("sigma_normal", C.c_float),
                 ("same_object", C.c_uint32), ("albedo_floor", C.c_float)]
+
+
+class RtwTemporal(C.Structure):
+    """Arguments of the temporal accumulation: the two blend floors, the history cap, the depth and normal tests (0 = term off), same_object
+    and the pixel offset of both frames' guides (include/rtw.h)."""
+    _fields_ = [("alpha", C.c_float), ("alpha_moments", C.c_float), ("max_history", C.c_uint32), ("depth_tol", C.c_float),
+                ("normal_cos", C.c_float), ("same_object", C.c_uint32), ("offset", C.c_float * 2)]
 
 
 class RtwFilterStats(C.Structure):
@@ -405,6 +417,9 @@ def lib() -> C.CDLL:
     L.rtw_sin_plain.argtypes = [fp, C.c_size_t, fp]
     L.rtw_atrous_filter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.POINTER(RtwAtrous), C.c_void_p, C.POINTER(RtwFilterStats)]
     L.rtw_ctx_atrous_filter.argtypes = [C.c_void_p] + L.rtw_atrous_filter.argtypes
+    L.rtw_temporal_accumulate.argtypes = ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwCamera)] + [C.c_void_p] * 3 + [C.POINTER(RtwCamera)] +
+                                          [C.c_void_p] * 6 + [C.POINTER(RtwTemporal)] + [C.c_void_p] * 4 + [C.POINTER(RtwFilterStats)])
+    L.rtw_ctx_temporal_accumulate.argtypes = [C.c_void_p] + L.rtw_temporal_accumulate.argtypes
     L.rtw_exp_plain.argtypes = [fp, C.c_size_t, fp]
     L.rtw_cos_plain.argtypes = [fp, C.c_size_t, fp]
     L.rtw_ctx_device_math.argtypes = [C.c_void_p, C.c_uint32, fp, C.c_uint32, C.c_uint32, fp, C.c_uint32]
@@ -1913,6 +1928,21 @@ class Renderer:
         _check(lib().rtw_ctx_atrous_filter(self._h, *args, C.byref(prm), dst, C.byref(st)), "rtw_ctx_atrous_filter")
         return out, st
 
+    def temporal_accumulate(self, cur, cam: RtwCamera, depth, normal=None, ids=None, history=None, out_color=None, **params):
+        """Temporal accumulation of a linear float32 frame [h][w][3] on this context's GPU (rtw_ctx_temporal_accumulate, include/rtw.h): the
+        previous call's accumulated colour, luminance moments and history length are fetched where each pixel's surface point lay in the
+        previous view, each of the four taps accepted or rejected against the guides, and blended with `cur`.  depth [h][w] float32, normal
+        [h][w][3] float32, ids [h][w] int32: what surface_map(cam, .., RAYS_PIXEL, offset) writes; a test whose guide is None is off.
+        history: None for the first frame, else the dict a previous call returned.  Keyword arguments: alpha, alpha_moments, max_history,
+        depth_tol, normal_cos, same_object (TEMPORAL_DEFAULTS) and offset (0.5, 0.5).  Every array is a numpy array (staged) or a contiguous
+        torch tensor on the context's device, read in place on the context's stream (use_torch_stream); the results are tensors when `cur` is
+        one.  out_color: None -> new; or an array / tensor of the frame's shape, which may be `cur`, never history["color"].
+        Returns (history, variance [h][w], RtwFilterStats): history = dict(color, moments, len, depth, normal, idx, cam) holds the results
+        and THIS call's guides (not copied: leave them unchanged until the next call has read them) and a copy of cam.  History coverage is
+        (history["len"] > 1).mean()."""
+        return _temporal_call(lib().rtw_ctx_temporal_accumulate, "rtw_ctx_temporal_accumulate", (self._h,), self._on_device, cur, cam, depth,
+                              normal, ids, history, out_color, params)
+
     def render(self, cam: RtwCamera, params: RtwParams, out=None):
         """Render into `out`: None -> new numpy array; numpy array -> host buffer; int -> raw device pointer
         (e.g. torch_tensor.data_ptr()) of [rows][width][3] f32.  Returns (out, RtwStats)."""
@@ -2112,24 +2142,25 @@ def guided_filter(img: np.ndarray, size: int, depth=None, normal=None, ids=None,
     return out, st
 
 
-def _atrous_pointer(name, a, dtype, shape, on_device, keep, writable=False):
-    """The pointer of one a-trous argument: None -> NULL; a torch tensor on the context's device, in place; a numpy array, shape-checked."""
+def _atrous_pointer(name, a, dtype, shape, on_device, keep, writable=False, who="atrous_filter"):
+    """The pointer of one a-trous (or temporal) argument: None -> NULL; a torch tensor on the context's device, in place; a numpy array,
+    shape-checked."""
     if a is None:
         return None
     if hasattr(a, "data_ptr"):
         import torch
         tdt = torch.float32 if dtype == np.float32 else torch.int32
         if on_device is None or not on_device(a, tdt) or tuple(a.shape) != shape:
-            raise ValueError(f"atrous_filter: {name} must be a contiguous {tdt} tensor of shape {shape} on the context's device")
+            raise ValueError(f"{who}: {name} must be a contiguous {tdt} tensor of shape {shape} on the context's device")
         keep.append(a)
         return C.c_void_p(int(a.data_ptr()))
     if writable:
         if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.flags["C_CONTIGUOUS"] and a.shape == shape):
-            raise ValueError(f"atrous_filter: {name} must be a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+            raise ValueError(f"{who}: {name} must be a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
         return C.c_void_p(a.ctypes.data)
     b = np.ascontiguousarray(a, dtype)
     if b.shape != shape:
-        raise ValueError(f"atrous_filter: {name} of shape {b.shape}, expected {shape}")
+        raise ValueError(f"{who}: {name} of shape {b.shape}, expected {shape}")
     keep.append(b)
     return C.c_void_p(b.ctypes.data)
 
@@ -2167,6 +2198,94 @@ def atrous_filter(frame, depth=None, normal=None, ids=None, albedo=None, emitted
     st = RtwFilterStats()
     _check(lib().rtw_atrous_filter(*args, C.byref(prm), C.c_void_p(out.ctypes.data), C.byref(st)), "rtw_atrous_filter")
     return out, st
+
+
+def _temporal_call(fn, fn_name, head, on_device, cur, cam, depth, normal, ids, history, out_color, params):
+    """rtw_temporal_accumulate / rtw_ctx_temporal_accumulate from the Python arguments of temporal_accumulate: (history, variance, stats)."""
+    who = "temporal_accumulate"
+    unknown = set(params) - set(TEMPORAL_DEFAULTS) - {"offset"}
+    if unknown:
+        raise TypeError(f"{who}: unknown arguments {sorted(unknown)}")
+    q = dict(TEMPORAL_DEFAULTS, **params)
+    offset = q.get("offset", (0.5, 0.5))
+    shp = tuple(cur.shape) if hasattr(cur, "shape") else np.shape(cur)
+    if len(shp) != 3 or shp[2] != 3:
+        raise ValueError(f"{who}: cur of shape {shp}, expected [h][w][3]")
+    h, w = int(shp[0]), int(shp[1])
+    keep = []
+    ptr = lambda name, a, dtype, shape, writable=False: _atrous_pointer(name, a, dtype, shape, on_device, keep, writable, who)
+    hist = history or {}
+    prev_cam = hist.get("cam")
+    if hasattr(cur, "data_ptr"):
+        import torch
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=cur.device)
+    else:
+        new = lambda *shape: np.empty(shape, np.float32)
+    out = dict(color=new(h, w, 3) if out_color is None else out_color, moments=new(h, w, 2), len=new(h, w), depth=depth, normal=normal, idx=ids,
+               cam=RtwCamera.from_buffer_copy(cam))
+    variance = new(h, w)
+    prm = RtwTemporal(float(q["alpha"]), float(q["alpha_moments"]), int(q["max_history"]), float(q["depth_tol"]) if depth is not None else 0.0,
+                      float(q["normal_cos"]) if normal is not None else 0.0, int(bool(q["same_object"]) and ids is not None),
+                      (C.c_float * 2)(float(offset[0]), float(offset[1])))
+    args = [ptr("cur", cur, np.float32, (h, w, 3)), w, h, C.byref(cam), ptr("depth", depth, np.float32, (h, w)),
+            ptr("normal", normal, np.float32, (h, w, 3)), ptr("ids", ids, np.int32, (h, w)),
+            C.byref(prev_cam) if prev_cam is not None else None,
+            ptr("history color", hist.get("color"), np.float32, (h, w, 3)), ptr("history moments", hist.get("moments"), np.float32, (h, w, 2)),
+            ptr("history len", hist.get("len"), np.float32, (h, w)), ptr("history depth", hist.get("depth"), np.float32, (h, w)),
+            ptr("history normal", hist.get("normal"), np.float32, (h, w, 3)), ptr("history idx", hist.get("idx"), np.int32, (h, w)),
+            C.byref(prm), ptr("out_color", out["color"], np.float32, (h, w, 3), True), ptr("moments", out["moments"], np.float32, (h, w, 2), True),
+            ptr("len", out["len"], np.float32, (h, w), True), ptr("variance", variance, np.float32, (h, w), True)]
+    st = RtwFilterStats()
+    _check(fn(*head, *args, C.byref(st)), fn_name)
+    return out, variance, st
+
+
+def temporal_accumulate(cur, cam: RtwCamera, depth, normal=None, ids=None, history=None, out_color=None, **params):
+    """The temporal accumulation on the host (rtw_temporal_accumulate), the bytes of Renderer.temporal_accumulate; numpy arrays only.
+    Arguments and result as there."""
+    return _temporal_call(lib().rtw_temporal_accumulate, "rtw_temporal_accumulate", (), None, cur, cam, depth, normal, ids, history, out_color, params)
+
+
+class TemporalDenoiser:
+    """Python only: a sequence driver around Renderer.temporal_accumulate for Viewport cameras and whole frames (part_count 1).
+    `params`: temporal_accumulate's keyword arguments (TEMPORAL_DEFAULTS), but for offset, which is (0.5, 0.5).  The scene is taken as
+    static from one step to the next."""
+
+    def __init__(self, renderer, **params):
+        if "offset" in params:
+            raise TypeError("TemporalDenoiser: the offset is (0.5, 0.5), the centre of the jittered samplers' pixel")
+        self.renderer, self.params, self.history = renderer, dict(params), None
+
+    def reset(self):
+        """Drop the history: the next step starts a sequence."""
+        self.history = None
+
+    def step(self, cam: RtwCamera, params: RtwParams, **atrous):
+        """One frame: params.seed is advanced by one (in `params`), the frame rendered at gamma 1, the guides taken from surface_map at the
+        pixel centres, the frame accumulated onto the history, atrous_filter (keyword arguments: its own) run on the accumulated colour
+        with albedo and emission, and params.gamma applied as render_denoised does.  Returns (frame, accumulated, variance, stats): frame
+        the filtered [h][w][3] float32 image, accumulated the linear accumulated colour (the history's), variance [h][w], stats a dict of
+        render (RtwStats), temporal and atrous (RtwFilterStats), coverage ((len > 1).mean()), and cur and guides, the rendered frame and
+        surface_map's dict this step accumulated."""
+        if params.part_count != 1:
+            raise ValueError("TemporalDenoiser: whole frames only (part_count 1)")
+        r = self.renderer
+        params.seed = (params.seed + 1) & 0xFFFFFFFFFFFFFFFF
+        gamma = float(params.gamma)
+        params.gamma = 1.0
+        try:
+            cur, st = r.render(cam, params)
+        finally:
+            params.gamma = gamma
+        g = r.surface_map(cam, params.width, params.height, params.mint, params.maxt, params.integrator, RAYS_PIXEL, (0.5, 0.5), accel=params.accel)
+        self.history, variance, st_t = r.temporal_accumulate(cur, cam, depth=g["depth"], normal=g["normal"], ids=g["idx"], history=self.history,
+                                                             offset=(0.5, 0.5), **self.params)
+        acc = self.history["color"]
+        frame, st_a = r.atrous_filter(acc, depth=g["depth"], normal=g["normal"], ids=g["idx"], albedo=g["albedo"], emitted=g["emitted"], **atrous)
+        if gamma != 1.0:
+            frame = np.power(np.maximum(frame, np.float32(0.0)), np.float32(1.0 / gamma)).astype(np.float32)
+        stats = dict(render=st, temporal=st_t, atrous=st_a, coverage=float((self.history["len"] > 1).mean()), cur=cur, guides=g)
+        return frame, acc, variance, stats
 
 
 def write_img_f32(img: np.ndarray, filename: str):

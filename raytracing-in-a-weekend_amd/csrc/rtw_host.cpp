@@ -2,6 +2,7 @@
 // Built with -ffp-contract=off: every f32 expression below rounds once per written operation,
 // like the Rust it restates.
 #include "rtw_host.h"
+#include "rtw_pixel_ray.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -186,13 +187,12 @@ int rtw_depth_rays(const RtwCamera *cam, uint32_t width, uint32_t height, float 
 // The pixel rays of a Viewport camera (viewport.rs:498-503 with an offset inside the pixel): rtw_ctx_surface_map's RTW_RAYS_PIXEL rule
 int rtw_pixel_rays(const RtwCamera *cam, uint32_t width, uint32_t height, const float *offset, float *rays_out) {
     if (!cam || !rays_out || width == 0 || height == 0) return RTW_E_INVALID;
-    const V pixel00 = ld(cam->pixel00), delta_u = ld(cam->delta_u), delta_v = ld(cam->delta_v);
     const float ox = offset ? offset[0] : 0.0f, oy = offset ? offset[1] : 0.0f;
     for (uint32_t j = 0; j < height; j++) {
         for (uint32_t i = 0; i < width; i++) {
-            const V dir = (pixel00 + delta_u * ((float)i + ox)) + delta_v * ((float)j + oy);
             float *r = rays_out + 6 * ((size_t)j * width + i);
-            st(r, ld(cam->origin)); st(r + 3, dir);
+            st(r, ld(cam->origin));
+            pixel_ray_dir(*cam, i, j, ox, oy, r[3], r[4], r[5]);
         }
     }
     return RTW_OK;

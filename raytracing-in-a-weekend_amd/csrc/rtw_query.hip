@@ -14,6 +14,7 @@
 // pass's own stays here: the acceptance of a root in range (q_sphere) and the loop over all the spheres kept outside the tree.
 #include "rtw_scene_walk.h"
 #include "rtw_mesh.h"
+#include "rtw_pixel_ray.h"
 
 namespace rtw {
 
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
             if (SURF && A.ray_rule == RTW_RAYS_PIXEL) {            // (a wave-uniform branch) Viewport's pixel ray, RTW_SAMPLER_NO_RAND's at offset 0 0
                 const uint32_t px = i % A.width, py = i / A.width;
                 o = ld3(A.cam.origin);
-                d = (ld3(A.cam.pixel00) + ld3(A.cam.delta_u) * ((float)px + A.off_x)) + ld3(A.cam.delta_v) * ((float)py + A.off_y);
+                pixel_ray_dir(A.cam, px, py, A.off_x, A.off_y, d.x, d.y, d.z);
             } else q_pixel_ray(A.cam, A.width, A.height, i, o, d);
         } else q_ray_load(A.rays, i, o, d);
         const float tm = A.time, mint = A.mint, maxt = A.maxt;

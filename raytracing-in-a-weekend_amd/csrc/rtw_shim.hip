@@ -7,6 +7,7 @@
 #include "rtw_host.h"
 #include "rtw_filter.h"
 #include "rtw_atrous_dev.h"
+#include "rtw_temporal_dev.h"
 #include "rtw_devmem.h"
 #include "rtw_exp.h"
 #include "rtw_probe.h"
@@ -95,6 +96,7 @@ struct rtw_ctx {
     DevNoise noise{};                    // device tables / per-texture entries (null when no noise is set)
     NoiseMem noise_mem;
     AtrousScratch *atrous = nullptr;     // buffers of rtw_ctx_atrous_filter (rtw_atrous.hip), created on its first call
+    TemporalScratch *temporal = nullptr; // buffers of rtw_ctx_temporal_accumulate (rtw_temporal.hip), created on its first call
     FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
     // Rust2 triangles of the scene (rtw_ctx_set_triangles; cleared by rtw_ctx_set_scene)
     DevTris tris{};                      // tris.nodes stays null here: a render sets it (tri_view) when the tree may be used
@@ -519,6 +521,7 @@ void rtw_ctx_destroy(rtw_ctx *c) {
     c->scr = ScratchMem{};
     filter_scratch_free(c->filter);
     atrous_scratch_free(c->atrous);
+    temporal_scratch_free(c->temporal);
     if (c->ev_mark) (void)hipEventDestroy(c->ev_mark);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1430,6 +1433,19 @@ int rtw_ctx_atrous_filter(rtw_ctx *c, const float *in, uint32_t w, uint32_t h, c
     if (c->pend.active) return RTW_E_INVALID;
     return atrous_filter_device(c->device, c->stream, &c->atrous, c->opt_atrous_layout, in, w, h, depth, normal, idx, albedo, emitted, p, out,
                                 stats, &g_last_hip);
+}
+
+// The temporal accumulation (rtw_temporal.hip) likewise.
+int rtw_ctx_temporal_accumulate(rtw_ctx *c, const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth, const float *normal,
+                                const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color, const float *prev_moments,
+                                const float *prev_len, const float *prev_depth, const float *prev_normal, const int32_t *prev_idx,
+                                const RtwTemporal *p, float *out_color, float *out_moments, float *out_len, float *out_variance,
+                                RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    const TemporalBuffers b = { cur, depth, normal, idx, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
+                                out_color, out_moments, out_len, out_variance };
+    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, stats, &g_last_hip);
 }
 
 // The device-math probe (rtw_probe.hip, rtw.h "device math, for tests") on this context's GPU and stream; the scene is not involved.

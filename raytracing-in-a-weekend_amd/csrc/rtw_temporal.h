@@ -1,0 +1,166 @@
+// rtw_temporal.h -- temporal accumulation of frames by reprojection (include/rtw.h "temporal accumulation"): the rule of one
+// pixel as ONE __host__ __device__ definition.  The host form (rtw_temporal.cpp) and the kernel (rtw_temporal.hip) run these with the same
+// plan, formed once per call on the host by temporal_check, so the device writes the host form's bytes: f32, one rounding per written
+// operation under -ffp-contract=off, dot products as (x*x' + y*y') + z*z', the four taps in the order (x0, y0), (x0+1, y0), (x0, y0+1),
+// (x0+1, y0+1).
+#pragma once
+#include <hip/hip_runtime.h>
+#include "rtw_pixel_ray.h"
+#include "rtw.h"
+
+namespace rtw {
+
+constexpr int TEMPORAL_DEPTH = 1, TEMPORAL_NORMAL = 2, TEMPORAL_IDX = 4;               // the terms that are on
+
+// What every pixel of a call shares: checked and derived once by temporal_check (rtw_temporal.cpp).
+struct TemporalPlan {
+    uint32_t w = 0, h = 0;
+    int terms = 0;
+    int has_prev = 0;                // 0: the first frame, every pixel is without a history
+    int is_static = 0;               // cam and prev_cam agree byte for byte in origin, pixel00, delta_u, delta_v: fx = i, fy = j, s = depth[p]
+    float alpha = 0.0f, alpha_moments = 0.0f, max_history = 1.0f, depth_tol = 0.0f, normal_cos = 0.0f, ox = 0.0f, oy = 0.0f;
+    RtwCamera cam = {};              // the current camera: pixel_ray_dir reads it
+    float po[3] = {};                // prev_cam.origin
+    float n[3] = {}, a[3] = {}, b[3] = {};     // n = du x dv, a = dv x n, b = n x du of prev_cam
+    float pn = 0.0f, pa = 0.0f, pb = 0.0f, ua = 0.0f, vb = 0.0f;     // p00.n, p00.a, p00.b, du.a, dv.b
+};
+
+// The buffers of a call (include/rtw.h): the current frame, the previous call's outputs and guides, this call's outputs.
+struct TemporalFrame { const float *cur, *depth, *normal; const int32_t *idx; };
+struct TemporalHistory { const float *color, *moments, *len, *depth, *normal; const int32_t *idx; };
+struct TemporalOut { float *color, *moments, *len, *variance; };
+
+// What the counted taps add up to.
+struct TemporalSum { float w, c0, c1, c2, m1, m2, len; };
+
+__host__ __device__ inline float temporal_dot(const float *x, const float *y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
+__host__ __device__ inline void temporal_cross(const float *x, const float *y, float *o) {
+    o[0] = x[1] * y[2] - x[2] * y[1];
+    o[1] = x[2] * y[0] - x[0] * y[2];
+    o[2] = x[0] * y[1] - x[1] * y[0];
+}
+__host__ __device__ inline bool temporal_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }      // (false for NaN)
+
+// Where pixel (i, j) of the current view, at depth `depth`, lay in the previous view: the tap position (fx, fy) in pixel units and s, the t
+// the previous depth buffer holds for a ray through (fx, fy) that meets the same world point.  false: no history (behind the previous
+// camera, outside its frame by a pixel or more, or a NaN anywhere -- every comparison is false for NaN).
+__host__ __device__ inline bool temporal_project(const TemporalPlan &pl, uint32_t i, uint32_t j, float depth, float &fx, float &fy, float &s) {
+    if (pl.is_static) {
+        fx = (float)i; fy = (float)j; s = depth;
+    } else {
+        float dir[3];
+        pixel_ray_dir(pl.cam, i, j, pl.ox, pl.oy, dir[0], dir[1], dir[2]);
+        float d[3];
+        for (int k = 0; k < 3; k++) {
+            const float P = pl.cam.origin[k] + dir[k] * depth;
+            d[k] = P - pl.po[k];
+        }
+        s = temporal_dot(d, pl.n) / pl.pn;
+        fx = ((temporal_dot(d, pl.a) / s - pl.pa) / pl.ua) - pl.ox;
+        fy = ((temporal_dot(d, pl.b) / s - pl.pb) / pl.vb) - pl.oy;
+    }
+    return s > 0.0f && fx > -1.0f && fx < (float)pl.w && fy > -1.0f && fy < (float)pl.h;
+}
+
+// Does previous pixel q (inside the frame) count as history for a centre with normal `np`, object `id` and reprojected depth s?
+__host__ __device__ inline bool temporal_tap_ok(const TemporalPlan &pl, const TemporalHistory &hs, size_t q, float s, const float *np, int32_t id) {
+    if (!(hs.len[q] > 0.0f)) return false;                                               // (a hole: 0, or NaN)
+    if (pl.terms & TEMPORAL_DEPTH) {
+        if (!(__builtin_fabsf(hs.depth[q] - s) <= pl.depth_tol * s)) return false;
+    }
+    if (pl.terms & TEMPORAL_NORMAL) {
+        if (!(temporal_dot(np, hs.normal + 3 * q) >= pl.normal_cos)) return false;
+    }
+    if ((pl.terms & TEMPORAL_IDX) && hs.idx[q] != id) return false;
+    return true;
+}
+
+// One tap: skipped outside the frame, when it fails a term, and when its weight is not > 0 (the a-trous filter's rule, rtw_atrous.h: for
+// finite values no bit changes, and a tap of weight 0 cannot enter as 0 * NaN).
+__host__ __device__ inline void temporal_tap(const TemporalPlan &pl, const TemporalHistory &hs, int qx, int qy, float wt, float s, const float *np,
+                                             int32_t id, TemporalSum &t) {
+    if (qx < 0 || qy < 0 || qx >= (int)pl.w || qy >= (int)pl.h) return;
+    const size_t q = (size_t)qy * pl.w + (size_t)qx;
+    if (!temporal_tap_ok(pl, hs, q, s, np, id)) return;
+    if (wt > 0.0f) {
+        t.w = t.w + wt;
+        t.c0 = t.c0 + wt * hs.color[3 * q];
+        t.c1 = t.c1 + wt * hs.color[3 * q + 1];
+        t.c2 = t.c2 + wt * hs.color[3 * q + 2];
+        t.m1 = t.m1 + wt * hs.moments[2 * q];
+        t.m2 = t.m2 + wt * hs.moments[2 * q + 1];
+        t.len = t.len + wt * hs.len[q];
+    }
+}
+
+// 1 / n_, raised to `floor_` when below it
+__host__ __device__ inline float temporal_blend_factor(float n_, float floor_) {
+    const float a_ = 1.0f / n_;
+    return a_ < floor_ ? floor_ : a_;
+}
+
+// Pixel (i, j).  o.color may be f.cur: the pixel's own cur is read before anything is written.
+__host__ __device__ inline void temporal_pixel(const TemporalPlan &pl, const TemporalFrame &f, const TemporalHistory &hs, const TemporalOut &o,
+                                               uint32_t i, uint32_t j) {
+    const size_t p = (size_t)j * pl.w + (size_t)i;
+    const float r = f.cur[3 * p], g = f.cur[3 * p + 1], b = f.cur[3 * p + 2];
+    const float L = (0.2126f * r + 0.7152f * g) + 0.0722f * b;
+    const bool fin = temporal_finite(r) && temporal_finite(g) && temporal_finite(b);
+
+    TemporalSum t = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+    float fx, fy, s;
+    if (pl.has_prev && temporal_project(pl, i, j, f.depth[p], fx, fy, s)) {
+        float np[3] = { 0.0f, 0.0f, 0.0f };
+        if (pl.terms & TEMPORAL_NORMAL) { np[0] = f.normal[3 * p]; np[1] = f.normal[3 * p + 1]; np[2] = f.normal[3 * p + 2]; }
+        const int32_t id = (pl.terms & TEMPORAL_IDX) ? f.idx[p] : 0;
+        if (pl.is_static) {
+            temporal_tap(pl, hs, (int)i, (int)j, 1.0f, s, np, id, t);                  // wx = wy = 0: the other three weigh 0
+        } else {
+            const float xf = __builtin_floorf(fx), yf = __builtin_floorf(fy);
+            const float wx = fx - xf, wy = fy - yf;
+            const int x0 = (int)xf, y0 = (int)yf;                                      // -1 .. w - 1, -1 .. h - 1
+            const float ux = 1.0f - wx, uy = 1.0f - wy;
+            temporal_tap(pl, hs, x0, y0, ux * uy, s, np, id, t);
+            temporal_tap(pl, hs, x0 + 1, y0, wx * uy, s, np, id, t);
+            temporal_tap(pl, hs, x0, y0 + 1, ux * wy, s, np, id, t);
+            temporal_tap(pl, hs, x0 + 1, y0 + 1, wx * wy, s, np, id, t);
+        }
+    }
+
+    float c0 = r, c1 = g, c2 = b, m1, m2, len;
+    if (t.w > 0.0f) {
+        const float h0 = t.c0 / t.w, h1 = t.c1 / t.w, h2 = t.c2 / t.w, hm1 = t.m1 / t.w, hm2 = t.m2 / t.w, hlen = t.len / t.w;
+        if (fin) {
+            const float n1 = hlen + 1.0f;
+            const float n_ = n1 < pl.max_history ? n1 : pl.max_history;
+            const float a_ = temporal_blend_factor(n_, pl.alpha), am_ = temporal_blend_factor(n_, pl.alpha_moments);
+            c0 = h0 + (r - h0) * a_;
+            c1 = h1 + (g - h1) * a_;
+            c2 = h2 + (b - h2) * a_;
+            m1 = hm1 + (L - hm1) * am_;
+            m2 = hm2 + (L * L - hm2) * am_;
+            len = n_;
+        } else {                                                                         // one bad sample does not enter
+            c0 = h0; c1 = h1; c2 = h2; m1 = hm1; m2 = hm2; len = hlen;
+        }
+    } else if (fin) {
+        m1 = L; m2 = L * L; len = 1.0f;
+    } else {                                                                             // len 0: no later frame reads this pixel as history
+        m1 = 0.0f; m2 = 0.0f; len = 0.0f;
+    }
+    o.color[3 * p] = c0; o.color[3 * p + 1] = c1; o.color[3 * p + 2] = c2;
+    o.moments[2 * p] = m1; o.moments[2 * p + 1] = m2;
+    o.len[p] = len;
+    if (o.variance) {
+        const float v = m2 - m1 * m1;
+        o.variance[p] = v > 0.0f ? v : 0.0f;
+    }
+}
+
+// Everything rtw_temporal_accumulate refuses (rtw.h); fills `pl`.  RTW_OK or RTW_E_INVALID.  (rtw_temporal.cpp)
+int temporal_check(const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth, const float *normal, const int32_t *idx,
+                   const RtwCamera *prev_cam, const float *prev_color, const float *prev_moments, const float *prev_len, const float *prev_depth,
+                   const float *prev_normal, const int32_t *prev_idx, const RtwTemporal *p, const float *out_color, const float *out_moments,
+                   const float *out_len, TemporalPlan &pl);
+
+} // namespace rtw

@@ -1,0 +1,122 @@
+// rtw_temporal.hip -- temporal accumulation by reprojection (rtw_temporal.h) on the GPU: rtw_ctx_temporal_accumulate's
+// device path.
+//
+// One launch, one thread per pixel running temporal_pixel -- the host form's definition with the host form's plan, so its bytes.
+// Workgroup b covers the 32 x 8 pixels of tile (b % tiles_x, b / tiles_x): a wave is two rows of 32 pixels, so its loads of cur and of the
+// guides, and under a small camera move its four taps, fall on a few consecutive cache lines.  The taps are plain global loads: each
+// previous pixel is read by about four threads, all of them neighbours, and the reuse is the caches'.  With a static camera
+// (TemporalPlan.is_static, a launch-uniform branch) a thread reads the one tap under it.  Results go straight into the caller's buffers
+// when those are device memory; host buffers are staged.
+#include "rtw_temporal_dev.h"
+#include "rtw_temporal.h"
+#include "rtw_devmem.h"
+
+#include <chrono>
+#include <new>
+
+namespace rtw {
+namespace {
+
+constexpr uint32_t TBX = 32, TBY = 8;                    // workgroup: 32 x 8 pixels, a wave covers two rows of 32
+
+// (f.cur and o.color may be the same buffer: no __restrict__ here)
+__global__ void __launch_bounds__(TBX * TBY) temporal_kernel(TemporalPlan pl, uint32_t tiles_x, TemporalFrame f, TemporalHistory hs, TemporalOut o) {
+    const uint32_t x = (blockIdx.x % tiles_x) * TBX + threadIdx.x % TBX;
+    const uint32_t y = (blockIdx.x / tiles_x) * TBY + threadIdx.x / TBX;
+    if (x < pl.w && y < pl.h) temporal_pixel(pl, f, hs, o, x, y);
+}
+
+float event_ms(hipEvent_t a, hipEvent_t b) {
+    float ms = 0.0f;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f;
+}
+
+} // namespace
+
+struct TemporalScratch {
+    DevMem cur, depth, normal, idx;                                      // the caller's host buffers, staged
+    DevMem prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx;
+    DevMem out_color, out_moments, out_len, out_variance;                // a result whose buffer is host memory
+    hipEvent_t ev[2] = { nullptr, nullptr };
+};
+
+void temporal_scratch_free(TemporalScratch *s) {
+    if (!s) return;
+    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
+    delete s;                                      // (the buffers free themselves)
+}
+
+#define TEMPORAL_TRY(expr)                                                                                                        \
+    do {                                                                                                                          \
+        hipError_t e_ = (expr);                                                                                                   \
+        if (e_ != hipSuccess) { *last_hip = (int)e_; return e_ == hipErrorOutOfMemory ? RTW_E_NOMEM : RTW_E_HIP; } \
+    } while (0)
+
+int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch **scratch, uint32_t w, uint32_t h, const RtwCamera *cam,
+                               const RtwCamera *prev_cam, const TemporalBuffers &b, const RtwTemporal *p, RtwFilterStats *stats, int *last_hip) {
+    const auto t0 = std::chrono::steady_clock::now();
+    TemporalPlan pl;
+    const int rc = temporal_check(b.cur, w, h, cam, b.depth, b.normal, b.idx, prev_cam, b.prev_color, b.prev_moments, b.prev_len, b.prev_depth,
+                                  b.prev_normal, b.prev_idx, p, b.out_color, b.out_moments, b.out_len, pl);
+    if (rc != RTW_OK) return rc;
+    TEMPORAL_TRY(hipSetDevice(device));
+    if (!*scratch) {
+        TemporalScratch *s = new (std::nothrow) TemporalScratch();
+        if (!s) return RTW_E_NOMEM;
+        *scratch = s;
+        for (hipEvent_t &e : s->ev) TEMPORAL_TRY(hipEventCreate(&e));
+    }
+    TemporalScratch *s = *scratch;
+    const size_t n_px = (size_t)w * h, f1 = n_px * sizeof(float), f2 = 2 * f1, f3 = 3 * f1;
+
+    // the caller's buffers on the device: a host one is staged; a guide whose term is off is not touched
+    TemporalFrame f = { b.cur, b.depth, (pl.terms & TEMPORAL_NORMAL) ? b.normal : nullptr, (pl.terms & TEMPORAL_IDX) ? b.idx : nullptr };
+    TemporalHistory hs = { b.prev_color, b.prev_moments, b.prev_len, (pl.terms & TEMPORAL_DEPTH) ? b.prev_depth : nullptr,
+                           (pl.terms & TEMPORAL_NORMAL) ? b.prev_normal : nullptr, (pl.terms & TEMPORAL_IDX) ? b.prev_idx : nullptr };
+    struct Stage { const void **p; DevMem *m; size_t bytes; };
+    const Stage stages[10] = { { (const void **)&f.cur, &s->cur, f3 },
+                               { (const void **)&f.depth, &s->depth, f1 },
+                               { (const void **)&f.normal, &s->normal, f3 },
+                               { (const void **)&f.idx, &s->idx, n_px * sizeof(int32_t) },
+                               { (const void **)&hs.color, &s->prev_color, f3 },
+                               { (const void **)&hs.moments, &s->prev_moments, f2 },
+                               { (const void **)&hs.len, &s->prev_len, f1 },
+                               { (const void **)&hs.depth, &s->prev_depth, f1 },
+                               { (const void **)&hs.normal, &s->prev_normal, f3 },
+                               { (const void **)&hs.idx, &s->prev_idx, n_px * sizeof(int32_t) } };
+    for (const Stage &st : stages) {
+        if (!*st.p || on_device(*st.p, device)) continue;
+        TEMPORAL_TRY(st.m->reserve(st.bytes));
+        TEMPORAL_TRY(hipMemcpyAsync(st.m->ptr, *st.p, st.bytes, hipMemcpyDefault, stream));
+        *st.p = st.m->ptr;
+    }
+    TemporalOut o = { b.out_color, b.out_moments, b.out_len, b.out_variance };
+    struct Result { float **p; float *host; DevMem *m; size_t bytes; };
+    Result results[4] = { { &o.color, nullptr, &s->out_color, f3 },
+                          { &o.moments, nullptr, &s->out_moments, f2 },
+                          { &o.len, nullptr, &s->out_len, f1 },
+                          { &o.variance, nullptr, &s->out_variance, f1 } };
+    for (Result &r : results) {
+        if (!*r.p || on_device(*r.p, device)) continue;
+        TEMPORAL_TRY(r.m->reserve(r.bytes));
+        r.host = *r.p;
+        *r.p = r.m->as<float>();
+    }
+
+    const uint32_t tiles_x = (w + TBX - 1) / TBX, tiles_y = (h + TBY - 1) / TBY;
+    TEMPORAL_TRY(hipEventRecord(s->ev[0], stream));
+    hipLaunchKernelGGL(temporal_kernel, dim3((unsigned)((uint64_t)tiles_x * tiles_y)), dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o);
+    TEMPORAL_TRY(hipGetLastError());
+    TEMPORAL_TRY(hipEventRecord(s->ev[1], stream));
+    for (const Result &r : results)
+        if (r.host) TEMPORAL_TRY(hipMemcpyAsync(r.host, *r.p, r.bytes, hipMemcpyDefault, stream));
+    TEMPORAL_TRY(hipStreamSynchronize(stream));
+    if (stats) {
+        const float total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        *stats = RtwFilterStats{ 0.0f, 0.0f, 0.0f, 0.0f, event_ms(s->ev[0], s->ev[1]), total, 4ull * w * h };
+    }
+    return RTW_OK;
+}
+#undef TEMPORAL_TRY
+
+} // namespace rtw
