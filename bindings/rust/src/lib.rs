@@ -77,6 +77,15 @@ pub struct RtwGuidedFilter { pub base: RtwBilateral, pub sigma_depth: f32, pub s
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct RtwAtrous { pub levels: u32, pub sigma_color: f32, pub sigma_depth: f32, pub sigma_normal: f32, pub same_object: u32, pub albedo_floor: f32 }
 pub const RTW_ATROUS_MAX_LEVELS: u32 = 8;
+/// Arguments of the variance estimate (include/rtw.h): the history length below which a pixel takes the spatial estimate (1 = never), its
+/// window's radius (1..3), the two sigmas (0 = term off) and same_object.
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RtwVarianceEstimate { pub min_history: u32, pub radius: u32, pub sigma_depth: f32, pub sigma_normal: f32, pub same_object: u32 }
+pub const RTW_VARIANCE_MAX_RADIUS: u32 = 3;
+/// What the variance-steered a-trous filter takes beside `RtwAtrous` (include/rtw.h): sigma_luminance (0 = term off), epsilon (> 0) and
+/// prefilter (1 = the centre's variance is its 3 x 3 Gaussian mean).
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RtwSvgf { pub sigma_luminance: f32, pub epsilon: f32, pub prefilter: u32 }
 /// `RTW_OPT_ATROUS_LAYOUT` (rtw.h): where a level of the a-trous filter reads its taps (0 the measured choice, 1 LDS tile, 2 global memory).
 pub const RTW_OPT_ATROUS_LAYOUT: u32 = 14;
 /// The ray rules of `rtw_ctx_surface_map` (rtw.h).
@@ -178,6 +187,16 @@ extern "C" {
                          emitted: *const f32, p: *const RtwAtrous, out: *mut f32, st: *mut RtwFilterStats) -> i32;
     fn rtw_ctx_atrous_filter(ctx: *mut RtwCtx, img: *const f32, w: u32, h: u32, depth: *const f32, normal: *const f32, idx: *const i32,
                              albedo: *const f32, emitted: *const f32, p: *const RtwAtrous, out: *mut f32, st: *mut RtwFilterStats) -> i32;
+    fn rtw_variance_estimate(moments: *const f32, len: *const f32, w: u32, h: u32, depth: *const f32, normal: *const f32, idx: *const i32,
+                             p: *const RtwVarianceEstimate, out: *mut f32, st: *mut RtwFilterStats) -> i32;
+    fn rtw_ctx_variance_estimate(ctx: *mut RtwCtx, moments: *const f32, len: *const f32, w: u32, h: u32, depth: *const f32, normal: *const f32,
+                                 idx: *const i32, p: *const RtwVarianceEstimate, out: *mut f32, st: *mut RtwFilterStats) -> i32;
+    fn rtw_svgf_filter(img: *const f32, variance: *const f32, w: u32, h: u32, depth: *const f32, normal: *const f32, idx: *const i32,
+                       albedo: *const f32, emitted: *const f32, p: *const RtwAtrous, vp: *const RtwSvgf, out: *mut f32, out_variance: *mut f32,
+                       st: *mut RtwFilterStats) -> i32;
+    fn rtw_ctx_svgf_filter(ctx: *mut RtwCtx, img: *const f32, variance: *const f32, w: u32, h: u32, depth: *const f32, normal: *const f32,
+                           idx: *const i32, albedo: *const f32, emitted: *const f32, p: *const RtwAtrous, vp: *const RtwSvgf, out: *mut f32,
+                           out_variance: *mut f32, st: *mut RtwFilterStats) -> i32;
     fn rtw_triangle_new(origin: *const f32, u: *const f32, v: *const f32, mat3: *const f32, emitted: *const f32,
                         color: *const f32, tex: i32, out: *mut RtwTriangle) -> i32;
     fn rtw_ctx_set_triangles(ctx: *mut RtwCtx, tris: *const RtwTriangle, n: u32) -> i32;
@@ -446,6 +465,27 @@ impl Renderer {
         check(unsafe { rtw_ctx_atrous_filter(self.ctx, rgb, w, h, depth, normal, idx, albedo, emitted, p, out.as_mut_ptr(), &mut st) })?;
         Ok((out, st))
     }
+    /// The variance estimate on this context's GPU (rtw_ctx_variance_estimate): moments [h][w][2] and len [h][w] as the temporal
+    /// accumulation writes them, the guides of `atrous_filter`; each host or device memory, a guide null where its term is off.
+    pub fn variance_estimate(&mut self, moments: *const f32, len: *const f32, w: u32, h: u32, depth: *const f32, normal: *const f32,
+                             idx: *const i32, p: &RtwVarianceEstimate) -> Result<(Vec<f32>, RtwFilterStats), RtwError> {
+        let mut out = vec![0f32; w as usize * h as usize];
+        let mut st = RtwFilterStats::default();
+        check(unsafe { rtw_ctx_variance_estimate(self.ctx, moments, len, w, h, depth, normal, idx, p, out.as_mut_ptr(), &mut st) })?;
+        Ok((out, st))
+    }
+    /// The variance-steered a-trous filter on this context's GPU (rtw_ctx_svgf_filter): `atrous_filter`'s arguments and a variance
+    /// [h][w] f32; returns the filtered frame, the filtered variance and the stats.
+    #[allow(clippy::type_complexity)]
+    pub fn svgf_filter(&mut self, rgb: *const f32, variance: *const f32, w: u32, h: u32, depth: *const f32, normal: *const f32, idx: *const i32,
+                       albedo: *const f32, emitted: *const f32, p: &RtwAtrous, vp: &RtwSvgf) -> Result<(Vec<f32>, Vec<f32>, RtwFilterStats), RtwError> {
+        let n = w as usize * h as usize;
+        let (mut out, mut var) = (vec![0f32; 3 * n], vec![0f32; n]);
+        let mut st = RtwFilterStats::default();
+        check(unsafe { rtw_ctx_svgf_filter(self.ctx, rgb, variance, w, h, depth, normal, idx, albedo, emitted, p, vp, out.as_mut_ptr(),
+                                           var.as_mut_ptr(), &mut st) })?;
+        Ok((out, var, st))
+    }
     /// What a camera sees (rtw_ctx_surface_map): (depth, idx, normal, albedo, emitted, material) of every pixel's first surface under
     /// `integrator`, rays by `ray_rule` (`RTW_RAYS_PIXEL` with `offset` inside the pixel for Viewport cameras).
     #[allow(clippy::type_complexity)]
@@ -603,6 +643,29 @@ pub fn atrous_filter_host(rgb: &[f32], w: u32, h: u32, depth: &[f32], normal: &[
     let ids = if idx.is_empty() { std::ptr::null() } else { idx.as_ptr() };
     check(unsafe { rtw_atrous_filter(rgb.as_ptr(), w, h, f(depth), f(normal), ids, f(albedo), f(emitted), p, out.as_mut_ptr(), std::ptr::null_mut()) })?;
     Ok(out)
+}
+
+/// rtw_variance_estimate: the host form of the variance estimate (a guide whose term is off may be empty).
+pub fn variance_estimate_host(moments: &[f32], len: &[f32], w: u32, h: u32, depth: &[f32], normal: &[f32], idx: &[i32],
+                              p: &RtwVarianceEstimate) -> Result<Vec<f32>, RtwError> {
+    let mut out = vec![0f32; len.len()];
+    let f = |s: &[f32]| if s.is_empty() { std::ptr::null() } else { s.as_ptr() };
+    let ids = if idx.is_empty() { std::ptr::null() } else { idx.as_ptr() };
+    check(unsafe { rtw_variance_estimate(f(moments), f(len), w, h, f(depth), f(normal), ids, p, out.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok(out)
+}
+
+/// rtw_svgf_filter: the host form of the variance-steered a-trous filter, (frame, variance) (a guide whose term is off, albedo and emitted
+/// may be empty).
+#[allow(clippy::too_many_arguments)]
+pub fn svgf_filter_host(rgb: &[f32], variance: &[f32], w: u32, h: u32, depth: &[f32], normal: &[f32], idx: &[i32], albedo: &[f32],
+                        emitted: &[f32], p: &RtwAtrous, vp: &RtwSvgf) -> Result<(Vec<f32>, Vec<f32>), RtwError> {
+    let (mut out, mut var) = (vec![0f32; rgb.len()], vec![0f32; variance.len()]);
+    let f = |s: &[f32]| if s.is_empty() { std::ptr::null() } else { s.as_ptr() };
+    let ids = if idx.is_empty() { std::ptr::null() } else { idx.as_ptr() };
+    check(unsafe { rtw_svgf_filter(f(rgb), f(variance), w, h, f(depth), f(normal), ids, f(albedo), f(emitted), p, vp, out.as_mut_ptr(),
+                                   var.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok((out, var))
 }
 
 /// rtw_pixel_rays: the pixel rays of a Viewport camera at `offset` inside the pixel, [h * w][6] = origin, direction (not normalised).

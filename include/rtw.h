@@ -324,7 +324,8 @@ enum {
                                      same.  Any other value: RTW_E_INVALID.  (added within v4)                                              */
     RTW_OPT_ATROUS_LAYOUT    = 14,/* where a level of rtw_ctx_atrous_filter reads its taps: 0 (default) the measured choice per level
                                      (DESIGN.md 8c); 1 from an LDS tile of the workgroup's pixels and their halo wherever that tile fits; 2 from
-                                     global memory.  The bytes are the same.  Any other value: RTW_E_INVALID.  (added within v4)          */
+                                     global memory.  The bytes are the same.  Any other value: RTW_E_INVALID.  (added within v4)
+                                     rtw_ctx_svgf_filter's levels and rtw_ctx_variance_estimate's window follow it too.    */
 };
 int  rtw_ctx_set_option(rtw_ctx *ctx, uint32_t key, double value);
 /* Which compiled build of the render kernel the context's last render launched, as text in template-argument order:
@@ -618,6 +619,86 @@ int rtw_ctx_temporal_accumulate(rtw_ctx *ctx, const float *cur, uint32_t w, uint
                                 const float *prev_moments, const float *prev_len, const float *prev_depth, const float *prev_normal,
                                 const int32_t *prev_idx, const RtwTemporal *params, float *out_color, float *out_moments, float *out_len,
                                 float *out_variance /* may be NULL */, RtwFilterStats *stats);
+
+/* ---- variance estimate: a luminance variance for every pixel of an accumulated frame -- added within v4 ---------------------------------
+ * SVGF's variance estimation (Schied et al. 2017, section 4.2): where the history is long enough the variance over time that the two
+ * accumulated moments hold, elsewhere (a first frame, a disocclusion) a variance over space from the moments of the neighbours on the same
+ * surface, raised by how short the history is.  moments [h][w][2] f32 and len [h][w] f32 are rtw_temporal_accumulate's out_moments and
+ * out_len; depth, normal, idx the guides of the same frame, as the a-trous filter reads them; out [h][w] f32.  Everything is f32 with one
+ * rounding per written operation (no fused multiply-add), exp_plain is rtw_exp_plain's.  Pixel p, n = len[p], (m1, m2) = moments[p]:
+ *   n >= min_history:   V = m2 - m1*m1;  out[p] = V > 0 ? V : 0      (rtw_temporal_accumulate's out_variance, byte for byte)
+ *   otherwise (also a NaN n):  the taps q = p + (dx, dy), dy = -radius..radius outer, dx = -radius..radius inner (the centre among them),
+ *   skipping those outside the frame and those with !(len[q] > 0);  a = 0
+ *     if sigma_depth  > 0:  dz = depth[q] - depth[p];    a = a + inv_depth * (dz * dz)
+ *     if sigma_normal > 0:  d = normal[q] - normal[p];   a = a + inv_normal * ((d.x*d.x + d.y*d.y) + d.z*d.z)
+ *     g = (a >= 0) ? exp_plain(-a) : 0;   if same_object and idx[q] != idx[p]:  g = 0
+ *     if g > 0:  s1 = s1 + g * m1[q];  s2 = s2 + g * m2[q];  ws = ws + g
+ *   (the a-trous filter's weight with its colour term off and its depth scale 1, inv_x = 0.5f / (sigma_x * sigma_x))
+ *   ws > 0:   M1 = s1 / ws;  M2 = s2 / ws;  V = M2 - M1*M1;  V = V > 0 ? V : 0;  out[p] = V * ((float)min_history / (n >= 1 ? n : 1))
+ *   else:     out[p] = 0
+ * min_history == 1 sends every pixel with len >= 1 down the first branch: the spatial estimate is off.  A guide whose term is off may be
+ * NULL and is never read.
+ * RTW_E_INVALID, nothing written: moments, len, out or params NULL; w or h zero or beyond RTW_ATROUS_MAX_SIDE, or w * h beyond 32 bits;
+ * min_history outside 1 .. 65535; radius outside 1 .. RTW_VARIANCE_MAX_RADIUS; a sigma that is negative or not finite, or so small that
+ * its inv_* is not finite; sigma_depth > 0 with depth NULL, sigma_normal > 0 with normal NULL, same_object with idx NULL; same_object > 1;
+ * out == moments or out == len (neighbours gather from both).  There is no rtw_mgpu_* form and no JSON form. */
+#define RTW_VARIANCE_MAX_RADIUS 3u
+typedef struct RtwVarianceEstimate {
+    uint32_t min_history;           /* 1 .. 65535: a pixel with len below it takes the spatial estimate; 1 = never      */
+    uint32_t radius;                /* 1 .. RTW_VARIANCE_MAX_RADIUS: the spatial window is (2 radius + 1)^2 pixels      */
+    float    sigma_depth;           /* 0 = no depth term; else in the units of `depth`                                 */
+    float    sigma_normal;          /* 0 = no normal term; else in units of |n - n'|                                   */
+    uint32_t same_object;           /* 1 = a tap on another idx weighs 0                                               */
+} RtwVarianceEstimate;
+/* The host form (one thread).  RtwFilterStats: filter_ms and total_ms are the call's time, taps counts the window entries inside the
+ * frame, the other fields are 0. */
+int rtw_variance_estimate(const float *moments, const float *len, uint32_t w, uint32_t h, const float *depth, const float *normal,
+                          const int32_t *idx, const RtwVarianceEstimate *params, float *out, RtwFilterStats *stats);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host form.  Every buffer may independently be host memory or device memory of
+ * ctx's GPU (host memory is staged).  One launch, one thread per pixel, the window read from an LDS tile or from global memory
+ * (RTW_OPT_ATROUS_LAYOUT); filter_ms is its device time.  Needs no scene and leaves the scene, and every render, untouched. */
+int rtw_ctx_variance_estimate(rtw_ctx *ctx, const float *moments, const float *len, uint32_t w, uint32_t h, const float *depth,
+                              const float *normal, const int32_t *idx, const RtwVarianceEstimate *params, float *out,
+                              RtwFilterStats *stats);
+
+/* ---- variance-steered a-trous filter: SVGF's filter stage -- added within v4 -----------------------------------------------------------
+ * rtw_atrous_filter with a variance channel beside the colour (Schied et al. 2017, section 4.4): a luminance term whose width follows
+ * the pixel's own variance, so that a pixel that has converged is left alone and a noisy one is filtered hard, and the variance itself
+ * filtered by the squared weights so that the next level sees what the last one left.  variance [h][w] f32 is what rtw_variance_estimate
+ * writes (the variance of the luminance of `in`); out_variance [h][w] f32 may be NULL.  Everything else is rtw_atrous_filter's, params
+ * included: its sigma_color term stays available, and sigma_color = 0 steers by the variance alone.
+ * With lum(c) = (0.2126f c.r + 0.7152f c.g) + 0.0722f c.b:
+ *   demodulate:  C0 as rtw_atrous_filter;  la = lum(a) of its a_c (exactly 1 without albedo);
+ *                V0[p] = variance[p] > 0 ? variance[p] / (la*la) : 0          (NaN and negatives become 0, +inf stays)
+ *   level i, centre p, when sigma_luminance > 0:
+ *     prefilter:  vbar = (sum G[|dx|] G[|dy|] Vi[q]) / (sum G[|dx|] G[|dy|]) over the q = p + (dx, dy) inside the frame, dy = -1..1
+ *                 outer, dx = -1..1 inner, G = {1/2, 1/4}; the step is 1 at every level.  Without prefilter:  vbar = Vi[p]
+ *     den = sl2 * vbar + epsilon,   sl2 = 2 * sigma_luminance * sigma_luminance formed once per call
+ *   each of the 25 taps q:  a as rtw_atrous_filter forms it (colour, depth, normal, in this order), then
+ *     if sigma_luminance > 0:  dl = lum(Ci[q]) - lum(Ci[p]);  a = a + (dl*dl) / den
+ *     g, wt as rtw_atrous_filter;   if wt > 0:  its sums, and  vs = vs + (wt*wt) * Vi[q]
+ *   Ci+1[p] as rtw_atrous_filter;   Vi+1[p] = wsum > 0 ? vs / (wsum*wsum) : Vi[p]
+ *   remodulate:  out as rtw_atrous_filter;   out_variance[p] = V_levels[p] * (la*la)
+ * The luminance term is Gaussian in dl, dl^2 / (2 sigma^2 v), where SVGF has |dl| / (sigma sqrt(v)): deliberately, so that it has the
+ * shape of the other three terms and needs no square root.  With sigma_luminance = 0 `out` holds rtw_atrous_filter's bytes.
+ * `out` may be `in`.
+ * RTW_E_INVALID, nothing written: everything rtw_atrous_filter refuses; variance or vparams NULL; sigma_luminance negative or not finite,
+ * or so large that sl2 is not finite; epsilon not finite or not > 0; prefilter > 1; out_variance == variance, in or out.
+ * There is no rtw_mgpu_* form and no JSON form. */
+typedef struct RtwSvgf {
+    float    sigma_luminance;       /* 0 = no luminance term; else in standard deviations of the pixel's luminance      */
+    float    epsilon;               /* > 0: added to the scaled variance, so that a variance of 0 does not divide by 0   */
+    uint32_t prefilter;             /* 1 = the centre's variance is the 3 x 3 Gaussian mean of its neighbourhood         */
+} RtwSvgf;
+/* The host form (one thread).  RtwFilterStats as rtw_atrous_filter. */
+int rtw_svgf_filter(const float *in, const float *variance, uint32_t w, uint32_t h, const float *depth, const float *normal,
+                    const int32_t *idx, const float *albedo, const float *emitted, const RtwAtrous *params, const RtwSvgf *vparams,
+                    float *out, float *out_variance /* may be NULL */, RtwFilterStats *stats);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host form; buffers as rtw_ctx_atrous_filter, whose scratch it shares and grows
+ * by two variance planes.  One launch per level (RTW_OPT_ATROUS_LAYOUT); filter_ms is the device time of all launches. */
+int rtw_ctx_svgf_filter(rtw_ctx *ctx, const float *in, const float *variance, uint32_t w, uint32_t h, const float *depth,
+                        const float *normal, const int32_t *idx, const float *albedo, const float *emitted, const RtwAtrous *params,
+                        const RtwSvgf *vparams, float *out, float *out_variance /* may be NULL */, RtwFilterStats *stats);
 
 /* ---- Rust2 triangles (Rust2/src/objects/triangle.rs) ----------------------------------------------------------------------------
  * `Triangle{origin, u, v, mat, texture}` with the derived fields of Triangle::new (:28-50): n = u x v, normal = unit(n),

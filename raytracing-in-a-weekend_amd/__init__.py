@@ -20,6 +20,8 @@ Reference surface mirrored (names and argument meaning):
   (extension) guided_filter(img, size, depth=, normal=, ids=, ..)   the bilateral filter steered by depth_map's buffers (Renderer.guided_filter)
   (extension) atrous_filter(frame, depth=, normal=, ids=, albedo=, emitted=, ..)   an edge-avoiding a-trous wavelet filter of linear f32 frames (Renderer.atrous_filter)
   (extension) temporal_accumulate(cur, cam, depth=, normal=, ids=, history=, ..)   frames of a sequence blended along reprojected pixels (Renderer.temporal_accumulate, TemporalDenoiser)
+  (extension) variance_estimate(moments, length, depth=, normal=, ids=, ..)   a luminance variance for every pixel of an accumulated frame (Renderer.variance_estimate)
+  (extension) svgf_filter(frame, variance, depth=, normal=, ids=, albedo=, emitted=, ..)   the a-trous filter steered by that variance (Renderer.svgf_filter, SvgfDenoiser)
   Triangle.new (+ from_mesh), Scene(triangles=)       Rust2/src/objects/triangle.rs:28-124 (triangle_hits; Renderer.triangle_hits)
 
 The directory name carries a hyphen (it is fixed by the build contract); import it with
@@ -73,6 +75,13 @@ TEMPORAL_MAX_SIDE = 65535
 # profiles/temporal.log); max_history and same_object were not swept
 TEMPORAL_DEFAULTS = {"alpha": 0.1, "alpha_moments": 0.1, "max_history": 32, "depth_tol": 0.05, "normal_cos": 0.9, "same_object": 1}
 ATROUS_DEFAULTS = {"levels": 3, "sigma_color": 1.0, "sigma_depth": 0.25, "sigma_normal": 0.3, "albedo_floor": 1e-3}
+VARIANCE_MAX_RADIUS = 3
+# Renderer.variance_estimate's, Renderer.svgf_filter's and SvgfDenoiser's defaults: levels, sigma_luminance, min_history and prefilter are the
+# best row, by the orbit's mean over frames 8..15, of the sweep on the 4-spp Book-1 orbit (profiles/svgf.log); the guide
+# sigmas and the floor are the a-trous filter's, sigma_color is off, radius and epsilon were not swept
+SVGF_DEFAULTS = {"levels": 3, "sigma_luminance": 1.0, "epsilon": 1e-8, "prefilter": False, "min_history": 4, "radius": 3, "sigma_color": 0.0,
+                 "sigma_depth": ATROUS_DEFAULTS["sigma_depth"], "sigma_normal": ATROUS_DEFAULTS["sigma_normal"],
+                 "albedo_floor": ATROUS_DEFAULTS["albedo_floor"]}
 
 # materials.rs:157-212 presets as (metallicness, opacity, ir)
 METALLIC_M = (1.0, 0.0, 1.0)
@@ -191,6 +200,18 @@ class RtwTemporal(C.Structure):
     and the pixel offset of both frames' guides (include/rtw.h)."""
     _fields_ = [("alpha", C.c_float), ("alpha_moments", C.c_float), ("max_history", C.c_uint32), ("depth_tol", C.c_float),
                 ("normal_cos", C.c_float), ("same_object", C.c_uint32), ("offset", C.c_float * 2)]
+
+
+class RtwVarianceEstimate(C.Structure):
+    """Arguments of the variance estimate: the history length below which a pixel takes the spatial estimate, its window's radius, the two
+    sigmas (0 = term off) and same_object (include/rtw.h)."""
+    _fields_ = [("min_history", C.c_uint32), ("radius", C.c_uint32), ("sigma_depth", C.c_float), ("sigma_normal", C.c_float),
+                ("same_object", C.c_uint32)]
+
+
+class RtwSvgf(C.Structure):
+    """What the variance-steered a-trous filter takes beside RtwAtrous: sigma_luminance (0 = term off), epsilon and prefilter (include/rtw.h)."""
+    _fields_ = [("sigma_luminance", C.c_float), ("epsilon", C.c_float), ("prefilter", C.c_uint32)]
 
 
 class RtwFilterStats(C.Structure):
@@ -420,6 +441,12 @@ def lib() -> C.CDLL:
     L.rtw_temporal_accumulate.argtypes = ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwCamera)] + [C.c_void_p] * 3 + [C.POINTER(RtwCamera)] +
                                           [C.c_void_p] * 6 + [C.POINTER(RtwTemporal)] + [C.c_void_p] * 4 + [C.POINTER(RtwFilterStats)])
     L.rtw_ctx_temporal_accumulate.argtypes = [C.c_void_p] + L.rtw_temporal_accumulate.argtypes
+    L.rtw_variance_estimate.argtypes = ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3 +
+                                        [C.POINTER(RtwVarianceEstimate), C.c_void_p, C.POINTER(RtwFilterStats)])
+    L.rtw_ctx_variance_estimate.argtypes = [C.c_void_p] + L.rtw_variance_estimate.argtypes
+    L.rtw_svgf_filter.argtypes = ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 +
+                                  [C.POINTER(RtwAtrous), C.POINTER(RtwSvgf), C.c_void_p, C.c_void_p, C.POINTER(RtwFilterStats)])
+    L.rtw_ctx_svgf_filter.argtypes = [C.c_void_p] + L.rtw_svgf_filter.argtypes
     L.rtw_exp_plain.argtypes = [fp, C.c_size_t, fp]
     L.rtw_cos_plain.argtypes = [fp, C.c_size_t, fp]
     L.rtw_ctx_device_math.argtypes = [C.c_void_p, C.c_uint32, fp, C.c_uint32, C.c_uint32, fp, C.c_uint32]
@@ -1943,6 +1970,34 @@ class Renderer:
         return _temporal_call(lib().rtw_ctx_temporal_accumulate, "rtw_ctx_temporal_accumulate", (self._h,), self._on_device, cur, cam, depth,
                               normal, ids, history, out_color, params)
 
+    def variance_estimate(self, moments, length, depth=None, normal=None, ids=None, min_history: int = SVGF_DEFAULTS["min_history"],
+                          radius: int = SVGF_DEFAULTS["radius"], sigma_depth: float = SVGF_DEFAULTS["sigma_depth"],
+                          sigma_normal: float = SVGF_DEFAULTS["sigma_normal"], same_object: bool = True, out=None):
+        """A luminance variance [h][w] for every pixel of an accumulated frame on this context's GPU (rtw_ctx_variance_estimate,
+        include/rtw.h): where length >= min_history the variance over time of the two moments, elsewhere the variance of the moments'
+        weighted mean over a (2 radius + 1)^2 window of pixels on the same surface, times min_history / length.  moments [h][w][2] and
+        length [h][w] float32: temporal_accumulate's history["moments"] and history["len"]; the guides and their terms as atrous_filter's.
+        min_history 1 turns the spatial estimate off.  Every argument is a numpy array (staged) or a contiguous torch tensor on the
+        context's device, read in place on the context's stream; `out`: None -> a new array or tensor like `moments`.  Returns
+        (variance, RtwFilterStats)."""
+        return _variance_call(lib().rtw_ctx_variance_estimate, "rtw_ctx_variance_estimate", (self._h,), self._on_device, moments, length, depth,
+                              normal, ids, min_history, radius, sigma_depth, sigma_normal, same_object, out)
+
+    def svgf_filter(self, frame, variance, depth=None, normal=None, ids=None, albedo=None, emitted=None, levels: int = SVGF_DEFAULTS["levels"],
+                    sigma_color: float = SVGF_DEFAULTS["sigma_color"], sigma_depth: float = SVGF_DEFAULTS["sigma_depth"],
+                    sigma_normal: float = SVGF_DEFAULTS["sigma_normal"], same_object: bool = True,
+                    albedo_floor: float = SVGF_DEFAULTS["albedo_floor"], sigma_luminance: float = SVGF_DEFAULTS["sigma_luminance"],
+                    epsilon: float = SVGF_DEFAULTS["epsilon"], prefilter: bool = SVGF_DEFAULTS["prefilter"], out=None, out_variance=None):
+        """The a-trous filter steered by a per-pixel variance on this context's GPU (rtw_ctx_svgf_filter, include/rtw.h): atrous_filter
+        with one more term in every tap's exponent, dl^2 / (2 sigma_luminance^2 vbar + epsilon) with dl the luminance difference and vbar
+        the centre's variance (its 3 x 3 Gaussian mean with prefilter), and the variance [h][w] filtered along by the squared weights.
+        variance: what variance_estimate returns.  Everything else, arrays and tensors included, as atrous_filter; sigma_luminance 0 gives
+        its bytes.  `out`, `out_variance`: None -> new arrays or tensors like `frame`; out may be `frame`, out_variance must be a buffer of
+        its own.  Returns (out, out_variance, RtwFilterStats)."""
+        return _svgf_call(lib().rtw_ctx_svgf_filter, "rtw_ctx_svgf_filter", (self._h,), self._on_device, frame, variance, depth, normal, ids,
+                          albedo, emitted, levels, sigma_color, sigma_depth, sigma_normal, same_object, albedo_floor, sigma_luminance, epsilon,
+                          prefilter, out, out_variance)
+
     def render(self, cam: RtwCamera, params: RtwParams, out=None):
         """Render into `out`: None -> new numpy array; numpy array -> host buffer; int -> raw device pointer
         (e.g. torch_tensor.data_ptr()) of [rows][width][3] f32.  Returns (out, RtwStats)."""
@@ -2285,6 +2340,112 @@ class TemporalDenoiser:
         if gamma != 1.0:
             frame = np.power(np.maximum(frame, np.float32(0.0)), np.float32(1.0 / gamma)).astype(np.float32)
         stats = dict(render=st, temporal=st_t, atrous=st_a, coverage=float((self.history["len"] > 1).mean()), cur=cur, guides=g)
+        return frame, acc, variance, stats
+
+
+def _like(a, shape):
+    """A new float32 array of `shape`, or a tensor on a's device when `a` is a tensor."""
+    if hasattr(a, "data_ptr"):
+        import torch
+        return torch.empty(shape, dtype=torch.float32, device=a.device)
+    return np.empty(shape, np.float32)
+
+
+def _variance_call(fn, fn_name, head, on_device, moments, length, depth, normal, ids, min_history, radius, sigma_depth, sigma_normal,
+                   same_object, out):
+    """rtw_variance_estimate / rtw_ctx_variance_estimate from the Python arguments of variance_estimate: (variance, stats)."""
+    who = "variance_estimate"
+    shp = tuple(length.shape) if hasattr(length, "shape") else np.shape(length)
+    if len(shp) != 2:
+        raise ValueError(f"{who}: length of shape {shp}, expected [h][w]")
+    h, w = int(shp[0]), int(shp[1])
+    keep = []
+    ptr = lambda name, a, dtype, shape, writable=False: _atrous_pointer(name, a, dtype, shape, on_device, keep, writable, who)
+    if out is None:
+        out = _like(moments, (h, w))
+    prm = RtwVarianceEstimate(int(min_history), int(radius), float(sigma_depth) if depth is not None else 0.0,
+                              float(sigma_normal) if normal is not None else 0.0, int(bool(same_object) and ids is not None))
+    args = [ptr("moments", moments, np.float32, (h, w, 2)), ptr("length", length, np.float32, (h, w)), w, h,
+            ptr("depth", depth, np.float32, (h, w)), ptr("normal", normal, np.float32, (h, w, 3)), ptr("ids", ids, np.int32, (h, w)),
+            C.byref(prm), ptr("out", out, np.float32, (h, w), True)]
+    st = RtwFilterStats()
+    _check(fn(*head, *args, C.byref(st)), fn_name)
+    return out, st
+
+
+def variance_estimate(moments, length, depth=None, normal=None, ids=None, min_history: int = SVGF_DEFAULTS["min_history"],
+                      radius: int = SVGF_DEFAULTS["radius"], sigma_depth: float = SVGF_DEFAULTS["sigma_depth"],
+                      sigma_normal: float = SVGF_DEFAULTS["sigma_normal"], same_object: bool = True, out=None):
+    """The variance estimate on the host (rtw_variance_estimate), the bytes of Renderer.variance_estimate; numpy arrays only.  Arguments and
+    result as there."""
+    return _variance_call(lib().rtw_variance_estimate, "rtw_variance_estimate", (), None, moments, length, depth, normal, ids, min_history, radius,
+                          sigma_depth, sigma_normal, same_object, out)
+
+
+def _svgf_call(fn, fn_name, head, on_device, frame, variance, depth, normal, ids, albedo, emitted, levels, sigma_color, sigma_depth, sigma_normal,
+               same_object, albedo_floor, sigma_luminance, epsilon, prefilter, out, out_variance):
+    """rtw_svgf_filter / rtw_ctx_svgf_filter from the Python arguments of svgf_filter: (out, out_variance, stats)."""
+    who = "svgf_filter"
+    args, h, w, keep = _atrous_arguments(frame, depth, normal, ids, albedo, emitted, on_device)
+    ptr = lambda name, a, dtype, shape, writable=False: _atrous_pointer(name, a, dtype, shape, on_device, keep, writable, who)
+    args.insert(1, ptr("variance", variance, np.float32, (h, w)))
+    if out is None:
+        out = _like(frame, (h, w, 3))
+    if out_variance is None:
+        out_variance = _like(frame, (h, w))
+    prm = _atrous_params(levels, sigma_color, sigma_depth, sigma_normal, same_object, albedo_floor, depth, normal, ids)
+    vprm = RtwSvgf(float(sigma_luminance), float(epsilon), int(bool(prefilter)))
+    st = RtwFilterStats()
+    _check(fn(*head, *args, C.byref(prm), C.byref(vprm), ptr("out", out, np.float32, (h, w, 3), True),
+              ptr("out_variance", out_variance, np.float32, (h, w), True), C.byref(st)), fn_name)
+    return out, out_variance, st
+
+
+def svgf_filter(frame, variance, depth=None, normal=None, ids=None, albedo=None, emitted=None, levels: int = SVGF_DEFAULTS["levels"],
+                sigma_color: float = SVGF_DEFAULTS["sigma_color"], sigma_depth: float = SVGF_DEFAULTS["sigma_depth"],
+                sigma_normal: float = SVGF_DEFAULTS["sigma_normal"], same_object: bool = True, albedo_floor: float = SVGF_DEFAULTS["albedo_floor"],
+                sigma_luminance: float = SVGF_DEFAULTS["sigma_luminance"], epsilon: float = SVGF_DEFAULTS["epsilon"], prefilter: bool = SVGF_DEFAULTS["prefilter"],
+                out=None, out_variance=None):
+    """The variance-steered a-trous filter on the host (rtw_svgf_filter), the bytes of Renderer.svgf_filter; numpy arrays only.  Arguments
+    and result as there."""
+    return _svgf_call(lib().rtw_svgf_filter, "rtw_svgf_filter", (), None, frame, variance, depth, normal, ids, albedo, emitted, levels, sigma_color,
+                      sigma_depth, sigma_normal, same_object, albedo_floor, sigma_luminance, epsilon, prefilter, out, out_variance)
+
+
+class SvgfDenoiser(TemporalDenoiser):
+    """Python only: TemporalDenoiser with the variance-steered filter stage behind the accumulation (Renderer.variance_estimate, then
+    Renderer.svgf_filter) where TemporalDenoiser has the fixed a-trous filter.  `params` as there."""
+
+    def step(self, cam: RtwCamera, params: RtwParams, min_history: int = SVGF_DEFAULTS["min_history"], radius: int = SVGF_DEFAULTS["radius"],
+             **svgf):
+        """One frame: rendered, its guides taken and accumulated as TemporalDenoiser.step does; variance_estimate (min_history, radius; the
+        guide sigmas and same_object those of **svgf) on the new history's moments and length; svgf_filter (keyword arguments: its own) on
+        the accumulated colour with albedo and emission; params.gamma applied.  Returns (frame, accumulated, variance, stats): variance is
+        the estimate the filter was steered by; stats holds render, temporal, variance and svgf (RtwStats and three RtwFilterStats),
+        coverage, cur, guides, and filtered_variance, the variance the filter's levels left."""
+        if params.part_count != 1:
+            raise ValueError("SvgfDenoiser: whole frames only (part_count 1)")
+        r = self.renderer
+        params.seed = (params.seed + 1) & 0xFFFFFFFFFFFFFFFF
+        gamma = float(params.gamma)
+        params.gamma = 1.0
+        try:
+            cur, st = r.render(cam, params)
+        finally:
+            params.gamma = gamma
+        g = r.surface_map(cam, params.width, params.height, params.mint, params.maxt, params.integrator, RAYS_PIXEL, (0.5, 0.5), accel=params.accel)
+        self.history, _, st_t = r.temporal_accumulate(cur, cam, depth=g["depth"], normal=g["normal"], ids=g["idx"], history=self.history,
+                                                      offset=(0.5, 0.5), **self.params)
+        acc = self.history["color"]
+        guide_kw = {k: svgf[k] for k in ("sigma_depth", "sigma_normal", "same_object") if k in svgf}
+        variance, st_v = r.variance_estimate(self.history["moments"], self.history["len"], depth=g["depth"], normal=g["normal"], ids=g["idx"],
+                                             min_history=min_history, radius=radius, **guide_kw)
+        frame, fvar, st_s = r.svgf_filter(acc, variance, depth=g["depth"], normal=g["normal"], ids=g["idx"], albedo=g["albedo"],
+                                          emitted=g["emitted"], **svgf)
+        if gamma != 1.0:
+            frame = np.power(np.maximum(frame, np.float32(0.0)), np.float32(1.0 / gamma)).astype(np.float32)
+        stats = dict(render=st, temporal=st_t, variance=st_v, svgf=st_s, coverage=float((self.history["len"] > 1).mean()), cur=cur, guides=g,
+                     filtered_variance=fvar)
         return frame, acc, variance, stats
 
 

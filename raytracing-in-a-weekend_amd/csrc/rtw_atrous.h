@@ -52,8 +52,9 @@ __host__ __device__ inline float atrous_remodulate(float c, const float *albedo,
 
 // The guide weight of tap q for centre p (with the colour difference): the guided filter's (rtw_filter.hip), a colour term in front and the
 // depth difference scaled by 2^-i.
-__host__ __device__ inline float atrous_weight(const AtrousLevel &lv, const AtrousColor &cp, const AtrousGuide &gp, const AtrousColor &cq,
-                                               const AtrousGuide &gq) {
+// Its two halves are separate so that the variance-steered filter (rtw_svgf.h) can add a term to `a` between them.
+__host__ __device__ inline float atrous_exponent(const AtrousLevel &lv, const AtrousColor &cp, const AtrousGuide &gp, const AtrousColor &cq,
+                                                 const AtrousGuide &gq) {
     float a = 0.0f;
     if (lv.terms & ATROUS_COLOR) {
         const float dx = cq.r - cp.r, dy = cq.g - cp.g, dz = cq.b - cp.b;
@@ -67,9 +68,16 @@ __host__ __device__ inline float atrous_weight(const AtrousLevel &lv, const Atro
         const float dx = gq.nx - gp.nx, dy = gq.ny - gp.ny, dz = gq.nz - gp.nz;
         a = a + lv.inv_normal * ((dx * dx + dy * dy) + dz * dz);
     }
+    return a;
+}
+__host__ __device__ inline float atrous_gate(const AtrousLevel &lv, float a, const AtrousGuide &gp, const AtrousGuide &gq) {
     float g = a >= 0.0f ? exp_plain(-a) : 0.0f;
     if ((lv.terms & ATROUS_IDX) && gq.id != gp.id) g = 0.0f;
     return g;
+}
+__host__ __device__ inline float atrous_weight(const AtrousLevel &lv, const AtrousColor &cp, const AtrousGuide &gp, const AtrousColor &cq,
+                                               const AtrousGuide &gq) {
+    return atrous_gate(lv, atrous_exponent(lv, cp, gp, cq, gq), gp, gq);
 }
 
 // Pixel (x, y) of one level.  `src` answers color(qx, qy) and guide(qx, qy) for pixels inside the frame -- from global memory on the host

@@ -18,8 +18,6 @@
 namespace rtw {
 namespace {
 
-constexpr uint32_t ABX = 32, ABY = 16;                   // workgroup: 32 x 16 pixels, a wave covers two rows of 32
-constexpr size_t ATROUS_TILE_LDS_MAX = 64u * 1024u;      // a tile beyond this is not tried: one workgroup per CU reads mostly halo
 constexpr uint32_t ATROUS_TILE_LEVELS = 3;               // RTW_OPT_ATROUS_LAYOUT 0: levels below this (steps 1, 2, 4) read a tile where it fits:
                                                          // measured faster there, and no faster from step 8 on (profiles/atrous.log)
 
@@ -117,17 +115,22 @@ float event_ms(hipEvent_t a, hipEvent_t b) {
 
 } // namespace
 
-struct AtrousScratch {
-    DevMem ping, pong;                             // the levels' two buffers, [h][w][3] f32 each
-    DevMem in, depth, normal, idx, albedo, emitted;   // the caller's host buffers, staged
-    DevMem out;                                    // the result when the caller's buffer is host memory
-    hipEvent_t ev[2] = { nullptr, nullptr };
-};
-
 void atrous_scratch_free(AtrousScratch *s) {
     if (!s) return;
     for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
     delete s;                                      // (the buffers free themselves)
+}
+
+hipError_t atrous_scratch_get(AtrousScratch **scratch) {
+    if (*scratch) return hipSuccess;
+    AtrousScratch *s = new (std::nothrow) AtrousScratch();
+    if (!s) return hipErrorOutOfMemory;
+    *scratch = s;                                  // (owned by the context from here on, whatever follows)
+    for (hipEvent_t &e : s->ev) {
+        const hipError_t rc = hipEventCreate(&e);
+        if (rc != hipSuccess) return rc;
+    }
+    return hipSuccess;
 }
 
 #define ATROUS_TRY(expr)                                                                                                          \
@@ -144,12 +147,7 @@ int atrous_filter_device(int device, hipStream_t stream, AtrousScratch **scratch
     const int rc = atrous_check(in, w, h, depth, normal, idx, albedo, p, out, pl);
     if (rc != RTW_OK) return rc;
     ATROUS_TRY(hipSetDevice(device));
-    if (!*scratch) {
-        AtrousScratch *s = new (std::nothrow) AtrousScratch();
-        if (!s) return RTW_E_NOMEM;
-        *scratch = s;
-        for (hipEvent_t &e : s->ev) ATROUS_TRY(hipEventCreate(&e));
-    }
+    ATROUS_TRY(atrous_scratch_get(scratch));
     AtrousScratch *s = *scratch;
     const size_t n_px = (size_t)w * h, n = 3 * n_px;
 

@@ -8,6 +8,7 @@
 #include "rtw_filter.h"
 #include "rtw_atrous_dev.h"
 #include "rtw_temporal_dev.h"
+#include "rtw_svgf_dev.h"
 #include "rtw_devmem.h"
 #include "rtw_exp.h"
 #include "rtw_probe.h"
@@ -95,7 +96,8 @@ struct rtw_ctx {
     bool noise_active = false;           // a used texture has noise: renders take the noise build (SPEC 7)
     DevNoise noise{};                    // device tables / per-texture entries (null when no noise is set)
     NoiseMem noise_mem;
-    AtrousScratch *atrous = nullptr;     // buffers of rtw_ctx_atrous_filter (rtw_atrous.hip), created on its first call
+    AtrousScratch *atrous = nullptr;     // buffers of rtw_ctx_atrous_filter (rtw_atrous.hip), rtw_ctx_svgf_filter and rtw_ctx_variance_estimate
+                                         // (rtw_svgf.hip), created on the first call of any of them
     TemporalScratch *temporal = nullptr; // buffers of rtw_ctx_temporal_accumulate (rtw_temporal.hip), created on its first call
     FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
     // Rust2 triangles of the scene (rtw_ctx_set_triangles; cleared by rtw_ctx_set_scene)
@@ -1446,6 +1448,24 @@ int rtw_ctx_temporal_accumulate(rtw_ctx *c, const float *cur, uint32_t w, uint32
     const TemporalBuffers b = { cur, depth, normal, idx, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
                                 out_color, out_moments, out_len, out_variance };
     return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, stats, &g_last_hip);
+}
+
+// The variance estimate and the variance-steered a-trous filter (rtw_svgf.hip) likewise, on the a-trous filter's scratch.
+int rtw_ctx_variance_estimate(rtw_ctx *c, const float *moments, const float *len, uint32_t w, uint32_t h, const float *depth, const float *normal,
+                              const int32_t *idx, const RtwVarianceEstimate *p, float *out, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return variance_estimate_device(c->device, c->stream, &c->atrous, c->opt_atrous_layout, moments, len, w, h, depth, normal, idx, p, out, stats,
+                                    &g_last_hip);
+}
+
+int rtw_ctx_svgf_filter(rtw_ctx *c, const float *in, const float *variance, uint32_t w, uint32_t h, const float *depth, const float *normal,
+                        const int32_t *idx, const float *albedo, const float *emitted, const RtwAtrous *p, const RtwSvgf *vp, float *out,
+                        float *out_variance, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return svgf_filter_device(c->device, c->stream, &c->atrous, c->opt_atrous_layout, in, variance, w, h, depth, normal, idx, albedo, emitted, p, vp,
+                              out, out_variance, stats, &g_last_hip);
 }
 
 // The device-math probe (rtw_probe.hip, rtw.h "device math, for tests") on this context's GPU and stream; the scene is not involved.

@@ -1,0 +1,182 @@
+"""The variance estimate and the variance-steered a-trous filter on the host (rtw_variance_estimate, rtw_svgf_filter, include/rtw.h,
+DESIGN.md 8e): each host form against an independent numpy restatement bit for bit over frames, levels, radii, history thresholds and
+terms, on inputs with NaN, infinite and miss pixels, holes and fractions in the history and variances of 0, +inf, NaN and below 0; the
+identities with the a-trous filter and the temporal accumulation; a known answer; out == in; the argument checks."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import rtw_amd as R
+from tests.atrous_common import TERM_SETS, call_kwargs, host_answer
+from tests.svgf_common import (EPSILON, F, LEVELS, MIN_HISTORIES, RADII, SHAPES, SIGMA_LUM, SVGF_TERM_SETS, VARIANCE_TERM_SETS, atrous_kwargs,
+                               check_refusals, filter_inputs, filter_kwargs, history, host_filter, host_variance, inputs, mismatch, ref_svgf,
+                               ref_variance, same_bits, variance_kwargs)
+
+SHAPE_IDS = lambda s: f"{s[1]}x{s[0]}"
+
+
+# ---- 1. the host forms against the restatements -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("terms", list(VARIANCE_TERM_SETS))
+@pytest.mark.parametrize("min_history", MIN_HISTORIES)
+@pytest.mark.parametrize("radius", RADII)
+@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
+def test_variance_host_equals_restatement(shape, radius, min_history, terms):
+    h, w = shape
+    moments, length = history(h, w)
+    got = host_variance(h, w, terms, min_history, radius)
+    want = ref_variance(moments, length, **variance_kwargs(h, w, terms, min_history, radius))
+    assert same_bits(got, want), mismatch(got, want)
+
+
+@pytest.mark.parametrize("prefilter", [0, 1])
+@pytest.mark.parametrize("terms", list(SVGF_TERM_SETS))
+@pytest.mark.parametrize("levels", LEVELS)
+@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
+def test_filter_host_equals_restatement(shape, levels, terms, prefilter):
+    h, w = shape
+    frame, variance = filter_inputs(h, w)
+    got, got_v = host_filter(h, w, terms, levels, prefilter)
+    want, want_v = ref_svgf(frame, variance, **filter_kwargs(h, w, terms, levels, prefilter))
+    assert same_bits(got, want), mismatch(got, want)
+    assert same_bits(got_v, want_v), mismatch(got_v, want_v)
+
+
+def test_inputs_hold_the_specials():
+    moments, length = history(35, 67)
+    assert (length == 0).any() and (length == 1).any() and (length == 5).any() and (length == 65535).any() and np.isnan(length).any()
+    frac = length[np.isfinite(length)]
+    assert (frac != np.floor(frac)).sum() > 10 and (length == F(0.5)).any()
+    assert np.isinf(moments).any()
+    below = (length < 4).sum()
+    assert 100 < below < length.size - 100                                # both branches of min_history 4 are well populated
+    frame, variance = filter_inputs(35, 67)
+    assert np.isnan(frame).any() and np.isinf(frame).any()
+    assert (variance == 0).any() and np.isposinf(variance).any() and np.isnan(variance).any() and (variance < 0).any()
+    assert (variance[np.isfinite(variance)] > 0).sum() > variance.size // 2
+
+
+def test_the_variance_steers_the_filter():
+    """(the matrix compares two implementations of one rule: this one holds the rule to what it is for)  A step edge under noise: where the
+    variance says the pixels are noisy the filter averages them, where it says they have converged it leaves them alone."""
+    rng = np.random.default_rng(6)
+    clean = np.full((24, 40, 3), 0.3, F)
+    clean[:, 20:] = 0.7
+    noisy = (clean + 0.05 * rng.standard_normal(clean.shape[:2])[..., None]).astype(F)      # (grey noise: equal luminance is equal colour)
+    mse = lambda a: float(((a - clean) ** 2).mean())
+    loud = R.svgf_filter(noisy, np.full((24, 40), 0.05 ** 2, F), levels=3, sigma_luminance=2.0, epsilon=1e-8, prefilter=False)[0]
+    quiet = R.svgf_filter(noisy, np.full((24, 40), 1e-10, F), levels=3, sigma_luminance=2.0, epsilon=1e-12, prefilter=False)[0]
+    blind = R.atrous_filter(noisy, levels=3, sigma_color=0.0)[0]
+    assert mse(loud) < 0.2 * mse(noisy)                                   # the noise goes
+    assert mse(loud) < 0.1 * mse(blind)                                   # ... and the edge, 8 standard deviations high, stays
+    assert np.abs(quiet - noisy).max() < 1e-3                             # "converged": left alone
+    v_out = R.svgf_filter(noisy, np.full((24, 40), 0.05 ** 2, F), levels=3, sigma_luminance=2.0, epsilon=1e-8, prefilter=False)[1]
+    assert (v_out[4:-4, 4:16] < 0.05 ** 2 / 10).all()                     # the filtered variance falls with the averaging
+
+
+# ---- 2. identities ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("terms", list(TERM_SETS))
+@pytest.mark.parametrize("levels", LEVELS)
+@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
+def test_without_the_luminance_term_it_is_the_atrous_filter(shape, levels, terms):
+    h, w = shape
+    want = host_answer(h, w, terms, levels)                                # (filter_inputs' frame is the a-trous tests' own)
+    for prefilter in (0, 1):
+        assert atrous_kwargs(filter_kwargs(h, w, terms, levels, prefilter)).keys() == call_kwargs(h, w, terms, levels).keys()
+        got = host_filter(h, w, terms, levels, prefilter)[0]
+        assert same_bits(got, want), (prefilter, mismatch(got, want))
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
+def test_min_history_1_is_the_temporal_variance(shape):
+    """variance_estimate with min_history 1 writes temporal_accumulate's out_variance bytes wherever len >= 1."""
+    from tests.temporal_common import ALL_OFF, dyadic_camera, turned
+    h, w = shape
+    g = inputs(h, w)
+    hist = None
+    for k, degrees in enumerate((0.0, 0.0, 1.2)):
+        with np.errstate(all="ignore"):
+            cur = (g["frame"] * F(1.0 + 0.1 * k)).astype(F)
+        hist, variance, _ = R.temporal_accumulate(cur, turned(dyadic_camera(h, w), degrees), g["depth"], history=hist, **ALL_OFF)
+        for terms in ("none", "all"):
+            got = R.variance_estimate(hist["moments"], hist["len"], **variance_kwargs(h, w, terms, 1, 3))[0]
+            there = hist["len"] >= 1
+            assert there.any() and same_bits(got[there], variance[there]), (k, terms)
+            assert (got[~there] == 0).all() or not (hist["len"][~there] > 0).all()
+
+
+@pytest.mark.parametrize("terms", ["var", "var+all+albedo+emitted"])
+def test_out_may_be_in(terms):
+    h, w = 9, 17
+    frame, variance = filter_inputs(h, w)
+    frame = frame.copy()
+    out, out_v, _ = R.svgf_filter(frame, variance, **filter_kwargs(h, w, terms, 3, 1), out=frame)
+    want, want_v = host_filter(h, w, terms, 3, 1)
+    assert out is frame and same_bits(frame, want) and same_bits(out_v, want_v)
+
+
+# ---- 3. a known answer -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(5, 5), (9, 17)], ids=SHAPE_IDS)
+def test_known_answer_of_a_unit_variance(shape):
+    """Every edge term off, one level, variance 1 everywhere: away from the border out_variance is (sum hw^2) / (sum hw)^2 = (35/128)^2
+    = 1225/16384 exactly -- every partial sum is a dyadic rational that float32 holds, checked here in numpy first."""
+    K = np.array([0.0625, 0.25, 0.375, 0.25, 0.0625], F)
+    hw = np.outer(K, K).astype(F)
+    s, s2 = F(0.0), F(0.0)
+    for y in range(5):
+        for x in range(5):
+            wt = hw[y, x]
+            assert float(wt) == float(K[y]) * float(K[x])
+            s, s2 = F(s + wt), F(s2 + F(wt * wt) * F(1.0))
+            assert float(s2) == sum(float(hw.reshape(-1)[k]) ** 2 for k in range(5 * y + x + 1))       # exact so far
+    assert float(s) == 1.0 and float(s2) == (35.0 / 128.0) ** 2 == 1225.0 / 16384.0
+    h, w = shape
+    frame = np.random.default_rng(8).random((h, w, 3)).astype(F)
+    ones = np.ones((h, w), F)
+    kw = dict(levels=1, sigma_color=0.0, sigma_luminance=0.0)
+    _, got, _ = R.svgf_filter(frame, ones, **kw)
+    assert (got[2:-2, 2:-2] == F(1225.0 / 16384.0)).all() and got[2:-2, 2:-2].size >= 1
+    assert same_bits(got, ref_svgf(frame, ones, **kw)[1])                   # the border: the restatement
+    assert (got[0, 0] > F(1225.0 / 16384.0))                              # (fewer taps average less)
+
+
+# ---- 4. stats, argument checks, layout -------------------------------------------------------------------------------------------------
+def test_stats():
+    moments, length = history(9, 17)
+    for r in (1, 3):
+        taps = sum(max(0, 17 - abs(d)) for d in range(-r, r + 1)) * sum(max(0, 9 - abs(d)) for d in range(-r, r + 1))
+        st = R.variance_estimate(moments, length, radius=r)[1]
+        assert st.taps == taps and st.filter_ms >= 0.0
+    frame, variance = filter_inputs(9, 17)
+    assert R.svgf_filter(frame, variance, levels=3)[2].taps == R.atrous_filter(frame, levels=3)[1].taps
+
+
+def test_error_paths_host():
+    check_refusals(R.lib().rtw_variance_estimate, R.lib().rtw_svgf_filter, ())
+    moments, length = history(9, 17)
+    frame, variance = filter_inputs(9, 17)
+    # the Python layer: shapes and dtypes
+    with pytest.raises(ValueError):
+        R.variance_estimate(moments[..., :1], length)
+    with pytest.raises(ValueError):
+        R.variance_estimate(moments, length[0])
+    with pytest.raises(ValueError):
+        R.variance_estimate(moments, length, out=np.empty((9, 17), np.float64))
+    with pytest.raises(ValueError):
+        R.svgf_filter(frame, variance[:, :16])
+    with pytest.raises(ValueError):
+        R.svgf_filter(frame, variance, out_variance=np.empty((9, 17, 1), F))
+    with pytest.raises(R.RtwError):
+        R.svgf_filter(frame, variance, epsilon=0.0)
+    with pytest.raises(R.RtwError):
+        R.variance_estimate(moments, length, radius=4)
+
+
+def test_pod_layout_and_defaults():
+    assert C.sizeof(R.RtwVarianceEstimate) == 20 and R.RtwVarianceEstimate.same_object.offset == 16
+    assert C.sizeof(R.RtwSvgf) == 12 and R.RtwSvgf.prefilter.offset == 8
+    assert C.sizeof(R.RtwAtrous) == 24 and R.lib().rtw_abi_version() == 4
+    assert R.VARIANCE_MAX_RADIUS == 3
+    assert set(R.SVGF_DEFAULTS) == {"levels", "sigma_luminance", "epsilon", "prefilter", "min_history", "radius", "sigma_color", "sigma_depth",
+                                    "sigma_normal", "albedo_floor"}
+    assert R.SVGF_DEFAULTS["sigma_color"] == 0.0 and issubclass(R.SvgfDenoiser, R.TemporalDenoiser)
