@@ -15,7 +15,7 @@ import rtw_amd as R
 
 F = np.float32
 SHAPES = [(1, 1), (3, 5), (9, 17), (35, 67)]                # (h, w): frames 1 x 1, 5 x 3, 17 x 9 and 67 x 35
-LEVELS = [1, 3, 8]                                          # at 8 the step (128) exceeds every frame: only the centre tap remains
+LEVELS = [1, 3, 8]                                          # at 8 the step (128) exceeds every frame of SHAPES: only the centre tap remains (DEEP_SHAPES)
 SIGMA_COLOR, SIGMA_DEPTH, SIGMA_NORMAL, FLOOR = 0.75, 0.5, 0.6, 0.05
 # name -> (sigma_color, sigma_depth, sigma_normal, same_object, albedo, emitted)
 TERM_SETS = {
@@ -27,6 +27,18 @@ TERM_SETS = {
     "all+albedo": (SIGMA_COLOR, SIGMA_DEPTH, SIGMA_NORMAL, True, True, False),
     "all+albedo+emitted": (SIGMA_COLOR, SIGMA_DEPTH, SIGMA_NORMAL, True, True, True),
     "none+emitted": (0.0, 0.0, 0.0, False, False, True),
+}
+# Levels 7 and 8 with taps inside the frame: 259 = 2 * 128 + 3 columns (or rows), so that at step 128 the taps at -256 .. +256 of some
+# pixel all land inside.  The term sets are those whose weights stay positive that far away -- none has the colour term, whose sigma
+# shrinks by 2^-i -- and the frame is deep_frame's: inputs' with its three non-finite pixels made finite, for without the colour term a
+# NaN tap is not dropped and seven levels spread it over the whole strip, where every level count gives the same answer, NaN.
+DEEP_SHAPES = [(3, 259), (259, 3)]
+DEEP_LEVELS = [7, 8]
+DEEP_TERM_SETS = {
+    "depth": TERM_SETS["depth"],
+    "normal": TERM_SETS["normal"],
+    "none+emitted": TERM_SETS["none+emitted"],
+    "guides+albedo+emitted": (0.0, SIGMA_DEPTH, SIGMA_NORMAL, False, True, True),
 }
 
 
@@ -83,7 +95,7 @@ def inputs(h, w, seed=5):
 
 def call_kwargs(h, w, terms, levels):
     """The keyword arguments of atrous_filter / Renderer.atrous_filter for one case (the frame is inputs(h, w)["frame"])."""
-    sc, sd, sn, same, alb, emi = TERM_SETS[terms]
+    sc, sd, sn, same, alb, emi = TERM_SETS[terms] if terms in TERM_SETS else DEEP_TERM_SETS[terms]
     g = inputs(h, w)
     return dict(depth=g["depth"] if sd > 0 else None, normal=g["normal"] if sn > 0 else None, ids=g["ids"] if same else None,
                 albedo=g["albedo"] if alb else None, emitted=g["emitted"] if emi else None, levels=levels, sigma_color=sc,
@@ -149,3 +161,26 @@ def host_answer(h, w, terms, levels):
     out = R.atrous_filter(inputs(h, w)["frame"], **call_kwargs(h, w, terms, levels))[0]
     out.setflags(write=False)
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def deep_frame(h, w):
+    """inputs(h, w)'s frame with its non-finite pixels set to 0.5 (DEEP_SHAPES' comment).  Read-only."""
+    frame = inputs(h, w)["frame"].copy()
+    frame[~np.isfinite(frame).all(-1)] = 0.5
+    frame.setflags(write=False)
+    return frame
+
+
+@functools.lru_cache(maxsize=None)
+def deep_answer(h, w, terms, levels):
+    """The host form's (answer, taps) on deep_frame, computed once (read-only)."""
+    out, st = R.atrous_filter(deep_frame(h, w), **call_kwargs(h, w, terms, levels))
+    out.setflags(write=False)
+    return out, int(st.taps)
+
+
+def taps_inside(h, w, levels):
+    """The taps inside an h x w frame over `levels` levels, and the count were every level left with its centre tap alone."""
+    taps = sum(sum(max(0, w - abs(d) * 2 ** i) for d in range(-2, 3)) * sum(max(0, h - abs(d) * 2 ** i) for d in range(-2, 3)) for i in range(levels))
+    return taps, levels * h * w

@@ -16,7 +16,8 @@ import functools
 import numpy as np
 
 import rtw_amd as R
-from tests.atrous_common import FLOOR, SHAPES, TERM_SETS, inputs, mismatch, same_bits  # noqa: F401  (re-exported to the two test files)
+from tests.atrous_common import (DEEP_LEVELS, DEEP_SHAPES, DEEP_TERM_SETS, FLOOR, SHAPES, TERM_SETS, deep_frame, inputs, mismatch,  # noqa: F401
+                                 same_bits, taps_inside)                       # (re-exported to the two test files)
 from tests.temporal_common import ALL_OFF, dyadic_camera, turned
 
 F = np.float32
@@ -36,6 +37,14 @@ SVGF_TERM_SETS.update({
     "var+albedo": (0.0, 0.0, 0.0, False, True, False, SIGMA_LUM),
     "var+guides+albedo+emitted": (0.0,) + TERM_SETS["all+albedo+emitted"][1:] + (SIGMA_LUM,),
     "var+all+albedo+emitted": TERM_SETS["all+albedo+emitted"] + (SIGMA_LUM,),
+})
+# Levels 7 and 8 with taps inside the frame (tests/atrous_common.py, DEEP_SHAPES): its term sets with the luminance term off, and the
+# luminance term -- whose width does not shrink with the level -- alone, beside an albedo, and beside the guides
+SVGF_DEEP_TERM_SETS = {name: t + (0.0,) for name, t in DEEP_TERM_SETS.items()}
+SVGF_DEEP_TERM_SETS.update({
+    "var": SVGF_TERM_SETS["var"],
+    "var+albedo": SVGF_TERM_SETS["var+albedo"],
+    "var+guides+albedo+emitted": DEEP_TERM_SETS["guides+albedo+emitted"] + (SIGMA_LUM,),
 })
 # name -> (sigma_depth, sigma_normal, same_object) of the variance estimate
 VARIANCE_TERM_SETS = {
@@ -109,7 +118,7 @@ def filter_inputs(h, w):
 
 def filter_kwargs(h, w, terms, levels, prefilter):
     """The keyword arguments of svgf_filter / Renderer.svgf_filter for one case (frame and variance are filter_inputs(h, w)'s)."""
-    sc, sd, sn, same, alb, emi, sl = SVGF_TERM_SETS[terms]
+    sc, sd, sn, same, alb, emi, sl = SVGF_DEEP_TERM_SETS[terms] if (h, w) in DEEP_SHAPES else SVGF_TERM_SETS[terms]
     g = inputs(h, w)
     return dict(depth=g["depth"] if sd > 0 else None, normal=g["normal"] if sn > 0 else None, ids=g["ids"] if same else None,
                 albedo=g["albedo"] if alb else None, emitted=g["emitted"] if emi else None, levels=levels, sigma_color=sc,
@@ -130,6 +139,26 @@ def host_filter(h, w, terms, levels, prefilter):
     out.setflags(write=False)
     var.setflags(write=False)
     return out, var
+
+
+@functools.lru_cache(maxsize=None)
+def deep_variance(h, w):
+    """filter_inputs(h, w)'s variance with its non-finite entries set to 0.25, for the reason deep_frame gives: out_variance sums every
+    counted tap's variance, and seven levels spread an infinite one over the strip.  (The 0 and the negative entry stay.)  Read-only."""
+    variance = filter_inputs(h, w)[1].copy()
+    variance[~np.isfinite(variance)] = 0.25
+    variance.setflags(write=False)
+    return variance
+
+
+@functools.lru_cache(maxsize=None)
+def deep_filter(h, w, terms, levels, prefilter):
+    """The host form's (out, out_variance, taps) of one of the cases at DEEP_SHAPES on deep_frame and deep_variance, computed once
+    (read-only)."""
+    out, var, st = R.svgf_filter(deep_frame(h, w), deep_variance(h, w), **filter_kwargs(h, w, terms, levels, prefilter))
+    out.setflags(write=False)
+    var.setflags(write=False)
+    return out, var, int(st.taps)
 
 
 # ---- the rules in numpy ------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """What the temporal-accumulation tests share (tests/test_temporal_cpu.py, tests/test_gpu_temporal.py): an independent numpy restatement of
 the rule of include/rtw.h ("temporal accumulation") in float32, which also hands out fx, fy and s for inspection, and the case builders:
-synthetic frames, guides and cameras, no renderer.
+synthetic frames, guides and cameras, no renderer.  The restatement is the rule typed again; what holds both to geometry is
+tests/temporal_geometry_common.py.
 
 A case is a list of frames accumulated one after the other, each a dict of cur, cam, depth, normal, idx (and optionally `poke`, a
 function that edits a copy of the history before this frame reads it), plus the parameters of every call.  "The same" is, as for the
@@ -67,6 +68,63 @@ def orbit(cam, degrees):
         for name in ("origin", "u", "v", "pixel00", "delta_u", "delta_v"):
             setattr(c, name, (R.C.c_float * 3)(*[float(F(x)) for x in rot @ np.array(list(getattr(cam, name)), np.float64)]))
     return c
+
+
+def look_camera(h, w, origin, target, vfov, roll=0.0, pixel_aspect=1.0):
+    """A camera as rtw_viewport_new lays one out (du, dv and the view direction mutually orthogonal, pixel00 the centre of pixel 0, 0), built
+    in float64 from its pose and rounded to float32 at the end: at `origin` looking at `target`, `vfov` degrees over the h rows, rolled by
+    `roll` radians about the view direction.  pixel_aspect: |du| / |dv| (1: square pixels; rtw_viewport_new gives others for a direction
+    that is not a unit vector)."""
+    origin, target = np.array(origin, np.float64), np.array(target, np.float64)
+    fwd = (target - origin) / np.linalg.norm(target - origin)
+    right = np.cross(fwd, np.array([0.0, 1.0, 0.0]))
+    right /= np.linalg.norm(right)
+    down = np.cross(fwd, right)
+    c, s = np.cos(roll), np.sin(roll)
+    right, down = c * right + s * down, c * down - s * right
+    vh = 2.0 * np.tan(np.deg2rad(vfov) / 2.0)
+    dv = down * (vh / h)
+    du = right * (vh / h) * pixel_aspect
+    p00 = fwd - du * (w / 2.0) - dv * (h / 2.0) + (du + dv) * 0.5
+    return camera(origin, p00, du, dv)
+
+
+# The camera pairs of the geometry cases (tests/temporal_geometry_common.py): name -> (current pose, previous pose), a pose the keyword
+# arguments of look_camera.  BOOK1 is the Book-1 view: from (13, 2, 3) at the origin, 20 degrees.  Every pair keeps most of the frame in
+# view for points 0.6 .. 1.4 times the target's distance away.  A skewed grid (du . dv != 0) is not among them: include/rtw.h gives the rule
+# "for cameras of rtw_viewport_new only", whose du, dv and view direction are orthogonal (|du| != |dv| they do reach).
+def _orbit_y(p, degrees):
+    t = np.deg2rad(degrees)
+    return (np.cos(t) * p[0] + np.sin(t) * p[2], p[1], -np.sin(t) * p[0] + np.cos(t) * p[2])
+
+
+BOOK1 = dict(origin=(13.0, 2.0, 3.0), target=(0.0, 0.0, 0.0), vfov=20.0)
+FAR = (600.0, 500.0, 620.0)                                                     # about 1000 units from the world's origin
+GEO_POSES = {
+    "orbit": (BOOK1, dict(BOOK1, origin=_orbit_y(BOOK1["origin"], 2.0))),
+    "vertical": (BOOK1, dict(BOOK1, origin=(13.0, 2.4, 3.0), target=(0.0, 0.4, 0.0))),
+    "roll": (dict(BOOK1, roll=0.2), BOOK1),
+    "zoom": (dict(BOOK1, vfov=25.0), BOOK1),
+    "roll+zoom": (dict(BOOK1, roll=0.2, vfov=25.0), dict(BOOK1, origin=_orbit_y(BOOK1["origin"], 1.0))),
+    "dolly": (dict(BOOK1, origin=(11.05, 1.7, 2.55)), BOOK1),
+    "past": (BOOK1, dict(BOOK1, origin=(3.25, 0.5, 0.75))),                    # the previous camera has passed the nearest fifth of the points
+    "nonsquare": (dict(BOOK1, pixel_aspect=1.25), dict(BOOK1, origin=_orbit_y(BOOK1["origin"], -1.5), pixel_aspect=0.8)),
+    "far": (dict(BOOK1, origin=tuple(a + b for a, b in zip(FAR, BOOK1["origin"])), target=FAR),
+            dict(BOOK1, origin=tuple(a + b for a, b in zip(FAR, _orbit_y(BOOK1["origin"], 2.0))), target=FAR)),
+}
+GEO_OFFSETS = {"half": (0.5, 0.5), "zero": (0.0, 0.0), "uneven": (0.25, 0.875)}
+GEO_NAMES = [f"geo-{c}-{o}" for c in GEO_POSES for o in GEO_OFFSETS]
+
+
+def geo_cameras(h, w, name):
+    """(current camera, previous camera, the distance of the current camera's target) of GEO_POSES[name] for an h x w frame."""
+    cur, prev = GEO_POSES[name]
+    return look_camera(h, w, **cur), look_camera(h, w, **prev), float(np.linalg.norm(np.subtract(cur["target"], cur["origin"])))
+
+
+def geo_depth(h, w, reach, seed=0):
+    """Depths 0.6 .. 1.4 times `reach`, random per pixel."""
+    return (reach * (0.6 + 0.8 * np.random.default_rng(4000 + 1000 * seed + 31 * h + w).random((h, w)))).astype(F)
 
 
 # ---- the rule in numpy -------------------------------------------------------------------------------------------------------------------
@@ -215,24 +273,33 @@ def cases(h, w):
                       dict(TEMPORAL_TEST_DEFAULTS, **ALL_OFF))
     out["saturate"] = ([frame(h, w, k, A, flat=True) for k in range(4)], dict(alpha=0.0, alpha_moments=0.0, max_history=2, **ALL_ON))
     out["floor"] = ([frame(h, w, k, A, flat=True) for k in range(4)], dict(alpha=0.5, alpha_moments=0.25, max_history=32, **ALL_ON))
+    # the cameras and offsets of the geometry probe (tests/temporal_geometry_common.py) with ordinary finite frames: the previous frame, then
+    # the current one; the depth test alone is on under the uneven offset (the depths are random: it accepts some taps and rejects others)
+    for c in GEO_POSES:
+        cur_cam, prev_cam, reach = geo_cameras(h, w, c)
+        for o, offset in GEO_OFFSETS.items():
+            f0, f1 = (dict(frame(h, w, k, cam), depth=geo_depth(h, w, reach, k)) for k, cam in enumerate((prev_cam, cur_cam)))
+            terms = dict(ALL_OFF, depth_tol=0.25) if o == "uneven" else ALL_OFF
+            out[f"geo-{c}-{o}"] = ([f0, f1], dict(TEMPORAL_TEST_DEFAULTS, offset=offset, **terms))
     return out
 
 
 CASE_NAMES = ["first", "static3", "shift1", "shift3", "shift-2", "turned", "dolly", "behind", "terms-depth", "terms-normal", "terms-idx",
-              "terms-all", "holes-static", "holes-turned", "bad-cur", "saturate", "floor"]
+              "terms-all", "holes-static", "holes-turned", "bad-cur", "saturate", "floor"] + GEO_NAMES
 
 
 def run(accumulate, frames, params, wrap=None):
     """The frames through `accumulate` (R.temporal_accumulate or a Renderer's), the history handed on: a list of dict(color, moments, len,
     variance) as numpy arrays, one per frame.  wrap: how an input array is handed over (e.g. onto the device)."""
     wrap = wrap or (lambda a: a)
+    params = dict(dict(offset=OFFSET), **params)                                 # (a case may bring its own offset)
     host = lambda a: a.cpu().numpy() if hasattr(a, "data_ptr") else np.asarray(a)
     hist, outs = None, []
     for fr in frames:
         if "poke" in fr:
             hist = {k: (wrap(v) if isinstance(v, np.ndarray) else v) for k, v in fr["poke"]({k: (host(v) if k != "cam" else v) for k, v in hist.items()}).items()}
         hist, var, st = accumulate(wrap(fr["cur"].copy()), fr["cam"], depth=wrap(fr["depth"]), normal=wrap(fr["normal"]), ids=wrap(fr["idx"]),
-                                   history=hist, offset=OFFSET, **params)
+                                   history=hist, **params)
         assert st.taps == 4 * fr["depth"].size
         outs.append(dict(color=host(hist["color"]).copy(), moments=host(hist["moments"]).copy(), len=host(hist["len"]).copy(), variance=host(var).copy()))
     return outs
@@ -241,10 +308,11 @@ def run(accumulate, frames, params, wrap=None):
 def run_restated(frames, params):
     """The same through restate(); each entry also carries fx, fy, s, cand."""
     prev, outs = None, []
+    params = dict(dict(offset=OFFSET), **params)
     for fr in frames:
         if "poke" in fr:
             prev = fr["poke"](prev)
-        o = restate(fr["cur"], fr["cam"], fr["depth"], fr["normal"], fr["idx"], prev, offset=OFFSET, **params)
+        o = restate(fr["cur"], fr["cam"], fr["depth"], fr["normal"], fr["idx"], prev, **params)
         prev = dict(color=o["color"], moments=o["moments"], len=o["len"], depth=fr["depth"], normal=fr["normal"], idx=fr["idx"], cam=fr["cam"])
         outs.append(o)
     return outs
@@ -329,3 +397,33 @@ def raw_call(fn, head=(), h=3, w=5, **change):
             ptr["prev_moments"], ptr["prev_len"], ptr["prev_depth"], ptr["prev_normal"], ptr["prev_idx"], None if params_null else C.byref(p),
             ptr["out_color"], ptr["out_moments"], ptr["out_len"], ptr["out_variance"], C.byref(st))
     return rc, [buf[k] for k in ("out_color", "out_moments", "out_len", "out_variance")], buf
+
+
+# ---- the C call, buffer by buffer ----------------------------------------------------------------------------------------------------------
+BUFFERS = ("cur", "depth", "normal", "idx", "prev_color", "prev_moments", "prev_len", "prev_depth", "prev_normal", "prev_idx",
+           "out_color", "out_moments", "out_len", "out_variance")                   # the 14 buffers of a call, in the order of its arguments
+OUT_BUFFERS = dict(out_color="color", out_moments="moments", out_len="len", out_variance="variance")
+
+
+def second_frame_buffers(h, w, name):
+    """The buffers of the second call of a two-frame case as numpy arrays -- the ten inputs (the history is the host form's answer to the
+    first frame), the four outputs filled with SENTINEL --, the two cameras, the parameters, and the host form's answer."""
+    frames, params = cases(h, w)[name]
+    (f0, f1), (first, want) = frames, host_answer(h, w, name)
+    assert "poke" not in f1
+    buf = dict(cur=f1["cur"].copy(), depth=f1["depth"], normal=f1["normal"], idx=f1["idx"], prev_color=first["color"], prev_moments=first["moments"],
+               prev_len=first["len"], prev_depth=f0["depth"], prev_normal=f0["normal"], prev_idx=f0["idx"],
+               out_color=np.full((h, w, 3), SENTINEL), out_moments=np.full((h, w, 2), SENTINEL), out_len=np.full((h, w), SENTINEL),
+               out_variance=np.full((h, w), SENTINEL))
+    return buf, f1["cam"], f0["cam"], params, want
+
+
+def c_call(fn, head, h, w, cam, prev_cam, address, params):
+    """One call of the C function `fn` (after the arguments `head`): address maps each of BUFFERS to an address in host or device memory (or
+    None).  Returns the status."""
+    C = R.C
+    q = dict(dict(offset=OFFSET), **params)
+    p = R.RtwTemporal(q["alpha"], q["alpha_moments"], q["max_history"], q["depth_tol"], q["normal_cos"], q["same_object"], (C.c_float * 2)(*q["offset"]))
+    a = [None if address.get(k) is None else C.c_void_p(int(address[k])) for k in BUFFERS]
+    st = R.RtwFilterStats()
+    return fn(*head, a[0], w, h, C.byref(cam), a[1], a[2], a[3], C.byref(prev_cam), *a[4:10], C.byref(p), *a[10:14], C.byref(st))

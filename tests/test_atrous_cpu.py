@@ -1,5 +1,6 @@
 """The a-trous filter on the host (rtw_atrous_filter, include/rtw.h): the host form against an independent numpy
-restatement bit for bit over frames, levels and terms with NaN, infinite and miss pixels and albedo at its floor; what the rule promises
+restatement bit for bit over frames, levels and terms with NaN, infinite and miss pixels and albedo at its floor, and over strips 259 pixels
+long on which the taps of levels 7 and 8 land inside the frame and count; what the rule promises
 of NaN pixels; the isolation the guides give; out == in; the argument checks."""
 import ctypes as C
 
@@ -7,7 +8,8 @@ import numpy as np
 import pytest
 
 import rtw_amd as R
-from tests.atrous_common import (F, FLOOR, LEVELS, SHAPES, TERM_SETS, call_kwargs, host_answer, inputs, mismatch, ref_atrous, same_bits)
+from tests.atrous_common import (DEEP_LEVELS, DEEP_SHAPES, DEEP_TERM_SETS, F, FLOOR, LEVELS, SHAPES, TERM_SETS, call_kwargs, deep_answer, deep_frame,
+                                 host_answer, inputs, mismatch, ref_atrous, same_bits, taps_inside)
 
 
 # ---- 1. the host form against the restatement ------------------------------------------------------------------------------------------
@@ -19,6 +21,32 @@ def test_host_equals_restatement(shape, levels, terms):
     got = host_answer(h, w, terms, levels)
     want = ref_atrous(inputs(h, w)["frame"], **call_kwargs(h, w, terms, levels))
     assert same_bits(got, want), mismatch(got, want)
+
+
+@pytest.mark.parametrize("terms", list(DEEP_TERM_SETS))
+@pytest.mark.parametrize("levels", DEEP_LEVELS)
+@pytest.mark.parametrize("shape", DEEP_SHAPES, ids=lambda s: f"{s[1]}x{s[0]}")
+def test_host_equals_restatement_with_taps_at_levels_7_and_8(shape, levels, terms):
+    """259 pixels long: the taps of step 64 and step 128 land inside the frame (tests/atrous_common.py, DEEP_SHAPES)."""
+    h, w = shape
+    got = deep_answer(h, w, terms, levels)[0]
+    want = ref_atrous(deep_frame(h, w), **call_kwargs(h, w, terms, levels))
+    assert same_bits(got, want), mismatch(got, want)
+
+
+@pytest.mark.parametrize("terms", list(DEEP_TERM_SETS))
+@pytest.mark.parametrize("shape", DEEP_SHAPES, ids=lambda s: f"{s[1]}x{s[0]}")
+def test_the_taps_of_levels_7_and_8_count(shape, terms):
+    """What the cases above are worth: the seventh and the eighth level each change the answer, through finite pixels, and the taps counted
+    exceed the centre taps alone by those of step 64 and step 128."""
+    h, w = shape
+    out = {levels: deep_answer(h, w, terms, levels) for levels in (6, 7, 8)}
+    assert all(np.isfinite(o).all(-1).mean() > 0.95 for o, _ in out.values())
+    changed = lambda a, b: np.isfinite(a).all(-1) & np.isfinite(b).all(-1) & (a != b).any(-1)
+    assert changed(out[8][0], out[7][0]).sum() > 100 and changed(out[7][0], out[6][0]).sum() > 100 and changed(out[8][0], out[6][0]).sum() > 100
+    for levels in (7, 8):
+        taps, centres = taps_inside(h, w, levels)
+        assert out[levels][1] == taps and taps - taps_inside(h, w, levels - 1)[0] > h * w and taps > centres
 
 
 def test_inputs_hold_the_specials():

@@ -1,5 +1,6 @@
 """The a-trous filter on the GPU (rtw_ctx_atrous_filter, csrc/rtw_atrous.hip) against the host form, bit for bit (as
-tests/atrous_common.py defines it: the same bits, or NaN on both sides): the CPU tests' matrix under every RTW_OPT_ATROUS_LAYOUT, frames
+tests/atrous_common.py defines it: the same bits, or NaN on both sides): the CPU tests' matrix under every RTW_OPT_ATROUS_LAYOUT, strips
+259 pixels long whose taps at levels 7 and 8 land inside the frame, frames
 around the workgroup's 32 x 16 tile, host and device memory mixed per argument, out == in, torch tensors behind use_torch_stream, a second
 context, the refusals, and the one thing asserted about quality.  The host form itself is held to a numpy restatement by
 tests/test_atrous_cpu.py."""
@@ -9,7 +10,8 @@ import numpy as np
 import pytest
 
 import rtw_amd as R
-from tests.atrous_common import F, FLOOR, LEVELS, SHAPES, TERM_SETS, call_kwargs, host_answer, inputs, mismatch, same_bits
+from tests.atrous_common import (DEEP_LEVELS, DEEP_SHAPES, DEEP_TERM_SETS, F, FLOOR, LEVELS, SHAPES, TERM_SETS, call_kwargs, deep_answer, deep_frame,
+                                 host_answer, inputs, mismatch, same_bits)
 from tests.test_gpu_stream_order import KINDS, Hazard, ctx, cycles_per_ms, torch  # noqa: F401  (the fixtures and helpers of the stream-order tests)
 
 pytestmark = pytest.mark.gpu
@@ -36,6 +38,20 @@ def test_device_equals_host(gpu, shape, levels, layout):
         want = host_answer(h, w, terms, levels)
         assert same_bits(got, want), (terms, mismatch(got, want))
         assert st.taps == R.atrous_filter(np.zeros((h, w, 3), F), levels=levels)[1].taps and st.filter_ms > 0.0
+
+
+@pytest.mark.parametrize("layout", LAYOUTS, indirect=True)
+@pytest.mark.parametrize("levels", DEEP_LEVELS)
+@pytest.mark.parametrize("shape", DEEP_SHAPES, ids=lambda s: f"{s[1]}x{s[0]}")
+def test_device_equals_host_with_taps_at_levels_7_and_8(gpu, shape, levels, layout):
+    """259 pixels long, so that the taps of step 64 and step 128 land inside the frame and count (tests/test_atrous_cpu.py asserts that they
+    do): 1 << i, 2^-i, the choice between tile and direct reads and the parity of the two buffers at the last levels."""
+    h, w = shape
+    for terms in DEEP_TERM_SETS:
+        got, st = gpu.atrous_filter(deep_frame(h, w), **call_kwargs(h, w, terms, levels))
+        want, taps = deep_answer(h, w, terms, levels)
+        assert same_bits(got, want), (terms, mismatch(got, want))
+        assert st.taps == taps
 
 
 # ---- 2. around the tile ------------------------------------------------------------------------------------------------------------------

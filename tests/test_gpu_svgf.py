@@ -1,6 +1,6 @@
 """The variance estimate and the variance-steered a-trous filter on the GPU (rtw_ctx_variance_estimate, rtw_ctx_svgf_filter,
 csrc/rtw_svgf.hip) against their host forms, bit for bit (tests/atrous_common.py's same_bits): the CPU tests' matrix under
-every RTW_OPT_ATROUS_LAYOUT, frames around the workgroup's 32 x 16 tile, many ragged tiles, host and device memory mixed per argument,
+every RTW_OPT_ATROUS_LAYOUT, strips 259 pixels long whose taps at levels 7 and 8 land inside the frame, frames around the workgroup's 32 x 16 tile, many ragged tiles, host and device memory mixed per argument,
 out == in, torch tensors behind use_torch_stream, a second context, the refusals, the a-trous filter on the scratch these calls grew, and
 SvgfDenoiser against the hand-chained calls.  The host forms themselves are held to numpy restatements by tests/test_svgf_cpu.py."""
 import numpy as np
@@ -8,7 +8,7 @@ import pytest
 
 import rtw_amd as R
 from tests.atrous_common import TERM_SETS, call_kwargs, host_answer
-from tests.svgf_common import (F, LEVELS, MANY_TILES, MIN_HISTORIES, RADII, SHAPES, SVGF_TERM_SETS, TILE_SHAPES, VARIANCE_TERM_SETS,
+from tests.svgf_common import (DEEP_LEVELS, DEEP_SHAPES, SVGF_DEEP_TERM_SETS, deep_filter, deep_frame, deep_variance, F, LEVELS, MANY_TILES, MIN_HISTORIES, RADII, SHAPES, SVGF_TERM_SETS, TILE_SHAPES, VARIANCE_TERM_SETS,
                                check_refusals, filter_inputs, filter_kwargs, history, host_filter, host_variance, inputs, mismatch, same_bits,
                                variance_kwargs)
 from tests.test_gpu_stream_order import KINDS, Hazard, ctx, cycles_per_ms, torch  # noqa: F401  (the fixtures and helpers of the stream-order tests)
@@ -65,6 +65,22 @@ def test_filter_device_equals_host(gpu, shape, levels, layout):
         for prefilter in (0, 1):
             st = check_filter(gpu, h, w, terms, levels, prefilter)
             assert st.taps == R.atrous_filter(np.zeros((h, w, 3), F), levels=levels)[1].taps and st.filter_ms > 0.0
+
+
+@pytest.mark.parametrize("layout", LAYOUTS, indirect=True)
+@pytest.mark.parametrize("levels", DEEP_LEVELS)
+@pytest.mark.parametrize("shape", DEEP_SHAPES, ids=SHAPE_IDS)
+def test_filter_device_equals_host_with_taps_at_levels_7_and_8(gpu, shape, levels, layout):
+    """259 pixels long, so that the taps of step 64 and step 128 land inside the frame and count (tests/test_svgf_cpu.py asserts that they
+    do): 1 << i, 2^-i, the choice between tile and direct reads and the parity of the buffers at the last levels."""
+    h, w = shape
+    for terms in SVGF_DEEP_TERM_SETS:
+        for prefilter in (0, 1):
+            got, got_v, st = gpu.svgf_filter(deep_frame(h, w), deep_variance(h, w), **filter_kwargs(h, w, terms, levels, prefilter))
+            want, want_v, taps = deep_filter(h, w, terms, levels, prefilter)
+            assert same_bits(got, want), (terms, prefilter, mismatch(got, want))
+            assert same_bits(got_v, want_v), (terms, prefilter, mismatch(got_v, want_v))
+            assert st.taps == taps
 
 
 # ---- 2. around the tile ------------------------------------------------------------------------------------------------------------------

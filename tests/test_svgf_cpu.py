@@ -1,6 +1,7 @@
 """The variance estimate and the variance-steered a-trous filter on the host (rtw_variance_estimate, rtw_svgf_filter, include/rtw.h,
 DESIGN.md 8e): each host form against an independent numpy restatement bit for bit over frames, levels, radii, history thresholds and
-terms, on inputs with NaN, infinite and miss pixels, holes and fractions in the history and variances of 0, +inf, NaN and below 0; the
+terms, on inputs with NaN, infinite and miss pixels, holes and fractions in the history and variances of 0, +inf, NaN and below 0, and over
+strips 259 pixels long on which the taps of levels 7 and 8 land inside the frame and count; the
 identities with the a-trous filter and the temporal accumulation; a known answer; out == in; the argument checks."""
 import ctypes as C
 
@@ -9,7 +10,7 @@ import pytest
 
 import rtw_amd as R
 from tests.atrous_common import TERM_SETS, call_kwargs, host_answer
-from tests.svgf_common import (EPSILON, F, LEVELS, MIN_HISTORIES, RADII, SHAPES, SIGMA_LUM, SVGF_TERM_SETS, VARIANCE_TERM_SETS, atrous_kwargs,
+from tests.svgf_common import (DEEP_LEVELS, DEEP_SHAPES, SVGF_DEEP_TERM_SETS, deep_filter, deep_frame, deep_variance, taps_inside, EPSILON, F, LEVELS, MIN_HISTORIES, RADII, SHAPES, SIGMA_LUM, SVGF_TERM_SETS, VARIANCE_TERM_SETS, atrous_kwargs,
                                check_refusals, filter_inputs, filter_kwargs, history, host_filter, host_variance, inputs, mismatch, ref_svgf,
                                ref_variance, same_bits, variance_kwargs)
 
@@ -40,6 +41,36 @@ def test_filter_host_equals_restatement(shape, levels, terms, prefilter):
     want, want_v = ref_svgf(frame, variance, **filter_kwargs(h, w, terms, levels, prefilter))
     assert same_bits(got, want), mismatch(got, want)
     assert same_bits(got_v, want_v), mismatch(got_v, want_v)
+
+
+@pytest.mark.parametrize("prefilter", [0, 1])
+@pytest.mark.parametrize("terms", list(SVGF_DEEP_TERM_SETS))
+@pytest.mark.parametrize("levels", DEEP_LEVELS)
+@pytest.mark.parametrize("shape", DEEP_SHAPES, ids=SHAPE_IDS)
+def test_filter_host_equals_restatement_with_taps_at_levels_7_and_8(shape, levels, terms, prefilter):
+    """259 pixels long: the taps of step 64 and step 128 land inside the frame (tests/atrous_common.py, DEEP_SHAPES)."""
+    h, w = shape
+    got, got_v, _ = deep_filter(h, w, terms, levels, prefilter)
+    want, want_v = ref_svgf(deep_frame(h, w), deep_variance(h, w), **filter_kwargs(h, w, terms, levels, prefilter))
+    assert same_bits(got, want), mismatch(got, want)
+    assert same_bits(got_v, want_v), mismatch(got_v, want_v)
+
+
+@pytest.mark.parametrize("terms", list(SVGF_DEEP_TERM_SETS))
+@pytest.mark.parametrize("shape", DEEP_SHAPES, ids=SHAPE_IDS)
+def test_the_taps_of_levels_7_and_8_count(shape, terms):
+    """What the cases above are worth: the seventh and the eighth level each change the colour and the variance, through finite pixels, and
+    the taps counted exceed the centre taps alone by those of step 64 and step 128."""
+    h, w = shape
+    changed = lambda a, b: (np.isfinite(a) & np.isfinite(b) & (a != b)).reshape(h * w, -1).any(-1)
+    for prefilter in (0, 1):
+        out = {levels: deep_filter(h, w, terms, levels, prefilter) for levels in (6, 7, 8)}
+        assert all(np.isfinite(o).all(-1).mean() > 0.95 and np.isfinite(v).mean() > 0.95 for o, v, _ in out.values()), prefilter
+        for a, b in ((8, 7), (7, 6), (8, 6)):
+            assert changed(out[a][0], out[b][0]).sum() > 100 and changed(out[a][1], out[b][1]).sum() > 100, (prefilter, a, b)
+        for levels in (7, 8):
+            taps, centres = taps_inside(h, w, levels)
+            assert out[levels][2] == taps and taps - taps_inside(h, w, levels - 1)[0] > h * w and taps > centres
 
 
 def test_inputs_hold_the_specials():

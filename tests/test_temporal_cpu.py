@@ -1,13 +1,19 @@
 """Temporal accumulation on the host (rtw_temporal_accumulate, include/rtw.h) against an independent numpy restatement of the
 rule (tests/temporal_common.py), bit for bit or NaN on both sides: the first frame, a static camera (also against the running mean written
 out), whole-pixel shifts whose reprojection is exact, turned and moved cameras, each test alone and all together, holes in the history,
-non-finite pixels, the history cap, the blend floor, out_color == cur, and every refusal.  No GPU."""
+non-finite pixels, the history cap, the blend floor, out_color == cur, and every refusal; and the reprojection -- of the host form and
+of the restatement -- against float64 geometry (tests/temporal_geometry_common.py, where the measured bounds stand).  No GPU."""
 import numpy as np
 import pytest
 
 import rtw_amd as R
 from tests.temporal_common import (ALL_OFF, CASE_NAMES, F, OFFSET, SENTINEL, SHAPES, TEMPORAL_TEST_DEFAULTS, assert_same_runs, bad_pixel_places, cases, dyadic_camera, frame,
                                    host_answer, raw_call, refusal_calls, run_restated, same_bits)
+
+from tests.temporal_geometry_common import (GEO_CASES, GEO_SHAPES, LEFT_OUT_MOST, POSITION_BOUND, POSITION_MEASURED, S_MEASURED, check_plane,
+                                            check_probe, check_static_is_continuous, plane_case, position_error, probe_case, probe_restated,
+                                            regions, RENDERED_UNDECIDED_MOST, analytic_guides, rendered_cameras, rendered_sets)
+from tests.temporal_common import GEO_POSES
 
 E_INVALID = -1                                                              # rtw.h
 shape_ids = lambda s: f"{s[1]}x{s[0]}"
@@ -162,3 +168,63 @@ def test_python_arguments():
     assert set(R.TEMPORAL_DEFAULTS) == {"alpha", "alpha_moments", "max_history", "depth_tol", "normal_cos", "same_object"}
     hist, var, st = R.temporal_accumulate(fr["cur"], fr["cam"], depth=fr["depth"], **TEMPORAL_TEST_DEFAULTS)
     assert set(hist) == {"color", "moments", "len", "depth", "normal", "idx", "cam"} and var.shape == (3, 5) and st.taps == 60
+
+
+# ---- the reprojection against float64 geometry (tests/temporal_geometry_common.py) ------------------------------------------------------
+geo_ids = lambda c: f"{c[0]}-{c[1]}"
+
+
+@pytest.mark.parametrize("shape", GEO_SHAPES, ids=shape_ids)
+def test_the_restatement_stays_within_the_measured_deviations(shape):
+    """What the bounds of the probe are derived from: the numpy restatement alone against the float64 reference, on every case -- positions
+    within POSITION_MEASURED, s on the fronto-parallel plane within S_MEASURED of D, and at most 2 % of the pixels left out."""
+    h, w = shape
+    worst = worst_s = 0.0
+    for cam_name, offset_name in GEO_CASES:
+        c = probe_case(h, w, cam_name, offset_name)
+        color, length, _ = probe_restated(c)
+        inside, outside, left_out = regions(c)
+        assert left_out.mean() <= LEFT_OUT_MOST and np.all(length[inside] == 1) and np.all(length[outside] == 0), (cam_name, offset_name)
+        worst = max(worst, position_error(c, color)[0])
+        p = plane_case(h, w, cam_name, offset_name)
+        inside = regions(p)[0]
+        assert regions(p)[2].mean() <= LEFT_OUT_MOST
+        worst_s = max(worst_s, float(np.abs(probe_restated(p)[2].astype(np.float64)[inside] / p["D"] - 1.0).max()))
+    print(f"\n[geometry] {w}x{h}: the restatement's largest position error {worst:.3g} px, largest |s / D - 1| {worst_s:.3g}")
+    assert worst <= POSITION_MEASURED and worst_s <= S_MEASURED, (worst, worst_s)
+    assert any((probe_case(h, w, c, "half")["s"] < 0).any() for c in GEO_POSES)      # (some case has points behind the previous camera)
+
+
+@pytest.mark.parametrize("case", GEO_CASES, ids=geo_ids)
+@pytest.mark.parametrize("shape", GEO_SHAPES, ids=shape_ids)
+def test_reprojection_against_float64_geometry(shape, case):
+    """fx, fy and the candidate test of the host form, read out through a ramp history, against the float64 solve."""
+    h, w = shape
+    check_probe(R.temporal_accumulate, probe_case(h, w, *case), f"host {w}x{h} {case}")
+
+
+@pytest.mark.parametrize("case", GEO_CASES, ids=geo_ids)
+@pytest.mark.parametrize("shape", GEO_SHAPES, ids=shape_ids)
+def test_s_against_a_fronto_parallel_plane(shape, case):
+    """s of the host form through the depth test: against prev_depth = D every candidate keeps its history under depth_tol = S_TOL, against
+    D (1 + 8 S_TOL) none does."""
+    h, w = shape
+    check_plane(R.temporal_accumulate, plane_case(h, w, *case), f"host {w}x{h} {case}")
+
+
+@pytest.mark.parametrize("cam_name", list(GEO_POSES))
+@pytest.mark.parametrize("shape", GEO_SHAPES, ids=shape_ids)
+def test_static_shortcut_is_continuous_with_the_general_path(shape, cam_name):
+    h, w = shape
+    check_static_is_continuous(R.temporal_accumulate, h, w, cam_name, f"host {w}x{h} {cam_name}")
+    assert POSITION_BOUND < 1.0 / 64.0
+
+
+def test_the_rendered_view_decides_most_of_its_pixels():
+    """The float64 reference of tests/test_gpu_temporal.py's rendered check alone, on the guides it expects surface_map to write: both of its
+    sets are populated and the undecided rest -- silhouettes, disocclusions, the frame's edge -- is at most a quarter of the frame."""
+    cam, prev_cam = rendered_cameras()
+    depth, idx = analytic_guides(cam, OFFSET)
+    keep, reset = rendered_sets(cam, prev_cam, depth, idx, OFFSET)
+    assert len(np.unique(idx)) >= 4 and keep.sum() > 100 and reset.sum() >= 8 and not (keep & reset).any()
+    assert 1.0 - keep.mean() - reset.mean() <= RENDERED_UNDECIDED_MOST
