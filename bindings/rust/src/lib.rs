@@ -86,6 +86,23 @@ pub const RTW_VARIANCE_MAX_RADIUS: u32 = 3;
 /// prefilter (1 = the centre's variance is its 3 x 3 Gaussian mean).
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct RtwSvgf { pub sigma_luminance: f32, pub epsilon: f32, pub prefilter: u32 }
+/// Arguments of the temporal accumulation (include/rtw.h): the two blend floors, the history cap, the depth and normal tests (0 = term
+/// off), same_object and the RTW_RAYS_PIXEL offset of both frames' guides.
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RtwTemporal { pub alpha: f32, pub alpha_moments: f32, pub max_history: u32, pub depth_tol: f32, pub normal_cos: f32,
+    pub same_object: u32, pub offset: [f32; 2] }
+/// One top-level object's rigid motion for the temporal accumulation with moving objects (include/rtw.h), 128 bytes: world points go
+/// current -> previous by a (x - from) + to, the normals surface_map writes by nrm; moving 0: the rest of the row is not read.
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RtwMotionRow { pub a: [f32; 9], pub from: [f32; 3], pub to: [f32; 3], pub nrm: [f32; 9], pub moving: u32, pub pad: [u32; 7] }
+/// The buffers of one temporal accumulation (include/rtw.h "temporal accumulation"), each host memory or, for a context's call, device
+/// memory of its GPU: the frame and its guides, the previous call's results and guides (all null on a first frame), the outputs
+/// (out_variance and out_prev_xy may be null).  A guide whose term is off may be null.
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct TemporalBuffers { pub cur: *const f32, pub depth: *const f32, pub normal: *const f32, pub idx: *const i32,
+    pub prev_color: *const f32, pub prev_moments: *const f32, pub prev_len: *const f32, pub prev_depth: *const f32, pub prev_normal: *const f32,
+    pub prev_idx: *const i32, pub out_color: *mut f32, pub out_moments: *mut f32, pub out_len: *mut f32, pub out_variance: *mut f32,
+    pub out_prev_xy: *mut f32 }
 /// `RTW_OPT_ATROUS_LAYOUT` (rtw.h): where a level of the a-trous filter reads its taps (0 the measured choice, 1 LDS tile, 2 global memory).
 pub const RTW_OPT_ATROUS_LAYOUT: u32 = 14;
 /// The ray rules of `rtw_ctx_surface_map` (rtw.h).
@@ -197,6 +214,21 @@ extern "C" {
     fn rtw_ctx_svgf_filter(ctx: *mut RtwCtx, img: *const f32, variance: *const f32, w: u32, h: u32, depth: *const f32, normal: *const f32,
                            idx: *const i32, albedo: *const f32, emitted: *const f32, p: *const RtwAtrous, vp: *const RtwSvgf, out: *mut f32,
                            out_variance: *mut f32, st: *mut RtwFilterStats) -> i32;
+    fn rtw_temporal_accumulate_motion(cur: *const f32, w: u32, h: u32, cam: *const RtwCamera, depth: *const f32, normal: *const f32,
+                                      idx: *const i32, prev_cam: *const RtwCamera, prev_color: *const f32, prev_moments: *const f32,
+                                      prev_len: *const f32, prev_depth: *const f32, prev_normal: *const f32, prev_idx: *const i32,
+                                      p: *const RtwTemporal, rows: *const RtwMotionRow, n_rows: u32, first: u32, out_color: *mut f32,
+                                      out_moments: *mut f32, out_len: *mut f32, out_variance: *mut f32, out_prev_xy: *mut f32,
+                                      st: *mut RtwFilterStats) -> i32;
+    fn rtw_ctx_temporal_accumulate_motion(ctx: *mut RtwCtx, cur: *const f32, w: u32, h: u32, cam: *const RtwCamera, depth: *const f32,
+                                          normal: *const f32, idx: *const i32, prev_cam: *const RtwCamera, prev_color: *const f32,
+                                          prev_moments: *const f32, prev_len: *const f32, prev_depth: *const f32, prev_normal: *const f32,
+                                          prev_idx: *const i32, p: *const RtwTemporal, rows: *const RtwMotionRow, n_rows: u32, first: u32,
+                                          out_color: *mut f32, out_moments: *mut f32, out_len: *mut f32, out_variance: *mut f32,
+                                          out_prev_xy: *mut f32, st: *mut RtwFilterStats) -> i32;
+    fn rtw_mesh_instance_motion(prev_poses: *const f32, cur_poses: *const f32, n: u32, rows_out: *mut RtwMotionRow, n_invalid: *mut u32) -> i32;
+    fn rtw_ctx_mesh_instance_motion(ctx: *mut RtwCtx, prev_poses: *const f32, cur_poses: *const f32, n: u32, rows_out: *mut RtwMotionRow,
+                                    n_invalid: *mut u32) -> i32;
     fn rtw_triangle_new(origin: *const f32, u: *const f32, v: *const f32, mat3: *const f32, emitted: *const f32,
                         color: *const f32, tex: i32, out: *mut RtwTriangle) -> i32;
     fn rtw_ctx_set_triangles(ctx: *mut RtwCtx, tris: *const RtwTriangle, n: u32) -> i32;
@@ -474,6 +506,25 @@ impl Renderer {
         check(unsafe { rtw_ctx_variance_estimate(self.ctx, moments, len, w, h, depth, normal, idx, p, out.as_mut_ptr(), &mut st) })?;
         Ok((out, st))
     }
+    /// The temporal accumulation on this context's GPU with moving objects (rtw_ctx_temporal_accumulate_motion): `rows` (may be null: the
+    /// world is static) holds the motion of the objects surface_map reports as first .. first + n_rows - 1; prev_cam None on a first frame.
+    #[allow(clippy::too_many_arguments)]
+    pub fn temporal_accumulate_motion(&mut self, b: &TemporalBuffers, w: u32, h: u32, cam: &RtwCamera, prev_cam: Option<&RtwCamera>, p: &RtwTemporal,
+                                      rows: *const RtwMotionRow, n_rows: u32, first: u32) -> Result<RtwFilterStats, RtwError> {
+        let mut st = RtwFilterStats::default();
+        let pc = prev_cam.map_or(std::ptr::null(), |c| c as *const RtwCamera);
+        check(unsafe { rtw_ctx_temporal_accumulate_motion(self.ctx, b.cur, w, h, cam, b.depth, b.normal, b.idx, pc, b.prev_color, b.prev_moments,
+                                                          b.prev_len, b.prev_depth, b.prev_normal, b.prev_idx, p, rows, n_rows, first, b.out_color,
+                                                          b.out_moments, b.out_len, b.out_variance, b.out_prev_xy, &mut st) })?;
+        Ok(st)
+    }
+    /// The motion rows of mesh placements on this context's GPU (rtw_ctx_mesh_instance_motion): poses [n][7] and rows_out [n], each host
+    /// or device memory; returns the number of refused poses.
+    pub fn mesh_instance_motion(&mut self, prev: *const f32, cur: *const f32, n: u32, rows_out: *mut RtwMotionRow) -> Result<u32, RtwError> {
+        let mut bad = 0u32;
+        check(unsafe { rtw_ctx_mesh_instance_motion(self.ctx, prev, cur, n, rows_out, &mut bad) })?;
+        Ok(bad)
+    }
     /// The variance-steered a-trous filter on this context's GPU (rtw_ctx_svgf_filter): `atrous_filter`'s arguments and a variance
     /// [h][w] f32; returns the filtered frame, the filtered variance and the stats.
     #[allow(clippy::type_complexity)]
@@ -698,6 +749,29 @@ pub fn mesh_instances_validate(tris: &[RtwTriangle], placements: &[RtwMeshInstan
     let t = if tris.is_empty() { std::ptr::null() } else { tris.as_ptr() };
     let p = if placements.is_empty() { std::ptr::null() } else { placements.as_ptr() };
     unsafe { rtw_mesh_instances_validate(t, tris.len() as u32, p, placements.len() as u32) }
+}
+
+/// The motion rows of mesh placements that went from `prev` to `cur` (rtw_mesh_instance_motion, host only): poses of position xyz,
+/// quaternion wxyz; returns the rows and the number of refused poses.
+pub fn mesh_instance_motion(prev: &[[f32; 7]], cur: &[[f32; 7]]) -> Result<(Vec<RtwMotionRow>, u32), RtwError> {
+    assert_eq!(prev.len(), cur.len());
+    let mut rows = vec![RtwMotionRow::default(); cur.len()];
+    let mut bad = 0u32;
+    check(unsafe { rtw_mesh_instance_motion(prev.as_ptr() as *const f32, cur.as_ptr() as *const f32, cur.len() as u32, rows.as_mut_ptr(), &mut bad) })?;
+    Ok((rows, bad))
+}
+
+/// rtw_temporal_accumulate_motion: the host form of `Renderer::temporal_accumulate_motion`, host memory only.
+#[allow(clippy::too_many_arguments)]
+pub fn temporal_accumulate_motion_host(b: &TemporalBuffers, w: u32, h: u32, cam: &RtwCamera, prev_cam: Option<&RtwCamera>, p: &RtwTemporal,
+                                       rows: &[RtwMotionRow], first: u32) -> Result<RtwFilterStats, RtwError> {
+    let mut st = RtwFilterStats::default();
+    let pc = prev_cam.map_or(std::ptr::null(), |c| c as *const RtwCamera);
+    let r = if rows.is_empty() { std::ptr::null() } else { rows.as_ptr() };
+    check(unsafe { rtw_temporal_accumulate_motion(b.cur, w, h, cam, b.depth, b.normal, b.idx, pc, b.prev_color, b.prev_moments, b.prev_len,
+                                                  b.prev_depth, b.prev_normal, b.prev_idx, p, r, rows.len() as u32, first, b.out_color, b.out_moments,
+                                                  b.out_len, b.out_variance, b.out_prev_xy, &mut st) })?;
+    Ok(st)
 }
 
 /// The closest placement of the mesh per ray on the host (rtw_mesh_instance_hits, the list walk).

@@ -554,7 +554,7 @@ int rtw_ctx_atrous_filter(rtw_ctx *ctx, const float *in, uint32_t w, uint32_t h,
  * The a-trous filter's temporal half (Schied et al. 2017, SVGF's accumulation): the previous call's accumulated colour, its two luminance
  * moments and its history length are fetched where each pixel's surface point lay in the previous view, accepted or rejected per tap
  * against the surface buffers, and blended with the new frame.  For cameras of rtw_viewport_new and the ray rule RTW_RAYS_PIXEL only; the
- * world is taken as static between the two frames.  Everything is f32 with one rounding per written operation (no fused multiply-add); a
+ * world is taken as static between the two frames (rtw_temporal_accumulate_motion, below, takes rigid motions of objects).  Everything is f32 with one rounding per written operation (no fused multiply-add); a
  * dot product is (x*x' + y*y') + z*z', a cross product x x y = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0).
  * Buffers, row-major: cur, *_color, *_normal [h][w][3] f32; *_moments [h][w][2] f32; *_len, *_depth, *_variance [h][w] f32; *_idx [h][w]
  * i32.  depth, normal, idx are what rtw_ctx_surface_map(.., RTW_RAYS_PIXEL, offset, ..) writes for `cam`, prev_depth, prev_normal, prev_idx
@@ -619,6 +619,74 @@ int rtw_ctx_temporal_accumulate(rtw_ctx *ctx, const float *cur, uint32_t w, uint
                                 const float *prev_moments, const float *prev_len, const float *prev_depth, const float *prev_normal,
                                 const int32_t *prev_idx, const RtwTemporal *params, float *out_color, float *out_moments, float *out_len,
                                 float *out_variance /* may be NULL */, RtwFilterStats *stats);
+
+/* ---- temporal accumulation with moving objects: one rigid motion per top-level object -- added within v4 ---------------------------------
+ * rtw_temporal_accumulate takes the world as static between the two frames.  Here a table of rows says, per top-level object, where a world
+ * point of the object lay in the previous frame; row k belongs to the object rtw_ctx_surface_map reports as idx first + k (mesh placement k
+ * is n_spheres + n_quads + n_instances + k).  Everything of "temporal accumulation" above holds, f32 with one rounding per written
+ * operation, but for a pixel that has a row:
+ *   Which pixels have a row:  rows != NULL, and with k = idx[p] - first formed without wrap-around (in 64 bits): 0 <= k < n_rows and
+ *     rows[k].moving != 0.  A miss (-1), an id below first, an id at or beyond first + n_rows and every other i32 value have no row, and no
+ *     address is formed from them.
+ *   Without a row:  the rule above, byte for byte, its per-call `static` shortcut included.
+ *   With a row r:   dir and P = cam.origin + dir * depth[p] as in the rule's "otherwise" line, under a static camera too;
+ *                   e = P - r.from;   P'_c = ((r.a[3c] e0 + r.a[3c+1] e1) + r.a[3c+2] e2) + r.to_c;   d = P' - prev_cam.origin;
+ *                   s, fx, fy from d as above; the four taps as above (never the static shortcut's one tap); and the normal test reads
+ *                   n'_c = (r.nrm[3c] n0 + r.nrm[3c+1] n1) + r.nrm[3c+2] n2  (n = normal[p])  in place of normal[p].
+ *                   A NaN in a, from or to gives an s or fx that is NaN -- "no history" by the comparisons above, never an index; a NaN in
+ *                   nrm fails the normal test when that is on.
+ * Points and normals of a mesh placement turn by different matrices (a placement meets a ray turned by its quaternion and reports the
+ * normal turned by the same quaternion, "mesh placements" below), so a row carries both; rtw_mesh_instance_motion makes such rows.
+ * idx must be given when rows is given, whether or not same_object is on (prev_idx only for that term).
+ * out_prev_xy [h][w][2] f32 (may be NULL) receives (fx, fy) as computed for every pixel of a call that has a history -- (i, j) under the
+ * shortcut; also where the candidate box then rejects the pixel -- and (NaN, NaN) on a first frame.
+ * RTW_E_INVALID, nothing written: the refusals above; rows with idx NULL; rows with n_rows == 0; first + n_rows beyond 2^31; out_prev_xy
+ * equal to out_color, out_moments, out_len or out_variance.  With rows NULL, n_rows and first are not read.
+ * With rows == NULL and out_prev_xy == NULL the calls write the bytes of rtw_temporal_accumulate / rtw_ctx_temporal_accumulate.
+ * What stays out: deforming meshes (rtw_ctx_refit_triangles: a point's previous place needs its barycentrics, not a row), the moving
+ * spheres of ray.time, a wider search when all four taps fail.  There is no rtw_mgpu_* form and no JSON form. */
+typedef struct RtwMotionRow {
+    float    a[9];      /* row-major 3 x 3: world points, current frame -> previous frame        */
+    float    from[3];   /* subtracted before a is applied (the object's current position)       */
+    float    to[3];     /* added after (its previous position)                                  */
+    float    nrm[9];    /* row-major 3 x 3: the normals surface_map writes, current -> previous */
+    uint32_t moving;    /* 0: the object did not move; nothing else of the row is read          */
+    uint32_t pad[7];
+} RtwMotionRow;
+/* The host form (one thread); stats as rtw_temporal_accumulate's. */
+int rtw_temporal_accumulate_motion(const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth, const float *normal,
+                                   const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color, const float *prev_moments,
+                                   const float *prev_len, const float *prev_depth, const float *prev_normal, const int32_t *prev_idx,
+                                   const RtwTemporal *params, const RtwMotionRow *rows /* may be NULL */, uint32_t n_rows, uint32_t first,
+                                   float *out_color, float *out_moments, float *out_len, float *out_variance /* may be NULL */,
+                                   float *out_prev_xy /* may be NULL */, RtwFilterStats *stats);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host form.  rows and out_prev_xy, like every other buffer, may be host memory
+ * (staged) or device memory of ctx's GPU.  One launch, one thread per pixel: with rows or out_prev_xy a second instantiation of the
+ * kernel, chosen on the host; without them the launch of rtw_ctx_temporal_accumulate. */
+int rtw_ctx_temporal_accumulate_motion(rtw_ctx *ctx, const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth,
+                                       const float *normal, const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color,
+                                       const float *prev_moments, const float *prev_len, const float *prev_depth,
+                                       const float *prev_normal, const int32_t *prev_idx, const RtwTemporal *params,
+                                       const RtwMotionRow *rows /* may be NULL */, uint32_t n_rows, uint32_t first, float *out_color,
+                                       float *out_moments, float *out_len, float *out_variance /* may be NULL */,
+                                       float *out_prev_xy /* may be NULL */, RtwFilterStats *stats);
+
+/* The rows of mesh placements that moved from prev_poses to cur_poses, both [n][7] f32 = position xyz, quaternion wxyz as
+ * rtw_ctx_move_mesh_instances takes them; rows_out [n] RtwMotionRow.  With (qn_c, pos_c) and (qn_p, pos_p) the normalised quaternion
+ * and position the walk uses for the two poses ("mesh placements" below), rotate(q, v) its rotation, e_j the unit vectors:
+ *   column j of a   = rotate(conj(qn_p), rotate(qn_c, e_j))      (a ray meets the placement at conj(qn).rotate(x') + position)
+ *   column j of nrm = rotate(qn_p, rotate(conj(qn_c), e_j))      (the reported normal is qn.rotate(n'))
+ *   from = pos_c;  to = pos_p;  pad = 0;  conj is three exact negations
+ *   moving = 0 exactly when the two poses agree in all 28 bytes; such a row is the identity (a = nrm = I, from = to = 0)
+ *   else a pose the placements refuse on either side (a component that is not finite, a quaternion of length 0 or not finite) gives
+ *   moving = 1, the quiet NaN 0x7fc00000 in all of a, from = to = 0 and the identity in nrm: its pixels have no history.
+ * The call still returns RTW_OK; *n_invalid (may be NULL) counts the rows with a refused pose on either side, equal poses included (a
+ * move leaves such a placement where it was).  RTW_E_INVALID: a NULL pointer, n == 0 or n > RTW_MAX_MESH_INSTANCES.  Host only, pure. */
+int rtw_mesh_instance_motion(const float *prev_poses, const float *cur_poses, uint32_t n, RtwMotionRow *rows_out, uint32_t *n_invalid);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host form, one thread per placement.  Each of the three buffers may be host
+ * memory (input staged, result copied back) or device memory of ctx's GPU (read and written in place).  Needs no scene. */
+int rtw_ctx_mesh_instance_motion(rtw_ctx *ctx, const float *prev_poses, const float *cur_poses, uint32_t n, RtwMotionRow *rows_out,
+                                 uint32_t *n_invalid);
 
 /* ---- variance estimate: a luminance variance for every pixel of an accumulated frame -- added within v4 ---------------------------------
  * SVGF's variance estimation (Schied et al. 2017, section 4.2): where the history is long enough the variance over time that the two

@@ -20,6 +20,7 @@ Reference surface mirrored (names and argument meaning):
   (extension) guided_filter(img, size, depth=, normal=, ids=, ..)   the bilateral filter steered by depth_map's buffers (Renderer.guided_filter)
   (extension) atrous_filter(frame, depth=, normal=, ids=, albedo=, emitted=, ..)   an edge-avoiding a-trous wavelet filter of linear f32 frames (Renderer.atrous_filter)
   (extension) temporal_accumulate(cur, cam, depth=, normal=, ids=, history=, ..)   frames of a sequence blended along reprojected pixels (Renderer.temporal_accumulate, TemporalDenoiser)
+  (extension) temporal_accumulate(.., motion=, motion_first=, out_prev_xy=)        ... with objects that moved rigidly since the previous frame (mesh_instance_motion, motion_rows)
   (extension) variance_estimate(moments, length, depth=, normal=, ids=, ..)   a luminance variance for every pixel of an accumulated frame (Renderer.variance_estimate)
   (extension) svgf_filter(frame, variance, depth=, normal=, ids=, albedo=, emitted=, ..)   the a-trous filter steered by that variance (Renderer.svgf_filter, SvgfDenoiser)
   Triangle.new (+ from_mesh), Scene(triangles=)       Rust2/src/objects/triangle.rs:28-124 (triangle_hits; Renderer.triangle_hits)
@@ -200,6 +201,19 @@ class RtwTemporal(C.Structure):
     and the pixel offset of both frames' guides (include/rtw.h)."""
     _fields_ = [("alpha", C.c_float), ("alpha_moments", C.c_float), ("max_history", C.c_uint32), ("depth_tol", C.c_float),
                 ("normal_cos", C.c_float), ("same_object", C.c_uint32), ("offset", C.c_float * 2)]
+
+
+class RtwMotionRow(C.Structure):
+    """One top-level object's rigid motion for temporal_accumulate(motion=): world points go current -> previous by a (x - from) + to, the
+    normals surface_map writes by nrm; moving 0: the object did not move and the rest is not read (include/rtw.h)."""
+    _fields_ = [("a", C.c_float * 9), ("from_", C.c_float * 3), ("to", C.c_float * 3), ("nrm", C.c_float * 9), ("moving", C.c_uint32),
+                ("pad", C.c_uint32 * 7)]
+
+
+# RtwMotionRow as a numpy record: what motion_rows and mesh_instance_motion return
+MOTION_ROW = np.dtype([("a", np.float32, (3, 3)), ("from", np.float32, 3), ("to", np.float32, 3), ("nrm", np.float32, (3, 3)),
+                       ("moving", np.uint32), ("pad", np.uint32, 7)])
+assert MOTION_ROW.itemsize == 128 == C.sizeof(RtwMotionRow)
 
 
 class RtwVarianceEstimate(C.Structure):
@@ -441,6 +455,11 @@ def lib() -> C.CDLL:
     L.rtw_temporal_accumulate.argtypes = ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwCamera)] + [C.c_void_p] * 3 + [C.POINTER(RtwCamera)] +
                                           [C.c_void_p] * 6 + [C.POINTER(RtwTemporal)] + [C.c_void_p] * 4 + [C.POINTER(RtwFilterStats)])
     L.rtw_ctx_temporal_accumulate.argtypes = [C.c_void_p] + L.rtw_temporal_accumulate.argtypes
+    L.rtw_temporal_accumulate_motion.argtypes = (L.rtw_temporal_accumulate.argtypes[:15] + [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 +
+                                                 [C.POINTER(RtwFilterStats)])
+    L.rtw_ctx_temporal_accumulate_motion.argtypes = [C.c_void_p] + L.rtw_temporal_accumulate_motion.argtypes
+    L.rtw_mesh_instance_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.rtw_ctx_mesh_instance_motion.argtypes = [C.c_void_p] + L.rtw_mesh_instance_motion.argtypes
     L.rtw_variance_estimate.argtypes = ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3 +
                                         [C.POINTER(RtwVarianceEstimate), C.c_void_p, C.POINTER(RtwFilterStats)])
     L.rtw_ctx_variance_estimate.argtypes = [C.c_void_p] + L.rtw_variance_estimate.argtypes
@@ -895,6 +914,29 @@ def mesh_top_refit(triangles, placements, moved=None, ouv=None):
     _check(lib().rtw_mesh_top_refit(arr, n, parr, pn, None if mv is None else mv.ctypes.data, None if a is None else a.ctypes.data,
                                     nodes.ctypes.data, len(nodes), C.byref(nn), rows.ctypes.data, C.byref(lw), C.byref(bad)), "rtw_mesh_top_refit")
     return nodes[:nn.value].copy(), rows[:pn].copy(), lw.value, bad.value
+
+
+def motion_rows(n: int) -> np.ndarray:
+    """`n` static motion rows (MOTION_ROW records: moving = 0, a = nrm = I, from = to = 0) for temporal_accumulate(motion=): fill in those
+    of the spheres, quads and instances you moved yourself through set_scene (row k belongs to the object surface_map reports as
+    motion_first + k) and set their `moving` to 1."""
+    rows = np.zeros(int(n), MOTION_ROW)
+    rows["a"] = rows["nrm"] = np.eye(3, dtype=np.float32)
+    return rows
+
+
+def mesh_instance_motion(prev_poses, cur_poses):
+    """rtw_mesh_instance_motion (host only): the motion rows of mesh placements that went from prev_poses to cur_poses, each a list of
+    (position, quat) pairs or an [n][7] array as move_mesh_instances takes them.  Returns (rows [n] of MOTION_ROW, n_invalid): a placement
+    whose poses agree byte for byte has moving = 0; one with a pose the placements refuse has NaN in `a` (its pixels get no history) and
+    is counted in n_invalid.  Row k is placement k: pass motion_first = Renderer.mesh_instance_first()."""
+    pp, cp = _poses(prev_poses), _poses(cur_poses)
+    if len(pp) != len(cp):
+        raise ValueError(f"mesh_instance_motion: {len(pp)} previous poses, {len(cp)} current ones")
+    rows = np.zeros(len(cp), MOTION_ROW)
+    bad = C.c_uint32()
+    _check(lib().rtw_mesh_instance_motion(pp.ctypes.data, cp.ctypes.data, len(cp), rows.ctypes.data, C.byref(bad)), "rtw_mesh_instance_motion")
+    return rows, bad.value
 
 
 def depth_rays(cam: RtwCamera, width: int, height: int) -> np.ndarray:
@@ -1563,6 +1605,37 @@ class Renderer:
         del keep_p, keep_o
         return lw.value
 
+    def mesh_instance_motion(self, prev_poses, cur_poses):
+        """rtw_ctx_mesh_instance_motion: mesh_instance_motion's rows on this context's GPU, on its stream, one thread per placement; the same
+        bytes.  Each pose argument: a list of (position, quat) pairs or a numpy [n][7] array (staged), or a torch tensor, float32, contiguous,
+        on the context's device, read in place behind its producers on the stream of use_torch_stream.  Returns (rows, n_invalid): rows a
+        float32 tensor [n][32] on the device when either input is a tensor (hand it to temporal_accumulate(motion=) as it is), else [n] of
+        MOTION_ROW."""
+        what = "mesh_instance_motion"
+        pp, pn, keep_p = self._device_floats(prev_poses, 7, None, what, "n")
+        cp, cn, keep_c = self._device_floats(cur_poses, 7, None, what, "n")
+        if pn != cn:
+            raise ValueError(f"{what}: {pn} previous poses, {cn} current ones")
+        like = next((x for x in (cur_poses, prev_poses) if hasattr(x, "data_ptr")), None)
+        if like is not None:
+            import torch
+            rows = torch.empty((cn, 32), dtype=torch.float32, device=like.device)
+            rp = int(rows.data_ptr())
+        else:
+            rows = np.zeros(cn, MOTION_ROW)
+            rp = rows.ctypes.data
+        bad = C.c_uint32()
+        _check(lib().rtw_ctx_mesh_instance_motion(self._h, C.c_void_p(pp), C.c_void_p(cp), cn, C.c_void_p(rp), C.byref(bad)),
+               "rtw_ctx_mesh_instance_motion")
+        del keep_p, keep_c
+        return rows, bad.value
+
+    def mesh_instance_first(self) -> int:
+        """The top-level index surface_map reports for placement 0 of the context's scene: n_spheres + n_quads + n_instances (0 without a
+        scene) -- temporal_accumulate's motion_first for the rows of mesh_instance_motion."""
+        sc = self._scene
+        return 0 if sc is None else int(sc.pod.n_spheres) + int(sc.pod.n_quads) + int(sc.pod.n_instances)
+
     def mesh_top_dump(self):
         """rtw_ctx_mesh_top_dump: the context's top-level tree and placement rows as the device holds them now -- (nodes [n_nodes] of TOP_NODE,
         rows [n][8] float32 = normalised quaternion w, x, y, z, position, 0)."""
@@ -1955,7 +2028,8 @@ class Renderer:
         _check(lib().rtw_ctx_atrous_filter(self._h, *args, C.byref(prm), dst, C.byref(st)), "rtw_ctx_atrous_filter")
         return out, st
 
-    def temporal_accumulate(self, cur, cam: RtwCamera, depth, normal=None, ids=None, history=None, out_color=None, **params):
+    def temporal_accumulate(self, cur, cam: RtwCamera, depth, normal=None, ids=None, history=None, out_color=None, motion=None,
+                            motion_first: int = 0, out_prev_xy=None, **params):
         """Temporal accumulation of a linear float32 frame [h][w][3] on this context's GPU (rtw_ctx_temporal_accumulate, include/rtw.h): the
         previous call's accumulated colour, luminance moments and history length are fetched where each pixel's surface point lay in the
         previous view, each of the four taps accepted or rejected against the guides, and blended with `cur`.  depth [h][w] float32, normal
@@ -1966,9 +2040,15 @@ class Renderer:
         one.  out_color: None -> new; or an array / tensor of the frame's shape, which may be `cur`, never history["color"].
         Returns (history, variance [h][w], RtwFilterStats): history = dict(color, moments, len, depth, normal, idx, cam) holds the results
         and THIS call's guides (not copied: leave them unchanged until the next call has read them) and a copy of cam.  History coverage is
-        (history["len"] > 1).mean()."""
+        (history["len"] > 1).mean().
+        Moving objects (rtw_ctx_temporal_accumulate_motion): motion -- rows of MOTION_ROW (motion_rows, mesh_instance_motion), a float32
+        array [n][32], or a contiguous float32 tensor [n][32] on the context's device -- gives the rigid motion of the objects surface_map
+        reports as motion_first .. motion_first + n - 1; their pixels are carried into the previous frame before they are projected.  It
+        needs `ids`, whether or not same_object is on.  out_prev_xy: True, or an array / tensor [h][w][2], receives where each pixel lay in
+        the previous view (NaN on a first frame) and is returned as history["prev_xy"].  With all three at their defaults the call is
+        rtw_ctx_temporal_accumulate."""
         return _temporal_call(lib().rtw_ctx_temporal_accumulate, "rtw_ctx_temporal_accumulate", (self._h,), self._on_device, cur, cam, depth,
-                              normal, ids, history, out_color, params)
+                              normal, ids, history, out_color, params, motion, motion_first, out_prev_xy, lib().rtw_ctx_temporal_accumulate_motion)
 
     def variance_estimate(self, moments, length, depth=None, normal=None, ids=None, min_history: int = SVGF_DEFAULTS["min_history"],
                           radius: int = SVGF_DEFAULTS["radius"], sigma_depth: float = SVGF_DEFAULTS["sigma_depth"],
@@ -2255,8 +2335,30 @@ def atrous_filter(frame, depth=None, normal=None, ids=None, albedo=None, emitted
     return out, st
 
 
-def _temporal_call(fn, fn_name, head, on_device, cur, cam, depth, normal, ids, history, out_color, params):
-    """rtw_temporal_accumulate / rtw_ctx_temporal_accumulate from the Python arguments of temporal_accumulate: (history, variance, stats)."""
+def _motion_pointer(motion, on_device, keep, who):
+    """(pointer, n_rows) of temporal_accumulate's motion argument."""
+    if hasattr(motion, "data_ptr"):
+        if on_device is None or not on_device(motion) or motion.dim() != 2 or motion.shape[1] != 32 or motion.shape[0] == 0:
+            raise ValueError(f"{who}: motion must be a contiguous float32 tensor of shape [n][32] on the context's device")
+        keep.append(motion)
+        return C.c_void_p(int(motion.data_ptr())), int(motion.shape[0])
+    a = np.asarray(motion)
+    if a.dtype == MOTION_ROW and a.ndim == 1:
+        b = np.ascontiguousarray(a)
+    elif a.ndim == 2 and a.shape[1] == 32 and a.dtype == np.float32:
+        b = np.ascontiguousarray(a)
+    else:
+        raise ValueError(f"{who}: motion must be rows of MOTION_ROW or a float32 array of shape [n][32]")
+    if len(b) == 0:
+        raise ValueError(f"{who}: motion holds no row")
+    keep.append(b)
+    return C.c_void_p(b.ctypes.data), len(b)
+
+
+def _temporal_call(fn, fn_name, head, on_device, cur, cam, depth, normal, ids, history, out_color, params, motion=None, motion_first=0,
+                   out_prev_xy=None, fn_motion=None):
+    """rtw_temporal_accumulate / rtw_ctx_temporal_accumulate from the Python arguments of temporal_accumulate: (history, variance, stats).
+    With motion or out_prev_xy: fn_motion, the call with moving objects."""
     who = "temporal_accumulate"
     unknown = set(params) - set(TEMPORAL_DEFAULTS) - {"offset"}
     if unknown:
@@ -2291,20 +2393,30 @@ def _temporal_call(fn, fn_name, head, on_device, cur, cam, depth, normal, ids, h
             C.byref(prm), ptr("out_color", out["color"], np.float32, (h, w, 3), True), ptr("moments", out["moments"], np.float32, (h, w, 2), True),
             ptr("len", out["len"], np.float32, (h, w), True), ptr("variance", variance, np.float32, (h, w), True)]
     st = RtwFilterStats()
-    _check(fn(*head, *args, C.byref(st)), fn_name)
+    if motion is None and out_prev_xy is None and not motion_first:
+        _check(fn(*head, *args, C.byref(st)), fn_name)
+        return out, variance, st
+    rows, n_rows = (None, 0) if motion is None else _motion_pointer(motion, on_device, keep, who)
+    if out_prev_xy is not None and out_prev_xy is not False:
+        out["prev_xy"] = new(h, w, 2) if out_prev_xy is True else out_prev_xy
+    args[15:15] = [rows, n_rows, int(motion_first)]
+    args.append(ptr("out_prev_xy", out.get("prev_xy"), np.float32, (h, w, 2), True))
+    _check(fn_motion(*head, *args, C.byref(st)), fn_name + "_motion")
     return out, variance, st
 
 
-def temporal_accumulate(cur, cam: RtwCamera, depth, normal=None, ids=None, history=None, out_color=None, **params):
-    """The temporal accumulation on the host (rtw_temporal_accumulate), the bytes of Renderer.temporal_accumulate; numpy arrays only.
-    Arguments and result as there."""
-    return _temporal_call(lib().rtw_temporal_accumulate, "rtw_temporal_accumulate", (), None, cur, cam, depth, normal, ids, history, out_color, params)
+def temporal_accumulate(cur, cam: RtwCamera, depth, normal=None, ids=None, history=None, out_color=None, motion=None, motion_first: int = 0,
+                        out_prev_xy=None, **params):
+    """The temporal accumulation on the host (rtw_temporal_accumulate, with motion or out_prev_xy rtw_temporal_accumulate_motion), the
+    bytes of Renderer.temporal_accumulate; numpy arrays only.  Arguments and result as there."""
+    return _temporal_call(lib().rtw_temporal_accumulate, "rtw_temporal_accumulate", (), None, cur, cam, depth, normal, ids, history, out_color, params,
+                          motion, motion_first, out_prev_xy, lib().rtw_temporal_accumulate_motion)
 
 
 class TemporalDenoiser:
     """Python only: a sequence driver around Renderer.temporal_accumulate for Viewport cameras and whole frames (part_count 1).
-    `params`: temporal_accumulate's keyword arguments (TEMPORAL_DEFAULTS), but for offset, which is (0.5, 0.5).  The scene is taken as
-    static from one step to the next."""
+    `params`: temporal_accumulate's keyword arguments (TEMPORAL_DEFAULTS), but for offset, which is (0.5, 0.5).  The scene is static
+    from one step to the next unless `motion` says otherwise."""
 
     def __init__(self, renderer, **params):
         if "offset" in params:
@@ -2315,8 +2427,8 @@ class TemporalDenoiser:
         """Drop the history: the next step starts a sequence."""
         self.history = None
 
-    def step(self, cam: RtwCamera, params: RtwParams, **atrous):
-        """One frame: params.seed is advanced by one (in `params`), the frame rendered at gamma 1, the guides taken from surface_map at the
+    def step(self, cam: RtwCamera, params: RtwParams, motion=None, motion_first: int = 0, **atrous):
+        """One frame (motion, motion_first: temporal_accumulate's, the motion of the scene's objects since the previous step): params.seed is advanced by one (in `params`), the frame rendered at gamma 1, the guides taken from surface_map at the
         pixel centres, the frame accumulated onto the history, atrous_filter (keyword arguments: its own) run on the accumulated colour
         with albedo and emission, and params.gamma applied as render_denoised does.  Returns (frame, accumulated, variance, stats): frame
         the filtered [h][w][3] float32 image, accumulated the linear accumulated colour (the history's), variance [h][w], stats a dict of
@@ -2334,7 +2446,7 @@ class TemporalDenoiser:
             params.gamma = gamma
         g = r.surface_map(cam, params.width, params.height, params.mint, params.maxt, params.integrator, RAYS_PIXEL, (0.5, 0.5), accel=params.accel)
         self.history, variance, st_t = r.temporal_accumulate(cur, cam, depth=g["depth"], normal=g["normal"], ids=g["idx"], history=self.history,
-                                                             offset=(0.5, 0.5), **self.params)
+                                                             motion=motion, motion_first=motion_first, offset=(0.5, 0.5), **self.params)
         acc = self.history["color"]
         frame, st_a = r.atrous_filter(acc, depth=g["depth"], normal=g["normal"], ids=g["idx"], albedo=g["albedo"], emitted=g["emitted"], **atrous)
         if gamma != 1.0:
@@ -2417,8 +2529,8 @@ class SvgfDenoiser(TemporalDenoiser):
     Renderer.svgf_filter) where TemporalDenoiser has the fixed a-trous filter.  `params` as there."""
 
     def step(self, cam: RtwCamera, params: RtwParams, min_history: int = SVGF_DEFAULTS["min_history"], radius: int = SVGF_DEFAULTS["radius"],
-             **svgf):
-        """One frame: rendered, its guides taken and accumulated as TemporalDenoiser.step does; variance_estimate (min_history, radius; the
+             motion=None, motion_first: int = 0, **svgf):
+        """One frame (motion, motion_first as TemporalDenoiser.step's): rendered, its guides taken and accumulated as TemporalDenoiser.step does; variance_estimate (min_history, radius; the
         guide sigmas and same_object those of **svgf) on the new history's moments and length; svgf_filter (keyword arguments: its own) on
         the accumulated colour with albedo and emission; params.gamma applied.  Returns (frame, accumulated, variance, stats): variance is
         the estimate the filter was steered by; stats holds render, temporal, variance and svgf (RtwStats and three RtwFilterStats),
@@ -2435,7 +2547,7 @@ class SvgfDenoiser(TemporalDenoiser):
             params.gamma = gamma
         g = r.surface_map(cam, params.width, params.height, params.mint, params.maxt, params.integrator, RAYS_PIXEL, (0.5, 0.5), accel=params.accel)
         self.history, _, st_t = r.temporal_accumulate(cur, cam, depth=g["depth"], normal=g["normal"], ids=g["idx"], history=self.history,
-                                                      offset=(0.5, 0.5), **self.params)
+                                                      motion=motion, motion_first=motion_first, offset=(0.5, 0.5), **self.params)
         acc = self.history["color"]
         guide_kw = {k: svgf[k] for k in ("sigma_depth", "sigma_normal", "same_object") if k in svgf}
         variance, st_v = r.variance_estimate(self.history["moments"], self.history["len"], depth=g["depth"], normal=g["normal"], ids=g["idx"],

@@ -51,6 +51,26 @@ __global__ __launch_bounds__(RTW_MESH_CLIMB_BLOCK) void mesh_top_climb_kernel(Tr
     }
 }
 
+// rtw_ctx_mesh_instance_motion: thread t forms the motion row of placement t (mesh_motion_row, rtw_refit.h -- the definition the host form runs)
+// in registers and stores its 128 bytes as eight 16-byte stores: the rows of consecutive threads are consecutive in memory, so a wave's
+// stores of one slot cover 64 lines that the next seven slots complete in L2.
+__global__ __launch_bounds__(RTW_MESH_MOVE_BLOCK) void mesh_motion_kernel(const float *prev_poses, const float *cur_poses, uint32_t n, RtwMotionRow *rows,
+                                                                          uint32_t *n_invalid) {
+    const uint32_t t = blockIdx.x * RTW_MESH_MOVE_BLOCK + threadIdx.x;
+    if (t >= n) return;
+    float prev[7], cur[7];
+    for (int k = 0; k < 7; k++) { prev[k] = prev_poses[7 * (size_t)t + k]; cur[k] = cur_poses[7 * (size_t)t + k]; }
+    RtwMotionRow r;
+    const bool invalid = mesh_motion_row(prev, cur, r);
+    rows[t] = r;
+    if (invalid) atomicAdd(n_invalid, 1u);
+}
+
+void launch_mesh_motion(const float *prev_poses, const float *cur_poses, uint32_t n, RtwMotionRow *rows, uint32_t *n_invalid, hipStream_t stream) {
+    hipLaunchKernelGGL(mesh_motion_kernel, dim3((n + RTW_MESH_MOVE_BLOCK - 1) / RTW_MESH_MOVE_BLOCK), dim3(RTW_MESH_MOVE_BLOCK), 0, stream, prev_poses,
+                       cur_poses, n, rows, n_invalid);
+}
+
 void launch_mesh_move(TriNode *top, const uint32_t *top_order, f4 *rows, const float *poses, const TriNode *root, const uint32_t *order,
                       const uint32_t *first, const uint32_t *d_first, uint32_t n_heights, bool one_group, uint32_t *counts, hipStream_t stream) {
     if (n_heights == 0) return;

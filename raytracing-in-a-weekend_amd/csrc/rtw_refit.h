@@ -173,6 +173,40 @@ __host__ __device__ inline MeshMoveCount mesh_top_refit_leaf(TriNode *nodes, con
 }
 // (The inner step is refit_inner_node, above.)
 
+// The motion row of one placement that went from pose `prev` to pose `cur` ([7] f32 each), the whole of what either side runs for it
+// (rtw_mesh_instance_motion, rtw.h): with (qn, pos) the rows of mesh_pose_rows -- the very quaternion the walk turns rays by --, points go
+// current -> previous by R(conj qn_p) R(qn_c), the normals the hit records carry by R(qn_p) R(conj qn_c); the columns are the images of the
+// unit vectors under quat_rotate_n.  Equal bytes: the identity row, moving 0.  A refused pose: moving 1 and NaN in a.  Returns whether a
+// pose was refused (equal poses included).
+__host__ __device__ inline bool mesh_motion_row(const float *prev, const float *cur, RtwMotionRow &r) {
+    bool same = true;
+    for (int k = 0; k < 7; k++) same = same && mesh_bits(prev[k]) == mesh_bits(cur[k]);
+    f4 ca, cb, pa, pb;
+    const bool ok_c = mesh_pose_rows(cur, ca, cb), ok_p = mesh_pose_rows(prev, pa, pb);
+    for (int k = 0; k < 9; k++) r.a[k] = r.nrm[k] = (k % 4 == 0) ? 1.0f : 0.0f;
+    for (int k = 0; k < 3; k++) r.from[k] = r.to[k] = 0.0f;
+    for (int k = 0; k < 7; k++) r.pad[k] = 0u;
+    r.moving = same ? 0u : 1u;
+    if (same) return !ok_c;
+    if (!ok_c || !ok_p) {
+        for (int k = 0; k < 9; k++) r.a[k] = __builtin_bit_cast(float, 0x7fc00000u);
+        return true;
+    }
+    const quat qc = qmk(ca.x, ca.y, ca.z, ca.w), qp = qmk(pa.x, pa.y, pa.z, pa.w);
+    const quat qcc = qmk(qc.w, -qc.x, -qc.y, -qc.z), qpc = qmk(qp.w, -qp.x, -qp.y, -qp.z);
+    for (int j = 0; j < 3; j++) {
+        const float e0 = j == 0 ? 1.0f : 0.0f, e1 = j == 1 ? 1.0f : 0.0f, e2 = j == 2 ? 1.0f : 0.0f;
+        float x, y, z;
+        quat_rotate_n(qc, e0, e1, e2, x, y, z);
+        quat_rotate_n(qpc, x, y, z, r.a[j], r.a[3 + j], r.a[6 + j]);
+        quat_rotate_n(qcc, e0, e1, e2, x, y, z);
+        quat_rotate_n(qp, x, y, z, r.nrm[j], r.nrm[3 + j], r.nrm[6 + j]);
+    }
+    r.from[0] = cb.x; r.from[1] = cb.y; r.from[2] = cb.z;
+    r.to[0] = pb.x; r.to[1] = pb.y; r.to[2] = pb.z;
+    return false;
+}
+
 // ---- host (rtw_tri.cpp) ---------------------------------------------------------------------------------------------------------------------
 // The order a refit visits the nodes in: `order` holds every node index sorted by height (a leaf: 0; an inner node: 1 + the higher child),
 // ties by index; height h owns order[first[h] .. first[h + 1]), first.size() = heights + 1.  Height 0 is the leaf pass, each further height
@@ -207,5 +241,8 @@ void launch_refit_climb(TriNode *nodes, const uint32_t *order, const uint32_t *f
 inline bool mesh_climb_one_group(uint32_t n_nodes) { return n_nodes <= RTW_MESH_CLIMB_ONE_GROUP_MAX; }
 void launch_mesh_move(TriNode *top, const uint32_t *top_order, f4 *rows, const float *poses, const TriNode *root, const uint32_t *order,
                       const uint32_t *first, const uint32_t *d_first, uint32_t n_heights, bool one_group, uint32_t *counts, hipStream_t stream);
+// rtw_ctx_mesh_instance_motion on `stream`: one thread per placement running mesh_motion_row; device pointers, *n_invalid (device u32, zeroed by
+// the caller) receives the count of refused poses.  Allocates nothing.
+void launch_mesh_motion(const float *prev_poses, const float *cur_poses, uint32_t n, RtwMotionRow *rows, uint32_t *n_invalid, hipStream_t stream);
 
 } // namespace rtw

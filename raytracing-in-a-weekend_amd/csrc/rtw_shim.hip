@@ -8,6 +8,7 @@
 #include "rtw_filter.h"
 #include "rtw_atrous_dev.h"
 #include "rtw_temporal_dev.h"
+#include "rtw_temporal.h"
 #include "rtw_svgf_dev.h"
 #include "rtw_devmem.h"
 #include "rtw_exp.h"
@@ -59,6 +60,9 @@ struct MeshMem {
                                          // the staging of host poses, the counts of invalid poses and of placements beyond reach
 };
 #define MOVE_POSE_BYTES (7 * sizeof(float))      // one placement of a move's input: position, quaternion
+// Buffers of rtw_ctx_mesh_instance_motion, grown on demand and kept until the context is destroyed: the staging of host poses and of rows for a
+// host result, the count of refused poses and its pinned read-back.  A call on device buffers of a size seen before allocates nothing.
+struct MotionMem { DevMem prev, cur, rows, bad; PinnedMem h_bad; };
 struct ScratchMem {
     DevMem queue, stats;
     PinnedMem h_stats;                   // pinned: the counter read-back is a true async copy
@@ -100,6 +104,7 @@ struct rtw_ctx {
                                          // (rtw_svgf.hip), created on the first call of any of them
     TemporalScratch *temporal = nullptr; // buffers of rtw_ctx_temporal_accumulate (rtw_temporal.hip), created on its first call
     FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
+    MotionMem motion_mem;                // buffers of rtw_ctx_mesh_instance_motion
     // Rust2 triangles of the scene (rtw_ctx_set_triangles; cleared by rtw_ctx_set_scene)
     DevTris tris{};                      // tris.nodes stays null here: a render sets it (tri_view) when the tree may be used
     bool tri_tree = false;               // no triangle breaks the cull's derivation (DESIGN.md "Rust2 triangles")
@@ -1447,7 +1452,60 @@ int rtw_ctx_temporal_accumulate(rtw_ctx *c, const float *cur, uint32_t w, uint32
     if (c->pend.active) return RTW_E_INVALID;
     const TemporalBuffers b = { cur, depth, normal, idx, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
                                 out_color, out_moments, out_len, out_variance };
-    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, stats, &g_last_hip);
+    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, nullptr, stats, &g_last_hip);
+}
+
+// ... and with moving objects (rtw.h "temporal accumulation with moving objects"): without rows and prev_xy the same launch
+int rtw_ctx_temporal_accumulate_motion(rtw_ctx *c, const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth, const float *normal,
+                                       const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color, const float *prev_moments,
+                                       const float *prev_len, const float *prev_depth, const float *prev_normal, const int32_t *prev_idx,
+                                       const RtwTemporal *p, const RtwMotionRow *rows, uint32_t n_rows, uint32_t first, float *out_color,
+                                       float *out_moments, float *out_len, float *out_variance, float *out_prev_xy, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    const TemporalBuffers b = { cur, depth, normal, idx, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
+                                out_color, out_moments, out_len, out_variance };
+    const TemporalMotion m = { rows, n_rows, first, out_prev_xy };
+    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, &m, stats, &g_last_hip);
+}
+
+// The motion rows of moved placements (rtw_mesh_move.hip) on this context's GPU and stream; the scene is not involved.
+int rtw_ctx_mesh_instance_motion(rtw_ctx *c, const float *prev_poses, const float *cur_poses, uint32_t n, RtwMotionRow *rows_out, uint32_t *n_invalid) {
+    if (!c || !prev_poses || !cur_poses || !rows_out || n == 0 || n > RTW_MAX_MESH_INSTANCES) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    MotionMem &m = c->motion_mem;
+    const size_t pose_bytes = MOVE_POSE_BYTES * (size_t)n, row_bytes = sizeof(RtwMotionRow) * (size_t)n;
+    HIP_TRY(m.bad.reserve(sizeof(uint32_t)));
+    HIP_TRY(m.h_bad.reserve(sizeof(uint32_t)));
+    const float *d_prev = prev_poses, *d_cur = cur_poses;
+    RtwMotionRow *d_rows = rows_out;
+    hipError_t e = hipSuccess;
+    if (!on_device(prev_poses, c->device)) {
+        HIP_TRY(m.prev.reserve(pose_bytes));
+        e = hipMemcpyAsync(m.prev.ptr, prev_poses, pose_bytes, hipMemcpyDefault, c->stream);
+        d_prev = m.prev.as<const float>();
+    }
+    if (e == hipSuccess && !on_device(cur_poses, c->device)) {
+        HIP_TRY(m.cur.reserve(pose_bytes));
+        e = hipMemcpyAsync(m.cur.ptr, cur_poses, pose_bytes, hipMemcpyDefault, c->stream);
+        d_cur = m.cur.as<const float>();
+    }
+    if (!on_device(rows_out, c->device)) {
+        HIP_TRY(m.rows.reserve(row_bytes));
+        d_rows = m.rows.as<RtwMotionRow>();
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(m.bad.ptr, 0, sizeof(uint32_t), c->stream);
+    if (e == hipSuccess) {
+        launch_mesh_motion(d_prev, d_cur, n, d_rows, m.bad.as<uint32_t>(), c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && d_rows != rows_out) e = hipMemcpyAsync(rows_out, d_rows, row_bytes, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(m.h_bad.ptr, m.bad.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (const int rc = call_status(c, e)) return rc;
+    if (n_invalid) *n_invalid = *m.h_bad.as<uint32_t>();
+    return RTW_OK;
 }
 
 // The variance estimate and the variance-steered a-trous filter (rtw_svgf.hip) likewise, on the a-trous filter's scratch.

@@ -3,6 +3,9 @@
 // plan, formed once per call on the host by temporal_check, so the device writes the host form's bytes: f32, one rounding per written
 // operation under -ffp-contract=off, dot products as (x*x' + y*y') + z*z', the four taps in the order (x0, y0), (x0+1, y0), (x0, y0+1),
 // (x0+1, y0+1).
+// With moving objects (rtw.h "temporal accumulation with moving objects") the same definition is instantiated a second time,
+// temporal_pixel_t<true>: a pixel whose object has a row in the caller's table carries its world point into the previous frame first
+// (temporal_row, temporal_project_row) and takes the four taps; every other pixel runs the code of temporal_pixel_t<false>.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rtw_pixel_ray.h"
@@ -29,6 +32,8 @@ struct TemporalPlan {
 struct TemporalFrame { const float *cur, *depth, *normal; const int32_t *idx; };
 struct TemporalHistory { const float *color, *moments, *len, *depth, *normal; const int32_t *idx; };
 struct TemporalOut { float *color, *moments, *len, *variance; };
+// What the calls with motion add (include/rtw.h "temporal accumulation with moving objects"): the table (rows null: none) and prev_xy (may be null)
+struct TemporalMotion { const RtwMotionRow *rows; uint32_t n_rows, first; float *prev_xy; };
 
 // What the counted taps add up to.
 struct TemporalSum { float w, c0, c1, c2, m1, m2, len; };
@@ -59,6 +64,36 @@ __host__ __device__ inline bool temporal_project(const TemporalPlan &pl, uint32_
         fx = ((temporal_dot(d, pl.a) / s - pl.pa) / pl.ua) - pl.ox;
         fy = ((temporal_dot(d, pl.b) / s - pl.pb) / pl.vb) - pl.oy;
     }
+    return s > 0.0f && fx > -1.0f && fx < (float)pl.w && fy > -1.0f && fy < (float)pl.h;
+}
+
+// The row of the object `id`, or null: k = id - first without wrap-around, 0 <= k < n_rows, rows[k].moving != 0.  No address is formed
+// from any other id.
+__host__ __device__ inline const RtwMotionRow *temporal_row(const TemporalMotion &mo, int32_t id) {
+    const int64_t k = (int64_t)id - (int64_t)mo.first;
+    if (k < 0 || k >= (int64_t)mo.n_rows) return nullptr;
+    const RtwMotionRow *r = mo.rows + k;
+    return r->moving != 0u ? r : nullptr;
+}
+
+// temporal_project for a pixel of a moving object: its world point is carried into the previous frame by the row before it is projected,
+// under a static camera too.  A NaN in the row ends as an s or fx that is NaN: false.
+__host__ __device__ inline bool temporal_project_row(const TemporalPlan &pl, const RtwMotionRow &r, uint32_t i, uint32_t j, float depth, float &fx,
+                                                     float &fy, float &s) {
+    float dir[3];
+    pixel_ray_dir(pl.cam, i, j, pl.ox, pl.oy, dir[0], dir[1], dir[2]);
+    float e[3], d[3];
+    for (int k = 0; k < 3; k++) {
+        const float P = pl.cam.origin[k] + dir[k] * depth;
+        e[k] = P - r.from[k];
+    }
+    for (int k = 0; k < 3; k++) {
+        const float Pp = ((r.a[3 * k] * e[0] + r.a[3 * k + 1] * e[1]) + r.a[3 * k + 2] * e[2]) + r.to[k];
+        d[k] = Pp - pl.po[k];
+    }
+    s = temporal_dot(d, pl.n) / pl.pn;
+    fx = ((temporal_dot(d, pl.a) / s - pl.pa) / pl.ua) - pl.ox;
+    fy = ((temporal_dot(d, pl.b) / s - pl.pb) / pl.vb) - pl.oy;
     return s > 0.0f && fx > -1.0f && fx < (float)pl.w && fy > -1.0f && fy < (float)pl.h;
 }
 
@@ -99,9 +134,11 @@ __host__ __device__ inline float temporal_blend_factor(float n_, float floor_) {
     return a_ < floor_ ? floor_ : a_;
 }
 
-// Pixel (i, j).  o.color may be f.cur: the pixel's own cur is read before anything is written.
-__host__ __device__ inline void temporal_pixel(const TemporalPlan &pl, const TemporalFrame &f, const TemporalHistory &hs, const TemporalOut &o,
-                                               uint32_t i, uint32_t j) {
+// Pixel (i, j).  o.color may be f.cur: the pixel's own cur is read before anything is written.  MOTION: the calls with a table of rows or
+// prev_xy; false compiles to the rule without them (`mo` is not read), which is what rtw_temporal_accumulate and its kernel run.
+template <bool MOTION>
+__host__ __device__ inline void temporal_pixel_t(const TemporalPlan &pl, const TemporalFrame &f, const TemporalHistory &hs, const TemporalOut &o,
+                                                 const TemporalMotion &mo, uint32_t i, uint32_t j) {
     const size_t p = (size_t)j * pl.w + (size_t)i;
     const float r = f.cur[3 * p], g = f.cur[3 * p + 1], b = f.cur[3 * p + 2];
     const float L = (0.2126f * r + 0.7152f * g) + 0.0722f * b;
@@ -109,11 +146,27 @@ __host__ __device__ inline void temporal_pixel(const TemporalPlan &pl, const Tem
 
     TemporalSum t = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
     float fx, fy, s;
-    if (pl.has_prev && temporal_project(pl, i, j, f.depth[p], fx, fy, s)) {
+    const RtwMotionRow *row = nullptr;
+    bool cand = false;
+    if (pl.has_prev) {
+        if (MOTION && mo.rows) row = temporal_row(mo, f.idx[p]);
+        cand = (MOTION && row) ? temporal_project_row(pl, *row, i, j, f.depth[p], fx, fy, s) : temporal_project(pl, i, j, f.depth[p], fx, fy, s);
+    }
+    if (MOTION && mo.prev_xy) {
+        mo.prev_xy[2 * p] = pl.has_prev ? fx : __builtin_nanf("");
+        mo.prev_xy[2 * p + 1] = pl.has_prev ? fy : __builtin_nanf("");
+    }
+    if (cand) {
         float np[3] = { 0.0f, 0.0f, 0.0f };
-        if (pl.terms & TEMPORAL_NORMAL) { np[0] = f.normal[3 * p]; np[1] = f.normal[3 * p + 1]; np[2] = f.normal[3 * p + 2]; }
+        if (pl.terms & TEMPORAL_NORMAL) {
+            np[0] = f.normal[3 * p]; np[1] = f.normal[3 * p + 1]; np[2] = f.normal[3 * p + 2];
+            if (MOTION && row) {
+                const float n0 = np[0], n1 = np[1], n2 = np[2];
+                for (int k = 0; k < 3; k++) np[k] = (row->nrm[3 * k] * n0 + row->nrm[3 * k + 1] * n1) + row->nrm[3 * k + 2] * n2;
+            }
+        }
         const int32_t id = (pl.terms & TEMPORAL_IDX) ? f.idx[p] : 0;
-        if (pl.is_static) {
+        if (pl.is_static && !(MOTION && row)) {
             temporal_tap(pl, hs, (int)i, (int)j, 1.0f, s, np, id, t);                  // wx = wy = 0: the other three weigh 0
         } else {
             const float xf = __builtin_floorf(fx), yf = __builtin_floorf(fy);
@@ -156,11 +209,18 @@ __host__ __device__ inline void temporal_pixel(const TemporalPlan &pl, const Tem
         o.variance[p] = v > 0.0f ? v : 0.0f;
     }
 }
+__host__ __device__ inline void temporal_pixel(const TemporalPlan &pl, const TemporalFrame &f, const TemporalHistory &hs, const TemporalOut &o,
+                                               uint32_t i, uint32_t j) {
+    temporal_pixel_t<false>(pl, f, hs, o, TemporalMotion{ nullptr, 0u, 0u, nullptr }, i, j);
+}
 
 // Everything rtw_temporal_accumulate refuses (rtw.h); fills `pl`.  RTW_OK or RTW_E_INVALID.  (rtw_temporal.cpp)
 int temporal_check(const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth, const float *normal, const int32_t *idx,
                    const RtwCamera *prev_cam, const float *prev_color, const float *prev_moments, const float *prev_len, const float *prev_depth,
                    const float *prev_normal, const int32_t *prev_idx, const RtwTemporal *p, const float *out_color, const float *out_moments,
                    const float *out_len, TemporalPlan &pl);
+// ... and what the calls with motion refuse besides (rtw.h "temporal accumulation with moving objects")
+int temporal_check_motion(const int32_t *idx, const RtwMotionRow *rows, uint32_t n_rows, uint32_t first, const float *out_color,
+                          const float *out_moments, const float *out_len, const float *out_variance, const float *out_prev_xy);
 
 } // namespace rtw

@@ -1,5 +1,5 @@
-// rtw_temporal.hip -- temporal accumulation by reprojection (rtw_temporal.h) on the GPU: rtw_ctx_temporal_accumulate's
-// device path.
+// rtw_temporal.hip -- temporal accumulation by reprojection (rtw_temporal.h) on the GPU: the device path of
+// rtw_ctx_temporal_accumulate and rtw_ctx_temporal_accumulate_motion.
 //
 // One launch, one thread per pixel running temporal_pixel -- the host form's definition with the host form's plan, so its bytes.
 // Workgroup b covers the 32 x 8 pixels of tile (b % tiles_x, b / tiles_x): a wave is two rows of 32 pixels, so its loads of cur and of the
@@ -26,6 +26,16 @@ __global__ void __launch_bounds__(TBX * TBY) temporal_kernel(TemporalPlan pl, ui
     if (x < pl.w && y < pl.h) temporal_pixel(pl, f, hs, o, x, y);
 }
 
+// The same with a table of motion rows and / or prev_xy (rtw_ctx_temporal_accumulate_motion): a second instantiation, chosen on the host, so
+// that the kernel above stays what it is.  A pixel of a moving object loads its row (128 bytes, the same for every lane on the object) and
+// takes the four taps; the others run the code above.
+__global__ void __launch_bounds__(TBX * TBY) temporal_motion_kernel(TemporalPlan pl, uint32_t tiles_x, TemporalFrame f, TemporalHistory hs, TemporalOut o,
+                                                                    TemporalMotion mo) {
+    const uint32_t x = (blockIdx.x % tiles_x) * TBX + threadIdx.x % TBX;
+    const uint32_t y = (blockIdx.x / tiles_x) * TBY + threadIdx.x / TBX;
+    if (x < pl.w && y < pl.h) temporal_pixel_t<true>(pl, f, hs, o, mo, x, y);
+}
+
 float event_ms(hipEvent_t a, hipEvent_t b) {
     float ms = 0.0f;
     return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f;
@@ -37,6 +47,7 @@ struct TemporalScratch {
     DevMem cur, depth, normal, idx;                                      // the caller's host buffers, staged
     DevMem prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx;
     DevMem out_color, out_moments, out_len, out_variance;                // a result whose buffer is host memory
+    DevMem rows, out_prev_xy;                                            // (the calls with motion)
     hipEvent_t ev[2] = { nullptr, nullptr };
 };
 
@@ -53,12 +64,21 @@ void temporal_scratch_free(TemporalScratch *s) {
     } while (0)
 
 int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch **scratch, uint32_t w, uint32_t h, const RtwCamera *cam,
-                               const RtwCamera *prev_cam, const TemporalBuffers &b, const RtwTemporal *p, RtwFilterStats *stats, int *last_hip) {
+                               const RtwCamera *prev_cam, const TemporalBuffers &b, const RtwTemporal *p, const TemporalMotion *m, RtwFilterStats *stats,
+                               int *last_hip) {
     const auto t0 = std::chrono::steady_clock::now();
     TemporalPlan pl;
     const int rc = temporal_check(b.cur, w, h, cam, b.depth, b.normal, b.idx, prev_cam, b.prev_color, b.prev_moments, b.prev_len, b.prev_depth,
                                   b.prev_normal, b.prev_idx, p, b.out_color, b.out_moments, b.out_len, pl);
     if (rc != RTW_OK) return rc;
+    TemporalMotion mo = { nullptr, 0u, 0u, nullptr };
+    if (m && (m->rows || m->prev_xy)) {
+        const int rm = temporal_check_motion(b.idx, m->rows, m->n_rows, m->first, b.out_color, b.out_moments, b.out_len, b.out_variance, m->prev_xy);
+        if (rm != RTW_OK) return rm;
+        mo = *m;
+        if (!mo.rows) mo.n_rows = mo.first = 0u;
+    }
+    const bool motion = mo.rows || mo.prev_xy;
     TEMPORAL_TRY(hipSetDevice(device));
     if (!*scratch) {
         TemporalScratch *s = new (std::nothrow) TemporalScratch();
@@ -70,11 +90,11 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
     const size_t n_px = (size_t)w * h, f1 = n_px * sizeof(float), f2 = 2 * f1, f3 = 3 * f1;
 
     // the caller's buffers on the device: a host one is staged; a guide whose term is off is not touched
-    TemporalFrame f = { b.cur, b.depth, (pl.terms & TEMPORAL_NORMAL) ? b.normal : nullptr, (pl.terms & TEMPORAL_IDX) ? b.idx : nullptr };
+    TemporalFrame f = { b.cur, b.depth, (pl.terms & TEMPORAL_NORMAL) ? b.normal : nullptr, ((pl.terms & TEMPORAL_IDX) || mo.rows) ? b.idx : nullptr };
     TemporalHistory hs = { b.prev_color, b.prev_moments, b.prev_len, (pl.terms & TEMPORAL_DEPTH) ? b.prev_depth : nullptr,
                            (pl.terms & TEMPORAL_NORMAL) ? b.prev_normal : nullptr, (pl.terms & TEMPORAL_IDX) ? b.prev_idx : nullptr };
     struct Stage { const void **p; DevMem *m; size_t bytes; };
-    const Stage stages[10] = { { (const void **)&f.cur, &s->cur, f3 },
+    const Stage stages[11] = { { (const void **)&f.cur, &s->cur, f3 },
                                { (const void **)&f.depth, &s->depth, f1 },
                                { (const void **)&f.normal, &s->normal, f3 },
                                { (const void **)&f.idx, &s->idx, n_px * sizeof(int32_t) },
@@ -83,7 +103,8 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
                                { (const void **)&hs.len, &s->prev_len, f1 },
                                { (const void **)&hs.depth, &s->prev_depth, f1 },
                                { (const void **)&hs.normal, &s->prev_normal, f3 },
-                               { (const void **)&hs.idx, &s->prev_idx, n_px * sizeof(int32_t) } };
+                               { (const void **)&hs.idx, &s->prev_idx, n_px * sizeof(int32_t) },
+                               { (const void **)&mo.rows, &s->rows, (size_t)mo.n_rows * sizeof(RtwMotionRow) } };
     for (const Stage &st : stages) {
         if (!*st.p || on_device(*st.p, device)) continue;
         TEMPORAL_TRY(st.m->reserve(st.bytes));
@@ -92,10 +113,11 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
     }
     TemporalOut o = { b.out_color, b.out_moments, b.out_len, b.out_variance };
     struct Result { float **p; float *host; DevMem *m; size_t bytes; };
-    Result results[4] = { { &o.color, nullptr, &s->out_color, f3 },
+    Result results[5] = { { &o.color, nullptr, &s->out_color, f3 },
                           { &o.moments, nullptr, &s->out_moments, f2 },
                           { &o.len, nullptr, &s->out_len, f1 },
-                          { &o.variance, nullptr, &s->out_variance, f1 } };
+                          { &o.variance, nullptr, &s->out_variance, f1 },
+                          { &mo.prev_xy, nullptr, &s->out_prev_xy, f2 } };
     for (Result &r : results) {
         if (!*r.p || on_device(*r.p, device)) continue;
         TEMPORAL_TRY(r.m->reserve(r.bytes));
@@ -105,7 +127,9 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
 
     const uint32_t tiles_x = (w + TBX - 1) / TBX, tiles_y = (h + TBY - 1) / TBY;
     TEMPORAL_TRY(hipEventRecord(s->ev[0], stream));
-    hipLaunchKernelGGL(temporal_kernel, dim3((unsigned)((uint64_t)tiles_x * tiles_y)), dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o);
+    const dim3 grid((unsigned)((uint64_t)tiles_x * tiles_y));
+    if (motion) hipLaunchKernelGGL(temporal_motion_kernel, grid, dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o, mo);
+    else hipLaunchKernelGGL(temporal_kernel, grid, dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o);
     TEMPORAL_TRY(hipGetLastError());
     TEMPORAL_TRY(hipEventRecord(s->ev[1], stream));
     for (const Result &r : results)

@@ -368,6 +368,16 @@ int rtw_mesh_top_refit(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshIn
     return RTW_OK;
 }
 
+// The motion rows of moved placements (rtw.h): mesh_motion_row per placement, the definition rtw_ctx_mesh_instance_motion's kernel runs
+int rtw_mesh_instance_motion(const float *prev_poses, const float *cur_poses, uint32_t n, RtwMotionRow *rows_out, uint32_t *n_invalid) {
+    if (!prev_poses || !cur_poses || !rows_out || n == 0 || n > RTW_MAX_MESH_INSTANCES) return RTW_E_INVALID;
+    uint32_t bad = 0;
+    for (uint32_t k = 0; k < n; k++)
+        if (mesh_motion_row(prev_poses + 7 * (size_t)k, cur_poses + 7 * (size_t)k, rows_out[k])) bad++;
+    if (n_invalid) *n_invalid = bad;
+    return RTW_OK;
+}
+
 int rtw_mesh_instance_hits_tree(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *p, uint32_t n, const float *rays, uint32_t n_rays,
                                 float mint, float maxt, float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out, RtwStats *stats) {
     if (!rays || !t_out || !placement_out || !tri_out || n_rays == 0 || n == 0) return RTW_E_INVALID;
