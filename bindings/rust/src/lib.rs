@@ -229,6 +229,25 @@ extern "C" {
     fn rtw_mesh_instance_motion(prev_poses: *const f32, cur_poses: *const f32, n: u32, rows_out: *mut RtwMotionRow, n_invalid: *mut u32) -> i32;
     fn rtw_ctx_mesh_instance_motion(ctx: *mut RtwCtx, prev_poses: *const f32, cur_poses: *const f32, n: u32, rows_out: *mut RtwMotionRow,
                                     n_invalid: *mut u32) -> i32;
+    // per-pixel motion (rtw.h "temporal accumulation with per-pixel motion"): declared for callers of the raw ABI; no safe wrapper yet
+    #[allow(dead_code)]
+    fn rtw_deform_motion(tri: *const i32, bary: *const f32, n: u32, prev_ouv: *const f32, n_tris: u32, idx: *const i32, prev_poses: *const f32,
+                         n_mesh: u32, first: u32, prev_point_out: *mut f32, carried_normal_out: *mut f32) -> i32;
+    #[allow(dead_code)]
+    fn rtw_ctx_deform_motion(ctx: *mut RtwCtx, tri: *const i32, bary: *const f32, n: u32, prev_ouv: *const f32, n_tris: u32, idx: *const i32,
+                             prev_poses: *const f32, n_mesh: u32, first: u32, prev_point_out: *mut f32, carried_normal_out: *mut f32) -> i32;
+    #[allow(dead_code)]
+    fn rtw_ctx_temporal_accumulate_points(ctx: *mut RtwCtx, cur: *const f32, w: u32, h: u32, cam: *const RtwCamera, depth: *const f32,
+                                          normal: *const f32, idx: *const i32, prev_cam: *const RtwCamera, prev_color: *const f32,
+                                          prev_moments: *const f32, prev_len: *const f32, prev_depth: *const f32, prev_normal: *const f32,
+                                          prev_idx: *const i32, p: *const RtwTemporal, rows: *const RtwMotionRow, n_rows: u32, first: u32,
+                                          prev_point: *const f32, carried_normal: *const f32, out_color: *mut f32, out_moments: *mut f32,
+                                          out_len: *mut f32, out_variance: *mut f32, out_prev_xy: *mut f32, st: *mut RtwFilterStats) -> i32;
+    #[allow(dead_code)]
+    fn rtw_ctx_surface_map_tri(ctx: *mut RtwCtx, cam: *const RtwCamera, width: u32, height: u32, ray_rule: u32, offset: *const f32, time: f32,
+                               mint: f32, maxt: f32, accel: u32, integrator: u32, depth_out: *mut f32, idx_out: *mut i32, normal_out: *mut f32,
+                               albedo_out: *mut f32, emitted_out: *mut f32, material_out: *mut f32, tri_out: *mut i32, bary_out: *mut f32,
+                               stats: *mut RtwStats) -> i32;
     fn rtw_triangle_new(origin: *const f32, u: *const f32, v: *const f32, mat3: *const f32, emitted: *const f32,
                         color: *const f32, tex: i32, out: *mut RtwTriangle) -> i32;
     fn rtw_ctx_set_triangles(ctx: *mut RtwCtx, tris: *const RtwTriangle, n: u32) -> i32;

@@ -643,8 +643,8 @@ int rtw_ctx_temporal_accumulate(rtw_ctx *ctx, const float *cur, uint32_t w, uint
  * RTW_E_INVALID, nothing written: the refusals above; rows with idx NULL; rows with n_rows == 0; first + n_rows beyond 2^31; out_prev_xy
  * equal to out_color, out_moments, out_len or out_variance.  With rows NULL, n_rows and first are not read.
  * With rows == NULL and out_prev_xy == NULL the calls write the bytes of rtw_temporal_accumulate / rtw_ctx_temporal_accumulate.
- * What stays out: deforming meshes (rtw_ctx_refit_triangles: a point's previous place needs its barycentrics, not a row), the moving
- * spheres of ray.time, a wider search when all four taps fail.  There is no rtw_mgpu_* form and no JSON form. */
+ * What stays out: the moving spheres of ray.time, a wider search when all four taps fail (deforming meshes: "temporal accumulation with
+ * per-pixel motion", below).  There is no rtw_mgpu_* form and no JSON form. */
 typedef struct RtwMotionRow {
     float    a[9];      /* row-major 3 x 3: world points, current frame -> previous frame        */
     float    from[3];   /* subtracted before a is applied (the object's current position)       */
@@ -687,6 +687,62 @@ int rtw_mesh_instance_motion(const float *prev_poses, const float *cur_poses, ui
  * memory (input staged, result copied back) or device memory of ctx's GPU (read and written in place).  Needs no scene. */
 int rtw_ctx_mesh_instance_motion(rtw_ctx *ctx, const float *prev_poses, const float *cur_poses, uint32_t n, RtwMotionRow *rows_out,
                                  uint32_t *n_invalid);
+
+/* ---- temporal accumulation with per-pixel motion: deforming meshes, and any geometry the caller moves itself -- added within v4 ------------
+ * A row carries a rigid object.  A mesh that rtw_ctx_refit_triangles deforms has no such row: where a surface point lay a frame ago depends
+ * on its triangle and its place inside it.  Three pieces close that gap, each f32 with one rounding per written operation, no fused
+ * multiply-add, dot products as (x*x' + y*y') + z*z':
+ *   1. rtw_ctx_surface_map_tri / rtw_ctx_scene_surface_tri ("surface buffers" below) report the triangle under each ray and (alfa, beta).
+ *   2. rtw_deform_motion turns them, with the PREVIOUS frame's ouv rows, into each pixel's previous world point and the normal it had there:
+ *        a pixel has a point when 0 <= tri[p] < n_tris (no wrap-around); {o, u, v} = row tri[p] of prev_ouv ([n_tris][9] as
+ *        rtw_ctx_refit_triangles takes it; the caller kept it, the context does not hold the old mesh)
+ *          x'_c = (o_c + alfa * u_c) + beta * v_c;     n' = unit(u x v) as Triangle::new forms it (n / |n|)
+ *        prev_poses == NULL:  prev_point = x', carried_normal = n'  (idx, n_mesh and first are not read)
+ *        else ([n_mesh][7] as rtw_ctx_move_mesh_instances took them a frame ago): k = idx[p] - first in 64 bits, 0 <= k < n_mesh or the
+ *          pixel has no point; (qn, pos) the normalised quaternion and position the walk uses for pose k ("mesh placements" below):
+ *          prev_point = rotate(conj(qn), x') + pos;   carried_normal = rotate(qn, n');   a pose the placements refuse: no point
+ *        a pixel without a point: the quiet NaN 0x7fc00000 in all six floats; no address is formed from such a tri or k.
+ *        A degenerate previous triangle (u x v = 0) gives a finite point and a normal that is not finite: it fails the normal test when
+ *        that is on, and only then.
+ *      RTW_E_INVALID, nothing written: a NULL tri, bary, prev_ouv or output; n == 0; n_tris == 0; prev_poses with idx NULL, n_mesh == 0 or
+ *      n_mesh > RTW_MAX_MESH_INSTANCES.
+ *   3. rtw_temporal_accumulate_points is rtw_temporal_accumulate_motion plus prev_point and carried_normal, both [h][w][3] f32, both may be
+ *      NULL.  A pixel HAS A POINT when prev_point != NULL and prev_point[p].x == prev_point[p].x.  For such a pixel
+ *          P' = prev_point[p];  d = P' - prev_cam.origin;  s, fx, fy from d and the four taps as in "with a row" above (never the static
+ *          shortcut's one tap); the normal test reads carried_normal[p] in place of normal[p] (carried_normal == NULL: normal[p] itself);
+ *          its row, if any, is ignored.  An infinity or a NaN in P'.y or P'.z ends as an s or fx that is not finite: "no history".
+ *      A pixel without a point follows "temporal accumulation with moving objects" byte for byte.  out_prev_xy as there.  The buffers may
+ *      come from anywhere: a caller who skins or simulates geometry itself fills them without rtw_deform_motion.
+ *      RTW_E_INVALID besides the refusals there: prev_point or carried_normal equal to out_color, out_moments, out_len, out_variance or
+ *      out_prev_xy; carried_normal without prev_point.  With both NULL the calls are the _motion calls, launch for launch.
+ * What stays out: a mesh whose topology changes (tri names another triangle), the moving spheres of ray.time, one fused launch for the
+ * three passes.  There is no rtw_mgpu_* form and no JSON form. */
+/* Host only, pure (one thread). */
+int rtw_deform_motion(const int32_t *tri /* [n] */, const float *bary /* [n][2] */, uint32_t n, const float *prev_ouv /* [n_tris][9] */,
+                      uint32_t n_tris, const int32_t *idx /* [n], with prev_poses */, const float *prev_poses /* [n_mesh][7] or NULL */,
+                      uint32_t n_mesh, uint32_t first, float *prev_point_out /* [n][3] */, float *carried_normal_out /* [n][3] */);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host form, one thread per pixel.  Each buffer may independently be host memory
+ * (staged; a result copied back) or device memory of ctx's GPU (used in place); the staging is kept, so a repeated size allocates nothing.
+ * Needs no scene. */
+int rtw_ctx_deform_motion(rtw_ctx *ctx, const int32_t *tri, const float *bary, uint32_t n, const float *prev_ouv, uint32_t n_tris,
+                          const int32_t *idx, const float *prev_poses, uint32_t n_mesh, uint32_t first, float *prev_point_out,
+                          float *carried_normal_out);
+/* The host form (one thread) and, on ctx's GPU and stream, its bytes: a third instantiation of the kernel, chosen on the host. */
+int rtw_temporal_accumulate_points(const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth, const float *normal,
+                                   const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color, const float *prev_moments,
+                                   const float *prev_len, const float *prev_depth, const float *prev_normal, const int32_t *prev_idx,
+                                   const RtwTemporal *params, const RtwMotionRow *rows /* may be NULL */, uint32_t n_rows, uint32_t first,
+                                   const float *prev_point /* may be NULL */, const float *carried_normal /* may be NULL */,
+                                   float *out_color, float *out_moments, float *out_len, float *out_variance /* may be NULL */,
+                                   float *out_prev_xy /* may be NULL */, RtwFilterStats *stats);
+int rtw_ctx_temporal_accumulate_points(rtw_ctx *ctx, const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth,
+                                       const float *normal, const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color,
+                                       const float *prev_moments, const float *prev_len, const float *prev_depth,
+                                       const float *prev_normal, const int32_t *prev_idx, const RtwTemporal *params,
+                                       const RtwMotionRow *rows /* may be NULL */, uint32_t n_rows, uint32_t first,
+                                       const float *prev_point /* may be NULL */, const float *carried_normal /* may be NULL */,
+                                       float *out_color, float *out_moments, float *out_len, float *out_variance /* may be NULL */,
+                                       float *out_prev_xy /* may be NULL */, RtwFilterStats *stats);
 
 /* ---- variance estimate: a luminance variance for every pixel of an accumulated frame -- added within v4 ---------------------------------
  * SVGF's variance estimation (Schied et al. 2017, section 4.2): where the history is long enough the variance over time that the two
@@ -890,6 +946,30 @@ int rtw_ctx_surface_map(rtw_ctx *ctx, const RtwCamera *cam, uint32_t width, uint
                         float time, float mint, float maxt, uint32_t accel, uint32_t integrator,
                         float *depth_out, int32_t *idx_out, float *normal_out, float *albedo_out, float *emitted_out,
                         float *material_out, RtwStats *stats);
+
+/* The surface calls with the triangle under each ray and the point's place inside it -- added within v4 (the calls above stay as they are).
+ *   tri_out  [n] / [height][width] i32      a winner that is a world-space triangle or a triangle of a mesh placement: its position in the
+ *                                           list rtw_ctx_set_triangles took, i.e. the row of `ouv`; every other winner and a miss: -1
+ *   bary_out [n][2] / [height][width][2] f32   (alfa, beta) as the hit test forms them for that winner: p = o + d * t, planar = p - origin,
+ *                                           alfa = w . (planar x v), beta = w . (u x planar), w = n / (n . n), n = u x v; for a placement
+ *                                           (o, d) is the ray turned into the placement's frame; otherwise 0 0
+ * Either may be NULL; with both NULL these are the calls above.  Everything else is written as by the calls above, byte for byte. */
+int rtw_ctx_scene_surface_tri(rtw_ctx *ctx, const float *rays, uint32_t n_rays, float time, float mint, float maxt, uint32_t accel,
+                              uint32_t integrator, float *t_out, int32_t *idx_out, float *normal_out, float *albedo_out, float *emitted_out,
+                              float *material_out, int32_t *tri_out, float *bary_out, RtwStats *stats);
+int rtw_ctx_surface_map_tri(rtw_ctx *ctx, const RtwCamera *cam, uint32_t width, uint32_t height, uint32_t ray_rule, const float offset[2],
+                            float time, float mint, float maxt, uint32_t accel, uint32_t integrator, float *depth_out, int32_t *idx_out,
+                            float *normal_out, float *albedo_out, float *emitted_out, float *material_out, int32_t *tri_out,
+                            float *bary_out, RtwStats *stats);
+/* Host only, pure: that rule from the mesh's ouv rows alone ([n_tris][9] = origin, u, v): for 0 <= tri[i] < n_tris the w of row tri[i] as
+ * Triangle::new derives it and (alfa, beta) of ray i ([n][6]) at t[i]; any other tri[i]: 0 0, no address formed.  For a placed mesh pass the
+ * rays of rtw_mesh_local_rays.  RTW_E_INVALID: a NULL pointer, n == 0, n_tris == 0. */
+int rtw_tri_bary(const float *ouv, uint32_t n_tris, const float *rays, uint32_t n, const float *t, const int32_t *tri, float *bary_out);
+/* Host only, pure: ray i as placement idx[i] - first meets it -- o' = qn.rotate(o - position), d' = qn.rotate(d), the walk's own operations
+ * ("mesh placements" below); poses [n_mesh][7].  A ray whose idx names no placement, or a refused pose, is copied.  RTW_E_INVALID: a NULL
+ * pointer, n == 0, n_mesh == 0 or beyond RTW_MAX_MESH_INSTANCES. */
+int rtw_mesh_local_rays(const float *poses, uint32_t n_mesh, uint32_t first, const int32_t *idx, const float *rays, uint32_t n,
+                        float *rays_out /* [n][6] */);
 
 /* ---- light-biased integrators (Rust2/src/viewport/ray_color.rs:55-164, objects/material.rs material_pdf) ---------------------------
  * RTW_INTEGRATOR_LIGHT_CAST / RTW_INTEGRATOR_LIGHT_BIASED send, from every surface hit h, one shadow ray per light: towards the MID-POINT of

@@ -460,6 +460,16 @@ def lib() -> C.CDLL:
     L.rtw_ctx_temporal_accumulate_motion.argtypes = [C.c_void_p] + L.rtw_temporal_accumulate_motion.argtypes
     L.rtw_mesh_instance_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     L.rtw_ctx_mesh_instance_motion.argtypes = [C.c_void_p] + L.rtw_mesh_instance_motion.argtypes
+    L.rtw_temporal_accumulate_points.argtypes = (L.rtw_temporal_accumulate_motion.argtypes[:18] + [C.c_void_p] * 2 +
+                                                 L.rtw_temporal_accumulate_motion.argtypes[18:])
+    L.rtw_ctx_temporal_accumulate_points.argtypes = [C.c_void_p] + L.rtw_temporal_accumulate_points.argtypes
+    L.rtw_ctx_scene_surface_tri.argtypes = L.rtw_ctx_scene_surface.argtypes[:-1] + [C.c_void_p] * 2 + [C.POINTER(RtwStats)]
+    L.rtw_ctx_surface_map_tri.argtypes = L.rtw_ctx_surface_map.argtypes[:-1] + [C.c_void_p] * 2 + [C.POINTER(RtwStats)]
+    L.rtw_tri_bary.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtw_mesh_local_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.rtw_deform_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                    C.c_void_p, C.c_void_p]
+    L.rtw_ctx_deform_motion.argtypes = [C.c_void_p] + L.rtw_deform_motion.argtypes
     L.rtw_variance_estimate.argtypes = ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3 +
                                         [C.POINTER(RtwVarianceEstimate), C.c_void_p, C.POINTER(RtwFilterStats)])
     L.rtw_ctx_variance_estimate.argtypes = [C.c_void_p] + L.rtw_variance_estimate.argtypes
@@ -937,6 +947,70 @@ def mesh_instance_motion(prev_poses, cur_poses):
     bad = C.c_uint32()
     _check(lib().rtw_mesh_instance_motion(pp.ctypes.data, cp.ctypes.data, len(cp), rows.ctypes.data, C.byref(bad)), "rtw_mesh_instance_motion")
     return rows, bad.value
+
+
+def mesh_local_rays(poses, idx, rays, first: int = 0) -> np.ndarray:
+    """rtw_mesh_local_rays (host only): ray i ([n][6]) as placement idx[i] - first of `poses` ((position, quat) pairs or [n_mesh][7]) meets
+    it, by the walk's own operations; a ray whose idx names no placement is copied.  The rays tri_bary wants for a placed mesh."""
+    pp, r = _poses(poses), _rays(rays)
+    ids = np.ascontiguousarray(idx, np.int32).reshape(-1)
+    if len(ids) != len(r):
+        raise ValueError(f"mesh_local_rays: {len(ids)} ids, {len(r)} rays")
+    out = np.empty_like(r)
+    _check(lib().rtw_mesh_local_rays(pp.ctypes.data, len(pp), int(first), ids.ctypes.data, r.ctypes.data, len(r), out.ctypes.data), "rtw_mesh_local_rays")
+    return out
+
+
+def tri_bary(ouv, rays, t, tri) -> np.ndarray:
+    """rtw_tri_bary (host only): the (alfa, beta) [n][2] float32 that surface_map(bary=True) and scene_surface(bary=True) write, from the
+    mesh's ouv rows ([n_tris][9]) alone: for 0 <= tri[i] < n_tris those of ray i ([n][6]) at t[i] inside triangle tri[i], else 0 0.  For a
+    placed mesh pass mesh_local_rays(poses, idx, rays, first)."""
+    a, r = _ouv(ouv), _rays(rays)
+    tt = np.ascontiguousarray(t, np.float32).reshape(-1)
+    tr = np.ascontiguousarray(tri, np.int32).reshape(-1)
+    if len(tt) != len(r) or len(tr) != len(r):
+        raise ValueError(f"tri_bary: {len(r)} rays, {len(tt)} t, {len(tr)} tri")
+    out = np.empty((len(r), 2), np.float32)
+    _check(lib().rtw_tri_bary(a.ctypes.data, len(a), r.ctypes.data, len(r), tt.ctypes.data, tr.ctypes.data, out.ctypes.data), "rtw_tri_bary")
+    return out
+
+
+def _deform_call(fn, fn_name, head, on_device, tri, bary, prev_ouv, idx, prev_poses, first):
+    """rtw_deform_motion / rtw_ctx_deform_motion from the Python arguments of deform_motion."""
+    who = "deform_motion"
+    shp = tuple(tri.shape)
+    n = int(np.prod(shp)) if len(shp) else 1
+    keep = []
+    ptr = lambda name, a, dtype, shape, writable=False: _atrous_pointer(name, a, dtype, shape, on_device, keep, writable, who)
+
+    def rows(name, a, per):
+        if hasattr(a, "data_ptr"):
+            if a.numel() % per:
+                raise ValueError(f"{who}: {name} must hold [n][{per}] floats")
+            return ptr(name, a, np.float32, tuple(a.shape)), a.numel() // per
+        b = _poses(a) if per == 7 else _ouv(a)
+        keep.append(b)
+        return C.c_void_p(b.ctypes.data), len(b)
+
+    op, n_tris = rows("prev_ouv", prev_ouv, 9)
+    pp, n_mesh = (None, 0) if prev_poses is None else rows("prev_poses", prev_poses, 7)
+    if prev_poses is not None and idx is None:
+        raise ValueError(f"{who}: prev_poses needs idx")
+    if hasattr(tri, "data_ptr"):
+        import torch
+        point, normal = (torch.empty(shp + (3,), dtype=torch.float32, device=tri.device) for _ in range(2))
+    else:
+        point, normal = np.empty(shp + (3,), np.float32), np.empty(shp + (3,), np.float32)
+    _check(fn(*head, ptr("tri", tri, np.int32, shp), ptr("bary", bary, np.float32, shp + (2,)), n, op, n_tris,
+              ptr("idx", idx if prev_poses is not None else None, np.int32, shp), pp, n_mesh, int(first),
+              ptr("prev_point", point, np.float32, shp + (3,), True), ptr("carried_normal", normal, np.float32, shp + (3,), True)), fn_name)
+    return point, normal
+
+
+def deform_motion(tri, bary, prev_ouv, idx=None, prev_poses=None, first: int = 0):
+    """rtw_deform_motion (host only), the bytes of Renderer.deform_motion; numpy arrays only.  Arguments and result as there."""
+    tri = np.ascontiguousarray(tri, np.int32)
+    return _deform_call(lib().rtw_deform_motion, "rtw_deform_motion", (), None, tri, bary, prev_ouv, idx, prev_poses, first)
 
 
 def depth_rays(cam: RtwCamera, width: int, height: int) -> np.ndarray:
@@ -1630,6 +1704,20 @@ class Renderer:
         del keep_p, keep_c
         return rows, bad.value
 
+    def deform_motion(self, tri, bary, prev_ouv, idx=None, prev_poses=None, first: int = 0):
+        """rtw_ctx_deform_motion: where each pixel's surface point lay a frame ago on a mesh that deformed, on this context's GPU and stream,
+        one thread per pixel.  tri [..] int32 and bary [..][2] float32: what surface_map(tri=True, bary=True) wrote for the CURRENT frame;
+        prev_ouv [n_tris][9]: the rows refit_triangles took a frame ago (the caller keeps them).  For a placed mesh also idx (surface_map's)
+        and prev_poses, the (position, quat) pairs or [n_mesh][7] move_mesh_instances took a frame ago, with first =
+        mesh_instance_first().  Every argument is a numpy array (staged) or a contiguous torch tensor on the context's device, read in
+        place on the stream of use_torch_stream.  Returns (prev_point, carried_normal), [..][3] float32 each -- tensors when `tri` is one --
+        for temporal_accumulate(prev_point=, carried_normal=): NaN in all six where the pixel is not on the mesh (tri outside [0, n_tris),
+        idx outside the placements, a refused pose)."""
+        if not hasattr(tri, "data_ptr"):
+            tri = np.ascontiguousarray(tri, np.int32)
+        return _deform_call(lib().rtw_ctx_deform_motion, "rtw_ctx_deform_motion", (self._h,), self._on_device, tri, bary, prev_ouv, idx, prev_poses,
+                            first)
+
     def mesh_instance_first(self) -> int:
         """The top-level index surface_map reports for placement 0 of the context's scene: n_spheres + n_quads + n_instances (0 without a
         scene) -- temporal_accumulate's motion_first for the rows of mesh_instance_motion."""
@@ -1738,35 +1826,55 @@ class Renderer:
                                        idx.ctypes.data if ids else None, nrm.ctypes.data if normals else None, C.byref(st)), "rtw_ctx_depth_map")
         return (depth,) + ((idx,) if ids else ()) + ((nrm,) if normals else ()) + (st,)
 
-    def scene_surface(self, rays, mint: float, maxt: float, integrator: int = INTEGRATOR_BG_COLOR, time: float = 0.0, accel: int = ACCEL_BVH):
+    def scene_surface(self, rays, mint: float, maxt: float, integrator: int = INTEGRATOR_BG_COLOR, time: float = 0.0, accel: int = ACCEL_BVH,
+                      tri: bool = False, bary: bool = False):
         """scene_hits with the rest of the winner's hit record as the render reads it under `integrator` (rtw_ctx_scene_surface): a dict of
         t [n] float32 (+inf on a miss), idx [n] int32 (-1), normal [n][3], albedo [n][3] (the colour the throughput is multiplied by, textures
-        resolved), emitted [n][3], material [n][3] = metallicness, opacity, ir -- all 0 on a miss -- and stats."""
+        resolved), emitted [n][3], material [n][3] = metallicness, opacity, ir -- all 0 on a miss -- and stats.  tri / bary
+        (rtw_ctx_scene_surface_tri): also tri [n] int32, the winning triangle's row of ouv (-1 for every other winner), and bary [n][2], its
+        (alfa, beta) (0 0)."""
         r = _rays(rays)
         n = len(r)
         out = dict(t=np.empty(n, np.float32), idx=np.empty(n, np.int32), normal=np.empty((n, 3), np.float32), albedo=np.empty((n, 3), np.float32),
                    emitted=np.empty((n, 3), np.float32), material=np.empty((n, 3), np.float32))
         st = RtwStats()
-        _check(lib().rtw_ctx_scene_surface(self._h, r.ctypes.data, n, float(time), float(mint), float(maxt), int(accel), int(integrator),
-                                           *(out[k].ctypes.data for k in ("t", "idx", "normal", "albedo", "emitted", "material")), C.byref(st)),
-               "rtw_ctx_scene_surface")
+        six = [out[k].ctypes.data for k in ("t", "idx", "normal", "albedo", "emitted", "material")]
+        head = (self._h, r.ctypes.data, n, float(time), float(mint), float(maxt), int(accel), int(integrator))
+        if tri or bary:
+            if tri:
+                out["tri"] = np.empty(n, np.int32)
+            if bary:
+                out["bary"] = np.empty((n, 2), np.float32)
+            _check(lib().rtw_ctx_scene_surface_tri(*head, *six, out["tri"].ctypes.data if tri else None, out["bary"].ctypes.data if bary else None,
+                                                   C.byref(st)), "rtw_ctx_scene_surface_tri")
+        else:
+            _check(lib().rtw_ctx_scene_surface(*head, *six, C.byref(st)), "rtw_ctx_scene_surface")
         out["stats"] = st
         return out
 
     def surface_map(self, cam: RtwCamera, width: int, height: int, mint: float, maxt: float, integrator: int = INTEGRATOR_BG_COLOR,
-                    ray_rule: int = RAYS_PIXEL, offset=(0.5, 0.5), time: float = 0.0, accel: int = ACCEL_BVH):
+                    ray_rule: int = RAYS_PIXEL, offset=(0.5, 0.5), time: float = 0.0, accel: int = ACCEL_BVH, tri: bool = False, bary: bool = False):
         """What a camera sees, in one launch (rtw_ctx_surface_map): a dict of depth [h][w] float32 (maxt * 1.6 on a miss), idx [h][w] int32,
         normal, albedo, emitted, material [h][w][3] and stats.  ray_rule RAYS_PIXEL: a Viewport camera's pixel rays at `offset` inside the
-        pixel (pixel_rays); RAYS_DEPTH_MAP: depth_map's rays for a camera of camera2_new.  The guides of Renderer.atrous_filter."""
+        pixel (pixel_rays); RAYS_DEPTH_MAP: depth_map's rays for a camera of camera2_new.  The guides of Renderer.atrous_filter.  tri / bary
+        (rtw_ctx_surface_map_tri): also tri [h][w] int32 and bary [h][w][2] as scene_surface's, the inputs of deform_motion."""
         width, height = int(width), int(height)
         out = dict(depth=np.empty((height, width), np.float32), idx=np.empty((height, width), np.int32))
         for k in ("normal", "albedo", "emitted", "material"):
             out[k] = np.empty((height, width, 3), np.float32)
         off = (C.c_float * 2)(float(offset[0]), float(offset[1]))
         st = RtwStats()
-        _check(lib().rtw_ctx_surface_map(self._h, C.byref(cam), width, height, int(ray_rule), off, float(time), float(mint), float(maxt), int(accel),
-                                         int(integrator), *(out[k].ctypes.data for k in ("depth", "idx", "normal", "albedo", "emitted", "material")),
-                                         C.byref(st)), "rtw_ctx_surface_map")
+        six = [out[k].ctypes.data for k in ("depth", "idx", "normal", "albedo", "emitted", "material")]
+        head = (self._h, C.byref(cam), width, height, int(ray_rule), off, float(time), float(mint), float(maxt), int(accel), int(integrator))
+        if tri or bary:
+            if tri:
+                out["tri"] = np.empty((height, width), np.int32)
+            if bary:
+                out["bary"] = np.empty((height, width, 2), np.float32)
+            _check(lib().rtw_ctx_surface_map_tri(*head, *six, out["tri"].ctypes.data if tri else None, out["bary"].ctypes.data if bary else None,
+                                                 C.byref(st)), "rtw_ctx_surface_map_tri")
+        else:
+            _check(lib().rtw_ctx_surface_map(*head, *six, C.byref(st)), "rtw_ctx_surface_map")
         out["stats"] = st
         return out
 
@@ -2029,7 +2137,7 @@ class Renderer:
         return out, st
 
     def temporal_accumulate(self, cur, cam: RtwCamera, depth, normal=None, ids=None, history=None, out_color=None, motion=None,
-                            motion_first: int = 0, out_prev_xy=None, **params):
+                            motion_first: int = 0, out_prev_xy=None, prev_point=None, carried_normal=None, **params):
         """Temporal accumulation of a linear float32 frame [h][w][3] on this context's GPU (rtw_ctx_temporal_accumulate, include/rtw.h): the
         previous call's accumulated colour, luminance moments and history length are fetched where each pixel's surface point lay in the
         previous view, each of the four taps accepted or rejected against the guides, and blended with `cur`.  depth [h][w] float32, normal
@@ -2046,9 +2154,14 @@ class Renderer:
         reports as motion_first .. motion_first + n - 1; their pixels are carried into the previous frame before they are projected.  It
         needs `ids`, whether or not same_object is on.  out_prev_xy: True, or an array / tensor [h][w][2], receives where each pixel lay in
         the previous view (NaN on a first frame) and is returned as history["prev_xy"].  With all three at their defaults the call is
-        rtw_ctx_temporal_accumulate."""
+        rtw_ctx_temporal_accumulate.
+        Per-pixel motion (rtw_ctx_temporal_accumulate_points): prev_point [h][w][3] float32 -- deform_motion's, or your own -- gives the
+        world point each pixel's surface point was a frame ago; a pixel whose prev_point x is not NaN projects that point and takes the four
+        taps, whatever its row says, and its normal test reads carried_normal [h][w][3] (None: normal itself).  With both at None the call
+        is the one above."""
         return _temporal_call(lib().rtw_ctx_temporal_accumulate, "rtw_ctx_temporal_accumulate", (self._h,), self._on_device, cur, cam, depth,
-                              normal, ids, history, out_color, params, motion, motion_first, out_prev_xy, lib().rtw_ctx_temporal_accumulate_motion)
+                              normal, ids, history, out_color, params, motion, motion_first, out_prev_xy, lib().rtw_ctx_temporal_accumulate_motion,
+                              prev_point, carried_normal, lib().rtw_ctx_temporal_accumulate_points)
 
     def variance_estimate(self, moments, length, depth=None, normal=None, ids=None, min_history: int = SVGF_DEFAULTS["min_history"],
                           radius: int = SVGF_DEFAULTS["radius"], sigma_depth: float = SVGF_DEFAULTS["sigma_depth"],
@@ -2356,9 +2469,9 @@ def _motion_pointer(motion, on_device, keep, who):
 
 
 def _temporal_call(fn, fn_name, head, on_device, cur, cam, depth, normal, ids, history, out_color, params, motion=None, motion_first=0,
-                   out_prev_xy=None, fn_motion=None):
+                   out_prev_xy=None, fn_motion=None, prev_point=None, carried_normal=None, fn_points=None):
     """rtw_temporal_accumulate / rtw_ctx_temporal_accumulate from the Python arguments of temporal_accumulate: (history, variance, stats).
-    With motion or out_prev_xy: fn_motion, the call with moving objects."""
+    With motion or out_prev_xy: fn_motion, the call with moving objects.  With prev_point or carried_normal: fn_points."""
     who = "temporal_accumulate"
     unknown = set(params) - set(TEMPORAL_DEFAULTS) - {"offset"}
     if unknown:
@@ -2393,7 +2506,8 @@ def _temporal_call(fn, fn_name, head, on_device, cur, cam, depth, normal, ids, h
             C.byref(prm), ptr("out_color", out["color"], np.float32, (h, w, 3), True), ptr("moments", out["moments"], np.float32, (h, w, 2), True),
             ptr("len", out["len"], np.float32, (h, w), True), ptr("variance", variance, np.float32, (h, w), True)]
     st = RtwFilterStats()
-    if motion is None and out_prev_xy is None and not motion_first:
+    points = prev_point is not None or carried_normal is not None
+    if motion is None and out_prev_xy is None and not motion_first and not points:
         _check(fn(*head, *args, C.byref(st)), fn_name)
         return out, variance, st
     rows, n_rows = (None, 0) if motion is None else _motion_pointer(motion, on_device, keep, who)
@@ -2401,16 +2515,22 @@ def _temporal_call(fn, fn_name, head, on_device, cur, cam, depth, normal, ids, h
         out["prev_xy"] = new(h, w, 2) if out_prev_xy is True else out_prev_xy
     args[15:15] = [rows, n_rows, int(motion_first)]
     args.append(ptr("out_prev_xy", out.get("prev_xy"), np.float32, (h, w, 2), True))
-    _check(fn_motion(*head, *args, C.byref(st)), fn_name + "_motion")
+    if not points:
+        _check(fn_motion(*head, *args, C.byref(st)), fn_name + "_motion")
+        return out, variance, st
+    args[18:18] = [ptr("prev_point", prev_point, np.float32, (h, w, 3)), ptr("carried_normal", carried_normal, np.float32, (h, w, 3))]
+    _check(fn_points(*head, *args, C.byref(st)), fn_name + "_points")
     return out, variance, st
 
 
 def temporal_accumulate(cur, cam: RtwCamera, depth, normal=None, ids=None, history=None, out_color=None, motion=None, motion_first: int = 0,
-                        out_prev_xy=None, **params):
-    """The temporal accumulation on the host (rtw_temporal_accumulate, with motion or out_prev_xy rtw_temporal_accumulate_motion), the
-    bytes of Renderer.temporal_accumulate; numpy arrays only.  Arguments and result as there."""
+                        out_prev_xy=None, prev_point=None, carried_normal=None, **params):
+    """The temporal accumulation on the host (rtw_temporal_accumulate, with motion or out_prev_xy rtw_temporal_accumulate_motion, with
+    prev_point or carried_normal rtw_temporal_accumulate_points), the bytes of Renderer.temporal_accumulate; numpy arrays only.  Arguments
+    and result as there."""
     return _temporal_call(lib().rtw_temporal_accumulate, "rtw_temporal_accumulate", (), None, cur, cam, depth, normal, ids, history, out_color, params,
-                          motion, motion_first, out_prev_xy, lib().rtw_temporal_accumulate_motion)
+                          motion, motion_first, out_prev_xy, lib().rtw_temporal_accumulate_motion, prev_point, carried_normal,
+                          lib().rtw_temporal_accumulate_points)
 
 
 class TemporalDenoiser:
@@ -2427,8 +2547,26 @@ class TemporalDenoiser:
         """Drop the history: the next step starts a sequence."""
         self.history = None
 
-    def step(self, cam: RtwCamera, params: RtwParams, motion=None, motion_first: int = 0, **atrous):
-        """One frame (motion, motion_first: temporal_accumulate's, the motion of the scene's objects since the previous step): params.seed is advanced by one (in `params`), the frame rendered at gamma 1, the guides taken from surface_map at the
+    def _guides(self, cam, params, prev_ouv, prev_poses):
+        """(surface_map's dict for this frame, temporal_accumulate's prev_point / carried_normal arguments): with prev_ouv the map also
+        reports tri and bary, and deform_motion turns them into the pixels' previous points."""
+        r = self.renderer
+        deform = prev_ouv is not None
+        if prev_poses is not None and not deform:
+            raise ValueError("step: prev_poses goes with prev_ouv (rigid motion alone: motion=)")
+        g = r.surface_map(cam, params.width, params.height, params.mint, params.maxt, params.integrator, RAYS_PIXEL, (0.5, 0.5), accel=params.accel,
+                          tri=deform, bary=deform)
+        if not deform:
+            return g, {}
+        point, normal = r.deform_motion(g["tri"], g["bary"], prev_ouv, g["idx"] if prev_poses is not None else None, prev_poses,
+                                        r.mesh_instance_first() if prev_poses is not None else 0)
+        return g, dict(prev_point=point, carried_normal=normal)
+
+    def step(self, cam: RtwCamera, params: RtwParams, motion=None, motion_first: int = 0, prev_ouv=None, prev_poses=None, **atrous):
+        """One frame (motion, motion_first: temporal_accumulate's, the motion of the scene's objects since the previous step; prev_ouv: the
+        rows the mesh had at the previous step when refit_triangles or move_mesh_instances(ouv=) deformed it since, with prev_poses, the
+        previous poses, when the mesh is placed -- the step then asks surface_map for tri and bary and deform_motion for the pixels'
+        previous points): params.seed is advanced by one (in `params`), the frame rendered at gamma 1, the guides taken from surface_map at the
         pixel centres, the frame accumulated onto the history, atrous_filter (keyword arguments: its own) run on the accumulated colour
         with albedo and emission, and params.gamma applied as render_denoised does.  Returns (frame, accumulated, variance, stats): frame
         the filtered [h][w][3] float32 image, accumulated the linear accumulated colour (the history's), variance [h][w], stats a dict of
@@ -2444,9 +2582,9 @@ class TemporalDenoiser:
             cur, st = r.render(cam, params)
         finally:
             params.gamma = gamma
-        g = r.surface_map(cam, params.width, params.height, params.mint, params.maxt, params.integrator, RAYS_PIXEL, (0.5, 0.5), accel=params.accel)
+        g, points = self._guides(cam, params, prev_ouv, prev_poses)
         self.history, variance, st_t = r.temporal_accumulate(cur, cam, depth=g["depth"], normal=g["normal"], ids=g["idx"], history=self.history,
-                                                             motion=motion, motion_first=motion_first, offset=(0.5, 0.5), **self.params)
+                                                             motion=motion, motion_first=motion_first, offset=(0.5, 0.5), **points, **self.params)
         acc = self.history["color"]
         frame, st_a = r.atrous_filter(acc, depth=g["depth"], normal=g["normal"], ids=g["idx"], albedo=g["albedo"], emitted=g["emitted"], **atrous)
         if gamma != 1.0:
@@ -2529,8 +2667,8 @@ class SvgfDenoiser(TemporalDenoiser):
     Renderer.svgf_filter) where TemporalDenoiser has the fixed a-trous filter.  `params` as there."""
 
     def step(self, cam: RtwCamera, params: RtwParams, min_history: int = SVGF_DEFAULTS["min_history"], radius: int = SVGF_DEFAULTS["radius"],
-             motion=None, motion_first: int = 0, **svgf):
-        """One frame (motion, motion_first as TemporalDenoiser.step's): rendered, its guides taken and accumulated as TemporalDenoiser.step does; variance_estimate (min_history, radius; the
+             motion=None, motion_first: int = 0, prev_ouv=None, prev_poses=None, **svgf):
+        """One frame (motion, motion_first, prev_ouv, prev_poses as TemporalDenoiser.step's): rendered, its guides taken and accumulated as TemporalDenoiser.step does; variance_estimate (min_history, radius; the
         guide sigmas and same_object those of **svgf) on the new history's moments and length; svgf_filter (keyword arguments: its own) on
         the accumulated colour with albedo and emission; params.gamma applied.  Returns (frame, accumulated, variance, stats): variance is
         the estimate the filter was steered by; stats holds render, temporal, variance and svgf (RtwStats and three RtwFilterStats),
@@ -2545,9 +2683,9 @@ class SvgfDenoiser(TemporalDenoiser):
             cur, st = r.render(cam, params)
         finally:
             params.gamma = gamma
-        g = r.surface_map(cam, params.width, params.height, params.mint, params.maxt, params.integrator, RAYS_PIXEL, (0.5, 0.5), accel=params.accel)
+        g, points = self._guides(cam, params, prev_ouv, prev_poses)
         self.history, _, st_t = r.temporal_accumulate(cur, cam, depth=g["depth"], normal=g["normal"], ids=g["idx"], history=self.history,
-                                                      motion=motion, motion_first=motion_first, offset=(0.5, 0.5), **self.params)
+                                                      motion=motion, motion_first=motion_first, offset=(0.5, 0.5), **points, **self.params)
         acc = self.history["color"]
         guide_kw = {k: svgf[k] for k in ("sigma_depth", "sigma_normal", "same_object") if k in svgf}
         variance, st_v = r.variance_estimate(self.history["moments"], self.history["len"], depth=g["depth"], normal=g["normal"], ids=g["idx"],

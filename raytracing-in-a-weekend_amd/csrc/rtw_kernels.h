@@ -147,6 +147,9 @@ struct QueryArgs {
     uint32_t rust2;               // the record follows Rust2's texel rules (RTW_INTEGRATOR_RUST2, _LIGHT_CAST, _LIGHT_BIASED)
     uint32_t ray_rule;            // from_camera: RTW_RAYS_DEPTH_MAP | RTW_RAYS_PIXEL
     float off_x, off_y;           // RTW_RAYS_PIXEL: the offset inside the pixel
+    // rtw_ctx_scene_surface_tri / rtw_ctx_surface_map_tri: the SURF builds only; at the END, so that no offset above moves
+    int32_t *tri_out;             // [n] or null: the winning triangle's position in the caller's list (win 3 or 4), else -1
+    float *bary_out;              // [n][2] or null: its (alfa, beta) as tri_inside forms them on the ray tri_record is given, else 0 0
 };
 #define RTW_QUERY_SLOTS 64u       // one atomic per wave and counter, spread over 64 cache lines: tens of thousands of waves adding to ONE line serialise
 #define RTW_QUERY_STRIDE 16u      // counters (u64) per line: 128 bytes

@@ -71,6 +71,24 @@ void launch_mesh_motion(const float *prev_poses, const float *cur_poses, uint32_
                        cur_poses, n, rows, n_invalid);
 }
 
+// rtw_ctx_deform_motion: thread p runs deform_point (rtw_refit.h -- the definition the host form runs) for pixel p.  The nine floats of a
+// previous triangle are a gather (neighbouring pixels mostly share a triangle); tri, bary and the two results are consecutive per lane.
+__global__ __launch_bounds__(RTW_MESH_MOVE_BLOCK) void deform_motion_kernel(const int32_t *tri, const float *bary, uint32_t n, DeformMesh m, float *point,
+                                                                            float *normal) {
+    const uint32_t p = blockIdx.x * RTW_MESH_MOVE_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const float2 ab = *reinterpret_cast<const float2 *>(bary + 2 * (size_t)p);
+    float x[3], nr[3];
+    deform_point(m, tri[p], ab.x, ab.y, m.prev_poses ? m.idx[p] : 0, x, nr);
+    *reinterpret_cast<float3 *>(point + 3 * (size_t)p) = make_float3(x[0], x[1], x[2]);
+    *reinterpret_cast<float3 *>(normal + 3 * (size_t)p) = make_float3(nr[0], nr[1], nr[2]);
+}
+
+void launch_deform_motion(const int32_t *tri, const float *bary, uint32_t n, const DeformMesh &m, float *point, float *normal, hipStream_t stream) {
+    hipLaunchKernelGGL(deform_motion_kernel, dim3((n + RTW_MESH_MOVE_BLOCK - 1) / RTW_MESH_MOVE_BLOCK), dim3(RTW_MESH_MOVE_BLOCK), 0, stream, tri, bary, n,
+                       m, point, normal);
+}
+
 void launch_mesh_move(TriNode *top, const uint32_t *top_order, f4 *rows, const float *poses, const TriNode *root, const uint32_t *order,
                       const uint32_t *first, const uint32_t *d_first, uint32_t n_heights, bool one_group, uint32_t *counts, hipStream_t stream) {
     if (n_heights == 0) return;

@@ -218,6 +218,22 @@ __global__ __launch_bounds__(RTW_BLOCK) void scene_hits_kernel(const QueryArgs A
             *reinterpret_cast<float3 *>(A.albedo_out + 3 * (size_t)i) = make_float3(cm.x, cm.y, cm.z);
             if (A.emitted_out) *reinterpret_cast<float3 *>(A.emitted_out + 3 * (size_t)i) = make_float3(em.x, em.y, em.z);
             if (A.material_out) *reinterpret_cast<float3 *>(A.material_out + 3 * (size_t)i) = make_float3(mt.x, mt.y, mt.z);
+            if (A.tri_out || A.bary_out) {                         // (a wave-uniform branch) the triangle under the ray and the point's place in it
+                const bool on_tri = found && win >= 3;
+                float alfa = 0.0f, beta = 0.0f;
+                if (on_tri) {                                      // tri_inside on the ray tri_record was given, above
+                    v3 lo = o, ld = d;
+                    if (win == 4) {
+                        quat qn; v3 pos;
+                        mesh_row_lane(A.mesh_rows, (uint32_t)mp, qn, pos);
+                        lo = mesh_rot(qn, o - pos); ld = mesh_rot(qn, d);
+                    }
+                    const DevTri &q = A.tris.list[tk];
+                    tri_inside(q.origin, q.u, q.v, q.w, lo.x, lo.y, lo.z, ld.x, ld.y, ld.z, ht, alfa, beta);
+                }
+                if (A.tri_out) A.tri_out[i] = on_tri ? tk : -1;
+                if (A.bary_out) *reinterpret_cast<float2 *>(A.bary_out + 2 * (size_t)i) = make_float2(alfa, beta);
+            }
         }
     }
     RTW_Q_COUNT_FLUSH(A.counters, n_sph, n_nodes, n_quad, overflow, 0u);

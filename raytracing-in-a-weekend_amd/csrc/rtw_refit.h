@@ -207,6 +207,60 @@ __host__ __device__ inline bool mesh_motion_row(const float *prev, const float *
     return false;
 }
 
+// ---- per-pixel motion of a deforming mesh (rtw.h "previous points of a deformed mesh") ----------------------------------------
+// The triangle and the barycentrics under a ray whose hit parameter is t, from the mesh's ouv rows alone (rtw_tri_bary): Triangle::new's w
+// of the row (tri_derive), then the interior part of the hit test (tri_inside) -- what the surface kernel writes for a winner of kind 3 or 4,
+// whose list rows hold the same tri_derive of the same ouv.  `tri` outside [0, n_tris), decided without wrap-around: 0 0, no address formed.
+__host__ __device__ inline void tri_bary_one(const float *ouv, uint32_t n_tris, const float *ray, float t, int32_t tri, float *bary) {
+    bary[0] = 0.0f; bary[1] = 0.0f;
+    if (tri < 0 || (int64_t)tri >= (int64_t)n_tris) return;
+    const float *s = ouv + 9 * (size_t)tri;
+    float normal[3], w[3], d;
+    tri_derive(s, s + 3, s + 6, normal, d, w);
+    tri_inside(s, s + 3, s + 6, w, ray[0], ray[1], ray[2], ray[3], ray[4], ray[5], t, bary[0], bary[1]);
+}
+
+// What the deform pass takes besides the per-pixel tri and bary: the previous frame's mesh, and for a placed mesh the pixels' ids and the
+// previous poses (poses null: the mesh stands in world space; idx and first are then not read).
+struct DeformMesh { const float *prev_ouv; uint32_t n_tris; const int32_t *idx; const float *prev_poses; uint32_t n_mesh, first; };
+
+// One pixel: where its surface point lay a frame ago and the normal it had there; the whole of what either side runs for it.
+//   a point:   0 <= tri < n_tris (and, with poses, 0 <= k = idx - first < n_mesh in 64 bits);   {o, u, v} = row tri of prev_ouv
+//              x'_c = (o_c + alfa * u_c) + beta * v_c;   n' = tri_derive's normal of the row
+//              without poses: point = x', normal = n';  with (qn, pos) = mesh_pose_rows(pose k): point = rotate(conj(qn), x') + pos,
+//              normal = rotate(qn, n')  (quat_rotate_n: the placement meets rays at conj(qn).rotate(x') + pos and reports qn.rotate(n'))
+//   no point:  the quiet NaN 0x7fc00000 in all six; also for a pose mesh_pose_rows refuses.  No address is formed from such a tri or k.
+__host__ __device__ inline void deform_point(const DeformMesh &m, int32_t tri, float alfa, float beta, int32_t id, float *point, float *normal) {
+    const float qnan = __builtin_bit_cast(float, 0x7fc00000u);
+    for (int c = 0; c < 3; c++) { point[c] = qnan; normal[c] = qnan; }
+    if (tri < 0 || (int64_t)tri >= (int64_t)m.n_tris) return;
+    f4 qa, qb;
+    if (m.prev_poses) {
+        const int64_t k = (int64_t)id - (int64_t)m.first;
+        if (k < 0 || k >= (int64_t)m.n_mesh) return;
+        if (!mesh_pose_rows(m.prev_poses + 7 * (size_t)k, qa, qb)) return;
+    }
+    const float *s = m.prev_ouv + 9 * (size_t)tri;
+    float x[3], n[3], w[3], d;
+    for (int c = 0; c < 3; c++) x[c] = (s[c] + alfa * s[3 + c]) + beta * s[6 + c];
+    tri_derive(s, s + 3, s + 6, n, d, w);
+    if (m.prev_poses) {
+        const quat qn = qmk(qa.x, qa.y, qa.z, qa.w), qc = qmk(qn.w, -qn.x, -qn.y, -qn.z);
+        float r0, r1, r2;
+        quat_rotate_n(qc, x[0], x[1], x[2], r0, r1, r2);
+        x[0] = r0 + qb.x; x[1] = r1 + qb.y; x[2] = r2 + qb.z;
+        quat_rotate_n(qn, n[0], n[1], n[2], r0, r1, r2);
+        n[0] = r0; n[1] = r1; n[2] = r2;
+    }
+    for (int c = 0; c < 3; c++) { point[c] = x[c]; normal[c] = n[c]; }
+}
+// Everything rtw_deform_motion refuses (rtw.h)
+inline bool deform_args_ok(const int32_t *tri, const float *bary, uint32_t n, const DeformMesh &m, const float *point, const float *normal) {
+    if (!tri || !bary || !m.prev_ouv || !point || !normal || n == 0 || m.n_tris == 0) return false;
+    if (m.prev_poses && (!m.idx || m.n_mesh == 0 || m.n_mesh > RTW_MAX_MESH_INSTANCES)) return false;
+    return true;
+}
+
 // ---- host (rtw_tri.cpp) ---------------------------------------------------------------------------------------------------------------------
 // The order a refit visits the nodes in: `order` holds every node index sorted by height (a leaf: 0; an inner node: 1 + the higher child),
 // ties by index; height h owns order[first[h] .. first[h + 1]), first.size() = heights + 1.  Height 0 is the leaf pass, each further height
@@ -244,5 +298,7 @@ void launch_mesh_move(TriNode *top, const uint32_t *top_order, f4 *rows, const f
 // rtw_ctx_mesh_instance_motion on `stream`: one thread per placement running mesh_motion_row; device pointers, *n_invalid (device u32, zeroed by
 // the caller) receives the count of refused poses.  Allocates nothing.
 void launch_mesh_motion(const float *prev_poses, const float *cur_poses, uint32_t n, RtwMotionRow *rows, uint32_t *n_invalid, hipStream_t stream);
+// rtw_ctx_deform_motion on `stream`: one thread per pixel running deform_point; device pointers.  Allocates nothing.
+void launch_deform_motion(const int32_t *tri, const float *bary, uint32_t n, const DeformMesh &m, float *point, float *normal, hipStream_t stream);
 
 } // namespace rtw

@@ -63,6 +63,8 @@ struct MeshMem {
 // Buffers of rtw_ctx_mesh_instance_motion, grown on demand and kept until the context is destroyed: the staging of host poses and of rows for a
 // host result, the count of refused poses and its pinned read-back.  A call on device buffers of a size seen before allocates nothing.
 struct MotionMem { DevMem prev, cur, rows, bad; PinnedMem h_bad; };
+// ... and of rtw_ctx_deform_motion: the staging of each host input and of each host result
+struct DeformMem { DevMem tri, bary, ouv, idx, poses, point, normal; };
 struct ScratchMem {
     DevMem queue, stats;
     PinnedMem h_stats;                   // pinned: the counter read-back is a true async copy
@@ -105,6 +107,7 @@ struct rtw_ctx {
     TemporalScratch *temporal = nullptr; // buffers of rtw_ctx_temporal_accumulate (rtw_temporal.hip), created on its first call
     FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
     MotionMem motion_mem;                // buffers of rtw_ctx_mesh_instance_motion
+    DeformMem deform_mem;                // buffers of rtw_ctx_deform_motion
     // Rust2 triangles of the scene (rtw_ctx_set_triangles; cleared by rtw_ctx_set_scene)
     DevTris tris{};                      // tris.nodes stays null here: a render sets it (tri_view) when the tree may be used
     bool tri_tree = false;               // no triangle breaks the cull's derivation (DESIGN.md "Rust2 triangles")
@@ -304,7 +307,7 @@ struct Staging {
     }
 
 private:
-    static constexpr int MAX = 7;        // (rtw_ctx_scene_surface stages seven)
+    static constexpr int MAX = 9;        // (rtw_ctx_scene_surface_tri stages nine)
     struct Back { void *dst; const void *src; size_t bytes; };
     rtw_ctx *c;
     bool always;
@@ -1208,6 +1211,7 @@ struct SurfaceAsk {
     float *albedo, *emitted, *material;
     uint32_t integrator, ray_rule;
     float off_x, off_y;
+    int32_t *tri; float *bary;           // (the _tri calls; either may be null)
 };
 
 // All four calls: cam != null builds the rays of a width x height map in the kernel, else `rays` [n][6] are read.  sf != null: the surface
@@ -1238,6 +1242,8 @@ static int scene_query(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_
         if (sf->material) q.material_out = st.out(sf->material, 3 * t_bytes);
         q.rust2 = sf->integrator == RTW_INTEGRATOR_RUST2 || sf->integrator == RTW_INTEGRATOR_LIGHT_CAST || sf->integrator == RTW_INTEGRATOR_LIGHT_BIASED;
         q.ray_rule = sf->ray_rule; q.off_x = sf->off_x; q.off_y = sf->off_y;
+        if (sf->tri) q.tri_out = st.out(sf->tri, sizeof(int32_t) * (size_t)n);
+        if (sf->bary) q.bary_out = st.out(sf->bary, 2 * t_bytes);
         if (st.e == hipSuccess && !q.albedo_out) st.e = hipErrorInvalidValue;      // (albedo_out selects the build)
     }
     return counted_pass(c, st, 0, n, stats, [&] { launch_scene_hits(q, cam != nullptr, tree, c->stream); });
@@ -1257,25 +1263,38 @@ int rtw_ctx_depth_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t
 }
 
 // The surface buffers (rtw.h "surface buffers"): the same pass, the winner's hit record written beside t, idx and normal
-int rtw_ctx_scene_surface(rtw_ctx *c, const float *rays, uint32_t n_rays, float time, float mint, float maxt, uint32_t accel, uint32_t integrator,
-                          float *t_out, int32_t *idx_out, float *normal_out, float *albedo_out, float *emitted_out, float *material_out,
-                          RtwStats *stats) {
+int rtw_ctx_scene_surface_tri(rtw_ctx *c, const float *rays, uint32_t n_rays, float time, float mint, float maxt, uint32_t accel, uint32_t integrator,
+                              float *t_out, int32_t *idx_out, float *normal_out, float *albedo_out, float *emitted_out, float *material_out,
+                              int32_t *tri_out, float *bary_out, RtwStats *stats) {
     if (!c || !rays || !t_out || !idx_out || n_rays == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
     if (!albedo_out || integrator > RTW_INTEGRATOR_LIGHT_BIASED) return RTW_E_INVALID;
-    const SurfaceAsk sf = { albedo_out, emitted_out, material_out, integrator, RTW_RAYS_DEPTH_MAP, 0.0f, 0.0f };
+    const SurfaceAsk sf = { albedo_out, emitted_out, material_out, integrator, RTW_RAYS_DEPTH_MAP, 0.0f, 0.0f, tri_out, bary_out };
     return scene_query(c, nullptr, 0, 0, rays, n_rays, time, mint, maxt, accel, std::numeric_limits<float>::infinity(), t_out, idx_out, normal_out, stats,
                        &sf);
 }
+int rtw_ctx_scene_surface(rtw_ctx *c, const float *rays, uint32_t n_rays, float time, float mint, float maxt, uint32_t accel, uint32_t integrator,
+                          float *t_out, int32_t *idx_out, float *normal_out, float *albedo_out, float *emitted_out, float *material_out,
+                          RtwStats *stats) {
+    return rtw_ctx_scene_surface_tri(c, rays, n_rays, time, mint, maxt, accel, integrator, t_out, idx_out, normal_out, albedo_out, emitted_out,
+                                     material_out, nullptr, nullptr, stats);
+}
 
-int rtw_ctx_surface_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, uint32_t ray_rule, const float *offset, float time,
-                        float mint, float maxt, uint32_t accel, uint32_t integrator, float *depth_out, int32_t *idx_out, float *normal_out,
-                        float *albedo_out, float *emitted_out, float *material_out, RtwStats *stats) {
+int rtw_ctx_surface_map_tri(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, uint32_t ray_rule, const float *offset, float time,
+                            float mint, float maxt, uint32_t accel, uint32_t integrator, float *depth_out, int32_t *idx_out, float *normal_out,
+                            float *albedo_out, float *emitted_out, float *material_out, int32_t *tri_out, float *bary_out, RtwStats *stats) {
     if (!c || !cam || !depth_out || width == 0 || height == 0 || accel > RTW_ACCEL_BVH) return RTW_E_INVALID;
     if ((uint64_t)width * height > 0xFFFFFFFFull) return RTW_E_INVALID;
     if (!albedo_out || integrator > RTW_INTEGRATOR_LIGHT_BIASED || ray_rule > RTW_RAYS_PIXEL) return RTW_E_INVALID;
-    const SurfaceAsk sf = { albedo_out, emitted_out, material_out, integrator, ray_rule, offset ? offset[0] : 0.0f, offset ? offset[1] : 0.0f };
+    const SurfaceAsk sf = { albedo_out, emitted_out, material_out, integrator, ray_rule, offset ? offset[0] : 0.0f, offset ? offset[1] : 0.0f,
+                            tri_out, bary_out };
     return scene_query(c, cam, width, height, nullptr, width * height, time, mint, maxt, accel, host_mul(maxt, 1.6f), depth_out, idx_out, normal_out,
                        stats, &sf);
+}
+int rtw_ctx_surface_map(rtw_ctx *c, const RtwCamera *cam, uint32_t width, uint32_t height, uint32_t ray_rule, const float *offset, float time,
+                        float mint, float maxt, uint32_t accel, uint32_t integrator, float *depth_out, int32_t *idx_out, float *normal_out,
+                        float *albedo_out, float *emitted_out, float *material_out, RtwStats *stats) {
+    return rtw_ctx_surface_map_tri(c, cam, width, height, ray_rule, offset, time, mint, maxt, accel, integrator, depth_out, idx_out, normal_out,
+                                   albedo_out, emitted_out, material_out, nullptr, nullptr, stats);
 }
 
 // The any-hit pass (rtw.h "occlusion queries"; kernel: rtw_occluded.hip): scene_query's conditions, views, staging and stream order
@@ -1452,7 +1471,7 @@ int rtw_ctx_temporal_accumulate(rtw_ctx *c, const float *cur, uint32_t w, uint32
     if (c->pend.active) return RTW_E_INVALID;
     const TemporalBuffers b = { cur, depth, normal, idx, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
                                 out_color, out_moments, out_len, out_variance };
-    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, nullptr, stats, &g_last_hip);
+    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, nullptr, nullptr, stats, &g_last_hip);
 }
 
 // ... and with moving objects (rtw.h "temporal accumulation with moving objects"): without rows and prev_xy the same launch
@@ -1466,7 +1485,23 @@ int rtw_ctx_temporal_accumulate_motion(rtw_ctx *c, const float *cur, uint32_t w,
     const TemporalBuffers b = { cur, depth, normal, idx, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
                                 out_color, out_moments, out_len, out_variance };
     const TemporalMotion m = { rows, n_rows, first, out_prev_xy };
-    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, &m, stats, &g_last_hip);
+    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, &m, nullptr, stats, &g_last_hip);
+}
+
+// ... and with per-pixel previous points (rtw.h "temporal accumulation with per-pixel motion"): without them the same launches
+int rtw_ctx_temporal_accumulate_points(rtw_ctx *c, const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth, const float *normal,
+                                       const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color, const float *prev_moments,
+                                       const float *prev_len, const float *prev_depth, const float *prev_normal, const int32_t *prev_idx,
+                                       const RtwTemporal *p, const RtwMotionRow *rows, uint32_t n_rows, uint32_t first, const float *prev_point,
+                                       const float *carried_normal, float *out_color, float *out_moments, float *out_len, float *out_variance,
+                                       float *out_prev_xy, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    const TemporalBuffers b = { cur, depth, normal, idx, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
+                                out_color, out_moments, out_len, out_variance };
+    const TemporalMotion m = { rows, n_rows, first, out_prev_xy };
+    const TemporalPoints pt = { prev_point, carried_normal };
+    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, &m, &pt, stats, &g_last_hip);
 }
 
 // The motion rows of moved placements (rtw_mesh_move.hip) on this context's GPU and stream; the scene is not involved.
@@ -1506,6 +1541,43 @@ int rtw_ctx_mesh_instance_motion(rtw_ctx *c, const float *prev_poses, const floa
     if (const int rc = call_status(c, e)) return rc;
     if (n_invalid) *n_invalid = *m.h_bad.as<uint32_t>();
     return RTW_OK;
+}
+
+// Previous points of a deformed mesh (rtw_mesh_move.hip) on this context's GPU and stream; the scene is not involved: the
+// caller kept prev_ouv (and prev_poses) from the previous frame.
+int rtw_ctx_deform_motion(rtw_ctx *c, const int32_t *tri, const float *bary, uint32_t n, const float *prev_ouv, uint32_t n_tris, const int32_t *idx,
+                          const float *prev_poses, uint32_t n_mesh, uint32_t first, float *prev_point_out, float *carried_normal_out) {
+    DeformMesh m = { prev_ouv, n_tris, idx, prev_poses, prev_poses ? n_mesh : 0u, prev_poses ? first : 0u };
+    if (!c || !deform_args_ok(tri, bary, n, m, prev_point_out, carried_normal_out)) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    HIP_TRY(hipSetDevice(c->device));
+    DeformMem &dm = c->deform_mem;
+    if (!prev_poses) m.idx = nullptr;
+    const size_t f1 = sizeof(float) * (size_t)n;
+    hipError_t e = hipSuccess;
+    struct Stage { const void **p; DevMem *mem; size_t bytes; };
+    const Stage stages[5] = { { (const void **)&tri, &dm.tri, sizeof(int32_t) * (size_t)n },
+                              { (const void **)&bary, &dm.bary, 2 * f1 },
+                              { (const void **)&m.prev_ouv, &dm.ouv, 9 * sizeof(float) * (size_t)n_tris },
+                              { (const void **)&m.idx, &dm.idx, sizeof(int32_t) * (size_t)n },
+                              { (const void **)&m.prev_poses, &dm.poses, MOVE_POSE_BYTES * (size_t)m.n_mesh } };
+    for (const Stage &st : stages) {
+        if (!*st.p || on_device(*st.p, c->device)) continue;
+        HIP_TRY(st.mem->reserve(st.bytes));
+        if (e == hipSuccess) e = hipMemcpyAsync(st.mem->ptr, *st.p, st.bytes, hipMemcpyDefault, c->stream);
+        *st.p = st.mem->ptr;
+    }
+    float *d_point = prev_point_out, *d_normal = carried_normal_out;
+    if (!on_device(prev_point_out, c->device)) { HIP_TRY(dm.point.reserve(3 * f1)); d_point = dm.point.as<float>(); }
+    if (!on_device(carried_normal_out, c->device)) { HIP_TRY(dm.normal.reserve(3 * f1)); d_normal = dm.normal.as<float>(); }
+    if (e == hipSuccess) {
+        launch_deform_motion(tri, bary, n, m, d_point, d_normal, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && d_point != prev_point_out) e = hipMemcpyAsync(prev_point_out, d_point, 3 * f1, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess && d_normal != carried_normal_out) e = hipMemcpyAsync(carried_normal_out, d_normal, 3 * f1, hipMemcpyDefault, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return call_status(c, e);
 }
 
 // The variance estimate and the variance-steered a-trous filter (rtw_svgf.hip) likewise, on the a-trous filter's scratch.

@@ -1,4 +1,4 @@
-// rtw_temporal.cpp -- the host forms of the temporal accumulation (rtw_temporal_accumulate, rtw_temporal_accumulate_motion, include/rtw.h) and the argument checks and
+// rtw_temporal.cpp -- the host forms of the temporal accumulation (rtw_temporal_accumulate, _motion, _points, include/rtw.h) and the argument checks and
 // plan it shares with the device path (rtw_temporal.hip).  Pure host code: no HIP call.  One thread over the pixels, each running
 // temporal_pixel (rtw_temporal.h), which the kernel runs too.
 #include "rtw_temporal.h"
@@ -71,6 +71,15 @@ int temporal_check_motion(const int32_t *idx, const RtwMotionRow *rows, uint32_t
     return RTW_OK;
 }
 
+int temporal_check_points(const float *prev_point, const float *carried_normal, const float *out_color, const float *out_moments, const float *out_len,
+                          const float *out_variance, const float *out_prev_xy) {
+    if (carried_normal && !prev_point) return RTW_E_INVALID;
+    for (const float *in : { prev_point, carried_normal })
+        for (const float *out : { out_color, out_moments, out_len, out_variance, out_prev_xy })
+            if (in && in == out) return RTW_E_INVALID;
+    return RTW_OK;
+}
+
 } // namespace rtw
 
 using namespace rtw;
@@ -118,7 +127,38 @@ extern "C" int rtw_temporal_accumulate_motion(const float *cur, uint32_t w, uint
     const TemporalOut o = { out_color, out_moments, out_len, out_variance };
     const TemporalMotion mo = { rows, n_rows, first, out_prev_xy };
     for (uint32_t j = 0; j < h; j++)
-        for (uint32_t i = 0; i < w; i++) temporal_pixel_t<true>(pl, f, hs, o, mo, i, j);
+        for (uint32_t i = 0; i < w; i++) temporal_pixel_t<true>(pl, f, hs, o, mo, TemporalPoints{ nullptr, nullptr }, i, j);
+    if (stats) {
+        const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        *stats = RtwFilterStats{ 0.0f, 0.0f, 0.0f, 0.0f, ms, ms, 4ull * w * h };
+    }
+    return RTW_OK;
+}
+
+extern "C" int rtw_temporal_accumulate_points(const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth, const float *normal,
+                                              const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color, const float *prev_moments,
+                                              const float *prev_len, const float *prev_depth, const float *prev_normal, const int32_t *prev_idx,
+                                              const RtwTemporal *params, const RtwMotionRow *rows, uint32_t n_rows, uint32_t first,
+                                              const float *prev_point, const float *carried_normal, float *out_color, float *out_moments,
+                                              float *out_len, float *out_variance, float *out_prev_xy, RtwFilterStats *stats) {
+    if (!prev_point && !carried_normal)
+        return rtw_temporal_accumulate_motion(cur, w, h, cam, depth, normal, idx, prev_cam, prev_color, prev_moments, prev_len, prev_depth,
+                                              prev_normal, prev_idx, params, rows, n_rows, first, out_color, out_moments, out_len, out_variance,
+                                              out_prev_xy, stats);
+    const auto t0 = std::chrono::steady_clock::now();
+    TemporalPlan pl;
+    int rc = temporal_check(cur, w, h, cam, depth, normal, idx, prev_cam, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
+                            params, out_color, out_moments, out_len, pl);
+    if (rc == RTW_OK) rc = temporal_check_motion(idx, rows, n_rows, first, out_color, out_moments, out_len, out_variance, out_prev_xy);
+    if (rc == RTW_OK) rc = temporal_check_points(prev_point, carried_normal, out_color, out_moments, out_len, out_variance, out_prev_xy);
+    if (rc != RTW_OK) return rc;
+    const TemporalFrame f = { cur, depth, normal, idx };
+    const TemporalHistory hs = { prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx };
+    const TemporalOut o = { out_color, out_moments, out_len, out_variance };
+    const TemporalMotion mo = { rows, n_rows, first, out_prev_xy };
+    const TemporalPoints pt = { prev_point, carried_normal };
+    for (uint32_t j = 0; j < h; j++)
+        for (uint32_t i = 0; i < w; i++) temporal_pixel_t<true, true>(pl, f, hs, o, mo, pt, i, j);
     if (stats) {
         const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         *stats = RtwFilterStats{ 0.0f, 0.0f, 0.0f, 0.0f, ms, ms, 4ull * w * h };

@@ -6,6 +6,8 @@
 // With moving objects (rtw.h "temporal accumulation with moving objects") the same definition is instantiated a second time,
 // temporal_pixel_t<true>: a pixel whose object has a row in the caller's table carries its world point into the previous frame first
 // (temporal_row, temporal_project_row) and takes the four taps; every other pixel runs the code of temporal_pixel_t<false>.
+// With per-pixel motion (rtw.h "temporal accumulation with per-pixel motion") a third time, temporal_pixel_t<true, true>: a pixel
+// whose prev_point is not NaN projects that point (temporal_project_point) and takes the four taps; every other pixel runs the code above.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rtw_pixel_ray.h"
@@ -34,6 +36,8 @@ struct TemporalHistory { const float *color, *moments, *len, *depth, *normal; co
 struct TemporalOut { float *color, *moments, *len, *variance; };
 // What the calls with motion add (include/rtw.h "temporal accumulation with moving objects"): the table (rows null: none) and prev_xy (may be null)
 struct TemporalMotion { const RtwMotionRow *rows; uint32_t n_rows, first; float *prev_xy; };
+// What the calls with per-pixel motion add: each pixel's previous world point (null: none) and the normal it had there (null: normal[p])
+struct TemporalPoints { const float *point, *normal; };
 
 // What the counted taps add up to.
 struct TemporalSum { float w, c0, c1, c2, m1, m2, len; };
@@ -97,6 +101,17 @@ __host__ __device__ inline bool temporal_project_row(const TemporalPlan &pl, con
     return s > 0.0f && fx > -1.0f && fx < (float)pl.w && fy > -1.0f && fy < (float)pl.h;
 }
 
+// temporal_project for a pixel that brings its previous world point P' along: d = P' - prev_cam.origin, then s, fx, fy as for a row.  An
+// infinity or a NaN in P' ends as an s or fx that is not finite or not in the box: false, never an index.
+__host__ __device__ inline bool temporal_project_point(const TemporalPlan &pl, const float *Pp, float &fx, float &fy, float &s) {
+    float d[3];
+    for (int k = 0; k < 3; k++) d[k] = Pp[k] - pl.po[k];
+    s = temporal_dot(d, pl.n) / pl.pn;
+    fx = ((temporal_dot(d, pl.a) / s - pl.pa) / pl.ua) - pl.ox;
+    fy = ((temporal_dot(d, pl.b) / s - pl.pb) / pl.vb) - pl.oy;
+    return s > 0.0f && fx > -1.0f && fx < (float)pl.w && fy > -1.0f && fy < (float)pl.h;
+}
+
 // Does previous pixel q (inside the frame) count as history for a centre with normal `np`, object `id` and reprojected depth s?
 __host__ __device__ inline bool temporal_tap_ok(const TemporalPlan &pl, const TemporalHistory &hs, size_t q, float s, const float *np, int32_t id) {
     if (!(hs.len[q] > 0.0f)) return false;                                               // (a hole: 0, or NaN)
@@ -135,10 +150,11 @@ __host__ __device__ inline float temporal_blend_factor(float n_, float floor_) {
 }
 
 // Pixel (i, j).  o.color may be f.cur: the pixel's own cur is read before anything is written.  MOTION: the calls with a table of rows or
-// prev_xy; false compiles to the rule without them (`mo` is not read), which is what rtw_temporal_accumulate and its kernel run.
-template <bool MOTION>
+// prev_xy; false compiles to the rule without them (`mo` is not read), which is what rtw_temporal_accumulate and its kernel run.  POINTS
+// (only with MOTION): the calls with prev_point; false compiles to the rule without it (`pt` is not read).
+template <bool MOTION, bool POINTS = false>
 __host__ __device__ inline void temporal_pixel_t(const TemporalPlan &pl, const TemporalFrame &f, const TemporalHistory &hs, const TemporalOut &o,
-                                                 const TemporalMotion &mo, uint32_t i, uint32_t j) {
+                                                 const TemporalMotion &mo, const TemporalPoints &pt, uint32_t i, uint32_t j) {
     const size_t p = (size_t)j * pl.w + (size_t)i;
     const float r = f.cur[3 * p], g = f.cur[3 * p + 1], b = f.cur[3 * p + 2];
     const float L = (0.2126f * r + 0.7152f * g) + 0.0722f * b;
@@ -147,10 +163,18 @@ __host__ __device__ inline void temporal_pixel_t(const TemporalPlan &pl, const T
     TemporalSum t = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
     float fx, fy, s;
     const RtwMotionRow *row = nullptr;
-    bool cand = false;
+    bool cand = false, has_pt = false;
     if (pl.has_prev) {
-        if (MOTION && mo.rows) row = temporal_row(mo, f.idx[p]);
-        cand = (MOTION && row) ? temporal_project_row(pl, *row, i, j, f.depth[p], fx, fy, s) : temporal_project(pl, i, j, f.depth[p], fx, fy, s);
+        float Pp[3] = { 0.0f, 0.0f, 0.0f };
+        if (POINTS && pt.point) {
+            Pp[0] = pt.point[3 * p]; Pp[1] = pt.point[3 * p + 1]; Pp[2] = pt.point[3 * p + 2];
+            has_pt = Pp[0] == Pp[0];                                                     // (a NaN in x: the pixel has no point; its row, if any, counts)
+        }
+        if (POINTS && has_pt) cand = temporal_project_point(pl, Pp, fx, fy, s);
+        else {
+            if (MOTION && mo.rows) row = temporal_row(mo, f.idx[p]);
+            cand = (MOTION && row) ? temporal_project_row(pl, *row, i, j, f.depth[p], fx, fy, s) : temporal_project(pl, i, j, f.depth[p], fx, fy, s);
+        }
     }
     if (MOTION && mo.prev_xy) {
         mo.prev_xy[2 * p] = pl.has_prev ? fx : __builtin_nanf("");
@@ -159,14 +183,15 @@ __host__ __device__ inline void temporal_pixel_t(const TemporalPlan &pl, const T
     if (cand) {
         float np[3] = { 0.0f, 0.0f, 0.0f };
         if (pl.terms & TEMPORAL_NORMAL) {
-            np[0] = f.normal[3 * p]; np[1] = f.normal[3 * p + 1]; np[2] = f.normal[3 * p + 2];
+            const float *nr = (POINTS && has_pt && pt.normal) ? pt.normal : f.normal;
+            np[0] = nr[3 * p]; np[1] = nr[3 * p + 1]; np[2] = nr[3 * p + 2];
             if (MOTION && row) {
                 const float n0 = np[0], n1 = np[1], n2 = np[2];
                 for (int k = 0; k < 3; k++) np[k] = (row->nrm[3 * k] * n0 + row->nrm[3 * k + 1] * n1) + row->nrm[3 * k + 2] * n2;
             }
         }
         const int32_t id = (pl.terms & TEMPORAL_IDX) ? f.idx[p] : 0;
-        if (pl.is_static && !(MOTION && row)) {
+        if (pl.is_static && !(MOTION && row) && !(POINTS && has_pt)) {
             temporal_tap(pl, hs, (int)i, (int)j, 1.0f, s, np, id, t);                  // wx = wy = 0: the other three weigh 0
         } else {
             const float xf = __builtin_floorf(fx), yf = __builtin_floorf(fy);
@@ -211,7 +236,7 @@ __host__ __device__ inline void temporal_pixel_t(const TemporalPlan &pl, const T
 }
 __host__ __device__ inline void temporal_pixel(const TemporalPlan &pl, const TemporalFrame &f, const TemporalHistory &hs, const TemporalOut &o,
                                                uint32_t i, uint32_t j) {
-    temporal_pixel_t<false>(pl, f, hs, o, TemporalMotion{ nullptr, 0u, 0u, nullptr }, i, j);
+    temporal_pixel_t<false>(pl, f, hs, o, TemporalMotion{ nullptr, 0u, 0u, nullptr }, TemporalPoints{ nullptr, nullptr }, i, j);
 }
 
 // Everything rtw_temporal_accumulate refuses (rtw.h); fills `pl`.  RTW_OK or RTW_E_INVALID.  (rtw_temporal.cpp)
@@ -222,5 +247,8 @@ int temporal_check(const float *cur, uint32_t w, uint32_t h, const RtwCamera *ca
 // ... and what the calls with motion refuse besides (rtw.h "temporal accumulation with moving objects")
 int temporal_check_motion(const int32_t *idx, const RtwMotionRow *rows, uint32_t n_rows, uint32_t first, const float *out_color,
                           const float *out_moments, const float *out_len, const float *out_variance, const float *out_prev_xy);
+// ... and the calls with per-pixel motion (rtw.h "temporal accumulation with per-pixel motion")
+int temporal_check_points(const float *prev_point, const float *carried_normal, const float *out_color, const float *out_moments, const float *out_len,
+                          const float *out_variance, const float *out_prev_xy);
 
 } // namespace rtw

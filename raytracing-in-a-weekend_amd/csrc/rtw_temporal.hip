@@ -1,5 +1,5 @@
 // rtw_temporal.hip -- temporal accumulation by reprojection (rtw_temporal.h) on the GPU: the device path of
-// rtw_ctx_temporal_accumulate and rtw_ctx_temporal_accumulate_motion.
+// rtw_ctx_temporal_accumulate, rtw_ctx_temporal_accumulate_motion and rtw_ctx_temporal_accumulate_points (8g).
 //
 // One launch, one thread per pixel running temporal_pixel -- the host form's definition with the host form's plan, so its bytes.
 // Workgroup b covers the 32 x 8 pixels of tile (b % tiles_x, b / tiles_x): a wave is two rows of 32 pixels, so its loads of cur and of the
@@ -33,7 +33,16 @@ __global__ void __launch_bounds__(TBX * TBY) temporal_motion_kernel(TemporalPlan
                                                                     TemporalMotion mo) {
     const uint32_t x = (blockIdx.x % tiles_x) * TBX + threadIdx.x % TBX;
     const uint32_t y = (blockIdx.x / tiles_x) * TBY + threadIdx.x / TBX;
-    if (x < pl.w && y < pl.h) temporal_pixel_t<true>(pl, f, hs, o, mo, x, y);
+    if (x < pl.w && y < pl.h) temporal_pixel_t<true>(pl, f, hs, o, mo, TemporalPoints{ nullptr, nullptr }, x, y);
+}
+
+// ... and with per-pixel previous points (rtw_ctx_temporal_accumulate_points): a third instantiation, chosen on the host likewise.  A pixel
+// with a point loads its 12 bytes (and the 12 of its carried normal) beside cur and takes the four taps; the others run the code above.
+__global__ void __launch_bounds__(TBX * TBY) temporal_points_kernel(TemporalPlan pl, uint32_t tiles_x, TemporalFrame f, TemporalHistory hs, TemporalOut o,
+                                                                    TemporalMotion mo, TemporalPoints pt) {
+    const uint32_t x = (blockIdx.x % tiles_x) * TBX + threadIdx.x % TBX;
+    const uint32_t y = (blockIdx.x / tiles_x) * TBY + threadIdx.x / TBX;
+    if (x < pl.w && y < pl.h) temporal_pixel_t<true, true>(pl, f, hs, o, mo, pt, x, y);
 }
 
 float event_ms(hipEvent_t a, hipEvent_t b) {
@@ -48,6 +57,7 @@ struct TemporalScratch {
     DevMem prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx;
     DevMem out_color, out_moments, out_len, out_variance;                // a result whose buffer is host memory
     DevMem rows, out_prev_xy;                                            // (the calls with motion)
+    DevMem point, carried;                                               // (the calls with per-pixel motion)
     hipEvent_t ev[2] = { nullptr, nullptr };
 };
 
@@ -64,8 +74,8 @@ void temporal_scratch_free(TemporalScratch *s) {
     } while (0)
 
 int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch **scratch, uint32_t w, uint32_t h, const RtwCamera *cam,
-                               const RtwCamera *prev_cam, const TemporalBuffers &b, const RtwTemporal *p, const TemporalMotion *m, RtwFilterStats *stats,
-                               int *last_hip) {
+                               const RtwCamera *prev_cam, const TemporalBuffers &b, const RtwTemporal *p, const TemporalMotion *m, const TemporalPoints *pts,
+                               RtwFilterStats *stats, int *last_hip) {
     const auto t0 = std::chrono::steady_clock::now();
     TemporalPlan pl;
     const int rc = temporal_check(b.cur, w, h, cam, b.depth, b.normal, b.idx, prev_cam, b.prev_color, b.prev_moments, b.prev_len, b.prev_depth,
@@ -77,6 +87,13 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
         if (rm != RTW_OK) return rm;
         mo = *m;
         if (!mo.rows) mo.n_rows = mo.first = 0u;
+    }
+    TemporalPoints pt = { nullptr, nullptr };
+    if (pts && (pts->point || pts->normal)) {
+        const int rp = temporal_check_points(pts->point, pts->normal, b.out_color, b.out_moments, b.out_len, b.out_variance, mo.prev_xy);
+        if (rp != RTW_OK) return rp;
+        pt = *pts;
+        if (!(pl.terms & TEMPORAL_NORMAL)) pt.normal = nullptr;                          // (read by the normal test only)
     }
     const bool motion = mo.rows || mo.prev_xy;
     TEMPORAL_TRY(hipSetDevice(device));
@@ -94,7 +111,7 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
     TemporalHistory hs = { b.prev_color, b.prev_moments, b.prev_len, (pl.terms & TEMPORAL_DEPTH) ? b.prev_depth : nullptr,
                            (pl.terms & TEMPORAL_NORMAL) ? b.prev_normal : nullptr, (pl.terms & TEMPORAL_IDX) ? b.prev_idx : nullptr };
     struct Stage { const void **p; DevMem *m; size_t bytes; };
-    const Stage stages[11] = { { (const void **)&f.cur, &s->cur, f3 },
+    const Stage stages[13] = { { (const void **)&f.cur, &s->cur, f3 },
                                { (const void **)&f.depth, &s->depth, f1 },
                                { (const void **)&f.normal, &s->normal, f3 },
                                { (const void **)&f.idx, &s->idx, n_px * sizeof(int32_t) },
@@ -104,7 +121,9 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
                                { (const void **)&hs.depth, &s->prev_depth, f1 },
                                { (const void **)&hs.normal, &s->prev_normal, f3 },
                                { (const void **)&hs.idx, &s->prev_idx, n_px * sizeof(int32_t) },
-                               { (const void **)&mo.rows, &s->rows, (size_t)mo.n_rows * sizeof(RtwMotionRow) } };
+                               { (const void **)&mo.rows, &s->rows, (size_t)mo.n_rows * sizeof(RtwMotionRow) },
+                               { (const void **)&pt.point, &s->point, f3 },
+                               { (const void **)&pt.normal, &s->carried, f3 } };
     for (const Stage &st : stages) {
         if (!*st.p || on_device(*st.p, device)) continue;
         TEMPORAL_TRY(st.m->reserve(st.bytes));
@@ -128,7 +147,8 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
     const uint32_t tiles_x = (w + TBX - 1) / TBX, tiles_y = (h + TBY - 1) / TBY;
     TEMPORAL_TRY(hipEventRecord(s->ev[0], stream));
     const dim3 grid((unsigned)((uint64_t)tiles_x * tiles_y));
-    if (motion) hipLaunchKernelGGL(temporal_motion_kernel, grid, dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o, mo);
+    if (pt.point) hipLaunchKernelGGL(temporal_points_kernel, grid, dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o, mo, pt);
+    else if (motion) hipLaunchKernelGGL(temporal_motion_kernel, grid, dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o, mo);
     else hipLaunchKernelGGL(temporal_kernel, grid, dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o);
     TEMPORAL_TRY(hipGetLastError());
     TEMPORAL_TRY(hipEventRecord(s->ev[1], stream));

@@ -22,9 +22,12 @@ struct TemporalBuffers {
 // rtw_ctx_temporal_accumulate on `device` / `stream`; *scratch is created on first use.  A failed HIP call stores its code in *last_hip.
 // m: rtw_ctx_temporal_accumulate_motion's table and prev_xy (rtw_temporal.h; host or device memory) -- null, or both of its pointers null:
 // the launch of rtw_ctx_temporal_accumulate.
+// pt: rtw_ctx_temporal_accumulate_points' prev_point and carried_normal (host or device memory) -- null, or prev_point null: the launch
+// `m` alone selects.
 struct TemporalMotion;
+struct TemporalPoints;
 int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch **scratch, uint32_t w, uint32_t h, const RtwCamera *cam,
                                const RtwCamera *prev_cam, const TemporalBuffers &b, const RtwTemporal *p, const TemporalMotion *m,
-                               RtwFilterStats *stats, int *last_hip);
+                               const TemporalPoints *pt, RtwFilterStats *stats, int *last_hip);
 
 } // namespace rtw

@@ -378,6 +378,47 @@ int rtw_mesh_instance_motion(const float *prev_poses, const float *cur_poses, ui
     return RTW_OK;
 }
 
+// The triangle's barycentrics under each ray (rtw.h "surface buffers"): tri_bary_one per ray, what the surface kernel writes for a triangle
+int rtw_tri_bary(const float *ouv, uint32_t n_tris, const float *rays, uint32_t n, const float *t, const int32_t *tri, float *bary_out) {
+    if (!ouv || !rays || !t || !tri || !bary_out || n == 0 || n_tris == 0) return RTW_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) tri_bary_one(ouv, n_tris, rays + 6 * (size_t)i, t[i], tri[i], bary_out + 2 * (size_t)i);
+    return RTW_OK;
+}
+
+// The rays as the placements meet them: ray i turned into the frame of placement idx[i] - first (mesh_pose_rows, quat_rotate_n -- the walk's
+// own operations); a ray without a valid placement is copied
+int rtw_mesh_local_rays(const float *poses, uint32_t n_mesh, uint32_t first, const int32_t *idx, const float *rays, uint32_t n, float *rays_out) {
+    if (!poses || !idx || !rays || !rays_out || n == 0 || n_mesh == 0 || n_mesh > RTW_MAX_MESH_INSTANCES) return RTW_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        const float *r = rays + 6 * (size_t)i;
+        float *o = rays_out + 6 * (size_t)i;
+        const int64_t k = (int64_t)idx[i] - (int64_t)first;
+        f4 a, b;
+        if (k < 0 || k >= (int64_t)n_mesh || !mesh_pose_rows(poses + 7 * (size_t)k, a, b)) {
+            for (int c = 0; c < 6; c++) o[c] = r[c];
+            continue;
+        }
+        const quat qn = qmk(a.x, a.y, a.z, a.w);
+        float x, y, z;
+        quat_rotate_n(qn, r[0] - b.x, r[1] - b.y, r[2] - b.z, x, y, z);
+        o[0] = x; o[1] = y; o[2] = z;
+        quat_rotate_n(qn, r[3], r[4], r[5], x, y, z);
+        o[3] = x; o[4] = y; o[5] = z;
+    }
+    return RTW_OK;
+}
+
+// Previous points of a deformed mesh (rtw.h): deform_point per pixel, the definition rtw_ctx_deform_motion's kernel runs
+int rtw_deform_motion(const int32_t *tri, const float *bary, uint32_t n, const float *prev_ouv, uint32_t n_tris, const int32_t *idx,
+                      const float *prev_poses, uint32_t n_mesh, uint32_t first, float *prev_point_out, float *carried_normal_out) {
+    const DeformMesh m = { prev_ouv, n_tris, idx, prev_poses, prev_poses ? n_mesh : 0u, prev_poses ? first : 0u };
+    if (!deform_args_ok(tri, bary, n, m, prev_point_out, carried_normal_out)) return RTW_E_INVALID;
+    for (uint32_t p = 0; p < n; p++)
+        deform_point(m, tri[p], bary[2 * (size_t)p], bary[2 * (size_t)p + 1], prev_poses ? idx[p] : 0, prev_point_out + 3 * (size_t)p,
+                     carried_normal_out + 3 * (size_t)p);
+    return RTW_OK;
+}
+
 int rtw_mesh_instance_hits_tree(const RtwTriangle *tris, uint32_t n_tris, const RtwMeshInstance *p, uint32_t n, const float *rays, uint32_t n_rays,
                                 float mint, float maxt, float *t_out, int32_t *placement_out, int32_t *tri_out, float *normal_out, RtwStats *stats) {
     if (!rays || !t_out || !placement_out || !tri_out || n_rays == 0 || n == 0) return RTW_E_INVALID;
