@@ -824,6 +824,76 @@ int rtw_ctx_svgf_filter(rtw_ctx *ctx, const float *in, const float *variance, ui
                         const float *normal, const int32_t *idx, const float *albedo, const float *emitted, const RtwAtrous *params,
                         const RtwSvgf *vparams, float *out, float *out_variance /* may be NULL */, RtwFilterStats *stats);
 
+/* ---- neighbourhood colour bounds: mean +- k sigma of the frame around each pixel -- added within v4 --------------------------------------
+ * The box that variance clipping clips a reprojected colour to ("bounded temporal accumulation" below), and, taken without the centre
+ * pixel, the usual firefly clamp of the frame itself.  in, out_lo, out_hi and out_clamped (may be NULL) are [h][w][3] f32; idx [h][w] i32 as
+ * rtw_ctx_surface_map writes it (may be NULL without same_object).  Everything is f32 with one rounding per written operation (no fused
+ * multiply-add), the divide and sqrtf correctly rounded.  Pixel p:
+ *   the taps q = p + (dx, dy), dy = -radius..radius outer, dx = -radius..radius inner, skipping those outside the frame; q == p with
+ *   exclude_centre; those with idx[q] != idx[p] with same_object; those with a channel of in[q] that is not finite
+ *   n = the taps that count, nf = (float)n
+ *   n == 0:  lo_c = -inf, hi_c = +inf for the three channels
+ *   else, per channel c, two sweeps over the counted taps in that order:
+ *     s = s + in[q]_c;              mu = s / nf
+ *     d = in[q]_c - mu;  qq = qq + d*d
+ *     sd = sqrtf(qq / nf);  e = k * sd;  lo_c = mu - e;  hi_c = mu + e
+ *   (two sweeps on purpose: beside values of 0.1 a firefly of 1e4 cancels away in s2/n - mu*mu)
+ *   out_clamped[p]_c, x = in[p]_c:  x finite:  x < lo_c ? lo_c : (x > hi_c ? hi_c : x);   else x as it is
+ * A NaN bound (a sum that overflowed, k = 0 beside an infinite sd) therefore clamps nothing and is no error.
+ * RTW_E_INVALID, nothing written: in, params, out_lo or out_hi NULL; w or h zero or beyond RTW_ATROUS_MAX_SIDE, or w * h beyond 32 bits;
+ * radius outside 1 .. RTW_BOUNDS_MAX_RADIUS; k negative or not finite; same_object > 1 or exclude_centre > 1; same_object with idx NULL;
+ * two of the three outputs the same buffer; an output that is `in` (neighbours gather from it).
+ * What stays out: boxes in YCoCg or of the luminance alone, bounds of a prefiltered frame, one launch fused with the accumulation.  There is
+ * no rtw_mgpu_* form and no JSON form. */
+#define RTW_BOUNDS_MAX_RADIUS 3u
+typedef struct RtwColourBounds {
+    uint32_t radius;          /* 1 .. RTW_BOUNDS_MAX_RADIUS: the window is (2 radius + 1)^2 pixels          */
+    float    k;               /* >= 0, finite: the half-width of the box in standard deviations            */
+    uint32_t same_object;     /* 1 = a tap on another idx is skipped                                       */
+    uint32_t exclude_centre;  /* 1 = the pixel itself is not a tap (the firefly form)                      */
+} RtwColourBounds;
+/* The host form (one thread).  RtwFilterStats as rtw_variance_estimate: taps counts the window entries inside the frame. */
+int rtw_colour_bounds(const float *in, uint32_t w, uint32_t h, const int32_t *idx /* may be NULL */, const RtwColourBounds *params,
+                      float *out_lo, float *out_hi, float *out_clamped /* may be NULL */, RtwFilterStats *stats);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host form.  Every buffer may independently be host memory (staged through a
+ * scratch the context keeps) or device memory of ctx's GPU (used in place).  One launch, one thread per pixel, the window read from an
+ * LDS tile or from global memory (RTW_OPT_ATROUS_LAYOUT); filter_ms is its device time.  Needs no scene. */
+int rtw_ctx_colour_bounds(rtw_ctx *ctx, const float *in, uint32_t w, uint32_t h, const int32_t *idx /* may be NULL */,
+                          const RtwColourBounds *params, float *out_lo, float *out_hi, float *out_clamped /* may be NULL */,
+                          RtwFilterStats *stats);
+
+/* ---- bounded temporal accumulation: the history's colour clipped to a box before it is blended -- added within v4 -------------------------
+ * The geometric tests accept a history however stale its lighting is.  rtw_temporal_accumulate_bounded is rtw_temporal_accumulate_points
+ * plus hist_lo and hist_hi, both [h][w][3] f32, both or neither NULL, and out_clipped [h][w] f32 (may be NULL).  For a pixel p with a
+ * history (the counted taps' weight > 0), directly after h = (the taps' colour) / (their weight) and before it is blended or kept:
+ *     h'_c = h_c < lo_c ? lo_c : (h_c > hi_c ? hi_c : h_c),   lo = hist_lo[p], hi = hist_hi[p]      (a NaN bound clips nothing)
+ *     out_clipped[p] = (|h_0 - h'_0| + |h_1 - h'_1|) + |h_2 - h'_2|
+ * and h' takes the place of h.  The moments and the length are the unbounded call's: a pixel whose lighting changed keeps a large variance,
+ * which the variance-steered filter then filters harder.  A pixel without a history reads no bound and writes out_clipped[p] = 0, as every
+ * pixel of a first frame does.  The bounds may come from anywhere: rtw_colour_bounds of the new frame, a prefiltered frame, an analytic box.
+ * RTW_E_INVALID besides the refusals of the _points call: exactly one of hist_lo and hist_hi; hist_lo, hist_hi or out_clipped equal to
+ * out_color, out_moments, out_len, out_variance or out_prev_xy; out_clipped equal to hist_lo or hist_hi.  With all three NULL the calls
+ * are the _points calls, launch for launch.
+ * What stays out: a response of the history length or of the moments to clipping.  There is no rtw_mgpu_* form and no JSON form. */
+/* The host form (one thread) and, on ctx's GPU and stream, its bytes: a fourth instantiation of the kernel, chosen on the host. */
+int rtw_temporal_accumulate_bounded(const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth, const float *normal,
+                                    const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color, const float *prev_moments,
+                                    const float *prev_len, const float *prev_depth, const float *prev_normal, const int32_t *prev_idx,
+                                    const RtwTemporal *params, const RtwMotionRow *rows /* may be NULL */, uint32_t n_rows, uint32_t first,
+                                    const float *prev_point /* may be NULL */, const float *carried_normal /* may be NULL */,
+                                    const float *hist_lo /* may be NULL */, const float *hist_hi /* may be NULL */,
+                                    float *out_color, float *out_moments, float *out_len, float *out_variance /* may be NULL */,
+                                    float *out_prev_xy /* may be NULL */, float *out_clipped /* may be NULL */, RtwFilterStats *stats);
+int rtw_ctx_temporal_accumulate_bounded(rtw_ctx *ctx, const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth,
+                                        const float *normal, const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color,
+                                        const float *prev_moments, const float *prev_len, const float *prev_depth,
+                                        const float *prev_normal, const int32_t *prev_idx, const RtwTemporal *params,
+                                        const RtwMotionRow *rows /* may be NULL */, uint32_t n_rows, uint32_t first,
+                                        const float *prev_point /* may be NULL */, const float *carried_normal /* may be NULL */,
+                                        const float *hist_lo /* may be NULL */, const float *hist_hi /* may be NULL */,
+                                        float *out_color, float *out_moments, float *out_len, float *out_variance /* may be NULL */,
+                                        float *out_prev_xy /* may be NULL */, float *out_clipped /* may be NULL */, RtwFilterStats *stats);
+
 /* ---- Rust2 triangles (Rust2/src/objects/triangle.rs) ----------------------------------------------------------------------------
  * `Triangle{origin, u, v, mat, texture}` with the derived fields of Triangle::new (:28-50): n = u x v, normal = unit(n),
  * d = normal . origin, w = n / (n . n); the hit test of get_hit (:95-124) restated operation by operation in f32: reject when

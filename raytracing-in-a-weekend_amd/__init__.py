@@ -21,6 +21,7 @@ Reference surface mirrored (names and argument meaning):
   (extension) atrous_filter(frame, depth=, normal=, ids=, albedo=, emitted=, ..)   an edge-avoiding a-trous wavelet filter of linear f32 frames (Renderer.atrous_filter)
   (extension) temporal_accumulate(cur, cam, depth=, normal=, ids=, history=, ..)   frames of a sequence blended along reprojected pixels (Renderer.temporal_accumulate, TemporalDenoiser)
   (extension) temporal_accumulate(.., motion=, motion_first=, out_prev_xy=)        ... with objects that moved rigidly since the previous frame (mesh_instance_motion, motion_rows)
+  (extension) colour_bounds(frame, ids=, radius=, k=, ..)   mean +- k sigma of the frame around each pixel: the firefly clamp, and the box of temporal_accumulate(.., hist_lo=, hist_hi=) (Renderer.colour_bounds)
   (extension) variance_estimate(moments, length, depth=, normal=, ids=, ..)   a luminance variance for every pixel of an accumulated frame (Renderer.variance_estimate)
   (extension) svgf_filter(frame, variance, depth=, normal=, ids=, albedo=, emitted=, ..)   the a-trous filter steered by that variance (Renderer.svgf_filter, SvgfDenoiser)
   Triangle.new (+ from_mesh), Scene(triangles=)       Rust2/src/objects/triangle.rs:28-124 (triangle_hits; Renderer.triangle_hits)
@@ -83,6 +84,11 @@ VARIANCE_MAX_RADIUS = 3
 SVGF_DEFAULTS = {"levels": 3, "sigma_luminance": 1.0, "epsilon": 1e-8, "prefilter": False, "min_history": 4, "radius": 3, "sigma_color": 0.0,
                  "sigma_depth": ATROUS_DEFAULTS["sigma_depth"], "sigma_normal": ATROUS_DEFAULTS["sigma_normal"],
                  "albedo_floor": ATROUS_DEFAULTS["albedo_floor"]}
+BOUNDS_MAX_RADIUS = 3
+# Renderer.colour_bounds' defaults, and what to give firefly= / history_clamp= of the denoisers' steps: the row of the sweep with the least
+# mean ratio, with both on, over the late frames of the five recorded sequences (0.359 against 0.400 as recorded; it helps four of them and
+# costs on the light scene: DESIGN.md 8h, profiles/history_clamp.log).  The denoisers' own default stays None.
+BOUNDS_DEFAULTS = {"radius": 1, "k": 1.0}
 
 # materials.rs:157-212 presets as (metallicness, opacity, ir)
 METALLIC_M = (1.0, 0.0, 1.0)
@@ -226,6 +232,12 @@ class RtwVarianceEstimate(C.Structure):
 class RtwSvgf(C.Structure):
     """What the variance-steered a-trous filter takes beside RtwAtrous: sigma_luminance (0 = term off), epsilon and prefilter (include/rtw.h)."""
     _fields_ = [("sigma_luminance", C.c_float), ("epsilon", C.c_float), ("prefilter", C.c_uint32)]
+
+
+class RtwColourBounds(C.Structure):
+    """Arguments of the neighbourhood colour bounds: the window's radius, the box's half-width k in standard deviations, same_object and
+    exclude_centre (include/rtw.h)."""
+    _fields_ = [("radius", C.c_uint32), ("k", C.c_float), ("same_object", C.c_uint32), ("exclude_centre", C.c_uint32)]
 
 
 class RtwFilterStats(C.Structure):
@@ -463,6 +475,11 @@ def lib() -> C.CDLL:
     L.rtw_temporal_accumulate_points.argtypes = (L.rtw_temporal_accumulate_motion.argtypes[:18] + [C.c_void_p] * 2 +
                                                  L.rtw_temporal_accumulate_motion.argtypes[18:])
     L.rtw_ctx_temporal_accumulate_points.argtypes = [C.c_void_p] + L.rtw_temporal_accumulate_points.argtypes
+    L.rtw_temporal_accumulate_bounded.argtypes = (L.rtw_temporal_accumulate_points.argtypes[:20] + [C.c_void_p] * 2 +
+                                                  L.rtw_temporal_accumulate_points.argtypes[20:25] + [C.c_void_p, C.POINTER(RtwFilterStats)])
+    L.rtw_ctx_temporal_accumulate_bounded.argtypes = [C.c_void_p] + L.rtw_temporal_accumulate_bounded.argtypes
+    L.rtw_colour_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtwColourBounds)] + [C.c_void_p] * 3 + [C.POINTER(RtwFilterStats)]
+    L.rtw_ctx_colour_bounds.argtypes = [C.c_void_p] + L.rtw_colour_bounds.argtypes
     L.rtw_ctx_scene_surface_tri.argtypes = L.rtw_ctx_scene_surface.argtypes[:-1] + [C.c_void_p] * 2 + [C.POINTER(RtwStats)]
     L.rtw_ctx_surface_map_tri.argtypes = L.rtw_ctx_surface_map.argtypes[:-1] + [C.c_void_p] * 2 + [C.POINTER(RtwStats)]
     L.rtw_tri_bary.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -2137,7 +2154,8 @@ class Renderer:
         return out, st
 
     def temporal_accumulate(self, cur, cam: RtwCamera, depth, normal=None, ids=None, history=None, out_color=None, motion=None,
-                            motion_first: int = 0, out_prev_xy=None, prev_point=None, carried_normal=None, **params):
+                            motion_first: int = 0, out_prev_xy=None, prev_point=None, carried_normal=None, hist_lo=None, hist_hi=None,
+                            out_clipped=None, **params):
         """Temporal accumulation of a linear float32 frame [h][w][3] on this context's GPU (rtw_ctx_temporal_accumulate, include/rtw.h): the
         previous call's accumulated colour, luminance moments and history length are fetched where each pixel's surface point lay in the
         previous view, each of the four taps accepted or rejected against the guides, and blended with `cur`.  depth [h][w] float32, normal
@@ -2158,10 +2176,27 @@ class Renderer:
         Per-pixel motion (rtw_ctx_temporal_accumulate_points): prev_point [h][w][3] float32 -- deform_motion's, or your own -- gives the
         world point each pixel's surface point was a frame ago; a pixel whose prev_point x is not NaN projects that point and takes the four
         taps, whatever its row says, and its normal test reads carried_normal [h][w][3] (None: normal itself).  With both at None the call
-        is the one above."""
+        is the one above.
+        Bounds on the history (rtw_ctx_temporal_accumulate_bounded): hist_lo and hist_hi [h][w][3] float32, both or neither -- colour_bounds'
+        of `cur`, or your own -- clip the reprojected colour of every pixel with a history before it is blended; the moments and the length
+        are untouched.  out_clipped: True, or an array / tensor [h][w], receives how far the box moved each pixel's history (summed over the
+        channels; 0 without a history) and is returned as history["clipped"].  With all three at None the call is the one above."""
         return _temporal_call(lib().rtw_ctx_temporal_accumulate, "rtw_ctx_temporal_accumulate", (self._h,), self._on_device, cur, cam, depth,
                               normal, ids, history, out_color, params, motion, motion_first, out_prev_xy, lib().rtw_ctx_temporal_accumulate_motion,
-                              prev_point, carried_normal, lib().rtw_ctx_temporal_accumulate_points)
+                              prev_point, carried_normal, lib().rtw_ctx_temporal_accumulate_points, hist_lo, hist_hi, out_clipped,
+                              lib().rtw_ctx_temporal_accumulate_bounded)
+
+    def colour_bounds(self, frame, ids=None, radius: int = BOUNDS_DEFAULTS["radius"], k: float = BOUNDS_DEFAULTS["k"], same_object: bool = False,
+                      exclude_centre: bool = False, out_lo=None, out_hi=None, out_clamped=None):
+        """mean - k sigma and mean + k sigma, per channel, of a linear float32 frame [h][w][3] over the (2 radius + 1)^2 window around each
+        pixel on this context's GPU (rtw_ctx_colour_bounds, include/rtw.h): the box temporal_accumulate(hist_lo=, hist_hi=) clips a
+        reprojected colour to, and with exclude_centre (the pixel itself is no tap) and out_clamped the firefly clamp of the frame.  A tap
+        outside the frame, one with a channel that is not finite, and with same_object one on another ids [h][w] int32, does not count; a
+        pixel without taps gets (-inf, +inf).  Every argument is a numpy array (staged) or a contiguous torch tensor on the context's device,
+        read and written in place on the context's stream.  out_lo, out_hi: None -> new arrays or tensors like `frame`.  out_clamped: None
+        or False -> not wanted, True -> new, else an array or tensor [h][w][3] of its own.  Returns (lo, hi, clamped or None, RtwFilterStats)."""
+        return _bounds_call(lib().rtw_ctx_colour_bounds, "rtw_ctx_colour_bounds", (self._h,), self._on_device, frame, ids, radius, k, same_object,
+                            exclude_centre, out_lo, out_hi, out_clamped)
 
     def variance_estimate(self, moments, length, depth=None, normal=None, ids=None, min_history: int = SVGF_DEFAULTS["min_history"],
                           radius: int = SVGF_DEFAULTS["radius"], sigma_depth: float = SVGF_DEFAULTS["sigma_depth"],
@@ -2469,9 +2504,11 @@ def _motion_pointer(motion, on_device, keep, who):
 
 
 def _temporal_call(fn, fn_name, head, on_device, cur, cam, depth, normal, ids, history, out_color, params, motion=None, motion_first=0,
-                   out_prev_xy=None, fn_motion=None, prev_point=None, carried_normal=None, fn_points=None):
+                   out_prev_xy=None, fn_motion=None, prev_point=None, carried_normal=None, fn_points=None, hist_lo=None, hist_hi=None,
+                   out_clipped=None, fn_bounded=None):
     """rtw_temporal_accumulate / rtw_ctx_temporal_accumulate from the Python arguments of temporal_accumulate: (history, variance, stats).
-    With motion or out_prev_xy: fn_motion, the call with moving objects.  With prev_point or carried_normal: fn_points."""
+    With motion or out_prev_xy: fn_motion, the call with moving objects.  With prev_point or carried_normal: fn_points.  With hist_lo,
+    hist_hi or out_clipped: fn_bounded."""
     who = "temporal_accumulate"
     unknown = set(params) - set(TEMPORAL_DEFAULTS) - {"offset"}
     if unknown:
@@ -2506,7 +2543,8 @@ def _temporal_call(fn, fn_name, head, on_device, cur, cam, depth, normal, ids, h
             C.byref(prm), ptr("out_color", out["color"], np.float32, (h, w, 3), True), ptr("moments", out["moments"], np.float32, (h, w, 2), True),
             ptr("len", out["len"], np.float32, (h, w), True), ptr("variance", variance, np.float32, (h, w), True)]
     st = RtwFilterStats()
-    points = prev_point is not None or carried_normal is not None
+    bounded = hist_lo is not None or hist_hi is not None or (out_clipped is not None and out_clipped is not False)
+    points = prev_point is not None or carried_normal is not None or bounded
     if motion is None and out_prev_xy is None and not motion_first and not points:
         _check(fn(*head, *args, C.byref(st)), fn_name)
         return out, variance, st
@@ -2519,18 +2557,58 @@ def _temporal_call(fn, fn_name, head, on_device, cur, cam, depth, normal, ids, h
         _check(fn_motion(*head, *args, C.byref(st)), fn_name + "_motion")
         return out, variance, st
     args[18:18] = [ptr("prev_point", prev_point, np.float32, (h, w, 3)), ptr("carried_normal", carried_normal, np.float32, (h, w, 3))]
-    _check(fn_points(*head, *args, C.byref(st)), fn_name + "_points")
+    if not bounded:
+        _check(fn_points(*head, *args, C.byref(st)), fn_name + "_points")
+        return out, variance, st
+    if out_clipped is not None and out_clipped is not False:
+        out["clipped"] = new(h, w) if out_clipped is True else out_clipped
+    args[20:20] = [ptr("hist_lo", hist_lo, np.float32, (h, w, 3)), ptr("hist_hi", hist_hi, np.float32, (h, w, 3))]
+    args.append(ptr("out_clipped", out.get("clipped"), np.float32, (h, w), True))
+    _check(fn_bounded(*head, *args, C.byref(st)), fn_name + "_bounded")
     return out, variance, st
 
 
 def temporal_accumulate(cur, cam: RtwCamera, depth, normal=None, ids=None, history=None, out_color=None, motion=None, motion_first: int = 0,
-                        out_prev_xy=None, prev_point=None, carried_normal=None, **params):
+                        out_prev_xy=None, prev_point=None, carried_normal=None, hist_lo=None, hist_hi=None, out_clipped=None, **params):
     """The temporal accumulation on the host (rtw_temporal_accumulate, with motion or out_prev_xy rtw_temporal_accumulate_motion, with
-    prev_point or carried_normal rtw_temporal_accumulate_points), the bytes of Renderer.temporal_accumulate; numpy arrays only.  Arguments
-    and result as there."""
+    prev_point or carried_normal rtw_temporal_accumulate_points, with hist_lo, hist_hi or out_clipped rtw_temporal_accumulate_bounded), the
+    bytes of Renderer.temporal_accumulate; numpy arrays only.  Arguments and result as there."""
     return _temporal_call(lib().rtw_temporal_accumulate, "rtw_temporal_accumulate", (), None, cur, cam, depth, normal, ids, history, out_color, params,
                           motion, motion_first, out_prev_xy, lib().rtw_temporal_accumulate_motion, prev_point, carried_normal,
-                          lib().rtw_temporal_accumulate_points)
+                          lib().rtw_temporal_accumulate_points, hist_lo, hist_hi, out_clipped, lib().rtw_temporal_accumulate_bounded)
+
+
+def _bounds_call(fn, fn_name, head, on_device, frame, ids, radius, k, same_object, exclude_centre, out_lo, out_hi, out_clamped):
+    """rtw_colour_bounds / rtw_ctx_colour_bounds from the Python arguments of colour_bounds: (lo, hi, clamped or None, stats)."""
+    who = "colour_bounds"
+    shp = tuple(frame.shape) if hasattr(frame, "shape") else np.shape(frame)
+    if len(shp) != 3 or shp[2] != 3:
+        raise ValueError(f"{who}: frame of shape {shp}, expected [h][w][3]")
+    h, w = int(shp[0]), int(shp[1])
+    keep = []
+    ptr = lambda name, a, dtype, shape, writable=False: _atrous_pointer(name, a, dtype, shape, on_device, keep, writable, who)
+    if hasattr(frame, "data_ptr"):
+        import torch
+        new = lambda: torch.empty((h, w, 3), dtype=torch.float32, device=frame.device)
+    else:
+        new = lambda: np.empty((h, w, 3), np.float32)
+    out_lo = new() if out_lo is None else out_lo
+    out_hi = new() if out_hi is None else out_hi
+    out_clamped = None if out_clamped is None or out_clamped is False else (new() if out_clamped is True else out_clamped)
+    prm = RtwColourBounds(int(radius), float(k), int(bool(same_object)), int(bool(exclude_centre)))
+    st = RtwFilterStats()
+    _check(fn(*head, ptr("frame", frame, np.float32, (h, w, 3)), w, h, ptr("ids", ids, np.int32, (h, w)), C.byref(prm),
+              ptr("out_lo", out_lo, np.float32, (h, w, 3), True), ptr("out_hi", out_hi, np.float32, (h, w, 3), True),
+              ptr("out_clamped", out_clamped, np.float32, (h, w, 3), True), C.byref(st)), fn_name)
+    return out_lo, out_hi, out_clamped, st
+
+
+def colour_bounds(frame, ids=None, radius: int = BOUNDS_DEFAULTS["radius"], k: float = BOUNDS_DEFAULTS["k"], same_object: bool = False,
+                  exclude_centre: bool = False, out_lo=None, out_hi=None, out_clamped=None):
+    """The neighbourhood colour bounds on the host (rtw_colour_bounds), the bytes of Renderer.colour_bounds; numpy arrays only.  Arguments
+    and result as there."""
+    return _bounds_call(lib().rtw_colour_bounds, "rtw_colour_bounds", (), None, frame, ids, radius, k, same_object, exclude_centre, out_lo, out_hi,
+                        out_clamped)
 
 
 class TemporalDenoiser:
@@ -2562,7 +2640,23 @@ class TemporalDenoiser:
                                         r.mesh_instance_first() if prev_poses is not None else 0)
         return g, dict(prev_point=point, carried_normal=normal)
 
-    def step(self, cam: RtwCamera, params: RtwParams, motion=None, motion_first: int = 0, prev_ouv=None, prev_poses=None, **atrous):
+    def _bounded(self, cur, g, firefly, history_clamp):
+        """(the frame that enters the accumulation, temporal_accumulate's hist_lo / hist_hi / out_clipped arguments, the RtwFilterStats of
+        the bounds calls made): with firefly the frame is out_clamped of colour_bounds(exclude_centre=True); with history_clamp a second
+        colour_bounds of that frame gives the box of the history.  Both None: (cur, {}, {}), no call."""
+        r = self.renderer
+        kw, stats = {}, {}
+        if firefly is not None:
+            _, _, cur, stats["firefly"] = r.colour_bounds(cur, radius=firefly["radius"], k=firefly["k"], exclude_centre=True, out_clamped=True)
+        if history_clamp is not None:
+            same = bool(history_clamp.get("same_object", False))
+            lo, hi, _, stats["history_clamp"] = r.colour_bounds(cur, ids=g["idx"] if same else None, radius=history_clamp["radius"],
+                                                                k=history_clamp["k"], same_object=same)
+            kw = dict(hist_lo=lo, hist_hi=hi, out_clipped=True)
+        return cur, kw, stats
+
+    def step(self, cam: RtwCamera, params: RtwParams, motion=None, motion_first: int = 0, prev_ouv=None, prev_poses=None, firefly=None,
+             history_clamp=None, **atrous):
         """One frame (motion, motion_first: temporal_accumulate's, the motion of the scene's objects since the previous step; prev_ouv: the
         rows the mesh had at the previous step when refit_triangles or move_mesh_instances(ouv=) deformed it since, with prev_poses, the
         previous poses, when the mesh is placed -- the step then asks surface_map for tri and bary and deform_motion for the pixels'
@@ -2571,7 +2665,11 @@ class TemporalDenoiser:
         with albedo and emission, and params.gamma applied as render_denoised does.  Returns (frame, accumulated, variance, stats): frame
         the filtered [h][w][3] float32 image, accumulated the linear accumulated colour (the history's), variance [h][w], stats a dict of
         render (RtwStats), temporal and atrous (RtwFilterStats), coverage ((len > 1).mean()), and cur and guides, the rendered frame and
-        surface_map's dict this step accumulated."""
+        surface_map's dict this step accumulated.
+        firefly: None, or dict(radius, k) -- the frame that enters everything behind the render is colour_bounds' out_clamped with
+        exclude_centre (stats["cur"] is then the clamped frame).  history_clamp: None, or dict(radius, k, same_object) -- colour_bounds of
+        that frame bounds the reprojected history (temporal_accumulate's hist_lo / hist_hi); history["clipped"] says by how much.  stats
+        gains firefly / history_clamp, the RtwFilterStats of those calls.  With both None the step makes the calls it made without them."""
         if params.part_count != 1:
             raise ValueError("TemporalDenoiser: whole frames only (part_count 1)")
         r = self.renderer
@@ -2583,13 +2681,15 @@ class TemporalDenoiser:
         finally:
             params.gamma = gamma
         g, points = self._guides(cam, params, prev_ouv, prev_poses)
+        cur, bounds, st_b = self._bounded(cur, g, firefly, history_clamp)
         self.history, variance, st_t = r.temporal_accumulate(cur, cam, depth=g["depth"], normal=g["normal"], ids=g["idx"], history=self.history,
-                                                             motion=motion, motion_first=motion_first, offset=(0.5, 0.5), **points, **self.params)
+                                                             motion=motion, motion_first=motion_first, offset=(0.5, 0.5), **points, **bounds,
+                                                             **self.params)
         acc = self.history["color"]
         frame, st_a = r.atrous_filter(acc, depth=g["depth"], normal=g["normal"], ids=g["idx"], albedo=g["albedo"], emitted=g["emitted"], **atrous)
         if gamma != 1.0:
             frame = np.power(np.maximum(frame, np.float32(0.0)), np.float32(1.0 / gamma)).astype(np.float32)
-        stats = dict(render=st, temporal=st_t, atrous=st_a, coverage=float((self.history["len"] > 1).mean()), cur=cur, guides=g)
+        stats = dict(render=st, temporal=st_t, atrous=st_a, coverage=float((self.history["len"] > 1).mean()), cur=cur, guides=g, **st_b)
         return frame, acc, variance, stats
 
 
@@ -2667,12 +2767,13 @@ class SvgfDenoiser(TemporalDenoiser):
     Renderer.svgf_filter) where TemporalDenoiser has the fixed a-trous filter.  `params` as there."""
 
     def step(self, cam: RtwCamera, params: RtwParams, min_history: int = SVGF_DEFAULTS["min_history"], radius: int = SVGF_DEFAULTS["radius"],
-             motion=None, motion_first: int = 0, prev_ouv=None, prev_poses=None, **svgf):
+             motion=None, motion_first: int = 0, prev_ouv=None, prev_poses=None, firefly=None, history_clamp=None, **svgf):
         """One frame (motion, motion_first, prev_ouv, prev_poses as TemporalDenoiser.step's): rendered, its guides taken and accumulated as TemporalDenoiser.step does; variance_estimate (min_history, radius; the
         guide sigmas and same_object those of **svgf) on the new history's moments and length; svgf_filter (keyword arguments: its own) on
         the accumulated colour with albedo and emission; params.gamma applied.  Returns (frame, accumulated, variance, stats): variance is
         the estimate the filter was steered by; stats holds render, temporal, variance and svgf (RtwStats and three RtwFilterStats),
-        coverage, cur, guides, and filtered_variance, the variance the filter's levels left."""
+        coverage, cur, guides, and filtered_variance, the variance the filter's levels left.  firefly, history_clamp: as
+        TemporalDenoiser.step's."""
         if params.part_count != 1:
             raise ValueError("SvgfDenoiser: whole frames only (part_count 1)")
         r = self.renderer
@@ -2684,8 +2785,10 @@ class SvgfDenoiser(TemporalDenoiser):
         finally:
             params.gamma = gamma
         g, points = self._guides(cam, params, prev_ouv, prev_poses)
+        cur, bounds, st_b = self._bounded(cur, g, firefly, history_clamp)
         self.history, _, st_t = r.temporal_accumulate(cur, cam, depth=g["depth"], normal=g["normal"], ids=g["idx"], history=self.history,
-                                                      motion=motion, motion_first=motion_first, offset=(0.5, 0.5), **points, **self.params)
+                                                      motion=motion, motion_first=motion_first, offset=(0.5, 0.5), **points, **bounds,
+                                                      **self.params)
         acc = self.history["color"]
         guide_kw = {k: svgf[k] for k in ("sigma_depth", "sigma_normal", "same_object") if k in svgf}
         variance, st_v = r.variance_estimate(self.history["moments"], self.history["len"], depth=g["depth"], normal=g["normal"], ids=g["idx"],
@@ -2695,7 +2798,7 @@ class SvgfDenoiser(TemporalDenoiser):
         if gamma != 1.0:
             frame = np.power(np.maximum(frame, np.float32(0.0)), np.float32(1.0 / gamma)).astype(np.float32)
         stats = dict(render=st, temporal=st_t, variance=st_v, svgf=st_s, coverage=float((self.history["len"] > 1).mean()), cur=cur, guides=g,
-                     filtered_variance=fvar)
+                     filtered_variance=fvar, **st_b)
         return frame, acc, variance, stats
 
 

@@ -10,6 +10,7 @@
 #include "rtw_temporal_dev.h"
 #include "rtw_temporal.h"
 #include "rtw_svgf_dev.h"
+#include "rtw_bounds_dev.h"
 #include "rtw_devmem.h"
 #include "rtw_exp.h"
 #include "rtw_probe.h"
@@ -104,6 +105,7 @@ struct rtw_ctx {
     NoiseMem noise_mem;
     AtrousScratch *atrous = nullptr;     // buffers of rtw_ctx_atrous_filter (rtw_atrous.hip), rtw_ctx_svgf_filter and rtw_ctx_variance_estimate
                                          // (rtw_svgf.hip), created on the first call of any of them
+    BoundsScratch *bounds = nullptr;     // buffers of rtw_ctx_colour_bounds (rtw_bounds.hip), created on its first call
     TemporalScratch *temporal = nullptr; // buffers of rtw_ctx_temporal_accumulate (rtw_temporal.hip), created on its first call
     FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
     MotionMem motion_mem;                // buffers of rtw_ctx_mesh_instance_motion
@@ -532,6 +534,7 @@ void rtw_ctx_destroy(rtw_ctx *c) {
     filter_scratch_free(c->filter);
     atrous_scratch_free(c->atrous);
     temporal_scratch_free(c->temporal);
+    bounds_scratch_free(c->bounds);
     if (c->ev_mark) (void)hipEventDestroy(c->ev_mark);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1471,7 +1474,7 @@ int rtw_ctx_temporal_accumulate(rtw_ctx *c, const float *cur, uint32_t w, uint32
     if (c->pend.active) return RTW_E_INVALID;
     const TemporalBuffers b = { cur, depth, normal, idx, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
                                 out_color, out_moments, out_len, out_variance };
-    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, nullptr, nullptr, stats, &g_last_hip);
+    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, nullptr, nullptr, nullptr, stats, &g_last_hip);
 }
 
 // ... and with moving objects (rtw.h "temporal accumulation with moving objects"): without rows and prev_xy the same launch
@@ -1485,7 +1488,7 @@ int rtw_ctx_temporal_accumulate_motion(rtw_ctx *c, const float *cur, uint32_t w,
     const TemporalBuffers b = { cur, depth, normal, idx, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
                                 out_color, out_moments, out_len, out_variance };
     const TemporalMotion m = { rows, n_rows, first, out_prev_xy };
-    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, &m, nullptr, stats, &g_last_hip);
+    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, &m, nullptr, nullptr, stats, &g_last_hip);
 }
 
 // ... and with per-pixel previous points (rtw.h "temporal accumulation with per-pixel motion"): without them the same launches
@@ -1501,7 +1504,25 @@ int rtw_ctx_temporal_accumulate_points(rtw_ctx *c, const float *cur, uint32_t w,
                                 out_color, out_moments, out_len, out_variance };
     const TemporalMotion m = { rows, n_rows, first, out_prev_xy };
     const TemporalPoints pt = { prev_point, carried_normal };
-    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, &m, &pt, stats, &g_last_hip);
+    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, &m, &pt, nullptr, stats, &g_last_hip);
+}
+
+// ... and with bounds on the history's colour (rtw.h "bounded temporal accumulation"): without them the same launches
+int rtw_ctx_temporal_accumulate_bounded(rtw_ctx *c, const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth,
+                                        const float *normal, const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color,
+                                        const float *prev_moments, const float *prev_len, const float *prev_depth, const float *prev_normal,
+                                        const int32_t *prev_idx, const RtwTemporal *p, const RtwMotionRow *rows, uint32_t n_rows, uint32_t first,
+                                        const float *prev_point, const float *carried_normal, const float *hist_lo, const float *hist_hi,
+                                        float *out_color, float *out_moments, float *out_len, float *out_variance, float *out_prev_xy,
+                                        float *out_clipped, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    const TemporalBuffers b = { cur, depth, normal, idx, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
+                                out_color, out_moments, out_len, out_variance };
+    const TemporalMotion m = { rows, n_rows, first, out_prev_xy };
+    const TemporalPoints pt = { prev_point, carried_normal };
+    const TemporalBounds bd = { hist_lo, hist_hi, out_clipped };
+    return temporal_accumulate_device(c->device, c->stream, &c->temporal, w, h, cam, prev_cam, b, p, &m, &pt, &bd, stats, &g_last_hip);
 }
 
 // The motion rows of moved placements (rtw_mesh_move.hip) on this context's GPU and stream; the scene is not involved.
@@ -1596,6 +1617,15 @@ int rtw_ctx_svgf_filter(rtw_ctx *c, const float *in, const float *variance, uint
     if (c->pend.active) return RTW_E_INVALID;
     return svgf_filter_device(c->device, c->stream, &c->atrous, c->opt_atrous_layout, in, variance, w, h, depth, normal, idx, albedo, emitted, p, vp,
                               out, out_variance, stats, &g_last_hip);
+}
+
+// The neighbourhood colour bounds (rtw_bounds.hip) likewise, on a scratch of their own.
+int rtw_ctx_colour_bounds(rtw_ctx *c, const float *in, uint32_t w, uint32_t h, const int32_t *idx, const RtwColourBounds *p, float *out_lo,
+                          float *out_hi, float *out_clamped, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return colour_bounds_device(c->device, c->stream, &c->bounds, c->opt_atrous_layout, in, w, h, idx, p, out_lo, out_hi, out_clamped, stats,
+                                &g_last_hip);
 }
 
 // The device-math probe (rtw_probe.hip, rtw.h "device math, for tests") on this context's GPU and stream; the scene is not involved.

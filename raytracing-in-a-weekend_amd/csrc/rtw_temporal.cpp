@@ -80,6 +80,16 @@ int temporal_check_points(const float *prev_point, const float *carried_normal, 
     return RTW_OK;
 }
 
+int temporal_check_bounds(const float *hist_lo, const float *hist_hi, const float *out_clipped, const float *out_color, const float *out_moments,
+                          const float *out_len, const float *out_variance, const float *out_prev_xy) {
+    if ((hist_lo != nullptr) != (hist_hi != nullptr)) return RTW_E_INVALID;              // both or neither
+    for (const float *b : { hist_lo, hist_hi, out_clipped })
+        for (const float *out : { out_color, out_moments, out_len, out_variance, out_prev_xy })
+            if (b && b == out) return RTW_E_INVALID;
+    if (out_clipped && (out_clipped == hist_lo || out_clipped == hist_hi)) return RTW_E_INVALID;
+    return RTW_OK;
+}
+
 } // namespace rtw
 
 using namespace rtw;
@@ -159,6 +169,40 @@ extern "C" int rtw_temporal_accumulate_points(const float *cur, uint32_t w, uint
     const TemporalPoints pt = { prev_point, carried_normal };
     for (uint32_t j = 0; j < h; j++)
         for (uint32_t i = 0; i < w; i++) temporal_pixel_t<true, true>(pl, f, hs, o, mo, pt, i, j);
+    if (stats) {
+        const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        *stats = RtwFilterStats{ 0.0f, 0.0f, 0.0f, 0.0f, ms, ms, 4ull * w * h };
+    }
+    return RTW_OK;
+}
+
+extern "C" int rtw_temporal_accumulate_bounded(const float *cur, uint32_t w, uint32_t h, const RtwCamera *cam, const float *depth, const float *normal,
+                                               const int32_t *idx, const RtwCamera *prev_cam, const float *prev_color, const float *prev_moments,
+                                               const float *prev_len, const float *prev_depth, const float *prev_normal, const int32_t *prev_idx,
+                                               const RtwTemporal *params, const RtwMotionRow *rows, uint32_t n_rows, uint32_t first,
+                                               const float *prev_point, const float *carried_normal, const float *hist_lo, const float *hist_hi,
+                                               float *out_color, float *out_moments, float *out_len, float *out_variance, float *out_prev_xy,
+                                               float *out_clipped, RtwFilterStats *stats) {
+    if (!hist_lo && !hist_hi && !out_clipped)
+        return rtw_temporal_accumulate_points(cur, w, h, cam, depth, normal, idx, prev_cam, prev_color, prev_moments, prev_len, prev_depth,
+                                              prev_normal, prev_idx, params, rows, n_rows, first, prev_point, carried_normal, out_color,
+                                              out_moments, out_len, out_variance, out_prev_xy, stats);
+    const auto t0 = std::chrono::steady_clock::now();
+    TemporalPlan pl;
+    int rc = temporal_check(cur, w, h, cam, depth, normal, idx, prev_cam, prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx,
+                            params, out_color, out_moments, out_len, pl);
+    if (rc == RTW_OK) rc = temporal_check_motion(idx, rows, n_rows, first, out_color, out_moments, out_len, out_variance, out_prev_xy);
+    if (rc == RTW_OK) rc = temporal_check_points(prev_point, carried_normal, out_color, out_moments, out_len, out_variance, out_prev_xy);
+    if (rc == RTW_OK) rc = temporal_check_bounds(hist_lo, hist_hi, out_clipped, out_color, out_moments, out_len, out_variance, out_prev_xy);
+    if (rc != RTW_OK) return rc;
+    const TemporalFrame f = { cur, depth, normal, idx };
+    const TemporalHistory hs = { prev_color, prev_moments, prev_len, prev_depth, prev_normal, prev_idx };
+    const TemporalOut o = { out_color, out_moments, out_len, out_variance };
+    const TemporalMotion mo = { rows, rows ? n_rows : 0u, rows ? first : 0u, out_prev_xy };
+    const TemporalPoints pt = { prev_point, carried_normal };
+    const TemporalBounds bd = { hist_lo, hist_hi, out_clipped };
+    for (uint32_t j = 0; j < h; j++)
+        for (uint32_t i = 0; i < w; i++) temporal_pixel_t<true, true, true>(pl, f, hs, o, mo, pt, i, j, bd);
     if (stats) {
         const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         *stats = RtwFilterStats{ 0.0f, 0.0f, 0.0f, 0.0f, ms, ms, 4ull * w * h };

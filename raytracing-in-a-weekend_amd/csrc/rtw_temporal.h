@@ -8,6 +8,8 @@
 // (temporal_row, temporal_project_row) and takes the four taps; every other pixel runs the code of temporal_pixel_t<false>.
 // With per-pixel motion (rtw.h "temporal accumulation with per-pixel motion") a third time, temporal_pixel_t<true, true>: a pixel
 // whose prev_point is not NaN projects that point (temporal_project_point) and takes the four taps; every other pixel runs the code above.
+// With bounds on the history (rtw.h "bounded temporal accumulation") a fourth time, temporal_pixel_t<true, true, true>: the
+// history's colour is clipped to the caller's box before it is blended; everything else is the code above.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rtw_pixel_ray.h"
@@ -38,6 +40,8 @@ struct TemporalOut { float *color, *moments, *len, *variance; };
 struct TemporalMotion { const RtwMotionRow *rows; uint32_t n_rows, first; float *prev_xy; };
 // What the calls with per-pixel motion add: each pixel's previous world point (null: none) and the normal it had there (null: normal[p])
 struct TemporalPoints { const float *point, *normal; };
+// What the bounded calls add: the box each pixel's history colour is clipped to (both null: none) and how far it was moved (may be null)
+struct TemporalBounds { const float *lo, *hi; float *clipped; };
 
 // What the counted taps add up to.
 struct TemporalSum { float w, c0, c1, c2, m1, m2, len; };
@@ -151,10 +155,12 @@ __host__ __device__ inline float temporal_blend_factor(float n_, float floor_) {
 
 // Pixel (i, j).  o.color may be f.cur: the pixel's own cur is read before anything is written.  MOTION: the calls with a table of rows or
 // prev_xy; false compiles to the rule without them (`mo` is not read), which is what rtw_temporal_accumulate and its kernel run.  POINTS
-// (only with MOTION): the calls with prev_point; false compiles to the rule without it (`pt` is not read).
-template <bool MOTION, bool POINTS = false>
+// (only with MOTION): the calls with prev_point; false compiles to the rule without it (`pt` is not read).  BOUNDS (only with POINTS): the
+// bounded calls; false compiles to the rule without them (`bd` is not read).
+template <bool MOTION, bool POINTS = false, bool BOUNDS = false>
 __host__ __device__ inline void temporal_pixel_t(const TemporalPlan &pl, const TemporalFrame &f, const TemporalHistory &hs, const TemporalOut &o,
-                                                 const TemporalMotion &mo, const TemporalPoints &pt, uint32_t i, uint32_t j) {
+                                                 const TemporalMotion &mo, const TemporalPoints &pt, uint32_t i, uint32_t j,
+                                                 const TemporalBounds &bd = TemporalBounds{ nullptr, nullptr, nullptr }) {
     const size_t p = (size_t)j * pl.w + (size_t)i;
     const float r = f.cur[3 * p], g = f.cur[3 * p + 1], b = f.cur[3 * p + 2];
     const float L = (0.2126f * r + 0.7152f * g) + 0.0722f * b;
@@ -205,9 +211,18 @@ __host__ __device__ inline void temporal_pixel_t(const TemporalPlan &pl, const T
         }
     }
 
-    float c0 = r, c1 = g, c2 = b, m1, m2, len;
+    float c0 = r, c1 = g, c2 = b, m1, m2, len, clipped = 0.0f;
     if (t.w > 0.0f) {
-        const float h0 = t.c0 / t.w, h1 = t.c1 / t.w, h2 = t.c2 / t.w, hm1 = t.m1 / t.w, hm2 = t.m2 / t.w, hlen = t.len / t.w;
+        float h0 = t.c0 / t.w, h1 = t.c1 / t.w, h2 = t.c2 / t.w;
+        const float hm1 = t.m1 / t.w, hm2 = t.m2 / t.w, hlen = t.len / t.w;
+        if (BOUNDS && bd.lo) {                                                           // (a pixel without a history does not read its box)
+            const float u0 = h0, u1 = h1, u2 = h2;
+            const float *lo = bd.lo + 3 * p, *hi = bd.hi + 3 * p;
+            h0 = h0 < lo[0] ? lo[0] : (h0 > hi[0] ? hi[0] : h0);
+            h1 = h1 < lo[1] ? lo[1] : (h1 > hi[1] ? hi[1] : h1);
+            h2 = h2 < lo[2] ? lo[2] : (h2 > hi[2] ? hi[2] : h2);
+            clipped = (__builtin_fabsf(u0 - h0) + __builtin_fabsf(u1 - h1)) + __builtin_fabsf(u2 - h2);
+        }
         if (fin) {
             const float n1 = hlen + 1.0f;
             const float n_ = n1 < pl.max_history ? n1 : pl.max_history;
@@ -229,6 +244,7 @@ __host__ __device__ inline void temporal_pixel_t(const TemporalPlan &pl, const T
     o.color[3 * p] = c0; o.color[3 * p + 1] = c1; o.color[3 * p + 2] = c2;
     o.moments[2 * p] = m1; o.moments[2 * p + 1] = m2;
     o.len[p] = len;
+    if (BOUNDS && bd.clipped) bd.clipped[p] = clipped;
     if (o.variance) {
         const float v = m2 - m1 * m1;
         o.variance[p] = v > 0.0f ? v : 0.0f;
@@ -250,5 +266,8 @@ int temporal_check_motion(const int32_t *idx, const RtwMotionRow *rows, uint32_t
 // ... and the calls with per-pixel motion (rtw.h "temporal accumulation with per-pixel motion")
 int temporal_check_points(const float *prev_point, const float *carried_normal, const float *out_color, const float *out_moments, const float *out_len,
                           const float *out_variance, const float *out_prev_xy);
+// ... and the bounded calls (rtw.h "bounded temporal accumulation")
+int temporal_check_bounds(const float *hist_lo, const float *hist_hi, const float *out_clipped, const float *out_color, const float *out_moments,
+                          const float *out_len, const float *out_variance, const float *out_prev_xy);
 
 } // namespace rtw

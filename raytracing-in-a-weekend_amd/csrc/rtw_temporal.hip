@@ -1,5 +1,6 @@
 // rtw_temporal.hip -- temporal accumulation by reprojection (rtw_temporal.h) on the GPU: the device path of
-// rtw_ctx_temporal_accumulate, rtw_ctx_temporal_accumulate_motion and rtw_ctx_temporal_accumulate_points (8g).
+// rtw_ctx_temporal_accumulate, rtw_ctx_temporal_accumulate_motion, rtw_ctx_temporal_accumulate_points (8g) and
+// rtw_ctx_temporal_accumulate_bounded (8h).
 //
 // One launch, one thread per pixel running temporal_pixel -- the host form's definition with the host form's plan, so its bytes.
 // Workgroup b covers the 32 x 8 pixels of tile (b % tiles_x, b / tiles_x): a wave is two rows of 32 pixels, so its loads of cur and of the
@@ -45,6 +46,16 @@ __global__ void __launch_bounds__(TBX * TBY) temporal_points_kernel(TemporalPlan
     if (x < pl.w && y < pl.h) temporal_pixel_t<true, true>(pl, f, hs, o, mo, pt, x, y);
 }
 
+// ... and with bounds on the history's colour (rtw_ctx_temporal_accumulate_bounded): a fourth instantiation, chosen on the host likewise.  A
+// pixel with a history loads its box (24 bytes) beside cur and writes how far the box moved its history (4 bytes); the others run the code
+// above.
+__global__ void __launch_bounds__(TBX * TBY) temporal_bounded_kernel(TemporalPlan pl, uint32_t tiles_x, TemporalFrame f, TemporalHistory hs, TemporalOut o,
+                                                                     TemporalMotion mo, TemporalPoints pt, TemporalBounds bd) {
+    const uint32_t x = (blockIdx.x % tiles_x) * TBX + threadIdx.x % TBX;
+    const uint32_t y = (blockIdx.x / tiles_x) * TBY + threadIdx.x / TBX;
+    if (x < pl.w && y < pl.h) temporal_pixel_t<true, true, true>(pl, f, hs, o, mo, pt, x, y, bd);
+}
+
 float event_ms(hipEvent_t a, hipEvent_t b) {
     float ms = 0.0f;
     return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f;
@@ -58,6 +69,7 @@ struct TemporalScratch {
     DevMem out_color, out_moments, out_len, out_variance;                // a result whose buffer is host memory
     DevMem rows, out_prev_xy;                                            // (the calls with motion)
     DevMem point, carried;                                               // (the calls with per-pixel motion)
+    DevMem hist_lo, hist_hi, out_clipped;                                // (the bounded calls)
     hipEvent_t ev[2] = { nullptr, nullptr };
 };
 
@@ -75,7 +87,7 @@ void temporal_scratch_free(TemporalScratch *s) {
 
 int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch **scratch, uint32_t w, uint32_t h, const RtwCamera *cam,
                                const RtwCamera *prev_cam, const TemporalBuffers &b, const RtwTemporal *p, const TemporalMotion *m, const TemporalPoints *pts,
-                               RtwFilterStats *stats, int *last_hip) {
+                               const TemporalBounds *bds, RtwFilterStats *stats, int *last_hip) {
     const auto t0 = std::chrono::steady_clock::now();
     TemporalPlan pl;
     const int rc = temporal_check(b.cur, w, h, cam, b.depth, b.normal, b.idx, prev_cam, b.prev_color, b.prev_moments, b.prev_len, b.prev_depth,
@@ -95,7 +107,13 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
         pt = *pts;
         if (!(pl.terms & TEMPORAL_NORMAL)) pt.normal = nullptr;                          // (read by the normal test only)
     }
-    const bool motion = mo.rows || mo.prev_xy;
+    TemporalBounds bd = { nullptr, nullptr, nullptr };
+    if (bds && (bds->lo || bds->hi || bds->clipped)) {
+        const int rb = temporal_check_bounds(bds->lo, bds->hi, bds->clipped, b.out_color, b.out_moments, b.out_len, b.out_variance, mo.prev_xy);
+        if (rb != RTW_OK) return rb;
+        bd = *bds;
+    }
+    const bool motion = mo.rows || mo.prev_xy, bounded = bd.lo || bd.clipped;
     TEMPORAL_TRY(hipSetDevice(device));
     if (!*scratch) {
         TemporalScratch *s = new (std::nothrow) TemporalScratch();
@@ -111,7 +129,7 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
     TemporalHistory hs = { b.prev_color, b.prev_moments, b.prev_len, (pl.terms & TEMPORAL_DEPTH) ? b.prev_depth : nullptr,
                            (pl.terms & TEMPORAL_NORMAL) ? b.prev_normal : nullptr, (pl.terms & TEMPORAL_IDX) ? b.prev_idx : nullptr };
     struct Stage { const void **p; DevMem *m; size_t bytes; };
-    const Stage stages[13] = { { (const void **)&f.cur, &s->cur, f3 },
+    const Stage stages[15] = { { (const void **)&f.cur, &s->cur, f3 },
                                { (const void **)&f.depth, &s->depth, f1 },
                                { (const void **)&f.normal, &s->normal, f3 },
                                { (const void **)&f.idx, &s->idx, n_px * sizeof(int32_t) },
@@ -123,7 +141,9 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
                                { (const void **)&hs.idx, &s->prev_idx, n_px * sizeof(int32_t) },
                                { (const void **)&mo.rows, &s->rows, (size_t)mo.n_rows * sizeof(RtwMotionRow) },
                                { (const void **)&pt.point, &s->point, f3 },
-                               { (const void **)&pt.normal, &s->carried, f3 } };
+                               { (const void **)&pt.normal, &s->carried, f3 },
+                               { (const void **)&bd.lo, &s->hist_lo, f3 },
+                               { (const void **)&bd.hi, &s->hist_hi, f3 } };
     for (const Stage &st : stages) {
         if (!*st.p || on_device(*st.p, device)) continue;
         TEMPORAL_TRY(st.m->reserve(st.bytes));
@@ -132,11 +152,12 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
     }
     TemporalOut o = { b.out_color, b.out_moments, b.out_len, b.out_variance };
     struct Result { float **p; float *host; DevMem *m; size_t bytes; };
-    Result results[5] = { { &o.color, nullptr, &s->out_color, f3 },
+    Result results[6] = { { &o.color, nullptr, &s->out_color, f3 },
                           { &o.moments, nullptr, &s->out_moments, f2 },
                           { &o.len, nullptr, &s->out_len, f1 },
                           { &o.variance, nullptr, &s->out_variance, f1 },
-                          { &mo.prev_xy, nullptr, &s->out_prev_xy, f2 } };
+                          { &mo.prev_xy, nullptr, &s->out_prev_xy, f2 },
+                          { &bd.clipped, nullptr, &s->out_clipped, f1 } };
     for (Result &r : results) {
         if (!*r.p || on_device(*r.p, device)) continue;
         TEMPORAL_TRY(r.m->reserve(r.bytes));
@@ -147,7 +168,8 @@ int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch *
     const uint32_t tiles_x = (w + TBX - 1) / TBX, tiles_y = (h + TBY - 1) / TBY;
     TEMPORAL_TRY(hipEventRecord(s->ev[0], stream));
     const dim3 grid((unsigned)((uint64_t)tiles_x * tiles_y));
-    if (pt.point) hipLaunchKernelGGL(temporal_points_kernel, grid, dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o, mo, pt);
+    if (bounded) hipLaunchKernelGGL(temporal_bounded_kernel, grid, dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o, mo, pt, bd);
+    else if (pt.point) hipLaunchKernelGGL(temporal_points_kernel, grid, dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o, mo, pt);
     else if (motion) hipLaunchKernelGGL(temporal_motion_kernel, grid, dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o, mo);
     else hipLaunchKernelGGL(temporal_kernel, grid, dim3(TBX * TBY), 0, stream, pl, tiles_x, f, hs, o);
     TEMPORAL_TRY(hipGetLastError());

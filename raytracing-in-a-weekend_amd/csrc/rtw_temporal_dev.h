@@ -24,10 +24,13 @@ struct TemporalBuffers {
 // the launch of rtw_ctx_temporal_accumulate.
 // pt: rtw_ctx_temporal_accumulate_points' prev_point and carried_normal (host or device memory) -- null, or prev_point null: the launch
 // `m` alone selects.
+// bd: rtw_ctx_temporal_accumulate_bounded's hist_lo, hist_hi and out_clipped (host or device memory) -- null, or all three null: the launch
+// `m` and `pt` select.
 struct TemporalMotion;
 struct TemporalPoints;
+struct TemporalBounds;
 int temporal_accumulate_device(int device, hipStream_t stream, TemporalScratch **scratch, uint32_t w, uint32_t h, const RtwCamera *cam,
                                const RtwCamera *prev_cam, const TemporalBuffers &b, const RtwTemporal *p, const TemporalMotion *m,
-                               const TemporalPoints *pt, RtwFilterStats *stats, int *last_hip);
+                               const TemporalPoints *pt, const TemporalBounds *bd, RtwFilterStats *stats, int *last_hip);
 
 } // namespace rtw
