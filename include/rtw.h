@@ -325,7 +325,8 @@ enum {
     RTW_OPT_ATROUS_LAYOUT    = 14,/* where a level of rtw_ctx_atrous_filter reads its taps: 0 (default) the measured choice per level
                                      (DESIGN.md 8c); 1 from an LDS tile of the workgroup's pixels and their halo wherever that tile fits; 2 from
                                      global memory.  The bytes are the same.  Any other value: RTW_E_INVALID.  (added within v4)
-                                     rtw_ctx_svgf_filter's levels and rtw_ctx_variance_estimate's window follow it too.    */
+                                     rtw_ctx_svgf_filter's levels and rtw_ctx_variance_estimate's window follow it too, and
+                                     so do rtw_ctx_colour_bounds' window (8h) and rtw_ctx_upsample_filter's low window (8i).              */
 };
 int  rtw_ctx_set_option(rtw_ctx *ctx, uint32_t key, double value);
 /* Which compiled build of the render kernel the context's last render launched, as text in template-argument order:
@@ -893,6 +894,71 @@ int rtw_ctx_temporal_accumulate_bounded(rtw_ctx *ctx, const float *cur, uint32_t
                                         const float *hist_lo /* may be NULL */, const float *hist_hi /* may be NULL */,
                                         float *out_color, float *out_moments, float *out_len, float *out_variance /* may be NULL */,
                                         float *out_prev_xy /* may be NULL */, float *out_clipped /* may be NULL */, RtwFilterStats *stats);
+
+/* ---- guided upsampling: a low-resolution frame reconstructed at the output size from full-size guides -- added within v4 -------------------
+ * Joint bilateral upsampling (Kopf et al. 2007) on demodulated colour: the expensive samples are traced on a grid `scale` times coarser, the
+ * guides (which cost almost nothing) at both sizes, and texture and silhouettes come from the output-size guides at full sharpness.
+ * `lo` is a linear f32 frame [h_lo][w_lo][3]; one RtwGuides is at the low size and one at the output size [h][w], both in the layouts
+ * rtw_ctx_surface_map writes: depth f32, normal [..][3] f32, idx i32, albedo [..][3] f32, emitted [..][3] f32.  scale = s is in
+ * 1 .. RTW_UPSAMPLE_MAX_SCALE, w_lo == ceil(w / s), h_lo == ceil(h / s); low pixel (I, J) covers output pixels s*I .. s*I+s-1 by
+ * s*J .. s*J+s-1 (rtw_camera_scaled gives the camera whose pixels those are).  Everything is f32 with one rounding per written operation
+ * (no fused multiply-add), exp_plain is rtw_exp_plain's:
+ *   demodulate, at a low pixel q:  a_c = (albedo_lo && albedo_lo[q][c] >= albedo_floor) ? albedo_lo[q][c] : 1;
+ *                e_c = emitted_lo ? emitted_lo[q][c] : 0;   L[q][c] = (lo[q][c] - e_c) / a_c
+ *   footprint of output pixel p = (i, j), formed in integers:  N = 2*i + 1 - s, D = 2*s;  I0 = floor(N / D) (floor division: -1 on the
+ *                first columns);  tx = (float)(N - I0*D) / (float)D;  J0 and ty likewise from j
+ *   taps ky = -(radius-1) .. radius outer, kx likewise inner, radius 1 or 2 (2 x 2 or 4 x 4 low pixels):  q = (I0 + kx, J0 + ky), those
+ *   outside the low frame skipped;  wx = kx <= 0 ? (float)(radius + kx) - tx : (float)(radius - kx) + tx, wy likewise;  hw = wx * wy
+ *   (a tent; the bilinear weights at radius 1);  a = 0
+ *     if sigma_depth  > 0:  dz = (depth_lo[q] - depth_hi[p]) * inv_s;  a = a + inv_depth * (dz * dz)        inv_s = 1.0f / (float)s
+ *     if sigma_normal > 0:  d = normal_lo[q] - normal_hi[p];           a = a + inv_normal * ((d.x*d.x + d.y*d.y) + d.z*d.z)
+ *     g = (a >= 0) ? exp_plain(-a) : 0;   if same_object and idx_lo[q] != idx_hi[p]:  g = 0;   wt = hw * g
+ *     if wt > 0 and L[q][0], L[q][1], L[q][2] are all finite:  sum_c = sum_c + L[q][c] * wt;  wsum = wsum + wt
+ *   C = wsum > 0 ? sum / wsum : L[(i / s, j / s)]         (the fallback: the covering low pixel, unguided; a NaN there passes through)
+ *   remodulate:  out[p][c] = C_c * ah_c + eh_c, ah_c and eh_c by the same floor rule from albedo_hi and emitted_hi
+ * with inv_x = 0.5f / (sigma_x * sigma_x) as in the a-trous filter.  wsum_out [h][w] f32 (may be NULL) receives every pixel's wsum: 0 exactly
+ * where the fallback was taken, the pass's diagnostic as out_clipped is the bounded accumulation's.  A guide whose term is off, and any
+ * albedo or emitted buffer, may be NULL and is then never read; guides_lo or guides_hi NULL is a struct of NULLs.
+ * RTW_E_INVALID, nothing written: lo, out or params NULL; w or h zero or beyond RTW_ATROUS_MAX_SIDE, or w * h beyond 32 bits; a low size that
+ * is not the ceiling above; scale outside 1 .. RTW_UPSAMPLE_MAX_SCALE or radius outside 1 .. RTW_UPSAMPLE_MAX_RADIUS; a sigma that is
+ * negative or not finite, or so small that its inv_* is not finite; a term that is on with its guide NULL on either side; same_object > 1;
+ * with an albedo given on either side, an albedo_floor that is not finite or not > 0; out or wsum_out equal to a buffer that is read, or to
+ * each other.  `out` must not overlap an input in any other way either.
+ * What stays out: a plane-distance depth term, fractional scales, a colour term, upsampling of a history.  There is no rtw_mgpu_* form and
+ * no JSON form. */
+#define RTW_UPSAMPLE_MAX_SCALE  8u
+#define RTW_UPSAMPLE_MAX_RADIUS 2u
+typedef struct RtwGuides {
+    const float   *depth;           /* [..] f32                                                                       */
+    const float   *normal;          /* [..][3] f32                                                                    */
+    const int32_t *idx;             /* [..] i32                                                                       */
+    const float   *albedo;          /* [..][3] f32, may be NULL whatever the terms                                    */
+    const float   *emitted;         /* [..][3] f32, may be NULL whatever the terms                                    */
+} RtwGuides;
+typedef struct RtwUpsample {
+    uint32_t scale;                 /* 1 .. RTW_UPSAMPLE_MAX_SCALE: output pixels per low pixel along a side          */
+    uint32_t radius;                /* 1 = 2 x 2 low pixels (bilinear), 2 = 4 x 4 (a tent)                            */
+    float    sigma_depth;           /* 0 = no depth term; else in the units of `depth` per low pixel                  */
+    float    sigma_normal;          /* 0 = no normal term; else in units of |n - n'|                                  */
+    uint32_t same_object;           /* 1 = a tap on another idx weighs 0                                             */
+    float    albedo_floor;          /* used when an albedo is given: a channel below it is not (de/re)modulated       */
+} RtwUpsample;
+/* The host form (one thread).  RtwFilterStats: filter_ms and total_ms are the call's time, taps counts the taps inside the low frame, the
+ * other fields are 0. */
+int rtw_upsample_filter(const float *lo, uint32_t w_lo, uint32_t h_lo, const RtwGuides *guides_lo, uint32_t w, uint32_t h,
+                        const RtwGuides *guides_hi, const RtwUpsample *params, float *out, float *wsum_out /* may be NULL */,
+                        RtwFilterStats *stats);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host form.  Every buffer may independently be host memory (staged through a
+ * scratch the context keeps) or device memory of ctx's GPU (used in place).  One launch, one thread per output pixel, the low window read
+ * from an LDS tile or from global memory (RTW_OPT_ATROUS_LAYOUT); filter_ms is its device time.  Needs no scene. */
+int rtw_ctx_upsample_filter(rtw_ctx *ctx, const float *lo, uint32_t w_lo, uint32_t h_lo, const RtwGuides *guides_lo, uint32_t w, uint32_t h,
+                            const RtwGuides *guides_hi, const RtwUpsample *params, float *out, float *wsum_out /* may be NULL */,
+                            RtwFilterStats *stats);
+/* Host only, pure: the camera whose pixel (I, J) is the scale x scale block of cam's pixels.  delta_u and delta_v are multiplied by
+ * (float)scale, every other field is copied (nothing goes back through vfov): its ray at offset (0.5, 0.5) is cam's at
+ * (scale*I + scale/2, scale*J + scale/2).  Render and take the low guides with it at ceil(w / scale) x ceil(h / scale), for any size.
+ * RTW_E_INVALID for NULL or a scale outside 1 .. RTW_UPSAMPLE_MAX_SCALE. */
+int rtw_camera_scaled(const RtwCamera *cam, uint32_t scale, RtwCamera *out);
 
 /* ---- Rust2 triangles (Rust2/src/objects/triangle.rs) ----------------------------------------------------------------------------
  * `Triangle{origin, u, v, mat, texture}` with the derived fields of Triangle::new (:28-50): n = u x v, normal = unit(n),

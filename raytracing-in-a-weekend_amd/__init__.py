@@ -89,6 +89,13 @@ BOUNDS_MAX_RADIUS = 3
 # mean ratio, with both on, over the late frames of the five recorded sequences (0.359 against 0.400 as recorded; it helps four of them and
 # costs on the light scene: DESIGN.md 8h, profiles/history_clamp.log).  The denoisers' own default stays None.
 BOUNDS_DEFAULTS = {"radius": 1, "k": 1.0}
+UPSAMPLE_MAX_SCALE = 8
+UPSAMPLE_MAX_RADIUS = 2
+# Renderer.upsample_filter's defaults: the best row of the sweep at half size on the 16-spp Book-1 view, by the sum of the upsampled and the
+# filtered-then-upsampled column (profiles/upsample.log) -- the 4 x 4 tent, a tight normal term, same_object, no depth term.
+# The a-trous filter's own sigmas (depth 0.25, normal 0.3) lose there: they let taps across a silhouette through, whose demodulated colour
+# is wrong by the ratio of two albedos.
+UPSAMPLE_DEFAULTS = {"radius": 2, "sigma_depth": 0.0, "sigma_normal": 0.1, "same_object": True, "albedo_floor": ATROUS_DEFAULTS["albedo_floor"]}
 
 # materials.rs:157-212 presets as (metallicness, opacity, ir)
 METALLIC_M = (1.0, 0.0, 1.0)
@@ -238,6 +245,18 @@ class RtwColourBounds(C.Structure):
     """Arguments of the neighbourhood colour bounds: the window's radius, the box's half-width k in standard deviations, same_object and
     exclude_centre (include/rtw.h)."""
     _fields_ = [("radius", C.c_uint32), ("k", C.c_float), ("same_object", C.c_uint32), ("exclude_centre", C.c_uint32)]
+
+
+class RtwGuides(C.Structure):
+    """One size's guide buffers of the guided upsampling, as surface_map writes them; NULL where not given (include/rtw.h)."""
+    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("idx", C.c_void_p), ("albedo", C.c_void_p), ("emitted", C.c_void_p)]
+
+
+class RtwUpsample(C.Structure):
+    """Arguments of the guided upsampling: scale, the footprint's radius, the guide sigmas (0 = term off), same_object and the albedo floor
+    (include/rtw.h)."""
+    _fields_ = [("scale", C.c_uint32), ("radius", C.c_uint32), ("sigma_depth", C.c_float), ("sigma_normal", C.c_float),
+                ("same_object", C.c_uint32), ("albedo_floor", C.c_float)]
 
 
 class RtwFilterStats(C.Structure):
@@ -480,6 +499,10 @@ def lib() -> C.CDLL:
     L.rtw_ctx_temporal_accumulate_bounded.argtypes = [C.c_void_p] + L.rtw_temporal_accumulate_bounded.argtypes
     L.rtw_colour_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtwColourBounds)] + [C.c_void_p] * 3 + [C.POINTER(RtwFilterStats)]
     L.rtw_ctx_colour_bounds.argtypes = [C.c_void_p] + L.rtw_colour_bounds.argtypes
+    L.rtw_upsample_filter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwGuides), C.c_uint32, C.c_uint32, C.POINTER(RtwGuides),
+                                      C.POINTER(RtwUpsample), C.c_void_p, C.c_void_p, C.POINTER(RtwFilterStats)]
+    L.rtw_ctx_upsample_filter.argtypes = [C.c_void_p] + L.rtw_upsample_filter.argtypes
+    L.rtw_camera_scaled.argtypes = [C.POINTER(RtwCamera), C.c_uint32, C.POINTER(RtwCamera)]
     L.rtw_ctx_scene_surface_tri.argtypes = L.rtw_ctx_scene_surface.argtypes[:-1] + [C.c_void_p] * 2 + [C.POINTER(RtwStats)]
     L.rtw_ctx_surface_map_tri.argtypes = L.rtw_ctx_surface_map.argtypes[:-1] + [C.c_void_p] * 2 + [C.POINTER(RtwStats)]
     L.rtw_tri_bary.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1046,6 +1069,14 @@ def pixel_rays(cam: RtwCamera, width: int, height: int, offset=(0.0, 0.0)) -> np
     out = np.empty((max(0, width * height), 6), np.float32)
     off = (C.c_float * 2)(float(offset[0]), float(offset[1]))
     _check(lib().rtw_pixel_rays(C.byref(cam), width, height, off, out.ctypes.data_as(C.POINTER(C.c_float))), "rtw_pixel_rays")
+    return out
+
+
+def camera_scaled(cam: RtwCamera, scale: int) -> RtwCamera:
+    """The camera whose pixel (I, J) is the scale x scale block of cam's pixels (rtw_camera_scaled): delta_u and delta_v times scale, every
+    other field copied.  Render and take the low guides of upsample_filter with it, at ceil(w / scale) x ceil(h / scale)."""
+    out = RtwCamera()
+    _check(lib().rtw_camera_scaled(C.byref(cam), int(scale), C.byref(out)), "rtw_camera_scaled")
     return out
 
 
@@ -2198,6 +2229,45 @@ class Renderer:
         return _bounds_call(lib().rtw_ctx_colour_bounds, "rtw_ctx_colour_bounds", (self._h,), self._on_device, frame, ids, radius, k, same_object,
                             exclude_centre, out_lo, out_hi, out_clamped)
 
+    def upsample_filter(self, frame_lo, size, lo=None, hi=None, scale: int = 2, radius: int = UPSAMPLE_DEFAULTS["radius"],
+                        sigma_depth: float = UPSAMPLE_DEFAULTS["sigma_depth"], sigma_normal: float = UPSAMPLE_DEFAULTS["sigma_normal"],
+                        same_object: bool = UPSAMPLE_DEFAULTS["same_object"], albedo_floor: float = UPSAMPLE_DEFAULTS["albedo_floor"], out=None,
+                        out_wsum=False):
+        """A linear float32 frame [h_lo][w_lo][3] reconstructed at size = (w, h) on this context's GPU (rtw_ctx_upsample_filter,
+        include/rtw.h), with w_lo = ceil(w / scale) and h_lo = ceil(h / scale): joint bilateral upsampling of (frame - emitted) / albedo.
+        Every output pixel takes the 2 x 2 (radius 1, bilinear) or 4 x 4 (radius 2, a tent) low pixels about its centre, each weighed by
+        exp_plain(-((dz / scale)^2 / (2 sigma_depth^2) + |dn|^2 / (2 sigma_normal^2))) between the LOW guide of the tap and the OUTPUT-size
+        guide of the pixel, and by 0 on another object with same_object; the result is multiplied by the output-size albedo and the
+        output-size emission added.  A pixel no tap reaches takes its covering low pixel.  lo, hi: dicts as surface_map returns them, at
+        the low size (taken with camera_scaled(cam, scale)) and at the output size; only the keys a term needs are read -- depth with
+        sigma_depth > 0, normal with sigma_normal > 0, idx with same_object -- and albedo and emitted where present.  Every array is a numpy
+        array (staged) or a contiguous torch tensor on the context's device, read and written in place on the context's stream.  out: None
+        -> a new array or tensor like frame_lo.  out_wsum: None or False -> not wanted, True -> new, else an array or tensor [h][w]; it
+        receives every pixel's weight sum, 0 exactly where the fallback was taken.  Returns (out, wsum or None, RtwFilterStats)."""
+        return _upsample_call(lib().rtw_ctx_upsample_filter, "rtw_ctx_upsample_filter", (self._h,), self._on_device, frame_lo, size, lo, hi, scale,
+                              radius, sigma_depth, sigma_normal, same_object, albedo_floor, out, out_wsum)
+
+    def render_upsampled(self, cam: RtwCamera, params: RtwParams, scale: int, atrous=None, **upsample):
+        """Python only: render at ceil(width / scale) x ceil(height / scale) with camera_scaled(cam, scale) at gamma 1, take the low guides
+        there at the pixel centres, optionally run atrous_filter at the low size with albedo and emission (atrous: a dict of its keyword
+        arguments, None = no filter), take the guides at params' size with `cam`, run upsample_filter (keyword arguments: its own), then
+        apply params.gamma as render_denoised does.  For Viewport cameras and whole frames (part_count 1).  Returns (frame [h][w][3]
+        float32, RtwStats of the render)."""
+        if params.part_count != 1:
+            raise ValueError("render_upsampled: whole frames only (part_count 1)")
+        lcam, lp = _scaled_view(cam, params, int(scale))
+        lp.gamma = 1.0
+        frame, st = self.render(lcam, lp)
+        surf = lambda c, p: self.surface_map(c, p.width, p.height, p.mint, p.maxt, p.integrator, RAYS_PIXEL, (0.5, 0.5), accel=p.accel)
+        g = surf(lcam, lp)
+        if atrous is not None:
+            frame = self.atrous_filter(frame, depth=g["depth"], normal=g["normal"], ids=g["idx"], albedo=g["albedo"], emitted=g["emitted"], **atrous)[0]
+        out = self.upsample_filter(frame, (params.width, params.height), lo=g, hi=surf(cam, params), scale=scale, **upsample)[0]
+        gamma = float(params.gamma)
+        if gamma != 1.0:
+            out = np.power(np.maximum(out, np.float32(0.0)), np.float32(1.0 / gamma)).astype(np.float32)
+        return out, st
+
     def variance_estimate(self, moments, length, depth=None, normal=None, ids=None, min_history: int = SVGF_DEFAULTS["min_history"],
                           radius: int = SVGF_DEFAULTS["radius"], sigma_depth: float = SVGF_DEFAULTS["sigma_depth"],
                           sigma_normal: float = SVGF_DEFAULTS["sigma_normal"], same_object: bool = True, out=None):
@@ -2611,19 +2681,88 @@ def colour_bounds(frame, ids=None, radius: int = BOUNDS_DEFAULTS["radius"], k: f
                         out_clamped)
 
 
+def _upsample_call(fn, fn_name, head, on_device, frame_lo, size, lo, hi, scale, radius, sigma_depth, sigma_normal, same_object, albedo_floor,
+                   out, out_wsum):
+    """rtw_upsample_filter / rtw_ctx_upsample_filter from the Python arguments of upsample_filter: (out, wsum or None, stats)."""
+    who = "upsample_filter"
+    shp = tuple(frame_lo.shape) if hasattr(frame_lo, "shape") else np.shape(frame_lo)
+    if len(shp) != 3 or shp[2] != 3:
+        raise ValueError(f"{who}: frame_lo of shape {shp}, expected [h_lo][w_lo][3]")
+    h_lo, w_lo = int(shp[0]), int(shp[1])
+    w, h = int(size[0]), int(size[1])
+    keep = []
+    ptr = lambda name, a, dtype, shape, writable=False: _atrous_pointer(name, a, dtype, shape, on_device, keep, writable, who)
+    prm = RtwUpsample(int(scale), int(radius), float(sigma_depth), float(sigma_normal), int(bool(same_object)), float(albedo_floor))
+
+    def guides(name, d, gh, gw):
+        d = d or {}
+        need = {"depth": prm.sigma_depth > 0.0, "normal": prm.sigma_normal > 0.0, "idx": bool(prm.same_object), "albedo": True, "emitted": True}
+        shapes = {"depth": (gh, gw), "normal": (gh, gw, 3), "idx": (gh, gw), "albedo": (gh, gw, 3), "emitted": (gh, gw, 3)}
+        p = {k: ptr(f"{name}[{k!r}]", d.get(k) if need[k] else None, np.int32 if k == "idx" else np.float32, shapes[k]) for k in need}
+        return RtwGuides(*(p[k].value if p[k] is not None else None for k in ("depth", "normal", "idx", "albedo", "emitted")))
+
+    g_lo, g_hi = guides("lo", lo, h_lo, w_lo), guides("hi", hi, h, w)
+    if out is None:
+        out = _like(frame_lo, (h, w, 3))
+    out_wsum = None if out_wsum is None or out_wsum is False else (_like(frame_lo, (h, w)) if out_wsum is True else out_wsum)
+    st = RtwFilterStats()
+    _check(fn(*head, ptr("frame_lo", frame_lo, np.float32, (h_lo, w_lo, 3)), w_lo, h_lo, C.byref(g_lo), w, h, C.byref(g_hi), C.byref(prm),
+              ptr("out", out, np.float32, (h, w, 3), True), ptr("out_wsum", out_wsum, np.float32, (h, w), True), C.byref(st)), fn_name)
+    return out, out_wsum, st
+
+
+def upsample_filter(frame_lo, size, lo=None, hi=None, scale: int = 2, radius: int = UPSAMPLE_DEFAULTS["radius"],
+                    sigma_depth: float = UPSAMPLE_DEFAULTS["sigma_depth"], sigma_normal: float = UPSAMPLE_DEFAULTS["sigma_normal"],
+                    same_object: bool = UPSAMPLE_DEFAULTS["same_object"], albedo_floor: float = UPSAMPLE_DEFAULTS["albedo_floor"], out=None,
+                    out_wsum=False):
+    """The guide-steered upsampling on the host (rtw_upsample_filter), the bytes of Renderer.upsample_filter; numpy arrays only.  Arguments
+    and result as there."""
+    return _upsample_call(lib().rtw_upsample_filter, "rtw_upsample_filter", (), None, frame_lo, size, lo, hi, scale, radius, sigma_depth,
+                          sigma_normal, same_object, albedo_floor, out, out_wsum)
+
+
+def _scaled_view(cam: RtwCamera, params: RtwParams, scale: int):
+    """(camera_scaled(cam, scale), a copy of params at ceil(width / scale) x ceil(height / scale))."""
+    lp = RtwParams.from_buffer_copy(params)
+    lp.width, lp.height = -(-params.width // scale), -(-params.height // scale)
+    return camera_scaled(cam, scale), lp
+
+
 class TemporalDenoiser:
     """Python only: a sequence driver around Renderer.temporal_accumulate for Viewport cameras and whole frames (part_count 1).
     `params`: temporal_accumulate's keyword arguments (TEMPORAL_DEFAULTS), but for offset, which is (0.5, 0.5).  The scene is static
-    from one step to the next unless `motion` says otherwise."""
+    from one step to the next unless `motion` says otherwise.
+    scale > 1: every step renders, takes its guides, reprojects, accumulates and filters at ceil(width / scale) x ceil(height / scale)
+    with camera_scaled(cam, scale) -- the history lives at that size -- then takes the guides at params' size with `cam` and upsamples
+    the filtered frame with Renderer.upsample_filter (`upsample`: a dict of its keyword arguments).  scale 1: the steps' calls are what
+    they were without it."""
 
-    def __init__(self, renderer, **params):
+    def __init__(self, renderer, scale: int = 1, upsample=None, **params):
         if "offset" in params:
             raise TypeError("TemporalDenoiser: the offset is (0.5, 0.5), the centre of the jittered samplers' pixel")
+        if not 1 <= int(scale) <= UPSAMPLE_MAX_SCALE:
+            raise ValueError(f"{type(self).__name__}: scale {scale} outside 1 .. {UPSAMPLE_MAX_SCALE}")
         self.renderer, self.params, self.history = renderer, dict(params), None
+        self.scale, self.upsample = int(scale), dict(upsample or {})
 
     def reset(self):
         """Drop the history: the next step starts a sequence."""
         self.history = None
+
+    def _low(self, cam, params):
+        """(the camera, the params) a step works with: the caller's own at scale 1."""
+        return (cam, params) if self.scale == 1 else _scaled_view(cam, params, self.scale)
+
+    def _upsampled(self, frame, g, cam, params, stats):
+        """The step's filtered linear frame at params' size: itself at scale 1; else upsampled with the output-size guides (stats gains
+        guides_hi, upsample and wsum)."""
+        if self.scale == 1:
+            return frame
+        r = self.renderer
+        hi = r.surface_map(cam, params.width, params.height, params.mint, params.maxt, params.integrator, RAYS_PIXEL, (0.5, 0.5), accel=params.accel)
+        frame, wsum, st_u = r.upsample_filter(frame, (params.width, params.height), lo=g, hi=hi, scale=self.scale, out_wsum=True, **self.upsample)
+        stats.update(guides_hi=hi, upsample=st_u, wsum=wsum)
+        return frame
 
     def _guides(self, cam, params, prev_ouv, prev_poses):
         """(surface_map's dict for this frame, temporal_accumulate's prev_point / carried_normal arguments): with prev_ouv the map also
@@ -2669,11 +2808,15 @@ class TemporalDenoiser:
         firefly: None, or dict(radius, k) -- the frame that enters everything behind the render is colour_bounds' out_clamped with
         exclude_centre (stats["cur"] is then the clamped frame).  history_clamp: None, or dict(radius, k, same_object) -- colour_bounds of
         that frame bounds the reprojected history (temporal_accumulate's hist_lo / hist_hi); history["clipped"] says by how much.  stats
-        gains firefly / history_clamp, the RtwFilterStats of those calls.  With both None the step makes the calls it made without them."""
+        gains firefly / history_clamp, the RtwFilterStats of those calls.  With both None the step makes the calls it made without them.
+        With the denoiser's scale > 1 only `frame` is at params' size: accumulated, variance, cur and guides are at the low size, and stats
+        gains guides_hi (surface_map's dict at params' size), upsample (RtwFilterStats) and wsum (upsample_filter's out_wsum)."""
         if params.part_count != 1:
             raise ValueError("TemporalDenoiser: whole frames only (part_count 1)")
         r = self.renderer
         params.seed = (params.seed + 1) & 0xFFFFFFFFFFFFFFFF
+        out_cam, out_params = cam, params
+        cam, params = self._low(cam, params)           # (the caller's own at scale 1)
         gamma = float(params.gamma)
         params.gamma = 1.0
         try:
@@ -2687,9 +2830,11 @@ class TemporalDenoiser:
                                                              **self.params)
         acc = self.history["color"]
         frame, st_a = r.atrous_filter(acc, depth=g["depth"], normal=g["normal"], ids=g["idx"], albedo=g["albedo"], emitted=g["emitted"], **atrous)
+        st_u = {}
+        frame = self._upsampled(frame, g, out_cam, out_params, st_u)
         if gamma != 1.0:
             frame = np.power(np.maximum(frame, np.float32(0.0)), np.float32(1.0 / gamma)).astype(np.float32)
-        stats = dict(render=st, temporal=st_t, atrous=st_a, coverage=float((self.history["len"] > 1).mean()), cur=cur, guides=g, **st_b)
+        stats = dict(render=st, temporal=st_t, atrous=st_a, coverage=float((self.history["len"] > 1).mean()), cur=cur, guides=g, **st_b, **st_u)
         return frame, acc, variance, stats
 
 
@@ -2772,12 +2917,14 @@ class SvgfDenoiser(TemporalDenoiser):
         guide sigmas and same_object those of **svgf) on the new history's moments and length; svgf_filter (keyword arguments: its own) on
         the accumulated colour with albedo and emission; params.gamma applied.  Returns (frame, accumulated, variance, stats): variance is
         the estimate the filter was steered by; stats holds render, temporal, variance and svgf (RtwStats and three RtwFilterStats),
-        coverage, cur, guides, and filtered_variance, the variance the filter's levels left.  firefly, history_clamp: as
-        TemporalDenoiser.step's."""
+        coverage, cur, guides, and filtered_variance, the variance the filter's levels left.  firefly, history_clamp and what a scale > 1
+        changes: as TemporalDenoiser.step's."""
         if params.part_count != 1:
             raise ValueError("SvgfDenoiser: whole frames only (part_count 1)")
         r = self.renderer
         params.seed = (params.seed + 1) & 0xFFFFFFFFFFFFFFFF
+        out_cam, out_params = cam, params
+        cam, params = self._low(cam, params)           # (the caller's own at scale 1)
         gamma = float(params.gamma)
         params.gamma = 1.0
         try:
@@ -2795,10 +2942,12 @@ class SvgfDenoiser(TemporalDenoiser):
                                              min_history=min_history, radius=radius, **guide_kw)
         frame, fvar, st_s = r.svgf_filter(acc, variance, depth=g["depth"], normal=g["normal"], ids=g["idx"], albedo=g["albedo"],
                                           emitted=g["emitted"], **svgf)
+        st_u = {}
+        frame = self._upsampled(frame, g, out_cam, out_params, st_u)
         if gamma != 1.0:
             frame = np.power(np.maximum(frame, np.float32(0.0)), np.float32(1.0 / gamma)).astype(np.float32)
         stats = dict(render=st, temporal=st_t, variance=st_v, svgf=st_s, coverage=float((self.history["len"] > 1).mean()), cur=cur, guides=g,
-                     filtered_variance=fvar, **st_b)
+                     filtered_variance=fvar, **st_b, **st_u)
         return frame, acc, variance, stats
 
 

@@ -11,6 +11,7 @@
 #include "rtw_temporal.h"
 #include "rtw_svgf_dev.h"
 #include "rtw_bounds_dev.h"
+#include "rtw_upsample_dev.h"
 #include "rtw_devmem.h"
 #include "rtw_exp.h"
 #include "rtw_probe.h"
@@ -106,6 +107,7 @@ struct rtw_ctx {
     AtrousScratch *atrous = nullptr;     // buffers of rtw_ctx_atrous_filter (rtw_atrous.hip), rtw_ctx_svgf_filter and rtw_ctx_variance_estimate
                                          // (rtw_svgf.hip), created on the first call of any of them
     BoundsScratch *bounds = nullptr;     // buffers of rtw_ctx_colour_bounds (rtw_bounds.hip), created on its first call
+    UpsampleScratch *upsample = nullptr; // buffers of rtw_ctx_upsample_filter (rtw_upsample.hip), created on its first call
     TemporalScratch *temporal = nullptr; // buffers of rtw_ctx_temporal_accumulate (rtw_temporal.hip), created on its first call
     FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
     MotionMem motion_mem;                // buffers of rtw_ctx_mesh_instance_motion
@@ -535,6 +537,7 @@ void rtw_ctx_destroy(rtw_ctx *c) {
     atrous_scratch_free(c->atrous);
     temporal_scratch_free(c->temporal);
     bounds_scratch_free(c->bounds);
+    upsample_scratch_free(c->upsample);
     if (c->ev_mark) (void)hipEventDestroy(c->ev_mark);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1626,6 +1629,15 @@ int rtw_ctx_colour_bounds(rtw_ctx *c, const float *in, uint32_t w, uint32_t h, c
     if (c->pend.active) return RTW_E_INVALID;
     return colour_bounds_device(c->device, c->stream, &c->bounds, c->opt_atrous_layout, in, w, h, idx, p, out_lo, out_hi, out_clamped, stats,
                                 &g_last_hip);
+}
+
+// The guide-steered upsampling (rtw_upsample.hip) likewise, on a scratch of its own.
+int rtw_ctx_upsample_filter(rtw_ctx *c, const float *lo, uint32_t w_lo, uint32_t h_lo, const RtwGuides *guides_lo, uint32_t w, uint32_t h,
+                            const RtwGuides *guides_hi, const RtwUpsample *p, float *out, float *wsum_out, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return upsample_filter_device(c->device, c->stream, &c->upsample, c->opt_atrous_layout, lo, w_lo, h_lo, guides_lo, w, h, guides_hi, p, out,
+                                  wsum_out, stats, &g_last_hip);
 }
 
 // The device-math probe (rtw_probe.hip, rtw.h "device math, for tests") on this context's GPU and stream; the scene is not involved.
