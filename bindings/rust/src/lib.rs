@@ -105,6 +105,8 @@ pub struct TemporalBuffers { pub cur: *const f32, pub depth: *const f32, pub nor
     pub out_prev_xy: *mut f32 }
 /// `RTW_OPT_ATROUS_LAYOUT` (rtw.h): where a level of the a-trous filter reads its taps (0 the measured choice, 1 LDS tile, 2 global memory).
 pub const RTW_OPT_ATROUS_LAYOUT: u32 = 14;
+/// `RTW_OPT_HISTOGRAM_COUNT` (rtw.h): how the luminance histogram keeps its LDS counts (0 the measured choice, 1 plain, 2 per wave, 3 ballot).
+pub const RTW_OPT_HISTOGRAM_COUNT: u32 = 15;
 /// The ray rules of `rtw_ctx_surface_map` (rtw.h).
 pub const RTW_RAYS_DEPTH_MAP: u32 = 0;
 pub const RTW_RAYS_PIXEL: u32 = 1;

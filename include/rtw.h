@@ -327,6 +327,10 @@ enum {
                                      global memory.  The bytes are the same.  Any other value: RTW_E_INVALID.  (added within v4)
                                      rtw_ctx_svgf_filter's levels and rtw_ctx_variance_estimate's window follow it too, and
                                      so do rtw_ctx_colour_bounds' window (8h) and rtw_ctx_upsample_filter's low window (8i).              */
+    RTW_OPT_HISTOGRAM_COUNT  = 15,/* how a workgroup of rtw_ctx_luminance_histogram keeps its LDS counts: 0 (default) the measured choice
+                                     (DESIGN.md 8j); 1 one LDS histogram, one LDS atomic a pixel; 2 one LDS histogram a wave, summed at the
+                                     end; 3 one LDS histogram, the lanes of a wave that share the first active lane's slot added as one
+                                     atomic.  The counts are the same.  Any other value: RTW_E_INVALID.  (added within v4)              */
 };
 int  rtw_ctx_set_option(rtw_ctx *ctx, uint32_t key, double value);
 /* Which compiled build of the render kernel the context's last render launched, as text in template-argument order:
@@ -959,6 +963,98 @@ int rtw_ctx_upsample_filter(rtw_ctx *ctx, const float *lo, uint32_t w_lo, uint32
  * (scale*I + scale/2, scale*J + scale/2).  Render and take the low guides with it at ceil(w / scale) x ceil(h / scale), for any size.
  * RTW_E_INVALID for NULL or a scale outside 1 .. RTW_UPSAMPLE_MAX_SCALE. */
 int rtw_camera_scaled(const RtwCamera *cam, uint32_t scale, RtwCamera *out);
+
+/* ---- display stage: luminance histogram, exposure from it, tone map / transfer / bytes -- added within v4 ----------------------------------
+ * The last steps from a linear f32 frame [h][w][3] to something to look at.  Three calls: a histogram of the frame's luminance (a kernel),
+ * an exposure metered from that histogram (pure host code), and the display transform (a kernel).  Everything per pixel is f32 with one
+ * rounding per written operation (no fused multiply-add), divides correctly rounded, pow_plain (rtw_pow_plain) the only elementary function.
+ *
+ * 1. rtw_luminance_histogram.  Per pixel  Y = (0.2126f * r + 0.7152f * g) + 0.0722f * b,  and exactly one of
+ *      non-finite:  a channel is NaN or infinite, or Y overflowed to +inf          -> counts[1]
+ *      black:       finite channels and Y <= 0 (a Y that overflowed to -inf too)   -> counts[0]
+ *      counted:     bin = clamp((int)(bits(Y) >> 20) - 888, 0, 255)                -> hist[bin]
+ *    bits(Y) >> 20 is the exponent and the top three mantissa bits: eight bins a stop over 2^-16 .. 2^16, linear in the mantissa within a stop;
+ *    subnormals and everything below 2^-16 land in bin 0, everything from 2^16 up in bin 255.  hist is uint32[256], counts uint32[2];
+ *    sum(hist) + counts[0] + counts[1] == w * h.  The counts are integers: the host form and the kernel agree exactly.
+ *    RTW_E_INVALID, nothing written: in, hist or counts NULL; w or h zero or beyond RTW_ATROUS_MAX_SIDE, or w * h beyond 32 bits; hist or counts
+ *    overlapping `in` or each other.
+ *
+ * 2. rtw_exposure_from_histogram.  Host only, pure, double arithmetic, no libm call.  With N = sum(hist):
+ *      drop the floor(N * low_permille / 1000) lowest and the floor(N * high_permille / 1000) highest counted pixels, in integers (a bin can
+ *      be cut in part);  over the n left:  S = sum c_i (2 i + 1) in uint64,  m = S / (2 n): the mean bin position, a bin's pixels at its centre;
+ *      m = clamp(m, min_level, max_level);   level = prev_level + rate * (m - prev_level), or m when prev_level is NaN (a first frame);
+ *      back through the inverse of the bin rule:  s = floor(level / 8),  f = level / 8 - s,  Ymeter = (1 + f) * 2^(s - 16),
+ *      exposure = (float)(key / Ymeter).
+ *    n == 0 (nothing counted):  level = prev_level and exposure = prev_exposure, or 1 when prev_level is NaN.
+ *    The mean and its inverse both live in the bin rule's piecewise-linear logarithm (1 + f for 2^f), which no elementary function enters: a
+ *    float64 restatement gives the same bits.  Against a true mean of log2 Y the metered level is off by at most 0.086 stops (the largest gap
+ *    between log2(1 + f) and f), which for metering is irrelevant.
+ *    RTW_E_INVALID, nothing written: a NULL; low_permille + high_permille >= 1000; key not finite or not > 0; rate outside [0, 1]; min_level or
+ *    max_level outside [0, 256] or min_level > max_level; a prev_level that is neither NaN nor in [0, 256].
+ *
+ * 3. rtw_display.  Per pixel (i, j), per channel c:
+ *      x = in_c * exposure
+ *      tone NONE:           v = x
+ *           REINHARD:       v = (x * (1.0f + x / (white * white))) / (1.0f + x)
+ *           REINHARD_LUMA:  Y = (0.2126f * x_r + 0.7152f * x_g) + 0.0722f * x_b;   T = (Y * (1.0f + Y / (white * white))) / (1.0f + Y);
+ *                           v_c = Y > 0 ? x_c * (T / Y) : x_c
+ *           ACES_FIT:       v = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f)                       (Narkowicz 2016)
+ *      clamp:               v = v != v ? v : (v < 0 ? 0 : (v > 1 ? 1 : v))                                          (a NaN propagates)
+ *      transfer GAMMA:      v = pow_plain(v, inv_gamma),  inv_gamma = 1.0f / gamma formed on the host; no call when inv_gamma == 1.0f
+ *               SRGB:       v = v <= 0.0031308f ? 12.92f * v : 1.055f * pow_plain(v, 0.4166666567325592f) - 0.055f   (the f32 of 1 / 2.4)
+ *      out_format F32:      out_c = v
+ *      bytes, dither 0:     t = v * scale;  t = t != t ? t : (t < 0 ? 0 : (t > 255 ? 255 : t));  byte = NaN ? 0 : round half away from zero
+ *                           -- rtw_quantize_u8 with quantise RUST (scale 255.0f), rtw_quantize_u8_rust2 with RUST2 (scale 255.99f)
+ *      bytes, dither 1:     t as above;  d = ((float)B[j & 7][i & 7] + 0.5f) * 0.015625f;  byte = NaN ? 0 : min(255, (int)floorf(t + d))
+ *    with B the 8 x 8 Bayer matrix
+ *        0 32  8 40  2 34 10 42 / 48 16 56 24 50 18 58 26 / 12 44  4 36 14 46  6 38 / 60 28 52 20 62 30 54 22 /
+ *        3 35 11 43  1 33  9 41 / 51 19 59 27 49 17 57 25 / 15 47  7 39 13 45  5 37 / 63 31 55 23 61 29 53 21      (rows j & 7 = 0 .. 7)
+ *    out is [h][w][3] uint8 (RGB8), [h][w][4] uint8 with alpha 255 (RGBA8) or [h][w][3] f32 (F32).
+ *    RTW_E_INVALID, nothing written: in, params or out NULL; sizes as above; exposure not finite or negative; gamma not finite or not > 0, or
+ *    so small that 1.0f / gamma is not finite; white not finite or not > 0 under a Reinhard form; tone, transfer, quantise or out_format out
+ *    of range; dither > 1; out overlapping in (F32 in place too: one rule).
+ * What stays out: local tone mapping, bloom, a BGRA or 10-bit output, an exposure that stays on the device (the calls block, and the histogram
+ * is 1 KB).  There is no rtw_mgpu_* form and no JSON form. */
+enum { RTW_TONE_NONE = 0, RTW_TONE_REINHARD = 1, RTW_TONE_REINHARD_LUMA = 2, RTW_TONE_ACES_FIT = 3 };
+enum { RTW_TRANSFER_GAMMA = 0, RTW_TRANSFER_SRGB = 1 };
+enum { RTW_QUANTISE_RUST = 0, RTW_QUANTISE_RUST2 = 1 };
+enum { RTW_DISPLAY_RGB8 = 0, RTW_DISPLAY_RGBA8 = 1, RTW_DISPLAY_F32 = 2 };
+typedef struct RtwMetering {
+    uint32_t low_permille;    /* the share of the darkest counted pixels left out, in 1/1000                */
+    uint32_t high_permille;   /* ... and of the brightest; low + high < 1000                                */
+    float    key;             /* > 0: the luminance the metered level maps to (0.18: middle grey)           */
+    float    rate;            /* 0 .. 1: the step towards this frame's level; 1 = no adaptation             */
+    float    min_level;       /* the metered level is clamped to [min_level, max_level], in bins (0 .. 256) */
+    float    max_level;
+} RtwMetering;
+typedef struct RtwDisplay {
+    float    exposure;        /* >= 0, finite                                                               */
+    uint32_t tone;            /* RTW_TONE_*                                                                 */
+    float    white;           /* the Reinhard forms: the luminance that maps to 1                           */
+    uint32_t transfer;        /* RTW_TRANSFER_*                                                             */
+    float    gamma;           /* > 0, finite; read under RTW_TRANSFER_GAMMA, checked always                 */
+    uint32_t quantise;        /* RTW_QUANTISE_*                                                             */
+    uint32_t dither;          /* 0 or 1                                                                     */
+    uint32_t out_format;      /* RTW_DISPLAY_*                                                              */
+} RtwDisplay;
+/* The host forms (one thread).  RtwFilterStats: filter_ms and total_ms are the call's time, taps is w * h, the other fields are 0. */
+int rtw_luminance_histogram(const float *in, uint32_t w, uint32_t h, uint32_t *hist /* [256] */, uint32_t *counts /* [2] */,
+                            RtwFilterStats *stats);
+int rtw_exposure_from_histogram(const uint32_t *hist /* [256] */, const RtwMetering *metering, double prev_level /* NaN: a first frame */,
+                                float prev_exposure, double *level_out, float *exposure_out);
+int rtw_display(const float *in, uint32_t w, uint32_t h, const RtwDisplay *params, void *out, RtwFilterStats *stats);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host forms.  Every buffer may independently be host memory (staged through a
+ * scratch the context keeps) or device memory of ctx's GPU (used in place); filter_ms is the kernel's device time.  They need no scene.
+ * The histogram is a grid-stride loop of at most RTW_HISTOGRAM_BLOCKS_PER_CU workgroups a compute unit, each pass of a workgroup taking
+ * RTW_HISTOGRAM_BLOCK_PIXELS pixels, counted in LDS and added to a zeroed device buffer once per non-empty slot and workgroup
+ * (RTW_OPT_HISTOGRAM_COUNT chooses how the LDS counts are kept).  The display transform is one thread per four consecutive pixels.  Both read
+ * 16 bytes at a time when `in` is 16-byte aligned (and `out` 4-byte aligned for RGB8, 16-byte aligned for RGBA8 and F32) and pixel by pixel
+ * otherwise and for the last w * h % 4 pixels. */
+#define RTW_HISTOGRAM_BLOCKS_PER_CU 4u
+#define RTW_HISTOGRAM_BLOCK_PIXELS  1024u
+int rtw_ctx_luminance_histogram(rtw_ctx *ctx, const float *in, uint32_t w, uint32_t h, uint32_t *hist /* [256] */, uint32_t *counts /* [2] */,
+                                RtwFilterStats *stats);
+int rtw_ctx_display(rtw_ctx *ctx, const float *in, uint32_t w, uint32_t h, const RtwDisplay *params, void *out, RtwFilterStats *stats);
 
 /* ---- Rust2 triangles (Rust2/src/objects/triangle.rs) ----------------------------------------------------------------------------
  * `Triangle{origin, u, v, mat, texture}` with the derived fields of Triangle::new (:28-50): n = u x v, normal = unit(n),

@@ -62,6 +62,7 @@ OPT_MESH_CLIMB = 13                                   # how move_mesh_instances 
 OPT_MESH_LIST_MAX = 12                               # at most this many mesh placements: list order even under ACCEL_BVH; more: the top-level tree
 MESH_LIST_MAX_DEFAULT = 16                           # its default (csrc/rtw_kernels.h RTW_MESH_LIST_MAX_DEFAULT): the measured crossover, DESIGN.md 4.11
 OPT_GUIDED_LAYOUT = 10                               # Renderer.guided_filter: 0 by size, 1 table + guides in LDS, 2 guides, 3 table, 4 neither
+OPT_HISTOGRAM_COUNT = 15                             # Renderer.luminance_histogram's LDS counts: 0 the measured choice, 1 plain, 2 per wave, 3 ballot
 OPT_ATROUS_LAYOUT = 14                               # Renderer.atrous_filter: 0 the measured choice per level, 1 LDS tile where it fits, 2 global memory
 ATROUS_MAX_LEVELS = 8
 SCENE_C1, SCENE_C2, SCENE_C4, SCENE_C5, SCENE_METAL_TEST, SCENE_QUAD_TEST, SCENE_PRESENTATION, SCENE_FIRST_FRAME = 1, 2, 4, 5, 6, 7, 8, 9
@@ -96,6 +97,19 @@ UPSAMPLE_MAX_RADIUS = 2
 # The a-trous filter's own sigmas (depth 0.25, normal 0.3) lose there: they let taps across a silhouette through, whose demodulated colour
 # is wrong by the ratio of two albedos.
 UPSAMPLE_DEFAULTS = {"radius": 2, "sigma_depth": 0.0, "sigma_normal": 0.1, "same_object": True, "albedo_floor": ATROUS_DEFAULTS["albedo_floor"]}
+# The display stage (include/rtw.h "display stage")
+TONE_NONE, TONE_REINHARD, TONE_REINHARD_LUMA, TONE_ACES_FIT = 0, 1, 2, 3
+TRANSFER_GAMMA, TRANSFER_SRGB = 0, 1
+QUANTISE_RUST, QUANTISE_RUST2 = 0, 1
+DISPLAY_RGB8, DISPLAY_RGBA8, DISPLAY_F32 = 0, 1, 2
+HISTOGRAM_BLOCKS_PER_CU = 4                           # Renderer.luminance_histogram's grid: at most this many workgroups a compute unit,
+HISTOGRAM_BLOCK_PIXELS = 1024                         # each pass of a workgroup taking this many pixels
+# display's defaults: exposure 1, the ACES fit (it needs no white point), sRGB, write_img_f32's byte rule, no dither, RGB8.  A choice, not a
+# measurement: nothing here was tuned against anything.
+DISPLAY_DEFAULTS = {"exposure": 1.0, "tone": TONE_ACES_FIT, "white": 4.0, "transfer": TRANSFER_SRGB, "gamma": 2.2, "quantise": QUANTISE_RUST,
+                    "dither": False, "out_format": DISPLAY_RGB8}
+# exposure_from_histogram's defaults: the darkest and brightest 5 % left out, middle grey, no adaptation, every level allowed.
+METERING_DEFAULTS = {"low_permille": 50, "high_permille": 50, "key": 0.18, "rate": 1.0, "min_level": 0.0, "max_level": 256.0}
 
 # materials.rs:157-212 presets as (metallicness, opacity, ir)
 METALLIC_M = (1.0, 0.0, 1.0)
@@ -257,6 +271,19 @@ class RtwUpsample(C.Structure):
     (include/rtw.h)."""
     _fields_ = [("scale", C.c_uint32), ("radius", C.c_uint32), ("sigma_depth", C.c_float), ("sigma_normal", C.c_float),
                 ("same_object", C.c_uint32), ("albedo_floor", C.c_float)]
+
+
+class RtwMetering(C.Structure):
+    """Arguments of rtw_exposure_from_histogram: the shares cut at both ends, the key, the adaptation rate, the level's bounds (include/rtw.h)."""
+    _fields_ = [("low_permille", C.c_uint32), ("high_permille", C.c_uint32), ("key", C.c_float), ("rate", C.c_float),
+                ("min_level", C.c_float), ("max_level", C.c_float)]
+
+
+class RtwDisplay(C.Structure):
+    """Arguments of the display transform: exposure, tone curve and its white, transfer and its gamma, byte rule, dither, output format
+    (include/rtw.h)."""
+    _fields_ = [("exposure", C.c_float), ("tone", C.c_uint32), ("white", C.c_float), ("transfer", C.c_uint32), ("gamma", C.c_float),
+                ("quantise", C.c_uint32), ("dither", C.c_uint32), ("out_format", C.c_uint32)]
 
 
 class RtwFilterStats(C.Structure):
@@ -503,6 +530,11 @@ def lib() -> C.CDLL:
                                       C.POINTER(RtwUpsample), C.c_void_p, C.c_void_p, C.POINTER(RtwFilterStats)]
     L.rtw_ctx_upsample_filter.argtypes = [C.c_void_p] + L.rtw_upsample_filter.argtypes
     L.rtw_camera_scaled.argtypes = [C.POINTER(RtwCamera), C.c_uint32, C.POINTER(RtwCamera)]
+    L.rtw_luminance_histogram.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RtwFilterStats)]
+    L.rtw_ctx_luminance_histogram.argtypes = [C.c_void_p] + L.rtw_luminance_histogram.argtypes
+    L.rtw_exposure_from_histogram.argtypes = [C.c_void_p, C.POINTER(RtwMetering), C.c_double, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_float)]
+    L.rtw_display.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwDisplay), C.c_void_p, C.POINTER(RtwFilterStats)]
+    L.rtw_ctx_display.argtypes = [C.c_void_p] + L.rtw_display.argtypes
     L.rtw_ctx_scene_surface_tri.argtypes = L.rtw_ctx_scene_surface.argtypes[:-1] + [C.c_void_p] * 2 + [C.POINTER(RtwStats)]
     L.rtw_ctx_surface_map_tri.argtypes = L.rtw_ctx_surface_map.argtypes[:-1] + [C.c_void_p] * 2 + [C.POINTER(RtwStats)]
     L.rtw_tri_bary.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -2268,6 +2300,24 @@ class Renderer:
             out = np.power(np.maximum(out, np.float32(0.0)), np.float32(1.0 / gamma)).astype(np.float32)
         return out, st
 
+    def luminance_histogram(self, frame, out_hist=None, out_counts=None):
+        """The luminance histogram of a linear float32 frame [h][w][3] on this context's GPU (rtw_ctx_luminance_histogram, include/rtw.h):
+        eight bins a stop over 2^-16 .. 2^16 of Y = 0.2126 r + 0.7152 g + 0.0722 b, the black (Y <= 0) and the non-finite pixels counted
+        apart.  frame: a numpy array (staged) or a contiguous torch tensor on the context's device, read in place on the context's
+        stream.  out_hist (uint32 [256]) and out_counts (uint32 [2] = black, non_finite): None -> new arrays, or tensors like `frame` when
+        it is one (torch has no uint32: int32 tensors, whose bits are the counts); a numpy array or such an int32 tensor otherwise.
+        Returns (hist, counts, RtwFilterStats)."""
+        return _histogram_call(lib().rtw_ctx_luminance_histogram, "rtw_ctx_luminance_histogram", (self._h,), self._on_device, frame, out_hist,
+                               out_counts)
+
+    def display(self, frame, out=None, **params):
+        """The display transform of a linear float32 frame [h][w][3] on this context's GPU (rtw_ctx_display, include/rtw.h): exposure, tone
+        curve, clamp, transfer function, then bytes or float32.  params: DISPLAY_DEFAULTS' keys.  frame: a numpy array (staged) or a
+        contiguous torch tensor on the context's device, read in place on the context's stream.  out: None -> a new array, or a tensor when
+        `frame` is one; else a C-contiguous numpy array or a contiguous tensor on the device of [h][w][3] uint8 (DISPLAY_RGB8), [h][w][4]
+        uint8 (DISPLAY_RGBA8) or [h][w][3] float32 (DISPLAY_F32), which must not overlap `frame`.  Returns (out, RtwFilterStats)."""
+        return _display_call(lib().rtw_ctx_display, "rtw_ctx_display", (self._h,), self._on_device, frame, out, params)
+
     def variance_estimate(self, moments, length, depth=None, normal=None, ids=None, min_history: int = SVGF_DEFAULTS["min_history"],
                           radius: int = SVGF_DEFAULTS["radius"], sigma_depth: float = SVGF_DEFAULTS["sigma_depth"],
                           sigma_normal: float = SVGF_DEFAULTS["sigma_normal"], same_object: bool = True, out=None):
@@ -2719,6 +2769,148 @@ def upsample_filter(frame_lo, size, lo=None, hi=None, scale: int = 2, radius: in
     and result as there."""
     return _upsample_call(lib().rtw_upsample_filter, "rtw_upsample_filter", (), None, frame_lo, size, lo, hi, scale, radius, sigma_depth,
                           sigma_normal, same_object, albedo_floor, out, out_wsum)
+
+
+def _display_pointer(who, name, a, np_dtype, shape, on_device, keep, writable):
+    """The pointer of one display-stage argument of any of the dtypes float32, uint8, uint32 (a tensor: int32): a torch tensor on the
+    context's device, in place; a numpy array, shape-checked."""
+    if hasattr(a, "data_ptr"):
+        import torch
+        tdt = {np.float32: torch.float32, np.uint8: torch.uint8, np.uint32: torch.int32}[np_dtype]
+        if on_device is None or not on_device(a, tdt) or tuple(a.shape) != shape:
+            raise ValueError(f"{who}: {name} must be a contiguous {tdt} tensor of shape {shape} on the context's device")
+        keep.append(a)
+        return C.c_void_p(int(a.data_ptr()))
+    if writable:
+        if not (isinstance(a, np.ndarray) and a.dtype == np_dtype and a.flags["C_CONTIGUOUS"] and a.shape == shape):
+            raise ValueError(f"{who}: {name} must be a C-contiguous {np.dtype(np_dtype).name} array of shape {shape}")
+        return C.c_void_p(a.ctypes.data)
+    b = np.ascontiguousarray(a, np_dtype)
+    if b.shape != shape:
+        raise ValueError(f"{who}: {name} of shape {b.shape}, expected {shape}")
+    keep.append(b)
+    return C.c_void_p(b.ctypes.data)
+
+
+def _frame_size(who, frame):
+    shp = tuple(frame.shape) if hasattr(frame, "shape") else np.shape(frame)
+    if len(shp) != 3 or shp[2] != 3:
+        raise ValueError(f"{who}: frame of shape {shp}, expected [h][w][3]")
+    return int(shp[0]), int(shp[1])
+
+
+def _new_like(a, shape, np_dtype):
+    """A new array of `shape`, or a tensor on a's device when `a` is a tensor (uint32 as int32 there)."""
+    if hasattr(a, "data_ptr"):
+        import torch
+        return torch.empty(shape, dtype={np.float32: torch.float32, np.uint8: torch.uint8, np.uint32: torch.int32}[np_dtype], device=a.device)
+    return np.empty(shape, np_dtype)
+
+
+def _histogram_call(fn, fn_name, head, on_device, frame, out_hist, out_counts):
+    """rtw_luminance_histogram / rtw_ctx_luminance_histogram from the Python arguments of luminance_histogram: (hist, counts, stats)."""
+    who = "luminance_histogram"
+    h, w = _frame_size(who, frame)
+    keep = []
+    out_hist = _new_like(frame, (256,), np.uint32) if out_hist is None else out_hist
+    out_counts = _new_like(frame, (2,), np.uint32) if out_counts is None else out_counts
+    st = RtwFilterStats()
+    _check(fn(*head, _display_pointer(who, "frame", frame, np.float32, (h, w, 3), on_device, keep, False), w, h,
+              _display_pointer(who, "out_hist", out_hist, np.uint32, (256,), on_device, keep, True),
+              _display_pointer(who, "out_counts", out_counts, np.uint32, (2,), on_device, keep, True), C.byref(st)), fn_name)
+    return out_hist, out_counts, st
+
+
+def luminance_histogram(frame, out_hist=None, out_counts=None):
+    """The luminance histogram on the host (rtw_luminance_histogram), the counts of Renderer.luminance_histogram; numpy arrays only.
+    Arguments and result as there."""
+    return _histogram_call(lib().rtw_luminance_histogram, "rtw_luminance_histogram", (), None, frame, out_hist, out_counts)
+
+
+def exposure_from_histogram(hist, prev_level=None, prev_exposure: float = 1.0, **metering):
+    """The exposure a luminance histogram meters to (rtw_exposure_from_histogram, include/rtw.h; host only, double arithmetic): the mean bin
+    position of the counted pixels between the low_permille darkest and the high_permille brightest, clamped to [min_level, max_level],
+    moved from prev_level by `rate` (None or NaN: a first frame, no adaptation), and the exposure that maps the luminance of that level to
+    `key`.  metering: METERING_DEFAULTS' keys.  hist: uint32 [256] (an int32 tensor as Renderer.luminance_histogram returns it is copied to
+    the host).  With nothing counted the level is prev_level and the exposure prev_exposure (1 on a first frame).
+    Returns (level: float, exposure: float, exactly a float32)."""
+    unknown = set(metering) - set(METERING_DEFAULTS)
+    if unknown:
+        raise TypeError(f"exposure_from_histogram: unknown arguments {sorted(unknown)}")
+    m = dict(METERING_DEFAULTS, **metering)
+    if hasattr(hist, "data_ptr"):
+        hist = hist.cpu().numpy().view(np.uint32)
+    hh = np.ascontiguousarray(hist, np.uint32)
+    if hh.shape != (256,):
+        raise ValueError(f"exposure_from_histogram: hist of shape {hh.shape}, expected (256,)")
+    prm = RtwMetering(int(m["low_permille"]), int(m["high_permille"]), float(m["key"]), float(m["rate"]), float(m["min_level"]), float(m["max_level"]))
+    level, exposure = C.c_double(), C.c_float()
+    _check(lib().rtw_exposure_from_histogram(hh.ctypes.data, C.byref(prm), float("nan") if prev_level is None else float(prev_level),
+                                             float(prev_exposure), C.byref(level), C.byref(exposure)), "rtw_exposure_from_histogram")
+    return level.value, exposure.value
+
+
+def _display_params(params) -> RtwDisplay:
+    unknown = set(params) - set(DISPLAY_DEFAULTS)
+    if unknown:
+        raise TypeError(f"display: unknown arguments {sorted(unknown)}")
+    d = dict(DISPLAY_DEFAULTS, **params)
+    return RtwDisplay(float(d["exposure"]), int(d["tone"]), float(d["white"]), int(d["transfer"]), float(d["gamma"]), int(d["quantise"]),
+                      int(d["dither"]), int(d["out_format"]))
+
+
+def _display_call(fn, fn_name, head, on_device, frame, out, params):
+    """rtw_display / rtw_ctx_display from the Python arguments of display: (out, stats)."""
+    who = "display"
+    h, w = _frame_size(who, frame)
+    prm = _display_params(params)
+    if prm.out_format not in (DISPLAY_RGB8, DISPLAY_RGBA8, DISPLAY_F32):
+        raise ValueError(f"{who}: out_format {prm.out_format}")
+    shape, dt = {DISPLAY_RGB8: ((h, w, 3), np.uint8), DISPLAY_RGBA8: ((h, w, 4), np.uint8), DISPLAY_F32: ((h, w, 3), np.float32)}[prm.out_format]
+    keep = []
+    if out is None:
+        out = _new_like(frame, shape, dt)
+    st = RtwFilterStats()
+    _check(fn(*head, _display_pointer(who, "frame", frame, np.float32, (h, w, 3), on_device, keep, False), w, h, C.byref(prm),
+              _display_pointer(who, "out", out, dt, shape, on_device, keep, True), C.byref(st)), fn_name)
+    return out, st
+
+
+def display(frame, out=None, **params):
+    """The display transform on the host (rtw_display), the bytes of Renderer.display; numpy arrays only.  Arguments and result as there."""
+    return _display_call(lib().rtw_display, "rtw_display", (), None, frame, out, params)
+
+
+class DisplayTransform:
+    """Python only: the display stage of a sequence.  step(frame) takes the frame's luminance histogram on the renderer's GPU, meters an
+    exposure from it (adapting from the level of the step before by metering's `rate`) and runs the display transform with that exposure.
+    params: DISPLAY_DEFAULTS' keys but for exposure, which is metered, and METERING_DEFAULTS' keys."""
+
+    def __init__(self, renderer, **params):
+        if "exposure" in params:
+            raise TypeError("DisplayTransform: the exposure is metered; call Renderer.display for a fixed one")
+        unknown = set(params) - set(DISPLAY_DEFAULTS) - set(METERING_DEFAULTS)
+        if unknown:
+            raise TypeError(f"DisplayTransform: unknown arguments {sorted(unknown)}")
+        self.renderer = renderer
+        self.metering = {k: v for k, v in params.items() if k in METERING_DEFAULTS}
+        self.params = {k: v for k, v in params.items() if k in DISPLAY_DEFAULTS}
+        self.reset()
+
+    def reset(self):
+        """Forget the level: the next step meters as a first frame."""
+        self.level, self.exposure = None, 1.0
+
+    def step(self, frame, out=None):
+        """Returns (out, level, exposure, stats): Renderer.display's result for the metered exposure, the level and exposure now kept, and a
+        dict of hist, counts and the two RtwFilterStats (histogram, display)."""
+        r = self.renderer
+        hist, counts, st_h = r.luminance_histogram(frame)
+        self.level, self.exposure = exposure_from_histogram(hist, prev_level=self.level, prev_exposure=self.exposure, **self.metering)
+        if self.level != self.level:               # nothing counted on a first frame: still a first frame
+            self.level = None
+        out, st_d = r.display(frame, out=out, exposure=self.exposure, **self.params)
+        return out, self.level, self.exposure, dict(hist=hist, counts=counts, histogram=st_h, display=st_d)
 
 
 def _scaled_view(cam: RtwCamera, params: RtwParams, scale: int):

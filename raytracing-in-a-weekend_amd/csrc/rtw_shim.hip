@@ -12,6 +12,7 @@
 #include "rtw_svgf_dev.h"
 #include "rtw_bounds_dev.h"
 #include "rtw_upsample_dev.h"
+#include "rtw_display_dev.h"
 #include "rtw_devmem.h"
 #include "rtw_exp.h"
 #include "rtw_probe.h"
@@ -108,6 +109,7 @@ struct rtw_ctx {
                                          // (rtw_svgf.hip), created on the first call of any of them
     BoundsScratch *bounds = nullptr;     // buffers of rtw_ctx_colour_bounds (rtw_bounds.hip), created on its first call
     UpsampleScratch *upsample = nullptr; // buffers of rtw_ctx_upsample_filter (rtw_upsample.hip), created on its first call
+    DisplayScratch *display = nullptr;   // buffers of rtw_ctx_luminance_histogram and rtw_ctx_display (rtw_display.hip), created on their first call
     TemporalScratch *temporal = nullptr; // buffers of rtw_ctx_temporal_accumulate (rtw_temporal.hip), created on its first call
     FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
     MotionMem motion_mem;                // buffers of rtw_ctx_mesh_instance_motion
@@ -163,6 +165,7 @@ struct rtw_ctx {
     double opt_tail_units = 0.0;         // RTW_OPT_TAIL_UNITS: blocks of short units per resident wave at the end of the queue (render_enqueue); 0 = off.
                                          // OFF by default: measured, it does not shorten a launch (profiles/r03_tail_units.log, r03_endtimes.log)
     uint32_t opt_guided_layout = 0;      // RTW_OPT_GUIDED_LAYOUT: where rtw_ctx_guided_filter keeps its table and guide tile (0 = by size)
+    uint32_t opt_histogram_count = 0;    // RTW_OPT_HISTOGRAM_COUNT: how rtw_ctx_luminance_histogram keeps its LDS counts (0 = the measured choice)
     uint32_t opt_atrous_layout = 0;      // RTW_OPT_ATROUS_LAYOUT: where a level of rtw_ctx_atrous_filter reads its taps (0 = the measured choice)
     uint32_t opt_node_format = 0;        // RTW_OPT_NODE_FORMAT: 0 = f32 planes where a build walks them and two of its workgroups fit a CU's LDS, 1 = f16, 2 = f32
     uint32_t opt_grab_blocks = 2;        // RTW_OPT_GRAB_BLOCKS (profiles/r02_grab_sweep.log: 1 / 2 / 4 / 8 / a tile's 42 blocks = 83.9 / 82.9 / 83.7 / 86.8 / 107.9 ms on the bench frame)
@@ -538,6 +541,7 @@ void rtw_ctx_destroy(rtw_ctx *c) {
     temporal_scratch_free(c->temporal);
     bounds_scratch_free(c->bounds);
     upsample_scratch_free(c->upsample);
+    display_scratch_free(c->display);
     if (c->ev_mark) (void)hipEventDestroy(c->ev_mark);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1640,6 +1644,19 @@ int rtw_ctx_upsample_filter(rtw_ctx *c, const float *lo, uint32_t w_lo, uint32_t
                                   wsum_out, stats, &g_last_hip);
 }
 
+// The display stage (rtw_display.hip) likewise, on a scratch of its own.
+int rtw_ctx_luminance_histogram(rtw_ctx *c, const float *in, uint32_t w, uint32_t h, uint32_t *hist, uint32_t *counts, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return luminance_histogram_device(c->device, c->stream, &c->display, c->opt_histogram_count, in, w, h, hist, counts, stats, &g_last_hip);
+}
+
+int rtw_ctx_display(rtw_ctx *c, const float *in, uint32_t w, uint32_t h, const RtwDisplay *p, void *out, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return display_device(c->device, c->stream, &c->display, in, w, h, p, out, stats, &g_last_hip);
+}
+
 // The device-math probe (rtw_probe.hip, rtw.h "device math, for tests") on this context's GPU and stream; the scene is not involved.
 int rtw_ctx_device_math(rtw_ctx *c, uint32_t fn, const float *in, uint32_t n_cols, uint32_t n, float *out, uint32_t out_cols) {
     if (!c) return RTW_E_INVALID;
@@ -2168,6 +2185,7 @@ int rtw_ctx_set_option(rtw_ctx *c, uint32_t key, double v) {
     case RTW_OPT_TAIL_UNITS:     if (!(v >= 0.0 && v <= 1024.0)) return RTW_E_INVALID; c->opt_tail_units = v; return RTW_OK;
     case RTW_OPT_GUIDED_LAYOUT:  if (!(v >= 0.0 && v <= 4.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_guided_layout = (uint32_t)v; return RTW_OK;
     case RTW_OPT_ATROUS_LAYOUT:  if (!(v == 0.0 || v == 1.0 || v == 2.0)) return RTW_E_INVALID; c->opt_atrous_layout = (uint32_t)v; return RTW_OK;
+    case RTW_OPT_HISTOGRAM_COUNT: if (!(v == 0.0 || v == 1.0 || v == 2.0 || v == 3.0)) return RTW_E_INVALID; c->opt_histogram_count = (uint32_t)v; return RTW_OK;
     case RTW_OPT_GRAB_BLOCKS:    if (!(v >= 0.0 && v <= 65536.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_grab_blocks = (uint32_t)v; return RTW_OK;
     case RTW_OPT_MESH_LIST_MAX:  if (!(v >= 0.0 && v <= 4294967295.0 && v == (double)(uint32_t)v)) return RTW_E_INVALID; c->opt_mesh_list_max = (uint32_t)v; return RTW_OK;
     case RTW_OPT_MESH_CLIMB:     if (!(v == 0.0 || v == 1.0 || v == 2.0)) return RTW_E_INVALID; c->opt_mesh_climb = (uint32_t)v; return RTW_OK;
