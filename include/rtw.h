@@ -326,7 +326,8 @@ enum {
                                      (DESIGN.md 8c); 1 from an LDS tile of the workgroup's pixels and their halo wherever that tile fits; 2 from
                                      global memory.  The bytes are the same.  Any other value: RTW_E_INVALID.  (added within v4)
                                      rtw_ctx_svgf_filter's levels and rtw_ctx_variance_estimate's window follow it too, and
-                                     so do rtw_ctx_colour_bounds' window (8h) and rtw_ctx_upsample_filter's low window (8i).              */
+                                     so do rtw_ctx_colour_bounds' window (8h) and rtw_ctx_upsample_filter's low window (8i), and every
+                                     step of rtw_ctx_bloom (8k: 0 = the measured choice per kernel and level size).                       */
     RTW_OPT_HISTOGRAM_COUNT  = 15,/* how a workgroup of rtw_ctx_luminance_histogram keeps its LDS counts: 0 (default) the measured choice
                                      (DESIGN.md 8j); 1 one LDS histogram, one LDS atomic a pixel; 2 one LDS histogram a wave, summed at the
                                      end; 3 one LDS histogram, the lanes of a wave that share the first active lane's slot added as one
@@ -1013,7 +1014,7 @@ int rtw_camera_scaled(const RtwCamera *cam, uint32_t scale, RtwCamera *out);
  *    RTW_E_INVALID, nothing written: in, params or out NULL; sizes as above; exposure not finite or negative; gamma not finite or not > 0, or
  *    so small that 1.0f / gamma is not finite; white not finite or not > 0 under a Reinhard form; tone, transfer, quantise or out_format out
  *    of range; dither > 1; out overlapping in (F32 in place too: one rule).
- * What stays out: local tone mapping, bloom, a BGRA or 10-bit output, an exposure that stays on the device (the calls block, and the histogram
+ * What stays out: local tone mapping, a BGRA or 10-bit output, an exposure that stays on the device (the calls block, and the histogram
  * is 1 KB).  There is no rtw_mgpu_* form and no JSON form. */
 enum { RTW_TONE_NONE = 0, RTW_TONE_REINHARD = 1, RTW_TONE_REINHARD_LUMA = 2, RTW_TONE_ACES_FIT = 3 };
 enum { RTW_TRANSFER_GAMMA = 0, RTW_TRANSFER_SRGB = 1 };
@@ -1055,6 +1056,73 @@ int rtw_display(const float *in, uint32_t w, uint32_t h, const RtwDisplay *param
 int rtw_ctx_luminance_histogram(rtw_ctx *ctx, const float *in, uint32_t w, uint32_t h, uint32_t *hist /* [256] */, uint32_t *counts /* [2] */,
                                 RtwFilterStats *stats);
 int rtw_ctx_display(rtw_ctx *ctx, const float *in, uint32_t w, uint32_t h, const RtwDisplay *params, void *out, RtwFilterStats *stats);
+
+/* ---- bloom: bright pass, dual-filter pyramid, composite -- added within v4 ------------------------------------------------------------------
+ * The glare of what is far above 1, on the linear f32 frame [h][w][3] in front of the display stage: a neighbourhood operation, where the
+ * display transform is a function of one pixel.  Everything is f32 with one rounding per written operation (no fused multiply-add), divides
+ * correctly rounded, no elementary function; sums run in the written order.
+ *
+ * Sizes.  Level 0 is the frame.  Level l + 1 has w' = (w_l + 1) / 2, h' = (h_l + 1) / 2; its pixel (I, J) sits over pixels 2I, 2I + 1 by
+ * 2J, 2J + 1 of level l.  A call asks for `levels` in 1 .. RTW_BLOOM_MAX_LEVELS; the chain stops early at the first level that is 1 x 1.
+ * rtw_bloom_levels (host only, pure) returns the number n of levels used and, when sizes is not NULL, w and h of levels 1 .. n; 0 for a w or
+ * h of zero or levels outside 1 .. RTW_BLOOM_MAX_LEVELS.
+ *
+ * Bright pass, per pixel x = (r, g, b) of level 0:
+ *      usable:  all three channels finite       (a pixel that is not usable is a tap of weight 0: a NaN or an infinity never spreads)
+ *      x_c = x_c < 0 ? 0 : x_c
+ *      Y = (0.2126f * x_r + 0.7152f * x_g) + 0.0722f * x_b                                      (the display stage's luminance)
+ *      s = Y - threshold
+ *      c = (knee > 0 && s > -knee && s < knee) ? ((s + knee) * (s + knee)) / (4.0f * knee) : (s > 0 ? s : 0)
+ *      b_c = Y > 0 ? x_c * (c / Y) : 0
+ *      kw  = karis ? 1.0f / (1.0f + ((0.2126f * b_r + 0.7152f * b_g) + 0.0722f * b_b)) : 1.0f
+ *    The quadratic meets max(s, 0) at both ends of the knee; with knee <= threshold c <= Y up to rounding, so b is finite whenever x is and Y
+ *    did not overflow.  kw is the Karis weight: it keeps one firefly from becoming a disc.
+ *
+ * Down, level l to l + 1, pixel (I, J): the taps are the pixels (2I + a, 2J + b) of level l, a, b = -2 .. 3, b the outer loop; a tap
+ * outside level l is skipped.  D[b + 2][a + 2] is
+ *        1 1 2 2 1 1 / 1 5 6 6 5 1 / 2 6 8 8 6 2 / 2 6 8 8 6 2 / 1 5 6 6 5 1 / 1 1 2 2 1 1                       (sum 128)
+ * -- the 13-tap downsample of Jimenez (SIGGRAPH 2014), a centre box at 1/2 and four corner boxes at 1/8 of bilinear fetches at pixel corners,
+ * as the 36 pixel weights it amounts to.
+ *      wt = (D / 128.0f) * kw            (kw of the tap in the first step, where a tap that is not usable adds nothing; 1.0f afterwards)
+ *      sum_c = sum_c + v_c * wt;  wsum = wsum + wt            (v = b of the bright pass in the first step, the level's pixel afterwards)
+ *      level[l + 1][(I, J)] = wsum > 0 ? sum / wsum : 0
+ *    The first step applies the bright pass to each tap as it reads it: no thresholded frame is ever stored.
+ *
+ * Up, in place over the down chain, from the last level to level 1:   level[l][p] = level[l][p] + spread * U(level[l + 1], p).
+ * U at pixel (i, j) of the finer level:  N = 2i - 1,  I0 = floor(N / 4) (-1 at i = 0),  r = N - 4 I0 (1 or 3);  the columns are I0 - 1 + k,
+ * k = 0 .. 3, weighted wx = {3, 7, 5, 1} when r == 1 and {1, 5, 7, 3} when r == 3;  the rows likewise from j;
+ *      wt = (float)(wx[kx] * wy[ky]) / 256.0f,  rows outer, columns inner;  a tap outside the coarser level is skipped;  U = sum / wsum
+ *    -- a 3 x 3 tent on the coarse level, then the bilinear fetch at the fine pixel's centre, multiplied out.  wsum > 0 always.
+ *
+ * Composite:  B = U(level[1], p) at level 0;  out[p][c] = in[p][c] + intensity * B_c;  layer_out[p][c] = B_c when layer_out is given.  A pixel
+ * of `in` that is not finite passes through by the arithmetic.  out may be in.
+ *
+ * RTW_E_INVALID, nothing written: in, out or params NULL; w or h zero or beyond RTW_ATROUS_MAX_SIDE, or w * h beyond 32 bits; levels outside
+ * 1 .. RTW_BLOOM_MAX_LEVELS; threshold, knee, spread or intensity negative or not finite; knee > threshold; karis > 1; layer_out overlapping
+ * in or out; out overlapping in other than being equal to it.
+ * The rule is total: finite channels so large that a sum or Y rounds to an infinity give what the arithmetic above gives.
+ * What stays out: one workgroup for the tail of small levels, lens dirt and anamorphic streaks, a threshold that follows the exposure on the
+ * device, threads in the host form.  There is no rtw_mgpu_* form and no JSON form. */
+#define RTW_BLOOM_MAX_LEVELS 8u
+typedef struct RtwBloom {
+    uint32_t levels;          /* 1 .. RTW_BLOOM_MAX_LEVELS                                                  */
+    float    threshold;       /* >= 0, finite: the luminance where the bright pass opens                    */
+    float    knee;            /* 0 .. threshold: the half-width of the quadratic around it                  */
+    uint32_t karis;           /* 0 or 1: the first down step weights a tap by 1 / (1 + its luminance)       */
+    float    spread;          /* >= 0, finite: what a level takes of the coarser one on the way up          */
+    float    intensity;       /* >= 0, finite: what the frame takes of the layer                            */
+} RtwBloom;
+uint32_t rtw_bloom_levels(uint32_t w, uint32_t h, uint32_t levels, uint32_t *sizes /* [2 * RTW_BLOOM_MAX_LEVELS]: w, h of levels 1 .. n; may be NULL */);
+/* The host form (one thread, a pyramid of its own).  RtwFilterStats: filter_ms and total_ms are the call's time, taps counts the taps inside
+ * their level over all steps, the other fields are 0. */
+int rtw_bloom(const float *in, uint32_t w, uint32_t h, const RtwBloom *params, float *out, float *layer_out /* may be NULL */,
+              RtwFilterStats *stats);
+/* On ctx's GPU, on its stream, blocking; the bytes of the host form.  Every buffer may independently be host memory (staged) or device memory
+ * of ctx's GPU (used in place); the pyramid is a scratch the context keeps.  2 n launches for n levels used, one thread per output pixel in
+ * workgroups of 16 x 16, each reading its source window from an LDS tile or from global memory (RTW_OPT_ATROUS_LAYOUT); filter_ms is the
+ * device time from before the first launch to after the last.  Needs no scene. */
+int rtw_ctx_bloom(rtw_ctx *ctx, const float *in, uint32_t w, uint32_t h, const RtwBloom *params, float *out, float *layer_out /* may be NULL */,
+                  RtwFilterStats *stats);
 
 /* ---- Rust2 triangles (Rust2/src/objects/triangle.rs) ----------------------------------------------------------------------------
  * `Triangle{origin, u, v, mat, texture}` with the derived fields of Triangle::new (:28-50): n = u x v, normal = unit(n),

@@ -110,6 +110,11 @@ DISPLAY_DEFAULTS = {"exposure": 1.0, "tone": TONE_ACES_FIT, "white": 4.0, "trans
                     "dither": False, "out_format": DISPLAY_RGB8}
 # exposure_from_histogram's defaults: the darkest and brightest 5 % left out, middle grey, no adaptation, every level allowed.
 METERING_DEFAULTS = {"low_permille": 50, "high_permille": 50, "key": 0.18, "rate": 1.0, "min_level": 0.0, "max_level": 256.0}
+# Bloom (include/rtw.h "bloom")
+BLOOM_MAX_LEVELS = 8
+# bloom's defaults: six levels, the bright pass opening at luminance 1 with a knee of a half, the Karis weight on, a half of each coarser
+# level on the way up, a quarter of the layer on the frame.  Choices, not measurements: nothing here was tuned against anything.
+BLOOM_DEFAULTS = {"levels": 6, "threshold": 1.0, "knee": 0.5, "karis": True, "spread": 0.5, "intensity": 0.25}
 
 # materials.rs:157-212 presets as (metallicness, opacity, ir)
 METALLIC_M = (1.0, 0.0, 1.0)
@@ -284,6 +289,12 @@ class RtwDisplay(C.Structure):
     (include/rtw.h)."""
     _fields_ = [("exposure", C.c_float), ("tone", C.c_uint32), ("white", C.c_float), ("transfer", C.c_uint32), ("gamma", C.c_float),
                 ("quantise", C.c_uint32), ("dither", C.c_uint32), ("out_format", C.c_uint32)]
+
+
+class RtwBloom(C.Structure):
+    """Arguments of bloom: levels asked for, the bright pass's threshold and knee, the Karis weight, spread, intensity (include/rtw.h)."""
+    _fields_ = [("levels", C.c_uint32), ("threshold", C.c_float), ("knee", C.c_float), ("karis", C.c_uint32), ("spread", C.c_float),
+                ("intensity", C.c_float)]
 
 
 class RtwFilterStats(C.Structure):
@@ -535,6 +546,10 @@ def lib() -> C.CDLL:
     L.rtw_exposure_from_histogram.argtypes = [C.c_void_p, C.POINTER(RtwMetering), C.c_double, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_float)]
     L.rtw_display.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwDisplay), C.c_void_p, C.POINTER(RtwFilterStats)]
     L.rtw_ctx_display.argtypes = [C.c_void_p] + L.rtw_display.argtypes
+    L.rtw_bloom_levels.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.rtw_bloom_levels.restype = C.c_uint32
+    L.rtw_bloom.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtwBloom), C.c_void_p, C.c_void_p, C.POINTER(RtwFilterStats)]
+    L.rtw_ctx_bloom.argtypes = [C.c_void_p] + L.rtw_bloom.argtypes
     L.rtw_ctx_scene_surface_tri.argtypes = L.rtw_ctx_scene_surface.argtypes[:-1] + [C.c_void_p] * 2 + [C.POINTER(RtwStats)]
     L.rtw_ctx_surface_map_tri.argtypes = L.rtw_ctx_surface_map.argtypes[:-1] + [C.c_void_p] * 2 + [C.POINTER(RtwStats)]
     L.rtw_tri_bary.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -2318,6 +2333,16 @@ class Renderer:
         uint8 (DISPLAY_RGBA8) or [h][w][3] float32 (DISPLAY_F32), which must not overlap `frame`.  Returns (out, RtwFilterStats)."""
         return _display_call(lib().rtw_ctx_display, "rtw_ctx_display", (self._h,), self._on_device, frame, out, params)
 
+    def bloom(self, frame, out=None, layer=False, **params):
+        """Bloom of a linear float32 frame [h][w][3] on this context's GPU (rtw_ctx_bloom, include/rtw.h): a bright pass (threshold, knee,
+        the Karis weight), a pyramid of `levels` 13-tap down steps and tent up steps (spread), and out = frame + intensity * layer.
+        params: BLOOM_DEFAULTS' keys.  frame: a numpy array (staged) or a contiguous torch tensor on the context's device, read in place
+        on the context's stream.  out: None -> a new array, or a tensor when `frame` is one; else a C-contiguous numpy array or a
+        contiguous tensor on the device of [h][w][3] float32, which may be `frame` itself and must not overlap it otherwise.  layer:
+        False -> no layer; True -> a new array or tensor like `frame`; else such a buffer, overlapping neither.
+        Returns (out, layer or None, RtwFilterStats)."""
+        return _bloom_call(lib().rtw_ctx_bloom, "rtw_ctx_bloom", (self._h,), self._on_device, frame, out, layer, params)
+
     def variance_estimate(self, moments, length, depth=None, normal=None, ids=None, min_history: int = SVGF_DEFAULTS["min_history"],
                           radius: int = SVGF_DEFAULTS["radius"], sigma_depth: float = SVGF_DEFAULTS["sigma_depth"],
                           sigma_normal: float = SVGF_DEFAULTS["sigma_normal"], same_object: bool = True, out=None):
@@ -2881,12 +2906,59 @@ def display(frame, out=None, **params):
     return _display_call(lib().rtw_display, "rtw_display", (), None, frame, out, params)
 
 
+def bloom_levels(w: int, h: int, levels: int):
+    """The levels a bloom call of `levels` uses on a w x h frame (rtw_bloom_levels): [(w, h) of level 1, ...]; the chain stops early at the
+    first 1 x 1 level."""
+    sizes = (C.c_uint32 * (2 * BLOOM_MAX_LEVELS))()
+    n = lib().rtw_bloom_levels(int(w), int(h), int(levels), sizes)
+    if n == 0:
+        raise ValueError(f"bloom_levels: w {w}, h {h}, levels {levels}")
+    return [(int(sizes[2 * l]), int(sizes[2 * l + 1])) for l in range(n)]
+
+
+def _bloom_params(params) -> RtwBloom:
+    unknown = set(params) - set(BLOOM_DEFAULTS)
+    if unknown:
+        raise TypeError(f"bloom: unknown arguments {sorted(unknown)}")
+    d = dict(BLOOM_DEFAULTS, **params)
+    return RtwBloom(int(d["levels"]), float(d["threshold"]), float(d["knee"]), int(d["karis"]), float(d["spread"]), float(d["intensity"]))
+
+
+def _bloom_call(fn, fn_name, head, on_device, frame, out, layer, params):
+    """rtw_bloom / rtw_ctx_bloom from the Python arguments of bloom: (out, layer or None, stats)."""
+    who = "bloom"
+    h, w = _frame_size(who, frame)
+    prm = _bloom_params(params)
+    keep = []
+    if out is None:
+        out = _new_like(frame, (h, w, 3), np.float32)
+    if layer is True:
+        layer = _new_like(frame, (h, w, 3), np.float32)
+    elif layer is False:
+        layer = None
+    # `out is frame`: one pointer for both (a numpy frame is otherwise read through a contiguous float32 copy)
+    p_out = _display_pointer(who, "out", out, np.float32, (h, w, 3), on_device, keep, True)
+    p_in = p_out if out is frame else _display_pointer(who, "frame", frame, np.float32, (h, w, 3), on_device, keep, False)
+    p_layer = None if layer is None else _display_pointer(who, "layer", layer, np.float32, (h, w, 3), on_device, keep, True)
+    st = RtwFilterStats()
+    _check(fn(*head, p_in, w, h, C.byref(prm), p_out, p_layer, C.byref(st)), fn_name)
+    return out, layer, st
+
+
+def bloom(frame, out=None, layer=False, **params):
+    """Bloom on the host (rtw_bloom), the bytes of Renderer.bloom; numpy arrays only.  Arguments and result as there."""
+    return _bloom_call(lib().rtw_bloom, "rtw_bloom", (), None, frame, out, layer, params)
+
+
 class DisplayTransform:
     """Python only: the display stage of a sequence.  step(frame) takes the frame's luminance histogram on the renderer's GPU, meters an
     exposure from it (adapting from the level of the step before by metering's `rate`) and runs the display transform with that exposure.
-    params: DISPLAY_DEFAULTS' keys but for exposure, which is metered, and METERING_DEFAULTS' keys."""
+    params: DISPLAY_DEFAULTS' keys but for exposure, which is metered, and METERING_DEFAULTS' keys.  bloom: None, or a dict of
+    BLOOM_DEFAULTS' keys: step then runs Renderer.bloom between metering and display, with `threshold` and `knee` divided by the metered
+    exposure as float32 (they are in exposed units), and displays its result.  The bloomed frame is a new frame-sized array or tensor on
+    every step (no buffer is kept between steps); an exposure so small that the divided threshold is not finite is a ValueError."""
 
-    def __init__(self, renderer, **params):
+    def __init__(self, renderer, bloom=None, **params):
         if "exposure" in params:
             raise TypeError("DisplayTransform: the exposure is metered; call Renderer.display for a fixed one")
         unknown = set(params) - set(DISPLAY_DEFAULTS) - set(METERING_DEFAULTS)
@@ -2895,6 +2967,12 @@ class DisplayTransform:
         self.renderer = renderer
         self.metering = {k: v for k, v in params.items() if k in METERING_DEFAULTS}
         self.params = {k: v for k, v in params.items() if k in DISPLAY_DEFAULTS}
+        if bloom is not None:
+            unknown = set(bloom) - set(BLOOM_DEFAULTS)
+            if unknown:
+                raise TypeError(f"DisplayTransform: unknown bloom arguments {sorted(unknown)}")
+            bloom = dict(BLOOM_DEFAULTS, **bloom)
+        self.bloom = bloom
         self.reset()
 
     def reset(self):
@@ -2903,14 +2981,23 @@ class DisplayTransform:
 
     def step(self, frame, out=None):
         """Returns (out, level, exposure, stats): Renderer.display's result for the metered exposure, the level and exposure now kept, and a
-        dict of hist, counts and the two RtwFilterStats (histogram, display)."""
+        dict of hist, counts and the two RtwFilterStats (histogram, display); with bloom its RtwFilterStats (bloom) too."""
         r = self.renderer
         hist, counts, st_h = r.luminance_histogram(frame)
         self.level, self.exposure = exposure_from_histogram(hist, prev_level=self.level, prev_exposure=self.exposure, **self.metering)
         if self.level != self.level:               # nothing counted on a first frame: still a first frame
             self.level = None
+        stats = dict(hist=hist, counts=counts, histogram=st_h)
+        if self.bloom is not None:
+            e = np.float32(self.exposure)
+            with np.errstate(all="ignore"):
+                b = dict(self.bloom, threshold=float(np.float32(self.bloom["threshold"]) / e), knee=float(np.float32(self.bloom["knee"]) / e))
+            if not (np.isfinite(b["threshold"]) and np.isfinite(b["knee"])):
+                raise ValueError(f"DisplayTransform: the metered exposure {self.exposure} is too small for bloom's threshold in exposed units")
+            frame, _, stats["bloom"] = r.bloom(frame, **b)
         out, st_d = r.display(frame, out=out, exposure=self.exposure, **self.params)
-        return out, self.level, self.exposure, dict(hist=hist, counts=counts, histogram=st_h, display=st_d)
+        stats["display"] = st_d
+        return out, self.level, self.exposure, stats
 
 
 def _scaled_view(cam: RtwCamera, params: RtwParams, scale: int):

@@ -13,6 +13,7 @@
 #include "rtw_bounds_dev.h"
 #include "rtw_upsample_dev.h"
 #include "rtw_display_dev.h"
+#include "rtw_bloom_dev.h"
 #include "rtw_devmem.h"
 #include "rtw_exp.h"
 #include "rtw_probe.h"
@@ -110,6 +111,7 @@ struct rtw_ctx {
     BoundsScratch *bounds = nullptr;     // buffers of rtw_ctx_colour_bounds (rtw_bounds.hip), created on its first call
     UpsampleScratch *upsample = nullptr; // buffers of rtw_ctx_upsample_filter (rtw_upsample.hip), created on its first call
     DisplayScratch *display = nullptr;   // buffers of rtw_ctx_luminance_histogram and rtw_ctx_display (rtw_display.hip), created on their first call
+    BloomScratch *bloom = nullptr;       // buffers and pyramid of rtw_ctx_bloom (rtw_bloom.hip), created on its first call
     TemporalScratch *temporal = nullptr; // buffers of rtw_ctx_temporal_accumulate (rtw_temporal.hip), created on its first call
     FilterScratch *filter = nullptr;     // buffers of rtw_ctx_bilateral_filter (rtw_filter.hip), created on its first call
     MotionMem motion_mem;                // buffers of rtw_ctx_mesh_instance_motion
@@ -542,6 +544,7 @@ void rtw_ctx_destroy(rtw_ctx *c) {
     bounds_scratch_free(c->bounds);
     upsample_scratch_free(c->upsample);
     display_scratch_free(c->display);
+    bloom_scratch_free(c->bloom);
     if (c->ev_mark) (void)hipEventDestroy(c->ev_mark);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1655,6 +1658,13 @@ int rtw_ctx_display(rtw_ctx *c, const float *in, uint32_t w, uint32_t h, const R
     if (!c) return RTW_E_INVALID;
     if (c->pend.active) return RTW_E_INVALID;
     return display_device(c->device, c->stream, &c->display, in, w, h, p, out, stats, &g_last_hip);
+}
+
+// Bloom (rtw_bloom.hip) likewise, on a scratch of its own.
+int rtw_ctx_bloom(rtw_ctx *c, const float *in, uint32_t w, uint32_t h, const RtwBloom *p, float *out, float *layer_out, RtwFilterStats *stats) {
+    if (!c) return RTW_E_INVALID;
+    if (c->pend.active) return RTW_E_INVALID;
+    return bloom_device(c->device, c->stream, &c->bloom, c->opt_atrous_layout, in, w, h, p, out, layer_out, stats, &g_last_hip);
 }
 
 // The device-math probe (rtw_probe.hip, rtw.h "device math, for tests") on this context's GPU and stream; the scene is not involved.
